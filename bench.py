@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the unidirectional path-tracing hot path on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full render of the workload BASELINE.json's metric is quoted on (configs[1]):
@@ -11,9 +11,15 @@ replicated, no data-path collective) and one RCCL gather brings the tile buffers
 de-interleaves them; that gather + de-interleave is inside the timed region.
 
 Rank 0 prints ONE JSON line. `value` is whole-job Mray/s (closest-hit + shadow traversals, all
-ranks) with the scene resident in HBM when the clock starts. Ray / box / triangle counts come from
-a counted, untimed pass of the identical (deterministic) workload, and the timed frame must equal
-the counted frame bit for bit (`frame_sha`; the run fails otherwise). `roofline` prices the
+ranks) with the scene resident in HBM when the clock starts; `ms_per_step` is the wall time of one
+timed step. Ray / box / triangle counts come from a counted, untimed pass of the identical
+(deterministic) workload, which is also the first warm-up step, and the timed frame must equal the
+counted frame bit for bit (`frame_sha`; the run fails otherwise). `--dump-outputs DIR` writes the
+frame of the last timed step (rank 0's assembled [H, W, 4] float32 radiance sums): see dump_frame().
+
+A plain run measures the headline and nothing else. `--full` adds the fields below (`roofline`,
+`secondary`, `projected_scaling`, `cpu_baseline`; `--no-secondary` / `--no-cpu-baseline` leave
+parts of them out). `roofline` prices the
 megakernel against the bound that binds it (tools/roofline.py): VALU issue slots for scenes that
 live in LDS (the headline), the L1's cache-line rate for scenes in HBM — both fractions are <= 1 by
 construction; SURVEY.md §8(d)'s algorithmic bytes are kept as the labelled field `algorithmic`.
@@ -110,8 +116,62 @@ def kernel_name(flags, variant):
     return "pt::megakernel<0, false, false, %s, %s, %s, false, 1, %s>" % (_tf(flags["onchip"]), _tf(flags["refill"]), _tf(flags["flat"]), lean)
 
 
-def measure(ctx, workload, spp_override, steps, warmup, opts, variant, culling):
-    """One workload: scene into HBM, counted pass, `steps` timed passes, frame check. Returns the result dict on rank 0."""
+def roofline_block(ctx, workload, spp, variant, flags, cnt, gnodes, own_tiles, kernel_ms):
+    """--full: the `roofline` field of one workload's line (see the module docstring)."""
+    world = ctx["world"]
+    kname = kernel_name(flags, variant)
+    # roofline of the dominant kernel (the megakernel) on THIS rank: what it did / its duration
+    own_bytes = RF.alg_bytes(cnt, own_tiles * 64)
+    entry = RF.find_entry(RF.load_inputs(), workload, spp, kname) if (world == 1 and variant == "megakernel") else None
+    # counters of a PMC pass describe the code they were measured on: use them only if the library being timed holds that very code
+    stale = entry is not None and not RF.profile_is_current(entry, ctx["code_hashes"])
+    if stale:
+        entry = None
+    if variant != "megakernel":
+        rf = {"bound": "l1_lines", "achieved": None, "peak": RF.PEAK_L1_LINES / 1e9, "unit": "Gline-access/s", "frac": None,
+              "note": "A/B variant: ~200 launches per frame, no single dominant launch; see value / ms_per_step against the megakernel's"}
+    elif not flags["onchip"]:
+        busy = RF.ta_busy(entry)                                 # from the committed PMC pass of this workload: how busy the unit behind this bound was
+        rf = {"ta_busy_frac": busy}                              # leads the block: the independent evidence that the unit behind the bound is saturated
+        rf.update(RF.l1_roofline(gnodes, cnt["tri_tests"], kernel_ms))
+        rf["peak_source"] = "micro-benchmark tools/ta_rate/quad_fetch.hip (one cache-line access per CU per clock), not a figure of MI355X_MICROARCH.md"
+        rf["global_node_fetches_per_launch"] = gnodes
+        rf["global_tri_tests_per_launch"] = cnt["tri_tests"]
+        if entry is not None:
+            rf["profile"] = {"file": "profiles/roofline_inputs.json", "workload": workload, "spp": spp, "source": entry.get("source")}
+    else:
+        rf = RF.valu_roofline(entry, kernel_ms)
+        if rf is None:                                           # no PMC pass of this exact workload / kernel / code is committed
+            rf = {"bound": "valu", "achieved": None, "peak": RF.PEAK_VALU / 1e9, "unit": "Gwave-instr/s", "frac": None}
+        else:
+            rf["profile"] = {"file": "profiles/roofline_inputs.json", "workload": workload, "spp": spp, "source": entry.get("source")}
+    if stale:
+        rf["stale_profile"] = True                               # a PMC pass exists, but of other code: re-run tools/profile_round.sh
+    issue = RF.issue_block(entry, 8 if "hbm_simple" in kname else (6 if "megakernel_hbm" in kname else 4)) if variant == "megakernel" else None
+    if issue is not None:
+        rf["issue"] = issue                                      # every instruction class against the CU's measured issue ceiling (DESIGN.md §6, round 3)
+    rf["code_sha256"] = ctx["code_hashes"].get(kname)
+    rf["traffic"] = RF.traffic_bytes(entry)
+    rf["kernel"] = kname
+    rf["kernel_ms"] = kernel_ms
+    rf["algorithmic"] = RF.algorithmic(own_bytes, kernel_ms)
+    return rf
+
+
+def dump_frame(f, dump_dir):
+    """The frame as finite arrays, losslessly. The path reproduces the reference's NaN pixels, so a radiance sum
+    may be NaN or +-Inf: DIR/frame.npy is the frame with those values set to 0, and DIR/frame_nonfinite.npy ([H, W] float32)
+    codes each pixel's non-finite channels as sum over channels c of k * 4**c, k = 1 NaN, 2 +Inf, 3 -Inf (0: all finite)."""
+    kind = np.isnan(f) * 1 + np.isposinf(f) * 2 + np.isneginf(f) * 3
+    code = (kind * 4 ** np.arange(f.shape[-1])).sum(axis=-1).astype(np.float32)
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "frame.npy"), np.where(kind == 0, f, np.float32(0)).astype(np.float32))
+    np.save(os.path.join(dump_dir, "frame_nonfinite.npy"), code)
+
+
+def measure(ctx, workload, spp_override, steps, warmup, opts, variant, culling, dump_dir=None):
+    """One workload: scene into HBM, counted pass, `steps` timed passes, frame check, the last frame into dump_dir (dump_frame)
+    if given. Returns the result dict on rank 0."""
     from cudapathtracer_amd import api, scenes
     from cudapathtracer_amd import distributed as D
     rank, world, red_dev, share = ctx["rank"], ctx["world"], ctx["red_dev"], ctx["share"]
@@ -161,7 +221,7 @@ def measure(ctx, workload, spp_override, steps, warmup, opts, variant, culling):
     scene.last_kernel_ms()                                       # raises if the counted launch did not complete its frame
     sha_counted = frame_sha()
     cnt = scene.counters()
-    gnodes = scene.global_node_fetches() if variant == "megakernel" else 0
+    gnodes = scene.global_node_fetches() if (ctx["full"] and variant == "megakernel") else 0
     cvec = torch.tensor([cnt[k] for k in api.COUNTER_KEYS], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(cvec)
@@ -188,46 +248,12 @@ def measure(ctx, workload, spp_override, steps, warmup, opts, variant, culling):
         return None, None, None
     if sha_timed != sha_counted:
         raise SystemExit("bench.py: the timed frame differs from the counted frame (%s vs %s) on %s" % (sha_timed, sha_counted, workload))
+    if dump_dir:
+        dump_frame(frame.cpu().numpy(), dump_dir)
 
     flags = scene.flags()
     rays = total["rays_closest"] + total["rays_shadow"]
     n_px = w * h
-    kname = kernel_name(flags, variant)
-    # roofline of the dominant kernel (the megakernel) on THIS rank: what it did / its duration
-    own_bytes = RF.alg_bytes(cnt, tr.count * 64)
-    entry = RF.find_entry(RF.load_inputs(), workload, spp, kname) if (world == 1 and variant == "megakernel") else None
-    # counters of a PMC pass describe the code they were measured on: use them only if the library being timed holds that very code
-    stale = entry is not None and not RF.profile_is_current(entry, ctx["code_hashes"])
-    if stale:
-        entry = None
-    if variant != "megakernel":
-        rf = {"bound": "l1_lines", "achieved": None, "peak": RF.PEAK_L1_LINES / 1e9, "unit": "Gline-access/s", "frac": None,
-              "note": "A/B variant: ~200 launches per frame, no single dominant launch; see value / ms_per_step against the megakernel's"}
-    elif not flags["onchip"]:
-        busy = RF.ta_busy(entry)                                 # from the committed PMC pass of this workload: how busy the unit behind this bound was
-        rf = {"ta_busy_frac": busy}                              # leads the block: the independent evidence that the unit behind the bound is saturated
-        rf.update(RF.l1_roofline(gnodes, cnt["tri_tests"], kernel_ms))
-        rf["peak_source"] = "micro-benchmark tools/ta_rate/quad_fetch.hip (one cache-line access per CU per clock), not a figure of MI355X_MICROARCH.md"
-        rf["global_node_fetches_per_launch"] = gnodes
-        rf["global_tri_tests_per_launch"] = cnt["tri_tests"]
-        if entry is not None:
-            rf["profile"] = {"file": "profiles/roofline_inputs.json", "workload": workload, "spp": spp, "source": entry.get("source")}
-    else:
-        rf = RF.valu_roofline(entry, kernel_ms)
-        if rf is None:                                           # no PMC pass of this exact workload / kernel / code is committed
-            rf = {"bound": "valu", "achieved": None, "peak": RF.PEAK_VALU / 1e9, "unit": "Gwave-instr/s", "frac": None}
-        else:
-            rf["profile"] = {"file": "profiles/roofline_inputs.json", "workload": workload, "spp": spp, "source": entry.get("source")}
-    if stale:
-        rf["stale_profile"] = True                               # a PMC pass exists, but of other code: re-run tools/profile_round.sh
-    issue = RF.issue_block(entry, 8 if "hbm_simple" in kname else (6 if "megakernel_hbm" in kname else 4)) if variant == "megakernel" else None
-    if issue is not None:
-        rf["issue"] = issue                                      # every instruction class against the CU's measured issue ceiling
-    rf["code_sha256"] = ctx["code_hashes"].get(kname)
-    rf["traffic"] = RF.traffic_bytes(entry)
-    rf["kernel"] = kname
-    rf["kernel_ms"] = kernel_ms
-    rf["algorithmic"] = RF.algorithmic(own_bytes, kernel_ms)
     out = {
         "metric": "Mray/s", "value": rays * steps / elapsed / 1e6, "unit": "Mray/s",
         "msample_per_s": n_px * spp * steps / elapsed / 1e6,
@@ -240,8 +266,9 @@ def measure(ctx, workload, spp_override, steps, warmup, opts, variant, culling):
                    "sharding": ("interleaved 8x8 tiles, 1 gather" + (" [REHEARSAL: all ranks share cuda:0, gloo]" if share else "")) if world > 1 else "none",
                    "rays_per_step": rays, "box_tests_per_step": total["box_tests"], "tri_tests_per_step": total["tri_tests"]},
         "frame_sha": sha_timed, "frame_equals_counted_frame": True,
-        "roofline": rf,
     }
+    if ctx["full"]:
+        out["roofline"] = roofline_block(ctx, workload, spp, variant, flags, cnt, gnodes, tr.count, kernel_ms)
     if ctx.get("project_shares") and world == 1 and variant == "megakernel":
         # what N GPUs could reach on this frame before the gather: kernel time of the full frame / kernel time of rank 0's 1/N share
         proj = {}
@@ -274,7 +301,14 @@ def main():
                     help="diagnostic: pt_set_option on the scene (kernel selection / scheduling A/B, include/pt_api.h); the JSON lists them")
     ap.add_argument("--culling", action="store_true",
                     help="diagnostic: opt-in box culling (pt_set_culling) - NOT the reference's visiting set, never the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step as DIR/frame.npy (float32 [H, W, 4], rank 0; non-finite values "
+                         "set to 0 and coded per pixel in DIR/frame_nonfinite.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline block, the secondary workloads, the share projections and the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -299,14 +333,15 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
 
     from cudapathtracer_amd import api
-    ctx = {"rank": rank, "world": world, "red_dev": red_dev, "share": share, "code_hashes": RF.kernel_code_hashes(api.LIB_PATH)}
+    ctx = {"rank": rank, "world": world, "red_dev": red_dev, "share": share, "full": args.full,
+           "code_hashes": RF.kernel_code_hashes(api.LIB_PATH) if args.full else {}}
     opts = api.parse_options(args.opt)
-    ctx["project_shares"] = world == 1 and not args.opt and not args.culling and not args.no_secondary
-    out, sinfo, info = measure(ctx, args.workload, args.spp, args.steps, args.warmup, opts, args.variant, args.culling)
+    ctx["project_shares"] = args.full and world == 1 and not args.opt and not args.culling and not args.no_secondary
+    out, sinfo, info = measure(ctx, args.workload, args.spp, args.steps, args.warmup, opts, args.variant, args.culling, args.dump_outputs)
     ctx["project_shares"] = False
 
     plain = world == 1 and not args.spp and not args.opt and not args.culling and args.variant == "megakernel"
-    if rank == 0 and plain and not args.no_secondary and args.workload == "cornell_1920x1080_1024spp_depth8_mis":
+    if rank == 0 and args.full and plain and not args.no_secondary and args.workload == "cornell_1920x1080_1024spp_depth8_mis":
         # Driver-visible numbers beyond the headline, one counted + one timed step each, labelled: the kernel that serves
         # scenes in HBM (BASELINE C3 at its full 1024 spp; the C4 / C5 scene at 32 of its 4096 spp, depth 16), the GENERAL
         # bounce (material dispatch, medium stack, dielectric / GGX / mirror arms) on an LDS-resident scene at the headline's
@@ -319,7 +354,7 @@ def main():
             sec.append({k: r[k] for k in ("value", "unit", "msample_per_s", "steps", "ms_per_step", "config", "frame_sha", "frame_equals_counted_frame", "roofline")})
         out["secondary"] = sec
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sinfo["config"], info)
         print(json.dumps(out), flush=True)
     if world > 1:

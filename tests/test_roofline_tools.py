@@ -108,7 +108,7 @@ def test_every_committed_build_of_the_round_rendered_the_same_full_frames():
 
 def test_rocprof_average_of_the_headline_kernel_agrees_with_the_bench_line():
     """profiles/<tag>_kernel_stats_headline.csv: rocprofv3 --kernel-trace --stats of `bench.py --no-secondary` (the headline's kernel
-    launched on whole frames only — the default command also launches it on 1/2, 1/4, 1/8 of the tiles for `projected_scaling`, which
+    launched on whole frames only — the `--full` command also launches it on 1/2, 1/4, 1/8 of the tiles for `projected_scaling`, which
     pulls that summary's AVERAGE away from a frame's duration; its MAX is the frame). Both must agree with the line's kernel_ms."""
     import csv
     bench = _bench_files()[-1]

@@ -31,14 +31,14 @@ run_pmc blob82k_1920x1080_1024spp_depth8_mis 1024 blob "TA_TA_BUSY_sum" "TCP_GAT
 run_pmc cornell_mixed_1920x1080_1024spp_depth8_mis 1024 cornell_mixed                                       # the general bounce, LDS-resident (VALU roofline)
 run_pmc blob82k_glass_1920x1080_1024spp_depth8_mis 128 blob_glass_spp128 "TA_TA_BUSY_sum" "TCP_GATE_EN1_sum"  # the general bounce, scene in HBM
 cp profiles/roofline_inputs.json $out/roofline_inputs.json
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$out/stats -- python3 $OLDPWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OLDPWD/$out/stats.log 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$out/stats -- python3 $OLDPWD/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $OLDPWD/$out/stats.log 2>&1 )
 # ... and of the headline alone (no secondaries, no share projections: those launch the headline's kernel on 1/2, 1/4, 1/8 of the tiles
 # and would pull its AVERAGE away from a frame's duration): this is the summary whose average must agree with bench.py's kernel_ms
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$out/stats_headline -- python3 $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $OLDPWD/$out/stats_headline.log 2>&1 )
-python bench.py --steps 5 --warmup 2 > $out/bench.json 2> $out/bench.err
+python bench.py --steps 5 --warmup 2 --full > $out/bench.json 2> $out/bench.err
 python tools/roofline.py check $out/bench.json
 tail -c 400 $out/bench.json
 if [ "$2" = "fullspp" ]; then      # BASELINE configs[3] at its own 4096 spp on one GPU (~4 min: a counted and a timed frame)
-  python bench.py --workload atrium262k_1920x1080_4096spp_depth16_mis --steps 1 --warmup 1 --no-cpu-baseline > $out/bench_atrium262k_fullspp.json 2> $out/bench_atrium262k_fullspp.err
+  python bench.py --workload atrium262k_1920x1080_4096spp_depth16_mis --steps 1 --warmup 1 --full --no-cpu-baseline > $out/bench_atrium262k_fullspp.json 2> $out/bench_atrium262k_fullspp.err
   tail -c 300 $out/bench_atrium262k_fullspp.json
 fi
