@@ -69,6 +69,10 @@ class TileRange(C.Structure):
     _fields_ = [("first", C.c_int32), ("stride", C.c_int32), ("count", C.c_int32)]
 
 
+class DenoiseParams(C.Structure):    # pt_denoise_params
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p)      # pt_progress_fn
 
 
@@ -151,6 +155,12 @@ def lib():
     L.novum_save_csv_mono.argtypes = [C.c_char_p, vp, i32, i32, i32]
     L.pt_launch_progressive.argtypes = [i32, i32, Camera, vp, i32, i32, i32, i32, vp, i32, PROGRESS_FN, vp]
     L.novum_save_bmp.argtypes = [C.c_char_p, vp, i32, i32, i32]
+    L.pt_render_aovs.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, u64, vp, vp]
+    L.pt_render_aovs_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, u64, vp, vp, vp]
+    L.pt_denoise_defaults.restype = None; L.pt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
+    L.pt_denoise_workspace_bytes.restype = C.c_size_t; L.pt_denoise_workspace_bytes.argtypes = [i32, i32]
+    L.pt_denoise.argtypes = [i32, i32, vp, i32, vp, vp, C.POINTER(DenoiseParams), vp]
+    L.pt_denoise_device.argtypes = [i32, i32, vp, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp]
     _lib = L
     return L
 
@@ -396,6 +406,19 @@ class Scene:
                                           d_tile_ptr, int(count_work), stream or None)
         _check(rc, "pt_render_tiles_device")
 
+    def render_aovs(self, camera, w, h, aov_spp=1, seed=SEED):
+        """pt_render_aovs: first-hit feature buffers, returns (albedo, normal_depth) as [h,w,4] float32 (y = 0 the bottom row).
+        albedo.w is the coverage (hits / aov_spp), normal_depth.w the mean hit distance."""
+        alb = np.zeros((h, w, 4), np.float32)
+        nd = np.zeros((h, w, 4), np.float32)
+        _check(lib().pt_render_aovs(self.h, C.byref(camera), w, h, aov_spp, seed, _p(alb), _p(nd)), "pt_render_aovs")
+        return alb, nd
+
+    def render_aovs_device(self, camera, w, h, d_albedo_ptr, d_normal_depth_ptr, aov_spp=1, seed=SEED, stream=0):
+        """pt_render_aovs_device: the same into device buffers of w*h float4 each, asynchronous on `stream`."""
+        _check(lib().pt_render_aovs_device(self.h, C.byref(camera), w, h, aov_spp, seed, d_albedo_ptr, d_normal_depth_ptr, stream or None),
+               "pt_render_aovs_device")
+
     def launch_unidirectional(self, max_depth, camera, num_sample, use_mis, w, h, d_colors_ptr):
         _check(lib().pt_launch_unidirectional(max_depth, camera, self.h, num_sample, int(use_mis), w, h, d_colors_ptr), "pt_launch_unidirectional")
 
@@ -574,6 +597,55 @@ def parse_options(pairs):
                 k, _, v = item.partition("=")
                 out[k.strip()] = int(v)
     return out
+
+
+def denoise_defaults():
+    """pt_denoise_defaults as a dict: iterations, sigma_color, sigma_normal, sigma_depth."""
+    p = DenoiseParams()
+    lib().pt_denoise_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in DenoiseParams._fields_}
+
+
+def _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth):
+    p = DenoiseParams()
+    lib().pt_denoise_defaults(C.byref(p))
+    for f, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+        if v is not None:
+            setattr(p, f, v)
+    return p
+
+
+def denoise_workspace_bytes(w, h):
+    return int(lib().pt_denoise_workspace_bytes(w, h))
+
+
+def denoise(rgba_sum, spp, albedo, normal_depth, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, out=None):
+    """pt_denoise (host, blocking): the a-trous filter guided by render_aovs' buffers. rgba_sum is the radiance SUM of
+    `spp` samples as pt_render leaves it ([h,w,4] float32); returns the same units. A None parameter takes the library
+    default (denoise_defaults()). `out` may be rgba_sum itself."""
+    arrs = []
+    for name, a in (("rgba_sum", rgba_sum), ("albedo", albedo), ("normal_depth", normal_depth)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or a.shape[2] != 4:
+            raise PtError("denoise: %s must be a float32 [h, w, 4] array" % name)
+        arrs.append(np.ascontiguousarray(a))
+    if arrs[1].shape != arrs[0].shape or arrs[2].shape != arrs[0].shape:
+        raise PtError("denoise: shapes differ: %s, %s, %s" % tuple(a.shape for a in arrs))
+    h, w = arrs[0].shape[:2]
+    res = np.empty_like(arrs[0]) if out is None else out
+    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == arrs[0].shape and res.flags.c_contiguous):
+        raise PtError("denoise: out must be a C-contiguous float32 array of shape %s" % (arrs[0].shape,))
+    p = _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise(w, h, _p(arrs[0]), int(spp), _p(arrs[1]), _p(arrs[2]), C.byref(p), _p(res)), "pt_denoise")
+    return res
+
+
+def denoise_device(w, h, d_rgba_sum_ptr, spp, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr, d_out_ptr, iterations=None,
+                   sigma_color=None, sigma_normal=None, sigma_depth=None, stream=0):
+    """pt_denoise_device: device buffers of w*h float4 (e.g. tensor.data_ptr()) and a workspace of
+    denoise_workspace_bytes(w, h) bytes; asynchronous on `stream`. d_out_ptr may equal d_rgba_sum_ptr."""
+    p = _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_device(w, h, d_rgba_sum_ptr, int(spp), d_albedo_ptr, d_normal_depth_ptr, C.byref(p), d_workspace_ptr, d_out_ptr,
+                                   stream or None), "pt_denoise_device")
 
 
 def untile_device(w, h, d_tiles_ptr, d_colors_ptr, tiles=None, stream=0):

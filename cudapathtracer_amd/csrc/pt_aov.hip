@@ -1,0 +1,97 @@
+// pt_aov.hip — first-hit feature buffers (albedo, normal, depth) for denoisers (pt_render_aovs, include/pt_api.h).
+//
+// One wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the tiles. Ray k of pixel (x, y) is
+// camera_ray drawn from a FRESH XORWOW stream keyed (seed + k, y*w+x) — the seeding of rng_init_kernel, into registers
+// — then the non-counting trace_closest (max_t 999999, as pt_probe_trace_closest) and resolve_hit, so t, the normal and
+// the material are those of pt_probe_trace_closest. The albedo is material_inputs' (the texture sample for textured
+// materials). First hit only: no specular chain is followed. The pass writes neither the scene's per-pixel RNG states nor
+// its tile accumulator nor its counters, so it may run between the chunks of a progressive render.
+#include "pt_path.h"
+#include "pt_params.h"
+
+namespace pt {
+
+// rng_init_kernel's per-lane body: stream `idx` of XORWOW(seed), via the 2^67-step jump matrices (row-image form).
+PT_DEV Rng aov_stream(const uint32_t* __restrict__ jump, unsigned long long seed, uint32_t idx) {
+    uint32_t s0 = (uint32_t)seed ^ 0xaad26b49u, s1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
+    uint32_t t0 = 1099087573u * s0, t1 = 2591861531u * s1;
+    uint32_t v[5] = {123456789u + t0, 362436069u ^ t0, 521288629u + t1, 88675123u ^ t1, 5783321u + t0};
+    uint32_t d = 6615241u + t1 + t0;
+    for (int k = 0; k < 32; k++) {
+        if (!__ballot((idx >> k) & 1u)) continue;
+        if ((idx >> k) & 1u) {
+            const uint32_t* M = jump + (size_t)k * 800;
+            uint32_t r[5] = {0, 0, 0, 0, 0};
+            for (int i = 0; i < 5; i++) {
+                uint32_t word = v[i];
+#pragma unroll 4          // fully unrolled, the 800 row loads take 256 VGPRs (1 wave per SIMD); by 4: 76 VGPRs, 6 waves
+                for (int j = 0; j < 32; j++) {
+                    uint32_t m = 0u - ((word >> j) & 1u);
+                    const uint32_t* row = M + (i * 32 + j) * 5;
+                    r[0] ^= row[0] & m; r[1] ^= row[1] & m; r[2] ^= row[2] & m; r[3] ^= row[3] & m; r[4] ^= row[4] & m;
+                }
+            }
+            for (int i = 0; i < 5; i++) v[i] = r[i];
+        }
+    }
+    Rng rng = {v[0], v[1], v[2], v[3], v[4], d};
+    return rng;
+}
+
+// spill: (gridDim.x * 4) waves x S.stackSpill entries x 64 lanes, the lane-interleaved layout of Stack.
+__global__ void __launch_bounds__(256) aov_kernel(DeviceScene S, CamK cam, const uint32_t* __restrict__ jump, unsigned long long seed,
+                                                  int w, int h, int tilesX, int nTiles, int aovSpp, float4* __restrict__ albedo,
+                                                  float4* __restrict__ normalDepth, int32_t* spill) {
+    __shared__ int32_t ldsStack[4][kStackLds][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + wave;
+    Stack<kStackLds> st; st.lds = (lds_i32*)&ldsStack[wave][0][0] + lane; st.sp = 0;
+    st.spill = spill ? spill + (size_t)gw * S.stackSpill * 64 + lane : nullptr;
+    SceneCache C; C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
+    Ctr c = {};
+    for (int tile = gw; tile < nTiles; tile += gridDim.x * 4) {
+        const int x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
+        const bool inside = x < w && y < h;
+        const uint32_t idx = inside ? (uint32_t)(y * w + x) : 0u;
+        V3 sa = v3(0.0f), sn = v3(0.0f);
+        float st_ = 0.0f;
+        int hits = 0;
+        for (int k = 0; k < aovSpp; k++) {
+            Rng rng = aov_stream(jump, seed + (unsigned long long)k, idx);      // (every lane: the seeding ballots per bit)
+            if (!inside) continue;
+            V3 o, d;
+            camera_ray<false>(cam, rng, x, y, o, d, c);
+            Hit hit;
+            trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+            if (hit.tri < 0) continue;
+            HitInfo hi; resolve_hit(S, hit, o, d, hi);
+            V3 a; float trans;
+            material_inputs(S.mats[hi.material], S.textures, hi.uvx, hi.uvy, true, a, trans);
+            // sums in k order; the first hit is stored, not added to 0, so that a -0 component survives (aov_spp = 1 is the hit itself)
+            if (hits == 0) { sa = a; sn = hi.normal; st_ = hit.t; }
+            else { sa = sa + a; sn = sn + hi.normal; st_ = st_ + hit.t; }
+            hits++;
+        }
+        if (!inside) continue;
+        float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
+        if (hits > 0) {
+            const float n = (float)hits;
+            oa = make_float4(sa.x / n, sa.y / n, sa.z / n, n / (float)aovSpp);
+            on = make_float4(sn.x / n, sn.y / n, sn.z / n, st_ / n);
+        }
+        albedo[idx] = oa;
+        normalDepth[idx] = on;
+    }
+}
+
+// Workgroups of the AOV pass: persistent, as many as are resident at once (76 VGPRs: 6 waves per SIMD = 6 workgroups per CU).
+int aov_blocks(int nTiles, int numCU) { return std::max(1, std::min((nTiles + 3) / 4, numCU * 6)); }
+
+hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
+                      int blocks, float4* albedo, float4* normalDepth, int32_t* spill, hipStream_t stream) {
+    const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
+    hipLaunchKernelGGL(aov_kernel, dim3(blocks), dim3(256), 0, stream, S, cam, jump, seed, w, h, tilesX, nTiles, aovSpp, albedo, normalDepth, spill);
+    return hipGetLastError();
+}
+
+}  // namespace pt

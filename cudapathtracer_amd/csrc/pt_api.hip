@@ -62,6 +62,7 @@ struct pt_scene {
     int nLeaves = 0;                                  // FLAT scenes: the leaf table (pt_trace.h: visited(leaf) == slab(leaf's own box))
     DevBuf rng, spill, tilebuf, colors, pixcnt, queue, left; // work buffers, grown on demand
     DevBuf wfState, wfCtl, wfCtr, wfSpill;            // wavefront variant
+    DevBuf aovSpill, aovOut;                          // pt_render_aovs: its own traversal spill area / host-form staging
     int variant = 0;                                  // 0 megakernel, 1 wavefront (pt_set_variant)
     int numCU = 256;
     DeviceScene ds{};
@@ -142,7 +143,8 @@ int pt_device_count(void) {
 void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
     DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves, &s->wnodes, &s->qnodes, &s->leafBox, &s->mids,
-                     &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill};
+                     &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
+                     &s->aovSpill, &s->aovOut};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1045,6 +1047,58 @@ int pt_render(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int maxD
 int pt_render_counted(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int maxDepth, int integrator, int useMIS, uint64_t seed,
                       const pt_tile_range* tiles, float* out, uint32_t* outCounters) {
     return render_host(s, cam, w, h, spp, maxDepth, integrator, useMIS, seed, tiles, out, outCounters, true);
+}
+
+}  // extern "C"
+
+namespace pt {      // pt_aov.hip
+int aov_blocks(int nTiles, int numCU);
+hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
+                      int blocks, float4* albedo, float4* normalDepth, int32_t* spill, hipStream_t stream);
+}
+
+// Argument checks of the AOV pass, all before the first HIP call (the device check comes last).
+static int check_aov_args(pt_scene* s, const pt_camera* cam, int w, int h, int aovSpp, const void* a, const void* nd) {
+    if (w <= 0 || h <= 0) return fail(-1, "pt_render_aovs: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return fail(-1, "pt_render_aovs: image of %d x %d pixels is too large", w, h);
+    if (aovSpp <= 0) return fail(-1, "pt_render_aovs: aov_spp %d must be positive", aovSpp);
+    if (!cam) return fail(-1, "pt_render_aovs: null camera");
+    if (cam->w != w || cam->h != h) return fail(-1, "pt_render_aovs: the camera is %d x %d, the image %d x %d", cam->w, cam->h, w, h);
+    if (!a || !nd) return fail(-1, "pt_render_aovs: null output buffer");
+    if (!s) return fail(-1, "pt_render_aovs: null scene");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->device) return fail(-1, "scene lives on HIP device %d but the current device is %d", s->device, dev);
+    return 0;
+}
+
+static int render_aovs(pt_scene* s, const pt_camera* cam, int w, int h, int aovSpp, uint64_t seed, void* dA, void* dN, hipStream_t stream) {
+    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = aov_blocks(nTiles, s->numCU);
+    int32_t* spill = nullptr;
+    if (s->ds.stackSpill > 0) {          // its own area: a render in flight on this scene keeps s->spill
+        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
+        spill = (int32_t*)s->aovSpill.p;
+    }
+    HIP_OK(launch_aov(s->ds, cam_to_kernel(*cam), (const uint32_t*)s->jump.p, seed, w, h, aovSpp, blocks, (float4*)dA, (float4*)dN, spill, stream));
+    return 0;
+}
+
+extern "C" {
+
+int pt_render_aovs_device(pt_scene* s, const pt_camera* cam, int w, int h, int aov_spp, uint64_t seed, void* d_albedo, void* d_normal_depth,
+                          void* stream) {
+    if (int r = check_aov_args(s, cam, w, h, aov_spp, d_albedo, d_normal_depth)) return r;
+    return render_aovs(s, cam, w, h, aov_spp, seed, d_albedo, d_normal_depth, (hipStream_t)stream);
+}
+
+int pt_render_aovs(pt_scene* s, const pt_camera* cam, int w, int h, int aov_spp, uint64_t seed, float* out_albedo, float* out_normal_depth) {
+    if (int r = check_aov_args(s, cam, w, h, aov_spp, out_albedo, out_normal_depth)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    if (int r = s->aovOut.ensure(2 * bytes)) return r;
+    char* d = (char*)s->aovOut.p;
+    if (int r = render_aovs(s, cam, w, h, aov_spp, seed, d, d + bytes, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int pt_has_experimental(void) {

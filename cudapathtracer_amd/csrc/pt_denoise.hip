@@ -1,0 +1,249 @@
+// pt_denoise.hip — edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on albedo-demodulated colour, guided by
+// the first-hit feature buffers of pt_render_aovs (include/pt_api.h states the arithmetic; tests/denoise_ref.py restates it
+// in numpy). Opt-in post-process: it is not part of the reference's image.
+//
+//   denoise_prepare_kernel   m = S / spp; pass-through flag; e = m / a (a = albedo where >= 0.01, else 1); the normalised mean
+//                            normal and depth; per-workgroup luminance partial sums (fixed order: reproducible)
+//   denoise_reduce_kernel    one workgroup: the mean luminance L of e over the filtered pixels
+//   denoise_iter_kernel      one launch per step s = 2^i: the 5x5 B3-spline taps at stride s, weighted by colour, normal, depth
+//   denoise_finish_kernel    out = spp * a * e, or S itself for pass-through pixels
+//
+// Workspace (pt_denoise_workspace_bytes): e ping-pong (2 x w*h float4: rgb, w = 1 filtered / 0 pass-through), the normal-depth
+// guide (w*h float4: unit normal or 0, depth), the partial sums (one float2 per 256 pixels) and the result of the reduction.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/pt_api.h"
+
+extern "C" int pt_fail_(int code, const char* msg);
+
+namespace pt {
+
+constexpr int kDnBlock = 256;              // prepare / reduce / finish: one pixel per thread
+constexpr int kDnMaxIterations = 16;
+
+struct DnLayout {
+    size_t n, e0, e1, guide, partials, lum, total;
+    int nParts;
+};
+static DnLayout dn_layout(int w, int h) {
+    DnLayout L;
+    L.n = (size_t)w * h;
+    L.nParts = (int)((L.n + kDnBlock - 1) / kDnBlock);
+    L.e0 = 0;
+    L.e1 = L.e0 + L.n * 16;
+    L.guide = L.e1 + L.n * 16;
+    L.partials = L.guide + L.n * 16;
+    L.lum = L.partials + (((size_t)L.nParts * 8 + 15) & ~(size_t)15);
+    L.total = L.lum + 16;
+    return L;
+}
+
+__device__ inline bool finite3(float4 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
+__device__ inline float demod_albedo(float a) { return a >= 0.01f ? a : 1.0f; }
+
+__global__ void __launch_bounds__(kDnBlock) denoise_prepare_kernel(int n, const float4* __restrict__ sum, float spp, const float4* __restrict__ albedo,
+                                                                   const float4* __restrict__ nd, float4* __restrict__ e, float4* __restrict__ guide,
+                                                                   float2* __restrict__ partials) {
+    __shared__ float sLum[kDnBlock], sCnt[kDnBlock];
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    float lum = 0.0f, cnt = 0.0f;
+    if (i < n) {
+        const float4 s = sum[i], a = albedo[i], g = nd[i];
+        const float4 m = make_float4(s.x / spp, s.y / spp, s.z / spp, s.w / spp);
+        const bool filtered = a.w > 0.0f && finite3(m);
+        float4 ev = make_float4(m.x / demod_albedo(a.x), m.y / demod_albedo(a.y), m.z / demod_albedo(a.z), filtered ? 1.0f : 0.0f);
+        e[i] = ev;
+        const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+        guide[i] = len > 0.0f ? make_float4(g.x / len, g.y / len, g.z / len, g.w) : make_float4(0.0f, 0.0f, 0.0f, g.w);
+        if (filtered) { lum = 0.2126f * ev.x + 0.7152f * ev.y + 0.0722f * ev.z; cnt = 1.0f; }
+    }
+    sLum[threadIdx.x] = lum; sCnt[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int k = kDnBlock / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) { sLum[threadIdx.x] += sLum[threadIdx.x + k]; sCnt[threadIdx.x] += sCnt[threadIdx.x + k]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = make_float2(sLum[0], sCnt[0]);
+}
+
+// One workgroup; every thread sums a fixed stride of the partials, then a fixed tree: the same L on every run.
+__global__ void __launch_bounds__(kDnBlock) denoise_reduce_kernel(int nParts, const float2* __restrict__ partials, float4* __restrict__ lum) {
+    __shared__ double sLum[kDnBlock], sCnt[kDnBlock];
+    double l = 0.0, c = 0.0;
+    for (int k = threadIdx.x; k < nParts; k += kDnBlock) { l += partials[k].x; c += partials[k].y; }
+    sLum[threadIdx.x] = l; sCnt[threadIdx.x] = c;
+    __syncthreads();
+    for (int k = kDnBlock / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) { sLum[threadIdx.x] += sLum[threadIdx.x + k]; sCnt[threadIdx.x] += sCnt[threadIdx.x + k]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) lum[0] = make_float4(sCnt[0] > 0.0 ? (float)(sLum[0] / sCnt[0]) : 0.0f, (float)sCnt[0], 0.0f, 0.0f);
+}
+
+// 16x16 pixels per workgroup as four 8x8 tiles, one per wave. Taps are plain cached float4 loads: at step s the 5x5 footprints
+// of neighbouring pixels share most of their lines.
+__global__ void __launch_bounds__(256) denoise_iter_kernel(int w, int h, int step, float colorScale, float sigmaNormal, float sigmaDepth,
+                                                           const float4* __restrict__ lum, const float4* __restrict__ eIn,
+                                                           const float4* __restrict__ guide, float4* __restrict__ eOut) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    const float4 ep = eIn[p];
+    if (ep.w == 0.0f) { eOut[p] = ep; return; }
+    const float4 gp = guide[p];
+    const bool normalP = gp.x != 0.0f || gp.y != 0.0f || gp.z != 0.0f;
+    const float L = lum[0].x;
+    // w_c = exp(-|de|^2 / (sigma_c^2 L^2 2^-i + 1e-20)), w_z = exp(-|dz| / (sigma_z z_p)), w_n = max(0, n.n')^sigma_n: one exp2 per tap
+    const float log2e = 1.4426950408889634f;
+    const float kc = log2e / (colorScale * L * L + 1e-20f), kz = log2e / (sigmaDepth * gp.w);
+    const float hk[3] = {0.375f, 0.25f, 0.0625f};
+    float sx = 0.140625f * ep.x, sy = 0.140625f * ep.y, sz = 0.140625f * ep.z, sw = 0.140625f;     // centre tap: h(0)^2
+    if (normalP) {
+        for (int dy = -2; dy <= 2; dy++) {
+            const int yq = y + dy * step;
+            if (yq < 0 || yq >= h) continue;
+            for (int dx = -2; dx <= 2; dx++) {
+                const int xq = x + dx * step;
+                if (xq < 0 || xq >= w || (dx == 0 && dy == 0)) continue;
+                const size_t q = (size_t)yq * w + xq;
+                const float4 eq = eIn[q];
+                if (eq.w == 0.0f) continue;
+                const float4 gq = guide[q];
+                if (gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f) continue;
+                const float cs = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+                float ln;
+                if (sigmaNormal == 0.0f) ln = 0.0f;
+                else if (cs > 0.0f) ln = sigmaNormal * __builtin_log2f(cs);
+                else continue;
+                const float dr = ep.x - eq.x, dg = ep.y - eq.y, db = ep.z - eq.z;
+                const float dc = dr * dr + dg * dg + db * db, dz = fabsf(gp.w - gq.w);
+                const float wt = (hk[dx < 0 ? -dx : dx] * hk[dy < 0 ? -dy : dy]) * __builtin_exp2f(ln - dc * kc - dz * kz);
+                sx += wt * eq.x; sy += wt * eq.y; sz += wt * eq.z; sw += wt;
+            }
+        }
+    }
+    eOut[p] = make_float4(sx / sw, sy / sw, sz / sw, 1.0f);
+}
+
+__global__ void __launch_bounds__(kDnBlock) denoise_finish_kernel(int n, const float4* sum, float spp, const float4* __restrict__ albedo,
+                                                                  const float4* __restrict__ e, float4* out) {
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 s = sum[i], ev = e[i];          // (out may alias sum: each thread reads its own pixel before it writes it)
+    if (ev.w == 0.0f) { out[i] = s; return; }
+    const float4 a = albedo[i];
+    out[i] = make_float4(spp * (demod_albedo(a.x) * ev.x), spp * (demod_albedo(a.y) * ev.y), spp * (demod_albedo(a.z) * ev.z), s.w);
+}
+
+static int dn_fail(int code, const char* fmt, int a = 0, int b = 0) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), fmt, a, b);
+    return pt_fail_(code, buf);
+}
+#define DN_HIP_OK(expr)                                                                                            \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) {                                                                                    \
+            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
+            return pt_fail_(-2, m_);                                                                               \
+        }                                                                                                          \
+    } while (0)
+
+static int check_denoise_args(int w, int h, const void* in, int spp, const void* albedo, const void* nd, const pt_denoise_params& P,
+                              const void* out) {
+    if (w <= 0 || h <= 0) return dn_fail(-1, "pt_denoise: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return dn_fail(-1, "pt_denoise: image of %d x %d pixels is too large", w, h);
+    if (spp <= 0) return dn_fail(-1, "pt_denoise: spp %d must be positive", spp);
+    if (!in || !albedo || !nd || !out) return dn_fail(-1, "pt_denoise: null buffer");
+    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return dn_fail(-1, "pt_denoise: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
+    if (!(P.sigma_color > 0.0f) || !std::isfinite(P.sigma_color)) return dn_fail(-1, "pt_denoise: sigma_color must be positive and finite");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return dn_fail(-1, "pt_denoise: sigma_normal must be >= 0 and finite");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return dn_fail(-1, "pt_denoise: sigma_depth must be positive and finite");
+    return 0;
+}
+
+static int denoise_launch(int w, int h, const float4* in, int spp, const float4* albedo, const float4* nd, const pt_denoise_params& P,
+                          char* ws, float4* out, hipStream_t stream) {
+    const DnLayout L = dn_layout(w, h);
+    float4* e[2] = {(float4*)(ws + L.e0), (float4*)(ws + L.e1)};
+    float4* guide = (float4*)(ws + L.guide);
+    float2* partials = (float2*)(ws + L.partials);
+    float4* lum = (float4*)(ws + L.lum);
+    const int n = (int)L.n;
+    const float fspp = (float)spp;
+    hipLaunchKernelGGL(denoise_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, nd, e[0], guide, partials);
+    DN_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
+    DN_HIP_OK(hipGetLastError());
+    const dim3 grid((w + 15) / 16, (h + 15) / 16);
+    for (int i = 0; i < P.iterations; i++) {
+        const float colorScale = P.sigma_color * P.sigma_color * std::ldexp(1.0f, -i);
+        hipLaunchKernelGGL(denoise_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, colorScale, P.sigma_normal, P.sigma_depth, lum,
+                           e[i & 1], guide, e[(i + 1) & 1]);
+        DN_HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(denoise_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
+    DN_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace pt
+
+using namespace pt;
+
+extern "C" {
+
+void pt_denoise_defaults(pt_denoise_params* out) {
+    if (!out) return;
+    out->iterations = 5;
+    out->sigma_color = 1.0f;
+    out->sigma_normal = 64.0f;
+    out->sigma_depth = 0.02f;
+}
+
+size_t pt_denoise_workspace_bytes(int w, int h) {
+    if (w <= 0 || h <= 0) return 0;
+    return dn_layout(w, h).total;
+}
+
+int pt_denoise_device(int w, int h, const void* d_rgba_sum, int spp, const void* d_albedo, const void* d_normal_depth,
+                      const pt_denoise_params* params, void* d_workspace, void* d_out, void* stream) {
+    pt_denoise_params P;
+    if (params) P = *params; else pt_denoise_defaults(&P);
+    if (int r = check_denoise_args(w, h, d_rgba_sum, spp, d_albedo, d_normal_depth, P, d_out)) return r;
+    if (!d_workspace) return pt_fail_(-1, "pt_denoise_device: null workspace");
+    return denoise_launch(w, h, (const float4*)d_rgba_sum, spp, (const float4*)d_albedo, (const float4*)d_normal_depth, P, (char*)d_workspace,
+                          (float4*)d_out, (hipStream_t)stream);
+}
+
+int pt_denoise(int w, int h, const float* rgba_sum, int spp, const float* albedo, const float* normal_depth, const pt_denoise_params* params,
+               float* out_rgba_sum) {
+    pt_denoise_params P;
+    if (params) P = *params; else pt_denoise_defaults(&P);
+    if (int r = check_denoise_args(w, h, rgba_sum, spp, albedo, normal_depth, P, out_rgba_sum)) return r;
+    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total;
+    char* d = nullptr;
+    DN_HIP_OK(hipMalloc(&d, ws + 3 * bytes));
+    char* dIn = d + ws;                      // in and out share one buffer (out may alias in)
+    char* dA = dIn + bytes;
+    char* dN = dA + bytes;
+    hipError_t e = hipMemcpy(dIn, rgba_sum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = dn_fail(-2, "pt_denoise: upload failed");
+    } else if ((r = denoise_launch(w, h, (const float4*)dIn, spp, (const float4*)dA, (const float4*)dN, P, d, (float4*)dIn, nullptr)) == 0) {
+        e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+}  // extern "C"

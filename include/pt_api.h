@@ -281,6 +281,53 @@ int pt_multi_render(pt_multi* m, const pt_camera* camera, int w, int h, int spp,
 int pt_render_multi(const pt_scene_desc* desc, int n_devices, const int* device_ids, const pt_camera* camera, int w, int h, int spp,
                     int max_depth, int integrator, int use_mis, uint64_t seed, float* out_rgba_sum, pt_multi_stats* stats);
 
+/* ---- feature buffers and denoiser (opt-in post-process; not part of the reference's image) ----------------------
+ * First-hit feature buffers, scan-line w*h float4 each, y = 0 the bottom row (as pt_render).
+ * out_albedo:       rgb = mean albedo over the rays that hit, w = coverage (hits / aov_spp; 0 = nothing hit)
+ * out_normal_depth: xyz = mean of resolve_hit's normal over the hits (NOT renormalised; it faces the camera ray),
+ *                   w = mean hit distance t
+ * Ray k (0 <= k < aov_spp) of pixel (x, y) is camera_ray drawn from a FRESH XORWOW stream keyed (seed + k, y*w + x).
+ * Ray 0 is therefore exactly the first camera ray of that pixel's beauty render with `seed`. The closest hit is the
+ * probe's (max_t 999999), the albedo what the bounce reads at that hit: the material's albedo, or the bilinear texture
+ * sample for textured materials, for every material type (emitters included). FIRST HIT ONLY: mirrors and glass report
+ * their own albedo; no specular chain is followed. Sums run in k order in f32, then one IEEE division by the hit count;
+ * a pixel with no hit is all zeros. The pass seeds its own streams and never touches the scene's per-pixel RNG states,
+ * tile accumulator or counters: it may run between the chunks of pt_launch_progressive. Arguments are checked before
+ * any HIP call (w, h, aov_spp > 0; camera->w / h equal to w / h; no NULL pointer). */
+int pt_render_aovs(pt_scene* scene, const pt_camera* camera, int w, int h, int aov_spp, uint64_t seed,
+                   float* out_albedo, float* out_normal_depth);                       /* host buffers, blocking */
+int pt_render_aovs_device(pt_scene* scene, const pt_camera* camera, int w, int h, int aov_spp, uint64_t seed,
+                          void* d_albedo, void* d_normal_depth, void* stream);       /* device buffers, async */
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on albedo-demodulated colour, guided by the buffers
+ * above. The contract, per pixel p (all buffers w*h float4):
+ *   m_p = S_p / spp. p PASSES THROUGH (output = S_p bit for bit, all four channels) if its coverage is 0 or any of m_p.rgb
+ *   is NaN / Inf (so novum_finalise still paints those); pass-through pixels are never taps.
+ *   a_p = albedo_p per channel where >= 0.01, else 1; e_p = m_p / a_p. L = mean luminance (0.2126, 0.7152, 0.0722) of e
+ *   over the filtered pixels. Iteration i (step s = 2^i): e'_p = sum_q w e_q / sum_q w over q = p + s (dx, dy),
+ *   dx, dy in -2..2, inside the image and not pass-through; w = h(dx) h(dy) w_c w_n w_z with h = (1, 4, 6, 4, 1) / 16,
+ *   w_c = exp(-|e_p - e_q|^2 / (sigma_color^2 L^2 2^-i + 1e-20)), w_n = max(0, n_p . n_q)^sigma_normal on the
+ *   normalised mean normals (0 if either normal is zero), w_z = exp(-|z_p - z_q| / (sigma_depth z_p)); the centre tap
+ *   weighs h(0)^2. Output: rgb = spp a_p e_p with the last iteration's e_p, w = S_p.w.
+ * Multi-GPU frames are denoised after the gather: the taps cross shard boundaries. */
+typedef struct pt_denoise_params {
+    int32_t iterations;          /* default 5: steps 1, 2, 4, 8, 16 (0..16) */
+    float sigma_color;           /* relative to the image's mean demodulated luminance (> 0) */
+    float sigma_normal;          /* exponent on the normals' cosine (>= 0) */
+    float sigma_depth;           /* relative depth difference (> 0) */
+                                 /* defaults 5, 1.0, 64, 0.02: DESIGN.md "Feature buffers and denoiser" */
+} pt_denoise_params;
+void   pt_denoise_defaults(pt_denoise_params* out);
+/* device workspace of pt_denoise_device: 3 * w*h float4 (two colour buffers, the guide) + 8 B per 256 pixels
+ * (rounded up to 16 B) + 16 B; 0 if w or h <= 0 */
+size_t pt_denoise_workspace_bytes(int w, int h);
+/* in: the radiance SUM of `spp` samples (what pt_render / the launchers leave). out: the same units, so novum_finalise /
+ * novum_save_bmp apply unchanged. out may alias in. params NULL = pt_denoise_defaults. */
+int pt_denoise(int w, int h, const float* rgba_sum, int spp, const float* albedo, const float* normal_depth,
+               const pt_denoise_params* params, float* out_rgba_sum);                                  /* host, blocking */
+int pt_denoise_device(int w, int h, const void* d_rgba_sum, int spp, const void* d_albedo, const void* d_normal_depth,
+                      const pt_denoise_params* params, void* d_workspace, void* d_out, void* stream);  /* async */
+
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
 int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* out_exp, float* out_rsqrt, float* out_pow5);
