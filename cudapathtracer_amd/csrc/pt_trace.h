@@ -776,9 +776,11 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 // that continues the path share ONE lockstep node walk (node fetch, child refs, loop control paid once for both), and
 // their triangle tests are dealt out over the wave together. A shadow ray needs no order at all when no triangle of the
 // scene is a MAT_LEAF (NOLEAF scenes: any hit below max_t occludes), the extension ray is resolved as in
-// trace_closest_flat. At most 64 internal nodes / triangles. Scratch: 24 x 64 words of the wave's stack area:
-//   entry v = lane (extension ray) or 64 + lane (shadow ray): o, d, max_t, triangle mask (9 fields x 128), exclusive
-//   prefix (128), the two u64 keys of the extension rays (2 x 128 words), the occlusion flags (64).
+// trace_closest_flat. At most 64 internal nodes / triangles. Scratch: 24 x 64 words of the wave's stack area, by SLOT — the
+// entries (a lane's extension ray, a lane's shadow ray) that have tests, extension rays first, in lane order:
+//   o, d, max_t, triangle mask (9 fields x 128 slots); 128 u64 minima, one per slot: the extension ray's (t, first index)
+//   key, or the shadow ray's occlusion word; 64 u64 minima (t, last index) of the extension slots. The slots' exclusive
+//   prefixes (128 words) live where the 128 minima go until the owner search has read them.
 template <int N>
 PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt,
                             bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
@@ -786,10 +788,10 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     const int lane = (int)(threadIdx.x & 63u);
     lds_i32* Wd = st.lds - lane;
-    // (the occlusion flags of the 64 shadow rays reuse the first half of the prefix field: the prefixes are only read by the owner
-    // search, which every lane of the wave has finished before the first test can set a flag — 24 x 256 B per wave instead of 25,
-    // which is what lets a fifth 4-wave workgroup fit a CU's 160 KB next to its copy of the Cornell scene)
-    constexpr int kPre = 9 * 128, kKeys = kPre + 128, kOcc = kPre;
+    // (the prefixes share the minima's words: every lane of the wave has finished the owner search before the minima are set —
+    // 24 x 256 B per wave instead of 25, which is what lets a fifth 4-wave workgroup fit a CU's 160 KB next to its copy of the
+    // Cornell scene)
+    constexpr int kKeyA = 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
     const V3 invE = inv3(ed), invS = inv3(sd);
     // 1. one lockstep node walk for both rays
     uint64_t tmE = 0ull, tmS = 0ull;
@@ -823,7 +825,7 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
             if (right >= 0) { visE |= eR ? bR : 0ull; visS |= sR ? bR : 0ull; } else { tmE |= eR ? bR : 0ull; tmS |= sR ? bR : 0ull; }
         }
     }
-    // 2. deal the tests of all 128 rays out: extension rays first (entries 0..63), then shadow rays (64..127)
+    // 2. deal the tests of all 128 rays out: extension rays first, then shadow rays, each ray's tests in a row
     auto scan = [&](int v, int& total) {                          // inclusive prefix sum over the wave
         v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
         v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
@@ -834,10 +836,17 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
         total = __builtin_amdgcn_readlane(v, 63);
         return v;
     };
+    auto below = [&](uint64_t m) {                                // set bits of m below this lane
+        return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    };
     const int nE = (int)__builtin_popcountll(tmE), nS = (int)__builtin_popcountll(tmS);
     int totalE, totalS;
     const int preE = scan(nE, totalE) - nE, preS = totalE + scan(nS, totalS) - nS;
     const int total = totalE + totalS;
+    // the slots: an entry with no tests takes none, so the ray after an exhausted one is always the next slot
+    const uint64_t withE = __builtin_amdgcn_ballot_w64(nE > 0), withS = __builtin_amdgcn_ballot_w64(nS > 0);
+    const int cntE = (int)__builtin_popcountll(withE), nSlots = cntE + (int)__builtin_popcountll(withS);
+    const int slotE = below(withE), slotS = cntE + below(withS);
     auto put = [&](int v, V3 ro, V3 rd, float mt, uint64_t tm, int pre) {
         Wd[0 * 128 + v] = __builtin_bit_cast(int32_t, ro.x); Wd[1 * 128 + v] = __builtin_bit_cast(int32_t, ro.y); Wd[2 * 128 + v] = __builtin_bit_cast(int32_t, ro.z);
         Wd[3 * 128 + v] = __builtin_bit_cast(int32_t, rd.x); Wd[4 * 128 + v] = __builtin_bit_cast(int32_t, rd.y); Wd[5 * 128 + v] = __builtin_bit_cast(int32_t, rd.z);
@@ -845,58 +854,61 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
         Wd[7 * 128 + v] = (int32_t)(uint32_t)tm; Wd[8 * 128 + v] = (int32_t)(uint32_t)(tm >> 32);
         Wd[kPre + v] = pre;
     };
-    put(lane, eo, ed, 999999.0f, tmE, preE);
-    put(64 + lane, so, sd, smaxt, tmS, preS);
-    lds_u64* kLo = (lds_u64*)(Wd + kKeys);
-    lds_u64* kHi = (lds_u64*)(Wd + kKeys + 128);
-    kLo[lane] = ~0ull; kHi[lane] = ~0ull;
+    if (nE > 0) put(slotE, eo, ed, 999999.0f, tmE, preE);
+    if (nS > 0) put(slotS, so, sd, smaxt, tmS, preS);
+    if (lane < 64 - (nSlots - cntE)) Wd[kPre + nSlots + lane] = total;  // the owner search reads up to slot cntE + 63: past the last slot, a prefix no test reaches
+    lds_u64* kA = (lds_u64*)(Wd + kKeyA);
+    lds_u64* kB = (lds_u64*)(Wd + kKeyB);
     wave_lds_sync();
     const int per = (total + 63) >> 6;
     int l = 0;
     uint64_t rem = 0ull;
     V3 ro = v3(0.0f), rd = v3(0.0f);
     float rmax = 0.0f;
+    lds_u64* pA = kA;
+    lds_u64* pB = kA;
     auto fetch = [&](int v) {
         rem = (uint64_t)(uint32_t)Wd[7 * 128 + v] | ((uint64_t)(uint32_t)Wd[8 * 128 + v] << 32);
         ro = v3(__builtin_bit_cast(float, Wd[0 * 128 + v]), __builtin_bit_cast(float, Wd[1 * 128 + v]), __builtin_bit_cast(float, Wd[2 * 128 + v]));
         rd = v3(__builtin_bit_cast(float, Wd[3 * 128 + v]), __builtin_bit_cast(float, Wd[4 * 128 + v]), __builtin_bit_cast(float, Wd[5 * 128 + v]));
         rmax = __builtin_bit_cast(float, Wd[6 * 128 + v]);
+        pA = kA + v;
+        pB = v < cntE ? kB + v : pA;                               // a shadow ray's two minima both go to its occlusion word
     };
     if (per > 0) {                                                // wave-uniform
         // Every lane runs exactly `per` tests, [p, p + per): the last lanes start early enough to stay inside [0, total) and repeat
-        // tests of their neighbours — a repeated test changes nothing (same keys into the same minima, the same flag), and the loop
-        // below needs no per-lane guard: this kernel runs at the CU's instruction-issue ceiling, a guard is three instructions per trip.
+        // tests of their neighbours — a repeated test changes nothing (same keys into the same minima), and the loop below needs
+        // no per-lane guard: this kernel runs at the CU's instruction-issue ceiling, a guard is three instructions per trip.
         int p = lane * per;
         p = p < total - per ? p : total - per;
-        l = p >= totalE ? 64 : 0;                                  // owner of test p among the 128 entries: the shadow rays' tests start at totalE,
-        for (int sft = 32; sft; sft >>= 1) { const int cand = l + sft; if (Wd[kPre + cand] <= p) l = cand; }     // six dependent LDS reads for the rest
+        l = p >= totalE ? cntE : 0;                                // owner of test p: the last slot whose prefix is <= p; the shadow rays' tests start
+        for (int sft = 32; sft; sft >>= 1) { const int cand = l + sft; if (Wd[kPre + cand] <= p) l = cand; }     // at totalE, six dependent LDS reads for the rest
         fetch(l);
         rem &= ~((1ull << select64(rem, p - Wd[kPre + l])) - 1ull);
     }
     wave_lds_sync();                                              // every lane has read its prefixes ...
-    Wd[kOcc + lane] = 0;                                          // ... their first 64 words now hold the shadow rays' "occluded" flags
+    kA[lane] = ~0ull; kA[64 + lane] = ~0ull; kB[lane] = ~0ull;     // ... the minima take their place
     wave_lds_sync();
     for (int trip = 0; trip < per; ++trip) {                      // wave-uniform loop
-        while (rem == 0ull) { l++; fetch(l); }                    // next ray that has tests (there is one: the lane's tests end below `total`)
+        if (rem == 0ull) { l++; fetch(l); }                       // the next slot has tests, and it exists: the lane's tests end below `total`
         const int ti = __builtin_ctzll(rem);
         rem &= rem - 1ull;
         const TriEdges q = load_tri_edges(C, ti);
         float t, u, v;
         const bool ok = moller_trumbore_sel(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e2z), ro, rd, t, u, v);
-        if (ok & (t < rmax)) {
-            if (l < 64) {
-                const uint64_t tb = (uint64_t)f2u(t) << 32;
-                __hip_atomic_fetch_min(kLo + l, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_min(kHi + l, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else Wd[kOcc + (l - 64)] = 1;                        // NOLEAF: any hit below max_t ends the shadow ray (BVHShadowRay returns 0)
-        }
+        if (ok & (t < rmax)) {                                    // the same two minima for both kinds of ray: no branch on the kind
+            const uint64_t tb = (uint64_t)f2u(t) << 32;
+            __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }                                                         // (NOLEAF: any hit below max_t ends the shadow ray, BVHShadowRay returns 0)
     }
     wave_lds_sync();
     // 3. results: the shadow ray's throughput, the extension ray's winner (ties as in trace_closest_flat)
-    thr = (hasShadow && Wd[kOcc + lane] != 0) ? v3(0.0f) : v3(1.0f);
+    const uint64_t occ = kA[slotS];                               // (slotS < 128 and slotE < 64 are in range whether or not the entry has a slot)
+    thr = (nS > 0 && occ != ~0ull) ? v3(0.0f) : v3(1.0f);        // (nS > 0: hasShadow)
     hit.tri = -1; hit.t = 0.0f; hit.u = 0.0f; hit.v = 0.0f; hit.material = 0;
-    if (hasExt) {
-        const uint64_t a = kLo[lane], b = kHi[lane];
+    if (nE > 0) {                                                 // (hasExt; with no test the ray misses)
+        const uint64_t a = kA[slotE], b = kB[slotE];
         if (a != ~0ull) {
             int win = (int)(uint32_t)a;
             const int last = 63 - (int)(uint32_t)b;

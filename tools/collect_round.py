@@ -30,13 +30,15 @@ if stats:
     shutil.copy(stats[0], os.path.join(dst, tag + "_kernel_stats_headline.csv"))
 inputs = json.load(open(os.path.join(dst, "roofline_inputs.json")))
 have = {(e.get("workload"), e.get("spp"), e.get("kernel"), e.get("code_sha256")) for e in inputs["entries"]}
+moved = {}                                               # where each entry's counters were measured -> the tracked file they now live in
 for ef in sorted(glob.glob(os.path.join(src, "entry_*.json"))):
     name = os.path.basename(ef)[len("entry_"):-len(".json")]
     out = os.path.join(dst, "%s_pmc_%s.json" % (tag, name))
     summed = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_sum.py"), os.path.join(src, "pmc_" + name)], capture_output=True, text=True, check=True).stdout
     open(out, "w").write(summed)
     e = json.load(open(ef))
-    e["source"] = os.path.relpath(out, ROOT)
+    moved[e.get("source")] = os.path.relpath(out, ROOT)
+    e["source"] = moved[e.get("source")]
     key = (e.get("workload"), e.get("spp"), e.get("kernel"), e.get("code_sha256"))
     if key in have:                                      # the same code measured again: the newer pass replaces the older one
         inputs["entries"] = [x for x in inputs["entries"] if (x.get("workload"), x.get("spp"), x.get("kernel"), x.get("code_sha256")) != key]
@@ -44,4 +46,10 @@ for ef in sorted(glob.glob(os.path.join(src, "entry_*.json"))):
     have.add(key)
     print("entry", name, e["kernel"], (e.get("code_sha256") or "")[:12], "kernel_ms", e.get("kernel_ms"))
 json.dump(inputs, open(os.path.join(dst, "roofline_inputs.json"), "w"), indent=1)
+# the bench line names the entries it used by their `source`, as it was when bench.py ran: point it at the tracked files too
+bench = os.path.join(dst, tag + "_bench.json")
+text = open(bench).read()
+for old, new in moved.items():
+    text = text.replace(json.dumps(old), json.dumps(new))
+open(bench, "w").write(text)
 print(len(inputs["entries"]), "entries in profiles/roofline_inputs.json")
