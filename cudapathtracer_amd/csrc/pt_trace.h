@@ -147,8 +147,9 @@ PT_DEV bool moller_trumbore(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float& u,
 // blob; the SIMPLE kernel at 64 VGPRs loses 1-6 % to it and keeps the branches, profiles/r03_ab_scalar_lean.log): the
 // degenerate-triangle exit, the range test of the exact reciprocal and the four acceptance tests are lane masks combined at the
 // end; the full division only runs when some lane of the wave has |a| > 1e30 (wave-uniform, practically never). Same value of
-// (ok, t, u, v) whenever ok — the callers read t, u, v only then.
-PT_DEV bool moller_trumbore_sel(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float& u, float& v) {
+// (ok, t, u, v) whenever ok — the callers read t, u, v only then. moller_trumbore_sel_uv is the test without its `t > 0` (the
+// pair pass folds that into one unsigned compare with its upper bound, trace_pair_flat).
+PT_DEV bool moller_trumbore_sel_uv(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float& u, float& v) {
     V3 h = cross(d, e2);
     float a = dot(h, e1);
     const float m = __builtin_fabsf(a);
@@ -161,7 +162,10 @@ PT_DEV bool moller_trumbore_sel(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float
     v = f * dot(d, q);
     t = f * dot(e2, q);
     // (u >= 0 && v >= 0 as one compare on v_min: it drops a NaN operand, but then u + v is NaN and the next test fails anyway)
-    return (m >= 1e-12f) & (fminf_(u, v) >= 0.0f) & (u + v <= 1.0f) & (t > 0.0f);
+    return (m >= 1e-12f) & (fminf_(u, v) >= 0.0f) & (u + v <= 1.0f);
+}
+PT_DEV bool moller_trumbore_sel(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float& u, float& v) {
+    return moller_trumbore_sel_uv(v0, e1, e2, o, d, t, u, v) & (t > 0.0f);
 }
 
 // ONCHIP (template flag of the traversals): every PNode and PTri is in the LDS scene cache and the stack
@@ -778,9 +782,15 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 // scene is a MAT_LEAF (NOLEAF scenes: any hit below max_t occludes), the extension ray is resolved as in
 // trace_closest_flat. At most 64 internal nodes / triangles. Scratch: 24 x 64 words of the wave's stack area, by SLOT — the
 // entries (a lane's extension ray, a lane's shadow ray) that have tests, extension rays first, in lane order:
-//   o, d, max_t, triangle mask (9 fields x 128 slots); 128 u64 minima, one per slot: the extension ray's (t, first index)
-//   key, or the shadow ray's occlusion word; 64 u64 minima (t, last index) of the extension slots. The slots' exclusive
-//   prefixes (128 words) live where the 128 minima go until the owner search has read them.
+//   a 32-byte record per slot, {o.x, o.y, o.z, d.x} {d.y, d.z, triangle mask lo, hi} (128 x 8 words: one fetch is two
+//   ds_read_b128); the slots' bounds (128 words, f2u(max_t) - 1, see below); 128 u64 minima, one per slot: the extension
+//   ray's (t, first index) key, or the shadow ray's occlusion word; 64 u64 minima (t, last index) of the extension slots.
+//   The slots' exclusive prefixes (128 words) live where the 128 minima go until the owner search has read them.
+// A slot's minimum is a hit iff its high word is not ~0u (no hit has a NaN's bit pattern for t): with PT_PAIR_MIN_ALWAYS
+// every trip folds a key into both minima, a miss as (~0u, index) — min with it keeps a hit and leaves a miss a miss.
+#ifndef PT_PAIR_MIN_ALWAYS
+#define PT_PAIR_MIN_ALWAYS 0
+#endif
 template <int N>
 PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt,
                             bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
@@ -791,7 +801,9 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     // (the prefixes share the minima's words: every lane of the wave has finished the owner search before the minima are set —
     // 24 x 256 B per wave instead of 25, which is what lets a fifth 4-wave workgroup fit a CU's 160 KB next to its copy of the
     // Cornell scene)
-    constexpr int kKeyA = 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
+    typedef __attribute__((address_space(3))) f4v lds_f4;
+    constexpr int kMax = 8 * 128, kKeyA = 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
+    lds_f4* Rec = (lds_f4*)Wd;                                    // slot v's record: Rec[2 v], Rec[2 v + 1] (the scene cache before the stacks is whole 16-byte records)
     const V3 invE = inv3(ed), invS = inv3(sd);
     // 1. one lockstep node walk for both rays
     uint64_t tmE = 0ull, tmS = 0ull;
@@ -847,11 +859,17 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     const uint64_t withE = __builtin_amdgcn_ballot_w64(nE > 0), withS = __builtin_amdgcn_ballot_w64(nS > 0);
     const int cntE = (int)__builtin_popcountll(withE), nSlots = cntE + (int)__builtin_popcountll(withS);
     const int slotE = below(withE), slotS = cntE + below(withS);
+    // The trip's acceptance `t > 0 && t < max_t` is ONE unsigned compare, f2u(t) - 1 < f2u(max_t) - 1, exact for every t (NaN
+    // included) when max_t is positive and not NaN (+inf allowed). With T = f2u(t), M = f2u(max_t) in [1, 0x7f800000]: T = 0 (+0)
+    // wraps to 0xffffffff; T >= 0x80000000 (negative, -0, negative NaN) gives T - 1 >= 0x7fffffff; T in (0x7f800000, 0x7fffffff]
+    // (positive NaN) gives T - 1 >= 0x7f800000 — all >= M - 1 (<= 0x7f7fffff): rejected, as `t > 0 && t < max_t` rejects them.
+    // T in [1, 0x7f800000] (positive, +inf included) orders like its value, so T - 1 < M - 1 <=> t < max_t. A shadow ray's
+    // smaxt may be <= 0 or NaN, and then nothing passes `t > 0 && t < smaxt`: it is stored as the smallest positive float
+    // (M - 1 = 0: nothing passes either).
     auto put = [&](int v, V3 ro, V3 rd, float mt, uint64_t tm, int pre) {
-        Wd[0 * 128 + v] = __builtin_bit_cast(int32_t, ro.x); Wd[1 * 128 + v] = __builtin_bit_cast(int32_t, ro.y); Wd[2 * 128 + v] = __builtin_bit_cast(int32_t, ro.z);
-        Wd[3 * 128 + v] = __builtin_bit_cast(int32_t, rd.x); Wd[4 * 128 + v] = __builtin_bit_cast(int32_t, rd.y); Wd[5 * 128 + v] = __builtin_bit_cast(int32_t, rd.z);
-        Wd[6 * 128 + v] = __builtin_bit_cast(int32_t, mt);
-        Wd[7 * 128 + v] = (int32_t)(uint32_t)tm; Wd[8 * 128 + v] = (int32_t)(uint32_t)(tm >> 32);
+        Rec[2 * v] = f4v{ro.x, ro.y, ro.z, rd.x};
+        Rec[2 * v + 1] = f4v{rd.y, rd.z, __builtin_bit_cast(float, (uint32_t)tm), __builtin_bit_cast(float, (uint32_t)(tm >> 32))};
+        Wd[kMax + v] = (int32_t)(f2u(mt > 0.0f ? mt : 1.401298464e-45f) - 1u);
         Wd[kPre + v] = pre;
     };
     if (nE > 0) put(slotE, eo, ed, 999999.0f, tmE, preE);
@@ -864,16 +882,19 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     int l = 0;
     uint64_t rem = 0ull;
     V3 ro = v3(0.0f), rd = v3(0.0f);
-    float rmax = 0.0f;
+    uint32_t rmax1 = 0u;                                           // f2u(max_t) - 1 of the lane's current slot
+    lds_f4* pR = Rec;                                              // the lane's current slot v: its record, its bound, its two minima
+    lds_i32* pM = Wd + kMax;
     lds_u64* pA = kA;
     lds_u64* pB = kA;
-    auto fetch = [&](int v) {
-        rem = (uint64_t)(uint32_t)Wd[7 * 128 + v] | ((uint64_t)(uint32_t)Wd[8 * 128 + v] << 32);
-        ro = v3(__builtin_bit_cast(float, Wd[0 * 128 + v]), __builtin_bit_cast(float, Wd[1 * 128 + v]), __builtin_bit_cast(float, Wd[2 * 128 + v]));
-        rd = v3(__builtin_bit_cast(float, Wd[3 * 128 + v]), __builtin_bit_cast(float, Wd[4 * 128 + v]), __builtin_bit_cast(float, Wd[5 * 128 + v]));
-        rmax = __builtin_bit_cast(float, Wd[6 * 128 + v]);
-        pA = kA + v;
-        pB = v < cntE ? kB + v : pA;                               // a shadow ray's two minima both go to its occlusion word
+    lds_u64* const kAE = kA + cntE;                                // the first shadow slot's minimum
+    auto fetch = [&]() {                                           // three LDS reads: the slot's record and its bound
+        const f4v a = pR[0], b = pR[1];
+        rem = (uint64_t)f2u(b.z) | ((uint64_t)f2u(b.w) << 32);
+        ro = v3(a.x, a.y, a.z);
+        rd = v3(a.w, b.x, b.y);
+        rmax1 = (uint32_t)*pM;
+        pB = pA < kAE ? pA + (kKeyB - kKeyA) / 2 : pA;            // a shadow ray's two minima both go to its occlusion word
     };
     if (per > 0) {                                                // wave-uniform
         // Every lane runs exactly `per` tests, [p, p + per): the last lanes start early enough to stay inside [0, total) and repeat
@@ -883,33 +904,41 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
         p = p < total - per ? p : total - per;
         l = p >= totalE ? cntE : 0;                                // owner of test p: the last slot whose prefix is <= p; the shadow rays' tests start
         for (int sft = 32; sft; sft >>= 1) { const int cand = l + sft; if (Wd[kPre + cand] <= p) l = cand; }     // at totalE, six dependent LDS reads for the rest
-        fetch(l);
+        pR = Rec + 2 * l; pM = Wd + kMax + l; pA = kA + l;
+        fetch();
         rem &= ~((1ull << select64(rem, p - Wd[kPre + l])) - 1ull);
     }
     wave_lds_sync();                                              // every lane has read its prefixes ...
     kA[lane] = ~0ull; kA[64 + lane] = ~0ull; kB[lane] = ~0ull;     // ... the minima take their place
     wave_lds_sync();
     for (int trip = 0; trip < per; ++trip) {                      // wave-uniform loop
-        if (rem == 0ull) { l++; fetch(l); }                       // the next slot has tests, and it exists: the lane's tests end below `total`
+        if (rem == 0ull) { pR += 2; pM++; pA++; fetch(); }        // the next slot has tests, and it exists: the lane's tests end below `total`
         const int ti = __builtin_ctzll(rem);
         rem &= rem - 1ull;
         const TriEdges q = load_tri_edges(C, ti);
         float t, u, v;
-        const bool ok = moller_trumbore_sel(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e2z), ro, rd, t, u, v);
-        if (ok & (t < rmax)) {                                    // the same two minima for both kinds of ray: no branch on the kind
+        const bool uvOk = moller_trumbore_sel_uv(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e2z), ro, rd, t, u, v);
+        const bool ok = uvOk & (f2u(t) - 1u < rmax1);             // t > 0 && t < max_t (see put)
+#if PT_PAIR_MIN_ALWAYS
+        const uint64_t tb = (uint64_t)(ok ? f2u(t) : ~0u) << 32;  // a miss: (~0u, index), which changes no minimum's hit state
+        __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_min(pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+        if (ok) {                                                 // the same two minima for both kinds of ray: no branch on the kind
             const uint64_t tb = (uint64_t)f2u(t) << 32;
             __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_min(pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }                                                         // (NOLEAF: any hit below max_t ends the shadow ray, BVHShadowRay returns 0)
+        }
+#endif                                                            // (NOLEAF: any hit below max_t ends the shadow ray, BVHShadowRay returns 0)
     }
     wave_lds_sync();
     // 3. results: the shadow ray's throughput, the extension ray's winner (ties as in trace_closest_flat)
     const uint64_t occ = kA[slotS];                               // (slotS < 128 and slotE < 64 are in range whether or not the entry has a slot)
-    thr = (nS > 0 && occ != ~0ull) ? v3(0.0f) : v3(1.0f);        // (nS > 0: hasShadow)
+    thr = (nS > 0 && (uint32_t)(occ >> 32) != ~0u) ? v3(0.0f) : v3(1.0f);      // (nS > 0: hasShadow)
     hit.tri = -1; hit.t = 0.0f; hit.u = 0.0f; hit.v = 0.0f; hit.material = 0;
     if (nE > 0) {                                                 // (hasExt; with no test the ray misses)
         const uint64_t a = kA[slotE], b = kB[slotE];
-        if (a != ~0ull) {
+        if ((uint32_t)(a >> 32) != ~0u) {
             int win = (int)(uint32_t)a;
             const int last = 63 - (int)(uint32_t)b;
             if (win != last) {
