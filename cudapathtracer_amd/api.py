@@ -73,6 +73,14 @@ class DenoiseParams(C.Structure):    # pt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):  # pt_adaptive_params
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("chunk_spp", C.c_int32), ("threshold", C.c_float)]
+
+
+class AdaptiveStats(C.Structure):   # pt_adaptive_stats
+    _fields_ = [("rounds", C.c_int32), ("tiles_at_max", C.c_int32), ("pixel_samples", C.c_longlong)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p)      # pt_progress_fn
 
 
@@ -161,6 +169,10 @@ def lib():
     L.pt_denoise_workspace_bytes.restype = C.c_size_t; L.pt_denoise_workspace_bytes.argtypes = [i32, i32]
     L.pt_denoise.argtypes = [i32, i32, vp, i32, vp, vp, C.POINTER(DenoiseParams), vp]
     L.pt_denoise_device.argtypes = [i32, i32, vp, i32, vp, vp, C.POINTER(DenoiseParams), vp, vp, vp]
+    L.pt_render_adaptive.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, u64, C.POINTER(AdaptiveParams), vp, vp, vp,
+                                     C.POINTER(AdaptiveStats)]
+    L.pt_render_adaptive_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, u64, C.POINTER(AdaptiveParams), vp, vp, vp,
+                                            C.POINTER(AdaptiveStats), vp]
     _lib = L
     return L
 
@@ -419,6 +431,32 @@ class Scene:
         _check(lib().pt_render_aovs_device(self.h, C.byref(camera), w, h, aov_spp, seed, d_albedo_ptr, d_normal_depth_ptr, stream or None),
                "pt_render_aovs_device")
 
+    def render_adaptive(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, integrator=UNIDIRECTIONAL, use_mis=True,
+                        seed=SEED):
+        """pt_render_adaptive: tiles stop when their error estimate falls below `threshold` (the schedule: include/pt_api.h).
+        Returns (colors [h,w,4] float32: each pixel the SUM of its own tile's samples, tile_spp [tilesY,tilesX] int32,
+        tile_err [tilesY,tilesX] float32, stats dict). adaptive_mean(colors, tile_spp) gives the per-pixel mean."""
+        ty, tx = (h + 7) // 8, (w + 7) // 8
+        col = np.zeros((h, w, 4), np.float32)
+        spp = np.zeros((ty, tx), np.int32)
+        err = np.zeros((ty, tx), np.float32)
+        st = AdaptiveStats()
+        p = adaptive_params(min_spp, max_spp, chunk_spp, threshold)
+        _check(lib().pt_render_adaptive(self.h, C.byref(camera), w, h, max_depth, integrator, int(use_mis), seed, C.byref(p), _p(col),
+                                        _p(spp), _p(err), C.byref(st)), "pt_render_adaptive")
+        return col, spp, err, {f: getattr(st, f) for f, _ in AdaptiveStats._fields_}
+
+    def render_adaptive_device(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, d_rgba_sum_ptr, d_tile_spp_ptr,
+                               d_tile_err_ptr=None, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, stream=0):
+        """pt_render_adaptive_device: the same into device buffers (w*h float4, one int32 / float32 per tile; the error buffer may be
+        None). Blocks; the work is enqueued on `stream`. Returns the stats dict."""
+        st = AdaptiveStats()
+        p = adaptive_params(min_spp, max_spp, chunk_spp, threshold)
+        _check(lib().pt_render_adaptive_device(self.h, C.byref(camera), w, h, max_depth, integrator, int(use_mis), seed, C.byref(p),
+                                               d_rgba_sum_ptr, d_tile_spp_ptr, d_tile_err_ptr or None, C.byref(st), stream or None),
+               "pt_render_adaptive_device")
+        return {f: getattr(st, f) for f, _ in AdaptiveStats._fields_}
+
     def launch_unidirectional(self, max_depth, camera, num_sample, use_mis, w, h, d_colors_ptr):
         _check(lib().pt_launch_unidirectional(max_depth, camera, self.h, num_sample, int(use_mis), w, h, d_colors_ptr), "pt_launch_unidirectional")
 
@@ -646,6 +684,25 @@ def denoise_device(w, h, d_rgba_sum_ptr, spp, d_albedo_ptr, d_normal_depth_ptr, 
     p = _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)
     _check(lib().pt_denoise_device(w, h, d_rgba_sum_ptr, int(spp), d_albedo_ptr, d_normal_depth_ptr, C.byref(p), d_workspace_ptr, d_out_ptr,
                                    stream or None), "pt_denoise_device")
+
+
+def adaptive_params(min_spp, max_spp, chunk_spp, threshold):
+    """pt_adaptive_params from Python numbers (the library checks the values)."""
+    return AdaptiveParams(int(min_spp), int(max_spp), int(chunk_spp), float(threshold))
+
+
+def adaptive_mean(colors, tile_spp):
+    """Per-pixel mean of an adaptive frame: colors [h,w,4] float32 (the sums render_adaptive returns) divided by the sample
+    count of the pixel's tile, one IEEE f32 division per channel. Pass the result to denoise(..., spp=1)."""
+    if not isinstance(colors, np.ndarray) or colors.dtype != np.float32 or colors.ndim != 3 or colors.shape[2] != 4:
+        raise PtError("adaptive_mean: colors must be a float32 [h, w, 4] array")
+    h, w = colors.shape[:2]
+    if not isinstance(tile_spp, np.ndarray) or tile_spp.dtype != np.int32 or tile_spp.shape != ((h + 7) // 8, (w + 7) // 8):
+        raise PtError("adaptive_mean: tile_spp must be an int32 [%d, %d] array for a %d x %d frame" % ((h + 7) // 8, (w + 7) // 8, w, h))
+    if (tile_spp <= 0).any():
+        raise PtError("adaptive_mean: every tile needs at least one sample")
+    n = np.repeat(np.repeat(tile_spp, 8, axis=0), 8, axis=1)[:h, :w].astype(np.float32)
+    return colors / n[..., None]
 
 
 def untile_device(w, h, d_tiles_ptr, d_colors_ptr, tiles=None, stream=0):

@@ -63,6 +63,7 @@ struct pt_scene {
     DevBuf rng, spill, tilebuf, colors, pixcnt, queue, left; // work buffers, grown on demand
     DevBuf wfState, wfCtl, wfCtr, wfSpill;            // wavefront variant
     DevBuf aovSpill, aovOut;                          // pt_render_aovs: its own traversal spill area / host-form staging
+    DevBuf adS, adM, adH, adList, adKeep, adCount, adOut, adSpp, adErr;   // pt_render_adaptive: sums, snapshot, half sums, live lists; host-form staging
     int variant = 0;                                  // 0 megakernel, 1 wavefront (pt_set_variant)
     int numCU = 256;
     DeviceScene ds{};
@@ -89,7 +90,8 @@ struct pt_scene {
     bool flatOk = false; int flatWanted = 1;      // "flat": 0 off, 1 (or 2) on: scenes of at most 128 nodes / triangles (64- or 128-bit masks)   // scene qualifies for the FLAT kernels (checked in repack) / "flat" 0 turns them off (A/B)
     int lastLaunchFlat = 0, lastLaunchSimple = 0, lastLaunchLeafTable = 0;
     bool lastLaunchQueued = false;        // the last megakernel launch used the tile queue (only then is its error word that launch's)
-    int lastLaunchTiles = 0;              // ... and held this many tiles (pt_last_tile_handovers: pushes beyond them are hand-overs)
+    int lastLaunchTiles = 0;              // ... and held this many tiles (the frame's, in list mode: the waiters' exit test)
+    int lastLaunchPushed = 0;             // ... of which it queued this many at the start (pt_last_tile_handovers: pushes beyond them are hand-overs)
     int lastLaunchRefill = 0;             // ... and whether it was a REFILL instantiation
     int lastLaunchHbm = -1;               // which megakernel the last launch used (-1: none yet)
     bool wavesHbmForce = false;           // "waves_hbm" 2: ... and the 6-wave kernel whatever the tile count (tests)
@@ -106,6 +108,7 @@ struct pt_scene {
 };
 
 static int queue_error(pt_scene* s);
+static int queue_words_error(pt_scene* s, const int* q, int tiles);
 
 // LDS-resident instantiation: every PNode and PTri in the scene cache, the tree no deeper than the LDS stack, and the
 // records the bounce reads (PAttr, PMat, PLight) within their own LDS budget.
@@ -144,7 +147,7 @@ void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
     DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves, &s->wnodes, &s->qnodes, &s->leafBox, &s->mids,
                      &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
-                     &s->aovSpill, &s->aovOut};
+                     &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -822,9 +825,15 @@ static int ensure_compact(pt_scene* s) {
 #endif  // PT_EXPERIMENTAL
 
 // rng init + megakernel on `stream`; d_tiles holds t.count*64 float4.
+// List mode (list != null: adaptive sampling): t is the whole frame and the launch renders the `live` tiles that the device
+// array `list` names, through the tile queue whatever "persistent" says; the kernel is picked by `live`. The RNG states, the
+// accumulator and `left` stay indexed by tile number, so every buffer is sized for the whole frame.
 static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int maxDepth, int integrator, int useMIS,
-                        uint64_t seed, const TileSpan& t, void* d_tiles, uint32_t* d_pixcnt, bool count, hipStream_t stream, bool continueStreams) {
+                        uint64_t seed, const TileSpan& t, void* d_tiles, uint32_t* d_pixcnt, bool count, hipStream_t stream, bool continueStreams,
+                        const int* list = nullptr, int live = -1) {
     if (t.count == 0) return 0;
+    if (!list) live = t.count;
+    if (list && (count || s->variant != 0 || t.first != 0 || t.stride != 1 || live < 0 || live > t.count)) return fail(-1, "render_tiles: bad tile list");
     // the reference keys the stream by the camera's image size (y*w+x with the launch's w, deviceCode.cu:59)
     if (int r = s->rng.ensure((size_t)t.count * 384 * sizeof(uint32_t))) return r;
     // Which kernel (pt_kernels.hip): the LDS-resident instantiation, or — for a scene in HBM — the 6-waves-per-SIMD
@@ -841,7 +850,7 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     //  the 263 k-triangle scene — the generic kernel's six from 5/4 of its 6144, profiles/r02_sched_shards.log)
     const long long slotsHbm = (long long)s->numCU * 4 * wavesHbm;
     const bool hbm = !onchip && !deferred && s->wavesHbmOk &&
-                     (s->wavesHbmForce || (simpleHbm ? (long long)t.count * 4 >= slotsHbm * 3 : (long long)t.count * 4 >= slotsHbm * 5));
+                     (s->wavesHbmForce || (simpleHbm ? (long long)live * 4 >= slotsHbm * 3 : (long long)live * 4 >= slotsHbm * 5));
     bool wide = false, compact = false;
 #ifdef PT_EXPERIMENTAL
     if (hbm && simpleHbm && s->wideWanted) {
@@ -918,7 +927,7 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.queue = nullptr; P.queueMask = 0; P.left = nullptr; P.gridBlocks = 0;
     P.lptPrio = s->lptPrio; P.sliceIters = s->sliceIters; P.schedMask = s->schedMask; P.sliceAlways = s->sliceAlways ? 1 : 0;
     P.queueTimeout = (unsigned long long)s->queueTimeoutMs * 100000ull;        // ms -> ticks of the 100 MHz steady counter (hipDeviceAttributeWallClockRate)
-    if (s->persistent && !s->xcdBands) {
+    if ((s->persistent && !s->xcdBands) || list) {
         int cap = 256;
         while (cap < t.count) cap <<= 1;
         if (int r = s->queue.ensure((size_t)(kQueueHeader + 2 * cap) * sizeof(int))) return r;
@@ -928,11 +937,12 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     }
     s->lastLaunchQueued = P.queue != nullptr;
     s->lastLaunchTiles = t.count;
+    s->lastLaunchPushed = live;
     P.rng = (uint32_t*)s->rng.p; P.out = (float4*)d_tiles; P.pixCounters = d_pixcnt;
     P.totals = count ? (unsigned long long*)s->totals.p : nullptr;
     P.spill = spillEntries > 0 ? (int32_t*)s->spill.p : nullptr;
     HIP_OK(hipEventRecord(s->ev0, stream));            // HIP events on the launch stream, around the megakernel only
-    HIP_OK(launch_megakernel(integrator, count, !(s->deferShadow && !s->armless), P, stream));
+    HIP_OK(launch_megakernel(integrator, count, !(s->deferShadow && !s->armless), P, live, list, stream));
     HIP_OK(hipEventRecord(s->ev1, stream));
     s->evPending = true;
     return 0;
@@ -1051,6 +1061,134 @@ int pt_render_counted(pt_scene* s, const pt_camera* cam, int w, int h, int spp, 
 
 }  // extern "C"
 
+namespace pt {      // pt_adaptive.hip
+hipError_t launch_adaptive_iota(int n, int* list, hipStream_t stream);
+hipError_t launch_adaptive_snapshot(const int* list, int nList, const float4* S, float4* M, hipStream_t stream);
+hipError_t launch_adaptive_error(const int* list, int nList, const float4* S, const float4* M, float4* H, int n, int w, int h, int tilesX,
+                                 int minSpp, float threshold, int32_t* tileSpp, float* tileErr, int32_t* keep, hipStream_t stream);
+hipError_t launch_adaptive_compact(const int* list, const int32_t* keep, int nList, int* out, int* outCount, hipStream_t stream);
+hipError_t launch_adaptive_queue_save(const int* q, int* save, hipStream_t stream);
+}
+
+// What one round of pt_render_adaptive reads back: the new live count and the first 8 queue words after each of its two launches.
+struct RoundWords { int count, pad[7]; int q[2][8]; };
+static_assert(sizeof(RoundWords) == 96, "pt_api.h states the read-back's size");
+
+// Argument checks of pt_render_adaptive[_device], all before the first HIP call: image size, params, NULL pointers, the scene.
+static int check_adaptive_args(pt_scene* s, const pt_camera* cam, int w, int h, int integrator, const pt_adaptive_params* p,
+                               const void* out, const void* tileSpp) {
+    if (w <= 0 || h <= 0) return fail(-1, "pt_render_adaptive: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return fail(-1, "pt_render_adaptive: image of %d x %d pixels is too large", w, h);
+    if (!p) return fail(-1, "pt_render_adaptive: null params");
+    if (p->max_spp < 2) return fail(-1, "pt_render_adaptive: max_spp %d must be at least 2", p->max_spp);
+    if (p->min_spp < 0 || p->min_spp > p->max_spp) return fail(-1, "pt_render_adaptive: min_spp %d must lie in 0..max_spp (%d)", p->min_spp, p->max_spp);
+    if (p->chunk_spp < 1) return fail(-1, "pt_render_adaptive: chunk_spp %d must be positive", p->chunk_spp);
+    if (!(p->threshold >= 0.0f)) return fail(-1, "pt_render_adaptive: threshold %g must be a number >= 0", (double)p->threshold);
+    if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
+        return fail(-3, "pt_render_adaptive: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", integrator);
+    if (!cam) return fail(-1, "pt_render_adaptive: null camera");
+    if (!out || !tileSpp) return fail(-1, "pt_render_adaptive: null output buffer");
+    if (!s) return fail(-1, "pt_render_adaptive: null scene");
+    if (s->variant != 0) return fail(-1, "pt_render_adaptive: the wavefront variant has no tile queue; select the megakernel (pt_set_variant 0)");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->device) return fail(-1, "scene lives on HIP device %d but the current device is %d", s->device, dev);
+    return 0;
+}
+
+// The schedule of include/pt_api.h. Every buffer is the scene's, sized for the whole frame (the tile number indexes it); dOut,
+// dSpp and dErr are device buffers. Once per round one read-back on `stream` brings the new live count and the queue words that
+// each of the round's two launches left (the second launch re-initialises the queue, so the first one's words are saved on the
+// device before it does): both launches are checked as queue_error checks a pt_render launch.
+static int render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int maxDepth, int integrator, int useMIS, uint64_t seed,
+                           const pt_adaptive_params& p, float4* dOut, int32_t* dSpp, float* dErr, pt_adaptive_stats* stats, hipStream_t stream) {
+    TileSpan t;
+    if (int r = resolve_tiles(w, h, nullptr, t)) return r;
+    const int T = t.count;
+    const size_t tileBytes = (size_t)T * 64 * sizeof(float4);
+    if (int r = s->adS.ensure(tileBytes)) return r;
+    if (int r = s->adM.ensure(tileBytes)) return r;
+    if (int r = s->adH.ensure(tileBytes)) return r;
+    if (int r = s->adList.ensure((size_t)2 * T * sizeof(int))) return r;
+    if (int r = s->adKeep.ensure((size_t)T * sizeof(int32_t))) return r;
+    if (int r = s->adCount.ensure(sizeof(RoundWords))) return r;
+    if (!dErr) {
+        if (int r = s->adErr.ensure((size_t)T * sizeof(float))) return r;
+        dErr = (float*)s->adErr.p;
+    }
+    float4* S = (float4*)s->adS.p;
+    int* lists[2] = {(int*)s->adList.p, (int*)s->adList.p + T};
+    HIP_OK(hipMemsetAsync(s->adS.p, 0, tileBytes, stream));           // this call writes the sums: they start at 0
+    HIP_OK(hipMemsetAsync(s->adH.p, 0, tileBytes, stream));
+    HIP_OK(launch_adaptive_iota(T, lists[0], stream));               // round 0: every tile, in the order of a full frame
+    int n = 0, live = T, cur = 0, rounds = 0;
+    while (live > 0) {
+        const int c = std::min(p.chunk_spp, (p.max_spp - n) / 2);
+        if (c == 0) break;
+        RoundWords* dw = (RoundWords*)s->adCount.p;
+        for (int half = 0; half < 2; half++) {
+            // (round 0's first launch seeds the streams of every tile, as pt_render does; every later launch continues them)
+            if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, rounds > 0 || half > 0,
+                                     lists[cur], live)) return r;
+            HIP_OK(launch_adaptive_queue_save((const int*)s->queue.p, dw->q[half], stream));
+            if (half == 0) HIP_OK(launch_adaptive_snapshot(lists[cur], live, S, (float4*)s->adM.p, stream));
+        }
+        n += 2 * c;
+        HIP_OK(launch_adaptive_error(lists[cur], live, S, (const float4*)s->adM.p, (float4*)s->adH.p, n, w, h, t.tilesX, p.min_spp, p.threshold,
+                                     dSpp, dErr, (int32_t*)s->adKeep.p, stream));
+        HIP_OK(launch_adaptive_compact(lists[cur], (const int32_t*)s->adKeep.p, live, lists[cur ^ 1], &dw->count, stream));
+        RoundWords hw;
+        HIP_OK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        for (int half = 0; half < 2; half++)                          // both launches left every listed tile finished (or report -4)
+            if (int r = queue_words_error(s, hw.q[half], T)) return r;
+        const int next = hw.count;
+        if (next < 0 || next > live) return fail(-2, "pt_render_adaptive: the live list grew from %d to %d tiles", live, next);
+        live = next; cur ^= 1; rounds++;
+    }
+    HIP_OK(launch_untile(w, h, t, S, dOut, stream));
+    if (stats) {
+        std::vector<int32_t> spp(T);
+        HIP_OK(hipMemcpyAsync(spp.data(), dSpp, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        stats->rounds = rounds; stats->tiles_at_max = 0; stats->pixel_samples = 0;
+        for (int tile = 0; tile < T; tile++) {
+            const int x0 = (tile % t.tilesX) * 8, y0 = (tile / t.tilesX) * 8;
+            const long long px = (long long)std::min(8, w - x0) * std::min(8, h - y0);
+            stats->pixel_samples += px * spp[tile];
+            stats->tiles_at_max += spp[tile] == n ? 1 : 0;
+        }
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+extern "C" {
+
+int pt_render_adaptive_device(pt_scene* s, const pt_camera* cam, int w, int h, int max_depth, int integrator, int use_mis, uint64_t seed,
+                              const pt_adaptive_params* params, void* d_rgba_sum, void* d_tile_spp, void* d_tile_err, pt_adaptive_stats* stats,
+                              void* stream) {
+    if (int r = check_adaptive_args(s, cam, w, h, integrator, params, d_rgba_sum, d_tile_spp)) return r;
+    return render_adaptive(s, cam, w, h, max_depth, integrator, use_mis, seed, *params, (float4*)d_rgba_sum, (int32_t*)d_tile_spp,
+                           (float*)d_tile_err, stats, (hipStream_t)stream);
+}
+
+int pt_render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int max_depth, int integrator, int use_mis, uint64_t seed,
+                       const pt_adaptive_params* params, float* out_rgba_sum, int32_t* out_tile_spp, float* out_tile_err, pt_adaptive_stats* stats) {
+    if (int r = check_adaptive_args(s, cam, w, h, integrator, params, out_rgba_sum, out_tile_spp)) return r;
+    const size_t px = (size_t)w * h, T = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    if (int r = s->adOut.ensure(px * sizeof(float4))) return r;
+    if (int r = s->adSpp.ensure(T * sizeof(int32_t))) return r;
+    if (int r = s->adErr.ensure(T * sizeof(float))) return r;
+    if (int r = render_adaptive(s, cam, w, h, max_depth, integrator, use_mis, seed, *params, (float4*)s->adOut.p, (int32_t*)s->adSpp.p,
+                                (float*)s->adErr.p, stats, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_rgba_sum, s->adOut.p, px * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_tile_spp, s->adSpp.p, T * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_tile_err) HIP_OK(hipMemcpy(out_tile_err, s->adErr.p, T * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
 namespace pt {      // pt_aov.hip
 int aov_blocks(int nTiles, int numCU);
 hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
@@ -1140,25 +1278,30 @@ static int queue_error(pt_scene* s) {
     if (!s->queue.p || s->variant != 0 || !s->lastLaunchQueued) return 0;     // (an error word left by an earlier queued launch is not this launch's)
     int q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (hipMemcpy(q, s->queue.p, sizeof(q), hipMemcpyDeviceToHost) != hipSuccess) return fail(-2, "tile queue read-back failed");
+    return queue_words_error(s, q, s->lastLaunchTiles);
+}
+// q: the first 8 header words that a queued launch of `tiles` tiles (the frame's, in list mode) left behind.
+static int queue_words_error(pt_scene* s, const int* q, int tiles) {
     if (q[3] != 0) {
         // A waiter saw no progress for the whole bound (bit 0: a stall, recorded; the waiters stayed), or gave up for good after four
         // more (bit 1; bit 2: a push found no slot). The frame is complete iff every tile has been finished (each wave counts its tile
         // in q[2] after its last state store, and the kernel has ended); only an unfinished tile is an error.
-        if (q[2] >= s->lastLaunchTiles) { s->queueStalls++; return 0; }
+        if (q[2] >= tiles) { s->queueStalls++; return 0; }
         return fail(-4, "megakernel tile queue timed out (code %d): %d of %d tiles finished, %d pops and %d pushes claimed; the first stalled waiter saw %d finished after %.1f M ticks "
-                        "of the device's steady counter without progress: the frame is incomplete", q[3], q[2], s->lastLaunchTiles, q[0], q[1], q[6], (double)q[7] * 1.048576);
+                        "of the device's steady counter without progress: the frame is incomplete", q[3], q[2], tiles, q[0], q[1], q[6], (double)q[7] * 1.048576);
     }
     return 0;
 }
 
-// How often did a tile change hands in the last megakernel launch? The ring starts with every tile pushed once (q[1] = tiles);
-// every further push is a wave yielding its tile at the end of a time slice for another wave to continue.
+// How often did a tile change hands in the last megakernel launch? The ring starts with every tile of the launch pushed once
+// (q[1] = its tiles, in list mode the listed ones); every further push is a wave yielding its tile at the end of a time slice for
+// another wave to continue.
 int pt_last_tile_handovers(pt_scene* s) {
     if (!s) return fail(-1, "null scene");
     if (!s->queue.p || s->variant != 0 || !s->lastLaunchQueued) return 0;
     int q[4] = {0, 0, 0, 0};
     HIP_OK(hipMemcpy(q, s->queue.p, sizeof(q), hipMemcpyDeviceToHost));
-    return std::max(0, q[1] - s->lastLaunchTiles);
+    return std::max(0, q[1] - s->lastLaunchPushed);
 }
 
 // The 16 header words of the tile queue after the last queued launch (tests: the words' layout — q[4] / q[5], the issue-priority

@@ -62,6 +62,16 @@ __global__ void queue_init_kernel(int* q, int mask, int nTiles, unsigned long lo
     if (i <= mask)
         ((unsigned long long*)(q + kQueueHeader))[i] = i < nTiles ? (((unsigned long long)(unsigned)(i | kFreshBit) << 32) | (unsigned long long)(i + 1)) : (unsigned long long)i;
 }
+// List mode (adaptive sampling, pt_adaptive.hip): the ring holds list[i] | kFreshBit for i < nList, tile numbers of the whole
+// frame (tileFirst 0, tileStride 1, tileCount nTiles). q[1] = nList, and q[2] = nTiles - nList pre-credits the tiles that are not
+// in the list as finished, so the waiters' exit test (q[2] >= nTiles) holds once the listed tiles are done. The kernels are the
+// same; only the "exhausted" hint (q[0] >= tileCount) changes meaning: pt_megakernel.h, the queue protocol.
+__global__ void queue_init_list_kernel(int* q, int mask, int nTiles, const int* __restrict__ list, int nList, unsigned long long timeout) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) { q[0] = 0; q[1] = nList; q[2] = nTiles - nList; q[3] = 0; q[4] = 0; q[5] = 0; q[6] = 0; q[7] = 0; ((unsigned long long*)q)[4] = timeout; }
+    if (i <= mask)
+        ((unsigned long long*)(q + kQueueHeader))[i] = i < nList ? (((unsigned long long)(unsigned)(list[i] | kFreshBit) << 32) | (unsigned long long)(i + 1)) : (unsigned long long)i;
+}
 
 // -------------------------------------------------------------------------------------------
 // tile-major [local tile][64] <-> scan-line colors[y*w+x]
@@ -235,12 +245,16 @@ hipError_t launch_rng_init(const uint32_t* jump, unsigned long long seed, int w,
 hipError_t launch_megakernel_lds(int integrator, bool count, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream);
 hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream);
 
-hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, hipStream_t stream) {
-    if (P.tileCount <= 0) return hipSuccess;
-    int nBlocks = megakernel_blocks(P.tileCount, P.wgWaves);
+// live: the tiles this launch renders — P.tileCount, or (list != null, queued launches only) the list's first `live` entries,
+// tile numbers below P.tileCount.
+hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream) {
+    if (live <= 0) return hipSuccess;
+    if (list && !(P.queue && P.gridBlocks > 0)) return hipErrorInvalidValue;
+    int nBlocks = megakernel_blocks(live, P.wgWaves);
     if (P.queue && P.gridBlocks > 0) {
         nBlocks = std::min(nBlocks, P.gridBlocks);
-        hipLaunchKernelGGL(queue_init_kernel, dim3((P.queueMask + 256) / 256), dim3(256), 0, stream, P.queue, P.queueMask, P.tileCount, P.queueTimeout);
+        if (list) hipLaunchKernelGGL(queue_init_list_kernel, dim3((P.queueMask + 256) / 256), dim3(256), 0, stream, P.queue, P.queueMask, P.tileCount, list, live, P.queueTimeout);
+        else hipLaunchKernelGGL(queue_init_kernel, dim3((P.queueMask + 256) / 256), dim3(256), 0, stream, P.queue, P.queueMask, P.tileCount, P.queueTimeout);
     }
     dim3 grid(nBlocks), block(64 * P.wgWaves);
     const bool hbm = P.hbm != 0;                               // chosen by the host together with the spill layout

@@ -88,6 +88,11 @@ PT_DEV void path_finish(PathState& ps, V3& acc, bool defer) {
 // would orphan whatever is pushed to the position it had claimed; from then on no wave yields its tile (the slices stop). Only after
 // four more bounds without progress does a waiter give up for good (bit 1; a push that cannot find its slot: bit 2): then every
 // waiter leaves, and the host reports the frame as incomplete if a tile is unfinished (q[2] < tiles) — never a silent partial frame.
+// List mode (adaptive sampling: pt_kernels.hip, queue_init_list_kernel). The ring starts with a LIST of A tile numbers of the whole
+// frame (tileFirst 0, tileStride 1, tileCount = the frame's T tiles), q[1] = A and q[2] = T - A: the unlisted tiles count as finished.
+// Nothing below changes. One hint changes meaning: "exhausted" (q[0] >= tileCount, in megakernel_body) now needs T pops, not A,
+// so it turns true later than "no fresh tile left". Under the defaults (slice_always 1, lpt_prio 2) it is not read; otherwise it
+// only steers when slices start and issue priorities: scheduling, never the image.
 constexpr int kFreshBit = 1 << 30;
 #define PT_QLOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define PT_QSTORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)

@@ -177,7 +177,8 @@ int pt_reset_counters(pt_scene* scene);
  * the tile buffer. */
 float pt_last_kernel_ms(pt_scene* scene);
 /* Tile hand-overs of the last megakernel launch (call after it has completed): how many times a wave yielded its tile at
- * the end of a time slice for another wave to continue (0 without time slices). For tests and scheduling measurements. */
+ * the end of a time slice for another wave to continue (0 without time slices); after pt_render_adaptive, in its last launch,
+ * which rendered the tiles still live. For tests and scheduling measurements. */
 int pt_last_tile_handovers(pt_scene* scene);
 /* How many launches of this scene had their queue waiters give up — no tile finished or handed over for "queue_timeout_ms"
  * (option, default 30 000) — although every tile was finished in the end. Not an error: waiters hold no tile, the frame is
@@ -327,6 +328,56 @@ int pt_denoise(int w, int h, const float* rgba_sum, int spp, const float* albedo
                const pt_denoise_params* params, float* out_rgba_sum);                                  /* host, blocking */
 int pt_denoise_device(int w, int h, const void* d_rgba_sum, int spp, const void* d_albedo, const void* d_normal_depth,
                       const pt_denoise_params* params, void* d_workspace, void* d_out, void* stream);  /* async */
+
+/* ---- adaptive sampling: 8x8 tiles stop when their error estimate converges ------------------
+ * The per-pixel stopping criterion of Dammertz et al., "A hierarchical automatic stopping condition for Monte Carlo
+ * global illumination" (2009), section 2.1, applied per tile. A pixel's samples are one XORWOW stream keyed by the pixel,
+ * so a tile that stops after n samples holds exactly the sums of pt_render(spp = n) over its pixels, bit for bit.
+ *
+ * Schedule and estimator. All arithmetic is f32 with IEEE rounding and no contraction, evaluated left to right:
+ *   n = 0; live = every tile of the ceil(w/8) x ceil(h/8) grid, ascending
+ *   loop:
+ *     c = min(chunk_spp, (max_spp - n) / 2)  (integer division); stop if c == 0 or live is empty
+ *     render c samples on live -> S;  M = S;  render c samples on live -> S
+ *     H = H + (S - M)  per rgb channel (H starts at 0);  n = n + 2c
+ *     per in-image pixel of a live tile:
+ *       d = |S.r - 2H.r| + |S.g - 2H.g| + |S.b - 2H.b|;  inv = 1.0f / (float)n
+ *       e = (d * inv) / (1e-4f + sqrtf((S.r + S.g + S.b) * inv))
+ *       e = 0 if any rgb channel of S or H is non-finite, or if e is NaN (such a pixel never holds its tile back)
+ *     E_T = max(0, e over the tile's in-image pixels)
+ *     a live tile stops, with tile_spp = n, if n >= min_spp and E_T < threshold; the others stay live, in ascending order
+ *   tiles still live at the end get tile_spp = n
+ * Round 0 renders the whole frame (streams seeded as in pt_render); later rounds render only the live tiles.
+ *
+ * Outputs. out_rgba_sum: w*h float4 scan-line, y = 0 the bottom row, each pixel the sum over its own tile_spp samples;
+ * w is 0. This call WRITES the sums, it does not add to them (unlike pt_render): the estimator must see this render's
+ * samples alone. out_tile_spp / out_tile_err: one entry per tile, row-major over the tile grid (tile = ty * ceil(w/8) + tx,
+ * the numbering of pt_tile_range); out_tile_err holds E_T of the last round the tile took part in and may be NULL.
+ * stats (may be NULL): rounds run, tiles whose tile_spp is the largest n the schedule reached, and the sum over in-image
+ * pixels of their sample counts.
+ * Both forms block; the device form enqueues all its work and read-backs on `stream`: once per round, one copy of 96 bytes
+ * (the live count and the tile queue's words after each of the round's two launches, both of which are checked: a launch that
+ * left a listed tile unfinished fails the call with -4, a stall counts in pt_queue_stalls). Arguments are checked
+ * before any HIP call: image size, params, NULL pointers (camera and the outputs), then the scene. The megakernel only:
+ * with the wavefront variant selected (pt_set_variant) the call fails with -1 and leaves the outputs untouched. Every
+ * launch uses the tile queue whatever the "persistent" option says; all other options apply as usual. */
+typedef struct pt_adaptive_params {
+    int32_t min_spp;             /* no tile stops before it has this many samples (0 <= min_spp <= max_spp) */
+    int32_t max_spp;             /* no tile gets more (>= 2; an odd budget ends at max_spp - 1) */
+    int32_t chunk_spp;           /* c: samples per half-round (>= 1) */
+    float threshold;             /* a tile stops when E_T < threshold; 0 = never early (uniform max_spp); NaN / < 0 rejected */
+} pt_adaptive_params;
+typedef struct pt_adaptive_stats {
+    int32_t rounds;              /* rounds run (each renders 2c samples on the live tiles) */
+    int32_t tiles_at_max;        /* tiles that ran to the end of the schedule */
+    long long pixel_samples;     /* sum of tile_spp over in-image pixels */
+} pt_adaptive_stats;
+int pt_render_adaptive(pt_scene* scene, const pt_camera* camera, int w, int h, int max_depth, int integrator, int use_mis,
+                       uint64_t seed, const pt_adaptive_params* params, float* out_rgba_sum, int32_t* out_tile_spp,
+                       float* out_tile_err, pt_adaptive_stats* stats);                                   /* host buffers */
+int pt_render_adaptive_device(pt_scene* scene, const pt_camera* camera, int w, int h, int max_depth, int integrator, int use_mis,
+                              uint64_t seed, const pt_adaptive_params* params, void* d_rgba_sum, void* d_tile_spp,
+                              void* d_tile_err, pt_adaptive_stats* stats, void* stream);                /* device buffers */
 
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
