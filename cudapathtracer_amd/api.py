@@ -73,6 +73,10 @@ class DenoiseParams(C.Structure):    # pt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class DenoiseVarParams(C.Structure):  # pt_denoise_var_params
+    _fields_ = [("iterations", C.c_int32), ("sigma_var", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("chunk_spp", C.c_int32), ("threshold", C.c_float)]
 
@@ -173,6 +177,12 @@ def lib():
                                      C.POINTER(AdaptiveStats)]
     L.pt_render_adaptive_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, u64, C.POINTER(AdaptiveParams), vp, vp, vp,
                                             C.POINTER(AdaptiveStats), vp]
+    L.pt_render_moments.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, u64, vp, vp]
+    L.pt_render_moments_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, u64, vp, vp, vp]
+    L.pt_denoise_var_defaults.restype = None; L.pt_denoise_var_defaults.argtypes = [C.POINTER(DenoiseVarParams)]
+    L.pt_denoise_var_workspace_bytes.restype = C.c_size_t; L.pt_denoise_var_workspace_bytes.argtypes = [i32, i32]
+    L.pt_denoise_var.argtypes = [i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(DenoiseVarParams), vp]
+    L.pt_denoise_var_device.argtypes = [i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(DenoiseVarParams), vp, vp, vp]
     _lib = L
     return L
 
@@ -457,6 +467,22 @@ class Scene:
                "pt_render_adaptive_device")
         return {f: getattr(st, f) for f, _ in AdaptiveStats._fields_}
 
+    def render_moments(self, camera, w, h, spp, batch_spp, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED):
+        """pt_render_moments: `spp` samples per pixel in spp / batch_spp batches. Returns (S, Q), both [h,w,4] float32: S the
+        sum of the samples (render(spp) into zeros, bit for bit), Q per rgb channel the sum of the squared batch sums, Q.w
+        the number of batches. denoise_var(S, Q, spp, spp // batch_spp, ...) reads the pair."""
+        S = np.zeros((h, w, 4), np.float32)
+        Q = np.zeros((h, w, 4), np.float32)
+        _check(lib().pt_render_moments(self.h, C.byref(camera), w, h, spp, batch_spp, max_depth, integrator, int(use_mis), seed, _p(S), _p(Q)),
+               "pt_render_moments")
+        return S, Q
+
+    def render_moments_device(self, camera, w, h, spp, batch_spp, max_depth, d_rgba_sum_ptr, d_sq_sum_ptr, integrator=UNIDIRECTIONAL,
+                              use_mis=True, seed=SEED, stream=0):
+        """pt_render_moments_device: the same into device buffers of w*h float4 each. Blocks; the work is enqueued on `stream`."""
+        _check(lib().pt_render_moments_device(self.h, C.byref(camera), w, h, spp, batch_spp, max_depth, integrator, int(use_mis), seed,
+                                              d_rgba_sum_ptr, d_sq_sum_ptr, stream or None), "pt_render_moments_device")
+
     def launch_unidirectional(self, max_depth, camera, num_sample, use_mis, w, h, d_colors_ptr):
         _check(lib().pt_launch_unidirectional(max_depth, camera, self.h, num_sample, int(use_mis), w, h, d_colors_ptr), "pt_launch_unidirectional")
 
@@ -684,6 +710,58 @@ def denoise_device(w, h, d_rgba_sum_ptr, spp, d_albedo_ptr, d_normal_depth_ptr, 
     p = _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)
     _check(lib().pt_denoise_device(w, h, d_rgba_sum_ptr, int(spp), d_albedo_ptr, d_normal_depth_ptr, C.byref(p), d_workspace_ptr, d_out_ptr,
                                    stream or None), "pt_denoise_device")
+
+
+def denoise_var_defaults():
+    """pt_denoise_var_defaults as a dict: iterations, sigma_var, sigma_normal, sigma_depth."""
+    p = DenoiseVarParams()
+    lib().pt_denoise_var_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in DenoiseVarParams._fields_}
+
+
+def _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth):
+    p = DenoiseVarParams()
+    lib().pt_denoise_var_defaults(C.byref(p))
+    for f, v in (("iterations", iterations), ("sigma_var", sigma_var), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+        if v is not None:
+            setattr(p, f, v)
+    return p
+
+
+def denoise_var_workspace_bytes(w, h):
+    return int(lib().pt_denoise_var_workspace_bytes(w, h))
+
+
+def denoise_var(rgba_sum, sq_sum, spp, batches, albedo, normal_depth, iterations=None, sigma_var=None, sigma_normal=None, sigma_depth=None,
+                out=None):
+    """pt_denoise_var (host, blocking): the a-trous filter with a variance-guided colour weight. rgba_sum and sq_sum are
+    what Scene.render_moments returned for `spp` samples in `batches` batches ([h,w,4] float32); albedo and normal_depth come
+    from render_aovs. Returns the filtered radiance sum. A None parameter takes the library default
+    (denoise_var_defaults()). `out` may be rgba_sum itself."""
+    arrs = []
+    for name, a in (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or a.shape[2] != 4:
+            raise PtError("denoise_var: %s must be a float32 [h, w, 4] array" % name)
+        arrs.append(np.ascontiguousarray(a))
+    if any(a.shape != arrs[0].shape for a in arrs[1:]):
+        raise PtError("denoise_var: shapes differ: %s, %s, %s, %s" % tuple(a.shape for a in arrs))
+    h, w = arrs[0].shape[:2]
+    res = np.empty_like(arrs[0]) if out is None else out
+    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == arrs[0].shape and res.flags.c_contiguous):
+        raise PtError("denoise_var: out must be a C-contiguous float32 array of shape %s" % (arrs[0].shape,))
+    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_var(w, h, _p(arrs[0]), _p(arrs[1]), int(spp), int(batches), _p(arrs[2]), _p(arrs[3]), C.byref(p), _p(res)),
+           "pt_denoise_var")
+    return res
+
+
+def denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr, d_out_ptr,
+                       iterations=None, sigma_var=None, sigma_normal=None, sigma_depth=None, stream=0):
+    """pt_denoise_var_device: device buffers of w*h float4 and a workspace of denoise_var_workspace_bytes(w, h) bytes;
+    asynchronous on `stream`. d_out_ptr may equal d_rgba_sum_ptr."""
+    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
+                                       C.byref(p), d_workspace_ptr, d_out_ptr, stream or None), "pt_denoise_var_device")
 
 
 def adaptive_params(min_spp, max_spp, chunk_spp, threshold):

@@ -64,6 +64,7 @@ struct pt_scene {
     DevBuf wfState, wfCtl, wfCtr, wfSpill;            // wavefront variant
     DevBuf aovSpill, aovOut;                          // pt_render_aovs: its own traversal spill area / host-form staging
     DevBuf adS, adM, adH, adList, adKeep, adCount, adOut, adSpp, adErr;   // pt_render_adaptive: sums, snapshot, half sums, live lists; host-form staging
+    DevBuf moS, moP, moQ, moOut;                      // pt_render_moments: sums, previous sums, squared batch sums (tile-major); host-form staging
     int variant = 0;                                  // 0 megakernel, 1 wavefront (pt_set_variant)
     int numCU = 256;
     DeviceScene ds{};
@@ -147,7 +148,8 @@ void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
     DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves, &s->wnodes, &s->qnodes, &s->leafBox, &s->mids,
                      &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
-                     &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr};
+                     &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr,
+                     &s->moS, &s->moP, &s->moQ, &s->moOut};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1184,6 +1186,84 @@ int pt_render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int max_
     HIP_OK(hipMemcpy(out_rgba_sum, s->adOut.p, px * sizeof(float4), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out_tile_spp, s->adSpp.p, T * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (out_tile_err) HIP_OK(hipMemcpy(out_tile_err, s->adErr.p, T * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace pt {      // pt_moments.hip
+hipError_t launch_moments_update(int nTiles, const float4* S, float4* P, float4* Q, bool first, int batches, hipStream_t stream);
+}
+
+// Argument checks of pt_render_moments[_device], all before the first HIP call: image size, the sample counts, the integrator,
+// NULL pointers (camera and the outputs), the camera's size, then the scene.
+static int check_moments_args(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int batchSpp, int integrator, const void* outS,
+                              const void* outQ) {
+    if (w <= 0 || h <= 0) return fail(-1, "pt_render_moments: image size %d x %d must be positive", w, h);
+    if ((long long)((w + 7) / 8) * ((h + 7) / 8) * 64 > 0x7fffffffll) return fail(-1, "pt_render_moments: image of %d x %d pixels is too large", w, h);
+    if (spp <= 0) return fail(-1, "pt_render_moments: spp %d must be positive", spp);
+    if (batchSpp <= 0) return fail(-1, "pt_render_moments: batch_spp %d must be positive", batchSpp);
+    if (spp % batchSpp != 0) return fail(-1, "pt_render_moments: spp %d must be a multiple of batch_spp %d", spp, batchSpp);
+    if (spp / batchSpp < 2) return fail(-1, "pt_render_moments: spp %d / batch_spp %d must give at least 2 batches", spp, batchSpp);
+    if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
+        return fail(-3, "pt_render_moments: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", integrator);
+    if (!cam) return fail(-1, "pt_render_moments: null camera");
+    if (cam->w != w || cam->h != h) return fail(-1, "pt_render_moments: the camera is %d x %d, the image %d x %d", cam->w, cam->h, w, h);
+    if (!outS || !outQ) return fail(-1, "pt_render_moments: null output buffer");
+    if (!s) return fail(-1, "pt_render_moments: null scene");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->device) return fail(-1, "scene lives on HIP device %d but the current device is %d", s->device, dev);
+    return 0;
+}
+
+// B = spp / c ordinary launches of c samples into the scene's own zeroed accumulator, the first seeding the streams as pt_render
+// does and the others continuing them; after each the bookkeeping pass, a wait, and the check pt_render makes of its launch (the
+// tile queue's words; the wavefront variant checks itself). A batch that fails ends the call. dS, dQ: device, scan-line.
+static int render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int c, int maxDepth, int integrator, int useMIS,
+                          uint64_t seed, float4* dS, float4* dQ, hipStream_t stream) {
+    TileSpan t;
+    if (int r = resolve_tiles(w, h, nullptr, t)) return r;
+    const int T = t.count, B = spp / c;
+    const size_t tileBytes = (size_t)T * 64 * sizeof(float4);
+    if (int r = s->moS.ensure(tileBytes)) return r;
+    if (int r = s->moP.ensure(tileBytes)) return r;
+    if (int r = s->moQ.ensure(tileBytes)) return r;
+    float4 *S = (float4*)s->moS.p, *P = (float4*)s->moP.p, *Q = (float4*)s->moQ.p;
+    HIP_OK(hipMemsetAsync(S, 0, tileBytes, stream));                  // this call writes the sums: they start at 0
+    for (int j = 0; j < B; j++) {
+        if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, j > 0)) return r;
+        HIP_OK(launch_moments_update(T, S, P, Q, j == 0, B, stream));
+        int q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const bool queued = s->queue.p && s->variant == 0 && s->lastLaunchQueued;
+        if (queued) HIP_OK(hipMemcpyAsync(q, s->queue.p, sizeof(q), hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        if (queued)
+            if (int r = queue_words_error(s, q, s->lastLaunchTiles)) return r;
+    }
+    HIP_OK(launch_untile(w, h, t, S, dS, stream));
+    HIP_OK(launch_untile(w, h, t, Q, dQ, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+extern "C" {
+
+int pt_render_moments_device(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int batch_spp, int max_depth, int integrator,
+                             int use_mis, uint64_t seed, void* d_rgba_sum, void* d_sq_sum, void* stream) {
+    if (int r = check_moments_args(s, cam, w, h, spp, batch_spp, integrator, d_rgba_sum, d_sq_sum)) return r;
+    return render_moments(s, cam, w, h, spp, batch_spp, max_depth, integrator, use_mis, seed, (float4*)d_rgba_sum, (float4*)d_sq_sum,
+                          (hipStream_t)stream);
+}
+
+int pt_render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int batch_spp, int max_depth, int integrator, int use_mis,
+                      uint64_t seed, float* out_rgba_sum, float* out_sq_sum) {
+    if (int r = check_moments_args(s, cam, w, h, spp, batch_spp, integrator, out_rgba_sum, out_sq_sum)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    if (int r = s->moOut.ensure(2 * bytes)) return r;
+    char* d = (char*)s->moOut.p;
+    if (int r = render_moments(s, cam, w, h, spp, batch_spp, max_depth, integrator, use_mis, seed, (float4*)d, (float4*)(d + bytes), nullptr)) return r;
+    HIP_OK(hipMemcpy(out_rgba_sum, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_sq_sum, d + bytes, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -8,6 +8,8 @@
 //   denoise_iter_kernel      one launch per step s = 2^i: the 5x5 B3-spline taps at stride s, weighted by colour, normal, depth
 //   denoise_finish_kernel    out = spp * a * e, or S itself for pass-through pixels
 //
+// pt_denoise_var's kernels (the variance-guided colour weight) follow pt_denoise's below and share its reduction and workspace layout.
+//
 // Workspace (pt_denoise_workspace_bytes): e ping-pong (2 x w*h float4: rgb, w = 1 filtered / 0 pass-through), the normal-depth
 // guide (w*h float4: unit normal or 0, depth), the partial sums (one float2 per 256 pixels) and the result of the reduction.
 #include <algorithm>
@@ -140,6 +142,118 @@ __global__ void __launch_bounds__(kDnBlock) denoise_finish_kernel(int n, const f
     out[i] = make_float4(spp * (demod_albedo(a.x) * ev.x), spp * (demod_albedo(a.y) * ev.y), spp * (demod_albedo(a.z) * ev.z), s.w);
 }
 
+// ---- pt_denoise_var: the same filter with a variance-guided colour weight (include/pt_api.h) --------------------------------
+// e.w carries the pixel's variance V of the demodulated mean (>= 0) or -1 for a pass-through pixel, so a tap is still one
+// float4 of e and one of the guide.
+//
+//   denoise_var_prepare_kernel   as denoise_prepare_kernel, plus V from S and Q in f32 in the header's order
+//   denoise_var_iter_kernel      the 3x3 binomial of V around p (plain cached loads of e.w: the step-1 taps of the same wave
+//                                read those lines anyway), then the 5x5 taps; e' = sum w e / sum w, V' = sum w^2 V / (sum w)^2
+//   denoise_var_finish_kernel    denoise_finish_kernel with the pass-through mark of this layout
+__global__ void __launch_bounds__(kDnBlock) denoise_var_prepare_kernel(int n, const float4* __restrict__ sum, const float4* __restrict__ sq, float spp,
+                                                                       float batches, const float4* __restrict__ albedo,
+                                                                       const float4* __restrict__ nd, float4* __restrict__ e,
+                                                                       float4* __restrict__ guide, float2* __restrict__ partials) {
+    __shared__ float sLum[kDnBlock], sCnt[kDnBlock];
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    float lum = 0.0f, cnt = 0.0f;
+    if (i < n) {
+        const float4 s = sum[i], q = sq[i], a = albedo[i], g = nd[i];
+        const float4 m = make_float4(s.x / spp, s.y / spp, s.z / spp, s.w / spp);
+        const float ax = demod_albedo(a.x), ay = demod_albedo(a.y), az = demod_albedo(a.z);
+        // var_c = max(0, Q_c - S_c^2 / B) / (B - 1) * B / spp^2, left to right; max(0, x) keeps a NaN
+        const float spp2 = spp * spp;
+        float vx = q.x - s.x * s.x / batches, vy = q.y - s.y * s.y / batches, vz = q.z - s.z * s.z / batches;
+        vx = (vx < 0.0f ? 0.0f : vx) / (batches - 1.0f) * batches / spp2;
+        vy = (vy < 0.0f ? 0.0f : vy) / (batches - 1.0f) * batches / spp2;
+        vz = (vz < 0.0f ? 0.0f : vz) / (batches - 1.0f) * batches / spp2;
+        const float V = vx / (ax * ax) + vy / (ay * ay) + vz / (az * az);
+        const bool filtered = a.w > 0.0f && finite3(m) && __builtin_isfinite(V);
+        const float4 ev = make_float4(m.x / ax, m.y / ay, m.z / az, filtered ? V : -1.0f);
+        e[i] = ev;
+        const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+        guide[i] = len > 0.0f ? make_float4(g.x / len, g.y / len, g.z / len, g.w) : make_float4(0.0f, 0.0f, 0.0f, g.w);
+        if (filtered) { lum = 0.2126f * ev.x + 0.7152f * ev.y + 0.0722f * ev.z; cnt = 1.0f; }
+    }
+    sLum[threadIdx.x] = lum; sCnt[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int k = kDnBlock / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) { sLum[threadIdx.x] += sLum[threadIdx.x + k]; sCnt[threadIdx.x] += sCnt[threadIdx.x + k]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = make_float2(sLum[0], sCnt[0]);
+}
+
+// The launch shape of denoise_iter_kernel: 16x16 pixels per workgroup as four 8x8 tiles, one per wave.
+__global__ void __launch_bounds__(256) denoise_var_iter_kernel(int w, int h, int step, float sigmaVar, float sigmaNormal, float sigmaDepth,
+                                                               const float4* __restrict__ lum, const float4* __restrict__ eIn,
+                                                               const float4* __restrict__ guide, float4* __restrict__ eOut) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    const float4 ep = eIn[p];
+    if (ep.w < 0.0f) { eOut[p] = ep; return; }
+    const float4 gp = guide[p];
+    const bool normalP = gp.x != 0.0f || gp.y != 0.0f || gp.z != 0.0f;
+    const float hk[3] = {0.375f, 0.25f, 0.0625f};
+    float sx = 0.140625f * ep.x, sy = 0.140625f * ep.y, sz = 0.140625f * ep.z, sw = 0.140625f;     // centre tap: h(0)^2
+    float sv = (0.140625f * 0.140625f) * ep.w;
+    if (normalP) {
+        // the 3x3 binomial of V, (1, 2, 1) x (1, 2, 1) / 16 at stride 1: a neighbour outside the image or pass-through gives V_p
+        float vt = 0.0f;
+        for (int dy = -1; dy <= 1; dy++) {
+            const int yq = y + dy;
+            for (int dx = -1; dx <= 1; dx++) {
+                const int xq = x + dx;
+                float v = ep.w;
+                if (yq >= 0 && yq < h && xq >= 0 && xq < w) {
+                    const float vq = eIn[(size_t)yq * w + xq].w;
+                    if (vq >= 0.0f) v = vq;
+                }
+                vt += ((dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f)) * v;
+            }
+        }
+        // w_c = exp(-|de| / (sigma_var sqrt(Vt) + 1e-3 L + 1e-20)), w_z = exp(-|dz| / (sigma_z z_p)), w_n = max(0, n.n')^sigma_n: one exp2 per tap
+        const float log2e = 1.4426950408889634f;
+        const float kc = log2e / (sigmaVar * __builtin_sqrtf(vt) + 1e-3f * lum[0].x + 1e-20f), kz = log2e / (sigmaDepth * gp.w);
+        for (int dy = -2; dy <= 2; dy++) {
+            const int yq = y + dy * step;
+            if (yq < 0 || yq >= h) continue;
+            for (int dx = -2; dx <= 2; dx++) {
+                const int xq = x + dx * step;
+                if (xq < 0 || xq >= w || (dx == 0 && dy == 0)) continue;
+                const size_t q = (size_t)yq * w + xq;
+                const float4 eq = eIn[q];
+                if (eq.w < 0.0f) continue;
+                const float4 gq = guide[q];
+                if (gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f) continue;
+                const float cs = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+                float ln;
+                if (sigmaNormal == 0.0f) ln = 0.0f;
+                else if (cs > 0.0f) ln = sigmaNormal * __builtin_log2f(cs);
+                else continue;
+                const float dr = ep.x - eq.x, dg = ep.y - eq.y, db = ep.z - eq.z;
+                const float dc = __builtin_sqrtf(dr * dr + dg * dg + db * db), dz = fabsf(gp.w - gq.w);
+                const float wt = (hk[dx < 0 ? -dx : dx] * hk[dy < 0 ? -dy : dy]) * __builtin_exp2f(ln - dc * kc - dz * kz);
+                sx += wt * eq.x; sy += wt * eq.y; sz += wt * eq.z; sw += wt;
+                sv += (wt * wt) * eq.w;
+            }
+        }
+    }
+    eOut[p] = make_float4(sx / sw, sy / sw, sz / sw, sv / (sw * sw));
+}
+
+__global__ void __launch_bounds__(kDnBlock) denoise_var_finish_kernel(int n, const float4* sum, float spp, const float4* __restrict__ albedo,
+                                                                      const float4* __restrict__ e, float4* out) {
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 s = sum[i], ev = e[i];          // (out may alias sum: each thread reads its own pixel before it writes it)
+    if (ev.w < 0.0f) { out[i] = s; return; }
+    const float4 a = albedo[i];
+    out[i] = make_float4(spp * (demod_albedo(a.x) * ev.x), spp * (demod_albedo(a.y) * ev.y), spp * (demod_albedo(a.z) * ev.z), s.w);
+}
+
 static int dn_fail(int code, const char* fmt, int a = 0, int b = 0) {
     char buf[256];
     snprintf(buf, sizeof(buf), fmt, a, b);
@@ -188,6 +302,46 @@ static int denoise_launch(int w, int h, const float4* in, int spp, const float4*
         DN_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
+    DN_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int check_denoise_var_args(int w, int h, const void* in, const void* sq, int spp, int batches, const void* albedo, const void* nd,
+                                  const pt_denoise_var_params& P, const void* out) {
+    if (w <= 0 || h <= 0) return dn_fail(-1, "pt_denoise_var: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return dn_fail(-1, "pt_denoise_var: image of %d x %d pixels is too large", w, h);
+    if (spp <= 0) return dn_fail(-1, "pt_denoise_var: spp %d must be positive", spp);
+    if (batches < 2) return dn_fail(-1, "pt_denoise_var: batches %d must be at least 2", batches);
+    if (spp % batches != 0) return dn_fail(-1, "pt_denoise_var: batches %d must divide spp %d", batches, spp);
+    if (!in || !sq || !albedo || !nd || !out) return dn_fail(-1, "pt_denoise_var: null buffer");
+    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return dn_fail(-1, "pt_denoise_var: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
+    if (!(P.sigma_var > 0.0f) || !std::isfinite(P.sigma_var)) return dn_fail(-1, "pt_denoise_var: sigma_var must be positive and finite");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return dn_fail(-1, "pt_denoise_var: sigma_normal must be >= 0 and finite");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return dn_fail(-1, "pt_denoise_var: sigma_depth must be positive and finite");
+    return 0;
+}
+
+static int denoise_var_launch(int w, int h, const float4* in, const float4* sq, int spp, int batches, const float4* albedo, const float4* nd,
+                              const pt_denoise_var_params& P, char* ws, float4* out, hipStream_t stream) {
+    const DnLayout L = dn_layout(w, h);
+    float4* e[2] = {(float4*)(ws + L.e0), (float4*)(ws + L.e1)};
+    float4* guide = (float4*)(ws + L.guide);
+    float2* partials = (float2*)(ws + L.partials);
+    float4* lum = (float4*)(ws + L.lum);
+    const int n = (int)L.n;
+    const float fspp = (float)spp;
+    hipLaunchKernelGGL(denoise_var_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, sq, fspp, (float)batches, albedo, nd, e[0], guide,
+                       partials);
+    DN_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
+    DN_HIP_OK(hipGetLastError());
+    const dim3 grid((w + 15) / 16, (h + 15) / 16);
+    for (int i = 0; i < P.iterations; i++) {
+        hipLaunchKernelGGL(denoise_var_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, P.sigma_var, P.sigma_normal, P.sigma_depth, lum,
+                           e[i & 1], guide, e[(i + 1) & 1]);
+        DN_HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(denoise_var_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
     DN_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -241,6 +395,57 @@ int pt_denoise(int w, int h, const float* rgba_sum, int spp, const float* albedo
     } else if ((r = denoise_launch(w, h, (const float4*)dIn, spp, (const float4*)dA, (const float4*)dN, P, d, (float4*)dIn, nullptr)) == 0) {
         e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) r = dn_fail(-2, "pt_denoise: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+void pt_denoise_var_defaults(pt_denoise_var_params* out) {
+    if (!out) return;
+    out->iterations = 3;
+    out->sigma_var = 6.0f;
+    out->sigma_normal = 64.0f;
+    out->sigma_depth = 0.02f;
+}
+
+size_t pt_denoise_var_workspace_bytes(int w, int h) {
+    if (w <= 0 || h <= 0) return 0;
+    return dn_layout(w, h).total;
+}
+
+int pt_denoise_var_device(int w, int h, const void* d_rgba_sum, const void* d_sq_sum, int spp, int batches, const void* d_albedo,
+                          const void* d_normal_depth, const pt_denoise_var_params* params, void* d_workspace, void* d_out, void* stream) {
+    pt_denoise_var_params P;
+    if (params) P = *params; else pt_denoise_var_defaults(&P);
+    if (int r = check_denoise_var_args(w, h, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, P, d_out)) return r;
+    if (!d_workspace) return pt_fail_(-1, "pt_denoise_var_device: null workspace");
+    return denoise_var_launch(w, h, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
+                              (const float4*)d_normal_depth, P, (char*)d_workspace, (float4*)d_out, (hipStream_t)stream);
+}
+
+int pt_denoise_var(int w, int h, const float* rgba_sum, const float* sq_sum, int spp, int batches, const float* albedo, const float* normal_depth,
+                   const pt_denoise_var_params* params, float* out_rgba_sum) {
+    pt_denoise_var_params P;
+    if (params) P = *params; else pt_denoise_var_defaults(&P);
+    if (int r = check_denoise_var_args(w, h, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, P, out_rgba_sum)) return r;
+    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total;
+    char* d = nullptr;
+    DN_HIP_OK(hipMalloc(&d, ws + 4 * bytes));
+    char* dIn = d + ws;                      // in and out share one buffer (out may alias in)
+    char* dQ = dIn + bytes;
+    char* dA = dQ + bytes;
+    char* dN = dA + bytes;
+    hipError_t e = hipMemcpy(dIn, rgba_sum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = dn_fail(-2, "pt_denoise_var: upload failed");
+    } else if ((r = denoise_var_launch(w, h, (const float4*)dIn, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN, P, d,
+                                       (float4*)dIn, nullptr)) == 0) {
+        e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_var: download failed");
     }
     (void)hipFree(d);
     return r;

@@ -379,6 +379,58 @@ int pt_render_adaptive_device(pt_scene* scene, const pt_camera* camera, int w, i
                               uint64_t seed, const pt_adaptive_params* params, void* d_rgba_sum, void* d_tile_spp,
                               void* d_tile_err, pt_adaptive_stats* stats, void* stream);                /* device buffers */
 
+/* ---- per-pixel variance: a frame plus its sum of squared batch sums; the variance-guided denoiser ------------------
+ * pt_render_moments renders `spp` samples per pixel as B = spp / batch_spp batches of c = batch_spp samples (c >= 1, spp a
+ * multiple of c, B >= 2) on the whole frame. All arithmetic is f32 with IEEE rounding and no contraction, left to right:
+ *   batch j = 1..B renders c samples per pixel; the streams are seeded as in pt_render before batch 1 and continue afterwards,
+ *   so after batch j the accumulator S_j is bit-identical to pt_render(spp = j c) into a zeroed buffer;
+ *   after each batch, per pixel and rgb channel: d = S_j - S_{j-1} (S_0 = 0), Q = Q + d d (Q_0 = 0; the product is rounded
+ *   before the add). Q.w = (float)B. No special case for NaN / Inf: they propagate into Q.
+ * Outputs, both w*h float4 scan-line, y = 0 the bottom row: out_rgba_sum = S_B (pt_render(spp) bit for bit), out_sq_sum = Q.
+ * This call WRITES both (like pt_render_adaptive, unlike pt_render). It never touches the counters, and a later pt_render of
+ * the same scene is unaffected (it re-seeds). Both forms block; the device form enqueues its work on `stream`. After every
+ * batch the host waits and checks the launch as pt_render checks its own: an unfinished frame fails the call with -4 (no
+ * further batch is launched), a stall counts in pt_queue_stalls. Both variants (pt_set_variant 0 and 1) and every option
+ * apply. Arguments are checked before any HIP call: image size, spp, batch_spp, the integrator, NULL camera, camera->w / h
+ * equal to w / h, NULL outputs, then the scene. Multi-GPU frames are out of scope. */
+int pt_render_moments(pt_scene* scene, const pt_camera* camera, int w, int h, int spp, int batch_spp, int max_depth, int integrator,
+                      int use_mis, uint64_t seed, float* out_rgba_sum, float* out_sq_sum);              /* host buffers */
+int pt_render_moments_device(pt_scene* scene, const pt_camera* camera, int w, int h, int spp, int batch_spp, int max_depth,
+                             int integrator, int use_mis, uint64_t seed, void* d_rgba_sum, void* d_sq_sum,
+                             void* stream);                                                              /* device buffers */
+
+/* pt_denoise's a-trous filter with a variance-guided colour weight (after SVGF: Schied et al., HPG 2017). The contract is
+ * pt_denoise's except for what is listed here (p a pixel, q a tap):
+ *   B = batches (>= 2, a divisor of spp; Q.w is not read). Per rgb channel, in f32, left to right,
+ *     var_c = max(0, Q_c - S_c S_c / B) / (B - 1) * B / (spp spp)     (the variance of the pixel's MEAN; max(0, NaN) is NaN)
+ *     V_p = var_r / (a_r a_r) + var_g / (a_g a_g) + var_b / (a_b a_b)  with pt_denoise's demodulation albedo a.
+ *   p PASSES THROUGH under pt_denoise's rule, and also if V_p is NaN / Inf. Pass-through pixels are never taps (neither of
+ *   the 5x5 nor of the 3x3 below).
+ *   Iteration i (step s = 2^i): Vt_p = the 3x3 binomial ((1, 2, 1) x (1, 2, 1) / 16, stride 1) of the current V around p,
+ *   where a neighbour outside the image or pass-through contributes V_p itself;
+ *     w_c = exp(-|e_p - e_q|_2 / (sigma_var sqrt(Vt_p) + 1e-3 L + 1e-20))
+ *   (L as in pt_denoise; the second term keeps the quotient defined where the variance is 0: identical samples, e.g. inside
+ *   the emitter; the third where L is 0 as well: a black frame). w_n, w_z, h and the centre weight h(0)^2 are pt_denoise's.
+ *     e'_p = sum_q w e_q / sum_q w,   V'_p = sum_q w^2 V_q / (sum_q w)^2     (a pixel with a zero normal keeps e_p and V_p)
+ *   Output as pt_denoise: rgb = spp a_p e_p, w = S_p.w; out may alias rgba_sum; host and device form are bit-identical. */
+typedef struct pt_denoise_var_params {
+    int32_t iterations;          /* default 3: steps 1, 2, 4 (0..16) */
+    float sigma_var;             /* colour tolerance in standard deviations of the pixel's mean (> 0) */
+    float sigma_normal;          /* exponent on the normals' cosine (>= 0) */
+    float sigma_depth;           /* relative depth difference (> 0) */
+                                 /* defaults 3, 6.0, 64, 0.02: DESIGN.md "Variance buffers and the variance-guided denoiser" */
+} pt_denoise_var_params;
+void   pt_denoise_var_defaults(pt_denoise_var_params* out);
+/* device workspace of pt_denoise_var_device: pt_denoise_device's layout and size (the variance travels in the colour
+ * buffers' w): 3 * w*h float4 + 8 B per 256 pixels (rounded up to 16 B) + 16 B; 0 if w or h <= 0 */
+size_t pt_denoise_var_workspace_bytes(int w, int h);
+/* rgba_sum, sq_sum: what pt_render_moments wrote (spp samples in `batches` batches). params NULL = pt_denoise_var_defaults. */
+int pt_denoise_var(int w, int h, const float* rgba_sum, const float* sq_sum, int spp, int batches, const float* albedo,
+                   const float* normal_depth, const pt_denoise_var_params* params, float* out_rgba_sum);        /* host, blocking */
+int pt_denoise_var_device(int w, int h, const void* d_rgba_sum, const void* d_sq_sum, int spp, int batches, const void* d_albedo,
+                          const void* d_normal_depth, const pt_denoise_var_params* params, void* d_workspace, void* d_out,
+                          void* stream);                                                                          /* async */
+
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
 int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* out_exp, float* out_rsqrt, float* out_pow5);

@@ -2,13 +2,18 @@
 
     python tools/denoise_time.py [--w 1920 --h 1080 --reps 20 --aov-spp 1 --iterations 5 --scene cornell|blob]
 
-Prints one JSON line: median / min milliseconds of pt_render_aovs_device and pt_denoise_device (all iterations), and of the
-16-spp depth-8 frame the pair post-processes, for scale."""
+Prints one JSON line: median / min milliseconds of pt_render_aovs_device, of pt_denoise_device and pt_denoise_var_device (all
+iterations; --iterations sets both, otherwise the variance-guided filter is timed at the classic filter's count and at its own
+default), of the 16-spp depth-8 frame they post-process in one launch (the megakernel's device time, and the launcher's wall
+time), of the same frame as a moments render of 4 batches of 4 and of 2 batches of 8 (pt_render_moments_device: wall time, it
+blocks) and as pt_launch_progressive in 4 chunks (the same launches without the bookkeeping), and the device time of a 4-spp
+launch."""
 import argparse
 import json
 import os
 import sys
 import tempfile
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -45,13 +50,54 @@ def main():
     def aov():
         sc.render_aovs_device(cam, w, h, alb.data_ptr(), nd.data_ptr(), aov_spp=a.aov_spp, stream=stream)
 
+    iters = a.iterations or api.denoise_defaults()["iterations"]
+    iters_var = a.iterations or api.denoise_var_defaults()["iterations"]
+
     def dn():
         api.denoise_device(w, h, colors.data_ptr(), 16, alb.data_ptr(), nd.data_ptr(), ws.data_ptr(), out.data_ptr(),
-                           iterations=a.iterations, stream=stream)
+                           iterations=iters, stream=stream)
 
-    res = {"w": w, "h": h, "scene": a.scene, "aov_spp": a.aov_spp, "iterations": a.iterations or api.denoise_defaults()["iterations"],
+    sq = torch.empty(h, w, 4, device="cuda:0")
+    ws_var = torch.empty(api.denoise_var_workspace_bytes(w, h), dtype=torch.uint8, device="cuda:0")
+
+    def dn_var(n):
+        api.denoise_var_device(w, h, colors.data_ptr(), sq.data_ptr(), 16, 4, alb.data_ptr(), nd.data_ptr(), ws_var.data_ptr(), out.data_ptr(),
+                               iterations=n, stream=stream)
+
+    # the frame in one launch and as 4 batches of 4: both calls block, so wall time on the host (median of --reps after warm-up)
+    def one_launch():
+        colors.zero_()
+        sc.launch_unidirectional(8, cam, 16, True, w, h, colors.data_ptr())
+
+    def moments(c):
+        return lambda: sc.render_moments_device(cam, w, h, 16, c, 8, colors.data_ptr(), sq.data_ptr(), stream=stream)
+
+    def progressive():                                    # the same four launches without the bookkeeping
+        colors.zero_()
+        sc.launch_progressive(0, 8, cam, 16, True, w, h, colors.data_ptr(), 4)
+
+    res = {"w": w, "h": h, "scene": a.scene, "aov_spp": a.aov_spp, "iterations": iters, "iterations_var_default": iters_var,
            "frame_16spp_depth8_ms": round(frame_ms, 3)}
-    for name, fn in (("aov", aov), ("denoise", dn)):
+    colors.zero_()
+    sc.launch_unidirectional(8, cam, 4, True, w, h, colors.data_ptr())
+    res["frame_4spp_depth8_ms"] = round(sc.last_kernel_ms(), 3)       # what one batch of four costs on the device
+    for name, fn in (("frame_16spp_one_launch_wall", one_launch), ("frame_16spp_moments_4x4_wall", moments(4)),
+                     ("frame_16spp_moments_2x8_wall", moments(8)), ("frame_16spp_progressive_4x4_wall", progressive)):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        res[name + "_ms_median"] = round(ts[len(ts) // 2], 3)
+        res[name + "_ms_min"] = round(ts[0], 3)
+    moments(4)()                                          # colors, sq: the 16-spp frame in 4 batches, what the filters below read
+    timed = [("aov", aov), ("denoise", dn), ("denoise_var", lambda: dn_var(iters))]
+    if iters_var != iters:
+        timed.append(("denoise_var_default", lambda: dn_var(iters_var)))
+    for name, fn in timed:
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
