@@ -77,6 +77,10 @@ class DenoiseVarParams(C.Structure):  # pt_denoise_var_params
     _fields_ = [("iterations", C.c_int32), ("sigma_var", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class TemporalParams(C.Structure):   # pt_temporal_params
+    _fields_ = [("max_history", C.c_int32), ("depth_tol", C.c_float), ("normal_tol", C.c_float)]
+
+
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("chunk_spp", C.c_int32), ("threshold", C.c_float)]
 
@@ -183,6 +187,14 @@ def lib():
     L.pt_denoise_var_workspace_bytes.restype = C.c_size_t; L.pt_denoise_var_workspace_bytes.argtypes = [i32, i32]
     L.pt_denoise_var.argtypes = [i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(DenoiseVarParams), vp]
     L.pt_denoise_var_device.argtypes = [i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(DenoiseVarParams), vp, vp, vp]
+    L.pt_temporal_defaults.restype = None; L.pt_temporal_defaults.argtypes = [C.POINTER(TemporalParams)]
+    L.pt_temporal_accumulate.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp,
+                                         C.POINTER(TemporalParams), vp, vp]
+    L.pt_temporal_accumulate_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp,
+                                                C.POINTER(TemporalParams), vp, vp, vp]
+    L.pt_denoise_hist_workspace_bytes.restype = C.c_size_t; L.pt_denoise_hist_workspace_bytes.argtypes = [i32, i32]
+    L.pt_denoise_hist.argtypes = [i32, i32, vp, vp, vp, C.POINTER(DenoiseVarParams), vp]
+    L.pt_denoise_hist_device.argtypes = [i32, i32, vp, vp, vp, C.POINTER(DenoiseVarParams), vp, vp, vp]
     _lib = L
     return L
 
@@ -762,6 +774,121 @@ def denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albed
     p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
     _check(lib().pt_denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
                                        C.byref(p), d_workspace_ptr, d_out_ptr, stream or None), "pt_denoise_var_device")
+
+
+def temporal_defaults():
+    """pt_temporal_defaults as a dict: max_history, depth_tol, normal_tol."""
+    p = TemporalParams()
+    lib().pt_temporal_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in TemporalParams._fields_}
+
+
+def _temporal_params(max_history, depth_tol, normal_tol):
+    p = TemporalParams()
+    lib().pt_temporal_defaults(C.byref(p))
+    for f, v in (("max_history", max_history), ("depth_tol", depth_tol), ("normal_tol", normal_tol)):
+        if v is not None:
+            setattr(p, f, v)
+    return p
+
+
+def _f4_frames(what, named, shape=None):
+    """The float32 [h, w, 4] checks of denoise_var, for a list of (name, array); returns the contiguous arrays."""
+    arrs = []
+    for name, a in named:
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or a.shape[2] != 4:
+            raise PtError("%s: %s must be a float32 [h, w, 4] array" % (what, name))
+        arrs.append(np.ascontiguousarray(a))
+    shape = arrs[0].shape if shape is None else shape
+    if any(a.shape != shape for a in arrs):
+        raise PtError("%s: shapes differ: %s" % (what, ", ".join(str(a.shape) for a in arrs)))
+    return arrs
+
+
+def temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None,
+                        hist_len=None, max_history=None, depth_tol=None, normal_tol=None):
+    """pt_temporal_accumulate (host, blocking): blend this frame (render_moments' sums, render_aovs' buffers) into the history
+    reprojected from the previous camera. prev_normal_depth, hist ([h,w,4] float32) and hist_len ([h,w] float32) are all None on
+    the first frame. camera_prev None = the camera did not move. Returns new (hist, hist_len); the inputs are left untouched.
+    A None parameter takes the library default (temporal_defaults())."""
+    S, Q, A, N = _f4_frames("temporal_accumulate", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = S.shape[:2]
+    given = [x is not None for x in (prev_normal_depth, hist, hist_len)]
+    if any(given) != all(given):
+        raise PtError("temporal_accumulate: prev_normal_depth, hist and hist_len must be all None or all given")
+    PN = H = HL = None
+    if all(given):
+        PN, H = _f4_frames("temporal_accumulate", (("prev_normal_depth", prev_normal_depth), ("hist", hist)), S.shape)
+        if not isinstance(hist_len, np.ndarray) or hist_len.dtype != np.float32 or hist_len.shape != (h, w):
+            raise PtError("temporal_accumulate: hist_len must be a float32 [%d, %d] array" % (h, w))
+        HL = np.ascontiguousarray(hist_len)
+    out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q), int(spp),
+                                        int(batches), _p(A), _p(N), _p(PN), _p(H), _p(HL), C.byref(p), _p(out), _p(out_len)),
+           "pt_temporal_accumulate")
+    return out, out_len
+
+
+def temporal_accumulate_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr,
+                               d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_out_hist_ptr, d_out_hist_len_ptr, max_history=None,
+                               depth_tol=None, normal_tol=None, stream=0):
+    """pt_temporal_accumulate_device: device buffers (w*h float4; the two lengths w*h float), asynchronous on `stream`, no
+    workspace. The three history pointers are 0 / None on the first frame; the outputs must not alias the input history."""
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, d_rgba_sum_ptr,
+                                               d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
+                                               d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None, C.byref(p),
+                                               d_out_hist_ptr, d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_device")
+
+
+def denoise_hist_workspace_bytes(w, h):
+    return int(lib().pt_denoise_hist_workspace_bytes(w, h))
+
+
+def denoise_hist(hist, albedo, normal_depth, iterations=None, sigma_var=None, sigma_normal=None, sigma_depth=None, out=None):
+    """pt_denoise_hist (host, blocking): denoise_var's filter on a history buffer of temporal_accumulate, guided by the current
+    frame's albedo and normal_depth. Returns the per-pixel radiance MEAN ([h,w,4] float32, w = 0): finalise(..., 1) applies.
+    `out` may be hist itself."""
+    H, A, N = _f4_frames("denoise_hist", (("hist", hist), ("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = H.shape[:2]
+    res = np.empty_like(H) if out is None else out
+    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == H.shape and res.flags.c_contiguous):
+        raise PtError("denoise_hist: out must be a C-contiguous float32 array of shape %s" % (H.shape,))
+    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_hist(w, h, _p(H), _p(A), _p(N), C.byref(p), _p(res)), "pt_denoise_hist")
+    return res
+
+
+def denoise_hist_device(w, h, d_hist_ptr, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr, d_out_ptr, iterations=None, sigma_var=None,
+                        sigma_normal=None, sigma_depth=None, stream=0):
+    """pt_denoise_hist_device: device buffers of w*h float4 and a workspace of denoise_hist_workspace_bytes(w, h) bytes;
+    asynchronous on `stream`. d_out_ptr may equal d_hist_ptr."""
+    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_hist_device(w, h, d_hist_ptr, d_albedo_ptr, d_normal_depth_ptr, C.byref(p), d_workspace_ptr, d_out_ptr, stream or None),
+           "pt_denoise_hist_device")
+
+
+class TemporalHistory:
+    """Host-side history of a w x h viewer: push() one frame after the other, each with the camera it was rendered with."""
+
+    def __init__(self, w, h, max_history=None, depth_tol=None, normal_tol=None):
+        self.w, self.h = w, h
+        self.params = dict(max_history=max_history, depth_tol=depth_tol, normal_tol=normal_tol)
+        self.reset()
+
+    def reset(self):
+        self.camera = self.normal_depth = self.hist = self.hist_len = None
+
+    def push(self, camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth):
+        """Blend the frame into the history; returns the current hist (pass it to denoise_hist with this frame's buffers)."""
+        if rgba_sum.shape != (self.h, self.w, 4):
+            raise PtError("TemporalHistory: frame is %s, the history %d x %d" % (rgba_sum.shape, self.w, self.h))
+        self.hist, self.hist_len = temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, self.camera,
+                                                       self.normal_depth, self.hist, self.hist_len, **self.params)
+        self.camera = Camera.frombytes(camera.tobytes())
+        self.normal_depth = normal_depth.copy()
+        return self.hist
 
 
 def adaptive_params(min_spp, max_spp, chunk_spp, threshold):

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
+#include "pt_denoise_shared.h"
 
 extern "C" int pt_fail_(int code, const char* msg);
 
@@ -43,9 +44,6 @@ static DnLayout dn_layout(int w, int h) {
     L.total = L.lum + 16;
     return L;
 }
-
-__device__ inline bool finite3(float4 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
-__device__ inline float demod_albedo(float a) { return a >= 0.01f ? a : 1.0f; }
 
 __global__ void __launch_bounds__(kDnBlock) denoise_prepare_kernel(int n, const float4* __restrict__ sum, float spp, const float4* __restrict__ albedo,
                                                                    const float4* __restrict__ nd, float4* __restrict__ e, float4* __restrict__ guide,
@@ -158,22 +156,11 @@ __global__ void __launch_bounds__(kDnBlock) denoise_var_prepare_kernel(int n, co
     const int i = blockIdx.x * kDnBlock + threadIdx.x;
     float lum = 0.0f, cnt = 0.0f;
     if (i < n) {
-        const float4 s = sum[i], q = sq[i], a = albedo[i], g = nd[i];
-        const float4 m = make_float4(s.x / spp, s.y / spp, s.z / spp, s.w / spp);
-        const float ax = demod_albedo(a.x), ay = demod_albedo(a.y), az = demod_albedo(a.z);
-        // var_c = max(0, Q_c - S_c^2 / B) / (B - 1) * B / spp^2, left to right; max(0, x) keeps a NaN
-        const float spp2 = spp * spp;
-        float vx = q.x - s.x * s.x / batches, vy = q.y - s.y * s.y / batches, vz = q.z - s.z * s.z / batches;
-        vx = (vx < 0.0f ? 0.0f : vx) / (batches - 1.0f) * batches / spp2;
-        vy = (vy < 0.0f ? 0.0f : vy) / (batches - 1.0f) * batches / spp2;
-        vz = (vz < 0.0f ? 0.0f : vz) / (batches - 1.0f) * batches / spp2;
-        const float V = vx / (ax * ax) + vy / (ay * ay) + vz / (az * az);
-        const bool filtered = a.w > 0.0f && finite3(m) && __builtin_isfinite(V);
-        const float4 ev = make_float4(m.x / ax, m.y / ay, m.z / az, filtered ? V : -1.0f);
+        float4 m;
+        const float4 ev = dn_var_pixel(sum[i], sq[i], albedo[i], spp, batches, m);
         e[i] = ev;
-        const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
-        guide[i] = len > 0.0f ? make_float4(g.x / len, g.y / len, g.z / len, g.w) : make_float4(0.0f, 0.0f, 0.0f, g.w);
-        if (filtered) { lum = 0.2126f * ev.x + 0.7152f * ev.y + 0.0722f * ev.z; cnt = 1.0f; }
+        guide[i] = dn_unit_guide(nd[i]);
+        if (ev.w >= 0.0f) { lum = 0.2126f * ev.x + 0.7152f * ev.y + 0.0722f * ev.z; cnt = 1.0f; }
     }
     sLum[threadIdx.x] = lum; sCnt[threadIdx.x] = cnt;
     __syncthreads();
@@ -252,6 +239,45 @@ __global__ void __launch_bounds__(kDnBlock) denoise_var_finish_kernel(int n, con
     if (ev.w < 0.0f) { out[i] = s; return; }
     const float4 a = albedo[i];
     out[i] = make_float4(spp * (demod_albedo(a.x) * ev.x), spp * (demod_albedo(a.y) * ev.y), spp * (demod_albedo(a.z) * ev.z), s.w);
+}
+
+// ---- pt_denoise_hist: pt_denoise_var's filter on a history buffer of pt_temporal_accumulate (include/pt_api.h) -------------------
+// (e, V) come from `hist` instead of S and Q; denoise_reduce_kernel and denoise_var_iter_kernel run unchanged on the same workspace.
+//
+//   denoise_hist_prepare_kernel   copy hist into the working buffer (a pixel whose e or V is not finite is marked pass-through
+//                                 there), the normalised guide, the luminance partials
+//   denoise_hist_finish_kernel    out = (a e, 0): the radiance MEAN; a pass-through pixel returns its hist.rgb
+__global__ void __launch_bounds__(kDnBlock) denoise_hist_prepare_kernel(int n, const float4* __restrict__ hist, const float4* __restrict__ nd,
+                                                                        float4* __restrict__ e, float4* __restrict__ guide,
+                                                                        float2* __restrict__ partials) {
+    __shared__ float sLum[kDnBlock], sCnt[kDnBlock];
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    float lum = 0.0f, cnt = 0.0f;
+    if (i < n) {
+        float4 ev = hist[i];
+        const bool filtered = ev.w >= 0.0f && __builtin_isfinite(ev.w) && finite3(ev);
+        if (!filtered) ev.w = -1.0f;
+        e[i] = ev;
+        guide[i] = dn_unit_guide(nd[i]);
+        if (filtered) { lum = 0.2126f * ev.x + 0.7152f * ev.y + 0.0722f * ev.z; cnt = 1.0f; }
+    }
+    sLum[threadIdx.x] = lum; sCnt[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int k = kDnBlock / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) { sLum[threadIdx.x] += sLum[threadIdx.x + k]; sCnt[threadIdx.x] += sCnt[threadIdx.x + k]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = make_float2(sLum[0], sCnt[0]);
+}
+
+__global__ void __launch_bounds__(kDnBlock) denoise_hist_finish_kernel(int n, const float4* __restrict__ albedo, const float4* __restrict__ e,
+                                                                       float4* __restrict__ out) {
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 ev = e[i];
+    if (ev.w < 0.0f) { out[i] = make_float4(ev.x, ev.y, ev.z, 0.0f); return; }
+    const float4 a = albedo[i];
+    out[i] = make_float4(demod_albedo(a.x) * ev.x, demod_albedo(a.y) * ev.y, demod_albedo(a.z) * ev.z, 0.0f);
 }
 
 static int dn_fail(int code, const char* fmt, int a = 0, int b = 0) {
@@ -342,6 +368,40 @@ static int denoise_var_launch(int w, int h, const float4* in, const float4* sq, 
         DN_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_var_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
+    DN_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int check_denoise_hist_args(int w, int h, const void* hist, const void* albedo, const void* nd, const pt_denoise_var_params& P, const void* out) {
+    if (w <= 0 || h <= 0) return dn_fail(-1, "pt_denoise_hist: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return dn_fail(-1, "pt_denoise_hist: image of %d x %d pixels is too large", w, h);
+    if (!hist || !albedo || !nd || !out) return dn_fail(-1, "pt_denoise_hist: null buffer");
+    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return dn_fail(-1, "pt_denoise_hist: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
+    if (!(P.sigma_var > 0.0f) || !std::isfinite(P.sigma_var)) return dn_fail(-1, "pt_denoise_hist: sigma_var must be positive and finite");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return dn_fail(-1, "pt_denoise_hist: sigma_normal must be >= 0 and finite");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return dn_fail(-1, "pt_denoise_hist: sigma_depth must be positive and finite");
+    return 0;
+}
+
+static int denoise_hist_launch(int w, int h, const float4* hist, const float4* albedo, const float4* nd, const pt_denoise_var_params& P, char* ws,
+                               float4* out, hipStream_t stream) {
+    const DnLayout L = dn_layout(w, h);
+    float4* e[2] = {(float4*)(ws + L.e0), (float4*)(ws + L.e1)};
+    float4* guide = (float4*)(ws + L.guide);
+    float2* partials = (float2*)(ws + L.partials);
+    float4* lum = (float4*)(ws + L.lum);
+    const int n = (int)L.n;
+    hipLaunchKernelGGL(denoise_hist_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, hist, nd, e[0], guide, partials);
+    DN_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
+    DN_HIP_OK(hipGetLastError());
+    const dim3 grid((w + 15) / 16, (h + 15) / 16);
+    for (int i = 0; i < P.iterations; i++) {
+        hipLaunchKernelGGL(denoise_var_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, P.sigma_var, P.sigma_normal, P.sigma_depth, lum,
+                           e[i & 1], guide, e[(i + 1) & 1]);
+        DN_HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(denoise_hist_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, albedo, e[P.iterations & 1], out);
     DN_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -446,6 +506,46 @@ int pt_denoise_var(int w, int h, const float* rgba_sum, const float* sq_sum, int
                                        (float4*)dIn, nullptr)) == 0) {
         e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_var: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+size_t pt_denoise_hist_workspace_bytes(int w, int h) {
+    if (w <= 0 || h <= 0) return 0;
+    return dn_layout(w, h).total;
+}
+
+int pt_denoise_hist_device(int w, int h, const void* d_hist, const void* d_albedo, const void* d_normal_depth, const pt_denoise_var_params* params,
+                           void* d_workspace, void* d_out, void* stream) {
+    pt_denoise_var_params P;
+    if (params) P = *params; else pt_denoise_var_defaults(&P);
+    if (int r = check_denoise_hist_args(w, h, d_hist, d_albedo, d_normal_depth, P, d_out)) return r;
+    if (!d_workspace) return pt_fail_(-1, "pt_denoise_hist_device: null workspace");
+    return denoise_hist_launch(w, h, (const float4*)d_hist, (const float4*)d_albedo, (const float4*)d_normal_depth, P, (char*)d_workspace,
+                               (float4*)d_out, (hipStream_t)stream);
+}
+
+int pt_denoise_hist(int w, int h, const float* hist, const float* albedo, const float* normal_depth, const pt_denoise_var_params* params,
+                    float* out_rgba_mean) {
+    pt_denoise_var_params P;
+    if (params) P = *params; else pt_denoise_var_defaults(&P);
+    if (int r = check_denoise_hist_args(w, h, hist, albedo, normal_depth, P, out_rgba_mean)) return r;
+    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total;
+    char* d = nullptr;
+    DN_HIP_OK(hipMalloc(&d, ws + 3 * bytes));
+    char* dH = d + ws;                       // hist and out share one buffer (out may alias hist)
+    char* dA = dH + bytes;
+    char* dN = dA + bytes;
+    hipError_t e = hipMemcpy(dH, hist, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = dn_fail(-2, "pt_denoise_hist: upload failed");
+    } else if ((r = denoise_hist_launch(w, h, (const float4*)dH, (const float4*)dA, (const float4*)dN, P, d, (float4*)dH, nullptr)) == 0) {
+        e = hipMemcpy(out_rgba_mean, dH, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_hist: download failed");
     }
     (void)hipFree(d);
     return r;

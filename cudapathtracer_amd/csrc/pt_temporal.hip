@@ -1,0 +1,251 @@
+// pt_temporal.hip — temporal accumulation with reprojection (the history stage of SVGF: Schied et al., HPG 2017) on the
+// albedo-demodulated mean and its variance, in pt_denoise_var's working format. include/pt_api.h states the arithmetic;
+// tests/temporal_ref.py restates it in numpy. Opt-in post-process on buffers: stateless, no workspace, no render path involved.
+//
+//   temporal_accumulate_kernel<IDENT>   one thread per pixel, 16x16 pixels per workgroup as four 8x8 tiles (one per wave, the
+//                                       tiling of denoise_var_iter_kernel: a wave's four gathers fall into a few lines).
+//                                       This frame's (e, V) from S and Q (dn_var_pixel, shared with denoise_var_prepare_kernel);
+//                                       the pixel's world point from its depth along the unjittered centre ray, projected into
+//                                       the previous camera; up to four bilinear taps of the previous history, each checked
+//                                       against the previous guide; the blend. IDENT: both cameras are the same bytes, the tap
+//                                       is the pixel itself and no projection is computed.
+// Both cameras travel by value as kernel arguments (SGPRs); plain cached float4 loads, no LDS.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/pt_api.h"
+#include "pt_denoise_shared.h"
+
+extern "C" int pt_fail_(int code, const char* msg);
+
+namespace pt {
+
+struct TemporalCam {                      // what the projection reads of a pt_camera
+    float ox, oy, oz, fovScale;
+    float fx, fy, fz, aspect;             // aspect = (float)w / (float)h, as camera_ray computes it
+    float rx, ry, rz, pad0;
+    float ux, uy, uz, pad1;
+};
+
+static TemporalCam temporal_cam(const pt_camera& c) {
+    TemporalCam t;
+    t.ox = c.cameraOrigin.x; t.oy = c.cameraOrigin.y; t.oz = c.cameraOrigin.z; t.fovScale = c.fovScale;
+    t.fx = c.forward.x; t.fy = c.forward.y; t.fz = c.forward.z; t.aspect = (float)c.w / (float)c.h;
+    t.rx = c.right.x; t.ry = c.right.y; t.rz = c.right.z; t.pad0 = 0.0f;
+    t.ux = c.up.x; t.uy = c.up.y; t.uz = c.up.z; t.pad1 = 0.0f;
+    return t;
+}
+
+struct TemporalTap {
+    float se_x, se_y, se_z, sv, sn, sw;   // sums over the valid taps of w e, w V, w N and w
+};
+
+// One tap of the previous history at (xq, yq) with bilinear weight wt: valid inside the image, not pass-through, at the
+// expected depth and with a matching unit normal. An invalid tap is skipped, never multiplied by 0 (its values may be NaN).
+__device__ inline void temporal_tap(TemporalTap& t, int w, int h, int xq, int yq, float wt, float4 gp, float zExp, float depthTol, float normalTol,
+                                    const float4* __restrict__ prevNd, const float4* __restrict__ hist, const float* __restrict__ histLen) {
+    if (xq < 0 || xq >= w || yq < 0 || yq >= h) return;
+    const size_t q = (size_t)yq * w + xq;
+    const float4 hq = hist[q];
+    if (!(hq.w >= 0.0f)) return;
+    const float4 gq = dn_unit_guide(prevNd[q]);
+    if (!(fabsf(gq.w - zExp) <= depthTol * zExp)) return;
+    if (gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f) return;
+    if (!(gp.x * gq.x + gp.y * gq.y + gp.z * gq.z >= normalTol)) return;
+    t.se_x += wt * hq.x; t.se_y += wt * hq.y; t.se_z += wt * hq.z;
+    t.sv += wt * hq.w;
+    t.sn += wt * histLen[q];
+    t.sw += wt;
+}
+
+template <bool IDENT>
+__global__ void __launch_bounds__(256) temporal_accumulate_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ sum,
+                                                                  const float4* __restrict__ sq, float spp, float batches,
+                                                                  const float4* __restrict__ albedo, const float4* __restrict__ nd,
+                                                                  const float4* __restrict__ prevNd, const float4* __restrict__ hist,
+                                                                  const float* __restrict__ histLen, float maxHistory, float depthTol,
+                                                                  float normalTol, float4* __restrict__ outHist, float* __restrict__ outLen) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    float4 m;
+    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
+    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
+    float4 res = cur;
+    float len = 1.0f;
+    if (hist != nullptr) {                                    // (uniform: a kernel argument)
+        const float4 gp = dn_unit_guide(nd[p]);
+        const bool normalP = gp.x != 0.0f || gp.y != 0.0f || gp.z != 0.0f;
+        TemporalTap t = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (IDENT) {
+            if (normalP) temporal_tap(t, w, h, x, y, 1.0f, gp, gp.w, depthTol, normalTol, prevNd, hist, histLen);
+        } else if (normalP) {
+            // the unjittered centre ray of the pixel (camera_ray with both jitters 0 and no lens sample), to the depth z_p
+            const float u = (2.0f * ((float)x / (float)w) - 1.0f) * cam.aspect * cam.fovScale;
+            const float v = (2.0f * ((float)y / (float)h) - 1.0f) * cam.fovScale;
+            const float tx = cam.rx * u + cam.ux * v + cam.fx, ty = cam.ry * u + cam.uy * v + cam.fy, tz = cam.rz * u + cam.uz * v + cam.fz;
+            const float tl = sqrtf(tx * tx + ty * ty + tz * tz);
+            const float px = cam.ox + tx / tl * gp.w, py = cam.oy + ty / tl * gp.w, pz = cam.oz + tz / tl * gp.w;
+            // ... seen from the previous camera
+            const float qx = px - prev.ox, qy = py - prev.oy, qz = pz - prev.oz;
+            const float zc = qx * prev.fx + qy * prev.fy + qz * prev.fz;
+            if (zc > 0.0f) {
+                const float fs = prev.aspect * prev.fovScale;
+                const float xp = (((qx * prev.rx + qy * prev.ry + qz * prev.rz) / zc) / fs + 1.0f) * (float)w / 2.0f;
+                const float yp = (((qx * prev.ux + qy * prev.uy + qz * prev.uz) / zc) / prev.fovScale + 1.0f) * (float)h / 2.0f;
+                const float zExp = sqrtf(qx * qx + qy * qy + qz * qz);
+                // outside [-1, w) x [-1, h) (or NaN) no tap is inside the image; inside, the conversions to int are safe
+                if (xp >= -1.0f && xp < (float)w && yp >= -1.0f && yp < (float)h) {
+                    const float x0 = floorf(xp), y0 = floorf(yp);
+                    const float ax = xp - x0, ay = yp - y0;
+                    const int xi = (int)x0, yi = (int)y0;
+                    temporal_tap(t, w, h, xi, yi, (1.0f - ax) * (1.0f - ay), gp, zExp, depthTol, normalTol, prevNd, hist, histLen);
+                    temporal_tap(t, w, h, xi + 1, yi, ax * (1.0f - ay), gp, zExp, depthTol, normalTol, prevNd, hist, histLen);
+                    temporal_tap(t, w, h, xi, yi + 1, (1.0f - ax) * ay, gp, zExp, depthTol, normalTol, prevNd, hist, histLen);
+                    temporal_tap(t, w, h, xi + 1, yi + 1, ax * ay, gp, zExp, depthTol, normalTol, prevNd, hist, histLen);
+                }
+            }
+        }
+        if (t.sw >= 0.01f) {
+            const float ehx = t.se_x / t.sw, ehy = t.se_y / t.sw, ehz = t.se_z / t.sw, vh = t.sv / t.sw, nh = t.sn / t.sw;
+            const float n1 = nh + 1.0f;
+            len = n1 < maxHistory ? n1 : maxHistory;
+            const float alpha = 1.0f / len, keep = 1.0f - alpha;
+            res = make_float4(ehx + alpha * (cur.x - ehx), ehy + alpha * (cur.y - ehy), ehz + alpha * (cur.z - ehz),
+                              (keep * keep) * vh + (alpha * alpha) * cur.w);
+        }
+    }
+    outHist[p] = res;
+    outLen[p] = len;
+}
+
+static int tp_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), fmt, a, b, c, d);
+    return pt_fail_(code, buf);
+}
+#define TP_HIP_OK(expr)                                                                                            \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) {                                                                                    \
+            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
+            return pt_fail_(-2, m_);                                                                               \
+        }                                                                                                          \
+    } while (0)
+
+static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
+    const char* pa = (const char*)a; const char* pb = (const char*)b;
+    return pa < pb + bBytes && pb < pa + aBytes;
+}
+
+static int check_temporal_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* sum, const void* sq, int spp, int batches,
+                               const void* albedo, const void* nd, const void* prevNd, const void* hist, const void* histLen,
+                               const pt_temporal_params& P, const void* outHist, const void* outLen) {
+    if (w <= 0 || h <= 0) return tp_fail(-1, "pt_temporal_accumulate: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return tp_fail(-1, "pt_temporal_accumulate: image of %d x %d pixels is too large", w, h);
+    if (spp <= 0) return tp_fail(-1, "pt_temporal_accumulate: spp %d must be positive", spp);
+    if (batches < 2) return tp_fail(-1, "pt_temporal_accumulate: batches %d must be at least 2", batches);
+    if (spp % batches != 0) return tp_fail(-1, "pt_temporal_accumulate: batches %d must divide spp %d", batches, spp);
+    if (!cam) return tp_fail(-1, "pt_temporal_accumulate: null camera");
+    if (cam->w != w || cam->h != h) return tp_fail(-1, "pt_temporal_accumulate: camera is %d x %d, the frame %d x %d", cam->w, cam->h, w, h);
+    if (prev && (prev->w != w || prev->h != h))
+        return tp_fail(-1, "pt_temporal_accumulate: previous camera is %d x %d, the frame %d x %d", prev->w, prev->h, w, h);
+    if (!sum || !sq || !albedo || !nd) return tp_fail(-1, "pt_temporal_accumulate: null buffer");
+    if (!outHist || !outLen) return tp_fail(-1, "pt_temporal_accumulate: null output");
+    const int given = (prevNd != nullptr) + (hist != nullptr) + (histLen != nullptr);
+    if (given != 0 && given != 3)
+        return tp_fail(-1, "pt_temporal_accumulate: prev_normal_depth, hist and hist_len must be all NULL (first frame) or all set");
+    if (given == 3) {
+        const size_t n = (size_t)w * h;
+        if (overlaps(outHist, n * 16, hist, n * 16) || overlaps(outLen, n * 4, histLen, n * 4) || overlaps(outHist, n * 16, histLen, n * 4) ||
+            overlaps(outLen, n * 4, hist, n * 16))
+            return tp_fail(-1, "pt_temporal_accumulate: the output history must not alias the input history (ping-pong two pairs)");
+    }
+    if (P.max_history < 1) return tp_fail(-1, "pt_temporal_accumulate: max_history %d must be at least 1", P.max_history);
+    if (!(P.depth_tol > 0.0f) || !std::isfinite(P.depth_tol)) return tp_fail(-1, "pt_temporal_accumulate: depth_tol must be positive and finite");
+    if (!(P.normal_tol > 0.0f) || !(P.normal_tol <= 1.0f)) return tp_fail(-1, "pt_temporal_accumulate: normal_tol must be in (0, 1]");
+    return 0;
+}
+
+static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* sum, const float4* sq, int spp, int batches,
+                           const float4* albedo, const float4* nd, const float4* prevNd, const float4* hist, const float* histLen,
+                           const pt_temporal_params& P, float4* outHist, float* outLen, hipStream_t stream) {
+    const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
+    const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
+    const dim3 grid((w + 15) / 16, (h + 15) / 16);
+    if (ident)
+        hipLaunchKernelGGL(temporal_accumulate_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
+                           prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else
+        hipLaunchKernelGGL(temporal_accumulate_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
+                           prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    TP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace pt
+
+using namespace pt;
+
+extern "C" {
+
+void pt_temporal_defaults(pt_temporal_params* out) {
+    if (!out) return;
+    out->max_history = 32;
+    out->depth_tol = 0.10f;
+    out->normal_tol = 0.9f;
+}
+
+int pt_temporal_accumulate_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum, const void* d_sq_sum, int spp,
+                                  int batches, const void* d_albedo, const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist,
+                                  const void* d_hist_len, const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len, void* stream) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_args(w, h, cam, cam_prev, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, d_prev_normal_depth, d_hist,
+                                    d_hist_len, P, d_out_hist, d_out_hist_len))
+        return r;
+    return temporal_launch(w, h, cam, cam_prev, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
+                           (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth, (const float4*)d_hist, (const float*)d_hist_len, P,
+                           (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream);
+}
+
+int pt_temporal_accumulate(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
+                           int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
+                           const float* hist_len, const pt_temporal_params* params, float* out_hist, float* out_hist_len) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
+                                    out_hist, out_hist_len))
+        return r;
+    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
+    const bool first = hist == nullptr;
+    char* d = nullptr;
+    TP_HIP_OK(hipMalloc(&d, 7 * b16 + 2 * b4));
+    char* dS = d; char* dQ = dS + b16; char* dA = dQ + b16; char* dN = dA + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16;
+    char* dHL = dO + b16; char* dOL = dHL + b4;
+    hipError_t e = hipMemcpy(dS, rgba_sum, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, albedo, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = tp_fail(-2, "pt_temporal_accumulate: upload failed");
+    } else if ((r = temporal_launch(w, h, cam, cam_prev, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN,
+                                    first ? nullptr : (const float4*)dPN, first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P,
+                                    (float4*)dO, (float*)dOL, nullptr)) == 0) {
+        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = tp_fail(-2, "pt_temporal_accumulate: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+}  // extern "C"

@@ -431,6 +431,73 @@ int pt_denoise_var_device(int w, int h, const void* d_rgba_sum, const void* d_sq
                           const void* d_normal_depth, const pt_denoise_var_params* params, void* d_workspace, void* d_out,
                           void* stream);                                                                          /* async */
 
+/* ---- temporal accumulation with reprojection (the history stage of SVGF: Schied et al., HPG 2017) ------------------
+ * Two opt-in post-processes on buffers, stateless like pt_denoise*: the caller keeps the history between frames. The scene is
+ * static; only the camera moves. One sample count per frame is assumed: the history length N counts FRAMES, not samples.
+ *
+ * The history: hist is w*h float4 = (e.r, e.g, e.b, V) in pt_denoise_var's working format: e the albedo-demodulated mean
+ * radiance, V the variance of that mean; V = -1 marks a PASS-THROUGH pixel, whose rgb holds the raw mean m. hist_len is w*h
+ * float: the number of frames blended into the pixel, 0 = none.
+ *
+ * pt_temporal_accumulate, per pixel p = (x, y) of this frame. All arithmetic is f32 with IEEE rounding (division and sqrtf
+ * included) and no contraction, left to right:
+ *   1. This frame: m, a, e_cur, V_cur and the pass-through rule are pt_denoise_var's from (S, Q, spp, batches, albedo). A
+ *      pass-through pixel writes (m.rgb, -1) and length 0.
+ *   2. No history given (prev_normal_depth, hist, hist_len all NULL: the first frame): write (e_cur, V_cur) and length 1.
+ *   3. Reprojection. The unjittered ray of pixel x passes through x, not x + 0.5 (camera_ray's jitter is centred on 0). With
+ *      cam's fields and aspect = (float)w / (float)h:
+ *        u = (2 (x / w) - 1) aspect fovScale,  v = (2 (y / h) - 1) fovScale,  t = right u + up v + forward,
+ *        d = t / sqrtf(t . t),  P = origin + d z_p   with z_p = normal_depth_p.w.
+ *      With cam_prev's fields (primed): q = P - origin', z_c = q . forward'; unless z_c > 0 the pixel has no history;
+ *        x' = ((q . right' / z_c) / (aspect' fovScale') + 1) w / 2,  y' = ((q . up' / z_c) / fovScale' + 1) h / 2,
+ *      and the expected previous depth is z' = sqrtf(q . q). The thin-lens camera uses the same centre ray: its lens sample is
+ *      ignored (the feature buffers' depth belongs to a ray from the lens, so history is rejected more often out of focus).
+ *      IDENTITY: if cam_prev is NULL or its 112 bytes equal cam's, then x' = x, y' = y, z' = z_p exactly and the only tap is
+ *      (x, y) with weight 1: a still camera does not depend on rounding in the projection.
+ *   4. Taps k = (floor(x') + {0, 1}, floor(y') + {0, 1}) in the order (0,0), (1,0), (0,1), (1,1), with the bilinear weights
+ *      (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy, fx = x' - floor(x'). A tap is VALID if it is inside the image,
+ *      hist_k.w >= 0, |z_prev(k) - z'| <= depth_tol z', and n_p . n_prev(k) >= normal_tol on the normals of normal_depth and
+ *      prev_normal_depth normalised as pt_denoise normalises them (a zero normal on either side: invalid). Invalid taps are
+ *      skipped, never weighted by 0. W = sum of the weights of the valid taps. W < 0.01: no history. Otherwise e_h, V_h, N_h =
+ *      (sum of weight times the tap's e, V, hist_len) / W.
+ *   5. Blend: N = min(N_h + 1, max_history), alpha = 1 / N, e = e_h + alpha (e_cur - e_h),
+ *      V = ((1 - alpha) (1 - alpha)) V_h + (alpha alpha) V_cur   (a blend of independent estimates; every frame brings its own
+ *      variance from pt_render_moments). Write (e, V) and N. With no history: (e_cur, V_cur) and length 1.
+ * out_hist / out_hist_len must not overlap hist / hist_len (the gather reads neighbours): rejected with -1; a viewer
+ * ping-pongs two pairs. Arguments are checked before any HIP call: image size, spp, batches (>= 2, a divisor of spp), NULL
+ * camera, camera (and cam_prev) w / h equal to w / h, NULL buffers and outputs, the three history pointers all NULL or all
+ * set, aliasing, params. Host and device form are bit-identical; the device form needs no workspace.
+ * Multi-GPU frames: accumulate after the gather, as for the denoisers. */
+typedef struct pt_temporal_params {
+    int32_t max_history;         /* N is capped here: alpha never falls below 1 / max_history (>= 1) */
+    float depth_tol;             /* relative depth difference a tap may have (> 0, finite) */
+    float normal_tol;            /* smallest cosine between the unit normals (0 < normal_tol <= 1) */
+                                 /* defaults 32, 0.10, 0.9: DESIGN.md "Temporal accumulation" */
+} pt_temporal_params;
+void pt_temporal_defaults(pt_temporal_params* out);
+/* rgba_sum, sq_sum: this frame's pt_render_moments (spp samples in `batches` batches); albedo, normal_depth: this frame's
+ * pt_render_aovs; prev_normal_depth: the previous frame's normal_depth. params NULL = pt_temporal_defaults. */
+int pt_temporal_accumulate(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum,
+                           int spp, int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth,
+                           const float* hist, const float* hist_len, const pt_temporal_params* params, float* out_hist,
+                           float* out_hist_len);                                                                 /* host, blocking */
+int pt_temporal_accumulate_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum,
+                                  const void* d_sq_sum, int spp, int batches, const void* d_albedo, const void* d_normal_depth,
+                                  const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len,
+                                  const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len, void* stream);  /* async */
+
+/* pt_denoise_var's filter on a history buffer: the contract is pt_denoise_var's from its prepare stage on, with (e_p, V_p)
+ * read from hist instead of derived from S and Q. p PASSES THROUGH if hist_p.w < 0 or any of hist_p is NaN / Inf; pass-through
+ * pixels are never taps. albedo and normal_depth are the current frame's. Output: the per-pixel radiance MEAN, rgb = a_p e_p
+ * with the last iteration's e_p, w = 0; a pass-through pixel returns hist_p.rgb bit for bit (w = 0), so novum_finalise(.., 1)
+ * paints NaN / Inf as before. The history itself stays unfiltered: feeding a filtered iteration back into it, as SVGF does, is
+ * out of scope. out may alias hist. Workspace: pt_denoise_var_device's size and layout. params NULL = pt_denoise_var_defaults. */
+size_t pt_denoise_hist_workspace_bytes(int w, int h);
+int pt_denoise_hist(int w, int h, const float* hist, const float* albedo, const float* normal_depth,
+                    const pt_denoise_var_params* params, float* out_rgba_mean);                                  /* host, blocking */
+int pt_denoise_hist_device(int w, int h, const void* d_hist, const void* d_albedo, const void* d_normal_depth,
+                           const pt_denoise_var_params* params, void* d_workspace, void* d_out, void* stream);   /* async */
+
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
 int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* out_exp, float* out_rsqrt, float* out_pow5);

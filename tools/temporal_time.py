@@ -1,0 +1,88 @@
+"""Device time of temporal accumulation and of the history filter at 1920x1080 (HIP events around each, after warm-up).
+
+    python tools/temporal_time.py [--w 1920 --h 1080 --reps 20]
+
+Prints one JSON line: median / min milliseconds of pt_temporal_accumulate_device for a still camera (the identity instantiation)
+and for a moving one (projection and four taps), of pt_denoise_hist_device at its default iterations and, in the same run for
+comparison, of pt_denoise_var_device at its defaults; the bytes the accumulate pass moves per pixel (64 B of this frame's four
+buffers, 20 B written, plus the previous guide, history and length once: 36 B, the gathers of neighbouring pixels share their
+lines) and the fraction of the 8 TB/s HBM peak that makes at the measured time."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BYTES_PER_PIXEL = 64 + 36 + 20
+HBM_PEAK = 8.0e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--w", type=int, default=1920)
+    ap.add_argument("--h", type=int, default=1080)
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    import torch
+    from cudapathtracer_amd import api, scenes
+    if not torch.cuda.is_available():
+        raise SystemExit("temporal_time.py needs a HIP device")
+    torch.cuda.set_device(0)
+    w, h = a.w, a.h
+    hs = api.HostScene(scenes.cornell(tempfile.mkdtemp(), width=w, height=h, spp=4, max_depth=8, name="tt")["config"])
+    sc = api.Scene(hs)
+    cam0 = api.make_camera(True, (0.0, 0.0, 1.0), (0.0, 0.0, 0.0), 60.0, w, h)
+    cam1 = api.make_camera(True, (0.03, 0.01, 1.0), (0.0, 0.8, 0.0), 60.0, w, h)
+    stream = torch.cuda.current_stream().cuda_stream
+    buf = lambda: torch.empty(h, w, 4, device="cuda:0")
+
+    def frame(cam, seed):
+        S, Q, A, N = buf(), buf(), buf(), buf()
+        sc.render_moments_device(cam, w, h, 4, 2, 8, S.data_ptr(), Q.data_ptr(), seed=seed, stream=stream)
+        sc.render_aovs_device(cam, w, h, A.data_ptr(), N.data_ptr(), seed=seed, stream=stream)
+        return S, Q, A, N
+
+    f0, f_still, f_moved = frame(cam0, 1), frame(cam0, 2), frame(cam1, 2)
+    hist0, hist1 = buf(), buf()
+    len0, len1 = torch.empty(h, w, device="cuda:0"), torch.empty(h, w, device="cuda:0")
+    ws = torch.empty(api.denoise_hist_workspace_bytes(w, h), dtype=torch.uint8, device="cuda:0")
+    out = buf()
+    p = lambda t: t.data_ptr()
+    api.temporal_accumulate_device(w, h, cam0, None, p(f0[0]), p(f0[1]), 4, 2, p(f0[2]), p(f0[3]), 0, 0, 0, p(hist0), p(len0), stream=stream)
+
+    def accumulate(cam, f):
+        return lambda: api.temporal_accumulate_device(w, h, cam, cam0, p(f[0]), p(f[1]), 4, 2, p(f[2]), p(f[3]), p(f0[3]), p(hist0), p(len0),
+                                                      p(hist1), p(len1), stream=stream)
+
+    def dn_hist():
+        api.denoise_hist_device(w, h, p(hist1), p(f_moved[2]), p(f_moved[3]), p(ws), p(out), stream=stream)
+
+    def dn_var():
+        api.denoise_var_device(w, h, p(f_moved[0]), p(f_moved[1]), 4, 2, p(f_moved[2]), p(f_moved[3]), p(ws), p(out), stream=stream)
+
+    res = {"w": w, "h": h, "iterations_default": api.denoise_var_defaults()["iterations"], "accumulate_bytes_per_pixel": BYTES_PER_PIXEL}
+    for name, fn in (("accumulate_identity", accumulate(cam0, f_still)), ("accumulate_moving", accumulate(cam1, f_moved)),
+                     ("denoise_hist", dn_hist), ("denoise_var", dn_var)):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        res[name + "_ms_median"] = round(ts[len(ts) // 2], 4)
+        res[name + "_ms_min"] = round(ts[0], 4)
+        if name.startswith("accumulate"):
+            res[name + "_hbm_fraction"] = round(BYTES_PER_PIXEL * w * h / (ts[len(ts) // 2] * 1e-3) / HBM_PEAK, 4)
+            res[name + "_mean_length"] = round(float(len1.mean()), 3)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
