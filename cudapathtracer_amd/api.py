@@ -81,6 +81,21 @@ class TemporalParams(C.Structure):   # pt_temporal_params
     _fields_ = [("max_history", C.c_int32), ("depth_tol", C.c_float), ("normal_tol", C.c_float)]
 
 
+class ResolveParams(C.Structure):    # pt_resolve_params
+    _fields_ = [("tonemap", C.c_int32), ("exposure", C.c_float)]
+
+
+class PreviewParams(C.Structure):    # pt_preview_params
+    _fields_ = [("spp", C.c_int32), ("batches", C.c_int32), ("max_depth", C.c_int32), ("integrator", C.c_int32), ("use_mis", C.c_int32),
+                ("aov_spp", C.c_int32), ("temporal", C.c_int32), ("filter", C.c_int32), ("temporal_params", TemporalParams),
+                ("filter_params", DenoiseVarParams), ("resolve_params", ResolveParams)]
+
+
+class PreviewStats(C.Structure):     # pt_preview_stats
+    _fields_ = [("frames", C.c_int32), ("render_ms", C.c_float), ("aov_ms", C.c_float), ("accumulate_ms", C.c_float),
+                ("filter_ms", C.c_float), ("resolve_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("chunk_spp", C.c_int32), ("threshold", C.c_float)]
 
@@ -195,6 +210,18 @@ def lib():
     L.pt_denoise_hist_workspace_bytes.restype = C.c_size_t; L.pt_denoise_hist_workspace_bytes.argtypes = [i32, i32]
     L.pt_denoise_hist.argtypes = [i32, i32, vp, vp, vp, C.POINTER(DenoiseVarParams), vp]
     L.pt_denoise_hist_device.argtypes = [i32, i32, vp, vp, vp, C.POINTER(DenoiseVarParams), vp, vp, vp]
+    L.pt_resolve_defaults.restype = None; L.pt_resolve_defaults.argtypes = [C.POINTER(ResolveParams)]
+    L.pt_resolve.argtypes = [i32, i32, vp, i32, vp, C.POINTER(ResolveParams), vp, vp]
+    L.pt_resolve_device.argtypes = [i32, i32, vp, i32, vp, C.POINTER(ResolveParams), vp, vp, vp]
+    L.pt_preview_defaults.restype = None; L.pt_preview_defaults.argtypes = [C.POINTER(PreviewParams)]
+    L.pt_preview_create.restype = vp; L.pt_preview_create.argtypes = [vp, i32, i32, C.POINTER(PreviewParams)]
+    L.pt_preview_frame.argtypes = [vp, C.POINTER(Camera), u64]
+    L.pt_preview_reset.argtypes = [vp]
+    L.pt_preview_read.argtypes = [vp, vp, vp, vp, vp]
+    L.pt_preview_device_rgba8.restype = vp; L.pt_preview_device_rgba8.argtypes = [vp]
+    L.pt_preview_device_mean.restype = vp; L.pt_preview_device_mean.argtypes = [vp]
+    L.pt_preview_last_stats.argtypes = [vp, C.POINTER(PreviewStats)]
+    L.pt_preview_destroy.restype = None; L.pt_preview_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -889,6 +916,126 @@ class TemporalHistory:
         self.camera = Camera.frombytes(camera.tobytes())
         self.normal_depth = normal_depth.copy()
         return self.hist
+
+
+def resolve_defaults():
+    """pt_resolve_defaults as a dict: tonemap, exposure."""
+    p = ResolveParams()
+    lib().pt_resolve_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in ResolveParams._fields_}
+
+
+def _resolve_params(tonemap, exposure):
+    p = ResolveParams()
+    lib().pt_resolve_defaults(C.byref(p))
+    if tonemap is not None:
+        p.tonemap = int(tonemap)
+    if exposure is not None:
+        p.exposure = exposure
+    return p
+
+
+def resolve(rgba, spp=0, tile_spp=None, tonemap=None, exposure=None):
+    """pt_resolve (host, blocking): display bytes of a frame of radiance sums. rgba is [h,w,4] float32; it is divided by `spp`,
+    or per 8x8 tile by tile_spp (int32 [ceil(h/8), ceil(w/8)], as render_adaptive returns it), painted as finalise paints NaN /
+    Inf, scaled by `exposure`, tone-mapped and gamma-corrected as save_bmp does (tonemap False: clamped only) and converted to
+    bytes. Returns (rgba8 [h,w,4] uint8 with alpha 255, mean [h,w,4] float32 = finalise(rgba, spp)); y = 0 stays the bottom row."""
+    S, = _f4_frames("resolve", (("rgba", rgba),))
+    h, w = S.shape[:2]
+    T = None
+    if tile_spp is not None:
+        if not isinstance(tile_spp, np.ndarray) or tile_spp.dtype != np.int32 or tile_spp.shape != ((h + 7) // 8, (w + 7) // 8):
+            raise PtError("resolve: tile_spp must be an int32 [%d, %d] array for a %d x %d frame" % ((h + 7) // 8, (w + 7) // 8, w, h))
+        T = np.ascontiguousarray(tile_spp)
+    out8, mean = np.empty((h, w, 4), np.uint8), np.empty_like(S)
+    p = _resolve_params(tonemap, exposure)
+    _check(lib().pt_resolve(w, h, _p(S), int(spp), _p(T), C.byref(p), _p(out8), _p(mean)), "pt_resolve")
+    return out8, mean
+
+
+def resolve_device(w, h, d_rgba_ptr, spp, d_rgba8_ptr, d_mean_ptr=0, d_tile_spp_ptr=0, tonemap=None, exposure=None, stream=0):
+    """pt_resolve_device: device buffers (w*h float4 in, w*h*4 bytes out, optionally the w*h float4 mean and one int32 per 8x8
+    tile), asynchronous on `stream`. The outputs must not alias the inputs."""
+    p = _resolve_params(tonemap, exposure)
+    _check(lib().pt_resolve_device(w, h, d_rgba_ptr, int(spp), d_tile_spp_ptr or None, C.byref(p), d_rgba8_ptr, d_mean_ptr or None,
+                                   stream or None), "pt_resolve_device")
+
+
+def preview_defaults():
+    """pt_preview_defaults as a dict; temporal_params, filter_params and resolve_params are dicts themselves."""
+    p = PreviewParams()
+    lib().pt_preview_defaults(C.byref(p))
+    sub = lambda s: {f: getattr(s, f) for f, _ in s._fields_}
+    return {f: (sub(getattr(p, f)) if f.endswith("_params") else getattr(p, f)) for f, _ in PreviewParams._fields_}
+
+
+class Preview:
+    """pt_preview: the device buffers of one w x h viewer of `scene` (which must outlive it) and one call per frame:
+    render_moments -> render_aovs -> temporal_accumulate -> denoise_hist -> resolve on the device, history and guide ping-ponged
+    there. Keyword arguments are pt_preview_params' fields (spp, batches, max_depth, integrator, use_mis, aov_spp, temporal,
+    filter) and those of the three stages (max_history, depth_tol, normal_tol; iterations, sigma_var, sigma_normal, sigma_depth;
+    tonemap, exposure); what is left out takes the library's default."""
+
+    def __init__(self, scene, w, h, **params):
+        p = PreviewParams()
+        lib().pt_preview_defaults(C.byref(p))
+        for k, v in params.items():
+            for s in (p, p.temporal_params, p.filter_params, p.resolve_params):
+                if any(k == f for f, _ in s._fields_) and not k.endswith("_params"):
+                    setattr(s, k, int(v) if isinstance(v, bool) else v)
+                    break
+            else:
+                raise PtError("Preview: unknown parameter %r" % k)
+        self.w, self.h, self.temporal = w, h, bool(p.temporal)
+        self._scene = scene
+        self.handle = lib().pt_preview_create(scene.h if scene is not None else None, w, h, C.byref(p))
+        if not self.handle:
+            raise PtError("pt_preview_create failed: " + lib().pt_last_error().decode(errors="replace"))
+
+    def frame(self, camera, seed=SEED):
+        """pt_preview_frame: render and post-process one frame; blocks. The image stays on the device (read(), device_rgba8())."""
+        _check(lib().pt_preview_frame(self.handle, C.byref(camera), seed), "pt_preview_frame")
+        return self
+
+    def reset(self):
+        """Drop the history: the next frame is a first frame."""
+        _check(lib().pt_preview_reset(self.handle), "pt_preview_reset")
+        return self
+
+    def read(self, rgba8=True, mean=True, hist=None, hist_len=None):
+        """pt_preview_read: the last good frame's outputs as a dict of the requested arrays: rgba8 [h,w,4] uint8, mean [h,w,4]
+        float32, hist [h,w,4] float32 and hist_len [h,w] float32 (the last two by default exactly when the session is temporal)."""
+        want = {"rgba8": rgba8, "mean": mean, "hist": self.temporal if hist is None else hist,
+                "hist_len": self.temporal if hist_len is None else hist_len}
+        shapes = {"rgba8": ((self.h, self.w, 4), np.uint8), "mean": ((self.h, self.w, 4), np.float32),
+                  "hist": ((self.h, self.w, 4), np.float32), "hist_len": ((self.h, self.w), np.float32)}
+        out = {k: np.empty(*shapes[k]) for k, v in want.items() if v}
+        _check(lib().pt_preview_read(self.handle, *[_p(out.get(k)) for k in ("rgba8", "mean", "hist", "hist_len")]), "pt_preview_read")
+        return out
+
+    def device_rgba8(self):
+        """Device address of the w*h*4 display bytes (valid until close(); holds the last good frame)."""
+        return lib().pt_preview_device_rgba8(self.handle)
+
+    def device_mean(self):
+        return lib().pt_preview_device_mean(self.handle)
+
+    def stats(self):
+        """pt_preview_last_stats: good frames since creation and the last one's stage times in milliseconds."""
+        st = PreviewStats()
+        _check(lib().pt_preview_last_stats(self.handle, C.byref(st)), "pt_preview_last_stats")
+        return {f: getattr(st, f) for f, _ in PreviewStats._fields_}
+
+    def close(self):
+        if self.handle:
+            lib().pt_preview_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def adaptive_params(min_spp, max_spp, chunk_spp, threshold):

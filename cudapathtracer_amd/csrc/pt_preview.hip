@@ -1,0 +1,313 @@
+// pt_preview.hip — what a viewer needs around the existing stages (include/pt_api.h, "preview"):
+//
+//   resolve_kernel      radiance sums to display bytes: the division of novum_finalise (or of an adaptive frame's tile map), its
+//                       NaN / Inf paint, exposure, novum_save_bmp's tone map + gamma and its byte conversion. One thread per pixel,
+//                       16x16 pixels per workgroup as four 8x8 tiles (one per wave, the tiling of temporal_accumulate_kernel), so a
+//                       wave's tile index is uniform and the tile's sample count is one scalar load. One float4 load, one dword
+//                       store (plus the optional float4 mean); no LDS, no scratch. tests/preview_ref.py restates it in numpy.
+//   pt_preview          a session that owns the device buffers of one w x h viewer and runs render_moments -> render_aovs ->
+//                       temporal_accumulate -> denoise_hist -> resolve per frame on one stream through the public *_device entry
+//                       points, ping-ponging history and guide. Nothing crosses PCIe unless pt_preview_read asks for it.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/pt_api.h"
+
+extern "C" int pt_fail_(int code, const char* msg);
+
+namespace pt {
+
+// novum_host.cpp's clamp01, aces and to_byte, operation for operation (-ffp-contract=off: nothing fuses).
+__device__ inline float rs_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+__device__ inline float rs_aces(float c) { return rs_clamp01((c * (2.51f * c + 0.03f)) / (c * (2.43f * c + 0.59f) + 0.14f)); }
+__device__ inline uint32_t rs_byte(float c) {
+    const float v = rs_clamp01(c) * 255.0f + 0.5f;
+    return v != v ? 0u : (uint32_t)v;                     // v is NaN or in [0.5, 255.5]
+}
+__device__ inline float rs_display(float m, float exposure, bool tonemap) {
+    const float c = m * exposure;
+    return tonemap ? powf(rs_aces(c), 1.0f / 2.2f) : c;
+}
+
+__global__ void __launch_bounds__(256) resolve_kernel(int w, int h, const float4* __restrict__ in, float spp, const int32_t* __restrict__ tileSpp,
+                                                      int tilesX, int tonemap, float exposure, uint32_t* __restrict__ out8,
+                                                      float4* __restrict__ mean) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tx = blockIdx.x * 2 + (wave & 1), ty = blockIdx.y * 2 + (wave >> 1);
+    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;                             // (a tile outside the grid has no lane left: no read past the map)
+    const float n = tileSpp ? (float)tileSpp[__builtin_amdgcn_readfirstlane(ty * tilesX + tx)] : spp;
+    const size_t p = (size_t)y * w + x;
+    const float4 s = in[p];
+    float4 m = make_float4(s.x / n, s.y / n, s.z / n, s.w);
+    if (m.x != m.x || m.y != m.y || m.z != m.z) m = make_float4(1.0f, 0.0f, 1.0f, 0.0f);
+    if (__builtin_isinf(m.x) || __builtin_isinf(m.y) || __builtin_isinf(m.z)) m = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
+    if (mean) mean[p] = m;
+    const uint32_t r = rs_byte(rs_display(m.x, exposure, tonemap != 0)), g = rs_byte(rs_display(m.y, exposure, tonemap != 0)),
+                   b = rs_byte(rs_display(m.z, exposure, tonemap != 0));
+    out8[p] = r | (g << 8) | (b << 16) | 0xff000000u;
+}
+
+static int pv_fail(int code, const char* fmt, int a = 0, int b = 0) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), fmt, a, b);
+    return pt_fail_(code, buf);
+}
+#define PV_HIP_OK(expr)                                                                                            \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) {                                                                                    \
+            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
+            return pt_fail_(-2, m_);                                                                               \
+        }                                                                                                          \
+    } while (0)
+
+static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
+    const char* pa = (const char*)a; const char* pb = (const char*)b;
+    return pa < pb + bBytes && pb < pa + aBytes;
+}
+
+static int check_resolve_params(const pt_resolve_params& P) {
+    if (P.tonemap != 0 && P.tonemap != 1) return pv_fail(-1, "pt_resolve: tonemap %d must be 0 or 1", P.tonemap);
+    if (!(P.exposure > 0.0f) || !std::isfinite(P.exposure)) return pv_fail(-1, "pt_resolve: exposure must be positive and finite");
+    return 0;
+}
+
+static int check_resolve_args(int w, int h, const void* in, int spp, const void* tileSpp, const pt_resolve_params& P, const void* out8,
+                              const void* mean) {
+    if (w <= 0 || h <= 0) return pv_fail(-1, "pt_resolve: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return pv_fail(-1, "pt_resolve: image of %d x %d pixels is too large", w, h);
+    if (!in) return pv_fail(-1, "pt_resolve: null buffer");
+    if (!out8) return pv_fail(-1, "pt_resolve: null output");
+    if (!tileSpp && spp < 1) return pv_fail(-1, "pt_resolve: spp %d must be at least 1 (or give a tile map)", spp);
+    if (int r = check_resolve_params(P)) return r;
+    const size_t n = (size_t)w * h, tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    if (overlaps(out8, n * 4, in, n * 16) || (mean && (overlaps(mean, n * 16, in, n * 16) || overlaps(mean, n * 16, out8, n * 4))) ||
+        (tileSpp && (overlaps(out8, n * 4, tileSpp, tiles * 4) || (mean && overlaps(mean, n * 16, tileSpp, tiles * 4)))))
+        return pv_fail(-1, "pt_resolve: the outputs must not alias the inputs or each other");
+    return 0;
+}
+
+static int resolve_launch(int w, int h, const float4* in, int spp, const int32_t* tileSpp, const pt_resolve_params& P, uint32_t* out8, float4* mean,
+                          hipStream_t stream) {
+    hipLaunchKernelGGL(resolve_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, stream, w, h, in, (float)spp, tileSpp, (w + 7) / 8,
+                       P.tonemap, P.exposure, out8, mean);
+    PV_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace pt
+
+using namespace pt;
+
+// One viewer: every buffer lives in `pool`. cur names the half of the ping-pong pairs that holds the history and the guide of the
+// last good frame; a frame writes the other half and flips only when all of its stages succeeded.
+struct pt_preview {
+    pt_scene* scene;
+    int w, h;
+    pt_preview_params P;
+    hipStream_t stream;
+    hipEvent_t ev[6];                     // before the frame and after each of its five stages
+    char* pool;
+    char *S, *Q, *A, *N[2], *H[2], *L[2]; // sums, albedo; guide, history and history length twice (temporal 0: one guide only)
+    char *ws, *filt, *mean, *rgba8;       // the filters' workspace, the filtered frame, the displayed mean and its bytes
+    int cur;
+    bool haveHist, haveFrame;
+    pt_camera prevCam;
+    pt_preview_stats stats;
+};
+
+extern "C" {
+
+void pt_resolve_defaults(pt_resolve_params* out) {
+    if (!out) return;
+    out->tonemap = 1;
+    out->exposure = 1.0f;
+}
+
+int pt_resolve_device(int w, int h, const void* d_rgba, int spp, const void* d_tile_spp, const pt_resolve_params* params, void* d_rgba8, void* d_mean,
+                      void* stream) {
+    pt_resolve_params P;
+    if (params) P = *params; else pt_resolve_defaults(&P);
+    if (int r = check_resolve_args(w, h, d_rgba, spp, d_tile_spp, P, d_rgba8, d_mean)) return r;
+    return resolve_launch(w, h, (const float4*)d_rgba, spp, (const int32_t*)d_tile_spp, P, (uint32_t*)d_rgba8, (float4*)d_mean, (hipStream_t)stream);
+}
+
+int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp, const pt_resolve_params* params, uint8_t* rgba8, float* mean) {
+    pt_resolve_params P;
+    if (params) P = *params; else pt_resolve_defaults(&P);
+    if (int r = check_resolve_args(w, h, rgba, spp, tile_spp, P, rgba8, mean)) return r;
+    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15, tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    if (tile_spp)
+        for (size_t t = 0; t < tiles; t++)
+            if (tile_spp[t] <= 0) return pv_fail(-1, "pt_resolve: tile %d has %d samples; every tile needs at least one", (int)t, tile_spp[t]);
+    char* d = nullptr;
+    PV_HIP_OK(hipMalloc(&d, 2 * b16 + b4 + tiles * 4));
+    char* dIn = d; char* dMean = dIn + b16; char* d8 = dMean + b16; char* dT = d8 + b4;
+    hipError_t e = hipMemcpy(dIn, rgba, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && tile_spp) e = hipMemcpy(dT, tile_spp, tiles * 4, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = pv_fail(-2, "pt_resolve: upload failed");
+    } else if ((r = resolve_launch(w, h, (const float4*)dIn, spp, tile_spp ? (const int32_t*)dT : nullptr, P, (uint32_t*)d8,
+                                   mean ? (float4*)dMean : nullptr, nullptr)) == 0) {
+        e = hipMemcpy(rgba8, d8, n * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && mean) e = hipMemcpy(mean, dMean, b16, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = pv_fail(-2, "pt_resolve: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+void pt_preview_defaults(pt_preview_params* out) {
+    if (!out) return;
+    out->spp = 4; out->batches = 2; out->max_depth = 8; out->integrator = PT_UNIDIRECTIONAL; out->use_mis = 1; out->aov_spp = 1;
+    out->temporal = 1; out->filter = 1;
+    pt_temporal_defaults(&out->temporal_params);
+    pt_denoise_var_defaults(&out->filter_params);
+    pt_resolve_defaults(&out->resolve_params);
+}
+
+void pt_preview_destroy(pt_preview* p) {
+    if (!p) return;
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    for (hipEvent_t e : p->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    if (p->pool) (void)hipFree(p->pool);
+    delete p;
+}
+
+pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_params* params) {
+    pt_preview_params P;
+    if (params) P = *params; else pt_preview_defaults(&P);
+    // what the stages would refuse on every frame is refused here, before any HIP call; the filters' and the history's own
+    // parameters are checked by their stages
+    int bad = 0;
+    if (!scene) bad = pv_fail(-1, "pt_preview_create: null scene");
+    else if (w <= 0 || h <= 0) bad = pv_fail(-1, "pt_preview_create: image size %d x %d must be positive", w, h);
+    else if ((long long)((w + 7) / 8) * ((h + 7) / 8) * 64 > 0x7fffffffll) bad = pv_fail(-1, "pt_preview_create: image of %d x %d pixels is too large", w, h);
+    else if (P.spp <= 0) bad = pv_fail(-1, "pt_preview_create: spp %d must be positive", P.spp);
+    else if (P.batches < 2) bad = pv_fail(-1, "pt_preview_create: batches %d must be at least 2", P.batches);
+    else if (P.spp % P.batches != 0) bad = pv_fail(-1, "pt_preview_create: batches %d must divide spp %d", P.batches, P.spp);
+    else if (P.integrator != PT_UNIDIRECTIONAL && P.integrator != PT_NAIVE_UNIDIRECTIONAL)
+        bad = pv_fail(-3, "pt_preview_create: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2)", P.integrator);
+    else if (P.aov_spp <= 0) bad = pv_fail(-1, "pt_preview_create: aov_spp %d must be positive", P.aov_spp);
+    else if ((P.temporal != 0 && P.temporal != 1) || (P.filter != 0 && P.filter != 1))
+        bad = pv_fail(-1, "pt_preview_create: temporal %d and filter %d must be 0 or 1", P.temporal, P.filter);
+    else bad = check_resolve_params(P.resolve_params);
+    if (bad) return nullptr;
+
+    pt_preview* p = new pt_preview();      // zeroed
+    p->scene = scene; p->w = w; p->h = h; p->P = P;
+    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
+    const size_t ws = (pt_denoise_var_workspace_bytes(w, h) + 15) & ~(size_t)15;
+    const int pairs = P.temporal ? 2 : 1;
+    const size_t total = 3 * b16 + pairs * b16 + (P.temporal ? 2 * (b16 + b4) : 0) + ws + 2 * b16 + b4;
+    bool ok = hipMalloc(&p->pool, total) == hipSuccess && hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; ok && i < 6; i++) ok = hipEventCreate(&p->ev[i]) == hipSuccess;
+    if (!ok) {
+        pv_fail(-2, "pt_preview_create: could not allocate the session's buffers, stream and events (no usable HIP device, or out of memory)");
+        pt_preview_destroy(p);
+        return nullptr;
+    }
+    char* c = p->pool;
+    auto take = [&c](size_t bytes) { char* r = c; c += bytes; return r; };
+    p->S = take(b16); p->Q = take(b16); p->A = take(b16);
+    for (int i = 0; i < pairs; i++) p->N[i] = take(b16);
+    if (P.temporal)
+        for (int i = 0; i < 2; i++) { p->H[i] = take(b16); p->L[i] = take(b4); }
+    p->ws = take(ws); p->filt = take(b16); p->mean = take(b16); p->rgba8 = take(b4);
+    return p;
+}
+
+int pt_preview_reset(pt_preview* p) {
+    if (!p) return pv_fail(-1, "pt_preview_reset: null session");
+    p->haveHist = p->haveFrame = false;
+    return 0;
+}
+
+// The five stages of a frame, enqueued on the session's stream with an event after each; the first error ends it. nxt: the half of
+// the ping-pong pairs this frame writes.
+static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
+    const pt_preview_params& P = p->P;
+    const int w = p->w, h = p->h;
+    hipStream_t st = p->stream;
+    PV_HIP_OK(hipEventRecord(p->ev[0], st));
+    // (the first stage checks its arguments, the camera's size among them, before it enqueues anything)
+    if (int r = pt_render_moments_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->S, p->Q, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[1], st));
+    if (int r = pt_render_aovs_device(p->scene, cam, w, h, P.aov_spp, seed, p->A, p->N[nxt], st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[2], st));
+    const void* shown = p->S;             // what the resolve divides, and by what
+    int shownSpp = P.spp;
+    if (P.temporal) {
+        const bool hist = p->haveHist;
+        if (int r = pt_temporal_accumulate_device(w, h, cam, hist ? &p->prevCam : nullptr, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt],
+                                                  hist ? p->N[p->cur] : nullptr, hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr,
+                                                  &P.temporal_params, p->H[nxt], p->L[nxt], st))
+            return r;
+        PV_HIP_OK(hipEventRecord(p->ev[3], st));
+        pt_denoise_var_params F = P.filter_params;
+        if (!P.filter) F.iterations = 0;  // no iteration: the history's mean a e, pass-through pixels as they are
+        if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[nxt], &F, p->ws, p->filt, st)) return r;
+        shown = p->filt; shownSpp = 1;
+    } else {
+        PV_HIP_OK(hipEventRecord(p->ev[3], st));
+        if (P.filter) {
+            if (int r = pt_denoise_var_device(w, h, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt], &P.filter_params, p->ws, p->filt, st)) return r;
+            shown = p->filt;
+        }
+    }
+    PV_HIP_OK(hipEventRecord(p->ev[4], st));
+    if (int r = pt_resolve_device(w, h, shown, shownSpp, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[5], st));
+    return 0;
+}
+
+int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
+    if (!p) return pv_fail(-1, "pt_preview_frame: null session");
+    if (!cam) return pv_fail(-1, "pt_preview_frame: null camera");
+    const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
+    const int r = preview_stages(p, cam, seed, nxt);
+    const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
+    if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
+    if (e != hipSuccess) return pv_fail(-2, "pt_preview_frame: the stream failed to synchronise");
+    float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, total = 0.0f;
+    for (int i = 0; i < 5; i++) PV_HIP_OK(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
+    PV_HIP_OK(hipEventElapsedTime(&total, p->ev[0], p->ev[5]));
+    p->cur = nxt;
+    p->haveHist = p->P.temporal != 0;
+    p->haveFrame = true;
+    p->prevCam = *cam;
+    p->stats.frames++;
+    p->stats.render_ms = ms[0]; p->stats.aov_ms = ms[1]; p->stats.accumulate_ms = ms[2]; p->stats.filter_ms = ms[3]; p->stats.resolve_ms = ms[4];
+    p->stats.total_ms = total;
+    return 0;
+}
+
+int pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len) {
+    if (!p) return pv_fail(-1, "pt_preview_read: null session");
+    if (!p->haveFrame) return pv_fail(-1, "pt_preview_read: no frame since the session was created or reset");
+    if ((hist || hist_len) && !p->P.temporal) return pv_fail(-1, "pt_preview_read: a session with temporal 0 keeps no history");
+    const size_t n = (size_t)p->w * p->h;
+    if (rgba8) PV_HIP_OK(hipMemcpy(rgba8, p->rgba8, n * 4, hipMemcpyDeviceToHost));
+    if (mean) PV_HIP_OK(hipMemcpy(mean, p->mean, n * 16, hipMemcpyDeviceToHost));
+    if (hist) PV_HIP_OK(hipMemcpy(hist, p->H[p->cur], n * 16, hipMemcpyDeviceToHost));
+    if (hist_len) PV_HIP_OK(hipMemcpy(hist_len, p->L[p->cur], n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+const void* pt_preview_device_rgba8(pt_preview* p) { return p ? p->rgba8 : nullptr; }
+const void* pt_preview_device_mean(pt_preview* p) { return p ? p->mean : nullptr; }
+
+int pt_preview_last_stats(pt_preview* p, pt_preview_stats* out) {
+    if (!p || !out) return pv_fail(-1, "pt_preview_last_stats: null argument");
+    *out = p->stats;
+    return 0;
+}
+
+}  // extern "C"

@@ -498,6 +498,76 @@ int pt_denoise_hist(int w, int h, const float* hist, const float* albedo, const 
 int pt_denoise_hist_device(int w, int h, const void* d_hist, const void* d_albedo, const void* d_normal_depth,
                            const pt_denoise_var_params* params, void* d_workspace, void* d_out, void* stream);   /* async */
 
+/* ---- preview: display bytes on the device, and a session that owns a viewer's buffers ------------------------------
+ * pt_resolve: a stateless post-process like pt_denoise*: radiance in, what a viewer shows out. Per pixel p, in f32 with IEEE
+ * rounding and no contraction, left to right:
+ *   1. n = (float)tile_spp[tile of p] with a tile map (one int32 per 8x8 tile, row-major over the ceil(w/8) x ceil(h/8) grid, as
+ *      pt_render_adaptive writes it; the map overrides spp), else n = (float)spp.
+ *   2. m.rgb = rgba_p.rgb / n (IEEE division: novum_finalise's, or the per-pixel mean of an adaptive frame); m.w = rgba_p.w.
+ *   3. The paint of novum_finalise, in its order: any of m.rgb NaN -> m = (1, 0, 1, 0); then any of m.rgb Inf -> m = (0, 1, 0, 0).
+ *   4. mean_p = m (if mean is given): bit for bit novum_finalise(rgba, spp).
+ *   5. c = m.rgb * exposure;  with tonemap: c = powf(aces(c), 1.0f / 2.2f), aces(c) = clamp01((c (2.51f c + 0.03f)) /
+ *      (c (2.43f c + 0.59f) + 0.14f)): novum_save_bmp's toneMap + gammaCorrect. (The device's powf may differ from the host
+ *      libm's in the last bits, so a byte may differ by one code from novum_save_bmp's; without the tone map they are equal.)
+ *   6. byte = (unsigned char)(clamp01(c) * 255.0f + 0.5f), 0 for a NaN: novum_save_bmp's.
+ *   7. rgba8_p = (r, g, b, 255), four bytes per pixel. Rows and pixels keep the input's order (y = 0 is the bottom row).
+ * Arguments are checked before any HIP call: image size, NULL rgba / rgba8, spp >= 1 unless a tile map is given, tonemap 0 or 1,
+ * exposure finite and > 0, and no output may overlap an input or the other output. The host form also refuses a tile count
+ * <= 0 (-1); the device form trusts the map it is given. Host and device form are bit-identical. params NULL = the defaults. */
+typedef struct pt_resolve_params {
+    int32_t tonemap;             /* 1: ACES + gamma 2.2 as novum_save_bmp(post_process = 1); 0: clamp and convert only */
+    float exposure;              /* linear scale before the tone map (> 0, finite) */
+                                 /* defaults 1, 1.0 */
+} pt_resolve_params;
+void pt_resolve_defaults(pt_resolve_params* out);
+int pt_resolve_device(int w, int h, const void* d_rgba, int spp, const void* d_tile_spp /* or NULL */, const pt_resolve_params* params,
+                      void* d_rgba8, void* d_mean /* w*h float4, or NULL */, void* stream);                         /* async */
+int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp, const pt_resolve_params* params, uint8_t* rgba8,
+               float* mean);                                                                                       /* host, blocking */
+
+/* pt_preview: the buffers of one w x h viewer on the current HIP device, and one call per frame that leaves a displayable image
+ * there. A frame runs, on the session's own stream and through the public entry points above:
+ *   pt_render_moments_device (spp samples in `batches` batches) -> pt_render_aovs_device (aov_spp rays, the beauty's seed) ->
+ *   temporal 1: pt_temporal_accumulate_device from the previous good frame's camera, guide and history into the other half of a
+ *               ping-pong pair (the guide ping-pongs too; the first frame after create / reset has no history), then
+ *               pt_denoise_hist_device on the new history (filter 0: with 0 iterations, i.e. the history's mean a e), then
+ *               pt_resolve_device(spp = 1) on that mean;
+ *   temporal 0: pt_denoise_var_device on this frame alone, then pt_resolve_device(spp) (filter 0: on the raw sums).
+ * So mean, hist and hist_len equal that chain through the host forms bit for bit. A camera whose 112 bytes equal the previous
+ * frame's takes pt_temporal_accumulate's identity path. pt_preview_frame blocks until the frame is done (as
+ * pt_render_moments_device does); nothing is copied to or from the host. A stage that fails ends the frame with its error and
+ * its message: history, guide and previous camera stay those of the last good frame (the ping-pong flips only after every stage
+ * was enqueued without error and the stream has synchronised). pt_preview_create checks its arguments before any HIP call
+ * (NULL scene, image size, spp, batches >= 2 dividing spp, integrator, aov_spp, temporal / filter 0 or 1, resolve_params) and
+ * allocates everything the session owns; temporal_params and filter_params are checked by their stages. The scene must outlive
+ * the session and is not to be rendered from another thread during a frame. pt_preview_read copies the last good frame's
+ * outputs to the host (any pointer may be NULL; hist / hist_len need temporal 1; -1 before the first frame after create / reset).
+ * The device pointers stay valid until destroy; their contents are the last good frame's. */
+typedef struct pt_preview pt_preview;
+typedef struct pt_preview_params {
+    int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
+    int32_t temporal;            /* 1: accumulate + pt_denoise_hist; 0: pt_denoise_var on this frame alone */
+    int32_t filter;              /* 0: no spatial filter (temporal 1: the history's mean a e; temporal 0: the raw mean) */
+    pt_temporal_params temporal_params;
+    pt_denoise_var_params filter_params;
+    pt_resolve_params resolve_params;
+                                 /* defaults 4, 2, 8, 0, 1, 1, 1, 1 and the three libraries' defaults */
+} pt_preview_params;
+typedef struct pt_preview_stats {
+    int32_t frames;              /* good frames since create */
+    float render_ms, aov_ms, accumulate_ms, filter_ms, resolve_ms, total_ms;   /* the last good frame: HIP events on the session's
+                                    stream around each stage (render_ms includes pt_render_moments_device's per-batch waits) */
+} pt_preview_stats;
+void pt_preview_defaults(pt_preview_params* out);
+pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_params* params);   /* NULL on error: pt_last_error() */
+int  pt_preview_frame(pt_preview* p, const pt_camera* camera, uint64_t seed);
+int  pt_preview_reset(pt_preview* p);                                      /* the next frame is a first frame */
+int  pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len);
+const void* pt_preview_device_rgba8(pt_preview* p);                        /* w*h*4 bytes */
+const void* pt_preview_device_mean(pt_preview* p);                         /* w*h float4 */
+int  pt_preview_last_stats(pt_preview* p, pt_preview_stats* out);
+void pt_preview_destroy(pt_preview* p);
+
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
 int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* out_exp, float* out_rsqrt, float* out_pow5);

@@ -1,0 +1,82 @@
+"""Wall time of one preview frame at 1920x1080: the pt_preview session next to the chain of host calls it replaces, in one run.
+
+    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3]
+
+Both render the same moving-camera sequence (tests/temporal_seq.py's camera) of the Cornell box with the session's defaults
+(4 spp in 2 batches, depth 8, MIS, 1 feature ray, temporal accumulation, the history filter, tone map). The host chain is
+render_moments + render_aovs + TemporalHistory.push + denoise_hist + finalise + the tone map, gamma and byte conversion in numpy:
+every buffer crosses PCIe, most of them twice. Prints one JSON line: the median and the minimum wall time of a frame for both
+(host clock around calls that end in a device synchronise), the session's median stage times from its HIP events, the host
+chain's median time per call, and whether the last frames' bytes agree."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--w", type=int, default=1920)
+    ap.add_argument("--h", type=int, default=1080)
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import preview_ref as R
+    import temporal_seq as Q
+    from cudapathtracer_amd import api, scenes
+    if not torch.cuda.is_available():
+        raise SystemExit("preview_time.py needs a HIP device")
+    torch.cuda.set_device(0)
+    w, h = a.w, a.h
+    d = api.preview_defaults()
+    spp, batches, depth = d["spp"], d["batches"], d["max_depth"]
+    sc = api.Scene(api.HostScene(scenes.cornell(tempfile.mkdtemp(), width=w, height=h, spp=spp, max_depth=depth, name="pvt")["config"]))
+    n = a.warmup + a.frames
+    cams = [Q.camera(api, t, True, w, h) for t in range(n)]
+    med = lambda v: round(sorted(v)[len(v) // 2], 4)
+
+    pv = api.Preview(sc, w, h)
+    wall, stages = [], []
+    for t in range(n):
+        t0 = time.perf_counter()
+        pv.frame(cams[t], Q.SEED0 + t)                    # blocks until the frame is on the device
+        wall.append(1e3 * (time.perf_counter() - t0))
+        stages.append(pv.stats())
+    session8 = pv.read(mean=False, hist=False, hist_len=False)["rgba8"]
+    pv.close()
+    res = {"w": w, "h": h, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth,
+           "session_frame_ms_median": med(wall[a.warmup:]), "session_frame_ms_min": round(min(wall[a.warmup:]), 4)}
+    for k in ("render_ms", "aov_ms", "accumulate_ms", "filter_ms", "resolve_ms", "total_ms"):
+        res["session_" + k + "_median"] = med([s[k] for s in stages[a.warmup:]])
+
+    th = api.TemporalHistory(w, h)
+    wall, parts = [], {k: [] for k in ("render_moments", "render_aovs", "push", "denoise_hist", "finalise", "bytes_numpy")}
+    for t in range(n):
+        marks = [time.perf_counter()]
+        S, Qs = sc.render_moments(cams[t], w, h, spp, spp // batches, depth, seed=Q.SEED0 + t); marks.append(time.perf_counter())
+        A, N = sc.render_aovs(cams[t], w, h, aov_spp=1, seed=Q.SEED0 + t); marks.append(time.perf_counter())
+        hist = th.push(cams[t], S, Qs, spp, batches, A, N); marks.append(time.perf_counter())
+        filt = api.denoise_hist(hist, A, N); marks.append(time.perf_counter())
+        mean = api.finalise(filt, 1); marks.append(time.perf_counter())
+        host8 = R.display(mean); marks.append(time.perf_counter())
+        wall.append(1e3 * (marks[-1] - marks[0]))
+        for k, (m0, m1) in zip(parts, zip(marks, marks[1:])):
+            parts[k].append(1e3 * (m1 - m0))
+    res["host_chain_frame_ms_median"] = med(wall[a.warmup:]); res["host_chain_frame_ms_min"] = round(min(wall[a.warmup:]), 4)
+    for k, v in parts.items():
+        res["host_" + k + "_ms_median"] = med(v[a.warmup:])
+    diff = np.abs(session8.astype(np.int32) - host8.astype(np.int32))
+    res["bytes_differing"] = int((diff > 0).sum()); res["bytes_max_difference"] = int(diff.max())
+    res["speedup"] = round(res["host_chain_frame_ms_median"] / res["session_frame_ms_median"], 2)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
