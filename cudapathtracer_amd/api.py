@@ -81,6 +81,10 @@ class TemporalParams(C.Structure):   # pt_temporal_params
     _fields_ = [("max_history", C.c_int32), ("depth_tol", C.c_float), ("normal_tol", C.c_float)]
 
 
+class UpsampleParams(C.Structure):   # pt_upsample_params
+    _fields_ = [("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class ResolveParams(C.Structure):    # pt_resolve_params
     _fields_ = [("tonemap", C.c_int32), ("exposure", C.c_float)]
 
@@ -210,6 +214,13 @@ def lib():
     L.pt_denoise_hist_workspace_bytes.restype = C.c_size_t; L.pt_denoise_hist_workspace_bytes.argtypes = [i32, i32]
     L.pt_denoise_hist.argtypes = [i32, i32, vp, vp, vp, C.POINTER(DenoiseVarParams), vp]
     L.pt_denoise_hist_device.argtypes = [i32, i32, vp, vp, vp, C.POINTER(DenoiseVarParams), vp, vp, vp]
+    L.pt_upsample_defaults.restype = None; L.pt_upsample_defaults.argtypes = [C.POINTER(UpsampleParams)]
+    L.pt_camera_scaled.argtypes = [C.POINTER(Camera), i32, C.POINTER(Camera)]
+    L.pt_upsample.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(UpsampleParams), vp]
+    L.pt_upsample_device.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp]
+    L.pt_temporal_accumulate_cur.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, C.POINTER(TemporalParams), vp, vp]
+    L.pt_temporal_accumulate_cur_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, C.POINTER(TemporalParams),
+                                                    vp, vp, vp]
     L.pt_resolve_defaults.restype = None; L.pt_resolve_defaults.argtypes = [C.POINTER(ResolveParams)]
     L.pt_resolve.argtypes = [i32, i32, vp, i32, vp, C.POINTER(ResolveParams), vp, vp]
     L.pt_resolve_device.argtypes = [i32, i32, vp, i32, vp, C.POINTER(ResolveParams), vp, vp, vp]
@@ -217,6 +228,8 @@ def lib():
     L.pt_preview_create.restype = vp; L.pt_preview_create.argtypes = [vp, i32, i32, C.POINTER(PreviewParams)]
     L.pt_preview_frame.argtypes = [vp, C.POINTER(Camera), u64]
     L.pt_preview_reset.argtypes = [vp]
+    L.pt_preview_set_scale.argtypes = [vp, i32]
+    L.pt_preview_scale.argtypes = [vp]
     L.pt_preview_read.argtypes = [vp, vp, vp, vp, vp]
     L.pt_preview_device_rgba8.restype = vp; L.pt_preview_device_rgba8.argtypes = [vp]
     L.pt_preview_device_mean.restype = vp; L.pt_preview_device_mean.argtypes = [vp]
@@ -832,6 +845,19 @@ def _f4_frames(what, named, shape=None):
     return arrs
 
 
+def _history_arrays(what, shape, prev_normal_depth, hist, hist_len):
+    """The three history arrays of temporal_accumulate*: all None, or checked against the frame's shape and made contiguous."""
+    given = [x is not None for x in (prev_normal_depth, hist, hist_len)]
+    if any(given) != all(given):
+        raise PtError("%s: prev_normal_depth, hist and hist_len must be all None or all given" % what)
+    if not all(given):
+        return None, None, None
+    PN, H = _f4_frames(what, (("prev_normal_depth", prev_normal_depth), ("hist", hist)), shape)
+    if not isinstance(hist_len, np.ndarray) or hist_len.dtype != np.float32 or hist_len.shape != shape[:2]:
+        raise PtError("%s: hist_len must be a float32 [%d, %d] array" % (what, shape[0], shape[1]))
+    return PN, H, np.ascontiguousarray(hist_len)
+
+
 def temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None,
                         hist_len=None, max_history=None, depth_tol=None, normal_tol=None):
     """pt_temporal_accumulate (host, blocking): blend this frame (render_moments' sums, render_aovs' buffers) into the history
@@ -840,15 +866,7 @@ def temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_d
     A None parameter takes the library default (temporal_defaults())."""
     S, Q, A, N = _f4_frames("temporal_accumulate", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
     h, w = S.shape[:2]
-    given = [x is not None for x in (prev_normal_depth, hist, hist_len)]
-    if any(given) != all(given):
-        raise PtError("temporal_accumulate: prev_normal_depth, hist and hist_len must be all None or all given")
-    PN = H = HL = None
-    if all(given):
-        PN, H = _f4_frames("temporal_accumulate", (("prev_normal_depth", prev_normal_depth), ("hist", hist)), S.shape)
-        if not isinstance(hist_len, np.ndarray) or hist_len.dtype != np.float32 or hist_len.shape != (h, w):
-            raise PtError("temporal_accumulate: hist_len must be a float32 [%d, %d] array" % (h, w))
-        HL = np.ascontiguousarray(hist_len)
+    PN, H, HL = _history_arrays("temporal_accumulate", S.shape, prev_normal_depth, hist, hist_len)
     out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
     p = _temporal_params(max_history, depth_tol, normal_tol)
     _check(lib().pt_temporal_accumulate(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q), int(spp),
@@ -867,6 +885,80 @@ def temporal_accumulate_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_s
                                                d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
                                                d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None, C.byref(p),
                                                d_out_hist_ptr, d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_device")
+
+
+def temporal_accumulate_cur(camera, cur, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None, hist_len=None, max_history=None,
+                            depth_tol=None, normal_tol=None):
+    """pt_temporal_accumulate_cur (host, blocking): temporal_accumulate with this frame's working pixels given in `cur` ([h,w,4]
+    float32: e and V, V = -1 for a pass-through pixel), as upsample returns them. Returns new (hist, hist_len)."""
+    E, N = _f4_frames("temporal_accumulate_cur", (("cur", cur), ("normal_depth", normal_depth)))
+    h, w = E.shape[:2]
+    PN, H, HL = _history_arrays("temporal_accumulate_cur", E.shape, prev_normal_depth, hist, hist_len)
+    out, out_len = np.empty_like(E), np.empty((h, w), np.float32)
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_cur(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(E), _p(N), _p(PN),
+                                            _p(H), _p(HL), C.byref(p), _p(out), _p(out_len)), "pt_temporal_accumulate_cur")
+    return out, out_len
+
+
+def temporal_accumulate_cur_device(w, h, camera, camera_prev, d_cur_ptr, d_normal_depth_ptr, d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr,
+                                   d_out_hist_ptr, d_out_hist_len_ptr, max_history=None, depth_tol=None, normal_tol=None, stream=0):
+    """pt_temporal_accumulate_cur_device: temporal_accumulate_device with the frame's (e, V) buffer in place of its sums."""
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_cur_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, d_cur_ptr,
+                                                   d_normal_depth_ptr, d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None,
+                                                   C.byref(p), d_out_hist_ptr, d_out_hist_len_ptr, stream or None),
+           "pt_temporal_accumulate_cur_device")
+
+
+def upsample_defaults():
+    """pt_upsample_defaults as a dict: sigma_normal, sigma_depth."""
+    p = UpsampleParams()
+    lib().pt_upsample_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in UpsampleParams._fields_}
+
+
+def _upsample_params(sigma_normal, sigma_depth):
+    p = UpsampleParams()
+    lib().pt_upsample_defaults(C.byref(p))
+    for f, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+        if v is not None:
+            setattr(p, f, v)
+    return p
+
+
+def scaled_camera(camera, scale):
+    """pt_camera_scaled: the camera of the low-res frame of render scale `scale` (w and h divided, nothing else changed)."""
+    out = Camera()
+    _check(lib().pt_camera_scaled(C.byref(camera), int(scale), C.byref(out)), "pt_camera_scaled")
+    return out
+
+
+def upsample(scale, rgba_sum_lo, sq_sum_lo, spp, batches, albedo_lo, normal_depth_lo, albedo, normal_depth, sigma_normal=None, sigma_depth=None):
+    """pt_upsample (host, blocking): a frame rendered with scaled_camera(cam, scale) (render_moments' sums of `spp` samples in
+    `batches` batches and render_aovs' buffers, [h / scale, w / scale, 4] float32) brought to the display size of albedo and
+    normal_depth ([h, w, 4], render_aovs with cam). Returns cur [h, w, 4]: e and V in denoise_var's working format, V = -1 for a
+    pass-through pixel; temporal_accumulate_cur and denoise_hist read it."""
+    A, N = _f4_frames("upsample", (("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = A.shape[:2]
+    scale = int(scale)
+    lo_shape = (h // scale, w // scale, 4) if scale > 0 else None
+    S, Q, Al, Nl = _f4_frames("upsample", (("rgba_sum_lo", rgba_sum_lo), ("sq_sum_lo", sq_sum_lo), ("albedo_lo", albedo_lo),
+                                           ("normal_depth_lo", normal_depth_lo)), lo_shape)
+    out = np.empty_like(A)
+    p = _upsample_params(sigma_normal, sigma_depth)
+    _check(lib().pt_upsample(w, h, scale, _p(S), _p(Q), int(spp), int(batches), _p(Al), _p(Nl), _p(A), _p(N), C.byref(p), _p(out)), "pt_upsample")
+    return out
+
+
+def upsample_device(w, h, scale, d_rgba_sum_lo_ptr, d_sq_sum_lo_ptr, spp, batches, d_albedo_lo_ptr, d_normal_depth_lo_ptr, d_albedo_ptr,
+                    d_normal_depth_ptr, d_out_cur_ptr, sigma_normal=None, sigma_depth=None, stream=0):
+    """pt_upsample_device: device buffers ((w / scale) * (h / scale) float4 for the four low-res ones, w*h float4 for the guides
+    and the output), asynchronous on `stream`, no workspace. The output must not alias an input."""
+    p = _upsample_params(sigma_normal, sigma_depth)
+    _check(lib().pt_upsample_device(w, h, int(scale), d_rgba_sum_lo_ptr, d_sq_sum_lo_ptr, int(spp), int(batches), d_albedo_lo_ptr,
+                                    d_normal_depth_lo_ptr, d_albedo_ptr, d_normal_depth_ptr, C.byref(p), d_out_cur_ptr, stream or None),
+           "pt_upsample_device")
 
 
 def denoise_hist_workspace_bytes(w, h):
@@ -913,6 +1005,16 @@ class TemporalHistory:
             raise PtError("TemporalHistory: frame is %s, the history %d x %d" % (rgba_sum.shape, self.w, self.h))
         self.hist, self.hist_len = temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, self.camera,
                                                        self.normal_depth, self.hist, self.hist_len, **self.params)
+        self.camera = Camera.frombytes(camera.tobytes())
+        self.normal_depth = normal_depth.copy()
+        return self.hist
+
+    def push_cur(self, camera, cur, normal_depth):
+        """push() for a frame given as (e, V) working pixels (upsample's output): frames of any render scale share the history."""
+        if cur.shape != (self.h, self.w, 4):
+            raise PtError("TemporalHistory: frame is %s, the history %d x %d" % (cur.shape, self.w, self.h))
+        self.hist, self.hist_len = temporal_accumulate_cur(camera, cur, normal_depth, self.camera, self.normal_depth, self.hist, self.hist_len,
+                                                           **self.params)
         self.camera = Camera.frombytes(camera.tobytes())
         self.normal_depth = normal_depth.copy()
         return self.hist
@@ -972,7 +1074,7 @@ def preview_defaults():
 class Preview:
     """pt_preview: the device buffers of one w x h viewer of `scene` (which must outlive it) and one call per frame:
     render_moments -> render_aovs -> temporal_accumulate -> denoise_hist -> resolve on the device, history and guide ping-ponged
-    there. Keyword arguments are pt_preview_params' fields (spp, batches, max_depth, integrator, use_mis, aov_spp, temporal,
+    there (set_scale: the beauty pass at a fraction of the resolution, upsampled by the guides). Keyword arguments are pt_preview_params' fields (spp, batches, max_depth, integrator, use_mis, aov_spp, temporal,
     filter) and those of the three stages (max_history, depth_tol, normal_tol; iterations, sigma_var, sigma_normal, sigma_depth;
     tonemap, exposure); what is left out takes the library's default."""
 
@@ -1001,6 +1103,16 @@ class Preview:
         """Drop the history: the next frame is a first frame."""
         _check(lib().pt_preview_reset(self.handle), "pt_preview_reset")
         return self
+
+    def set_scale(self, scale):
+        """pt_preview_set_scale: the frames that follow render their beauty pass at 1 / scale of the size in each axis (1..8, a
+        divisor of w and h) and upsample it with the full-resolution guides; 1 is the full-resolution frame. History carries over."""
+        _check(lib().pt_preview_set_scale(self.handle, int(scale)), "pt_preview_set_scale")
+        return self
+
+    @property
+    def scale(self):
+        return lib().pt_preview_scale(self.handle)
 
     def read(self, rgba8=True, mean=True, hist=None, hist_len=None):
         """pt_preview_read: the last good frame's outputs as a dict of the requested arrays: rgba8 [h,w,4] uint8, mean [h,w,4]

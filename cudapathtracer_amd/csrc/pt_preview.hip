@@ -8,6 +8,8 @@
 //   pt_preview          a session that owns the device buffers of one w x h viewer and runs render_moments -> render_aovs ->
 //                       temporal_accumulate -> denoise_hist -> resolve per frame on one stream through the public *_device entry
 //                       points, ping-ponging history and guide. Nothing crosses PCIe unless pt_preview_read asks for it.
+//                       With a render scale s > 1 (pt_preview_set_scale) the moments render runs at 1/s of the size in each axis and
+//                       pt_upsample + pt_temporal_accumulate_cur bring it into the same display-size history.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -51,9 +53,9 @@ __global__ void __launch_bounds__(256) resolve_kernel(int w, int h, const float4
     out8[p] = r | (g << 8) | (b << 16) | 0xff000000u;
 }
 
-static int pv_fail(int code, const char* fmt, int a = 0, int b = 0) {
+static int pv_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
     char buf[256];
-    snprintf(buf, sizeof(buf), fmt, a, b);
+    snprintf(buf, sizeof(buf), fmt, a, b, c, d);
     return pt_fail_(code, buf);
 }
 #define PV_HIP_OK(expr)                                                                                            \
@@ -114,6 +116,10 @@ struct pt_preview {
     char* pool;
     char *S, *Q, *A, *N[2], *H[2], *L[2]; // sums, albedo; guide, history and history length twice (temporal 0: one guide only)
     char *ws, *filt, *mean, *rgba8;       // the filters' workspace, the filtered frame, the displayed mean and its bytes
+    int scale;                            // render scale of the next frame; > 1 uses the buffers below (their own allocations)
+    char* lo;                             // four low-res float4 buffers of loCap pixels each: S, Q, albedo, guide
+    size_t loCap;
+    char* curEV;                          // w*h float4: pt_upsample's output
     int cur;
     bool haveHist, haveFrame;
     pt_camera prevCam;
@@ -178,6 +184,8 @@ void pt_preview_destroy(pt_preview* p) {
         if (e) (void)hipEventDestroy(e);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     if (p->pool) (void)hipFree(p->pool);
+    if (p->lo) (void)hipFree(p->lo);
+    if (p->curEV) (void)hipFree(p->curEV);
     delete p;
 }
 
@@ -202,7 +210,7 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
     if (bad) return nullptr;
 
     pt_preview* p = new pt_preview();      // zeroed
-    p->scene = scene; p->w = w; p->h = h; p->P = P;
+    p->scene = scene; p->w = w; p->h = h; p->P = P; p->scale = 1;
     const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
     const size_t ws = (pt_denoise_var_workspace_bytes(w, h) + 15) & ~(size_t)15;
     const int pairs = P.temporal ? 2 : 1;
@@ -227,6 +235,71 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 int pt_preview_reset(pt_preview* p) {
     if (!p) return pv_fail(-1, "pt_preview_reset: null session");
     p->haveHist = p->haveFrame = false;
+    return 0;
+}
+
+int pt_preview_set_scale(pt_preview* p, int scale) {
+    if (!p) return pv_fail(-1, "pt_preview_set_scale: null session");
+    if (scale < 1 || scale > 8) return pv_fail(-1, "pt_preview_set_scale: scale %d must be 1..8", scale);
+    if (p->w % scale != 0 || p->h % scale != 0)
+        return pv_fail(-1, "pt_preview_set_scale: scale %d must divide the session's size %d x %d", scale, p->w, p->h);
+    if (scale > 1) {                      // (no frame is in flight: pt_preview_frame blocks)
+        const size_t need = (size_t)(p->w / scale) * (p->h / scale);
+        char* cur = p->curEV;
+        char* lo = nullptr;
+        bool ok = cur || hipMalloc(&cur, (size_t)p->w * p->h * 16) == hipSuccess;
+        if (ok && need > p->loCap) ok = hipMalloc(&lo, 4 * need * 16) == hipSuccess;
+        if (!ok) {
+            if (cur && !p->curEV) (void)hipFree(cur);
+            return pv_fail(-2, "pt_preview_set_scale: could not allocate the buffers of scale %d", scale);
+        }
+        p->curEV = cur;
+        if (lo) {
+            if (p->lo) (void)hipFree(p->lo);
+            p->lo = lo; p->loCap = need;
+        }
+    }
+    p->scale = scale;
+    return 0;
+}
+
+int pt_preview_scale(pt_preview* p) { return p ? p->scale : pv_fail(-1, "pt_preview_scale: null session"); }
+
+// A frame at render scale s > 1: the same five events around low-res moments | both feature passes | upsample + accumulate |
+// filter | resolve.
+static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
+    const pt_preview_params& P = p->P;
+    const int w = p->w, h = p->h, s = p->scale, wl = w / s, hl = h / s;
+    hipStream_t st = p->stream;
+    if (cam->w != w || cam->h != h)       // (before the low-res camera is made: the stages would see a size that need not divide)
+        return pv_fail(-1, "pt_preview_frame: camera is %d x %d, the session %d x %d", cam->w, cam->h, w, h);
+    pt_camera lowCam;
+    if (int r = pt_camera_scaled(cam, s, &lowCam)) return r;
+    const size_t lb = p->loCap * 16;
+    char *S = p->lo, *Q = S + lb, *Al = Q + lb, *Nl = Al + lb;
+    PV_HIP_OK(hipEventRecord(p->ev[0], st));
+    if (int r = pt_render_moments_device(p->scene, &lowCam, wl, hl, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, S, Q, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[1], st));
+    if (int r = pt_render_aovs_device(p->scene, &lowCam, wl, hl, P.aov_spp, seed, Al, Nl, st)) return r;
+    if (int r = pt_render_aovs_device(p->scene, cam, w, h, P.aov_spp, seed, p->A, p->N[nxt], st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[2], st));
+    if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[nxt], nullptr, p->curEV, st)) return r;
+    const void* shown = p->curEV;         // the (e, V) buffer the filter reads
+    if (P.temporal) {
+        const bool hist = p->haveHist;
+        if (int r = pt_temporal_accumulate_cur_device(w, h, cam, hist ? &p->prevCam : nullptr, p->curEV, p->N[nxt], hist ? p->N[p->cur] : nullptr,
+                                                      hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt],
+                                                      p->L[nxt], st))
+            return r;
+        shown = p->H[nxt];
+    }
+    PV_HIP_OK(hipEventRecord(p->ev[3], st));
+    pt_denoise_var_params F = P.filter_params;
+    if (!P.filter) F.iterations = 0;
+    if (int r = pt_denoise_hist_device(w, h, shown, p->A, p->N[nxt], &F, p->ws, p->filt, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[4], st));
+    if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[5], st));
     return 0;
 }
 
@@ -272,7 +345,7 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     if (!p) return pv_fail(-1, "pt_preview_frame: null session");
     if (!cam) return pv_fail(-1, "pt_preview_frame: null camera");
     const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
-    const int r = preview_stages(p, cam, seed, nxt);
+    const int r = p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt) : preview_stages(p, cam, seed, nxt);
     const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
     if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
     if (e != hipSuccess) return pv_fail(-2, "pt_preview_frame: the stream failed to synchronise");

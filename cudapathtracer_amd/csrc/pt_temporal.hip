@@ -9,6 +9,8 @@
 //                                       the previous camera; up to four bilinear taps of the previous history, each checked
 //                                       against the previous guide; the blend. IDENT: both cameras are the same bytes, the tap
 //                                       is the pixel itself and no projection is computed.
+//   temporal_accumulate_cur_kernel<IDENT>  the same with this frame's (e, V) read from a buffer (pt_upsample's output): the two
+//                                       kernels share temporal_blend, everything after the working pixel.
 // Both cameras travel by value as kernel arguments (SGPRs); plain cached float4 loads, no LDS.
 #include <cmath>
 #include <cstdio>
@@ -61,20 +63,13 @@ __device__ inline void temporal_tap(TemporalTap& t, int w, int h, int xq, int yq
     t.sw += wt;
 }
 
+// Steps 2-5 of the contract for a pixel whose working value `cur` (e, V >= 0) is known: reproject, gather, blend, write.
 template <bool IDENT>
-__global__ void __launch_bounds__(256) temporal_accumulate_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ sum,
-                                                                  const float4* __restrict__ sq, float spp, float batches,
-                                                                  const float4* __restrict__ albedo, const float4* __restrict__ nd,
-                                                                  const float4* __restrict__ prevNd, const float4* __restrict__ hist,
-                                                                  const float* __restrict__ histLen, float maxHistory, float depthTol,
-                                                                  float normalTol, float4* __restrict__ outHist, float* __restrict__ outLen) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= w || y >= h) return;
+__device__ inline void temporal_blend(int w, int h, int x, int y, float4 cur, const TemporalCam& cam, const TemporalCam& prev,
+                                      const float4* __restrict__ nd, const float4* __restrict__ prevNd, const float4* __restrict__ hist,
+                                      const float* __restrict__ histLen, float maxHistory, float depthTol, float normalTol,
+                                      float4* __restrict__ outHist, float* __restrict__ outLen) {
     const size_t p = (size_t)y * w + x;
-    float4 m;
-    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
-    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
     float4 res = cur;
     float len = 1.0f;
     if (hist != nullptr) {                                    // (uniform: a kernel argument)
@@ -123,9 +118,43 @@ __global__ void __launch_bounds__(256) temporal_accumulate_kernel(int w, int h, 
     outLen[p] = len;
 }
 
-static int tp_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
+template <bool IDENT>
+__global__ void __launch_bounds__(256) temporal_accumulate_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ sum,
+                                                                  const float4* __restrict__ sq, float spp, float batches,
+                                                                  const float4* __restrict__ albedo, const float4* __restrict__ nd,
+                                                                  const float4* __restrict__ prevNd, const float4* __restrict__ hist,
+                                                                  const float* __restrict__ histLen, float maxHistory, float depthTol,
+                                                                  float normalTol, float4* __restrict__ outHist, float* __restrict__ outLen) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    float4 m;
+    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
+    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
+    temporal_blend<IDENT>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
+}
+
+// pt_temporal_accumulate_cur: this frame's working pixel is given (pt_upsample wrote it), not derived from S and Q.
+template <bool IDENT>
+__global__ void __launch_bounds__(256) temporal_accumulate_cur_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ curIn,
+                                                                      const float4* __restrict__ nd, const float4* __restrict__ prevNd,
+                                                                      const float4* __restrict__ hist, const float* __restrict__ histLen,
+                                                                      float maxHistory, float depthTol, float normalTol,
+                                                                      float4* __restrict__ outHist, float* __restrict__ outLen) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    const float4 cur = curIn[p];
+    if (!(cur.w >= 0.0f)) { outHist[p] = make_float4(cur.x, cur.y, cur.z, -1.0f); outLen[p] = 0.0f; return; }
+    temporal_blend<IDENT>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
+}
+
+static int tp_fail(int code, const char* fn, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
     char buf[256];
-    snprintf(buf, sizeof(buf), fmt, a, b, c, d);
+    const int n = snprintf(buf, sizeof(buf), "%s: ", fn);
+    snprintf(buf + n, sizeof(buf) - n, fmt, a, b, c, d);
     return pt_fail_(code, buf);
 }
 #define TP_HIP_OK(expr)                                                                                            \
@@ -142,33 +171,50 @@ static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
     return pa < pb + bBytes && pb < pa + aBytes;
 }
 
-static int check_temporal_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* sum, const void* sq, int spp, int batches,
-                               const void* albedo, const void* nd, const void* prevNd, const void* hist, const void* histLen,
-                               const pt_temporal_params& P, const void* outHist, const void* outLen) {
-    if (w <= 0 || h <= 0) return tp_fail(-1, "pt_temporal_accumulate: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return tp_fail(-1, "pt_temporal_accumulate: image of %d x %d pixels is too large", w, h);
-    if (spp <= 0) return tp_fail(-1, "pt_temporal_accumulate: spp %d must be positive", spp);
-    if (batches < 2) return tp_fail(-1, "pt_temporal_accumulate: batches %d must be at least 2", batches);
-    if (spp % batches != 0) return tp_fail(-1, "pt_temporal_accumulate: batches %d must divide spp %d", batches, spp);
-    if (!cam) return tp_fail(-1, "pt_temporal_accumulate: null camera");
-    if (cam->w != w || cam->h != h) return tp_fail(-1, "pt_temporal_accumulate: camera is %d x %d, the frame %d x %d", cam->w, cam->h, w, h);
-    if (prev && (prev->w != w || prev->h != h))
-        return tp_fail(-1, "pt_temporal_accumulate: previous camera is %d x %d, the frame %d x %d", prev->w, prev->h, w, h);
-    if (!sum || !sq || !albedo || !nd) return tp_fail(-1, "pt_temporal_accumulate: null buffer");
-    if (!outHist || !outLen) return tp_fail(-1, "pt_temporal_accumulate: null output");
+// What both entry points check after their own frame inputs (`inputs`: none of this frame's buffers is NULL).
+static int check_history_args(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* prev, bool inputs, const void* prevNd,
+                              const void* hist, const void* histLen, const pt_temporal_params& P, const void* outHist, const void* outLen) {
+    if (!cam) return tp_fail(-1, fn, "null camera");
+    if (cam->w != w || cam->h != h) return tp_fail(-1, fn, "camera is %d x %d, the frame %d x %d", cam->w, cam->h, w, h);
+    if (prev && (prev->w != w || prev->h != h)) return tp_fail(-1, fn, "previous camera is %d x %d, the frame %d x %d", prev->w, prev->h, w, h);
+    if (!inputs) return tp_fail(-1, fn, "null buffer");
+    if (!outHist || !outLen) return tp_fail(-1, fn, "null output");
     const int given = (prevNd != nullptr) + (hist != nullptr) + (histLen != nullptr);
-    if (given != 0 && given != 3)
-        return tp_fail(-1, "pt_temporal_accumulate: prev_normal_depth, hist and hist_len must be all NULL (first frame) or all set");
+    if (given != 0 && given != 3) return tp_fail(-1, fn, "prev_normal_depth, hist and hist_len must be all NULL (first frame) or all set");
     if (given == 3) {
         const size_t n = (size_t)w * h;
         if (overlaps(outHist, n * 16, hist, n * 16) || overlaps(outLen, n * 4, histLen, n * 4) || overlaps(outHist, n * 16, histLen, n * 4) ||
             overlaps(outLen, n * 4, hist, n * 16))
-            return tp_fail(-1, "pt_temporal_accumulate: the output history must not alias the input history (ping-pong two pairs)");
+            return tp_fail(-1, fn, "the output history must not alias the input history (ping-pong two pairs)");
     }
-    if (P.max_history < 1) return tp_fail(-1, "pt_temporal_accumulate: max_history %d must be at least 1", P.max_history);
-    if (!(P.depth_tol > 0.0f) || !std::isfinite(P.depth_tol)) return tp_fail(-1, "pt_temporal_accumulate: depth_tol must be positive and finite");
-    if (!(P.normal_tol > 0.0f) || !(P.normal_tol <= 1.0f)) return tp_fail(-1, "pt_temporal_accumulate: normal_tol must be in (0, 1]");
+    if (P.max_history < 1) return tp_fail(-1, fn, "max_history %d must be at least 1", P.max_history);
+    if (!(P.depth_tol > 0.0f) || !std::isfinite(P.depth_tol)) return tp_fail(-1, fn, "depth_tol must be positive and finite");
+    if (!(P.normal_tol > 0.0f) || !(P.normal_tol <= 1.0f)) return tp_fail(-1, fn, "normal_tol must be in (0, 1]");
     return 0;
+}
+
+static int check_size(const char* fn, int w, int h) {
+    if (w <= 0 || h <= 0) return tp_fail(-1, fn, "image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return tp_fail(-1, fn, "image of %d x %d pixels is too large", w, h);
+    return 0;
+}
+
+static int check_temporal_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* sum, const void* sq, int spp, int batches,
+                               const void* albedo, const void* nd, const void* prevNd, const void* hist, const void* histLen,
+                               const pt_temporal_params& P, const void* outHist, const void* outLen) {
+    const char* fn = "pt_temporal_accumulate";
+    if (int r = check_size(fn, w, h)) return r;
+    if (spp <= 0) return tp_fail(-1, fn, "spp %d must be positive", spp);
+    if (batches < 2) return tp_fail(-1, fn, "batches %d must be at least 2", batches);
+    if (spp % batches != 0) return tp_fail(-1, fn, "batches %d must divide spp %d", batches, spp);
+    return check_history_args(fn, w, h, cam, prev, sum && sq && albedo && nd, prevNd, hist, histLen, P, outHist, outLen);
+}
+
+static int check_temporal_cur_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* cur, const void* nd, const void* prevNd,
+                                   const void* hist, const void* histLen, const pt_temporal_params& P, const void* outHist, const void* outLen) {
+    const char* fn = "pt_temporal_accumulate_cur";
+    if (int r = check_size(fn, w, h)) return r;
+    return check_history_args(fn, w, h, cam, prev, cur && nd, prevNd, hist, histLen, P, outHist, outLen);
 }
 
 static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* sum, const float4* sq, int spp, int batches,
@@ -183,6 +229,22 @@ static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* 
     else
         hipLaunchKernelGGL(temporal_accumulate_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
                            prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    TP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int temporal_cur_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* cur, const float4* nd, const float4* prevNd,
+                               const float4* hist, const float* histLen, const pt_temporal_params& P, float4* outHist, float* outLen,
+                               hipStream_t stream) {
+    const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
+    const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
+    const dim3 grid((w + 15) / 16, (h + 15) / 16);
+    if (ident)
+        hipLaunchKernelGGL(temporal_accumulate_cur_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen,
+                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else
+        hipLaunchKernelGGL(temporal_accumulate_cur_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen,
+                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
     TP_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -236,13 +298,55 @@ int pt_temporal_accumulate(int w, int h, const pt_camera* cam, const pt_camera* 
     if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
     int r = 0;
     if (e != hipSuccess) {
-        r = tp_fail(-2, "pt_temporal_accumulate: upload failed");
+        r = tp_fail(-2, "pt_temporal_accumulate", "upload failed");
     } else if ((r = temporal_launch(w, h, cam, cam_prev, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN,
                                     first ? nullptr : (const float4*)dPN, first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P,
                                     (float4*)dO, (float*)dOL, nullptr)) == 0) {
         e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = tp_fail(-2, "pt_temporal_accumulate: download failed");
+        if (e != hipSuccess) r = tp_fail(-2, "pt_temporal_accumulate", "download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+int pt_temporal_accumulate_cur_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur, const void* d_normal_depth,
+                                      const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len, const pt_temporal_params* params,
+                                      void* d_out_hist, void* d_out_hist_len, void* stream) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, d_cur, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, P, d_out_hist,
+                                        d_out_hist_len))
+        return r;
+    return temporal_cur_launch(w, h, cam, cam_prev, (const float4*)d_cur, (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth,
+                               (const float4*)d_hist, (const float*)d_hist_len, P, (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream);
+}
+
+int pt_temporal_accumulate_cur(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
+                               const float* prev_normal_depth, const float* hist, const float* hist_len, const pt_temporal_params* params,
+                               float* out_hist, float* out_hist_len) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, P, out_hist, out_hist_len)) return r;
+    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
+    const bool first = hist == nullptr;
+    char* d = nullptr;
+    TP_HIP_OK(hipMalloc(&d, 5 * b16 + 2 * b4));
+    char* dC = d; char* dN = dC + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16; char* dHL = dO + b16; char* dOL = dHL + b4;
+    hipError_t e = hipMemcpy(dC, cur, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = tp_fail(-2, "pt_temporal_accumulate_cur", "upload failed");
+    } else if ((r = temporal_cur_launch(w, h, cam, cam_prev, (const float4*)dC, (const float4*)dN, first ? nullptr : (const float4*)dPN,
+                                        first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P, (float4*)dO, (float*)dOL,
+                                        nullptr)) == 0) {
+        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = tp_fail(-2, "pt_temporal_accumulate_cur", "download failed");
     }
     (void)hipFree(d);
     return r;

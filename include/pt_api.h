@@ -498,6 +498,61 @@ int pt_denoise_hist(int w, int h, const float* hist, const float* albedo, const 
 int pt_denoise_hist_device(int w, int h, const void* d_hist, const void* d_albedo, const void* d_normal_depth,
                            const pt_denoise_var_params* params, void* d_workspace, void* d_out, void* stream);   /* async */
 
+/* ---- render scale: a low-resolution frame upsampled by full-resolution guides ------------------------------------------------
+ * pt_camera_scaled: *out = *cam with w and h divided by `scale`; nothing else in the struct depends on the size. -1 unless
+ * 1 <= scale <= 8 and scale divides cam->w and cam->h (and on a NULL pointer). Host only. The unjittered ray of pixel X of the
+ * scaled camera passes through display coordinate scale * X (camera_ray's jitter is centred on 0, and (float)w / (float)h is
+ * the same number for both sizes), so low-res pixel X sits exactly on display pixel scale * X.
+ *
+ * pt_upsample: a stateless post-process like pt_denoise*. In: the low-res frame of the scaled camera, wl x hl = (w / s) x (h / s)
+ * float4 each: rgba_sum, sq_sum (pt_render_moments, spp samples in `batches` batches), albedo_lo, normal_depth_lo
+ * (pt_render_aovs); and the display camera's albedo and normal_depth, w x h float4. Out: cur, w x h float4 in pt_denoise_var's
+ * working format (rgb = e, w = V; V = -1 marks a PASS-THROUGH pixel whose rgb holds a raw mean): what pt_temporal_accumulate_cur
+ * and pt_denoise_hist read. Re-modulated by the full-resolution albedo there, texture and material edges come back at display
+ * resolution. Per display pixel p = (x, y), in f32 with IEEE rounding and no contraction, left to right:
+ *   1. X0 = x / s, Y0 = y / s (integer division); fx = (float)(x - s X0) / (float)s, fy likewise.
+ *   2. Taps k = (X0 + dx, Y0 + dy) in the order (0,0), (1,0), (0,1), (1,1) with the bilinear weights b_k = (1 - fx)(1 - fy),
+ *      fx (1 - fy), (1 - fx) fy, fx fy. A tap is a CANDIDATE if b_k > 0 and it lies inside the low-res image; USABLE if it is a
+ *      candidate and its working pixel (m_k, e_k, V_k: pt_denoise_var's from S_k, Q_k, albedo_lo_k, spp, batches) is not
+ *      pass-through. Tap (0,0) is always a candidate.
+ *   3. n_p, z_p from normal_depth_p and n_k, z_k from normal_depth_lo_k, normalised as pt_denoise normalises them.
+ *      w_k = b_k max(0, n_p . n_k)^sigma_normal exp(-|z_p - z_k| / (sigma_depth z_p)), formed as pt_denoise_var forms w_n w_z
+ *      (one exp2 of sigma_normal log2(n_p . n_k) - |z_p - z_k| (log2(e) / (sigma_depth z_p))); 0 if either normal is zero. A usable
+ *      tap whose w_k is not > 0 (0 or NaN) is skipped, never multiplied in: its values may be NaN.
+ *   4. W = sum of w_k over the usable, non-skipped taps, in tap order. W >= 1e-4: e = sum w_k e_k / W, V = sum (w_k w_k) V_k / (W W).
+ *   5. FALLBACK otherwise: (e_k, V_k) of the usable tap with the largest b_k (the first in tap order wins a tie), bit for bit.
+ *   6. PASS-THROUGH if !(albedo_p.w > 0) (nothing hit at display resolution) or if no tap is usable: (m_k.rgb, -1) of the
+ *      candidate tap with the largest b_k, the first on ties (m = S / spp, the raw mean).
+ * V is a pixel's own variance: neighbouring display pixels share taps, so their errors are correlated and a later filter's
+ * sum w^2 V rule understates what it leaves. Arguments are checked before any HIP call: image size, 2 <= scale
+ * <= 8 dividing w and h, spp, batches (>= 2, a divisor of spp), NULL pointers, the output overlapping an input, params. Host and
+ * device form are bit-identical; the device form is asynchronous on `stream` and needs no workspace. */
+typedef struct pt_upsample_params {
+    float sigma_normal;          /* exponent on the normals' cosine (finite, >= 0) */
+    float sigma_depth;           /* relative depth difference (finite, > 0) */
+                                 /* defaults 64, 0.10: DESIGN.md "Render scale" */
+} pt_upsample_params;
+void pt_upsample_defaults(pt_upsample_params* out);
+int pt_camera_scaled(const pt_camera* cam, int scale, pt_camera* out);
+int pt_upsample(int w, int h, int scale, const float* rgba_sum_lo, const float* sq_sum_lo, int spp, int batches, const float* albedo_lo,
+                const float* normal_depth_lo, const float* albedo, const float* normal_depth, const pt_upsample_params* params,
+                float* out_cur);                                                                                 /* host, blocking */
+int pt_upsample_device(int w, int h, int scale, const void* d_rgba_sum_lo, const void* d_sq_sum_lo, int spp, int batches,
+                       const void* d_albedo_lo, const void* d_normal_depth_lo, const void* d_albedo, const void* d_normal_depth,
+                       const pt_upsample_params* params, void* d_out_cur, void* stream);                         /* async */
+
+/* pt_temporal_accumulate with step 1 replaced: this frame's working pixel (e_cur, V_cur) is read from cur (w*h float4, as
+ * pt_upsample writes it) instead of derived from S, Q, spp, batches and albedo. A pixel with !(cur.w >= 0) passes through: it
+ * writes (cur.rgb, -1) and length 0. Steps 2-5, the identity path, the aliasing rule and the checks of the size, the cameras,
+ * the history pointers and params are pt_temporal_accumulate's. Frames of any render scale blend into one history this way. */
+int pt_temporal_accumulate_cur(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
+                               const float* prev_normal_depth, const float* hist, const float* hist_len, const pt_temporal_params* params,
+                               float* out_hist, float* out_hist_len);                                            /* host, blocking */
+int pt_temporal_accumulate_cur_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur,
+                                      const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist,
+                                      const void* d_hist_len, const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len,
+                                      void* stream);                                                             /* async */
+
 /* ---- preview: display bytes on the device, and a session that owns a viewer's buffers ------------------------------
  * pt_resolve: a stateless post-process like pt_denoise*: radiance in, what a viewer shows out. Per pixel p, in f32 with IEEE
  * rounding and no contraction, left to right:
@@ -542,7 +597,20 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  * allocates everything the session owns; temporal_params and filter_params are checked by their stages. The scene must outlive
  * the session and is not to be rendered from another thread during a frame. pt_preview_read copies the last good frame's
  * outputs to the host (any pointer may be NULL; hist / hist_len need temporal 1; -1 before the first frame after create / reset).
- * The device pointers stay valid until destroy; their contents are the last good frame's. */
+ * The device pointers stay valid until destroy; their contents are the last good frame's.
+ *
+ * RENDER SCALE. pt_preview_set_scale(p, s): s = 1 (the default) is the frame above, bit for bit. s = 2..8 must divide the
+ * session's w and h (-1 otherwise, the scale unchanged); the first such call allocates four low-res float4 buffers and one
+ * w*h float4 `cur`, a later one grows the low-res buffers if its low-res frame is larger (-2 if that fails, the scale and the
+ * buffers unchanged). A scaled frame runs, on the same stream and through the public entry points: pt_camera_scaled ->
+ * pt_render_moments_device with the low-res camera -> pt_render_aovs_device with the low-res camera and the beauty's seed ->
+ * pt_render_aovs_device with the display camera and the same seed (into the guide half of the ping-pong) -> pt_upsample_device ->
+ *   temporal 1: pt_temporal_accumulate_cur_device from the previous good frame's camera, guide and history, then
+ *               pt_denoise_hist_device on the new history, then pt_resolve_device(spp = 1);
+ *   temporal 0: pt_denoise_hist_device on cur itself (filter 0: with 0 iterations), then pt_resolve_device(spp = 1).
+ * History, its lengths, the guide and the previous camera are display-size at every scale, so the scale may change from frame
+ * to frame without a reset. A failed scaled frame leaves the session as a failed frame does above. Stats of a scaled frame:
+ * render_ms is the low-res moments render, aov_ms both feature passes, accumulate_ms the upsample and the accumulation. */
 typedef struct pt_preview pt_preview;
 typedef struct pt_preview_params {
     int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
@@ -562,6 +630,8 @@ void pt_preview_defaults(pt_preview_params* out);
 pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_params* params);   /* NULL on error: pt_last_error() */
 int  pt_preview_frame(pt_preview* p, const pt_camera* camera, uint64_t seed);
 int  pt_preview_reset(pt_preview* p);                                      /* the next frame is a first frame */
+int  pt_preview_set_scale(pt_preview* p, int scale);                       /* 1..8: the render scale of the frames that follow */
+int  pt_preview_scale(pt_preview* p);                                      /* the current scale; -1 on a NULL session */
 int  pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len);
 const void* pt_preview_device_rgba8(pt_preview* p);                        /* w*h*4 bytes */
 const void* pt_preview_device_mean(pt_preview* p);                         /* w*h float4 */

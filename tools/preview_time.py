@@ -1,13 +1,15 @@
 """Wall time of one preview frame at 1920x1080: the pt_preview session next to the chain of host calls it replaces, in one run.
 
-    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3]
+    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3 --scale 1 --scene cornell]
 
 Both render the same moving-camera sequence (tests/temporal_seq.py's camera) of the Cornell box with the session's defaults
 (4 spp in 2 batches, depth 8, MIS, 1 feature ray, temporal accumulation, the history filter, tone map). The host chain is
 render_moments + render_aovs + TemporalHistory.push + denoise_hist + finalise + the tone map, gamma and byte conversion in numpy:
 every buffer crosses PCIe, most of them twice. Prints one JSON line: the median and the minimum wall time of a frame for both
 (host clock around calls that end in a device synchronise), the session's median stage times from its HIP events, the host
-chain's median time per call, and whether the last frames' bytes agree."""
+chain's median time per call, and whether the last frames' bytes agree. --scale N runs both at render scale N (the beauty pass at
+1 / N of the size in each axis, upsampled by the guides: the host chain then goes through scaled_camera, upsample and
+TemporalHistory.push_cur); --scene blob renders the 82 k-triangle blob in the box, whose tree lives in HBM."""
 import argparse
 import json
 import os
@@ -25,6 +27,8 @@ def main():
     ap.add_argument("--h", type=int, default=1080)
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--scale", type=int, default=1)
+    ap.add_argument("--scene", choices=("cornell", "blob"), default="cornell")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -37,12 +41,14 @@ def main():
     w, h = a.w, a.h
     d = api.preview_defaults()
     spp, batches, depth = d["spp"], d["batches"], d["max_depth"]
-    sc = api.Scene(api.HostScene(scenes.cornell(tempfile.mkdtemp(), width=w, height=h, spp=spp, max_depth=depth, name="pvt")["config"]))
+    make = scenes.cornell if a.scene == "cornell" else scenes.blob_in_box
+    sc = api.Scene(api.HostScene(make(tempfile.mkdtemp(), width=w, height=h, spp=spp, max_depth=depth, name="pvt")["config"]))
+    s = a.scale
     n = a.warmup + a.frames
     cams = [Q.camera(api, t, True, w, h) for t in range(n)]
     med = lambda v: round(sorted(v)[len(v) // 2], 4)
 
-    pv = api.Preview(sc, w, h)
+    pv = api.Preview(sc, w, h).set_scale(s)
     wall, stages = [], []
     for t in range(n):
         t0 = time.perf_counter()
@@ -51,7 +57,7 @@ def main():
         stages.append(pv.stats())
     session8 = pv.read(mean=False, hist=False, hist_len=False)["rgba8"]
     pv.close()
-    res = {"w": w, "h": h, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth,
+    res = {"w": w, "h": h, "scene": a.scene, "scale": s, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth,
            "session_frame_ms_median": med(wall[a.warmup:]), "session_frame_ms_min": round(min(wall[a.warmup:]), 4)}
     for k in ("render_ms", "aov_ms", "accumulate_ms", "filter_ms", "resolve_ms", "total_ms"):
         res["session_" + k + "_median"] = med([s[k] for s in stages[a.warmup:]])
@@ -60,9 +66,17 @@ def main():
     wall, parts = [], {k: [] for k in ("render_moments", "render_aovs", "push", "denoise_hist", "finalise", "bytes_numpy")}
     for t in range(n):
         marks = [time.perf_counter()]
-        S, Qs = sc.render_moments(cams[t], w, h, spp, spp // batches, depth, seed=Q.SEED0 + t); marks.append(time.perf_counter())
-        A, N = sc.render_aovs(cams[t], w, h, aov_spp=1, seed=Q.SEED0 + t); marks.append(time.perf_counter())
-        hist = th.push(cams[t], S, Qs, spp, batches, A, N); marks.append(time.perf_counter())
+        lo = api.scaled_camera(cams[t], s)
+        S, Qs = sc.render_moments(lo, w // s, h // s, spp, spp // batches, depth, seed=Q.SEED0 + t); marks.append(time.perf_counter())
+        A, N = sc.render_aovs(cams[t], w, h, aov_spp=1, seed=Q.SEED0 + t)
+        if s > 1:
+            Al, Nl = sc.render_aovs(lo, w // s, h // s, aov_spp=1, seed=Q.SEED0 + t)
+        marks.append(time.perf_counter())
+        if s > 1:
+            hist = th.push_cur(cams[t], api.upsample(s, S, Qs, spp, batches, Al, Nl, A, N), N)
+        else:
+            hist = th.push(cams[t], S, Qs, spp, batches, A, N)
+        marks.append(time.perf_counter())
         filt = api.denoise_hist(hist, A, N); marks.append(time.perf_counter())
         mean = api.finalise(filt, 1); marks.append(time.perf_counter())
         host8 = R.display(mean); marks.append(time.perf_counter())
