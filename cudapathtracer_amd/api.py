@@ -100,6 +100,10 @@ class PreviewStats(C.Structure):     # pt_preview_stats
                 ("filter_ms", C.c_float), ("resolve_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class ConvergeParams(C.Structure):   # pt_converge_params
+    _fields_ = [("threshold", C.c_float), ("min_history", C.c_int32)]
+
+
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("chunk_spp", C.c_int32), ("threshold", C.c_float)]
 
@@ -235,6 +239,18 @@ def lib():
     L.pt_preview_device_mean.restype = vp; L.pt_preview_device_mean.argtypes = [vp]
     L.pt_preview_last_stats.argtypes = [vp, C.POINTER(PreviewStats)]
     L.pt_preview_destroy.restype = None; L.pt_preview_destroy.argtypes = [vp]
+    L.pt_converge_defaults.restype = None; L.pt_converge_defaults.argtypes = [C.POINTER(ConvergeParams)]
+    L.pt_temporal_select.argtypes = [i32, i32, vp, vp, C.POINTER(ConvergeParams), vp, vp, vp, vp]
+    L.pt_temporal_select_device.argtypes = [i32, i32, vp, vp, C.POINTER(ConvergeParams), vp, vp, vp, vp, vp]
+    L.pt_render_moments_tiles.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp, vp]
+    L.pt_render_moments_tiles_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp, vp, vp]
+    L.pt_temporal_accumulate_live.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                              C.POINTER(TemporalParams), vp, vp]
+    L.pt_temporal_accumulate_live_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                     C.POINTER(TemporalParams), vp, vp, vp]
+    L.pt_preview_set_converge.argtypes = [vp, C.POINTER(ConvergeParams)]
+    L.pt_preview_last_live.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pt_preview_read_tiles.argtypes = [vp, vp, vp]
     _lib = L
     return L
 
@@ -534,6 +550,27 @@ class Scene:
         """pt_render_moments_device: the same into device buffers of w*h float4 each. Blocks; the work is enqueued on `stream`."""
         _check(lib().pt_render_moments_device(self.h, C.byref(camera), w, h, spp, batch_spp, max_depth, integrator, int(use_mis), seed,
                                               d_rgba_sum_ptr, d_sq_sum_ptr, stream or None), "pt_render_moments_device")
+
+    def render_moments_tiles(self, camera, w, h, spp, batch_spp, max_depth, tile_list, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED):
+        """pt_render_moments_tiles: render_moments on the 8x8 tiles of `tile_list` (int32 [count], strictly ascending tile numbers,
+        row-major over the tile grid). Returns (S, Q) as render_moments does: its values on the listed tiles, S = 0 and Q.rgb = 0
+        elsewhere, Q.w the number of batches everywhere."""
+        if not isinstance(tile_list, np.ndarray) or tile_list.dtype != np.int32 or tile_list.ndim != 1:
+            raise PtError("render_moments_tiles: tile_list must be a one-dimensional int32 array")
+        lst = np.ascontiguousarray(tile_list)
+        S = np.zeros((h, w, 4), np.float32)
+        Q = np.zeros((h, w, 4), np.float32)
+        _check(lib().pt_render_moments_tiles(self.h, C.byref(camera), w, h, spp, batch_spp, max_depth, integrator, int(use_mis), seed,
+                                             _p(lst) if lst.size else None, int(lst.size), _p(S), _p(Q)), "pt_render_moments_tiles")
+        return S, Q
+
+    def render_moments_tiles_device(self, camera, w, h, spp, batch_spp, max_depth, d_tile_list_ptr, count, d_rgba_sum_ptr, d_sq_sum_ptr,
+                                    integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, stream=0):
+        """pt_render_moments_tiles_device: the same from a device list of `count` tiles (trusted) into device buffers of w*h float4
+        each. Blocks; the work is enqueued on `stream`."""
+        _check(lib().pt_render_moments_tiles_device(self.h, C.byref(camera), w, h, spp, batch_spp, max_depth, integrator, int(use_mis), seed,
+                                                    d_tile_list_ptr or None, int(count), d_rgba_sum_ptr, d_sq_sum_ptr, stream or None),
+               "pt_render_moments_tiles_device")
 
     def launch_unidirectional(self, max_depth, camera, num_sample, use_mis, w, h, d_colors_ptr):
         _check(lib().pt_launch_unidirectional(max_depth, camera, self.h, num_sample, int(use_mis), w, h, d_colors_ptr), "pt_launch_unidirectional")
@@ -887,6 +924,84 @@ def temporal_accumulate_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_s
                                                d_out_hist_ptr, d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_device")
 
 
+def _tile_map(what, tile_live, h, w):
+    shape = ((h + 7) // 8, (w + 7) // 8)
+    if not isinstance(tile_live, np.ndarray) or tile_live.dtype != np.int32 or tile_live.shape != shape:
+        raise PtError("%s: tile_live must be an int32 [%d, %d] array for a %d x %d frame" % (what, shape[0], shape[1], w, h))
+    return np.ascontiguousarray(tile_live)
+
+
+def temporal_accumulate_live(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, tile_live,
+                             camera_prev=None, max_history=None, depth_tol=None, normal_tol=None):
+    """pt_temporal_accumulate_live (host, blocking): temporal_accumulate for a resting camera with a map of live tiles (int32
+    [ceil(h/8), ceil(w/8)], as temporal_select returns it; None = every tile live). A tile whose entry is 0 keeps its history and
+    length bit for bit; the others blend this frame in. camera_prev must be None or equal to camera. Returns new (hist, hist_len)."""
+    S, Q, A, N = _f4_frames("temporal_accumulate_live", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = S.shape[:2]
+    PN, H, HL = _history_arrays("temporal_accumulate_live", S.shape, prev_normal_depth, hist, hist_len)
+    T = _tile_map("temporal_accumulate_live", tile_live, h, w) if tile_live is not None else None
+    out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_live(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q),
+                                             int(spp), int(batches), _p(A), _p(N), _p(PN), _p(H), _p(HL), _p(T), C.byref(p), _p(out),
+                                             _p(out_len)), "pt_temporal_accumulate_live")
+    return out, out_len
+
+
+def temporal_accumulate_live_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr,
+                                    d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_tile_live_ptr, d_out_hist_ptr, d_out_hist_len_ptr,
+                                    max_history=None, depth_tol=None, normal_tol=None, stream=0):
+    """pt_temporal_accumulate_live_device: temporal_accumulate_device plus the device map of live tiles (0 / None: every tile)."""
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_live_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
+                                                    d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
+                                                    d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None,
+                                                    d_tile_live_ptr or None, C.byref(p), d_out_hist_ptr, d_out_hist_len_ptr, stream or None),
+           "pt_temporal_accumulate_live_device")
+
+
+def converge_defaults():
+    """pt_converge_defaults as a dict: threshold, min_history."""
+    p = ConvergeParams()
+    lib().pt_converge_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in ConvergeParams._fields_}
+
+
+def _converge_params(threshold, min_history):
+    p = ConvergeParams()
+    lib().pt_converge_defaults(C.byref(p))
+    if threshold is not None:
+        p.threshold = threshold
+    if min_history is not None:
+        p.min_history = int(min_history)
+    return p
+
+
+def temporal_select(hist, hist_len, threshold=None, min_history=None):
+    """pt_temporal_select (host, blocking): which 8x8 tiles of a history still need samples. hist is [h,w,4] float32, hist_len
+    [h,w] float32. Returns (tile_err float32 [ceil(h/8), ceil(w/8)], tile_live int32 of the same shape, live_list: the live
+    tiles' numbers, ascending int32). A None parameter takes the library default (converge_defaults())."""
+    H, = _f4_frames("temporal_select", (("hist", hist),))
+    h, w = H.shape[:2]
+    if not isinstance(hist_len, np.ndarray) or hist_len.dtype != np.float32 or hist_len.shape != (h, w):
+        raise PtError("temporal_select: hist_len must be a float32 [%d, %d] array" % (h, w))
+    HL = np.ascontiguousarray(hist_len)
+    ty, tx = (h + 7) // 8, (w + 7) // 8
+    err, live, lst, cnt = np.empty((ty, tx), np.float32), np.empty((ty, tx), np.int32), np.empty(ty * tx, np.int32), np.zeros(1, np.int32)
+    p = _converge_params(threshold, min_history)
+    _check(lib().pt_temporal_select(w, h, _p(H), _p(HL), C.byref(p), _p(err), _p(live), _p(lst), _p(cnt)), "pt_temporal_select")
+    return err, live, lst[:int(cnt[0])].copy()
+
+
+def temporal_select_device(w, h, d_hist_ptr, d_hist_len_ptr, d_tile_err_ptr, d_tile_live_ptr, d_list_ptr, d_count_ptr, threshold=None,
+                           min_history=None, stream=0):
+    """pt_temporal_select_device: device buffers (one float, one int32 and one list slot per 8x8 tile, one int32 count),
+    asynchronous on `stream`."""
+    p = _converge_params(threshold, min_history)
+    _check(lib().pt_temporal_select_device(w, h, d_hist_ptr, d_hist_len_ptr, C.byref(p), d_tile_err_ptr, d_tile_live_ptr, d_list_ptr,
+                                           d_count_ptr, stream or None), "pt_temporal_select_device")
+
+
 def temporal_accumulate_cur(camera, cur, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None, hist_len=None, max_history=None,
                             depth_tol=None, normal_tol=None):
     """pt_temporal_accumulate_cur (host, blocking): temporal_accumulate with this frame's working pixels given in `cur` ([h,w,4]
@@ -1113,6 +1228,30 @@ class Preview:
     @property
     def scale(self):
         return lib().pt_preview_scale(self.handle)
+
+    def set_converge(self, threshold=None, min_history=None):
+        """pt_preview_set_converge: while the camera rests, the frames that follow render only the 8x8 tiles whose history has
+        not converged (temporal_select's rule) and carry the others forward. threshold 0 (or False) turns it off, None takes the
+        library default; off is a session's initial state."""
+        if threshold is False:
+            _check(lib().pt_preview_set_converge(self.handle, None), "pt_preview_set_converge")
+            return self
+        p = _converge_params(threshold, min_history)
+        _check(lib().pt_preview_set_converge(self.handle, C.byref(p)), "pt_preview_set_converge")
+        return self
+
+    def last_live(self):
+        """pt_preview_last_live: (live tiles, all tiles) of the last good frame; they are equal on a frame that did not converge."""
+        live, total = C.c_int(-1), C.c_int(-1)
+        _check(lib().pt_preview_last_live(self.handle, C.byref(live), C.byref(total)), "pt_preview_last_live")
+        return live.value, total.value
+
+    def read_tiles(self):
+        """pt_preview_read_tiles: (tile_err float32, tile_live int32), both [ceil(h/8), ceil(w/8)], of the last converging frame."""
+        ty, tx = (self.h + 7) // 8, (self.w + 7) // 8
+        err, live = np.empty((ty, tx), np.float32), np.empty((ty, tx), np.int32)
+        _check(lib().pt_preview_read_tiles(self.handle, _p(err), _p(live)), "pt_preview_read_tiles")
+        return err, live
 
     def read(self, rgba8=True, mean=True, hist=None, hist_len=None):
         """pt_preview_read: the last good frame's outputs as a dict of the requested arrays: rgba8 [h,w,4] uint8, mean [h,w,4]

@@ -65,6 +65,7 @@ struct pt_scene {
     DevBuf aovSpill, aovOut;                          // pt_render_aovs: its own traversal spill area / host-form staging
     DevBuf adS, adM, adH, adList, adKeep, adCount, adOut, adSpp, adErr;   // pt_render_adaptive: sums, snapshot, half sums, live lists; host-form staging
     DevBuf moS, moP, moQ, moOut;                      // pt_render_moments: sums, previous sums, squared batch sums (tile-major); host-form staging
+    DevBuf moList;                                    // pt_render_moments_tiles, host form: the tile list on the device
     int variant = 0;                                  // 0 megakernel, 1 wavefront (pt_set_variant)
     int numCU = 256;
     DeviceScene ds{};
@@ -149,7 +150,7 @@ void pt_scene_destroy(pt_scene* s) {
     DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves, &s->wnodes, &s->qnodes, &s->leafBox, &s->mids,
                      &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
                      &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr,
-                     &s->moS, &s->moP, &s->moQ, &s->moOut};
+                     &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1219,8 +1220,11 @@ static int check_moments_args(pt_scene* s, const pt_camera* cam, int w, int h, i
 // B = spp / c ordinary launches of c samples into the scene's own zeroed accumulator, the first seeding the streams as pt_render
 // does and the others continuing them; after each the bookkeeping pass, a wait, and the check pt_render makes of its launch (the
 // tile queue's words; the wavefront variant checks itself). A batch that fails ends the call. dS, dQ: device, scan-line.
+// With a list (pt_render_moments_tiles: `live` tiles, a device array, ascending) every launch renders the listed tiles through the
+// tile queue, as render_adaptive's do. The streams are still seeded for the whole frame and the bookkeeping pass and the untile
+// still cover it: S stays 0 where nothing was rendered, so Q.rgb does too. An empty list launches no render at all.
 static int render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int c, int maxDepth, int integrator, int useMIS,
-                          uint64_t seed, float4* dS, float4* dQ, hipStream_t stream) {
+                          uint64_t seed, float4* dS, float4* dQ, hipStream_t stream, bool listed = false, const int* list = nullptr, int live = -1) {
     TileSpan t;
     if (int r = resolve_tiles(w, h, nullptr, t)) return r;
     const int T = t.count, B = spp / c;
@@ -1230,8 +1234,9 @@ static int render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int s
     if (int r = s->moQ.ensure(tileBytes)) return r;
     float4 *S = (float4*)s->moS.p, *P = (float4*)s->moP.p, *Q = (float4*)s->moQ.p;
     HIP_OK(hipMemsetAsync(S, 0, tileBytes, stream));                  // this call writes the sums: they start at 0
-    for (int j = 0; j < B; j++) {
-        if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, j > 0)) return r;
+    if (listed && live == 0) HIP_OK(launch_moments_update(T, S, P, Q, true, B, stream));    // the zero frame: Q = (0, 0, 0, B)
+    for (int j = 0; j < B && !(listed && live == 0); j++) {
+        if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, j > 0, listed ? list : nullptr, live)) return r;
         HIP_OK(launch_moments_update(T, S, P, Q, j == 0, B, stream));
         int q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const bool queued = s->queue.p && s->variant == 0 && s->lastLaunchQueued;
@@ -1245,6 +1250,54 @@ static int render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int s
     HIP_OK(hipStreamSynchronize(stream));
     return 0;
 }
+
+// What the list forms check before check_moments_args: the image size (the tile count derives from it), the count and the list.
+static int check_moments_list_args(int w, int h, const void* list, int count) {
+    if (w <= 0 || h <= 0) return fail(-1, "pt_render_moments_tiles: image size %d x %d must be positive", w, h);
+    const long long T = (long long)((w + 7) / 8) * ((h + 7) / 8);
+    if (count < 0 || count > T) return fail(-1, "pt_render_moments_tiles: count %d must lie in 0..%lld, the frame's tiles", count, T);
+    if (count > 0 && !list) return fail(-1, "pt_render_moments_tiles: null tile list");
+    return 0;
+}
+static int check_moments_list_variant(pt_scene* s) {
+    if (s->variant != 0) return fail(-1, "pt_render_moments_tiles: the wavefront variant has no tile queue; select the megakernel (pt_set_variant 0)");
+    return 0;
+}
+
+extern "C" {
+
+int pt_render_moments_tiles_device(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int batch_spp, int max_depth, int integrator,
+                                   int use_mis, uint64_t seed, const void* d_tile_list, int count, void* d_rgba_sum, void* d_sq_sum,
+                                   void* stream) {
+    if (int r = check_moments_list_args(w, h, d_tile_list, count)) return r;
+    if (int r = check_moments_args(s, cam, w, h, spp, batch_spp, integrator, d_rgba_sum, d_sq_sum)) return r;
+    if (int r = check_moments_list_variant(s)) return r;
+    return render_moments(s, cam, w, h, spp, batch_spp, max_depth, integrator, use_mis, seed, (float4*)d_rgba_sum, (float4*)d_sq_sum,
+                          (hipStream_t)stream, true, (const int*)d_tile_list, count);
+}
+
+int pt_render_moments_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int batch_spp, int max_depth, int integrator, int use_mis,
+                            uint64_t seed, const int32_t* tile_list, int count, float* out_rgba_sum, float* out_sq_sum) {
+    if (int r = check_moments_list_args(w, h, tile_list, count)) return r;
+    const int T = ((w + 7) / 8) * ((h + 7) / 8);
+    for (int i = 0; i < count; i++)
+        if (tile_list[i] < 0 || tile_list[i] >= T || (i > 0 && tile_list[i] <= tile_list[i - 1]))
+            return fail(-1, "pt_render_moments_tiles: tile_list[%d] = %d: the list must be strictly ascending within 0..%d", i, tile_list[i], T - 1);
+    if (int r = check_moments_args(s, cam, w, h, spp, batch_spp, integrator, out_rgba_sum, out_sq_sum)) return r;
+    if (int r = check_moments_list_variant(s)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    if (int r = s->moOut.ensure(2 * bytes)) return r;
+    if (int r = s->moList.ensure((size_t)std::max(count, 1) * sizeof(int))) return r;
+    if (count > 0) HIP_OK(hipMemcpy(s->moList.p, tile_list, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+    char* d = (char*)s->moOut.p;
+    if (int r = render_moments(s, cam, w, h, spp, batch_spp, max_depth, integrator, use_mis, seed, (float4*)d, (float4*)(d + bytes), nullptr, true,
+                               (const int*)s->moList.p, count)) return r;
+    HIP_OK(hipMemcpy(out_rgba_sum, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_sq_sum, d + bytes, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
 
 extern "C" {
 

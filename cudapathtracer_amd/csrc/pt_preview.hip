@@ -10,6 +10,8 @@
 //                       points, ping-ponging history and guide. Nothing crosses PCIe unless pt_preview_read asks for it.
 //                       With a render scale s > 1 (pt_preview_set_scale) the moments render runs at 1/s of the size in each axis and
 //                       pt_upsample + pt_temporal_accumulate_cur bring it into the same display-size history.
+//                       With converge on (pt_preview_set_converge) a frame whose camera rests selects the tiles that still need
+//                       samples from the history, renders moments on that list alone and carries the other tiles' history forward.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +23,8 @@
 extern "C" int pt_fail_(int code, const char* msg);
 
 namespace pt {
+
+int check_converge_params(const char* fn, const pt_converge_params& P);       // pt_converge.hip
 
 // novum_host.cpp's clamp01, aces and to_byte, operation for operation (-ffp-contract=off: nothing fuses).
 __device__ inline float rs_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
@@ -124,6 +128,16 @@ struct pt_preview {
     bool haveHist, haveFrame;
     pt_camera prevCam;
     pt_preview_stats stats;
+    // converge (pt_preview_set_converge): one allocation holding the tile error and the live map twice (a converging frame writes
+    // the half that curT does not name and flips with the history), the live list and its count
+    bool converge;
+    pt_converge_params C;
+    char* tiles;
+    char *tErr[2], *tLive[2], *tList, *tCount;
+    int curT;
+    bool haveTiles;
+    int lastLive;                         // live tiles of the last good frame (its total is the frame's tile count)
+    int frameLive; bool frameConverged;   // what the frame in flight found; committed with the flip
 };
 
 extern "C" {
@@ -186,6 +200,7 @@ void pt_preview_destroy(pt_preview* p) {
     if (p->pool) (void)hipFree(p->pool);
     if (p->lo) (void)hipFree(p->lo);
     if (p->curEV) (void)hipFree(p->curEV);
+    if (p->tiles) (void)hipFree(p->tiles);
     delete p;
 }
 
@@ -234,7 +249,7 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 
 int pt_preview_reset(pt_preview* p) {
     if (!p) return pv_fail(-1, "pt_preview_reset: null session");
-    p->haveHist = p->haveFrame = false;
+    p->haveHist = p->haveFrame = p->haveTiles = false;
     return 0;
 }
 
@@ -264,6 +279,75 @@ int pt_preview_set_scale(pt_preview* p, int scale) {
 }
 
 int pt_preview_scale(pt_preview* p) { return p ? p->scale : pv_fail(-1, "pt_preview_scale: null session"); }
+
+int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
+    if (!p) return pv_fail(-1, "pt_preview_set_converge: null session");
+    if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
+    if (int r = check_converge_params("pt_preview_set_converge", *params)) return r;
+    if (!p->tiles) {                      // (no frame is in flight: pt_preview_frame blocks)
+        const size_t tb = ((size_t)((p->w + 7) / 8) * ((p->h + 7) / 8) * 4 + 15) & ~(size_t)15;
+        if (hipMalloc(&p->tiles, 5 * tb + 16) != hipSuccess) {
+            p->tiles = nullptr;
+            return pv_fail(-2, "pt_preview_set_converge: could not allocate the tile buffers");
+        }
+        char* c = p->tiles;
+        for (int i = 0; i < 2; i++) { p->tErr[i] = c; c += tb; p->tLive[i] = c; c += tb; }
+        p->tList = c; c += tb; p->tCount = c;
+    }
+    p->converge = true;
+    p->C = *params;
+    return 0;
+}
+
+int pt_preview_last_live(pt_preview* p, int* live, int* total) {
+    if (!p) return pv_fail(-1, "pt_preview_last_live: null session");
+    if (!p->haveFrame) return pv_fail(-1, "pt_preview_last_live: no frame since the session was created or reset");
+    if (live) *live = p->lastLive;
+    if (total) *total = ((p->w + 7) / 8) * ((p->h + 7) / 8);
+    return 0;
+}
+
+int pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live) {
+    if (!p) return pv_fail(-1, "pt_preview_read_tiles: null session");
+    if (!p->haveTiles) return pv_fail(-1, "pt_preview_read_tiles: no converging frame since the session was created or reset");
+    const size_t tb = (size_t)((p->w + 7) / 8) * ((p->h + 7) / 8) * 4;
+    if (tile_err) PV_HIP_OK(hipMemcpy(tile_err, p->tErr[p->curT], tb, hipMemcpyDeviceToHost));
+    if (tile_live) PV_HIP_OK(hipMemcpy(tile_live, p->tLive[p->curT], tb, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// A converging frame (the camera rests, a history exists, scale 1): the same five events around select + read-back + moments on
+// the live list | the whole feature pass | the accumulation with the live map | filter | resolve.
+static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
+    const pt_preview_params& P = p->P;
+    const int w = p->w, h = p->h, T = ((w + 7) / 8) * ((h + 7) / 8), nt = p->curT ^ 1;
+    hipStream_t st = p->stream;
+    PV_HIP_OK(hipEventRecord(p->ev[0], st));
+    if (int r = pt_temporal_select_device(w, h, p->H[p->cur], p->L[p->cur], &p->C, p->tErr[nt], p->tLive[nt], p->tList, p->tCount, st)) return r;
+    int count = -1;
+    PV_HIP_OK(hipMemcpyAsync(&count, p->tCount, sizeof(int), hipMemcpyDeviceToHost, st));
+    PV_HIP_OK(hipStreamSynchronize(st));
+    if (count < 0 || count > T) return pv_fail(-2, "pt_preview_frame: the live list holds %d of %d tiles", count, T);
+    if (count > 0)
+        if (int r = pt_render_moments_tiles_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->tList,
+                                                   count, p->S, p->Q, st))
+            return r;
+    PV_HIP_OK(hipEventRecord(p->ev[1], st));
+    if (int r = pt_render_aovs_device(p->scene, cam, w, h, P.aov_spp, seed, p->A, p->N[nxt], st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[2], st));
+    if (int r = pt_temporal_accumulate_live_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt], p->N[p->cur], p->H[p->cur],
+                                                   p->L[p->cur], p->tLive[nt], &P.temporal_params, p->H[nxt], p->L[nxt], st))
+        return r;
+    PV_HIP_OK(hipEventRecord(p->ev[3], st));
+    pt_denoise_var_params F = P.filter_params;
+    if (!P.filter) F.iterations = 0;
+    if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[nxt], &F, p->ws, p->filt, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[4], st));
+    if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
+    PV_HIP_OK(hipEventRecord(p->ev[5], st));
+    p->frameLive = count; p->frameConverged = true;
+    return 0;
+}
 
 // A frame at render scale s > 1: the same five events around low-res moments | both feature passes | upsample + accumulate |
 // filter | resolve.
@@ -345,7 +429,10 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     if (!p) return pv_fail(-1, "pt_preview_frame: null session");
     if (!cam) return pv_fail(-1, "pt_preview_frame: null camera");
     const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
-    const int r = p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt) : preview_stages(p, cam, seed, nxt);
+    p->frameLive = ((p->w + 7) / 8) * ((p->h + 7) / 8); p->frameConverged = false;
+    const bool rests = p->converge && p->P.temporal && p->scale == 1 && p->haveHist && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
+    const int r = rests ? preview_stages_converge(p, cam, seed, nxt)
+                        : (p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt) : preview_stages(p, cam, seed, nxt));
     const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
     if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
     if (e != hipSuccess) return pv_fail(-2, "pt_preview_frame: the stream failed to synchronise");
@@ -356,6 +443,8 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     p->haveHist = p->P.temporal != 0;
     p->haveFrame = true;
     p->prevCam = *cam;
+    p->lastLive = p->frameLive;
+    if (p->frameConverged) { p->curT ^= 1; p->haveTiles = true; }
     p->stats.frames++;
     p->stats.render_ms = ms[0]; p->stats.aov_ms = ms[1]; p->stats.accumulate_ms = ms[2]; p->stats.filter_ms = ms[3]; p->stats.resolve_ms = ms[4];
     p->stats.total_ms = total;

@@ -11,6 +11,11 @@
 //                                       is the pixel itself and no projection is computed.
 //   temporal_accumulate_cur_kernel<IDENT>  the same with this frame's (e, V) read from a buffer (pt_upsample's output): the two
 //                                       kernels share temporal_blend, everything after the working pixel.
+//   temporal_accumulate_live_kernel    the identity instantiation with a map of live 8x8 tiles (pt_temporal_accumulate_live: a
+//                                       resting viewer whose converged tiles were not rendered). A wave is one tile, so the
+//                                       map entry is one scalar load and the branch does not diverge: a carried wave copies its
+//                                       history and length (two loads, two stores), a live wave runs temporal_accumulate_kernel<true>'s
+//                                       code.
 // Both cameras travel by value as kernel arguments (SGPRs); plain cached float4 loads, no LDS.
 #include <cmath>
 #include <cstdio>
@@ -135,6 +140,31 @@ __global__ void __launch_bounds__(256) temporal_accumulate_kernel(int w, int h, 
     temporal_blend<IDENT>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
 }
 
+// pt_temporal_accumulate_live: the identity path with a tile map. tileLive[tile] == 0: the tile was not rendered this frame and
+// keeps its history and length bit for bit (S, Q and albedo are not read there).
+__global__ void __launch_bounds__(256) temporal_accumulate_live_kernel(int w, int h, int tilesX, const int32_t* __restrict__ tileLive,
+                                                                       const float4* __restrict__ sum, const float4* __restrict__ sq, float spp,
+                                                                       float batches, const float4* __restrict__ albedo, const float4* __restrict__ nd,
+                                                                       const float4* __restrict__ prevNd, const float4* __restrict__ hist,
+                                                                       const float* __restrict__ histLen, float maxHistory, float depthTol,
+                                                                       float normalTol, float4* __restrict__ outHist, float* __restrict__ outLen) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tx = blockIdx.x * 2 + (wave & 1), ty = blockIdx.y * 2 + (wave >> 1);
+    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;                             // (a tile outside the grid has no lane left: no read past the map)
+    const size_t p = (size_t)y * w + x;
+    if (tileLive[__builtin_amdgcn_readfirstlane(ty * tilesX + tx)] == 0) {
+        outHist[p] = hist[p];
+        outLen[p] = histLen[p];
+        return;
+    }
+    float4 m;
+    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
+    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
+    const TemporalCam none = {};                              // (the identity path reads neither camera)
+    temporal_blend<true>(w, h, x, y, cur, none, none, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
+}
+
 // pt_temporal_accumulate_cur: this frame's working pixel is given (pt_upsample wrote it), not derived from S and Q.
 template <bool IDENT>
 __global__ void __launch_bounds__(256) temporal_accumulate_cur_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ curIn,
@@ -210,6 +240,19 @@ static int check_temporal_args(int w, int h, const pt_camera* cam, const pt_came
     return check_history_args(fn, w, h, cam, prev, sum && sq && albedo && nd, prevNd, hist, histLen, P, outHist, outLen);
 }
 
+// What a tile map adds (pt_temporal_accumulate_live): the identity path and a history, and outputs that leave the map alone.
+static int check_live_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* hist, const void* tileLive, const void* outHist,
+                           const void* outLen) {
+    const char* fn = "pt_temporal_accumulate_live";
+    if (!tileLive) return 0;
+    if (!hist) return tp_fail(-1, fn, "a tile map needs a history: a carried pixel keeps what it had");
+    if (prev && memcmp(cam, prev, sizeof(pt_camera)) != 0)
+        return tp_fail(-1, fn, "a tile map needs an unchanged camera (cam_prev NULL or equal to cam): a carried pixel keeps what it had at the same place");
+    const size_t n = (size_t)w * h, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
+    if (overlaps(outHist, n * 16, tileLive, tb) || overlaps(outLen, n * 4, tileLive, tb)) return tp_fail(-1, fn, "the outputs must not alias the tile map");
+    return 0;
+}
+
 static int check_temporal_cur_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* cur, const void* nd, const void* prevNd,
                                    const void* hist, const void* histLen, const pt_temporal_params& P, const void* outHist, const void* outLen) {
     const char* fn = "pt_temporal_accumulate_cur";
@@ -219,11 +262,14 @@ static int check_temporal_cur_args(int w, int h, const pt_camera* cam, const pt_
 
 static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* sum, const float4* sq, int spp, int batches,
                            const float4* albedo, const float4* nd, const float4* prevNd, const float4* hist, const float* histLen,
-                           const pt_temporal_params& P, float4* outHist, float* outLen, hipStream_t stream) {
+                           const pt_temporal_params& P, float4* outHist, float* outLen, hipStream_t stream, const int32_t* tileLive = nullptr) {
     const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
     const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
-    if (ident)
+    if (tileLive)                                             // (check_live_args: the identity path, with a history)
+        hipLaunchKernelGGL(temporal_accumulate_live_kernel, grid, dim3(256), 0, stream, w, h, (w + 7) / 8, tileLive, sum, sq, (float)spp, (float)batches,
+                           albedo, nd, prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else if (ident)
         hipLaunchKernelGGL(temporal_accumulate_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
                            prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
     else
@@ -275,6 +321,38 @@ int pt_temporal_accumulate_device(int w, int h, const pt_camera* cam, const pt_c
                            (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream);
 }
 
+// The host forms of pt_temporal_accumulate and pt_temporal_accumulate_live (tileLive NULL: the former).
+static int temporal_host(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum,
+                         int spp, int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
+                         const float* hist_len, const int32_t* tileLive, const pt_temporal_params& P, float* out_hist, float* out_hist_len) {
+    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
+    const bool first = hist == nullptr;
+    char* d = nullptr;
+    TP_HIP_OK(hipMalloc(&d, 7 * b16 + 2 * b4 + (tileLive ? tb : 0)));
+    char* dS = d; char* dQ = dS + b16; char* dA = dQ + b16; char* dN = dA + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16;
+    char* dHL = dO + b16; char* dOL = dHL + b4; char* dT = dOL + b4;
+    hipError_t e = hipMemcpy(dS, rgba_sum, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, albedo, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && tileLive) e = hipMemcpy(dT, tileLive, tb, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = tp_fail(-2, fn, "upload failed");
+    } else if ((r = temporal_launch(w, h, cam, cam_prev, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN,
+                                    first ? nullptr : (const float4*)dPN, first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P,
+                                    (float4*)dO, (float*)dOL, nullptr, tileLive ? (const int32_t*)dT : nullptr)) == 0) {
+        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = tp_fail(-2, fn, "download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
 int pt_temporal_accumulate(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
                            int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
                            const float* hist_len, const pt_temporal_params* params, float* out_hist, float* out_hist_len) {
@@ -283,31 +361,37 @@ int pt_temporal_accumulate(int w, int h, const pt_camera* cam, const pt_camera* 
     if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
                                     out_hist, out_hist_len))
         return r;
-    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
-    const bool first = hist == nullptr;
-    char* d = nullptr;
-    TP_HIP_OK(hipMalloc(&d, 7 * b16 + 2 * b4));
-    char* dS = d; char* dQ = dS + b16; char* dA = dQ + b16; char* dN = dA + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16;
-    char* dHL = dO + b16; char* dOL = dHL + b4;
-    hipError_t e = hipMemcpy(dS, rgba_sum, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = tp_fail(-2, "pt_temporal_accumulate", "upload failed");
-    } else if ((r = temporal_launch(w, h, cam, cam_prev, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN,
-                                    first ? nullptr : (const float4*)dPN, first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P,
-                                    (float4*)dO, (float*)dOL, nullptr)) == 0) {
-        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = tp_fail(-2, "pt_temporal_accumulate", "download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    return temporal_host("pt_temporal_accumulate", w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist,
+                         hist_len, nullptr, P, out_hist, out_hist_len);
+}
+
+int pt_temporal_accumulate_live_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum, const void* d_sq_sum,
+                                       int spp, int batches, const void* d_albedo, const void* d_normal_depth, const void* d_prev_normal_depth,
+                                       const void* d_hist, const void* d_hist_len, const void* d_tile_live, const pt_temporal_params* params,
+                                       void* d_out_hist, void* d_out_hist_len, void* stream) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_args(w, h, cam, cam_prev, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, d_prev_normal_depth, d_hist,
+                                    d_hist_len, P, d_out_hist, d_out_hist_len))
+        return r;
+    if (int r = check_live_args(w, h, cam, cam_prev, d_hist, d_tile_live, d_out_hist, d_out_hist_len)) return r;
+    return temporal_launch(w, h, cam, cam_prev, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
+                           (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth, (const float4*)d_hist, (const float*)d_hist_len, P,
+                           (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream, (const int32_t*)d_tile_live);
+}
+
+int pt_temporal_accumulate_live(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
+                                int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
+                                const float* hist_len, const int32_t* tile_live, const pt_temporal_params* params, float* out_hist,
+                                float* out_hist_len) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
+                                    out_hist, out_hist_len))
+        return r;
+    if (int r = check_live_args(w, h, cam, cam_prev, hist, tile_live, out_hist, out_hist_len)) return r;
+    return temporal_host("pt_temporal_accumulate_live", w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth,
+                         hist, hist_len, tile_live, P, out_hist, out_hist_len);
 }
 
 int pt_temporal_accumulate_cur_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur, const void* d_normal_depth,

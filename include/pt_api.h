@@ -638,6 +638,90 @@ const void* pt_preview_device_mean(pt_preview* p);                         /* w*
 int  pt_preview_last_stats(pt_preview* p, pt_preview_stats* out);
 void pt_preview_destroy(pt_preview* p);
 
+/* ---- converge: a resting viewer stops sampling the 8x8 tiles whose history has converged ---------------------------------------
+ * Three stateless stages and the session's switch for them. Tiles are the 8x8 tiles of pt_tile_range, row-major over the
+ * ceil(w/8) x ceil(h/8) grid; T is their number. All arithmetic is f32 with IEEE rounding (division and sqrtf included) and no
+ * contraction, left to right.
+ *
+ * pt_temporal_select: which tiles of a history (pt_temporal_accumulate's hist and hist_len) still need samples. Per in-image
+ * pixel p of tile t:
+ *   p is EXEMPT if hist_p.w < 0 or any of hist_p's four values is NaN / Inf (pt_denoise_hist's pass-through rule): r_p = 0 and
+ *   p is never young, so it never holds its tile back (as a non-finite pixel never holds a tile of pt_render_adaptive back).
+ *   Otherwise lum = 0.2126f e.r + 0.7152f e.g + 0.0722f e.b (pt_denoise's constants on hist_p.rgb) and
+ *     r_p = sqrtf(V) / (1e-4f + sqrtf(lum))     with V = hist_p.w: the standard error of the mean over the root of the mean, the
+ *   shape of pt_render_adaptive's estimator; a NaN r_p (lum < 0) counts as 0. p is YOUNG if hist_len_p < (float)min_history.
+ *   E_t = max(0, r_p over the tile's in-image pixels). The tile is LIVE unless E_t < threshold and none of its pixels is young.
+ * Outputs: out_tile_err[t] = E_t (T floats), out_tile_live[t] = 1 or 0 (T int32), out_list = the live tiles in ascending order
+ * (room for T int32; the device form leaves the entries past the count as they were, the host form returns them as 0) and
+ * *out_count = their number. threshold 0 keeps every tile live. Host and device form are bit-identical, and a float maximum does
+ * not depend on its order, so the numpy restatement (tests/converge_ref.py) is exact as well. Arguments are checked before any
+ * HIP call: image size, NULL pointers, params, and no output may overlap an input or another output. The device form is
+ * asynchronous on `stream`; it needs no workspace from the caller (the library keeps one constant tile list per device and
+ * process, and waits for `stream` once when that list has to grow). params NULL = pt_converge_defaults. */
+typedef struct pt_converge_params {
+    float threshold;             /* a tile stops when E_t < threshold; 0 = never (every tile live); NaN / < 0 / Inf rejected */
+    int32_t min_history;         /* no tile stops while one of its filtered pixels has fewer frames (>= 1) */
+                                 /* defaults 0.5, 8: DESIGN.md "Converged tiles" */
+} pt_converge_params;
+void pt_converge_defaults(pt_converge_params* out);
+int pt_temporal_select(int w, int h, const float* hist, const float* hist_len, const pt_converge_params* params, float* out_tile_err,
+                       int32_t* out_tile_live, int32_t* out_list, int32_t* out_count);                             /* host, blocking */
+int pt_temporal_select_device(int w, int h, const void* d_hist, const void* d_hist_len, const pt_converge_params* params, void* d_tile_err,
+                              void* d_tile_live, void* d_list, void* d_count, void* stream);                       /* async */
+
+/* pt_render_moments_tiles: pt_render_moments on a list of tiles. A pixel's stream is keyed by the pixel alone, so the pixels
+ * of the listed tiles get S and Q equal to pt_render_moments' bit for bit; every other pixel gets S = 0 and Q.rgb = 0; Q.w =
+ * (float)B everywhere. count 0 launches no render and writes that zero frame. The host form takes a host list and refuses one
+ * that is not strictly ascending within 0..T-1 (-1); the device form takes a device list and the host-known count and trusts
+ * the list's contents (as pt_resolve_device trusts its map). count outside 0..T: -1. The megakernel only: with the wavefront
+ * variant selected the call fails with -1 and leaves the outputs untouched (list mode needs the tile queue, as
+ * pt_render_adaptive does); every launch uses the tile queue whatever the "persistent" option says. After every batch the host
+ * waits and checks the queue's words as pt_render_moments does: an unfinished listed tile fails the call with -4 and no further
+ * batch is launched. The scene's work buffers stay sized for the whole frame. Checks before any HIP call: image size, count and
+ * list, then pt_render_moments', then the variant. */
+int pt_render_moments_tiles(pt_scene* scene, const pt_camera* camera, int w, int h, int spp, int batch_spp, int max_depth, int integrator,
+                            int use_mis, uint64_t seed, const int32_t* tile_list, int count, float* out_rgba_sum,
+                            float* out_sq_sum);                                                                    /* host buffers */
+int pt_render_moments_tiles_device(pt_scene* scene, const pt_camera* camera, int w, int h, int spp, int batch_spp, int max_depth,
+                                   int integrator, int use_mis, uint64_t seed, const void* d_tile_list, int count, void* d_rgba_sum,
+                                   void* d_sq_sum, void* stream);                                                  /* device buffers */
+
+/* pt_temporal_accumulate_live: pt_temporal_accumulate with a map of live tiles (T int32, as pt_temporal_select writes it). A NULL
+ * map means every tile live: pt_temporal_accumulate bit for bit. A map is accepted only on the identity path with a history
+ * (cam_prev NULL or its 112 bytes equal to cam's, and the three history pointers set), -1 otherwise: a carried pixel has no
+ * sample of its own, so it can only keep what it had at the same place. In a tile whose entry is 0, out_hist_p = hist_p and
+ * out_hist_len_p = hist_len_p bit for bit, and S, Q and albedo are not read there: the length counts frames BLENDED, so a
+ * carried pixel does not age. In every other tile: pt_temporal_accumulate's result bit for bit. The outputs must not overlap the
+ * map. Everything else (checks, aliasing rule, params) is pt_temporal_accumulate's. */
+int pt_temporal_accumulate_live(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum,
+                                int spp, int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth,
+                                const float* hist, const float* hist_len, const int32_t* tile_live, const pt_temporal_params* params,
+                                float* out_hist, float* out_hist_len);                                             /* host, blocking */
+int pt_temporal_accumulate_live_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum,
+                                       const void* d_sq_sum, int spp, int batches, const void* d_albedo, const void* d_normal_depth,
+                                       const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len, const void* d_tile_live,
+                                       const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len, void* stream);  /* async */
+
+/* The session's switch. pt_preview_set_converge(p, params): NULL or threshold 0 turns it off; off is the default, and an off
+ * session is the session above bit for bit. The first call that turns it on allocates the session's tile buffers (-2, with the
+ * state unchanged, if that fails); params are checked as pt_temporal_select checks them (-1, the state unchanged).
+ * A frame CONVERGES only if converge is on, the session is temporal, the scale is 1, a history exists and the camera's 112 bytes
+ * equal the previous good frame's. Every other frame (a moved camera, a scale above 1, the first frame after create or reset,
+ * temporal 0) renders every tile exactly as above and reports live == total. A converging frame runs, on the session's stream
+ * and through the public entry points:
+ *   pt_temporal_select_device on the current history -> one 4-byte read-back of the count -> pt_render_moments_tiles_device
+ *   (skipped if the count is 0) -> pt_render_aovs_device on the full frame (the guide stays whole) ->
+ *   pt_temporal_accumulate_live_device -> pt_denoise_hist_device -> pt_resolve_device(spp = 1),
+ * so its results equal that chain of host calls bit for bit. The failed-frame rule holds unchanged: history, guide, camera, the
+ * tile map and the live count flip only after every stage was enqueued without error and the stream has synchronised.
+ * pt_preview_stats keeps its layout: render_ms of a converging frame includes the select stage and the read-back.
+ * pt_preview_last_live: the live and total tile counts of the last good frame (-1 before the first). pt_preview_read_tiles: E_t
+ * and the live map of the last converging frame (either pointer may be NULL; T entries each; -1 before the first converging
+ * frame since create / reset). */
+int  pt_preview_set_converge(pt_preview* p, const pt_converge_params* params);
+int  pt_preview_last_live(pt_preview* p, int* live, int* total);
+int  pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live);
+
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
 int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* out_exp, float* out_rsqrt, float* out_pow5);
