@@ -143,6 +143,7 @@ def lib():
     L.pt_scene_create.restype = vp; L.pt_scene_create.argtypes = [C.POINTER(SceneDesc)]
     L.pt_scene_create_from_mesh.restype = vp; L.pt_scene_create_from_mesh.argtypes = [C.POINTER(SceneDesc), i32, vp]
     L.pt_debug_packed.argtypes = [vp, i32, vp, C.c_size_t]
+    L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
     L.pt_render.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, u64, C.POINTER(TileRange), vp]
     L.pt_render_counted.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, u64, C.POINTER(TileRange), vp, vp]
@@ -390,6 +391,35 @@ class HostScene:
             pass
 
 
+def _desc_from_arrays(arrays):
+    """SceneDesc over arrays in the reference's layouts; the second value keeps the buffers it points into alive."""
+    a = {k: np.ascontiguousarray(v).view(np.uint8) for k, v in arrays.items()}
+    d = SceneDesc()
+    d.positions, d.n_positions = a["points"].ctypes.data, a["points"].size // 16
+    d.normals, d.n_normals = a["normals"].ctypes.data, a["normals"].size // 16
+    d.uvs, d.n_uvs = a["uvs"].ctypes.data, a["uvs"].size // 8
+    d.triangles, d.n_triangles = a["mesh"].ctypes.data, a["mesh"].size // 80
+    d.lights, d.n_lights = (a["lights"].ctypes.data if a["lights"].size else None), a["lights"].size // 80
+    d.bvh, d.n_nodes = a["bvh"].ctypes.data, a["bvh"].size // 48
+    d.bvh_indices = a["indices"].ctypes.data
+    d.materials, d.n_materials = a["materials"].ctypes.data, a["materials"].size // 176
+    t = a.get("textures")
+    d.textures, d.n_texels = (t.ctypes.data if t is not None and t.size else None), (t.size // 16 if t is not None else 0)
+    return d, a
+
+
+def light_triangles(host=None, arrays=None):
+    """pt_light_triangles (host only): per light the packed (leaf-order) triangle it was made from, or -1."""
+    if host is not None:
+        d, keep = host.desc, host
+    else:
+        d, keep = _desc_from_arrays(arrays)
+    out = np.full(max(d.n_lights, 1), -1, np.int32)
+    _check(lib().pt_light_triangles(C.byref(d), _p(out)), "pt_light_triangles")
+    del keep
+    return out[:d.n_lights]
+
+
 class Scene:
     """Device-resident, re-packed scene (pt_scene). Created on the CURRENT HIP device."""
 
@@ -445,18 +475,7 @@ class Scene:
     def from_arrays(arrays, options=None):
         """pt_scene_create straight from arrays in the reference's layouts (dict of buffers: points,
         normals, uvs, mesh, lights, bvh, indices, materials[, textures])."""
-        a = {k: np.ascontiguousarray(v).view(np.uint8) for k, v in arrays.items()}
-        d = SceneDesc()
-        d.positions, d.n_positions = a["points"].ctypes.data, a["points"].size // 16
-        d.normals, d.n_normals = a["normals"].ctypes.data, a["normals"].size // 16
-        d.uvs, d.n_uvs = a["uvs"].ctypes.data, a["uvs"].size // 8
-        d.triangles, d.n_triangles = a["mesh"].ctypes.data, a["mesh"].size // 80
-        d.lights, d.n_lights = (a["lights"].ctypes.data if a["lights"].size else None), a["lights"].size // 80
-        d.bvh, d.n_nodes = a["bvh"].ctypes.data, a["bvh"].size // 48
-        d.bvh_indices = a["indices"].ctypes.data
-        d.materials, d.n_materials = a["materials"].ctypes.data, a["materials"].size // 176
-        t = a.get("textures")
-        d.textures, d.n_texels = (t.ctypes.data if t is not None and t.size else None), (t.size // 16 if t is not None else 0)
+        d, _keep = _desc_from_arrays(arrays)
         return Scene(desc=d, options=options)
 
     @staticmethod

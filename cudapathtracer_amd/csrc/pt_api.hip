@@ -81,6 +81,7 @@ struct pt_scene {
     int refill = 1, refillKeep = 6;       // "refill" / "refill_keep": REFILL instantiation of the kernel for scenes in HBM (pt_trace.h: trace_resume)
     bool refillKeepSet = false;           // (unset: the 4-wave kernel of small shares uses kRefillKeepSmall — it is chain-bound and wants its lanes back sooner)
     bool cull = false;                    // pt_set_culling / "culling": opt-in, not parity-exact by construction
+    unsigned long long lightTri8 = 0ull;          // a byte per light, for the first 8: 1 + the packed triangle the light is, 0 = none (light_triangles); KParams::lightTri8
     bool leafBoxes = true;                        // "leaf_boxes" 0: the FLAT kernels walk the nodes in lockstep instead of testing the leaves' own boxes (A/B)
     int flat2Wanted = 1; int lastLaunchFlat2 = 0;   // "flat2" 1 (default): SIMPLE FLAT scenes trace shadow + extension ray in one FLAT pass (DEFER logic step)
     bool noLeafTris = false;                      // no triangle carries a MAT_LEAF material: a shadow ray is occluded by any hit (order-free)
@@ -185,6 +186,26 @@ static bool boxes_nested_and_finite(const std::vector<PNode>& pn, int nInternal)
         }
     }
     return true;
+}
+
+// For each light: the packed triangle (position in leaf order, the FLAT kernels' numbering) it was made from, or -1. The pair pass
+// leaves that triangle out of the tests of a shadow ray aimed at the light (pt_trace.h: trace_pair_flat), which is exact only if
+// the bounce's own test of the ray against the light (PLight a, b - a, c - a) and the pass's test against the triangle (PTri v0, e1,
+// e2) see the same operands: checked here bit for bit, on the records as the kernels read them. A light that is no triangle of
+// the scene, or whose vertices are in another order, gets -1 and its shadow rays are tested against everything.
+static void light_triangles(const PTri* pt, int nT, const pt_scene_desc* d, int32_t* out) {
+    for (int i = 0; i < d->n_lights; i++) {
+        out[i] = -1;
+        const pt_triangle& t = d->lights[i];
+        if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions) continue;
+        const pt_float4 a = d->positions[t.aInd], b = d->positions[t.bInd], c = d->positions[t.cInd];
+        const float v0[3] = {a.x, a.y, a.z}, e1[3] = {b.x - a.x, b.y - a.y, b.z - a.z}, e2[3] = {c.x - a.x, c.y - a.y, c.z - a.z};
+        for (int p = 0; p < nT && p < 63; p++) {                 // (the pair pass holds a ray's triangles in one 64-bit mask, and clears bit p as (1 << (p + 1)) >> 1)
+            const int idx = (int)(pt[p].idx & 0x7fffffffu);
+            if (idx >= d->n_triangles || d->triangles[idx].lightInd != i) continue;
+            if (!memcmp(pt[p].v0, v0, 12) && !memcmp(pt[p].e1, e1, 12) && !memcmp(pt[p].e2, e2, 12)) { out[i] = p; break; }
+        }
+    }
 }
 
 // Re-pack the reference's data model for gfx950.
@@ -450,6 +471,8 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
 #endif
     }
     if (int r = upload(s->lights, lights.data(), lights.size() * sizeof(PLight))) return r;
+    std::vector<int32_t> lightTri(lights.size(), -1);      // filled in below for the scenes the pair kernels can run
+    s->lightTri8 = 0ull;
     if (int r = upload(s->mats, mats.data(), mats.size() * sizeof(PMat))) return r;
     if (int r = upload(s->textures, d->textures, (size_t)std::max(d->n_texels, 0) * sizeof(float4))) return r;
     const std::vector<uint32_t>& jt = xorwow_host::jump_table();
@@ -505,6 +528,12 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (ok && nInternal > 0) HIP_OK(hipMemcpy(s->nodes.p, pn.data(), (size_t)nInternal * sizeof(PNode), hipMemcpyHostToDevice));
         s->flatOk = ok;
         s->nLeaves = 0;
+        if (ok && d->n_lights > 0 && d->lights) {
+            // the table travels as a kernel argument, a byte per light: the first 8 lights (a scene of at most 64 triangles rarely has
+            // more; a light beyond them is simply tested like any other triangle)
+            light_triangles(pt.data(), nT, d, lightTri.data());
+            for (int i = 0; i < d->n_lights && i < 8; i++) s->lightTri8 |= (uint64_t)(lightTri[i] + 1) << (8 * i);
+        }
         if (ok && nInternal > 0 && boxes_nested_and_finite(pn, nInternal)) {     // the leaf table: every leaf child's box and triangle range
             std::vector<PLeaf> lf;
             for (int i = 0; i < nInternal; i++) {
@@ -560,6 +589,28 @@ int pt_debug_packed(pt_scene* s, int what, void* dst, size_t capacity) {
     const size_t bytes = std::min((size_t)count * rec, capacity);
     if (dst && bytes) HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return count;
+}
+
+// Host only: light_triangles on the triangles in the leaf order desc->bvh_indices gives, packed as repack packs them.
+int pt_light_triangles(const pt_scene_desc* d, int32_t* out) {
+    if (!d || !out) return fail(-1, "null argument");
+    if (d->n_triangles <= 0 || !d->triangles || !d->bvh_indices || !d->positions || (d->n_lights > 0 && !d->lights)) return fail(-1, "pt_light_triangles: empty scene");
+    std::vector<PTri> pt((size_t)d->n_triangles);
+    for (int i = 0; i < d->n_triangles; i++) {
+        const int idx = d->bvh_indices[i];
+        if (idx < 0 || idx >= d->n_triangles) return fail(-1, "pt_light_triangles: BVHindices[%d] = %d out of range", i, idx);
+        const pt_triangle& t = d->triangles[idx];
+        if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions)
+            return fail(-1, "pt_light_triangles: triangle %d position index out of range", idx);
+        const pt_float4 a = d->positions[t.aInd], b = d->positions[t.bInd], c = d->positions[t.cInd];
+        PTri& p = pt[i];
+        p.v0[0] = a.x; p.v0[1] = a.y; p.v0[2] = a.z;
+        p.e1[0] = b.x - a.x; p.e1[1] = b.y - a.y; p.e1[2] = b.z - a.z;
+        p.e2[0] = c.x - a.x; p.e2[1] = c.y - a.y; p.e2[2] = c.z - a.z;
+        p.idx = (uint32_t)idx; p.material = t.materialID; p.flags = 0u;
+    }
+    light_triangles(pt.data(), d->n_triangles, d, out);
+    return 0;
 }
 
 // ---- helpers ----------------------------------------------------------------------------------
@@ -883,6 +934,7 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     if (onchip) { P.cacheNodes = s->nInternal; P.cacheTris = s->nTrisPacked; }      // the whole scene, in workgroups large enough to hold it
     P.cacheAttrs = P.cacheMats = P.cacheLights = 0;
     P.nLeaves = 0; P.leaves = nullptr;
+    P.lightTri8 = s->lightTri8;
     if (onchip && kAttrCacheBytes > 0) { P.cacheAttrs = s->nTrisPacked; P.cacheMats = s->nMats; P.cacheLights = s->nLightsPacked; }   // the bounce's records in LDS as well
     if (onchip && kAttrCacheBytes > 0 && s->flatOk && s->leafBoxes && s->nLeaves > 0) { P.nLeaves = s->nLeaves; P.leaves = (const PLeaf*)s->leaves.p; }
     P.wgWaves = wgWaves;
@@ -943,6 +995,9 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     s->lastLaunchPushed = live;
     P.rng = (uint32_t*)s->rng.p; P.out = (float4*)d_tiles; P.pixCounters = d_pixcnt;
     P.totals = count ? (unsigned long long*)s->totals.p : nullptr;
+#ifdef PT_STAMPS
+    P.totals = (unsigned long long*)s->totals.p;           // the diagnostic build sums its stamps for timed launches too
+#endif
     P.spill = spillEntries > 0 ? (int32_t*)s->spill.p : nullptr;
     HIP_OK(hipEventRecord(s->ev0, stream));            // HIP events on the launch stream, around the megakernel only
     HIP_OK(launch_megakernel(integrator, count, !(s->deferShadow && !s->armless), P, live, list, stream));

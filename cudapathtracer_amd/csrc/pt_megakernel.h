@@ -171,6 +171,10 @@ PT_DEV void megakernel_body(const KParams& P) {
     // of the resumable traversal, and the DEFER record holds the finished NEE term (PRE). True for SIMPLE and LEAN scenes and
     // for every scene the pair form of FLAT is launched on (pt_api.hip: noLeafTris).
     constexpr bool NOLEAF = SIMPLE || LEAN || (DEFER && FLAT);
+    // LTRI: the bounce notes which triangle the sampled light is, and the pair pass skips the shadow ray's test against it (pt_trace.h:
+    // trace_pair_flat). The SIMPLE pair kernel only — the headline: in the other two the note costs one more spilled register around
+    // the logic step (private segment 52 -> 56 B in the LEAN one, which tests/test_isa.py pins), for one test in eleven.
+    constexpr bool LTRI = DEFER && FLAT && SIMPLE;
     // (... and for the 4-wave SIMPLE kernel that small shares of a scene in HBM run — 128 VGPRs, chain-bound: 1/8 shares +4-5 %,
     //  profiles/r03_shards_hbm_final.log; the 8-wave kernel at 64 VGPRs loses 1-6 % to it)
 #ifndef PT_TRISEL_SIMPLE4
@@ -289,6 +293,7 @@ PT_DEV void megakernel_body(const KParams& P) {
     unsigned long long stamp[4] = {0, 0, 0, 0};
     unsigned long long tprev = __builtin_amdgcn_s_memtime();
     const unsigned long long wall0 = wall_clock64();     // device-wide 100 MHz clock: slot occupancy (tools/stamps.py)
+    unsigned long long occ[4] = {0, 0, 0, 0};            // lane occupancy of the logic step and rays traced (tools/lane_occupancy.py)
 #endif
     auto shadowSync = [&](V3 ro, V3 wi, float maxt) {
         PT_STAMP(2);
@@ -421,9 +426,13 @@ PT_DEV void megakernel_body(const KParams& P) {
             PT_STAMP(1);
             continue;
         }
+#ifdef PT_STAMPS
+        // a lane is busy in this logic step if it shades a hit or starts a sample; the rest of the wave's 64 slots are idle lanes
+        occ[0] += 64; occ[1] += __builtin_popcountll(__ballot((ps.flags & kInPath) != 0 || (samplesLeft > 0 && !stopStarting)));
+#endif
         if (DEFER) apply_pending<NOLEAF>(ps, thr, acc);
         if (ps.flags & kInPath) {
-            bool done = path_bounce<INTEG, COUNT, DEFER, SIMPLE, LEAN, NOLEAF>(S, ps, ms, h, P.maxDepth, P.useMIS, shadowSync, c);
+            bool done = path_bounce<INTEG, COUNT, DEFER, SIMPLE, LEAN, NOLEAF, LTRI>(S, ps, ms, h, P.maxDepth, P.useMIS, shadowSync, c, LTRI ? P.lightTri8 : 0ull);
             if (!done) done = path_exhausted<INTEG>(ps, P.maxDepth);
             if (done) path_finish(ps, acc, DEFER);
         }
@@ -436,11 +445,14 @@ PT_DEV void megakernel_body(const KParams& P) {
         const bool hasExt = (ps.flags & kInPath) != 0;
         const bool hasShadow = DEFER && (ps.flags & kShadowPending) != 0;
         PT_STAMP(0);
+#ifdef PT_STAMPS
+        occ[2] += __builtin_popcountll(__ballot(hasExt)); occ[3] += __builtin_popcountll(__ballot(hasShadow));
+#endif
         if (__ballot(hasExt || hasShadow) == 0ull) break;
         if constexpr (DEFER && FLAT) {
-            trace_pair_flat<STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves);
+            trace_pair_flat<STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves);
 #ifdef PT_DIAG_DOUBLE_PAIR          // cost measurement only: the pair pass run twice, same result
-            { Hit h2; V3 thr2; trace_pair_flat<STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, hasExt, ps.o, ps.d, thr2, h2, c, P.cacheNodes, P.leaves, P.nLeaves);
+            { Hit h2; V3 thr2; trace_pair_flat<STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr2, h2, c, P.cacheNodes, P.leaves, P.nLeaves);
               if (hasExt && h2.tri == h.tri) h.t = fminf_(h.t, h2.t); thr.x = fminf_(thr.x, thr2.x); }
 #endif
         }
@@ -469,6 +481,10 @@ PT_DEV void megakernel_body(const KParams& P) {
         atomicAdd(&P.totals[11], wall1 - wall0);             // sum of wave lifetimes
         atomicMax(&P.totals[12], ~wall0);                     // ~(earliest start)
         atomicMax(&P.totals[13], wall1);                      // latest end
+        if (!COUNT) {                                         // (a counting kernel's own counters live in these slots)
+            atomicAdd(&P.totals[0], occ[2]); atomicAdd(&P.totals[1], occ[3]);    // rays this kernel traced: counters() rays_closest / rays_shadow
+            atomicAdd(&P.totals[7], occ[1]); atomicAdd(&P.totals[15], occ[0]);   // busy lanes at logic-step entry ("iters") of the lane slots ("slot7")
+        }
     }
 #endif
     if (inImage) {

@@ -112,6 +112,7 @@ struct KParams {
     int* left;                     // [tile][64] samples left per pixel of a yielded tile
     int schedMask;                 // the wave looks at the queue / its priority every schedMask + 1 iterations (31)
     int lptPrio;                   // longest-remaining-first issue priority once no fresh tile is left
+    unsigned long long lightTri8;  // the SIMPLE pair kernel: a byte per light, for the first 8: 1 + the packed triangle the light is (same v0, e1, e2 bit for bit), 0 = none (pt_api.hip: light_triangles)
 };
 
 struct TileSpan { int first, stride, count, tilesX; };

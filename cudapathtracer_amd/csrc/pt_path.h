@@ -49,6 +49,7 @@ enum : uint32_t {
     kShadowPending = 4u,     // DEFER: (so, sd, smaxt) must be traced and applied
     kNeeValid = 8u,          // DEFER: the recorded NEE sample had light_pdf > EPSILON
     kFinishPending = 16u,    // DEFER: the previous path ended with its last NEE term still pending: `Li` still holds ITS sum
+    kLightTriShift = 8u, kLightTriMask = 0x7fu << 8,     // pair kernels: 1 + the packed triangle of the light the pending shadow ray was aimed at (0: none); set and cleared with kShadowPending
 };
 
 struct PathState {
@@ -129,7 +130,7 @@ PT_DEV void apply_pending(PathState& ps, V3 thr, V3& acc) {
     const V3 done = acc + li;
     acc = v3(fin ? done.x : acc.x, fin ? done.y : acc.y, fin ? done.z : acc.z);
     ps.Li = v3(fin ? 0.0f : li.x, fin ? 0.0f : li.y, fin ? 0.0f : li.z);
-    ps.flags &= ~(kShadowPending | kNeeValid | kFinishPending);
+    ps.flags &= ~(kShadowPending | kNeeValid | kFinishPending | kLightTriMask);
 }
 
 // The loop-top tests of the reference for a live path: `depth < 100` (MIS, deviceCode.cu:318) or
@@ -155,10 +156,12 @@ struct NeeRecord { V3 so, sd; float smaxt; V3 neeRaw, neeBeta; float neeW; };
 // have one arm each, and all of that is known at compile time: same values, a third of the code.
 // LEAN: see pt_shade.h (no MAT_LEAF triangle, no textures). PRE: the DEFER record holds the finished NEE term (apply_pending<PRE>)
 // — valid when no triangle is a MAT_LEAF: SIMPLE and LEAN scenes, and every scene the pair form of FLAT accepts.
-template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE, bool LEAN, bool PRE, class MS, class ShadowFn>
+// LTRI (the pair pass, pt_trace.h: trace_pair_flat): `flags` also names the packed triangle of the sampled light (kLightTriMask, from
+// the kernel's argument lightTri8) — the one triangle the shadow ray need not be tested against. In a flag word, not a field: it costs no register.
+template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE, bool LEAN, bool PRE, bool LTRI, class MS, class ShadowFn>
 PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, V3& Li, V3& prevPoint, V3& woLocal,
                         float& pdf, float& etaI, float& etaT, int& depth, int& msTop, uint32_t& flags, NeeRecord& nr,
-                        MS& ms, const Hit& h, int maxDepth, int useMIS, ShadowFn shadow, Ctr& c) {
+                        MS& ms, const Hit& h, int maxDepth, int useMIS, ShadowFn shadow, Ctr& c, uint64_t lightTri8) {
     if (COUNT) c.iters++;
     if (h.tri < 0) {
         Li = Li + beta * v3(0.0f);          // `Li += beta * sampleSky()`; the sky is black (integratorUtilities.cuh:436-438)
@@ -253,6 +256,8 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
             // nextEventEstimation, deviceCode.cu:87-156 (with nLights == 0 it draws nothing and adds nothing)
             int index = min((int)(draw<COUNT>(rng, c) * (float)S.nLights), S.nLights - 1);
             const PLight& L = S.lights[index];
+            // (set here, while `index` is live, whether or not a shadow ray follows: read only with kShadowPending, cleared by apply_pending)
+            if (LTRI) flags |= index < 8 ? ((uint32_t)(lightTri8 >> (uint32_t)(index * 8)) & 0x7fu) << kLightTriShift : 0u;
             V3 A = ld3(L.a), B = ld3(L.b), Cc = ld3(L.c);
             float u = __builtin_sqrtf(draw<COUNT>(rng, c));
             float v = draw<COUNT>(rng, c);
@@ -288,14 +293,23 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
                     if (DEFER) {
                         if (PRE) nr.neeRaw = (beta * nee) * wN;               // apply_pending<PRE>: the finished term (thr is exactly 1 when it is added)
                         else { nr.neeRaw = nee; nr.neeBeta = beta; nr.neeW = wN; }
-                        flags |= kNeeValid;
+                        flags |= COUNT ? kNeeValid : (kNeeValid | kShadowPending);
                     } else {
                         pdf = pdfB;
                         nee = nee * thr;
                         Li = Li + (beta * nee) * wN;
                     }
                 }
-                if (DEFER) { nr.so = ro; nr.sd = wi; nr.smaxt = maxt; flags |= kShadowPending; }
+                // The shadow ray is TRACED only with a term to apply (kShadowPending is set with kNeeValid, above): apply_pending adds
+                // nothing without kNeeValid, so a ray whose term is invalid (a light facing away: cosL < 0 makes lightPdf negative —
+                // every hit on Cornell's ceiling) would be traced and its result dropped. Without it a path that ends here adds Li at
+                // once (path_finish) instead of through kFinishPending: `acc` receives the same addends in the same order.
+                // The counting kernels trace every ray: their counters are the reference's, which traces it before it looks at the
+                // pdf (deviceCode.cu:127). (The ray itself is written either way: selects on the flag only cost registers.)
+                if (DEFER) {
+                    nr.so = ro; nr.sd = wi; nr.smaxt = maxt;
+                    if (COUNT) flags |= kShadowPending;
+                }
             }
         }
         V3 f = v3(0.0f);
@@ -331,8 +345,8 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
 }
 
 
-template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE = false, bool LEAN = false, bool PRE = SIMPLE, class MS, class ShadowFn>
-PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& h, int maxDepth, int useMIS, ShadowFn shadow, Ctr& c) {
+template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE = false, bool LEAN = false, bool PRE = SIMPLE, bool LTRI = false, class MS, class ShadowFn>
+PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& h, int maxDepth, int useMIS, ShadowFn shadow, Ctr& c, uint64_t lightTri8 = 0ull) {
     Rng rng = ps.rng;
     V3 o = ps.o, d = ps.d, beta = ps.beta, Li = ps.Li, prevPoint = ps.prevPoint, woLocal = ps.woLocal;
     float pdf = ps.pdf, etaI = ps.etaI, etaT = ps.etaT;
@@ -349,8 +363,8 @@ PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& 
 #else
     nr.so = ps.so; nr.sd = ps.sd; nr.smaxt = ps.smaxt; nr.neeRaw = ps.neeRaw; nr.neeBeta = ps.neeBeta; nr.neeW = ps.neeW;
 #endif
-    bool done = bounce_core<INTEG, COUNT, DEFER, SIMPLE, LEAN, PRE>(S, rng, o, d, beta, Li, prevPoint, woLocal, pdf, etaI, etaT, depth, msTop, flags, nr,
-                                                 ms, h, maxDepth, useMIS, shadow, c);
+    bool done = bounce_core<INTEG, COUNT, DEFER, SIMPLE, LEAN, PRE, LTRI>(S, rng, o, d, beta, Li, prevPoint, woLocal, pdf, etaI, etaT, depth, msTop, flags, nr,
+                                                 ms, h, maxDepth, useMIS, shadow, c, lightTri8);
     ps.rng = rng;
     ps.o = o; ps.d = d; ps.beta = beta; ps.Li = Li; ps.prevPoint = prevPoint; ps.woLocal = woLocal;
     ps.pdf = pdf; ps.etaI = etaI; ps.etaT = etaT; ps.depth = depth; ps.msTop = msTop; ps.flags = flags;

@@ -792,7 +792,7 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 #define PT_PAIR_MIN_ALWAYS 0
 #endif
 template <int N>
-PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt,
+PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt, uint32_t ltri1,
                             bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
     static_assert(N >= 24, "the scratch layout needs 24 x 64 words of the wave's stack area");
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
@@ -837,6 +837,14 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
             if (right >= 0) { visE |= eR ? bR : 0ull; visS |= sR ? bR : 0ull; } else { tmE |= eR ? bR : 0ull; tmS |= sR ? bR : 0ull; }
         }
     }
+    // The shadow ray is not tested against the light triangle it was aimed at (ltri1: 1 + that triangle's packed index, 0 if the
+    // light is no triangle of the scene; at most 63). Its bound is smaxt = t * (1 - kEps), where t is what the bounce's own test of (so, sd) against
+    // that triangle returned: the same operations on the same ray and the same v0, e1, e2 (pt_api.hip: light_triangles checks
+    // them bit for bit), so the trip below would compute the same t and reject it — t < t * (1 - kEps) is false for every
+    // positive t (the product rounds to t or below), and a t <= 0 or NaN passes no test at all. Where the bounce's test failed
+    // (uvOk false, or t <= 0), the trip's fails identically. One test less per shadow ray, and the result is the same. Once per
+    // pass, not per leaf.
+    tmS &= ~((1ull << ltri1) >> 1);                               // (0: no bit)
     // 2. deal the tests of all 128 rays out: extension rays first, then shadow rays, each ray's tests in a row
     auto scan = [&](int v, int& total) {                          // inclusive prefix sum over the wave
         v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);

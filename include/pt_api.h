@@ -244,7 +244,10 @@ int pt_has_experimental(void);
  * that went to global memory (node index beyond the LDS scene cache) — with tri_tests, the L1 line-access count behind
  * bench.py's roofline for scenes in HBM; the rest zero. Diagnostic builds:
  * -DPT_STAMPS: s_memtime spent in regeneration, closest-hit traversal, bounce logic (incl. the shadow ray), then the
- * sum of wave lifetimes, ~(earliest start) and the latest end on the 100 MHz wall clock, 0, 0 (tools/stamps.py).
+ * sum of wave lifetimes, ~(earliest start) and the latest end on the 100 MHz wall clock, 0, and — timed (non-counting)
+ * launches, which this build sums as well — 64 x the logic steps of all waves; such a launch also leaves the rays IT traced
+ * in pt_get_counters' rays_closest / rays_shadow and the lanes that were busy at logic-step entry in `iterations`
+ * (tools/stamps.py, tools/lane_occupancy.py).
  * -DPT_UTIL (counting launches): {trips of a wave, trips summed over its lanes} through the node loop and the
  * triangle loop of the closest-hit traversal, then of the shadow traversal (tools/lane_util.py). */
 int pt_debug_stamps(pt_scene* scene, unsigned long long* out8);
@@ -768,6 +771,11 @@ pt_scene* pt_scene_create_from_mesh(const pt_scene_desc* desc, int max_leaf_size
 /* Test hook: copy the packed traversal records back (what: 0 nodes 64 B, 1 triangles 48 B, 2 attributes 80 B);
  * returns the record count. */
 int pt_debug_packed(pt_scene* scene, int what, void* dst, size_t capacity_bytes);
+/* Test hook, host only (needs no device): out[i], for each of desc->n_lights lights, is the position in leaf order
+ * (desc->bvh_indices) of the scene triangle the light was made from — the triangle whose lightInd is i and whose packed
+ * v0, e1 = b - a, e2 = c - a equal the light's bit for bit — or -1. Only positions below 63 are reported: the table serves
+ * the kernels for scenes of at most 64 triangles, which do not test a shadow ray against the light it was aimed at. */
+int pt_light_triangles(const pt_scene_desc* desc, int32_t* out);
 int novum_bvh_build_host(const pt_float4* positions, int n_positions, const pt_triangle* triangles, int n_triangles,
                          int max_leaf_size, pt_bvh_node* nodes_out, int nodes_capacity,
                          int32_t* indices_out, pt_bvh_build_stats* stats);
