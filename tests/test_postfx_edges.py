@@ -1,0 +1,255 @@
+"""The post-process kernels on the GPU against their numpy restatements at ragged sizes, edge cameras and their own parameters:
+pt_denoise, pt_denoise_var, pt_denoise_hist (denoise_ref, denoise_var_ref, temporal_ref.denoise_hist), pt_temporal_accumulate, _cur
+and _live (temporal_ref, upsample_ref.accumulate_cur) and pt_upsample (upsample_ref), on the analytic frames of tests/postfx_cases.py.
+
+Nothing is rendered and no scene is loaded: every case goes through the host form of the API, one allocation, a few small copies and
+the launches. The comparisons and tolerances are those of test_denoise.py, test_denoise_var.py, test_temporal.py and test_upsample.py;
+tests/test_postfx_cases.py shows without a GPU that each case reaches the branch it is named for (DESIGN.md §15 lists which size and
+which pair pins which guard)."""
+import numpy as np
+import pytest
+
+import converge_ref as R
+import postfx_cases as C
+import temporal_ref as T
+import upsample_ref as U
+from denoise_ref import LUMA, denoise as denoise_ref
+from denoise_var_ref import denoise_var as denoise_var_ref
+from test_temporal import FRAGILE_CAP, _assert_hist_close
+from util import assert_bits_equal
+
+pytestmark = pytest.mark.gpu
+
+SPP, BATCHES = C.SPP, C.BATCHES
+f32 = np.float32
+
+
+# ---- a. the filters ----------------------------------------------------------------------------------------------------------------------
+def _assert_rgb_close(got, want, use, atol, what):
+    """rtol 1e-3 and the filter's atol on the filtered pixels' rgb, after printing the largest deviations."""
+    if use.any():
+        err = np.abs(got[use][:, :3].astype(np.float64) - want[use][:, :3])
+        print("%s: max |got - want| = %.3g (atol %.3g), max relative %.3g" % (
+            what, err.max(), atol, (err / np.maximum(np.abs(want[use][:, :3]), 1e-30)).max()))
+    else:
+        print("%s: every pixel passes through" % what)
+    np.testing.assert_allclose(got[use][:, :3], want[use][:, :3], rtol=1e-3, atol=atol, err_msg=what)
+
+
+def _check_denoise(api, frame, what, **params):
+    """test_denoise.py's comparison, with parameters."""
+    S, Q, A, N = frame
+    got = api.denoise(S, SPP, A, N, **params)
+    want, skip, L = denoise_ref(S, SPP, A, N, **dict(api.denoise_defaults(), **params))
+    assert_bits_equal(got[skip], S[skip], what + ": pass-through pixels")
+    assert_bits_equal(got[..., 3], S[..., 3], what + ": w channel")
+    _assert_rgb_close(got, want, ~skip, 1e-6 * L * SPP, what)
+    return got, skip
+
+
+def _check_denoise_var(api, frame, what, **params):
+    """test_denoise_var.py's comparison, with parameters."""
+    S, Q, A, N = frame
+    got = api.denoise_var(S, Q, SPP, BATCHES, A, N, **params)
+    want, skip, L = denoise_var_ref(S, Q, SPP, BATCHES, A, N, **dict(api.denoise_var_defaults(), **params))
+    assert_bits_equal(got[skip], S[skip], what + ": pass-through pixels")
+    assert_bits_equal(got[..., 3], S[..., 3], what + ": w channel")
+    _assert_rgb_close(got, want, ~skip, 1e-6 * L * SPP, what)
+    return got, skip
+
+
+def _check_denoise_hist(api, frame, what, **params):
+    """test_temporal.py's comparison of the history filter, with parameters; the frame's own (e, V) is the history."""
+    S, Q, A, N = frame
+    hist = C.history_of(S, Q, A, N)
+    got = api.denoise_hist(hist, A, N, **params)
+    want, skip, L = T.denoise_hist(hist, A, N, **dict(api.denoise_var_defaults(), **params))
+    assert_bits_equal(got[skip][:, :3], hist[skip][:, :3], what + ": pass-through pixels")
+    assert np.all(got[..., 3] == 0), what
+    _assert_rgb_close(got, want, ~skip, 1e-6 * L, what)
+    return got, skip
+
+
+FILTERS = {"denoise": (_check_denoise, C.DENOISE_OFF), "denoise_var": (_check_denoise_var, C.VAR_OFF), "denoise_hist": (_check_denoise_hist, C.VAR_OFF)}
+
+
+@pytest.fixture(scope="module")
+def filter_frames(api):
+    """The yawed analytic frame with planted edge pixels at every size, made once and left unchanged."""
+    frames = {}
+    for w, h in C.FILTER_SIZES:
+        frames[(w, h)] = C.filter_frame(api, w, h)
+        for a in frames[(w, h)]:
+            a.setflags(write=False)
+    return frames
+
+
+@pytest.mark.parametrize("w,h", C.FILTER_SIZES)
+@pytest.mark.parametrize("name", list(FILTERS))
+def test_filter_matches_numpy_at_ragged_sizes(api, gpu_ready, filter_frames, name, w, h):
+    check, off = FILTERS[name]
+    frame = filter_frames[(w, h)]
+    plain = None
+    for iterations in C.ITERATIONS[(w, h)]:
+        kw = {} if iterations is None else {"iterations": iterations}
+        got, skip = check(api, frame, "%s %d x %d, iterations %s" % (name, w, h, iterations), **kw)
+        assert np.isfinite(got[~skip]).all()
+        if iterations == 0:
+            plain = got
+        elif w * h > 1:
+            assert not np.array_equal(got, plain)            # the filter ran
+    # every parameter off its default, sigma_normal = 0 among them: they arrive, each at its own place
+    moved, _ = check(api, frame, "%s %d x %d, %s" % (name, w, h, off), **off)
+    if w * h > 1:
+        default, _ = check(api, frame, "%s %d x %d, %d iterations" % (name, w, h, off["iterations"]), iterations=off["iterations"])
+        assert not np.allclose(moved[~skip], default[~skip], rtol=1e-3)
+    if (w, h) != (1, 1):
+        assert set(C.edge_places(frame[2])) == set(C.EDGE_KINDS) and skip.sum() > (frame[2][..., 3] == 0).sum()
+
+
+@pytest.mark.parametrize("name", list(FILTERS))
+def test_exchanging_two_parameters_moves_the_restatement(api, gpu_ready, filter_frames, name):
+    """The off-default values are distinct enough that a launch site which passed two of them in each other's place would leave the
+    tolerance: shown on the restatement, at the size the 16-iteration case runs at."""
+    S, Q, A, N = filter_frames[(61, 43)]
+    hist = C.history_of(S, Q, A, N)
+
+    def restate(iterations, **p):
+        if name == "denoise":
+            out, skip, L = denoise_ref(S, SPP, A, N, iterations=iterations, **p)
+            return out[..., :3], ~skip, 1e-6 * L * SPP
+        if name == "denoise_var":
+            out, skip, L = denoise_var_ref(S, Q, SPP, BATCHES, A, N, iterations=iterations, **p)
+            return out[..., :3], ~skip, 1e-6 * L * SPP
+        out, skip, L = T.denoise_hist(hist, A, N, iterations=iterations, **p)
+        return out[..., :3], ~skip, 1e-6 * L
+    off = FILTERS[name][1]
+    C.assert_exchanges_matter(restate, off, [k for k in off if k != "iterations"], name)
+
+
+@pytest.mark.parametrize("w,h", [(17, 9), (300, 221)])
+@pytest.mark.parametrize("name", list(FILTERS))
+def test_a_frame_of_pass_through_pixels_comes_back_bit_for_bit(api, gpu_ready, name, w, h):
+    """Coverage 0 everywhere: no pixel counts towards L (0 / 0 pixels), and every kernel of the chain copies."""
+    frame = C.pass_through_frame(w, h)
+    got, skip = FILTERS[name][0](api, frame, "%s %d x %d, all pass-through" % (name, w, h))
+    assert skip.all()
+    if name == "denoise_hist":
+        assert_bits_equal(got[..., :3], C.history_of(*frame)[..., :3], "hist.rgb")
+    else:
+        assert_bits_equal(got, frame[0], "the input")
+
+
+@pytest.mark.parametrize("name", list(FILTERS))
+def test_a_black_frame_stays_finite(api, gpu_ready, name):
+    """Every hit pixel filtered with e = 0, V = 0 and L = 0: the weights' denominators are their 1e-20 floors. atol is 0 here, and the
+    restatement's answer is 0 exactly."""
+    w, h = 17, 9
+    frame = C.black_frame(api, w, h)
+    for iterations in (1, None):
+        kw = {} if iterations is None else {"iterations": iterations}
+        got, skip = FILTERS[name][0](api, frame, "%s %d x %d, black, iterations %s" % (name, w, h, iterations), **kw)
+        assert np.array_equal(skip, frame[2][..., 3] == 0) and (~skip).sum() > 100
+        assert np.isfinite(got).all() and not got[..., :3].any()
+
+
+# ---- b. temporal -------------------------------------------------------------------------------------------------------------------------
+def _temporal_cases():
+    return [(name, w, h) for w, h in C.TEMPORAL_SIZES for name in C.PAIRS] + [(name, 1, 1) for name in ("same", "sideways")]
+
+
+def _compare_hist(got, got_len, want, want_len, fragile, what):
+    """test_temporal._assert_hist_close; a frame of pass-through pixels only (it has nothing to take a maximum over) is that
+    function's first three assertions on the whole frame."""
+    if (want[..., 3] < 0).all():
+        assert_bits_equal(got, want, what + ": pass-through pixels")
+        assert np.all(got_len == 0) and not fragile.any()
+        print("%s: every pixel passes through, bit-equal" % what)
+    else:
+        _assert_hist_close(got, got_len, want, want_len, fragile, what)
+
+
+@pytest.mark.parametrize("name,w,h", _temporal_cases())
+def test_accumulate_matches_numpy_on_every_pair(api, gpu_ready, name, w, h):
+    case = C.temporal_case(api, name, w, h)
+    S, Qm, A, N = case["frame"]
+    history = (case["prev_nd"], case["hist"], case["hist_len"])
+    m, e, V, skip = T.frame_ev(S, Qm, SPP, BATCHES, A)
+    cur = np.concatenate([np.where(skip[..., None], m, e), np.where(skip, f32(-1), V)[..., None]], -1).astype(f32)
+    for params in (T.DEFAULTS, C.OFF_DEFAULT):
+        what = "%s %d x %d, %s" % (name, w, h, "defaults" if params is T.DEFAULTS else params)
+        got, got_len = api.temporal_accumulate(case["cur"], S, Qm, SPP, BATCHES, A, N, case["prev"], *history, **params)
+        want, want_len, fragile = C.restate_temporal(case, **params)
+        _compare_hist(got, got_len, want, want_len, fragile, what)
+        counts = C.branch_counts(case, want_len, params)
+        print(what, counts)
+        C.check_branches(case, counts, params)
+        live = got[..., 3] >= 0
+        assert np.isfinite(got[live]).all() and np.isfinite(got_len).all()      # the NaN planted in the history reached nobody
+        # the frame's working pixels handed over: pt_temporal_accumulate_cur is pt_temporal_accumulate from step 2 on
+        got_cur, got_cur_len = api.temporal_accumulate_cur(case["cur"], cur, N, case["prev"], *history, **params)
+        assert_bits_equal(got_cur, got, what + ": accumulate_cur hist"); assert_bits_equal(got_cur_len, got_len, what + ": accumulate_cur hist_len")
+        want_cur, want_cur_len, fragile_cur = U.accumulate_cur(case["cur"], case["prev"], cur, N, *history, **params)
+        _compare_hist(got_cur, got_cur_len, want_cur, want_cur_len, fragile_cur, what + ", accumulate_cur")
+
+
+def test_the_parameters_reach_the_blend(api, gpu_ready):
+    """max_history, depth_tol and normal_tol are neighbours on their way to the kernel: with the off-default values the restatement
+    tells every exchange of two apart, and the kernel agrees with the restatement (test_accumulate_matches_numpy_on_every_pair)."""
+    case = C.temporal_case(api, "yaw25", 61, 43)
+
+    def restate(**p):
+        out, ln, fragile = C.restate_temporal(case, **p)
+        return np.concatenate([out, ln[..., None]], -1), ~(out[..., 3] < 0) & ~fragile, 1e-6
+    C.assert_exchanges_matter(restate, C.OFF_DEFAULT, ("max_history", "depth_tol", "normal_tol"), "pt_temporal_accumulate")
+    S, Qm, A, N = case["frame"]
+    got = [api.temporal_accumulate(case["cur"], S, Qm, SPP, BATCHES, A, N, case["prev"], case["prev_nd"], case["hist"], case["hist_len"], **p)
+           for p in (T.DEFAULTS, C.OFF_DEFAULT)]
+    assert abs(got[0][1].max() - (C.HIST_LEN_SCALE + 1)) < 1e-3 and got[1][1].max() == C.OFF_DEFAULT["max_history"]
+    assert ((got[0][1] > 1) != (got[1][1] > 1)).any()         # the tighter tolerances drop taps the defaults take
+
+
+def test_accumulate_with_a_map_at_a_ragged_size(api, gpu_ready):
+    """17 x 9 is 3 x 2 tiles, the last column one pixel wide and the last row one pixel high."""
+    w, h = 17, 9
+    case = C.temporal_case(api, "same", w, h)
+    S, Qm, A, N = case["frame"]
+    hist, ln = case["hist"], case["hist_len"]
+    live = np.array([[1, 0, 1], [0, 1, 0]], np.int32)
+    assert live.shape == R.tile_grid(h, w)
+    m = R.per_pixel(live != 0, h, w)
+    full, full_len = api.temporal_accumulate(case["cur"], S, Qm, SPP, BATCHES, A, N, None, case["prev_nd"], hist, ln)
+    got, got_len = api.temporal_accumulate_live(case["cur"], S, Qm, SPP, BATCHES, A, N, case["prev_nd"], hist, ln, live)
+    assert_bits_equal(got[~m], hist[~m], "carried tiles: hist"); assert_bits_equal(got_len[~m], ln[~m], "carried tiles: hist_len")
+    assert_bits_equal(got[m], full[m], "live tiles: hist"); assert_bits_equal(got_len[m], full_len[m], "live tiles: hist_len")
+    assert (full_len[~m] != ln[~m]).any() and (full_len[m] != ln[m]).any()
+    want_len = R.accumulate_live(case["cur"], S, Qm, SPP, BATCHES, A, N, case["prev_nd"], hist, ln, live)[1]
+    assert_bits_equal(got_len, want_len, "restatement: hist_len")
+
+
+# ---- c. upsample -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("yawed", [False, True])
+@pytest.mark.parametrize("wl,hl,s", C.UPSAMPLE_SHAPES)
+def test_upsample_matches_numpy_at_small_sizes(api, gpu_ready, wl, hl, s, yawed):
+    """test_upsample.py's comparison on frames of one, six and 35 low-res pixels: every display pixel of the first sits in the last
+    low-res column and row, where only tap (0, 0) is a candidate."""
+    b = C.upsample_case(api, wl, hl, s, yawed)
+    got = api.upsample(s, b[0], b[1], SPP, BATCHES, *b[2:])
+    want, kind, fragile = U.upsample(s, b[0], b[1], SPP, BATCHES, *b[2:], **U.DEFAULTS)
+    what = "%d x %d scale %d %s" % (wl * s, hl * s, s, "yawed" if yawed else "front")
+    skip = kind == U.PASS
+    assert np.array_equal(got[..., 3] < 0, skip), what
+    assert_bits_equal(got[skip], want[skip], what + ": pass-through pixels")
+    fb = (kind == U.FALLBACK) & ~fragile
+    assert_bits_equal(got[fb], want[fb], what + ": fallback pixels")
+    cmp = (kind == U.WEIGHTED) & ~fragile
+    L = float((want[~skip][:, :3].astype(np.float64) @ LUMA).mean())
+    err = np.abs(got[cmp].astype(np.float64) - want[cmp])
+    print("%s: pass-through %.2f %%, fallback %.2f %%, fragile %.4f %% of the pixels; max |got - want| = %.3g (atol %.3g), max relative %.3g" % (
+        what, 100 * skip.mean(), 100 * (kind == U.FALLBACK).mean(), 100 * fragile.mean(), err.max(), 1e-6 * L,
+        (err / np.maximum(np.abs(want[cmp]), 1e-30)).max()))
+    assert fragile.mean() <= FRAGILE_CAP, what
+    np.testing.assert_allclose(got[cmp], want[cmp], rtol=1e-3, atol=1e-6 * L, err_msg=what)
+    assert skip.any() and cmp.any(), what
+    if (wl, hl, s) == (1, 1, 8):
+        assert fb.any(), what                                # one low-res pixel: the wall's display pixels have no tap on their plane
