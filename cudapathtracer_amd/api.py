@@ -197,6 +197,8 @@ def lib():
     L.novum_save_bmp.argtypes = [C.c_char_p, vp, i32, i32, i32]
     L.pt_render_aovs.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, u64, vp, vp]
     L.pt_render_aovs_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, u64, vp, vp, vp]
+    L.pt_render_aovs_chain.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, u64, vp, vp, vp]
+    L.pt_render_aovs_chain_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, u64, vp, vp, vp, vp]
     L.pt_denoise_defaults.restype = None; L.pt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
     L.pt_denoise_workspace_bytes.restype = C.c_size_t; L.pt_denoise_workspace_bytes.argtypes = [i32, i32]
     L.pt_denoise.argtypes = [i32, i32, vp, i32, vp, vp, C.POINTER(DenoiseParams), vp]
@@ -235,6 +237,8 @@ def lib():
     L.pt_preview_reset.argtypes = [vp]
     L.pt_preview_set_scale.argtypes = [vp, i32]
     L.pt_preview_scale.argtypes = [vp]
+    L.pt_preview_set_guide_chain.argtypes = [vp, i32]
+    L.pt_preview_guide_chain.argtypes = [vp]
     L.pt_preview_read.argtypes = [vp, vp, vp, vp, vp]
     L.pt_preview_device_rgba8.restype = vp; L.pt_preview_device_rgba8.argtypes = [vp]
     L.pt_preview_device_mean.restype = vp; L.pt_preview_device_mean.argtypes = [vp]
@@ -527,6 +531,22 @@ class Scene:
         """pt_render_aovs_device: the same into device buffers of w*h float4 each, asynchronous on `stream`."""
         _check(lib().pt_render_aovs_device(self.h, C.byref(camera), w, h, aov_spp, seed, d_albedo_ptr, d_normal_depth_ptr, stream or None),
                "pt_render_aovs_device")
+
+    def render_aovs_chain(self, camera, w, h, max_links, aov_spp=1, seed=SEED, links=False):
+        """pt_render_aovs_chain: feature buffers that follow mirrors and glass (at most max_links specular links, 0..16) to the first
+        non-specular surface: its albedo and normal, the summed path length as depth. Returns (albedo, normal_depth) as render_aovs
+        does, and with links=True also the mean link count per pixel, [h,w] float32."""
+        alb = np.zeros((h, w, 4), np.float32)
+        nd = np.zeros((h, w, 4), np.float32)
+        ln = np.zeros((h, w), np.float32) if links else None
+        _check(lib().pt_render_aovs_chain(self.h, C.byref(camera), w, h, aov_spp, max_links, seed, _p(alb), _p(nd), _p(ln) if links else None),
+               "pt_render_aovs_chain")
+        return (alb, nd, ln) if links else (alb, nd)
+
+    def render_aovs_chain_device(self, camera, w, h, max_links, d_albedo_ptr, d_normal_depth_ptr, d_links_ptr=None, aov_spp=1, seed=SEED, stream=0):
+        """pt_render_aovs_chain_device: the same into device buffers (w*h float4 twice, and w*h floats or None), asynchronous on `stream`."""
+        _check(lib().pt_render_aovs_chain_device(self.h, C.byref(camera), w, h, aov_spp, max_links, seed, d_albedo_ptr, d_normal_depth_ptr,
+                                                 d_links_ptr or None, stream or None), "pt_render_aovs_chain_device")
 
     def render_adaptive(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, integrator=UNIDIRECTIONAL, use_mis=True,
                         seed=SEED):
@@ -1247,6 +1267,16 @@ class Preview:
     @property
     def scale(self):
         return lib().pt_preview_scale(self.handle)
+
+    def set_guide_chain(self, max_links):
+        """pt_preview_set_guide_chain: the frames that follow take their guides from render_aovs_chain(max_links) (1..16) in place of
+        render_aovs (0, the default). A call that changes the value drops the history, as reset() does."""
+        _check(lib().pt_preview_set_guide_chain(self.handle, int(max_links)), "pt_preview_set_guide_chain")
+        return self
+
+    @property
+    def guide_chain(self):
+        return lib().pt_preview_guide_chain(self.handle)
 
     def set_converge(self, threshold=None, min_history=None):
         """pt_preview_set_converge: while the camera rests, the frames that follow render only the 8x8 tiles whose history has

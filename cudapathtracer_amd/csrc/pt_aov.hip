@@ -6,6 +6,7 @@
 // the material are those of pt_probe_trace_closest. The albedo is material_inputs' (the texture sample for textured
 // materials). First hit only: no specular chain is followed. The pass writes neither the scene's per-pixel RNG states nor
 // its tile accumulator nor its counters, so it may run between the chunks of a progressive render.
+// aov_chain_kernel (below, pt_render_aovs_chain) is the same pass with each ray followed through mirrors and glass.
 #include "pt_path.h"
 #include "pt_params.h"
 
@@ -91,6 +92,126 @@ hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jum
                       int blocks, float4* albedo, float4* normalDepth, int32_t* spill, hipStream_t stream) {
     const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
     hipLaunchKernelGGL(aov_kernel, dim3(blocks), dim3(256), 0, stream, S, cam, jump, seed, w, h, tilesX, nTiles, aovSpp, albedo, normalDepth, spill);
+    return hipGetLastError();
+}
+
+// aov_chain_kernel — the feature buffers of pt_render_aovs_chain (include/pt_api.h states the contract): aov_kernel's tiling, rays,
+// sums and division, but each ray follows mirrors (type 6) and smooth dielectrics (type 2) deterministically to the first
+// non-specular surface and reports THAT surface's albedo and normal, the summed path length as depth and the number of links.
+// One trace_closest call site serves the camera ray (i = 0) and every link (i >= 1): lanes leave the loop at different links,
+// the wave leaves it when one ballot finds no lane left. Live across a traversal: o, d, the running depth and the link count; the
+// first-hit record sits in LDS, becomes the result in place when the chain ends on a surface and simply stays when it does not.
+// The direction arithmetic is written out operation by operation (no dot(), normalize(), fmaf): tests/aov_chain_ref.py restates it.
+__global__ void __launch_bounds__(256) aov_chain_kernel(DeviceScene S, CamK cam, const uint32_t* __restrict__ jump, unsigned long long seed,
+                                                        int w, int h, int tilesX, int nTiles, int aovSpp, int maxLinks,
+                                                        float4* __restrict__ albedo, float4* __restrict__ normalDepth,
+                                                        float* __restrict__ linksOut, int32_t* spill) {
+    __shared__ int32_t ldsStack[4][kStackLds][64];
+    __shared__ float ldsRec[4][7][64];           // a ray's record (albedo, normal, depth), lane-interleaved: see below
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + wave;
+    Stack<kStackLds> st; st.lds = (lds_i32*)&ldsStack[wave][0][0] + lane; st.sp = 0;
+    st.spill = spill ? spill + (size_t)gw * S.stackSpill * 64 + lane : nullptr;
+    float* rec = &ldsRec[wave][0][lane];          // rec[j * 64], j = 0..6; only this lane touches it
+    SceneCache C; C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
+    Ctr c = {};
+    for (int tile = gw; tile < nTiles; tile += gridDim.x * 4) {
+        const int x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
+        const bool inside = x < w && y < h;
+        const uint32_t idx = inside ? (uint32_t)(y * w + x) : 0u;
+        V3 sa = v3(0.0f), sn = v3(0.0f);
+        float st_ = 0.0f;
+        int hits = 0, linkSum = 0;
+        for (int k = 0; k < aovSpp; k++) {
+            Rng rng = aov_stream(jump, seed + (unsigned long long)k, idx);      // (every lane: the seeding ballots per bit)
+            V3 o = v3(0.0f), d = v3(0.0f);
+            if (inside) camera_ray<false>(cam, rng, x, y, o, d, c);
+            // The ray's record lives in LDS, not in registers: it is written at the first hit, overwritten where the chain ends on a
+            // surface and read once after the loop, so it need not be live across the traversals (7 VGPRs: 86 -> 6 waves per SIMD).
+            float depth = 0.0f;
+            int links = -1;                      // -1: no hit at all
+            bool live = inside;
+            for (int i = 0; i <= maxLinks; i++) {
+                if (!__ballot(live)) break;
+                if (live) {
+                    Hit hit;
+                    trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+                    live = false;
+                    if (hit.tri >= 0) {          // (a miss: no hit at all at i = 0, the first hit's record stands after that)
+                        HitInfo hi; resolve_hit(S, hit, o, d, hi);
+                        const PMat& m = S.mats[hi.material];
+                        const bool spec = (m.flags & kMatSpecular) && (m.type == 6 || m.type == 2);
+                        depth = i == 0 ? hit.t : depth + hit.t;
+                        if (i == 0 || !spec) {
+                            V3 a; float trans;
+                            material_inputs(m, S.textures, hi.uvx, hi.uvy, true, a, trans);
+                            rec[0] = a.x; rec[64] = a.y; rec[128] = a.z;
+                            rec[192] = hi.normal.x; rec[256] = hi.normal.y; rec[320] = hi.normal.z; rec[384] = depth;
+                            links = i;
+                        }
+                        if (spec && i < maxLinks) {
+                            const V3 n = hi.normal;
+                            const float dn = d.x * n.x + d.y * n.y + d.z * n.z;
+                            bool reflect = true;
+                            V3 r = v3(0.0f);
+                            if (m.type == 2) {
+                                const float cosI = fminf_(fmaxf_(-dn, kEps), 1.0f);
+                                const float eta = hi.backface ? m.ior : 1.0f / m.ior;
+                                const float kk = 1.0f - (eta * eta) * (1.0f - cosI * cosI);
+                                if (!(kk < 0.0f)) {
+                                    const float cn = eta * cosI - __builtin_sqrtf(kk);
+                                    r = v3(eta * d.x + cn * n.x, eta * d.y + cn * n.y, eta * d.z + cn * n.z);
+                                    reflect = false;
+                                }
+                            }
+                            if (reflect) {
+                                const float s2 = 2.0f * dn;
+                                r = v3(d.x - s2 * n.x, d.y - s2 * n.y, d.z - s2 * n.z);
+                            }
+                            const float len = __builtin_sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
+                            d = v3(r.x / len, r.y / len, r.z / len);
+                            const V3 off = v3(n.x * kEps, n.y * kEps, n.z * kEps);
+                            o = reflect ? v3(hi.point.x + off.x, hi.point.y + off.y, hi.point.z + off.z)
+                                        : v3(hi.point.x - off.x, hi.point.y - off.y, hi.point.z - off.z);
+                            live = true;
+                        }
+                    }
+                }
+            }
+            if (links < 0) continue;
+            const V3 ra = v3(rec[0], rec[64], rec[128]), rn = v3(rec[192], rec[256], rec[320]);
+            const float rt = rec[384];
+            // sums in k order; the first contributing ray is stored, not added to 0, so that a -0 component survives
+            if (hits == 0) { sa = ra; sn = rn; st_ = rt; }
+            else { sa = sa + ra; sn = sn + rn; st_ = st_ + rt; }
+            linkSum += links;
+            hits++;
+        }
+        if (!inside) continue;
+        float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
+        float ol = 0.0f;
+        if (hits > 0) {
+            const float n = (float)hits;
+            oa = make_float4(sa.x / n, sa.y / n, sa.z / n, n / (float)aovSpp);
+            on = make_float4(sn.x / n, sn.y / n, sn.z / n, st_ / n);
+            ol = (float)linkSum / n;
+        }
+        albedo[idx] = oa;
+        normalDepth[idx] = on;
+        if (linksOut) linksOut[idx] = ol;
+    }
+}
+
+// Workgroups of the chain pass: its own count, from its own resources (80 VGPRs, 23 KB of LDS per workgroup: 6 waves per SIMD =
+// 6 workgroups per CU, 138 of the CU's 160 KB). aov_blocks is the first-hit kernel's.
+constexpr int kAovChainWavesPerSimd = 6;
+int aov_chain_blocks(int nTiles, int numCU) { return std::max(1, std::min((nTiles + 3) / 4, numCU * kAovChainWavesPerSimd)); }
+
+hipError_t launch_aov_chain(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
+                            int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, int32_t* spill, hipStream_t stream) {
+    const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
+    hipLaunchKernelGGL(aov_chain_kernel, dim3(blocks), dim3(256), 0, stream, S, cam, jump, seed, w, h, tilesX, nTiles, aovSpp, maxLinks, albedo,
+                       normalDepth, links, spill);
     return hipGetLastError();
 }
 

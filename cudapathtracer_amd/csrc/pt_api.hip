@@ -1381,6 +1381,9 @@ namespace pt {      // pt_aov.hip
 int aov_blocks(int nTiles, int numCU);
 hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
                       int blocks, float4* albedo, float4* normalDepth, int32_t* spill, hipStream_t stream);
+int aov_chain_blocks(int nTiles, int numCU);
+hipError_t launch_aov_chain(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
+                            int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, int32_t* spill, hipStream_t stream);
 }
 
 // Argument checks of the AOV pass, all before the first HIP call (the device check comes last).
@@ -1424,6 +1427,44 @@ int pt_render_aovs(pt_scene* s, const pt_camera* cam, int w, int h, int aov_spp,
     if (int r = render_aovs(s, cam, w, h, aov_spp, seed, d, d + bytes, nullptr)) return r;
     HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The chain pass (pt_aov.hip: aov_chain_kernel): max_links, then the checks it shares with the first-hit pass, all before any HIP call.
+static int check_aov_chain_args(pt_scene* s, const pt_camera* cam, int w, int h, int aovSpp, int maxLinks, const void* a, const void* nd) {
+    if (maxLinks < 0 || maxLinks > 16) return fail(-1, "pt_render_aovs_chain: max_links %d must be 0..16", maxLinks);
+    return check_aov_args(s, cam, w, h, aovSpp, a, nd);
+}
+
+static int render_aovs_chain(pt_scene* s, const pt_camera* cam, int w, int h, int aovSpp, int maxLinks, uint64_t seed, void* dA, void* dN, void* dL,
+                             hipStream_t stream) {
+    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = aov_chain_blocks(nTiles, s->numCU);
+    int32_t* spill = nullptr;
+    if (s->ds.stackSpill > 0) {          // the AOV passes' own area (they share it: both run on the caller's stream, one after the other)
+        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
+        spill = (int32_t*)s->aovSpill.p;
+    }
+    HIP_OK(launch_aov_chain(s->ds, cam_to_kernel(*cam), (const uint32_t*)s->jump.p, seed, w, h, aovSpp, maxLinks, blocks, (float4*)dA, (float4*)dN,
+                            (float*)dL, spill, stream));
+    return 0;
+}
+
+int pt_render_aovs_chain_device(pt_scene* s, const pt_camera* cam, int w, int h, int aov_spp, int max_links, uint64_t seed, void* d_albedo,
+                                void* d_normal_depth, void* d_links, void* stream) {
+    if (int r = check_aov_chain_args(s, cam, w, h, aov_spp, max_links, d_albedo, d_normal_depth)) return r;
+    return render_aovs_chain(s, cam, w, h, aov_spp, max_links, seed, d_albedo, d_normal_depth, d_links, (hipStream_t)stream);
+}
+
+int pt_render_aovs_chain(pt_scene* s, const pt_camera* cam, int w, int h, int aov_spp, int max_links, uint64_t seed, float* out_albedo,
+                         float* out_normal_depth, float* out_links) {
+    if (int r = check_aov_chain_args(s, cam, w, h, aov_spp, max_links, out_albedo, out_normal_depth)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4), lbytes = (size_t)w * h * sizeof(float);
+    if (int r = s->aovOut.ensure(2 * bytes + lbytes)) return r;
+    char* d = (char*)s->aovOut.p;
+    if (int r = render_aovs_chain(s, cam, w, h, aov_spp, max_links, seed, d, d + bytes, out_links ? d + 2 * bytes : nullptr, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
+    if (out_links) HIP_OK(hipMemcpy(out_links, d + 2 * bytes, lbytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -12,6 +12,7 @@
 //                       pt_upsample + pt_temporal_accumulate_cur bring it into the same display-size history.
 //                       With converge on (pt_preview_set_converge) a frame whose camera rests selects the tiles that still need
 //                       samples from the history, renders moments on that list alone and carries the other tiles' history forward.
+//                       With a guide chain (pt_preview_set_guide_chain) every feature pass of a frame is pt_render_aovs_chain_device.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -121,6 +122,7 @@ struct pt_preview {
     char *S, *Q, *A, *N[2], *H[2], *L[2]; // sums, albedo; guide, history and history length twice (temporal 0: one guide only)
     char *ws, *filt, *mean, *rgba8;       // the filters' workspace, the filtered frame, the displayed mean and its bytes
     int scale;                            // render scale of the next frame; > 1 uses the buffers below (their own allocations)
+    int guideChain;                       // max_links of the feature passes; 0: the first-hit pass (pt_preview_set_guide_chain)
     char* lo;                             // four low-res float4 buffers of loCap pixels each: S, Q, albedo, guide
     size_t loCap;
     char* curEV;                          // w*h float4: pt_upsample's output
@@ -280,6 +282,17 @@ int pt_preview_set_scale(pt_preview* p, int scale) {
 
 int pt_preview_scale(pt_preview* p) { return p ? p->scale : pv_fail(-1, "pt_preview_scale: null session"); }
 
+int pt_preview_set_guide_chain(pt_preview* p, int max_links) {
+    if (!p) return pv_fail(-1, "pt_preview_set_guide_chain: null session");
+    if (max_links < 0 || max_links > 16) return pv_fail(-1, "pt_preview_set_guide_chain: max_links %d must be 0..16", max_links);
+    // guides from before and after a change do not validate against each other: the next frame is a first frame
+    if (max_links != p->guideChain) p->haveHist = p->haveFrame = p->haveTiles = false;
+    p->guideChain = max_links;
+    return 0;
+}
+
+int pt_preview_guide_chain(pt_preview* p) { return p ? p->guideChain : pv_fail(-1, "pt_preview_guide_chain: null session"); }
+
 int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
     if (!p) return pv_fail(-1, "pt_preview_set_converge: null session");
     if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
@@ -316,6 +329,12 @@ int pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live) {
     return 0;
 }
 
+// A feature pass of a frame: the first-hit pass, or the chain pass when the session has a guide chain.
+static int preview_aovs(pt_preview* p, const pt_camera* cam, int w, int h, uint64_t seed, void* dA, void* dN) {
+    if (p->guideChain > 0) return pt_render_aovs_chain_device(p->scene, cam, w, h, p->P.aov_spp, p->guideChain, seed, dA, dN, nullptr, p->stream);
+    return pt_render_aovs_device(p->scene, cam, w, h, p->P.aov_spp, seed, dA, dN, p->stream);
+}
+
 // A converging frame (the camera rests, a history exists, scale 1): the same five events around select + read-back + moments on
 // the live list | the whole feature pass | the accumulation with the live map | filter | resolve.
 static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
@@ -333,7 +352,7 @@ static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t
                                                    count, p->S, p->Q, st))
             return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (int r = pt_render_aovs_device(p->scene, cam, w, h, P.aov_spp, seed, p->A, p->N[nxt], st)) return r;
+    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[nxt])) return r;
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
     if (int r = pt_temporal_accumulate_live_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt], p->N[p->cur], p->H[p->cur],
                                                    p->L[p->cur], p->tLive[nt], &P.temporal_params, p->H[nxt], p->L[nxt], st))
@@ -364,8 +383,8 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
     PV_HIP_OK(hipEventRecord(p->ev[0], st));
     if (int r = pt_render_moments_device(p->scene, &lowCam, wl, hl, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, S, Q, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (int r = pt_render_aovs_device(p->scene, &lowCam, wl, hl, P.aov_spp, seed, Al, Nl, st)) return r;
-    if (int r = pt_render_aovs_device(p->scene, cam, w, h, P.aov_spp, seed, p->A, p->N[nxt], st)) return r;
+    if (int r = preview_aovs(p, &lowCam, wl, hl, seed, Al, Nl)) return r;
+    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[nxt])) return r;
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
     if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[nxt], nullptr, p->curEV, st)) return r;
     const void* shown = p->curEV;         // the (e, V) buffer the filter reads
@@ -397,7 +416,7 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
     // (the first stage checks its arguments, the camera's size among them, before it enqueues anything)
     if (int r = pt_render_moments_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->S, p->Q, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (int r = pt_render_aovs_device(p->scene, cam, w, h, P.aov_spp, seed, p->A, p->N[nxt], st)) return r;
+    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[nxt])) return r;
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
     const void* shown = p->S;             // what the resolve divides, and by what
     int shownSpp = P.spp;

@@ -303,6 +303,38 @@ int pt_render_aovs(pt_scene* scene, const pt_camera* camera, int w, int h, int a
 int pt_render_aovs_device(pt_scene* scene, const pt_camera* camera, int w, int h, int aov_spp, uint64_t seed,
                           void* d_albedo, void* d_normal_depth, void* stream);       /* device buffers, async */
 
+/* Feature buffers that follow mirrors and glass to the surface behind them. Same buffers, layout, rays (ray k of pixel (x, y)
+ * from the fresh stream keyed (seed + k, y*w + x)), closest hit (max_t 999999), sums in k order and final division as
+ * pt_render_aovs, but after its first hit each ray follows a deterministic CHAIN of at most max_links (0..16) specular links:
+ *   LINK RULE. The ray is in its chain while the material at its hit has isSpecular set and is a delta mirror (type 6) or a
+ *   smooth dielectric (type 2). A mirror reflects; a dielectric refracts, or reflects on total internal reflection. A hit on
+ *   any other material ends the chain there.
+ *   DIRECTION ARITHMETIC, every operation rounded once to f32 in the order written, left to right, nothing fused. d is the
+ *   unit ray direction, n resolve_hit's normal at the hit (it faces the ray), dn = d.x*n.x + d.y*n.y + d.z*n.z:
+ *     reflect:     r = d - (2*dn)*n                                   (per component: d.c - (2*dn)*n.c)
+ *     dielectric:  cosI = min(max(-dn, EPS), 1); eta = backface ? ior : 1/ior; k = 1 - (eta*eta)*(1 - cosI*cosI);
+ *                  k < 0: reflect as above; otherwise r = eta*d + (eta*cosI - sqrtf(k))*n   (per component: eta*d.c + (..)*n.c)
+ *     next ray:    d' = r / sqrtf(r.x*r.x + r.y*r.y + r.z*r.z)  (three IEEE divisions);
+ *                  o' = point + n*EPS after a reflection, point - n*EPS after a refraction (EPS = 1e-5: the beauty path's offsets).
+ *   RESULT OF A RAY whose chain ends on a non-specular surface after L links: that surface's albedo (material's albedo, or the
+ *   texture sample: no tint is multiplied at a mirror or an interface, as the path multiplies none), resolve_hit's normal there,
+ *   depth = the f32 sum of the links' t in link order (t0, + t1, + t2 ...), links = L. For a planar mirror, camera ray * depth is
+ *   the virtual image point, so pt_temporal_accumulate's reprojection holds through it.
+ *   FALLBACK: a ray whose chain leaves the scene, or that is still on a specular surface after max_links links, reports its
+ *   FIRST hit's albedo, normal and t, with links = 0. A ray whose first ray misses contributes nothing, as in pt_render_aovs.
+ *   DELIBERATE SIMPLIFICATIONS: the medium stack and priorities are ignored (an interface the beauty path would pass straight
+ *   through, such as a nested lower-priority dielectric, is refracted); there is no Fresnel branch choice (refraction is always
+ *   followed where it exists); there is no absorption. The guide is a feature buffer, not radiance.
+ * out_links (w*h floats, may be NULL): the mean link count over the rays that hit (integer sum, converted to f32, divided by the
+ * hit count), 0 where nothing hit. The coverage channel is bit-identical to pt_render_aovs'; a pixel whose rays all hit a
+ * non-specular surface first is bit-identical to pt_render_aovs in all eight floats; max_links = 0 is pt_render_aovs bit for bit
+ * with links all 0. Like pt_render_aovs the pass touches no RNG state, accumulator or counter of the scene. Arguments are checked
+ * before any HIP call (those of pt_render_aovs, and max_links in 0..16: -1 with a message). */
+int pt_render_aovs_chain(pt_scene* scene, const pt_camera* camera, int w, int h, int aov_spp, int max_links, uint64_t seed,
+                         float* out_albedo, float* out_normal_depth, float* out_links /* w*h floats, may be NULL */);
+int pt_render_aovs_chain_device(pt_scene* scene, const pt_camera* camera, int w, int h, int aov_spp, int max_links, uint64_t seed,
+                                void* d_albedo, void* d_normal_depth, void* d_links /* may be NULL */, void* stream);
+
 /* Edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on albedo-demodulated colour, guided by the buffers
  * above. The contract, per pixel p (all buffers w*h float4):
  *   m_p = S_p / spp. p PASSES THROUGH (output = S_p bit for bit, all four channels) if its coverage is 0 or any of m_p.rgb
@@ -613,7 +645,14 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  *   temporal 0: pt_denoise_hist_device on cur itself (filter 0: with 0 iterations), then pt_resolve_device(spp = 1).
  * History, its lengths, the guide and the previous camera are display-size at every scale, so the scale may change from frame
  * to frame without a reset. A failed scaled frame leaves the session as a failed frame does above. Stats of a scaled frame:
- * render_ms is the low-res moments render, aov_ms both feature passes, accumulate_ms the upsample and the accumulation. */
+ * render_ms is the low-res moments render, aov_ms both feature passes, accumulate_ms the upsample and the accumulation.
+ *
+ * GUIDE CHAIN. pt_preview_set_guide_chain(p, max_links): 0 (the default) is the frames above, bit for bit. With 1..16 EVERY
+ * feature pass of a frame (the display-size guide, at a render scale above 1 the low-res one too, and a converging frame's) is
+ * pt_render_aovs_chain_device(max_links, links NULL) with the same camera, aov_spp and seed in place of pt_render_aovs_device, so
+ * the frames equal that chain of host calls. The value may change between frames; a call that CHANGES it resets the session as
+ * pt_preview_reset does, because guides from before and after the change do not validate against each other (a call with the
+ * current value changes nothing). -1 on a NULL session or a value outside 0..16, the session unchanged. */
 typedef struct pt_preview pt_preview;
 typedef struct pt_preview_params {
     int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
@@ -635,6 +674,8 @@ int  pt_preview_frame(pt_preview* p, const pt_camera* camera, uint64_t seed);
 int  pt_preview_reset(pt_preview* p);                                      /* the next frame is a first frame */
 int  pt_preview_set_scale(pt_preview* p, int scale);                       /* 1..8: the render scale of the frames that follow */
 int  pt_preview_scale(pt_preview* p);                                      /* the current scale; -1 on a NULL session */
+int  pt_preview_set_guide_chain(pt_preview* p, int max_links);             /* 0..16: the feature passes of the frames that follow */
+int  pt_preview_guide_chain(pt_preview* p);                                /* the current value; -1 on a NULL session */
 int  pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len);
 const void* pt_preview_device_rgba8(pt_preview* p);                        /* w*h*4 bytes */
 const void* pt_preview_device_mean(pt_preview* p);                         /* w*h float4 */

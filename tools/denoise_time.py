@@ -1,8 +1,11 @@
 """Device time of the feature-buffer pass and of the denoiser at 1920x1080 (HIP events around each, after warm-up).
 
-    python tools/denoise_time.py [--w 1920 --h 1080 --reps 20 --aov-spp 1 --iterations 5 --scene cornell|blob]
+    python tools/denoise_time.py [--w 1920 --h 1080 --reps 20 --aov-spp 1 --iterations 5 --scene cornell|mixed|blob --max-links 8]
+    python tools/denoise_time.py --resources          (no device needed: compiles pt_aov.hip and prints both kernels' registers)
 
-Prints one JSON line: median / min milliseconds of pt_render_aovs_device, of pt_denoise_device and pt_denoise_var_device (all
+Prints one JSON line: median / min milliseconds of pt_render_aovs_device, of pt_render_aovs_chain_device (`aov_chain`: the pass that
+follows mirrors and glass, --max-links links; on `cornell` no ray has a chain, `mixed` is bench.py --full's mixed Cornell box with
+a mirror box, a glass box around a water box and a gold box), of pt_denoise_device and pt_denoise_var_device (all
 iterations; --iterations sets both, otherwise the variance-guided filter is timed at the classic filter's count and at its own
 default), of the 16-spp depth-8 frame they post-process in one launch (the megakernel's device time, and the launcher's wall
 time), of the same frame as a moments render of 4 batches of 4 and of 2 batches of 8 (pt_render_moments_device: wall time, it
@@ -11,12 +14,34 @@ launch."""
 import argparse
 import json
 import os
+import re
+import subprocess
 import sys
 import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def aov_kernel_resources():
+    """{kernel: {vgpr_count, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size (scratch bytes per lane),
+    group_segment_fixed_size (LDS bytes per workgroup)}} of pt_aov.hip's two kernels, from the code-object notes of a device-only
+    compile with the Makefile's flags."""
+    csrc = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "pt_aov.s")
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S",
+                               "--cuda-device-only", "-o", out, os.path.join(csrc, "pt_aov.hip")], stderr=subprocess.DEVNULL)
+        text = open(out).read()
+    res = {}
+    notes = text[text.index("amdhsa.kernels:"):]
+    for block in re.split(r"^  - ", notes, flags=re.M)[1:]:            # one list item per kernel; its keys come in alphabetical order
+        name = re.search(r"^\s*\.name:\s+_ZN2pt\d+(aov\w*?_kernel)E", block, flags=re.M)
+        if name:
+            res[name.group(1)] = {k: int(v) for k, v in re.findall(
+                r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)$", block, flags=re.M)}
+    return res
 
 
 def main():
@@ -26,8 +51,13 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--aov-spp", type=int, default=1)
     ap.add_argument("--iterations", type=int, default=None)
-    ap.add_argument("--scene", choices=("cornell", "blob"), default="cornell")
+    ap.add_argument("--scene", choices=("cornell", "mixed", "blob"), default="cornell")
+    ap.add_argument("--max-links", type=int, default=8)
+    ap.add_argument("--resources", action="store_true")
     a = ap.parse_args()
+    if a.resources:
+        print(json.dumps(aov_kernel_resources()))
+        return
     import torch
     from cudapathtracer_amd import api, scenes
     if not torch.cuda.is_available():
@@ -35,8 +65,9 @@ def main():
     torch.cuda.set_device(0)
     w, h = a.w, a.h
     d = tempfile.mkdtemp()
-    gen = scenes.cornell if a.scene == "cornell" else scenes.blob_in_box
-    hs = api.HostScene(gen(d, width=w, height=h, spp=16, max_depth=8, name="dt")["config"])
+    gen = scenes.blob_in_box if a.scene == "blob" else scenes.cornell
+    kw = dict(tall_material=19, short_material=5, nested=True, extra_boxes=1, extra_materials=[4]) if a.scene == "mixed" else {}
+    hs = api.HostScene(gen(d, width=w, height=h, spp=16, max_depth=8, name="dt", **kw)["config"])
     sc = api.Scene(hs)
     cam = hs.camera()
     colors = torch.zeros(h, w, 4, device="cuda:0")
@@ -49,6 +80,11 @@ def main():
 
     def aov():
         sc.render_aovs_device(cam, w, h, alb.data_ptr(), nd.data_ptr(), aov_spp=a.aov_spp, stream=stream)
+
+    lnk = torch.empty(h, w, device="cuda:0")
+
+    def aov_chain():
+        sc.render_aovs_chain_device(cam, w, h, a.max_links, alb.data_ptr(), nd.data_ptr(), lnk.data_ptr(), aov_spp=a.aov_spp, stream=stream)
 
     iters = a.iterations or api.denoise_defaults()["iterations"]
     iters_var = a.iterations or api.denoise_var_defaults()["iterations"]
@@ -94,7 +130,7 @@ def main():
         res[name + "_ms_median"] = round(ts[len(ts) // 2], 3)
         res[name + "_ms_min"] = round(ts[0], 3)
     moments(4)()                                          # colors, sq: the 16-spp frame in 4 batches, what the filters below read
-    timed = [("aov", aov), ("denoise", dn), ("denoise_var", lambda: dn_var(iters))]
+    timed = [("aov_chain", aov_chain), ("aov", aov), ("denoise", dn), ("denoise_var", lambda: dn_var(iters))]    # (aov last of the two: the filters read ITS buffers)
     if iters_var != iters:
         timed.append(("denoise_var_default", lambda: dn_var(iters_var)))
     for name, fn in timed:
@@ -110,6 +146,8 @@ def main():
         ts.sort()
         res[name + "_ms_median"] = round(ts[len(ts) // 2], 4)
         res[name + "_ms_min"] = round(ts[0], 4)
+    res["max_links"] = a.max_links
+    res["mean_links"] = round(float(lnk.mean().item()), 4)     # of the chain pass: how much of the frame has a chain at all
     print(json.dumps(res))
 
 

@@ -1,12 +1,15 @@
 """Device time of temporal accumulation and of the history filter at 1920x1080 (HIP events around each, after warm-up).
 
-    python tools/temporal_time.py [--w 1920 --h 1080 --reps 20]
+    python tools/temporal_time.py [--w 1920 --h 1080 --reps 20] [--specular [--max-links 8]]
 
 Prints one JSON line: median / min milliseconds of pt_temporal_accumulate_device for a still camera (the identity instantiation)
 and for a moving one (projection and four taps), of pt_denoise_hist_device at its default iterations and, in the same run for
 comparison, of pt_denoise_var_device at its defaults; the bytes the accumulate pass moves per pixel (64 B of this frame's four
 buffers, 20 B written, plus the previous guide, history and length once: 36 B, the gathers of neighbouring pixels share their
-lines) and the fraction of the 8 TB/s HBM peak that makes at the measured time."""
+lines) and the fraction of the 8 TB/s HBM peak that makes at the measured time.
+--specular runs the same still and moving frames on the glass + mirror Cornell box, once with first-hit guides and once with the
+guides of pt_render_aovs_chain (--max-links): the line then holds both sets of numbers under "first_hit" and "chain", with the
+feature pass's own time and the mean history length after the moving frame (what share of the history still validates)."""
 import argparse
 import json
 import os
@@ -25,6 +28,8 @@ def main():
     ap.add_argument("--w", type=int, default=1920)
     ap.add_argument("--h", type=int, default=1080)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--specular", action="store_true")
+    ap.add_argument("--max-links", type=int, default=8)
     a = ap.parse_args()
     import torch
     from cudapathtracer_amd import api, scenes
@@ -32,8 +37,19 @@ def main():
         raise SystemExit("temporal_time.py needs a HIP device")
     torch.cuda.set_device(0)
     w, h = a.w, a.h
-    hs = api.HostScene(scenes.cornell(tempfile.mkdtemp(), width=w, height=h, spp=4, max_depth=8, name="tt")["config"])
+    kw = dict(tall_material=5, short_material=19) if a.specular else {}
+    hs = api.HostScene(scenes.cornell(tempfile.mkdtemp(), width=w, height=h, spp=4, max_depth=8, name="tt", **kw)["config"])
     sc = api.Scene(hs)
+    if a.specular:
+        print(json.dumps({"w": w, "h": h, "scene": "glass + mirror Cornell", "max_links": a.max_links,
+                          "first_hit": measure(a, torch, api, sc, 0), "chain": measure(a, torch, api, sc, a.max_links)}))
+    else:
+        print(json.dumps(measure(a, torch, api, sc, 0)))
+
+
+def measure(a, torch, api, sc, links):
+    """The tool's numbers with first-hit guides (links 0) or chain guides."""
+    w, h = a.w, a.h
     cam0 = api.make_camera(True, (0.0, 0.0, 1.0), (0.0, 0.0, 0.0), 60.0, w, h)
     cam1 = api.make_camera(True, (0.03, 0.01, 1.0), (0.0, 0.8, 0.0), 60.0, w, h)
     stream = torch.cuda.current_stream().cuda_stream
@@ -42,8 +58,14 @@ def main():
     def frame(cam, seed):
         S, Q, A, N = buf(), buf(), buf(), buf()
         sc.render_moments_device(cam, w, h, 4, 2, 8, S.data_ptr(), Q.data_ptr(), seed=seed, stream=stream)
-        sc.render_aovs_device(cam, w, h, A.data_ptr(), N.data_ptr(), seed=seed, stream=stream)
+        aovs(cam, A, N, seed)
         return S, Q, A, N
+
+    def aovs(cam, A, N, seed):
+        if links:
+            sc.render_aovs_chain_device(cam, w, h, links, A.data_ptr(), N.data_ptr(), None, seed=seed, stream=stream)
+        else:
+            sc.render_aovs_device(cam, w, h, A.data_ptr(), N.data_ptr(), seed=seed, stream=stream)
 
     f0, f_still, f_moved = frame(cam0, 1), frame(cam0, 2), frame(cam1, 2)
     hist0, hist1 = buf(), buf()
@@ -64,8 +86,12 @@ def main():
         api.denoise_var_device(w, h, p(f_moved[0]), p(f_moved[1]), 4, 2, p(f_moved[2]), p(f_moved[3]), p(ws), p(out), stream=stream)
 
     res = {"w": w, "h": h, "iterations_default": api.denoise_var_defaults()["iterations"], "accumulate_bytes_per_pixel": BYTES_PER_PIXEL}
-    for name, fn in (("accumulate_identity", accumulate(cam0, f_still)), ("accumulate_moving", accumulate(cam1, f_moved)),
-                     ("denoise_hist", dn_hist), ("denoise_var", dn_var)):
+    timed = [("accumulate_identity", accumulate(cam0, f_still)), ("accumulate_moving", accumulate(cam1, f_moved)),
+             ("denoise_hist", dn_hist), ("denoise_var", dn_var)]
+    if a.specular:
+        fa, fn_ = buf(), buf()
+        timed.insert(0, ("feature_pass", lambda: aovs(cam1, fa, fn_, 2)))
+    for name, fn in timed:
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
@@ -81,7 +107,7 @@ def main():
         if name.startswith("accumulate"):
             res[name + "_hbm_fraction"] = round(BYTES_PER_PIXEL * w * h / (ts[len(ts) // 2] * 1e-3) / HBM_PEAK, 4)
             res[name + "_mean_length"] = round(float(len1.mean()), 3)
-    print(json.dumps(res))
+    return res
 
 
 if __name__ == "__main__":
