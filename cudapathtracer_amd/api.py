@@ -199,6 +199,9 @@ def lib():
     L.pt_render_aovs_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, u64, vp, vp, vp]
     L.pt_render_aovs_chain.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, u64, vp, vp, vp]
     L.pt_render_aovs_chain_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, u64, vp, vp, vp, vp]
+    L.pt_render_aovs_centre.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp, vp, vp]
+    L.pt_render_aovs_centre_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp, vp, vp, vp]
+    L.pt_probe_centre_rays.argtypes = [C.POINTER(Camera), i32, vp, vp]
     L.pt_denoise_defaults.restype = None; L.pt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
     L.pt_denoise_workspace_bytes.restype = C.c_size_t; L.pt_denoise_workspace_bytes.argtypes = [i32, i32]
     L.pt_denoise.argtypes = [i32, i32, vp, i32, vp, vp, C.POINTER(DenoiseParams), vp]
@@ -225,6 +228,8 @@ def lib():
     L.pt_camera_scaled.argtypes = [C.POINTER(Camera), i32, C.POINTER(Camera)]
     L.pt_upsample.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(UpsampleParams), vp]
     L.pt_upsample_device.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp]
+    L.pt_guide_subsample.argtypes = [i32, i32, i32, vp, vp, vp, vp]
+    L.pt_guide_subsample_device.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
     L.pt_temporal_accumulate_cur.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, C.POINTER(TemporalParams), vp, vp]
     L.pt_temporal_accumulate_cur_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, C.POINTER(TemporalParams),
                                                     vp, vp, vp]
@@ -239,6 +244,9 @@ def lib():
     L.pt_preview_scale.argtypes = [vp]
     L.pt_preview_set_guide_chain.argtypes = [vp, i32]
     L.pt_preview_guide_chain.argtypes = [vp]
+    L.pt_preview_set_guide_centre.argtypes = [vp, i32]
+    L.pt_preview_guide_centre.argtypes = [vp]
+    L.pt_preview_guide_passes.argtypes = [vp]
     L.pt_preview_read.argtypes = [vp, vp, vp, vp, vp]
     L.pt_preview_device_rgba8.restype = vp; L.pt_preview_device_rgba8.argtypes = [vp]
     L.pt_preview_device_mean.restype = vp; L.pt_preview_device_mean.argtypes = [vp]
@@ -547,6 +555,22 @@ class Scene:
         """pt_render_aovs_chain_device: the same into device buffers (w*h float4 twice, and w*h floats or None), asynchronous on `stream`."""
         _check(lib().pt_render_aovs_chain_device(self.h, C.byref(camera), w, h, aov_spp, max_links, seed, d_albedo_ptr, d_normal_depth_ptr,
                                                  d_links_ptr or None, stream or None), "pt_render_aovs_chain_device")
+
+    def render_aovs_centre(self, camera, w, h, max_links=0, links=False):
+        """pt_render_aovs_centre: feature buffers through pixel centres: one ray per pixel that no random draw reaches (the camera's
+        jitter and aperture play no part), so there is no aov_spp and no seed. Equals render_aovs_chain(cam0, w, h, max_links,
+        aov_spp=1) bit for bit, cam0 being the camera with antiAliasJitterDist = aperture = 0. Returns (albedo, normal_depth), and
+        the link count [h,w] float32 as a third item with links=True."""
+        alb = np.zeros((h, w, 4), np.float32); nd = np.zeros((h, w, 4), np.float32)
+        ln = np.zeros((h, w), np.float32) if links else None
+        _check(lib().pt_render_aovs_centre(self.h, C.byref(camera), w, h, max_links, _p(alb), _p(nd), _p(ln) if links else None),
+               "pt_render_aovs_centre")
+        return (alb, nd, ln) if links else (alb, nd)
+
+    def render_aovs_centre_device(self, camera, w, h, max_links, d_albedo_ptr, d_normal_depth_ptr, d_links_ptr=0, stream=0):
+        """pt_render_aovs_centre_device: the same into device buffers (w*h float4 twice, and w*h floats or None), asynchronous on `stream`."""
+        _check(lib().pt_render_aovs_centre_device(self.h, C.byref(camera), w, h, max_links, d_albedo_ptr, d_normal_depth_ptr, d_links_ptr or None,
+                                                  stream or None), "pt_render_aovs_centre_device")
 
     def render_adaptive(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, integrator=UNIDIRECTIONAL, use_mis=True,
                         seed=SEED):
@@ -1115,6 +1139,25 @@ def upsample_device(w, h, scale, d_rgba_sum_lo_ptr, d_sq_sum_lo_ptr, spp, batche
            "pt_upsample_device")
 
 
+def guide_subsample(scale, albedo, normal_depth):
+    """pt_guide_subsample (host, blocking): the low-res guide of CENTRE feature buffers ([h, w, 4] float32, render_aovs_centre) at
+    render scale `scale`: (albedo_lo, normal_depth_lo) = the inputs' [::scale, ::scale], which is render_aovs_centre with
+    scaled_camera(cam, scale) bit for bit."""
+    A, N = _f4_frames("guide_subsample", (("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = A.shape[:2]
+    scale = int(scale)
+    lo = (h // scale, w // scale, 4) if scale > 0 else (0, 0, 4)
+    Al, Nl = np.empty(lo, np.float32), np.empty(lo, np.float32)
+    _check(lib().pt_guide_subsample(w, h, scale, _p(A), _p(N), _p(Al), _p(Nl)), "pt_guide_subsample")
+    return Al, Nl
+
+
+def guide_subsample_device(w, h, scale, d_albedo_ptr, d_normal_depth_ptr, d_out_albedo_lo_ptr, d_out_normal_depth_lo_ptr, stream=0):
+    """pt_guide_subsample_device: device buffers (w*h float4 in, (w / scale) * (h / scale) float4 out), asynchronous on `stream`."""
+    _check(lib().pt_guide_subsample_device(w, h, int(scale), d_albedo_ptr, d_normal_depth_ptr, d_out_albedo_lo_ptr, d_out_normal_depth_lo_ptr,
+                                           stream or None), "pt_guide_subsample_device")
+
+
 def denoise_hist_workspace_bytes(w, h):
     return int(lib().pt_denoise_hist_workspace_bytes(w, h))
 
@@ -1278,6 +1321,22 @@ class Preview:
     def guide_chain(self):
         return lib().pt_preview_guide_chain(self.handle)
 
+    def set_guide_centre(self, on):
+        """pt_preview_set_guide_centre: the frames that follow trace their guides through pixel centres (render_aovs_centre with the
+        guide chain's max_links), take a scaled frame's low-res guide by guide_subsample, and launch no feature pass while the camera
+        rests. A call that changes the value drops the history, as reset() does."""
+        _check(lib().pt_preview_set_guide_centre(self.handle, int(on)), "pt_preview_set_guide_centre")
+        return self
+
+    @property
+    def guide_centre(self):
+        return lib().pt_preview_guide_centre(self.handle)
+
+    @property
+    def guide_passes(self):
+        """pt_preview_guide_passes: feature-pass launches of all good frames since the session was created."""
+        return lib().pt_preview_guide_passes(self.handle)
+
     def set_converge(self, threshold=None, min_history=None):
         """pt_preview_set_converge: while the camera rests, the frames that follow render only the 8x8 tiles whose history has
         not converged (temporal_select's rule) and carry the others forward. threshold 0 (or False) turns it off, None takes the
@@ -1403,4 +1462,12 @@ def probe_camera_rays(camera, xy, seed=SEED):
     xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
     out = np.zeros((len(xy), 6), np.float32)
     _check(lib().pt_probe_camera_rays(C.byref(camera), seed, len(xy), _p(xy), _p(out)), "pt_probe_camera_rays")
+    return out
+
+
+def probe_centre_rays(camera, xy):
+    """pt_probe_centre_rays: the centre rays of render_aovs_centre, [n, 6] float32 (o, d); no seed, none is read."""
+    xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+    out = np.zeros((len(xy), 6), np.float32)
+    _check(lib().pt_probe_centre_rays(C.byref(camera), len(xy), _p(xy), _p(out)), "pt_probe_centre_rays")
     return out

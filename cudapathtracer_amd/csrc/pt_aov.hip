@@ -215,4 +215,168 @@ hipError_t launch_aov_chain(const DeviceScene& S, const CamK& cam, const uint32_
     return hipGetLastError();
 }
 
+// ---- centre guides (pt_render_aovs_centre, pt_probe_centre_rays) -------------------------------------------------------------------
+// The centre ray of pixel (x, y): camera_ray with antiAliasJitterDist = 0 and aperture = 0, operation for operation. With those two
+// zeros camera_ray's draws reach nothing: (u01 - 0.5) * 0 is +-0 and (float)x + +-0 is (float)x; the lens sample is skipped and lens
+// stays (0, 0, 0). So no Rng is needed, and the ray has no seed. `origin + 0` is kept: it turns a -0 component of the origin into +0,
+// as camera_ray does.
+PT_DEV void camera_ray_centre(const CamK& cam, int x, int y, V3& o, V3& d) {
+    const float aspect = (float)cam.w / (float)cam.h;
+    const float u = (2.0f * ((float)x / (float)cam.w) - 1.0f) * aspect * cam.fovScale;
+    const float v = (2.0f * ((float)y / (float)cam.h) - 1.0f) * cam.fovScale;
+    const V3 focal = cam.origin + (cam.right * (u * cam.focalDist)) + (cam.up * (v * cam.focalDist)) + (cam.forward * cam.focalDist);
+    o = cam.origin + v3(0.0f);
+    d = normalize(focal - o);
+}
+
+__global__ void probe_centre_kernel(CamK cam, int n, const int* __restrict__ xy, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3 o, d;
+    camera_ray_centre(cam, xy[2 * i], xy[2 * i + 1], o, d);
+    out[6 * i] = o.x; out[6 * i + 1] = o.y; out[6 * i + 2] = o.z; out[6 * i + 3] = d.x; out[6 * i + 4] = d.y; out[6 * i + 5] = d.z;
+}
+
+hipError_t launch_probe_centre(const CamK& cam, int n, const int* xy, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(probe_centre_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, cam, n, xy, out);
+    return hipGetLastError();
+}
+
+// aov_centre_kernel — aov_kernel for the one centre ray of each pixel: its tiling, traversal and record, without the stream seeding
+// (no jump table, no Rng in registers) and without the sums over k: one ray, so the hit itself is the result (aov_kernel divides
+// it by n = 1, which changes no bit, and writes coverage 1 / 1).
+__global__ void __launch_bounds__(256) aov_centre_kernel(DeviceScene S, CamK cam, int w, int h, int tilesX, int nTiles,
+                                                         float4* __restrict__ albedo, float4* __restrict__ normalDepth, int32_t* spill) {
+    __shared__ int32_t ldsStack[4][kStackLds][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + wave;
+    Stack<kStackLds> st; st.lds = (lds_i32*)&ldsStack[wave][0][0] + lane; st.sp = 0;
+    st.spill = spill ? spill + (size_t)gw * S.stackSpill * 64 + lane : nullptr;
+    SceneCache C; C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
+    Ctr c = {};
+    for (int tile = gw; tile < nTiles; tile += gridDim.x * 4) {
+        const int x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
+        if (!(x < w && y < h)) continue;
+        const size_t idx = (size_t)y * w + x;
+        V3 o, d;
+        camera_ray_centre(cam, x, y, o, d);
+        Hit hit;
+        trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+        float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
+        if (hit.tri >= 0) {
+            HitInfo hi; resolve_hit(S, hit, o, d, hi);
+            V3 a; float trans;
+            material_inputs(S.mats[hi.material], S.textures, hi.uvx, hi.uvy, true, a, trans);
+            oa = make_float4(a.x, a.y, a.z, 1.0f);
+            on = make_float4(hi.normal.x, hi.normal.y, hi.normal.z, hit.t);
+        }
+        albedo[idx] = oa;
+        normalDepth[idx] = on;
+    }
+}
+
+// Workgroups of the centre first-hit pass: without the seeding the kernel needs 63 VGPRs, so 8 waves per SIMD = 8 workgroups per CU
+// are resident (8 x 16 KB of LDS). The centre chain kernel (69 VGPRs, 23 KB) stays at aov_chain_blocks' 6: 7 would need 161 KB.
+int aov_centre_blocks(int nTiles, int numCU) { return std::max(1, std::min((nTiles + 3) / 4, numCU * 8)); }
+
+hipError_t launch_aov_centre(const DeviceScene& S, const CamK& cam, int w, int h, int blocks, float4* albedo, float4* normalDepth, int32_t* spill,
+                             hipStream_t stream) {
+    const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
+    hipLaunchKernelGGL(aov_centre_kernel, dim3(blocks), dim3(256), 0, stream, S, cam, w, h, tilesX, nTiles, albedo, normalDepth, spill);
+    return hipGetLastError();
+}
+
+// aov_centre_chain_kernel — aov_chain_kernel for the one centre ray of each pixel: the same link loop, link rule, fallback and LDS
+// record (the arithmetic below is aov_chain_kernel's, operation for operation: tests/aov_chain_ref.py restates both), without the
+// stream seeding and the sums over k.
+__global__ void __launch_bounds__(256) aov_centre_chain_kernel(DeviceScene S, CamK cam, int w, int h, int tilesX, int nTiles, int maxLinks,
+                                                               float4* __restrict__ albedo, float4* __restrict__ normalDepth,
+                                                               float* __restrict__ linksOut, int32_t* spill) {
+    __shared__ int32_t ldsStack[4][kStackLds][64];
+    __shared__ float ldsRec[4][7][64];           // the ray's record (albedo, normal, depth), lane-interleaved, as in aov_chain_kernel
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + wave;
+    Stack<kStackLds> st; st.lds = (lds_i32*)&ldsStack[wave][0][0] + lane; st.sp = 0;
+    st.spill = spill ? spill + (size_t)gw * S.stackSpill * 64 + lane : nullptr;
+    float* rec = &ldsRec[wave][0][lane];          // rec[j * 64], j = 0..6; only this lane touches it
+    SceneCache C; C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
+    Ctr c = {};
+    for (int tile = gw; tile < nTiles; tile += gridDim.x * 4) {
+        const int x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
+        const bool inside = x < w && y < h;
+        V3 o = v3(0.0f), d = v3(0.0f);
+        if (inside) camera_ray_centre(cam, x, y, o, d);
+        float depth = 0.0f;
+        int links = -1;                          // -1: no hit at all
+        bool live = inside;
+        for (int i = 0; i <= maxLinks; i++) {
+            if (!__ballot(live)) break;
+            if (live) {
+                Hit hit;
+                trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+                live = false;
+                if (hit.tri >= 0) {              // (a miss: no hit at all at i = 0, the first hit's record stands after that)
+                    HitInfo hi; resolve_hit(S, hit, o, d, hi);
+                    const PMat& m = S.mats[hi.material];
+                    const bool spec = (m.flags & kMatSpecular) && (m.type == 6 || m.type == 2);
+                    depth = i == 0 ? hit.t : depth + hit.t;
+                    if (i == 0 || !spec) {
+                        V3 a; float trans;
+                        material_inputs(m, S.textures, hi.uvx, hi.uvy, true, a, trans);
+                        rec[0] = a.x; rec[64] = a.y; rec[128] = a.z;
+                        rec[192] = hi.normal.x; rec[256] = hi.normal.y; rec[320] = hi.normal.z; rec[384] = depth;
+                        links = i;
+                    }
+                    if (spec && i < maxLinks) {
+                        const V3 n = hi.normal;
+                        const float dn = d.x * n.x + d.y * n.y + d.z * n.z;
+                        bool reflect = true;
+                        V3 r = v3(0.0f);
+                        if (m.type == 2) {
+                            const float cosI = fminf_(fmaxf_(-dn, kEps), 1.0f);
+                            const float eta = hi.backface ? m.ior : 1.0f / m.ior;
+                            const float kk = 1.0f - (eta * eta) * (1.0f - cosI * cosI);
+                            if (!(kk < 0.0f)) {
+                                const float cn = eta * cosI - __builtin_sqrtf(kk);
+                                r = v3(eta * d.x + cn * n.x, eta * d.y + cn * n.y, eta * d.z + cn * n.z);
+                                reflect = false;
+                            }
+                        }
+                        if (reflect) {
+                            const float s2 = 2.0f * dn;
+                            r = v3(d.x - s2 * n.x, d.y - s2 * n.y, d.z - s2 * n.z);
+                        }
+                        const float len = __builtin_sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
+                        d = v3(r.x / len, r.y / len, r.z / len);
+                        const V3 off = v3(n.x * kEps, n.y * kEps, n.z * kEps);
+                        o = reflect ? v3(hi.point.x + off.x, hi.point.y + off.y, hi.point.z + off.z)
+                                    : v3(hi.point.x - off.x, hi.point.y - off.y, hi.point.z - off.z);
+                        live = true;
+                    }
+                }
+            }
+        }
+        if (!inside) continue;
+        const size_t idx = (size_t)y * w + x;
+        float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
+        float ol = 0.0f;
+        if (links >= 0) {
+            oa = make_float4(rec[0], rec[64], rec[128], 1.0f);
+            on = make_float4(rec[192], rec[256], rec[320], rec[384]);
+            ol = (float)links;
+        }
+        albedo[idx] = oa;
+        normalDepth[idx] = on;
+        if (linksOut) linksOut[idx] = ol;
+    }
+}
+
+hipError_t launch_aov_centre_chain(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth,
+                                   float* links, int32_t* spill, hipStream_t stream) {
+    const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
+    hipLaunchKernelGGL(aov_centre_chain_kernel, dim3(blocks), dim3(256), 0, stream, S, cam, w, h, tilesX, nTiles, maxLinks, albedo, normalDepth, links,
+                       spill);
+    return hipGetLastError();
+}
+
 }  // namespace pt

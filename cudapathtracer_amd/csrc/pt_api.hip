@@ -1384,6 +1384,12 @@ hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jum
 int aov_chain_blocks(int nTiles, int numCU);
 hipError_t launch_aov_chain(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
                             int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, int32_t* spill, hipStream_t stream);
+int aov_centre_blocks(int nTiles, int numCU);
+hipError_t launch_aov_centre(const DeviceScene& S, const CamK& cam, int w, int h, int blocks, float4* albedo, float4* normalDepth, int32_t* spill,
+                             hipStream_t stream);
+hipError_t launch_aov_centre_chain(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth,
+                                   float* links, int32_t* spill, hipStream_t stream);
+hipError_t launch_probe_centre(const CamK& cam, int n, const int* xy, float* out, hipStream_t stream);
 }
 
 // Argument checks of the AOV pass, all before the first HIP call (the device check comes last).
@@ -1462,6 +1468,45 @@ int pt_render_aovs_chain(pt_scene* s, const pt_camera* cam, int w, int h, int ao
     if (int r = s->aovOut.ensure(2 * bytes + lbytes)) return r;
     char* d = (char*)s->aovOut.p;
     if (int r = render_aovs_chain(s, cam, w, h, aov_spp, max_links, seed, d, d + bytes, out_links ? d + 2 * bytes : nullptr, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
+    if (out_links) HIP_OK(hipMemcpy(out_links, d + 2 * bytes, lbytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The centre pass (pt_aov.hip: aov_centre_kernel, aov_centre_chain_kernel): one unjittered pinhole ray per pixel, no seed.
+static int check_aov_centre_args(pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, const void* a, const void* nd) {
+    if (maxLinks < 0 || maxLinks > 16) return fail(-1, "pt_render_aovs_centre: max_links %d must be 0..16", maxLinks);
+    return check_aov_args(s, cam, w, h, 1, a, nd);
+}
+
+// max_links 0 without a links buffer is the first-hit kernel; everything else the chain kernel (bit-identical where both apply).
+static int render_aovs_centre(pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, void* dA, void* dN, void* dL, hipStream_t stream) {
+    const bool chain = maxLinks > 0 || dL;
+    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = chain ? aov_chain_blocks(nTiles, s->numCU) : aov_centre_blocks(nTiles, s->numCU);
+    int32_t* spill = nullptr;
+    if (s->ds.stackSpill > 0) {          // the AOV passes' own area
+        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
+        spill = (int32_t*)s->aovSpill.p;
+    }
+    if (chain) HIP_OK(launch_aov_centre_chain(s->ds, cam_to_kernel(*cam), w, h, maxLinks, blocks, (float4*)dA, (float4*)dN, (float*)dL, spill, stream));
+    else HIP_OK(launch_aov_centre(s->ds, cam_to_kernel(*cam), w, h, blocks, (float4*)dA, (float4*)dN, spill, stream));
+    return 0;
+}
+
+int pt_render_aovs_centre_device(pt_scene* s, const pt_camera* cam, int w, int h, int max_links, void* d_albedo, void* d_normal_depth, void* d_links,
+                                 void* stream) {
+    if (int r = check_aov_centre_args(s, cam, w, h, max_links, d_albedo, d_normal_depth)) return r;
+    return render_aovs_centre(s, cam, w, h, max_links, d_albedo, d_normal_depth, d_links, (hipStream_t)stream);
+}
+
+int pt_render_aovs_centre(pt_scene* s, const pt_camera* cam, int w, int h, int max_links, float* out_albedo, float* out_normal_depth,
+                          float* out_links) {
+    if (int r = check_aov_centre_args(s, cam, w, h, max_links, out_albedo, out_normal_depth)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4), lbytes = (size_t)w * h * sizeof(float);
+    if (int r = s->aovOut.ensure(2 * bytes + lbytes)) return r;
+    char* d = (char*)s->aovOut.p;
+    if (int r = render_aovs_centre(s, cam, w, h, max_links, d, d + bytes, out_links ? d + 2 * bytes : nullptr, nullptr)) return r;
     HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
     if (out_links) HIP_OK(hipMemcpy(out_links, d + 2 * bytes, lbytes, hipMemcpyDeviceToHost));
@@ -1759,6 +1804,17 @@ int pt_probe_camera_rays(const pt_camera* cam, uint64_t seed, int n, const int32
     SCRATCH(dout, float, (size_t)n * 24, nullptr);
     HIP_OK(launch_probe_rng(dj, seed, n, dsub, 0, dst, du, df, nullptr));
     HIP_OK(launch_probe_camera(dst, cam_to_kernel(*cam), n, dxy, dout, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(outRays6, dout, (size_t)n * 24, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pt_probe_centre_rays(const pt_camera* cam, int n, const int32_t* xy, float* outRays6) {
+    if (!cam || n <= 0 || !xy || !outRays6) return fail(-1, "pt_probe_centre_rays: bad arguments");
+    Scratch sc;
+    SCRATCH(dxy, int, (size_t)n * 8, xy);
+    SCRATCH(dout, float, (size_t)n * 24, nullptr);
+    HIP_OK(launch_probe_centre(cam_to_kernel(*cam), n, dxy, dout, nullptr));
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(outRays6, dout, (size_t)n * 24, hipMemcpyDeviceToHost));
     return 0;

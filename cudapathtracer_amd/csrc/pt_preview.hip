@@ -13,6 +13,9 @@
 //                       With converge on (pt_preview_set_converge) a frame whose camera rests selects the tiles that still need
 //                       samples from the history, renders moments on that list alone and carries the other tiles' history forward.
 //                       With a guide chain (pt_preview_set_guide_chain) every feature pass of a frame is pt_render_aovs_chain_device.
+//                       With centre guides (pt_preview_set_guide_centre) every feature pass is pt_render_aovs_centre_device, the
+//                       low-res guide of a scaled frame is pt_guide_subsample_device of the display guide, and a frame whose camera
+//                       rests reuses the previous frame's guide: the guide has no seed, so nothing in it could have changed.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -123,6 +126,10 @@ struct pt_preview {
     char *ws, *filt, *mean, *rgba8;       // the filters' workspace, the filtered frame, the displayed mean and its bytes
     int scale;                            // render scale of the next frame; > 1 uses the buffers below (their own allocations)
     int guideChain;                       // max_links of the feature passes; 0: the first-hit pass (pt_preview_set_guide_chain)
+    int guideCentre;                      // 1: the feature passes trace pixel centres (pt_preview_set_guide_centre)
+    int curG;                             // the half of N that holds the last good frame's guide: cur's, until a frame reuses the guide
+    bool guideFresh;                      // A and N[curG] are the guide of prevCam (no later frame has written A and then failed)
+    int guidePasses, framePasses;         // feature-pass launches of all good frames / of the frame in flight (committed with the flip)
     char* lo;                             // four low-res float4 buffers of loCap pixels each: S, Q, albedo, guide
     size_t loCap;
     char* curEV;                          // w*h float4: pt_upsample's output
@@ -293,6 +300,19 @@ int pt_preview_set_guide_chain(pt_preview* p, int max_links) {
 
 int pt_preview_guide_chain(pt_preview* p) { return p ? p->guideChain : pv_fail(-1, "pt_preview_guide_chain: null session"); }
 
+int pt_preview_set_guide_centre(pt_preview* p, int on) {
+    if (on != 0 && on != 1) return pv_fail(-1, "pt_preview_set_guide_centre: on %d must be 0 or 1", on);
+    if (!p) return pv_fail(-1, "pt_preview_set_guide_centre: null session");
+    // jittered and centre guides do not validate against each other: the next frame is a first frame
+    if (on != p->guideCentre) p->haveHist = p->haveFrame = p->haveTiles = false;
+    p->guideCentre = on;
+    return 0;
+}
+
+int pt_preview_guide_centre(pt_preview* p) { return p ? p->guideCentre : pv_fail(-1, "pt_preview_guide_centre: null session"); }
+
+int pt_preview_guide_passes(pt_preview* p) { return p ? p->guidePasses : pv_fail(-1, "pt_preview_guide_passes: null session"); }
+
 int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
     if (!p) return pv_fail(-1, "pt_preview_set_converge: null session");
     if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
@@ -329,15 +349,18 @@ int pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live) {
     return 0;
 }
 
-// A feature pass of a frame: the first-hit pass, or the chain pass when the session has a guide chain.
+// A feature pass of a frame: the first-hit pass, or the chain pass when the session has a guide chain; with centre guides the
+// centre pass of either kind, which has no aov_spp and no seed.
 static int preview_aovs(pt_preview* p, const pt_camera* cam, int w, int h, uint64_t seed, void* dA, void* dN) {
+    p->framePasses++;
+    if (p->guideCentre) return pt_render_aovs_centre_device(p->scene, cam, w, h, p->guideChain, dA, dN, nullptr, p->stream);
     if (p->guideChain > 0) return pt_render_aovs_chain_device(p->scene, cam, w, h, p->P.aov_spp, p->guideChain, seed, dA, dN, nullptr, p->stream);
     return pt_render_aovs_device(p->scene, cam, w, h, p->P.aov_spp, seed, dA, dN, p->stream);
 }
 
 // A converging frame (the camera rests, a history exists, scale 1): the same five events around select + read-back + moments on
 // the live list | the whole feature pass | the accumulation with the live map | filter | resolve.
-static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
+static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt, int gn, bool reuse) {
     const pt_preview_params& P = p->P;
     const int w = p->w, h = p->h, T = ((w + 7) / 8) * ((h + 7) / 8), nt = p->curT ^ 1;
     hipStream_t st = p->stream;
@@ -352,15 +375,16 @@ static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t
                                                    count, p->S, p->Q, st))
             return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[nxt])) return r;
+    if (!reuse)
+        if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
-    if (int r = pt_temporal_accumulate_live_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt], p->N[p->cur], p->H[p->cur],
+    if (int r = pt_temporal_accumulate_live_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], p->N[p->curG], p->H[p->cur],
                                                    p->L[p->cur], p->tLive[nt], &P.temporal_params, p->H[nxt], p->L[nxt], st))
         return r;
     PV_HIP_OK(hipEventRecord(p->ev[3], st));
     pt_denoise_var_params F = P.filter_params;
     if (!P.filter) F.iterations = 0;
-    if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[nxt], &F, p->ws, p->filt, st)) return r;
+    if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[5], st));
@@ -369,8 +393,8 @@ static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t
 }
 
 // A frame at render scale s > 1: the same five events around low-res moments | both feature passes | upsample + accumulate |
-// filter | resolve.
-static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
+// filter | resolve. With centre guides the feature stage is the display pass (none when the guide is reused) and its subsample.
+static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt, int gn, bool reuse) {
     const pt_preview_params& P = p->P;
     const int w = p->w, h = p->h, s = p->scale, wl = w / s, hl = h / s;
     hipStream_t st = p->stream;
@@ -383,14 +407,21 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
     PV_HIP_OK(hipEventRecord(p->ev[0], st));
     if (int r = pt_render_moments_device(p->scene, &lowCam, wl, hl, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, S, Q, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (int r = preview_aovs(p, &lowCam, wl, hl, seed, Al, Nl)) return r;
-    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[nxt])) return r;
+    if (p->guideCentre) {
+        if (!reuse)
+            if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
+        // (also when the guide is reused: the scale may have changed since, and the copy is w * h / s^2 pixels)
+        if (int r = pt_guide_subsample_device(w, h, s, p->A, p->N[gn], Al, Nl, st)) return r;
+    } else {
+        if (int r = preview_aovs(p, &lowCam, wl, hl, seed, Al, Nl)) return r;
+        if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
+    }
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
-    if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[nxt], nullptr, p->curEV, st)) return r;
+    if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[gn], nullptr, p->curEV, st)) return r;
     const void* shown = p->curEV;         // the (e, V) buffer the filter reads
     if (P.temporal) {
         const bool hist = p->haveHist;
-        if (int r = pt_temporal_accumulate_cur_device(w, h, cam, hist ? &p->prevCam : nullptr, p->curEV, p->N[nxt], hist ? p->N[p->cur] : nullptr,
+        if (int r = pt_temporal_accumulate_cur_device(w, h, cam, hist ? &p->prevCam : nullptr, p->curEV, p->N[gn], hist ? p->N[p->curG] : nullptr,
                                                       hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt],
                                                       p->L[nxt], st))
             return r;
@@ -399,7 +430,7 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
     PV_HIP_OK(hipEventRecord(p->ev[3], st));
     pt_denoise_var_params F = P.filter_params;
     if (!P.filter) F.iterations = 0;
-    if (int r = pt_denoise_hist_device(w, h, shown, p->A, p->N[nxt], &F, p->ws, p->filt, st)) return r;
+    if (int r = pt_denoise_hist_device(w, h, shown, p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[5], st));
@@ -407,8 +438,9 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
 }
 
 // The five stages of a frame, enqueued on the session's stream with an event after each; the first error ends it. nxt: the half of
-// the ping-pong pairs this frame writes.
-static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt) {
+// the history pair this frame writes, gn: the half of the guide pair it writes, or, when it reuses the guide (centre guides, resting
+// camera), the half it reads as this frame's guide and the previous frame's at once.
+static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt, int gn, bool reuse) {
     const pt_preview_params& P = p->P;
     const int w = p->w, h = p->h;
     hipStream_t st = p->stream;
@@ -416,25 +448,26 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
     // (the first stage checks its arguments, the camera's size among them, before it enqueues anything)
     if (int r = pt_render_moments_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->S, p->Q, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[nxt])) return r;
+    if (!reuse)
+        if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
     const void* shown = p->S;             // what the resolve divides, and by what
     int shownSpp = P.spp;
     if (P.temporal) {
         const bool hist = p->haveHist;
-        if (int r = pt_temporal_accumulate_device(w, h, cam, hist ? &p->prevCam : nullptr, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt],
-                                                  hist ? p->N[p->cur] : nullptr, hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr,
+        if (int r = pt_temporal_accumulate_device(w, h, cam, hist ? &p->prevCam : nullptr, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn],
+                                                  hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr,
                                                   &P.temporal_params, p->H[nxt], p->L[nxt], st))
             return r;
         PV_HIP_OK(hipEventRecord(p->ev[3], st));
         pt_denoise_var_params F = P.filter_params;
         if (!P.filter) F.iterations = 0;  // no iteration: the history's mean a e, pass-through pixels as they are
-        if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[nxt], &F, p->ws, p->filt, st)) return r;
+        if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
         shown = p->filt; shownSpp = 1;
     } else {
         PV_HIP_OK(hipEventRecord(p->ev[3], st));
         if (P.filter) {
-            if (int r = pt_denoise_var_device(w, h, p->S, p->Q, P.spp, P.batches, p->A, p->N[nxt], &P.filter_params, p->ws, p->filt, st)) return r;
+            if (int r = pt_denoise_var_device(w, h, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], &P.filter_params, p->ws, p->filt, st)) return r;
             shown = p->filt;
         }
     }
@@ -449,9 +482,15 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     if (!cam) return pv_fail(-1, "pt_preview_frame: null camera");
     const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
     p->frameLive = ((p->w + 7) / 8) * ((p->h + 7) / 8); p->frameConverged = false;
-    const bool rests = p->converge && p->P.temporal && p->scale == 1 && p->haveHist && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
-    const int r = rests ? preview_stages_converge(p, cam, seed, nxt)
-                        : (p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt) : preview_stages(p, cam, seed, nxt));
+    const bool same = p->haveHist && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
+    const bool rests = p->converge && p->P.temporal && p->scale == 1 && same;
+    // centre guides, the camera of the last good frame, and that frame's guide still in place: no feature pass, no guide flip
+    const bool reuse = p->guideCentre && same && p->guideFresh;
+    const int gn = reuse ? p->curG : (p->P.temporal ? p->curG ^ 1 : 0);
+    if (!reuse) p->guideFresh = false;                     // (the feature pass writes A, of which there is one)
+    p->framePasses = 0;
+    const int r = rests ? preview_stages_converge(p, cam, seed, nxt, gn, reuse)
+                        : (p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt, gn, reuse) : preview_stages(p, cam, seed, nxt, gn, reuse));
     const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
     if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
     if (e != hipSuccess) return pv_fail(-2, "pt_preview_frame: the stream failed to synchronise");
@@ -459,6 +498,9 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     for (int i = 0; i < 5; i++) PV_HIP_OK(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
     PV_HIP_OK(hipEventElapsedTime(&total, p->ev[0], p->ev[5]));
     p->cur = nxt;
+    p->curG = gn;
+    p->guideFresh = true;
+    p->guidePasses += p->framePasses;
     p->haveHist = p->P.temporal != 0;
     p->haveFrame = true;
     p->prevCam = *cam;

@@ -8,6 +8,9 @@
 //                     each of the four low-res buffers, a few lines. Each tap's working pixel comes from S and Q again
 //                     (dn_var_pixel, shared with denoise_var_prepare_kernel): no prepare pass, no workspace. Plain cached float4
 //                     loads, no LDS.
+//   guide_subsample_kernel   the low-res guide of CENTRE feature buffers (pt_guide_subsample): out[Y][X] = in[sY][sX] for both buffers,
+//                     one thread per low-res pixel. A strided copy, because the centre ray of low-res pixel (X, Y) is the centre ray
+//                     of display pixel (sX, sY) bit for bit.
 // pt_camera_scaled lives here as well: the low-res camera of a scaled frame.
 #include <cmath>
 #include <cstdio>
@@ -68,6 +71,16 @@ __global__ void __launch_bounds__(256) upsample_kernel(int w, int h, int s, cons
     else out[p] = useE;
 }
 
+__global__ void __launch_bounds__(256) guide_subsample_kernel(int w, int wl, int hl, int s, const float4* __restrict__ albedo,
+                                                              const float4* __restrict__ nd, float4* __restrict__ albedoLo,
+                                                              float4* __restrict__ ndLo) {
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);      // a wave: 64 pixels of one row
+    if (X >= wl || Y >= hl) return;
+    const size_t q = (size_t)Y * wl + X, p = (size_t)(Y * s) * w + (size_t)X * s;
+    albedoLo[q] = albedo[p];
+    ndLo[q] = nd[p];
+}
+
 static int up_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0) {
     char buf[256];
     snprintf(buf, sizeof(buf), fmt, a, b, c);
@@ -111,6 +124,27 @@ static int upsample_launch(int w, int h, int s, const float4* sumLo, const float
                            const float4* ndLo, const float4* albedo, const float4* nd, const pt_upsample_params& P, float4* out, hipStream_t stream) {
     hipLaunchKernelGGL(upsample_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, stream, w, h, s, sumLo, sqLo, (float)spp, (float)batches,
                        albedoLo, ndLo, albedo, nd, P.sigma_normal, P.sigma_depth, out);
+    UP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int check_subsample_args(int w, int h, int s, const void* albedo, const void* nd, const void* outA, const void* outN) {
+    if (w <= 0 || h <= 0) return up_fail(-1, "pt_guide_subsample: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return up_fail(-1, "pt_guide_subsample: image of %d x %d pixels is too large", w, h);
+    if (s < 2 || s > 8) return up_fail(-1, "pt_guide_subsample: scale %d must be 2..8", s);
+    if (w % s != 0 || h % s != 0) return up_fail(-1, "pt_guide_subsample: scale %d must divide the image size %d x %d", s, w, h);
+    if (!albedo || !nd) return up_fail(-1, "pt_guide_subsample: null buffer");
+    if (!outA || !outN) return up_fail(-1, "pt_guide_subsample: null output");
+    const size_t full = (size_t)w * h * 16, lo = (size_t)(w / s) * (h / s) * 16;
+    if (overlaps(outA, lo, albedo, full) || overlaps(outA, lo, nd, full) || overlaps(outN, lo, albedo, full) || overlaps(outN, lo, nd, full) ||
+        overlaps(outA, lo, outN, lo))
+        return up_fail(-1, "pt_guide_subsample: the outputs must not alias the inputs or each other");
+    return 0;
+}
+
+static int subsample_launch(int w, int h, int s, const float4* albedo, const float4* nd, float4* outA, float4* outN, hipStream_t stream) {
+    const int wl = w / s, hl = h / s;
+    hipLaunchKernelGGL(guide_subsample_kernel, dim3((wl + 63) / 64, (hl + 3) / 4), dim3(256), 0, stream, w, wl, hl, s, albedo, nd, outA, outN);
     UP_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -173,6 +207,33 @@ int pt_upsample(int w, int h, int scale, const float* rgba_sum_lo, const float* 
                                     (const float4*)dA, (const float4*)dN, P, (float4*)dO, nullptr)) == 0) {
         e = hipMemcpy(out_cur, dO, full, hipMemcpyDeviceToHost);
         if (e != hipSuccess) r = up_fail(-2, "pt_upsample: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+int pt_guide_subsample_device(int w, int h, int scale, const void* d_albedo, const void* d_normal_depth, void* d_out_albedo_lo,
+                              void* d_out_normal_depth_lo, void* stream) {
+    if (int r = check_subsample_args(w, h, scale, d_albedo, d_normal_depth, d_out_albedo_lo, d_out_normal_depth_lo)) return r;
+    return subsample_launch(w, h, scale, (const float4*)d_albedo, (const float4*)d_normal_depth, (float4*)d_out_albedo_lo,
+                            (float4*)d_out_normal_depth_lo, (hipStream_t)stream);
+}
+
+int pt_guide_subsample(int w, int h, int scale, const float* albedo, const float* normal_depth, float* out_albedo_lo, float* out_normal_depth_lo) {
+    if (int r = check_subsample_args(w, h, scale, albedo, normal_depth, out_albedo_lo, out_normal_depth_lo)) return r;
+    const size_t full = (size_t)w * h * 16, lo = (size_t)(w / scale) * (h / scale) * 16;
+    char* d = nullptr;
+    UP_HIP_OK(hipMalloc(&d, 2 * full + 2 * lo));
+    char* dA = d; char* dN = dA + full; char* dAl = dN + full; char* dNl = dAl + lo;
+    hipError_t e = hipMemcpy(dA, albedo, full, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, full, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = up_fail(-2, "pt_guide_subsample: upload failed");
+    } else if ((r = subsample_launch(w, h, scale, (const float4*)dA, (const float4*)dN, (float4*)dAl, (float4*)dNl, nullptr)) == 0) {
+        e = hipMemcpy(out_albedo_lo, dAl, lo, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_normal_depth_lo, dNl, lo, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = up_fail(-2, "pt_guide_subsample: download failed");
     }
     (void)hipFree(d);
     return r;

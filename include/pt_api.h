@@ -335,6 +335,25 @@ int pt_render_aovs_chain(pt_scene* scene, const pt_camera* camera, int w, int h,
 int pt_render_aovs_chain_device(pt_scene* scene, const pt_camera* camera, int w, int h, int aov_spp, int max_links, uint64_t seed,
                                 void* d_albedo, void* d_normal_depth, void* d_links /* may be NULL */, void* stream);
 
+/* Feature buffers through PIXEL CENTRES: one ray per pixel that no random draw reaches, so the pass has no aov_spp and no seed and
+ * seeds no stream. cam0 is *camera with antiAliasJitterDist = 0 and aperture = 0, everything else unchanged (focalDist included);
+ * the centre ray of pixel (x, y) is camera_ray(cam0, x, y). In f32, every operation rounded once in the order written, nothing
+ * fused:
+ *   u = (2 ((float)x / (float)w) - 1) aspect fovScale, aspect = (float)w / (float)h;  v = (2 ((float)y / (float)h) - 1) fovScale;
+ *   focal = origin + right (u focalDist) + up (v focalDist) + forward focalDist;  o = origin + 0 (a -0 component becomes +0, as
+ *   camera_ray's lens sum makes it);  d = normalize(focal - o).
+ * The buffers are bit-identical, in all eight floats and in links, to pt_render_aovs_chain(scene, &cam0, w, h, aov_spp = 1,
+ * max_links, any seed, ...), so for max_links = 0 to pt_render_aovs(scene, &cam0, w, h, 1, any seed, ...) as well: layout, closest
+ * hit (max_t 999999), link rule, direction arithmetic, fallback, "no hit is all zeros" and coverage (0 or 1) are those functions'.
+ * The antiAliasJitterDist and aperture of *camera play no part. Because the ray depends on the pixel only through x / w and y / h,
+ * the centre ray of pixel (X, Y) of pt_camera_scaled(camera, s) IS the centre ray of pixel (sX, sY) of camera: see
+ * pt_guide_subsample. Like the other feature passes this one touches no RNG state, accumulator or counter of the scene. Arguments
+ * are checked before any HIP call (those of pt_render_aovs, and max_links in 0..16: -1 with a message). */
+int pt_render_aovs_centre(pt_scene* scene, const pt_camera* camera, int w, int h, int max_links,
+                          float* out_albedo, float* out_normal_depth, float* out_links /* w*h floats, may be NULL */);
+int pt_render_aovs_centre_device(pt_scene* scene, const pt_camera* camera, int w, int h, int max_links,
+                                 void* d_albedo, void* d_normal_depth, void* d_links /* may be NULL */, void* stream);
+
 /* Edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on albedo-demodulated colour, guided by the buffers
  * above. The contract, per pixel p (all buffers w*h float4):
  *   m_p = S_p / spp. p PASSES THROUGH (output = S_p bit for bit, all four channels) if its coverage is 0 or any of m_p.rgb
@@ -576,6 +595,17 @@ int pt_upsample_device(int w, int h, int scale, const void* d_rgba_sum_lo, const
                        const void* d_albedo_lo, const void* d_normal_depth_lo, const void* d_albedo, const void* d_normal_depth,
                        const pt_upsample_params* params, void* d_out_cur, void* stream);                         /* async */
 
+/* The low-res guide of CENTRE feature buffers (pt_render_aovs_centre) without a second trace: out_lo[Y][X] = in[sY][sX], all four
+ * floats, for both buffers; in is w x h float4, out (w / s) x (h / s). For a centre ray (float)(sX) / (float)(sW) and
+ * (float)X / (float)W round the same rational and the aspect is the same number, so the result equals
+ * pt_render_aovs_centre(pt_camera_scaled(camera, s)) bit for bit. It is NOT the low-res guide of jittered buffers. Arguments are
+ * checked before any HIP call: image size, 2 <= scale <= 8 dividing w and h, NULL pointers, and no output may overlap an input or
+ * the other output. Host and device form are bit-identical; the device form is asynchronous on `stream`. */
+int pt_guide_subsample(int w, int h, int scale, const float* albedo, const float* normal_depth, float* out_albedo_lo,
+                       float* out_normal_depth_lo);                                                              /* host, blocking */
+int pt_guide_subsample_device(int w, int h, int scale, const void* d_albedo, const void* d_normal_depth, void* d_out_albedo_lo,
+                              void* d_out_normal_depth_lo, void* stream);                                        /* async */
+
 /* pt_temporal_accumulate with step 1 replaced: this frame's working pixel (e_cur, V_cur) is read from cur (w*h float4, as
  * pt_upsample writes it) instead of derived from S, Q, spp, batches and albedo. A pixel with !(cur.w >= 0) passes through: it
  * writes (cur.rgb, -1) and length 0. Steps 2-5, the identity path, the aliasing rule and the checks of the size, the cameras,
@@ -652,7 +682,22 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  * pt_render_aovs_chain_device(max_links, links NULL) with the same camera, aov_spp and seed in place of pt_render_aovs_device, so
  * the frames equal that chain of host calls. The value may change between frames; a call that CHANGES it resets the session as
  * pt_preview_reset does, because guides from before and after the change do not validate against each other (a call with the
- * current value changes nothing). -1 on a NULL session or a value outside 0..16, the session unchanged. */
+ * current value changes nothing). -1 on a NULL session or a value outside 0..16, the session unchanged.
+ *
+ * CENTRE GUIDES. pt_preview_set_guide_centre(p, on): 0 (the default) is the frames above, bit for bit. With 1:
+ *   - every feature pass is pt_render_aovs_centre_device(display camera, max_links = the guide chain's value, links NULL); aov_spp
+ *     and the seed play no part in the guide;
+ *   - at a render scale above 1 the low-res guide is pt_guide_subsample_device of the display guide: no low-res trace is launched;
+ *   - a frame whose camera's 112 bytes equal the previous good frame's, while a history exists, launches NO feature pass
+ *     (converging frames included): the previous good frame's guide is this frame's guide and its previous guide at once. The
+ *     stages only read it, and the guide half of the ping-pong does not flip (the history half does). At a scale above 1 the
+ *     subsample still runs. If a frame failed in between, the display guide is traced again: same camera, same bits.
+ * So a frame equals, bit for bit, the chain of host calls above with pt_render_aovs_centre as the feature pass, pt_guide_subsample
+ * for the low-res guide, and the previous guide passed as both guides on such a resting frame. A call that CHANGES the value
+ * resets the session as pt_preview_reset does (a call with the current value changes nothing); -1 on a NULL session or a value
+ * other than 0 or 1, the session unchanged. The failed-frame rule is unchanged. aov_ms covers the trace and the subsample and is
+ * about 0 on a frame that reuses its guide. pt_preview_guide_passes: the feature-pass launches of all good frames since create
+ * (with or without centre guides; a failed frame's are not counted, a subsample is none). */
 typedef struct pt_preview pt_preview;
 typedef struct pt_preview_params {
     int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
@@ -676,6 +721,9 @@ int  pt_preview_set_scale(pt_preview* p, int scale);                       /* 1.
 int  pt_preview_scale(pt_preview* p);                                      /* the current scale; -1 on a NULL session */
 int  pt_preview_set_guide_chain(pt_preview* p, int max_links);             /* 0..16: the feature passes of the frames that follow */
 int  pt_preview_guide_chain(pt_preview* p);                                /* the current value; -1 on a NULL session */
+int  pt_preview_set_guide_centre(pt_preview* p, int on);                   /* 0 or 1: centre guides for the frames that follow */
+int  pt_preview_guide_centre(pt_preview* p);                               /* the current value; -1 on a NULL session */
+int  pt_preview_guide_passes(pt_preview* p);                               /* feature-pass launches of the good frames; -1 on NULL */
 int  pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len);
 const void* pt_preview_device_rgba8(pt_preview* p);                        /* w*h*4 bytes */
 const void* pt_preview_device_mean(pt_preview* p);                         /* w*h float4 */
@@ -776,6 +824,8 @@ int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* 
  * for the range guard). first_bad (may be NULL): the lowest differing bit pattern, 0xffffffff if none. ~0.1 s. */
 int pt_probe_rcp_exhaustive(unsigned long long* out3, uint32_t* first_bad);
 int pt_probe_camera_rays(const pt_camera* camera, uint64_t seed, int n, const int32_t* xy, float* out_rays6);
+/* The centre rays of pt_render_aovs_centre for n pixels xy = (x0, y0, x1, y1, ...): o.xyz, d.xyz per ray. No seed: none is read. */
+int pt_probe_centre_rays(const pt_camera* camera, int n, const int32_t* xy, float* out_rays6);
 /* rays: n x 6 floats. out_i: n x 4 (valid, triIDX, materialID, backface);
  * out_f: n x 12 (t,u,v, point xyz, normal xyz, uv xy, 0); counters: summed over the n rays. */
 int pt_probe_trace_closest(pt_scene* scene, int n, const float* rays6, int32_t* out_i, float* out_f, pt_counters* counters);

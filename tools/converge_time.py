@@ -1,6 +1,6 @@
 """What a resting camera costs with and without converged tiles: two pt_preview sessions side by side at 1920x1080.
 
-    python tools/converge_time.py [--w 1920 --h 1080 --frames 64 --scene cornell --ref-spp 1024 --threshold T --min-history N]
+    python tools/converge_time.py [--w 1920 --h 1080 --frames 64 --scene cornell --ref-spp 1024 --threshold T --min-history N --centre]
 
 Both sessions render the same still camera (tests/temporal_seq.py's) with the session's defaults (4 spp in 2 batches, depth 8,
 MIS, 1 feature ray, temporal accumulation, the history filter, tone map) and the same seeds; one of them has
@@ -9,7 +9,8 @@ live share of the converging session, its stage times from the session's HIP eve
 both (host clock around a call that ends in a device synchronise). At the end one JSON line: the medians over the frames from
 min_history on, both sessions' MSE of the displayed mean against a --ref-spp render with another seed (over the pixels that are
 finite in all three), and the share of pixel-samples that were not rendered. --scene blob renders the 82 k-triangle blob in the
-box, whose tree lives in HBM."""
+box, whose tree lives in HBM. --centre gives BOTH sessions centre guides (pt_preview_set_guide_centre): a resting camera then
+launches no feature pass at all, so compare aov_ms and the frame times with a run without the flag."""
 import argparse
 import json
 import os
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=1024)
     ap.add_argument("--threshold", type=float, default=None)
     ap.add_argument("--min-history", type=int, default=None)
+    ap.add_argument("--centre", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -48,6 +50,8 @@ def main():
     sc = api.Scene(api.HostScene(make(tempfile.mkdtemp(), width=w, height=h, spp=spp, max_depth=depth, name="cvt")["config"]))
     cam = Q.camera(api, 0, False, w, h)
     conv, plain = api.Preview(sc, w, h).set_converge(thr, mh), api.Preview(sc, w, h)
+    if a.centre:
+        conv.set_guide_centre(1); plain.set_guide_centre(1)
     keys = ("render_ms", "aov_ms", "accumulate_ms", "filter_ms", "resolve_ms", "total_ms")
     rows = []
     print("frame live_share " + " ".join(keys) + " | wall_ms converging, not converging")
@@ -68,7 +72,7 @@ def main():
     med = lambda v: round(sorted(v)[len(v) // 2], 4)
     tail = rows[min(mh, len(rows) - 1):]
     res = {"w": w, "h": h, "scene": a.scene, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth, "threshold": thr,
-           "min_history": mh, "ref_spp": a.ref_spp,
+           "min_history": mh, "ref_spp": a.ref_spp, "centre": int(a.centre), "guide_passes": conv.guide_passes,
            "live_share_last": round(rows[-1][0], 4), "live_share_mean": round(sum(r[0] for r in rows) / len(rows), 4),
            "pixel_samples_saved": round(1.0 - sum(r[0] for r in rows) / len(rows), 4),
            "converging_frame_ms_median": med([r[2][0] for r in tail]), "converging_frame_ms_last": round(rows[-1][2][0], 4),

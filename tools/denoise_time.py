@@ -1,7 +1,7 @@
 """Device time of the feature-buffer pass and of the denoiser at 1920x1080 (HIP events around each, after warm-up).
 
-    python tools/denoise_time.py [--w 1920 --h 1080 --reps 20 --aov-spp 1 --iterations 5 --scene cornell|mixed|blob --max-links 8]
-    python tools/denoise_time.py --resources          (no device needed: compiles pt_aov.hip and prints both kernels' registers)
+    python tools/denoise_time.py [--w 1920 --h 1080 --reps 20 --aov-spp 1 --iterations 5 --scene cornell|mixed|blob --max-links 8 --centre]
+    python tools/denoise_time.py --resources          (no device needed: compiles pt_aov.hip and prints its kernels' registers)
 
 Prints one JSON line: median / min milliseconds of pt_render_aovs_device, of pt_render_aovs_chain_device (`aov_chain`: the pass that
 follows mirrors and glass, --max-links links; on `cornell` no ray has a chain, `mixed` is bench.py --full's mixed Cornell box with
@@ -10,7 +10,8 @@ iterations; --iterations sets both, otherwise the variance-guided filter is time
 default), of the 16-spp depth-8 frame they post-process in one launch (the megakernel's device time, and the launcher's wall
 time), of the same frame as a moments render of 4 batches of 4 and of 2 batches of 8 (pt_render_moments_device: wall time, it
 blocks) and as pt_launch_progressive in 4 chunks (the same launches without the bookkeeping), and the device time of a 4-spp
-launch."""
+launch. --centre times only the four feature passes, in one run: pt_render_aovs_centre_device with max_links 0 (`aov_centre`) and
+with --max-links (`aov_centre_chain`) next to the jittered `aov` and `aov_chain`."""
 import argparse
 import json
 import os
@@ -26,7 +27,7 @@ sys.path.insert(0, ROOT)
 
 def aov_kernel_resources():
     """{kernel: {vgpr_count, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size (scratch bytes per lane),
-    group_segment_fixed_size (LDS bytes per workgroup)}} of pt_aov.hip's two kernels, from the code-object notes of a device-only
+    group_segment_fixed_size (LDS bytes per workgroup)}} of pt_aov.hip's feature-pass kernels (jittered and centre), from the code-object notes of a device-only
     compile with the Makefile's flags."""
     csrc = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
     with tempfile.TemporaryDirectory() as d:
@@ -54,6 +55,7 @@ def main():
     ap.add_argument("--scene", choices=("cornell", "mixed", "blob"), default="cornell")
     ap.add_argument("--max-links", type=int, default=8)
     ap.add_argument("--resources", action="store_true")
+    ap.add_argument("--centre", action="store_true")
     a = ap.parse_args()
     if a.resources:
         print(json.dumps(aov_kernel_resources()))
@@ -86,6 +88,14 @@ def main():
     def aov_chain():
         sc.render_aovs_chain_device(cam, w, h, a.max_links, alb.data_ptr(), nd.data_ptr(), lnk.data_ptr(), aov_spp=a.aov_spp, stream=stream)
 
+    alb_c = torch.empty(h, w, 4, device="cuda:0"); nd_c = torch.empty(h, w, 4, device="cuda:0")      # the centre passes' own buffers
+
+    def aov_centre():
+        sc.render_aovs_centre_device(cam, w, h, 0, alb_c.data_ptr(), nd_c.data_ptr(), stream=stream)
+
+    def aov_centre_chain():
+        sc.render_aovs_centre_device(cam, w, h, a.max_links, alb_c.data_ptr(), nd_c.data_ptr(), lnk.data_ptr(), stream=stream)
+
     iters = a.iterations or api.denoise_defaults()["iterations"]
     iters_var = a.iterations or api.denoise_var_defaults()["iterations"]
 
@@ -117,8 +127,8 @@ def main():
     colors.zero_()
     sc.launch_unidirectional(8, cam, 4, True, w, h, colors.data_ptr())
     res["frame_4spp_depth8_ms"] = round(sc.last_kernel_ms(), 3)       # what one batch of four costs on the device
-    for name, fn in (("frame_16spp_one_launch_wall", one_launch), ("frame_16spp_moments_4x4_wall", moments(4)),
-                     ("frame_16spp_moments_2x8_wall", moments(8)), ("frame_16spp_progressive_4x4_wall", progressive)):
+    for name, fn in () if a.centre else (("frame_16spp_one_launch_wall", one_launch), ("frame_16spp_moments_4x4_wall", moments(4)),
+                                         ("frame_16spp_moments_2x8_wall", moments(8)), ("frame_16spp_progressive_4x4_wall", progressive)):
         for _ in range(2):
             fn()
         torch.cuda.synchronize()
@@ -133,6 +143,8 @@ def main():
     timed = [("aov_chain", aov_chain), ("aov", aov), ("denoise", dn), ("denoise_var", lambda: dn_var(iters))]    # (aov last of the two: the filters read ITS buffers)
     if iters_var != iters:
         timed.append(("denoise_var_default", lambda: dn_var(iters_var)))
+    if a.centre:
+        timed = [("aov_centre_chain", aov_centre_chain), ("aov_chain", aov_chain), ("aov_centre", aov_centre), ("aov", aov)]
     for name, fn in timed:
         for _ in range(3):
             fn()

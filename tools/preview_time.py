@@ -1,6 +1,6 @@
 """Wall time of one preview frame at 1920x1080: the pt_preview session next to the chain of host calls it replaces, in one run.
 
-    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3 --scale 1 --scene cornell]
+    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3 --scale 1 --scene cornell --centre]
 
 Both render the same moving-camera sequence (tests/temporal_seq.py's camera) of the Cornell box with the session's defaults
 (4 spp in 2 batches, depth 8, MIS, 1 feature ray, temporal accumulation, the history filter, tone map). The host chain is
@@ -9,7 +9,9 @@ every buffer crosses PCIe, most of them twice. Prints one JSON line: the median 
 (host clock around calls that end in a device synchronise), the session's median stage times from its HIP events, the host
 chain's median time per call, and whether the last frames' bytes agree. --scale N runs both at render scale N (the beauty pass at
 1 / N of the size in each axis, upsampled by the guides: the host chain then goes through scaled_camera, upsample and
-TemporalHistory.push_cur); --scene blob renders the 82 k-triangle blob in the box, whose tree lives in HBM."""
+TemporalHistory.push_cur); --scene blob renders the 82 k-triangle blob in the box, whose tree lives in HBM. --centre leaves the host chain out and runs two sessions frame by frame instead, one with centre
+guides (pt_preview_set_guide_centre) and one without: `session_*` is the one without, `centre_*` the one with; after the moving
+sequence both rest for --frames more frames (`*_resting_*`: the centre session launches no feature pass then)."""
 import argparse
 import json
 import os
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scale", type=int, default=1)
     ap.add_argument("--scene", choices=("cornell", "blob"), default="cornell")
+    ap.add_argument("--centre", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -48,6 +51,27 @@ def main():
     cams = [Q.camera(api, t, True, w, h) for t in range(n)]
     med = lambda v: round(sorted(v)[len(v) // 2], 4)
 
+    keys = ("render_ms", "aov_ms", "accumulate_ms", "filter_ms", "resolve_ms", "total_ms")
+    if a.centre:
+        both = {"session": api.Preview(sc, w, h).set_scale(s), "centre": api.Preview(sc, w, h).set_scale(s).set_guide_centre(1)}
+        res = {"w": w, "h": h, "scene": a.scene, "scale": s, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth}
+        for phase, seq in (("", cams), ("_resting", [cams[-1]] * n)):
+            wall, stages = {k: [] for k in both}, {k: [] for k in both}
+            for t, cam in enumerate(seq):
+                for k, pv in both.items():
+                    t0 = time.perf_counter()
+                    pv.frame(cam, Q.SEED0 + t)
+                    wall[k].append(1e3 * (time.perf_counter() - t0))
+                    stages[k].append(pv.stats())
+            for k in both:
+                res[k + phase + "_frame_ms_median"] = med(wall[k][a.warmup:])
+                for key in keys:
+                    res[k + phase + "_" + key + "_median"] = med([st[key] for st in stages[k][a.warmup:]])
+        res["centre_guide_passes"] = both["centre"].guide_passes; res["session_guide_passes"] = both["session"].guide_passes
+        print(json.dumps(res))
+        for pv in both.values():
+            pv.close()
+        return
     pv = api.Preview(sc, w, h).set_scale(s)
     wall, stages = [], []
     for t in range(n):
