@@ -264,6 +264,14 @@ def lib():
     L.pt_preview_set_converge.argtypes = [vp, C.POINTER(ConvergeParams)]
     L.pt_preview_last_live.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pt_preview_read_tiles.argtypes = [vp, vp, vp]
+    L.pt_render_adaptive_moments.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, u64, C.POINTER(AdaptiveParams), vp, vp, vp, vp,
+                                             C.POINTER(AdaptiveStats)]
+    L.pt_render_adaptive_moments_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, u64, C.POINTER(AdaptiveParams), vp, vp, vp,
+                                                    vp, C.POINTER(AdaptiveStats), vp]
+    L.pt_probe_adaptive_moments.argtypes = [i32, i32, i32, i32, vp]
+    L.pt_denoise_var_tiles_workspace_bytes.restype = C.c_size_t; L.pt_denoise_var_tiles_workspace_bytes.argtypes = [i32, i32]
+    L.pt_denoise_var_tiles.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(DenoiseVarParams), vp]
+    L.pt_denoise_var_tiles_device.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(DenoiseVarParams), vp, vp, vp]
     _lib = L
     return L
 
@@ -598,6 +606,34 @@ class Scene:
                "pt_render_adaptive_device")
         return {f: getattr(st, f) for f, _ in AdaptiveStats._fields_}
 
+    def render_adaptive_moments(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, integrator=UNIDIRECTIONAL,
+                                use_mis=True, seed=SEED):
+        """pt_render_adaptive_moments: render_adaptive plus the sum of squared batch sums (a batch = a half-round of chunk_spp
+        samples; max_spp must be a multiple of 2 * chunk_spp). Returns (colors, sq, tile_spp, tile_err, stats): sq [h,w,4] float32 as
+        render_moments' Q at each tile's own count, the rest as render_adaptive. denoise_var_tiles(colors, sq, tile_spp, chunk_spp,
+        ...) reads them."""
+        ty, tx = (h + 7) // 8, (w + 7) // 8
+        col = np.zeros((h, w, 4), np.float32)
+        sq = np.zeros((h, w, 4), np.float32)
+        spp = np.zeros((ty, tx), np.int32)
+        err = np.zeros((ty, tx), np.float32)
+        st = AdaptiveStats()
+        p = adaptive_params(min_spp, max_spp, chunk_spp, threshold)
+        _check(lib().pt_render_adaptive_moments(self.h, C.byref(camera), w, h, max_depth, integrator, int(use_mis), seed, C.byref(p), _p(col),
+                                                _p(sq), _p(spp), _p(err), C.byref(st)), "pt_render_adaptive_moments")
+        return col, sq, spp, err, {f: getattr(st, f) for f, _ in AdaptiveStats._fields_}
+
+    def render_adaptive_moments_device(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, d_rgba_sum_ptr, d_sq_sum_ptr,
+                                       d_tile_spp_ptr, d_tile_err_ptr=None, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, stream=0):
+        """pt_render_adaptive_moments_device: the same into device buffers (two of w*h float4, one int32 / float32 per tile; the
+        error buffer may be None). Blocks; the work is enqueued on `stream`. Returns the stats dict."""
+        st = AdaptiveStats()
+        p = adaptive_params(min_spp, max_spp, chunk_spp, threshold)
+        _check(lib().pt_render_adaptive_moments_device(self.h, C.byref(camera), w, h, max_depth, integrator, int(use_mis), seed, C.byref(p),
+                                                       d_rgba_sum_ptr, d_sq_sum_ptr, d_tile_spp_ptr, d_tile_err_ptr or None, C.byref(st),
+                                                       stream or None), "pt_render_adaptive_moments_device")
+        return {f: getattr(st, f) for f, _ in AdaptiveStats._fields_}
+
     def render_moments(self, camera, w, h, spp, batch_spp, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED):
         """pt_render_moments: `spp` samples per pixel in spp / batch_spp batches. Returns (S, Q), both [h,w,4] float32: S the
         sum of the samples (render(spp) into zeros, bit for bit), Q per rgb channel the sum of the squared batch sums, Q.w
@@ -914,6 +950,39 @@ def denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albed
     p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
     _check(lib().pt_denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
                                        C.byref(p), d_workspace_ptr, d_out_ptr, stream or None), "pt_denoise_var_device")
+
+
+def denoise_var_tiles_workspace_bytes(w, h):
+    return int(lib().pt_denoise_var_tiles_workspace_bytes(w, h))
+
+
+def denoise_var_tiles(rgba_sum, sq_sum, tile_spp, batch_spp, albedo, normal_depth, iterations=None, sigma_var=None, sigma_normal=None,
+                      sigma_depth=None, out=None):
+    """pt_denoise_var_tiles (host, blocking): denoise_var on an adaptive frame. rgba_sum, sq_sum and tile_spp (int32
+    [ceil(h/8), ceil(w/8)]) are what Scene.render_adaptive_moments returned with chunk_spp = batch_spp; albedo and normal_depth come
+    from render_aovs*. Returns the filtered radiance sum in the units of rgba_sum: adaptive_mean(result, tile_spp) and
+    resolve(result, tile_spp=tile_spp) apply as to the raw frame. `out` may be rgba_sum itself."""
+    arrs = _f4_frames("denoise_var_tiles", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = arrs[0].shape[:2]
+    if not isinstance(tile_spp, np.ndarray) or tile_spp.dtype != np.int32 or tile_spp.shape != ((h + 7) // 8, (w + 7) // 8):
+        raise PtError("denoise_var_tiles: tile_spp must be an int32 [%d, %d] array for a %d x %d frame" % ((h + 7) // 8, (w + 7) // 8, w, h))
+    res = np.empty_like(arrs[0]) if out is None else out
+    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == arrs[0].shape and res.flags.c_contiguous):
+        raise PtError("denoise_var_tiles: out must be a C-contiguous float32 array of shape %s" % (arrs[0].shape,))
+    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_var_tiles(w, h, _p(arrs[0]), _p(arrs[1]), _p(np.ascontiguousarray(tile_spp)), int(batch_spp), _p(arrs[2]),
+                                      _p(arrs[3]), C.byref(p), _p(res)), "pt_denoise_var_tiles")
+    return res
+
+
+def denoise_var_tiles_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, d_tile_spp_ptr, batch_spp, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr,
+                             d_out_ptr, iterations=None, sigma_var=None, sigma_normal=None, sigma_depth=None, stream=0):
+    """pt_denoise_var_tiles_device: device buffers of w*h float4, the tile map (one int32 per tile, trusted) and a workspace of
+    denoise_var_tiles_workspace_bytes(w, h) bytes; asynchronous on `stream`. d_out_ptr may equal d_rgba_sum_ptr."""
+    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
+    _check(lib().pt_denoise_var_tiles_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, d_tile_spp_ptr, int(batch_spp), d_albedo_ptr,
+                                             d_normal_depth_ptr, C.byref(p), d_workspace_ptr, d_out_ptr, stream or None),
+           "pt_denoise_var_tiles_device")
 
 
 def temporal_defaults():
@@ -1441,6 +1510,13 @@ def probe_rng(subsequences, n_draws, seed=SEED):
     st = np.zeros((n, 6), np.uint32); u = np.zeros((n, max(n_draws, 1)), np.uint32); f = np.zeros((n, max(n_draws, 1)), np.float32)
     _check(lib().pt_probe_rng(seed, n, _p(sub), n_draws, _p(st), _p(u), _p(f)), "pt_probe_rng")
     return st, u[:, :n_draws], f[:, :n_draws]
+
+
+def probe_adaptive_moments(w, h, live, reps=20):
+    """pt_probe_adaptive_moments: the mean time in ms of render_adaptive_moments' bookkeeping pass on `live` tiles of a w x h frame."""
+    ms = C.c_float(0.0)
+    _check(lib().pt_probe_adaptive_moments(w, h, live, reps, C.byref(ms)), "pt_probe_adaptive_moments")
+    return float(ms.value)
 
 
 def probe_math(x):

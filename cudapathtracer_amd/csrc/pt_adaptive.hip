@@ -5,6 +5,8 @@
 //   adaptive_compact_kernel  the live list without the stopped tiles, in the same (ascending) order, and its length;
 //   adaptive_queue_save_kernel, after each launch: the tile queue's first 8 words, which the next launch's queue init resets —
 //                            the host checks both launches of a round from one read-back (pt_api.hip: render_adaptive).
+// pt_render_adaptive_moments adds, after each of a round's two launches,
+//   adaptive_moments_kernel  d = S - P, Q = Q + d d per rgb channel, P = S on the live tiles: pt_moments.hip's pass on a list.
 // The renders are the ordinary megakernels, launched on the list through the tile queue (pt_kernels.hip: queue_init_list_kernel).
 // S, M and H are tile-major over the whole frame ([tile][64] float4, lane = ly*8+lx), so one wave per live tile reads 1 KB
 // coalesced per buffer. These kernels run once per round: correct and cheap, not clever. Host side: pt_api.hip.
@@ -24,6 +26,23 @@ __global__ void __launch_bounds__(256) adaptive_snapshot_kernel(const int* __res
     if (i >= nList) return;
     const size_t o = (size_t)list[i] * 64 + lane;
     M[o] = S[o];
+}
+
+// One wave per live tile, lane = pixel: moments_update_kernel's arithmetic (pt_moments.hip) in its order (-ffp-contract=off: the
+// product is rounded before the add), on the tiles of the list. Q.w = the batches the tile has taken so far. `first`: the first
+// launch of round 0, which lists every tile and takes P = Q = 0 without reading them. Lanes outside the image carry zeros along.
+__global__ void __launch_bounds__(256) adaptive_moments_kernel(const int* __restrict__ list, int nList, const float4* __restrict__ S,
+                                                               float4* __restrict__ P, float4* __restrict__ Q, int first, float batches) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= nList) return;
+    const size_t o = (size_t)list[i] * 64 + lane;
+    const float4 s = S[o];
+    float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = p;
+    if (!first) { p = P[o]; q = Q[o]; }
+    const float dx = s.x - p.x, dy = s.y - p.y, dz = s.z - p.z;
+    q.x = q.x + dx * dx; q.y = q.y + dy * dy; q.z = q.z + dz * dz; q.w = batches;
+    P[o] = s;
+    Q[o] = q;
 }
 
 PT_DEV bool finite3(float x, float y, float z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
@@ -103,6 +122,12 @@ hipError_t launch_adaptive_iota(int n, int* list, hipStream_t stream) {
 hipError_t launch_adaptive_snapshot(const int* list, int nList, const float4* S, float4* M, hipStream_t stream) {
     if (nList <= 0) return hipSuccess;
     hipLaunchKernelGGL(adaptive_snapshot_kernel, dim3((nList + 3) / 4), dim3(256), 0, stream, list, nList, S, M);
+    return hipGetLastError();
+}
+hipError_t launch_adaptive_moments(const int* list, int nList, const float4* S, float4* P, float4* Q, bool first, int batches,
+                                   hipStream_t stream) {
+    if (nList <= 0) return hipSuccess;
+    hipLaunchKernelGGL(adaptive_moments_kernel, dim3((nList + 3) / 4), dim3(256), 0, stream, list, nList, S, P, Q, first ? 1 : 0, (float)batches);
     return hipGetLastError();
 }
 hipError_t launch_adaptive_error(const int* list, int nList, const float4* S, const float4* M, float4* H, int n, int w, int h, int tilesX,

@@ -64,6 +64,7 @@ struct pt_scene {
     DevBuf wfState, wfCtl, wfCtr, wfSpill;            // wavefront variant
     DevBuf aovSpill, aovOut;                          // pt_render_aovs: its own traversal spill area / host-form staging
     DevBuf adS, adM, adH, adList, adKeep, adCount, adOut, adSpp, adErr;   // pt_render_adaptive: sums, snapshot, half sums, live lists; host-form staging
+    DevBuf adP, adQ, adSq;                            // pt_render_adaptive_moments: previous sums, squared batch sums (tile-major); host-form staging
     DevBuf moS, moP, moQ, moOut;                      // pt_render_moments: sums, previous sums, squared batch sums (tile-major); host-form staging
     DevBuf moList;                                    // pt_render_moments_tiles, host form: the tile list on the device
     int variant = 0;                                  // 0 megakernel, 1 wavefront (pt_set_variant)
@@ -151,6 +152,7 @@ void pt_scene_destroy(pt_scene* s) {
     DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves, &s->wnodes, &s->qnodes, &s->leafBox, &s->mids,
                      &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
                      &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr,
+                     &s->adP, &s->adQ, &s->adSq,
                      &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -1126,6 +1128,7 @@ hipError_t launch_adaptive_error(const int* list, int nList, const float4* S, co
                                  int minSpp, float threshold, int32_t* tileSpp, float* tileErr, int32_t* keep, hipStream_t stream);
 hipError_t launch_adaptive_compact(const int* list, const int32_t* keep, int nList, int* out, int* outCount, hipStream_t stream);
 hipError_t launch_adaptive_queue_save(const int* q, int* save, hipStream_t stream);
+hipError_t launch_adaptive_moments(const int* list, int nList, const float4* S, float4* P, float4* Q, bool first, int batches, hipStream_t stream);
 }
 
 // What one round of pt_render_adaptive reads back: the new live count and the first 8 queue words after each of its two launches.
@@ -1133,8 +1136,9 @@ struct RoundWords { int count, pad[7]; int q[2][8]; };
 static_assert(sizeof(RoundWords) == 96, "pt_api.h states the read-back's size");
 
 // Argument checks of pt_render_adaptive[_device], all before the first HIP call: image size, params, NULL pointers, the scene.
+// moments: pt_render_adaptive_moments[_device], which also wants equal batches (after the params' own checks) and outSq.
 static int check_adaptive_args(pt_scene* s, const pt_camera* cam, int w, int h, int integrator, const pt_adaptive_params* p,
-                               const void* out, const void* tileSpp) {
+                               const void* out, const void* tileSpp, const void* outSq = nullptr, bool moments = false) {
     if (w <= 0 || h <= 0) return fail(-1, "pt_render_adaptive: image size %d x %d must be positive", w, h);
     if ((long long)w * h > 0x7fffffffll) return fail(-1, "pt_render_adaptive: image of %d x %d pixels is too large", w, h);
     if (!p) return fail(-1, "pt_render_adaptive: null params");
@@ -1142,10 +1146,13 @@ static int check_adaptive_args(pt_scene* s, const pt_camera* cam, int w, int h, 
     if (p->min_spp < 0 || p->min_spp > p->max_spp) return fail(-1, "pt_render_adaptive: min_spp %d must lie in 0..max_spp (%d)", p->min_spp, p->max_spp);
     if (p->chunk_spp < 1) return fail(-1, "pt_render_adaptive: chunk_spp %d must be positive", p->chunk_spp);
     if (!(p->threshold >= 0.0f)) return fail(-1, "pt_render_adaptive: threshold %g must be a number >= 0", (double)p->threshold);
+    if (moments && p->max_spp % (2 * p->chunk_spp) != 0)
+        return fail(-1, "pt_render_adaptive_moments: max_spp %d must be a multiple of 2 * chunk_spp (%d), so that every batch has chunk_spp samples",
+                    p->max_spp, 2 * p->chunk_spp);
     if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
         return fail(-3, "pt_render_adaptive: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", integrator);
     if (!cam) return fail(-1, "pt_render_adaptive: null camera");
-    if (!out || !tileSpp) return fail(-1, "pt_render_adaptive: null output buffer");
+    if (!out || !tileSpp || (moments && !outSq)) return fail(-1, "pt_render_adaptive: null output buffer");
     if (!s) return fail(-1, "pt_render_adaptive: null scene");
     if (s->variant != 0) return fail(-1, "pt_render_adaptive: the wavefront variant has no tile queue; select the megakernel (pt_set_variant 0)");
     int dev = -1;
@@ -1157,8 +1164,11 @@ static int check_adaptive_args(pt_scene* s, const pt_camera* cam, int w, int h, 
 // dSpp and dErr are device buffers. Once per round one read-back on `stream` brings the new live count and the queue words that
 // each of the round's two launches left (the second launch re-initialises the queue, so the first one's words are saved on the
 // device before it does): both launches are checked as queue_error checks a pt_render launch.
+// With dSq (pt_render_adaptive_moments: a device buffer, scan-line) every launch is followed by the moments pass on its list and
+// Q is untiled into dSq at the end; nothing else changes, so the other outputs are pt_render_adaptive's.
 static int render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int maxDepth, int integrator, int useMIS, uint64_t seed,
-                           const pt_adaptive_params& p, float4* dOut, int32_t* dSpp, float* dErr, pt_adaptive_stats* stats, hipStream_t stream) {
+                           const pt_adaptive_params& p, float4* dOut, int32_t* dSpp, float* dErr, pt_adaptive_stats* stats, hipStream_t stream,
+                           float4* dSq = nullptr) {
     TileSpan t;
     if (int r = resolve_tiles(w, h, nullptr, t)) return r;
     const int T = t.count;
@@ -1169,6 +1179,10 @@ static int render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int 
     if (int r = s->adList.ensure((size_t)2 * T * sizeof(int))) return r;
     if (int r = s->adKeep.ensure((size_t)T * sizeof(int32_t))) return r;
     if (int r = s->adCount.ensure(sizeof(RoundWords))) return r;
+    if (dSq) {
+        if (int r = s->adP.ensure(tileBytes)) return r;
+        if (int r = s->adQ.ensure(tileBytes)) return r;
+    }
     if (!dErr) {
         if (int r = s->adErr.ensure((size_t)T * sizeof(float))) return r;
         dErr = (float*)s->adErr.p;
@@ -1188,6 +1202,9 @@ static int render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int 
             if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, rounds > 0 || half > 0,
                                      lists[cur], live)) return r;
             HIP_OK(launch_adaptive_queue_save((const int*)s->queue.p, dw->q[half], stream));
+            if (dSq)                                                  // (every half-round renders chunk_spp samples: the entry point checked)
+                HIP_OK(launch_adaptive_moments(lists[cur], live, S, (float4*)s->adP.p, (float4*)s->adQ.p, rounds == 0 && half == 0,
+                                               2 * rounds + half + 1, stream));
             if (half == 0) HIP_OK(launch_adaptive_snapshot(lists[cur], live, S, (float4*)s->adM.p, stream));
         }
         n += 2 * c;
@@ -1204,6 +1221,7 @@ static int render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int 
         live = next; cur ^= 1; rounds++;
     }
     HIP_OK(launch_untile(w, h, t, S, dOut, stream));
+    if (dSq) HIP_OK(launch_untile(w, h, t, (const float4*)s->adQ.p, dSq, stream));
     if (stats) {
         std::vector<int32_t> spp(T);
         HIP_OK(hipMemcpyAsync(spp.data(), dSpp, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -1240,6 +1258,32 @@ int pt_render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int max_
     if (int r = render_adaptive(s, cam, w, h, max_depth, integrator, use_mis, seed, *params, (float4*)s->adOut.p, (int32_t*)s->adSpp.p,
                                 (float*)s->adErr.p, stats, nullptr)) return r;
     HIP_OK(hipMemcpy(out_rgba_sum, s->adOut.p, px * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_tile_spp, s->adSpp.p, T * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_tile_err) HIP_OK(hipMemcpy(out_tile_err, s->adErr.p, T * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pt_render_adaptive_moments_device(pt_scene* s, const pt_camera* cam, int w, int h, int max_depth, int integrator, int use_mis, uint64_t seed,
+                                      const pt_adaptive_params* params, void* d_rgba_sum, void* d_sq_sum, void* d_tile_spp, void* d_tile_err,
+                                      pt_adaptive_stats* stats, void* stream) {
+    if (int r = check_adaptive_args(s, cam, w, h, integrator, params, d_rgba_sum, d_tile_spp, d_sq_sum, true)) return r;
+    return render_adaptive(s, cam, w, h, max_depth, integrator, use_mis, seed, *params, (float4*)d_rgba_sum, (int32_t*)d_tile_spp,
+                           (float*)d_tile_err, stats, (hipStream_t)stream, (float4*)d_sq_sum);
+}
+
+int pt_render_adaptive_moments(pt_scene* s, const pt_camera* cam, int w, int h, int max_depth, int integrator, int use_mis, uint64_t seed,
+                               const pt_adaptive_params* params, float* out_rgba_sum, float* out_sq_sum, int32_t* out_tile_spp,
+                               float* out_tile_err, pt_adaptive_stats* stats) {
+    if (int r = check_adaptive_args(s, cam, w, h, integrator, params, out_rgba_sum, out_tile_spp, out_sq_sum, true)) return r;
+    const size_t px = (size_t)w * h, T = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    if (int r = s->adOut.ensure(px * sizeof(float4))) return r;
+    if (int r = s->adSq.ensure(px * sizeof(float4))) return r;
+    if (int r = s->adSpp.ensure(T * sizeof(int32_t))) return r;
+    if (int r = s->adErr.ensure(T * sizeof(float))) return r;
+    if (int r = render_adaptive(s, cam, w, h, max_depth, integrator, use_mis, seed, *params, (float4*)s->adOut.p, (int32_t*)s->adSpp.p,
+                                (float*)s->adErr.p, stats, nullptr, (float4*)s->adSq.p)) return r;
+    HIP_OK(hipMemcpy(out_rgba_sum, s->adOut.p, px * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_sq_sum, s->adSq.p, px * sizeof(float4), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out_tile_spp, s->adSpp.p, T * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (out_tile_err) HIP_OK(hipMemcpy(out_tile_err, s->adErr.p, T * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
@@ -1760,6 +1804,40 @@ int pt_probe_rng(uint64_t seed, int n, const uint32_t* subseq, int nDraws, uint3
     if (outState6) HIP_OK(hipMemcpy(outState6, dst, (size_t)n * 24, hipMemcpyDeviceToHost));
     if (outU32 && nDraws) HIP_OK(hipMemcpy(outU32, du, (size_t)n * nDraws * 4, hipMemcpyDeviceToHost));
     if (outUni && nDraws) HIP_OK(hipMemcpy(outUni, df, (size_t)n * nDraws * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The moments pass of pt_render_adaptive_moments alone, as a round runs it: `live` tiles (the first of the frame, ascending) of a
+// w x h frame's tile-major S, P and Q, one warm-up launch and then `reps` launches between two HIP events. *out_ms: their mean.
+int pt_probe_adaptive_moments(int w, int h, int live, int reps, float* out_ms) {
+    if (w <= 0 || h <= 0) return fail(-1, "pt_probe_adaptive_moments: image size %d x %d must be positive", w, h);
+    const long long T = (long long)((w + 7) / 8) * ((h + 7) / 8);
+    if (T * 64 > 0x7fffffffll) return fail(-1, "pt_probe_adaptive_moments: image of %d x %d pixels is too large", w, h);
+    if (live < 1 || live > T) return fail(-1, "pt_probe_adaptive_moments: live %d must lie in 1..%lld, the frame's tiles", live, T);
+    if (reps < 1) return fail(-1, "pt_probe_adaptive_moments: reps %d must be positive", reps);
+    if (!out_ms) return fail(-1, "pt_probe_adaptive_moments: null output");
+    Scratch sc;
+    const size_t tileBytes = (size_t)T * 64 * sizeof(float4);
+    SCRATCH(S, float4, tileBytes, nullptr);
+    SCRATCH(P, float4, tileBytes, nullptr);
+    SCRATCH(Q, float4, tileBytes, nullptr);
+    SCRATCH(list, int, (size_t)live * sizeof(int), nullptr);
+    HIP_OK(hipMemset(S, 0, tileBytes));
+    HIP_OK(launch_adaptive_iota(live, list, nullptr));
+    HIP_OK(launch_adaptive_moments(list, live, S, P, Q, true, 1, nullptr));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_OK(hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
+    for (int k = 0; k < reps && e == hipSuccess; k++) e = launch_adaptive_moments(list, live, S, P, Q, false, k + 2, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e != hipSuccess) return fail(-2, "pt_probe_adaptive_moments: %s", hipGetErrorString(e));
+    *out_ms = ms / (float)reps;
     return 0;
 }
 

@@ -8,7 +8,8 @@
 //   denoise_iter_kernel      one launch per step s = 2^i: the 5x5 B3-spline taps at stride s, weighted by colour, normal, depth
 //   denoise_finish_kernel    out = spp * a * e, or S itself for pass-through pixels
 //
-// pt_denoise_var's kernels (the variance-guided colour weight) follow pt_denoise's below and share its reduction and workspace layout.
+// pt_denoise_var's kernels (the variance-guided colour weight) follow pt_denoise's below and share its reduction and workspace layout;
+// pt_denoise_var_tiles' prepare and finish kernels (the sample count per 8x8 tile, an adaptive frame's map) follow those.
 //
 // Workspace (pt_denoise_workspace_bytes): e ping-pong (2 x w*h float4: rgb, w = 1 filtered / 0 pass-through), the normal-depth
 // guide (w*h float4: unit normal or 0, depth), the partial sums (one float2 per 256 pixels) and the result of the reduction.
@@ -241,6 +242,57 @@ __global__ void __launch_bounds__(kDnBlock) denoise_var_finish_kernel(int n, con
     out[i] = make_float4(spp * (demod_albedo(a.x) * ev.x), spp * (demod_albedo(a.y) * ev.y), spp * (demod_albedo(a.z) * ev.z), s.w);
 }
 
+// ---- pt_denoise_var_tiles: pt_denoise_var on an adaptive frame (include/pt_api.h) --------------------------------------------
+// spp and the batch count come per pixel from the frame's tile map, tile = (y / 8) * ceil(w / 8) + x / 8, as pt_resolve reads it;
+// denoise_reduce_kernel and denoise_var_iter_kernel run unchanged on the same workspace.
+//
+//   denoise_var_tiles_prepare_kernel   denoise_var_prepare_kernel with spp_p = map[tile], B_p = spp_p / batch_spp
+//   denoise_var_tiles_finish_kernel    denoise_var_finish_kernel with spp_p
+// A thread is a pixel of the scan-line frame, so the 64 lanes of a wave read at most 9 entries of the map (8 where w is a
+// multiple of 8): cached loads, 4 B against the pixel's 64 B. The map is trusted here: the host form checks it.
+__device__ inline int dn_tile_spp(const int32_t* __restrict__ tileSpp, int i, int w, int tilesX) {
+    const int y = i / w, x = i - y * w;
+    return tileSpp[(y >> 3) * tilesX + (x >> 3)];
+}
+
+__global__ void __launch_bounds__(kDnBlock) denoise_var_tiles_prepare_kernel(int n, int w, int tilesX, const float4* __restrict__ sum,
+                                                                             const float4* __restrict__ sq, const int32_t* __restrict__ tileSpp,
+                                                                             int batchSpp, const float4* __restrict__ albedo,
+                                                                             const float4* __restrict__ nd, float4* __restrict__ e,
+                                                                             float4* __restrict__ guide, float2* __restrict__ partials) {
+    __shared__ float sLum[kDnBlock], sCnt[kDnBlock];
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    float lum = 0.0f, cnt = 0.0f;
+    if (i < n) {
+        const int spp = dn_tile_spp(tileSpp, i, w, tilesX);
+        float4 m;
+        const float4 ev = dn_var_pixel(sum[i], sq[i], albedo[i], (float)spp, (float)(spp / batchSpp), m);
+        e[i] = ev;
+        guide[i] = dn_unit_guide(nd[i]);
+        if (ev.w >= 0.0f) { lum = 0.2126f * ev.x + 0.7152f * ev.y + 0.0722f * ev.z; cnt = 1.0f; }
+    }
+    sLum[threadIdx.x] = lum; sCnt[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int k = kDnBlock / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) { sLum[threadIdx.x] += sLum[threadIdx.x + k]; sCnt[threadIdx.x] += sCnt[threadIdx.x + k]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = make_float2(sLum[0], sCnt[0]);
+}
+
+__global__ void __launch_bounds__(kDnBlock) denoise_var_tiles_finish_kernel(int n, int w, int tilesX, const float4* sum,
+                                                                            const int32_t* __restrict__ tileSpp,
+                                                                            const float4* __restrict__ albedo, const float4* __restrict__ e,
+                                                                            float4* out) {
+    const int i = blockIdx.x * kDnBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 s = sum[i], ev = e[i];          // (out may alias sum: each thread reads its own pixel before it writes it)
+    if (ev.w < 0.0f) { out[i] = s; return; }
+    const float4 a = albedo[i];
+    const float spp = (float)dn_tile_spp(tileSpp, i, w, tilesX);
+    out[i] = make_float4(spp * (demod_albedo(a.x) * ev.x), spp * (demod_albedo(a.y) * ev.y), spp * (demod_albedo(a.z) * ev.z), s.w);
+}
+
 // ---- pt_denoise_hist: pt_denoise_var's filter on a history buffer of pt_temporal_accumulate (include/pt_api.h) -------------------
 // (e, V) come from `hist` instead of S and Q; denoise_reduce_kernel and denoise_var_iter_kernel run unchanged on the same workspace.
 //
@@ -368,6 +420,40 @@ static int denoise_var_launch(int w, int h, const float4* in, const float4* sq, 
         DN_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_var_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
+    DN_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// pt_denoise_var's checks that do not concern spp / batches, then batch_spp and the map's pointer.
+static int check_denoise_var_tiles_args(int w, int h, const void* in, const void* sq, const void* tileSpp, int batchSpp, const void* albedo,
+                                        const void* nd, const pt_denoise_var_params& P, const void* out) {
+    if (int r = check_denoise_var_args(w, h, in, sq, 2, 2, albedo, nd, P, out)) return r;
+    if (batchSpp < 1) return dn_fail(-1, "pt_denoise_var_tiles: batch_spp %d must be positive", batchSpp);
+    if (!tileSpp) return dn_fail(-1, "pt_denoise_var_tiles: null tile map");
+    return 0;
+}
+
+static int denoise_var_tiles_launch(int w, int h, const float4* in, const float4* sq, const int32_t* tileSpp, int batchSpp, const float4* albedo,
+                                    const float4* nd, const pt_denoise_var_params& P, char* ws, float4* out, hipStream_t stream) {
+    const DnLayout L = dn_layout(w, h);
+    float4* e[2] = {(float4*)(ws + L.e0), (float4*)(ws + L.e1)};
+    float4* guide = (float4*)(ws + L.guide);
+    float2* partials = (float2*)(ws + L.partials);
+    float4* lum = (float4*)(ws + L.lum);
+    const int n = (int)L.n, tilesX = (w + 7) / 8;
+    hipLaunchKernelGGL(denoise_var_tiles_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, w, tilesX, in, sq, tileSpp, batchSpp, albedo,
+                       nd, e[0], guide, partials);
+    DN_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
+    DN_HIP_OK(hipGetLastError());
+    const dim3 grid((w + 15) / 16, (h + 15) / 16);
+    for (int i = 0; i < P.iterations; i++) {
+        hipLaunchKernelGGL(denoise_var_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, P.sigma_var, P.sigma_normal, P.sigma_depth, lum,
+                           e[i & 1], guide, e[(i + 1) & 1]);
+        DN_HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(denoise_var_tiles_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, w, tilesX, in, tileSpp, albedo,
+                       e[P.iterations & 1], out);
     DN_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -506,6 +592,58 @@ int pt_denoise_var(int w, int h, const float* rgba_sum, const float* sq_sum, int
                                        (float4*)dIn, nullptr)) == 0) {
         e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_var: download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
+size_t pt_denoise_var_tiles_workspace_bytes(int w, int h) {
+    if (w <= 0 || h <= 0) return 0;
+    return dn_layout(w, h).total;
+}
+
+int pt_denoise_var_tiles_device(int w, int h, const void* d_rgba_sum, const void* d_sq_sum, const void* d_tile_spp, int batch_spp,
+                                const void* d_albedo, const void* d_normal_depth, const pt_denoise_var_params* params, void* d_workspace,
+                                void* d_out, void* stream) {
+    pt_denoise_var_params P;
+    if (params) P = *params; else pt_denoise_var_defaults(&P);
+    if (int r = check_denoise_var_tiles_args(w, h, d_rgba_sum, d_sq_sum, d_tile_spp, batch_spp, d_albedo, d_normal_depth, P, d_out)) return r;
+    if (!d_workspace) return pt_fail_(-1, "pt_denoise_var_tiles_device: null workspace");
+    return denoise_var_tiles_launch(w, h, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, (const int32_t*)d_tile_spp, batch_spp,
+                                    (const float4*)d_albedo, (const float4*)d_normal_depth, P, (char*)d_workspace, (float4*)d_out,
+                                    (hipStream_t)stream);
+}
+
+int pt_denoise_var_tiles(int w, int h, const float* rgba_sum, const float* sq_sum, const int32_t* tile_spp, int batch_spp, const float* albedo,
+                         const float* normal_depth, const pt_denoise_var_params* params, float* out_rgba_sum) {
+    pt_denoise_var_params P;
+    if (params) P = *params; else pt_denoise_var_defaults(&P);
+    if (int r = check_denoise_var_tiles_args(w, h, rgba_sum, sq_sum, tile_spp, batch_spp, albedo, normal_depth, P, out_rgba_sum)) return r;
+    const int T = ((w + 7) / 8) * ((h + 7) / 8);
+    for (int t = 0; t < T; t++)
+        if (tile_spp[t] <= 0 || tile_spp[t] % batch_spp != 0 || tile_spp[t] < 2 * batch_spp)
+            return dn_fail(-1, "pt_denoise_var_tiles: tile_spp[%d] = %d must be a positive multiple of batch_spp that gives at least 2 batches", t,
+                           tile_spp[t]);
+    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total, mapBytes = (size_t)T * sizeof(int32_t);
+    char* d = nullptr;
+    DN_HIP_OK(hipMalloc(&d, ws + 4 * bytes + mapBytes));
+    char* dIn = d + ws;                      // in and out share one buffer (out may alias in)
+    char* dQ = dIn + bytes;
+    char* dA = dQ + bytes;
+    char* dN = dA + bytes;
+    char* dMap = dN + bytes;
+    hipError_t e = hipMemcpy(dIn, rgba_sum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dMap, tile_spp, mapBytes, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = dn_fail(-2, "pt_denoise_var_tiles: upload failed");
+    } else if ((r = denoise_var_tiles_launch(w, h, (const float4*)dIn, (const float4*)dQ, (const int32_t*)dMap, batch_spp, (const float4*)dA,
+                                             (const float4*)dN, P, d, (float4*)dIn, nullptr)) == 0) {
+        e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_var_tiles: download failed");
     }
     (void)hipFree(d);
     return r;

@@ -814,8 +814,52 @@ int  pt_preview_set_converge(pt_preview* p, const pt_converge_params* params);
 int  pt_preview_last_live(pt_preview* p, int* live, int* total);
 int  pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live);
 
+/* ---- adaptive frames with their variance; the variance-guided denoiser on a tile map ------------------
+ * pt_render_adaptive_moments: pt_render_adaptive plus the second moment that pt_render_moments keeps. The schedule, the
+ * estimator, the live lists, the checks, the -4 / stall handling and the megakernel-only rule are pt_render_adaptive's, and
+ * out_rgba_sum, out_tile_spp, out_tile_err and stats are bit-identical to pt_render_adaptive's for the same arguments.
+ * One more argument check, after pt_render_adaptive's checks of params and before any HIP call: max_spp must be a multiple of
+ * 2 * chunk_spp (-1), so that every half-round renders exactly c = chunk_spp samples: a half-round is a batch of
+ * pt_render_moments, and batches of unequal size would make pt_denoise_var's variance formula wrong. A NULL out_sq_sum: -1.
+ * Q. All arithmetic is f32 with IEEE rounding and no contraction, the product rounded before the add. After each of a round's
+ * two launches, per pixel of a live tile and per rgb channel: d = S - P, Q = Q + d d, P = S (P and Q start at 0). A tile that
+ * stops with tile_spp = n therefore holds, over its in-image pixels, S and Q.rgb bit-identical to
+ * pt_render_moments(spp = n, batch_spp = c), and Q.w = (float)(n / c): the batches of that tile. NaN / Inf propagate into Q.
+ * out_sq_sum: w*h float4 scan-line like out_rgba_sum. This call WRITES both; it never touches the counters, and a later
+ * pt_render of the same scene is unaffected. pt_render_adaptive itself launches exactly what it launched before. */
+int pt_render_adaptive_moments(pt_scene* scene, const pt_camera* camera, int w, int h, int max_depth, int integrator, int use_mis,
+                               uint64_t seed, const pt_adaptive_params* params, float* out_rgba_sum, float* out_sq_sum,
+                               int32_t* out_tile_spp, float* out_tile_err, pt_adaptive_stats* stats);           /* host buffers */
+int pt_render_adaptive_moments_device(pt_scene* scene, const pt_camera* camera, int w, int h, int max_depth, int integrator,
+                                      int use_mis, uint64_t seed, const pt_adaptive_params* params, void* d_rgba_sum,
+                                      void* d_sq_sum, void* d_tile_spp, void* d_tile_err, pt_adaptive_stats* stats,
+                                      void* stream);                                                             /* device buffers */
+
+/* pt_denoise_var_tiles: pt_denoise_var on such a frame. The contract is pt_denoise_var's except that the sample count and the
+ * batch count are per pixel, from the frame's tile map (one int32 per tile, as pt_render_adaptive* writes it and pt_resolve
+ * reads it):
+ *   spp_p = tile_spp[(y / 8) * ceil(w / 8) + x / 8],   B_p = spp_p / batch_spp   (integer; Q.w is not read)
+ *   m_p = S_p / spp_p; var_c and V_p as in pt_denoise_var with B_p and spp_p in place of B and spp.
+ * L, the pass-through rule, the 3x3 prefilter, the weights and the iterations are pt_denoise_var's (the same iteration kernel).
+ * Output: rgb = spp_p a_p e_p, w = S_p.w, in the units of the input, so pt_resolve(tile_spp = the map) applies unchanged; out
+ * may alias rgba_sum. With a map whose entries all equal spp the result is bit-identical to pt_denoise_var(spp, batches = spp /
+ * batch_spp), in the host and the device form, which are bit-identical to each other.
+ * Checks before any HIP call: pt_denoise_var's (image size, NULL buffers, params), batch_spp >= 1, a NULL map. The host form
+ * also refuses (-1) a map entry that is <= 0, no multiple of batch_spp, or smaller than 2 * batch_spp (B_p >= 2); the device
+ * form trusts the map, as pt_resolve_device does. Workspace: pt_denoise_var_device's size and layout. */
+size_t pt_denoise_var_tiles_workspace_bytes(int w, int h);
+int pt_denoise_var_tiles(int w, int h, const float* rgba_sum, const float* sq_sum, const int32_t* tile_spp, int batch_spp,
+                         const float* albedo, const float* normal_depth, const pt_denoise_var_params* params,
+                         float* out_rgba_sum);                                                                     /* host, blocking */
+int pt_denoise_var_tiles_device(int w, int h, const void* d_rgba_sum, const void* d_sq_sum, const void* d_tile_spp, int batch_spp,
+                                const void* d_albedo, const void* d_normal_depth, const pt_denoise_var_params* params,
+                                void* d_workspace, void* d_out, void* stream);                                     /* async */
+
 /* ---- probes: single stages of the path on the GPU, for known-answer tests -------------- */
 int pt_probe_rng(uint64_t seed, int n, const uint32_t* subsequences, int n_draws, uint32_t* out_state6, uint32_t* out_u32, float* out_uniform);
+/* The bookkeeping pass of pt_render_adaptive_moments alone: on the first `live` tiles (1..T) of a w x h frame's buffers, one
+ * warm-up launch, then `reps` launches between two HIP events; *out_ms = their mean time in milliseconds. For tools. */
+int pt_probe_adaptive_moments(int w, int h, int live, int reps, float* out_ms);
 int pt_probe_math(int n, const float* x, float* out_sin, float* out_cos, float* out_exp, float* out_rsqrt, float* out_pow5);
 /* All 2^32 binary32 inputs through the kernels' exact fast reciprocal (v_rcp_f32 + one Newton step inside 1e-12 <= |a| <= 1e30,
  * the IEEE division outside) against the IEEE division it stands for (`f = 1.0 / a`, integratorUtilities.cuh:22; 1 / dir, :50-55;
