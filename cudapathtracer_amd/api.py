@@ -159,6 +159,7 @@ def lib():
     L.pt_last_kernel_ms.restype = f32; L.pt_last_kernel_ms.argtypes = [vp]
     L.pt_scene_flags.argtypes = [vp]
     L.pt_last_tile_handovers.argtypes = [vp]
+    L.pt_last_moments_launches.argtypes = [vp]
     L.pt_queue_stalls.argtypes = [vp]
     L.pt_debug_queue_header.argtypes = [vp, C.POINTER(C.c_int)]
     L.pt_set_culling.argtypes = [vp, i32]
@@ -731,6 +732,11 @@ class Scene:
         n = lib().pt_last_tile_handovers(self.h)
         _check(min(n, 0), "pt_last_tile_handovers")
         return n
+
+    def last_moments_launches(self):
+        """pt_last_moments_launches: render launches of the last render_moments* call on this scene — 1 if it ran fused (option
+        "moments_fused"), spp / batch_spp in batches, 0 for an empty tile list, -1 before any such call."""
+        return int(lib().pt_last_moments_launches(self.h))
 
     def queue_header(self):
         """pt_debug_queue_header: the tile queue's 16 header words after the last queued launch (None: that launch used no queue)."""

@@ -90,6 +90,8 @@ struct pt_scene {
     int queueStalls = 0;                          // launches whose waiters gave up (q[3] != 0) although every tile was finished: not an error, counted (pt_queue_stalls)
     bool leanOk = false, leanWanted = true;       // scene qualifies for the LEAN generic bounce (no MAT_LEAF triangle, no texture / transmission map on any triangle's material) / "lean" 0 turns it off (A/B)
     int lastLaunchLean = 0;
+    bool momentsFused = false;                    // "moments_fused" 1: pt_render_moments* renders all its samples in one launch that keeps Q itself, where the kernel has a fused twin
+    int lastMomentsLaunches = -1;                 // render launches of the last pt_render_moments* call (pt_last_moments_launches; -1: none yet)
     bool simpleOk = false, simpleWanted = true;   // scene qualifies for the SIMPLE bounce (diffuse-only, pt_path.h) / "simple" 0 turns it off (A/B)
     bool flatOk = false; int flatWanted = 1;      // "flat": 0 off, 1 (or 2) on: scenes of at most 128 nodes / triangles (64- or 128-bit masks)   // scene qualifies for the FLAT kernels (checked in repack) / "flat" 0 turns them off (A/B)
     int lastLaunchFlat = 0, lastLaunchSimple = 0, lastLaunchLeafTable = 0;
@@ -884,10 +886,15 @@ static int ensure_compact(pt_scene* s) {
 // List mode (list != null: adaptive sampling): t is the whole frame and the launch renders the `live` tiles that the device
 // array `list` names, through the tile queue whatever "persistent" says; the kernel is picked by `live`. The RNG states, the
 // accumulator and `left` stay indexed by tile number, so every buffer is sized for the whole frame.
+// Fused (render_moments with "moments_fused"): the launch is to keep the squared batch sums itself, batches of c samples, in the
+// tile-major buffers P and Q. If the kernel this launch gets has no fused twin, or the scene renders with the wavefront variant,
+// nothing is rendered and `launched` stays false; `seeded` then says whether the streams have been seeded on `stream` already.
+struct FusedMoments { float4* P; float4* Q; int c; bool launched, seeded; };
 static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp, int maxDepth, int integrator, int useMIS,
                         uint64_t seed, const TileSpan& t, void* d_tiles, uint32_t* d_pixcnt, bool count, hipStream_t stream, bool continueStreams,
-                        const int* list = nullptr, int live = -1) {
+                        const int* list = nullptr, int live = -1, FusedMoments* fused = nullptr) {
     if (t.count == 0) return 0;
+    if (fused && s->variant == 1) return 0;
     if (!list) live = t.count;
     if (list && (count || s->variant != 0 || t.first != 0 || t.stride != 1 || live < 0 || live > t.count)) return fail(-1, "render_tiles: bad tile list");
     // the reference keys the stream by the camera's image size (y*w+x with the launch's w, deviceCode.cu:59)
@@ -926,6 +933,7 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     // continueStreams: a later chunk of a progressive render keeps the per-pixel XORWOW states the
     // previous chunk stored (the reference reloads / stores them around every sample, deviceCode.cu:294, 541)
     if (!continueStreams) HIP_OK(launch_rng_init((const uint32_t*)s->jump.p, seed, w, h, t, (uint32_t*)s->rng.p, stream));
+    if (fused) fused->seeded = !continueStreams;
     if (s->variant == 1) return render_tiles_wavefront(s, cam, w, h, spp, maxDepth, integrator, useMIS, t, d_tiles, d_pixcnt, count, stream);
     KParams P;
     P.S = s->ds;
@@ -1001,8 +1009,14 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.totals = (unsigned long long*)s->totals.p;           // the diagnostic build sums its stamps for timed launches too
 #endif
     P.spill = spillEntries > 0 ? (int32_t*)s->spill.p : nullptr;
+    MomentsK M = {nullptr, nullptr, 0, 0.0f};
+    if (fused) {
+        if (!megakernel_has_moments_twin(integrator, count, !(s->deferShadow && !s->armless), P)) return 0;      // the caller renders in batches
+        M.P = fused->P; M.Q = fused->Q; M.c = fused->c; M.rc = 1.0f / (float)fused->c;
+        fused->launched = true;
+    }
     HIP_OK(hipEventRecord(s->ev0, stream));            // HIP events on the launch stream, around the megakernel only
-    HIP_OK(launch_megakernel(integrator, count, !(s->deferShadow && !s->armless), P, live, list, stream));
+    HIP_OK(launch_megakernel(integrator, count, !(s->deferShadow && !s->armless), P, live, list, stream, fused ? &M : nullptr));
     HIP_OK(hipEventRecord(s->ev1, stream));
     s->evPending = true;
     return 0;
@@ -1332,10 +1346,33 @@ static int render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int s
     if (int r = s->moP.ensure(tileBytes)) return r;
     if (int r = s->moQ.ensure(tileBytes)) return r;
     float4 *S = (float4*)s->moS.p, *P = (float4*)s->moP.p, *Q = (float4*)s->moQ.p;
+    s->lastMomentsLaunches = 0;
     HIP_OK(hipMemsetAsync(S, 0, tileBytes, stream));                  // this call writes the sums: they start at 0
     if (listed && live == 0) HIP_OK(launch_moments_update(T, S, P, Q, true, B, stream));    // the zero frame: Q = (0, 0, 0, B)
-    for (int j = 0; j < B && !(listed && live == 0); j++) {
-        if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, j > 0, listed ? list : nullptr, live)) return r;
+    // "moments_fused": ONE launch of all spp samples whose lanes do the bookkeeping themselves at every c-th sample of their pixel
+    // (pt_megakernel.h: MOMENTS) except the last, from P = Q = 0; then the same check and wait as after a batch, and ONE bookkeeping
+    // pass: the last batch's boundary (S is final then) and Q.w. Same bits as the loop below. Where the launch's kernel has no fused twin (render_tiles says so and renders nothing) the loop below runs instead.
+    bool seeded = false, ranFused = false;
+    if (s->momentsFused && !(listed && live == 0) && spp < (1 << 22)) {        // (the kernel's boundary test is exact below 2^22 samples)
+        HIP_OK(hipMemsetAsync(P, 0, tileBytes, stream));
+        HIP_OK(hipMemsetAsync(Q, 0, tileBytes, stream));
+        FusedMoments fused = {P, Q, c, false, false};
+        if (int r = render_tiles(s, cam, w, h, spp, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, false, listed ? list : nullptr, live, &fused)) return r;
+        seeded = fused.seeded;                                         // (the streams are seeded already: the first batch below must not seed them again)
+        if (fused.launched) {
+            s->lastMomentsLaunches = 1; ranFused = true;
+            int q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            const bool queued = s->queue.p && s->lastLaunchQueued;
+            if (queued) HIP_OK(hipMemcpyAsync(q, s->queue.p, sizeof(q), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            if (queued)
+                if (int r = queue_words_error(s, q, s->lastLaunchTiles)) return r;
+            HIP_OK(launch_moments_update(T, S, P, Q, false, B, stream));      // the last batch's boundary, and Q.w, for the whole frame
+        }
+    }
+    for (int j = 0; j < B && !(listed && live == 0) && !ranFused; j++) {
+        if (int r = render_tiles(s, cam, w, h, c, maxDepth, integrator, useMIS, seed, t, S, nullptr, false, stream, j > 0 || seeded, listed ? list : nullptr, live)) return r;
+        s->lastMomentsLaunches = j + 1;
         HIP_OK(launch_moments_update(T, S, P, Q, j == 0, B, stream));
         int q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const bool queued = s->queue.p && s->variant == 0 && s->lastLaunchQueued;
@@ -1632,6 +1669,9 @@ int pt_debug_queue_header(pt_scene* s, int* out16) {
     return 1;
 }
 
+// Render launches of the last pt_render_moments* call on this scene: 1 when it ran fused, B in batches, 0 for an empty list.
+int pt_last_moments_launches(pt_scene* s) { return s ? s->lastMomentsLaunches : -1; }
+
 // Launches of this scene whose queue waiters gave up (no progress for "queue_timeout_ms") although the frame was complete.
 int pt_queue_stalls(pt_scene* s) { return s ? s->queueStalls : 0; }
 
@@ -1652,6 +1692,7 @@ const OptionRef kOptions[] = {
     {"defer_shadow", 0, 1}, {"slice_iters", 0, 1 << 30}, {"slice_always", 0, 1}, {"sched_mask", 0, 1 << 20}, {"lpt_prio", 0, 2},
     {"persistent", 0, 1}, {"xcd_bands", 0, 1}, {"culling", 0, 1}, {"spec", 0, 2}, {"simple", 0, 1}, {"flat2", 0, 1}, {"leaf_boxes", 0, 1}, {"wide", 0, 1},
     {"compact", 0, 1}, {"wf_wide_wg", 0, 2}, {"lean", 0, 1}, {"queue_timeout_ms", 0, 1 << 22},
+    {"moments_fused", 0, 1},          // (new options go at the END: the experimental gate in pt_set_option indexes this table by position)
 };
 int option_index(const char* name) {
     if (!name) return -1;
@@ -1661,10 +1702,11 @@ int option_index(const char* name) {
 }  // namespace
 
 int pt_set_option(pt_scene* s, const char* name, int v) {
-    if (!s) return fail(-1, "null scene");
+    // (the name and the value are checked before the scene: what the library accepts can be asked without a device)
     const int k = option_index(name);
     if (k < 0) return fail(-1, "pt_set_option: unknown option '%s'", name ? name : "(null)");
     if (v < kOptions[k].lo || v > kOptions[k].hi) return fail(-1, "pt_set_option: %s = %d is outside [%d, %d]", name, v, kOptions[k].lo, kOptions[k].hi);
+    if (!s) return fail(-1, "pt_set_option: null scene");
 #ifndef PT_EXPERIMENTAL
     // A/B variants that lost their measurements are not in a default build: only their "off" value is accepted.
     {
@@ -1697,12 +1739,14 @@ int pt_set_option(pt_scene* s, const char* name, int v) {
         case 21: s->wfWideWg = v; break;
         case 22: s->leanWanted = v != 0; break;
         case 23: s->queueTimeoutMs = v; break;
+        case 24: s->momentsFused = v != 0; break;
     }
     return 0;
 }
 
 int pt_get_option(pt_scene* s, const char* name, int* out) {
-    if (!s || !out) return fail(-1, "null argument");
+    if (option_index(name) < 0) return fail(-1, "pt_get_option: unknown option '%s'", name ? name : "(null)");
+    if (!s || !out) return fail(-1, "pt_get_option: null argument");
     switch (option_index(name)) {
         case 0: *out = s->flatWanted; break;
         case 1: *out = s->onchipOk; break;
@@ -1728,6 +1772,7 @@ int pt_get_option(pt_scene* s, const char* name, int* out) {
         case 21: *out = s->wfWideWg; break;
         case 22: *out = s->leanWanted; break;
         case 23: *out = s->queueTimeoutMs; break;
+        case 24: *out = s->momentsFused; break;
         default: return fail(-1, "pt_get_option: unknown option '%s'", name ? name : "(null)");
     }
     return 0;

@@ -242,13 +242,35 @@ hipError_t launch_rng_init(const uint32_t* jump, unsigned long long seed, int w,
 
 // The megakernel instantiations live in two translation units with different code-generation flags (pt_megakernel.h):
 // scenes that live in LDS (ONCHIP kernels) and scenes in HBM (megakernel_hbm and the general 4-wave kernel).
-hipError_t launch_megakernel_lds(int integrator, bool count, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream);
-hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream);
+hipError_t launch_megakernel_lds(int integrator, bool count, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream, const MomentsK* M);
+hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream, const MomentsK* M);
+
+// The twins that are built (pt_megakernel.h, the end): one per non-counting kernel the dispatch below reaches under default options —
+// the LDS-resident forms (pair, FLAT, plain; all trace the shadow ray inside the bounce or pair it) and the REFILL forms for scenes in
+// HBM with their 4-wave forms. Not built: culling, the plain loops ("refill" 0), and whatever only an experimental build launches.
+bool megakernel_has_moments_twin(int integrator, bool count, bool syncShadow, const KParams& P) {
+#ifdef PT_EXPERIMENTAL
+    return false;
+#else
+    if (count || P.cull || P.wide || P.compact || P.xcdBands) return false;
+    if (integrator != 0 && integrator != 2) return false;
+    if (integrator == 0 && !syncShadow) return false;
+    const bool flat2 = P.flat == 3 && integrator == 0;
+    // The SIMPLE pair kernel's twin (megakernel_flat2_moments<0, true>) is built and bit-exact but out of the dispatch: on the 1080p
+    // Cornell frame at 4 spp in 2 batches it measured 13.01 ms a preview frame against 12.71 ms in two launches.
+    if (flat2 && P.simple) return false;
+    const bool ldsScene = P.onchip && !P.hbm && (integrator == 2 || syncShadow || flat2);
+    return ldsScene ? !P.refill : P.refill != 0;
+#endif
+}
 
 // live: the tiles this launch renders — P.tileCount, or (list != null, queued launches only) the list's first `live` entries,
 // tile numbers below P.tileCount.
-hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream) {
+// M (samples per batch > 0): the fused moments twin of that kernel.
+hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream, const MomentsK* M) {
     if (live <= 0) return hipSuccess;
+    if (M && M->c <= 0) M = nullptr;
+    if (M && !megakernel_has_moments_twin(integrator, count, syncShadow, P)) return hipErrorInvalidValue;
     if (list && !(P.queue && P.gridBlocks > 0)) return hipErrorInvalidValue;
     int nBlocks = megakernel_blocks(live, P.wgWaves);
     if (P.queue && P.gridBlocks > 0) {
@@ -263,8 +285,8 @@ hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const 
     const bool simpleKernel = P.simple && !count && ((ldsScene && P.flat) || (!ldsScene && P.refill && !P.cull));      // the instantiations without medium stacks
     const unsigned lds = (unsigned)megakernel_lds_bytes(P.cacheNodes, P.cacheTris, hbm ? ((P.simple && P.refill && !count) ? kStackLdsHbm : kStackLdsHbmGen) : (flat2 ? kStackFlat2 : kStackLds), P.wgWaves,
                                                         ldsScene ? attr_cache_bytes(P.cacheAttrs, P.cacheMats, P.cacheLights) : 0, !simpleKernel);
-    if (ldsScene) return launch_megakernel_lds(integrator, count, P, grid, block, lds, stream);
-    return launch_megakernel_hbm(integrator, count, syncShadow, hbm, P, grid, block, lds, stream);
+    if (ldsScene) return launch_megakernel_lds(integrator, count, P, grid, block, lds, stream, M);
+    return launch_megakernel_hbm(integrator, count, syncShadow, hbm, P, grid, block, lds, stream, M);
 }
 
 hipError_t launch_untile(int w, int h, TileSpan t, const float4* tiles, float4* colors, hipStream_t stream) {

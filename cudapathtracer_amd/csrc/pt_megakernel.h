@@ -165,8 +165,12 @@ PT_DEV void state_store(uint32_t* p, uint32_t v, bool shared) { if (shared) PT_Q
 // scene is in the LDS cache and the stack never spills (pt_trace.h); the host decides per scene. STACKN: LDS
 // stack entries per lane. The body is shared by the two kernels below, which differ in their register cap.
 // LEAN: the generic bounce for scenes without MAT_LEAF triangles and without textures (pt_shade.h).
-template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, int STACKN, bool CULL = false, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, int TREE = 0, bool LEAN = false>
-PT_DEV void megakernel_body(const KParams& P) {
+// MOMENTS: the launch also keeps pt_render_moments' Q, the sum of squared batch sums (moments_land below; the fused twins at the
+// end of this file). Everything it adds sits behind `if constexpr (MOMENTS)`: the other instantiations' code does not change.
+template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, int STACKN, bool CULL = false, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, int TREE = 0, bool LEAN = false,
+          bool MOMENTS = false>
+PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullptr, nullptr, 0, 0.0f}) {
+    static_assert(!MOMENTS || !COUNT, "the fused moments render has no counting form");
     // NOLEAF: no triangle of the scene carries a MAT_LEAF material, so a shadow ray's throughput is exactly 0 or 1 — one flag bit
     // of the resumable traversal, and the DEFER record holds the finished NEE term (PRE). True for SIMPLE and LEAN scenes and
     // for every scene the pair form of FLAT is launched on (pt_api.hip: noLeafTris).
@@ -307,6 +311,45 @@ PT_DEV void megakernel_body(const KParams& P) {
         PT_STAMP(3);
         return t_;
     };
+    // MOMENTS. Sample k of this lane's pixel (1-based) has just LANDED — its Li was added to `acc` — so `acc` is what a launch of k
+    // samples would have left in S. At every M.c-th sample that is the end of a batch of the B-launch form (pt_moments.hip), and
+    // the lane does that form's bookkeeping itself, in its arithmetic and order: d = S - P, Q = Q + d d per channel, P = S.
+    // P and Q live in memory, tile-major like the accumulator and read and written in the same form (state_load / state_store):
+    // the boundary comes once per M.c samples, a tile that changes hands carries nothing extra, and the kernels that live at 64
+    // VGPRs keep their budget. The stores are ahead of the hand-over's wait for this wave's stores like every other state word.
+    // Two of the B boundaries cost no load. The first (k == c) starts from prev = Q = 0, which the lane knows: it only stores. The
+    // last (k == spp) is not taken here at all: `acc` is then the frame's S, and the host runs the batch form's own bookkeeping pass
+    // once after the launch (pt_api.hip: render_moments). A load in the logic step is a round trip to the memory side that the wave
+    // waits for, at four waves per SIMD in the VALU-bound kernels: measured, it is what a boundary costs. Two batches: none at all.
+    auto moments_land = [&](int k) {
+        if (k >= P.spp) return;
+        // k % c == 0 without a division: q is k / c or one off it (k < 2^22, the host's bound: the product's error is far below 1),
+        // so the remainder against q is 0, c or -c exactly when c divides k
+        const int r = k - (int)((float)k * M.rc) * M.c;
+        if (r != 0 && r != M.c && r != -M.c) return;
+        const uint32_t mo = (uint32_t)(lt * 64 + lane);                   // (tiles x 64 fits an int: the host checks the frame's size)
+        uint32_t* mp = (uint32_t*)(M.P + mo);
+        uint32_t* mq = (uint32_t*)(M.Q + mo);
+        float px = 0.0f, py = 0.0f, pz = 0.0f, qx = 0.0f, qy = 0.0f, qz = 0.0f;
+        if (k != M.c) {
+            px = __uint_as_float(state_load(mp, shared)); py = __uint_as_float(state_load(mp + 1, shared)); pz = __uint_as_float(state_load(mp + 2, shared));
+            qx = __uint_as_float(state_load(mq, shared)); qy = __uint_as_float(state_load(mq + 1, shared)); qz = __uint_as_float(state_load(mq + 2, shared));
+        }
+        const float dx = acc.x - px, dy = acc.y - py, dz = acc.z - pz;
+        qx = qx + dx * dx; qy = qy + dy * dy; qz = qz + dz * dz;
+        state_store(mp, __float_as_uint(acc.x), shared); state_store(mp + 1, __float_as_uint(acc.y), shared); state_store(mp + 2, __float_as_uint(acc.z), shared);
+        state_store(mq, __float_as_uint(qx), shared); state_store(mq + 1, __float_as_uint(qy), shared); state_store(mq + 2, __float_as_uint(qz), shared);
+    };
+    // Which sample landed. A lane's samples land in order, and P.spp - samplesLeft of them have been STARTED. path_finish adds at
+    // once unless the path's last NEE term is still in flight (kFinishPending afterwards): then every earlier sample has landed
+    // (apply_pending ran first in this logic step) and the one that lands is the last one started. Otherwise apply_pending adds it
+    // one logic step later, when the lane may already have begun the next sample (kInPath): that one does not count yet.
+    // A batch size of 1 puts a boundary at every sample and shows a wrong count at once.
+    auto landed_by_finish = [&]() { if (!(ps.flags & kFinishPending)) moments_land(P.spp - samplesLeft); };                  // right after path_finish
+    auto landed_by_apply = [&](uint32_t before) {                                                                           // right after apply_pending; before: the flags it found
+        if (before & kFinishPending) moments_land(P.spp - samplesLeft - ((before & kInPath) ? 1 : 0));
+    };
+    (void)landed_by_finish; (void)landed_by_apply;
 
     // Every iteration: one logic step per lane (finish the previous bounce's NEE, shade the hit,
     // regenerate if the path ended), then one traversal round for the rays the logic produced. A
@@ -361,16 +404,18 @@ PT_DEV void megakernel_body(const KParams& P) {
             // inside the bounce) and start their next pair of rays; lanes still tracing skip it and resume below.
             if (!(rs.flags & kRayBusy)) {
                 if constexpr (NOLEAF) thr = (rs.flags & kRayOccluded) ? v3(0.0f) : v3(1.0f);      // the shadow ray's result is one flag bit (pt_trace.h: RayState)
+                const uint32_t flagsIn = ps.flags;
                 apply_pending<NOLEAF>(ps, thr, acc);
+                if constexpr (MOMENTS) landed_by_apply(flagsIn);
                 if (ps.flags & kInPath) {
                     bool done = path_bounce<INTEG, COUNT, true, SIMPLE, LEAN, NOLEAF>(S, ps, ms, h, P.maxDepth, P.useMIS, shadowSync, c);
                     if (!done) done = path_exhausted<INTEG>(ps, P.maxDepth);
-                    if (done) path_finish(ps, acc, true);
+                    if (done) { path_finish(ps, acc, true); if constexpr (MOMENTS) landed_by_finish(); }
                 }
                 while (!(ps.flags & kInPath) && samplesLeft > 0 && !stopStarting) {
                     samplesLeft--;
                     path_begin<COUNT>(P.cam, ps, ms, PT_PX, PT_PY, c);
-                    if (path_exhausted<INTEG>(ps, P.maxDepth)) path_finish(ps, acc, true);
+                    if (path_exhausted<INTEG>(ps, P.maxDepth)) { path_finish(ps, acc, true); if constexpr (MOMENTS) landed_by_finish(); }
                 }
                 const bool hasExt = (ps.flags & kInPath) != 0, hasShadow = (ps.flags & kShadowPending) != 0;
                 if (hasExt || hasShadow) {
@@ -430,17 +475,19 @@ PT_DEV void megakernel_body(const KParams& P) {
         // a lane is busy in this logic step if it shades a hit or starts a sample; the rest of the wave's 64 slots are idle lanes
         occ[0] += 64; occ[1] += __builtin_popcountll(__ballot((ps.flags & kInPath) != 0 || (samplesLeft > 0 && !stopStarting)));
 #endif
+        const uint32_t flagsIn = ps.flags;
         if (DEFER) apply_pending<NOLEAF>(ps, thr, acc);
+        if constexpr (MOMENTS && DEFER) landed_by_apply(flagsIn);
         if (ps.flags & kInPath) {
             bool done = path_bounce<INTEG, COUNT, DEFER, SIMPLE, LEAN, NOLEAF, LTRI>(S, ps, ms, h, P.maxDepth, P.useMIS, shadowSync, c, LTRI ? P.lightTri8 : 0ull);
             if (!done) done = path_exhausted<INTEG>(ps, P.maxDepth);
-            if (done) path_finish(ps, acc, DEFER);
+            if (done) { path_finish(ps, acc, DEFER); if constexpr (MOMENTS) landed_by_finish(); }
         }
         PT_STAMP(2);                                   // slot 2: scheduling check + bounce logic (shading, NEE shadow ray)
         while (!(ps.flags & kInPath) && samplesLeft > 0 && !stopStarting) {
             samplesLeft--;
             path_begin<COUNT>(P.cam, ps, ms, PT_PX, PT_PY, c);
-            if (path_exhausted<INTEG>(ps, P.maxDepth)) path_finish(ps, acc, DEFER);
+            if (path_exhausted<INTEG>(ps, P.maxDepth)) { path_finish(ps, acc, DEFER); if constexpr (MOMENTS) landed_by_finish(); }
         }
         const bool hasExt = (ps.flags & kInPath) != 0;
         const bool hasShadow = DEFER && (ps.flags & kShadowPending) != 0;
@@ -577,6 +624,32 @@ megakernel_hbm_compact(KParams P) { megakernel_body<INTEG, false, false, false, 
 template <int INTEG>
 __global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
 megakernel_hbm_simple(KParams P) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true>(P); }
+
+// ---- the fused moments twins (option "moments_fused", pt_api.hip: render_moments) ----
+// One twin per timed kernel that the launcher picks under default options: the same body with MOMENTS, under the same launch
+// bounds and register cap, launched with the LDS size, workgroup shape and grid the host computes for its counterpart. Entry points
+// of their own, so that the kernels above keep their names, their parameter lists and their code.
+template <int INTEG, bool ONCHIP, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, bool LEAN = false>
+__global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
+#if PT_MIN_WAVES > 0
+__attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
+#endif
+megakernel_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, 0, LEAN, true>(P, M); }
+
+template <int INTEG, bool SIMPLE, bool LEAN = false>
+__global__ void __launch_bounds__(1024)
+#if PT_MIN_WAVES > 0
+__attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
+#endif
+megakernel_flat2_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, 0, LEAN, true>(P, M); }
+
+template <int INTEG, bool LEAN>        // the REFILL forms of megakernel_hbm: the generic bounce and its LEAN form
+__global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))
+megakernel_hbm_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbmGen, false, true, false, false, 1, 0, LEAN, true>(P, M); }
+
+template <int INTEG>
+__global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
+megakernel_hbm_simple_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 0, false, true>(P, M); }
 
 
 }  // namespace pt

@@ -11,9 +11,23 @@
 
 namespace pt {
 
-hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream) {
+hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream, const MomentsK* M) {
     // more than 64 KB of dynamic LDS per workgroup has to be asked for (a workgroup may take all 160 KB of its CU)
 #define PT_LDS_OK(K) do { if (lds > 65536u) { hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e_ != hipSuccess) return e_; } } while (0)
+    if (M) {                                                 // the fused moments twins, picked exactly as their counterparts are below
+        if (count || !P.refill || P.cull || P.wide || P.compact || (integrator != 2 && !syncShadow)) return hipErrorInvalidValue;
+#define PT_LAUNCH_MO(K) do { PT_LDS_OK((K)); hipLaunchKernelGGL((K), grid, block, lds, stream, P, *M); } while (0)
+#define PT_PICK_MO(I) do { if (hbm) { if (P.simple) PT_LAUNCH_MO((megakernel_hbm_simple_moments<I>)); \
+                                      else if (P.lean) PT_LAUNCH_MO((megakernel_hbm_moments<I, true>)); \
+                                      else PT_LAUNCH_MO((megakernel_hbm_moments<I, false>)); } \
+                           else if (P.simple) PT_LAUNCH_MO((megakernel_moments<I, false, true, false, true>)); \
+                           else if (P.lean) PT_LAUNCH_MO((megakernel_moments<I, false, true, false, false, 1, true>)); \
+                           else PT_LAUNCH_MO((megakernel_moments<I, false, true>)); } while (0)
+        if (integrator == 2) PT_PICK_MO(2); else PT_PICK_MO(0);
+#undef PT_PICK_MO
+#undef PT_LAUNCH_MO
+        return hipGetLastError();
+    }
 #define PT_LAUNCH_MK(I, C, D, RF) hipLaunchKernelGGL((megakernel<I, C, D, false, RF>), grid, block, lds, stream, P)
 #define PT_LAUNCH_HBM1(I, C, CU, RF) do { PT_LDS_OK((megakernel_hbm<I, C, CU, RF>)); hipLaunchKernelGGL((megakernel_hbm<I, C, CU, RF>), grid, block, lds, stream, P); } while (0)
 #ifdef PT_EXPERIMENTAL

@@ -114,6 +114,14 @@ struct KParams {
     int lptPrio;                   // longest-remaining-first issue priority once no fresh tile is left
     unsigned long long lightTri8;  // the SIMPLE pair kernel: a byte per light, for the first 8: 1 + the packed triangle the light is (same v0, e1, e2 bit for bit), 0 = none (pt_api.hip: light_triangles)
 };
+// What the fused moments twins take besides (pt_megakernel.h: MOMENTS), as a SECOND kernel argument: the hidden arguments
+// (the workgroup's size) follow the explicit ones, so a KParams that grew would move them and change the code of every kernel.
+struct MomentsK {
+    float4* P;                     // [tile][64] the accumulator at the last batch boundary
+    float4* Q;                     // [tile][64] the sum of squared batch sums so far (.w is the host's)
+    int c;                         // samples per batch; 0: an ordinary launch
+    float rc;                      // 1 / c (the kernel's test for "c divides k" multiplies; spp < 2^22)
+};
 
 struct TileSpan { int first, stride, count, tilesX; };
 
@@ -162,7 +170,11 @@ hipError_t launch_wf_counters(const WfParams& W, uint32_t* pixCounters, unsigned
 hipError_t launch_rng_init(const uint32_t* jump, unsigned long long seed, int w, int h, TileSpan t, uint32_t* rng, hipStream_t stream);
 // syncShadow: trace the NEE shadow ray inside the bounce (needed only for materials without a dispatch arm). live: tiles to
 // render, P.tileCount unless `list` (device, queued launches only) names them: the list form of the queue (pt_kernels.hip)
-hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream);
+// M (M->c > 0): launch that kernel's fused moments twin instead.
+hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream, const MomentsK* M = nullptr);
+// Is there a fused moments twin of the kernel launch_megakernel would pick for these arguments? Without one the
+// launch fails: the caller asks first and renders in batches instead.
+bool megakernel_has_moments_twin(int integrator, bool count, bool syncShadow, const KParams& P);
 hipError_t launch_untile(int w, int h, TileSpan t, const float4* tiles, float4* colors, hipStream_t stream);
 hipError_t launch_tile(int w, int h, TileSpan t, const float4* colors, float4* tiles, hipStream_t stream);
 hipError_t launch_probe_rng(const uint32_t* jump, unsigned long long seed, int n, const uint32_t* subseq, int nDraws,

@@ -185,6 +185,10 @@ int pt_last_tile_handovers(pt_scene* scene);
  * complete and exact; it says the device stalled (seen with several persistent kernels co-resident on one device). A launch
  * that ends with unfinished tiles IS an error (-4). */
 int pt_queue_stalls(pt_scene* scene);
+/* Render launches of the last pt_render_moments / _device / _tiles / _tiles_device call on this scene: 1 if it ran fused
+ * (option "moments_fused"), spp / batch_spp if it rendered in batches, 0 for an empty tile list; -1 before any such call and
+ * for a NULL scene. For tests and measurements. */
+int pt_last_moments_launches(pt_scene* scene);
 /* Debug: the 16 header words of the tile queue after the last queued launch of this scene (1: copied, 0: the last launch used no
  * queue). [0] pops claimed, [1] pushes claimed, [2] tiles finished, [3] stall / error bits (1: a waiter recorded a stall and kept
  * waiting, 2: a waiter gave up for good, 4: a push found no slot), [4] / [5] the issue-priority steering's sums (zero once the kernel
@@ -230,6 +234,13 @@ int pt_set_culling(pt_scene* scene, int on);
  *   "lpt_prio" 0|1|2      issue-priority steering: off / once no fresh tile is left / always (2)
  *   "persistent" 0|1      persistent waves on the tile queue (1)
  *   "queue_timeout_ms" n  how long a wait on the tile queue may see no progress before the waiters leave (30 000)
+ *   "moments_fused" 0|1   pt_render_moments and its _device / _tiles forms render all spp samples in ONE megakernel launch whose
+ *                         lanes keep the squared batch sums themselves, at every batch_spp-th sample of their pixel, instead of
+ *                         spp / batch_spp launches with a bookkeeping pass between them: the same two buffers in every bit.
+ *                         Where the launch's kernel has no fused form in the dispatch — culling, "refill" 0, the wavefront
+ *                         variant, an experimental build, the SIMPLE pair kernel of diffuse-only LDS-resident scenes
+ *                          — the call renders in batches as without the option;
+ *                         pt_last_moments_launches tells which it was (0)
  * Experimental options — variants that were built, proven bit-identical and measured SLOWER. The default
  * library does not contain their kernels (pt_has_experimental() == 0) and accepts only their "off" value, returning -3
  * otherwise; `make -C cudapathtracer_amd/csrc EXPERIMENTAL=1` builds them for the A/B:

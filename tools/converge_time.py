@@ -1,6 +1,6 @@
 """What a resting camera costs with and without converged tiles: two pt_preview sessions side by side at 1920x1080.
 
-    python tools/converge_time.py [--w 1920 --h 1080 --frames 64 --scene cornell --ref-spp 1024 --threshold T --min-history N --centre]
+    python tools/converge_time.py [--w 1920 --h 1080 --frames 64 --scene cornell --ref-spp 1024 --threshold T --min-history N --centre --fused]
 
 Both sessions render the same still camera (tests/temporal_seq.py's) with the session's defaults (4 spp in 2 batches, depth 8,
 MIS, 1 feature ray, temporal accumulation, the history filter, tone map) and the same seeds; one of them has
@@ -10,7 +10,9 @@ both (host clock around a call that ends in a device synchronise). At the end on
 min_history on, both sessions' MSE of the displayed mean against a --ref-spp render with another seed (over the pixels that are
 finite in all three), and the share of pixel-samples that were not rendered. --scene blob renders the 82 k-triangle blob in the
 box, whose tree lives in HBM. --centre gives BOTH sessions centre guides (pt_preview_set_guide_centre): a resting camera then
-launches no feature pass at all, so compare aov_ms and the frame times with a run without the flag."""
+launches no feature pass at all, so compare aov_ms and the frame times with a run without the flag. --fused sets the option
+"moments_fused" on the sessions' scene (every moments render, on a tile list or not, is one launch; `moments_launches` is what
+pt_last_moments_launches reported after the last frame): compare with a run without the flag."""
 import argparse
 import json
 import os
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--threshold", type=float, default=None)
     ap.add_argument("--min-history", type=int, default=None)
     ap.add_argument("--centre", action="store_true")
+    ap.add_argument("--fused", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -48,6 +51,8 @@ def main():
     mh = c["min_history"] if a.min_history is None else a.min_history
     make = scenes.cornell if a.scene == "cornell" else scenes.blob_in_box
     sc = api.Scene(api.HostScene(make(tempfile.mkdtemp(), width=w, height=h, spp=spp, max_depth=depth, name="cvt")["config"]))
+    if a.fused:
+        sc.set_option("moments_fused", 1)
     cam = Q.camera(api, 0, False, w, h)
     conv, plain = api.Preview(sc, w, h).set_converge(thr, mh), api.Preview(sc, w, h)
     if a.centre:
@@ -73,6 +78,7 @@ def main():
     tail = rows[min(mh, len(rows) - 1):]
     res = {"w": w, "h": h, "scene": a.scene, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth, "threshold": thr,
            "min_history": mh, "ref_spp": a.ref_spp, "centre": int(a.centre), "guide_passes": conv.guide_passes,
+           "fused": int(a.fused), "moments_launches": sc.last_moments_launches(),
            "live_share_last": round(rows[-1][0], 4), "live_share_mean": round(sum(r[0] for r in rows) / len(rows), 4),
            "pixel_samples_saved": round(1.0 - sum(r[0] for r in rows) / len(rows), 4),
            "converging_frame_ms_median": med([r[2][0] for r in tail]), "converging_frame_ms_last": round(rows[-1][2][0], 4),

@@ -9,8 +9,9 @@ a mirror box, a glass box around a water box and a gold box), of pt_denoise_devi
 iterations; --iterations sets both, otherwise the variance-guided filter is timed at the classic filter's count and at its own
 default), of the 16-spp depth-8 frame they post-process in one launch (the megakernel's device time, and the launcher's wall
 time), of the same frame as a moments render of 4 batches of 4 and of 2 batches of 8 (pt_render_moments_device: wall time, it
-blocks) and as pt_launch_progressive in 4 chunks (the same launches without the bookkeeping), and the device time of a 4-spp
-launch. --centre times only the four feature passes, in one run: pt_render_aovs_centre_device with max_links 0 (`aov_centre`) and
+blocks), of both again with the scene's option "moments_fused" on (`*_fused_wall`: one launch that keeps the squared batch sums
+itself; `*_fused_launches` is what pt_last_moments_launches reported, 1 unless the kernel has no fused twin) and as
+pt_launch_progressive in 4 chunks (the same launches without the bookkeeping), and the device time of a 4-spp launch. --centre times only the four feature passes, in one run: pt_render_aovs_centre_device with max_links 0 (`aov_centre`) and
 with --max-links (`aov_centre_chain`) next to the jittered `aov` and `aov_chain`."""
 import argparse
 import json
@@ -115,8 +116,12 @@ def main():
         colors.zero_()
         sc.launch_unidirectional(8, cam, 16, True, w, h, colors.data_ptr())
 
-    def moments(c):
-        return lambda: sc.render_moments_device(cam, w, h, 16, c, 8, colors.data_ptr(), sq.data_ptr(), stream=stream)
+    def moments(c, fused=0):
+        def run():
+            sc.set_option("moments_fused", fused)
+            sc.render_moments_device(cam, w, h, 16, c, 8, colors.data_ptr(), sq.data_ptr(), stream=stream)
+            sc.set_option("moments_fused", 0)
+        return run
 
     def progressive():                                    # the same four launches without the bookkeeping
         colors.zero_()
@@ -128,7 +133,8 @@ def main():
     sc.launch_unidirectional(8, cam, 4, True, w, h, colors.data_ptr())
     res["frame_4spp_depth8_ms"] = round(sc.last_kernel_ms(), 3)       # what one batch of four costs on the device
     for name, fn in () if a.centre else (("frame_16spp_one_launch_wall", one_launch), ("frame_16spp_moments_4x4_wall", moments(4)),
-                                         ("frame_16spp_moments_2x8_wall", moments(8)), ("frame_16spp_progressive_4x4_wall", progressive)):
+                                         ("frame_16spp_moments_2x8_wall", moments(8)), ("frame_16spp_moments_4x4_fused_wall", moments(4, 1)),
+                                         ("frame_16spp_moments_2x8_fused_wall", moments(8, 1)), ("frame_16spp_progressive_4x4_wall", progressive)):
         for _ in range(2):
             fn()
         torch.cuda.synchronize()
@@ -139,6 +145,8 @@ def main():
         ts.sort()
         res[name + "_ms_median"] = round(ts[len(ts) // 2], 3)
         res[name + "_ms_min"] = round(ts[0], 3)
+        if name.endswith("_fused_wall"):
+            res[name[:-5] + "_launches"] = sc.last_moments_launches()
     moments(4)()                                          # colors, sq: the 16-spp frame in 4 batches, what the filters below read
     timed = [("aov_chain", aov_chain), ("aov", aov), ("denoise", dn), ("denoise_var", lambda: dn_var(iters))]    # (aov last of the two: the filters read ITS buffers)
     if iters_var != iters:

@@ -1,6 +1,6 @@
 """Wall time of one preview frame at 1920x1080: the pt_preview session next to the chain of host calls it replaces, in one run.
 
-    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3 --scale 1 --scene cornell --centre]
+    python tools/preview_time.py [--w 1920 --h 1080 --frames 20 --warmup 3 --scale 1 --scene cornell --centre --fused]
 
 Both render the same moving-camera sequence (tests/temporal_seq.py's camera) of the Cornell box with the session's defaults
 (4 spp in 2 batches, depth 8, MIS, 1 feature ray, temporal accumulation, the history filter, tone map). The host chain is
@@ -11,7 +11,10 @@ chain's median time per call, and whether the last frames' bytes agree. --scale 
 1 / N of the size in each axis, upsampled by the guides: the host chain then goes through scaled_camera, upsample and
 TemporalHistory.push_cur); --scene blob renders the 82 k-triangle blob in the box, whose tree lives in HBM. --centre leaves the host chain out and runs two sessions frame by frame instead, one with centre
 guides (pt_preview_set_guide_centre) and one without: `session_*` is the one without, `centre_*` the one with; after the moving
-sequence both rest for --frames more frames (`*_resting_*`: the centre session launches no feature pass then)."""
+sequence both rest for --frames more frames (`*_resting_*`: the centre session launches no feature pass then). --fused leaves the
+host chain out as well and runs two sessions frame by frame, on two scenes that differ in the option "moments_fused": `session_*` is
+the one without, `fused_*` the one with (its moments render is one launch); `*_moments_launches` is what pt_last_moments_launches
+reported after the last frame, and `bytes_differing` compares the two sessions' last frames."""
 import argparse
 import json
 import os
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--scale", type=int, default=1)
     ap.add_argument("--scene", choices=("cornell", "blob"), default="cornell")
     ap.add_argument("--centre", action="store_true")
+    ap.add_argument("--fused", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -52,6 +56,29 @@ def main():
     med = lambda v: round(sorted(v)[len(v) // 2], 4)
 
     keys = ("render_ms", "aov_ms", "accumulate_ms", "filter_ms", "resolve_ms", "total_ms")
+    if a.fused:
+        cfg = make(tempfile.mkdtemp(), width=w, height=h, spp=spp, max_depth=depth, name="pvf")["config"]
+        scf = api.Scene(api.HostScene(cfg), options={"moments_fused": 1})
+        both = {"session": (api.Preview(sc, w, h).set_scale(s), sc), "fused": (api.Preview(scf, w, h).set_scale(s), scf)}
+        res = {"w": w, "h": h, "scene": a.scene, "scale": s, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth}
+        wall, stages = {k: [] for k in both}, {k: [] for k in both}
+        for t, cam in enumerate(cams):
+            for k, (pv, _) in both.items():
+                t0 = time.perf_counter()
+                pv.frame(cam, Q.SEED0 + t)
+                wall[k].append(1e3 * (time.perf_counter() - t0))
+                stages[k].append(pv.stats())
+        for k, (pv, scene) in both.items():
+            res[k + "_frame_ms_median"] = med(wall[k][a.warmup:]); res[k + "_frame_ms_min"] = round(min(wall[k][a.warmup:]), 4)
+            for key in keys:
+                res[k + "_" + key + "_median"] = med([st[key] for st in stages[k][a.warmup:]])
+            res[k + "_moments_launches"] = scene.last_moments_launches()
+        last = [pv.read(mean=False, hist=False, hist_len=False)["rgba8"] for pv, _ in both.values()]
+        res["bytes_differing"] = int((last[0] != last[1]).sum())
+        print(json.dumps(res))
+        for pv, _ in both.values():
+            pv.close()
+        return
     if a.centre:
         both = {"session": api.Preview(sc, w, h).set_scale(s), "centre": api.Preview(sc, w, h).set_scale(s).set_guide_centre(1)}
         res = {"w": w, "h": h, "scene": a.scene, "scale": s, "frames": a.frames, "spp": spp, "batches": batches, "max_depth": depth}
