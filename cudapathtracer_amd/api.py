@@ -143,6 +143,11 @@ def lib():
     L.pt_scene_create.restype = vp; L.pt_scene_create.argtypes = [C.POINTER(SceneDesc)]
     L.pt_scene_create_from_mesh.restype = vp; L.pt_scene_create_from_mesh.argtypes = [C.POINTER(SceneDesc), i32, vp]
     L.pt_debug_packed.argtypes = [vp, i32, vp, C.c_size_t]
+    L.pt_scene_update_mesh.argtypes = [vp, C.POINTER(SceneDesc), i32, vp]
+    L.pt_scene_update_vertices.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.pt_scene_update_vertices_device.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.pt_scene_generation.argtypes = [vp]
+    L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
     L.pt_render.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, u64, C.POINTER(TileRange), vp]
@@ -241,6 +246,7 @@ def lib():
     L.pt_preview_create.restype = vp; L.pt_preview_create.argtypes = [vp, i32, i32, C.POINTER(PreviewParams)]
     L.pt_preview_frame.argtypes = [vp, C.POINTER(Camera), u64]
     L.pt_preview_reset.argtypes = [vp]
+    L.pt_preview_scene_changed.argtypes = [vp, i32]
     L.pt_preview_set_scale.argtypes = [vp, i32]
     L.pt_preview_scale.argtypes = [vp]
     L.pt_preview_set_guide_chain.argtypes = [vp, i32]
@@ -421,8 +427,9 @@ def _desc_from_arrays(arrays):
     d.uvs, d.n_uvs = a["uvs"].ctypes.data, a["uvs"].size // 8
     d.triangles, d.n_triangles = a["mesh"].ctypes.data, a["mesh"].size // 80
     d.lights, d.n_lights = (a["lights"].ctypes.data if a["lights"].size else None), a["lights"].size // 80
-    d.bvh, d.n_nodes = a["bvh"].ctypes.data, a["bvh"].size // 48
-    d.bvh_indices = a["indices"].ctypes.data
+    if "bvh" in a:                    # (the device builder reads neither: from_mesh / update_mesh take arrays without a tree)
+        d.bvh, d.n_nodes = a["bvh"].ctypes.data, a["bvh"].size // 48
+        d.bvh_indices = a["indices"].ctypes.data
     d.materials, d.n_materials = a["materials"].ctypes.data, a["materials"].size // 176
     t = a.get("textures")
     d.textures, d.n_texels = (t.ctypes.data if t is not None and t.size else None), (t.size // 16 if t is not None else 0)
@@ -467,23 +474,83 @@ class Scene:
         return int(out[0])
 
     @staticmethod
+    def _mesh_desc(host_or_desc, max_leaf_size):
+        """(SceneDesc, what keeps its arrays alive, leaf size) of a HostScene, a SceneDesc or a dict of arrays in the reference's
+        layouts (points, normals, uvs, mesh, lights, materials[, textures]; a tree is not needed). A HostScene brings its config's
+        leaf size; the other two need max_leaf_size."""
+        if isinstance(host_or_desc, HostScene):
+            return host_or_desc.desc, host_or_desc, host_or_desc.info["leaf_size"] if max_leaf_size is None else int(max_leaf_size)
+        if max_leaf_size is None:
+            raise PtError("max_leaf_size is needed with a SceneDesc or a dict of arrays (only a HostScene knows its config's)")
+        if isinstance(host_or_desc, SceneDesc):
+            return host_or_desc, host_or_desc, int(max_leaf_size)
+        d, keep = _desc_from_arrays(host_or_desc)
+        return d, keep, int(max_leaf_size)
+
+    @staticmethod
     def from_mesh(host: "HostScene", max_leaf_size=None, options=None):
         """pt_scene_create_from_mesh: BVH build (reference tree) and re-layout on the device from the host scene's
-        geometry; its host-built tree is not used. Returns the scene; `.build_stats` has the builder's numbers."""
+        geometry; its host-built tree is not used. `host` may also be a SceneDesc or a dict of arrays (then with
+        max_leaf_size). Returns the scene; `.build_stats` has the builder's numbers."""
         st = np.zeros(1, BUILD_STATS)
-        leaf = host.info["leaf_size"] if max_leaf_size is None else int(max_leaf_size)
-        h = lib().pt_scene_create_from_mesh(C.byref(host.desc), leaf, _p(st))
+        d, keep, leaf = Scene._mesh_desc(host, max_leaf_size)
+        h = lib().pt_scene_create_from_mesh(C.byref(d), leaf, _p(st))
         if not h:
             raise PtError("pt_scene_create_from_mesh failed: " + lib().pt_last_error().decode(errors="replace"))
         sc = Scene.__new__(Scene)
         sc.h = h; sc._keep = host
         sc.set_options(options)
         sc.build_stats = {f: st[0][f].item() for f in BUILD_STATS.names}
+        del keep
         return sc
 
+    def update_mesh(self, host_or_desc, max_leaf_size=None):
+        """pt_scene_update_mesh: replace mesh, materials, lights and textures in place and rebuild the reference tree on the
+        device, as from_mesh would; options, variant, culling, counters and work buffers stay. host_or_desc: a HostScene, a
+        SceneDesc, or a dict of arrays (the last two with max_leaf_size). `.build_stats` has the builder's numbers."""
+        st = np.zeros(1, BUILD_STATS)
+        d, keep, leaf = Scene._mesh_desc(host_or_desc, max_leaf_size)
+        _check(lib().pt_scene_update_mesh(self.h, C.byref(d), leaf, _p(st)), "pt_scene_update_mesh")
+        del keep
+        self.build_stats = {f: st[0][f].item() for f in BUILD_STATS.names}
+        return self
+
+    def update_vertices(self, points, normals=None, n_points=None, n_normals=None):
+        """pt_scene_update_vertices[_device]: new vertex positions (float4 each) and, optionally, new normals for a scene that
+        went through the device builder; topology, materials, lights' triangles and textures stay, and the tree is rebuilt on the
+        device. Host arrays (anything numpy can view as bytes) go to the host form. A device buffer goes to the _device form: an
+        object with data_ptr() (a tensor on the scene's device, 16 bytes per element row), or a raw device pointer as an int with
+        its count in n_points / n_normals, as the other *_device wrappers take pointers. `.build_stats` has the builder's numbers."""
+        def dev(x, n):
+            if isinstance(x, int):
+                if n is None:
+                    raise PtError("update_vertices: a raw device pointer needs its count (n_points / n_normals)")
+                return x, int(n)
+            return x.data_ptr(), (x.numel() * x.element_size()) // 16 if n is None else int(n)
+        st = np.zeros(1, BUILD_STATS)
+        on_device = isinstance(points, int) or hasattr(points, "data_ptr")
+        if on_device:
+            if normals is not None and not (isinstance(normals, int) or hasattr(normals, "data_ptr")):
+                raise PtError("update_vertices: points are on the device, normals must be too")
+            pp, np_ = dev(points, n_points)
+            nn, nn_ = dev(normals, n_normals) if normals is not None else (None, 0)
+            _check(lib().pt_scene_update_vertices_device(self.h, pp, np_, nn, nn_, _p(st)), "pt_scene_update_vertices_device")
+        else:
+            pts = np.ascontiguousarray(points).view(np.uint8).reshape(-1)
+            nrm = np.ascontiguousarray(normals).view(np.uint8).reshape(-1) if normals is not None else None
+            _check(lib().pt_scene_update_vertices(self.h, _p(pts), pts.size // 16, _p(nrm), nrm.size // 16 if nrm is not None else 0, _p(st)),
+                   "pt_scene_update_vertices")
+        self.build_stats = {f: st[0][f].item() for f in BUILD_STATS.names}
+        return self
+
+    @property
+    def generation(self):
+        """pt_scene_generation: 0 after create, +1 per successful update_mesh / update_vertices."""
+        return lib().pt_scene_generation(self.h)
+
     def packed(self, what):
-        """Test hook (pt_debug_packed): the traversal records as uint8 [count, record size]; what = nodes / tris / attrs."""
-        code, rec = {"nodes": (0, 64), "tris": (1, 48), "attrs": (2, 80)}[what]
+        """Test hook (pt_debug_packed): the traversal records as uint8 [count, record size]; what = nodes / tris / attrs / lights."""
+        code, rec = {"nodes": (0, 64), "tris": (1, 48), "attrs": (2, 80), "lights": (3, 64)}[what]
         n = lib().pt_debug_packed(self.h, code, None, 0)
         if n < 0:
             raise PtError("pt_debug_packed failed")
@@ -1374,6 +1441,14 @@ class Preview:
     def reset(self):
         """Drop the history: the next frame is a first frame."""
         _check(lib().pt_preview_reset(self.handle), "pt_preview_reset")
+        return self
+
+    def scene_changed(self, keep_history=False):
+        """pt_preview_scene_changed: the scene was updated (Scene.update_mesh / update_vertices) since the last frame. The next
+        frame renders every tile and traces its guide again; keep_history False also drops the history (as reset does), True
+        blends into it where depth and normal still validate. Without this call a session that finds the scene's generation
+        changed behaves as with keep_history False."""
+        _check(lib().pt_preview_scene_changed(self.handle, 1 if keep_history else 0), "pt_preview_scene_changed")
         return self
 
     def set_scale(self, scale):

@@ -2,6 +2,7 @@
 // launcher boundary (launch_unidirectional / launch_naive_unidirectional, deviceCode.cuh:8-12)
 // and the probe entry points. Host code only; the kernels live in pt_kernels.hip.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -13,6 +14,7 @@
 
 #include "../../include/pt_api.h"
 #include "pt_params.h"
+#include "pt_bvh_build.h"
 #include "xorwow_host.h"
 
 using namespace pt;
@@ -108,6 +110,15 @@ struct pt_scene {
     bool persistent = true;      // "persistent" 0: one tile per wave, workgroups launched per 4 tiles (A/B)
     bool xcdBands = false;       // "xcd_bands" 1: one contiguous band of tiles per XCD (A/B; loses to interleaving)
     bool deferShadow = false;    // "defer_shadow" 1: megakernel traces shadow + extension ray as a pair (A/B; slower)
+    // dynamic geometry (pt_scene_update_*): what the device builder packs from, kept on the device; the spare halves an update builds
+    // into and swaps in on success; the builder's pool (grown on demand, freed at destroy)
+    int generation = 0;                   // pt_scene_generation: +1 per successful update
+    int deviceLeaf = -1;                  // the device builder's leaf size; -1: the tree was the caller's (pt_scene_create)
+    int nPositions = 0, nNormals = 0, nUvs = 0;
+    DevBuf kTris, kNormals, kUvs, kTypes, kLightTris;
+    DevBuf spNodes, spTris, spAttrs, spLights, spLeaves, spNormals;
+    DevBuf buildPool;
+    float renumberMs = 0.0f, updateMs = 0.0f;   // host wall clock of the last renumber_by_area / of the last successful update (pt_debug_update_ms)
     float lastKernelMs = 0.0f;
     bool evPending = false;                            // ev0/ev1 recorded, elapsed time not read yet
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -155,12 +166,16 @@ void pt_scene_destroy(pt_scene* s) {
                      &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
                      &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr,
                      &s->adP, &s->adQ, &s->adSq,
-                     &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList};
+                     &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList,
+                     &s->kTris, &s->kNormals, &s->kUvs, &s->kTypes, &s->kLightTris,
+                     &s->spNodes, &s->spTris, &s->spAttrs, &s->spLights, &s->spLeaves, &s->spNormals, &s->buildPool};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
 }
+
+static double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static int upload(DevBuf& b, const void* src, size_t bytes) {
     if (int r = b.ensure(std::max<size_t>(bytes, 16))) return r;
@@ -197,28 +212,49 @@ static bool boxes_nested_and_finite(const std::vector<PNode>& pn, int nInternal)
 // the bounce's own test of the ray against the light (PLight a, b - a, c - a) and the pass's test against the triangle (PTri v0, e1,
 // e2) see the same operands: checked here bit for bit, on the records as the kernels read them. A light that is no triangle of
 // the scene, or whose vertices are in another order, gets -1 and its shadow rays are tested against everything.
-static void light_triangles(const PTri* pt, int nT, const pt_scene_desc* d, int32_t* out) {
-    for (int i = 0; i < d->n_lights; i++) {
+// The records are read as the kernels read them: PLight a, b, c ARE the positions' floats, and lightIndOf(idx) is the lightInd of
+// original triangle idx (anything outside 0..nLights-1 matches no light), so the table can be made from a description's host
+// arrays and from a scene's device records alike.
+extern "C++" {
+template <class LightIndOf>
+static void light_triangles(const PTri* pt, int nT, const PLight* lights, int nLights, int nTriangles, LightIndOf lightIndOf, int32_t* out) {
+    for (int i = 0; i < nLights; i++) {
         out[i] = -1;
-        const pt_triangle& t = d->lights[i];
-        if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions) continue;
-        const pt_float4 a = d->positions[t.aInd], b = d->positions[t.bInd], c = d->positions[t.cInd];
-        const float v0[3] = {a.x, a.y, a.z}, e1[3] = {b.x - a.x, b.y - a.y, b.z - a.z}, e2[3] = {c.x - a.x, c.y - a.y, c.z - a.z};
+        const PLight& L = lights[i];
+        const float v0[3] = {L.a[0], L.a[1], L.a[2]}, e1[3] = {L.b[0] - L.a[0], L.b[1] - L.a[1], L.b[2] - L.a[2]},
+                    e2[3] = {L.c[0] - L.a[0], L.c[1] - L.a[1], L.c[2] - L.a[2]};
         for (int p = 0; p < nT && p < 63; p++) {                 // (the pair pass holds a ray's triangles in one 64-bit mask, and clears bit p as (1 << (p + 1)) >> 1)
             const int idx = (int)(pt[p].idx & 0x7fffffffu);
-            if (idx >= d->n_triangles || d->triangles[idx].lightInd != i) continue;
+            if (idx >= nTriangles || lightIndOf(idx) != i) continue;
             if (!memcmp(pt[p].v0, v0, 12) && !memcmp(pt[p].e1, e1, 12) && !memcmp(pt[p].e2, e2, 12)) { out[i] = p; break; }
         }
     }
 }
+}  // extern "C++"
+// ... from a description: a light whose vertex indices are out of range gets -1.
+static void light_triangles(const PTri* pt, int nT, const pt_scene_desc* d, int32_t* out) {
+    std::vector<PLight> L((size_t)std::max(d->n_lights, 1));
+    std::vector<uint8_t> bad((size_t)std::max(d->n_lights, 1), 0);
+    for (int i = 0; i < d->n_lights; i++) {
+        const pt_triangle& t = d->lights[i];
+        L[i] = PLight{};
+        if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions) { bad[i] = 1; continue; }
+        const pt_float4 a = d->positions[t.aInd], b = d->positions[t.bInd], c = d->positions[t.cInd];
+        L[i].a[0] = a.x; L[i].a[1] = a.y; L[i].a[2] = a.z; L[i].b[0] = b.x; L[i].b[1] = b.y; L[i].b[2] = b.z; L[i].c[0] = c.x; L[i].c[1] = c.y; L[i].c[2] = c.z;
+    }
+    light_triangles(pt, nT, L.data(), d->n_lights, d->n_triangles, [&](int idx) { const int li = d->triangles[idx].lightInd; return (li >= 0 && li < d->n_lights && bad[li]) ? -1 : li; }, out);
+}
 
 // Re-pack the reference's data model for gfx950.
-extern "C" int pt_bvh_build_pack_(const pt_scene_desc* d, const int* mat_types, int max_leaf_size, void* d_nodes, void* d_tris, void* d_attrs,
-                                  int* out5, pt_bvh_build_stats* stats);
-
 // deviceLeaf < 0: the caller's BVH, packed on the host. deviceLeaf >= 0 (pt_scene_create_from_mesh): the tree is built AND
 // packed on the device (pt_bvh_build.hip) with that leaf size; d->bvh / d->bvh_indices are not read.
-static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_bvh_build_stats* buildStats = nullptr) {
+static int renumber_by_area(pt_scene* s, int nInternal, int rootRef);
+static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef, int nT, int nLights, bool haveLights, int nMats, const PLight* hostLights,
+                         const int32_t* lightIndOf, int nLightInd);
+
+// update: the scene is being updated in place (pt_scene_update_mesh): `s` is the staging scene whose buffers are swapped in on
+// success; the jump table and the counters stay the live scene's and are not touched here.
+static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_bvh_build_stats* buildStats = nullptr, bool update = false) {
     const bool onDevice = deviceLeaf >= 0;
     const int nT = d->n_triangles, nN = onDevice ? 1 : d->n_nodes;
     if (nT <= 0 || nN <= 0 || !d->triangles || (!onDevice && (!d->bvh || !d->bvh_indices)) || !d->positions || !d->materials)
@@ -427,14 +463,49 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (int r = s->attrs.ensure((size_t)nT * sizeof(PAttr))) return r;
         std::vector<int> types(d->n_materials);
         for (int i = 0; i < d->n_materials; i++) types[i] = d->materials[i].type;
+        // what the builder packs from stays on the device with the scene: pt_scene_update_vertices rebuilds from it
+        if (int r = upload(s->kTris, d->triangles, (size_t)nT * sizeof(pt_triangle))) return r;
+        if (int r = upload(s->kNormals, d->normals, d->normals ? (size_t)std::max(d->n_normals, 0) * sizeof(pt_float4) : 0)) return r;
+        if (int r = upload(s->kUvs, d->uvs, d->uvs ? (size_t)std::max(d->n_uvs, 0) * sizeof(pt_float2) : 0)) return r;
+        if (int r = upload(s->kTypes, types.data(), types.size() * sizeof(int))) return r;
+        if (int r = upload(s->kLightTris, d->lights, d->lights ? (size_t)std::max(d->n_lights, 0) * sizeof(pt_triangle) : 0)) return r;
+        s->deviceLeaf = deviceLeaf; s->nPositions = d->n_positions; s->nNormals = d->normals ? std::max(d->n_normals, 0) : 0; s->nUvs = d->uvs ? std::max(d->n_uvs, 0) : 0;
+        pt_build_src_ src{};
+        src.positions = d->positions; src.n_positions = d->n_positions; src.positions_on_device = 0;
+        src.d_triangles = (const pt_triangle*)s->kTris.p; src.n_triangles = nT;
+        src.d_normals = (const pt_float4*)s->kNormals.p; src.n_normals = s->nNormals;
+        src.d_uvs = (const pt_float2*)s->kUvs.p; src.n_uvs = s->nUvs;
+        src.d_mat_types = (const int*)s->kTypes.p; src.n_materials = d->n_materials;
+        src.d_light_tris = (const pt_triangle*)s->kLightTris.p; src.n_lights = d->n_lights;
+        if (update) { src.pool = &s->buildPool.p; src.pool_bytes = &s->buildPool.bytes; }     // (creation allocates and frees its pool, as it always did)
         int out5[5] = {0, 0, 0, 0, 0};
-        if (int r = pt_bvh_build_pack_(d, types.data(), deviceLeaf, s->nodes.p, s->tris.p, s->attrs.p, out5, buildStats)) return r;
+        if (int r = pt_bvh_build_pack_(&src, deviceLeaf, s->nodes.p, s->tris.p, s->attrs.p, nullptr, out5, buildStats)) return r;
         nInternal = out5[0]; stackNeed = out5[1]; rootRef = out5[2];
         if (out5[3]) s->armless = true;
         if (stackNeed > 128) return fail(-1, "pt_scene_create_from_mesh: BVH depth %d exceeds the reference's nodeStack[128] (integratorUtilities.cuh:89)", stackNeed);
+        if (int r = renumber_by_area(s, nInternal, rootRef)) return r;
+    }
+    if (int r = upload(s->lights, lights.data(), lights.size() * sizeof(PLight))) return r;
+    if (int r = upload(s->mats, mats.data(), mats.size() * sizeof(PMat))) return r;
+    if (int r = upload(s->textures, d->textures, (size_t)std::max(d->n_texels, 0) * sizeof(float4))) return r;
+    if (!update) {
+        const std::vector<uint32_t>& jt = xorwow_host::jump_table();
+        if (int r = upload(s->jump, jt.data(), jt.size() * sizeof(uint32_t))) return r;
+        if (int r = s->totals.ensure(16 * sizeof(unsigned long long))) return r;      // 8 counters + 6 diagnostic stamp sums
+        HIP_OK(hipMemset(s->totals.p, 0, 16 * sizeof(unsigned long long)));
+    }
+    std::vector<int32_t> lightInd;                         // (only the scenes the pair kernels can run look at it)
+    if (nT <= 128) { lightInd.resize((size_t)nT); for (int i = 0; i < nT; i++) lightInd[i] = d->triangles[i].lightInd; }
+    return derive_layout(s, nInternal, stackNeed, rootRef, nT, d->n_lights, d->lights != nullptr, d->n_materials, lights.data(), lightInd.data(), (int)lightInd.size());
+}
+
+// Scenes in HBM: the numbering the host re-pack gives the internal nodes (descending surface area of a node's own box — here
+// read from its parent's record, the same floats — so that the LDS copy of PNodes [0, K) holds the most-visited ones), applied to
+// the records the device builder packed into s->nodes. Through the host: one download and one upload of the internal nodes.
+static int renumber_by_area(pt_scene* s, int nInternal, int rootRef) {
+    s->renumberMs = 0.0f;
 #if PT_NODE_ORDER_AREA
-        // the same numbering as the host re-pack gives scenes in HBM (above): descending surface area of a node's own box — here
-        // read from its parent's record, the same floats — so that the LDS copy of PNodes [0, K) holds the most-visited ones
+    const double t0 = wall_ms();
         if (nInternal > 128 && rootRef == 0) {
             std::vector<PNode> pn((size_t)nInternal);
             HIP_OK(hipMemcpy(pn.data(), s->nodes.p, (size_t)nInternal * sizeof(PNode), hipMemcpyDeviceToHost));
@@ -471,26 +542,28 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
                 }
                 HIP_OK(hipMemcpy(s->nodes.p, out.data(), (size_t)nInternal * sizeof(PNode), hipMemcpyHostToDevice));
             }
+            s->renumberMs = (float)(wall_ms() - t0);
         }
 #endif
-    }
-    if (int r = upload(s->lights, lights.data(), lights.size() * sizeof(PLight))) return r;
-    std::vector<int32_t> lightTri(lights.size(), -1);      // filled in below for the scenes the pair kernels can run
-    s->lightTri8 = 0ull;
-    if (int r = upload(s->mats, mats.data(), mats.size() * sizeof(PMat))) return r;
-    if (int r = upload(s->textures, d->textures, (size_t)std::max(d->n_texels, 0) * sizeof(float4))) return r;
-    const std::vector<uint32_t>& jt = xorwow_host::jump_table();
-    if (int r = upload(s->jump, jt.data(), jt.size() * sizeof(uint32_t))) return r;
-    if (int r = s->totals.ensure(16 * sizeof(unsigned long long))) return r;      // 8 counters + 6 diagnostic stamp sums
-    HIP_OK(hipMemset(s->totals.p, 0, 16 * sizeof(unsigned long long)));
+    return 0;
+}
 
+// What creation derives from the packed records in s->nodes / tris / attrs / lights, and an update derives again: the device
+// scene's pointers, the LDS cache split, the spill need, whether the FLAT kernels can run it (and then the leaf counts in the
+// PNodes' spare words, the leaf table and the lights' triangles). hostLights: the PLight records as uploaded (haveLights: the
+// scene has a light list at all); lightIndOf[i]: lightInd of original triangle i (nLightInd entries; read only for scenes of at
+// most 128 triangles).
+static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef, int nT, int nLights, bool haveLights, int nMats, const PLight* hostLights,
+                         const int32_t* lightIndOf, int nLightInd) {
+    std::vector<int32_t> lightTri((size_t)std::max(nLights, 1), -1);      // filled in below for the scenes the pair kernels can run
+    s->lightTri8 = 0ull;
     s->nInternal = nInternal;
     s->stackNeed = stackNeed;
     s->ds.nodes = (const PNode*)s->nodes.p; s->ds.tris = (const PTri*)s->tris.p; s->ds.attrs = (const PAttr*)s->attrs.p;
     s->ds.lights = (const PLight*)s->lights.p; s->ds.mats = (const PMat*)s->mats.p; s->ds.textures = (const float4*)s->textures.p;
     s->ds.rootRef = rootRef;
-    s->ds.nLights = d->n_lights; s->ds.nTris = nT;
-    s->nMats = d->n_materials; s->nLightsPacked = std::max(d->n_lights, 1);
+    s->ds.nLights = nLights; s->ds.nTris = nT;
+    s->nMats = nMats; s->nLightsPacked = std::max(nLights, 1);
     s->ds.stackSpill = std::max(0, stackNeed - kStackLds);
     // scene cache: everything if it fits the LDS budget, else only the top of the (breadth-first) tree
     s->nTrisPacked = nT;
@@ -532,11 +605,11 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (ok && nInternal > 0) HIP_OK(hipMemcpy(s->nodes.p, pn.data(), (size_t)nInternal * sizeof(PNode), hipMemcpyHostToDevice));
         s->flatOk = ok;
         s->nLeaves = 0;
-        if (ok && d->n_lights > 0 && d->lights) {
+        if (ok && nLights > 0 && haveLights) {
             // the table travels as a kernel argument, a byte per light: the first 8 lights (a scene of at most 64 triangles rarely has
             // more; a light beyond them is simply tested like any other triangle)
-            light_triangles(pt.data(), nT, d, lightTri.data());
-            for (int i = 0; i < d->n_lights && i < 8; i++) s->lightTri8 |= (uint64_t)(lightTri[i] + 1) << (8 * i);
+            light_triangles(pt.data(), nT, hostLights, nLights, nLightInd, [&](int idx) { return lightIndOf[idx]; }, lightTri.data());
+            for (int i = 0; i < nLights && i < 8; i++) s->lightTri8 |= (uint64_t)(lightTri[i] + 1) << (8 * i);
         }
         if (ok && nInternal > 0 && boxes_nested_and_finite(pn, nInternal)) {     // the leaf table: every leaf child's box and triangle range
             std::vector<PLeaf> lf;
@@ -582,13 +655,151 @@ pt_scene* pt_scene_create_from_mesh(const pt_scene_desc* desc, int max_leaf_size
     return create_scene(desc, max_leaf_size, stats);
 }
 
-// what: 0 PNodes (64 B each), 1 PTris (48 B), 2 PAttrs (80 B). Returns the record count (or < 0); copies
+// ---- dynamic geometry: pt_scene_update_* ---------------------------------------------------------------------------------
+// An update fills a STAGING scene — a default pt_scene on the caller's stack that borrows the live scene's spare buffers and the
+// builder's pool — through the code creation runs (repack, or the builder + renumber_by_area + derive_layout), and only a
+// complete one is swapped into the live scene. The buffers swapped out become the spares of the next update.
+static void stage_begin(pt_scene* s, pt_scene& t) {
+    auto take = [](DevBuf& from) { DevBuf b = from; from = DevBuf{}; return b; };
+    t.device = s->device; t.numCU = s->numCU;
+    t.nodes = take(s->spNodes); t.tris = take(s->spTris); t.attrs = take(s->spAttrs); t.lights = take(s->spLights); t.leaves = take(s->spLeaves);
+    t.kNormals = take(s->spNormals); t.buildPool = take(s->buildPool);
+}
+static void stage_end(pt_scene* s, pt_scene& t) {
+    s->spNodes = t.nodes; s->spTris = t.tris; s->spAttrs = t.attrs; s->spLights = t.lights; s->spLeaves = t.leaves;
+    s->spNormals = t.kNormals; s->buildPool = t.buildPool;
+    DevBuf* rest[] = {&t.mats, &t.textures, &t.kTris, &t.kUvs, &t.kTypes, &t.kLightTris};     // an update of the whole mesh: the old ones (or, failed, the new ones)
+    for (DevBuf* b : rest) b->release();
+}
+// mesh: materials, textures and the builder's inputs are the staging scene's too (pt_scene_update_mesh); otherwise only the
+// geometry and, if the update brought normals, those.
+static void adopt_geometry(pt_scene* s, pt_scene& t, bool mesh, bool normals) {
+    std::swap(s->nodes, t.nodes); std::swap(s->tris, t.tris); std::swap(s->attrs, t.attrs); std::swap(s->lights, t.lights); std::swap(s->leaves, t.leaves);
+    if (mesh || normals) std::swap(s->kNormals, t.kNormals);
+    if (mesh) {
+        std::swap(s->mats, t.mats); std::swap(s->textures, t.textures);
+        std::swap(s->kTris, t.kTris); std::swap(s->kUvs, t.kUvs); std::swap(s->kTypes, t.kTypes); std::swap(s->kLightTris, t.kLightTris);
+        s->deviceLeaf = t.deviceLeaf; s->nPositions = t.nPositions; s->nNormals = t.nNormals; s->nUvs = t.nUvs;
+    }
+    s->ds = t.ds;
+    s->ds.nodes = (const PNode*)s->nodes.p; s->ds.tris = (const PTri*)s->tris.p; s->ds.attrs = (const PAttr*)s->attrs.p;
+    s->ds.lights = (const PLight*)s->lights.p; s->ds.mats = (const PMat*)s->mats.p; s->ds.textures = (const float4*)s->textures.p;
+    s->stackNeed = t.stackNeed; s->nInternal = t.nInternal; s->cacheNodes = t.cacheNodes; s->cacheTris = t.cacheTris;
+    s->nMats = t.nMats; s->nLightsPacked = t.nLightsPacked; s->nTrisPacked = t.nTrisPacked; s->nLeaves = t.nLeaves; s->lightTri8 = t.lightTri8;
+    s->armless = t.armless; s->simpleOk = t.simpleOk; s->noLeafTris = t.noLeafTris; s->leanOk = t.leanOk; s->flatOk = t.flatOk;
+    // the opt-in trees of EXPERIMENTAL builds were the old geometry's: dropped, and built again on demand
+    s->wnodes.release(); s->qnodes.release(); s->leafBox.release(); s->mids.release();
+    s->compactTried = s->compactOk = s->wideTried = false; s->nWide = 0; s->wideStackNeed = 0;
+    // pt_scene_flags describes the last launch: there is none on this geometry yet
+    s->lastLaunchFlat = s->lastLaunchSimple = s->lastLaunchLeafTable = s->lastLaunchFlat2 = s->lastLaunchLean = s->lastLaunchRefill = 0;
+    s->lastLaunchHbm = -1;
+    s->renumberMs = t.renumberMs;
+    s->generation++;
+}
+
+// The per-frame path: everything but the positions (and the normals, if given) is the scene's own device copy.
+static int update_vertices_staged(pt_scene* s, pt_scene& t, const void* pos, const void* nrm, bool onDevice, pt_bvh_build_stats* stats) {
+    const int nT = s->nTrisPacked, nL = s->ds.nLights;
+    if (int r = t.nodes.ensure((size_t)nT * sizeof(PNode))) return r;
+    if (int r = t.tris.ensure((size_t)nT * sizeof(PTri))) return r;
+    if (int r = t.attrs.ensure((size_t)nT * sizeof(PAttr))) return r;
+    if (int r = t.lights.ensure((size_t)std::max(nL, 1) * sizeof(PLight))) return r;
+    const void* normals = s->kNormals.p;
+    if (nrm) {
+        const size_t bytes = (size_t)s->nNormals * sizeof(pt_float4);
+        if (int r = t.kNormals.ensure(std::max<size_t>(bytes, 16))) return r;
+        if (bytes) HIP_OK(hipMemcpy(t.kNormals.p, nrm, bytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        normals = t.kNormals.p;
+    }
+    pt_build_src_ src{};
+    src.positions = (const pt_float4*)pos; src.n_positions = s->nPositions; src.positions_on_device = onDevice ? 1 : 0;
+    src.d_triangles = (const pt_triangle*)s->kTris.p; src.n_triangles = nT;
+    src.d_normals = (const pt_float4*)normals; src.n_normals = s->nNormals;
+    src.d_uvs = (const pt_float2*)s->kUvs.p; src.n_uvs = s->nUvs;
+    src.d_mat_types = (const int*)s->kTypes.p; src.n_materials = s->nMats;
+    src.d_light_tris = (const pt_triangle*)s->kLightTris.p; src.n_lights = nL;
+    src.pool = &t.buildPool.p; src.pool_bytes = &t.buildPool.bytes;
+    int out5[5] = {0, 0, 0, 0, 0};
+    if (int r = pt_bvh_build_pack_(&src, s->deviceLeaf, t.nodes.p, t.tris.p, t.attrs.p, t.lights.p, out5, stats)) return r;
+    const int nInternal = out5[0], stackNeed = out5[1], rootRef = out5[2];
+    if (stackNeed > 128) return fail(-1, "pt_scene_update_vertices: BVH depth %d exceeds the reference's nodeStack[128] (integratorUtilities.cuh:89)", stackNeed);
+    // what creation decides from the triangles' materials alone stands: neither changed
+    t.armless = s->armless; t.simpleOk = s->simpleOk; t.noLeafTris = s->noLeafTris; t.leanOk = s->leanOk;
+    if (int r = renumber_by_area(&t, nInternal, rootRef)) return r;
+    std::vector<PLight> hostLights((size_t)std::max(nL, 1));
+    std::vector<int32_t> lightInd;
+    if (nT <= 128) {                       // the scenes whose lights' triangles derive_layout looks for: read the records the device made
+        HIP_OK(hipMemcpy(hostLights.data(), t.lights.p, hostLights.size() * sizeof(PLight), hipMemcpyDeviceToHost));
+        std::vector<PAttr> at((size_t)nT);
+        HIP_OK(hipMemcpy(at.data(), t.attrs.p, at.size() * sizeof(PAttr), hipMemcpyDeviceToHost));
+        lightInd.resize((size_t)nT);
+        for (int i = 0; i < nT; i++) lightInd[i] = at[i].lightInd;
+    }
+    return derive_layout(&t, nInternal, stackNeed, rootRef, nT, nL, nL > 0, s->nMats, hostLights.data(), lightInd.data(), (int)lightInd.size());
+}
+
+static int update_vertices(pt_scene* s, const void* pos, int nPos, const void* nrm, int nNrm, bool onDevice, pt_bvh_build_stats* stats, const char* fn) {
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!pos) return fail(-1, "%s: null positions", fn);
+    if (s->deviceLeaf < 0)
+        return fail(-1, "%s: the scene's tree was the caller's (pt_scene_create): only a scene that went through the device builder "
+                        "(pt_scene_create_from_mesh, or one pt_scene_update_mesh) keeps what a vertex update rebuilds from", fn);
+    if (nPos != s->nPositions) return fail(-1, "%s: %d positions, the scene has %d", fn, nPos, s->nPositions);
+    if (nrm && nNrm != s->nNormals) return fail(-1, "%s: %d normals, the scene has %d", fn, nNrm, s->nNormals);
+    const double t0 = wall_ms();
+    HIP_OK(hipDeviceSynchronize());        // a frame boundary: nothing of the old geometry is in flight
+    pt_scene t;
+    stage_begin(s, t);
+    const int r = update_vertices_staged(s, t, pos, nrm, onDevice, stats);
+    if (r == 0) adopt_geometry(s, t, false, nrm != nullptr);
+    stage_end(s, t);
+    if (r == 0) s->updateMs = (float)(wall_ms() - t0);
+    if (r == 0 && stats) stats->total_ms = s->updateMs;
+    return r;
+}
+
+int pt_scene_update_vertices(pt_scene* s, const pt_float4* positions, int n_positions, const pt_float4* normals, int n_normals, pt_bvh_build_stats* stats) {
+    return update_vertices(s, positions, n_positions, normals, n_normals, false, stats, "pt_scene_update_vertices");
+}
+int pt_scene_update_vertices_device(pt_scene* s, const void* d_positions, int n_positions, const void* d_normals, int n_normals, pt_bvh_build_stats* stats) {
+    return update_vertices(s, d_positions, n_positions, d_normals, n_normals, true, stats, "pt_scene_update_vertices_device");
+}
+
+int pt_scene_update_mesh(pt_scene* s, const pt_scene_desc* d, int max_leaf_size, pt_bvh_build_stats* stats) {
+    if (!s) return fail(-1, "pt_scene_update_mesh: null scene");
+    if (!d) return fail(-1, "pt_scene_update_mesh: null desc");
+    if (max_leaf_size < 0) return fail(-1, "pt_scene_update_mesh: negative leaf size");
+    if (d->n_triangles <= 0 || d->n_positions <= 0 || !d->triangles || !d->positions || !d->materials)
+        return fail(-1, "pt_scene_update_mesh: empty scene (triangles, positions and materials are needed)");
+    if ((d->n_lights > 0 && !d->lights) || (d->n_normals > 0 && !d->normals) || (d->n_uvs > 0 && !d->uvs) || (d->n_texels > 0 && !d->textures))
+        return fail(-1, "pt_scene_update_mesh: an array with a positive count is NULL");
+    const double t0 = wall_ms();
+    HIP_OK(hipDeviceSynchronize());        // a frame boundary: nothing of the old geometry is in flight
+    pt_scene t;
+    stage_begin(s, t);
+    const int r = repack(&t, d, max_leaf_size, stats, true);
+    if (r == 0) adopt_geometry(s, t, true, true);
+    stage_end(s, t);
+    if (r == 0) s->updateMs = (float)(wall_ms() - t0);
+    if (r == 0 && stats) stats->total_ms = s->updateMs;
+    return r;
+}
+
+int pt_scene_generation(pt_scene* s) { return s ? s->generation : fail(-1, "pt_scene_generation: null scene"); }
+
+int pt_debug_update_ms(pt_scene* s, float* out3) {
+    if (!s || !out3) return fail(-1, "pt_debug_update_ms: null argument");
+    out3[0] = s->renumberMs; out3[1] = s->updateMs; out3[2] = 0.0f;
+    return 0;
+}
+
+// what: 0 PNodes (64 B each), 1 PTris (48 B), 2 PAttrs (80 B), 3 PLights (64 B). Returns the record count (or < 0); copies
 // min(count * size, capacity) bytes. For tests: the device re-layout must equal the host one.
 int pt_debug_packed(pt_scene* s, int what, void* dst, size_t capacity) {
     if (!s) return fail(-1, "null scene");
-    const void* src = what == 0 ? s->nodes.p : what == 1 ? s->tris.p : what == 2 ? s->attrs.p : nullptr;
-    const size_t rec = what == 0 ? sizeof(PNode) : what == 1 ? sizeof(PTri) : sizeof(PAttr);
-    const int count = what == 0 ? s->nInternal : s->nTrisPacked;
+    const void* src = what == 0 ? s->nodes.p : what == 1 ? s->tris.p : what == 2 ? s->attrs.p : what == 3 ? s->lights.p : nullptr;
+    const size_t rec = what == 0 ? sizeof(PNode) : what == 1 ? sizeof(PTri) : what == 2 ? sizeof(PAttr) : sizeof(PLight);
+    const int count = what == 0 ? s->nInternal : what == 3 ? s->ds.nLights : s->nTrisPacked;
     if (!src) return fail(-1, "pt_debug_packed: unknown array %d", what);
     const size_t bytes = std::min((size_t)count * rec, capacity);
     if (dst && bytes) HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));

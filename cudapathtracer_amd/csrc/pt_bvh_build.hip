@@ -44,6 +44,7 @@
 
 #include "../../include/pt_api.h"
 #include "pt_device.h"
+#include "pt_bvh_build.h"
 
 extern "C" int pt_fail_(int code, const char* msg);
 
@@ -948,9 +949,38 @@ __global__ void k_pack_attrs(Arrays A, PackIn in, pt::PAttr* attrs, int* flagsOu
     a.lightInd = (t.lightInd >= 0 && t.lightInd < in.nLights) ? t.lightInd : -51;
     attrs[i] = a;
 }
+// The light records (pt_api.hip's host re-pack, same operations in the same order): the light's triangle with the CURRENT positions,
+// its first normal, its emission and its area = 0.5f * length(cross3(b - a, c - a)) as the kernels used to evaluate it per NEE
+// sample: IEEE subtractions, cross = fma(p, q, -(r * s)), dot = fma(z, z', fma(y, y', x * x')), correctly rounded sqrt. `lights`
+// was zeroed (a scene without lights keeps one zero record).
+__global__ void k_pack_lights(Arrays A, PackIn in, const pt_triangle* lightTris, pt::PLight* lights, int* flagsOut) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= in.nLights) return;
+    const pt_triangle t = lightTris[i];
+    int ia = t.aInd, ib = t.bInd, ic = t.cInd, na = t.naInd;
+    if ((unsigned)ia >= (unsigned)A.nPos || (unsigned)ib >= (unsigned)A.nPos || (unsigned)ic >= (unsigned)A.nPos || na < 0 || na >= in.nNormals) {
+        atomicOr(flagsOut, 8);
+        return;
+    }
+    const pt_float4 a = A.pos[ia], b = A.pos[ib], c = A.pos[ic], n = in.normals[na];
+    pt::PLight L;
+    L.a[0] = a.x; L.a[1] = a.y; L.a[2] = a.z; L.b[0] = b.x; L.b[1] = b.y; L.b[2] = b.z; L.c[0] = c.x; L.c[1] = c.y; L.c[2] = c.z;
+    L.na[0] = n.x; L.na[1] = n.y; L.na[2] = n.z;
+    L.emission[0] = t.emission.x; L.emission[1] = t.emission.y; L.emission[2] = t.emission.z;
+    const float ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z, vx = c.x - a.x, vy = c.y - a.y, vz = c.z - a.z;
+    const float cx = fmaf(uy, vz, -(uz * vy)), cy = fmaf(uz, vx, -(ux * vz)), cz = fmaf(ux, vy, -(uy * vx));
+    L.area = 0.5f * sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
+    lights[i] = L;
+}
 
 struct Built {                        // what build_core leaves on the device (pool still allocated)
     void* pool = nullptr;
+    bool owned = true;                // false: the pool is the caller's and outlives the build
+    void drop() {                     // the end of a build, good or bad
+        if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
+        if (pool && owned) (void)hipFree(pool);
+        pool = nullptr;
+    }
     Arrays A{};
     int* idx = nullptr;               // the final BVHindices permutation
     int total = 0, outTotal = 0, levels = 0, height = 0;   // reference nodes, breadth-first records, levels built level by level, tree height
@@ -965,14 +995,16 @@ struct Built {                        // what build_core leaves on the device (p
         if (e_ != hipSuccess) {                                                                   \
             char m_[384];                                                                         \
             snprintf(m_, sizeof(m_), "pt_bvh_build_device: %s failed: %s", #expr, hipGetErrorString(e_)); \
-            if (B.pool) { (void)hipFree(B.pool); B.pool = nullptr; }                              \
+            B.drop();                                                                             \
             return pt_fail_(-2, m_);                                                              \
         }                                                                                         \
     } while (0)
 
 // Upload, build, number; leaves everything in B (fin nodes in B.A.fin, BVHindices in B.idx). Returns 0 or < 0.
-int build_core(const pt_float4* positions, int n_positions, const pt_triangle* triangles, int n_triangles, int max_leaf_size,
-               size_t extraBytes, Built& B) {
+// posOnDevice / trisOnDevice: the array is a device array and is read in place instead of uploaded into the pool.
+// extPool / extBytes (both or neither): the caller's pool, grown here if it is too small and never freed by the build.
+int build_core(const pt_float4* positions, bool posOnDevice, int n_positions, const pt_triangle* triangles, bool trisOnDevice, int n_triangles,
+               int max_leaf_size, size_t extraBytes, void** extPool, size_t* extBytes, Built& B) {
     if (!positions || !triangles) return pt_fail_(-1, "pt_bvh_build_device: null argument");
     if (n_triangles <= 0 || n_positions <= 0) return pt_fail_(-1, "pt_bvh_build_device: empty scene (the reference aborts with 'No triangles loaded', main.cu:505-508)");
     if (n_triangles > (1 << 28)) return pt_fail_(-1, "pt_bvh_build_device: more than 2^28 triangles");
@@ -991,14 +1023,28 @@ int build_core(const pt_float4* positions, int n_positions, const pt_triangle* t
     Arrays& A = B.A;
     Carver sizer; carve(sizer, A, n, n_positions, maxBins);
     const size_t extraOff = (sizer.off + 255) & ~(size_t)255;
-    BVH_HIP(hipMalloc(&B.pool, extraOff + extraBytes + 256));
+    const size_t poolBytes = extraOff + extraBytes + 256;
+    if (extPool && extBytes) {
+        B.owned = false;
+        if (*extBytes < poolBytes) {
+            if (*extPool) (void)hipFree(*extPool);
+            *extPool = nullptr; *extBytes = 0;
+            BVH_HIP(hipMalloc(extPool, poolBytes));
+            *extBytes = poolBytes;
+        }
+        B.pool = *extPool;
+    } else {
+        BVH_HIP(hipMalloc(&B.pool, poolBytes));
+    }
     Carver real; real.base = (char*)B.pool; carve(real, A, n, n_positions, maxBins);
     B.extra = (char*)B.pool + extraOff;
     A.n = n; A.nPos = n_positions;
     hipStream_t st = nullptr;
     BVH_HIP(hipEventCreate(&B.ev0));
-    BVH_HIP(hipMemcpy((void*)A.pos, positions, sizeof(pt_float4) * (size_t)n_positions, hipMemcpyHostToDevice));
-    BVH_HIP(hipMemcpy((void*)A.mesh, triangles, sizeof(pt_triangle) * (size_t)n, hipMemcpyHostToDevice));
+    if (posOnDevice) A.pos = positions;
+    else BVH_HIP(hipMemcpy((void*)A.pos, positions, sizeof(pt_float4) * (size_t)n_positions, hipMemcpyHostToDevice));
+    if (trisOnDevice) A.mesh = triangles;
+    else BVH_HIP(hipMemcpy((void*)A.mesh, triangles, sizeof(pt_triangle) * (size_t)n, hipMemcpyHostToDevice));
 
     Ctl& ctl = B.ctl;
     ctl = Ctl{};
@@ -1021,7 +1067,7 @@ int build_core(const pt_float4* positions, int n_positions, const pt_triangle* t
     int levels = 0;
     long long bound = 1;                  // upper bound of the level's node count before the host knows it
     for (;;) {
-        if (levels > 4096) { (void)hipFree(B.pool); B.pool = nullptr; return pt_fail_(-4, "pt_bvh_build_device: more than 4096 levels"); }
+        if (levels > 4096) { B.drop(); return pt_fail_(-4, "pt_bvh_build_device: more than 4096 levels"); }
         const int gB = blocks(std::min<long long>(bound, n));
         hipLaunchKernelGGL(k_next_level, dim3(1), dim3(1), 0, st, A);
         hipLaunchKernelGGL(k_classify, dim3(gB), dim3(kBlock), 0, st, A, work, max_leaf_size);
@@ -1031,7 +1077,7 @@ int build_core(const pt_float4* positions, int n_positions, const pt_triangle* t
         BVH_HIP(hipMemcpyAsync(&ctl, A.ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
         BVH_HIP(hipStreamSynchronize(st));
         if (ctl.bad) {
-            (void)hipFree(B.pool); B.pool = nullptr;
+            B.drop();
             return pt_fail_(ctl.bad >= 3 ? -4 : -1, ctl.bad == 1 ? "pt_bvh_build_device: a triangle's vertex index is out of range"
                                           : ctl.bad == 2 ? "pt_bvh_build_device: non-finite vertex position (the reference's tree is undefined for it)"
                                           : ctl.bad == 4 ? "pt_bvh_build_device: internal error in the small-subtree pass"
@@ -1113,8 +1159,8 @@ extern "C" int pt_bvh_build_device(const pt_float4* positions, int n_positions, 
     if (!nodes_out || !indices_out) return pt_fail_(-1, "pt_bvh_build_device: null argument");
     const auto wall0 = std::chrono::steady_clock::now();
     Built B;
-    if (int r = build_core(positions, n_positions, triangles, n_triangles, max_leaf_size, 0, B)) return r;
-    if (B.total > nodes_capacity) { (void)hipFree(B.pool); return pt_fail_(-1, "pt_bvh_build_device: nodes_out too small (2*n_triangles-1 always suffices)"); }
+    if (int r = build_core(positions, false, n_positions, triangles, false, n_triangles, max_leaf_size, 0, nullptr, nullptr, B)) return r;
+    if (B.total > nodes_capacity) { B.drop(); return pt_fail_(-1, "pt_bvh_build_device: nodes_out too small (2*n_triangles-1 always suffices)"); }
     hipEvent_t ev1 = nullptr;
     BVH_HIP(hipEventCreate(&ev1));
     BVH_HIP(hipEventRecord(ev1, nullptr));
@@ -1122,36 +1168,30 @@ extern "C" int pt_bvh_build_device(const pt_float4* positions, int n_positions, 
     BVH_HIP(hipMemcpy(indices_out, B.idx, sizeof(int32_t) * (size_t)n_triangles, hipMemcpyDeviceToHost));
     float ms = 0.0f;
     BVH_HIP(hipEventElapsedTime(&ms, B.ev0, ev1));
-    (void)hipEventDestroy(B.ev0); (void)hipEventDestroy(ev1);
-    (void)hipFree(B.pool);
+    (void)hipEventDestroy(ev1);
+    B.drop();
     fill_stats(stats, B, ms, wall0);
     return B.total;
 }
 
-// Build + re-layout without leaving the device (pt_scene_create_from_mesh, pt_api.hip). d_nodes / d_tris / d_attrs:
-// device buffers for n_triangles PNodes, n_triangles PTris, n_triangles PAttrs. out[0..4] = internal nodes, stack need
-// (internal nodes on the longest root-to-leaf path), root reference, 1 if a triangle uses a material type without a
-// dispatch arm, total reference nodes.
-extern "C" int pt_bvh_build_pack_(const pt_scene_desc* d, const int* mat_types, int max_leaf_size,
-                                  void* d_nodes, void* d_tris, void* d_attrs, int* out5, pt_bvh_build_stats* stats) {
+// Build + re-layout without leaving the device (pt_scene_create_from_mesh and pt_scene_update_*, pt_api.hip): pt_bvh_build.h.
+extern "C" int pt_bvh_build_pack_(const pt_build_src_* d, int max_leaf_size, void* d_nodes, void* d_tris, void* d_attrs, void* d_lights,
+                                  int* out5, pt_bvh_build_stats* stats) {
     const auto wall0 = std::chrono::steady_clock::now();
     const int n = d->n_triangles;
-    const size_t szNormals = sizeof(pt_float4) * (size_t)std::max(d->n_normals, 1), szUvs = sizeof(pt_float2) * (size_t)std::max(d->n_uvs, 1);
-    const size_t szTypes = sizeof(int) * (size_t)std::max(d->n_materials, 1);
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t offUvs = al(szNormals), offTypes = offUvs + al(szUvs), offLeafEnd = offTypes + al(szTypes);
+    const size_t offLeafEnd = 0;
     const size_t offF = offLeafEnd + al((size_t)n + 16), offS = offF + al(2 * (size_t)n + 16), offBlk = offS + al(sizeof(int) * (2 * (size_t)n + 2));
     const size_t offS2 = offBlk + al(sizeof(int) * ((size_t)blocks(2LL * n, kScanTile) + 2));
     const size_t offFlags = offS2 + al(sizeof(int) * (2 * (size_t)n + 2)), extraBytes = offFlags + 256;
     Built B;
-    if (int r = build_core(d->positions, d->n_positions, d->triangles, n, max_leaf_size, extraBytes, B)) return r;
+    if (int r = build_core(d->positions, d->positions_on_device != 0, d->n_positions, d->d_triangles, true, n, max_leaf_size, extraBytes, d->pool,
+                           d->pool_bytes, B))
+        return r;
     char* X = B.extra;
-    if (d->n_normals > 0) BVH_HIP(hipMemcpy(X, d->normals, sizeof(pt_float4) * (size_t)d->n_normals, hipMemcpyHostToDevice));
-    if (d->n_uvs > 0) BVH_HIP(hipMemcpy(X + offUvs, d->uvs, sizeof(pt_float2) * (size_t)d->n_uvs, hipMemcpyHostToDevice));
-    BVH_HIP(hipMemcpy(X + offTypes, mat_types, sizeof(int) * (size_t)d->n_materials, hipMemcpyHostToDevice));
     BVH_HIP(hipMemsetAsync(X + offLeafEnd, 0, (size_t)n + 16, nullptr));
     BVH_HIP(hipMemsetAsync(X + offFlags, 0, 16, nullptr));
-    PackIn in{(const pt_float4*)X, d->n_normals, (const pt_float2*)(X + offUvs), d->n_uvs, (const int*)(X + offTypes), d->n_materials, d->n_lights};
+    PackIn in{d->d_normals, d->n_normals, d->d_uvs, d->n_uvs, d->d_mat_types, d->n_materials, d->n_lights};
     unsigned char* leafEnd = (unsigned char*)(X + offLeafEnd);
     int* flags = (int*)(X + offFlags);
     // internal nodes of the breadth-first part in that order (exclusive scan of "is internal" over the builder's
@@ -1174,6 +1214,10 @@ extern "C" int pt_bvh_build_pack_(const pt_scene_desc* d, const int* mat_types, 
     hipLaunchKernelGGL(k_pack_nodes, dim3(gT), dim3(kBlock), 0, st, B.A, T, S.S, S2.S, (pt::PNode*)d_nodes, leafEnd);
     hipLaunchKernelGGL(k_pack_tris, dim3(blocks(n)), dim3(kBlock), 0, st, B.A, B.idx, in, leafEnd, (pt::PTri*)d_tris, flags);
     hipLaunchKernelGGL(k_pack_attrs, dim3(blocks(n)), dim3(kBlock), 0, st, B.A, in, (pt::PAttr*)d_attrs, flags);
+    if (d_lights) {
+        BVH_HIP(hipMemsetAsync(d_lights, 0, sizeof(pt::PLight) * (size_t)std::max(d->n_lights, 1), st));
+        if (d->n_lights > 0) hipLaunchKernelGGL(k_pack_lights, dim3(blocks(d->n_lights)), dim3(kBlock), 0, st, B.A, in, d->d_light_tris, (pt::PLight*)d_lights, flags);
+    }
     hipEvent_t ev1 = nullptr;
     BVH_HIP(hipEventCreate(&ev1));
     BVH_HIP(hipEventRecord(ev1, st));
@@ -1189,8 +1233,9 @@ extern "C" int pt_bvh_build_pack_(const pt_scene_desc* d, const int* mat_types, 
     const int rootRef = rootRec.sub >= 0 ? (rootSub.count > 0 ? ~rootSub.first : nBfs) : (rootRec.count > 0 ? ~rootRec.first : 0);
     float ms = 0.0f;
     BVH_HIP(hipEventElapsedTime(&ms, B.ev0, ev1));
-    (void)hipEventDestroy(B.ev0); (void)hipEventDestroy(ev1);
-    (void)hipFree(B.pool); B.pool = nullptr;
+    (void)hipEventDestroy(ev1);
+    B.drop();
+    if (fl & 8) return pt_fail_(-1, "pt_scene_create_from_mesh: a light's vertex or normal index is out of range");
     if (fl & 1) return pt_fail_(-1, "pt_scene_create_from_mesh: a triangle's material index is out of range");
     if (fl & 2) return pt_fail_(-1, "pt_scene_create_from_mesh: a triangle's normal index is out of range (faces without vn must be given a normal by the loader)");
     if (fl & 4) return pt_fail_(-1, "pt_scene_create_from_mesh: a triangle's uv index is out of range");

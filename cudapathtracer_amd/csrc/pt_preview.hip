@@ -147,6 +147,8 @@ struct pt_preview {
     bool haveTiles;
     int lastLive;                         // live tiles of the last good frame (its total is the frame's tile count)
     int frameLive; bool frameConverged;   // what the frame in flight found; committed with the flip
+    int sceneGen;                         // pt_scene_generation at the last good frame (at create before the first)
+    bool sceneChanged;                    // pt_preview_scene_changed since the last good frame: the next frame counts as a moved camera
 };
 
 extern "C" {
@@ -235,6 +237,7 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 
     pt_preview* p = new pt_preview();      // zeroed
     p->scene = scene; p->w = w; p->h = h; p->P = P; p->scale = 1;
+    p->sceneGen = pt_scene_generation(scene);
     const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
     const size_t ws = (pt_denoise_var_workspace_bytes(w, h) + 15) & ~(size_t)15;
     const int pairs = P.temporal ? 2 : 1;
@@ -259,6 +262,14 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 int pt_preview_reset(pt_preview* p) {
     if (!p) return pv_fail(-1, "pt_preview_reset: null session");
     p->haveHist = p->haveFrame = p->haveTiles = false;
+    return 0;
+}
+
+int pt_preview_scene_changed(pt_preview* p, int keep_history) {
+    if (!p) return pv_fail(-1, "pt_preview_scene_changed: null session");
+    if (keep_history != 0 && keep_history != 1) return pv_fail(-1, "pt_preview_scene_changed: keep_history %d must be 0 or 1", keep_history);
+    if (!keep_history) p->haveHist = p->haveFrame = p->haveTiles = false;
+    p->sceneChanged = true;
     return 0;
 }
 
@@ -482,7 +493,11 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     if (!cam) return pv_fail(-1, "pt_preview_frame: null camera");
     const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
     p->frameLive = ((p->w + 7) / 8) * ((p->h + 7) / 8); p->frameConverged = false;
-    const bool same = p->haveHist && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
+    // a scene updated behind the session's back: its history and guide are another geometry's, and nobody said to keep them
+    const int gen = pt_scene_generation(p->scene);
+    if (gen != p->sceneGen && !p->sceneChanged) { p->haveHist = p->haveFrame = p->haveTiles = false; p->sceneChanged = true; }
+    // (a changed scene is a moved camera to the converge and guide-reuse decisions; the accumulation still sees the camera's bytes)
+    const bool same = p->haveHist && !p->sceneChanged && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
     const bool rests = p->converge && p->P.temporal && p->scale == 1 && same;
     // centre guides, the camera of the last good frame, and that frame's guide still in place: no feature pass, no guide flip
     const bool reuse = p->guideCentre && same && p->guideFresh;
@@ -504,6 +519,7 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     p->haveHist = p->P.temporal != 0;
     p->haveFrame = true;
     p->prevCam = *cam;
+    p->sceneGen = gen; p->sceneChanged = false;
     p->lastLive = p->frameLive;
     if (p->frameConverged) { p->curT ^= 1; p->haveTiles = true; }
     p->stats.frames++;

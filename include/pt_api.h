@@ -708,7 +708,20 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  * resets the session as pt_preview_reset does (a call with the current value changes nothing); -1 on a NULL session or a value
  * other than 0 or 1, the session unchanged. The failed-frame rule is unchanged. aov_ms covers the trace and the subsample and is
  * about 0 on a frame that reuses its guide. pt_preview_guide_passes: the feature-pass launches of all good frames since create
- * (with or without centre guides; a failed frame's are not counted, a subsample is none). */
+ * (with or without centre guides; a failed frame's are not counted, a subsample is none).
+ *
+ * CHANGED SCENE. pt_preview_scene_changed(p, keep_history) tells the session that the scene was updated (pt_scene_update_*)
+ * since its last good frame. The next frame is then treated like a moved camera, whatever the camera's bytes say: it renders
+ * every tile (no converging frame; pt_preview_last_live reports live == total) and traces its guide again (centre guides do
+ * not reuse the previous guide; pt_preview_guide_passes counts the pass). keep_history 0 additionally resets the session as
+ * pt_preview_reset does: the frame equals the first frame of a fresh session on a fresh scene of the new arrays, bit for bit.
+ * keep_history 1 accumulates through the public entry points as usual: the previous guide is the old geometry's, a camera
+ * whose 112 bytes are unchanged takes pt_temporal_accumulate's identity path, whose tap is still validated by depth and
+ * normal, and the frame equals that chain of host calls bit for bit. Motion vectors for moving surfaces are out of scope: a
+ * surface that moved keeps its history only where depth and normal still agree at the same pixel. A session also remembers
+ * pt_scene_generation from its last good frame (from create before the first): if the generation differs at pt_preview_frame
+ * and this call was not made since that frame, the session behaves as if it had been made with keep_history 0. The
+ * announcement holds until the next good frame. -1 on a NULL session or a keep_history other than 0 or 1. */
 typedef struct pt_preview pt_preview;
 typedef struct pt_preview_params {
     int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
@@ -728,6 +741,7 @@ void pt_preview_defaults(pt_preview_params* out);
 pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_params* params);   /* NULL on error: pt_last_error() */
 int  pt_preview_frame(pt_preview* p, const pt_camera* camera, uint64_t seed);
 int  pt_preview_reset(pt_preview* p);                                      /* the next frame is a first frame */
+int  pt_preview_scene_changed(pt_preview* p, int keep_history);            /* the scene was updated: see CHANGED SCENE */
 int  pt_preview_set_scale(pt_preview* p, int scale);                       /* 1..8: the render scale of the frames that follow */
 int  pt_preview_scale(pt_preview* p);                                      /* the current scale; -1 on a NULL session */
 int  pt_preview_set_guide_chain(pt_preview* p, int max_links);             /* 0..16: the feature passes of the frames that follow */
@@ -914,9 +928,50 @@ int pt_bvh_build_device(const pt_float4* positions, int n_positions, const pt_tr
  * (buildBVH + uploads) becomes when the geometry is large. The scene renders exactly like one made by
  * pt_scene_create from the host-built tree. */
 pt_scene* pt_scene_create_from_mesh(const pt_scene_desc* desc, int max_leaf_size, pt_bvh_build_stats* stats);
-/* Test hook: copy the packed traversal records back (what: 0 nodes 64 B, 1 triangles 48 B, 2 attributes 80 B);
- * returns the record count. */
+/* Test hook: copy the packed traversal records back (what: 0 nodes 64 B, 1 triangles 48 B, 2 attributes 80 B,
+ * 3 lights 64 B); returns the record count. */
 int pt_debug_packed(pt_scene* scene, int what, void* dst, size_t capacity_bytes);
+
+/* ---- dynamic geometry: in-place updates of a scene, the reference's tree rebuilt on the device -------------------
+ * pt_scene_update_mesh: replace the scene's mesh, materials, lights and textures by desc's and rebuild the reference tree on
+ * the device (desc->bvh / bvh_indices are not read), as pt_scene_create_from_mesh(desc, max_leaf_size) would. It accepts any
+ * scene, one made by pt_scene_create from a caller's BVH included, which becomes a device-built scene.
+ * pt_scene_update_vertices: topology, materials, the lights' triangles and textures unchanged; new vertex positions and,
+ * optionally, new normals (normals NULL = keep the scene's; n_normals is then ignored). n_positions / n_normals must equal the
+ * scene's. Host arrays; the _device form takes device arrays of the same layout on the scene's device and uploads nothing.
+ * Both need a scene that went through the device builder — made by pt_scene_create_from_mesh, or updated once by
+ * pt_scene_update_mesh — because only such a scene knows its leaf size and keeps device copies of its triangles, normals,
+ * uvs, material types and light triangles: -1 with a message otherwise. This is the per-frame path: the builder's pool
+ * belongs to the scene (grown on demand, freed by pt_scene_destroy), the light records are recomputed on the device, and
+ * only the renumbering of the internal nodes by area for scenes in HBM still passes through the host, as at creation.
+ * stats (may be NULL): the builder's, as pt_scene_create_from_mesh fills them; total_ms is the whole call's wall clock.
+ *
+ * EQUIVALENCE. After a successful update every entry point that takes the scene — the renders, _counted, both variants,
+ * adaptive, moments (fused and batched), the feature passes, the probes, pt_scene_flags — gives results bit-identical to a
+ * fresh pt_scene_create_from_mesh of the new arrays with the same options, variant and culling applied. The packed
+ * triangles, attributes and lights are byte-identical and the packed tree is the same tree; what creation derives from them
+ * (which kernels the scene qualifies for, the leaf table, the lights' triangles, the LDS cache split, the stack need and
+ * the spill sizes that follow from it) is derived again by the same code, and the trees of EXPERIMENTAL builds are dropped
+ * and rebuilt on demand.
+ * KEPT: option values (pt_get_option), variant and culling; the sums of pt_get_counters; pt_queue_stalls; the work buffers.
+ * ATOMICITY. Arguments are checked on the host before any HIP call (NULL pointers, counts, for the vertex forms the counts
+ * against the scene's). The build goes into spare node / triangle / attribute / light buffers that are swapped in on
+ * success. A failed update returns the builder's error (a non-finite position, an index out of range, a tree deeper than
+ * 128) and leaves the scene rendering bit for bit what it rendered before.
+ * ORDERING. An update is a frame boundary: it waits for the device's outstanding work on entry and is complete on return;
+ * no launch on the scene may be in flight on another thread, and device arrays passed to the _device form must not be
+ * written until the call returns. pt_scene_generation: 0 after create, +1 per successful update; -1 on NULL.
+ * Multi-GPU replicas (pt_multi_*) are not updated: out of scope. */
+int pt_scene_update_mesh(pt_scene* scene, const pt_scene_desc* desc, int max_leaf_size, pt_bvh_build_stats* stats);
+int pt_scene_update_vertices(pt_scene* scene, const pt_float4* positions, int n_positions,
+                             const pt_float4* normals, int n_normals, pt_bvh_build_stats* stats);
+int pt_scene_update_vertices_device(pt_scene* scene, const void* d_positions, int n_positions,
+                                    const void* d_normals, int n_normals, pt_bvh_build_stats* stats);
+int pt_scene_generation(pt_scene* scene);
+/* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
+ * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
+ * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */
+int pt_debug_update_ms(pt_scene* scene, float* out3);
 /* Test hook, host only (needs no device): out[i], for each of desc->n_lights lights, is the position in leaf order
  * (desc->bvh_indices) of the scene triangle the light was made from — the triangle whose lightInd is i and whose packed
  * v0, e1 = b - a, e2 = c - a equal the light's bit for bit — or -1. Only positions below 63 are reported: the table serves
