@@ -147,6 +147,19 @@ def lib():
     L.pt_scene_update_vertices.argtypes = [vp, vp, i32, vp, i32, vp]
     L.pt_scene_update_vertices_device.argtypes = [vp, vp, i32, vp, i32, vp]
     L.pt_scene_generation.argtypes = [vp]
+    L.pt_scene_has_motion.argtypes = [vp]
+    L.pt_render_motion.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, vp, vp]
+    L.pt_render_motion_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, vp, vp, vp]
+    L.pt_temporal_accumulate_motion.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                C.POINTER(TemporalParams), vp, vp]
+    L.pt_temporal_accumulate_motion_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                       C.POINTER(TemporalParams), vp, vp, vp]
+    L.pt_temporal_accumulate_cur_motion.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, vp,
+                                                    C.POINTER(TemporalParams), vp, vp]
+    L.pt_temporal_accumulate_cur_motion_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, vp,
+                                                           C.POINTER(TemporalParams), vp, vp, vp]
+    L.pt_preview_set_motion.argtypes = [vp, i32]
+    L.pt_preview_motion.argtypes = [vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
@@ -648,6 +661,28 @@ class Scene:
         _check(lib().pt_render_aovs_centre_device(self.h, C.byref(camera), w, h, max_links, d_albedo_ptr, d_normal_depth_ptr, d_links_ptr or None,
                                                   stream or None), "pt_render_aovs_centre_device")
 
+    def render_motion(self, camera, w, h, guides=False):
+        """pt_render_motion: per pixel centre, where the surface point it shows was before the scene's most recent update_vertices:
+        [h,w,4] float32, (P'.x, P'.y, P'.z, 1) for a surface that moved, all zeros for a static one or no hit. First hit only.
+        guides=True returns (albedo, normal_depth, motion), the first two being render_aovs_centre(camera, w, h, 0) bit for bit
+        from the same trace."""
+        mv = np.zeros((h, w, 4), np.float32)
+        alb = np.zeros((h, w, 4), np.float32) if guides else None
+        nd = np.zeros((h, w, 4), np.float32) if guides else None
+        _check(lib().pt_render_motion(self.h, C.byref(camera), w, h, _p(alb), _p(nd), _p(mv)), "pt_render_motion")
+        return (alb, nd, mv) if guides else mv
+
+    def render_motion_device(self, camera, w, h, d_albedo_ptr, d_normal_depth_ptr, d_motion_ptr, stream=0):
+        """pt_render_motion_device: the same into device buffers (w*h float4 each; the two guide pointers both 0 / None or both set),
+        asynchronous on `stream`."""
+        _check(lib().pt_render_motion_device(self.h, C.byref(camera), w, h, d_albedo_ptr or None, d_normal_depth_ptr or None, d_motion_ptr or None,
+                                             stream or None), "pt_render_motion_device")
+
+    @property
+    def has_motion(self):
+        """pt_scene_has_motion: 1 if the scene keeps the positions from before its last update (it was an update_vertices), else 0."""
+        return lib().pt_scene_has_motion(self.h)
+
     def render_adaptive(self, camera, w, h, max_depth, min_spp, max_spp, chunk_spp, threshold, integrator=UNIDIRECTIONAL, use_mis=True,
                         seed=SEED):
         """pt_render_adaptive: tiles stop when their error estimate falls below `threshold` (the schedule: include/pt_api.h).
@@ -1129,6 +1164,67 @@ def temporal_accumulate_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_s
                                                d_out_hist_ptr, d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_device")
 
 
+def _motion_array(what, motion, shape):
+    return None if motion is None else _f4_frames(what, (("motion", motion),), shape)[0]
+
+
+def temporal_accumulate_motion(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None,
+                               hist_len=None, motion=None, max_history=None, depth_tol=None, normal_tol=None):
+    """pt_temporal_accumulate_motion (host, blocking): temporal_accumulate with Scene.render_motion's buffer for this camera: a pixel
+    whose motion.w is 1 reprojects motion.xyz, where its surface point was, and never takes the identity path. motion None is
+    temporal_accumulate bit for bit. Returns new (hist, hist_len)."""
+    what = "temporal_accumulate_motion"
+    S, Q, A, N = _f4_frames(what, (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
+    h, w = S.shape[:2]
+    PN, H, HL = _history_arrays(what, S.shape, prev_normal_depth, hist, hist_len)
+    M = _motion_array(what, motion, S.shape)
+    out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_motion(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q),
+                                               int(spp), int(batches), _p(A), _p(N), _p(PN), _p(H), _p(HL), _p(M), C.byref(p), _p(out),
+                                               _p(out_len)), "pt_temporal_accumulate_motion")
+    return out, out_len
+
+
+def temporal_accumulate_motion_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr,
+                                      d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_motion_ptr, d_out_hist_ptr, d_out_hist_len_ptr,
+                                      max_history=None, depth_tol=None, normal_tol=None, stream=0):
+    """pt_temporal_accumulate_motion_device: temporal_accumulate_device plus the device motion buffer (0 / None: none)."""
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_motion_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
+                                                      d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
+                                                      d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None,
+                                                      d_motion_ptr or None, C.byref(p), d_out_hist_ptr, d_out_hist_len_ptr, stream or None),
+           "pt_temporal_accumulate_motion_device")
+
+
+def temporal_accumulate_cur_motion(camera, cur, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None, hist_len=None, motion=None,
+                                   max_history=None, depth_tol=None, normal_tol=None):
+    """pt_temporal_accumulate_cur_motion (host, blocking): temporal_accumulate_cur with a motion buffer, as temporal_accumulate_motion."""
+    what = "temporal_accumulate_cur_motion"
+    E, N = _f4_frames(what, (("cur", cur), ("normal_depth", normal_depth)))
+    h, w = E.shape[:2]
+    PN, H, HL = _history_arrays(what, E.shape, prev_normal_depth, hist, hist_len)
+    M = _motion_array(what, motion, E.shape)
+    out, out_len = np.empty_like(E), np.empty((h, w), np.float32)
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_cur_motion(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(E), _p(N),
+                                                   _p(PN), _p(H), _p(HL), _p(M), C.byref(p), _p(out), _p(out_len)),
+           "pt_temporal_accumulate_cur_motion")
+    return out, out_len
+
+
+def temporal_accumulate_cur_motion_device(w, h, camera, camera_prev, d_cur_ptr, d_normal_depth_ptr, d_prev_normal_depth_ptr, d_hist_ptr,
+                                          d_hist_len_ptr, d_motion_ptr, d_out_hist_ptr, d_out_hist_len_ptr, max_history=None, depth_tol=None,
+                                          normal_tol=None, stream=0):
+    """pt_temporal_accumulate_cur_motion_device: temporal_accumulate_cur_device plus the device motion buffer (0 / None: none)."""
+    p = _temporal_params(max_history, depth_tol, normal_tol)
+    _check(lib().pt_temporal_accumulate_cur_motion_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
+                                                          d_cur_ptr, d_normal_depth_ptr, d_prev_normal_depth_ptr or None, d_hist_ptr or None,
+                                                          d_hist_len_ptr or None, d_motion_ptr or None, C.byref(p), d_out_hist_ptr,
+                                                          d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_cur_motion_device")
+
+
 def _tile_map(what, tile_live, h, w):
     shape = ((h + 7) // 8, (w + 7) // 8)
     if not isinstance(tile_live, np.ndarray) or tile_live.dtype != np.int32 or tile_live.shape != shape:
@@ -1481,6 +1577,17 @@ class Preview:
     @property
     def guide_centre(self):
         return lib().pt_preview_guide_centre(self.handle)
+
+    def set_motion(self, on):
+        """pt_preview_set_motion: with 1, the frame after one announced update_vertices that keeps its history (scene_changed(True))
+        also traces Scene.render_motion and accumulates through temporal_accumulate[_cur]_motion, so surfaces that moved keep their
+        history. Off by default; changing it does not reset the session."""
+        _check(lib().pt_preview_set_motion(self.handle, int(on)), "pt_preview_set_motion")
+        return self
+
+    @property
+    def motion(self):
+        return lib().pt_preview_motion(self.handle)
 
     @property
     def guide_passes(self):

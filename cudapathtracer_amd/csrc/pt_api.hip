@@ -118,6 +118,11 @@ struct pt_scene {
     DevBuf kTris, kNormals, kUvs, kTypes, kLightTris;
     DevBuf spNodes, spTris, spAttrs, spLights, spLeaves, spNormals;
     DevBuf buildPool;
+    // motion (pt_render_motion): the positions as of the last successful update (or creation) and, while hasMotion, those before it.
+    // A vertex update copies its positions into posPrev and swaps the pair; 2 x 16 B per vertex, device-built scenes only.
+    DevBuf posCur, posPrev;
+    bool hasMotion = false;               // pt_scene_has_motion: the last successful update was a vertex update
+    DevBuf motionOut;                     // pt_render_motion, host form: staging
     float renumberMs = 0.0f, updateMs = 0.0f;   // host wall clock of the last renumber_by_area / of the last successful update (pt_debug_update_ms)
     float lastKernelMs = 0.0f;
     bool evPending = false;                            // ev0/ev1 recorded, elapsed time not read yet
@@ -168,7 +173,8 @@ void pt_scene_destroy(pt_scene* s) {
                      &s->adP, &s->adQ, &s->adSq,
                      &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList,
                      &s->kTris, &s->kNormals, &s->kUvs, &s->kTypes, &s->kLightTris,
-                     &s->spNodes, &s->spTris, &s->spAttrs, &s->spLights, &s->spLeaves, &s->spNormals, &s->buildPool};
+                     &s->spNodes, &s->spTris, &s->spAttrs, &s->spLights, &s->spLeaves, &s->spNormals, &s->buildPool,
+                     &s->posCur, &s->posPrev, &s->motionOut};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -469,6 +475,7 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (int r = upload(s->kUvs, d->uvs, d->uvs ? (size_t)std::max(d->n_uvs, 0) * sizeof(pt_float2) : 0)) return r;
         if (int r = upload(s->kTypes, types.data(), types.size() * sizeof(int))) return r;
         if (int r = upload(s->kLightTris, d->lights, d->lights ? (size_t)std::max(d->n_lights, 0) * sizeof(pt_triangle) : 0)) return r;
+        if (int r = upload(s->posCur, d->positions, (size_t)d->n_positions * sizeof(pt_float4))) return r;      // the motion pass reads them
         s->deviceLeaf = deviceLeaf; s->nPositions = d->n_positions; s->nNormals = d->normals ? std::max(d->n_normals, 0) : 0; s->nUvs = d->uvs ? std::max(d->n_uvs, 0) : 0;
         pt_build_src_ src{};
         src.positions = d->positions; src.n_positions = d->n_positions; src.positions_on_device = 0;
@@ -668,7 +675,7 @@ static void stage_begin(pt_scene* s, pt_scene& t) {
 static void stage_end(pt_scene* s, pt_scene& t) {
     s->spNodes = t.nodes; s->spTris = t.tris; s->spAttrs = t.attrs; s->spLights = t.lights; s->spLeaves = t.leaves;
     s->spNormals = t.kNormals; s->buildPool = t.buildPool;
-    DevBuf* rest[] = {&t.mats, &t.textures, &t.kTris, &t.kUvs, &t.kTypes, &t.kLightTris};     // an update of the whole mesh: the old ones (or, failed, the new ones)
+    DevBuf* rest[] = {&t.mats, &t.textures, &t.kTris, &t.kUvs, &t.kTypes, &t.kLightTris, &t.posCur};     // an update of the whole mesh: the old ones (or, failed, the new ones)
     for (DevBuf* b : rest) b->release();
 }
 // mesh: materials, textures and the builder's inputs are the staging scene's too (pt_scene_update_mesh); otherwise only the
@@ -679,6 +686,7 @@ static void adopt_geometry(pt_scene* s, pt_scene& t, bool mesh, bool normals) {
     if (mesh) {
         std::swap(s->mats, t.mats); std::swap(s->textures, t.textures);
         std::swap(s->kTris, t.kTris); std::swap(s->kUvs, t.kUvs); std::swap(s->kTypes, t.kTypes); std::swap(s->kLightTris, t.kLightTris);
+        std::swap(s->posCur, t.posCur); s->hasMotion = false;        // the topology may have changed: no previous positions, no motion
         s->deviceLeaf = t.deviceLeaf; s->nPositions = t.nPositions; s->nNormals = t.nNormals; s->nUvs = t.nUvs;
     }
     s->ds = t.ds;
@@ -750,8 +758,18 @@ static int update_vertices(pt_scene* s, const void* pos, int nPos, const void* n
     HIP_OK(hipDeviceSynchronize());        // a frame boundary: nothing of the old geometry is in flight
     pt_scene t;
     stage_begin(s, t);
-    const int r = update_vertices_staged(s, t, pos, nrm, onDevice, stats);
-    if (r == 0) adopt_geometry(s, t, false, nrm != nullptr);
+    int r = update_vertices_staged(s, t, pos, nrm, onDevice, stats);
+    // the new positions go into the spare of the pair, and only once the build has taken them: a refused update touches neither
+    const size_t posBytes = (size_t)nPos * sizeof(pt_float4);
+    if (r == 0) r = s->posPrev.ensure(std::max<size_t>(posBytes, 16));
+    if (r == 0) {
+        const hipError_t e = hipMemcpy(s->posPrev.p, pos, posBytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+        if (e != hipSuccess) { s->hasMotion = false; r = fail(-2, "%s: copying the positions failed: %s", fn, hipGetErrorString(e)); }
+    }
+    if (r == 0) {
+        std::swap(s->posCur, s->posPrev); s->hasMotion = true;
+        adopt_geometry(s, t, false, nrm != nullptr);
+    }
     stage_end(s, t);
     if (r == 0) s->updateMs = (float)(wall_ms() - t0);
     if (r == 0 && stats) stats->total_ms = s->updateMs;
@@ -786,6 +804,8 @@ int pt_scene_update_mesh(pt_scene* s, const pt_scene_desc* d, int max_leaf_size,
 }
 
 int pt_scene_generation(pt_scene* s) { return s ? s->generation : fail(-1, "pt_scene_generation: null scene"); }
+
+int pt_scene_has_motion(pt_scene* s) { return s ? (s->hasMotion ? 1 : 0) : fail(-1, "pt_scene_has_motion: null scene"); }
 
 int pt_debug_update_ms(pt_scene* s, float* out3) {
     if (!s || !out3) return fail(-1, "pt_debug_update_ms: null argument");
@@ -1682,6 +1702,10 @@ hipError_t launch_aov_centre(const DeviceScene& S, const CamK& cam, int w, int h
 hipError_t launch_aov_centre_chain(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth,
                                    float* links, int32_t* spill, hipStream_t stream);
 hipError_t launch_probe_centre(const CamK& cam, int n, const int* xy, float* out, hipStream_t stream);
+// pt_motion.hip
+int motion_blocks(int nTiles, int numCU);
+hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w, int h,
+                         int blocks, float4* albedo, float4* normalDepth, float4* motion, int32_t* spill, hipStream_t stream);
 }
 
 // Argument checks of the AOV pass, all before the first HIP call (the device check comes last).
@@ -1802,6 +1826,45 @@ int pt_render_aovs_centre(pt_scene* s, const pt_camera* cam, int w, int h, int m
     HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
     if (out_links) HIP_OK(hipMemcpy(out_links, d + 2 * bytes, lbytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The motion pass (pt_motion.hip: motion_kernel): the centre pass's checks, the guide outputs both or neither, and the motion output.
+static int check_motion_args(pt_scene* s, const pt_camera* cam, int w, int h, const void* a, const void* nd, const void* mv) {
+    if ((a != nullptr) != (nd != nullptr)) return fail(-1, "pt_render_motion: albedo and normal_depth must be both NULL or both set");
+    if (!mv) return fail(-1, "pt_render_motion: null motion output");
+    return check_aov_centre_args(s, cam, w, h, 0, mv, mv);
+}
+
+static int render_motion(pt_scene* s, const pt_camera* cam, int w, int h, void* dA, void* dN, void* dM, hipStream_t stream) {
+    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = motion_blocks(nTiles, s->numCU);
+    int32_t* spill = nullptr;
+    if (s->ds.stackSpill > 0) {          // the AOV passes' own area (they share it: all run on the caller's stream, one after the other)
+        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
+        spill = (int32_t*)s->aovSpill.p;
+    }
+    const bool moving = s->hasMotion && s->deviceLeaf >= 0;
+    HIP_OK(launch_motion(s->ds, s->kTris.p, s->posCur.p, moving ? s->posPrev.p : nullptr, s->nPositions, cam_to_kernel(*cam), w, h, blocks, (float4*)dA,
+                         (float4*)dN, (float4*)dM, spill, stream));
+    return 0;
+}
+
+int pt_render_motion_device(pt_scene* s, const pt_camera* cam, int w, int h, void* d_albedo, void* d_normal_depth, void* d_motion, void* stream) {
+    if (int r = check_motion_args(s, cam, w, h, d_albedo, d_normal_depth, d_motion)) return r;
+    return render_motion(s, cam, w, h, d_albedo, d_normal_depth, d_motion, (hipStream_t)stream);
+}
+
+int pt_render_motion(pt_scene* s, const pt_camera* cam, int w, int h, float* out_albedo, float* out_normal_depth, float* out_motion) {
+    if (int r = check_motion_args(s, cam, w, h, out_albedo, out_normal_depth, out_motion)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    if (int r = s->motionOut.ensure(3 * bytes)) return r;
+    char* d = (char*)s->motionOut.p;
+    if (int r = render_motion(s, cam, w, h, out_albedo ? d : nullptr, out_albedo ? d + bytes : nullptr, d + 2 * bytes, nullptr)) return r;
+    if (out_albedo) {
+        HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
+    }
+    HIP_OK(hipMemcpy(out_motion, d + 2 * bytes, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,0 +1,92 @@
+// pt_motion.hip — the motion pass (pt_render_motion, include/pt_api.h): for the centre ray of each pixel, where the surface point it
+// hits WAS before the scene's most recent vertex update. pt_temporal_accumulate_motion reprojects that point in place of the one on
+// the ray, so a surface that moved finds the history it left behind.
+//
+// aov_centre_kernel's organisation (pt_aov.hip): one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over
+// the tiles, the non-counting trace_closest with the LDS stack and the scene's spill area. After the traversal the hit's original
+// triangle index names three vertex indices in the scene's kept pt_triangle array, and those name three current and three previous
+// positions: three int32 loads, then six float4 loads, all dependent on the hit, none live across the traversal. The previous
+// point is the barycentric sum of the previous positions with resolve_hit's weights, every operation rounded once (no fma).
+// With albedo / normalDepth set the kernel also writes aov_centre_kernel's record, from the same hit through the same functions.
+#include "pt_path.h"
+#include "pt_params.h"
+#include "pt_centre_ray.h"
+#include "../../include/pt_api.h"
+
+namespace pt {
+
+// What the pass reads beside the packed scene, passed next to DeviceScene (which every megakernel takes and which stays as it is).
+// prev NULL: the scene has no previous positions, every pixel is static.
+struct MotionSrc {
+    const pt_triangle* tris;    // original order: Hit::tri indexes it
+    const float4* cur;          // nPos positions as of the last update (or creation)
+    const float4* prev;         // ... and before it
+    int nPos;
+};
+
+// spill: (gridDim.x * 4) waves x S.stackSpill entries x 64 lanes, the lane-interleaved layout of Stack.
+__global__ void __launch_bounds__(256) motion_kernel(DeviceScene S, MotionSrc M, CamK cam, int w, int h, int tilesX, int nTiles,
+                                                     float4* __restrict__ albedo, float4* __restrict__ normalDepth, float4* __restrict__ motion,
+                                                     int32_t* spill) {
+    __shared__ int32_t ldsStack[4][kStackLds][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + wave;
+    Stack<kStackLds> st; st.lds = (lds_i32*)&ldsStack[wave][0][0] + lane; st.sp = 0;
+    st.spill = spill ? spill + (size_t)gw * S.stackSpill * 64 + lane : nullptr;
+    SceneCache C; C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
+    Ctr c = {};
+    for (int tile = gw; tile < nTiles; tile += gridDim.x * 4) {
+        const int x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
+        if (!(x < w && y < h)) continue;
+        const size_t idx = (size_t)y * w + x;
+        V3 o, d;
+        camera_ray_centre(cam, x, y, o, d);
+        Hit hit;
+        trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+        float4 om = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (hit.tri >= 0 && M.prev != nullptr) {
+            const pt_triangle& T = M.tris[hit.tri];
+            const int ia = T.aInd, ib = T.bInd, ic = T.cInd;
+            // (the builder refused the mesh if an index were out of range: the test only keeps a corrupt array from a wild read)
+            if ((unsigned)ia < (unsigned)M.nPos && (unsigned)ib < (unsigned)M.nPos && (unsigned)ic < (unsigned)M.nPos) {
+                const float4 a = M.cur[ia], b = M.cur[ib], cc = M.cur[ic];
+                const float4 pa = M.prev[ia], pb = M.prev[ib], pc = M.prev[ic];
+                const bool still = a.x == pa.x && a.y == pa.y && a.z == pa.z && b.x == pb.x && b.y == pb.y && b.z == pb.z &&
+                                   cc.x == pc.x && cc.y == pc.y && cc.z == pc.z;
+                if (!still) {
+                    const float bz = 1.0f - hit.u - hit.v;         // as resolve_hit forms it
+                    om = make_float4(pa.x * bz + pb.x * hit.u + pc.x * hit.v, pa.y * bz + pb.y * hit.u + pc.y * hit.v,
+                                     pa.z * bz + pb.z * hit.u + pc.z * hit.v, 1.0f);
+                }
+            }
+        }
+        motion[idx] = om;
+        if (albedo != nullptr) {                                   // (uniform: a kernel argument) aov_centre_kernel's record
+            float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
+            if (hit.tri >= 0) {
+                HitInfo hi; resolve_hit(S, hit, o, d, hi);
+                V3 a; float trans;
+                material_inputs(S.mats[hi.material], S.textures, hi.uvx, hi.uvy, true, a, trans);
+                oa = make_float4(a.x, a.y, a.z, 1.0f);
+                on = make_float4(hi.normal.x, hi.normal.y, hi.normal.z, hit.t);
+            }
+            albedo[idx] = oa;
+            normalDepth[idx] = on;
+        }
+    }
+}
+
+// Workgroups of the motion pass: its own count, from its own resources (see the compile's line in DESIGN.md §19).
+constexpr int kMotionWavesPerSimd = 8;
+int motion_blocks(int nTiles, int numCU) { return std::max(1, std::min((nTiles + 3) / 4, numCU * kMotionWavesPerSimd)); }
+
+hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w, int h,
+                         int blocks, float4* albedo, float4* normalDepth, float4* motion, int32_t* spill, hipStream_t stream) {
+    const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
+    MotionSrc M;
+    M.tris = (const pt_triangle*)tris; M.cur = (const float4*)posCur; M.prev = (const float4*)posPrev; M.nPos = nPos;
+    hipLaunchKernelGGL(motion_kernel, dim3(blocks), dim3(256), 0, stream, S, M, cam, w, h, tilesX, nTiles, albedo, normalDepth, motion, spill);
+    return hipGetLastError();
+}
+
+}  // namespace pt

@@ -16,6 +16,8 @@
 //                       With centre guides (pt_preview_set_guide_centre) every feature pass is pt_render_aovs_centre_device, the
 //                       low-res guide of a scaled frame is pt_guide_subsample_device of the display guide, and a frame whose camera
 //                       rests reuses the previous frame's guide: the guide has no seed, so nothing in it could have changed.
+//                       With motion on (pt_preview_set_motion) the frame after an announced vertex update that keeps its history
+//                       also runs pt_render_motion_device and accumulates through pt_temporal_accumulate[_cur]_motion_device.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -149,6 +151,9 @@ struct pt_preview {
     int frameLive; bool frameConverged;   // what the frame in flight found; committed with the flip
     int sceneGen;                         // pt_scene_generation at the last good frame (at create before the first)
     bool sceneChanged;                    // pt_preview_scene_changed since the last good frame: the next frame counts as a moved camera
+    int motion;                           // 1: MOTION FRAMES reproject moved surfaces (pt_preview_set_motion)
+    char* M;                              // w*h float4: pt_render_motion's output (its own allocation, made when motion is first turned on)
+    bool frameMotion;                     // the frame in flight is a motion frame
 };
 
 extern "C" {
@@ -212,6 +217,7 @@ void pt_preview_destroy(pt_preview* p) {
     if (p->lo) (void)hipFree(p->lo);
     if (p->curEV) (void)hipFree(p->curEV);
     if (p->tiles) (void)hipFree(p->tiles);
+    if (p->M) (void)hipFree(p->M);
     delete p;
 }
 
@@ -324,6 +330,21 @@ int pt_preview_guide_centre(pt_preview* p) { return p ? p->guideCentre : pv_fail
 
 int pt_preview_guide_passes(pt_preview* p) { return p ? p->guidePasses : pv_fail(-1, "pt_preview_guide_passes: null session"); }
 
+int pt_preview_set_motion(pt_preview* p, int on) {
+    if (on != 0 && on != 1) return pv_fail(-1, "pt_preview_set_motion: on %d must be 0 or 1", on);
+    if (!p) return pv_fail(-1, "pt_preview_set_motion: null session");
+    if (on && !p->M) {                    // (no frame is in flight: pt_preview_frame blocks)
+        if (hipMalloc(&p->M, (size_t)p->w * p->h * 16) != hipSuccess) {
+            p->M = nullptr;
+            return pv_fail(-2, "pt_preview_set_motion: could not allocate the motion buffer");
+        }
+    }
+    p->motion = on;                       // (no reset: the guides do not depend on it)
+    return 0;
+}
+
+int pt_preview_motion(pt_preview* p) { return p ? p->motion : pv_fail(-1, "pt_preview_motion: null session"); }
+
 int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
     if (!p) return pv_fail(-1, "pt_preview_set_converge: null session");
     if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
@@ -367,6 +388,20 @@ static int preview_aovs(pt_preview* p, const pt_camera* cam, int w, int h, uint6
     if (p->guideCentre) return pt_render_aovs_centre_device(p->scene, cam, w, h, p->guideChain, dA, dN, nullptr, p->stream);
     if (p->guideChain > 0) return pt_render_aovs_chain_device(p->scene, cam, w, h, p->P.aov_spp, p->guideChain, seed, dA, dN, nullptr, p->stream);
     return pt_render_aovs_device(p->scene, cam, w, h, p->P.aov_spp, seed, dA, dN, p->stream);
+}
+
+// The display-size guide of a frame that traces one and, on a motion frame, the motion buffer: one fused pass where the guide is the
+// centre first-hit pass (the motion pass writes that guide from its own trace), else the guide pass and then the motion pass.
+static int preview_display_guide(pt_preview* p, const pt_camera* cam, uint64_t seed, int gn) {
+    const int w = p->w, h = p->h;
+    if (p->frameMotion && p->guideCentre && p->guideChain == 0) {
+        p->framePasses++;
+        return pt_render_motion_device(p->scene, cam, w, h, p->A, p->N[gn], p->M, p->stream);
+    }
+    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
+    if (!p->frameMotion) return 0;
+    p->framePasses++;
+    return pt_render_motion_device(p->scene, cam, w, h, nullptr, nullptr, p->M, p->stream);
 }
 
 // A converging frame (the camera rests, a history exists, scale 1): the same five events around select + read-back + moments on
@@ -420,21 +455,25 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
     if (p->guideCentre) {
         if (!reuse)
-            if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
+            if (int r = preview_display_guide(p, cam, seed, gn)) return r;
         // (also when the guide is reused: the scale may have changed since, and the copy is w * h / s^2 pixels)
         if (int r = pt_guide_subsample_device(w, h, s, p->A, p->N[gn], Al, Nl, st)) return r;
     } else {
         if (int r = preview_aovs(p, &lowCam, wl, hl, seed, Al, Nl)) return r;
-        if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
+        if (int r = preview_display_guide(p, cam, seed, gn)) return r;
     }
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
     if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[gn], nullptr, p->curEV, st)) return r;
     const void* shown = p->curEV;         // the (e, V) buffer the filter reads
     if (P.temporal) {
         const bool hist = p->haveHist;
-        if (int r = pt_temporal_accumulate_cur_device(w, h, cam, hist ? &p->prevCam : nullptr, p->curEV, p->N[gn], hist ? p->N[p->curG] : nullptr,
-                                                      hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt],
-                                                      p->L[nxt], st))
+        if (p->frameMotion) {             // (a motion frame has a history)
+            if (int r = pt_temporal_accumulate_cur_motion_device(w, h, cam, &p->prevCam, p->curEV, p->N[gn], p->N[p->curG], p->H[p->cur], p->L[p->cur],
+                                                                 p->M, &P.temporal_params, p->H[nxt], p->L[nxt], st))
+                return r;
+        } else if (int r = pt_temporal_accumulate_cur_device(w, h, cam, hist ? &p->prevCam : nullptr, p->curEV, p->N[gn],
+                                                             hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr,
+                                                             hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt], p->L[nxt], st))
             return r;
         shown = p->H[nxt];
     }
@@ -460,15 +499,19 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
     if (int r = pt_render_moments_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->S, p->Q, st)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[1], st));
     if (!reuse)
-        if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
+        if (int r = preview_display_guide(p, cam, seed, gn)) return r;
     PV_HIP_OK(hipEventRecord(p->ev[2], st));
     const void* shown = p->S;             // what the resolve divides, and by what
     int shownSpp = P.spp;
     if (P.temporal) {
         const bool hist = p->haveHist;
-        if (int r = pt_temporal_accumulate_device(w, h, cam, hist ? &p->prevCam : nullptr, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn],
-                                                  hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr, hist ? p->L[p->cur] : nullptr,
-                                                  &P.temporal_params, p->H[nxt], p->L[nxt], st))
+        if (p->frameMotion) {             // (a motion frame has a history)
+            if (int r = pt_temporal_accumulate_motion_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], p->N[p->curG],
+                                                             p->H[p->cur], p->L[p->cur], p->M, &P.temporal_params, p->H[nxt], p->L[nxt], st))
+                return r;
+        } else if (int r = pt_temporal_accumulate_device(w, h, cam, hist ? &p->prevCam : nullptr, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn],
+                                                         hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr,
+                                                         hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt], p->L[nxt], st))
             return r;
         PV_HIP_OK(hipEventRecord(p->ev[3], st));
         pt_denoise_var_params F = P.filter_params;
@@ -498,6 +541,9 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     if (gen != p->sceneGen && !p->sceneChanged) { p->haveHist = p->haveFrame = p->haveTiles = false; p->sceneChanged = true; }
     // (a changed scene is a moved camera to the converge and guide-reuse decisions; the accumulation still sees the camera's bytes)
     const bool same = p->haveHist && !p->sceneChanged && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
+    // a MOTION FRAME: the one vertex update since the last good frame was announced with its history kept, and the scene still has
+    // the positions from before it
+    p->frameMotion = p->motion && p->P.temporal && p->haveHist && p->sceneChanged && gen == p->sceneGen + 1 && pt_scene_has_motion(p->scene) == 1;
     const bool rests = p->converge && p->P.temporal && p->scale == 1 && same;
     // centre guides, the camera of the last good frame, and that frame's guide still in place: no feature pass, no guide flip
     const bool reuse = p->guideCentre && same && p->guideFresh;

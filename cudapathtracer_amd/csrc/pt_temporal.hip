@@ -16,6 +16,10 @@
 //                                       map entry is one scalar load and the branch does not diverge: a carried wave copies its
 //                                       history and length (two loads, two stores), a live wave runs temporal_accumulate_kernel<true>'s
 //                                       code.
+//   temporal_accumulate_motion_kernel<IDENT>, temporal_accumulate_cur_motion_kernel<IDENT>  the two kernels above with a motion
+//                                       buffer (pt_render_motion): a pixel whose motion.w is 1 reprojects the point the buffer
+//                                       names — where its surface point WAS — and never takes the identity tap; every other
+//                                       pixel runs the base kernel's code (temporal_blend<IDENT, true>). One more float4 load.
 // Both cameras travel by value as kernel arguments (SGPRs); plain cached float4 loads, no LDS.
 #include <cmath>
 #include <cstdio>
@@ -69,11 +73,12 @@ __device__ inline void temporal_tap(TemporalTap& t, int w, int h, int xq, int yq
 }
 
 // Steps 2-5 of the contract for a pixel whose working value `cur` (e, V >= 0) is known: reproject, gather, blend, write.
-template <bool IDENT>
+// MOTION: `motion` is set, and a pixel with motion.w == 1 takes its xyz as the point to reproject (no identity tap for it).
+template <bool IDENT, bool MOTION = false>
 __device__ inline void temporal_blend(int w, int h, int x, int y, float4 cur, const TemporalCam& cam, const TemporalCam& prev,
                                       const float4* __restrict__ nd, const float4* __restrict__ prevNd, const float4* __restrict__ hist,
                                       const float* __restrict__ histLen, float maxHistory, float depthTol, float normalTol,
-                                      float4* __restrict__ outHist, float* __restrict__ outLen) {
+                                      float4* __restrict__ outHist, float* __restrict__ outLen, const float4* __restrict__ motion = nullptr) {
     const size_t p = (size_t)y * w + x;
     float4 res = cur;
     float len = 1.0f;
@@ -81,15 +86,23 @@ __device__ inline void temporal_blend(int w, int h, int x, int y, float4 cur, co
         const float4 gp = dn_unit_guide(nd[p]);
         const bool normalP = gp.x != 0.0f || gp.y != 0.0f || gp.z != 0.0f;
         TemporalTap t = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (IDENT) {
+        float4 mv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (MOTION) mv = motion[p];                           // (read only with a history)
+        const bool moved = MOTION && mv.w == 1.0f;
+        if (IDENT && !moved) {
             if (normalP) temporal_tap(t, w, h, x, y, 1.0f, gp, gp.w, depthTol, normalTol, prevNd, hist, histLen);
         } else if (normalP) {
             // the unjittered centre ray of the pixel (camera_ray with both jitters 0 and no lens sample), to the depth z_p
-            const float u = (2.0f * ((float)x / (float)w) - 1.0f) * cam.aspect * cam.fovScale;
-            const float v = (2.0f * ((float)y / (float)h) - 1.0f) * cam.fovScale;
-            const float tx = cam.rx * u + cam.ux * v + cam.fx, ty = cam.ry * u + cam.uy * v + cam.fy, tz = cam.rz * u + cam.uz * v + cam.fz;
-            const float tl = sqrtf(tx * tx + ty * ty + tz * tz);
-            const float px = cam.ox + tx / tl * gp.w, py = cam.oy + ty / tl * gp.w, pz = cam.oz + tz / tl * gp.w;
+            float px, py, pz;
+            if (moved) {                                      // where this surface point was when the previous frame was made
+                px = mv.x; py = mv.y; pz = mv.z;
+            } else {
+                const float u = (2.0f * ((float)x / (float)w) - 1.0f) * cam.aspect * cam.fovScale;
+                const float v = (2.0f * ((float)y / (float)h) - 1.0f) * cam.fovScale;
+                const float tx = cam.rx * u + cam.ux * v + cam.fx, ty = cam.ry * u + cam.uy * v + cam.fy, tz = cam.rz * u + cam.uz * v + cam.fz;
+                const float tl = sqrtf(tx * tx + ty * ty + tz * tz);
+                px = cam.ox + tx / tl * gp.w; py = cam.oy + ty / tl * gp.w; pz = cam.oz + tz / tl * gp.w;
+            }
             // ... seen from the previous camera
             const float qx = px - prev.ox, qy = py - prev.oy, qz = pz - prev.oz;
             const float zc = qx * prev.fx + qy * prev.fy + qz * prev.fz;
@@ -181,6 +194,41 @@ __global__ void __launch_bounds__(256) temporal_accumulate_cur_kernel(int w, int
     temporal_blend<IDENT>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
 }
 
+// pt_temporal_accumulate_motion / _cur_motion: the two kernels above with the motion buffer (the launch gives them a history).
+template <bool IDENT>
+__global__ void __launch_bounds__(256) temporal_accumulate_motion_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ sum,
+                                                                         const float4* __restrict__ sq, float spp, float batches,
+                                                                         const float4* __restrict__ albedo, const float4* __restrict__ nd,
+                                                                         const float4* __restrict__ prevNd, const float4* __restrict__ hist,
+                                                                         const float* __restrict__ histLen, const float4* __restrict__ motion,
+                                                                         float maxHistory, float depthTol, float normalTol,
+                                                                         float4* __restrict__ outHist, float* __restrict__ outLen) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    float4 m;
+    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
+    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
+    temporal_blend<IDENT, true>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen, motion);
+}
+
+template <bool IDENT>
+__global__ void __launch_bounds__(256) temporal_accumulate_cur_motion_kernel(int w, int h, TemporalCam cam, TemporalCam prev,
+                                                                             const float4* __restrict__ curIn, const float4* __restrict__ nd,
+                                                                             const float4* __restrict__ prevNd, const float4* __restrict__ hist,
+                                                                             const float* __restrict__ histLen, const float4* __restrict__ motion,
+                                                                             float maxHistory, float depthTol, float normalTol,
+                                                                             float4* __restrict__ outHist, float* __restrict__ outLen) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    const float4 cur = curIn[p];
+    if (!(cur.w >= 0.0f)) { outHist[p] = make_float4(cur.x, cur.y, cur.z, -1.0f); outLen[p] = 0.0f; return; }
+    temporal_blend<IDENT, true>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen, motion);
+}
+
 static int tp_fail(int code, const char* fn, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
     char buf[256];
     const int n = snprintf(buf, sizeof(buf), "%s: ", fn);
@@ -260,15 +308,30 @@ static int check_temporal_cur_args(int w, int h, const pt_camera* cam, const pt_
     return check_history_args(fn, w, h, cam, prev, cur && nd, prevNd, hist, histLen, P, outHist, outLen);
 }
 
+// What a motion buffer adds (pt_temporal_accumulate_motion, _cur_motion): outputs that leave it alone.
+static int check_motion_args(const char* fn, int w, int h, const void* motion, const void* outHist, const void* outLen) {
+    if (!motion) return 0;
+    const size_t n = (size_t)w * h;
+    if (overlaps(outHist, n * 16, motion, n * 16) || overlaps(outLen, n * 4, motion, n * 16)) return tp_fail(-1, fn, "the outputs must not alias the motion buffer");
+    return 0;
+}
+
 static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* sum, const float4* sq, int spp, int batches,
                            const float4* albedo, const float4* nd, const float4* prevNd, const float4* hist, const float* histLen,
-                           const pt_temporal_params& P, float4* outHist, float* outLen, hipStream_t stream, const int32_t* tileLive = nullptr) {
+                           const pt_temporal_params& P, float4* outHist, float* outLen, hipStream_t stream, const int32_t* tileLive = nullptr,
+                           const float4* motion = nullptr) {
     const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
     const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
     if (tileLive)                                             // (check_live_args: the identity path, with a history)
         hipLaunchKernelGGL(temporal_accumulate_live_kernel, grid, dim3(256), 0, stream, w, h, (w + 7) / 8, tileLive, sum, sq, (float)spp, (float)batches,
                            albedo, nd, prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else if (motion && hist && ident)                         // (without a history the base kernel: the buffer is not read)
+        hipLaunchKernelGGL(temporal_accumulate_motion_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo,
+                           nd, prevNd, hist, histLen, motion, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else if (motion && hist)
+        hipLaunchKernelGGL(temporal_accumulate_motion_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo,
+                           nd, prevNd, hist, histLen, motion, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
     else if (ident)
         hipLaunchKernelGGL(temporal_accumulate_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
                            prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
@@ -281,11 +344,17 @@ static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* 
 
 static int temporal_cur_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* cur, const float4* nd, const float4* prevNd,
                                const float4* hist, const float* histLen, const pt_temporal_params& P, float4* outHist, float* outLen,
-                               hipStream_t stream) {
+                               hipStream_t stream, const float4* motion = nullptr) {
     const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
     const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
-    if (ident)
+    if (motion && hist && ident)
+        hipLaunchKernelGGL(temporal_accumulate_cur_motion_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen, motion,
+                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else if (motion && hist)
+        hipLaunchKernelGGL(temporal_accumulate_cur_motion_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen, motion,
+                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
+    else if (ident)
         hipLaunchKernelGGL(temporal_accumulate_cur_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen,
                            (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
     else
@@ -321,16 +390,19 @@ int pt_temporal_accumulate_device(int w, int h, const pt_camera* cam, const pt_c
                            (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream);
 }
 
-// The host forms of pt_temporal_accumulate and pt_temporal_accumulate_live (tileLive NULL: the former).
+// The host forms of pt_temporal_accumulate, pt_temporal_accumulate_live (tileLive set) and pt_temporal_accumulate_motion (motion set).
 static int temporal_host(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum,
                          int spp, int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
-                         const float* hist_len, const int32_t* tileLive, const pt_temporal_params& P, float* out_hist, float* out_hist_len) {
+                         const float* hist_len, const int32_t* tileLive, const pt_temporal_params& P, float* out_hist, float* out_hist_len,
+                         const float* motion = nullptr) {
     const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
     const bool first = hist == nullptr;
+    if (first) motion = nullptr;                              // (not read without a history)
+    const size_t tbp = tileLive ? (tb + 15) & ~(size_t)15 : 0;
     char* d = nullptr;
-    TP_HIP_OK(hipMalloc(&d, 7 * b16 + 2 * b4 + (tileLive ? tb : 0)));
+    TP_HIP_OK(hipMalloc(&d, 7 * b16 + 2 * b4 + tbp + (motion ? b16 : 0)));
     char* dS = d; char* dQ = dS + b16; char* dA = dQ + b16; char* dN = dA + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16;
-    char* dHL = dO + b16; char* dOL = dHL + b4; char* dT = dOL + b4;
+    char* dHL = dO + b16; char* dOL = dHL + b4; char* dT = dOL + b4; char* dM = dT + tbp;
     hipError_t e = hipMemcpy(dS, rgba_sum, b16, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, b16, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dA, albedo, b16, hipMemcpyHostToDevice);
@@ -339,12 +411,14 @@ static int temporal_host(const char* fn, int w, int h, const pt_camera* cam, con
     if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
     if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && tileLive) e = hipMemcpy(dT, tileLive, tb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && motion) e = hipMemcpy(dM, motion, b16, hipMemcpyHostToDevice);
     int r = 0;
     if (e != hipSuccess) {
         r = tp_fail(-2, fn, "upload failed");
     } else if ((r = temporal_launch(w, h, cam, cam_prev, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN,
                                     first ? nullptr : (const float4*)dPN, first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P,
-                                    (float4*)dO, (float*)dOL, nullptr, tileLive ? (const int32_t*)dT : nullptr)) == 0) {
+                                    (float4*)dO, (float*)dOL, nullptr, tileLive ? (const int32_t*)dT : nullptr,
+                                    motion ? (const float4*)dM : nullptr)) == 0) {
         e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) r = tp_fail(-2, fn, "download failed");
@@ -394,6 +468,37 @@ int pt_temporal_accumulate_live(int w, int h, const pt_camera* cam, const pt_cam
                          hist, hist_len, tile_live, P, out_hist, out_hist_len);
 }
 
+// The host forms of pt_temporal_accumulate_cur and pt_temporal_accumulate_cur_motion (motion set).
+static int temporal_cur_host(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
+                             const float* prev_normal_depth, const float* hist, const float* hist_len, const float* motion,
+                             const pt_temporal_params& P, float* out_hist, float* out_hist_len) {
+    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
+    const bool first = hist == nullptr;
+    if (first) motion = nullptr;                              // (not read without a history)
+    char* d = nullptr;
+    TP_HIP_OK(hipMalloc(&d, 5 * b16 + 2 * b4 + (motion ? b16 : 0)));
+    char* dC = d; char* dN = dC + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16; char* dHL = dO + b16; char* dOL = dHL + b4;
+    char* dM = dOL + b4;
+    hipError_t e = hipMemcpy(dC, cur, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && motion) e = hipMemcpy(dM, motion, b16, hipMemcpyHostToDevice);
+    int r = 0;
+    if (e != hipSuccess) {
+        r = tp_fail(-2, fn, "upload failed");
+    } else if ((r = temporal_cur_launch(w, h, cam, cam_prev, (const float4*)dC, (const float4*)dN, first ? nullptr : (const float4*)dPN,
+                                        first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P, (float4*)dO, (float*)dOL,
+                                        nullptr, motion ? (const float4*)dM : nullptr)) == 0) {
+        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) r = tp_fail(-2, fn, "download failed");
+    }
+    (void)hipFree(d);
+    return r;
+}
+
 int pt_temporal_accumulate_cur_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur, const void* d_normal_depth,
                                       const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len, const pt_temporal_params* params,
                                       void* d_out_hist, void* d_out_hist_len, void* stream) {
@@ -412,28 +517,64 @@ int pt_temporal_accumulate_cur(int w, int h, const pt_camera* cam, const pt_came
     pt_temporal_params P;
     if (params) P = *params; else pt_temporal_defaults(&P);
     if (int r = check_temporal_cur_args(w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, P, out_hist, out_hist_len)) return r;
-    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
-    const bool first = hist == nullptr;
-    char* d = nullptr;
-    TP_HIP_OK(hipMalloc(&d, 5 * b16 + 2 * b4));
-    char* dC = d; char* dN = dC + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16; char* dHL = dO + b16; char* dOL = dHL + b4;
-    hipError_t e = hipMemcpy(dC, cur, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = tp_fail(-2, "pt_temporal_accumulate_cur", "upload failed");
-    } else if ((r = temporal_cur_launch(w, h, cam, cam_prev, (const float4*)dC, (const float4*)dN, first ? nullptr : (const float4*)dPN,
-                                        first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P, (float4*)dO, (float*)dOL,
-                                        nullptr)) == 0) {
-        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = tp_fail(-2, "pt_temporal_accumulate_cur", "download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    return temporal_cur_host("pt_temporal_accumulate_cur", w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, nullptr, P, out_hist,
+                             out_hist_len);
+}
+
+// ---- with a motion buffer (pt_render_motion): motion NULL is the base function ----------------------------------------------------
+int pt_temporal_accumulate_motion_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum, const void* d_sq_sum,
+                                         int spp, int batches, const void* d_albedo, const void* d_normal_depth, const void* d_prev_normal_depth,
+                                         const void* d_hist, const void* d_hist_len, const void* d_motion, const pt_temporal_params* params,
+                                         void* d_out_hist, void* d_out_hist_len, void* stream) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_args(w, h, cam, cam_prev, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, d_prev_normal_depth, d_hist,
+                                    d_hist_len, P, d_out_hist, d_out_hist_len))
+        return r;
+    if (int r = check_motion_args("pt_temporal_accumulate_motion", w, h, d_motion, d_out_hist, d_out_hist_len)) return r;
+    return temporal_launch(w, h, cam, cam_prev, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
+                           (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth, (const float4*)d_hist, (const float*)d_hist_len, P,
+                           (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream, nullptr, (const float4*)d_motion);
+}
+
+int pt_temporal_accumulate_motion(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
+                                  int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
+                                  const float* hist_len, const float* motion, const pt_temporal_params* params, float* out_hist,
+                                  float* out_hist_len) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
+                                    out_hist, out_hist_len))
+        return r;
+    if (int r = check_motion_args("pt_temporal_accumulate_motion", w, h, motion, out_hist, out_hist_len)) return r;
+    return temporal_host("pt_temporal_accumulate_motion", w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth,
+                         hist, hist_len, nullptr, P, out_hist, out_hist_len, motion);
+}
+
+int pt_temporal_accumulate_cur_motion_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur,
+                                             const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len,
+                                             const void* d_motion, const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len,
+                                             void* stream) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, d_cur, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, P, d_out_hist,
+                                        d_out_hist_len))
+        return r;
+    if (int r = check_motion_args("pt_temporal_accumulate_cur_motion", w, h, d_motion, d_out_hist, d_out_hist_len)) return r;
+    return temporal_cur_launch(w, h, cam, cam_prev, (const float4*)d_cur, (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth,
+                               (const float4*)d_hist, (const float*)d_hist_len, P, (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream,
+                               (const float4*)d_motion);
+}
+
+int pt_temporal_accumulate_cur_motion(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
+                                      const float* prev_normal_depth, const float* hist, const float* hist_len, const float* motion,
+                                      const pt_temporal_params* params, float* out_hist, float* out_hist_len) {
+    pt_temporal_params P;
+    if (params) P = *params; else pt_temporal_defaults(&P);
+    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, P, out_hist, out_hist_len)) return r;
+    if (int r = check_motion_args("pt_temporal_accumulate_cur_motion", w, h, motion, out_hist, out_hist_len)) return r;
+    return temporal_cur_host("pt_temporal_accumulate_cur_motion", w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, motion, P,
+                             out_hist, out_hist_len);
 }
 
 }  // extern "C"

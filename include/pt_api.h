@@ -497,8 +497,9 @@ int pt_denoise_var_device(int w, int h, const void* d_rgba_sum, const void* d_sq
                           void* stream);                                                                          /* async */
 
 /* ---- temporal accumulation with reprojection (the history stage of SVGF: Schied et al., HPG 2017) ------------------
- * Two opt-in post-processes on buffers, stateless like pt_denoise*: the caller keeps the history between frames. The scene is
- * static; only the camera moves. One sample count per frame is assumed: the history length N counts FRAMES, not samples.
+ * Two opt-in post-processes on buffers, stateless like pt_denoise*: the caller keeps the history between frames. In these two the
+ * scene is static and only the camera moves; the _motion forms (below, "motion") take a buffer that says where the surfaces of a
+ * scene updated in place were before. One sample count per frame is assumed: the history length N counts FRAMES, not samples.
  *
  * The history: hist is w*h float4 = (e.r, e.g, e.b, V) in pt_denoise_var's working format: e the albedo-demodulated mean
  * radiance, V the variance of that mean; V = -1 marks a PASS-THROUGH pixel, whose rgb holds the raw mean m. hist_len is w*h
@@ -717,11 +718,24 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  * pt_preview_reset does: the frame equals the first frame of a fresh session on a fresh scene of the new arrays, bit for bit.
  * keep_history 1 accumulates through the public entry points as usual: the previous guide is the old geometry's, a camera
  * whose 112 bytes are unchanged takes pt_temporal_accumulate's identity path, whose tap is still validated by depth and
- * normal, and the frame equals that chain of host calls bit for bit. Motion vectors for moving surfaces are out of scope: a
+ * normal, and the frame equals that chain of host calls bit for bit. Without motion vectors (MOTION below, off by default) a
  * surface that moved keeps its history only where depth and normal still agree at the same pixel. A session also remembers
  * pt_scene_generation from its last good frame (from create before the first): if the generation differs at pt_preview_frame
  * and this call was not made since that frame, the session behaves as if it had been made with keep_history 0. The
- * announcement holds until the next good frame. -1 on a NULL session or a keep_history other than 0 or 1. */
+ * announcement holds until the next good frame. -1 on a NULL session or a keep_history other than 0 or 1.
+ *
+ * MOTION. pt_preview_set_motion(p, on): 0 (the default) is the frames above, bit for bit. The first call that turns it on allocates
+ * one w*h float4 buffer M (-2 if that fails, the state unchanged); -1 on a NULL session or a value other than 0 or 1. Changing the
+ * value does not reset the session: the guides do not depend on it. With 1, a frame is a MOTION FRAME if the session is temporal, a
+ * history exists, pt_preview_scene_changed(p, 1) was called since the last good frame, pt_scene_generation equals the last good
+ * frame's + 1 and pt_scene_has_motion(scene) is 1. Such a frame runs as above, and
+ *   - after the display-size guide pass it runs pt_render_motion_device(display camera, NULL, NULL, M); with centre guides and guide
+ *     chain 0 ONE pt_render_motion_device(display camera, A, N, M) replaces the display-size guide pass;
+ *   - its accumulation is pt_temporal_accumulate_motion_device (scale 1) or pt_temporal_accumulate_cur_motion_device (scale > 1)
+ *     with M;
+ * so it equals that chain of host calls bit for bit. aov_ms includes the motion pass and pt_preview_guide_passes counts it as one
+ * pass. Every other frame is unchanged: a generation that jumped by more than one, keep_history 0, an unannounced change, a
+ * converging frame. The failed-frame rule holds. Motion through mirrors and glass is out of scope (see pt_render_motion). */
 typedef struct pt_preview pt_preview;
 typedef struct pt_preview_params {
     int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
@@ -748,6 +762,8 @@ int  pt_preview_set_guide_chain(pt_preview* p, int max_links);             /* 0.
 int  pt_preview_guide_chain(pt_preview* p);                                /* the current value; -1 on a NULL session */
 int  pt_preview_set_guide_centre(pt_preview* p, int on);                   /* 0 or 1: centre guides for the frames that follow */
 int  pt_preview_guide_centre(pt_preview* p);                               /* the current value; -1 on a NULL session */
+int  pt_preview_set_motion(pt_preview* p, int on);                         /* 0 or 1: motion frames, see MOTION */
+int  pt_preview_motion(pt_preview* p);                                     /* the current value; -1 on a NULL session */
 int  pt_preview_guide_passes(pt_preview* p);                               /* feature-pass launches of the good frames; -1 on NULL */
 int  pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len);
 const void* pt_preview_device_rgba8(pt_preview* p);                        /* w*h*4 bytes */
@@ -968,6 +984,62 @@ int pt_scene_update_vertices(pt_scene* scene, const pt_float4* positions, int n_
 int pt_scene_update_vertices_device(pt_scene* scene, const void* d_positions, int n_positions,
                                     const void* d_normals, int n_normals, pt_bvh_build_stats* stats);
 int pt_scene_generation(pt_scene* scene);
+
+/* ---- motion: where a moved surface was, and a history stage that looks there ---------------------------------------------------
+ * PREVIOUS POSITIONS. A device-built scene keeps two device arrays of n_positions pt_float4 (32 B per vertex): the current positions
+ * and the positions before the most recent successful pt_scene_update_vertices[_device]. pt_scene_create_from_mesh uploads the
+ * positions once: there are no previous ones yet. A successful vertex update copies its positions into the spare array and the pair
+ * rotates, so a steady animation allocates nothing; a failed update touches neither. pt_scene_update_mesh keeps the new positions
+ * and drops the previous ones (the topology may have changed). A pt_scene_create scene keeps none.
+ * pt_scene_has_motion: 1 if previous positions exist (the last successful update was a vertex update), 0 otherwise, -1 on NULL.
+ *
+ * pt_render_motion: per pixel (x, y) the ray is pt_render_aovs_centre's centre ray (antiAliasJitterDist and aperture ignored, no
+ * seed, no RNG stream) and the hit its closest hit (max_t 999999). out_motion is w*h float4, scan-line, y = 0 the bottom row. In
+ * f32, every operation rounded once, left to right, nothing fused:
+ *   no hit: (0, 0, 0, 0).
+ *   STATIC, (0, 0, 0, 0): the scene has no previous positions; or, with tri the hit's original triangle index, (ia, ib, ic) its
+ *     aInd, bInd, cInd in the scene's kept triangles, A, B, C the current and A', B', C' the previous positions at those indices,
+ *     all nine floats of A, B, C compare equal (==) to those of A', B', C' (positions are finite: the builder refuses others).
+ *   MOVED otherwise: bz = 1 - u - v (the hit's barycentrics, as the attribute interpolation forms it);
+ *     P'.c = A'.c bz + B'.c u + C'.c v per component; the pixel is (P'.x, P'.y, P'.z, 1): where the point the ray hits was before
+ *     the update.
+ * out_albedo and out_normal_depth must be both NULL or both set (-1 otherwise); when set they are bit-identical, in all eight
+ * floats, to pt_render_aovs_centre(max_links = 0): one trace serves the guide and the motion. The pass is FIRST HIT ONLY: a moved
+ * object seen through a mirror or through glass reports the static mirror or pane in front of it, and so takes the path without
+ * motion. Like the other feature passes this one touches no RNG state, accumulator or counter of the scene. Arguments are checked
+ * before any HIP call: those of pt_render_aovs_centre, the guide outputs both or neither, and out_motion not NULL. */
+int pt_scene_has_motion(pt_scene* scene);
+int pt_render_motion(pt_scene* scene, const pt_camera* camera, int w, int h, float* out_albedo /* NULL ok */,
+                     float* out_normal_depth /* NULL ok */, float* out_motion);                                   /* host, blocking */
+int pt_render_motion_device(pt_scene* scene, const pt_camera* camera, int w, int h, void* d_albedo /* NULL ok */,
+                            void* d_normal_depth /* NULL ok */, void* d_motion, void* stream);                    /* async */
+
+/* pt_temporal_accumulate / pt_temporal_accumulate_cur with a motion buffer (w*h float4, as pt_render_motion writes it for the
+ * current camera). The contract is the base function's except in step 3: a pixel p with motion_p.w == 1.0f takes P = motion_p.xyz
+ * in place of origin + d z_p. The rest of step 3 is unchanged and uses the previous camera's fields (cam_prev NULL = the current
+ * camera): q = P - origin'; z_c, x', y' as written; the expected previous depth is z' = sqrtf(q . q). The identity path does not
+ * apply to such a pixel even when the cameras' 112 bytes are equal. Steps 4 and 5 are unchanged: the taps are validated against
+ * prev_normal_depth with z' and the CURRENT normal, so a surface that rotates beyond normal_tol between the frames still loses
+ * its history (a previous-normal transform is out of scope). Every other pixel is the base function bit for bit, the identity
+ * path included. motion NULL is the base function bit for bit; without a history (the first frame) motion is not read. The outputs
+ * must not overlap motion (-1); all other checks are the base function's. Host and device form are bit-identical. */
+int pt_temporal_accumulate_motion(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum,
+                                  const float* sq_sum, int spp, int batches, const float* albedo, const float* normal_depth,
+                                  const float* prev_normal_depth, const float* hist, const float* hist_len, const float* motion,
+                                  const pt_temporal_params* params, float* out_hist, float* out_hist_len);       /* host, blocking */
+int pt_temporal_accumulate_motion_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum,
+                                         const void* d_sq_sum, int spp, int batches, const void* d_albedo, const void* d_normal_depth,
+                                         const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len,
+                                         const void* d_motion, const pt_temporal_params* params, void* d_out_hist,
+                                         void* d_out_hist_len, void* stream);                                    /* async */
+int pt_temporal_accumulate_cur_motion(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur,
+                                      const float* normal_depth, const float* prev_normal_depth, const float* hist,
+                                      const float* hist_len, const float* motion, const pt_temporal_params* params, float* out_hist,
+                                      float* out_hist_len);                                                      /* host, blocking */
+int pt_temporal_accumulate_cur_motion_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur,
+                                             const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist,
+                                             const void* d_hist_len, const void* d_motion, const pt_temporal_params* params,
+                                             void* d_out_hist, void* d_out_hist_len, void* stream);              /* async */
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
  * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */

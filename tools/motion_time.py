@@ -1,0 +1,182 @@
+"""What motion vectors cost and what they buy, in one run.
+
+    python tools/motion_time.py [--w 1920 --h 1080 --reps 20 --warmup 3 --frames 20 --quality-frames 8 --ref-spp 1024
+                                 --parts pass,preview,quality --animation all|object] [--resources]
+
+(a) pass: pt_render_motion_device (motion alone, and with the guide outputs) next to pt_render_aovs_centre_device(max_links 0) on
+    the Cornell box and on the 82 k blob in the box, after one vertex update (so the scene has previous positions): HIP events
+    around each launch, median of --reps after --warmup.
+(b) preview: the animated preview of tools/update_time.py — the blob, every vertex moved through the device form before each frame,
+    render scale 1 and 2 — with motion on, next to keep_history 1 without it and keep_history 0: median wall time of update +
+    scene_changed + frame as frames per second, and the session's aov_ms.
+(c) quality: over --quality-frames such frames at 4 spp (each frame's geometry a small step further), the mean relMSE of the
+    session's `mean` against a --ref-spp pt_render of the frame's own geometry, for the same three modes, over the whole frame and
+    over the pixels whose motion.w is 1. relMSE = mean over pixels and rgb of (x - ref)^2 / (ref^2 + 1e-2), over the pixels
+    whose reference is finite. --animation object moves the blob alone, rigidly and sideways by 0.004 a frame (about three
+    pixels), in place of the displacement of every vertex: there the walls, floor and light stand still.
+--resources prints the motion kernel's registers, scratch and LDS from the code-object notes and needs no GPU. Prints one JSON line."""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+GEOMETRY = ("points", "normals", "uvs", "mesh", "lights", "materials", "textures")
+
+
+def motion_kernel_resources():
+    """{vgpr_count, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size (scratch bytes per lane), group_segment_fixed_size
+    (LDS bytes per workgroup)} of pt_motion.hip's motion_kernel, from the code-object notes of a device-only compile with the
+    Makefile's flags."""
+    csrc = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "pt_motion.s")
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S",
+                               "--cuda-device-only", "-o", out, os.path.join(csrc, "pt_motion.hip")], stderr=subprocess.DEVNULL)
+        text = open(out).read()
+    notes = text[text.index("amdhsa.kernels:"):]
+    for block in re.split(r"^  - ", notes, flags=re.M)[1:]:
+        if re.search(r"^\s*\.name:\s+_ZN2pt\d+motion_kernelE", block, flags=re.M):
+            return {k: int(v) for k, v in re.findall(
+                r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)$", block, flags=re.M)}
+    raise RuntimeError("motion_kernel is not in pt_motion.hip's code object")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--w", type=int, default=1920)
+    ap.add_argument("--h", type=int, default=1080)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--quality-frames", type=int, default=8)
+    ap.add_argument("--ref-spp", type=int, default=1024)
+    ap.add_argument("--parts", default="pass,preview,quality")
+    ap.add_argument("--animation", choices=("all", "object"), default="all", help="what moves in the quality frames")
+    ap.add_argument("--resources", action="store_true")
+    a = ap.parse_args()
+    if a.resources:
+        print(json.dumps({"motion_kernel": motion_kernel_resources()}))
+        return
+    import numpy as np
+    import torch
+    import temporal_seq as Q
+    from cudapathtracer_amd import api, scenes
+    if not torch.cuda.is_available():
+        raise SystemExit("motion_time.py needs a HIP device")
+    torch.cuda.set_device(0)
+    w, h = a.w, a.h
+    parts = a.parts.split(",")
+    med = lambda v: round(sorted(v)[len(v) // 2], 4)
+
+    def displaced(hs, phase):
+        """The scene's points with every vertex displaced a little, as tools/update_time.py displaces them: float32 [n, 4]."""
+        p = hs.array("points").view(np.float32).reshape(-1, 4).copy()
+        p[:, 2] += (0.02 * np.sin(7.0 * p[:, 0] + 3.0 * p[:, 1] + phase)).astype(np.float32)
+        return p
+
+    def host(maker, name):
+        return api.HostScene(maker(tempfile.mkdtemp(), width=w, height=h, spp=4, max_depth=8, name="mt_" + name)["config"])
+
+    res = {"w": w, "h": h, "reps": a.reps, "warmup": a.warmup}
+    cam = Q.camera(api, 0, True, w, h)
+    blob = host(scenes.blob_in_box, "blob") if ("preview" in parts or "quality" in parts or "pass" in parts) else None
+
+    if "pass" in parts:
+        buf = [torch.empty(h, w, 4, device="cuda:0") for _ in range(3)]
+        A, N, M = (b.data_ptr() for b in buf)
+        res["pass"] = {}
+        for name, hs in (("cornell", host(scenes.cornell, "cornell")), ("blob", blob)):
+            sc = api.Scene.from_mesh(hs)
+            sc.update_vertices(torch.from_numpy(displaced(hs, 1.3)).cuda())
+            assert sc.has_motion == 1
+            runs = {"aovs_centre_ms": lambda: sc.render_aovs_centre_device(cam, w, h, 0, A, N),
+                    "motion_ms": lambda: sc.render_motion_device(cam, w, h, 0, 0, M),
+                    "motion_with_guides_ms": lambda: sc.render_motion_device(cam, w, h, A, N, M)}
+            row = {"n_tris": hs.info["n_tris"]}
+            for key, run in runs.items():
+                ms = []
+                for _ in range(a.warmup + a.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record(torch.cuda.default_stream()); run(); e1.record(torch.cuda.default_stream())
+                    torch.cuda.synchronize()
+                    ms.append(e0.elapsed_time(e1))
+                row[key] = med(ms[a.warmup:])
+            row["moved_share"] = round(float((buf[2][..., 3] == 1).float().mean().item()), 4)
+            row["motion_over_centre"] = round(row["motion_ms"] / row["aovs_centre_ms"], 3)
+            row["fused_over_centre"] = round(row["motion_with_guides_ms"] / row["aovs_centre_ms"], 3)
+            res["pass"][name] = row
+            sc.close()
+
+    modes = (("motion", 1, 1), ("keep1", 1, 0), ("keep0", 0, 0))        # (name, keep_history, motion)
+    if "preview" in parts:
+        dev = [torch.from_numpy(displaced(blob, ph)).cuda() for ph in (0.0, 1.3)]
+        nf = a.warmup + a.frames
+        pvr = {}
+        for scale in (1, 2):
+            for name, keep, motion in modes:
+                sc = api.Scene.from_mesh(blob)
+                pv = api.Preview(sc, w, h).set_scale(scale).set_motion(motion)
+                wall, aov = [], []
+                for t in range(nf):
+                    t0 = time.perf_counter()
+                    sc.update_vertices(dev[t & 1])
+                    pv.scene_changed(bool(keep))
+                    pv.frame(cam, Q.SEED0 + t)
+                    wall.append(1e3 * (time.perf_counter() - t0)); aov.append(pv.stats()["aov_ms"])
+                m = med(wall[a.warmup:])
+                pvr["scale%d_%s" % (scale, name)] = {"frame_ms": m, "fps": round(1e3 / m, 1), "aov_ms": med(aov[a.warmup:])}
+                pv.close(); sc.close()
+        res["preview_blob"] = {"frames": a.frames, **pvr}
+
+    if "quality" in parts:
+        nq = a.quality_frames
+        if a.animation == "all":
+            steps = [displaced(blob, 0.15 * t) for t in range(nq)]
+        else:                                                 # the icosphere's vertices are the scene's last 10 * 4^6 + 2
+            n_blob = 10 * 4 ** 6 + 2
+            assert blob.info["n_points"] > n_blob and blob.info["n_tris"] == 20 * 4 ** 6 + 12
+            steps = []
+            for t in range(nq):
+                p = blob.array("points").view(np.float32).reshape(-1, 4).copy()
+                p[-n_blob:, 0] += np.float32(0.004 * (t + 1))
+                steps.append(p)
+        sc = api.Scene.from_mesh(blob)
+        refs, moved = [], []
+        for t in range(nq):
+            sc.update_vertices(steps[t])
+            refs.append(sc.render(cam, w, h, a.ref_spp, 8, seed=Q.REF_SEED)[0][..., :3] / np.float32(a.ref_spp))
+            moved.append(sc.render_motion(cam, w, h)[..., 3] == 1)
+            print("reference frame %d of %d" % (t + 1, nq), file=sys.stderr, flush=True)
+        sc.close()
+        qual = {"frames": nq, "ref_spp": a.ref_spp, "animation": a.animation, "moved_share": round(float(np.mean([m.mean() for m in moved])), 4)}
+        for scale in (1, 2):
+            for name, keep, motion in modes:
+                sc = api.Scene.from_mesh(blob)
+                pv = api.Preview(sc, w, h).set_scale(scale).set_motion(motion)
+                whole, part = [], []
+                for t in range(nq):
+                    sc.update_vertices(steps[t])
+                    pv.scene_changed(bool(keep))
+                    x = pv.frame(cam, Q.SEED0 + t).read(rgba8=False, hist=False, hist_len=False)["mean"][..., :3]
+                    err = ((x - refs[t]) ** 2 / (refs[t] ** 2 + 1e-2)).mean(-1)
+                    ok = np.isfinite(err)                     # (a pixel whose reference holds a NaN or an Inf sample is left out)
+                    whole.append(float(err[ok].mean()))
+                    if (moved[t] & ok).any():
+                        part.append(float(err[moved[t] & ok].mean()))
+                qual["scale%d_%s" % (scale, name)] = {"relmse": round(float(np.mean(whole)), 6), "relmse_moved": round(float(np.mean(part)), 6) if part else None,
+                                                      "relmse_last": round(whole[-1], 6)}
+                pv.close(); sc.close()
+        res["quality_blob"] = qual
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
