@@ -14,6 +14,7 @@
 
 #include "../../include/pt_api.h"
 #include "pt_params.h"
+#include "pt_feature_host.h"
 #include "pt_bvh_build.h"
 #include "xorwow_host.h"
 
@@ -1689,23 +1690,34 @@ int pt_render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int spp, 
 
 }  // extern "C"
 
-namespace pt {      // pt_aov.hip
-int aov_blocks(int nTiles, int numCU);
-hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
-                      int blocks, float4* albedo, float4* normalDepth, int32_t* spill, hipStream_t stream);
-int aov_chain_blocks(int nTiles, int numCU);
-hipError_t launch_aov_chain(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
-                            int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, int32_t* spill, hipStream_t stream);
-int aov_centre_blocks(int nTiles, int numCU);
-hipError_t launch_aov_centre(const DeviceScene& S, const CamK& cam, int w, int h, int blocks, float4* albedo, float4* normalDepth, int32_t* spill,
-                             hipStream_t stream);
-hipError_t launch_aov_centre_chain(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth,
-                                   float* links, int32_t* spill, hipStream_t stream);
-hipError_t launch_probe_centre(const CamK& cam, int n, const int* xy, float* out, hipStream_t stream);
-// pt_motion.hip
-int motion_blocks(int nTiles, int numCU);
-hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w, int h,
-                         int blocks, float4* albedo, float4* normalDepth, float4* motion, int32_t* spill, hipStream_t stream);
+// The feature passes (pt_aov.hip, pt_motion.hip; their launchers and block counts: pt_feature_host.h).
+
+// The traversal spill area of a feature pass of `blocks` workgroups: the passes' own (a render in flight on this scene keeps s->spill),
+// shared among them, since all run on the caller's stream, one after the other. NULL for a scene whose stack never leaves the LDS.
+static int feature_spill(pt_scene* s, int blocks, int32_t** spill) {
+    *spill = nullptr;
+    if (s->ds.stackSpill > 0) {
+        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
+        *spill = (int32_t*)s->aovSpill.p;
+    }
+    return 0;
+}
+
+// The host form of a feature pass: render(d) into `staging`, where d[i] is output i's slice (NULL for an output the caller left out,
+// whose slice stays reserved), then the copies to the host in order.
+struct HostOut { void* host; size_t bytes; };
+template <class Render>
+static int feature_download(DevBuf& staging, const HostOut (&out)[3], Render render) {
+    size_t total = 0;
+    for (const HostOut& o : out) total += o.bytes;
+    if (int r = staging.ensure(total)) return r;
+    void* d[3];
+    char* at = (char*)staging.p;
+    for (int i = 0; i < 3; at += out[i++].bytes) d[i] = out[i].host ? at : nullptr;
+    if (int r = render(d)) return r;
+    for (int i = 0; i < 3; i++)
+        if (out[i].host) HIP_OK(hipMemcpy(out[i].host, d[i], out[i].bytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // Argument checks of the AOV pass, all before the first HIP call (the device check comes last).
@@ -1723,12 +1735,9 @@ static int check_aov_args(pt_scene* s, const pt_camera* cam, int w, int h, int a
 }
 
 static int render_aovs(pt_scene* s, const pt_camera* cam, int w, int h, int aovSpp, uint64_t seed, void* dA, void* dN, hipStream_t stream) {
-    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = aov_blocks(nTiles, s->numCU);
-    int32_t* spill = nullptr;
-    if (s->ds.stackSpill > 0) {          // its own area: a render in flight on this scene keeps s->spill
-        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
-        spill = (int32_t*)s->aovSpill.p;
-    }
+    const int blocks = feature_blocks(feature_tiles(w, h).nTiles, s->numCU, kAovWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
     HIP_OK(launch_aov(s->ds, cam_to_kernel(*cam), (const uint32_t*)s->jump.p, seed, w, h, aovSpp, blocks, (float4*)dA, (float4*)dN, spill, stream));
     return 0;
 }
@@ -1744,12 +1753,8 @@ int pt_render_aovs_device(pt_scene* s, const pt_camera* cam, int w, int h, int a
 int pt_render_aovs(pt_scene* s, const pt_camera* cam, int w, int h, int aov_spp, uint64_t seed, float* out_albedo, float* out_normal_depth) {
     if (int r = check_aov_args(s, cam, w, h, aov_spp, out_albedo, out_normal_depth)) return r;
     const size_t bytes = (size_t)w * h * sizeof(float4);
-    if (int r = s->aovOut.ensure(2 * bytes)) return r;
-    char* d = (char*)s->aovOut.p;
-    if (int r = render_aovs(s, cam, w, h, aov_spp, seed, d, d + bytes, nullptr)) return r;
-    HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return feature_download(s->aovOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {nullptr, 0}},
+                            [&](void* const* d) { return render_aovs(s, cam, w, h, aov_spp, seed, d[0], d[1], nullptr); });
 }
 
 // The chain pass (pt_aov.hip: aov_chain_kernel): max_links, then the checks it shares with the first-hit pass, all before any HIP call.
@@ -1760,12 +1765,9 @@ static int check_aov_chain_args(pt_scene* s, const pt_camera* cam, int w, int h,
 
 static int render_aovs_chain(pt_scene* s, const pt_camera* cam, int w, int h, int aovSpp, int maxLinks, uint64_t seed, void* dA, void* dN, void* dL,
                              hipStream_t stream) {
-    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = aov_chain_blocks(nTiles, s->numCU);
-    int32_t* spill = nullptr;
-    if (s->ds.stackSpill > 0) {          // the AOV passes' own area (they share it: both run on the caller's stream, one after the other)
-        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
-        spill = (int32_t*)s->aovSpill.p;
-    }
+    const int blocks = feature_blocks(feature_tiles(w, h).nTiles, s->numCU, kAovChainWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
     HIP_OK(launch_aov_chain(s->ds, cam_to_kernel(*cam), (const uint32_t*)s->jump.p, seed, w, h, aovSpp, maxLinks, blocks, (float4*)dA, (float4*)dN,
                             (float*)dL, spill, stream));
     return 0;
@@ -1781,13 +1783,8 @@ int pt_render_aovs_chain(pt_scene* s, const pt_camera* cam, int w, int h, int ao
                          float* out_normal_depth, float* out_links) {
     if (int r = check_aov_chain_args(s, cam, w, h, aov_spp, max_links, out_albedo, out_normal_depth)) return r;
     const size_t bytes = (size_t)w * h * sizeof(float4), lbytes = (size_t)w * h * sizeof(float);
-    if (int r = s->aovOut.ensure(2 * bytes + lbytes)) return r;
-    char* d = (char*)s->aovOut.p;
-    if (int r = render_aovs_chain(s, cam, w, h, aov_spp, max_links, seed, d, d + bytes, out_links ? d + 2 * bytes : nullptr, nullptr)) return r;
-    HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
-    if (out_links) HIP_OK(hipMemcpy(out_links, d + 2 * bytes, lbytes, hipMemcpyDeviceToHost));
-    return 0;
+    return feature_download(s->aovOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_links, lbytes}},
+                            [&](void* const* d) { return render_aovs_chain(s, cam, w, h, aov_spp, max_links, seed, d[0], d[1], d[2], nullptr); });
 }
 
 // The centre pass (pt_aov.hip: aov_centre_kernel, aov_centre_chain_kernel): one unjittered pinhole ray per pixel, no seed.
@@ -1799,12 +1796,9 @@ static int check_aov_centre_args(pt_scene* s, const pt_camera* cam, int w, int h
 // max_links 0 without a links buffer is the first-hit kernel; everything else the chain kernel (bit-identical where both apply).
 static int render_aovs_centre(pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, void* dA, void* dN, void* dL, hipStream_t stream) {
     const bool chain = maxLinks > 0 || dL;
-    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = chain ? aov_chain_blocks(nTiles, s->numCU) : aov_centre_blocks(nTiles, s->numCU);
-    int32_t* spill = nullptr;
-    if (s->ds.stackSpill > 0) {          // the AOV passes' own area
-        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
-        spill = (int32_t*)s->aovSpill.p;
-    }
+    const int blocks = feature_blocks(feature_tiles(w, h).nTiles, s->numCU, chain ? kAovChainWavesPerSimd : kAovCentreWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
     if (chain) HIP_OK(launch_aov_centre_chain(s->ds, cam_to_kernel(*cam), w, h, maxLinks, blocks, (float4*)dA, (float4*)dN, (float*)dL, spill, stream));
     else HIP_OK(launch_aov_centre(s->ds, cam_to_kernel(*cam), w, h, blocks, (float4*)dA, (float4*)dN, spill, stream));
     return 0;
@@ -1820,13 +1814,8 @@ int pt_render_aovs_centre(pt_scene* s, const pt_camera* cam, int w, int h, int m
                           float* out_links) {
     if (int r = check_aov_centre_args(s, cam, w, h, max_links, out_albedo, out_normal_depth)) return r;
     const size_t bytes = (size_t)w * h * sizeof(float4), lbytes = (size_t)w * h * sizeof(float);
-    if (int r = s->aovOut.ensure(2 * bytes + lbytes)) return r;
-    char* d = (char*)s->aovOut.p;
-    if (int r = render_aovs_centre(s, cam, w, h, max_links, d, d + bytes, out_links ? d + 2 * bytes : nullptr, nullptr)) return r;
-    HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
-    if (out_links) HIP_OK(hipMemcpy(out_links, d + 2 * bytes, lbytes, hipMemcpyDeviceToHost));
-    return 0;
+    return feature_download(s->aovOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_links, lbytes}},
+                            [&](void* const* d) { return render_aovs_centre(s, cam, w, h, max_links, d[0], d[1], d[2], nullptr); });
 }
 
 // The motion pass (pt_motion.hip: motion_kernel): the centre pass's checks, the guide outputs both or neither, and the motion output.
@@ -1837,12 +1826,9 @@ static int check_motion_args(pt_scene* s, const pt_camera* cam, int w, int h, co
 }
 
 static int render_motion(pt_scene* s, const pt_camera* cam, int w, int h, void* dA, void* dN, void* dM, hipStream_t stream) {
-    const int nTiles = ((w + 7) / 8) * ((h + 7) / 8), blocks = motion_blocks(nTiles, s->numCU);
-    int32_t* spill = nullptr;
-    if (s->ds.stackSpill > 0) {          // the AOV passes' own area (they share it: all run on the caller's stream, one after the other)
-        if (int r = s->aovSpill.ensure((size_t)blocks * 4 * s->ds.stackSpill * 64 * sizeof(int32_t))) return r;
-        spill = (int32_t*)s->aovSpill.p;
-    }
+    const int blocks = feature_blocks(feature_tiles(w, h).nTiles, s->numCU, kMotionWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
     const bool moving = s->hasMotion && s->deviceLeaf >= 0;
     HIP_OK(launch_motion(s->ds, s->kTris.p, s->posCur.p, moving ? s->posPrev.p : nullptr, s->nPositions, cam_to_kernel(*cam), w, h, blocks, (float4*)dA,
                          (float4*)dN, (float4*)dM, spill, stream));
@@ -1857,15 +1843,8 @@ int pt_render_motion_device(pt_scene* s, const pt_camera* cam, int w, int h, voi
 int pt_render_motion(pt_scene* s, const pt_camera* cam, int w, int h, float* out_albedo, float* out_normal_depth, float* out_motion) {
     if (int r = check_motion_args(s, cam, w, h, out_albedo, out_normal_depth, out_motion)) return r;
     const size_t bytes = (size_t)w * h * sizeof(float4);
-    if (int r = s->motionOut.ensure(3 * bytes)) return r;
-    char* d = (char*)s->motionOut.p;
-    if (int r = render_motion(s, cam, w, h, out_albedo ? d : nullptr, out_albedo ? d + bytes : nullptr, d + 2 * bytes, nullptr)) return r;
-    if (out_albedo) {
-        HIP_OK(hipMemcpy(out_albedo, d, bytes, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(out_normal_depth, d + bytes, bytes, hipMemcpyDeviceToHost));
-    }
-    HIP_OK(hipMemcpy(out_motion, d + 2 * bytes, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return feature_download(s->motionOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_motion, bytes}},
+                            [&](void* const* d) { return render_motion(s, cam, w, h, d[0], d[1], d[2], nullptr); });
 }
 
 int pt_has_experimental(void) {

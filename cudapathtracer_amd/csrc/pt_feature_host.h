@@ -1,0 +1,41 @@
+// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip): the tiling and block count every one of
+// them is launched with, each kernel's waves per SIMD, and the launchers pt_api.hip calls. The kernels' shared pieces are in
+// pt_feature.h.
+#pragma once
+#include <algorithm>
+#include "pt_params.h"
+
+namespace pt {
+
+// One wave per 8x8 tile, tiles in row-major order.
+struct FeatureTiles { int tilesX, nTiles; };
+inline FeatureTiles feature_tiles(int w, int h) {
+    const int tilesX = (w + 7) / 8;
+    return {tilesX, tilesX * ((h + 7) / 8)};
+}
+
+// Workgroups of a feature pass: four waves each, persistent over the tiles, as many as are resident at once at the kernel's waves per
+// SIMD (= workgroups per CU). Each kernel's count comes from its own resources (the table in DESIGN.md §9):
+constexpr int kAovWavesPerSimd = 6;          // aov_kernel: 76 VGPRs (the stream seeding), 16 KB of LDS per workgroup
+constexpr int kAovChainWavesPerSimd = 6;     // aov_chain_kernel: 80 VGPRs, 23 KB of LDS: 6 workgroups are 138 of the CU's 160 KB. Also
+                                             // aov_centre_chain_kernel (69 VGPRs, 23 KB): 7 workgroups would need 161 KB
+constexpr int kAovCentreWavesPerSimd = 8;    // aov_centre_kernel: without the seeding 63 VGPRs, 8 x 16 KB of LDS
+constexpr int kMotionWavesPerSimd = 8;       // motion_kernel: 63 VGPRs, 8 x 16 KB of LDS, as the centre pass
+inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
+
+// spill (every launcher): blocks * 4 waves x S.stackSpill entries x 64 lanes, or NULL for a scene whose stack never leaves the LDS.
+// pt_aov.hip
+hipError_t launch_aov(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
+                      int blocks, float4* albedo, float4* normalDepth, int32_t* spill, hipStream_t stream);
+hipError_t launch_aov_chain(const DeviceScene& S, const CamK& cam, const uint32_t* jump, unsigned long long seed, int w, int h, int aovSpp,
+                            int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, int32_t* spill, hipStream_t stream);
+hipError_t launch_aov_centre(const DeviceScene& S, const CamK& cam, int w, int h, int blocks, float4* albedo, float4* normalDepth, int32_t* spill,
+                             hipStream_t stream);
+hipError_t launch_aov_centre_chain(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth,
+                                   float* links, int32_t* spill, hipStream_t stream);
+hipError_t launch_probe_centre(const CamK& cam, int n, const int* xy, float* out, hipStream_t stream);
+// pt_motion.hip
+hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w, int h,
+                         int blocks, float4* albedo, float4* normalDepth, float4* motion, int32_t* spill, hipStream_t stream);
+
+}  // namespace pt

@@ -2,15 +2,12 @@
 // hits WAS before the scene's most recent vertex update. pt_temporal_accumulate_motion reprojects that point in place of the one on
 // the ray, so a surface that moved finds the history it left behind.
 //
-// aov_centre_kernel's organisation (pt_aov.hip): one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over
-// the tiles, the non-counting trace_closest with the LDS stack and the scene's spill area. After the traversal the hit's original
-// triangle index names three vertex indices in the scene's kept pt_triangle array, and those name three current and three previous
-// positions: three int32 loads, then six float4 loads, all dependent on the hit, none live across the traversal. The previous
+// pt_feature.h's FeatureWave and tile loop around the centre ray, as aov_centre_kernel (pt_aov.hip). After the traversal the hit's
+// original triangle index names three vertex indices in the scene's kept pt_triangle array, and those name three current and three
+// previous positions: three int32 loads, then six float4 loads, all dependent on the hit, none live across the traversal. The previous
 // point is the barycentric sum of the previous positions with resolve_hit's weights, every operation rounded once (no fma).
-// With albedo / normalDepth set the kernel also writes aov_centre_kernel's record, from the same hit through the same functions.
-#include "pt_path.h"
-#include "pt_params.h"
-#include "pt_centre_ray.h"
+// With albedo / normalDepth set the kernel also writes first_hit_record of the same hit: aov_centre_kernel's output.
+#include "pt_feature.h"
 #include "../../include/pt_api.h"
 
 namespace pt {
@@ -24,25 +21,19 @@ struct MotionSrc {
     int nPos;
 };
 
-// spill: (gridDim.x * 4) waves x S.stackSpill entries x 64 lanes, the lane-interleaved layout of Stack.
 __global__ void __launch_bounds__(256) motion_kernel(DeviceScene S, MotionSrc M, CamK cam, int w, int h, int tilesX, int nTiles,
                                                      float4* __restrict__ albedo, float4* __restrict__ normalDepth, float4* __restrict__ motion,
                                                      int32_t* spill) {
     __shared__ int32_t ldsStack[4][kStackLds][64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gw = blockIdx.x * 4 + wave;
-    Stack<kStackLds> st; st.lds = (lds_i32*)&ldsStack[wave][0][0] + lane; st.sp = 0;
-    st.spill = spill ? spill + (size_t)gw * S.stackSpill * 64 + lane : nullptr;
-    SceneCache C; C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
-    Ctr c = {};
-    for (int tile = gw; tile < nTiles; tile += gridDim.x * 4) {
-        const int x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
-        if (!(x < w && y < h)) continue;
-        const size_t idx = (size_t)y * w + x;
+    FeatureWave W(ldsStack, S, spill);
+    for (int tile = W.gw; tile < nTiles; tile += gridDim.x * 4) {
+        const TilePixel p = tile_pixel(tile, tilesX, W.lane, w, h);
+        if (!p.inside) continue;
+        const size_t idx = (size_t)p.y * w + p.x;
         V3 o, d;
-        camera_ray_centre(cam, x, y, o, d);
+        camera_ray_centre(cam, p.x, p.y, o, d);
         Hit hit;
-        trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+        trace_closest<false, kStackLds>(S, W.C, o, d, 999999.0f, W.st, hit, W.c);
         float4 om = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (hit.tri >= 0 && M.prev != nullptr) {
             const pt_triangle& T = M.tris[hit.tri];
@@ -61,31 +52,21 @@ __global__ void __launch_bounds__(256) motion_kernel(DeviceScene S, MotionSrc M,
             }
         }
         motion[idx] = om;
-        if (albedo != nullptr) {                                   // (uniform: a kernel argument) aov_centre_kernel's record
+        if (albedo != nullptr) {                                   // (uniform: a kernel argument)
             float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
-            if (hit.tri >= 0) {
-                HitInfo hi; resolve_hit(S, hit, o, d, hi);
-                V3 a; float trans;
-                material_inputs(S.mats[hi.material], S.textures, hi.uvx, hi.uvy, true, a, trans);
-                oa = make_float4(a.x, a.y, a.z, 1.0f);
-                on = make_float4(hi.normal.x, hi.normal.y, hi.normal.z, hit.t);
-            }
+            if (hit.tri >= 0) { HitInfo hi; resolve_hit(S, hit, o, d, hi); first_hit_record(S, hi, hit.t, oa, on); }
             albedo[idx] = oa;
             normalDepth[idx] = on;
         }
     }
 }
 
-// Workgroups of the motion pass: its own count, from its own resources (see the compile's line in DESIGN.md §19).
-constexpr int kMotionWavesPerSimd = 8;
-int motion_blocks(int nTiles, int numCU) { return std::max(1, std::min((nTiles + 3) / 4, numCU * kMotionWavesPerSimd)); }
-
 hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w, int h,
                          int blocks, float4* albedo, float4* normalDepth, float4* motion, int32_t* spill, hipStream_t stream) {
-    const int tilesX = (w + 7) / 8, nTiles = tilesX * ((h + 7) / 8);
+    const FeatureTiles T = feature_tiles(w, h);
     MotionSrc M;
     M.tris = (const pt_triangle*)tris; M.cur = (const float4*)posCur; M.prev = (const float4*)posPrev; M.nPos = nPos;
-    hipLaunchKernelGGL(motion_kernel, dim3(blocks), dim3(256), 0, stream, S, M, cam, w, h, tilesX, nTiles, albedo, normalDepth, motion, spill);
+    hipLaunchKernelGGL(motion_kernel, dim3(blocks), dim3(256), 0, stream, S, M, cam, w, h, T.tilesX, T.nTiles, albedo, normalDepth, motion, spill);
     return hipGetLastError();
 }
 

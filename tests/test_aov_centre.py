@@ -188,3 +188,55 @@ def test_the_scaled_cameras_guide_is_a_subsample(api, gpu_ready, s):
         assert_bits_equal(oA.cpu().numpy(), gA, "device form, albedo"); assert_bits_equal(oN.cpu().numpy(), gN, "device form, normal + depth")
         assert_bits_equal(dA.cpu().numpy(), A, "the input is left as it was")
     gs.close()
+
+
+# ---- 6. more tiles than resident waves, on a scene that spills ------------------------------------------------------------------------
+def test_a_waves_second_tile_on_a_scene_that_spills(api, gpu_ready, scene_dir):
+    """Every size above is a few tiles, so no wave there takes a second one. Here the frame has more tiles than the widest launch of
+    the feature kernels has waves (8 per SIMD, 4 SIMDs per CU), on a tree deep enough to use the spill area: the kernels' stack and
+    spill slice must serve a wave's second tile as they served its first. The four AOV kernels are tied to each other through
+    cam0, the motion kernel to the centre pass, and the centre pass to pt_probe_trace_closest, which shares none of their set-up."""
+    from cudapathtracer_amd import scenes
+    from test_scene_update import _moved
+    num_cu = gpu_ready.cuda.get_device_properties(0).multi_processor_count
+    w = 1021                                                 # 128 tile columns, the last one partial
+    h = (num_cu * 8 * 4 // 128 + 1) * 8 + 3                  # ... and one tile row more than the waves cover, then a partial one
+    tiles = ((w + 7) // 8) * ((h + 7) // 8)
+    assert tiles > num_cu * 8 * 4
+    hs = api.HostScene(scenes.blob_in_box(os.path.join(scene_dir, "aov_trip_blob"), w, h, 2, 5, subdiv=4, name="aov_trip_blob")["config"])
+    assert hs.info["n_tris"] == 20 * 4 ** 4 + 12             # the shell's 12 triangles, then the blob's
+    sc = api.Scene.from_mesh(hs)
+    assert not sc.flags()["onchip"]                          # a scene in HBM, with a spill area
+    sc.update_vertices(_moved(hs, "displace")["points"])
+    assert sc.has_motion == 1 and not sc.flags()["onchip"]
+    cam = api.Camera.frombytes(hs.camera().tobytes())
+    cam.antiAliasJitterDist = 1.0
+    cam.aperture = 0.05
+    cam0 = _cam0(api, cam)
+    seed = SEEDS[0]
+    # (a) the centre kernels equal the jittered kernels handed cam0
+    for links in (0, 4):
+        got = sc.render_aovs_centre(cam, w, h, links, links=True)
+        want = sc.render_aovs_chain(cam0, w, h, links, aov_spp=1, seed=seed, links=True)
+        for g, x, what in zip(got, want, ("albedo", "normal + depth", "links")):
+            assert_bits_equal(g, x, "%d x %d, max_links %d: %s" % (w, h, links, what))
+    first = sc.render_aovs_centre(cam, w, h)
+    want = sc.render_aovs(cam0, w, h, aov_spp=1, seed=seed)
+    assert_bits_equal(first[0], want[0], "first hit, albedo"); assert_bits_equal(first[1], want[1], "first hit, normal + depth")
+    # (b) the motion kernel's guides are the centre pass, and the motion is the same without them
+    A, N, mv = sc.render_motion(cam, w, h, guides=True)
+    assert_bits_equal(A, first[0], "motion: albedo"); assert_bits_equal(N, first[1], "motion: normal_depth")
+    assert_bits_equal(sc.render_motion(cam, w, h), mv, "motion without the guide outputs")
+    assert (mv[-16:, :, 3] == 1).any()
+    # (c) coverage and depth against the probe, over the first and the last 16 rows (the last ones are second tiles)
+    rows = list(range(16)) + list(range(h - 16, h))
+    xy = np.array([(x, y) for y in rows for x in range(w)], np.int32)
+    gi, gf, _ = sc.trace_closest(api.probe_centre_rays(cam, xy))
+    valid, t = (gi[:, 0] == 1).reshape(32, w), gf[:, 0].reshape(32, w)
+    cov, depth = first[0][rows, :, 3], first[1][rows, :, 3]
+    assert_bits_equal(cov, valid.astype(np.float32), "coverage")
+    assert_bits_equal(depth, np.where(valid, t, np.float32(0.0)).astype(np.float32), "depth")
+    # (d) ... and the last rows are not empty, nor all blob
+    shell = valid & (gi[:, 1].reshape(32, w) < 12)
+    assert valid[16:].any() and ((~valid[16:]).any() or shell[16:].any())
+    sc.close()

@@ -16,34 +16,18 @@ with --max-links (`aov_centre_chain`) next to the jittered `aov` and `aov_chain`
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
 import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 
 def aov_kernel_resources():
-    """{kernel: {vgpr_count, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size (scratch bytes per lane),
-    group_segment_fixed_size (LDS bytes per workgroup)}} of pt_aov.hip's feature-pass kernels (jittered and centre), from the code-object notes of a device-only
-    compile with the Makefile's flags."""
-    csrc = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "pt_aov.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S",
-                               "--cuda-device-only", "-o", out, os.path.join(csrc, "pt_aov.hip")], stderr=subprocess.DEVNULL)
-        text = open(out).read()
-    res = {}
-    notes = text[text.index("amdhsa.kernels:"):]
-    for block in re.split(r"^  - ", notes, flags=re.M)[1:]:            # one list item per kernel; its keys come in alphabetical order
-        name = re.search(r"^\s*\.name:\s+_ZN2pt\d+(aov\w*?_kernel)E", block, flags=re.M)
-        if name:
-            res[name.group(1)] = {k: int(v) for k, v in re.findall(
-                r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)$", block, flags=re.M)}
-    return res
+    """kernel_resources.kernel_resources of pt_aov.hip's feature-pass kernels (jittered and centre), by kernel name."""
+    from kernel_resources import kernel_resources
+    return kernel_resources("pt_aov", r"(aov\w*?_kernel)")
 
 
 def main():

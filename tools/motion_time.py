@@ -18,34 +18,20 @@
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
 import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 GEOMETRY = ("points", "normals", "uvs", "mesh", "lights", "materials", "textures")
 
 
 def motion_kernel_resources():
-    """{vgpr_count, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size (scratch bytes per lane), group_segment_fixed_size
-    (LDS bytes per workgroup)} of pt_motion.hip's motion_kernel, from the code-object notes of a device-only compile with the
-    Makefile's flags."""
-    csrc = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "pt_motion.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-S",
-                               "--cuda-device-only", "-o", out, os.path.join(csrc, "pt_motion.hip")], stderr=subprocess.DEVNULL)
-        text = open(out).read()
-    notes = text[text.index("amdhsa.kernels:"):]
-    for block in re.split(r"^  - ", notes, flags=re.M)[1:]:
-        if re.search(r"^\s*\.name:\s+_ZN2pt\d+motion_kernelE", block, flags=re.M):
-            return {k: int(v) for k, v in re.findall(
-                r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)$", block, flags=re.M)}
-    raise RuntimeError("motion_kernel is not in pt_motion.hip's code object")
+    """kernel_resources.kernel_resources of pt_motion.hip's motion_kernel: the one kernel's dict."""
+    from kernel_resources import kernel_resources
+    return kernel_resources("pt_motion", "(motion_kernel)")["motion_kernel"]
 
 
 def main():
