@@ -1135,21 +1135,44 @@ def _history_arrays(what, shape, prev_normal_depth, hist, hist_len):
     return PN, H, np.ascontiguousarray(hist_len)
 
 
+_SUMS = ("rgba_sum", "sq_sum", "albedo", "normal_depth")
+_CUR = ("cur", "normal_depth")
+
+
+def _temporal_host(what, camera, camera_prev, names, frames, sums, history, params, motion=None, tile_live=None):
+    """The host form pt_<what>: `frames` are its [h, w, 4] arrays in the order of the C arguments, called `names` in the messages; the
+    (spp, batches) of `sums` follow the first two of them. `motion` and `tile_live` are (array or None,) for an entry that takes one."""
+    arrs = _f4_frames(what, tuple(zip(names, frames)))
+    h, w = arrs[0].shape[:2]
+    extra = list(_history_arrays(what, arrs[0].shape, *history))
+    if motion is not None:
+        extra.append(None if motion[0] is None else _f4_frames(what, (("motion", motion[0]),), arrs[0].shape)[0])
+    if tile_live is not None:
+        extra.append(None if tile_live[0] is None else _tile_map(what, tile_live[0], h, w))
+    out, out_len = np.empty_like(arrs[0]), np.empty((h, w), np.float32)
+    p = _temporal_params(*params)
+    args = [_p(a) for a in arrs[:2]] + [int(v) for v in sums] + [_p(a) for a in arrs[2:] + extra]
+    _check(getattr(lib(), "pt_" + what)(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, *args, C.byref(p),
+                                        _p(out), _p(out_len)), "pt_" + what)
+    return out, out_len
+
+
+def _temporal_device(what, w, h, camera, camera_prev, frame, optional, outputs, params, stream):
+    """The device form pt_<what>_device: `frame` are this frame's arguments in C order, `optional` the pointers that may be 0 / None
+    (the history triple, then the motion buffer or the tile map)."""
+    p = _temporal_params(*params)
+    _check(getattr(lib(), "pt_%s_device" % what)(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, *frame,
+                                                 *(x or None for x in optional), C.byref(p), *outputs, stream or None), "pt_%s_device" % what)
+
+
 def temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None,
                         hist_len=None, max_history=None, depth_tol=None, normal_tol=None):
     """pt_temporal_accumulate (host, blocking): blend this frame (render_moments' sums, render_aovs' buffers) into the history
     reprojected from the previous camera. prev_normal_depth, hist ([h,w,4] float32) and hist_len ([h,w] float32) are all None on
     the first frame. camera_prev None = the camera did not move. Returns new (hist, hist_len); the inputs are left untouched.
     A None parameter takes the library default (temporal_defaults())."""
-    S, Q, A, N = _f4_frames("temporal_accumulate", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
-    h, w = S.shape[:2]
-    PN, H, HL = _history_arrays("temporal_accumulate", S.shape, prev_normal_depth, hist, hist_len)
-    out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q), int(spp),
-                                        int(batches), _p(A), _p(N), _p(PN), _p(H), _p(HL), C.byref(p), _p(out), _p(out_len)),
-           "pt_temporal_accumulate")
-    return out, out_len
+    return _temporal_host("temporal_accumulate", camera, camera_prev, _SUMS, (rgba_sum, sq_sum, albedo, normal_depth), (spp, batches),
+                          (prev_normal_depth, hist, hist_len), (max_history, depth_tol, normal_tol))
 
 
 def temporal_accumulate_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr,
@@ -1157,15 +1180,10 @@ def temporal_accumulate_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_s
                                depth_tol=None, normal_tol=None, stream=0):
     """pt_temporal_accumulate_device: device buffers (w*h float4; the two lengths w*h float), asynchronous on `stream`, no
     workspace. The three history pointers are 0 / None on the first frame; the outputs must not alias the input history."""
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, d_rgba_sum_ptr,
-                                               d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
-                                               d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None, C.byref(p),
-                                               d_out_hist_ptr, d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_device")
-
-
-def _motion_array(what, motion, shape):
-    return None if motion is None else _f4_frames(what, (("motion", motion),), shape)[0]
+    _temporal_device("temporal_accumulate", w, h, camera, camera_prev,
+                     (d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr),
+                     (d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr), (d_out_hist_ptr, d_out_hist_len_ptr),
+                     (max_history, depth_tol, normal_tol), stream)
 
 
 def temporal_accumulate_motion(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None,
@@ -1173,56 +1191,34 @@ def temporal_accumulate_motion(camera, rgba_sum, sq_sum, spp, batches, albedo, n
     """pt_temporal_accumulate_motion (host, blocking): temporal_accumulate with Scene.render_motion's buffer for this camera: a pixel
     whose motion.w is 1 reprojects motion.xyz, where its surface point was, and never takes the identity path. motion None is
     temporal_accumulate bit for bit. Returns new (hist, hist_len)."""
-    what = "temporal_accumulate_motion"
-    S, Q, A, N = _f4_frames(what, (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
-    h, w = S.shape[:2]
-    PN, H, HL = _history_arrays(what, S.shape, prev_normal_depth, hist, hist_len)
-    M = _motion_array(what, motion, S.shape)
-    out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_motion(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q),
-                                               int(spp), int(batches), _p(A), _p(N), _p(PN), _p(H), _p(HL), _p(M), C.byref(p), _p(out),
-                                               _p(out_len)), "pt_temporal_accumulate_motion")
-    return out, out_len
+    return _temporal_host("temporal_accumulate_motion", camera, camera_prev, _SUMS, (rgba_sum, sq_sum, albedo, normal_depth), (spp, batches),
+                          (prev_normal_depth, hist, hist_len), (max_history, depth_tol, normal_tol), motion=(motion,))
 
 
 def temporal_accumulate_motion_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr,
                                       d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_motion_ptr, d_out_hist_ptr, d_out_hist_len_ptr,
                                       max_history=None, depth_tol=None, normal_tol=None, stream=0):
     """pt_temporal_accumulate_motion_device: temporal_accumulate_device plus the device motion buffer (0 / None: none)."""
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_motion_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
-                                                      d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
-                                                      d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None,
-                                                      d_motion_ptr or None, C.byref(p), d_out_hist_ptr, d_out_hist_len_ptr, stream or None),
-           "pt_temporal_accumulate_motion_device")
+    _temporal_device("temporal_accumulate_motion", w, h, camera, camera_prev,
+                     (d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr),
+                     (d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_motion_ptr), (d_out_hist_ptr, d_out_hist_len_ptr),
+                     (max_history, depth_tol, normal_tol), stream)
 
 
 def temporal_accumulate_cur_motion(camera, cur, normal_depth, camera_prev=None, prev_normal_depth=None, hist=None, hist_len=None, motion=None,
                                    max_history=None, depth_tol=None, normal_tol=None):
     """pt_temporal_accumulate_cur_motion (host, blocking): temporal_accumulate_cur with a motion buffer, as temporal_accumulate_motion."""
-    what = "temporal_accumulate_cur_motion"
-    E, N = _f4_frames(what, (("cur", cur), ("normal_depth", normal_depth)))
-    h, w = E.shape[:2]
-    PN, H, HL = _history_arrays(what, E.shape, prev_normal_depth, hist, hist_len)
-    M = _motion_array(what, motion, E.shape)
-    out, out_len = np.empty_like(E), np.empty((h, w), np.float32)
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_cur_motion(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(E), _p(N),
-                                                   _p(PN), _p(H), _p(HL), _p(M), C.byref(p), _p(out), _p(out_len)),
-           "pt_temporal_accumulate_cur_motion")
-    return out, out_len
+    return _temporal_host("temporal_accumulate_cur_motion", camera, camera_prev, _CUR, (cur, normal_depth), (),
+                          (prev_normal_depth, hist, hist_len), (max_history, depth_tol, normal_tol), motion=(motion,))
 
 
 def temporal_accumulate_cur_motion_device(w, h, camera, camera_prev, d_cur_ptr, d_normal_depth_ptr, d_prev_normal_depth_ptr, d_hist_ptr,
                                           d_hist_len_ptr, d_motion_ptr, d_out_hist_ptr, d_out_hist_len_ptr, max_history=None, depth_tol=None,
                                           normal_tol=None, stream=0):
     """pt_temporal_accumulate_cur_motion_device: temporal_accumulate_cur_device plus the device motion buffer (0 / None: none)."""
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_cur_motion_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
-                                                          d_cur_ptr, d_normal_depth_ptr, d_prev_normal_depth_ptr or None, d_hist_ptr or None,
-                                                          d_hist_len_ptr or None, d_motion_ptr or None, C.byref(p), d_out_hist_ptr,
-                                                          d_out_hist_len_ptr, stream or None), "pt_temporal_accumulate_cur_motion_device")
+    _temporal_device("temporal_accumulate_cur_motion", w, h, camera, camera_prev, (d_cur_ptr, d_normal_depth_ptr),
+                     (d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_motion_ptr), (d_out_hist_ptr, d_out_hist_len_ptr),
+                     (max_history, depth_tol, normal_tol), stream)
 
 
 def _tile_map(what, tile_live, h, w):
@@ -1237,28 +1233,18 @@ def temporal_accumulate_live(camera, rgba_sum, sq_sum, spp, batches, albedo, nor
     """pt_temporal_accumulate_live (host, blocking): temporal_accumulate for a resting camera with a map of live tiles (int32
     [ceil(h/8), ceil(w/8)], as temporal_select returns it; None = every tile live). A tile whose entry is 0 keeps its history and
     length bit for bit; the others blend this frame in. camera_prev must be None or equal to camera. Returns new (hist, hist_len)."""
-    S, Q, A, N = _f4_frames("temporal_accumulate_live", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
-    h, w = S.shape[:2]
-    PN, H, HL = _history_arrays("temporal_accumulate_live", S.shape, prev_normal_depth, hist, hist_len)
-    T = _tile_map("temporal_accumulate_live", tile_live, h, w) if tile_live is not None else None
-    out, out_len = np.empty_like(S), np.empty((h, w), np.float32)
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_live(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(S), _p(Q),
-                                             int(spp), int(batches), _p(A), _p(N), _p(PN), _p(H), _p(HL), _p(T), C.byref(p), _p(out),
-                                             _p(out_len)), "pt_temporal_accumulate_live")
-    return out, out_len
+    return _temporal_host("temporal_accumulate_live", camera, camera_prev, _SUMS, (rgba_sum, sq_sum, albedo, normal_depth), (spp, batches),
+                          (prev_normal_depth, hist, hist_len), (max_history, depth_tol, normal_tol), tile_live=(tile_live,))
 
 
 def temporal_accumulate_live_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr,
                                     d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_tile_live_ptr, d_out_hist_ptr, d_out_hist_len_ptr,
                                     max_history=None, depth_tol=None, normal_tol=None, stream=0):
     """pt_temporal_accumulate_live_device: temporal_accumulate_device plus the device map of live tiles (0 / None: every tile)."""
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_live_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
-                                                    d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr,
-                                                    d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None,
-                                                    d_tile_live_ptr or None, C.byref(p), d_out_hist_ptr, d_out_hist_len_ptr, stream or None),
-           "pt_temporal_accumulate_live_device")
+    _temporal_device("temporal_accumulate_live", w, h, camera, camera_prev,
+                     (d_rgba_sum_ptr, d_sq_sum_ptr, int(spp), int(batches), d_albedo_ptr, d_normal_depth_ptr),
+                     (d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_tile_live_ptr), (d_out_hist_ptr, d_out_hist_len_ptr),
+                     (max_history, depth_tol, normal_tol), stream)
 
 
 def converge_defaults():
@@ -1307,24 +1293,16 @@ def temporal_accumulate_cur(camera, cur, normal_depth, camera_prev=None, prev_no
                             depth_tol=None, normal_tol=None):
     """pt_temporal_accumulate_cur (host, blocking): temporal_accumulate with this frame's working pixels given in `cur` ([h,w,4]
     float32: e and V, V = -1 for a pass-through pixel), as upsample returns them. Returns new (hist, hist_len)."""
-    E, N = _f4_frames("temporal_accumulate_cur", (("cur", cur), ("normal_depth", normal_depth)))
-    h, w = E.shape[:2]
-    PN, H, HL = _history_arrays("temporal_accumulate_cur", E.shape, prev_normal_depth, hist, hist_len)
-    out, out_len = np.empty_like(E), np.empty((h, w), np.float32)
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_cur(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, _p(E), _p(N), _p(PN),
-                                            _p(H), _p(HL), C.byref(p), _p(out), _p(out_len)), "pt_temporal_accumulate_cur")
-    return out, out_len
+    return _temporal_host("temporal_accumulate_cur", camera, camera_prev, _CUR, (cur, normal_depth), (),
+                          (prev_normal_depth, hist, hist_len), (max_history, depth_tol, normal_tol))
 
 
 def temporal_accumulate_cur_device(w, h, camera, camera_prev, d_cur_ptr, d_normal_depth_ptr, d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr,
                                    d_out_hist_ptr, d_out_hist_len_ptr, max_history=None, depth_tol=None, normal_tol=None, stream=0):
     """pt_temporal_accumulate_cur_device: temporal_accumulate_device with the frame's (e, V) buffer in place of its sums."""
-    p = _temporal_params(max_history, depth_tol, normal_tol)
-    _check(lib().pt_temporal_accumulate_cur_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None, d_cur_ptr,
-                                                   d_normal_depth_ptr, d_prev_normal_depth_ptr or None, d_hist_ptr or None, d_hist_len_ptr or None,
-                                                   C.byref(p), d_out_hist_ptr, d_out_hist_len_ptr, stream or None),
-           "pt_temporal_accumulate_cur_device")
+    _temporal_device("temporal_accumulate_cur", w, h, camera, camera_prev, (d_cur_ptr, d_normal_depth_ptr),
+                     (d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr), (d_out_hist_ptr, d_out_hist_len_ptr),
+                     (max_history, depth_tol, normal_tol), stream)
 
 
 def upsample_defaults():

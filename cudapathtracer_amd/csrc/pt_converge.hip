@@ -2,7 +2,7 @@
 // tests/converge_ref.py restates the arithmetic in numpy.
 //
 //   converge_select_kernel   one wave per 8x8 tile, 16x16 pixels per workgroup as four tiles (the tiling of
-//                            temporal_accumulate_kernel, so a wave's loads fall into a few lines). Per lane one float4 of the
+//                            temporal_kernel, so a wave's loads fall into a few lines). Per lane one float4 of the
 //                            history and one float of its length; r = sqrtf(V) / (1e-4 + sqrtf(lum)), the standard error of
 //                            the pixel's mean over the root of the mean (the shape of pt_render_adaptive's estimator); a 64-lane
 //                            max through cross-lane shuffles and a ballot for "some pixel is young"; lane 0 stores the tile's
@@ -11,14 +11,12 @@
 // with the live flags as its keep flags. The other two stages of a converging frame live with what they extend: moments on a
 // list in pt_api.hip (render_moments), the accumulation with a tile map in pt_temporal.hip.
 #include <cmath>
-#include <cstdio>
 #include <mutex>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
-
-extern "C" int pt_fail_(int code, const char* msg);
+#include "pt_postfx_host.h"
 
 namespace pt {
 
@@ -57,54 +55,27 @@ __global__ void __launch_bounds__(256) converge_select_kernel(int w, int h, int 
     }
 }
 
-static int cv_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), fmt, a, b, c, d);
-    return pt_fail_(code, buf);
-}
-#define CV_HIP_OK(expr)                                                                                            \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) {                                                                                    \
-            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
-            return pt_fail_(-2, m_);                                                                               \
-        }                                                                                                          \
-    } while (0)
-
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa < pb + bBytes && pb < pa + aBytes;
-}
-
 int check_converge_params(const char* fn, const pt_converge_params& P) {
-    char buf[160];
-    if (!(P.threshold >= 0.0f) || !std::isfinite(P.threshold)) {
-        snprintf(buf, sizeof(buf), "%s: threshold must be a finite number >= 0", fn);
-        return pt_fail_(-1, buf);
-    }
-    if (P.min_history < 1) {
-        snprintf(buf, sizeof(buf), "%s: min_history %d must be at least 1", fn, P.min_history);
-        return pt_fail_(-1, buf);
-    }
+    if (!(P.threshold >= 0.0f) || !std::isfinite(P.threshold)) return postfx_fail_fn(-1, fn, "threshold must be a finite number >= 0");
+    if (P.min_history < 1) return postfx_fail_fn(-1, fn, "min_history %d must be at least 1", P.min_history);
     return 0;
 }
 
 static int check_select_args(int w, int h, const void* hist, const void* histLen, const pt_converge_params& P, const void* tileErr,
                              const void* tileLive, const void* list, const void* count) {
-    if (w <= 0 || h <= 0) return cv_fail(-1, "pt_temporal_select: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return cv_fail(-1, "pt_temporal_select: image of %d x %d pixels is too large", w, h);
-    if (!hist || !histLen) return cv_fail(-1, "pt_temporal_select: null buffer");
-    if (!tileErr || !tileLive || !list || !count) return cv_fail(-1, "pt_temporal_select: null output");
+    if (int r = postfx_check_size("pt_temporal_select", w, h)) return r;
+    if (!hist || !histLen) return postfx_fail(-1, "pt_temporal_select: null buffer");
+    if (!tileErr || !tileLive || !list || !count) return postfx_fail(-1, "pt_temporal_select: null output");
     if (int r = check_converge_params("pt_temporal_select", P)) return r;
     const size_t n = (size_t)w * h, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
     const void* out[4] = {tileErr, tileLive, list, count};
     const size_t outBytes[4] = {tb, tb, tb, 4};
     for (int i = 0; i < 4; i++) {
         if (overlaps(out[i], outBytes[i], hist, n * 16) || overlaps(out[i], outBytes[i], histLen, n * 4))
-            return cv_fail(-1, "pt_temporal_select: the outputs must not alias the inputs or each other");
+            return postfx_fail(-1, "pt_temporal_select: the outputs must not alias the inputs or each other");
         for (int j = 0; j < i; j++)
             if (overlaps(out[i], outBytes[i], out[j], outBytes[j]))
-                return cv_fail(-1, "pt_temporal_select: the outputs must not alias the inputs or each other");
+                return postfx_fail(-1, "pt_temporal_select: the outputs must not alias the inputs or each other");
     }
     return 0;
 }
@@ -117,18 +88,18 @@ static IotaList g_iota[PT_MULTI_MAX_DEVICES];
 
 static int iota_list(int n, hipStream_t stream, const int** out) {
     int dev = -1;
-    CV_HIP_OK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= PT_MULTI_MAX_DEVICES) return cv_fail(-2, "pt_temporal_select: HIP device %d is out of range", dev);
+    POSTFX_HIP_OK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= PT_MULTI_MAX_DEVICES) return postfx_fail(-2, "pt_temporal_select: HIP device %d is out of range", dev);
     std::lock_guard<std::mutex> lock(g_iotaMutex);
     IotaList& L = g_iota[dev];
     if (L.n < n) {
         int cap = 4096;
         while (cap < n) cap <<= 1;
         int* p = nullptr;
-        CV_HIP_OK(hipMalloc(&p, (size_t)cap * sizeof(int)));
+        POSTFX_HIP_OK(hipMalloc(&p, (size_t)cap * sizeof(int)));
         hipError_t e = launch_adaptive_iota(cap, p, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { (void)hipFree(p); return cv_fail(-2, "pt_temporal_select: could not fill the tile list"); }
+        if (e != hipSuccess) { (void)hipFree(p); return postfx_fail(-2, "pt_temporal_select: could not fill the tile list"); }
         if (L.p) (void)hipFree(L.p);                       // (hipFree waits for whatever still reads it)
         L.p = p; L.n = cap;
     }
@@ -143,8 +114,8 @@ static int select_launch(int w, int h, const float4* hist, const float* histLen,
     if (int r = iota_list(T, stream, &iota)) return r;
     hipLaunchKernelGGL(converge_select_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, stream, w, h, tilesX, tilesY, hist, histLen,
                        P.threshold, (float)P.min_history, tileErr, tileLive);
-    CV_HIP_OK(hipGetLastError());
-    CV_HIP_OK(launch_adaptive_compact(iota, tileLive, T, list, count, stream));
+    POSTFX_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(launch_adaptive_compact(iota, tileLive, T, list, count, stream));
     return 0;
 }
 
@@ -174,26 +145,14 @@ int pt_temporal_select(int w, int h, const float* hist, const float* hist_len, c
     pt_converge_params P;
     if (params) P = *params; else pt_converge_defaults(&P);
     if (int r = check_select_args(w, h, hist, hist_len, P, out_tile_err, out_tile_live, out_list, out_count)) return r;
-    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
-    const size_t T = (size_t)((w + 7) / 8) * ((h + 7) / 8), tb = (T * 4 + 15) & ~(size_t)15;
-    char* d = nullptr;
-    CV_HIP_OK(hipMalloc(&d, b16 + b4 + 3 * tb + 16));
-    char* dH = d; char* dL = dH + b16; char* dE = dL + b4; char* dV = dE + tb; char* dI = dV + tb; char* dC = dI + tb;
-    hipError_t e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dL, hist_len, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dI, 0, tb);         // the list's entries past the count read back as 0
-    int r = 0;
-    if (e != hipSuccess) {
-        r = cv_fail(-2, "pt_temporal_select: upload failed");
-    } else if ((r = select_launch(w, h, (const float4*)dH, (const float*)dL, P, (float*)dE, (int32_t*)dV, (int*)dI, (int*)dC, nullptr)) == 0) {
-        e = hipMemcpy(out_tile_err, dE, T * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_tile_live, dV, T * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_list, dI, T * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_count, dC, 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = cv_fail(-2, "pt_temporal_select: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const size_t n = (size_t)w * h, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
+    const HostIn in[] = {{hist, n * 16}, {hist_len, n * 4}};
+    const HostOut out[] = {{out_tile_err, tb}, {out_tile_live, tb}, {out_list, tb}, {out_count, 4}};
+    return postfx_host_form("pt_temporal_select", 0, in, out, [&](char*, char** d, char** o) {
+        if (hipMemset(o[2], 0, tb) != hipSuccess)          // the list's entries past the count read back as 0
+            return postfx_fail(-2, "pt_temporal_select: upload failed");
+        return select_launch(w, h, (const float4*)d[0], (const float*)d[1], P, (float*)o[0], (int32_t*)o[1], (int*)o[2], (int*)o[3], nullptr);
+    });
 }
 
 }  // extern "C"

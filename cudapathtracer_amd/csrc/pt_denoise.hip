@@ -15,14 +15,12 @@
 // guide (w*h float4: unit normal or 0, depth), the partial sums (one float2 per 256 pixels) and the result of the reduction.
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
 #include "pt_denoise_shared.h"
-
-extern "C" int pt_fail_(int code, const char* msg);
+#include "pt_postfx_host.h"
 
 namespace pt {
 
@@ -332,30 +330,15 @@ __global__ void __launch_bounds__(kDnBlock) denoise_hist_finish_kernel(int n, co
     out[i] = make_float4(demod_albedo(a.x) * ev.x, demod_albedo(a.y) * ev.y, demod_albedo(a.z) * ev.z, 0.0f);
 }
 
-static int dn_fail(int code, const char* fmt, int a = 0, int b = 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), fmt, a, b);
-    return pt_fail_(code, buf);
-}
-#define DN_HIP_OK(expr)                                                                                            \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) {                                                                                    \
-            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
-            return pt_fail_(-2, m_);                                                                               \
-        }                                                                                                          \
-    } while (0)
-
 static int check_denoise_args(int w, int h, const void* in, int spp, const void* albedo, const void* nd, const pt_denoise_params& P,
                               const void* out) {
-    if (w <= 0 || h <= 0) return dn_fail(-1, "pt_denoise: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return dn_fail(-1, "pt_denoise: image of %d x %d pixels is too large", w, h);
-    if (spp <= 0) return dn_fail(-1, "pt_denoise: spp %d must be positive", spp);
-    if (!in || !albedo || !nd || !out) return dn_fail(-1, "pt_denoise: null buffer");
-    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return dn_fail(-1, "pt_denoise: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
-    if (!(P.sigma_color > 0.0f) || !std::isfinite(P.sigma_color)) return dn_fail(-1, "pt_denoise: sigma_color must be positive and finite");
-    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return dn_fail(-1, "pt_denoise: sigma_normal must be >= 0 and finite");
-    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return dn_fail(-1, "pt_denoise: sigma_depth must be positive and finite");
+    if (int r = postfx_check_size("pt_denoise", w, h)) return r;
+    if (spp <= 0) return postfx_fail(-1, "pt_denoise: spp %d must be positive", spp);
+    if (!in || !albedo || !nd || !out) return postfx_fail(-1, "pt_denoise: null buffer");
+    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return postfx_fail(-1, "pt_denoise: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
+    if (!(P.sigma_color > 0.0f) || !std::isfinite(P.sigma_color)) return postfx_fail(-1, "pt_denoise: sigma_color must be positive and finite");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return postfx_fail(-1, "pt_denoise: sigma_normal must be >= 0 and finite");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return postfx_fail(-1, "pt_denoise: sigma_depth must be positive and finite");
     return 0;
 }
 
@@ -369,33 +352,32 @@ static int denoise_launch(int w, int h, const float4* in, int spp, const float4*
     const int n = (int)L.n;
     const float fspp = (float)spp;
     hipLaunchKernelGGL(denoise_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, nd, e[0], guide, partials);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
     for (int i = 0; i < P.iterations; i++) {
         const float colorScale = P.sigma_color * P.sigma_color * std::ldexp(1.0f, -i);
         hipLaunchKernelGGL(denoise_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, colorScale, P.sigma_normal, P.sigma_depth, lum,
                            e[i & 1], guide, e[(i + 1) & 1]);
-        DN_HIP_OK(hipGetLastError());
+        POSTFX_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
 static int check_denoise_var_args(int w, int h, const void* in, const void* sq, int spp, int batches, const void* albedo, const void* nd,
                                   const pt_denoise_var_params& P, const void* out) {
-    if (w <= 0 || h <= 0) return dn_fail(-1, "pt_denoise_var: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return dn_fail(-1, "pt_denoise_var: image of %d x %d pixels is too large", w, h);
-    if (spp <= 0) return dn_fail(-1, "pt_denoise_var: spp %d must be positive", spp);
-    if (batches < 2) return dn_fail(-1, "pt_denoise_var: batches %d must be at least 2", batches);
-    if (spp % batches != 0) return dn_fail(-1, "pt_denoise_var: batches %d must divide spp %d", batches, spp);
-    if (!in || !sq || !albedo || !nd || !out) return dn_fail(-1, "pt_denoise_var: null buffer");
-    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return dn_fail(-1, "pt_denoise_var: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
-    if (!(P.sigma_var > 0.0f) || !std::isfinite(P.sigma_var)) return dn_fail(-1, "pt_denoise_var: sigma_var must be positive and finite");
-    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return dn_fail(-1, "pt_denoise_var: sigma_normal must be >= 0 and finite");
-    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return dn_fail(-1, "pt_denoise_var: sigma_depth must be positive and finite");
+    if (int r = postfx_check_size("pt_denoise_var", w, h)) return r;
+    if (spp <= 0) return postfx_fail(-1, "pt_denoise_var: spp %d must be positive", spp);
+    if (batches < 2) return postfx_fail(-1, "pt_denoise_var: batches %d must be at least 2", batches);
+    if (spp % batches != 0) return postfx_fail(-1, "pt_denoise_var: batches %d must divide spp %d", batches, spp);
+    if (!in || !sq || !albedo || !nd || !out) return postfx_fail(-1, "pt_denoise_var: null buffer");
+    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return postfx_fail(-1, "pt_denoise_var: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
+    if (!(P.sigma_var > 0.0f) || !std::isfinite(P.sigma_var)) return postfx_fail(-1, "pt_denoise_var: sigma_var must be positive and finite");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return postfx_fail(-1, "pt_denoise_var: sigma_normal must be >= 0 and finite");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return postfx_fail(-1, "pt_denoise_var: sigma_depth must be positive and finite");
     return 0;
 }
 
@@ -410,17 +392,17 @@ static int denoise_var_launch(int w, int h, const float4* in, const float4* sq, 
     const float fspp = (float)spp;
     hipLaunchKernelGGL(denoise_var_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, sq, fspp, (float)batches, albedo, nd, e[0], guide,
                        partials);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
     for (int i = 0; i < P.iterations; i++) {
         hipLaunchKernelGGL(denoise_var_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, P.sigma_var, P.sigma_normal, P.sigma_depth, lum,
                            e[i & 1], guide, e[(i + 1) & 1]);
-        DN_HIP_OK(hipGetLastError());
+        POSTFX_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_var_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, in, fspp, albedo, e[P.iterations & 1], out);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -428,8 +410,8 @@ static int denoise_var_launch(int w, int h, const float4* in, const float4* sq, 
 static int check_denoise_var_tiles_args(int w, int h, const void* in, const void* sq, const void* tileSpp, int batchSpp, const void* albedo,
                                         const void* nd, const pt_denoise_var_params& P, const void* out) {
     if (int r = check_denoise_var_args(w, h, in, sq, 2, 2, albedo, nd, P, out)) return r;
-    if (batchSpp < 1) return dn_fail(-1, "pt_denoise_var_tiles: batch_spp %d must be positive", batchSpp);
-    if (!tileSpp) return dn_fail(-1, "pt_denoise_var_tiles: null tile map");
+    if (batchSpp < 1) return postfx_fail(-1, "pt_denoise_var_tiles: batch_spp %d must be positive", batchSpp);
+    if (!tileSpp) return postfx_fail(-1, "pt_denoise_var_tiles: null tile map");
     return 0;
 }
 
@@ -443,29 +425,28 @@ static int denoise_var_tiles_launch(int w, int h, const float4* in, const float4
     const int n = (int)L.n, tilesX = (w + 7) / 8;
     hipLaunchKernelGGL(denoise_var_tiles_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, w, tilesX, in, sq, tileSpp, batchSpp, albedo,
                        nd, e[0], guide, partials);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
     for (int i = 0; i < P.iterations; i++) {
         hipLaunchKernelGGL(denoise_var_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, P.sigma_var, P.sigma_normal, P.sigma_depth, lum,
                            e[i & 1], guide, e[(i + 1) & 1]);
-        DN_HIP_OK(hipGetLastError());
+        POSTFX_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_var_tiles_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, w, tilesX, in, tileSpp, albedo,
                        e[P.iterations & 1], out);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
 static int check_denoise_hist_args(int w, int h, const void* hist, const void* albedo, const void* nd, const pt_denoise_var_params& P, const void* out) {
-    if (w <= 0 || h <= 0) return dn_fail(-1, "pt_denoise_hist: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return dn_fail(-1, "pt_denoise_hist: image of %d x %d pixels is too large", w, h);
-    if (!hist || !albedo || !nd || !out) return dn_fail(-1, "pt_denoise_hist: null buffer");
-    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return dn_fail(-1, "pt_denoise_hist: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
-    if (!(P.sigma_var > 0.0f) || !std::isfinite(P.sigma_var)) return dn_fail(-1, "pt_denoise_hist: sigma_var must be positive and finite");
-    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return dn_fail(-1, "pt_denoise_hist: sigma_normal must be >= 0 and finite");
-    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return dn_fail(-1, "pt_denoise_hist: sigma_depth must be positive and finite");
+    if (int r = postfx_check_size("pt_denoise_hist", w, h)) return r;
+    if (!hist || !albedo || !nd || !out) return postfx_fail(-1, "pt_denoise_hist: null buffer");
+    if (P.iterations < 0 || P.iterations > kDnMaxIterations) return postfx_fail(-1, "pt_denoise_hist: iterations %d out of range 0..%d", P.iterations, kDnMaxIterations);
+    if (!(P.sigma_var > 0.0f) || !std::isfinite(P.sigma_var)) return postfx_fail(-1, "pt_denoise_hist: sigma_var must be positive and finite");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return postfx_fail(-1, "pt_denoise_hist: sigma_normal must be >= 0 and finite");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return postfx_fail(-1, "pt_denoise_hist: sigma_depth must be positive and finite");
     return 0;
 }
 
@@ -478,17 +459,17 @@ static int denoise_hist_launch(int w, int h, const float4* hist, const float4* a
     float4* lum = (float4*)(ws + L.lum);
     const int n = (int)L.n;
     hipLaunchKernelGGL(denoise_hist_prepare_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, hist, nd, e[0], guide, partials);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(denoise_reduce_kernel, dim3(1), dim3(kDnBlock), 0, stream, L.nParts, partials, lum);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     const dim3 grid((w + 15) / 16, (h + 15) / 16);
     for (int i = 0; i < P.iterations; i++) {
         hipLaunchKernelGGL(denoise_var_iter_kernel, grid, dim3(256), 0, stream, w, h, 1 << i, P.sigma_var, P.sigma_normal, P.sigma_depth, lum,
                            e[i & 1], guide, e[(i + 1) & 1]);
-        DN_HIP_OK(hipGetLastError());
+        POSTFX_HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(denoise_hist_finish_kernel, dim3(L.nParts), dim3(kDnBlock), 0, stream, n, albedo, e[P.iterations & 1], out);
-    DN_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -526,24 +507,12 @@ int pt_denoise(int w, int h, const float* rgba_sum, int spp, const float* albedo
     pt_denoise_params P;
     if (params) P = *params; else pt_denoise_defaults(&P);
     if (int r = check_denoise_args(w, h, rgba_sum, spp, albedo, normal_depth, P, out_rgba_sum)) return r;
-    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total;
-    char* d = nullptr;
-    DN_HIP_OK(hipMalloc(&d, ws + 3 * bytes));
-    char* dIn = d + ws;                      // in and out share one buffer (out may alias in)
-    char* dA = dIn + bytes;
-    char* dN = dA + bytes;
-    hipError_t e = hipMemcpy(dIn, rgba_sum, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = dn_fail(-2, "pt_denoise: upload failed");
-    } else if ((r = denoise_launch(w, h, (const float4*)dIn, spp, (const float4*)dA, (const float4*)dN, P, d, (float4*)dIn, nullptr)) == 0) {
-        e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const size_t bytes = (size_t)w * h * 16;
+    const HostIn in[] = {{rgba_sum, bytes}, {albedo, bytes}, {normal_depth, bytes}};
+    const HostOut out[] = {{out_rgba_sum, bytes, 0}};          // in and out share one buffer (out may alias in)
+    return postfx_host_form("pt_denoise", dn_layout(w, h).total, in, out, [&](char* ws, char** d, char**) {
+        return denoise_launch(w, h, (const float4*)d[0], spp, (const float4*)d[1], (const float4*)d[2], P, ws, (float4*)d[0], nullptr);
+    });
 }
 
 void pt_denoise_var_defaults(pt_denoise_var_params* out) {
@@ -574,27 +543,13 @@ int pt_denoise_var(int w, int h, const float* rgba_sum, const float* sq_sum, int
     pt_denoise_var_params P;
     if (params) P = *params; else pt_denoise_var_defaults(&P);
     if (int r = check_denoise_var_args(w, h, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, P, out_rgba_sum)) return r;
-    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total;
-    char* d = nullptr;
-    DN_HIP_OK(hipMalloc(&d, ws + 4 * bytes));
-    char* dIn = d + ws;                      // in and out share one buffer (out may alias in)
-    char* dQ = dIn + bytes;
-    char* dA = dQ + bytes;
-    char* dN = dA + bytes;
-    hipError_t e = hipMemcpy(dIn, rgba_sum, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = dn_fail(-2, "pt_denoise_var: upload failed");
-    } else if ((r = denoise_var_launch(w, h, (const float4*)dIn, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN, P, d,
-                                       (float4*)dIn, nullptr)) == 0) {
-        e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_var: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const size_t bytes = (size_t)w * h * 16;
+    const HostIn in[] = {{rgba_sum, bytes}, {sq_sum, bytes}, {albedo, bytes}, {normal_depth, bytes}};
+    const HostOut out[] = {{out_rgba_sum, bytes, 0}};          // in and out share one buffer (out may alias in)
+    return postfx_host_form("pt_denoise_var", dn_layout(w, h).total, in, out, [&](char* ws, char** d, char**) {
+        return denoise_var_launch(w, h, (const float4*)d[0], (const float4*)d[1], spp, batches, (const float4*)d[2], (const float4*)d[3], P, ws,
+                                  (float4*)d[0], nullptr);
+    });
 }
 
 size_t pt_denoise_var_tiles_workspace_bytes(int w, int h) {
@@ -622,31 +577,15 @@ int pt_denoise_var_tiles(int w, int h, const float* rgba_sum, const float* sq_su
     const int T = ((w + 7) / 8) * ((h + 7) / 8);
     for (int t = 0; t < T; t++)
         if (tile_spp[t] <= 0 || tile_spp[t] % batch_spp != 0 || tile_spp[t] < 2 * batch_spp)
-            return dn_fail(-1, "pt_denoise_var_tiles: tile_spp[%d] = %d must be a positive multiple of batch_spp that gives at least 2 batches", t,
+            return postfx_fail(-1, "pt_denoise_var_tiles: tile_spp[%d] = %d must be a positive multiple of batch_spp that gives at least 2 batches", t,
                            tile_spp[t]);
-    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total, mapBytes = (size_t)T * sizeof(int32_t);
-    char* d = nullptr;
-    DN_HIP_OK(hipMalloc(&d, ws + 4 * bytes + mapBytes));
-    char* dIn = d + ws;                      // in and out share one buffer (out may alias in)
-    char* dQ = dIn + bytes;
-    char* dA = dQ + bytes;
-    char* dN = dA + bytes;
-    char* dMap = dN + bytes;
-    hipError_t e = hipMemcpy(dIn, rgba_sum, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dMap, tile_spp, mapBytes, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = dn_fail(-2, "pt_denoise_var_tiles: upload failed");
-    } else if ((r = denoise_var_tiles_launch(w, h, (const float4*)dIn, (const float4*)dQ, (const int32_t*)dMap, batch_spp, (const float4*)dA,
-                                             (const float4*)dN, P, d, (float4*)dIn, nullptr)) == 0) {
-        e = hipMemcpy(out_rgba_sum, dIn, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_var_tiles: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const size_t bytes = (size_t)w * h * 16;
+    const HostIn in[] = {{rgba_sum, bytes}, {sq_sum, bytes}, {albedo, bytes}, {normal_depth, bytes}, {tile_spp, (size_t)T * sizeof(int32_t)}};
+    const HostOut out[] = {{out_rgba_sum, bytes, 0}};          // in and out share one buffer (out may alias in)
+    return postfx_host_form("pt_denoise_var_tiles", dn_layout(w, h).total, in, out, [&](char* ws, char** d, char**) {
+        return denoise_var_tiles_launch(w, h, (const float4*)d[0], (const float4*)d[1], (const int32_t*)d[4], batch_spp, (const float4*)d[2],
+                                        (const float4*)d[3], P, ws, (float4*)d[0], nullptr);
+    });
 }
 
 size_t pt_denoise_hist_workspace_bytes(int w, int h) {
@@ -669,24 +608,12 @@ int pt_denoise_hist(int w, int h, const float* hist, const float* albedo, const 
     pt_denoise_var_params P;
     if (params) P = *params; else pt_denoise_var_defaults(&P);
     if (int r = check_denoise_hist_args(w, h, hist, albedo, normal_depth, P, out_rgba_mean)) return r;
-    const size_t bytes = (size_t)w * h * 16, ws = dn_layout(w, h).total;
-    char* d = nullptr;
-    DN_HIP_OK(hipMalloc(&d, ws + 3 * bytes));
-    char* dH = d + ws;                       // hist and out share one buffer (out may alias hist)
-    char* dA = dH + bytes;
-    char* dN = dA + bytes;
-    hipError_t e = hipMemcpy(dH, hist, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, bytes, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = dn_fail(-2, "pt_denoise_hist: upload failed");
-    } else if ((r = denoise_hist_launch(w, h, (const float4*)dH, (const float4*)dA, (const float4*)dN, P, d, (float4*)dH, nullptr)) == 0) {
-        e = hipMemcpy(out_rgba_mean, dH, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = dn_fail(-2, "pt_denoise_hist: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const size_t bytes = (size_t)w * h * 16;
+    const HostIn in[] = {{hist, bytes}, {albedo, bytes}, {normal_depth, bytes}};
+    const HostOut out[] = {{out_rgba_mean, bytes, 0}};         // hist and out share one buffer (out may alias hist)
+    return postfx_host_form("pt_denoise_hist", dn_layout(w, h).total, in, out, [&](char* ws, char** d, char**) {
+        return denoise_hist_launch(w, h, (const float4*)d[0], (const float4*)d[1], (const float4*)d[2], P, ws, (float4*)d[0], nullptr);
+    });
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 //
 //   resolve_kernel      radiance sums to display bytes: the division of novum_finalise (or of an adaptive frame's tile map), its
 //                       NaN / Inf paint, exposure, novum_save_bmp's tone map + gamma and its byte conversion. One thread per pixel,
-//                       16x16 pixels per workgroup as four 8x8 tiles (one per wave, the tiling of temporal_accumulate_kernel), so a
+//                       16x16 pixels per workgroup as four 8x8 tiles (one per wave, the tiling of temporal_kernel), so a
 //                       wave's tile index is uniform and the tile's sample count is one scalar load. One float4 load, one dword
 //                       store (plus the optional float4 mean); no LDS, no scratch. tests/preview_ref.py restates it in numpy.
 //   pt_preview          a session that owns the device buffers of one w x h viewer and runs render_moments -> render_aovs ->
@@ -19,14 +19,12 @@
 //                       With motion on (pt_preview_set_motion) the frame after an announced vertex update that keeps its history
 //                       also runs pt_render_motion_device and accumulates through pt_temporal_accumulate[_cur]_motion_device.
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
-
-extern "C" int pt_fail_(int code, const char* msg);
+#include "pt_postfx_host.h"
 
 namespace pt {
 
@@ -63,43 +61,23 @@ __global__ void __launch_bounds__(256) resolve_kernel(int w, int h, const float4
     out8[p] = r | (g << 8) | (b << 16) | 0xff000000u;
 }
 
-static int pv_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), fmt, a, b, c, d);
-    return pt_fail_(code, buf);
-}
-#define PV_HIP_OK(expr)                                                                                            \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) {                                                                                    \
-            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
-            return pt_fail_(-2, m_);                                                                               \
-        }                                                                                                          \
-    } while (0)
-
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa < pb + bBytes && pb < pa + aBytes;
-}
-
 static int check_resolve_params(const pt_resolve_params& P) {
-    if (P.tonemap != 0 && P.tonemap != 1) return pv_fail(-1, "pt_resolve: tonemap %d must be 0 or 1", P.tonemap);
-    if (!(P.exposure > 0.0f) || !std::isfinite(P.exposure)) return pv_fail(-1, "pt_resolve: exposure must be positive and finite");
+    if (P.tonemap != 0 && P.tonemap != 1) return postfx_fail(-1, "pt_resolve: tonemap %d must be 0 or 1", P.tonemap);
+    if (!(P.exposure > 0.0f) || !std::isfinite(P.exposure)) return postfx_fail(-1, "pt_resolve: exposure must be positive and finite");
     return 0;
 }
 
 static int check_resolve_args(int w, int h, const void* in, int spp, const void* tileSpp, const pt_resolve_params& P, const void* out8,
                               const void* mean) {
-    if (w <= 0 || h <= 0) return pv_fail(-1, "pt_resolve: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return pv_fail(-1, "pt_resolve: image of %d x %d pixels is too large", w, h);
-    if (!in) return pv_fail(-1, "pt_resolve: null buffer");
-    if (!out8) return pv_fail(-1, "pt_resolve: null output");
-    if (!tileSpp && spp < 1) return pv_fail(-1, "pt_resolve: spp %d must be at least 1 (or give a tile map)", spp);
+    if (int r = postfx_check_size("pt_resolve", w, h)) return r;
+    if (!in) return postfx_fail(-1, "pt_resolve: null buffer");
+    if (!out8) return postfx_fail(-1, "pt_resolve: null output");
+    if (!tileSpp && spp < 1) return postfx_fail(-1, "pt_resolve: spp %d must be at least 1 (or give a tile map)", spp);
     if (int r = check_resolve_params(P)) return r;
     const size_t n = (size_t)w * h, tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
     if (overlaps(out8, n * 4, in, n * 16) || (mean && (overlaps(mean, n * 16, in, n * 16) || overlaps(mean, n * 16, out8, n * 4))) ||
         (tileSpp && (overlaps(out8, n * 4, tileSpp, tiles * 4) || (mean && overlaps(mean, n * 16, tileSpp, tiles * 4)))))
-        return pv_fail(-1, "pt_resolve: the outputs must not alias the inputs or each other");
+        return postfx_fail(-1, "pt_resolve: the outputs must not alias the inputs or each other");
     return 0;
 }
 
@@ -107,7 +85,7 @@ static int resolve_launch(int w, int h, const float4* in, int spp, const int32_t
                           hipStream_t stream) {
     hipLaunchKernelGGL(resolve_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, stream, w, h, in, (float)spp, tileSpp, (w + 7) / 8,
                        P.tonemap, P.exposure, out8, mean);
-    PV_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -176,26 +154,15 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
     pt_resolve_params P;
     if (params) P = *params; else pt_resolve_defaults(&P);
     if (int r = check_resolve_args(w, h, rgba, spp, tile_spp, P, rgba8, mean)) return r;
-    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15, tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    const size_t n = (size_t)w * h, tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
     if (tile_spp)
         for (size_t t = 0; t < tiles; t++)
-            if (tile_spp[t] <= 0) return pv_fail(-1, "pt_resolve: tile %d has %d samples; every tile needs at least one", (int)t, tile_spp[t]);
-    char* d = nullptr;
-    PV_HIP_OK(hipMalloc(&d, 2 * b16 + b4 + tiles * 4));
-    char* dIn = d; char* dMean = dIn + b16; char* d8 = dMean + b16; char* dT = d8 + b4;
-    hipError_t e = hipMemcpy(dIn, rgba, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && tile_spp) e = hipMemcpy(dT, tile_spp, tiles * 4, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = pv_fail(-2, "pt_resolve: upload failed");
-    } else if ((r = resolve_launch(w, h, (const float4*)dIn, spp, tile_spp ? (const int32_t*)dT : nullptr, P, (uint32_t*)d8,
-                                   mean ? (float4*)dMean : nullptr, nullptr)) == 0) {
-        e = hipMemcpy(rgba8, d8, n * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && mean) e = hipMemcpy(mean, dMean, b16, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = pv_fail(-2, "pt_resolve: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+            if (tile_spp[t] <= 0) return postfx_fail(-1, "pt_resolve: tile %d has %d samples; every tile needs at least one", (int)t, tile_spp[t]);
+    const HostIn in[] = {{rgba, n * 16}, {tile_spp, tiles * 4}};
+    const HostOut out[] = {{rgba8, n * 4}, {mean, n * 16}};
+    return postfx_host_form("pt_resolve", 0, in, out, [&](char*, char** d, char** o) {
+        return resolve_launch(w, h, (const float4*)d[0], spp, (const int32_t*)d[1], P, (uint32_t*)o[0], (float4*)o[1], nullptr);
+    });
 }
 
 void pt_preview_defaults(pt_preview_params* out) {
@@ -227,17 +194,17 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
     // what the stages would refuse on every frame is refused here, before any HIP call; the filters' and the history's own
     // parameters are checked by their stages
     int bad = 0;
-    if (!scene) bad = pv_fail(-1, "pt_preview_create: null scene");
-    else if (w <= 0 || h <= 0) bad = pv_fail(-1, "pt_preview_create: image size %d x %d must be positive", w, h);
-    else if ((long long)((w + 7) / 8) * ((h + 7) / 8) * 64 > 0x7fffffffll) bad = pv_fail(-1, "pt_preview_create: image of %d x %d pixels is too large", w, h);
-    else if (P.spp <= 0) bad = pv_fail(-1, "pt_preview_create: spp %d must be positive", P.spp);
-    else if (P.batches < 2) bad = pv_fail(-1, "pt_preview_create: batches %d must be at least 2", P.batches);
-    else if (P.spp % P.batches != 0) bad = pv_fail(-1, "pt_preview_create: batches %d must divide spp %d", P.batches, P.spp);
+    if (!scene) bad = postfx_fail(-1, "pt_preview_create: null scene");
+    else if (w <= 0 || h <= 0) bad = postfx_fail(-1, "pt_preview_create: image size %d x %d must be positive", w, h);
+    else if ((long long)((w + 7) / 8) * ((h + 7) / 8) * 64 > 0x7fffffffll) bad = postfx_fail(-1, "pt_preview_create: image of %d x %d pixels is too large", w, h);
+    else if (P.spp <= 0) bad = postfx_fail(-1, "pt_preview_create: spp %d must be positive", P.spp);
+    else if (P.batches < 2) bad = postfx_fail(-1, "pt_preview_create: batches %d must be at least 2", P.batches);
+    else if (P.spp % P.batches != 0) bad = postfx_fail(-1, "pt_preview_create: batches %d must divide spp %d", P.batches, P.spp);
     else if (P.integrator != PT_UNIDIRECTIONAL && P.integrator != PT_NAIVE_UNIDIRECTIONAL)
-        bad = pv_fail(-3, "pt_preview_create: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2)", P.integrator);
-    else if (P.aov_spp <= 0) bad = pv_fail(-1, "pt_preview_create: aov_spp %d must be positive", P.aov_spp);
+        bad = postfx_fail(-3, "pt_preview_create: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2)", P.integrator);
+    else if (P.aov_spp <= 0) bad = postfx_fail(-1, "pt_preview_create: aov_spp %d must be positive", P.aov_spp);
     else if ((P.temporal != 0 && P.temporal != 1) || (P.filter != 0 && P.filter != 1))
-        bad = pv_fail(-1, "pt_preview_create: temporal %d and filter %d must be 0 or 1", P.temporal, P.filter);
+        bad = postfx_fail(-1, "pt_preview_create: temporal %d and filter %d must be 0 or 1", P.temporal, P.filter);
     else bad = check_resolve_params(P.resolve_params);
     if (bad) return nullptr;
 
@@ -251,7 +218,7 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
     bool ok = hipMalloc(&p->pool, total) == hipSuccess && hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; ok && i < 6; i++) ok = hipEventCreate(&p->ev[i]) == hipSuccess;
     if (!ok) {
-        pv_fail(-2, "pt_preview_create: could not allocate the session's buffers, stream and events (no usable HIP device, or out of memory)");
+        postfx_fail(-2, "pt_preview_create: could not allocate the session's buffers, stream and events (no usable HIP device, or out of memory)");
         pt_preview_destroy(p);
         return nullptr;
     }
@@ -266,24 +233,24 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 }
 
 int pt_preview_reset(pt_preview* p) {
-    if (!p) return pv_fail(-1, "pt_preview_reset: null session");
+    if (!p) return postfx_fail(-1, "pt_preview_reset: null session");
     p->haveHist = p->haveFrame = p->haveTiles = false;
     return 0;
 }
 
 int pt_preview_scene_changed(pt_preview* p, int keep_history) {
-    if (!p) return pv_fail(-1, "pt_preview_scene_changed: null session");
-    if (keep_history != 0 && keep_history != 1) return pv_fail(-1, "pt_preview_scene_changed: keep_history %d must be 0 or 1", keep_history);
+    if (!p) return postfx_fail(-1, "pt_preview_scene_changed: null session");
+    if (keep_history != 0 && keep_history != 1) return postfx_fail(-1, "pt_preview_scene_changed: keep_history %d must be 0 or 1", keep_history);
     if (!keep_history) p->haveHist = p->haveFrame = p->haveTiles = false;
     p->sceneChanged = true;
     return 0;
 }
 
 int pt_preview_set_scale(pt_preview* p, int scale) {
-    if (!p) return pv_fail(-1, "pt_preview_set_scale: null session");
-    if (scale < 1 || scale > 8) return pv_fail(-1, "pt_preview_set_scale: scale %d must be 1..8", scale);
+    if (!p) return postfx_fail(-1, "pt_preview_set_scale: null session");
+    if (scale < 1 || scale > 8) return postfx_fail(-1, "pt_preview_set_scale: scale %d must be 1..8", scale);
     if (p->w % scale != 0 || p->h % scale != 0)
-        return pv_fail(-1, "pt_preview_set_scale: scale %d must divide the session's size %d x %d", scale, p->w, p->h);
+        return postfx_fail(-1, "pt_preview_set_scale: scale %d must divide the session's size %d x %d", scale, p->w, p->h);
     if (scale > 1) {                      // (no frame is in flight: pt_preview_frame blocks)
         const size_t need = (size_t)(p->w / scale) * (p->h / scale);
         char* cur = p->curEV;
@@ -292,7 +259,7 @@ int pt_preview_set_scale(pt_preview* p, int scale) {
         if (ok && need > p->loCap) ok = hipMalloc(&lo, 4 * need * 16) == hipSuccess;
         if (!ok) {
             if (cur && !p->curEV) (void)hipFree(cur);
-            return pv_fail(-2, "pt_preview_set_scale: could not allocate the buffers of scale %d", scale);
+            return postfx_fail(-2, "pt_preview_set_scale: could not allocate the buffers of scale %d", scale);
         }
         p->curEV = cur;
         if (lo) {
@@ -304,56 +271,56 @@ int pt_preview_set_scale(pt_preview* p, int scale) {
     return 0;
 }
 
-int pt_preview_scale(pt_preview* p) { return p ? p->scale : pv_fail(-1, "pt_preview_scale: null session"); }
+int pt_preview_scale(pt_preview* p) { return p ? p->scale : postfx_fail(-1, "pt_preview_scale: null session"); }
 
 int pt_preview_set_guide_chain(pt_preview* p, int max_links) {
-    if (!p) return pv_fail(-1, "pt_preview_set_guide_chain: null session");
-    if (max_links < 0 || max_links > 16) return pv_fail(-1, "pt_preview_set_guide_chain: max_links %d must be 0..16", max_links);
+    if (!p) return postfx_fail(-1, "pt_preview_set_guide_chain: null session");
+    if (max_links < 0 || max_links > 16) return postfx_fail(-1, "pt_preview_set_guide_chain: max_links %d must be 0..16", max_links);
     // guides from before and after a change do not validate against each other: the next frame is a first frame
     if (max_links != p->guideChain) p->haveHist = p->haveFrame = p->haveTiles = false;
     p->guideChain = max_links;
     return 0;
 }
 
-int pt_preview_guide_chain(pt_preview* p) { return p ? p->guideChain : pv_fail(-1, "pt_preview_guide_chain: null session"); }
+int pt_preview_guide_chain(pt_preview* p) { return p ? p->guideChain : postfx_fail(-1, "pt_preview_guide_chain: null session"); }
 
 int pt_preview_set_guide_centre(pt_preview* p, int on) {
-    if (on != 0 && on != 1) return pv_fail(-1, "pt_preview_set_guide_centre: on %d must be 0 or 1", on);
-    if (!p) return pv_fail(-1, "pt_preview_set_guide_centre: null session");
+    if (on != 0 && on != 1) return postfx_fail(-1, "pt_preview_set_guide_centre: on %d must be 0 or 1", on);
+    if (!p) return postfx_fail(-1, "pt_preview_set_guide_centre: null session");
     // jittered and centre guides do not validate against each other: the next frame is a first frame
     if (on != p->guideCentre) p->haveHist = p->haveFrame = p->haveTiles = false;
     p->guideCentre = on;
     return 0;
 }
 
-int pt_preview_guide_centre(pt_preview* p) { return p ? p->guideCentre : pv_fail(-1, "pt_preview_guide_centre: null session"); }
+int pt_preview_guide_centre(pt_preview* p) { return p ? p->guideCentre : postfx_fail(-1, "pt_preview_guide_centre: null session"); }
 
-int pt_preview_guide_passes(pt_preview* p) { return p ? p->guidePasses : pv_fail(-1, "pt_preview_guide_passes: null session"); }
+int pt_preview_guide_passes(pt_preview* p) { return p ? p->guidePasses : postfx_fail(-1, "pt_preview_guide_passes: null session"); }
 
 int pt_preview_set_motion(pt_preview* p, int on) {
-    if (on != 0 && on != 1) return pv_fail(-1, "pt_preview_set_motion: on %d must be 0 or 1", on);
-    if (!p) return pv_fail(-1, "pt_preview_set_motion: null session");
+    if (on != 0 && on != 1) return postfx_fail(-1, "pt_preview_set_motion: on %d must be 0 or 1", on);
+    if (!p) return postfx_fail(-1, "pt_preview_set_motion: null session");
     if (on && !p->M) {                    // (no frame is in flight: pt_preview_frame blocks)
         if (hipMalloc(&p->M, (size_t)p->w * p->h * 16) != hipSuccess) {
             p->M = nullptr;
-            return pv_fail(-2, "pt_preview_set_motion: could not allocate the motion buffer");
+            return postfx_fail(-2, "pt_preview_set_motion: could not allocate the motion buffer");
         }
     }
     p->motion = on;                       // (no reset: the guides do not depend on it)
     return 0;
 }
 
-int pt_preview_motion(pt_preview* p) { return p ? p->motion : pv_fail(-1, "pt_preview_motion: null session"); }
+int pt_preview_motion(pt_preview* p) { return p ? p->motion : postfx_fail(-1, "pt_preview_motion: null session"); }
 
 int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
-    if (!p) return pv_fail(-1, "pt_preview_set_converge: null session");
+    if (!p) return postfx_fail(-1, "pt_preview_set_converge: null session");
     if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
     if (int r = check_converge_params("pt_preview_set_converge", *params)) return r;
     if (!p->tiles) {                      // (no frame is in flight: pt_preview_frame blocks)
         const size_t tb = ((size_t)((p->w + 7) / 8) * ((p->h + 7) / 8) * 4 + 15) & ~(size_t)15;
         if (hipMalloc(&p->tiles, 5 * tb + 16) != hipSuccess) {
             p->tiles = nullptr;
-            return pv_fail(-2, "pt_preview_set_converge: could not allocate the tile buffers");
+            return postfx_fail(-2, "pt_preview_set_converge: could not allocate the tile buffers");
         }
         char* c = p->tiles;
         for (int i = 0; i < 2; i++) { p->tErr[i] = c; c += tb; p->tLive[i] = c; c += tb; }
@@ -365,19 +332,19 @@ int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
 }
 
 int pt_preview_last_live(pt_preview* p, int* live, int* total) {
-    if (!p) return pv_fail(-1, "pt_preview_last_live: null session");
-    if (!p->haveFrame) return pv_fail(-1, "pt_preview_last_live: no frame since the session was created or reset");
+    if (!p) return postfx_fail(-1, "pt_preview_last_live: null session");
+    if (!p->haveFrame) return postfx_fail(-1, "pt_preview_last_live: no frame since the session was created or reset");
     if (live) *live = p->lastLive;
     if (total) *total = ((p->w + 7) / 8) * ((p->h + 7) / 8);
     return 0;
 }
 
 int pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live) {
-    if (!p) return pv_fail(-1, "pt_preview_read_tiles: null session");
-    if (!p->haveTiles) return pv_fail(-1, "pt_preview_read_tiles: no converging frame since the session was created or reset");
+    if (!p) return postfx_fail(-1, "pt_preview_read_tiles: null session");
+    if (!p->haveTiles) return postfx_fail(-1, "pt_preview_read_tiles: no converging frame since the session was created or reset");
     const size_t tb = (size_t)((p->w + 7) / 8) * ((p->h + 7) / 8) * 4;
-    if (tile_err) PV_HIP_OK(hipMemcpy(tile_err, p->tErr[p->curT], tb, hipMemcpyDeviceToHost));
-    if (tile_live) PV_HIP_OK(hipMemcpy(tile_live, p->tLive[p->curT], tb, hipMemcpyDeviceToHost));
+    if (tile_err) POSTFX_HIP_OK(hipMemcpy(tile_err, p->tErr[p->curT], tb, hipMemcpyDeviceToHost));
+    if (tile_live) POSTFX_HIP_OK(hipMemcpy(tile_live, p->tLive[p->curT], tb, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -410,30 +377,30 @@ static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t
     const pt_preview_params& P = p->P;
     const int w = p->w, h = p->h, T = ((w + 7) / 8) * ((h + 7) / 8), nt = p->curT ^ 1;
     hipStream_t st = p->stream;
-    PV_HIP_OK(hipEventRecord(p->ev[0], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[0], st));
     if (int r = pt_temporal_select_device(w, h, p->H[p->cur], p->L[p->cur], &p->C, p->tErr[nt], p->tLive[nt], p->tList, p->tCount, st)) return r;
     int count = -1;
-    PV_HIP_OK(hipMemcpyAsync(&count, p->tCount, sizeof(int), hipMemcpyDeviceToHost, st));
-    PV_HIP_OK(hipStreamSynchronize(st));
-    if (count < 0 || count > T) return pv_fail(-2, "pt_preview_frame: the live list holds %d of %d tiles", count, T);
+    POSTFX_HIP_OK(hipMemcpyAsync(&count, p->tCount, sizeof(int), hipMemcpyDeviceToHost, st));
+    POSTFX_HIP_OK(hipStreamSynchronize(st));
+    if (count < 0 || count > T) return postfx_fail(-2, "pt_preview_frame: the live list holds %d of %d tiles", count, T);
     if (count > 0)
         if (int r = pt_render_moments_tiles_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->tList,
                                                    count, p->S, p->Q, st))
             return r;
-    PV_HIP_OK(hipEventRecord(p->ev[1], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
     if (!reuse)
         if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[2], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
     if (int r = pt_temporal_accumulate_live_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], p->N[p->curG], p->H[p->cur],
                                                    p->L[p->cur], p->tLive[nt], &P.temporal_params, p->H[nxt], p->L[nxt], st))
         return r;
-    PV_HIP_OK(hipEventRecord(p->ev[3], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
     pt_denoise_var_params F = P.filter_params;
     if (!P.filter) F.iterations = 0;
     if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[4], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[5], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
     p->frameLive = count; p->frameConverged = true;
     return 0;
 }
@@ -445,14 +412,14 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
     const int w = p->w, h = p->h, s = p->scale, wl = w / s, hl = h / s;
     hipStream_t st = p->stream;
     if (cam->w != w || cam->h != h)       // (before the low-res camera is made: the stages would see a size that need not divide)
-        return pv_fail(-1, "pt_preview_frame: camera is %d x %d, the session %d x %d", cam->w, cam->h, w, h);
+        return postfx_fail(-1, "pt_preview_frame: camera is %d x %d, the session %d x %d", cam->w, cam->h, w, h);
     pt_camera lowCam;
     if (int r = pt_camera_scaled(cam, s, &lowCam)) return r;
     const size_t lb = p->loCap * 16;
     char *S = p->lo, *Q = S + lb, *Al = Q + lb, *Nl = Al + lb;
-    PV_HIP_OK(hipEventRecord(p->ev[0], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[0], st));
     if (int r = pt_render_moments_device(p->scene, &lowCam, wl, hl, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, S, Q, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[1], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
     if (p->guideCentre) {
         if (!reuse)
             if (int r = preview_display_guide(p, cam, seed, gn)) return r;
@@ -462,7 +429,7 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
         if (int r = preview_aovs(p, &lowCam, wl, hl, seed, Al, Nl)) return r;
         if (int r = preview_display_guide(p, cam, seed, gn)) return r;
     }
-    PV_HIP_OK(hipEventRecord(p->ev[2], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
     if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[gn], nullptr, p->curEV, st)) return r;
     const void* shown = p->curEV;         // the (e, V) buffer the filter reads
     if (P.temporal) {
@@ -477,13 +444,13 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
             return r;
         shown = p->H[nxt];
     }
-    PV_HIP_OK(hipEventRecord(p->ev[3], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
     pt_denoise_var_params F = P.filter_params;
     if (!P.filter) F.iterations = 0;
     if (int r = pt_denoise_hist_device(w, h, shown, p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[4], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[5], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
     return 0;
 }
 
@@ -494,13 +461,13 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
     const pt_preview_params& P = p->P;
     const int w = p->w, h = p->h;
     hipStream_t st = p->stream;
-    PV_HIP_OK(hipEventRecord(p->ev[0], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[0], st));
     // (the first stage checks its arguments, the camera's size among them, before it enqueues anything)
     if (int r = pt_render_moments_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->S, p->Q, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[1], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
     if (!reuse)
         if (int r = preview_display_guide(p, cam, seed, gn)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[2], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
     const void* shown = p->S;             // what the resolve divides, and by what
     int shownSpp = P.spp;
     if (P.temporal) {
@@ -513,27 +480,27 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
                                                          hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr,
                                                          hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt], p->L[nxt], st))
             return r;
-        PV_HIP_OK(hipEventRecord(p->ev[3], st));
+        POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
         pt_denoise_var_params F = P.filter_params;
         if (!P.filter) F.iterations = 0;  // no iteration: the history's mean a e, pass-through pixels as they are
         if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
         shown = p->filt; shownSpp = 1;
     } else {
-        PV_HIP_OK(hipEventRecord(p->ev[3], st));
+        POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
         if (P.filter) {
             if (int r = pt_denoise_var_device(w, h, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], &P.filter_params, p->ws, p->filt, st)) return r;
             shown = p->filt;
         }
     }
-    PV_HIP_OK(hipEventRecord(p->ev[4], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, shown, shownSpp, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
-    PV_HIP_OK(hipEventRecord(p->ev[5], st));
+    POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
     return 0;
 }
 
 int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
-    if (!p) return pv_fail(-1, "pt_preview_frame: null session");
-    if (!cam) return pv_fail(-1, "pt_preview_frame: null camera");
+    if (!p) return postfx_fail(-1, "pt_preview_frame: null session");
+    if (!cam) return postfx_fail(-1, "pt_preview_frame: null camera");
     const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
     p->frameLive = ((p->w + 7) / 8) * ((p->h + 7) / 8); p->frameConverged = false;
     // a scene updated behind the session's back: its history and guide are another geometry's, and nobody said to keep them
@@ -554,10 +521,10 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
                         : (p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt, gn, reuse) : preview_stages(p, cam, seed, nxt, gn, reuse));
     const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
     if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
-    if (e != hipSuccess) return pv_fail(-2, "pt_preview_frame: the stream failed to synchronise");
+    if (e != hipSuccess) return postfx_fail(-2, "pt_preview_frame: the stream failed to synchronise");
     float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, total = 0.0f;
-    for (int i = 0; i < 5; i++) PV_HIP_OK(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
-    PV_HIP_OK(hipEventElapsedTime(&total, p->ev[0], p->ev[5]));
+    for (int i = 0; i < 5; i++) POSTFX_HIP_OK(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
+    POSTFX_HIP_OK(hipEventElapsedTime(&total, p->ev[0], p->ev[5]));
     p->cur = nxt;
     p->curG = gn;
     p->guideFresh = true;
@@ -575,14 +542,14 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
 }
 
 int pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len) {
-    if (!p) return pv_fail(-1, "pt_preview_read: null session");
-    if (!p->haveFrame) return pv_fail(-1, "pt_preview_read: no frame since the session was created or reset");
-    if ((hist || hist_len) && !p->P.temporal) return pv_fail(-1, "pt_preview_read: a session with temporal 0 keeps no history");
+    if (!p) return postfx_fail(-1, "pt_preview_read: null session");
+    if (!p->haveFrame) return postfx_fail(-1, "pt_preview_read: no frame since the session was created or reset");
+    if ((hist || hist_len) && !p->P.temporal) return postfx_fail(-1, "pt_preview_read: a session with temporal 0 keeps no history");
     const size_t n = (size_t)p->w * p->h;
-    if (rgba8) PV_HIP_OK(hipMemcpy(rgba8, p->rgba8, n * 4, hipMemcpyDeviceToHost));
-    if (mean) PV_HIP_OK(hipMemcpy(mean, p->mean, n * 16, hipMemcpyDeviceToHost));
-    if (hist) PV_HIP_OK(hipMemcpy(hist, p->H[p->cur], n * 16, hipMemcpyDeviceToHost));
-    if (hist_len) PV_HIP_OK(hipMemcpy(hist_len, p->L[p->cur], n * 4, hipMemcpyDeviceToHost));
+    if (rgba8) POSTFX_HIP_OK(hipMemcpy(rgba8, p->rgba8, n * 4, hipMemcpyDeviceToHost));
+    if (mean) POSTFX_HIP_OK(hipMemcpy(mean, p->mean, n * 16, hipMemcpyDeviceToHost));
+    if (hist) POSTFX_HIP_OK(hipMemcpy(hist, p->H[p->cur], n * 16, hipMemcpyDeviceToHost));
+    if (hist_len) POSTFX_HIP_OK(hipMemcpy(hist_len, p->L[p->cur], n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -590,7 +557,7 @@ const void* pt_preview_device_rgba8(pt_preview* p) { return p ? p->rgba8 : nullp
 const void* pt_preview_device_mean(pt_preview* p) { return p ? p->mean : nullptr; }
 
 int pt_preview_last_stats(pt_preview* p, pt_preview_stats* out) {
-    if (!p || !out) return pv_fail(-1, "pt_preview_last_stats: null argument");
+    if (!p || !out) return postfx_fail(-1, "pt_preview_last_stats: null argument");
     *out = p->stats;
     return 0;
 }

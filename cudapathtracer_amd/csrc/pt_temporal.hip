@@ -2,35 +2,31 @@
 // albedo-demodulated mean and its variance, in pt_denoise_var's working format. include/pt_api.h states the arithmetic;
 // tests/temporal_ref.py restates it in numpy. Opt-in post-process on buffers: stateless, no workspace, no render path involved.
 //
-//   temporal_accumulate_kernel<IDENT>   one thread per pixel, 16x16 pixels per workgroup as four 8x8 tiles (one per wave, the
-//                                       tiling of denoise_var_iter_kernel: a wave's four gathers fall into a few lines).
-//                                       This frame's (e, V) from S and Q (dn_var_pixel, shared with denoise_var_prepare_kernel);
-//                                       the pixel's world point from its depth along the unjittered centre ray, projected into
-//                                       the previous camera; up to four bilinear taps of the previous history, each checked
-//                                       against the previous guide; the blend. IDENT: both cameras are the same bytes, the tap
-//                                       is the pixel itself and no projection is computed.
-//   temporal_accumulate_cur_kernel<IDENT>  the same with this frame's (e, V) read from a buffer (pt_upsample's output): the two
-//                                       kernels share temporal_blend, everything after the working pixel.
-//   temporal_accumulate_live_kernel    the identity instantiation with a map of live 8x8 tiles (pt_temporal_accumulate_live: a
-//                                       resting viewer whose converged tiles were not rendered). A wave is one tile, so the
-//                                       map entry is one scalar load and the branch does not diverge: a carried wave copies its
-//                                       history and length (two loads, two stores), a live wave runs temporal_accumulate_kernel<true>'s
-//                                       code.
-//   temporal_accumulate_motion_kernel<IDENT>, temporal_accumulate_cur_motion_kernel<IDENT>  the two kernels above with a motion
-//                                       buffer (pt_render_motion): a pixel whose motion.w is 1 reprojects the point the buffer
-//                                       names — where its surface point WAS — and never takes the identity tap; every other
-//                                       pixel runs the base kernel's code (temporal_blend<IDENT, true>). One more float4 load.
-// Both cameras travel by value as kernel arguments (SGPRs); plain cached float4 loads, no LDS.
+//   temporal_kernel<Source, IDENT, MOTION, LIVE>   the one kernel of all ten entry points: one thread per pixel, 16x16 pixels per
+//                 workgroup as four 8x8 tiles (one per wave, the tiling of denoise_var_iter_kernel: a wave's four gathers fall
+//                 into a few lines). The pixel's working value (e, V), then temporal_blend: its world point from its depth along
+//                 the unjittered centre ray, projected into the previous camera; up to four bilinear taps of the previous history,
+//                 each checked against the previous guide; the blend.
+//       Source    FromSums: (e, V) from S and Q (dn_var_pixel, shared with denoise_var_prepare_kernel). FromCur: read from a
+//                 buffer (pt_upsample's output). Each says which pixels pass through and what they write.
+//       IDENT     both cameras are the same bytes: the tap is the pixel itself and no projection is computed.
+//       MOTION    a motion buffer (pt_render_motion): a pixel whose motion.w is 1 reprojects the point the buffer names — where its
+//                 surface point WAS — and never takes the identity tap; every other pixel runs the base code. One more float4 load.
+//       LIVE      a map of live 8x8 tiles (pt_temporal_accumulate_live: a resting viewer whose converged tiles were not rendered).
+//                 A wave is one tile, so the map entry is one scalar load and the branch does not diverge: a carried wave copies
+//                 its history and length (two loads, two stores), a live wave runs on. FromSums, IDENT and no MOTION only.
+//   Nine instantiations exist (temporal_launch's table). Everything travels by value in one TemporalArgs (SGPRs), the two
+//   cameras included; plain cached float4 loads, no LDS.
+// Host side: every entry point fills a TemporalCall; temporal_run checks it (check_temporal_call), and launches it (temporal_launch)
+// on the caller's buffers or, for a host form, on staged copies (postfx_host_form).
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
 #include "pt_denoise_shared.h"
-
-extern "C" int pt_fail_(int code, const char* msg);
+#include "pt_postfx_host.h"
 
 namespace pt {
 
@@ -136,232 +132,177 @@ __device__ inline void temporal_blend(int w, int h, int x, int y, float4 cur, co
     outLen[p] = len;
 }
 
-template <bool IDENT>
-__global__ void __launch_bounds__(256) temporal_accumulate_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ sum,
-                                                                  const float4* __restrict__ sq, float spp, float batches,
-                                                                  const float4* __restrict__ albedo, const float4* __restrict__ nd,
-                                                                  const float4* __restrict__ prevNd, const float4* __restrict__ hist,
-                                                                  const float* __restrict__ histLen, float maxHistory, float depthTol,
-                                                                  float normalTol, float4* __restrict__ outHist, float* __restrict__ outLen) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= w || y >= h) return;
-    const size_t p = (size_t)y * w + x;
-    float4 m;
-    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
-    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
-    temporal_blend<IDENT>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
-}
+// Everything a launch hands the kernel. A pointer the instantiation does not use is NULL and never read.
+struct TemporalArgs {
+    int w, h;
+    TemporalCam cam, prev;
+    const float4 *sum, *sq, *albedo;          // FromSums
+    float spp, batches;
+    const float4* cur;                        // FromCur
+    const float4 *nd, *prevNd, *hist;
+    const float* histLen;
+    const float4* motion;                     // MOTION
+    const int32_t* tileLive;                  // LIVE
+    int tilesX;
+    float maxHistory, depthTol, normalTol;
+    float4* outHist;
+    float* outLen;
+};
 
-// pt_temporal_accumulate_live: the identity path with a tile map. tileLive[tile] == 0: the tile was not rendered this frame and
-// keeps its history and length bit for bit (S, Q and albedo are not read there).
-__global__ void __launch_bounds__(256) temporal_accumulate_live_kernel(int w, int h, int tilesX, const int32_t* __restrict__ tileLive,
-                                                                       const float4* __restrict__ sum, const float4* __restrict__ sq, float spp,
-                                                                       float batches, const float4* __restrict__ albedo, const float4* __restrict__ nd,
-                                                                       const float4* __restrict__ prevNd, const float4* __restrict__ hist,
-                                                                       const float* __restrict__ histLen, float maxHistory, float depthTol,
-                                                                       float normalTol, float4* __restrict__ outHist, float* __restrict__ outLen) {
+// The two sources of a pixel's working value: load() returns whether the pixel passes through, and then `raw` is what it writes.
+struct FromSums {
+    static __device__ inline bool load(const TemporalArgs& a, size_t p, float4& cur, float4& raw) {
+        cur = dn_var_pixel(a.sum[p], a.sq[p], a.albedo[p], a.spp, a.batches, raw);
+        return cur.w < 0.0f;
+    }
+};
+struct FromCur {                              // (pt_upsample wrote it; a NaN variance passes through as well)
+    static __device__ inline bool load(const TemporalArgs& a, size_t p, float4& cur, float4& raw) {
+        cur = raw = a.cur[p];
+        return !(cur.w >= 0.0f);
+    }
+};
+
+template <class Source, bool IDENT, bool MOTION, bool LIVE>
+__global__ void __launch_bounds__(256) temporal_kernel(TemporalArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tx = blockIdx.x * 2 + (wave & 1), ty = blockIdx.y * 2 + (wave >> 1);
     const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-    if (x >= w || y >= h) return;                             // (a tile outside the grid has no lane left: no read past the map)
-    const size_t p = (size_t)y * w + x;
-    if (tileLive[__builtin_amdgcn_readfirstlane(ty * tilesX + tx)] == 0) {
-        outHist[p] = hist[p];
-        outLen[p] = histLen[p];
+    if (x >= a.w || y >= a.h) return;                         // (a tile outside the grid has no lane left: no read past the map)
+    const size_t p = (size_t)y * a.w + x;
+    // tileLive[tile] == 0: the tile was not rendered this frame and keeps its history and length bit for bit (S, Q and albedo are
+    // not read there)
+    if (LIVE && a.tileLive[__builtin_amdgcn_readfirstlane(ty * a.tilesX + tx)] == 0) {
+        a.outHist[p] = a.hist[p];
+        a.outLen[p] = a.histLen[p];
         return;
     }
-    float4 m;
-    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
-    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
-    const TemporalCam none = {};                              // (the identity path reads neither camera)
-    temporal_blend<true>(w, h, x, y, cur, none, none, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
+    float4 cur, raw;
+    if (Source::load(a, p, cur, raw)) { a.outHist[p] = make_float4(raw.x, raw.y, raw.z, -1.0f); a.outLen[p] = 0.0f; return; }
+    temporal_blend<IDENT, MOTION>(a.w, a.h, x, y, cur, a.cam, a.prev, a.nd, a.prevNd, a.hist, a.histLen, a.maxHistory, a.depthTol, a.normalTol,
+                                  a.outHist, a.outLen, a.motion);
 }
 
-// pt_temporal_accumulate_cur: this frame's working pixel is given (pt_upsample wrote it), not derived from S and Q.
-template <bool IDENT>
-__global__ void __launch_bounds__(256) temporal_accumulate_cur_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ curIn,
-                                                                      const float4* __restrict__ nd, const float4* __restrict__ prevNd,
-                                                                      const float4* __restrict__ hist, const float* __restrict__ histLen,
-                                                                      float maxHistory, float depthTol, float normalTol,
-                                                                      float4* __restrict__ outHist, float* __restrict__ outLen) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= w || y >= h) return;
-    const size_t p = (size_t)y * w + x;
-    const float4 cur = curIn[p];
-    if (!(cur.w >= 0.0f)) { outHist[p] = make_float4(cur.x, cur.y, cur.z, -1.0f); outLen[p] = 0.0f; return; }
-    temporal_blend<IDENT>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen);
+// One call of any of the ten entry points, on host or on device buffers.
+struct TemporalCall {
+    const char* fn;                           // the entry point, for the messages of its host form
+    int w, h;
+    const pt_camera *cam, *prev;
+    bool fromCur;                             // the frame is `cur`; otherwise sum, sq, spp, batches and albedo
+    const void *sum, *sq, *albedo, *cur;
+    int spp, batches;
+    const void *nd, *prevNd, *hist, *histLen;
+    const void* tileLive;                     // pt_temporal_accumulate_live only
+    const void* motion;                       // pt_temporal_accumulate_motion and _cur_motion only
+    pt_temporal_params P;
+    void *outHist, *outLen;
+};
+
+static TemporalCall temporal_call(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* prev, const void* nd, const void* prevNd,
+                                  const void* hist, const void* histLen, const pt_temporal_params* params, void* outHist, void* outLen) {
+    TemporalCall c = {};
+    c.fn = fn; c.w = w; c.h = h; c.cam = cam; c.prev = prev;
+    c.nd = nd; c.prevNd = prevNd; c.hist = hist; c.histLen = histLen; c.outHist = outHist; c.outLen = outLen;
+    if (params) c.P = *params; else pt_temporal_defaults(&c.P);
+    return c;
+}
+static TemporalCall& from_sums(TemporalCall& c, const void* sum, const void* sq, int spp, int batches, const void* albedo) {
+    c.sum = sum; c.sq = sq; c.spp = spp; c.batches = batches; c.albedo = albedo;
+    return c;
+}
+static TemporalCall& from_cur(TemporalCall& c, const void* cur) {
+    c.fromCur = true; c.cur = cur;
+    return c;
 }
 
-// pt_temporal_accumulate_motion / _cur_motion: the two kernels above with the motion buffer (the launch gives them a history).
-template <bool IDENT>
-__global__ void __launch_bounds__(256) temporal_accumulate_motion_kernel(int w, int h, TemporalCam cam, TemporalCam prev, const float4* __restrict__ sum,
-                                                                         const float4* __restrict__ sq, float spp, float batches,
-                                                                         const float4* __restrict__ albedo, const float4* __restrict__ nd,
-                                                                         const float4* __restrict__ prevNd, const float4* __restrict__ hist,
-                                                                         const float* __restrict__ histLen, const float4* __restrict__ motion,
-                                                                         float maxHistory, float depthTol, float normalTol,
-                                                                         float4* __restrict__ outHist, float* __restrict__ outLen) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= w || y >= h) return;
-    const size_t p = (size_t)y * w + x;
-    float4 m;
-    const float4 cur = dn_var_pixel(sum[p], sq[p], albedo[p], spp, batches, m);
-    if (cur.w < 0.0f) { outHist[p] = make_float4(m.x, m.y, m.z, -1.0f); outLen[p] = 0.0f; return; }
-    temporal_blend<IDENT, true>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen, motion);
-}
+static bool temporal_ident(const TemporalCall& c) { return !c.prev || memcmp(c.cam, c.prev, sizeof(pt_camera)) == 0; }
 
-template <bool IDENT>
-__global__ void __launch_bounds__(256) temporal_accumulate_cur_motion_kernel(int w, int h, TemporalCam cam, TemporalCam prev,
-                                                                             const float4* __restrict__ curIn, const float4* __restrict__ nd,
-                                                                             const float4* __restrict__ prevNd, const float4* __restrict__ hist,
-                                                                             const float* __restrict__ histLen, const float4* __restrict__ motion,
-                                                                             float maxHistory, float depthTol, float normalTol,
-                                                                             float4* __restrict__ outHist, float* __restrict__ outLen) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= w || y >= h) return;
-    const size_t p = (size_t)y * w + x;
-    const float4 cur = curIn[p];
-    if (!(cur.w >= 0.0f)) { outHist[p] = make_float4(cur.x, cur.y, cur.z, -1.0f); outLen[p] = 0.0f; return; }
-    temporal_blend<IDENT, true>(w, h, x, y, cur, cam, prev, nd, prevNd, hist, histLen, maxHistory, depthTol, normalTol, outHist, outLen, motion);
-}
-
-static int tp_fail(int code, const char* fn, const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
-    char buf[256];
-    const int n = snprintf(buf, sizeof(buf), "%s: ", fn);
-    snprintf(buf + n, sizeof(buf) - n, fmt, a, b, c, d);
-    return pt_fail_(code, buf);
-}
-#define TP_HIP_OK(expr)                                                                                            \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) {                                                                                    \
-            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
-            return pt_fail_(-2, m_);                                                                               \
-        }                                                                                                          \
-    } while (0)
-
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa < pb + bBytes && pb < pa + aBytes;
-}
-
-// What both entry points check after their own frame inputs (`inputs`: none of this frame's buffers is NULL).
-static int check_history_args(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* prev, bool inputs, const void* prevNd,
-                              const void* hist, const void* histLen, const pt_temporal_params& P, const void* outHist, const void* outLen) {
-    if (!cam) return tp_fail(-1, fn, "null camera");
-    if (cam->w != w || cam->h != h) return tp_fail(-1, fn, "camera is %d x %d, the frame %d x %d", cam->w, cam->h, w, h);
-    if (prev && (prev->w != w || prev->h != h)) return tp_fail(-1, fn, "previous camera is %d x %d, the frame %d x %d", prev->w, prev->h, w, h);
-    if (!inputs) return tp_fail(-1, fn, "null buffer");
-    if (!outHist || !outLen) return tp_fail(-1, fn, "null output");
-    const int given = (prevNd != nullptr) + (hist != nullptr) + (histLen != nullptr);
-    if (given != 0 && given != 3) return tp_fail(-1, fn, "prev_normal_depth, hist and hist_len must be all NULL (first frame) or all set");
-    if (given == 3) {
-        const size_t n = (size_t)w * h;
-        if (overlaps(outHist, n * 16, hist, n * 16) || overlaps(outLen, n * 4, histLen, n * 4) || overlaps(outHist, n * 16, histLen, n * 4) ||
-            overlaps(outLen, n * 4, hist, n * 16))
-            return tp_fail(-1, fn, "the output history must not alias the input history (ping-pong two pairs)");
+// All of a call's checks, before the first HIP call. The messages carry the name of the entry point that introduced the check.
+static int check_temporal_call(const TemporalCall& c) {
+    const char* fn = c.fromCur ? "pt_temporal_accumulate_cur" : "pt_temporal_accumulate";
+    const int w = c.w, h = c.h;
+    if (int r = postfx_check_size(fn, w, h)) return r;
+    if (!c.fromCur) {
+        if (c.spp <= 0) return postfx_fail_fn(-1, fn, "spp %d must be positive", c.spp);
+        if (c.batches < 2) return postfx_fail_fn(-1, fn, "batches %d must be at least 2", c.batches);
+        if (c.spp % c.batches != 0) return postfx_fail_fn(-1, fn, "batches %d must divide spp %d", c.batches, c.spp);
     }
-    if (P.max_history < 1) return tp_fail(-1, fn, "max_history %d must be at least 1", P.max_history);
-    if (!(P.depth_tol > 0.0f) || !std::isfinite(P.depth_tol)) return tp_fail(-1, fn, "depth_tol must be positive and finite");
-    if (!(P.normal_tol > 0.0f) || !(P.normal_tol <= 1.0f)) return tp_fail(-1, fn, "normal_tol must be in (0, 1]");
-    return 0;
-}
-
-static int check_size(const char* fn, int w, int h) {
-    if (w <= 0 || h <= 0) return tp_fail(-1, fn, "image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return tp_fail(-1, fn, "image of %d x %d pixels is too large", w, h);
-    return 0;
-}
-
-static int check_temporal_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* sum, const void* sq, int spp, int batches,
-                               const void* albedo, const void* nd, const void* prevNd, const void* hist, const void* histLen,
-                               const pt_temporal_params& P, const void* outHist, const void* outLen) {
-    const char* fn = "pt_temporal_accumulate";
-    if (int r = check_size(fn, w, h)) return r;
-    if (spp <= 0) return tp_fail(-1, fn, "spp %d must be positive", spp);
-    if (batches < 2) return tp_fail(-1, fn, "batches %d must be at least 2", batches);
-    if (spp % batches != 0) return tp_fail(-1, fn, "batches %d must divide spp %d", batches, spp);
-    return check_history_args(fn, w, h, cam, prev, sum && sq && albedo && nd, prevNd, hist, histLen, P, outHist, outLen);
-}
-
-// What a tile map adds (pt_temporal_accumulate_live): the identity path and a history, and outputs that leave the map alone.
-static int check_live_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* hist, const void* tileLive, const void* outHist,
-                           const void* outLen) {
-    const char* fn = "pt_temporal_accumulate_live";
-    if (!tileLive) return 0;
-    if (!hist) return tp_fail(-1, fn, "a tile map needs a history: a carried pixel keeps what it had");
-    if (prev && memcmp(cam, prev, sizeof(pt_camera)) != 0)
-        return tp_fail(-1, fn, "a tile map needs an unchanged camera (cam_prev NULL or equal to cam): a carried pixel keeps what it had at the same place");
-    const size_t n = (size_t)w * h, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
-    if (overlaps(outHist, n * 16, tileLive, tb) || overlaps(outLen, n * 4, tileLive, tb)) return tp_fail(-1, fn, "the outputs must not alias the tile map");
-    return 0;
-}
-
-static int check_temporal_cur_args(int w, int h, const pt_camera* cam, const pt_camera* prev, const void* cur, const void* nd, const void* prevNd,
-                                   const void* hist, const void* histLen, const pt_temporal_params& P, const void* outHist, const void* outLen) {
-    const char* fn = "pt_temporal_accumulate_cur";
-    if (int r = check_size(fn, w, h)) return r;
-    return check_history_args(fn, w, h, cam, prev, cur && nd, prevNd, hist, histLen, P, outHist, outLen);
-}
-
-// What a motion buffer adds (pt_temporal_accumulate_motion, _cur_motion): outputs that leave it alone.
-static int check_motion_args(const char* fn, int w, int h, const void* motion, const void* outHist, const void* outLen) {
-    if (!motion) return 0;
+    // the cameras, the buffers and the history
+    if (!c.cam) return postfx_fail_fn(-1, fn, "null camera");
+    if (c.cam->w != w || c.cam->h != h) return postfx_fail_fn(-1, fn, "camera is %d x %d, the frame %d x %d", c.cam->w, c.cam->h, w, h);
+    if (c.prev && (c.prev->w != w || c.prev->h != h))
+        return postfx_fail_fn(-1, fn, "previous camera is %d x %d, the frame %d x %d", c.prev->w, c.prev->h, w, h);
+    if (!(c.fromCur ? c.cur && c.nd : c.sum && c.sq && c.albedo && c.nd)) return postfx_fail_fn(-1, fn, "null buffer");
+    if (!c.outHist || !c.outLen) return postfx_fail_fn(-1, fn, "null output");
+    const int given = (c.prevNd != nullptr) + (c.hist != nullptr) + (c.histLen != nullptr);
+    if (given != 0 && given != 3) return postfx_fail_fn(-1, fn, "prev_normal_depth, hist and hist_len must be all NULL (first frame) or all set");
     const size_t n = (size_t)w * h;
-    if (overlaps(outHist, n * 16, motion, n * 16) || overlaps(outLen, n * 4, motion, n * 16)) return tp_fail(-1, fn, "the outputs must not alias the motion buffer");
+    if (given == 3 && (overlaps(c.outHist, n * 16, c.hist, n * 16) || overlaps(c.outLen, n * 4, c.histLen, n * 4) ||
+                       overlaps(c.outHist, n * 16, c.histLen, n * 4) || overlaps(c.outLen, n * 4, c.hist, n * 16)))
+        return postfx_fail_fn(-1, fn, "the output history must not alias the input history (ping-pong two pairs)");
+    if (c.P.max_history < 1) return postfx_fail_fn(-1, fn, "max_history %d must be at least 1", c.P.max_history);
+    if (!(c.P.depth_tol > 0.0f) || !std::isfinite(c.P.depth_tol)) return postfx_fail_fn(-1, fn, "depth_tol must be positive and finite");
+    if (!(c.P.normal_tol > 0.0f) || !(c.P.normal_tol <= 1.0f)) return postfx_fail_fn(-1, fn, "normal_tol must be in (0, 1]");
+    // what a tile map adds: the identity path and a history, and outputs that leave the map alone
+    if (c.tileLive) {
+        fn = "pt_temporal_accumulate_live";
+        if (!c.hist) return postfx_fail_fn(-1, fn, "a tile map needs a history: a carried pixel keeps what it had");
+        if (!temporal_ident(c))
+            return postfx_fail_fn(-1, fn, "a tile map needs an unchanged camera (cam_prev NULL or equal to cam): a carried pixel keeps what it had at the same place");
+        const size_t tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
+        if (overlaps(c.outHist, n * 16, c.tileLive, tb) || overlaps(c.outLen, n * 4, c.tileLive, tb))
+            return postfx_fail_fn(-1, fn, "the outputs must not alias the tile map");
+    }
+    // what a motion buffer adds: outputs that leave it alone
+    if (c.motion && (overlaps(c.outHist, n * 16, c.motion, n * 16) || overlaps(c.outLen, n * 4, c.motion, n * 16)))
+        return postfx_fail_fn(-1, c.fromCur ? "pt_temporal_accumulate_cur_motion" : "pt_temporal_accumulate_motion",
+                              "the outputs must not alias the motion buffer");
     return 0;
 }
 
-static int temporal_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* sum, const float4* sq, int spp, int batches,
-                           const float4* albedo, const float4* nd, const float4* prevNd, const float4* hist, const float* histLen,
-                           const pt_temporal_params& P, float4* outHist, float* outLen, hipStream_t stream, const int32_t* tileLive = nullptr,
-                           const float4* motion = nullptr) {
-    const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
-    const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
-    const dim3 grid((w + 15) / 16, (h + 15) / 16);
-    if (tileLive)                                             // (check_live_args: the identity path, with a history)
-        hipLaunchKernelGGL(temporal_accumulate_live_kernel, grid, dim3(256), 0, stream, w, h, (w + 7) / 8, tileLive, sum, sq, (float)spp, (float)batches,
-                           albedo, nd, prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else if (motion && hist && ident)                         // (without a history the base kernel: the buffer is not read)
-        hipLaunchKernelGGL(temporal_accumulate_motion_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo,
-                           nd, prevNd, hist, histLen, motion, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else if (motion && hist)
-        hipLaunchKernelGGL(temporal_accumulate_motion_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo,
-                           nd, prevNd, hist, histLen, motion, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else if (ident)
-        hipLaunchKernelGGL(temporal_accumulate_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
-                           prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else
-        hipLaunchKernelGGL(temporal_accumulate_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, sum, sq, (float)spp, (float)batches, albedo, nd,
-                           prevNd, hist, histLen, (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    TP_HIP_OK(hipGetLastError());
+// The nine instantiations, by source, identity and motion; a tile map takes the ninth (check_temporal_call: the identity path, with
+// a history). Without a history the motion kernels are not chosen: the buffer is not read.
+static int temporal_launch(const TemporalCall& c, hipStream_t stream) {
+    using Kernel = void (*)(TemporalArgs);
+    static const Kernel table[2][2][2] = {
+        {{temporal_kernel<FromSums, false, false, false>, temporal_kernel<FromSums, false, true, false>},
+         {temporal_kernel<FromSums, true, false, false>, temporal_kernel<FromSums, true, true, false>}},
+        {{temporal_kernel<FromCur, false, false, false>, temporal_kernel<FromCur, false, true, false>},
+         {temporal_kernel<FromCur, true, false, false>, temporal_kernel<FromCur, true, true, false>}}};
+    const bool motion = c.motion && c.hist;
+    const Kernel kernel = c.tileLive ? temporal_kernel<FromSums, true, false, true> : table[c.fromCur][temporal_ident(c)][motion];
+    TemporalArgs a = {};
+    a.w = c.w; a.h = c.h;
+    a.cam = temporal_cam(*c.cam); a.prev = temporal_cam(c.prev ? *c.prev : *c.cam);
+    a.sum = (const float4*)c.sum; a.sq = (const float4*)c.sq; a.albedo = (const float4*)c.albedo;
+    a.spp = (float)c.spp; a.batches = (float)c.batches;
+    a.cur = (const float4*)c.cur;
+    a.nd = (const float4*)c.nd; a.prevNd = (const float4*)c.prevNd; a.hist = (const float4*)c.hist; a.histLen = (const float*)c.histLen;
+    a.motion = motion ? (const float4*)c.motion : nullptr;
+    a.tileLive = (const int32_t*)c.tileLive; a.tilesX = (c.w + 7) / 8;
+    a.maxHistory = (float)c.P.max_history; a.depthTol = c.P.depth_tol; a.normalTol = c.P.normal_tol;
+    a.outHist = (float4*)c.outHist; a.outLen = (float*)c.outLen;
+    hipLaunchKernelGGL(kernel, dim3((c.w + 15) / 16, (c.h + 15) / 16), dim3(256), 0, stream, a);
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
-static int temporal_cur_launch(int w, int h, const pt_camera* cam, const pt_camera* prev, const float4* cur, const float4* nd, const float4* prevNd,
-                               const float4* hist, const float* histLen, const pt_temporal_params& P, float4* outHist, float* outLen,
-                               hipStream_t stream, const float4* motion = nullptr) {
-    const bool ident = !prev || memcmp(cam, prev, sizeof(pt_camera)) == 0;
-    const TemporalCam c = temporal_cam(*cam), q = temporal_cam(prev ? *prev : *cam);
-    const dim3 grid((w + 15) / 16, (h + 15) / 16);
-    if (motion && hist && ident)
-        hipLaunchKernelGGL(temporal_accumulate_cur_motion_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen, motion,
-                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else if (motion && hist)
-        hipLaunchKernelGGL(temporal_accumulate_cur_motion_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen, motion,
-                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else if (ident)
-        hipLaunchKernelGGL(temporal_accumulate_cur_kernel<true>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen,
-                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    else
-        hipLaunchKernelGGL(temporal_accumulate_cur_kernel<false>, grid, dim3(256), 0, stream, w, h, c, q, cur, nd, prevNd, hist, histLen,
-                           (float)P.max_history, P.depth_tol, P.normal_tol, outHist, outLen);
-    TP_HIP_OK(hipGetLastError());
-    return 0;
+// Check and launch: on the caller's device buffers, or (host) on staged copies of the slices the call has. The history slices are
+// absent on a first frame, and the motion slice with them (it is not read without a history).
+static int temporal_run(const TemporalCall& c, bool host, hipStream_t stream) {
+    if (int r = check_temporal_call(c)) return r;
+    if (!host) return temporal_launch(c, stream);
+    const size_t n = (size_t)c.w * c.h, b16 = n * 16, tb = (size_t)((c.w + 7) / 8) * ((c.h + 7) / 8) * 4;
+    const HostIn in[] = {{c.sum, b16}, {c.sq, b16}, {c.albedo, b16}, {c.cur, b16}, {c.nd, b16}, {c.prevNd, b16}, {c.hist, b16},
+                         {c.histLen, n * 4}, {c.tileLive, tb}, {c.hist ? c.motion : nullptr, b16}};
+    const HostOut out[] = {{c.outHist, b16}, {c.outLen, n * 4}};
+    return postfx_host_form(c.fn, 0, in, out, [&](char*, char** dIn, char** dOut) {
+        TemporalCall d = c;
+        d.sum = dIn[0]; d.sq = dIn[1]; d.albedo = dIn[2]; d.cur = dIn[3]; d.nd = dIn[4]; d.prevNd = dIn[5]; d.hist = dIn[6]; d.histLen = dIn[7];
+        d.tileLive = dIn[8]; d.motion = dIn[9];
+        d.outHist = dOut[0]; d.outLen = dOut[1];
+        return temporal_launch(d, nullptr);
+    });
 }
 
 }  // namespace pt
@@ -380,145 +321,53 @@ void pt_temporal_defaults(pt_temporal_params* out) {
 int pt_temporal_accumulate_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum, const void* d_sq_sum, int spp,
                                   int batches, const void* d_albedo, const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist,
                                   const void* d_hist_len, const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len, void* stream) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_args(w, h, cam, cam_prev, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, d_prev_normal_depth, d_hist,
-                                    d_hist_len, P, d_out_hist, d_out_hist_len))
-        return r;
-    return temporal_launch(w, h, cam, cam_prev, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
-                           (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth, (const float4*)d_hist, (const float*)d_hist_len, P,
-                           (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream);
-}
-
-// The host forms of pt_temporal_accumulate, pt_temporal_accumulate_live (tileLive set) and pt_temporal_accumulate_motion (motion set).
-static int temporal_host(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum,
-                         int spp, int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
-                         const float* hist_len, const int32_t* tileLive, const pt_temporal_params& P, float* out_hist, float* out_hist_len,
-                         const float* motion = nullptr) {
-    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15, tb = (size_t)((w + 7) / 8) * ((h + 7) / 8) * 4;
-    const bool first = hist == nullptr;
-    if (first) motion = nullptr;                              // (not read without a history)
-    const size_t tbp = tileLive ? (tb + 15) & ~(size_t)15 : 0;
-    char* d = nullptr;
-    TP_HIP_OK(hipMalloc(&d, 7 * b16 + 2 * b4 + tbp + (motion ? b16 : 0)));
-    char* dS = d; char* dQ = dS + b16; char* dA = dQ + b16; char* dN = dA + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16;
-    char* dHL = dO + b16; char* dOL = dHL + b4; char* dT = dOL + b4; char* dM = dT + tbp;
-    hipError_t e = hipMemcpy(dS, rgba_sum, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && tileLive) e = hipMemcpy(dT, tileLive, tb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && motion) e = hipMemcpy(dM, motion, b16, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = tp_fail(-2, fn, "upload failed");
-    } else if ((r = temporal_launch(w, h, cam, cam_prev, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dA, (const float4*)dN,
-                                    first ? nullptr : (const float4*)dPN, first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P,
-                                    (float4*)dO, (float*)dOL, nullptr, tileLive ? (const int32_t*)dT : nullptr,
-                                    motion ? (const float4*)dM : nullptr)) == 0) {
-        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = tp_fail(-2, fn, "download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    TemporalCall c = temporal_call("pt_temporal_accumulate", w, h, cam, cam_prev, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, params,
+                                   d_out_hist, d_out_hist_len);
+    return temporal_run(from_sums(c, d_rgba_sum, d_sq_sum, spp, batches, d_albedo), false, (hipStream_t)stream);
 }
 
 int pt_temporal_accumulate(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
                            int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
                            const float* hist_len, const pt_temporal_params* params, float* out_hist, float* out_hist_len) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
-                                    out_hist, out_hist_len))
-        return r;
-    return temporal_host("pt_temporal_accumulate", w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist,
-                         hist_len, nullptr, P, out_hist, out_hist_len);
+    TemporalCall c = temporal_call("pt_temporal_accumulate", w, h, cam, cam_prev, normal_depth, prev_normal_depth, hist, hist_len, params, out_hist,
+                                   out_hist_len);
+    return temporal_run(from_sums(c, rgba_sum, sq_sum, spp, batches, albedo), true, nullptr);
 }
 
 int pt_temporal_accumulate_live_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum, const void* d_sq_sum,
                                        int spp, int batches, const void* d_albedo, const void* d_normal_depth, const void* d_prev_normal_depth,
                                        const void* d_hist, const void* d_hist_len, const void* d_tile_live, const pt_temporal_params* params,
                                        void* d_out_hist, void* d_out_hist_len, void* stream) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_args(w, h, cam, cam_prev, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, d_prev_normal_depth, d_hist,
-                                    d_hist_len, P, d_out_hist, d_out_hist_len))
-        return r;
-    if (int r = check_live_args(w, h, cam, cam_prev, d_hist, d_tile_live, d_out_hist, d_out_hist_len)) return r;
-    return temporal_launch(w, h, cam, cam_prev, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
-                           (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth, (const float4*)d_hist, (const float*)d_hist_len, P,
-                           (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream, (const int32_t*)d_tile_live);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_live", w, h, cam, cam_prev, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, params,
+                                   d_out_hist, d_out_hist_len);
+    c.tileLive = d_tile_live;
+    return temporal_run(from_sums(c, d_rgba_sum, d_sq_sum, spp, batches, d_albedo), false, (hipStream_t)stream);
 }
 
 int pt_temporal_accumulate_live(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
                                 int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
                                 const float* hist_len, const int32_t* tile_live, const pt_temporal_params* params, float* out_hist,
                                 float* out_hist_len) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
-                                    out_hist, out_hist_len))
-        return r;
-    if (int r = check_live_args(w, h, cam, cam_prev, hist, tile_live, out_hist, out_hist_len)) return r;
-    return temporal_host("pt_temporal_accumulate_live", w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth,
-                         hist, hist_len, tile_live, P, out_hist, out_hist_len);
-}
-
-// The host forms of pt_temporal_accumulate_cur and pt_temporal_accumulate_cur_motion (motion set).
-static int temporal_cur_host(const char* fn, int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
-                             const float* prev_normal_depth, const float* hist, const float* hist_len, const float* motion,
-                             const pt_temporal_params& P, float* out_hist, float* out_hist_len) {
-    const size_t n = (size_t)w * h, b16 = n * 16, b4 = (n * 4 + 15) & ~(size_t)15;
-    const bool first = hist == nullptr;
-    if (first) motion = nullptr;                              // (not read without a history)
-    char* d = nullptr;
-    TP_HIP_OK(hipMalloc(&d, 5 * b16 + 2 * b4 + (motion ? b16 : 0)));
-    char* dC = d; char* dN = dC + b16; char* dPN = dN + b16; char* dH = dPN + b16; char* dO = dH + b16; char* dHL = dO + b16; char* dOL = dHL + b4;
-    char* dM = dOL + b4;
-    hipError_t e = hipMemcpy(dC, cur, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dPN, prev_normal_depth, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dH, hist, b16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !first) e = hipMemcpy(dHL, hist_len, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && motion) e = hipMemcpy(dM, motion, b16, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = tp_fail(-2, fn, "upload failed");
-    } else if ((r = temporal_cur_launch(w, h, cam, cam_prev, (const float4*)dC, (const float4*)dN, first ? nullptr : (const float4*)dPN,
-                                        first ? nullptr : (const float4*)dH, first ? nullptr : (const float*)dHL, P, (float4*)dO, (float*)dOL,
-                                        nullptr, motion ? (const float4*)dM : nullptr)) == 0) {
-        e = hipMemcpy(out_hist, dO, b16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_hist_len, dOL, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = tp_fail(-2, fn, "download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    TemporalCall c = temporal_call("pt_temporal_accumulate_live", w, h, cam, cam_prev, normal_depth, prev_normal_depth, hist, hist_len, params, out_hist,
+                                   out_hist_len);
+    c.tileLive = tile_live;
+    return temporal_run(from_sums(c, rgba_sum, sq_sum, spp, batches, albedo), true, nullptr);
 }
 
 int pt_temporal_accumulate_cur_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur, const void* d_normal_depth,
                                       const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len, const pt_temporal_params* params,
                                       void* d_out_hist, void* d_out_hist_len, void* stream) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, d_cur, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, P, d_out_hist,
-                                        d_out_hist_len))
-        return r;
-    return temporal_cur_launch(w, h, cam, cam_prev, (const float4*)d_cur, (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth,
-                               (const float4*)d_hist, (const float*)d_hist_len, P, (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_cur", w, h, cam, cam_prev, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, params,
+                                   d_out_hist, d_out_hist_len);
+    return temporal_run(from_cur(c, d_cur), false, (hipStream_t)stream);
 }
 
 int pt_temporal_accumulate_cur(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
                                const float* prev_normal_depth, const float* hist, const float* hist_len, const pt_temporal_params* params,
                                float* out_hist, float* out_hist_len) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, P, out_hist, out_hist_len)) return r;
-    return temporal_cur_host("pt_temporal_accumulate_cur", w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, nullptr, P, out_hist,
-                             out_hist_len);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_cur", w, h, cam, cam_prev, normal_depth, prev_normal_depth, hist, hist_len, params, out_hist,
+                                   out_hist_len);
+    return temporal_run(from_cur(c, cur), true, nullptr);
 }
 
 // ---- with a motion buffer (pt_render_motion): motion NULL is the base function ----------------------------------------------------
@@ -526,55 +375,39 @@ int pt_temporal_accumulate_motion_device(int w, int h, const pt_camera* cam, con
                                          int spp, int batches, const void* d_albedo, const void* d_normal_depth, const void* d_prev_normal_depth,
                                          const void* d_hist, const void* d_hist_len, const void* d_motion, const pt_temporal_params* params,
                                          void* d_out_hist, void* d_out_hist_len, void* stream) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_args(w, h, cam, cam_prev, d_rgba_sum, d_sq_sum, spp, batches, d_albedo, d_normal_depth, d_prev_normal_depth, d_hist,
-                                    d_hist_len, P, d_out_hist, d_out_hist_len))
-        return r;
-    if (int r = check_motion_args("pt_temporal_accumulate_motion", w, h, d_motion, d_out_hist, d_out_hist_len)) return r;
-    return temporal_launch(w, h, cam, cam_prev, (const float4*)d_rgba_sum, (const float4*)d_sq_sum, spp, batches, (const float4*)d_albedo,
-                           (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth, (const float4*)d_hist, (const float*)d_hist_len, P,
-                           (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream, nullptr, (const float4*)d_motion);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_motion", w, h, cam, cam_prev, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, params,
+                                   d_out_hist, d_out_hist_len);
+    c.motion = d_motion;
+    return temporal_run(from_sums(c, d_rgba_sum, d_sq_sum, spp, batches, d_albedo), false, (hipStream_t)stream);
 }
 
 int pt_temporal_accumulate_motion(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum, const float* sq_sum, int spp,
                                   int batches, const float* albedo, const float* normal_depth, const float* prev_normal_depth, const float* hist,
                                   const float* hist_len, const float* motion, const pt_temporal_params* params, float* out_hist,
                                   float* out_hist_len) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_args(w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth, hist, hist_len, P,
-                                    out_hist, out_hist_len))
-        return r;
-    if (int r = check_motion_args("pt_temporal_accumulate_motion", w, h, motion, out_hist, out_hist_len)) return r;
-    return temporal_host("pt_temporal_accumulate_motion", w, h, cam, cam_prev, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, prev_normal_depth,
-                         hist, hist_len, nullptr, P, out_hist, out_hist_len, motion);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_motion", w, h, cam, cam_prev, normal_depth, prev_normal_depth, hist, hist_len, params,
+                                   out_hist, out_hist_len);
+    c.motion = motion;
+    return temporal_run(from_sums(c, rgba_sum, sq_sum, spp, batches, albedo), true, nullptr);
 }
 
 int pt_temporal_accumulate_cur_motion_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_cur,
                                              const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist, const void* d_hist_len,
                                              const void* d_motion, const pt_temporal_params* params, void* d_out_hist, void* d_out_hist_len,
                                              void* stream) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, d_cur, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len, P, d_out_hist,
-                                        d_out_hist_len))
-        return r;
-    if (int r = check_motion_args("pt_temporal_accumulate_cur_motion", w, h, d_motion, d_out_hist, d_out_hist_len)) return r;
-    return temporal_cur_launch(w, h, cam, cam_prev, (const float4*)d_cur, (const float4*)d_normal_depth, (const float4*)d_prev_normal_depth,
-                               (const float4*)d_hist, (const float*)d_hist_len, P, (float4*)d_out_hist, (float*)d_out_hist_len, (hipStream_t)stream,
-                               (const float4*)d_motion);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_cur_motion", w, h, cam, cam_prev, d_normal_depth, d_prev_normal_depth, d_hist, d_hist_len,
+                                   params, d_out_hist, d_out_hist_len);
+    c.motion = d_motion;
+    return temporal_run(from_cur(c, d_cur), false, (hipStream_t)stream);
 }
 
 int pt_temporal_accumulate_cur_motion(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* cur, const float* normal_depth,
                                       const float* prev_normal_depth, const float* hist, const float* hist_len, const float* motion,
                                       const pt_temporal_params* params, float* out_hist, float* out_hist_len) {
-    pt_temporal_params P;
-    if (params) P = *params; else pt_temporal_defaults(&P);
-    if (int r = check_temporal_cur_args(w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, P, out_hist, out_hist_len)) return r;
-    if (int r = check_motion_args("pt_temporal_accumulate_cur_motion", w, h, motion, out_hist, out_hist_len)) return r;
-    return temporal_cur_host("pt_temporal_accumulate_cur_motion", w, h, cam, cam_prev, cur, normal_depth, prev_normal_depth, hist, hist_len, motion, P,
-                             out_hist, out_hist_len);
+    TemporalCall c = temporal_call("pt_temporal_accumulate_cur_motion", w, h, cam, cam_prev, normal_depth, prev_normal_depth, hist, hist_len, params,
+                                   out_hist, out_hist_len);
+    c.motion = motion;
+    return temporal_run(from_cur(c, cur), true, nullptr);
 }
 
 }  // extern "C"

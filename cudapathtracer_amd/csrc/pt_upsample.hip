@@ -4,7 +4,7 @@
 // arithmetic; tests/upsample_ref.py restates it in numpy. Stateless, no workspace, no render path involved.
 //
 //   upsample_kernel   one thread per display pixel, 16x16 pixels per workgroup as four 8x8 tiles (one per wave, the tiling of
-//                     temporal_accumulate_kernel and resolve_kernel): a wave's tile reads at most (8 / s + 1)^2 low-res pixels of
+//                     temporal_kernel and resolve_kernel): a wave's tile reads at most (8 / s + 1)^2 low-res pixels of
 //                     each of the four low-res buffers, a few lines. Each tap's working pixel comes from S and Q again
 //                     (dn_var_pixel, shared with denoise_var_prepare_kernel): no prepare pass, no workspace. Plain cached float4
 //                     loads, no LDS.
@@ -13,14 +13,12 @@
 //                     of display pixel (sX, sY) bit for bit.
 // pt_camera_scaled lives here as well: the low-res camera of a scaled frame.
 #include <cmath>
-#include <cstdio>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/pt_api.h"
 #include "pt_denoise_shared.h"
-
-extern "C" int pt_fail_(int code, const char* msg);
+#include "pt_postfx_host.h"
 
 namespace pt {
 
@@ -81,42 +79,22 @@ __global__ void __launch_bounds__(256) guide_subsample_kernel(int w, int wl, int
     ndLo[q] = nd[p];
 }
 
-static int up_fail(int code, const char* fmt, int a = 0, int b = 0, int c = 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), fmt, a, b, c);
-    return pt_fail_(code, buf);
-}
-#define UP_HIP_OK(expr)                                                                                            \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) {                                                                                    \
-            char m_[256]; snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));                 \
-            return pt_fail_(-2, m_);                                                                               \
-        }                                                                                                          \
-    } while (0)
-
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa < pb + bBytes && pb < pa + aBytes;
-}
-
 static int check_upsample_args(int w, int h, int s, const void* sumLo, const void* sqLo, int spp, int batches, const void* albedoLo,
                                const void* ndLo, const void* albedo, const void* nd, const pt_upsample_params& P, const void* out) {
-    if (w <= 0 || h <= 0) return up_fail(-1, "pt_upsample: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return up_fail(-1, "pt_upsample: image of %d x %d pixels is too large", w, h);
-    if (s < 2 || s > 8) return up_fail(-1, "pt_upsample: scale %d must be 2..8", s);
-    if (w % s != 0 || h % s != 0) return up_fail(-1, "pt_upsample: scale %d must divide the image size %d x %d", s, w, h);
-    if (spp <= 0) return up_fail(-1, "pt_upsample: spp %d must be positive", spp);
-    if (batches < 2) return up_fail(-1, "pt_upsample: batches %d must be at least 2", batches);
-    if (spp % batches != 0) return up_fail(-1, "pt_upsample: batches %d must divide spp %d", batches, spp);
-    if (!sumLo || !sqLo || !albedoLo || !ndLo || !albedo || !nd) return up_fail(-1, "pt_upsample: null buffer");
-    if (!out) return up_fail(-1, "pt_upsample: null output");
+    if (int r = postfx_check_size("pt_upsample", w, h)) return r;
+    if (s < 2 || s > 8) return postfx_fail(-1, "pt_upsample: scale %d must be 2..8", s);
+    if (w % s != 0 || h % s != 0) return postfx_fail(-1, "pt_upsample: scale %d must divide the image size %d x %d", s, w, h);
+    if (spp <= 0) return postfx_fail(-1, "pt_upsample: spp %d must be positive", spp);
+    if (batches < 2) return postfx_fail(-1, "pt_upsample: batches %d must be at least 2", batches);
+    if (spp % batches != 0) return postfx_fail(-1, "pt_upsample: batches %d must divide spp %d", batches, spp);
+    if (!sumLo || !sqLo || !albedoLo || !ndLo || !albedo || !nd) return postfx_fail(-1, "pt_upsample: null buffer");
+    if (!out) return postfx_fail(-1, "pt_upsample: null output");
     const size_t full = (size_t)w * h * 16, lo = (size_t)(w / s) * (h / s) * 16;
     if (overlaps(out, full, sumLo, lo) || overlaps(out, full, sqLo, lo) || overlaps(out, full, albedoLo, lo) || overlaps(out, full, ndLo, lo) ||
         overlaps(out, full, albedo, full) || overlaps(out, full, nd, full))
-        return up_fail(-1, "pt_upsample: the output must not alias an input (the gather reads neighbours)");
-    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return up_fail(-1, "pt_upsample: sigma_normal must be finite and >= 0");
-    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return up_fail(-1, "pt_upsample: sigma_depth must be finite and > 0");
+        return postfx_fail(-1, "pt_upsample: the output must not alias an input (the gather reads neighbours)");
+    if (!(P.sigma_normal >= 0.0f) || !std::isfinite(P.sigma_normal)) return postfx_fail(-1, "pt_upsample: sigma_normal must be finite and >= 0");
+    if (!(P.sigma_depth > 0.0f) || !std::isfinite(P.sigma_depth)) return postfx_fail(-1, "pt_upsample: sigma_depth must be finite and > 0");
     return 0;
 }
 
@@ -124,28 +102,27 @@ static int upsample_launch(int w, int h, int s, const float4* sumLo, const float
                            const float4* ndLo, const float4* albedo, const float4* nd, const pt_upsample_params& P, float4* out, hipStream_t stream) {
     hipLaunchKernelGGL(upsample_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, stream, w, h, s, sumLo, sqLo, (float)spp, (float)batches,
                        albedoLo, ndLo, albedo, nd, P.sigma_normal, P.sigma_depth, out);
-    UP_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
 static int check_subsample_args(int w, int h, int s, const void* albedo, const void* nd, const void* outA, const void* outN) {
-    if (w <= 0 || h <= 0) return up_fail(-1, "pt_guide_subsample: image size %d x %d must be positive", w, h);
-    if ((long long)w * h > 0x7fffffffll) return up_fail(-1, "pt_guide_subsample: image of %d x %d pixels is too large", w, h);
-    if (s < 2 || s > 8) return up_fail(-1, "pt_guide_subsample: scale %d must be 2..8", s);
-    if (w % s != 0 || h % s != 0) return up_fail(-1, "pt_guide_subsample: scale %d must divide the image size %d x %d", s, w, h);
-    if (!albedo || !nd) return up_fail(-1, "pt_guide_subsample: null buffer");
-    if (!outA || !outN) return up_fail(-1, "pt_guide_subsample: null output");
+    if (int r = postfx_check_size("pt_guide_subsample", w, h)) return r;
+    if (s < 2 || s > 8) return postfx_fail(-1, "pt_guide_subsample: scale %d must be 2..8", s);
+    if (w % s != 0 || h % s != 0) return postfx_fail(-1, "pt_guide_subsample: scale %d must divide the image size %d x %d", s, w, h);
+    if (!albedo || !nd) return postfx_fail(-1, "pt_guide_subsample: null buffer");
+    if (!outA || !outN) return postfx_fail(-1, "pt_guide_subsample: null output");
     const size_t full = (size_t)w * h * 16, lo = (size_t)(w / s) * (h / s) * 16;
     if (overlaps(outA, lo, albedo, full) || overlaps(outA, lo, nd, full) || overlaps(outN, lo, albedo, full) || overlaps(outN, lo, nd, full) ||
         overlaps(outA, lo, outN, lo))
-        return up_fail(-1, "pt_guide_subsample: the outputs must not alias the inputs or each other");
+        return postfx_fail(-1, "pt_guide_subsample: the outputs must not alias the inputs or each other");
     return 0;
 }
 
 static int subsample_launch(int w, int h, int s, const float4* albedo, const float4* nd, float4* outA, float4* outN, hipStream_t stream) {
     const int wl = w / s, hl = h / s;
     hipLaunchKernelGGL(guide_subsample_kernel, dim3((wl + 63) / 64, (hl + 3) / 4), dim3(256), 0, stream, w, wl, hl, s, albedo, nd, outA, outN);
-    UP_HIP_OK(hipGetLastError());
+    POSTFX_HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -162,10 +139,10 @@ void pt_upsample_defaults(pt_upsample_params* out) {
 }
 
 int pt_camera_scaled(const pt_camera* cam, int scale, pt_camera* out) {
-    if (!cam || !out) return up_fail(-1, "pt_camera_scaled: null camera");
-    if (scale < 1 || scale > 8) return up_fail(-1, "pt_camera_scaled: scale %d must be 1..8", scale);
+    if (!cam || !out) return postfx_fail(-1, "pt_camera_scaled: null camera");
+    if (scale < 1 || scale > 8) return postfx_fail(-1, "pt_camera_scaled: scale %d must be 1..8", scale);
     if (cam->w <= 0 || cam->h <= 0 || cam->w % scale != 0 || cam->h % scale != 0)
-        return up_fail(-1, "pt_camera_scaled: scale %d must divide the camera's size %d x %d", scale, cam->w, cam->h);
+        return postfx_fail(-1, "pt_camera_scaled: scale %d must divide the camera's size %d x %d", scale, cam->w, cam->h);
     *out = *cam;
     out->w = cam->w / scale; out->h = cam->h / scale;
     return 0;
@@ -191,25 +168,12 @@ int pt_upsample(int w, int h, int scale, const float* rgba_sum_lo, const float* 
     if (int r = check_upsample_args(w, h, scale, rgba_sum_lo, sq_sum_lo, spp, batches, albedo_lo, normal_depth_lo, albedo, normal_depth, P, out_cur))
         return r;
     const size_t full = (size_t)w * h * 16, lo = (size_t)(w / scale) * (h / scale) * 16;
-    char* d = nullptr;
-    UP_HIP_OK(hipMalloc(&d, 4 * lo + 3 * full));
-    char* dS = d; char* dQ = dS + lo; char* dAl = dQ + lo; char* dNl = dAl + lo; char* dA = dNl + lo; char* dN = dA + full; char* dO = dN + full;
-    hipError_t e = hipMemcpy(dS, rgba_sum_lo, lo, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dQ, sq_sum_lo, lo, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dAl, albedo_lo, lo, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dNl, normal_depth_lo, lo, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, albedo, full, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, full, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = up_fail(-2, "pt_upsample: upload failed");
-    } else if ((r = upsample_launch(w, h, scale, (const float4*)dS, (const float4*)dQ, spp, batches, (const float4*)dAl, (const float4*)dNl,
-                                    (const float4*)dA, (const float4*)dN, P, (float4*)dO, nullptr)) == 0) {
-        e = hipMemcpy(out_cur, dO, full, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = up_fail(-2, "pt_upsample: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const HostIn in[] = {{rgba_sum_lo, lo}, {sq_sum_lo, lo}, {albedo_lo, lo}, {normal_depth_lo, lo}, {albedo, full}, {normal_depth, full}};
+    const HostOut out[] = {{out_cur, full}};
+    return postfx_host_form("pt_upsample", 0, in, out, [&](char*, char** d, char** o) {
+        return upsample_launch(w, h, scale, (const float4*)d[0], (const float4*)d[1], spp, batches, (const float4*)d[2], (const float4*)d[3],
+                               (const float4*)d[4], (const float4*)d[5], P, (float4*)o[0], nullptr);
+    });
 }
 
 int pt_guide_subsample_device(int w, int h, int scale, const void* d_albedo, const void* d_normal_depth, void* d_out_albedo_lo,
@@ -222,21 +186,11 @@ int pt_guide_subsample_device(int w, int h, int scale, const void* d_albedo, con
 int pt_guide_subsample(int w, int h, int scale, const float* albedo, const float* normal_depth, float* out_albedo_lo, float* out_normal_depth_lo) {
     if (int r = check_subsample_args(w, h, scale, albedo, normal_depth, out_albedo_lo, out_normal_depth_lo)) return r;
     const size_t full = (size_t)w * h * 16, lo = (size_t)(w / scale) * (h / scale) * 16;
-    char* d = nullptr;
-    UP_HIP_OK(hipMalloc(&d, 2 * full + 2 * lo));
-    char* dA = d; char* dN = dA + full; char* dAl = dN + full; char* dNl = dAl + lo;
-    hipError_t e = hipMemcpy(dA, albedo, full, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dN, normal_depth, full, hipMemcpyHostToDevice);
-    int r = 0;
-    if (e != hipSuccess) {
-        r = up_fail(-2, "pt_guide_subsample: upload failed");
-    } else if ((r = subsample_launch(w, h, scale, (const float4*)dA, (const float4*)dN, (float4*)dAl, (float4*)dNl, nullptr)) == 0) {
-        e = hipMemcpy(out_albedo_lo, dAl, lo, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_normal_depth_lo, dNl, lo, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = up_fail(-2, "pt_guide_subsample: download failed");
-    }
-    (void)hipFree(d);
-    return r;
+    const HostIn in[] = {{albedo, full}, {normal_depth, full}};
+    const HostOut out[] = {{out_albedo_lo, lo}, {out_normal_depth_lo, lo}};
+    return postfx_host_form("pt_guide_subsample", 0, in, out, [&](char*, char** d, char** o) {
+        return subsample_launch(w, h, scale, (const float4*)d[0], (const float4*)d[1], (float4*)o[0], (float4*)o[1], nullptr);
+    });
 }
 
 }  // extern "C"

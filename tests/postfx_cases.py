@@ -250,6 +250,50 @@ def check_branches(case, counts, params):
         assert counts["clamped"] >= 1, what
 
 
+# ---- every dispatch target of pt_temporal.hip at a ragged size -------------------------------------------------------------------
+RAGGED = (17, 9)                          # two workgroups in x; 3 x 2 tiles, the last column one pixel wide and the last row one pixel high
+RAGGED_PAIRS = ("same", "sideways")       # the identity and the projecting instantiations
+RAGGED_LIVE = np.array([[1, 0, 1], [0, 1, 0]], np.int32)      # live and carried tiles, of both a partial one
+
+
+def ragged_case(api, name):
+    """temporal_case at RAGGED with what the other entry points need: `working`, the frame's (e, V) as pt_temporal_accumulate_cur
+    takes them, one hit pixel's variance NaN (it passes through there, and nowhere else); `motion`, a synthetic motion buffer: every
+    third pixel that has a right neighbour has w = 1 and the world point of that neighbour's guide as xyz, all others are 0."""
+    w, h = RAGGED
+    case = temporal_case(api, name, w, h)
+    S, Q, A, N = case["frame"]
+    m, e, V, skip = T.frame_ev(S, Q, SPP, BATCHES, A)
+    cur = np.concatenate([np.where(skip[..., None], m, e), np.where(skip, f32(-1), V)[..., None]], -1).astype(f32)
+    ys, xs = np.nonzero(~skip)
+    cur[ys[ys.size // 3], xs[ys.size // 3], 3] = np.nan
+    o, d = centre_rays(case["cur"])
+    P = o + d * N[..., 3:4].astype(np.float64)
+    idx = np.arange(h * w).reshape(h, w)
+    moved = (idx % 3 == 1) & (idx % w < w - 1)
+    motion = np.zeros((h, w, 4), f32)
+    motion[moved, :3] = np.roll(P, -1, axis=1)[moved]
+    motion[moved, 3] = 1
+    return dict(case, working=cur, motion=motion)
+
+
+def check_ragged_case(case, motion_len):
+    """What the restatement's result with the motion buffer (its lengths) and the map must show, so that the kernels' agreement
+    with it says something: moved pixels that found history and one that did not, partial tiles of both kinds, a pass-through pixel
+    in a live tile."""
+    w, h = RAGGED
+    moved = case["motion"][..., 3] == 1
+    assert (moved & (motion_len > 1)).sum() >= 4 and (moved & (motion_len == 1)).sum() >= 1
+    ty, tx = RAGGED_LIVE.shape
+    assert (ty, tx) == ((h + 7) // 8, (w + 7) // 8) and (w % 8 or h % 8)
+    partial = np.zeros((ty, tx), bool)
+    if w % 8: partial[:, -1] = True
+    if h % 8: partial[-1, :] = True
+    assert (partial & (RAGGED_LIVE != 0)).any() and (partial & (RAGGED_LIVE == 0)).any()
+    live = np.repeat(np.repeat(RAGGED_LIVE != 0, 8, axis=0), 8, axis=1)[:h, :w]
+    assert ((motion_len == 0) & live).any()
+
+
 # ---- upsample ------------------------------------------------------------------------------------------------------------------------
 UPSAMPLE_SHAPES = ((1, 1, 8), (2, 3, 8), (7, 5, 5))          # (wl, hl, s)
 

@@ -116,6 +116,21 @@ def test_every_pair_reaches_its_branch_in_the_restatement(api, name, w, h):
         assert ln.max() <= min(params["max_history"], C.HIST_LEN_SCALE + 1) + 1e-3
 
 
+@pytest.mark.parametrize("name", C.RAGGED_PAIRS)
+def test_the_ragged_dispatch_case_in_the_restatement(api, name):
+    """The motion buffer and the map of test_every_entry_point_at_a_ragged_size reach what they are made for."""
+    import motion_ref as M
+    case = C.ragged_case(api, name)
+    S, Q, A, N = case["frame"]
+    history = (case["prev_nd"], case["hist"], case["hist_len"])
+    out, ln, fragile = M.accumulate(case["cur"], case["prev"], S, Q, C.SPP, C.BATCHES, A, N, *history, motion=case["motion"])
+    C.check_ragged_case(case, ln)
+    base_len = T.accumulate(case["cur"], case["prev"], S, Q, C.SPP, C.BATCHES, A, N, *history)[1]
+    assert (ln != base_len).any()                               # the buffer changes the result
+    cur_out = M.accumulate_cur(case["cur"], case["prev"], case["working"], N, *history)[0]
+    assert ((cur_out[..., 3] < 0) & ~(out[..., 3] < 0)).sum() == 1      # the NaN variance passes through
+
+
 @pytest.mark.parametrize("w,h", [(17, 9), (61, 43)])
 def test_the_behind_pair_tells_the_sign_of_zc(api, monkeypatch, w, h):
     """A restatement that takes z_c != 0 for z_c > 0 finds history for slab pixels that lay behind the previous camera (their mirrored

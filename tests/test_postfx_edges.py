@@ -1,6 +1,6 @@
 """The post-process kernels on the GPU against their numpy restatements at ragged sizes, edge cameras and their own parameters:
-pt_denoise, pt_denoise_var, pt_denoise_hist (denoise_ref, denoise_var_ref, temporal_ref.denoise_hist), pt_temporal_accumulate, _cur
-and _live (temporal_ref, upsample_ref.accumulate_cur) and pt_upsample (upsample_ref), on the analytic frames of tests/postfx_cases.py.
+pt_denoise, pt_denoise_var, pt_denoise_hist (denoise_ref, denoise_var_ref, temporal_ref.denoise_hist), pt_temporal_accumulate, _cur,
+_live, _motion and _cur_motion (temporal_ref, upsample_ref.accumulate_cur, converge_ref, motion_ref) and pt_upsample (upsample_ref), on the analytic frames of tests/postfx_cases.py.
 
 Nothing is rendered and no scene is loaded: every case goes through the host form of the API, one allocation, a few small copies and
 the launches. The comparisons and tolerances are those of test_denoise.py, test_denoise_var.py, test_temporal.py and test_upsample.py;
@@ -225,6 +225,60 @@ def test_accumulate_with_a_map_at_a_ragged_size(api, gpu_ready):
     assert (full_len[~m] != ln[~m]).any() and (full_len[m] != ln[m]).any()
     want_len = R.accumulate_live(case["cur"], S, Qm, SPP, BATCHES, A, N, case["prev_nd"], hist, ln, live)[1]
     assert_bits_equal(got_len, want_len, "restatement: hist_len")
+
+
+def test_every_entry_point_at_a_ragged_size(api, gpu_ready):
+    """All nine instantiations of temporal_kernel share one pixel map and one argument block: each entry point, host and device form,
+    at 17 x 9 (two workgroups in x, partial tiles in both directions) on the identity and on a projecting pair, bit for bit against
+    the numpy restatements, with the planted pass-through and NaN pixels, a synthetic motion buffer and a map of live tiles."""
+    import motion_ref as M
+    torch = gpu_ready
+    w, h = C.RAGGED
+    for name in C.RAGGED_PAIRS:
+        case = C.ragged_case(api, name)
+        cam, prev, (S, Qm, A, N), cur, mv = case["cur"], case["prev"], case["frame"], case["working"], case["motion"]
+        history = (case["prev_nd"], case["hist"], case["hist_len"])
+        sums = (S, Qm, SPP, BATCHES, A, N)
+        want = {"accumulate": T.accumulate(cam, prev, *sums, *history)[:2],
+                "accumulate_cur": M.accumulate_cur(cam, prev, cur, N, *history)[:2],
+                "accumulate_motion": M.accumulate(cam, prev, *sums, *history, motion=mv)[:2],
+                "accumulate_cur_motion": M.accumulate_cur(cam, prev, cur, N, *history, motion=mv)[:2]}
+        C.check_ragged_case(case, want["accumulate_motion"][1])          # (on the CPU, before the GPU is asked anything)
+        host = {"accumulate": api.temporal_accumulate(cam, *sums, prev, *history),
+                "accumulate_cur": api.temporal_accumulate_cur(cam, cur, N, prev, *history),
+                "accumulate_motion": api.temporal_accumulate_motion(cam, *sums, prev, *history, mv),
+                "accumulate_cur_motion": api.temporal_accumulate_cur_motion(cam, cur, N, prev, *history, mv),
+                "motion NULL": api.temporal_accumulate_motion(cam, *sums, prev, *history, None),
+                "map NULL": api.temporal_accumulate_live(cam, *sums, *history, None, prev)}
+        dev = lambda a: torch.from_numpy(a.copy()).to("cuda:0")
+        p = lambda t: t.data_ptr()
+        dS, dQ, dA, dN, dC, dM, dPN, dH, dL = (dev(a) for a in (S, Qm, A, N, cur, mv) + history)
+        dsums, dhist = (p(dS), p(dQ), SPP, BATCHES, p(dA), p(dN)), (p(dPN), p(dH), p(dL))
+        outs = {k: (torch.full((h, w, 4), 3.0, device="cuda:0"), torch.full((h, w), 3.0, device="cuda:0")) for k in list(host) + ["accumulate_live"]}
+        o = lambda k: (p(outs[k][0]), p(outs[k][1]))
+        api.temporal_accumulate_device(w, h, cam, prev, *dsums, *dhist, *o("accumulate"))
+        api.temporal_accumulate_cur_device(w, h, cam, prev, p(dC), p(dN), *dhist, *o("accumulate_cur"))
+        api.temporal_accumulate_motion_device(w, h, cam, prev, *dsums, *dhist, p(dM), *o("accumulate_motion"))
+        api.temporal_accumulate_cur_motion_device(w, h, cam, prev, p(dC), p(dN), *dhist, p(dM), *o("accumulate_cur_motion"))
+        api.temporal_accumulate_motion_device(w, h, cam, prev, *dsums, *dhist, 0, *o("motion NULL"))
+        api.temporal_accumulate_live_device(w, h, cam, prev, *dsums, *dhist, 0, *o("map NULL"))
+        if name == "same":
+            want["accumulate_live"] = R.accumulate_live(cam, *sums, *history, C.RAGGED_LIVE)
+            host["accumulate_live"] = api.temporal_accumulate_live(cam, *sums, *history, C.RAGGED_LIVE, prev)
+            dT = dev(C.RAGGED_LIVE)
+            api.temporal_accumulate_live_device(w, h, cam, prev, *dsums, *dhist, p(dT), *o("accumulate_live"))
+        torch.cuda.synchronize()
+        for k in host:
+            got = (outs[k][0].cpu().numpy(), outs[k][1].cpu().numpy())
+            ref = want[k if k in want else "accumulate"]                 # motion NULL and a NULL map are the base entry
+            for form, res in (("host", host[k]), ("device", got)):
+                what = "%s, %s, %s form" % (name, k, form)
+                differ = (res[0].view(np.uint32) != ref[0].view(np.uint32)).any(-1) | (res[1].view(np.uint32) != ref[1].view(np.uint32))
+                print("%s: %d of %d pixels differ from the restatement" % (what, int(differ.sum()), w * h))
+                assert_bits_equal(res[0], ref[0], what + ": hist"); assert_bits_equal(res[1], ref[1], what + ": hist_len")
+                if k in ("motion NULL", "map NULL"):
+                    assert_bits_equal(res[0], host["accumulate"][0], what + " against the base entry: hist")
+                    assert_bits_equal(res[1], host["accumulate"][1], what + " against the base entry: hist_len")
 
 
 # ---- c. upsample -------------------------------------------------------------------------------------------------------------------------

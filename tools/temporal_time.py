@@ -3,7 +3,9 @@
     python tools/temporal_time.py [--w 1920 --h 1080 --reps 20] [--specular [--max-links 8]]
 
 Prints one JSON line: median / min milliseconds of pt_temporal_accumulate_device for a still camera (the identity instantiation)
-and for a moving one (projection and four taps), of pt_denoise_hist_device at its default iterations and, in the same run for
+and for a moving one (projection and four taps); the same two of _cur_device (the frames' own (e, V) as `cur`), of _motion_device
+(a seeded motion buffer: a tenth of the pixels moved, to points inside the box) and of _cur_motion_device, and of _live_device with
+every other tile live (accumulate_cur_*, accumulate_motion_*, accumulate_cur_motion_*, accumulate_live_half); of pt_denoise_hist_device at its default iterations and, in the same run for
 comparison, of pt_denoise_var_device at its defaults; the bytes the accumulate pass moves per pixel (64 B of this frame's four
 buffers, 20 B written, plus the previous guide, history and length once: 36 B, the gathers of neighbouring pixels share their
 lines) and the fraction of the 8 TB/s HBM peak that makes at the measured time.
@@ -79,6 +81,32 @@ def measure(a, torch, api, sc, links):
         return lambda: api.temporal_accumulate_device(w, h, cam, cam0, p(f[0]), p(f[1]), 4, 2, p(f[2]), p(f[3]), p(f0[3]), p(hist0), p(len0),
                                                       p(hist1), p(len1), stream=stream)
 
+    def own_ev(cam, f):                                        # a frame's (e, V): what its first frame leaves as the history
+        cur, ln = buf(), torch.empty(h, w, device="cuda:0")
+        api.temporal_accumulate_device(w, h, cam, None, p(f[0]), p(f[1]), 4, 2, p(f[2]), p(f[3]), 0, 0, 0, p(cur), p(ln), stream=stream)
+        return cur
+
+    gen = torch.Generator(device="cuda:0").manual_seed(7)
+    motion = torch.rand(h, w, 4, device="cuda:0", generator=gen) * 1.6 - 0.8
+    motion[..., 3] = (torch.rand(h, w, device="cuda:0", generator=gen) < 0.1).float()
+    ty, tx = (h + 7) // 8, (w + 7) // 8
+    half = ((torch.arange(ty, device="cuda:0")[:, None] + torch.arange(tx, device="cuda:0")[None, :]) % 2).to(torch.int32).contiguous()
+    history = (p(f0[3]), p(hist0), p(len0))
+
+    def variants(tag, cam, f):
+        cur = own_ev(cam, f)
+        sums = (p(f[0]), p(f[1]), 4, 2, p(f[2]), p(f[3]))
+        return [("accumulate_cur_" + tag, lambda: api.temporal_accumulate_cur_device(w, h, cam, cam0, p(cur), p(f[3]), *history, p(hist1), p(len1),
+                                                                                      stream=stream)),
+                ("accumulate_motion_" + tag, lambda: api.temporal_accumulate_motion_device(w, h, cam, cam0, *sums, *history, p(motion), p(hist1),
+                                                                                            p(len1), stream=stream)),
+                ("accumulate_cur_motion_" + tag, lambda: api.temporal_accumulate_cur_motion_device(w, h, cam, cam0, p(cur), p(f[3]), *history,
+                                                                                                    p(motion), p(hist1), p(len1), stream=stream))]
+
+    def live_half():
+        api.temporal_accumulate_live_device(w, h, cam0, cam0, p(f_still[0]), p(f_still[1]), 4, 2, p(f_still[2]), p(f_still[3]), *history, p(half),
+                                            p(hist1), p(len1), stream=stream)
+
     def dn_hist():
         api.denoise_hist_device(w, h, p(hist1), p(f_moved[2]), p(f_moved[3]), p(ws), p(out), stream=stream)
 
@@ -88,6 +116,7 @@ def measure(a, torch, api, sc, links):
     res = {"w": w, "h": h, "iterations_default": api.denoise_var_defaults()["iterations"], "accumulate_bytes_per_pixel": BYTES_PER_PIXEL}
     timed = [("accumulate_identity", accumulate(cam0, f_still)), ("accumulate_moving", accumulate(cam1, f_moved)),
              ("denoise_hist", dn_hist), ("denoise_var", dn_var)]
+    timed += variants("identity", cam0, f_still) + variants("moving", cam1, f_moved) + [("accumulate_live_half", live_half)]
     if a.specular:
         fa, fn_ = buf(), buf()
         timed.insert(0, ("feature_pass", lambda: aovs(cam1, fa, fn_, 2)))
@@ -104,7 +133,7 @@ def measure(a, torch, api, sc, links):
         ts.sort()
         res[name + "_ms_median"] = round(ts[len(ts) // 2], 4)
         res[name + "_ms_min"] = round(ts[0], 4)
-        if name.startswith("accumulate"):
+        if name in ("accumulate_identity", "accumulate_moving"):
             res[name + "_hbm_fraction"] = round(BYTES_PER_PIXEL * w * h / (ts[len(ts) // 2] * 1e-3) / HBM_PEAK, 4)
             res[name + "_mean_length"] = round(float(len1.mean()), 3)
     return res
