@@ -966,13 +966,30 @@ def denoise_defaults():
     return {f: getattr(p, f) for f, _ in DenoiseParams._fields_}
 
 
-def _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth):
-    p = DenoiseParams()
-    lib().pt_denoise_defaults(C.byref(p))
-    for f, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+def _filter_params(struct, defaults, **given):
+    """A pt_denoise_params or pt_denoise_var_params: the library's defaults, then every parameter that is not None."""
+    p = struct()
+    defaults(C.byref(p))
+    for f, v in given.items():
         if v is not None:
             setattr(p, f, v)
     return p
+
+
+def _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth):
+    return _filter_params(DenoiseParams, lib().pt_denoise_defaults, iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal,
+                          sigma_depth=sigma_depth)
+
+
+def _denoise_call(what, frame, out, call):
+    """What the host form pt_<what> of a filter does once its arrays are checked: `out`, or a new array like `frame` (the input it
+    may alias), checked; then call(w, h, out pointer), which returns the library's status."""
+    h, w = frame.shape[:2]
+    res = np.empty_like(frame) if out is None else out
+    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == frame.shape and res.flags.c_contiguous):
+        raise PtError("%s: out must be a C-contiguous float32 array of shape %s" % (what, frame.shape))
+    _check(call(w, h, _p(res)), "pt_" + what)
+    return res
 
 
 def denoise_workspace_bytes(w, h):
@@ -983,20 +1000,9 @@ def denoise(rgba_sum, spp, albedo, normal_depth, iterations=None, sigma_color=No
     """pt_denoise (host, blocking): the a-trous filter guided by render_aovs' buffers. rgba_sum is the radiance SUM of
     `spp` samples as pt_render leaves it ([h,w,4] float32); returns the same units. A None parameter takes the library
     default (denoise_defaults()). `out` may be rgba_sum itself."""
-    arrs = []
-    for name, a in (("rgba_sum", rgba_sum), ("albedo", albedo), ("normal_depth", normal_depth)):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or a.shape[2] != 4:
-            raise PtError("denoise: %s must be a float32 [h, w, 4] array" % name)
-        arrs.append(np.ascontiguousarray(a))
-    if arrs[1].shape != arrs[0].shape or arrs[2].shape != arrs[0].shape:
-        raise PtError("denoise: shapes differ: %s, %s, %s" % tuple(a.shape for a in arrs))
-    h, w = arrs[0].shape[:2]
-    res = np.empty_like(arrs[0]) if out is None else out
-    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == arrs[0].shape and res.flags.c_contiguous):
-        raise PtError("denoise: out must be a C-contiguous float32 array of shape %s" % (arrs[0].shape,))
-    p = _denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)
-    _check(lib().pt_denoise(w, h, _p(arrs[0]), int(spp), _p(arrs[1]), _p(arrs[2]), C.byref(p), _p(res)), "pt_denoise")
-    return res
+    S, A, N = _f4_frames("denoise", (("rgba_sum", rgba_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
+    return _denoise_call("denoise", S, out, lambda w, h, res: lib().pt_denoise(
+        w, h, _p(S), int(spp), _p(A), _p(N), C.byref(_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)), res))
 
 
 def denoise_device(w, h, d_rgba_sum_ptr, spp, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr, d_out_ptr, iterations=None,
@@ -1016,12 +1022,8 @@ def denoise_var_defaults():
 
 
 def _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth):
-    p = DenoiseVarParams()
-    lib().pt_denoise_var_defaults(C.byref(p))
-    for f, v in (("iterations", iterations), ("sigma_var", sigma_var), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
-        if v is not None:
-            setattr(p, f, v)
-    return p
+    return _filter_params(DenoiseVarParams, lib().pt_denoise_var_defaults, iterations=iterations, sigma_var=sigma_var, sigma_normal=sigma_normal,
+                          sigma_depth=sigma_depth)
 
 
 def denoise_var_workspace_bytes(w, h):
@@ -1034,21 +1036,9 @@ def denoise_var(rgba_sum, sq_sum, spp, batches, albedo, normal_depth, iterations
     what Scene.render_moments returned for `spp` samples in `batches` batches ([h,w,4] float32); albedo and normal_depth come
     from render_aovs. Returns the filtered radiance sum. A None parameter takes the library default
     (denoise_var_defaults()). `out` may be rgba_sum itself."""
-    arrs = []
-    for name, a in (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or a.shape[2] != 4:
-            raise PtError("denoise_var: %s must be a float32 [h, w, 4] array" % name)
-        arrs.append(np.ascontiguousarray(a))
-    if any(a.shape != arrs[0].shape for a in arrs[1:]):
-        raise PtError("denoise_var: shapes differ: %s, %s, %s, %s" % tuple(a.shape for a in arrs))
-    h, w = arrs[0].shape[:2]
-    res = np.empty_like(arrs[0]) if out is None else out
-    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == arrs[0].shape and res.flags.c_contiguous):
-        raise PtError("denoise_var: out must be a C-contiguous float32 array of shape %s" % (arrs[0].shape,))
-    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
-    _check(lib().pt_denoise_var(w, h, _p(arrs[0]), _p(arrs[1]), int(spp), int(batches), _p(arrs[2]), _p(arrs[3]), C.byref(p), _p(res)),
-           "pt_denoise_var")
-    return res
+    S, Q, A, N = _f4_frames("denoise_var", tuple(zip(_SUMS, (rgba_sum, sq_sum, albedo, normal_depth))))
+    return _denoise_call("denoise_var", S, out, lambda w, h, res: lib().pt_denoise_var(
+        w, h, _p(S), _p(Q), int(spp), int(batches), _p(A), _p(N), C.byref(_denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)), res))
 
 
 def denoise_var_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr, d_out_ptr,
@@ -1070,17 +1060,13 @@ def denoise_var_tiles(rgba_sum, sq_sum, tile_spp, batch_spp, albedo, normal_dept
     [ceil(h/8), ceil(w/8)]) are what Scene.render_adaptive_moments returned with chunk_spp = batch_spp; albedo and normal_depth come
     from render_aovs*. Returns the filtered radiance sum in the units of rgba_sum: adaptive_mean(result, tile_spp) and
     resolve(result, tile_spp=tile_spp) apply as to the raw frame. `out` may be rgba_sum itself."""
-    arrs = _f4_frames("denoise_var_tiles", (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("normal_depth", normal_depth)))
-    h, w = arrs[0].shape[:2]
+    S, Q, A, N = _f4_frames("denoise_var_tiles", tuple(zip(_SUMS, (rgba_sum, sq_sum, albedo, normal_depth))))
+    h, w = S.shape[:2]
     if not isinstance(tile_spp, np.ndarray) or tile_spp.dtype != np.int32 or tile_spp.shape != ((h + 7) // 8, (w + 7) // 8):
         raise PtError("denoise_var_tiles: tile_spp must be an int32 [%d, %d] array for a %d x %d frame" % ((h + 7) // 8, (w + 7) // 8, w, h))
-    res = np.empty_like(arrs[0]) if out is None else out
-    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == arrs[0].shape and res.flags.c_contiguous):
-        raise PtError("denoise_var_tiles: out must be a C-contiguous float32 array of shape %s" % (arrs[0].shape,))
-    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
-    _check(lib().pt_denoise_var_tiles(w, h, _p(arrs[0]), _p(arrs[1]), _p(np.ascontiguousarray(tile_spp)), int(batch_spp), _p(arrs[2]),
-                                      _p(arrs[3]), C.byref(p), _p(res)), "pt_denoise_var_tiles")
-    return res
+    return _denoise_call("denoise_var_tiles", S, out, lambda w, h, res: lib().pt_denoise_var_tiles(
+        w, h, _p(S), _p(Q), _p(np.ascontiguousarray(tile_spp)), int(batch_spp), _p(A), _p(N),
+        C.byref(_denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)), res))
 
 
 def denoise_var_tiles_device(w, h, d_rgba_sum_ptr, d_sq_sum_ptr, d_tile_spp_ptr, batch_spp, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr,
@@ -1383,13 +1369,8 @@ def denoise_hist(hist, albedo, normal_depth, iterations=None, sigma_var=None, si
     frame's albedo and normal_depth. Returns the per-pixel radiance MEAN ([h,w,4] float32, w = 0): finalise(..., 1) applies.
     `out` may be hist itself."""
     H, A, N = _f4_frames("denoise_hist", (("hist", hist), ("albedo", albedo), ("normal_depth", normal_depth)))
-    h, w = H.shape[:2]
-    res = np.empty_like(H) if out is None else out
-    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == H.shape and res.flags.c_contiguous):
-        raise PtError("denoise_hist: out must be a C-contiguous float32 array of shape %s" % (H.shape,))
-    p = _denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)
-    _check(lib().pt_denoise_hist(w, h, _p(H), _p(A), _p(N), C.byref(p), _p(res)), "pt_denoise_hist")
-    return res
+    return _denoise_call("denoise_hist", H, out, lambda w, h, res: lib().pt_denoise_hist(
+        w, h, _p(H), _p(A), _p(N), C.byref(_denoise_var_params(iterations, sigma_var, sigma_normal, sigma_depth)), res))
 
 
 def denoise_hist_device(w, h, d_hist_ptr, d_albedo_ptr, d_normal_depth_ptr, d_workspace_ptr, d_out_ptr, iterations=None, sigma_var=None,

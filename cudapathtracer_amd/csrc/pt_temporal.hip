@@ -3,11 +3,11 @@
 // tests/temporal_ref.py restates it in numpy. Opt-in post-process on buffers: stateless, no workspace, no render path involved.
 //
 //   temporal_kernel<Source, IDENT, MOTION, LIVE>   the one kernel of all ten entry points: one thread per pixel, 16x16 pixels per
-//                 workgroup as four 8x8 tiles (one per wave, the tiling of denoise_var_iter_kernel: a wave's four gathers fall
+//                 workgroup as four 8x8 tiles (one per wave, the tiling of dn_atrous_kernel: a wave's four gathers fall
 //                 into a few lines). The pixel's working value (e, V), then temporal_blend: its world point from its depth along
 //                 the unjittered centre ray, projected into the previous camera; up to four bilinear taps of the previous history,
 //                 each checked against the previous guide; the blend.
-//       Source    FromSums: (e, V) from S and Q (dn_var_pixel, shared with denoise_var_prepare_kernel). FromCur: read from a
+//       Source    FromSums: (e, V) from S and Q (dn_var_pixel, shared with dn_prepare_kernel's VarSource). FromCur: read from a
 //                 buffer (pt_upsample's output). Each says which pixels pass through and what they write.
 //       IDENT     both cameras are the same bytes: the tap is the pixel itself and no projection is computed.
 //       MOTION    a motion buffer (pt_render_motion): a pixel whose motion.w is 1 reprojects the point the buffer names — where its

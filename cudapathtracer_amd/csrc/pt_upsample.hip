@@ -6,7 +6,7 @@
 //   upsample_kernel   one thread per display pixel, 16x16 pixels per workgroup as four 8x8 tiles (one per wave, the tiling of
 //                     temporal_kernel and resolve_kernel): a wave's tile reads at most (8 / s + 1)^2 low-res pixels of
 //                     each of the four low-res buffers, a few lines. Each tap's working pixel comes from S and Q again
-//                     (dn_var_pixel, shared with denoise_var_prepare_kernel): no prepare pass, no workspace. Plain cached float4
+//                     (dn_var_pixel, shared with dn_prepare_kernel's VarSource): no prepare pass, no workspace. Plain cached float4
 //                     loads, no LDS.
 //   guide_subsample_kernel   the low-res guide of CENTRE feature buffers (pt_guide_subsample): out[Y][X] = in[sY][sX] for both buffers,
 //                     one thread per low-res pixel. A strided copy, because the centre ray of low-res pixel (X, Y) is the centre ray
@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(256) upsample_kernel(int w, int h, int s, cons
     const bool hitP = albedo[p].w > 0.0f;
     const float4 gp = dn_unit_guide(nd[p]);
     const bool normalP = gp.x != 0.0f || gp.y != 0.0f || gp.z != 0.0f;
-    const float kz = 1.4426950408889634f / (sigmaDepth * gp.w);             // w_z = exp2(-|dz| kz), as denoise_var_iter_kernel forms it
+    const float kz = 1.4426950408889634f / (sigmaDepth * gp.w);             // w_z = exp2(-|dz| kz), as dn_atrous_kernel forms it
     float4 candM = make_float4(0.0f, 0.0f, 0.0f, 0.0f), useE = candM;       // the nearest candidate's raw mean, the nearest usable tap's (e, V)
     float candB = 0.0f, useB = 0.0f;                                        // (b > 0 for both kinds of tap: 0 = none yet)
     float sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f, sw = 0.0f;

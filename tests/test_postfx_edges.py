@@ -281,6 +281,59 @@ def test_every_entry_point_at_a_ragged_size(api, gpu_ready):
                     assert_bits_equal(res[1], host["accumulate"][1], what + " against the base entry: hist_len")
 
 
+def test_every_filter_entry_at_a_ragged_size(api, gpu_ready, filter_frames):
+    """The four filters share dn_prepare_kernel, dn_atrous_kernel and dn_finish_kernel, picked from one table: each entry point at
+    17 x 9 (two workgroups in x, partial tiles in both directions, 41 of 153 pixels pass-through) with one iteration, the default
+    count and every parameter off its default. Bit for bit: (a) the host form against the device form, (b) the device form with out
+    = in against it, (c) denoise_var_tiles with a uniform map against denoise_var, (d) denoise_var against SPP times denoise_hist of
+    the frame's own (e, V) on the filtered pixels' rgb: the same reduce and a-trous kernels behind two prepare and finish sources
+    (SPP = 4 scales exactly, and test_temporal shows the restatement's first-frame (e, V) bit-equal to the device's dn_var_pixel)."""
+    torch = gpu_ready
+    w, h = C.RAGGED
+    S, Q, A, N = filter_frames[(w, h)]
+    hist = C.history_of(S, Q, A, N)
+    skip = T.frame_ev(S, Q, SPP, BATCHES, A)[3]
+    assert np.array_equal(skip, hist[..., 3] < 0) and int(skip.sum()) == 41 and skip.size == 153      # one pass-through set
+    tm = np.full(((h + 7) // 8, (w + 7) // 8), SPP, np.int32)
+    dev = lambda a: torch.from_numpy(a.copy()).to("cuda:0")
+    dQ, dA, dN, dT = (dev(a) for a in (Q, A, N, tm))
+    # name: (host form, device form, their input, its arguments between w, h and the workspace: in is a place holder)
+    entries = {"denoise": (api.denoise, api.denoise_device, S, lambda i: (i, SPP, dA.data_ptr(), dN.data_ptr()), (S, SPP, A, N)),
+               "denoise_var": (api.denoise_var, api.denoise_var_device, S,
+                               lambda i: (i, dQ.data_ptr(), SPP, BATCHES, dA.data_ptr(), dN.data_ptr()), (S, Q, SPP, BATCHES, A, N)),
+               "denoise_var_tiles": (api.denoise_var_tiles, api.denoise_var_tiles_device, S,
+                                     lambda i: (i, dQ.data_ptr(), dT.data_ptr(), SPP // BATCHES, dA.data_ptr(), dN.data_ptr()),
+                                     (S, Q, tm, SPP // BATCHES, A, N)),
+               "denoise_hist": (api.denoise_hist, api.denoise_hist_device, hist, lambda i: (i, dA.data_ptr(), dN.data_ptr()), (hist, A, N))}
+    ws = torch.empty(api.denoise_workspace_bytes(w, h), dtype=torch.uint8, device="cuda:0")
+    assert all(getattr(api, k + "_workspace_bytes")(w, h) == ws.numel() for k in entries)
+    plain = {name: e[0](*e[4], iterations=0) for name, e in entries.items()}
+    for var_kw in ({"iterations": 1}, {}, C.VAR_OFF):
+        got = {}
+        for name, (host_form, device_form, src, dargs, hargs) in entries.items():
+            kw = C.DENOISE_OFF if name == "denoise" and var_kw is C.VAR_OFF else var_kw
+            what = "%s %s" % (name, kw or "defaults")
+            got[name] = host_form(*hargs, **kw)
+            dIn, out = dev(src), torch.full((h, w, 4), 3.0, device="cuda:0")
+            device_form(w, h, *dargs(dIn.data_ptr()), ws.data_ptr(), out.data_ptr(), **kw)
+            device_form(w, h, *dargs(dIn.data_ptr()), ws.data_ptr(), dIn.data_ptr(), **kw)
+            torch.cuda.synchronize()
+            apart, inplace = out.cpu().numpy(), dIn.cpu().numpy()
+            for other, res in (("device form", apart), ("device form, out = in", inplace)):
+                differ = (res.view(np.uint32) != got[name].view(np.uint32)).any(-1)
+                print("%s: %d of %d pixels differ between the host form and the %s" % (what, int(differ.sum()), w * h, other))
+            assert_bits_equal(apart, got[name], what + ": (a) host form against device form")
+            assert_bits_equal(inplace, apart, what + ": (b) out = in against out apart")
+            assert not np.array_equal(got[name], plain[name]), what                     # the filter ran
+        assert_bits_equal(got["denoise_var_tiles"], got["denoise_var"], "(c) a uniform map, %s" % (var_kw or "defaults"))
+        assert_bits_equal(got["denoise_var"][skip], S[skip], "pass-through pixels of denoise_var")
+        assert_bits_equal(got["denoise_hist"][skip][:, :3], hist[skip][:, :3], "pass-through pixels of denoise_hist")
+        scaled = (f32(SPP) * got["denoise_hist"][~skip][:, :3]).astype(f32)
+        differ = (scaled.view(np.uint32) != np.ascontiguousarray(got["denoise_var"][~skip][:, :3]).view(np.uint32)).any(-1)
+        print("(d) %s: %d of %d filtered pixels differ between denoise_var and SPP * denoise_hist" % (var_kw or "defaults", int(differ.sum()), differ.size))
+        assert_bits_equal(got["denoise_var"][~skip][:, :3], scaled, "(d) denoise_var against SPP * denoise_hist, %s" % (var_kw or "defaults"))
+
+
 # ---- c. upsample -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("yawed", [False, True])
 @pytest.mark.parametrize("wl,hl,s", C.UPSAMPLE_SHAPES)

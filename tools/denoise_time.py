@@ -1,13 +1,16 @@
 """Device time of the feature-buffer pass and of the denoiser at 1920x1080 (HIP events around each, after warm-up).
 
     python tools/denoise_time.py [--w 1920 --h 1080 --reps 20 --aov-spp 1 --iterations 5 --scene cornell|mixed|blob --max-links 8 --centre]
-    python tools/denoise_time.py --resources          (no device needed: compiles pt_aov.hip and prints its kernels' registers)
+    python tools/denoise_time.py --resources          (no device needed: compiles pt_aov.hip and pt_denoise.hip and prints their
+                                                       kernels' registers, scratch and LDS)
 
 Prints one JSON line: median / min milliseconds of pt_render_aovs_device, of pt_render_aovs_chain_device (`aov_chain`: the pass that
 follows mirrors and glass, --max-links links; on `cornell` no ray has a chain, `mixed` is bench.py --full's mixed Cornell box with
 a mirror box, a glass box around a water box and a gold box), of pt_denoise_device and pt_denoise_var_device (all
 iterations; --iterations sets both, otherwise the variance-guided filter is timed at the classic filter's count and at its own
-default), of the 16-spp depth-8 frame they post-process in one launch (the megakernel's device time, and the launcher's wall
+default), of pt_denoise_var_tiles_device (`denoise_var_tiles`: the `denoise_var` row's buffers and count with a uniform map of 16
+samples in batches of 4) and pt_denoise_hist_device (`denoise_hist`: the same frame's (e, V) as a first-frame history, the same
+count), of the 16-spp depth-8 frame they post-process in one launch (the megakernel's device time, and the launcher's wall
 time), of the same frame as a moments render of 4 batches of 4 and of 2 batches of 8 (pt_render_moments_device: wall time, it
 blocks), of both again with the scene's option "moments_fused" on (`*_fused_wall`: one launch that keeps the squared batch sums
 itself; `*_fused_launches` is what pt_last_moments_launches reported, 1 unless the kernel has no fused twin) and as
@@ -30,6 +33,12 @@ def aov_kernel_resources():
     return kernel_resources("pt_aov", r"(aov\w*?_kernel)")
 
 
+def denoise_kernel_resources():
+    """kernel_resources.kernel_resources of pt_denoise.hip's kernels: the instantiations of the three templates and the reduction."""
+    from kernel_resources import kernel_resources
+    return kernel_resources("pt_denoise", r"(dn_\w+?_kernel|denoise_reduce_kernel)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--w", type=int, default=1920)
@@ -43,7 +52,7 @@ def main():
     ap.add_argument("--centre", action="store_true")
     a = ap.parse_args()
     if a.resources:
-        print(json.dumps(aov_kernel_resources()))
+        print(json.dumps(dict(aov_kernel_resources(), **denoise_kernel_resources())))
         return
     import torch
     from cudapathtracer_amd import api, scenes
@@ -95,6 +104,18 @@ def main():
         api.denoise_var_device(w, h, colors.data_ptr(), sq.data_ptr(), 16, 4, alb.data_ptr(), nd.data_ptr(), ws_var.data_ptr(), out.data_ptr(),
                                iterations=n, stream=stream)
 
+    tile_spp = torch.full(((h + 7) // 8, (w + 7) // 8), 16, dtype=torch.int32, device="cuda:0")     # a uniform map: denoise_var's frame
+
+    def dn_var_tiles():
+        api.denoise_var_tiles_device(w, h, colors.data_ptr(), sq.data_ptr(), tile_spp.data_ptr(), 4, alb.data_ptr(), nd.data_ptr(),
+                                     ws_var.data_ptr(), out.data_ptr(), iterations=iters, stream=stream)
+
+    hist = torch.empty(h, w, 4, device="cuda:0"); hist_len = torch.empty(h, w, device="cuda:0")
+
+    def dn_hist():
+        api.denoise_hist_device(w, h, hist.data_ptr(), alb.data_ptr(), nd.data_ptr(), ws_var.data_ptr(), out.data_ptr(), iterations=iters,
+                                stream=stream)
+
     # the frame in one launch and as 4 batches of 4: both calls block, so wall time on the host (median of --reps after warm-up)
     def one_launch():
         colors.zero_()
@@ -132,9 +153,13 @@ def main():
         if name.endswith("_fused_wall"):
             res[name[:-5] + "_launches"] = sc.last_moments_launches()
     moments(4)()                                          # colors, sq: the 16-spp frame in 4 batches, what the filters below read
+    aov()                                                 # the frame's (e, V) as a first-frame history, what denoise_hist reads
+    api.temporal_accumulate_device(w, h, cam, None, colors.data_ptr(), sq.data_ptr(), 16, 4, alb.data_ptr(), nd.data_ptr(), 0, 0, 0,
+                                   hist.data_ptr(), hist_len.data_ptr(), stream=stream)
     timed = [("aov_chain", aov_chain), ("aov", aov), ("denoise", dn), ("denoise_var", lambda: dn_var(iters))]    # (aov last of the two: the filters read ITS buffers)
     if iters_var != iters:
         timed.append(("denoise_var_default", lambda: dn_var(iters_var)))
+    timed += [("denoise_var_tiles", dn_var_tiles), ("denoise_hist", dn_hist)]
     if a.centre:
         timed = [("aov_centre_chain", aov_centre_chain), ("aov_chain", aov_chain), ("aov_centre", aov_centre), ("aov", aov)]
     for name, fn in timed:
