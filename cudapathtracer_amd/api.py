@@ -81,6 +81,10 @@ class TemporalParams(C.Structure):   # pt_temporal_params
     _fields_ = [("max_history", C.c_int32), ("depth_tol", C.c_float), ("normal_tol", C.c_float)]
 
 
+class RespondParams(C.Structure):    # pt_respond_params
+    _fields_ = [("radius", C.c_int32), ("power", C.c_int32), ("threshold", C.c_float)]
+
+
 class UpsampleParams(C.Structure):   # pt_upsample_params
     _fields_ = [("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
@@ -158,6 +162,14 @@ def lib():
                                                     C.POINTER(TemporalParams), vp, vp]
     L.pt_temporal_accumulate_cur_motion_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, vp, vp, vp, vp,
                                                            C.POINTER(TemporalParams), vp, vp, vp]
+    L.pt_respond_defaults.restype = None; L.pt_respond_defaults.argtypes = [C.POINTER(RespondParams)]
+    L.pt_temporal_respond_workspace_bytes.restype = C.c_size_t; L.pt_temporal_respond_workspace_bytes.argtypes = [i32, i32]
+    L.pt_temporal_accumulate_respond.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                 C.POINTER(TemporalParams), C.POINTER(RespondParams), vp, vp, vp]
+    L.pt_temporal_accumulate_respond_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                        C.POINTER(TemporalParams), C.POINTER(RespondParams), vp, vp, vp, vp, vp]
+    L.pt_preview_set_respond.argtypes = [vp, C.POINTER(RespondParams)]
+    L.pt_preview_respond.argtypes = [vp, C.POINTER(RespondParams)]
     L.pt_preview_set_motion.argtypes = [vp, i32]
     L.pt_preview_motion.argtypes = [vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -1207,6 +1219,69 @@ def temporal_accumulate_cur_motion_device(w, h, camera, camera_prev, d_cur_ptr, 
                      (max_history, depth_tol, normal_tol), stream)
 
 
+def respond_defaults():
+    """pt_respond_defaults as a dict: radius, power, threshold."""
+    p = RespondParams()
+    lib().pt_respond_defaults(C.byref(p))
+    return {f: getattr(p, f) for f, _ in RespondParams._fields_}
+
+
+def _respond_params(threshold=None, radius=None, power=None):
+    p = RespondParams()
+    lib().pt_respond_defaults(C.byref(p))
+    for f, v in (("threshold", threshold), ("radius", radius), ("power", power)):
+        if v is not None:
+            setattr(p, f, v if f == "threshold" else int(v))
+    return p
+
+
+def temporal_respond_workspace_bytes(w, h):
+    """pt_temporal_respond_workspace_bytes: the device form's workspace, 36 bytes per pixel."""
+    return int(lib().pt_temporal_respond_workspace_bytes(w, h))
+
+
+def temporal_accumulate_respond(camera, normal_depth, rgba_sum=None, sq_sum=None, spp=0, batches=0, albedo=None, cur=None, camera_prev=None,
+                                prev_normal_depth=None, hist=None, hist_len=None, motion=None, max_history=None, depth_tol=None, normal_tol=None,
+                                threshold=None, radius=None, power=None, scale=True):
+    """pt_temporal_accumulate_respond (host, blocking): temporal_accumulate (the frame as rgba_sum, sq_sum, spp, batches, albedo) or
+    temporal_accumulate_cur (the frame as `cur`), with or without `motion`, and a per-pixel change test that scales the gathered
+    history length by lambda in [0, 1] where the frame and the history disagree by more than `threshold` standard deviations over a
+    (2 radius + 1)^2 window. threshold inf is the base function bit for bit. Returns (hist, hist_len, lambda [h,w] float32 or None
+    with scale False). A None parameter takes the library default (temporal_defaults(), respond_defaults())."""
+    what = "temporal_accumulate_respond"
+    named = [(n, a) for n, a in (("rgba_sum", rgba_sum), ("sq_sum", sq_sum), ("albedo", albedo), ("cur", cur)) if a is not None]
+    arrs = dict(zip([n for n, _ in named] + ["normal_depth"], _f4_frames(what, tuple(named) + (("normal_depth", normal_depth),))))
+    nd = arrs["normal_depth"]
+    h, w = nd.shape[:2]
+    PN, H, HL = _history_arrays(what, nd.shape, prev_normal_depth, hist, hist_len)
+    M = None if motion is None else _f4_frames(what, (("motion", motion),), nd.shape)[0]
+    out, out_len = np.empty_like(nd), np.empty((h, w), np.float32)
+    lam = np.empty((h, w), np.float32) if scale else None
+    tp, rp = _temporal_params(max_history, depth_tol, normal_tol), _respond_params(threshold, radius, power)
+    _check(lib().pt_temporal_accumulate_respond(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
+                                                _p(arrs.get("rgba_sum")), _p(arrs.get("sq_sum")), int(spp), int(batches), _p(arrs.get("albedo")),
+                                                _p(arrs.get("cur")), _p(nd), _p(PN), _p(H), _p(HL), _p(M), C.byref(tp), C.byref(rp), _p(out),
+                                                _p(out_len), _p(lam)), "pt_" + what)
+    return out, out_len, lam
+
+
+def temporal_accumulate_respond_device(w, h, camera, camera_prev, d_rgba_sum_ptr, d_sq_sum_ptr, spp, batches, d_albedo_ptr, d_cur_ptr,
+                                       d_normal_depth_ptr, d_prev_normal_depth_ptr, d_hist_ptr, d_hist_len_ptr, d_motion_ptr, d_workspace_ptr,
+                                       d_out_hist_ptr, d_out_hist_len_ptr, d_out_scale_ptr=0, max_history=None, depth_tol=None, normal_tol=None,
+                                       threshold=None, radius=None, power=None, stream=0):
+    """pt_temporal_accumulate_respond_device: device buffers, asynchronous on `stream` (two launches). Exactly one of the sums
+    (d_rgba_sum_ptr, d_sq_sum_ptr, d_albedo_ptr) and d_cur_ptr is given, the other 0 / None; d_workspace_ptr holds
+    temporal_respond_workspace_bytes(w, h) bytes; d_motion_ptr and d_out_scale_ptr may be 0 / None."""
+    tp, rp = _temporal_params(max_history, depth_tol, normal_tol), _respond_params(threshold, radius, power)
+    o = lambda x: x or None
+    _check(lib().pt_temporal_accumulate_respond_device(w, h, C.byref(camera), C.byref(camera_prev) if camera_prev is not None else None,
+                                                       o(d_rgba_sum_ptr), o(d_sq_sum_ptr), int(spp), int(batches), o(d_albedo_ptr), o(d_cur_ptr),
+                                                       d_normal_depth_ptr, o(d_prev_normal_depth_ptr), o(d_hist_ptr), o(d_hist_len_ptr),
+                                                       o(d_motion_ptr), C.byref(tp), C.byref(rp), o(d_workspace_ptr), d_out_hist_ptr,
+                                                       d_out_hist_len_ptr, o(d_out_scale_ptr), stream or None),
+           "pt_temporal_accumulate_respond_device")
+
+
 def _tile_map(what, tile_live, h, w):
     shape = ((h + 7) // 8, (w + 7) // 8)
     if not isinstance(tile_live, np.ndarray) or tile_live.dtype != np.int32 or tile_live.shape != shape:
@@ -1385,20 +1460,28 @@ def denoise_hist_device(w, h, d_hist_ptr, d_albedo_ptr, d_normal_depth_ptr, d_wo
 class TemporalHistory:
     """Host-side history of a w x h viewer: push() one frame after the other, each with the camera it was rendered with."""
 
-    def __init__(self, w, h, max_history=None, depth_tol=None, normal_tol=None):
+    def __init__(self, w, h, max_history=None, depth_tol=None, normal_tol=None, respond=None):
+        """respond: None (off), True (the library's respond_defaults()) or a dict of threshold / radius / power: the frames that have
+        a history are blended by temporal_accumulate_respond, and self.scale holds the last frame's lambda."""
         self.w, self.h = w, h
         self.params = dict(max_history=max_history, depth_tol=depth_tol, normal_tol=normal_tol)
+        self.respond = None if respond is None or respond is False else ({} if respond is True else dict(respond))
         self.reset()
 
     def reset(self):
-        self.camera = self.normal_depth = self.hist = self.hist_len = None
+        self.camera = self.normal_depth = self.hist = self.hist_len = self.scale = None
 
     def push(self, camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth):
         """Blend the frame into the history; returns the current hist (pass it to denoise_hist with this frame's buffers)."""
         if rgba_sum.shape != (self.h, self.w, 4):
             raise PtError("TemporalHistory: frame is %s, the history %d x %d" % (rgba_sum.shape, self.w, self.h))
-        self.hist, self.hist_len = temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, self.camera,
-                                                       self.normal_depth, self.hist, self.hist_len, **self.params)
+        if self.respond is not None and self.hist is not None:
+            self.hist, self.hist_len, self.scale = temporal_accumulate_respond(
+                camera, normal_depth, rgba_sum, sq_sum, spp, batches, albedo, camera_prev=self.camera, prev_normal_depth=self.normal_depth,
+                hist=self.hist, hist_len=self.hist_len, **self.params, **self.respond)
+        else:
+            self.hist, self.hist_len = temporal_accumulate(camera, rgba_sum, sq_sum, spp, batches, albedo, normal_depth, self.camera,
+                                                           self.normal_depth, self.hist, self.hist_len, **self.params)
         self.camera = Camera.frombytes(camera.tobytes())
         self.normal_depth = normal_depth.copy()
         return self.hist
@@ -1407,8 +1490,13 @@ class TemporalHistory:
         """push() for a frame given as (e, V) working pixels (upsample's output): frames of any render scale share the history."""
         if cur.shape != (self.h, self.w, 4):
             raise PtError("TemporalHistory: frame is %s, the history %d x %d" % (cur.shape, self.w, self.h))
-        self.hist, self.hist_len = temporal_accumulate_cur(camera, cur, normal_depth, self.camera, self.normal_depth, self.hist, self.hist_len,
-                                                           **self.params)
+        if self.respond is not None and self.hist is not None:
+            self.hist, self.hist_len, self.scale = temporal_accumulate_respond(
+                camera, normal_depth, cur=cur, camera_prev=self.camera, prev_normal_depth=self.normal_depth, hist=self.hist,
+                hist_len=self.hist_len, **self.params, **self.respond)
+        else:
+            self.hist, self.hist_len = temporal_accumulate_cur(camera, cur, normal_depth, self.camera, self.normal_depth, self.hist,
+                                                               self.hist_len, **self.params)
         self.camera = Camera.frombytes(camera.tobytes())
         self.normal_depth = normal_depth.copy()
         return self.hist
@@ -1547,6 +1635,25 @@ class Preview:
     @property
     def motion(self):
         return lib().pt_preview_motion(self.handle)
+
+    def set_respond(self, threshold=None, radius=None, power=None):
+        """pt_preview_set_respond: the frames that follow and have a history (converging frames excepted) accumulate through
+        temporal_accumulate_respond, so a static surface whose lighting changed shortens its own history. A None parameter takes the
+        library default (respond_defaults()); set_respond(False) turns it off, which is a session's initial state. Changing it does
+        not reset the session."""
+        if threshold is False:
+            _check(lib().pt_preview_set_respond(self.handle, None), "pt_preview_set_respond")
+            return self
+        p = _respond_params(threshold, radius, power)
+        _check(lib().pt_preview_set_respond(self.handle, C.byref(p)), "pt_preview_set_respond")
+        return self
+
+    def respond(self):
+        """pt_preview_respond: the option's parameters as a dict (radius, power, threshold), or None while it is off."""
+        p = RespondParams()
+        r = lib().pt_preview_respond(self.handle, C.byref(p))
+        _check(min(r, 0), "pt_preview_respond")
+        return {f: getattr(p, f) for f, _ in RespondParams._fields_} if r == 1 else None
 
     @property
     def guide_passes(self):

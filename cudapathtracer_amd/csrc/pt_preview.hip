@@ -18,6 +18,8 @@
 //                       rests reuses the previous frame's guide: the guide has no seed, so nothing in it could have changed.
 //                       With motion on (pt_preview_set_motion) the frame after an announced vertex update that keeps its history
 //                       also runs pt_render_motion_device and accumulates through pt_temporal_accumulate[_cur]_motion_device.
+//                       With respond on (pt_preview_set_respond) every frame with a history that is not a converging frame accumulates
+//                       through pt_temporal_accumulate_respond_device, with the arguments of the form it would have taken.
 #include <cmath>
 #include <cstring>
 
@@ -29,6 +31,7 @@
 namespace pt {
 
 int check_converge_params(const char* fn, const pt_converge_params& P);       // pt_converge.hip
+int check_respond_params(const char* fn, const pt_respond_params& R);         // pt_temporal.hip
 
 // novum_host.cpp's clamp01, aces and to_byte, operation for operation (-ffp-contract=off: nothing fuses).
 __device__ inline float rs_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
@@ -132,6 +135,9 @@ struct pt_preview {
     int motion;                           // 1: MOTION FRAMES reproject moved surfaces (pt_preview_set_motion)
     char* M;                              // w*h float4: pt_render_motion's output (its own allocation, made when motion is first turned on)
     bool frameMotion;                     // the frame in flight is a motion frame
+    bool respond;                         // frames with a history accumulate through pt_temporal_accumulate_respond_device
+    pt_respond_params R;
+    char* respondWs;                      // its workspace (its own allocation, made when respond is first turned on)
 };
 
 extern "C" {
@@ -185,6 +191,7 @@ void pt_preview_destroy(pt_preview* p) {
     if (p->curEV) (void)hipFree(p->curEV);
     if (p->tiles) (void)hipFree(p->tiles);
     if (p->M) (void)hipFree(p->M);
+    if (p->respondWs) (void)hipFree(p->respondWs);
     delete p;
 }
 
@@ -312,6 +319,27 @@ int pt_preview_set_motion(pt_preview* p, int on) {
 
 int pt_preview_motion(pt_preview* p) { return p ? p->motion : postfx_fail(-1, "pt_preview_motion: null session"); }
 
+int pt_preview_set_respond(pt_preview* p, const pt_respond_params* params) {
+    if (!p) return postfx_fail(-1, "pt_preview_set_respond: null session");
+    if (!params) { p->respond = false; return 0; }
+    if (int r = check_respond_params("pt_preview_set_respond", *params)) return r;
+    if (!p->respondWs) {                  // (no frame is in flight: pt_preview_frame blocks)
+        if (hipMalloc(&p->respondWs, pt_temporal_respond_workspace_bytes(p->w, p->h)) != hipSuccess) {
+            p->respondWs = nullptr;
+            return postfx_fail(-2, "pt_preview_set_respond: could not allocate the workspace");
+        }
+    }
+    p->respond = true;                    // (no reset: neither the guides nor the history's format depend on it)
+    p->R = *params;
+    return 0;
+}
+
+int pt_preview_respond(pt_preview* p, pt_respond_params* out) {
+    if (!p) return postfx_fail(-1, "pt_preview_respond: null session");
+    if (p->respond && out) *out = p->R;
+    return p->respond ? 1 : 0;
+}
+
 int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
     if (!p) return postfx_fail(-1, "pt_preview_set_converge: null session");
     if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
@@ -434,7 +462,12 @@ static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t s
     const void* shown = p->curEV;         // the (e, V) buffer the filter reads
     if (P.temporal) {
         const bool hist = p->haveHist;
-        if (p->frameMotion) {             // (a motion frame has a history)
+        if (p->respond && hist) {         // (the arguments of the form below that the frame would have taken)
+            if (int r = pt_temporal_accumulate_respond_device(w, h, cam, &p->prevCam, nullptr, nullptr, 0, 0, nullptr, p->curEV, p->N[gn], p->N[p->curG],
+                                                              p->H[p->cur], p->L[p->cur], p->frameMotion ? p->M : nullptr, &P.temporal_params, &p->R,
+                                                              p->respondWs, p->H[nxt], p->L[nxt], nullptr, st))
+                return r;
+        } else if (p->frameMotion) {      // (a motion frame has a history)
             if (int r = pt_temporal_accumulate_cur_motion_device(w, h, cam, &p->prevCam, p->curEV, p->N[gn], p->N[p->curG], p->H[p->cur], p->L[p->cur],
                                                                  p->M, &P.temporal_params, p->H[nxt], p->L[nxt], st))
                 return r;
@@ -472,7 +505,12 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
     int shownSpp = P.spp;
     if (P.temporal) {
         const bool hist = p->haveHist;
-        if (p->frameMotion) {             // (a motion frame has a history)
+        if (p->respond && hist) {         // (the arguments of the form below that the frame would have taken)
+            if (int r = pt_temporal_accumulate_respond_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, nullptr, p->N[gn], p->N[p->curG],
+                                                              p->H[p->cur], p->L[p->cur], p->frameMotion ? p->M : nullptr, &P.temporal_params, &p->R,
+                                                              p->respondWs, p->H[nxt], p->L[nxt], nullptr, st))
+                return r;
+        } else if (p->frameMotion) {      // (a motion frame has a history)
             if (int r = pt_temporal_accumulate_motion_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], p->N[p->curG],
                                                              p->H[p->cur], p->L[p->cur], p->M, &P.temporal_params, p->H[nxt], p->L[nxt], st))
                 return r;

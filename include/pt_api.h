@@ -719,7 +719,9 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  * keep_history 1 accumulates through the public entry points as usual: the previous guide is the old geometry's, a camera
  * whose 112 bytes are unchanged takes pt_temporal_accumulate's identity path, whose tap is still validated by depth and
  * normal, and the frame equals that chain of host calls bit for bit. Without motion vectors (MOTION below, off by default) a
- * surface that moved keeps its history only where depth and normal still agree at the same pixel. A session also remembers
+ * surface that moved keeps its history only where depth and normal still agree at the same pixel. With respond on (RESPOND
+ * below, off by default) keep_history 1 is also right when a light moved: a static surface whose lighting changed shortens its
+ * own history. A session also remembers
  * pt_scene_generation from its last good frame (from create before the first): if the generation differs at pt_preview_frame
  * and this call was not made since that frame, the session behaves as if it had been made with keep_history 0. The
  * announcement holds until the next good frame. -1 on a NULL session or a keep_history other than 0 or 1.
@@ -1040,6 +1042,72 @@ int pt_temporal_accumulate_cur_motion_device(int w, int h, const pt_camera* cam,
                                              const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist,
                                              const void* d_hist_len, const void* d_motion, const pt_temporal_params* params,
                                              void* d_out_hist, void* d_out_hist_len, void* stream);              /* async */
+/* ---- RESPOND: a responsive history: detect stale lighting and shorten the history per pixel -------------------------------------
+ * pt_temporal_accumulate validates a tap by depth and normal only, so a static surface whose lighting changed (a light or an
+ * occluder moved) keeps blending with alpha = 1 / N into a history that is no longer its own. Every frame carries its own variance
+ * V and the history the variance of its mean V_h; pt_temporal_accumulate_respond compares the difference of the two means with the
+ * sum of the two variances over a small window and scales the history length N_h by a factor lambda in [0, 1] per pixel.
+ *
+ * One host / device pair covers the four base forms: the frame as sums (rgba_sum, sq_sum, spp, batches, albedo; cur NULL) or as
+ * working pixels (cur, as pt_upsample writes them; rgba_sum, sq_sum and albedo NULL, spp and batches ignored) - exactly one of the
+ * two, -1 otherwise - and motion NULL or pt_render_motion's buffer.
+ *
+ * Steps 1-4 are the base function's (pt_temporal_accumulate, _cur, _motion, _cur_motion by the arguments given), bit for bit. They
+ * give pixel p its working value (e, V), or mark it pass-through, and the gathered history (e_h, V_h, N_h) when the valid tap
+ * weight W >= 0.01. A WITNESS is a pixel that is not pass-through and has a gathered history. It carries
+ *     d = e - e_h (three f32 subtractions)   and   v = V + V_h.
+ * A witness p whose own d and v are finite walks the window of (2 radius + 1)^2 pixels around it in raster order (dy from -radius
+ * outermost, dx from -radius inner; p itself at its place in that order). A pixel q COUNTS if it is inside the image, is a witness,
+ * its d and v are finite, and it passes a tap's two guide comparisons against p on the CURRENT guide: |z_q - z_p| <= depth_tol z_p,
+ * both unit normals non-zero, and their dot product (x, y, z left to right) >= normal_tol. A pixel that does not count is skipped,
+ * never multiplied by zero. Then in f32, one rounding per operation, no fma:
+ *     D_c = sum of d_q,c and Vs = sum of v_q over the counted pixels, in walk order from 0;
+ *     T = D_x D_x + D_y D_y + D_z D_z, left to right;   lim = (threshold threshold) Vs;
+ *     lambda = 1 unless T > lim; otherwise rho = lim / T and lambda = rho, rho rho or (rho rho) (rho rho) for power 1, 2, 4.
+ * Step 5 is the base blend with lambda N_h in place of N_h: len = min(lambda N_h + 1, max_history), alpha = 1 / len, and the same
+ * e and V formulas. Every other pixel runs no test and has lambda = 1: a pass-through pixel, a pixel without a gathered history,
+ * a witness whose own d or v is not finite. Since 1 N_h == N_h exactly, a pixel with lambda = 1 is the base function's bit for
+ * bit, and so is every pixel with threshold +inf (lim is +inf or NaN and T > lim is false). Without a history (the first frame)
+ * the call is the base function. Under unchanged lighting E[T] = Vs (V is the sum of the three channels' variances, hence T sums
+ * the three squared channel sums), so threshold is a z-score.
+ *
+ * out_scale (NULL, or w*h floats) receives lambda of every pixel, 1 where no test ran; the other outputs do not depend on it.
+ * The device form needs a workspace of pt_temporal_respond_workspace_bytes(w, h) = 36 w h bytes (two launches: the gather, then the
+ * walk and the blend); the host form stages its own. -1 before any HIP call: everything the base functions check, a radius outside
+ * 1..3, a power other than 1, 2 or 4, a threshold that is not > 0 (+inf is allowed), not exactly one frame form, a NULL workspace,
+ * a workspace or out_scale that overlaps any other buffer of the call or each other. params or respond NULL: the defaults. Host
+ * and device form are bit-identical. tests/respond_ref.py restates the function in numpy. */
+typedef struct pt_respond_params {
+    int32_t radius;     /* 1..3: the window is (2 radius + 1)^2 pixels */
+    int32_t power;      /* 1, 2 or 4 */
+    float   threshold;  /* k > 0; +inf is allowed and makes every pixel the base function's */
+} pt_respond_params;
+void   pt_respond_defaults(pt_respond_params* out);                                      /* radius 3, power 4, threshold 2 */
+size_t pt_temporal_respond_workspace_bytes(int w, int h);                                /* 36 w h; 0 for a size that is not positive */
+int pt_temporal_accumulate_respond(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const float* rgba_sum,
+                                   const float* sq_sum, int spp, int batches, const float* albedo, const float* cur,
+                                   const float* normal_depth, const float* prev_normal_depth, const float* hist, const float* hist_len,
+                                   const float* motion /* NULL ok */, const pt_temporal_params* params, const pt_respond_params* respond,
+                                   float* out_hist, float* out_hist_len, float* out_scale /* NULL ok */);        /* host, blocking */
+int pt_temporal_accumulate_respond_device(int w, int h, const pt_camera* cam, const pt_camera* cam_prev, const void* d_rgba_sum,
+                                          const void* d_sq_sum, int spp, int batches, const void* d_albedo, const void* d_cur,
+                                          const void* d_normal_depth, const void* d_prev_normal_depth, const void* d_hist,
+                                          const void* d_hist_len, const void* d_motion /* NULL ok */, const pt_temporal_params* params,
+                                          const pt_respond_params* respond, void* d_workspace, void* d_out_hist, void* d_out_hist_len,
+                                          void* d_out_scale /* NULL ok */, void* stream);                         /* async */
+/* The session's option. pt_preview_set_respond(p, params): NULL turns it off (the default: the frames of "preview", bit for bit),
+ * a parameter set turns it on. The first call that turns it on allocates the workspace (-2 if that fails, the state unchanged); -1
+ * on a NULL session or parameters out of range, the session unchanged. A change of value does not reset the session: the guides
+ * and the history's format do not depend on it. With the option on, every temporal frame that has a history and is not a
+ * converging frame accumulates through pt_temporal_accumulate_respond_device with exactly the arguments it would have given the
+ * base, _cur, _motion or _cur_motion form, so the frame equals that chain of host calls bit for bit. Converging frames (the camera
+ * rests and the scene is unchanged: nothing to detect, and pt_temporal_accumulate_live carries tiles forward as before), first
+ * frames, non-temporal sessions, pt_preview_stats (accumulate_ms covers both launches) and the failed-frame rule are unchanged.
+ * A shortened history makes its tile live again in the next pt_temporal_select: that is intended, the tile needs samples.
+ * pt_preview_respond(p, out): 1 and *out (NULL ok) = the parameters if the option is on, 0 if off, -1 on a NULL session. */
+int  pt_preview_set_respond(pt_preview* p, const pt_respond_params* params);
+int  pt_preview_respond(pt_preview* p, pt_respond_params* out);
+
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
  * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */
