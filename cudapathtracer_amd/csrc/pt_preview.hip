@@ -8,18 +8,30 @@
 //   pt_preview          a session that owns the device buffers of one w x h viewer and runs render_moments -> render_aovs ->
 //                       temporal_accumulate -> denoise_hist -> resolve per frame on one stream through the public *_device entry
 //                       points, ping-ponging history and guide. Nothing crosses PCIe unless pt_preview_read asks for it.
-//                       With a render scale s > 1 (pt_preview_set_scale) the moments render runs at 1/s of the size in each axis and
-//                       pt_upsample + pt_temporal_accumulate_cur bring it into the same display-size history.
-//                       With converge on (pt_preview_set_converge) a frame whose camera rests selects the tiles that still need
-//                       samples from the history, renders moments on that list alone and carries the other tiles' history forward.
-//                       With a guide chain (pt_preview_set_guide_chain) every feature pass of a frame is pt_render_aovs_chain_device.
-//                       With centre guides (pt_preview_set_guide_centre) every feature pass is pt_render_aovs_centre_device, the
-//                       low-res guide of a scaled frame is pt_guide_subsample_device of the display guide, and a frame whose camera
-//                       rests reuses the previous frame's guide: the guide has no seed, so nothing in it could have changed.
-//                       With motion on (pt_preview_set_motion) the frame after an announced vertex update that keeps its history
-//                       also runs pt_render_motion_device and accumulates through pt_temporal_accumulate[_cur]_motion_device.
-//                       With respond on (pt_preview_set_respond) every frame with a history that is not a converging frame accumulates
-//                       through pt_temporal_accumulate_respond_device, with the arguments of the form it would have taken.
+//
+// pt_preview_frame decides once what kind of frame this is (FramePlan) and preview_stages enqueues it: one sequence, an event after
+// each stage. What the options change, stage by stage (SCALED: pt_preview_set_scale > 1; CONVERGING: pt_preview_set_converge, a
+// temporal session at scale 1 whose camera rests on a history; MOTION FRAME: pt_preview_set_motion, the frame after one announced
+// vertex update that kept its history; a converging frame is neither scaled nor a motion frame):
+//   before    scaled: the session's own check of the camera's size, and pt_camera_scaled; nothing is enqueued if either fails.
+//             Every other frame gets the camera-size error from its first stage.
+//   render    pt_render_moments_device into S and Q. Scaled: the low-res camera and size, into the low-res S and Q. Converging:
+//             pt_temporal_select_device on the history, its count read back, pt_render_moments_tiles_device on that list.
+//   guides    the display-size feature pass into albedo and the other half of the guide pair: pt_render_aovs_device; with a guide
+//             chain pt_render_aovs_chain_device; with centre guides pt_render_aovs_centre_device, and then no pass at all when the
+//             camera rests and the last guide is still in place (it has no seed: nothing in it could have changed). A motion frame
+//             adds pt_render_motion_device, fused with the guide where that is the centre first-hit pass. Scaled: the low-res guide
+//             is one more feature pass, before the display pass; with centre guides pt_guide_subsample_device of the display guide,
+//             after it, also when that guide is reused.
+//   accumulate  temporal 0: nothing. Else one call (preview_accumulate): pt_temporal_accumulate_motion_device on S, Q and albedo;
+//             scaled: pt_upsample_device first, then pt_temporal_accumulate_cur_motion_device on its output. Both take the motion
+//             buffer on a motion frame and NULL otherwise: the _motion forms with a NULL buffer are the base forms (include/pt_api.h),
+//             so the base case has no call of its own. Converging: pt_temporal_accumulate_live_device with the new live map. With
+//             respond on (pt_preview_set_respond), a frame with a history that is not converging:
+//             pt_temporal_accumulate_respond_device, with the same frame form and motion buffer.
+//   filter    pt_denoise_hist_device on the new history, or on the upsampled frame of a scaled frame with temporal 0; filter 0 gives
+//             it no iterations. A plain frame with temporal 0: pt_denoise_var_device on S and Q, or with filter 0 nothing.
+//   resolve   pt_resolve_device of the filtered frame as a mean, or of S with the frame's spp where nothing filtered.
 #include <cmath>
 #include <cstring>
 
@@ -112,7 +124,7 @@ struct pt_preview {
     int guideCentre;                      // 1: the feature passes trace pixel centres (pt_preview_set_guide_centre)
     int curG;                             // the half of N that holds the last good frame's guide: cur's, until a frame reuses the guide
     bool guideFresh;                      // A and N[curG] are the guide of prevCam (no later frame has written A and then failed)
-    int guidePasses, framePasses;         // feature-pass launches of all good frames / of the frame in flight (committed with the flip)
+    int guidePasses;                      // feature-pass launches of all good frames
     char* lo;                             // four low-res float4 buffers of loCap pixels each: S, Q, albedo, guide
     size_t loCap;
     char* curEV;                          // w*h float4: pt_upsample's output
@@ -129,16 +141,29 @@ struct pt_preview {
     int curT;
     bool haveTiles;
     int lastLive;                         // live tiles of the last good frame (its total is the frame's tile count)
-    int frameLive; bool frameConverged;   // what the frame in flight found; committed with the flip
     int sceneGen;                         // pt_scene_generation at the last good frame (at create before the first)
     bool sceneChanged;                    // pt_preview_scene_changed since the last good frame: the next frame counts as a moved camera
     int motion;                           // 1: MOTION FRAMES reproject moved surfaces (pt_preview_set_motion)
     char* M;                              // w*h float4: pt_render_motion's output (its own allocation, made when motion is first turned on)
-    bool frameMotion;                     // the frame in flight is a motion frame
     bool respond;                         // frames with a history accumulate through pt_temporal_accumulate_respond_device
     pt_respond_params R;
     char* respondWs;                      // its workspace (its own allocation, made when respond is first turned on)
 };
+
+static size_t tile_count(int w, int h) { return (size_t)((w + 7) / 8) * ((h + 7) / 8); }       // 8x8 tiles, as the tile maps count them
+
+// The next frame is a first frame.
+static void drop_history(pt_preview* p) { p->haveHist = p->haveFrame = p->haveTiles = false; }
+
+// A buffer of its own that the session allocates when an option first needs it, or needs it larger: the one in *slot is freed only
+// once the new one exists, so a failure changes nothing (and the caller reports -2). No frame is in flight: pt_preview_frame blocks.
+static bool session_alloc(char** slot, size_t bytes) {
+    char* fresh = nullptr;
+    if (hipMalloc(&fresh, bytes) != hipSuccess) return false;
+    if (*slot) (void)hipFree(*slot);
+    *slot = fresh;
+    return true;
+}
 
 extern "C" {
 
@@ -203,7 +228,7 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
     int bad = 0;
     if (!scene) bad = postfx_fail(-1, "pt_preview_create: null scene");
     else if (w <= 0 || h <= 0) bad = postfx_fail(-1, "pt_preview_create: image size %d x %d must be positive", w, h);
-    else if ((long long)((w + 7) / 8) * ((h + 7) / 8) * 64 > 0x7fffffffll) bad = postfx_fail(-1, "pt_preview_create: image of %d x %d pixels is too large", w, h);
+    else if (tile_count(w, h) * 64 > 0x7fffffffull) bad = postfx_fail(-1, "pt_preview_create: image of %d x %d pixels is too large", w, h);
     else if (P.spp <= 0) bad = postfx_fail(-1, "pt_preview_create: spp %d must be positive", P.spp);
     else if (P.batches < 2) bad = postfx_fail(-1, "pt_preview_create: batches %d must be at least 2", P.batches);
     else if (P.spp % P.batches != 0) bad = postfx_fail(-1, "pt_preview_create: batches %d must divide spp %d", P.batches, P.spp);
@@ -241,14 +266,14 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 
 int pt_preview_reset(pt_preview* p) {
     if (!p) return postfx_fail(-1, "pt_preview_reset: null session");
-    p->haveHist = p->haveFrame = p->haveTiles = false;
+    drop_history(p);
     return 0;
 }
 
 int pt_preview_scene_changed(pt_preview* p, int keep_history) {
     if (!p) return postfx_fail(-1, "pt_preview_scene_changed: null session");
     if (keep_history != 0 && keep_history != 1) return postfx_fail(-1, "pt_preview_scene_changed: keep_history %d must be 0 or 1", keep_history);
-    if (!keep_history) p->haveHist = p->haveFrame = p->haveTiles = false;
+    if (!keep_history) drop_history(p);
     p->sceneChanged = true;
     return 0;
 }
@@ -258,21 +283,11 @@ int pt_preview_set_scale(pt_preview* p, int scale) {
     if (scale < 1 || scale > 8) return postfx_fail(-1, "pt_preview_set_scale: scale %d must be 1..8", scale);
     if (p->w % scale != 0 || p->h % scale != 0)
         return postfx_fail(-1, "pt_preview_set_scale: scale %d must divide the session's size %d x %d", scale, p->w, p->h);
-    if (scale > 1) {                      // (no frame is in flight: pt_preview_frame blocks)
+    if (scale > 1) {                      // (curEV stays if lo then fails: it is the size every scale needs)
         const size_t need = (size_t)(p->w / scale) * (p->h / scale);
-        char* cur = p->curEV;
-        char* lo = nullptr;
-        bool ok = cur || hipMalloc(&cur, (size_t)p->w * p->h * 16) == hipSuccess;
-        if (ok && need > p->loCap) ok = hipMalloc(&lo, 4 * need * 16) == hipSuccess;
-        if (!ok) {
-            if (cur && !p->curEV) (void)hipFree(cur);
+        if ((!p->curEV && !session_alloc(&p->curEV, (size_t)p->w * p->h * 16)) || (need > p->loCap && !session_alloc(&p->lo, 4 * need * 16)))
             return postfx_fail(-2, "pt_preview_set_scale: could not allocate the buffers of scale %d", scale);
-        }
-        p->curEV = cur;
-        if (lo) {
-            if (p->lo) (void)hipFree(p->lo);
-            p->lo = lo; p->loCap = need;
-        }
+        if (need > p->loCap) p->loCap = need;
     }
     p->scale = scale;
     return 0;
@@ -284,7 +299,7 @@ int pt_preview_set_guide_chain(pt_preview* p, int max_links) {
     if (!p) return postfx_fail(-1, "pt_preview_set_guide_chain: null session");
     if (max_links < 0 || max_links > 16) return postfx_fail(-1, "pt_preview_set_guide_chain: max_links %d must be 0..16", max_links);
     // guides from before and after a change do not validate against each other: the next frame is a first frame
-    if (max_links != p->guideChain) p->haveHist = p->haveFrame = p->haveTiles = false;
+    if (max_links != p->guideChain) drop_history(p);
     p->guideChain = max_links;
     return 0;
 }
@@ -295,7 +310,7 @@ int pt_preview_set_guide_centre(pt_preview* p, int on) {
     if (on != 0 && on != 1) return postfx_fail(-1, "pt_preview_set_guide_centre: on %d must be 0 or 1", on);
     if (!p) return postfx_fail(-1, "pt_preview_set_guide_centre: null session");
     // jittered and centre guides do not validate against each other: the next frame is a first frame
-    if (on != p->guideCentre) p->haveHist = p->haveFrame = p->haveTiles = false;
+    if (on != p->guideCentre) drop_history(p);
     p->guideCentre = on;
     return 0;
 }
@@ -307,12 +322,8 @@ int pt_preview_guide_passes(pt_preview* p) { return p ? p->guidePasses : postfx_
 int pt_preview_set_motion(pt_preview* p, int on) {
     if (on != 0 && on != 1) return postfx_fail(-1, "pt_preview_set_motion: on %d must be 0 or 1", on);
     if (!p) return postfx_fail(-1, "pt_preview_set_motion: null session");
-    if (on && !p->M) {                    // (no frame is in flight: pt_preview_frame blocks)
-        if (hipMalloc(&p->M, (size_t)p->w * p->h * 16) != hipSuccess) {
-            p->M = nullptr;
-            return postfx_fail(-2, "pt_preview_set_motion: could not allocate the motion buffer");
-        }
-    }
+    if (on && !p->M && !session_alloc(&p->M, (size_t)p->w * p->h * 16))
+        return postfx_fail(-2, "pt_preview_set_motion: could not allocate the motion buffer");
     p->motion = on;                       // (no reset: the guides do not depend on it)
     return 0;
 }
@@ -323,12 +334,8 @@ int pt_preview_set_respond(pt_preview* p, const pt_respond_params* params) {
     if (!p) return postfx_fail(-1, "pt_preview_set_respond: null session");
     if (!params) { p->respond = false; return 0; }
     if (int r = check_respond_params("pt_preview_set_respond", *params)) return r;
-    if (!p->respondWs) {                  // (no frame is in flight: pt_preview_frame blocks)
-        if (hipMalloc(&p->respondWs, pt_temporal_respond_workspace_bytes(p->w, p->h)) != hipSuccess) {
-            p->respondWs = nullptr;
-            return postfx_fail(-2, "pt_preview_set_respond: could not allocate the workspace");
-        }
-    }
+    if (!p->respondWs && !session_alloc(&p->respondWs, pt_temporal_respond_workspace_bytes(p->w, p->h)))
+        return postfx_fail(-2, "pt_preview_set_respond: could not allocate the workspace");
     p->respond = true;                    // (no reset: neither the guides nor the history's format depend on it)
     p->R = *params;
     return 0;
@@ -344,12 +351,9 @@ int pt_preview_set_converge(pt_preview* p, const pt_converge_params* params) {
     if (!p) return postfx_fail(-1, "pt_preview_set_converge: null session");
     if (!params || params->threshold == 0.0f) { p->converge = false; return 0; }
     if (int r = check_converge_params("pt_preview_set_converge", *params)) return r;
-    if (!p->tiles) {                      // (no frame is in flight: pt_preview_frame blocks)
-        const size_t tb = ((size_t)((p->w + 7) / 8) * ((p->h + 7) / 8) * 4 + 15) & ~(size_t)15;
-        if (hipMalloc(&p->tiles, 5 * tb + 16) != hipSuccess) {
-            p->tiles = nullptr;
-            return postfx_fail(-2, "pt_preview_set_converge: could not allocate the tile buffers");
-        }
+    if (!p->tiles) {
+        const size_t tb = (tile_count(p->w, p->h) * 4 + 15) & ~(size_t)15;
+        if (!session_alloc(&p->tiles, 5 * tb + 16)) return postfx_fail(-2, "pt_preview_set_converge: could not allocate the tile buffers");
         char* c = p->tiles;
         for (int i = 0; i < 2; i++) { p->tErr[i] = c; c += tb; p->tLive[i] = c; c += tb; }
         p->tList = c; c += tb; p->tCount = c;
@@ -363,23 +367,38 @@ int pt_preview_last_live(pt_preview* p, int* live, int* total) {
     if (!p) return postfx_fail(-1, "pt_preview_last_live: null session");
     if (!p->haveFrame) return postfx_fail(-1, "pt_preview_last_live: no frame since the session was created or reset");
     if (live) *live = p->lastLive;
-    if (total) *total = ((p->w + 7) / 8) * ((p->h + 7) / 8);
+    if (total) *total = (int)tile_count(p->w, p->h);
     return 0;
 }
 
 int pt_preview_read_tiles(pt_preview* p, float* tile_err, int32_t* tile_live) {
     if (!p) return postfx_fail(-1, "pt_preview_read_tiles: null session");
     if (!p->haveTiles) return postfx_fail(-1, "pt_preview_read_tiles: no converging frame since the session was created or reset");
-    const size_t tb = (size_t)((p->w + 7) / 8) * ((p->h + 7) / 8) * 4;
+    const size_t tb = tile_count(p->w, p->h) * 4;
     if (tile_err) POSTFX_HIP_OK(hipMemcpy(tile_err, p->tErr[p->curT], tb, hipMemcpyDeviceToHost));
     if (tile_live) POSTFX_HIP_OK(hipMemcpy(tile_live, p->tLive[p->curT], tb, hipMemcpyDeviceToHost));
     return 0;
 }
 
+// What pt_preview_frame decides about a frame before it enqueues anything, and what the frame's stages find. It travels with the
+// frame; the session takes it over only when the frame has succeeded (pt_preview_frame's commit).
+struct FramePlan {
+    int gen;                              // pt_scene_generation at this frame
+    bool same;                            // a history, no change of the scene, and the camera of the last good frame byte for byte
+    bool motion;                          // a MOTION FRAME: M is rendered and accumulated through
+    bool converging;                      // a resting frame of a converging session: only the tiles its history has not settled
+    bool reuse;                           // centre guides, `same`, and the last good frame's guide still in place: no feature pass
+    int nxt;                              // the half of the history pair the frame writes
+    int gn;                               // the half of the guide pair it writes; when it reuses the guide, the half it reads as this
+                                          // frame's guide and the previous frame's at once
+    int live;                             // found: the tiles the frame rendered (all of them unless it converges)
+    int passes;                           // found: its feature-pass launches
+};
+
 // A feature pass of a frame: the first-hit pass, or the chain pass when the session has a guide chain; with centre guides the
 // centre pass of either kind, which has no aov_spp and no seed.
-static int preview_aovs(pt_preview* p, const pt_camera* cam, int w, int h, uint64_t seed, void* dA, void* dN) {
-    p->framePasses++;
+static int preview_aovs(pt_preview* p, FramePlan& f, const pt_camera* cam, int w, int h, uint64_t seed, void* dA, void* dN) {
+    f.passes++;
     if (p->guideCentre) return pt_render_aovs_centre_device(p->scene, cam, w, h, p->guideChain, dA, dN, nullptr, p->stream);
     if (p->guideChain > 0) return pt_render_aovs_chain_device(p->scene, cam, w, h, p->P.aov_spp, p->guideChain, seed, dA, dN, nullptr, p->stream);
     return pt_render_aovs_device(p->scene, cam, w, h, p->P.aov_spp, seed, dA, dN, p->stream);
@@ -387,149 +406,112 @@ static int preview_aovs(pt_preview* p, const pt_camera* cam, int w, int h, uint6
 
 // The display-size guide of a frame that traces one and, on a motion frame, the motion buffer: one fused pass where the guide is the
 // centre first-hit pass (the motion pass writes that guide from its own trace), else the guide pass and then the motion pass.
-static int preview_display_guide(pt_preview* p, const pt_camera* cam, uint64_t seed, int gn) {
+static int preview_display_guide(pt_preview* p, FramePlan& f, const pt_camera* cam, uint64_t seed) {
     const int w = p->w, h = p->h;
-    if (p->frameMotion && p->guideCentre && p->guideChain == 0) {
-        p->framePasses++;
-        return pt_render_motion_device(p->scene, cam, w, h, p->A, p->N[gn], p->M, p->stream);
+    if (f.motion && p->guideCentre && p->guideChain == 0) {
+        f.passes++;
+        return pt_render_motion_device(p->scene, cam, w, h, p->A, p->N[f.gn], p->M, p->stream);
     }
-    if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
-    if (!p->frameMotion) return 0;
-    p->framePasses++;
+    if (int r = preview_aovs(p, f, cam, w, h, seed, p->A, p->N[f.gn])) return r;
+    if (!f.motion) return 0;
+    f.passes++;
     return pt_render_motion_device(p->scene, cam, w, h, nullptr, nullptr, p->M, p->stream);
 }
 
-// A converging frame (the camera rests, a history exists, scale 1): the same five events around select + read-back + moments on
-// the live list | the whole feature pass | the accumulation with the live map | filter | resolve.
-static int preview_stages_converge(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt, int gn, bool reuse) {
-    const pt_preview_params& P = p->P;
-    const int w = p->w, h = p->h, T = ((w + 7) / 8) * ((h + 7) / 8), nt = p->curT ^ 1;
-    hipStream_t st = p->stream;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[0], st));
-    if (int r = pt_temporal_select_device(w, h, p->H[p->cur], p->L[p->cur], &p->C, p->tErr[nt], p->tLive[nt], p->tList, p->tCount, st)) return r;
-    int count = -1;
-    POSTFX_HIP_OK(hipMemcpyAsync(&count, p->tCount, sizeof(int), hipMemcpyDeviceToHost, st));
-    POSTFX_HIP_OK(hipStreamSynchronize(st));
-    if (count < 0 || count > T) return postfx_fail(-2, "pt_preview_frame: the live list holds %d of %d tiles", count, T);
-    if (count > 0)
-        if (int r = pt_render_moments_tiles_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->tList,
-                                                   count, p->S, p->Q, st))
-            return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (!reuse)
-        if (int r = preview_aovs(p, cam, w, h, seed, p->A, p->N[gn])) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
-    if (int r = pt_temporal_accumulate_live_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], p->N[p->curG], p->H[p->cur],
-                                                   p->L[p->cur], p->tLive[nt], &P.temporal_params, p->H[nxt], p->L[nxt], st))
-        return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
-    pt_denoise_var_params F = P.filter_params;
-    if (!P.filter) F.iterations = 0;
-    if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
-    if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
-    p->frameLive = count; p->frameConverged = true;
-    return 0;
-}
-
-// A frame at render scale s > 1: the same five events around low-res moments | both feature passes | upsample + accumulate |
-// filter | resolve. With centre guides the feature stage is the display pass (none when the guide is reused) and its subsample.
-static int preview_stages_scaled(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt, int gn, bool reuse) {
-    const pt_preview_params& P = p->P;
-    const int w = p->w, h = p->h, s = p->scale, wl = w / s, hl = h / s;
-    hipStream_t st = p->stream;
-    if (cam->w != w || cam->h != h)       // (before the low-res camera is made: the stages would see a size that need not divide)
-        return postfx_fail(-1, "pt_preview_frame: camera is %d x %d, the session %d x %d", cam->w, cam->h, w, h);
-    pt_camera lowCam;
-    if (int r = pt_camera_scaled(cam, s, &lowCam)) return r;
-    const size_t lb = p->loCap * 16;
-    char *S = p->lo, *Q = S + lb, *Al = Q + lb, *Nl = Al + lb;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[0], st));
-    if (int r = pt_render_moments_device(p->scene, &lowCam, wl, hl, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, S, Q, st)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (p->guideCentre) {
-        if (!reuse)
-            if (int r = preview_display_guide(p, cam, seed, gn)) return r;
-        // (also when the guide is reused: the scale may have changed since, and the copy is w * h / s^2 pixels)
-        if (int r = pt_guide_subsample_device(w, h, s, p->A, p->N[gn], Al, Nl, st)) return r;
-    } else {
-        if (int r = preview_aovs(p, &lowCam, wl, hl, seed, Al, Nl)) return r;
-        if (int r = preview_display_guide(p, cam, seed, gn)) return r;
-    }
-    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
-    if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[gn], nullptr, p->curEV, st)) return r;
-    const void* shown = p->curEV;         // the (e, V) buffer the filter reads
-    if (P.temporal) {
-        const bool hist = p->haveHist;
-        if (p->respond && hist) {         // (the arguments of the form below that the frame would have taken)
-            if (int r = pt_temporal_accumulate_respond_device(w, h, cam, &p->prevCam, nullptr, nullptr, 0, 0, nullptr, p->curEV, p->N[gn], p->N[p->curG],
-                                                              p->H[p->cur], p->L[p->cur], p->frameMotion ? p->M : nullptr, &P.temporal_params, &p->R,
-                                                              p->respondWs, p->H[nxt], p->L[nxt], nullptr, st))
-                return r;
-        } else if (p->frameMotion) {      // (a motion frame has a history)
-            if (int r = pt_temporal_accumulate_cur_motion_device(w, h, cam, &p->prevCam, p->curEV, p->N[gn], p->N[p->curG], p->H[p->cur], p->L[p->cur],
-                                                                 p->M, &P.temporal_params, p->H[nxt], p->L[nxt], st))
-                return r;
-        } else if (int r = pt_temporal_accumulate_cur_device(w, h, cam, hist ? &p->prevCam : nullptr, p->curEV, p->N[gn],
-                                                             hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr,
-                                                             hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt], p->L[nxt], st))
-            return r;
-        shown = p->H[nxt];
-    }
-    POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
-    pt_denoise_var_params F = P.filter_params;
-    if (!P.filter) F.iterations = 0;
-    if (int r = pt_denoise_hist_device(w, h, shown, p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
-    if (int r = pt_resolve_device(w, h, p->filt, 1, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
-    return 0;
-}
-
-// The five stages of a frame, enqueued on the session's stream with an event after each; the first error ends it. nxt: the half of
-// the history pair this frame writes, gn: the half of the guide pair it writes, or, when it reuses the guide (centre guides, resting
-// camera), the half it reads as this frame's guide and the previous frame's at once.
-static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, int nxt, int gn, bool reuse) {
+// The one accumulate call of a temporal frame, into H[nxt] and L[nxt]. cur: the upsampled (e, V) frame of a scaled frame, NULL for
+// the sums S and Q with albedo A. live: the live map of a converging frame, else NULL. A first frame has no previous camera, guide,
+// history or length; a motion frame has all four and hands M on.
+static int preview_accumulate(pt_preview* p, const FramePlan& f, const pt_camera* cam, const void* cur, const void* live) {
     const pt_preview_params& P = p->P;
     const int w = p->w, h = p->h;
+    const bool hist = p->haveHist;
+    const pt_camera* prevCam = hist ? &p->prevCam : nullptr;
+    const void *prevN = hist ? p->N[p->curG] : nullptr, *H = hist ? p->H[p->cur] : nullptr, *L = hist ? p->L[p->cur] : nullptr;
+    const void *N = p->N[f.gn], *M = f.motion ? p->M : nullptr;
+    void *outH = p->H[f.nxt], *outL = p->L[f.nxt];
+    if (live)
+        return pt_temporal_accumulate_live_device(w, h, cam, prevCam, p->S, p->Q, P.spp, P.batches, p->A, N, prevN, H, L, live, &P.temporal_params,
+                                                  outH, outL, p->stream);
+    if (p->respond && hist) {             // (either frame form: the sums' arguments are absent beside cur)
+        const void *S = cur ? nullptr : p->S, *Q = cur ? nullptr : p->Q, *A = cur ? nullptr : p->A;
+        return pt_temporal_accumulate_respond_device(w, h, cam, prevCam, S, Q, cur ? 0 : P.spp, cur ? 0 : P.batches, A, cur, N, prevN, H, L, M,
+                                                     &P.temporal_params, &p->R, p->respondWs, outH, outL, nullptr, p->stream);
+    }
+    // (M NULL: the base forms pt_temporal_accumulate_cur_device and pt_temporal_accumulate_device)
+    if (cur) return pt_temporal_accumulate_cur_motion_device(w, h, cam, prevCam, cur, N, prevN, H, L, M, &P.temporal_params, outH, outL, p->stream);
+    return pt_temporal_accumulate_motion_device(w, h, cam, prevCam, p->S, p->Q, P.spp, P.batches, p->A, N, prevN, H, L, M, &P.temporal_params, outH,
+                                                outL, p->stream);
+}
+
+// The five stages of a frame, enqueued on the session's stream with an event after each; the first error ends it. The file's head
+// lists what each kind of frame runs in each stage.
+static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, FramePlan& f) {
+    const pt_preview_params& P = p->P;
+    const int w = p->w, h = p->h, s = p->scale, gn = f.gn;
+    const bool scaled = s > 1;
     hipStream_t st = p->stream;
+    // what the render writes and at which size: a scaled frame's are the low-res camera and buffers
+    const pt_camera* renderCam = cam;
+    pt_camera lowCam;
+    char *S = p->S, *Q = p->Q, *Al = nullptr, *Nl = nullptr;
+    if (scaled) {
+        if (cam->w != w || cam->h != h)   // (before the low-res camera is made: the stages would see a size that need not divide)
+            return postfx_fail(-1, "pt_preview_frame: camera is %d x %d, the session %d x %d", cam->w, cam->h, w, h);
+        if (int r = pt_camera_scaled(cam, s, &lowCam)) return r;
+        const size_t lb = p->loCap * 16;
+        renderCam = &lowCam;
+        S = p->lo; Q = S + lb; Al = Q + lb; Nl = Al + lb;
+    }
+
     POSTFX_HIP_OK(hipEventRecord(p->ev[0], st));
-    // (the first stage checks its arguments, the camera's size among them, before it enqueues anything)
-    if (int r = pt_render_moments_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->S, p->Q, st)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
-    if (!reuse)
-        if (int r = preview_display_guide(p, cam, seed, gn)) return r;
-    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
-    const void* shown = p->S;             // what the resolve divides, and by what
-    int shownSpp = P.spp;
-    if (P.temporal) {
-        const bool hist = p->haveHist;
-        if (p->respond && hist) {         // (the arguments of the form below that the frame would have taken)
-            if (int r = pt_temporal_accumulate_respond_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, nullptr, p->N[gn], p->N[p->curG],
-                                                              p->H[p->cur], p->L[p->cur], p->frameMotion ? p->M : nullptr, &P.temporal_params, &p->R,
-                                                              p->respondWs, p->H[nxt], p->L[nxt], nullptr, st))
+    const int nt = p->curT ^ 1;           // the half of the tile buffers a converging frame writes
+    if (f.converging) {
+        const int T = (int)tile_count(w, h);
+        if (int r = pt_temporal_select_device(w, h, p->H[p->cur], p->L[p->cur], &p->C, p->tErr[nt], p->tLive[nt], p->tList, p->tCount, st)) return r;
+        int count = -1;
+        POSTFX_HIP_OK(hipMemcpyAsync(&count, p->tCount, sizeof(int), hipMemcpyDeviceToHost, st));
+        POSTFX_HIP_OK(hipStreamSynchronize(st));
+        if (count < 0 || count > T) return postfx_fail(-2, "pt_preview_frame: the live list holds %d of %d tiles", count, T);
+        if (count > 0)
+            if (int r = pt_render_moments_tiles_device(p->scene, cam, w, h, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, p->tList,
+                                                       count, S, Q, st))
                 return r;
-        } else if (p->frameMotion) {      // (a motion frame has a history)
-            if (int r = pt_temporal_accumulate_motion_device(w, h, cam, &p->prevCam, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], p->N[p->curG],
-                                                             p->H[p->cur], p->L[p->cur], p->M, &P.temporal_params, p->H[nxt], p->L[nxt], st))
-                return r;
-        } else if (int r = pt_temporal_accumulate_device(w, h, cam, hist ? &p->prevCam : nullptr, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn],
-                                                         hist ? p->N[p->curG] : nullptr, hist ? p->H[p->cur] : nullptr,
-                                                         hist ? p->L[p->cur] : nullptr, &P.temporal_params, p->H[nxt], p->L[nxt], st))
+        f.live = count;
+    } else {
+        // (the first stage checks its arguments, the camera's size among them, before it enqueues anything)
+        if (int r = pt_render_moments_device(p->scene, renderCam, w / s, h / s, P.spp, P.spp / P.batches, P.max_depth, P.integrator, P.use_mis, seed, S, Q,
+                                             st))
             return r;
-        POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
+    }
+
+    POSTFX_HIP_OK(hipEventRecord(p->ev[1], st));
+    if (scaled && !p->guideCentre)
+        if (int r = preview_aovs(p, f, &lowCam, w / s, h / s, seed, Al, Nl)) return r;
+    if (!f.reuse)
+        if (int r = preview_display_guide(p, f, cam, seed)) return r;
+    if (scaled && p->guideCentre)         // (also when the guide is reused: the scale may have changed since, and the copy is w * h / s^2 pixels)
+        if (int r = pt_guide_subsample_device(w, h, s, p->A, p->N[gn], Al, Nl, st)) return r;
+
+    POSTFX_HIP_OK(hipEventRecord(p->ev[2], st));
+    if (scaled)
+        if (int r = pt_upsample_device(w, h, s, S, Q, P.spp, P.batches, Al, Nl, p->A, p->N[gn], nullptr, p->curEV, st)) return r;
+    if (P.temporal)
+        if (int r = preview_accumulate(p, f, cam, scaled ? p->curEV : nullptr, f.converging ? p->tLive[nt] : nullptr)) return r;
+
+    POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
+    const void* eV = P.temporal ? p->H[f.nxt] : (scaled ? p->curEV : nullptr);     // the (e, V) buffer the history filter reads, if any
+    const void* shown = p->filt;          // what the resolve divides, and by what
+    int shownSpp = 1;
+    if (eV) {
         pt_denoise_var_params F = P.filter_params;
         if (!P.filter) F.iterations = 0;  // no iteration: the history's mean a e, pass-through pixels as they are
-        if (int r = pt_denoise_hist_device(w, h, p->H[nxt], p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
-        shown = p->filt; shownSpp = 1;
+        if (int r = pt_denoise_hist_device(w, h, eV, p->A, p->N[gn], &F, p->ws, p->filt, st)) return r;
     } else {
-        POSTFX_HIP_OK(hipEventRecord(p->ev[3], st));
-        if (P.filter) {
-            if (int r = pt_denoise_var_device(w, h, p->S, p->Q, P.spp, P.batches, p->A, p->N[gn], &P.filter_params, p->ws, p->filt, st)) return r;
-            shown = p->filt;
-        }
+        shownSpp = P.spp;
+        if (!P.filter) shown = S;
+        else if (int r = pt_denoise_var_device(w, h, S, Q, P.spp, P.batches, p->A, p->N[gn], &P.filter_params, p->ws, p->filt, st)) return r;
     }
+
     POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, shown, shownSpp, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
     POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
@@ -539,40 +521,42 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, in
 int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     if (!p) return postfx_fail(-1, "pt_preview_frame: null session");
     if (!cam) return postfx_fail(-1, "pt_preview_frame: null camera");
-    const int nxt = p->P.temporal ? p->cur ^ 1 : 0;
-    p->frameLive = ((p->w + 7) / 8) * ((p->h + 7) / 8); p->frameConverged = false;
-    // a scene updated behind the session's back: its history and guide are another geometry's, and nobody said to keep them
-    const int gen = pt_scene_generation(p->scene);
-    if (gen != p->sceneGen && !p->sceneChanged) { p->haveHist = p->haveFrame = p->haveTiles = false; p->sceneChanged = true; }
+    FramePlan f = {};
+    f.nxt = p->P.temporal ? p->cur ^ 1 : 0;
+    f.live = (int)tile_count(p->w, p->h);
+    // a scene updated behind the session's back: its history and guide are another geometry's, and nobody said to keep them. (What
+    // pt_preview_scene_changed(p, 0) would have done: it holds whether or not this frame succeeds, so it is no part of the plan.)
+    f.gen = pt_scene_generation(p->scene);
+    if (f.gen != p->sceneGen && !p->sceneChanged) { drop_history(p); p->sceneChanged = true; }
     // (a changed scene is a moved camera to the converge and guide-reuse decisions; the accumulation still sees the camera's bytes)
-    const bool same = p->haveHist && !p->sceneChanged && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
+    f.same = p->haveHist && !p->sceneChanged && memcmp(cam, &p->prevCam, sizeof(pt_camera)) == 0;
     // a MOTION FRAME: the one vertex update since the last good frame was announced with its history kept, and the scene still has
     // the positions from before it
-    p->frameMotion = p->motion && p->P.temporal && p->haveHist && p->sceneChanged && gen == p->sceneGen + 1 && pt_scene_has_motion(p->scene) == 1;
-    const bool rests = p->converge && p->P.temporal && p->scale == 1 && same;
+    f.motion = p->motion && p->P.temporal && p->haveHist && p->sceneChanged && f.gen == p->sceneGen + 1 && pt_scene_has_motion(p->scene) == 1;
+    f.converging = p->converge && p->P.temporal && p->scale == 1 && f.same;
     // centre guides, the camera of the last good frame, and that frame's guide still in place: no feature pass, no guide flip
-    const bool reuse = p->guideCentre && same && p->guideFresh;
-    const int gn = reuse ? p->curG : (p->P.temporal ? p->curG ^ 1 : 0);
-    if (!reuse) p->guideFresh = false;                     // (the feature pass writes A, of which there is one)
-    p->framePasses = 0;
-    const int r = rests ? preview_stages_converge(p, cam, seed, nxt, gn, reuse)
-                        : (p->scale > 1 ? preview_stages_scaled(p, cam, seed, nxt, gn, reuse) : preview_stages(p, cam, seed, nxt, gn, reuse));
+    f.reuse = p->guideCentre && f.same && p->guideFresh;
+    f.gn = f.reuse ? p->curG : (p->P.temporal ? p->curG ^ 1 : 0);
+    // the feature pass writes A, of which there is one: the one thing a frame that then fails has done to the session
+    if (!f.reuse) p->guideFresh = false;
+    const int r = preview_stages(p, cam, seed, f);
     const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
     if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
     if (e != hipSuccess) return postfx_fail(-2, "pt_preview_frame: the stream failed to synchronise");
     float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, total = 0.0f;
     for (int i = 0; i < 5; i++) POSTFX_HIP_OK(hipEventElapsedTime(&ms[i], p->ev[i], p->ev[i + 1]));
     POSTFX_HIP_OK(hipEventElapsedTime(&total, p->ev[0], p->ev[5]));
-    p->cur = nxt;
-    p->curG = gn;
+    // the commit: from here on the frame is the session's last good frame
+    p->cur = f.nxt;
+    p->curG = f.gn;
     p->guideFresh = true;
-    p->guidePasses += p->framePasses;
+    p->guidePasses += f.passes;
     p->haveHist = p->P.temporal != 0;
     p->haveFrame = true;
     p->prevCam = *cam;
-    p->sceneGen = gen; p->sceneChanged = false;
-    p->lastLive = p->frameLive;
-    if (p->frameConverged) { p->curT ^= 1; p->haveTiles = true; }
+    p->sceneGen = f.gen; p->sceneChanged = false;
+    p->lastLive = f.live;
+    if (f.converging) { p->curT ^= 1; p->haveTiles = true; }
     p->stats.frames++;
     p->stats.render_ms = ms[0]; p->stats.aov_ms = ms[1]; p->stats.accumulate_ms = ms[2]; p->stats.filter_ms = ms[3]; p->stats.resolve_ms = ms[4];
     p->stats.total_ms = total;

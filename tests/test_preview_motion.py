@@ -83,7 +83,9 @@ def _chain_step(api, gs, state, cam, seed, centre, links, scale, motion_frame):
     (1, 0, 1, "pinhole", 1),
     (1, 2, 1, "pinhole", 2),       # a guide chain: the chain pass, then the motion pass
     (0, 0, 2, "pinhole", 3),       # scale 2: the low-res guide, the display guide, the motion pass
-    (1, 0, 2, "pinhole", 1)])      # ... with centre guides the subsample is no pass
+    (1, 0, 2, "pinhole", 1),       # ... with centre guides the subsample is no pass
+    (0, 2, 2, "pinhole", 3),       # scale 2 with a guide chain: the low-res chain, the display chain, the motion pass
+    (1, 2, 2, "pinhole", 2)])      # ... with centre guides: the centre chain, the motion pass
 def test_motion_frames_equal_the_chain_of_host_calls(api, host, moves, centre, links, scale, kind, rise):
     cams = _cams(api, kind, W, H, BEFORE + AFTER)
     seeds = [70 + t for t in range(BEFORE + AFTER)]
