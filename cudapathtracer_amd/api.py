@@ -151,6 +151,8 @@ def lib():
     L.pt_scene_update_vertices.argtypes = [vp, vp, i32, vp, i32, vp]
     L.pt_scene_update_vertices_device.argtypes = [vp, vp, i32, vp, i32, vp]
     L.pt_scene_generation.argtypes = [vp]
+    L.pt_scene_update_materials.argtypes = [vp, vp, i32]
+    L.pt_scene_update_emission.argtypes = [vp, i32, vp, vp]
     L.pt_scene_has_motion.argtypes = [vp]
     L.pt_render_motion.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, vp, vp]
     L.pt_render_motion_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, vp, vp, vp]
@@ -568,14 +570,37 @@ class Scene:
         self.build_stats = {f: st[0][f].item() for f in BUILD_STATS.names}
         return self
 
+    def update_materials(self, materials):
+        """pt_scene_update_materials: replace the material table in place; nothing is rebuilt. materials: the scene's number of
+        176-byte pt_material records, as an array of them or anything numpy can view as bytes (HostScene.array("materials") gives
+        one). Works on any scene; the scene then renders as a fresh one of the edited description, and has_motion drops to 0."""
+        m = np.ascontiguousarray(materials).view(np.uint8).reshape(-1)
+        if m.size % 176:
+            raise PtError("update_materials: %d bytes are no whole number of 176-byte material records" % m.size)
+        _check(lib().pt_scene_update_materials(self.h, _p(m), m.size // 176), "pt_scene_update_materials")
+        return self
+
+    def update_emission(self, light_indices, emission):
+        """pt_scene_update_emission: lights[light_indices[k]] and every triangle of that light emit emission[k] (float4 each; rows
+        of three floats get w = 0). The set of lights stays; a repeated index takes its last entry."""
+        idx = np.ascontiguousarray(light_indices, np.int32).reshape(-1)
+        e = np.ascontiguousarray(emission, np.float32).reshape(len(idx), -1)
+        if e.shape[1] == 3:
+            e = np.ascontiguousarray(np.concatenate([e, np.zeros((len(idx), 1), np.float32)], axis=1))
+        if e.shape[1] != 4:
+            raise PtError("update_emission: one float3 or float4 per light index is needed")
+        _check(lib().pt_scene_update_emission(self.h, len(idx), _p(idx), _p(e)), "pt_scene_update_emission")
+        return self
+
     @property
     def generation(self):
-        """pt_scene_generation: 0 after create, +1 per successful update_mesh / update_vertices."""
+        """pt_scene_generation: 0 after create, +1 per successful update_mesh / update_vertices / update_materials /
+        update_emission."""
         return lib().pt_scene_generation(self.h)
 
     def packed(self, what):
-        """Test hook (pt_debug_packed): the traversal records as uint8 [count, record size]; what = nodes / tris / attrs / lights."""
-        code, rec = {"nodes": (0, 64), "tris": (1, 48), "attrs": (2, 80), "lights": (3, 64)}[what]
+        """Test hook (pt_debug_packed): the records as uint8 [count, record size]; what = nodes / tris / attrs / lights / mats."""
+        code, rec = {"nodes": (0, 64), "tris": (1, 48), "attrs": (2, 80), "lights": (3, 64), "mats": (4, 96)}[what]
         n = lib().pt_debug_packed(self.h, code, None, 0)
         if n < 0:
             raise PtError("pt_debug_packed failed")

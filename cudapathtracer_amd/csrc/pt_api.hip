@@ -74,7 +74,7 @@ struct pt_scene {
     int numCU = 256;
     DeviceScene ds{};
     int stackNeed = 0, nInternal = 0, cacheNodes = 0, cacheTris = 0;
-    int nMats = 0, nLightsPacked = 0;
+    int nMats = 0, nLightsPacked = 0, nTexels = 0;
     bool armless = false;        // a triangle uses a material type without a dispatch arm (pt_path.h): DEFER is not exact
     // Everything below is set per scene through pt_set_option (names in quotes); the library reads no environment variable.
     int schedMask = 31;          // "sched_mask": scheduling checks every schedMask + 1 bounce iterations (tests use 3)
@@ -124,6 +124,7 @@ struct pt_scene {
     DevBuf posCur, posPrev;
     bool hasMotion = false;               // pt_scene_has_motion: the last successful update was a vertex update
     DevBuf motionOut;                     // pt_render_motion, host form: staging
+    DevBuf edit;                          // pt_scene_update_materials / _emission: the edit's table and the kernel's result word
     float renumberMs = 0.0f, updateMs = 0.0f;   // host wall clock of the last renumber_by_area / of the last successful update (pt_debug_update_ms)
     float lastKernelMs = 0.0f;
     bool evPending = false;                            // ev0/ev1 recorded, elapsed time not read yet
@@ -175,7 +176,7 @@ void pt_scene_destroy(pt_scene* s) {
                      &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList,
                      &s->kTris, &s->kNormals, &s->kUvs, &s->kTypes, &s->kLightTris,
                      &s->spNodes, &s->spTris, &s->spAttrs, &s->spLights, &s->spLeaves, &s->spNormals, &s->buildPool,
-                     &s->posCur, &s->posPrev, &s->motionOut};
+                     &s->posCur, &s->posPrev, &s->motionOut, &s->edit};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -258,6 +259,44 @@ static void light_triangles(const PTri* pt, int nT, const pt_scene_desc* d, int3
 static int renumber_by_area(pt_scene* s, int nInternal, int rootRef);
 static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef, int nT, int nLights, bool haveLights, int nMats, const PLight* hostLights,
                          const int32_t* lightIndOf, int nLightInd);
+
+// The material table as the kernels read it, and the class word of every row (pt_bvh_build.h: pt_material_class_). Creation and
+// pt_scene_update_materials both pack through here; fn names the caller in the message of a refused texture window.
+static int pack_materials(const pt_material* materials, int nMats, int nTexels, const char* fn, std::vector<PMat>& mats, std::vector<uint32_t>& matClass) {
+    mats.resize((size_t)nMats); matClass.resize((size_t)nMats);
+    std::memset(mats.data(), 0, mats.size() * sizeof(PMat));
+    for (int i = 0; i < nMats; i++) {
+        const pt_material& m = materials[i];
+        PMat& p = mats[i];
+        p.type = m.type;
+        p.flags = (m.hasTexture ? kMatHasTexture : 0) | (m.hasTransMap ? kMatHasTransMap : 0) | (m.isSpecular ? kMatSpecular : 0) | (m.boundary ? kMatBoundary : 0);
+        p.priority = m.priority;
+        p.texStart = m.startInd; p.texW = m.width; p.texH = m.height;
+        if ((m.hasTexture || m.hasTransMap) && m.width > 0 && m.height > 0 &&
+            (m.startInd < 0 || (long long)m.startInd + (long long)m.width * m.height > nTexels))
+            return fail(-1, "%s: material %d texture window exceeds the texel array", fn, i);
+        p.roughness = m.roughness; p.ior = m.ior; p.transmission = m.transmission;
+        p.albedo[0] = m.albedo.x; p.albedo[1] = m.albedo.y; p.albedo[2] = m.albedo.z;
+        p.eta[0] = m.eta.x; p.eta[1] = m.eta.y; p.eta[2] = m.eta.z;
+        p.k[0] = m.k.x; p.k[1] = m.k.y; p.k[2] = m.k.z;
+        p.absorption[0] = m.absorption.x; p.absorption[1] = m.absorption.y; p.absorption[2] = m.absorption.z;
+        p.albedoOverPi[0] = m.albedo.x / kPi; p.albedoOverPi[1] = m.albedo.y / kPi; p.albedoOverPi[2] = m.albedo.z / kPi;   // cosine_f, reflectors.cuh:10-13
+        matClass[i] = pt_material_class_(m);
+    }
+    return 0;
+}
+
+// What a scene decides from its triangles' materials alone, from `used` = the class words of the rows its triangles use, OR-ed:
+// all four from scratch, since an edit can clear what another set.
+// SIMPLE scenes (pt_path.h): every triangle's material an untextured MAT_DIFFUSE that is neither boundary nor specular, in air
+// (material 0) that does not absorb — then the medium stack never changes and the dispatchers have one arm. noLeafTris: no triangle
+// carries MAT_LEAF. LEAN (pt_shade.h): additionally no triangle's material samples a texture. armless: pt_bvh_build.h.
+static void apply_material_class(pt_scene* s, uint32_t used, const pt_material& air) {
+    s->simpleOk = air.absorption.x == 0.0f && air.absorption.y == 0.0f && air.absorption.z == 0.0f && !(used & kRowNotSimple);
+    s->noLeafTris = !(used & kTriLeaf);
+    s->leanOk = s->noLeafTris && !(used & kRowTextured);
+    s->armless = (used & kTriArmless) != 0;
+}
 
 // update: the scene is being updated in place (pt_scene_update_mesh): `s` is the staging scene whose buffers are swapped in on
 // success; the jump table and the counters stay the live scene's and are not touched here.
@@ -371,11 +410,7 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         p.e2[0] = c.x - a.x; p.e2[1] = c.y - a.y; p.e2[2] = c.z - a.z;      // tric - tria, :14
         p.idx = (uint32_t)idx | (leafEnd[i] ? 0x80000000u : 0u);
         p.material = t.materialID;
-        p.flags = d->materials[t.materialID].type == PT_MAT_LEAF ? 1u : 0u;
-        {
-            const int ty = d->materials[t.materialID].type;
-            if (!(ty == PT_MAT_DIFFUSE || ty == PT_MAT_METAL || ty == PT_MAT_SMOOTHDIELECTRIC || ty == PT_MAT_LEAF || ty == PT_MAT_DELTAMIRROR)) s->armless = true;
-        }
+        p.flags = pt_tri_flags_(d->materials[t.materialID].type);
     }
     // --- hit attributes by original index ---
     attrs.resize(nT);
@@ -416,49 +451,15 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         L.area = 0.5f * sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
     }
     // --- materials ---
-    std::vector<PMat> mats(d->n_materials);
-    std::memset(mats.data(), 0, mats.size() * sizeof(PMat));
-    for (int i = 0; i < d->n_materials; i++) {
-        const pt_material& m = d->materials[i];
-        PMat& p = mats[i];
-        p.type = m.type;
-        p.flags = (m.hasTexture ? kMatHasTexture : 0) | (m.hasTransMap ? kMatHasTransMap : 0) | (m.isSpecular ? kMatSpecular : 0) | (m.boundary ? kMatBoundary : 0);
-        p.priority = m.priority;
-        p.texStart = m.startInd; p.texW = m.width; p.texH = m.height;
-        if ((m.hasTexture || m.hasTransMap) && m.width > 0 && m.height > 0 &&
-            (m.startInd < 0 || (long long)m.startInd + (long long)m.width * m.height > d->n_texels))
-            return fail(-1, "pt_scene_create: material %d texture window exceeds the texel array", i);
-        p.roughness = m.roughness; p.ior = m.ior; p.transmission = m.transmission;
-        p.albedo[0] = m.albedo.x; p.albedo[1] = m.albedo.y; p.albedo[2] = m.albedo.z;
-        p.eta[0] = m.eta.x; p.eta[1] = m.eta.y; p.eta[2] = m.eta.z;
-        p.k[0] = m.k.x; p.k[1] = m.k.y; p.k[2] = m.k.z;
-        p.absorption[0] = m.absorption.x; p.absorption[1] = m.absorption.y; p.absorption[2] = m.absorption.z;
-        p.albedoOverPi[0] = m.albedo.x / kPi; p.albedoOverPi[1] = m.albedo.y / kPi; p.albedoOverPi[2] = m.albedo.z / kPi;   // cosine_f, reflectors.cuh:10-13
-    }
-
-    // SIMPLE scenes (pt_path.h): every triangle's material an untextured MAT_DIFFUSE that is neither boundary nor specular,
-    // in air (material 0) that does not absorb — then the medium stack never changes and the dispatchers have one arm.
+    std::vector<PMat> mats; std::vector<uint32_t> matClass;
+    if (int r = pack_materials(d->materials, d->n_materials, d->n_texels, "pt_scene_create", mats, matClass)) return r;
     {
-        bool simple = d->materials[0].absorption.x == 0.0f && d->materials[0].absorption.y == 0.0f && d->materials[0].absorption.z == 0.0f;
-        for (int i = 0; i < nT && simple; i++) {
+        uint32_t used = 0u;                       // the classes of the rows the triangles use (a device-built scene's builder refuses an index outside the table)
+        for (int i = 0; i < nT; i++) {
             const int id = d->triangles[i].materialID;
-            if (id < 0 || id >= d->n_materials) { simple = false; break; }
-            const pt_material& m = d->materials[id];
-            simple = m.type == PT_MAT_DIFFUSE && !m.hasTexture && !m.hasTransMap && !m.boundary && !m.isSpecular;
+            if (id >= 0 && id < d->n_materials) used |= matClass[id];
         }
-        s->simpleOk = simple;
-        bool noLeaf = true;
-        for (int i = 0; i < nT && noLeaf; i++) {
-            const int id = d->triangles[i].materialID;
-            noLeaf = id >= 0 && id < d->n_materials && d->materials[id].type != PT_MAT_LEAF;
-        }
-        s->noLeafTris = noLeaf;
-        bool lean = noLeaf;                       // LEAN (pt_shade.h): additionally no triangle's material samples a texture
-        for (int i = 0; i < nT && lean; i++) {
-            const pt_material& m = d->materials[d->triangles[i].materialID];
-            lean = !m.hasTexture && !m.hasTransMap;
-        }
-        s->leanOk = lean;
+        apply_material_class(s, used, d->materials[0]);
     }
     if (!onDevice) {
         if (int r = upload(s->nodes, nodes.data(), nodes.size() * sizeof(PNode))) return r;
@@ -496,6 +497,7 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
     if (int r = upload(s->lights, lights.data(), lights.size() * sizeof(PLight))) return r;
     if (int r = upload(s->mats, mats.data(), mats.size() * sizeof(PMat))) return r;
     if (int r = upload(s->textures, d->textures, (size_t)std::max(d->n_texels, 0) * sizeof(float4))) return r;
+    s->nTexels = d->n_texels;                 // (what a later material edit checks its texture windows against, as above)
     if (!update) {
         const std::vector<uint32_t>& jt = xorwow_host::jump_table();
         if (int r = upload(s->jump, jt.data(), jt.size() * sizeof(uint32_t))) return r;
@@ -688,7 +690,7 @@ static void adopt_geometry(pt_scene* s, pt_scene& t, bool mesh, bool normals) {
         std::swap(s->mats, t.mats); std::swap(s->textures, t.textures);
         std::swap(s->kTris, t.kTris); std::swap(s->kUvs, t.kUvs); std::swap(s->kTypes, t.kTypes); std::swap(s->kLightTris, t.kLightTris);
         std::swap(s->posCur, t.posCur); s->hasMotion = false;        // the topology may have changed: no previous positions, no motion
-        s->deviceLeaf = t.deviceLeaf; s->nPositions = t.nPositions; s->nNormals = t.nNormals; s->nUvs = t.nUvs;
+        s->deviceLeaf = t.deviceLeaf; s->nPositions = t.nPositions; s->nNormals = t.nNormals; s->nUvs = t.nUvs; s->nTexels = t.nTexels;
     }
     s->ds = t.ds;
     s->ds.nodes = (const PNode*)s->nodes.p; s->ds.tris = (const PTri*)s->tris.p; s->ds.attrs = (const PAttr*)s->attrs.p;
@@ -804,6 +806,85 @@ int pt_scene_update_mesh(pt_scene* s, const pt_scene_desc* d, int max_leaf_size,
     return r;
 }
 
+// ---- material and emission edits: pt_scene_update_materials / pt_scene_update_emission --------------------------------------------
+// Neither touches the tree, the geometry records' geometry, the leaf table, lightTri8 or the cache split: derive_layout reads a
+// material only through scene_onchip_wg's per-wave area (a medium stack unless the scene is SIMPLE), and that cannot decide whether
+// a scene small enough for the FLAT kernels is LDS-resident: at 16 waves the largest such scene fits with the medium stacks.
+static_assert(kAttrCacheBytes > 0 && 128 * 64 + 128 * 48 + 4 * kAttrCacheBytes + 16 * (kStackFlat2Rows * 256 + kMediumMax * 64) <= 160 * 1024,
+              "a material edit would have to derive flatOk again");
+
+// The end of a successful edit: one generation on, and the previous positions describe a step the viewer has already seen.
+static void edit_done(pt_scene* s, double t0) {
+    s->hasMotion = false;
+    // pt_scene_flags describes the last launch: there is none on these records yet
+    s->lastLaunchFlat = s->lastLaunchSimple = s->lastLaunchLeafTable = s->lastLaunchFlat2 = s->lastLaunchLean = s->lastLaunchRefill = 0;
+    s->lastLaunchHbm = -1;
+    s->generation++;
+    s->updateMs = (float)(wall_ms() - t0);
+}
+
+int pt_scene_update_materials(pt_scene* s, const pt_material* materials, int n_materials) {
+    const char* fn = "pt_scene_update_materials";
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!materials) return fail(-1, "%s: null materials", fn);
+    if (n_materials != s->nMats) return fail(-1, "%s: %d materials, the scene has %d", fn, n_materials, s->nMats);
+    std::vector<PMat> mats; std::vector<uint32_t> matClass;
+    if (int r = pack_materials(materials, n_materials, s->nTexels, fn, mats, matClass)) return r;
+    const double t0 = wall_ms();
+    HIP_OK(hipDeviceSynchronize());        // a frame boundary: nothing that reads the old table is in flight
+    // the edit buffer: the kernel's result word, then the class of every row
+    const size_t classOff = 256, classBytes = matClass.size() * sizeof(uint32_t);
+    if (int r = s->edit.ensure(classOff + classBytes)) return r;
+    uint32_t* dUsed = (uint32_t*)s->edit.p;
+    uint32_t* dClass = (uint32_t*)((char*)s->edit.p + classOff);
+    HIP_OK(hipMemset(dUsed, 0, sizeof(uint32_t)));
+    HIP_OK(hipMemcpy(dClass, matClass.data(), classBytes, hipMemcpyHostToDevice));
+    if (int r = pt_edit_materials_(s->tris.p, s->nTrisPacked, dClass, n_materials, dUsed)) return r;
+    uint32_t used = 0u;
+    HIP_OK(hipMemcpy(&used, dUsed, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(s->mats.p, mats.data(), mats.size() * sizeof(PMat), hipMemcpyHostToDevice));
+    if (s->deviceLeaf >= 0) {              // what the next vertex update packs the triangles' flags from
+        std::vector<int> types((size_t)n_materials);
+        for (int i = 0; i < n_materials; i++) types[i] = materials[i].type;
+        HIP_OK(hipMemcpy(s->kTypes.p, types.data(), types.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    apply_material_class(s, used, materials[0]);
+    edit_done(s, t0);
+    return 0;
+}
+
+int pt_scene_update_emission(pt_scene* s, int n, const int32_t* light_indices, const pt_float4* emission) {
+    const char* fn = "pt_scene_update_emission";
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (n < 0) return fail(-1, "%s: negative count", fn);
+    if (n > 0 && (!light_indices || !emission)) return fail(-1, "%s: null %s", fn, !light_indices ? "light_indices" : "emission");
+    const int nL = s->ds.nLights, nT = s->nTrisPacked;
+    for (int k = 0; k < n; k++)
+        if (light_indices[k] < 0 || light_indices[k] >= nL) return fail(-1, "%s: light index %d (entry %d) out of range, the scene has %d lights", fn, light_indices[k], k, nL);
+    // the edit as a table by light: the new emission and whether the light is edited at all (a repeated index: the last entry stands)
+    std::vector<pt_float4> table((size_t)std::max(nL, 1));
+    std::vector<int32_t> on((size_t)std::max(nL, 1), 0);
+    std::memset(table.data(), 0, table.size() * sizeof(pt_float4));
+    for (int k = 0; k < n; k++) { table[light_indices[k]] = emission[k]; on[light_indices[k]] = 1; }
+    const double t0 = wall_ms();
+    HIP_OK(hipDeviceSynchronize());        // a frame boundary
+    if (n > 0) {
+        const size_t tableBytes = table.size() * sizeof(pt_float4), onBytes = on.size() * sizeof(int32_t);
+        if (int r = s->edit.ensure(tableBytes + onBytes)) return r;
+        pt_float4* dTable = (pt_float4*)s->edit.p;
+        int32_t* dOn = (int32_t*)((char*)s->edit.p + tableBytes);
+        HIP_OK(hipMemcpy(dTable, table.data(), tableBytes, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dOn, on.data(), onBytes, hipMemcpyHostToDevice));
+        const bool kept = s->deviceLeaf >= 0;       // ... and what the next vertex update packs attributes and lights from
+        if (int r = pt_edit_emission_(s->attrs.p, nT, s->lights.p, nL, dTable, dOn, kept ? (pt_triangle*)s->kTris.p : nullptr,
+                                      kept ? (pt_triangle*)s->kLightTris.p : nullptr))
+            return r;
+        HIP_OK(hipDeviceSynchronize());
+    }
+    edit_done(s, t0);
+    return 0;
+}
+
 int pt_scene_generation(pt_scene* s) { return s ? s->generation : fail(-1, "pt_scene_generation: null scene"); }
 
 int pt_scene_has_motion(pt_scene* s) { return s ? (s->hasMotion ? 1 : 0) : fail(-1, "pt_scene_has_motion: null scene"); }
@@ -814,13 +895,13 @@ int pt_debug_update_ms(pt_scene* s, float* out3) {
     return 0;
 }
 
-// what: 0 PNodes (64 B each), 1 PTris (48 B), 2 PAttrs (80 B), 3 PLights (64 B). Returns the record count (or < 0); copies
-// min(count * size, capacity) bytes. For tests: the device re-layout must equal the host one.
+// what: 0 PNodes (64 B each), 1 PTris (48 B), 2 PAttrs (80 B), 3 PLights (64 B), 4 PMats (96 B). Returns the record count (or < 0);
+// copies min(count * size, capacity) bytes. For tests: the device re-layout must equal the host one.
 int pt_debug_packed(pt_scene* s, int what, void* dst, size_t capacity) {
     if (!s) return fail(-1, "null scene");
-    const void* src = what == 0 ? s->nodes.p : what == 1 ? s->tris.p : what == 2 ? s->attrs.p : what == 3 ? s->lights.p : nullptr;
-    const size_t rec = what == 0 ? sizeof(PNode) : what == 1 ? sizeof(PTri) : what == 2 ? sizeof(PAttr) : sizeof(PLight);
-    const int count = what == 0 ? s->nInternal : what == 3 ? s->ds.nLights : s->nTrisPacked;
+    const void* src = what == 0 ? s->nodes.p : what == 1 ? s->tris.p : what == 2 ? s->attrs.p : what == 3 ? s->lights.p : what == 4 ? s->mats.p : nullptr;
+    const size_t rec = what == 0 ? sizeof(PNode) : what == 1 ? sizeof(PTri) : what == 2 ? sizeof(PAttr) : what == 3 ? sizeof(PLight) : sizeof(PMat);
+    const int count = what == 0 ? s->nInternal : what == 3 ? s->ds.nLights : what == 4 ? s->nMats : s->nTrisPacked;
     if (!src) return fail(-1, "pt_debug_packed: unknown array %d", what);
     const size_t bytes = std::min((size_t)count * rec, capacity);
     if (dst && bytes) HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));

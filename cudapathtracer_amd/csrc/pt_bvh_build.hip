@@ -924,8 +924,8 @@ __global__ void k_pack_tris(Arrays A, const int* idx, PackIn in, const unsigned 
     if (mat < 0 || mat >= in.nMats) { atomicOr(flagsOut, 1); mat = 0; }
     p.material = mat;
     const int ty = in.matType[mat];
-    p.flags = ty == PT_MAT_LEAF ? 1u : 0u;
-    if (!(ty == PT_MAT_DIFFUSE || ty == PT_MAT_METAL || ty == PT_MAT_SMOOTHDIELECTRIC || ty == PT_MAT_LEAF || ty == PT_MAT_DELTAMIRROR)) atomicOr(flagsOut, 0x100);
+    p.flags = pt_tri_flags_(ty);
+    if (!pt_type_has_arm_(ty)) atomicOr(flagsOut, (int)kTriArmless);
     tris[i] = p;
 }
 __global__ void k_pack_attrs(Arrays A, PackIn in, pt::PAttr* attrs, int* flagsOut) {
@@ -971,6 +971,45 @@ __global__ void k_pack_lights(Arrays A, PackIn in, const pt_triangle* lightTris,
     const float cx = fmaf(uy, vz, -(uz * vy)), cy = fmaf(uz, vx, -(ux * vz)), cz = fmaf(ux, vy, -(uy * vx));
     L.area = 0.5f * sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
     lights[i] = L;
+}
+
+// ---- edits in place (pt_scene_update_materials / pt_scene_update_emission, pt_bvh_build.h): what the pack kernels above would
+// write for the edited description, without the tree, the positions or the builder's arrays.
+// One thread per packed triangle: its flags word from its material row's class (pt_material_class_), the only word of the record a
+// material decides; the classes are OR-ed over the wave with one ballot per class bit and leave it in one atomicOr. Lanes past the
+// end carry class 0 and stay for the ballots.
+constexpr uint32_t kClassBits[4] = {kTriLeaf, kRowTextured, kRowNotSimple, kTriArmless};
+__global__ void k_edit_materials(pt::PTri* tris, int n, const uint32_t* cls, int nMats, uint32_t* orOut) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c = 0u;
+    if (i < n) {
+        const int mat = tris[i].material;                      // creation refused an index outside the table
+        if (mat >= 0 && mat < nMats) c = cls[mat];
+        tris[i].flags = c & kTriLeaf;
+    }
+    uint32_t w = 0u;
+    for (int b = 0; b < 4; b++)
+        if (__ballot((c & kClassBits[b]) != 0u)) w |= kClassBits[b];
+    if ((threadIdx.x & 63) == 0 && w) atomicOr(orOut, w);
+}
+// Thread i < n: attribute i (original triangle index, as the kept triangles are) takes its light's emission if that light is edited;
+// thread i < nLights: light i itself. emission / on: the edit as a table by light, so that a triangle does one lookup.
+__global__ void k_edit_emission(pt::PAttr* attrs, int n, pt::PLight* lights, int nLights, const pt_float4* emission, const int32_t* on,
+                                pt_triangle* keptTris, pt_triangle* keptLightTris) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int li = attrs[i].lightInd;
+        if (li >= 0 && li < nLights && on[li]) {
+            const pt_float4 e = emission[li];
+            attrs[i].emission[0] = e.x; attrs[i].emission[1] = e.y; attrs[i].emission[2] = e.z;
+            if (keptTris) keptTris[i].emission = e;
+        }
+    }
+    if (i < nLights && on[i]) {
+        const pt_float4 e = emission[i];
+        lights[i].emission[0] = e.x; lights[i].emission[1] = e.y; lights[i].emission[2] = e.z;
+        if (keptLightTris) keptLightTris[i].emission = e;
+    }
 }
 
 struct Built {                        // what build_core leaves on the device (pool still allocated)
@@ -1242,4 +1281,18 @@ extern "C" int pt_bvh_build_pack_(const pt_build_src_* d, int max_leaf_size, voi
     out5[0] = nInternal; out5[1] = B.height - 1; out5[2] = rootRef; out5[3] = (fl & 0x100) ? 1 : 0; out5[4] = B.total;
     fill_stats(stats, B, ms, wall0);
     return 0;
+}
+
+extern "C" int pt_edit_materials_(void* d_tris, int n_triangles, const uint32_t* d_class, int n_materials, uint32_t* d_or) {
+    hipLaunchKernelGGL(k_edit_materials, dim3(blocks(n_triangles)), dim3(kBlock), 0, nullptr, (pt::PTri*)d_tris, n_triangles, d_class, n_materials, d_or);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : pt_fail_(-2, hipGetErrorString(e));
+}
+
+extern "C" int pt_edit_emission_(void* d_attrs, int n_triangles, void* d_lights, int n_lights, const pt_float4* d_emission, const int32_t* d_on,
+                                 pt_triangle* d_kept_tris, pt_triangle* d_kept_light_tris) {
+    hipLaunchKernelGGL(k_edit_emission, dim3(blocks(std::max(n_triangles, n_lights))), dim3(kBlock), 0, nullptr, (pt::PAttr*)d_attrs, n_triangles,
+                       (pt::PLight*)d_lights, n_lights, d_emission, d_on, d_kept_tris, d_kept_light_tris);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : pt_fail_(-2, hipGetErrorString(e));
 }

@@ -947,7 +947,8 @@ int pt_bvh_build_device(const pt_float4* positions, int n_positions, const pt_tr
  * pt_scene_create from the host-built tree. */
 pt_scene* pt_scene_create_from_mesh(const pt_scene_desc* desc, int max_leaf_size, pt_bvh_build_stats* stats);
 /* Test hook: copy the packed traversal records back (what: 0 nodes 64 B, 1 triangles 48 B, 2 attributes 80 B,
- * 3 lights 64 B); returns the record count. */
+ * 3 lights 64 B,
+ * 4 materials 96 B); returns the record count. */
 int pt_debug_packed(pt_scene* scene, int what, void* dst, size_t capacity_bytes);
 
 /* ---- dynamic geometry: in-place updates of a scene, the reference's tree rebuilt on the device -------------------
@@ -986,6 +987,35 @@ int pt_scene_update_vertices(pt_scene* scene, const pt_float4* positions, int n_
 int pt_scene_update_vertices_device(pt_scene* scene, const void* d_positions, int n_positions,
                                     const void* d_normals, int n_normals, pt_bvh_build_stats* stats);
 int pt_scene_generation(pt_scene* scene);
+
+/* ---- material and emission edits: the look of a live scene changed in place, nothing rebuilt ------------------------------------
+ * pt_scene_update_materials: the scene's description with its material table replaced by `materials`. n_materials must equal the
+ * scene's (-1 otherwise: the number of materials does not change). Texture windows are checked against the scene's texel count
+ * exactly as creation checks them. The triangles' materialIDs, the textures and everything else stay.
+ * pt_scene_update_emission: for each k < n, with li = light_indices[k] in 0..n_lights-1, the description has lights[li].emission =
+ * emission[k] and every triangle whose lightInd == li has that emission; a repeated index takes its last entry. The set of lights
+ * does not change: a light set to (0, 0, 0) stays in the light list, as it would in a fresh scene of that description, and turning a
+ * triangle that is no light into one stays pt_scene_update_mesh's job. n = 0 edits nothing and still counts as an edit.
+ * Both are host, blocking calls on ANY scene, one made by pt_scene_create from a caller's BVH included: the edit runs on the packed
+ * records, on the device, one thread per triangle. A device-built scene additionally refreshes what its next
+ * pt_scene_update_vertices packs from (the material types; the emission of its kept triangles and light triangles).
+ *
+ * EQUIVALENCE, as for the updates above: after a successful call every entry point that takes the scene gives results bit-identical
+ * to a fresh scene of the edited description — pt_scene_create_from_mesh for a device-built scene, pt_scene_create for one made from
+ * a caller's BVH — with the same options, variant and culling. The packed triangles, attributes, lights and materials are
+ * byte-identical to the fresh scene's, and so are pt_scene_flags before and after a launch and the choice of kernel: which kernel
+ * family the scene qualifies for (SIMPLE, LEAN, the pair form's "no leaf triangle", a material type without a dispatch arm) is
+ * decided again from scratch, so a diffuse box turned into a mirror leaves the SIMPLE kernels and comes back with the edit undone.
+ * KEPT: everything the updates above keep, and the tree, the leaf table, the lights' triangles and the LDS cache split, which no
+ * material or emission decides and which are neither read nor rebuilt; the trees of EXPERIMENTAL builds stay too.
+ * GENERATION AND MOTION. A successful call adds 1 to pt_scene_generation and makes pt_scene_has_motion 0 until the next vertex
+ * update: the previous positions describe a step the viewer has already seen, and a session must not reproject through them again.
+ * The position buffers are kept; only the flag drops. So a frame preceded by a vertex update AND THEN an edit is no motion frame.
+ * ATOMICITY. All arguments are checked on the host before any HIP call (NULL pointers, counts, light indices, texture windows); a
+ * refused call returns -1 with a message that names the function and leaves the scene rendering bit for bit what it rendered. After
+ * the checks nothing can fail but HIP itself. ORDERING: a frame boundary, exactly as for the updates above. */
+int pt_scene_update_materials(pt_scene* scene, const pt_material* materials, int n_materials);
+int pt_scene_update_emission(pt_scene* scene, int n, const int32_t* light_indices, const pt_float4* emission);
 
 /* ---- motion: where a moved surface was, and a history stage that looks there ---------------------------------------------------
  * PREVIOUS POSITIONS. A device-built scene keeps two device arrays of n_positions pt_float4 (32 B per vertex): the current positions
