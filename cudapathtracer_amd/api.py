@@ -156,6 +156,8 @@ def lib():
     L.pt_scene_has_motion.argtypes = [vp]
     L.pt_render_motion.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, vp, vp]
     L.pt_render_motion_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, vp, vp, vp]
+    L.pt_render_motion_chain.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp, vp, vp, vp]
+    L.pt_render_motion_chain_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp, vp, vp, vp, vp]
     L.pt_temporal_accumulate_motion.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(TemporalParams), vp, vp]
     L.pt_temporal_accumulate_motion_device.argtypes = [i32, i32, C.POINTER(Camera), C.POINTER(Camera), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
@@ -174,6 +176,8 @@ def lib():
     L.pt_preview_respond.argtypes = [vp, C.POINTER(RespondParams)]
     L.pt_preview_set_motion.argtypes = [vp, i32]
     L.pt_preview_motion.argtypes = [vp]
+    L.pt_preview_set_motion_chain.argtypes = [vp, i32]
+    L.pt_preview_motion_chain.argtypes = [vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
@@ -714,6 +718,26 @@ class Scene:
         asynchronous on `stream`."""
         _check(lib().pt_render_motion_device(self.h, C.byref(camera), w, h, d_albedo_ptr or None, d_normal_depth_ptr or None, d_motion_ptr or None,
                                              stream or None), "pt_render_motion_device")
+
+    def render_motion_chain(self, camera, w, h, max_links, guides=False, links=False):
+        """pt_render_motion_chain: render_motion along render_aovs_centre's chain of at most max_links mirror and glass links: for a
+        moved surface seen behind static mirrors or panes, (V'.x, V'.y, V'.z, 1) with V' the virtual image of where it was; zeros
+        where a mirror on the way moved. max_links 0 is render_motion. guides=True returns (albedo, normal_depth, motion), the first
+        two being render_aovs_centre(camera, w, h, max_links) bit for bit from the same trace; links=True (with guides) appends the
+        link count [h,w] float32."""
+        mv = np.zeros((h, w, 4), np.float32)
+        alb = np.zeros((h, w, 4), np.float32) if guides else None
+        nd = np.zeros((h, w, 4), np.float32) if guides else None
+        ln = np.zeros((h, w), np.float32) if links else None
+        _check(lib().pt_render_motion_chain(self.h, C.byref(camera), w, h, max_links, _p(alb), _p(nd), _p(ln), _p(mv)), "pt_render_motion_chain")
+        out = ((alb, nd, mv) if guides else (mv,)) + ((ln,) if links else ())
+        return out if len(out) > 1 else mv
+
+    def render_motion_chain_device(self, camera, w, h, max_links, d_albedo_ptr, d_normal_depth_ptr, d_links_ptr, d_motion_ptr, stream=0):
+        """pt_render_motion_chain_device: the same into device buffers (w*h float4 each, w*h floats for the links; the two guide
+        pointers both 0 / None or both set, the links pointer only with them), asynchronous on `stream`."""
+        _check(lib().pt_render_motion_chain_device(self.h, C.byref(camera), w, h, max_links, d_albedo_ptr or None, d_normal_depth_ptr or None,
+                                                   d_links_ptr or None, d_motion_ptr or None, stream or None), "pt_render_motion_chain_device")
 
     @property
     def has_motion(self):
@@ -1660,6 +1684,18 @@ class Preview:
     @property
     def motion(self):
         return lib().pt_preview_motion(self.handle)
+
+    def set_motion_chain(self, on):
+        """pt_preview_set_motion_chain: with 1, a motion frame (set_motion(1)) of a session with a guide chain traces
+        Scene.render_motion_chain along that chain in place of render_motion, so a moved object seen in a mirror or through glass
+        keeps its history too; with centre guides that one pass also writes the frame's guide. Off by default; changing it does not
+        reset the session."""
+        _check(lib().pt_preview_set_motion_chain(self.handle, int(on)), "pt_preview_set_motion_chain")
+        return self
+
+    @property
+    def motion_chain(self):
+        return lib().pt_preview_motion_chain(self.handle)
 
     def set_respond(self, threshold=None, radius=None, power=None):
         """pt_preview_set_respond: the frames that follow and have a history (converging frames excepted) accumulate through

@@ -1771,7 +1771,7 @@ int pt_render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int spp, 
 
 }  // extern "C"
 
-// The feature passes (pt_aov.hip, pt_motion.hip; their launchers and block counts: pt_feature_host.h).
+// The feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip; their launchers and block counts: pt_feature_host.h).
 
 // The traversal spill area of a feature pass of `blocks` workgroups: the passes' own (a render in flight on this scene keeps s->spill),
 // shared among them, since all run on the caller's stream, one after the other. NULL for a scene whose stack never leaves the LDS.
@@ -1787,16 +1787,16 @@ static int feature_spill(pt_scene* s, int blocks, int32_t** spill) {
 // The host form of a feature pass: render(d) into `staging`, where d[i] is output i's slice (NULL for an output the caller left out,
 // whose slice stays reserved), then the copies to the host in order.
 struct HostOut { void* host; size_t bytes; };
-template <class Render>
-static int feature_download(DevBuf& staging, const HostOut (&out)[3], Render render) {
+template <int N, class Render>
+static int feature_download(DevBuf& staging, const HostOut (&out)[N], Render render) {
     size_t total = 0;
     for (const HostOut& o : out) total += o.bytes;
     if (int r = staging.ensure(total)) return r;
-    void* d[3];
+    void* d[N];
     char* at = (char*)staging.p;
-    for (int i = 0; i < 3; at += out[i++].bytes) d[i] = out[i].host ? at : nullptr;
+    for (int i = 0; i < N; at += out[i++].bytes) d[i] = out[i].host ? at : nullptr;
     if (int r = render(d)) return r;
-    for (int i = 0; i < 3; i++)
+    for (int i = 0; i < N; i++)
         if (out[i].host) HIP_OK(hipMemcpy(out[i].host, d[i], out[i].bytes, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1926,6 +1926,50 @@ int pt_render_motion(pt_scene* s, const pt_camera* cam, int w, int h, float* out
     const size_t bytes = (size_t)w * h * sizeof(float4);
     return feature_download(s->motionOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_motion, bytes}},
                             [&](void* const* d) { return render_motion(s, cam, w, h, d[0], d[1], d[2], nullptr); });
+}
+
+// The motion pass through mirrors and glass (pt_motion_chain.hip: motion_chain_kernel). Its own checks, every message under its own
+// name, all before any HIP call (the device check comes last).
+static int check_motion_chain_args(pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, const void* a, const void* nd, const void* l,
+                                   const void* mv) {
+    if (maxLinks < 0 || maxLinks > 16) return fail(-1, "pt_render_motion_chain: max_links %d must be 0..16", maxLinks);
+    if ((a != nullptr) != (nd != nullptr)) return fail(-1, "pt_render_motion_chain: albedo and normal_depth must be both NULL or both set");
+    if (l && !a) return fail(-1, "pt_render_motion_chain: links needs albedo and normal_depth");
+    if (!mv) return fail(-1, "pt_render_motion_chain: null motion output");
+    if (w <= 0 || h <= 0) return fail(-1, "pt_render_motion_chain: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > 0x7fffffffll) return fail(-1, "pt_render_motion_chain: image of %d x %d pixels is too large", w, h);
+    if (!cam) return fail(-1, "pt_render_motion_chain: null camera");
+    if (cam->w != w || cam->h != h) return fail(-1, "pt_render_motion_chain: the camera is %d x %d, the image %d x %d", cam->w, cam->h, w, h);
+    if (!s) return fail(-1, "pt_render_motion_chain: null scene");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->device)
+        return fail(-1, "pt_render_motion_chain: scene lives on HIP device %d but the current device is %d", s->device, dev);
+    return 0;
+}
+
+static int render_motion_chain(pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, void* dA, void* dN, void* dL, void* dM,
+                               hipStream_t stream) {
+    const int blocks = feature_blocks(feature_tiles(w, h).nTiles, s->numCU, kMotionChainWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    const bool moving = s->hasMotion && s->deviceLeaf >= 0;
+    HIP_OK(launch_motion_chain(s->ds, s->kTris.p, s->posCur.p, moving ? s->posPrev.p : nullptr, s->nPositions, cam_to_kernel(*cam), w, h, maxLinks,
+                               blocks, (float4*)dA, (float4*)dN, (float*)dL, (float4*)dM, spill, stream));
+    return 0;
+}
+
+int pt_render_motion_chain_device(pt_scene* s, const pt_camera* cam, int w, int h, int max_links, void* d_albedo, void* d_normal_depth,
+                                  void* d_links, void* d_motion, void* stream) {
+    if (int r = check_motion_chain_args(s, cam, w, h, max_links, d_albedo, d_normal_depth, d_links, d_motion)) return r;
+    return render_motion_chain(s, cam, w, h, max_links, d_albedo, d_normal_depth, d_links, d_motion, (hipStream_t)stream);
+}
+
+int pt_render_motion_chain(pt_scene* s, const pt_camera* cam, int w, int h, int max_links, float* out_albedo, float* out_normal_depth,
+                           float* out_links, float* out_motion) {
+    if (int r = check_motion_chain_args(s, cam, w, h, max_links, out_albedo, out_normal_depth, out_links, out_motion)) return r;
+    const size_t bytes = (size_t)w * h * sizeof(float4), lbytes = (size_t)w * h * sizeof(float);
+    return feature_download(s->motionOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_motion, bytes}, {out_links, lbytes}},
+                            [&](void* const* d) { return render_motion_chain(s, cam, w, h, max_links, d[0], d[1], d[3], d[2], nullptr); });
 }
 
 int pt_has_experimental(void) {

@@ -1,16 +1,19 @@
 // pt_feature.h — what the feature kernels are assembled from (pt_aov.hip: aov_kernel, aov_chain_kernel, aov_centre_kernel,
-// aov_centre_chain_kernel; pt_motion.hip: motion_kernel). Every one of them is one wave per 8x8 tile (lane = ly*8+lx), four waves per
-// workgroup, persistent over the tiles, with the non-counting trace_closest (max_t 999999, as pt_probe_trace_closest) on an LDS stack
-// that overflows into the scene's spill area:
+// aov_centre_chain_kernel; pt_motion.hip: motion_kernel; pt_motion_chain.hip: motion_chain_kernel). Every one of them is one wave per
+// 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the tiles, with the non-counting trace_closest (max_t 999999,
+// as pt_probe_trace_closest) on an LDS stack that overflows into the scene's spill area:
 //   FeatureWave, tile_pixel   the wave's traversal state and the pixel of a lane in a tile
 //   first_hit_record          a resolved hit's (albedo, 1) and (normal, t)
-//   follow_chain              a ray followed through mirrors and glass to the first non-specular surface
+//   follow_chain              a ray followed through mirrors and glass to the first non-specular surface; a kernel's ChainHook
+//                             sees every surface and link on the way
+//   MotionSrc                 what the motion kernels read beside the packed scene
 //   FeatureSum                the sums over a pixel's rays and their division
 // The __shared__ arrays stay declared in each kernel, so each kernel's LDS size is its own. pt_feature_host.h has the host's side.
 #pragma once
 #include "pt_path.h"
 #include "pt_centre_ray.h"
 #include "pt_feature_host.h"
+#include "../../include/pt_api.h"
 
 namespace pt {
 
@@ -53,6 +56,17 @@ PT_DEV void first_hit_record(const DeviceScene& S, const HitInfo& hi, float t, f
     on = make_float4(hi.normal.x, hi.normal.y, hi.normal.z, t);
 }
 
+// What a kernel does beside follow_chain's record at each step of its lane's chain: it passes a type with these two members. This
+// one does nothing (aov_chain_kernel, aov_centre_chain_kernel).
+struct ChainHook {
+    // Hit i of the chain, resolved, at summed path length depth. With i == 0 or !spec its record is the chain's result unless a later
+    // call says so too; with spec && i < maxLinks the chain goes on through it. (Plain arguments: with the two conditions formed at
+    // the call the chain kernels of pt_aov.hip compile to other code, though this body is empty.)
+    PT_DEV void surface(int i, const Hit& hit, const HitInfo& hi, bool spec, float depth) {}
+    // The link through the surface just seen reflected (a mirror, or total internal reflection) or refracted, at normal n.
+    PT_DEV void link(bool reflect, const V3& n) {}
+};
+
 // The ray (o, d) of a `live` lane followed through mirrors (type 6) and smooth dielectrics (type 2), deterministically, to the first
 // non-specular surface or for maxLinks links. Returns the number of links followed, -1 if the ray hit nothing at all, and leaves in
 // rec[j * 64], j = 0..6 (the lane's words of an LDS array float[7][64]) that surface's albedo and normal and the summed path length.
@@ -62,7 +76,10 @@ PT_DEV void first_hit_record(const DeviceScene& S, const HitInfo& hi, float t, f
 // first hit, overwritten where the chain ends on a surface and simply stays when it does not (a miss after the first hit, or the cap),
 // and the caller reads it once afterwards, so it need not be live across the traversals (7 VGPRs: 86 -> 6 waves per SIMD).
 // The direction arithmetic is written out operation by operation (no dot(), normalize(), fmaf): tests/aov_chain_ref.py restates it.
-PT_DEV int follow_chain(const DeviceScene& S, const SceneCache& C, Stack<kStackLds>& st, Ctr& c, V3 o, V3 d, bool live, int maxLinks, float* rec) {
+// hook: the kernel's ChainHook; whatever it keeps is live across the traversals too.
+template <class Hook = ChainHook>
+PT_DEV int follow_chain(const DeviceScene& S, const SceneCache& C, Stack<kStackLds>& st, Ctr& c, V3 o, V3 d, bool live, int maxLinks, float* rec,
+                        Hook&& hook = Hook()) {
     float depth = 0.0f;
     int links = -1;
     for (int i = 0; i <= maxLinks; i++) {
@@ -76,6 +93,7 @@ PT_DEV int follow_chain(const DeviceScene& S, const SceneCache& C, Stack<kStackL
                 const PMat& m = S.mats[hi.material];
                 const bool spec = (m.flags & kMatSpecular) && (m.type == 6 || m.type == 2);
                 depth = i == 0 ? hit.t : depth + hit.t;
+                hook.surface(i, hit, hi, spec, depth);
                 if (i == 0 || !spec) {
                     V3 a; float trans;
                     material_inputs(m, S.textures, hi.uvx, hi.uvy, true, a, trans);
@@ -102,6 +120,7 @@ PT_DEV int follow_chain(const DeviceScene& S, const SceneCache& C, Stack<kStackL
                         const float s2 = 2.0f * dn;
                         r = v3(d.x - s2 * n.x, d.y - s2 * n.y, d.z - s2 * n.z);
                     }
+                    hook.link(reflect, n);
                     const float len = __builtin_sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
                     d = v3(r.x / len, r.y / len, r.z / len);
                     const V3 off = v3(n.x * kEps, n.y * kEps, n.z * kEps);
@@ -114,6 +133,15 @@ PT_DEV int follow_chain(const DeviceScene& S, const SceneCache& C, Stack<kStackL
     }
     return links;
 }
+
+// What the motion passes read beside the packed scene, passed next to DeviceScene (which every megakernel takes and which stays as it
+// is). prev NULL: the scene has no previous positions, every pixel is static.
+struct MotionSrc {
+    const pt_triangle* tris;    // original order: Hit::tri indexes it
+    const float4* cur;          // nPos positions as of the last update (or creation)
+    const float4* prev;         // ... and before it
+    int nPos;
+};
 
 // The sums over the aov_spp rays of a pixel, in k order, and their division. The first contribution is stored, not added to 0, so
 // that a -0 component survives (aov_spp = 1 is the hit itself: dividing by n = 1 changes no bit). Coverage is n / aov_spp.

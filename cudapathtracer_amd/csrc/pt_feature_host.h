@@ -1,5 +1,5 @@
-// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip): the tiling and block count every one of
-// them is launched with, each kernel's waves per SIMD, and the launchers pt_api.hip calls. The kernels' shared pieces are in
+// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip): the tiling and block
+// count every one of them is launched with, each kernel's waves per SIMD, and the launchers pt_api.hip calls. The kernels' shared pieces are in
 // pt_feature.h.
 #pragma once
 #include <algorithm>
@@ -21,6 +21,8 @@ constexpr int kAovChainWavesPerSimd = 6;     // aov_chain_kernel: 80 VGPRs, 23 K
                                              // aov_centre_chain_kernel (69 VGPRs, 23 KB): 7 workgroups would need 161 KB
 constexpr int kAovCentreWavesPerSimd = 8;    // aov_centre_kernel: without the seeding 63 VGPRs, 8 x 16 KB of LDS
 constexpr int kMotionWavesPerSimd = 8;       // motion_kernel: 63 VGPRs, 8 x 16 KB of LDS, as the centre pass
+constexpr int kMotionChainWavesPerSimd = 5;  // motion_chain_kernel: 93 VGPRs (the unfolding matrix stays in registers), 26 KB of LDS: 6 workgroups
+                                             // would fit the LDS, 5 waves fit the registers
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
 
 // spill (every launcher): blocks * 4 waves x S.stackSpill entries x 64 lanes, or NULL for a scene whose stack never leaves the LDS.
@@ -37,5 +39,9 @@ hipError_t launch_probe_centre(const CamK& cam, int n, const int* xy, float* out
 // pt_motion.hip
 hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w, int h,
                          int blocks, float4* albedo, float4* normalDepth, float4* motion, int32_t* spill, hipStream_t stream);
+// pt_motion_chain.hip
+hipError_t launch_motion_chain(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w,
+                               int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, float4* motion, int32_t* spill,
+                               hipStream_t stream);
 
 }  // namespace pt

@@ -7,19 +7,12 @@
 // previous positions: three int32 loads, then six float4 loads, all dependent on the hit, none live across the traversal. The previous
 // point is the barycentric sum of the previous positions with resolve_hit's weights, every operation rounded once (no fma).
 // With albedo / normalDepth set the kernel also writes first_hit_record of the same hit: aov_centre_kernel's output.
+// MotionSrc, what the pass reads beside the packed scene, is in pt_feature.h: pt_motion_chain.hip's pass through mirrors and glass
+// reads the same.
 #include "pt_feature.h"
 #include "../../include/pt_api.h"
 
 namespace pt {
-
-// What the pass reads beside the packed scene, passed next to DeviceScene (which every megakernel takes and which stays as it is).
-// prev NULL: the scene has no previous positions, every pixel is static.
-struct MotionSrc {
-    const pt_triangle* tris;    // original order: Hit::tri indexes it
-    const float4* cur;          // nPos positions as of the last update (or creation)
-    const float4* prev;         // ... and before it
-    int nPos;
-};
 
 __global__ void __launch_bounds__(256) motion_kernel(DeviceScene S, MotionSrc M, CamK cam, int w, int h, int tilesX, int nTiles,
                                                      float4* __restrict__ albedo, float4* __restrict__ normalDepth, float4* __restrict__ motion,

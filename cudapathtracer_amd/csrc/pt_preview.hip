@@ -20,9 +20,10 @@
 //   guides    the display-size feature pass into albedo and the other half of the guide pair: pt_render_aovs_device; with a guide
 //             chain pt_render_aovs_chain_device; with centre guides pt_render_aovs_centre_device, and then no pass at all when the
 //             camera rests and the last guide is still in place (it has no seed: nothing in it could have changed). A motion frame
-//             adds pt_render_motion_device, fused with the guide where that is the centre first-hit pass. Scaled: the low-res guide
-//             is one more feature pass, before the display pass; with centre guides pt_guide_subsample_device of the display guide,
-//             after it, also when that guide is reused.
+//             adds pt_render_motion_device, fused with the guide where that is the centre first-hit pass; with
+//             pt_preview_set_motion_chain and a guide chain it is pt_render_motion_chain_device, fused with any centre guide.
+//             Scaled: the low-res guide is one more feature pass, before the display pass; with centre guides
+//             pt_guide_subsample_device of the display guide, after it, also when that guide is reused.
 //   accumulate  temporal 0: nothing. Else one call (preview_accumulate): pt_temporal_accumulate_motion_device on S, Q and albedo;
 //             scaled: pt_upsample_device first, then pt_temporal_accumulate_cur_motion_device on its output. Both take the motion
 //             buffer on a motion frame and NULL otherwise: the _motion forms with a NULL buffer are the base forms (include/pt_api.h),
@@ -145,6 +146,7 @@ struct pt_preview {
     bool sceneChanged;                    // pt_preview_scene_changed since the last good frame: the next frame counts as a moved camera
     int motion;                           // 1: MOTION FRAMES reproject moved surfaces (pt_preview_set_motion)
     char* M;                              // w*h float4: pt_render_motion's output (its own allocation, made when motion is first turned on)
+    int motionChain;                      // 1: a motion frame of a session with a guide chain runs pt_render_motion_chain_device (MOTION CHAIN)
     bool respond;                         // frames with a history accumulate through pt_temporal_accumulate_respond_device
     pt_respond_params R;
     char* respondWs;                      // its workspace (its own allocation, made when respond is first turned on)
@@ -330,6 +332,15 @@ int pt_preview_set_motion(pt_preview* p, int on) {
 
 int pt_preview_motion(pt_preview* p) { return p ? p->motion : postfx_fail(-1, "pt_preview_motion: null session"); }
 
+int pt_preview_set_motion_chain(pt_preview* p, int on) {
+    if (on != 0 && on != 1) return postfx_fail(-1, "pt_preview_set_motion_chain: on %d must be 0 or 1", on);
+    if (!p) return postfx_fail(-1, "pt_preview_set_motion_chain: null session");
+    p->motionChain = on;                  // (no reset, no buffer: M is pt_preview_set_motion's, without which there is no motion frame)
+    return 0;
+}
+
+int pt_preview_motion_chain(pt_preview* p) { return p ? p->motionChain : postfx_fail(-1, "pt_preview_motion_chain: null session"); }
+
 int pt_preview_set_respond(pt_preview* p, const pt_respond_params* params) {
     if (!p) return postfx_fail(-1, "pt_preview_set_respond: null session");
     if (!params) { p->respond = false; return 0; }
@@ -404,18 +415,22 @@ static int preview_aovs(pt_preview* p, FramePlan& f, const pt_camera* cam, int w
     return pt_render_aovs_device(p->scene, cam, w, h, p->P.aov_spp, seed, dA, dN, p->stream);
 }
 
-// The display-size guide of a frame that traces one and, on a motion frame, the motion buffer: one fused pass where the guide is the
-// centre first-hit pass (the motion pass writes that guide from its own trace), else the guide pass and then the motion pass.
-static int preview_display_guide(pt_preview* p, FramePlan& f, const pt_camera* cam, uint64_t seed) {
-    const int w = p->w, h = p->h;
-    if (f.motion && p->guideCentre && p->guideChain == 0) {
-        f.passes++;
-        return pt_render_motion_device(p->scene, cam, w, h, p->A, p->N[f.gn], p->M, p->stream);
-    }
-    if (int r = preview_aovs(p, f, cam, w, h, seed, p->A, p->N[f.gn])) return r;
-    if (!f.motion) return 0;
+// The motion pass of a motion frame, with the display guide outputs (dA, dN) or without (NULL, NULL): pt_render_motion_device, or
+// with the motion-chain switch on and a guide chain pt_render_motion_chain_device along that chain.
+static int preview_motion(pt_preview* p, FramePlan& f, const pt_camera* cam, void* dA, void* dN) {
     f.passes++;
-    return pt_render_motion_device(p->scene, cam, w, h, nullptr, nullptr, p->M, p->stream);
+    if (p->motionChain && p->guideChain > 0)
+        return pt_render_motion_chain_device(p->scene, cam, p->w, p->h, p->guideChain, dA, dN, nullptr, p->M, p->stream);
+    return pt_render_motion_device(p->scene, cam, p->w, p->h, dA, dN, p->M, p->stream);
+}
+
+// The display-size guide of a frame that traces one and, on a motion frame, the motion buffer: one fused pass where a motion pass
+// writes the session's guide from its own trace (centre guides: the first-hit guide from pt_render_motion_device, a chain guide from
+// pt_render_motion_chain_device), else the guide pass and then the motion pass.
+static int preview_display_guide(pt_preview* p, FramePlan& f, const pt_camera* cam, uint64_t seed) {
+    if (f.motion && p->guideCentre && (p->guideChain == 0 || p->motionChain)) return preview_motion(p, f, cam, p->A, p->N[f.gn]);
+    if (int r = preview_aovs(p, f, cam, p->w, p->h, seed, p->A, p->N[f.gn])) return r;
+    return f.motion ? preview_motion(p, f, cam, nullptr, nullptr) : 0;
 }
 
 // The one accumulate call of a temporal frame, into H[nxt] and L[nxt]. cur: the upsampled (e, V) frame of a scaled frame, NULL for

@@ -737,7 +737,16 @@ int pt_resolve(int w, int h, const float* rgba, int spp, const int32_t* tile_spp
  *     with M;
  * so it equals that chain of host calls bit for bit. aov_ms includes the motion pass and pt_preview_guide_passes counts it as one
  * pass. Every other frame is unchanged: a generation that jumped by more than one, keep_history 0, an unannounced change, a
- * converging frame. The failed-frame rule holds. Motion through mirrors and glass is out of scope (see pt_render_motion). */
+ * converging frame. The failed-frame rule holds. pt_render_motion is first hit only; MOTION CHAIN follows mirrors and glass.
+ *
+ * MOTION CHAIN. pt_preview_set_motion_chain(p, on): 0 (the default) is the frames above, bit for bit; -1 on a NULL session or a value
+ * other than 0 or 1. Changing the value does not reset the session and allocates nothing. With 1, a MOTION FRAME (as defined above:
+ * it needs pt_preview_set_motion(p, 1) as before) of a session whose guide chain is > 0 runs
+ * pt_render_motion_chain_device(display camera, max_links = the guide chain) where it ran pt_render_motion_device: after the
+ * display-size guide pass with the guide outputs NULL; with centre guides ONE pt_render_motion_chain_device(display camera,
+ * max_links, A, N, NULL, M) replaces the display-size guide pass (its guide outputs are pt_render_aovs_centre_device's, bit for
+ * bit). A session with guide chain 0 is unaffected by the switch. aov_ms, pt_preview_guide_passes (the fused pass counts as one),
+ * the failed-frame rule, converging frames and respond compose as for motion frames above. */
 typedef struct pt_preview pt_preview;
 typedef struct pt_preview_params {
     int32_t spp, batches, max_depth, integrator, use_mis, aov_spp;
@@ -766,6 +775,8 @@ int  pt_preview_set_guide_centre(pt_preview* p, int on);                   /* 0 
 int  pt_preview_guide_centre(pt_preview* p);                               /* the current value; -1 on a NULL session */
 int  pt_preview_set_motion(pt_preview* p, int on);                         /* 0 or 1: motion frames, see MOTION */
 int  pt_preview_motion(pt_preview* p);                                     /* the current value; -1 on a NULL session */
+int  pt_preview_set_motion_chain(pt_preview* p, int on);                   /* 0 or 1: motion frames follow the guide chain, see MOTION CHAIN */
+int  pt_preview_motion_chain(pt_preview* p);                               /* the current value; -1 on a NULL session */
 int  pt_preview_guide_passes(pt_preview* p);                               /* feature-pass launches of the good frames; -1 on NULL */
 int  pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, float* hist_len);
 const void* pt_preview_device_rgba8(pt_preview* p);                        /* w*h*4 bytes */
@@ -1038,13 +1049,46 @@ int pt_scene_update_emission(pt_scene* scene, int n, const int32_t* light_indice
  * out_albedo and out_normal_depth must be both NULL or both set (-1 otherwise); when set they are bit-identical, in all eight
  * floats, to pt_render_aovs_centre(max_links = 0): one trace serves the guide and the motion. The pass is FIRST HIT ONLY: a moved
  * object seen through a mirror or through glass reports the static mirror or pane in front of it, and so takes the path without
- * motion. Like the other feature passes this one touches no RNG state, accumulator or counter of the scene. Arguments are checked
+ * motion; pt_render_motion_chain (below) is the pass that follows the ray to the object. Like the other feature passes this one touches no RNG state, accumulator or counter of the scene. Arguments are checked
  * before any HIP call: those of pt_render_aovs_centre, the guide outputs both or neither, and out_motion not NULL. */
 int pt_scene_has_motion(pt_scene* scene);
 int pt_render_motion(pt_scene* scene, const pt_camera* camera, int w, int h, float* out_albedo /* NULL ok */,
                      float* out_normal_depth /* NULL ok */, float* out_motion);                                   /* host, blocking */
 int pt_render_motion_device(pt_scene* scene, const pt_camera* camera, int w, int h, void* d_albedo /* NULL ok */,
                             void* d_normal_depth /* NULL ok */, void* d_motion, void* stream);                    /* async */
+
+/* pt_render_motion_chain: motion through mirrors and glass, for sessions whose guides follow them (pt_render_aovs_centre with
+ * max_links > 0). The ray is pt_render_aovs_centre's centre ray and the chain pt_render_aovs_chain's: its link rule, direction
+ * arithmetic and fallback, max_links 0..16. out_albedo, out_normal_depth and out_links, when set, are bit-identical to
+ * pt_render_aovs_centre(max_links) in all eight floats and in links; albedo and normal_depth must be both set or both NULL, and
+ * out_links needs them set (-1 otherwise). max_links = 0 is pt_render_motion bit for bit in every output.
+ * out_motion, w*h float4, in f32, every operation rounded once, left to right, nothing fused:
+ *   no hit, or the scene has no previous positions: (0, 0, 0, 0).
+ *   A ray whose result is its FIRST HIT (a non-specular first hit; the fallback where the chain leaves the scene or reaches the
+ *     cap, links = 0): pt_render_motion's pixel for that hit, bit for bit.
+ *   A ray whose chain ended on a non-specular surface after L >= 1 links:
+ *     (0, 0, 0, 0) if the triangle of ANY of the L specular hits on the way MOVED (pt_render_motion's nine-float test on that
+ *       triangle): a moving mirror changes the whole reflection, and the pixel stays on the path without motion;
+ *     (0, 0, 0, 0) if the final triangle is STATIC by the same test;
+ *     otherwise, with P' pt_render_motion's barycentric sum of the final triangle's previous positions at the final hit's u, v and
+ *       bz = 1 - u - v, and P the final hit's point as pt_probe_trace_closest reports it: D.c = P'.c - P.c.
+ *       UNFOLDING. A 3x3 M starts as the identity. At each link that REFLECTED (a mirror, or a dielectric's total internal
+ *       reflection), in link order, with n the hit's normal at that link as pt_probe_trace_closest reports it, every row r becomes
+ *         s = 2 * (M[r].x n.x + M[r].y n.y + M[r].z n.z);  M[r].c = M[r].c - s * n.c
+ *       and a link that REFRACTED leaves M unchanged (a deliberate simplification: a pane shifts the image, it does not mirror it).
+ *       Du.r = M[r].x D.x + M[r].y D.y + M[r].z D.z: the displacement reflected through the last mirror first.
+ *       V.c = o.c + d.c * depth, (o, d) the centre ray and depth the chain's summed path length (the guide's w): for planar
+ *       mirrors the virtual image of P. The pixel is (V.x + Du.x, V.y + Du.y, V.z + Du.z, 1): the virtual image of P'.
+ * pt_temporal_accumulate[_cur]_motion and pt_temporal_accumulate_respond take this buffer as they take pt_render_motion's: they
+ * reproject any point whose w is 1. Still out of scope: moving mirrors (zero, above), the image shift of a refraction, a
+ * previous-normal transform, pt_multi_* replicas. Like every feature pass this one touches no RNG state, accumulator or counter
+ * of the scene; it needs a device-built scene exactly where pt_render_motion does (any other scene is static). All arguments are
+ * checked before any HIP call, -1 with a message that names pt_render_motion_chain: max_links, the guide outputs, out_links,
+ * out_motion, the size, the camera and its size, then the scene. */
+int pt_render_motion_chain(pt_scene* scene, const pt_camera* camera, int w, int h, int max_links, float* out_albedo /* NULL ok */,
+                           float* out_normal_depth /* NULL ok */, float* out_links /* NULL ok */, float* out_motion);   /* host, blocking */
+int pt_render_motion_chain_device(pt_scene* scene, const pt_camera* camera, int w, int h, int max_links, void* d_albedo /* NULL ok */,
+                                  void* d_normal_depth /* NULL ok */, void* d_links /* NULL ok */, void* d_motion, void* stream); /* async */
 
 /* pt_temporal_accumulate / pt_temporal_accumulate_cur with a motion buffer (w*h float4, as pt_render_motion writes it for the
  * current camera). The contract is the base function's except in step 3: a pixel p with motion_p.w == 1.0f takes P = motion_p.xyz
