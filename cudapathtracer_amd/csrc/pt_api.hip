@@ -152,6 +152,16 @@ static int scene_onchip_wg(const pt_scene* s) {
     return 0;
 }
 static bool scene_onchip(const pt_scene* s) { return scene_onchip_wg(s) > 0; }
+// Does a launch of `tiles` tiles get megakernel_hbm — six waves per SIMD, eight with the SIMPLE bounce — and not the general 4-wave
+// kernel? A scene in HBM does, with enough tiles to fill those waves: with fewer (a 1/8 shard of a 1080p frame is 4050 tiles for 6144
+// slots) the extra slots stay empty and the 4-wave kernel's faster waves win (measured: 1/8 shard 176 vs 185 ms, 1/4 shard equal, 1/2
+// shard 602 vs 518 ms on the 263 k-triangle scene). The SIMPLE kernel's eight waves pay from ~3/4 of its 8192 slots on — a 1/4 share of
+// a 1080p frame: 201 vs 269 ms — the generic kernel's six from 5/4 of its 6144 (profiles/r02_sched_shards.log).
+static bool hbm_kernel_pays(const pt_scene* s, bool simple, long long tiles) {
+    if (scene_onchip(s) || (s->deferShadow && !s->armless) || !s->wavesHbmOk) return false;
+    const long long slots = (long long)s->numCU * 4 * (simple ? kWavesHbmSimple : kWavesHbm);
+    return s->wavesHbmForce || tiles * 4 >= slots * (simple ? 3 : 5);
+}
 
 extern "C" {
 
@@ -1212,21 +1222,22 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     if (list && (count || s->variant != 0 || t.first != 0 || t.stride != 1 || live < 0 || live > t.count)) return fail(-1, "render_tiles: bad tile list");
     // the reference keys the stream by the camera's image size (y*w+x with the launch's w, deviceCode.cu:59)
     if (int r = s->rng.ensure((size_t)t.count * 384 * sizeof(uint32_t))) return r;
-    // Which kernel (pt_kernels.hip): the LDS-resident instantiation, or — for a scene in HBM — the 6-waves-per-SIMD
-    // one with its shorter LDS stack (so the spill area is laid out for THAT stack length).
+    // continueStreams: a later chunk of a progressive render keeps the per-pixel XORWOW states the
+    // previous chunk stored (the reference reloads / stores them around every sample, deviceCode.cu:294, 541)
+    if (!continueStreams) HIP_OK(launch_rng_init((const uint32_t*)s->jump.p, seed, w, h, t, (uint32_t*)s->rng.p, stream));
+    if (fused) fused->seeded = !continueStreams;
+    if (s->variant == 1) return render_tiles_wavefront(s, cam, w, h, spp, maxDepth, integrator, useMIS, t, d_tiles, d_pixcnt, count, stream);
+    // First the selector fields of the launch, then the kernel they choose (pt_kernels.hip: megakernel_choose), then everything that is
+    // sized for THAT kernel: its LDS stack length lays out the spill area, its launch bounds give the workgroup and the grid.
     const bool deferred = s->deferShadow && !s->armless;
     const bool onchip = scene_onchip(s) && !deferred;       // (the DEFER A/B instantiation exists for the general 4-wave kernel only)
-    // ... and only with enough tiles to fill its 6 waves per SIMD: with fewer (a 1/8 shard of a 1080p frame is 4050
-    // tiles for 6144 slots) the extra slots stay empty and the 4-wave kernel's faster waves win (measured: 1/8 shard
-    // 176 vs 185 ms, 1/4 shard equal, 1/2 shard 602 vs 518 ms on the 263 k-triangle scene).
-    // ... of which the SIMPLE instantiation (diffuse-only scenes; timed launches with the resumable traversal) runs at 8 waves per SIMD
-    const bool simpleHbm = !onchip && !deferred && s->wavesHbmOk && s->simpleOk && s->simpleWanted && s->refill && !s->cull && !s->armless && !count;
-    const int wavesHbm = simpleHbm ? kWavesHbmSimple : kWavesHbm;
-    // (the SIMPLE kernel's eight waves per SIMD pay from ~3/4 of its 8192 slots on — a 1/4 share of a 1080p frame: 201 vs 269 ms on
-    //  the 263 k-triangle scene — the generic kernel's six from 5/4 of its 6144, profiles/r02_sched_shards.log)
-    const long long slotsHbm = (long long)s->numCU * 4 * wavesHbm;
-    const bool hbm = !onchip && !deferred && s->wavesHbmOk &&
-                     (s->wavesHbmForce || (simpleHbm ? (long long)live * 4 >= slotsHbm * 3 : (long long)live * 4 >= slotsHbm * 5));
+    // the SIMPLE bounce for a scene in HBM: diffuse-only scenes, timed launches with the resumable traversal
+    const bool simpleTimed = s->simpleOk && s->simpleWanted && s->refill && !s->cull && !s->armless;
+    const bool simpleHbm = !onchip && !deferred && s->wavesHbmOk && simpleTimed && !count;
+    const bool hbm = hbm_kernel_pays(s, simpleHbm, live);
+    KParams P;
+    P.onchip = onchip ? 1 : 0;
+    P.hbm = hbm ? 1 : 0;
     bool wide = false, compact = false;
 #ifdef PT_EXPERIMENTAL
     if (hbm && simpleHbm && s->wideWanted) {
@@ -1238,17 +1249,27 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
         compact = s->compactOk;
     }
 #endif
-    const int spillEntries = hbm ? std::max(0, (wide ? std::max(s->wideStackNeed, s->stackNeed) : s->stackNeed) - (simpleHbm ? kStackLdsHbm : kStackLdsHbmGen)) : s->ds.stackSpill;
-    const int wgWaves = hbm ? (simpleHbm ? kWgWavesHbmSimple : kWgWavesHbm) : (onchip ? scene_onchip_wg(s) : 4);
+    P.wide = wide ? 1 : 0; P.compact = compact ? 1 : 0;
+    P.xcdBands = s->xcdBands ? 1 : 0;
+    P.cull = (s->cull && hbm) ? 1 : 0;
+    P.refill = (s->refill && !deferred && !P.cull && !s->armless && (!onchip || s->refill == 2)) ? 1 : 0;   // 2: also the LDS-resident kernel (A/B)
+    P.flat = 0;                                             // 1: FLAT with 64-bit masks, 2: with 128-bit masks
+    if (onchip && s->flatOk && s->flatWanted && !deferred && !P.refill) {
+        P.flat = (s->nInternal <= 64 && s->nTrisPacked <= 64) ? 1 : 2;     // 65..128: +17-20 % over the stack walk with the leaf-box form (profiles/r02_flat_crossover.jsonl)
+    }
+    // the instantiations that have the SIMPLE bounce: FLAT, the production kernel for scenes in HBM and its 4-wave form (small shares)
+    P.simple = ((P.flat && s->simpleOk && s->simpleWanted) || simpleHbm) ? 1 : 0;
+    if (P.flat == 1 && s->noLeafTris && !s->armless && s->flat2Wanted && integrator == PT_UNIDIRECTIONAL && !count && useMIS) P.flat = 3;   // ... and the pair form of FLAT
+    // the LEAN generic bounce exists for the three timed kernels generic scenes run: the pair form of FLAT, the kernel for scenes in HBM
+    // and its 4-wave form (both REFILL)
+    P.lean = (s->leanOk && s->leanWanted && !s->armless && !P.simple && !count && !P.cull && (P.flat == 3 || (!onchip && P.refill))) ? 1 : 0;
+    const MkRow* row = megakernel_choose(integrator, count, !deferred, P, false);
+    if (!row) return fail(-1, "render_tiles: no megakernel is built for this launch");
+    const int spillEntries = hbm ? std::max(0, (wide ? std::max(s->wideStackNeed, s->stackNeed) : s->stackNeed) - row->f.stackEntries) : s->ds.stackSpill;
+    const int wgWaves = row->f.wgWaves ? row->f.wgWaves : (onchip ? scene_onchip_wg(s) : 4);
     int blocks = megakernel_blocks(t.count, wgWaves);
     if (spillEntries > 0)
         if (int r = s->spill.ensure((size_t)blocks * wgWaves * spillEntries * 64 * sizeof(int32_t))) return r;
-    // continueStreams: a later chunk of a progressive render keeps the per-pixel XORWOW states the
-    // previous chunk stored (the reference reloads / stores them around every sample, deviceCode.cu:294, 541)
-    if (!continueStreams) HIP_OK(launch_rng_init((const uint32_t*)s->jump.p, seed, w, h, t, (uint32_t*)s->rng.p, stream));
-    if (fused) fused->seeded = !continueStreams;
-    if (s->variant == 1) return render_tiles_wavefront(s, cam, w, h, spp, maxDepth, integrator, useMIS, t, d_tiles, d_pixcnt, count, stream);
-    KParams P;
     P.S = s->ds;
     P.cam = cam_to_kernel(*cam);
     P.w = w; P.h = h; P.spp = spp; P.maxDepth = maxDepth; P.useMIS = useMIS;
@@ -1263,45 +1284,26 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.wgWaves = wgWaves;
     if (hbm && s->cacheTris == 0) P.cacheNodes = std::min(s->nInternal, (simpleHbm ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64);     // its workgroups share a larger copy of the top of the tree
     P.gnodeFrom = P.cacheNodes;
-    if (count && !onchip && !deferred && s->wavesHbmOk) {
+    if (count && !onchip && !deferred && s->wavesHbmOk && s->cacheTris == 0) {
         // a counting launch stands in for the timed launch of the same tiles (bench.py): count a node fetch as "global" against THAT
         // instantiation's LDS copy of the tree top — the SIMPLE production kernel holds 768 nodes, this counting kernel 704 (or 192)
-        const bool simpleTimed = s->simpleOk && s->simpleWanted && s->refill && !s->cull && !s->armless;
-        const long long slotsTimed = (long long)s->numCU * 4 * (simpleTimed ? kWavesHbmSimple : kWavesHbm);
-        const bool hbmTimed = s->wavesHbmForce || (simpleTimed ? (long long)t.count * 4 >= slotsTimed * 3 : (long long)t.count * 4 >= slotsTimed * 5);
-        if (s->cacheTris == 0) P.gnodeFrom = hbmTimed ? std::min(s->nInternal, (simpleTimed ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64) : s->cacheNodes;
+        P.gnodeFrom = hbm_kernel_pays(s, simpleTimed, t.count) ? std::min(s->nInternal, (simpleTimed ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64) : s->cacheNodes;
     }
-    P.wide = wide ? 1 : 0; P.wnodes = wide ? (const WNode*)s->wnodes.p : nullptr;
+    P.wnodes = wide ? (const WNode*)s->wnodes.p : nullptr;
     if (wide) P.cacheNodes = 2 * std::min(s->nWide, kCacheBytesHbmSimple / 128);            // wide nodes, counted in 64-byte halves
-    P.compact = compact ? 1 : 0;
     P.qnodes = compact ? (const QNode*)s->qnodes.p : nullptr; P.leafBox = compact ? s->leafBox.p : nullptr; P.mids = compact ? (const int32_t*)s->mids.p : nullptr;
     if (compact) P.cacheNodes = std::min(s->nInternal & ~1, kCacheBytesHbmSimple / 32) / 2;     // compact nodes, two per 64-byte unit
-    P.xcdBands = s->xcdBands ? 1 : 0;
     P.S.stackSpill = spillEntries;
-    P.cull = (s->cull && hbm) ? 1 : 0;
-    P.refill = (s->refill && !deferred && !P.cull && !s->armless && (!onchip || s->refill == 2)) ? 1 : 0;   // 2: also the LDS-resident kernel (A/B)
     P.refillKeep = (hbm || s->refillKeepSet) ? s->refillKeep : kRefillKeepSmall;      // re-swept on the round's kernels: 6 for the 8-wave kernel, 10 for the 4-wave one (1/8 shares +5.5 % / +6 %, profiles/r03_shards_hbm_final.log)
     P.spec = s->spec;
     P.nodeKeep = s->nodeKeep; P.triKeep = s->triKeep;
-    P.flat = 0;                                             // 1: FLAT with 64-bit masks, 2: with 128-bit masks
-    if (onchip && s->flatOk && s->flatWanted && !deferred && !P.refill) {
-        P.flat = (s->nInternal <= 64 && s->nTrisPacked <= 64) ? 1 : 2;     // 65..128: +17-20 % over the stack walk with the leaf-box form (profiles/r02_flat_crossover.jsonl)
-    }
-    // the instantiations that have the SIMPLE bounce: FLAT, the production kernel for scenes in HBM and its 4-wave form (small shares)
-    P.simple = ((P.flat && s->simpleOk && s->simpleWanted) || simpleHbm) ? 1 : 0;
-    if (P.flat == 1 && s->noLeafTris && !s->armless && s->flat2Wanted && integrator == PT_UNIDIRECTIONAL && !count && useMIS) P.flat = 3;   // ... and the pair form of FLAT
-    // the LEAN generic bounce exists for the three timed kernels generic scenes run: the pair form of FLAT, the kernel for scenes in HBM
-    // and its 4-wave form (both REFILL)
-    P.lean = (s->leanOk && s->leanWanted && !s->armless && !P.simple && !count && !P.cull && (P.flat == 3 || (!onchip && P.refill))) ? 1 : 0;
     s->lastLaunchLean = P.lean;
     s->lastLaunchRefill = P.refill; s->lastLaunchFlat = (P.flat && !count) ? 1 : 0;
     s->lastLaunchSimple = (P.simple && !count) ? 1 : 0;
     s->lastLaunchFlat2 = (P.flat == 3) ? 1 : 0;
     s->lastLaunchLeafTable = (P.flat && !count && P.nLeaves > 0) ? 1 : 0;
     s->lastLaunchHbm = hbm ? 1 : 0;
-    P.onchip = onchip ? 1 : 0;
-    P.wavesPerSimd = hbm ? wavesHbm : (PT_MIN_WAVES > 0 ? PT_MIN_WAVES : 4);
-    P.hbm = hbm ? 1 : 0;
+    P.wavesPerSimd = row->f.wavesPerSimd;
     P.queue = nullptr; P.queueMask = 0; P.left = nullptr; P.gridBlocks = 0;
     P.lptPrio = s->lptPrio; P.sliceIters = s->sliceIters; P.schedMask = s->schedMask; P.sliceAlways = s->sliceAlways ? 1 : 0;
     P.queueTimeout = (unsigned long long)s->queueTimeoutMs * 100000ull;        // ms -> ticks of the 100 MHz steady counter (hipDeviceAttributeWallClockRate)
@@ -1324,12 +1326,13 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.spill = spillEntries > 0 ? (int32_t*)s->spill.p : nullptr;
     MomentsK M = {nullptr, nullptr, 0, 0.0f};
     if (fused) {
-        if (!megakernel_has_moments_twin(integrator, count, !(s->deferShadow && !s->armless), P)) return 0;      // the caller renders in batches
+        row = megakernel_choose(integrator, count, !deferred, P, true);     // the twin: its counterpart's facts, so everything sized above stands
+        if (!row || (row->key & kMkBuiltOnly)) return 0;                    // the caller renders in batches
         M.P = fused->P; M.Q = fused->Q; M.c = fused->c; M.rc = 1.0f / (float)fused->c;
         fused->launched = true;
     }
     HIP_OK(hipEventRecord(s->ev0, stream));            // HIP events on the launch stream, around the megakernel only
-    HIP_OK(launch_megakernel(integrator, count, !(s->deferShadow && !s->armless), P, live, list, stream, fused ? &M : nullptr));
+    HIP_OK(launch_megakernel(*row, P, live, list, stream, fused ? &M : nullptr));
     HIP_OK(hipEventRecord(s->ev1, stream));
     s->evPending = true;
     return 0;
@@ -2160,8 +2163,8 @@ int pt_scene_flags(pt_scene* s) {
     if (!s) return 0;
     const bool onchip = scene_onchip(s);
     const bool pers = s->persistent && !s->xcdBands;
-    // the kernel the last launch used; before any launch, the one a full 1080p-class frame would get
-    const bool hbm = s->lastLaunchHbm >= 0 ? s->lastLaunchHbm == 1 : (!onchip && !(s->deferShadow && !s->armless) && s->wavesHbmOk);
+    // the kernel the last launch used; before any launch, the one a frame with tiles enough for any kernel would get
+    const bool hbm = s->lastLaunchHbm >= 0 ? s->lastLaunchHbm == 1 : hbm_kernel_pays(s, false, 1ll << 40);
     return (onchip ? 1 : 0) | (pers ? 2 : 0) | ((pers && s->sliceIters > 0) ? 4 : 0) | (hbm ? 8 : 0) | ((s->cull && hbm) ? 16 : 0) | (s->lastLaunchRefill ? 32 : 0) | (s->lastLaunchFlat ? 64 : 0) | (s->lastLaunchSimple ? 128 : 0) | (s->lastLaunchFlat2 ? 256 : 0) | (s->lastLaunchLeafTable ? 512 : 0) | (s->lastLaunchLean ? 1024 : 0);
 }
 

@@ -240,37 +240,38 @@ hipError_t launch_rng_init(const uint32_t* jump, unsigned long long seed, int w,
     return hipGetLastError();
 }
 
-// The megakernel instantiations live in two translation units with different code-generation flags (pt_megakernel.h):
-// scenes that live in LDS (ONCHIP kernels) and scenes in HBM (megakernel_hbm and the general 4-wave kernel).
-hipError_t launch_megakernel_lds(int integrator, bool count, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream, const MomentsK* M);
-hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream, const MomentsK* M);
-
-// The twins that are built (pt_megakernel.h, the end): one per non-counting kernel the dispatch below reaches under default options —
-// the LDS-resident forms (pair, FLAT, plain; all trace the shadow ray inside the bounce or pair it) and the REFILL forms for scenes in
-// HBM with their 4-wave forms. Not built: culling, the plain loops ("refill" 0), and whatever only an experimental build launches.
-bool megakernel_has_moments_twin(int integrator, bool count, bool syncShadow, const KParams& P) {
+// Which kernel a launch gets: decided here and nowhere else. The instantiations live in two translation units with different
+// code-generation flags (pt_megakernel.h), each with the table of what it builds (pt_mk_lds.hip: scenes that live in LDS; pt_mk_hbm.hip:
+// megakernel_hbm and the general 4-wave kernel). A launch is reduced to the key of the row that serves it; a launch no row serves has no
+// kernel (what only an experimental build launches has its rows there, and pt_api.hip never asks for it in a default build).
+const MkRow* megakernel_choose(int integrator, bool count, bool syncShadow, const KParams& P, bool moments) {
 #ifdef PT_EXPERIMENTAL
-    return false;
-#else
-    if (count || P.cull || P.wide || P.compact || P.xcdBands) return false;
-    if (integrator != 0 && integrator != 2) return false;
-    if (integrator == 0 && !syncShadow) return false;
-    const bool flat2 = P.flat == 3 && integrator == 0;
-    // The SIMPLE pair kernel's twin (megakernel_flat2_moments<0, true>) is built and bit-exact but out of the dispatch: on the 1080p
-    // Cornell frame at 4 spp in 2 batches it measured 13.01 ms a preview frame against 12.71 ms in two launches.
-    if (flat2 && P.simple) return false;
-    const bool ldsScene = P.onchip && !P.hbm && (integrator == 2 || syncShadow || flat2);
-    return ldsScene ? !P.refill : P.refill != 0;
+    if (moments) return nullptr;                              // the twins are picked under default options only: an A/B build renders its moments in batches
 #endif
+    if ((integrator != 0 && integrator != 2) || (unsigned)P.flat > 3u) return nullptr;
+    // What the kernels do not distinguish. Only timed kernels have the FLAT and SIMPLE forms: a counting launch of such a scene takes the
+    // plain counting kernel. The pair form of FLAT (3) is integrator 0's, FLAT otherwise. The naive integrator has no shadow ray to defer.
+    int flat = count ? 0 : P.flat;
+    if (flat == 3 && integrator != 0) flat = 1;
+    const bool simple = P.simple && !count, defer = !syncShadow && integrator != 2;
+    const unsigned key = (integrator == 2 ? kMkI2 : 0u) | (count ? kMkCount : 0u) | (defer ? kMkDefer : 0u) | ((P.onchip && !P.hbm) ? kMkLds : 0u) | (P.hbm ? kMkHbm : 0u) |
+                         kMkFlat * (unsigned)flat | (simple ? kMkSimple : 0u) | (P.lean ? kMkLean : 0u) | (P.refill ? kMkRefill : 0u) | (P.cull ? kMkCull : 0u) |
+                         (P.wide ? kMkWide : 0u) | (P.compact ? kMkCompact : 0u) | (moments ? kMkMoments : 0u);
+    for (int i = 0; i < kMkRowsLdsCount; i++) if ((kMkRowsLds[i].key & ~kMkBuiltOnly) == key) return &kMkRowsLds[i];
+    for (int i = 0; i < kMkRowsHbmCount; i++) if ((kMkRowsHbm[i].key & ~kMkBuiltOnly) == key) return &kMkRowsHbm[i];
+    return nullptr;
+}
+
+bool megakernel_has_moments_twin(int integrator, bool count, bool syncShadow, const KParams& P) {
+    const MkRow* row = megakernel_choose(integrator, count, syncShadow, P, true);
+    return row && !(row->key & kMkBuiltOnly);
 }
 
 // live: the tiles this launch renders — P.tileCount, or (list != null, queued launches only) the list's first `live` entries,
 // tile numbers below P.tileCount.
-// M (samples per batch > 0): the fused moments twin of that kernel.
-hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream, const MomentsK* M) {
+hipError_t launch_megakernel(const MkRow& row, const KParams& P, int live, const int* list, hipStream_t stream, const MomentsK* M) {
     if (live <= 0) return hipSuccess;
-    if (M && M->c <= 0) M = nullptr;
-    if (M && !megakernel_has_moments_twin(integrator, count, syncShadow, P)) return hipErrorInvalidValue;
+    if ((row.key & kMkBuiltOnly) || ((row.key & kMkMoments) ? !(M && M->c > 0) : M != nullptr)) return hipErrorInvalidValue;
     if (list && !(P.queue && P.gridBlocks > 0)) return hipErrorInvalidValue;
     int nBlocks = megakernel_blocks(live, P.wgWaves);
     if (P.queue && P.gridBlocks > 0) {
@@ -278,15 +279,16 @@ hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const 
         if (list) hipLaunchKernelGGL(queue_init_list_kernel, dim3((P.queueMask + 256) / 256), dim3(256), 0, stream, P.queue, P.queueMask, P.tileCount, list, live, P.queueTimeout);
         else hipLaunchKernelGGL(queue_init_kernel, dim3((P.queueMask + 256) / 256), dim3(256), 0, stream, P.queue, P.queueMask, P.tileCount, P.queueTimeout);
     }
-    dim3 grid(nBlocks), block(64 * P.wgWaves);
-    const bool hbm = P.hbm != 0;                               // chosen by the host together with the spill layout
-    const bool flat2 = P.flat == 3 && integrator == 0 && !count;
-    const bool ldsScene = P.onchip && !hbm && (integrator == 2 || syncShadow || flat2);
-    const bool simpleKernel = P.simple && !count && ((ldsScene && P.flat) || (!ldsScene && P.refill && !P.cull));      // the instantiations without medium stacks
-    const unsigned lds = (unsigned)megakernel_lds_bytes(P.cacheNodes, P.cacheTris, hbm ? ((P.simple && P.refill && !count) ? kStackLdsHbm : kStackLdsHbmGen) : (flat2 ? kStackFlat2 : kStackLds), P.wgWaves,
-                                                        ldsScene ? attr_cache_bytes(P.cacheAttrs, P.cacheMats, P.cacheLights) : 0, !simpleKernel);
-    if (ldsScene) return launch_megakernel_lds(integrator, count, P, grid, block, lds, stream, M);
-    return launch_megakernel_hbm(integrator, count, syncShadow, hbm, P, grid, block, lds, stream, M);
+    // the dynamic LDS is laid out by the kernel's own facts; more than 64 KB per workgroup has to be asked for (a workgroup may take all
+    // 160 KB of its CU: the workgroups of 8, 12 or 16 waves)
+    const unsigned lds = (unsigned)megakernel_lds_bytes(P.cacheNodes, P.cacheTris, row.f.stackEntries, P.wgWaves,
+                                                        row.f.attrCache ? attr_cache_bytes(P.cacheAttrs, P.cacheMats, P.cacheLights) : 0, row.f.mediumStacks);
+    if (lds > 65536u) {
+        const hipError_t e = hipFuncSetAttribute(row.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    void* args[] = {const_cast<KParams*>(&P), const_cast<MomentsK*>(M)};     // (KParams) or, the twins, (KParams, MomentsK)
+    return hipLaunchKernel(row.fn, dim3(nBlocks), dim3(64 * P.wgWaves), args, lds, stream);
 }
 
 hipError_t launch_untile(int w, int h, TileSpan t, const float4* tiles, float4* colors, hipStream_t stream) {

@@ -592,10 +592,18 @@ __global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))     // cap VGPRs so that PT_MIN_WAVES waves fit per SIMD
 #endif
 megakernel(KParams P) { megakernel_body<INTEG, COUNT, DEFER, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, 0, LEAN>(P); }
+// Each wrapper is followed by what the host needs to know about it (pt_params.h: MkFacts; the tables' rows take it from here): the STACKN
+// it hands the body, whether that body has medium stacks (megakernel_body: kMedBytes, none with SIMPLE), whether it stages the bounce's
+// records (ATTRLDS: the ONCHIP kernels), and its launch bounds and register cap.
+constexpr int kMkMinWaves = PT_MIN_WAVES > 0 ? PT_MIN_WAVES : 4;
+template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, bool REFILL, bool FLAT, bool SIMPLE, int FLATW, bool LEAN>
+constexpr MkFacts megakernel_facts = {kStackLds, !SIMPLE, ONCHIP, 0, kMkMinWaves};
 
 template <int INTEG, bool COUNT, bool CULL, bool REFILL, bool SIMPLE = false, bool LEAN = false>
 __global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))
 megakernel_hbm(KParams P) { megakernel_body<INTEG, COUNT, false, false, kStackLdsHbmGen, CULL, REFILL, false, SIMPLE, 1, 0, LEAN>(P); }
+template <int INTEG, bool COUNT, bool CULL, bool REFILL, bool SIMPLE, bool LEAN>
+constexpr MkFacts megakernel_hbm_facts = {kStackLdsHbmGen, !SIMPLE, false, kWgWavesHbm, kWavesHbm};
 
 // FLAT for both rays of a lane (pt_trace.h: trace_pair_flat): scenes of at most 64 nodes / triangles none of which is a MAT_LEAF
 // (any hit occludes a shadow ray) and all of whose materials have a dispatch arm (the DEFER logic step is exact), MIS
@@ -607,23 +615,31 @@ __global__ void __launch_bounds__(1024)
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
 #endif
 megakernel_flat2(KParams P) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, 0, LEAN>(P); }
+template <int INTEG, bool SIMPLE, bool LEAN>
+constexpr MkFacts megakernel_flat2_facts = {kStackFlat2, !SIMPLE, true, 0, kMkMinWaves};
 
 #ifdef PT_EXPERIMENTAL
 // ... and the same on the reference tree collapsed to 4-wide nodes (pt_trace_experimental.h: trace_resume_w4).
 template <int INTEG>
 __global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
 megakernel_hbm_wide(KParams P) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 1>(P); }
+template <int INTEG>
+constexpr MkFacts megakernel_hbm_wide_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
 
 // ... and on 32-byte quantised nodes with exact leaf boxes (pt_trace_experimental.h: trace_resume_q).
 template <int INTEG>
 __global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
 megakernel_hbm_compact(KParams P) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 2>(P); }
+template <int INTEG>
+constexpr MkFacts megakernel_hbm_compact_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
 #endif
 
 // The SIMPLE production kernel for scenes in HBM: 8 waves per SIMD, 16-wave workgroups (pt_params.h).
 template <int INTEG>
 __global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
 megakernel_hbm_simple(KParams P) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true>(P); }
+template <int INTEG>
+constexpr MkFacts megakernel_hbm_simple_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
 
 // ---- the fused moments twins (option "moments_fused", pt_api.hip: render_moments) ----
 // One twin per timed kernel that the launcher picks under default options: the same body with MOMENTS, under the same launch
@@ -635,6 +651,8 @@ __global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
 #endif
 megakernel_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, 0, LEAN, true>(P, M); }
+template <int INTEG, bool ONCHIP, bool REFILL, bool FLAT, bool SIMPLE, int FLATW, bool LEAN>
+constexpr MkFacts megakernel_moments_facts = {kStackLds, !SIMPLE, ONCHIP, 0, kMkMinWaves};
 
 template <int INTEG, bool SIMPLE, bool LEAN = false>
 __global__ void __launch_bounds__(1024)
@@ -642,14 +660,19 @@ __global__ void __launch_bounds__(1024)
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
 #endif
 megakernel_flat2_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, 0, LEAN, true>(P, M); }
+template <int INTEG, bool SIMPLE, bool LEAN>
+constexpr MkFacts megakernel_flat2_moments_facts = {kStackFlat2, !SIMPLE, true, 0, kMkMinWaves};
 
 template <int INTEG, bool LEAN>        // the REFILL forms of megakernel_hbm: the generic bounce and its LEAN form
 __global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))
 megakernel_hbm_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbmGen, false, true, false, false, 1, 0, LEAN, true>(P, M); }
+template <int INTEG, bool LEAN>
+constexpr MkFacts megakernel_hbm_moments_facts = {kStackLdsHbmGen, true, false, kWgWavesHbm, kWavesHbm};
 
 template <int INTEG>
 __global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
 megakernel_hbm_simple_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 0, false, true>(P, M); }
-
+template <int INTEG>
+constexpr MkFacts megakernel_hbm_simple_moments_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
 
 }  // namespace pt

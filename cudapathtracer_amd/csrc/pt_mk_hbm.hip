@@ -11,61 +11,42 @@
 
 namespace pt {
 
-hipError_t launch_megakernel_hbm(int integrator, bool count, bool syncShadow, bool hbm, const KParams& P, dim3 grid, dim3 block, unsigned lds, hipStream_t stream, const MomentsK* M) {
-    // more than 64 KB of dynamic LDS per workgroup has to be asked for (a workgroup may take all 160 KB of its CU)
-#define PT_LDS_OK(K) do { if (lds > 65536u) { hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e_ != hipSuccess) return e_; } } while (0)
-    if (M) {                                                 // the fused moments twins, picked exactly as their counterparts are below
-        if (count || !P.refill || P.cull || P.wide || P.compact || (integrator != 2 && !syncShadow)) return hipErrorInvalidValue;
-#define PT_LAUNCH_MO(K) do { PT_LDS_OK((K)); hipLaunchKernelGGL((K), grid, block, lds, stream, P, *M); } while (0)
-#define PT_PICK_MO(I) do { if (hbm) { if (P.simple) PT_LAUNCH_MO((megakernel_hbm_simple_moments<I>)); \
-                                      else if (P.lean) PT_LAUNCH_MO((megakernel_hbm_moments<I, true>)); \
-                                      else PT_LAUNCH_MO((megakernel_hbm_moments<I, false>)); } \
-                           else if (P.simple) PT_LAUNCH_MO((megakernel_moments<I, false, true, false, true>)); \
-                           else if (P.lean) PT_LAUNCH_MO((megakernel_moments<I, false, true, false, false, 1, true>)); \
-                           else PT_LAUNCH_MO((megakernel_moments<I, false, true>)); } while (0)
-        if (integrator == 2) PT_PICK_MO(2); else PT_PICK_MO(0);
-#undef PT_PICK_MO
-#undef PT_LAUNCH_MO
-        return hipGetLastError();
-    }
-#define PT_LAUNCH_MK(I, C, D, RF) hipLaunchKernelGGL((megakernel<I, C, D, false, RF>), grid, block, lds, stream, P)
-#define PT_LAUNCH_HBM1(I, C, CU, RF) do { PT_LDS_OK((megakernel_hbm<I, C, CU, RF>)); hipLaunchKernelGGL((megakernel_hbm<I, C, CU, RF>), grid, block, lds, stream, P); } while (0)
+// The kernels this file builds, and the launch each serves (pt_params.h: MkRow; pt_kernels.hip: megakernel_choose). A row is what
+// instantiates its kernel. PT_MK_ROW2: the row for integrator 0 and the one for integrator 2.
+const MkRow kMkRowsHbm[] = {
+    // megakernel_hbm: counting and timed, the plain loops, REFILL, culling; timed REFILL launches with the LEAN and the SIMPLE bounce
+    PT_MK_ROW2(kMkHbm | kMkCount, megakernel_hbm, true, false, false, false, false),
+    PT_MK_ROW2(kMkHbm, megakernel_hbm, false, false, false, false, false),
+    PT_MK_ROW2(kMkHbm | kMkCount | kMkRefill, megakernel_hbm, true, false, true, false, false),
+    PT_MK_ROW2(kMkHbm | kMkRefill, megakernel_hbm, false, false, true, false, false),
+    PT_MK_ROW2(kMkHbm | kMkCount | kMkCull, megakernel_hbm, true, true, false, false, false),
+    PT_MK_ROW2(kMkHbm | kMkCull, megakernel_hbm, false, true, false, false, false),
+    PT_MK_ROW2(kMkHbm | kMkRefill | kMkLean, megakernel_hbm, false, false, true, false, true),
+    PT_MK_ROW2(kMkHbm | kMkRefill | kMkSimple, megakernel_hbm_simple),
 #ifdef PT_EXPERIMENTAL
-#define PT_LAUNCH_HBM_TREES(I, C) if (P.refill && P.simple && P.wide && !C) { PT_LDS_OK((megakernel_hbm_wide<I>)); \
-                                                                             hipLaunchKernelGGL((megakernel_hbm_wide<I>), grid, block, lds, stream, P); } \
-                                  else if (P.refill && P.simple && P.compact && !C) { PT_LDS_OK((megakernel_hbm_compact<I>)); \
-                                                                                      hipLaunchKernelGGL((megakernel_hbm_compact<I>), grid, block, lds, stream, P); } else
-#else
-#define PT_LAUNCH_HBM_TREES(I, C)
+    PT_MK_ROW2(kMkHbm | kMkRefill | kMkSimple | kMkWide, megakernel_hbm_wide),
+    PT_MK_ROW2(kMkHbm | kMkRefill | kMkSimple | kMkCompact, megakernel_hbm_compact),
 #endif
-#define PT_LAUNCH_HBM(I, C) do { if (P.cull) PT_LAUNCH_HBM1(I, C, true, false); \
-                                 else PT_LAUNCH_HBM_TREES(I, C) \
-                                 if (P.refill && P.simple && !C) { PT_LDS_OK((megakernel_hbm_simple<I>)); \
-                                                                   hipLaunchKernelGGL((megakernel_hbm_simple<I>), grid, block, lds, stream, P); } \
-                                 else if (P.refill && P.lean && !C) { PT_LDS_OK((megakernel_hbm<I, false, false, true, false, true>)); \
-                                                                      hipLaunchKernelGGL((megakernel_hbm<I, false, false, true, false, true>), grid, block, lds, stream, P); } \
-                                 else if (P.refill) PT_LAUNCH_HBM1(I, C, false, true); \
-                                 else PT_LAUNCH_HBM1(I, C, false, false); } while (0)
-#define PT_PICK(I) do { if (hbm) { if (count) PT_LAUNCH_HBM(I, true); else PT_LAUNCH_HBM(I, false); } \
-                        else if (P.refill && P.simple && !count) hipLaunchKernelGGL((megakernel<I, false, false, false, true, false, true>), grid, block, lds, stream, P); \
-                        else if (P.refill && P.lean && !count) hipLaunchKernelGGL((megakernel<I, false, false, false, true, false, false, 1, true>), grid, block, lds, stream, P); \
-                        else if (P.refill) { if (count) PT_LAUNCH_MK(I, true, false, true); else PT_LAUNCH_MK(I, false, false, true); } \
-                        else if (count) PT_LAUNCH_MK(I, true, false, false); \
-                        else PT_LAUNCH_MK(I, false, false, false); } while (0)
-    if (integrator == 2) PT_PICK(2);
-    else if (syncShadow) PT_PICK(0);
-#ifdef PT_EXPERIMENTAL
-    else { if (count) PT_LAUNCH_MK(0, true, true, false); else PT_LAUNCH_MK(0, false, true, false); }      // option "defer_shadow": the DEFER pair walk
-#else
-    else return hipErrorInvalidValue;                                     // pt_api.hip never asks for it in a default build
+    // the general 4-wave kernel, the same forms but culling
+    PT_MK_ROW2(kMkCount, megakernel, true, false, false, false, false, false, 1, false),
+    PT_MK_ROW2(0u, megakernel, false, false, false, false, false, false, 1, false),
+    PT_MK_ROW2(kMkCount | kMkRefill, megakernel, true, false, false, true, false, false, 1, false),
+    PT_MK_ROW2(kMkRefill, megakernel, false, false, false, true, false, false, 1, false),
+    PT_MK_ROW2(kMkRefill | kMkLean, megakernel, false, false, false, true, false, false, 1, true),
+    PT_MK_ROW2(kMkRefill | kMkSimple, megakernel, false, false, false, true, false, true, 1, false),
+#ifdef PT_EXPERIMENTAL      // option "defer_shadow": the DEFER pair walk; pt_api.hip never asks for it in a default build
+    PT_MK_ROW(kMkDefer | kMkCount, megakernel, 0, true, true, false, false, false, false, 1, false),
+    PT_MK_ROW(kMkDefer, megakernel, 0, false, true, false, false, false, false, 1, false),
 #endif
-#undef PT_PICK
-#undef PT_LAUNCH_HBM
-#undef PT_LAUNCH_HBM_TREES
-#undef PT_LAUNCH_HBM1
-#undef PT_LAUNCH_MK
-#undef PT_LDS_OK
-    return hipGetLastError();
-}
+    // The fused moments twins: the REFILL forms with their 4-wave forms. Not built: culling, the plain loops ("refill" 0), and whatever
+    // only an experimental build launches.
+    PT_MK_ROW2(kMkMoments | kMkHbm | kMkRefill, megakernel_hbm_moments, false),
+    PT_MK_ROW2(kMkMoments | kMkHbm | kMkRefill | kMkLean, megakernel_hbm_moments, true),
+    PT_MK_ROW2(kMkMoments | kMkHbm | kMkRefill | kMkSimple, megakernel_hbm_simple_moments),
+    PT_MK_ROW2(kMkMoments | kMkRefill, megakernel_moments, false, true, false, false, 1, false),
+    PT_MK_ROW2(kMkMoments | kMkRefill | kMkLean, megakernel_moments, false, true, false, false, 1, true),
+    PT_MK_ROW2(kMkMoments | kMkRefill | kMkSimple, megakernel_moments, false, true, false, true, 1, false),
+};
+const int kMkRowsHbmCount = sizeof(kMkRowsHbm) / sizeof(kMkRowsHbm[0]);
 
 }  // namespace pt

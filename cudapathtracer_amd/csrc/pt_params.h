@@ -166,14 +166,39 @@ hipError_t launch_wf_logic(int integrator, bool count, bool simple, const WfPara
 hipError_t launch_wf_trace(bool count, int wgWaves, int blocks, const WfParams& W, const DeviceScene& S, int cacheNodes, int cacheTris, int32_t* spill, int spillPerLane, int it, hipStream_t s);
 hipError_t launch_wf_counters(const WfParams& W, uint32_t* pixCounters, unsigned long long* totals, hipStream_t s);
 
+// ---- the megakernel's instantiations as data (one table, one choice) ----
+// What the host must know about a built kernel to launch it. Written once per kernel family, next to the family's __global__
+// wrapper (pt_megakernel.h), from the constants and template arguments that wrapper hands to megakernel_body.
+struct MkFacts {
+    int stackEntries;              // LDS traversal-stack entries per lane: the dynamic LDS and the global spill area are laid out for them
+    bool mediumStacks;             // kMediumMax x 64 B of medium stacks per wave behind the traversal stacks (not the SIMPLE bounce)
+    bool attrCache;                // the LDS-resident family: the bounce's records are staged behind the stacks
+    int wgWaves;                   // waves per workgroup its launch bounds fix; 0: the host picks (4, or what holds an LDS-resident scene)
+    int wavesPerSimd;              // its register cap
+};
+// Which launch a kernel serves: the selector fields of a launch after megakernel_choose's normalisation, as bits. kMkMoments: a fused
+// moments twin, MomentsK is its second argument.
+enum : unsigned {
+    kMkI2 = 1u, kMkCount = 2u, kMkDefer = 4u, kMkLds = 8u, kMkHbm = 16u, kMkFlat = 32u /* x KParams::flat, two bits */, kMkSimple = 128u, kMkLean = 256u,
+    kMkRefill = 512u, kMkCull = 1024u, kMkWide = 2048u, kMkCompact = 4096u, kMkMoments = 8192u,
+    kMkBuiltOnly = 16384u          // built and correct, but out of the dispatch: megakernel_choose returns the row, nobody launches it
+};
+struct MkRow { const void* fn; const char* name; MkFacts f; unsigned key; };
+// One row per kernel a translation unit instantiates. All template arguments are spelled out: the facts template has no defaults to drift.
+#define PT_MK_ROW(KEY, K, ...) MkRow{reinterpret_cast<const void*>(&K<__VA_ARGS__>), #K "<" #__VA_ARGS__ ">", K##_facts<__VA_ARGS__>, (KEY)}
+#define PT_MK_ROW2(KEY, K, ...) PT_MK_ROW(KEY, K, 0, ##__VA_ARGS__), PT_MK_ROW((KEY) | kMkI2, K, 2, ##__VA_ARGS__)      // INTEG leads every family's arguments
+extern const MkRow kMkRowsLds[]; extern const int kMkRowsLdsCount;      // pt_mk_lds.hip
+extern const MkRow kMkRowsHbm[]; extern const int kMkRowsHbmCount;      // pt_mk_hbm.hip
+// The kernel for a launch: null if none is built for it. `moments`: its fused moments twin (a row marked kMkBuiltOnly counts as none).
+const MkRow* megakernel_choose(int integrator, bool count, bool syncShadow, const KParams& P, bool moments);
+
 // Launchers (asynchronous on `stream`); defined in pt_kernels.hip.
 hipError_t launch_rng_init(const uint32_t* jump, unsigned long long seed, int w, int h, TileSpan t, uint32_t* rng, hipStream_t stream);
-// syncShadow: trace the NEE shadow ray inside the bounce (needed only for materials without a dispatch arm). live: tiles to
-// render, P.tileCount unless `list` (device, queued launches only) names them: the list form of the queue (pt_kernels.hip)
-// M (M->c > 0): launch that kernel's fused moments twin instead.
-hipError_t launch_megakernel(int integrator, bool count, bool syncShadow, const KParams& P, int live, const int* list, hipStream_t stream, const MomentsK* M = nullptr);
-// Is there a fused moments twin of the kernel launch_megakernel would pick for these arguments? Without one the
-// launch fails: the caller asks first and renders in batches instead.
+// row: what megakernel_choose returned for this launch (syncShadow there: trace the NEE shadow ray inside the bounce, needed only
+// for materials without a dispatch arm). live: tiles to render, P.tileCount unless `list` (device, queued launches only) names them:
+// the list form of the queue (pt_kernels.hip). M: a twin's second argument, null for every other row.
+hipError_t launch_megakernel(const MkRow& row, const KParams& P, int live, const int* list, hipStream_t stream, const MomentsK* M = nullptr);
+// Is there a fused moments twin of the kernel these arguments get? Without one the caller renders in batches instead.
 bool megakernel_has_moments_twin(int integrator, bool count, bool syncShadow, const KParams& P);
 hipError_t launch_untile(int w, int h, TileSpan t, const float4* tiles, float4* colors, hipStream_t stream);
 hipError_t launch_tile(int w, int h, TileSpan t, const float4* colors, float4* tiles, hipStream_t stream);
