@@ -71,6 +71,18 @@ PT_DEV float rcp_exact(float a) {
     return 1.0f / a;
 #endif
 }
+// The pair kernels' logic step: forms that issue a sequence once per wave where two exclusive arms each
+// carried their own copy, or that leave out work nothing reads. Same IEEE operations on the same operands per lane. One bit per
+// step, so that A/B variants build from one tree (-DPT_LOGIC_ARMS=n); the template switch ARMS (pt_megakernel.h) turns them on
+// for the pair kernels only, every other kernel keeps its code.
+//   1 inv3 of a ray the lane does not have   2 one basis normalise   4 one light pdf and MIS weight for the emitter and the NEE arm
+//   8 one direction normalise for bounce and regeneration           16 the `o` select of a SIMPLE bounce
+// 16 is off: exact, eight static instructions less, and 0.3 % SLOWER in both A/B forms (profiles/r07_ab_logic_arms.log).
+#ifndef PT_LOGIC_ARMS
+#define PT_LOGIC_ARMS 15
+#endif
+constexpr bool kArmInv3 = (PT_LOGIC_ARMS & 1) != 0, kArmOnb = (PT_LOGIC_ARMS & 2) != 0, kArmMis = (PT_LOGIC_ARMS & 4) != 0,
+               kArmNorm = (PT_LOGIC_ARMS & 8) != 0, kArmDead = (PT_LOGIC_ARMS & 16) != 0;
 PT_DEV float rsqrt_(float x) { return rcp_exact(__builtin_sqrtf(x)); }    // rsqrtf := 1/sqrt, both correctly rounded
 PT_DEV V3 normalize(V3 v) { float il = rsqrt_(dot(v, v)); return V3{v.x * il, v.y * il, v.z * il}; }   // util.cuh:128-131
 PT_DEV float length(V3 v) { return __builtin_sqrtf(dot(v, v)); }

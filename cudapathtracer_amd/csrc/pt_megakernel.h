@@ -179,6 +179,11 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     // trace_pair_flat). The SIMPLE pair kernel only — the headline: in the other two the note costs one more spilled register around
     // the logic step (private segment 52 -> 56 B in the LEAN one, which tests/test_isa.py pins), for one test in eleven.
     constexpr bool LTRI = DEFER && FLAT && SIMPLE;
+    // ARMS: the logic step and the head of the pair pass issue once per wave what two exclusive arms each carried, and leave out
+    // what nothing reads (pt_device.h: PT_LOGIC_ARMS; pt_path.h: bounce_core; pt_trace.h: inv3_uniform) — the two timed pair kernels,
+    // which run at the CU's instruction-issue ceiling, and their moments twins. Every other instantiation keeps its code byte for
+    // byte: the kernels at 64 and 80 VGPRs have lost their scratch pins to a single extra select before.
+    constexpr bool ARMS = DEFER && FLAT && (SIMPLE || LEAN);
     // (... and for the 4-wave SIMPLE kernel that small shares of a scene in HBM run — 128 VGPRs, chain-bound: 1/8 shares +4-5 %,
     //  profiles/r03_shards_hbm_final.log; the 8-wave kernel at 64 VGPRs loses 1-6 % to it)
 #ifndef PT_TRISEL_SIMPLE4
@@ -476,19 +481,24 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
         occ[0] += 64; occ[1] += __builtin_popcountll(__ballot((ps.flags & kInPath) != 0 || (samplesLeft > 0 && !stopStarting)));
 #endif
         const uint32_t flagsIn = ps.flags;
-        if (DEFER) apply_pending<NOLEAF>(ps, thr, acc);
+        if (DEFER) apply_pending<NOLEAF, ARMS && kArmNorm>(ps, thr, acc);
         if constexpr (MOMENTS && DEFER) landed_by_apply(flagsIn);
+        // ARMS: the bounce and camera_ray hand back an unnormalised direction, and ONE normalise serves both (they ran back to back
+        // for disjoint sets of lanes). kDirRaw: this lane got a new ps.d in this step. A lane that got none keeps its old, normalised
+        // one untouched (a LEAN bounce through a boundary that is no true hit; a miss). path_exhausted and path_finish do not read d.
+        // The bit costs no clearing of its own: the next step's apply_pending drops it with the flags it clears anyway.
         if (ps.flags & kInPath) {
-            bool done = path_bounce<INTEG, COUNT, DEFER, SIMPLE, LEAN, NOLEAF, LTRI>(S, ps, ms, h, P.maxDepth, P.useMIS, shadowSync, c, LTRI ? P.lightTri8 : 0ull);
+            bool done = path_bounce<INTEG, COUNT, DEFER, SIMPLE, LEAN, NOLEAF, LTRI, ARMS>(S, ps, ms, h, P.maxDepth, P.useMIS, shadowSync, c, LTRI ? P.lightTri8 : 0ull);
             if (!done) done = path_exhausted<INTEG>(ps, P.maxDepth);
             if (done) { path_finish(ps, acc, DEFER); if constexpr (MOMENTS) landed_by_finish(); }
         }
         PT_STAMP(2);                                   // slot 2: scheduling check + bounce logic (shading, NEE shadow ray)
         while (!(ps.flags & kInPath) && samplesLeft > 0 && !stopStarting) {
             samplesLeft--;
-            path_begin<COUNT>(P.cam, ps, ms, PT_PX, PT_PY, c);
+            path_begin<COUNT, ARMS && kArmNorm>(P.cam, ps, ms, PT_PX, PT_PY, c);
             if (path_exhausted<INTEG>(ps, P.maxDepth)) { path_finish(ps, acc, DEFER); if constexpr (MOMENTS) landed_by_finish(); }
         }
+        if constexpr (ARMS && kArmNorm) { if (ps.flags & kDirRaw) ps.d = normalize(ps.d); }
         const bool hasExt = (ps.flags & kInPath) != 0;
         const bool hasShadow = DEFER && (ps.flags & kShadowPending) != 0;
         PT_STAMP(0);
@@ -497,9 +507,9 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
 #endif
         if (__ballot(hasExt || hasShadow) == 0ull) break;
         if constexpr (DEFER && FLAT) {
-            trace_pair_flat<STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves);
+            trace_pair_flat<STACKN, ARMS>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves);
 #ifdef PT_DIAG_DOUBLE_PAIR          // cost measurement only: the pair pass run twice, same result
-            { Hit h2; V3 thr2; trace_pair_flat<STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr2, h2, c, P.cacheNodes, P.leaves, P.nLeaves);
+            { Hit h2; V3 thr2; trace_pair_flat<STACKN, ARMS>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr2, h2, c, P.cacheNodes, P.leaves, P.nLeaves);
               if (hasExt && h2.tri == h.tri) h.t = fminf_(h.t, h2.t); thr.x = fminf_(thr.x, thr2.x); }
 #endif
         }

@@ -49,6 +49,7 @@ enum : uint32_t {
     kShadowPending = 4u,     // DEFER: (so, sd, smaxt) must be traced and applied
     kNeeValid = 8u,          // DEFER: the recorded NEE sample had light_pdf > EPSILON
     kFinishPending = 16u,    // DEFER: the previous path ended with its last NEE term still pending: `Li` still holds ITS sum
+    kDirRaw = 32u,           // pair kernels (ARMS): `d` was written in this logic step and is not normalised yet; cleared by the next apply_pending
     kLightTriShift = 8u, kLightTriMask = 0x7fu << 8,     // pair kernels: 1 + the packed triangle of the light the pending shadow ray was aimed at (0: none); set and cleared with kShadowPending
 };
 
@@ -103,21 +104,21 @@ PT_DEV void medium_remove(MS& ms, int& top, int materialID) {
 }
 
 // Start the next sample of a pixel (the top of the reference kernels, deviceCode.cu:294-316).
-template <bool COUNT, class MS>
+template <bool COUNT, bool RAW = false, class MS>
 PT_DEV void path_begin(const CamK& cam, PathState& ps, MS& ms, int x, int y, Ctr& c) {
-    camera_ray<COUNT>(cam, ps.rng, x, y, ps.o, ps.d, c);
+    camera_ray<COUNT, RAW>(cam, ps.rng, x, y, ps.o, ps.d, c);        // RAW: ps.d is not normalised yet (pt_shade.h)
     const bool fin = (ps.flags & kFinishPending) != 0;       // Li still holds the finished path's sum (see PathState); this path's own Li is 0 until then
     ps.beta = v3(1.0f); ps.Li = v3(fin ? ps.Li.x : 0.0f, fin ? ps.Li.y : 0.0f, fin ? ps.Li.z : 0.0f); ps.prevPoint = v3(0.0f); ps.woLocal = v3(0.0f);
     ps.pdf = kEps; ps.etaI = kEps; ps.etaT = kEps;
     ps.depth = 0; ps.guard = 0; ps.msTop = 1; ms.set(0, 0);
-    ps.flags = (ps.flags & ~kHitFirstNonSpec) | kInPath;
+    ps.flags = (ps.flags & ~kHitFirstNonSpec) | (RAW ? kInPath | kDirRaw : kInPath);
 }
 
 // DEFER: add the NEE term recorded by the previous bounce (and close a path that ended on it): `Li += (beta * (nee * thr)) * w`
 // exactly as deviceCode.cu:153 groups it, then — if that path had ended — `colors[pixelIdx] += Li` (:540).
 // PRE: no triangle of the scene is a MAT_LEAF, so a shadow ray's throughput is exactly 0 or exactly 1 (BVHShadowRay,
 // integratorUtilities.cuh:188-288); nee * 1.0f == nee bit for bit, and the bounce has recorded the finished term.
-template <bool PRE = false>
+template <bool PRE = false, bool ARMS = false>
 PT_DEV void apply_pending(PathState& ps, V3 thr, V3& acc) {
     // (value selects only: a branch that picks WHICH field to update becomes a pointer select and
     // forces the whole PathState into scratch memory)
@@ -130,7 +131,7 @@ PT_DEV void apply_pending(PathState& ps, V3 thr, V3& acc) {
     const V3 done = acc + li;
     acc = v3(fin ? done.x : acc.x, fin ? done.y : acc.y, fin ? done.z : acc.z);
     ps.Li = v3(fin ? 0.0f : li.x, fin ? 0.0f : li.y, fin ? 0.0f : li.z);
-    ps.flags &= ~(kShadowPending | kNeeValid | kFinishPending | kLightTriMask);
+    ps.flags &= ~(kShadowPending | kNeeValid | kFinishPending | kLightTriMask | (ARMS ? kDirRaw : 0u));       // (kDirRaw: the step's merged normalise has run)
 }
 
 // The loop-top tests of the reference for a live path: `depth < 100` (MIS, deviceCode.cu:318) or
@@ -158,10 +159,14 @@ struct NeeRecord { V3 so, sd; float smaxt; V3 neeRaw, neeBeta; float neeW; };
 // — valid when no triangle is a MAT_LEAF: SIMPLE and LEAN scenes, and every scene the pair form of FLAT accepts.
 // LTRI (the pair pass, pt_trace.h: trace_pair_flat): `flags` also names the packed triangle of the sampled light (kLightTriMask, from
 // the kernel's argument lightTri8) — the one triangle the shadow ray need not be tested against. In a flag word, not a field: it costs no register.
-template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE, bool LEAN, bool PRE, bool LTRI, class MS, class ShadowFn>
+// ARMS (the pair kernels, pt_megakernel.h; the steps are pt_device.h: PT_LOGIC_ARMS): the same operations per lane, issued once
+// per wave where two exclusive arms each had their copy. With its step 8 the new direction comes back UNNORMALISED and kDirRaw
+// says that this bounce wrote one: the caller normalises it together with the directions regeneration produces.
+template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE, bool LEAN, bool PRE, bool LTRI, bool ARMS, class MS, class ShadowFn>
 PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, V3& Li, V3& prevPoint, V3& woLocal,
                         float& pdf, float& etaI, float& etaT, int& depth, int& msTop, uint32_t& flags, NeeRecord& nr,
                         MS& ms, const Hit& h, int maxDepth, int useMIS, ShadowFn shadow, Ctr& c, uint64_t lightTri8) {
+    static_assert(!ARMS || (DEFER && INTEG != 2 && !COUNT), "ARMS is a form of the DEFER logic step of the timed MIS kernels");
     if (COUNT) c.iters++;
     if (h.tri < 0) {
         Li = Li + beta * v3(0.0f);          // `Li += beta * sampleSky()`; the sky is black (integratorUtilities.cuh:436-438)
@@ -188,7 +193,7 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
         return false;
     }
     // ---- Li_unidirectional, deviceCode.cu:332-537 ----
-    const Onb frame = onb_of(hi.normal);                 // toLocal / toWorld of this bounce all use the hit's normal
+    const Onb frame = onb_of<ARMS && kArmOnb>(hi.normal);       // toLocal / toWorld of this bounce all use the hit's normal
     V3 wiLocal = to_local(d, frame);
     bool isSpecular = false, trueHit = true;
     if (!SIMPLE) {
@@ -233,6 +238,69 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
     bool done = false;
     if (trueHit) {
         float le2 = dot(hi.emission, hi.emission);
+        if constexpr (ARMS && kArmMis) {
+            // One light pdf and one MIS weight for the two arms below (`else`), which exclude each other per lane (le2 > kEps
+            // against le2 < kEps) and both compute s2l, normalize(s2l), dist2, cosL and lightPdf of a light, then a weight
+            // a * a / (b * b + a * a): (a, b) = (pdf, lightPdf) for a hit on an emitter, (lightPdf, pdfB) for the NEE sample. The
+            // lanes of either arm select s2l, the light record and (a, b); everything else stays under its arm's own condition,
+            // in the arm's own order (the NEE arm's three draws first, as before; the emitter arm draws nothing).
+            const bool firstSeen = depth == 0 || !(flags & kHitFirstNonSpec);
+            const bool emArm = le2 > kEps && !firstSeen && useMIS && !isSpecular && hi.lightInd >= 0;      // (without a light record: lightPdf = kEps, nothing added)
+            const bool neeArm = useMIS && le2 < kEps && !isSpecular && S.nLights > 0;
+            if (le2 > kEps && firstSeen) Li = Li + beta * hi.emission;
+            int li = 0;
+            V3 s2l = v3(0.0f), A = v3(0.0f), B = v3(0.0f), Cc = v3(0.0f);
+            if (neeArm) {
+                li = min((int)(draw<COUNT>(rng, c) * (float)S.nLights), S.nLights - 1);
+                const PLight& L = S.lights[li];
+                if (LTRI) flags |= li < 8 ? ((uint32_t)(lightTri8 >> (uint32_t)(li * 8)) & 0x7fu) << kLightTriShift : 0u;
+                A = ld3(L.a); B = ld3(L.b); Cc = ld3(L.c);
+                float u = __builtin_sqrtf(draw<COUNT>(rng, c));
+                float v = draw<COUNT>(rng, c);
+                V3 p = (1.0f - u) * A + (u * (1.0f - v)) * B + (u * v) * Cc;
+                s2l = p - hi.point;
+            } else if (emArm) {
+                li = hi.lightInd;
+                s2l = hi.point - prevPoint;
+            }
+            if (neeArm || emArm) {
+                const PLight& L = S.lights[li];
+                V3 wi = normalize(s2l);
+                float dist2 = dot(s2l, s2l);
+                float cosL = dot(ld3(L.na), -wi);
+                float lightPdf = dist2 / (cosL * (float)S.nLights * L.area);
+                float a = pdf, b = lightPdf;
+                V3 nee = v3(0.0f);
+                if (neeArm) {
+                    V3 ro = hi.point + wi * kEps;
+                    float t = length(s2l) - kEps;
+                    {
+                        float tt, uu, vv;
+                        if ((PT_RCP_UNIFORM ? moller_trumbore_sel : moller_trumbore)(A, B - A, Cc - A, ro, wi, tt, uu, vv)) t = tt;
+                    }
+                    const float maxt = t * (1.0f - kEps);
+                    float cosS = __builtin_fabsf(dot(hi.normal, wi));
+                    V3 wiL = to_local(wi, frame);
+                    V3 f = SIMPLE ? ld3(m.albedoOverPi) : f_eval<LEAN>(m, S.textures, wiLocal, wiL, etaI, hi.uvx, hi.uvy);
+                    nee = ((f * ld3(L.emission)) * cosS) / lightPdf;
+                    if (lightPdf > kEps) {
+                        float pdfB = pdf;
+                        if (SIMPLE) pdfB = cosine_pdf(wiL);
+                        else pdf_eval<LEAN>(m, S.textures, wiLocal, wiL, etaI, hi.uvx, hi.uvy, pdfB);
+                        a = lightPdf; b = pdfB;
+                    }
+                    nr.so = ro; nr.sd = wi; nr.smaxt = maxt;          // (traced only with kShadowPending, see the arm below)
+                }
+                if (lightPdf > kEps) {
+                    const float w = a * a / (b * b + a * a);
+                    if (neeArm) {
+                        if (PRE) nr.neeRaw = (beta * nee) * w;
+                        else { nr.neeRaw = nee; nr.neeBeta = beta; nr.neeW = w; }
+                        flags |= kNeeValid | kShadowPending;
+                    } else Li = Li + (beta * hi.emission) * w;
+                }
+            }
+        } else {
         if (le2 > kEps) {
             if (depth == 0 || !(flags & kHitFirstNonSpec)) Li = Li + beta * hi.emission;
             else if (useMIS && !isSpecular) {
@@ -312,6 +380,7 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
                 }
             }
         }
+        }   // (!ARMS)
         V3 f = v3(0.0f);
         if (SIMPLE) cosine_sample_f<COUNT>(rng, ld3(m.albedo), woLocal, f, pdf, c, m.albedoOverPi);
         else sample_f_eval<COUNT, LEAN>(rng, m, S.textures, wiLocal, etaI, hi.backface, woLocal, f, pdf, hi.uvx, hi.uvy, c);
@@ -322,9 +391,13 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
             else medium_remove(ms, msTop, hi.material);
         }
         beta = beta * ((f * __builtin_fabsf(woLocal.z)) / pdf);
-        if (woLocal.z > 0.0f) o = hi.point + hi.normal * kEps;
+        // SIMPLE: woLocal.z = sqrtf(1 - u1) with u1 <= 1 - kEps (cosine_sample_f clamps it), so 1 - u1 >= kEps > 0 and its correctly
+        // rounded root is positive — the `+` arm, always (the !SIMPLE guard above says the same). Taking it unconditionally (step 16
+        // of PT_LOGIC_ARMS) saves the exec split and measured 0.3 % slower, twice: off by default.
+        if ((ARMS && kArmDead && SIMPLE) || woLocal.z > 0.0f) o = hi.point + hi.normal * kEps;
         else o = hi.point - hi.normal * kEps;
-        d = normalize(woWorld);
+        if constexpr (ARMS && kArmNorm) { d = woWorld; flags |= kDirRaw; }
+        else d = normalize(woWorld);
         prevPoint = hi.point;
     } else {
         woLocal = wiLocal;                               // toLocal(ray.direction, normal) again (deviceCode.cu:516): the value computed above
@@ -345,7 +418,7 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
 }
 
 
-template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE = false, bool LEAN = false, bool PRE = SIMPLE, bool LTRI = false, class MS, class ShadowFn>
+template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE = false, bool LEAN = false, bool PRE = SIMPLE, bool LTRI = false, bool ARMS = false, class MS, class ShadowFn>
 PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& h, int maxDepth, int useMIS, ShadowFn shadow, Ctr& c, uint64_t lightTri8 = 0ull) {
     Rng rng = ps.rng;
     V3 o = ps.o, d = ps.d, beta = ps.beta, Li = ps.Li, prevPoint = ps.prevPoint, woLocal = ps.woLocal;
@@ -363,7 +436,7 @@ PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& 
 #else
     nr.so = ps.so; nr.sd = ps.sd; nr.smaxt = ps.smaxt; nr.neeRaw = ps.neeRaw; nr.neeBeta = ps.neeBeta; nr.neeW = ps.neeW;
 #endif
-    bool done = bounce_core<INTEG, COUNT, DEFER, SIMPLE, LEAN, PRE, LTRI>(S, rng, o, d, beta, Li, prevPoint, woLocal, pdf, etaI, etaT, depth, msTop, flags, nr,
+    bool done = bounce_core<INTEG, COUNT, DEFER, SIMPLE, LEAN, PRE, LTRI, ARMS>(S, rng, o, d, beta, Li, prevPoint, woLocal, pdf, etaI, etaT, depth, msTop, flags, nr,
                                                  ms, h, maxDepth, useMIS, shadow, c, lightTri8);
     ps.rng = rng;
     ps.o = o; ps.d = d; ps.beta = beta; ps.Li = Li; ps.prevPoint = prevPoint; ps.woLocal = woLocal;

@@ -13,7 +13,8 @@ template <bool COUNT>
 PT_DEV float draw(Rng& r, Ctr& c) { if (COUNT) c.draws++; return rng_uniform(r); }
 
 // objects.cuh:268-307
-template <bool COUNT>
+// RAW: `d` comes back unnormalised, and the caller normalises it (megakernel_body, together with the bounce's new direction).
+template <bool COUNT, bool RAW = false>
 PT_DEV void camera_ray(const CamK& cam, Rng& rng, int x, int y, V3& o, V3& d, Ctr& c) {
     float aspect = (float)cam.w / (float)cam.h;
     float jitterX = (draw<COUNT>(rng, c) - 0.5f) * cam.jitter;
@@ -30,13 +31,29 @@ PT_DEV void camera_ray(const CamK& cam, Rng& rng, int x, int y, V3& o, V3& d, Ct
         lens = (cam.right * (radius * cs)) + (cam.up * (radius * sn));
     }
     o = cam.origin + lens;
-    d = normalize(focal - o);
+    d = RAW ? focal - o : normalize(focal - o);
 }
 
 // util.cuh:163-185
 PT_DEV V3 onb_tangent(V3 n) {
     if (__builtin_fabsf(n.x) > __builtin_fabsf(n.z)) return normalize(v3(-n.y, n.x, 0.0f));
     return normalize(v3(0.0f, -n.z, n.y));
+}
+// The same values from ONE normalise: a wave whose lanes sit on different walls ran both arms above, each with its own dot, sqrt
+// and reciprocal. Per lane only WHICH two components enter differs, so they are selected and the sequence runs once.
+//   arm |n.x| > |n.z|: v = (-n.y, n.x, 0) and dot(v, v) = fma(0, 0, fma(n.x, n.x, (-n.y) * (-n.y)))
+//   the other arm:     v = (0, -n.z, n.y) and dot(v, v) = fma(n.y, n.y, fma(-n.z, -n.z, 0 * 0))
+// (-a) * (-a) and a * a are the same product. fma(0, 0, x) = RN(0 + x) = x for every x that is not -0, and x here is a rounded
+// sum of two squares: +0, positive, +inf or NaN, never -0. fma(a, a, +0) = RN(a * a + 0) = RN(a * a), the rounded
+// product (a square is never -0 either). So both arms are fma(p, p, q * q) with (p, q) = (n.x, n.y) or (n.y, n.z), bit for bit — the
+// folding the compiler itself does to the two arms above. `t` is formed from the same three products per arm, 0 * il included
+// (NaN when il is).
+PT_DEV V3 onb_tangent_sel(V3 n) {
+    const bool xArm = __builtin_fabsf(n.x) > __builtin_fabsf(n.z);
+    const float p = xArm ? n.x : n.y, q = xArm ? n.y : n.z;
+    const float il = rsqrt_(__builtin_fmaf(p, p, q * q));
+    const V3 v = v3(xArm ? -n.y : 0.0f, xArm ? n.x : -n.z, xArm ? 0.0f : n.y);
+    return V3{v.x * il, v.y * il, v.z * il};
 }
 PT_DEV V3 to_world(V3 l, V3 n) {
     V3 t = onb_tangent(n);
@@ -51,7 +68,8 @@ PT_DEV V3 to_local(V3 w, V3 n) {
 // The reference rebuilds the basis in every toLocal / toWorld call (util.cuh:163-185), three times per bounce on the
 // same normal; it is a pure function of n, so one bounce builds it once (same values).
 struct Onb { V3 t, b, n; };
-PT_DEV Onb onb_of(V3 n) { Onb f; f.t = onb_tangent(n); f.b = cross(n, f.t); f.n = n; return f; }
+template <bool SEL = false>
+PT_DEV Onb onb_of(V3 n) { Onb f; f.t = SEL ? onb_tangent_sel(n) : onb_tangent(n); f.b = cross(n, f.t); f.n = n; return f; }
 PT_DEV V3 to_world(V3 l, const Onb& f) { return l.x * f.t + l.y * f.b + l.z * f.n; }
 PT_DEV V3 to_local(V3 w, const Onb& f) { return v3(dot(w, f.t), dot(w, f.b), dot(w, f.n)); }
 

@@ -96,6 +96,28 @@ PT_DEV V3 inv3(V3 d) {
 #endif
     return v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
 }
+// The same with a wave-uniform range test, as rcp_exact has (pt_device.h), for the pair pass: every lane computes the fast form,
+// and the IEEE divisions run only when some lane that HAS the ray (`has`) is outside the fast form's range — those lanes take them.
+// A lane with the ray gets inv3(d) bit for bit. A lane without it keeps what the fast form gave (for d = 0: NaN), and nothing reads
+// that: trace_pair_flat gates its inv_is_regular ballot, the leaf loop's final select, the node walk's visited sets and the
+// tie-break (nE > 0) by hasExt / hasShadow. The per-lane form above split exec for the zero direction of every lane whose bounce
+// recorded no shadow ray (pt_path.h: a fresh NeeRecord), in practically every pass.
+PT_DEV V3 inv3_uniform(V3 d, bool has) {
+#if PT_FAST_RCP
+    const float lo = fminf_(fminf_(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
+    const float hi = fmaxf_(fmaxf_(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
+    const float rx = __builtin_amdgcn_rcpf(d.x), ry = __builtin_amdgcn_rcpf(d.y), rz = __builtin_amdgcn_rcpf(d.z);
+    V3 r = v3(__builtin_fmaf(rx, __builtin_fmaf(-d.x, rx, 1.0f), rx), __builtin_fmaf(ry, __builtin_fmaf(-d.y, ry, 1.0f), ry),
+              __builtin_fmaf(rz, __builtin_fmaf(-d.z, rz, 1.0f), rz));
+    const bool out = has && !(lo >= 1e-12f && hi <= 1.0e30f);      // (NaN components fail the comparisons, as above)
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(out) != 0ull, 0)) {
+        if (out) r = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    }
+    return r;
+#else
+    return v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+#endif
+}
 
 // aabbIntersect (integratorUtilities.cuh:44-82) with a hoisted reciprocal direction.
 PT_DEV bool slab(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, V3 o, V3 inv, float& tmin) {
@@ -791,7 +813,7 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 #ifndef PT_PAIR_MIN_ALWAYS
 #define PT_PAIR_MIN_ALWAYS 0
 #endif
-template <int N>
+template <int N, bool ARMS = false>
 PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt, uint32_t ltri1,
                             bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
     static_assert(N >= 24, "the scratch layout needs 24 x 64 words of the wave's stack area");
@@ -804,7 +826,9 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     typedef __attribute__((address_space(3))) f4v lds_f4;
     constexpr int kMax = 8 * 128, kKeyA = 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
     lds_f4* Rec = (lds_f4*)Wd;                                    // slot v's record: Rec[2 v], Rec[2 v + 1] (the scene cache before the stacks is whole 16-byte records)
-    const V3 invE = inv3(ed), invS = inv3(sd);
+    V3 invE, invS;
+    if constexpr (ARMS && kArmInv3) { invE = inv3_uniform(ed, hasExt); invS = inv3_uniform(sd, hasShadow); }      // (see inv3_uniform: read only where the lane has the ray)
+    else { invE = inv3(ed); invS = inv3(sd); }
     // 1. one lockstep node walk for both rays
     uint64_t tmE = 0ull, tmS = 0ull;
     if (S.rootRef < 0) { const uint64_t all = ~0ull >> (64 - S.nTris); tmE = hasExt ? all : 0ull; tmS = hasShadow ? all : 0ull; }

@@ -125,7 +125,9 @@ def regions(lines):
     assert trip, "no trip loop (ds_min_u64) found"
     th, te = min(trip, key=lambda x: x[1] - x[0])             # the innermost loop that picks a triangle (ctz) and folds its hit
     leaf = [(h, e) for h, e in lp if e < th and any("s_load_dwordx8" in lines[k] for k in range(h, e + 1))]
-    lh, le = max(leaf, key=lambda x: x[1]) if leaf else (th, th)
+    # the innermost of them: a cold block the compiler lays out behind the loop (the IEEE divisions of inv3_uniform) branches back to
+    # code in front of it, which makes an enclosing "loop" of this kind that is no loop of the source
+    lh, le = min(leaf, key=lambda x: x[1] - x[0]) if leaf else (th, th)
     s0 = next(k for k in range(le, th) if "row_shr:1 " in lines[k] or lines[k].rstrip().endswith("row_shr:1"))
     trip_lines = lines[th:te + 1]
     inner = [(h, e) for h, e in lp if th < h and e <= te]                 # (branches back to the header itself are the loop's own)
