@@ -93,6 +93,11 @@ class ResolveParams(C.Structure):    # pt_resolve_params
     _fields_ = [("tonemap", C.c_int32), ("exposure", C.c_float)]
 
 
+class SelectEntry(C.Structure):      # pt_select_entry
+    _fields_ = [("component", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("colour", C.c_uint8 * 4), ("radius", C.c_int32),
+                ("fill_alpha", C.c_int32)]
+
+
 class PreviewParams(C.Structure):    # pt_preview_params
     _fields_ = [("spp", C.c_int32), ("batches", C.c_int32), ("max_depth", C.c_int32), ("integrator", C.c_int32), ("use_mis", C.c_int32),
                 ("aov_spp", C.c_int32), ("temporal", C.c_int32), ("filter", C.c_int32), ("temporal_params", TemporalParams),
@@ -178,6 +183,16 @@ def lib():
     L.pt_preview_motion.argtypes = [vp]
     L.pt_preview_set_motion_chain.argtypes = [vp, i32]
     L.pt_preview_motion_chain.argtypes = [vp]
+    L.pt_render_ids.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp]
+    L.pt_render_ids_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp, vp]
+    L.pt_pick.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, vp, i32, vp, vp]
+    L.pt_select_overlay.argtypes = [i32, i32, vp, i32, C.POINTER(SelectEntry), vp]
+    L.pt_select_overlay_device.argtypes = [i32, i32, vp, i32, C.POINTER(SelectEntry), vp, vp]
+    L.pt_preview_set_selection.argtypes = [vp, i32, C.POINTER(SelectEntry), i32]
+    L.pt_preview_pick.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.pt_preview_read_ids.argtypes = [vp, vp]
+    L.pt_preview_device_ids.restype = vp; L.pt_preview_device_ids.argtypes = [vp]
+    L.pt_preview_id_passes.argtypes = [vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
@@ -738,6 +753,26 @@ class Scene:
         pointers both 0 / None or both set, the links pointer only with them), asynchronous on `stream`."""
         _check(lib().pt_render_motion_chain_device(self.h, C.byref(camera), w, h, max_links, d_albedo_ptr or None, d_normal_depth_ptr or None,
                                                    d_links_ptr or None, d_motion_ptr or None, stream or None), "pt_render_motion_chain_device")
+
+    def render_ids(self, camera, w, h, max_links=0):
+        """pt_render_ids: [h,w,4] int32 per pixel centre: (tri, material, light or -1, info), info = backface bit | links << 8, of
+        the surface render_aovs_centre(camera, w, h, max_links) shows there; (-1, -1, -1, 0) where the ray hits nothing. tri indexes
+        the description's triangles, material is update_materials' row, light is update_emission's index."""
+        ids = np.zeros((h, w, 4), np.int32)
+        _check(lib().pt_render_ids(self.h, C.byref(camera), w, h, max_links, _p(ids)), "pt_render_ids")
+        return ids
+
+    def render_ids_device(self, camera, w, h, max_links, d_ids_ptr, stream=0):
+        """pt_render_ids_device: the same into a device buffer of w*h int32x4, asynchronous on `stream`."""
+        _check(lib().pt_render_ids_device(self.h, C.byref(camera), w, h, max_links, d_ids_ptr or None, stream or None), "pt_render_ids_device")
+
+    def pick(self, camera, w, h, xy, max_links=0):
+        """pt_pick: render_ids at the pixels xy ([n,2] int32, (x, y) each): (ids [n,4] int32, hit [n,4] float32), hit being the
+        surface's point and the chain's summed path length (render_aovs_centre's depth there); zeros for a miss. Blocking."""
+        q = np.ascontiguousarray(np.asarray(xy, np.int32).reshape(-1, 2))
+        ids, hit = np.zeros((len(q), 4), np.int32), np.zeros((len(q), 4), np.float32)
+        _check(lib().pt_pick(self.h, C.byref(camera), w, h, len(q), _p(q), max_links, _p(ids), _p(hit)), "pt_pick")
+        return ids, hit
 
     @property
     def has_motion(self):
@@ -1594,6 +1629,45 @@ def resolve_device(w, h, d_rgba_ptr, spp, d_rgba8_ptr, d_mean_ptr=0, d_tile_spp_
                                    stream or None), "pt_resolve_device")
 
 
+def select_entries(entries):
+    """A pt_select_entry array from SelectEntry objects or dicts / tuples (component, lo, hi, colour (r, g, b, outline alpha), radius,
+    fill_alpha); component may be "tri", "material" or "light". Returns (n, array or None)."""
+    entries = list(entries or ())
+    if not entries:
+        return 0, None
+    arr = (SelectEntry * len(entries))()
+    for i, e in enumerate(entries):
+        if isinstance(e, SelectEntry):
+            e = (e.component, e.lo, e.hi, tuple(e.colour), e.radius, e.fill_alpha)
+        elif isinstance(e, dict):
+            e = tuple(e[k] for k in ("component", "lo", "hi", "colour", "radius", "fill_alpha"))
+        comp, lo, hi, colour, radius, fill = e
+        comp = {"tri": 0, "material": 1, "light": 2}.get(comp, comp)
+        arr[i] = SelectEntry(int(comp), int(lo), int(hi), (C.c_uint8 * 4)(*[int(c) for c in colour]), int(radius), int(fill))
+    return len(entries), arr
+
+
+def select_overlay(ids, rgba8, entries):
+    """pt_select_overlay (host, blocking): a copy of rgba8 ([h,w,4] uint8) with the selections `entries` (at most four, see
+    select_entries) drawn from ids ([h,w,4] int32, render_ids' output): outline pixels blended with the entry's colour at its outline
+    alpha, fill pixels at fill_alpha, the alpha byte and unselected pixels untouched."""
+    if not (isinstance(ids, np.ndarray) and ids.dtype == np.int32 and ids.ndim == 3 and ids.shape[2] == 4):
+        raise PtError("select_overlay: ids must be an int32 [h, w, 4] array")
+    if not (isinstance(rgba8, np.ndarray) and rgba8.dtype == np.uint8 and rgba8.shape == ids.shape):
+        raise PtError("select_overlay: rgba8 must be a uint8 array of ids' shape")
+    h, w = ids.shape[:2]
+    out = np.ascontiguousarray(rgba8).copy()
+    n, arr = select_entries(entries)
+    _check(lib().pt_select_overlay(w, h, _p(np.ascontiguousarray(ids)), n, arr, _p(out)), "pt_select_overlay")
+    return out
+
+
+def select_overlay_device(w, h, d_ids_ptr, entries, d_rgba8_ptr, stream=0):
+    """pt_select_overlay_device: in place on device buffers (w*h int32x4 in, w*h*4 bytes in and out), asynchronous on `stream`."""
+    n, arr = select_entries(entries)
+    _check(lib().pt_select_overlay_device(w, h, d_ids_ptr or None, n, arr, d_rgba8_ptr or None, stream or None), "pt_select_overlay_device")
+
+
 def preview_defaults():
     """pt_preview_defaults as a dict; temporal_params, filter_params and resolve_params are dicts themselves."""
     p = PreviewParams()
@@ -1720,6 +1794,36 @@ class Preview:
     def guide_passes(self):
         """pt_preview_guide_passes: feature-pass launches of all good frames since the session was created."""
         return lib().pt_preview_guide_passes(self.handle)
+
+    def set_selection(self, entries=(), max_links=0):
+        """pt_preview_set_selection: the frames that follow end with select_overlay(entries) on their rgba8, drawn from the session's
+        own ID buffer (render_ids(the frame's camera, max_links) at display size, traced again only when the camera, the scene or
+        max_links changed). No entries turns it off, which is a session's initial state. Nothing but rgba8 changes, and the session
+        is not reset."""
+        n, arr = select_entries(entries)
+        _check(lib().pt_preview_set_selection(self.handle, n, arr, int(max_links)), "pt_preview_set_selection")
+        return self
+
+    def pick(self, x, y, max_links=0):
+        """pt_preview_pick: Scene.pick of one pixel with the last good frame's camera at display size: (ids [4] int32, hit [4] float32)."""
+        ids, hit = np.zeros(4, np.int32), np.zeros(4, np.float32)
+        _check(lib().pt_preview_pick(self.handle, int(x), int(y), int(max_links), _p(ids), _p(hit)), "pt_preview_pick")
+        return ids, hit
+
+    def read_ids(self):
+        """pt_preview_read_ids: the session's ID buffer, [h,w,4] int32."""
+        ids = np.empty((self.h, self.w, 4), np.int32)
+        _check(lib().pt_preview_read_ids(self.handle, _p(ids)), "pt_preview_read_ids")
+        return ids
+
+    def device_ids(self):
+        """Device address of the w*h int32x4 ID buffer (None before the first selection; valid until close())."""
+        return lib().pt_preview_device_ids(self.handle)
+
+    @property
+    def id_passes(self):
+        """pt_preview_id_passes: ID-pass launches of all good frames since the session was created."""
+        return lib().pt_preview_id_passes(self.handle)
 
     def set_converge(self, threshold=None, min_history=None):
         """pt_preview_set_converge: while the camera rests, the frames that follow render only the 8x8 tiles whose history has

@@ -124,6 +124,7 @@ struct pt_scene {
     DevBuf posCur, posPrev;
     bool hasMotion = false;               // pt_scene_has_motion: the last successful update was a vertex update
     DevBuf motionOut;                     // pt_render_motion, host form: staging
+    DevBuf idsOut;                        // pt_render_ids, host form, and pt_pick: staging
     DevBuf edit;                          // pt_scene_update_materials / _emission: the edit's table and the kernel's result word
     float renumberMs = 0.0f, updateMs = 0.0f;   // host wall clock of the last renumber_by_area / of the last successful update (pt_debug_update_ms)
     float lastKernelMs = 0.0f;
@@ -186,7 +187,7 @@ void pt_scene_destroy(pt_scene* s) {
                      &s->moS, &s->moP, &s->moQ, &s->moOut, &s->moList,
                      &s->kTris, &s->kNormals, &s->kUvs, &s->kTypes, &s->kLightTris,
                      &s->spNodes, &s->spTris, &s->spAttrs, &s->spLights, &s->spLeaves, &s->spNormals, &s->buildPool,
-                     &s->posCur, &s->posPrev, &s->motionOut, &s->edit};
+                     &s->posCur, &s->posPrev, &s->motionOut, &s->idsOut, &s->edit};
     for (DevBuf* b : all) b->release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1774,7 +1775,7 @@ int pt_render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int spp, 
 
 }  // extern "C"
 
-// The feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip; their launchers and block counts: pt_feature_host.h).
+// The feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip; their launchers and block counts: pt_feature_host.h).
 
 // The traversal spill area of a feature pass of `blocks` workgroups: the passes' own (a render in flight on this scene keeps s->spill),
 // shared among them, since all run on the caller's stream, one after the other. NULL for a scene whose stack never leaves the LDS.
@@ -1973,6 +1974,63 @@ int pt_render_motion_chain(pt_scene* s, const pt_camera* cam, int w, int h, int 
     const size_t bytes = (size_t)w * h * sizeof(float4), lbytes = (size_t)w * h * sizeof(float);
     return feature_download(s->motionOut, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_motion, bytes}, {out_links, lbytes}},
                             [&](void* const* d) { return render_motion_chain(s, cam, w, h, max_links, d[0], d[1], d[3], d[2], nullptr); });
+}
+
+// The ID pass and the pick queries (pt_ids.hip: ids_kernel, ids_chain_kernel). Every message under the caller's name, all before any
+// HIP call (the device check comes last).
+static int check_ids_args(const char* fn, pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, const void* ids, const int32_t* xy = nullptr,
+                          int n = 0) {
+    if (maxLinks < 0 || maxLinks > 16) return fail(-1, "%s: max_links %d must be 0..16", fn, maxLinks);
+    if (w <= 0 || h <= 0) return fail(-1, "%s: image size %d x %d must be positive", fn, w, h);
+    if ((long long)w * h > 0x7fffffffll) return fail(-1, "%s: image of %d x %d pixels is too large", fn, w, h);
+    if (!cam) return fail(-1, "%s: null camera", fn);
+    if (cam->w != w || cam->h != h) return fail(-1, "%s: the camera is %d x %d, the image %d x %d", fn, cam->w, cam->h, w, h);
+    if (!ids) return fail(-1, "%s: null ids output", fn);
+    for (int k = 0; k < n; k++)
+        if (xy[2 * k] < 0 || xy[2 * k] >= w || xy[2 * k + 1] < 0 || xy[2 * k + 1] >= h)
+            return fail(-1, "%s: pixel %d is (%d, %d), outside the %d x %d image", fn, k, xy[2 * k], xy[2 * k + 1], w, h);
+    if (!s) return fail(-1, "%s: null scene", fn);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->device) return fail(-1, "%s: scene lives on HIP device %d but the current device is %d", fn, s->device, dev);
+    return 0;
+}
+
+// xy NULL: the image. xy set: nPick pixels (device memory), and dHit their (point, depth) records.
+static int render_ids(pt_scene* s, const pt_camera* cam, int w, int h, int maxLinks, const int32_t* xy, int nPick, void* dIds, void* dHit,
+                      hipStream_t stream) {
+    const int nTiles = xy ? (nPick + 63) / 64 : feature_tiles(w, h).nTiles;
+    const int blocks = feature_blocks(nTiles, s->numCU, maxLinks > 0 ? kIdsChainWavesPerSimd : kIdsWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_ids(s->ds, cam_to_kernel(*cam), w, h, maxLinks, xy, nPick, blocks, (int4*)dIds, (float4*)dHit, spill, stream));
+    return 0;
+}
+
+int pt_render_ids_device(pt_scene* s, const pt_camera* cam, int w, int h, int max_links, void* d_ids, void* stream) {
+    if (int r = check_ids_args("pt_render_ids", s, cam, w, h, max_links, d_ids)) return r;
+    return render_ids(s, cam, w, h, max_links, nullptr, 0, d_ids, nullptr, (hipStream_t)stream);
+}
+
+int pt_render_ids(pt_scene* s, const pt_camera* cam, int w, int h, int max_links, int32_t* out_ids) {
+    if (int r = check_ids_args("pt_render_ids", s, cam, w, h, max_links, out_ids)) return r;
+    return feature_download(s->idsOut, {{out_ids, (size_t)w * h * sizeof(int4)}},
+                            [&](void* const* d) { return render_ids(s, cam, w, h, max_links, nullptr, 0, d[0], nullptr, nullptr); });
+}
+
+int pt_pick(pt_scene* s, const pt_camera* cam, int w, int h, int n, const int32_t* xy, int max_links, int32_t* out_ids, float* out_hit) {
+    if (n <= 0) return fail(-1, "pt_pick: n %d must be positive", n);
+    if (!xy) return fail(-1, "pt_pick: null pixel list");
+    if (!out_hit) return fail(-1, "pt_pick: null hit output");
+    if (int r = check_ids_args("pt_pick", s, cam, w, h, max_links, out_ids, xy, n)) return r;
+    // staging: the list, then the two outputs, each slice a multiple of 16 bytes
+    const size_t xyBytes = ((size_t)n * 8 + 15) & ~(size_t)15, recBytes = (size_t)n * 16;
+    if (int r = s->idsOut.ensure(xyBytes + 2 * recBytes)) return r;
+    char* d = (char*)s->idsOut.p;
+    HIP_OK(hipMemcpy(d, xy, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (int r = render_ids(s, cam, w, h, max_links, (const int32_t*)d, n, d + xyBytes, d + xyBytes + recBytes, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_ids, d + xyBytes, recBytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_hit, d + xyBytes + recBytes, recBytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int pt_has_experimental(void) {

@@ -1,4 +1,4 @@
-// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip): the tiling and block
+// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip): the tiling and block
 // count every one of them is launched with, each kernel's waves per SIMD, and the launchers pt_api.hip calls. The kernels' shared pieces are in
 // pt_feature.h.
 #pragma once
@@ -23,6 +23,9 @@ constexpr int kAovCentreWavesPerSimd = 8;    // aov_centre_kernel: without the s
 constexpr int kMotionWavesPerSimd = 8;       // motion_kernel: 63 VGPRs, 8 x 16 KB of LDS, as the centre pass
 constexpr int kMotionChainWavesPerSimd = 5;  // motion_chain_kernel: 93 VGPRs (the unfolding matrix stays in registers), 26 KB of LDS: 6 workgroups
                                              // would fit the LDS, 5 waves fit the registers
+constexpr int kIdsWavesPerSimd = 8;          // ids_kernel: 63 VGPRs, 8 x 16 KB of LDS, as the centre pass
+constexpr int kIdsChainWavesPerSimd = 6;     // ids_chain_kernel: 76 VGPRs, 18 KB of LDS (the compiler drops follow_chain's record, which the
+                                             // kernel never reads): register-bound at aov_centre_chain_kernel's 6
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
 
 // spill (every launcher): blocks * 4 waves x S.stackSpill entries x 64 lanes, or NULL for a scene whose stack never leaves the LDS.
@@ -43,5 +46,9 @@ hipError_t launch_motion(const DeviceScene& S, const void* tris, const void* pos
 hipError_t launch_motion_chain(const DeviceScene& S, const void* tris, const void* posCur, const void* posPrev, int nPos, const CamK& cam, int w,
                                int h, int maxLinks, int blocks, float4* albedo, float4* normalDepth, float* links, float4* motion, int32_t* spill,
                                hipStream_t stream);
+// pt_ids.hip: the first-hit kernel for maxLinks 0, else the chain kernel. xy NULL: the w x h tile map, hit NULL. xy set: nPick pixels,
+// one lane each, ids and hit indexed by entry.
+hipError_t launch_ids(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, const int32_t* xy, int nPick, int blocks, int4* ids,
+                      float4* hit, int32_t* spill, hipStream_t stream);
 
 }  // namespace pt

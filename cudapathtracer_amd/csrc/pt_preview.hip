@@ -32,7 +32,9 @@
 //             pt_temporal_accumulate_respond_device, with the same frame form and motion buffer.
 //   filter    pt_denoise_hist_device on the new history, or on the upsampled frame of a scaled frame with temporal 0; filter 0 gives
 //             it no iterations. A plain frame with temporal 0: pt_denoise_var_device on S and Q, or with filter 0 nothing.
-//   resolve   pt_resolve_device of the filtered frame as a mean, or of S with the frame's spp where nothing filtered.
+//   resolve   pt_resolve_device of the filtered frame as a mean, or of S with the frame's spp where nothing filtered. With a selection
+//             (pt_preview_set_selection): pt_render_ids_device at display size if the session's ID buffer is stale (ids_stale), then
+//             pt_select_overlay_device on the frame's bytes.
 #include <cmath>
 #include <cstring>
 
@@ -45,6 +47,7 @@ namespace pt {
 
 int check_converge_params(const char* fn, const pt_converge_params& P);       // pt_converge.hip
 int check_respond_params(const char* fn, const pt_respond_params& R);         // pt_temporal.hip
+int check_select_entries(const char* fn, int n, const pt_select_entry* e);    // pt_select.hip
 
 // novum_host.cpp's clamp01, aces and to_byte, operation for operation (-ffp-contract=off: nothing fuses).
 __device__ inline float rs_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
@@ -150,12 +153,28 @@ struct pt_preview {
     bool respond;                         // frames with a history accumulate through pt_temporal_accumulate_respond_device
     pt_respond_params R;
     char* respondWs;                      // its workspace (its own allocation, made when respond is first turned on)
+    // selection (pt_preview_set_selection): the entries the overlay draws, and the ID buffer they are drawn from with what it was
+    // traced for. The buffer is traced again only when a frame finds it stale: none yet (idsValid false: also after a reset,
+    // pt_preview_scene_changed or a frame that failed after tracing it), or another camera, scene generation or max_links.
+    int selN;
+    pt_select_entry sel[4];
+    int selLinks;
+    char* ids;                            // w*h int32x4 (its own allocation, made when a selection is first set)
+    bool idsValid;
+    pt_camera idsCam;
+    int idsGen, idsLinks;
+    int idPasses;                         // ID-pass launches of all good frames
 };
 
 static size_t tile_count(int w, int h) { return (size_t)((w + 7) / 8) * ((h + 7) / 8); }       // 8x8 tiles, as the tile maps count them
 
 // The next frame is a first frame.
 static void drop_history(pt_preview* p) { p->haveHist = p->haveFrame = p->haveTiles = false; }
+
+// Whether a frame with camera `cam` at scene generation `gen` has to trace the ID buffer again.
+static bool ids_stale(const pt_preview* p, const pt_camera* cam, int gen) {
+    return !p->idsValid || gen != p->idsGen || p->selLinks != p->idsLinks || memcmp(cam, &p->idsCam, sizeof(pt_camera)) != 0;
+}
 
 // A buffer of its own that the session allocates when an option first needs it, or needs it larger: the one in *slot is freed only
 // once the new one exists, so a failure changes nothing (and the caller reports -2). No frame is in flight: pt_preview_frame blocks.
@@ -219,6 +238,7 @@ void pt_preview_destroy(pt_preview* p) {
     if (p->tiles) (void)hipFree(p->tiles);
     if (p->M) (void)hipFree(p->M);
     if (p->respondWs) (void)hipFree(p->respondWs);
+    if (p->ids) (void)hipFree(p->ids);
     delete p;
 }
 
@@ -269,6 +289,7 @@ pt_preview* pt_preview_create(pt_scene* scene, int w, int h, const pt_preview_pa
 int pt_preview_reset(pt_preview* p) {
     if (!p) return postfx_fail(-1, "pt_preview_reset: null session");
     drop_history(p);
+    p->idsValid = false;
     return 0;
 }
 
@@ -277,6 +298,7 @@ int pt_preview_scene_changed(pt_preview* p, int keep_history) {
     if (keep_history != 0 && keep_history != 1) return postfx_fail(-1, "pt_preview_scene_changed: keep_history %d must be 0 or 1", keep_history);
     if (!keep_history) drop_history(p);
     p->sceneChanged = true;
+    p->idsValid = false;
     return 0;
 }
 
@@ -404,6 +426,7 @@ struct FramePlan {
                                           // frame's guide and the previous frame's at once
     int live;                             // found: the tiles the frame rendered (all of them unless it converges)
     int passes;                           // found: its feature-pass launches
+    bool idsTrace;                        // a selection is set and the ID buffer is stale: the frame traces it before the overlay
 };
 
 // A feature pass of a frame: the first-hit pass, or the chain pass when the session has a guide chain; with centre guides the
@@ -529,6 +552,11 @@ static int preview_stages(pt_preview* p, const pt_camera* cam, uint64_t seed, Fr
 
     POSTFX_HIP_OK(hipEventRecord(p->ev[4], st));
     if (int r = pt_resolve_device(w, h, shown, shownSpp, nullptr, &P.resolve_params, p->rgba8, p->mean, st)) return r;
+    if (p->selN > 0) {
+        if (f.idsTrace)
+            if (int r = pt_render_ids_device(p->scene, cam, w, h, p->selLinks, p->ids, st)) return r;
+        if (int r = pt_select_overlay_device(w, h, p->ids, p->selN, p->sel, p->rgba8, st)) return r;
+    }
     POSTFX_HIP_OK(hipEventRecord(p->ev[5], st));
     return 0;
 }
@@ -554,6 +582,8 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     f.gn = f.reuse ? p->curG : (p->P.temporal ? p->curG ^ 1 : 0);
     // the feature pass writes A, of which there is one: the one thing a frame that then fails has done to the session
     if (!f.reuse) p->guideFresh = false;
+    f.idsTrace = p->selN > 0 && ids_stale(p, cam, f.gen);
+    if (f.idsTrace) p->idsValid = false;   // (as the guide: a frame that fails after tracing it leaves no buffer to trust)
     const int r = preview_stages(p, cam, seed, f);
     const hipError_t e = hipStreamSynchronize(p->stream);  // also after a failed stage: nothing of this frame is left in flight
     if (r) return r;                                       // (the stage's message stands; cur and the previous camera do too)
@@ -566,6 +596,7 @@ int pt_preview_frame(pt_preview* p, const pt_camera* cam, uint64_t seed) {
     p->curG = f.gn;
     p->guideFresh = true;
     p->guidePasses += f.passes;
+    if (f.idsTrace) { p->idsValid = true; p->idsCam = *cam; p->idsGen = f.gen; p->idsLinks = p->selLinks; p->idPasses++; }
     p->haveHist = p->P.temporal != 0;
     p->haveFrame = true;
     p->prevCam = *cam;
@@ -592,6 +623,37 @@ int pt_preview_read(pt_preview* p, uint8_t* rgba8, float* mean, float* hist, flo
 
 const void* pt_preview_device_rgba8(pt_preview* p) { return p ? p->rgba8 : nullptr; }
 const void* pt_preview_device_mean(pt_preview* p) { return p ? p->mean : nullptr; }
+
+int pt_preview_set_selection(pt_preview* p, int n, const pt_select_entry* e, int max_links) {
+    const char* fn = "pt_preview_set_selection";
+    if (!p) return postfx_fail_fn(-1, fn, "null session");
+    if (max_links < 0 || max_links > 16) return postfx_fail_fn(-1, fn, "max_links %d must be 0..16", max_links);
+    if (int r = check_select_entries(fn, n, e)) return r;
+    if (n > 0 && !p->ids && !session_alloc(&p->ids, (size_t)p->w * p->h * 16)) return postfx_fail_fn(-2, fn, "could not allocate the ID buffer");
+    p->selN = n;                          // (no reset: nothing but the frame's bytes depends on it)
+    for (int i = 0; i < n; i++) p->sel[i] = e[i];
+    if (n > 0) p->selLinks = max_links;
+    return 0;
+}
+
+int pt_preview_pick(pt_preview* p, int x, int y, int max_links, int32_t out_ids[4], float out_hit[4]) {
+    if (!p) return postfx_fail(-1, "pt_preview_pick: null session");
+    if (!p->haveFrame) return postfx_fail(-1, "pt_preview_pick: no frame since the session was created or reset");
+    const int32_t xy[2] = {x, y};
+    return pt_pick(p->scene, &p->prevCam, p->w, p->h, 1, xy, max_links, out_ids, out_hit);     // (the last good frame's camera, at display size)
+}
+
+int pt_preview_read_ids(pt_preview* p, int32_t* out) {
+    if (!p) return postfx_fail(-1, "pt_preview_read_ids: null session");
+    if (!out) return postfx_fail(-1, "pt_preview_read_ids: null output");
+    if (!p->ids || !p->idsValid) return postfx_fail(-1, "pt_preview_read_ids: no frame with a selection since the ID buffer was last dropped");
+    POSTFX_HIP_OK(hipMemcpy(out, p->ids, (size_t)p->w * p->h * 16, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+const void* pt_preview_device_ids(pt_preview* p) { return p ? p->ids : nullptr; }
+
+int pt_preview_id_passes(pt_preview* p) { return p ? p->idPasses : postfx_fail(-1, "pt_preview_id_passes: null session"); }
 
 int pt_preview_last_stats(pt_preview* p, pt_preview_stats* out) {
     if (!p || !out) return postfx_fail(-1, "pt_preview_last_stats: null argument");

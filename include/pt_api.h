@@ -1182,6 +1182,66 @@ int pt_temporal_accumulate_respond_device(int w, int h, const pt_camera* cam, co
 int  pt_preview_set_respond(pt_preview* p, const pt_respond_params* params);
 int  pt_preview_respond(pt_preview* p, pt_respond_params* out);
 
+/* ---- picking: per-pixel IDs, pick queries and a selection overlay ------- */
+/* pt_render_ids: WHICH surface the centre guides show at each pixel, as the indices the edit calls take. Per pixel the pass follows
+ * the one unjittered pinhole ray of pt_render_aovs_centre (no RNG, no seed) and writes one int32x4:
+ *   [0] tri       index into the description's triangle array
+ *   [1] material  the row pt_scene_update_materials replaces
+ *   [2] light     the index pt_scene_update_emission takes, or -1 for a triangle that is no light
+ *   [3] info      bit 0: the surface is seen from its back; bits 8 and up: the number of links followed to reach it
+ * A miss writes (-1, -1, -1, 0). max_links 0 reports the first hit; max_links 1..16 follows the ray through delta mirrors and smooth
+ * dielectrics exactly as pt_render_aovs_centre(max_links) does and reports THE SURFACE WHOSE RECORD THE GUIDES HOLD: the first
+ * non-specular surface, or, where the chain leaves the scene after the first hit or reaches max_links on a specular surface, the
+ * first hit, whose albedo the guide shows there (info then counts 0 links). What the guide shows is what is picked.
+ * Like the other feature passes this one touches no RNG state, accumulator or counter of the scene and may run between the chunks
+ * of a render. Arguments are checked before any HIP call, -1 with a message that names pt_render_ids: max_links, the size, the
+ * camera (its w, h must be the image's), the output, the scene; the device check comes last. */
+int pt_render_ids(pt_scene* scene, const pt_camera* camera, int w, int h, int max_links, int32_t* out_ids /* w*h*4 */);       /* host, blocking */
+int pt_render_ids_device(pt_scene* scene, const pt_camera* camera, int w, int h, int max_links, void* d_ids, void* stream);   /* async */
+/* pt_pick: the same kernels on a list of n >= 1 pixels xy[k] = (x, y), one lane per pixel. out_ids[k] is pt_render_ids's pixel bit
+ * for bit. out_hit[k] = (point.xyz, depth): the reported surface's point (ray origin + t * direction of the ray that reached it) and
+ * the chain's summed path length, which is normal_depth.w of pt_render_aovs_centre(max_links) at that pixel bit for bit: what a
+ * viewer sets focal_dist to on click-to-focus. A miss writes four zeros. Blocking. The checks of pt_render_ids under pt_pick's name,
+ * and: n, the list, both outputs, and every pixel inside [0, w) x [0, h): -1 before any HIP call, nothing written. */
+int pt_pick(pt_scene* scene, const pt_camera* camera, int w, int h, int n, const int32_t* xy /* n*2 */, int max_links,
+            int32_t* out_ids /* n*4 */, float* out_hit /* n*4 */);
+/* pt_select_overlay: up to four selections drawn onto display bytes (pt_resolve's rgba8) from an ID buffer, in place. Integer
+ * arithmetic only: the host form, the device form and tests/ids_ref.py agree in every byte. Entries apply in order. For entry e a
+ * pixel p is SELECTED if lo <= ids_p[component] <= hi. A selected pixel is an OUTLINE pixel if some pixel INSIDE THE IMAGE in the
+ * (2 radius + 1)^2 window around it is not selected, else a FILL pixel; the outline lies inside the selection, and there is none
+ * along the frame. Per colour byte out = (in * (255 - a) + colour * a + 127) / 255 with a = colour[3] on the outline and fill_alpha
+ * on the fill; the fourth byte and every unselected pixel stay as they are; n = 0 writes nothing (entries may be NULL).
+ * Checked before any HIP call (-1): the size, NULL buffers, n 0..4, NULL entries, component 0..2, 0 <= lo <= hi, radius 1..4,
+ * fill_alpha 0..255, and ids overlapping rgba8. */
+typedef struct pt_select_entry {
+    int32_t component;      /* 0 tri, 1 material, 2 light */
+    int32_t lo, hi;         /* inclusive id range, 0 <= lo <= hi (a triangle range is an object) */
+    uint8_t colour[4];      /* r, g, b, outline alpha */
+    int32_t radius;         /* 1..4 */
+    int32_t fill_alpha;     /* 0..255, 0 = no tint */
+} pt_select_entry;
+int pt_select_overlay(int w, int h, const int32_t* ids, int n /* 0..4 */, const pt_select_entry* e, uint8_t* rgba8 /* in place */);   /* host, blocking */
+int pt_select_overlay_device(int w, int h, const void* d_ids, int n, const pt_select_entry* e, void* d_rgba8, void* stream);          /* async */
+/* The session. pt_preview_set_selection(p, n, e, max_links): n = 0 (the default) turns the selection off and gives the frames of
+ * "preview" bit for bit; n = 1..4 entries (checked as pt_select_overlay checks them) make every frame end with
+ * pt_select_overlay_device on its rgba8, after pt_resolve_device. The ID buffer the overlay reads is the session's own, w*h int32x4
+ * at display size at any render scale, allocated by the first call with n > 0 (-2 if that fails, the state unchanged) and traced by
+ * pt_render_ids_device(the frame's camera, max_links) on the session's stream ONLY WHEN IT IS STALE: there is none yet, the camera's
+ * bytes, pt_scene_generation or max_links differ from those it was traced with, the session was reset, pt_preview_scene_changed was
+ * called, or a frame failed after tracing it. A resting camera on an unchanged scene traces it once; pt_preview_id_passes counts
+ * the launches of all good frames (-1 on NULL). Nothing but rgba8 depends on the selection: mean, the history, the tile outputs,
+ * pt_preview_guide_passes and the layout of pt_preview_stats (resolve_ms covers the ID pass and the overlay) are unchanged, and no
+ * call here resets the session.
+ * pt_preview_pick: pt_pick of one pixel with the last good frame's camera at display size; -1 before the first good frame (and
+ * after a reset), or with the pixel outside the session's size. pt_preview_read_ids copies the ID buffer to the host (-1 while
+ * there is no valid one); pt_preview_device_ids is the buffer itself, valid until the session is destroyed (NULL before the first
+ * selection). */
+int  pt_preview_set_selection(pt_preview* p, int n, const pt_select_entry* e, int max_links);
+int  pt_preview_pick(pt_preview* p, int x, int y, int max_links, int32_t out_ids[4], float out_hit[4]);
+int  pt_preview_read_ids(pt_preview* p, int32_t* out /* w*h*4 */);
+const void* pt_preview_device_ids(pt_preview* p);
+int  pt_preview_id_passes(pt_preview* p);
+
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
  * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */
