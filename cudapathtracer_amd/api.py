@@ -339,8 +339,8 @@ def _check(rc, what):
 
 
 def has_experimental():
-    """True if libptamd.so was built with EXPERIMENTAL=1 (the A/B variants of DESIGN.md §6: options wide, compact, spec,
-    defer_shadow, xcd_bands, refill = 2). The default library refuses those options with -3."""
+    """Always False: the A/B variants of DESIGN.md §6 (options wide, compact, spec, defer_shadow, xcd_bands, refill = 2) were
+    removed, and the library refuses those options with -3. Kept for callers that ask."""
     return bool(lib().pt_has_experimental())
 
 

@@ -58,10 +58,8 @@ struct DevBuf {
 
 struct pt_scene {
     int device = 0;
-    DevBuf nodes, tris, attrs, lights, mats, textures, jump, totals, leaves, wnodes, qnodes, leafBox, mids;
-    bool compactTried = false, compactOk = false, compactWanted = false;
-    int wfWideWg = 1;                                                                 // wavefront trace kernel: 16-wave workgroups for scenes in HBM ("wf_wide_wg")   // 32-byte quantised nodes of trace_resume_q ("compact" 1)
-    int nWide = 0, wideStackNeed = 0; bool wideTried = false, wideWanted = false;   // the 4-wide collapsed tree of trace_resume_w4 ("wide" 1: opt-in, measured slower)
+    DevBuf nodes, tris, attrs, lights, mats, textures, jump, totals, leaves;
+    int wfWideWg = 1;                                 // wavefront trace kernel: 16-wave workgroups for scenes in HBM ("wf_wide_wg")
     int nLeaves = 0;                                  // FLAT scenes: the leaf table (pt_trace.h: visited(leaf) == slab(leaf's own box))
     DevBuf rng, spill, tilebuf, colors, pixcnt, queue, left; // work buffers, grown on demand
     DevBuf wfState, wfCtl, wfCtr, wfSpill;            // wavefront variant
@@ -76,26 +74,26 @@ struct pt_scene {
     int stackNeed = 0, nInternal = 0, cacheNodes = 0, cacheTris = 0;
     int nMats = 0, nLightsPacked = 0, nTexels = 0;
     bool armless = false;        // a triangle uses a material type without a dispatch arm (pt_path.h): DEFER is not exact
-    // Everything below is set per scene through pt_set_option (names in quotes); the library reads no environment variable.
+    // Everything below is set per scene through pt_set_option (names in quotes; kOptions stores into the int members by
+    // pointer-to-member, so an option's switch is an int); the library reads no environment variable.
     int schedMask = 31;          // "sched_mask": scheduling checks every schedMask + 1 bounce iterations (tests use 3)
-    bool sliceAlways = true;     // "slice_always" 0: slices only once no fresh tile is left
+    int sliceAlways = 1;         // "slice_always" 0: slices only once no fresh tile is left
     bool wavesHbmOk = PT_WAVES_HBM > 0;   // "waves_hbm" 0: scenes in HBM use the 4-waves-per-SIMD kernel too (A/B)
     int nodeKeep = 10, triKeep = 8;        // "node_keep" / "tri_keep" (pt_trace.h: LoopExit)
-    int spec = 2;                          // -DPT_SPEC=1 builds only (A/B): speculative descent for shadow rays too (2) or closest-hit rays only (1)
     int refill = 1, refillKeep = 6;       // "refill" / "refill_keep": REFILL instantiation of the kernel for scenes in HBM (pt_trace.h: trace_resume)
     bool refillKeepSet = false;           // (unset: the 4-wave kernel of small shares uses kRefillKeepSmall — it is chain-bound and wants its lanes back sooner)
-    bool cull = false;                    // pt_set_culling / "culling": opt-in, not parity-exact by construction
+    int cull = 0;                         // pt_set_culling / "culling": opt-in, not parity-exact by construction
     unsigned long long lightTri8 = 0ull;          // a byte per light, for the first 8: 1 + the packed triangle the light is, 0 = none (light_triangles); KParams::lightTri8
-    bool leafBoxes = true;                        // "leaf_boxes" 0: the FLAT kernels walk the nodes in lockstep instead of testing the leaves' own boxes (A/B)
+    int leafBoxes = 1;                            // "leaf_boxes" 0: the FLAT kernels walk the nodes in lockstep instead of testing the leaves' own boxes (A/B)
     int flat2Wanted = 1; int lastLaunchFlat2 = 0;   // "flat2" 1 (default): SIMPLE FLAT scenes trace shadow + extension ray in one FLAT pass (DEFER logic step)
     bool noLeafTris = false;                      // no triangle carries a MAT_LEAF material: a shadow ray is occluded by any hit (order-free)
     int queueTimeoutMs = 30000;                   // "queue_timeout_ms": how long a wait on the tile queue may see no progress (tests use 0-1 to exercise the give-up path)
     int queueStalls = 0;                          // launches whose waiters gave up (q[3] != 0) although every tile was finished: not an error, counted (pt_queue_stalls)
-    bool leanOk = false, leanWanted = true;       // scene qualifies for the LEAN generic bounce (no MAT_LEAF triangle, no texture / transmission map on any triangle's material) / "lean" 0 turns it off (A/B)
+    bool leanOk = false; int leanWanted = 1;      // scene qualifies for the LEAN generic bounce (no MAT_LEAF triangle, no texture / transmission map on any triangle's material) / "lean" 0 turns it off (A/B)
     int lastLaunchLean = 0;
-    bool momentsFused = false;                    // "moments_fused" 1: pt_render_moments* renders all its samples in one launch that keeps Q itself, where the kernel has a fused twin
+    int momentsFused = 0;                         // "moments_fused" 1: pt_render_moments* renders all its samples in one launch that keeps Q itself, where the kernel has a fused twin
     int lastMomentsLaunches = -1;                 // render launches of the last pt_render_moments* call (pt_last_moments_launches; -1: none yet)
-    bool simpleOk = false, simpleWanted = true;   // scene qualifies for the SIMPLE bounce (diffuse-only, pt_path.h) / "simple" 0 turns it off (A/B)
+    bool simpleOk = false; int simpleWanted = 1;  // scene qualifies for the SIMPLE bounce (diffuse-only, pt_path.h) / "simple" 0 turns it off (A/B)
     bool flatOk = false; int flatWanted = 1;      // "flat": 0 off, 1 (or 2) on: scenes of at most 128 nodes / triangles (64- or 128-bit masks)   // scene qualifies for the FLAT kernels (checked in repack) / "flat" 0 turns them off (A/B)
     int lastLaunchFlat = 0, lastLaunchSimple = 0, lastLaunchLeafTable = 0;
     bool lastLaunchQueued = false;        // the last megakernel launch used the tile queue (only then is its error word that launch's)
@@ -104,13 +102,11 @@ struct pt_scene {
     int lastLaunchRefill = 0;             // ... and whether it was a REFILL instantiation
     int lastLaunchHbm = -1;               // which megakernel the last launch used (-1: none yet)
     bool wavesHbmForce = false;           // "waves_hbm" 2: ... and the 6-wave kernel whatever the tile count (tests)
-    bool onchipOk = true;        // "onchip" 0: never pick the LDS-only kernel instantiation (A/B)
+    int onchipOk = 1;            // "onchip" 0: never pick the LDS-only kernel instantiation (A/B)
     int nTrisPacked = 0;
     int sliceIters = 512;        // "slice_iters": time slice of the tile queue (0 = off)
     int lptPrio = 2;             // "lpt_prio": 0 no issue-priority steering, 1 once no fresh tile is left, 2 always (A/B)
-    bool persistent = true;      // "persistent" 0: one tile per wave, workgroups launched per 4 tiles (A/B)
-    bool xcdBands = false;       // "xcd_bands" 1: one contiguous band of tiles per XCD (A/B; loses to interleaving)
-    bool deferShadow = false;    // "defer_shadow" 1: megakernel traces shadow + extension ray as a pair (A/B; slower)
+    int persistent = 1;          // "persistent" 0: one tile per wave, workgroups launched per 4 tiles (A/B)
     // dynamic geometry (pt_scene_update_*): what the device builder packs from, kept on the device; the spare halves an update builds
     // into and swaps in on success; the builder's pool (grown on demand, freed at destroy)
     int generation = 0;                   // pt_scene_generation: +1 per successful update
@@ -159,7 +155,7 @@ static bool scene_onchip(const pt_scene* s) { return scene_onchip_wg(s) > 0; }
 // shard 602 vs 518 ms on the 263 k-triangle scene). The SIMPLE kernel's eight waves pay from ~3/4 of its 8192 slots on — a 1/4 share of
 // a 1080p frame: 201 vs 269 ms — the generic kernel's six from 5/4 of its 6144 (profiles/r02_sched_shards.log).
 static bool hbm_kernel_pays(const pt_scene* s, bool simple, long long tiles) {
-    if (scene_onchip(s) || (s->deferShadow && !s->armless) || !s->wavesHbmOk) return false;
+    if (scene_onchip(s) || !s->wavesHbmOk) return false;
     const long long slots = (long long)s->numCU * 4 * (simple ? kWavesHbmSimple : kWavesHbm);
     return s->wavesHbmForce || tiles * 4 >= slots * (simple ? 3 : 5);
 }
@@ -180,7 +176,7 @@ int pt_device_count(void) {
 
 void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
-    DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves, &s->wnodes, &s->qnodes, &s->leafBox, &s->mids,
+    DevBuf* all[] = {&s->nodes, &s->tris, &s->attrs, &s->lights, &s->mats, &s->textures, &s->jump, &s->totals, &s->leaves,
                      &s->rng, &s->spill, &s->tilebuf, &s->colors, &s->pixcnt, &s->queue, &s->left, &s->wfState, &s->wfCtl, &s->wfCtr, &s->wfSpill,
                      &s->aovSpill, &s->aovOut, &s->adS, &s->adM, &s->adH, &s->adList, &s->adKeep, &s->adCount, &s->adOut, &s->adSpp, &s->adErr,
                      &s->adP, &s->adQ, &s->adSq,
@@ -202,8 +198,8 @@ static int upload(DevBuf& b, const void* src, size_t bytes) {
     return 0;
 }
 
-// The leaf table of the FLAT kernels (and the opt-in trees of EXPERIMENTAL builds) replace the reference's root-to-leaf box
-// walk by a test of each leaf's OWN box. That equals the reference's visiting set only if every box contains the boxes
+// The leaf table of the FLAT kernels replaces the reference's root-to-leaf box walk by a test of each leaf's OWN box.
+// That equals the reference's visiting set only if every box contains the boxes
 // below it and no box holds a NaN or an infinity (pt_trace.h: inv_is_regular and the monotonicity argument above it). The
 // reference's builder nests exactly (a parent's box is the float-wise min / max of its children's, main.cu:20-233), but
 // pt_scene_create also takes a caller's own BVH arrays — a refit, loose or corrupt tree must fall back to the walk that
@@ -709,9 +705,6 @@ static void adopt_geometry(pt_scene* s, pt_scene& t, bool mesh, bool normals) {
     s->stackNeed = t.stackNeed; s->nInternal = t.nInternal; s->cacheNodes = t.cacheNodes; s->cacheTris = t.cacheTris;
     s->nMats = t.nMats; s->nLightsPacked = t.nLightsPacked; s->nTrisPacked = t.nTrisPacked; s->nLeaves = t.nLeaves; s->lightTri8 = t.lightTri8;
     s->armless = t.armless; s->simpleOk = t.simpleOk; s->noLeafTris = t.noLeafTris; s->leanOk = t.leanOk; s->flatOk = t.flatOk;
-    // the opt-in trees of EXPERIMENTAL builds were the old geometry's: dropped, and built again on demand
-    s->wnodes.release(); s->qnodes.release(); s->leafBox.release(); s->mids.release();
-    s->compactTried = s->compactOk = s->wideTried = false; s->nWide = 0; s->wideStackNeed = 0;
     // pt_scene_flags describes the last launch: there is none on this geometry yet
     s->lastLaunchFlat = s->lastLaunchSimple = s->lastLaunchLeafTable = s->lastLaunchFlat2 = s->lastLaunchLean = s->lastLaunchRefill = 0;
     s->lastLaunchHbm = -1;
@@ -1031,181 +1024,6 @@ static int render_tiles_wavefront(pt_scene* s, const pt_camera* cam, int w, int 
     return 0;
 }
 
-#ifdef PT_EXPERIMENTAL
-// The reference tree collapsed to 4-wide nodes for trace_resume_w4 (pt_trace_experimental.h): same leaves, same float boxes, half the
-// levels. Built once per scene from the packed binary records (whoever packed them, host or device), numbered breadth-first
-// so that the first K wide nodes are the top of the tree (the LDS scene cache). A slot takes the place of an internal child
-// by that child's two children — the child with the largest box first — until the node has four slots or only leaves.
-static int ensure_wide(pt_scene* s) {
-    if (s->wideTried) return 0;
-    s->wideTried = true;
-    const int nI = s->nInternal;
-    if (nI <= 0 || s->ds.rootRef != 0) return 0;
-    std::vector<PNode> pn((size_t)nI);
-    HIP_OK(hipMemcpy(pn.data(), s->nodes.p, (size_t)nI * sizeof(PNode), hipMemcpyDeviceToHost));
-    if (!boxes_nested_and_finite(pn, nI)) return 0;                    // a caller's loose tree: the reference's walk (nWide stays 0)
-    struct Slot { float mn[3], mx[3]; int32_t ref; };
-    auto area = [](const Slot& b) { const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2]; return dx * dy + dy * dz + dz * dx; };
-    auto children = [&](int32_t node, Slot out[2]) {
-        const PNode& p = pn[node];
-        for (int a = 0; a < 3; a++) { out[0].mn[a] = p.lmin[a]; out[0].mx[a] = p.lmax[a]; out[1].mn[a] = p.rmin[a]; out[1].mx[a] = p.rmax[a]; }
-        out[0].ref = p.left; out[1].ref = p.right;
-    };
-    std::vector<WNode> wn;
-    std::vector<int32_t> binaryOf;                    // wide node -> the binary node it was collapsed from
-    std::vector<int> need;                            // stack entries a traversal can hold below this node (filled bottom-up)
-    binaryOf.push_back(0);
-    for (size_t w = 0; w < binaryOf.size(); w++) {    // breadth-first: a wide node's internal slots are appended as they are met
-        Slot sl[4]; int n = 2;
-        children(binaryOf[w], sl);
-        while (n < 4) {
-            int best = -1; float bestA = -1.0f;
-            for (int i = 0; i < n; i++) if (sl[i].ref >= 0) { const float a = area(sl[i]); if (a > bestA) { bestA = a; best = i; } }
-            if (best < 0) break;
-            Slot two[2];
-            children(sl[best].ref, two);
-            sl[best] = two[0]; sl[n++] = two[1];
-        }
-        WNode W;
-        std::memset(&W, 0, sizeof(W));
-        for (int i = 0; i < 4; i++) {
-            if (i < n) {
-                W.mnx[i] = sl[i].mn[0]; W.mny[i] = sl[i].mn[1]; W.mnz[i] = sl[i].mn[2];
-                W.mxx[i] = sl[i].mx[0]; W.mxy[i] = sl[i].mx[1]; W.mxz[i] = sl[i].mx[2];
-                if (sl[i].ref >= 0) { W.ref[i] = (int32_t)binaryOf.size(); binaryOf.push_back(sl[i].ref); }
-                else W.ref[i] = sl[i].ref;
-            } else W.ref[i] = kRefNone;
-        }
-        W.pad[0] = n;
-        wn.push_back(W);
-        if (binaryOf.size() > (size_t)nI + 1) return fail(-1, "wide collapse: the packed tree is not a tree");
-    }
-    need.assign(wn.size(), 0);
-    int worst = 0;
-    for (int w = (int)wn.size() - 1; w >= 0; w--) {   // children come after their parent: bottom-up
-        int below = 0;
-        for (int i = 0; i < 4; i++) if (wn[w].ref[i] >= 0) below = std::max(below, need[wn[w].ref[i]]);
-        need[w] = (wn[w].pad[0] - 1) + below;         // the other slots wait on the stack while one is descended into
-        worst = std::max(worst, need[w]);
-    }
-#if PT_NODE_ORDER_AREA
-    // as for the binary nodes: the LDS copy holds wide nodes [0, K) — number them by the area of their own box (the slot box in
-    // their parent), root first, so that K most-visited ones are cached
-    if (wn.size() > 128) {
-        const int nW = (int)wn.size();
-        std::vector<float> area((size_t)nW, 0.0f);
-        for (int w = 0; w < nW; w++)
-            for (int i = 0; i < 4; i++) {
-                const int32_t c = wn[w].ref[i];
-                if (c < 0 || c >= nW) continue;
-                const float dx = wn[w].mxx[i] - wn[w].mnx[i], dy = wn[w].mxy[i] - wn[w].mny[i], dz = wn[w].mxz[i] - wn[w].mnz[i];
-                const float a = dx * dy + dy * dz + dz * dx;
-                area[c] = std::isfinite(a) ? a : 0.0f;
-            }
-        std::vector<int> order((size_t)nW);
-        for (int w = 0; w < nW; w++) order[w] = w;
-        std::stable_sort(order.begin() + 1, order.end(), [&](int a, int b) { return area[a] > area[b]; });
-        std::vector<int> rank((size_t)nW);
-        for (int k = 0; k < nW; k++) rank[order[k]] = k;
-        std::vector<WNode> out((size_t)nW);
-        for (int w = 0; w < nW; w++) {
-            WNode x = wn[w];
-            for (int i = 0; i < 4; i++) if (x.ref[i] >= 0 && x.ref[i] < nW) x.ref[i] = rank[x.ref[i]];
-            out[rank[w]] = x;
-        }
-        wn.swap(out);
-    }
-#endif
-    if (int r = upload(s->wnodes, wn.data(), wn.size() * sizeof(WNode))) return r;
-    s->nWide = (int)wn.size(); s->wideStackNeed = worst;
-    return 0;
-}
-
-// The compact form of the tree for trace_resume_q (pt_trace.h), built once per scene from the packed binary records: per
-// internal node a QNode (both child boxes as 8-bit offsets in the node's own frame, rounded OUTWARD with the very fmaf the
-// kernel decodes with), per leaf its exact float box (at the index of its first packed triangle) and per internal node the
-// first triangle of its right subtree (the tie rule's walk).
-static int ensure_compact(pt_scene* s) {
-    if (s->compactTried) return 0;
-    s->compactTried = true;
-    const int nI = s->nInternal, nT = s->nTrisPacked;
-    if (nI <= 0 || s->ds.rootRef != 0 || nI >= (1 << 24) || nT >= (1 << 24)) return 0;
-    std::vector<PNode> pn((size_t)nI);
-    HIP_OK(hipMemcpy(pn.data(), s->nodes.p, (size_t)nI * sizeof(PNode), hipMemcpyDeviceToHost));
-    if (!boxes_nested_and_finite(pn, nI)) return 0;                    // a caller's loose tree: the reference's walk (compactOk stays false)
-    std::vector<QNode> qn((size_t)nI);
-    std::vector<float> lb((size_t)nT * 8, 0.0f);                   // two 16-byte halves per packed triangle index; filled at the first of each leaf
-    std::vector<int32_t> mids((size_t)nI, 0), minFirst((size_t)nI, 0), maxFirst((size_t)nI, 0);
-    bool ok = true;
-    for (int i = nI - 1; i >= 0 && ok; i--) {                      // children come after their parent (breadth-first numbering): bottom-up
-        const PNode& p = pn[i];
-        QNode& q = qn[i];
-        float org[3], ext = 0.0f;
-        for (int a = 0; a < 3 && ok; a++) {
-            ok = std::isfinite(p.lmin[a]) && std::isfinite(p.lmax[a]) && std::isfinite(p.rmin[a]) && std::isfinite(p.rmax[a]);
-            org[a] = std::min(p.lmin[a], p.rmin[a]);
-            ext = std::max(ext, std::max(p.lmax[a], p.rmax[a]) - org[a]);
-        }
-        if (!ok) break;
-        int k = -64;                                               // step 2^k: the smallest with fma(255, 2^k, origin) >= the node's maximum on every axis
-        if (ext > 0.0f) { int e; std::frexp(ext / 255.0f, &e); k = std::max(e - 1, -64); }
-        for (; k <= 63; k++) {
-            const float sc = std::ldexp(1.0f, k);
-            bool fits = true;
-            for (int a = 0; a < 3; a++) fits = fits && std::fmaf(255.0f, sc, org[a]) >= std::max(p.lmax[a], p.rmax[a]);
-            if (fits) break;
-        }
-        if (k > 63) { ok = false; break; }
-        const float sc = std::ldexp(1.0f, k);
-        auto down = [&](float x, int a) {                          // largest q with decode(q) <= x
-            int v = (int)std::floor(((double)x - org[a]) / sc);
-            v = std::min(std::max(v, 0), 255);
-            while (v > 0 && std::fmaf((float)v, sc, org[a]) > x) v--;
-            return (uint8_t)v;
-        };
-        auto up = [&](float x, int a) {                            // smallest q with decode(q) >= x
-            int v = (int)std::ceil(((double)x - org[a]) / sc);
-            v = std::min(std::max(v, 0), 255);
-            while (v < 255 && std::fmaf((float)v, sc, org[a]) < x) v++;
-            return (uint8_t)v;
-        };
-        for (int a = 0; a < 3; a++) {
-            q.o[a] = org[a];
-            q.lmin[a] = down(p.lmin[a], a); q.lmax[a] = up(p.lmax[a], a); q.rmin[a] = down(p.rmin[a], a); q.rmax[a] = up(p.rmax[a], a);
-            auto dec = [&](uint8_t v) { return std::fmaf((float)v, sc, org[a]); };
-            ok = ok && dec(q.lmin[a]) <= p.lmin[a] && dec(q.lmax[a]) >= p.lmax[a] && dec(q.rmin[a]) <= p.rmin[a] && dec(q.rmax[a]) >= p.rmax[a];
-        }
-        int mn[2], mx[2];
-        uint32_t word[2];
-        const int32_t ref[2] = {p.left, p.right};
-        for (int c = 0; c < 2 && ok; c++) {
-            if (ref[c] >= 0) {
-                ok = ref[c] > i && ref[c] < nI;
-                if (ok) { mn[c] = minFirst[ref[c]]; mx[c] = maxFirst[ref[c]]; word[c] = (uint32_t)ref[c]; }
-            } else {
-                const int f = ~ref[c];
-                ok = ref[c] != kRefNone && f >= 0 && f < nT;
-                if (!ok) break;
-                mn[c] = mx[c] = f; word[c] = 0x80000000u | (uint32_t)f;
-                const float* bmn = c == 0 ? p.lmin : p.rmin; const float* bmx = c == 0 ? p.lmax : p.rmax;
-                float* o = &lb[(size_t)f * 8];
-                o[0] = bmn[0]; o[1] = bmn[1]; o[2] = bmn[2]; o[3] = bmx[0]; o[4] = bmx[1]; o[5] = bmx[2];
-            }
-        }
-        if (!ok) break;
-        q.left = word[0] | ((uint32_t)(k + 64) << 24); q.right = word[1];
-        ok = mx[0] < mn[1];                                        // leaf order is left to right
-        minFirst[i] = mn[0]; maxFirst[i] = mx[1]; mids[i] = mn[1];
-    }
-    if (!ok) return 0;
-    if (int r = upload(s->qnodes, qn.data(), qn.size() * sizeof(QNode))) return r;
-    if (int r = upload(s->leafBox, lb.data(), lb.size() * sizeof(float))) return r;
-    if (int r = upload(s->mids, mids.data(), mids.size() * sizeof(int32_t))) return r;
-    s->compactOk = true;
-    return 0;
-}
-#endif  // PT_EXPERIMENTAL
-
 // rng init + megakernel on `stream`; d_tiles holds t.count*64 float4.
 // List mode (list != null: adaptive sampling): t is the whole frame and the launch renders the `live` tiles that the device
 // array `list` names, through the tile queue whatever "persistent" says; the kernel is picked by `live`. The RNG states, the
@@ -1230,32 +1048,18 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     if (s->variant == 1) return render_tiles_wavefront(s, cam, w, h, spp, maxDepth, integrator, useMIS, t, d_tiles, d_pixcnt, count, stream);
     // First the selector fields of the launch, then the kernel they choose (pt_kernels.hip: megakernel_choose), then everything that is
     // sized for THAT kernel: its LDS stack length lays out the spill area, its launch bounds give the workgroup and the grid.
-    const bool deferred = s->deferShadow && !s->armless;
-    const bool onchip = scene_onchip(s) && !deferred;       // (the DEFER A/B instantiation exists for the general 4-wave kernel only)
+    const bool onchip = scene_onchip(s);
     // the SIMPLE bounce for a scene in HBM: diffuse-only scenes, timed launches with the resumable traversal
     const bool simpleTimed = s->simpleOk && s->simpleWanted && s->refill && !s->cull && !s->armless;
-    const bool simpleHbm = !onchip && !deferred && s->wavesHbmOk && simpleTimed && !count;
+    const bool simpleHbm = !onchip && s->wavesHbmOk && simpleTimed && !count;
     const bool hbm = hbm_kernel_pays(s, simpleHbm, live);
-    KParams P;
+    KParams P = {};                                         // (its padding too: pt_params.h)
     P.onchip = onchip ? 1 : 0;
     P.hbm = hbm ? 1 : 0;
-    bool wide = false, compact = false;
-#ifdef PT_EXPERIMENTAL
-    if (hbm && simpleHbm && s->wideWanted) {
-        if (int r = ensure_wide(s)) return r;
-        wide = s->nWide > 0;
-    }
-    if (hbm && simpleHbm && s->compactWanted && !wide) {
-        if (int r = ensure_compact(s)) return r;
-        compact = s->compactOk;
-    }
-#endif
-    P.wide = wide ? 1 : 0; P.compact = compact ? 1 : 0;
-    P.xcdBands = s->xcdBands ? 1 : 0;
     P.cull = (s->cull && hbm) ? 1 : 0;
-    P.refill = (s->refill && !deferred && !P.cull && !s->armless && (!onchip || s->refill == 2)) ? 1 : 0;   // 2: also the LDS-resident kernel (A/B)
+    P.refill = (s->refill && !P.cull && !s->armless && !onchip) ? 1 : 0;
     P.flat = 0;                                             // 1: FLAT with 64-bit masks, 2: with 128-bit masks
-    if (onchip && s->flatOk && s->flatWanted && !deferred && !P.refill) {
+    if (onchip && s->flatOk && s->flatWanted) {
         P.flat = (s->nInternal <= 64 && s->nTrisPacked <= 64) ? 1 : 2;     // 65..128: +17-20 % over the stack walk with the leaf-box form (profiles/r02_flat_crossover.jsonl)
     }
     // the instantiations that have the SIMPLE bounce: FLAT, the production kernel for scenes in HBM and its 4-wave form (small shares)
@@ -1264,9 +1068,9 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     // the LEAN generic bounce exists for the three timed kernels generic scenes run: the pair form of FLAT, the kernel for scenes in HBM
     // and its 4-wave form (both REFILL)
     P.lean = (s->leanOk && s->leanWanted && !s->armless && !P.simple && !count && !P.cull && (P.flat == 3 || (!onchip && P.refill))) ? 1 : 0;
-    const MkRow* row = megakernel_choose(integrator, count, !deferred, P, false);
+    const MkRow* row = megakernel_choose(integrator, count, true, P, false);      // (syncShadow: outside the pair form of FLAT no kernel defers the shadow ray)
     if (!row) return fail(-1, "render_tiles: no megakernel is built for this launch");
-    const int spillEntries = hbm ? std::max(0, (wide ? std::max(s->wideStackNeed, s->stackNeed) : s->stackNeed) - row->f.stackEntries) : s->ds.stackSpill;
+    const int spillEntries = hbm ? std::max(0, s->stackNeed - row->f.stackEntries) : s->ds.stackSpill;
     const int wgWaves = row->f.wgWaves ? row->f.wgWaves : (onchip ? scene_onchip_wg(s) : 4);
     int blocks = megakernel_blocks(t.count, wgWaves);
     if (spillEntries > 0)
@@ -1285,18 +1089,13 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.wgWaves = wgWaves;
     if (hbm && s->cacheTris == 0) P.cacheNodes = std::min(s->nInternal, (simpleHbm ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64);     // its workgroups share a larger copy of the top of the tree
     P.gnodeFrom = P.cacheNodes;
-    if (count && !onchip && !deferred && s->wavesHbmOk && s->cacheTris == 0) {
+    if (count && !onchip && s->wavesHbmOk && s->cacheTris == 0) {
         // a counting launch stands in for the timed launch of the same tiles (bench.py): count a node fetch as "global" against THAT
         // instantiation's LDS copy of the tree top — the SIMPLE production kernel holds 768 nodes, this counting kernel 704 (or 192)
         P.gnodeFrom = hbm_kernel_pays(s, simpleTimed, t.count) ? std::min(s->nInternal, (simpleTimed ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64) : s->cacheNodes;
     }
-    P.wnodes = wide ? (const WNode*)s->wnodes.p : nullptr;
-    if (wide) P.cacheNodes = 2 * std::min(s->nWide, kCacheBytesHbmSimple / 128);            // wide nodes, counted in 64-byte halves
-    P.qnodes = compact ? (const QNode*)s->qnodes.p : nullptr; P.leafBox = compact ? s->leafBox.p : nullptr; P.mids = compact ? (const int32_t*)s->mids.p : nullptr;
-    if (compact) P.cacheNodes = std::min(s->nInternal & ~1, kCacheBytesHbmSimple / 32) / 2;     // compact nodes, two per 64-byte unit
     P.S.stackSpill = spillEntries;
     P.refillKeep = (hbm || s->refillKeepSet) ? s->refillKeep : kRefillKeepSmall;      // re-swept on the round's kernels: 6 for the 8-wave kernel, 10 for the 4-wave one (1/8 shares +5.5 % / +6 %, profiles/r03_shards_hbm_final.log)
-    P.spec = s->spec;
     P.nodeKeep = s->nodeKeep; P.triKeep = s->triKeep;
     s->lastLaunchLean = P.lean;
     s->lastLaunchRefill = P.refill; s->lastLaunchFlat = (P.flat && !count) ? 1 : 0;
@@ -1308,7 +1107,7 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.queue = nullptr; P.queueMask = 0; P.left = nullptr; P.gridBlocks = 0;
     P.lptPrio = s->lptPrio; P.sliceIters = s->sliceIters; P.schedMask = s->schedMask; P.sliceAlways = s->sliceAlways ? 1 : 0;
     P.queueTimeout = (unsigned long long)s->queueTimeoutMs * 100000ull;        // ms -> ticks of the 100 MHz steady counter (hipDeviceAttributeWallClockRate)
-    if ((s->persistent && !s->xcdBands) || list) {
+    if (s->persistent || list) {
         int cap = 256;
         while (cap < t.count) cap <<= 1;
         if (int r = s->queue.ensure((size_t)(kQueueHeader + 2 * cap) * sizeof(int))) return r;
@@ -1327,7 +1126,7 @@ static int render_tiles(pt_scene* s, const pt_camera* cam, int w, int h, int spp
     P.spill = spillEntries > 0 ? (int32_t*)s->spill.p : nullptr;
     MomentsK M = {nullptr, nullptr, 0, 0.0f};
     if (fused) {
-        row = megakernel_choose(integrator, count, !deferred, P, true);     // the twin: its counterpart's facts, so everything sized above stands
+        row = megakernel_choose(integrator, count, true, P, true);     // the twin: its counterpart's facts, so everything sized above stands
         if (!row || (row->key & kMkBuiltOnly)) return 0;                    // the caller renders in batches
         M.P = fused->P; M.Q = fused->Q; M.c = fused->c; M.rc = 1.0f / (float)fused->c;
         fused->launched = true;
@@ -2033,13 +1832,7 @@ int pt_pick(pt_scene* s, const pt_camera* cam, int w, int h, int n, const int32_
     return 0;
 }
 
-int pt_has_experimental(void) {
-#ifdef PT_EXPERIMENTAL
-    return 1;
-#else
-    return 0;
-#endif
-}
+int pt_has_experimental(void) { return 0; }     // always: the experimental variants were removed; kept for callers that ask
 
 int pt_set_variant(pt_scene* s, int variant) {
     if (!s) return fail(-1, "null scene");
@@ -2125,102 +1918,76 @@ int pt_set_culling(pt_scene* s, int on) {
 // "culling" can reach the image (pt_set_culling); every other option selects between instantiations / schedules that
 // are bit-identical by construction and by test.
 namespace {
-struct OptionRef { const char* name; int lo, hi; };
-const OptionRef kOptions[] = {
-    {"flat", 0, 2}, {"onchip", 0, 1}, {"waves_hbm", 0, 2}, {"refill", 0, 2}, {"refill_keep", 0, 15}, {"node_keep", 0, 15}, {"tri_keep", 0, 15},
-    {"defer_shadow", 0, 1}, {"slice_iters", 0, 1 << 30}, {"slice_always", 0, 1}, {"sched_mask", 0, 1 << 20}, {"lpt_prio", 0, 2},
-    {"persistent", 0, 1}, {"xcd_bands", 0, 1}, {"culling", 0, 1}, {"spec", 0, 2}, {"simple", 0, 1}, {"flat2", 0, 1}, {"leaf_boxes", 0, 1}, {"wide", 0, 1},
-    {"compact", 0, 1}, {"wf_wide_wg", 0, 2}, {"lean", 0, 1}, {"queue_timeout_ms", 0, 1 << 22},
-    {"moments_fused", 0, 1},          // (new options go at the END: the experimental gate in pt_set_option indexes this table by position)
+// One row per option: its name and range, and where its value lives — an int member of pt_scene, or a set / get pair where a
+// plain store is not enough. A row with neither is an option of a variant that was removed: the name is still
+// known, and `off`, the value that meant "not that variant", is the only one it accepts and the one it reads back.
+struct Option {
+    const char* name; int lo, hi;
+    int pt_scene::*field;
+    int (*set)(pt_scene*, int);          // returns an error code
+    int (*get)(const pt_scene*);
+    int off;
 };
-int option_index(const char* name) {
-    if (!name) return -1;
-    for (size_t i = 0; i < sizeof(kOptions) / sizeof(kOptions[0]); i++) if (!strcmp(kOptions[i].name, name)) return (int)i;
-    return -1;
+int removed(const char* name, int v) {
+    return fail(-3, "pt_set_option: %s = %d selected an experimental variant that lost its measurement and was removed (DESIGN.md §6 has the results "
+                    "and the commit that last held the code)", name, v);
+}
+const Option kOptions[] = {
+    {"flat", 0, 2, &pt_scene::flatWanted}, {"onchip", 0, 1, &pt_scene::onchipOk},
+    {"waves_hbm", 0, 2, nullptr,
+     [](pt_scene* s, int v) { s->wavesHbmOk = v != 0 && PT_WAVES_HBM > 0; s->wavesHbmForce = s->wavesHbmOk && v == 2; return 0; },
+     [](const pt_scene* s) { return s->wavesHbmForce ? 2 : (s->wavesHbmOk ? 1 : 0); }},
+    {"refill", 0, 2, nullptr,            // (2 was REFILL for LDS-resident scenes: removed)
+     [](pt_scene* s, int v) { if (v == 2) return removed("refill", v); s->refill = v; return 0; },
+     [](const pt_scene* s) { return s->refill; }},
+    {"refill_keep", 0, 15, nullptr,
+     [](pt_scene* s, int v) { s->refillKeep = v; s->refillKeepSet = true; return 0; },
+     [](const pt_scene* s) { return s->refillKeep; }},
+    {"node_keep", 0, 15, &pt_scene::nodeKeep}, {"tri_keep", 0, 15, &pt_scene::triKeep},
+    {"defer_shadow", 0, 1, nullptr, nullptr, nullptr, 0},
+    {"slice_iters", 0, 1 << 30, &pt_scene::sliceIters}, {"slice_always", 0, 1, &pt_scene::sliceAlways},
+    {"sched_mask", 0, 1 << 20, nullptr,
+     [](pt_scene* s, int v) { if (((v + 1) & v) != 0) return fail(-1, "pt_set_option: sched_mask must be 2^k - 1"); s->schedMask = v; return 0; },
+     [](const pt_scene* s) { return s->schedMask; }},
+    {"lpt_prio", 0, 2, &pt_scene::lptPrio}, {"persistent", 0, 1, &pt_scene::persistent},
+    {"xcd_bands", 0, 1, nullptr, nullptr, nullptr, 0},
+    {"culling", 0, 1, &pt_scene::cull},
+    {"spec", 0, 2, nullptr, nullptr, nullptr, 2},
+    {"simple", 0, 1, &pt_scene::simpleWanted}, {"flat2", 0, 1, &pt_scene::flat2Wanted}, {"leaf_boxes", 0, 1, &pt_scene::leafBoxes},
+    {"wide", 0, 1, nullptr, nullptr, nullptr, 0}, {"compact", 0, 1, nullptr, nullptr, nullptr, 0},
+    {"wf_wide_wg", 0, 2, &pt_scene::wfWideWg}, {"lean", 0, 1, &pt_scene::leanWanted},
+    {"queue_timeout_ms", 0, 1 << 22, &pt_scene::queueTimeoutMs}, {"moments_fused", 0, 1, &pt_scene::momentsFused},
+};
+const Option* find_option(const char* name) {
+    if (name) for (const Option& o : kOptions) if (!strcmp(o.name, name)) return &o;
+    return nullptr;
 }
 }  // namespace
 
 int pt_set_option(pt_scene* s, const char* name, int v) {
     // (the name and the value are checked before the scene: what the library accepts can be asked without a device)
-    const int k = option_index(name);
-    if (k < 0) return fail(-1, "pt_set_option: unknown option '%s'", name ? name : "(null)");
-    if (v < kOptions[k].lo || v > kOptions[k].hi) return fail(-1, "pt_set_option: %s = %d is outside [%d, %d]", name, v, kOptions[k].lo, kOptions[k].hi);
+    const Option* o = find_option(name);
+    if (!o) return fail(-1, "pt_set_option: unknown option '%s'", name ? name : "(null)");
+    if (v < o->lo || v > o->hi) return fail(-1, "pt_set_option: %s = %d is outside [%d, %d]", name, v, o->lo, o->hi);
     if (!s) return fail(-1, "pt_set_option: null scene");
-#ifndef PT_EXPERIMENTAL
-    // A/B variants that lost their measurements are not in a default build: only their "off" value is accepted.
-    {
-        const bool exp = ((k == 7 || k == 13 || k == 19 || k == 20) && v != 0) || (k == 3 && v == 2) || (k == 15 && v != 2);
-        if (exp) return fail(-3, "pt_set_option: %s = %d selects an experimental kernel; rebuild with `make EXPERIMENTAL=1` (pt_has_experimental() == 0)", name, v);
-    }
-#endif
-    switch (k) {
-        case 0: s->flatWanted = v; break;
-        case 1: s->onchipOk = v != 0; break;
-        case 2: s->wavesHbmOk = v != 0 && PT_WAVES_HBM > 0; s->wavesHbmForce = s->wavesHbmOk && v == 2; break;
-        case 3: s->refill = v; break;
-        case 4: s->refillKeep = v; s->refillKeepSet = true; break;
-        case 5: s->nodeKeep = v; break;
-        case 6: s->triKeep = v; break;
-        case 7: s->deferShadow = v != 0; break;
-        case 8: s->sliceIters = v; break;
-        case 9: s->sliceAlways = v != 0; break;
-        case 10: if (((v + 1) & v) != 0) return fail(-1, "pt_set_option: sched_mask must be 2^k - 1"); s->schedMask = v; break;
-        case 11: s->lptPrio = v; break;
-        case 12: s->persistent = v != 0; break;
-        case 13: s->xcdBands = v != 0; break;
-        case 14: s->cull = v != 0; break;
-        case 15: s->spec = v; break;
-        case 16: s->simpleWanted = v != 0; break;
-        case 17: s->flat2Wanted = v; break;
-        case 18: s->leafBoxes = v != 0; break;
-        case 19: s->wideWanted = v != 0; break;
-        case 20: s->compactWanted = v != 0; break;
-        case 21: s->wfWideWg = v; break;
-        case 22: s->leanWanted = v != 0; break;
-        case 23: s->queueTimeoutMs = v; break;
-        case 24: s->momentsFused = v != 0; break;
-    }
+    if (o->set) return o->set(s, v);
+    if (!o->field) return v == o->off ? 0 : removed(name, v);
+    s->*(o->field) = v;
     return 0;
 }
 
 int pt_get_option(pt_scene* s, const char* name, int* out) {
-    if (option_index(name) < 0) return fail(-1, "pt_get_option: unknown option '%s'", name ? name : "(null)");
+    const Option* o = find_option(name);
+    if (!o) return fail(-1, "pt_get_option: unknown option '%s'", name ? name : "(null)");
     if (!s || !out) return fail(-1, "pt_get_option: null argument");
-    switch (option_index(name)) {
-        case 0: *out = s->flatWanted; break;
-        case 1: *out = s->onchipOk; break;
-        case 2: *out = s->wavesHbmForce ? 2 : (s->wavesHbmOk ? 1 : 0); break;
-        case 3: *out = s->refill; break;
-        case 4: *out = s->refillKeep; break;
-        case 5: *out = s->nodeKeep; break;
-        case 6: *out = s->triKeep; break;
-        case 7: *out = s->deferShadow; break;
-        case 8: *out = s->sliceIters; break;
-        case 9: *out = s->sliceAlways; break;
-        case 10: *out = s->schedMask; break;
-        case 11: *out = s->lptPrio; break;
-        case 12: *out = s->persistent; break;
-        case 13: *out = s->xcdBands; break;
-        case 14: *out = s->cull; break;
-        case 15: *out = s->spec; break;
-        case 16: *out = s->simpleWanted; break;
-        case 17: *out = s->flat2Wanted; break;
-        case 18: *out = s->leafBoxes; break;
-        case 19: *out = s->wideWanted; break;
-        case 20: *out = s->compactWanted; break;
-        case 21: *out = s->wfWideWg; break;
-        case 22: *out = s->leanWanted; break;
-        case 23: *out = s->queueTimeoutMs; break;
-        case 24: *out = s->momentsFused; break;
-        default: return fail(-1, "pt_get_option: unknown option '%s'", name ? name : "(null)");
-    }
+    *out = o->get ? o->get(s) : (o->field ? s->*(o->field) : o->off);
     return 0;
 }
 
 int pt_scene_flags(pt_scene* s) {
     if (!s) return 0;
     const bool onchip = scene_onchip(s);
-    const bool pers = s->persistent && !s->xcdBands;
+    const bool pers = s->persistent != 0;
     // the kernel the last launch used; before any launch, the one a frame with tiles enough for any kernel would get
     const bool hbm = s->lastLaunchHbm >= 0 ? s->lastLaunchHbm == 1 : hbm_kernel_pays(s, false, 1ll << 40);
     return (onchip ? 1 : 0) | (pers ? 2 : 0) | ((pers && s->sliceIters > 0) ? 4 : 0) | (hbm ? 8 : 0) | ((s->cull && hbm) ? 16 : 0) | (s->lastLaunchRefill ? 32 : 0) | (s->lastLaunchFlat ? 64 : 0) | (s->lastLaunchSimple ? 128 : 0) | (s->lastLaunchFlat2 ? 256 : 0) | (s->lastLaunchLeafTable ? 512 : 0) | (s->lastLaunchLean ? 1024 : 0);

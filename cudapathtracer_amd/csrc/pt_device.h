@@ -191,28 +191,6 @@ struct __attribute__((aligned(16))) PMat {
 static_assert(sizeof(PMat) == 96, "PMat");
 constexpr uint32_t kMatHasTexture = 1, kMatHasTransMap = 2, kMatSpecular = 4, kMatBoundary = 8;
 
-// Wide node (4 children) of the collapsed tree the SIMPLE kernel for scenes in HBM may traverse (pt_trace.h: trace_resume_w4):
-// the children's boxes are the reference tree's own float boxes, axis-major; ref as in PNode (>= 0 wide node, < 0 leaf,
-// kRefNone = empty slot). One 128-byte line.
-struct __attribute__((aligned(128))) WNode {
-    float mnx[4], mny[4], mnz[4], mxx[4], mxy[4], mxz[4];
-    int32_t ref[4];
-    int32_t pad[4];
-};
-static_assert(sizeof(WNode) == 128, "WNode");
-
-// Compact internal node for the SIMPLE kernel for scenes in HBM (pt_trace.h: trace_resume_q): both children's boxes as 8-bit
-// offsets in the node's OWN frame — origin = the node's box minimum (exact floats), one power-of-two step for all three axes,
-// x = fma(q, 2^k, origin) — rounded OUTWARD so that each decoded box contains the reference's float box: the step is 1/255
-// of the node's largest extent at every depth. Child words: bit 31 = leaf, bits 24-30 of `left` = k + 64, bits 0-23 = the
-// node index or the leaf's first packed triangle. Half a PNode: two 16-byte loads per visit instead of four.
-struct __attribute__((aligned(16))) QNode {
-    float o[3];
-    uint8_t lmin[3], lmax[3], rmin[3], rmax[3];
-    uint32_t left, right;
-};
-static_assert(sizeof(QNode) == 32, "QNode");
-
 // FLAT kernels: one record per LEAF of the tree — the leaf's own box (as stored with its parent) and its triangle range.
 struct __attribute__((aligned(16))) PLeaf {
     float mn[3], mx[3];

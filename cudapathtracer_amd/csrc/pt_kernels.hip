@@ -243,11 +243,8 @@ hipError_t launch_rng_init(const uint32_t* jump, unsigned long long seed, int w,
 // Which kernel a launch gets: decided here and nowhere else. The instantiations live in two translation units with different
 // code-generation flags (pt_megakernel.h), each with the table of what it builds (pt_mk_lds.hip: scenes that live in LDS; pt_mk_hbm.hip:
 // megakernel_hbm and the general 4-wave kernel). A launch is reduced to the key of the row that serves it; a launch no row serves has no
-// kernel (what only an experimental build launches has its rows there, and pt_api.hip never asks for it in a default build).
+// kernel: syncShadow false asks for the general kernel with the deferred shadow ray (kMkDefer), which is not built.
 const MkRow* megakernel_choose(int integrator, bool count, bool syncShadow, const KParams& P, bool moments) {
-#ifdef PT_EXPERIMENTAL
-    if (moments) return nullptr;                              // the twins are picked under default options only: an A/B build renders its moments in batches
-#endif
     if ((integrator != 0 && integrator != 2) || (unsigned)P.flat > 3u) return nullptr;
     // What the kernels do not distinguish. Only timed kernels have the FLAT and SIMPLE forms: a counting launch of such a scene takes the
     // plain counting kernel. The pair form of FLAT (3) is integrator 0's, FLAT otherwise. The naive integrator has no shadow ray to defer.
@@ -256,7 +253,7 @@ const MkRow* megakernel_choose(int integrator, bool count, bool syncShadow, cons
     const bool simple = P.simple && !count, defer = !syncShadow && integrator != 2;
     const unsigned key = (integrator == 2 ? kMkI2 : 0u) | (count ? kMkCount : 0u) | (defer ? kMkDefer : 0u) | ((P.onchip && !P.hbm) ? kMkLds : 0u) | (P.hbm ? kMkHbm : 0u) |
                          kMkFlat * (unsigned)flat | (simple ? kMkSimple : 0u) | (P.lean ? kMkLean : 0u) | (P.refill ? kMkRefill : 0u) | (P.cull ? kMkCull : 0u) |
-                         (P.wide ? kMkWide : 0u) | (P.compact ? kMkCompact : 0u) | (moments ? kMkMoments : 0u);
+                         (moments ? kMkMoments : 0u);
     for (int i = 0; i < kMkRowsLdsCount; i++) if ((kMkRowsLds[i].key & ~kMkBuiltOnly) == key) return &kMkRowsLds[i];
     for (int i = 0; i < kMkRowsHbmCount; i++) if ((kMkRowsHbm[i].key & ~kMkBuiltOnly) == key) return &kMkRowsHbm[i];
     return nullptr;

@@ -167,7 +167,7 @@ PT_DEV void state_store(uint32_t* p, uint32_t v, bool shared) { if (shared) PT_Q
 // LEAN: the generic bounce for scenes without MAT_LEAF triangles and without textures (pt_shade.h).
 // MOMENTS: the launch also keeps pt_render_moments' Q, the sum of squared batch sums (moments_land below; the fused twins at the
 // end of this file). Everything it adds sits behind `if constexpr (MOMENTS)`: the other instantiations' code does not change.
-template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, int STACKN, bool CULL = false, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, int TREE = 0, bool LEAN = false,
+template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, int STACKN, bool CULL = false, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, bool LEAN = false,
           bool MOMENTS = false>
 PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullptr, nullptr, 0, 0.0f}) {
     static_assert(!MOMENTS || !COUNT, "the fused moments render has no counting form");
@@ -197,15 +197,7 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     constexpr bool ATTRLDS = ONCHIP && kAttrCacheBytes > 0;
     constexpr int kMedBytes = SIMPLE ? 0 : kMediumMax * 64;                 // SIMPLE kernels have no medium stack (pt_path.h)
     const int attrOff = ATTRLDS ? P.cacheNodes * 64 + P.cacheTris * 48 + nW * (STACKN * 256 + kMedBytes) : 0;
-    DeviceScene Sstage = S;
-#ifdef PT_EXPERIMENTAL
-    constexpr bool WIDE = TREE == 1, COMPACT = TREE == 2;
-    if (WIDE) Sstage.nodes = reinterpret_cast<const PNode*>(P.wnodes);       // the LDS scene cache of the WIDE kernel holds wide nodes (P.cacheNodes counts 64-byte halves)
-    if (COMPACT) Sstage.nodes = reinterpret_cast<const PNode*>(P.qnodes);    // ... of the COMPACT kernel 32-byte nodes, two per unit
-#else
-    static_assert(TREE == 0, "the wide / compact trees are -DPT_EXPERIMENTAL builds (pt_trace_experimental.h)");
-#endif
-    const SceneCache SC = stage_scene_cache(Sstage, P.cacheNodes, P.cacheTris, attrOff, P.cacheAttrs, P.cacheMats, P.cacheLights);      // contains the only barrier
+    const SceneCache SC = stage_scene_cache(S, P.cacheNodes, P.cacheTris, attrOff, P.cacheAttrs, P.cacheMats, P.cacheLights);      // contains the only barrier
     if constexpr (ATTRLDS) {
         // The bounce reads its records through S; pointing S at the LDS copies makes those loads ds_reads (the address
         // space is visible to the compiler: everything below is inlined into this function).
@@ -221,14 +213,8 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     // XCDs interleave over the frame at 32x8-pixel granularity — every XCD gets the same mix of cheap and expensive
     // regions. (One contiguous band of tiles per XCD, so that its L2 holds only that band's geometry, measured no gain on
     // the 263 k scene — secondary rays leave the band at once — and -14 % / -9 % on the 82 k scene / Cornell: bands differ
-    // in cost and a static 1/8 split cannot rebalance. Option "xcd_bands" of -DPT_EXPERIMENTAL builds.)
-    int vb = blockIdx.x;
-#ifdef PT_EXPERIMENTAL
-    if (P.xcdBands) {
-        const int nB = gridDim.x, q = nB >> 3, r = nB & 7, x = vb & 7;
-        vb = x * q + (x < r ? x : r) + (vb >> 3);
-    }
-#endif
+    // in cost and a static 1/8 split cannot rebalance)
+    const int vb = blockIdx.x;
     // Persistent waves (P.queue != null): the grid only fills the chip and every wave takes its next tile
     // from the queue, so a wave slot is never parked behind the slowest of four sibling waves or behind
     // workgroup launch; tiles are independent, so the order does not reach the image.
@@ -295,9 +281,6 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     V3 thr = v3(1.0f);
     RayState rs;                                          // REFILL: a lane's traversal state between two visits of the loops
     rs.o = v3(0.0f); rs.d = v3(0.0f); rs.max_t = 0.0f; rs.cur = kRefNone; rs.flags = 0u;
-#ifdef PT_EXPERIMENTAL
-    rs.inv = v3(0.0f); rs.min_t = 0.0f; rs.pend = kRefNone;
-#endif
 #ifdef PT_STAMPS
     unsigned long long stamp[4] = {0, 0, 0, 0};
     unsigned long long tprev = __builtin_amdgcn_s_memtime();
@@ -424,55 +407,13 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
                 }
                 const bool hasExt = (ps.flags & kInPath) != 0, hasShadow = (ps.flags & kShadowPending) != 0;
                 if (hasExt || hasShadow) {
-#ifdef PT_EXPERIMENTAL
-                    bool irregular = false;
-                    if constexpr (WIDE) irregular = (hasExt && !inv_is_regular(inv3(ps.d))) || (hasShadow && !inv_is_regular(inv3(ps.sd)));
-                    if (WIDE && irregular) {
-                        // a zero direction component: the monotonicity argument behind the wide tree does not hold (0 * inf = NaN), so
-                        // this lane's rays take the reference traversal, here and now (rare: an axis-parallel direction)
-                        SceneCache none; none.nodes = nullptr; none.nNodes = 0; none.tris = nullptr; none.nTris = 0;
-                        thr = v3(1.0f);
-                        if (hasShadow) thr = trace_shadow_plain<false, STACKN, false, false, true>(S, none, ps.so, ps.sd, ps.smaxt, st, c);
-                        h.tri = -1; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.material = 0;
-                        if (hasExt) trace_closest_plain<false, STACKN, false, false>(S, none, ps.o, ps.d, 999999.0f, st, h, c);
-                        rs.flags = (hasShadow && thr.x == 0.0f) ? kRayOccluded : 0u;      // (a NOLEAF scene: the throughput is 0 or 1; the next logic step reads the bit)
-                    } else
-#endif
                     ray_start<COUNT, STACKN>(S, st, rs, hasShadow, ps.so, ps.sd, ps.smaxt, hasExt, ps.o, ps.d, thr, h, c);
                 }
             }
             PT_STAMP(2);
             const int nBusy = __builtin_popcountll(__ballot((rs.flags & kRayBusy) != 0));
             if (nBusy == 0) break;
-#ifdef PT_EXPERIMENTAL
-            if constexpr (COMPACT) {
-                const Compact K{P.qnodes, reinterpret_cast<const f4v*>(P.leafBox), P.mids};
-                trace_resume_q<STACKN>(S, SC, K, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, Keep{P.nodeKeep, P.triKeep});
-                PT_STAMP(1);
-                continue;
-            }
-            if constexpr (WIDE) {
-                trace_resume_w4<STACKN>(S, SC, P.wnodes, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, c, Keep{P.nodeKeep, P.triKeep});
-                if (!(rs.flags & kRayBusy) && (rs.flags & kRayTie)) {
-                    // two triangles returned the SAME closest t: the reference keeps the one it visits first — its own traversal decides
-                    SceneCache none; none.nodes = nullptr; none.nNodes = 0; none.tris = nullptr; none.nTris = 0;
-                    trace_closest_plain<false, STACKN, false, false>(S, none, ps.o, ps.d, 999999.0f, st, h, c);
-                    rs.flags &= ~kRayTie;
-                }
-                PT_STAMP(1);
-                continue;
-            }
-#endif
-#if !defined(PT_EXPERIMENTAL)
             trace_resume<COUNT, STACKN, ONCHIP, NOLEAF, TRISEL>(S, SC, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, c, Keep{P.nodeKeep, P.triKeep});
-#elif PT_SPEC == 2            // both bodies in the kernel, chosen per launch (A/B only: the second body costs registers)
-            if (P.spec) trace_resume_spec<COUNT, STACKN, ONCHIP, NOLEAF>(S, SC, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, c, Keep{P.nodeKeep, P.triKeep}, P.spec == 2);
-            else trace_resume<COUNT, STACKN, ONCHIP, NOLEAF, TRISEL>(S, SC, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, c, Keep{P.nodeKeep, P.triKeep});
-#elif PT_SPEC == 1
-            trace_resume_spec<COUNT, STACKN, ONCHIP, NOLEAF>(S, SC, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, c, Keep{P.nodeKeep, P.triKeep}, P.spec == 2);
-#else
-            trace_resume<COUNT, STACKN, ONCHIP, NOLEAF, TRISEL>(S, SC, st, rs, ps.o, ps.d, (nBusy * P.refillKeep) >> 4, thr, h, c, Keep{P.nodeKeep, P.triKeep});
-#endif
             PT_STAMP(1);
             continue;
         }
@@ -513,9 +454,6 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
               if (hasExt && h2.tri == h.tri) h.t = fminf_(h.t, h2.t); thr.x = fminf_(thr.x, thr2.x); }
 #endif
         }
-#ifdef PT_EXPERIMENTAL
-        else if (DEFER) trace_pair<COUNT, STACKN>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, hasExt, ps.o, ps.d, thr, h, c);
-#endif
         else if constexpr (FLAT) {
             trace_closest_flat<STACKN, FLATW>(S, SC, hasExt, ps.o, ps.d, 999999.0f, st, h, c, P.cacheNodes, P.leaves, P.nLeaves);
 #ifdef PT_DIAG_DOUBLE_CLOSEST       // cost measurement only: the closest-hit traversal run twice, same result
@@ -601,7 +539,7 @@ __global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
 #if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))     // cap VGPRs so that PT_MIN_WAVES waves fit per SIMD
 #endif
-megakernel(KParams P) { megakernel_body<INTEG, COUNT, DEFER, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, 0, LEAN>(P); }
+megakernel(KParams P) { megakernel_body<INTEG, COUNT, DEFER, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, LEAN>(P); }
 // Each wrapper is followed by what the host needs to know about it (pt_params.h: MkFacts; the tables' rows take it from here): the STACKN
 // it hands the body, whether that body has medium stacks (megakernel_body: kMedBytes, none with SIMPLE), whether it stages the bounce's
 // records (ATTRLDS: the ONCHIP kernels), and its launch bounds and register cap.
@@ -611,7 +549,7 @@ constexpr MkFacts megakernel_facts = {kStackLds, !SIMPLE, ONCHIP, 0, kMkMinWaves
 
 template <int INTEG, bool COUNT, bool CULL, bool REFILL, bool SIMPLE = false, bool LEAN = false>
 __global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))
-megakernel_hbm(KParams P) { megakernel_body<INTEG, COUNT, false, false, kStackLdsHbmGen, CULL, REFILL, false, SIMPLE, 1, 0, LEAN>(P); }
+megakernel_hbm(KParams P) { megakernel_body<INTEG, COUNT, false, false, kStackLdsHbmGen, CULL, REFILL, false, SIMPLE, 1, LEAN>(P); }
 template <int INTEG, bool COUNT, bool CULL, bool REFILL, bool SIMPLE, bool LEAN>
 constexpr MkFacts megakernel_hbm_facts = {kStackLdsHbmGen, !SIMPLE, false, kWgWavesHbm, kWavesHbm};
 
@@ -624,25 +562,9 @@ __global__ void __launch_bounds__(1024)
 #if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
 #endif
-megakernel_flat2(KParams P) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, 0, LEAN>(P); }
+megakernel_flat2(KParams P) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, LEAN>(P); }
 template <int INTEG, bool SIMPLE, bool LEAN>
 constexpr MkFacts megakernel_flat2_facts = {kStackFlat2, !SIMPLE, true, 0, kMkMinWaves};
-
-#ifdef PT_EXPERIMENTAL
-// ... and the same on the reference tree collapsed to 4-wide nodes (pt_trace_experimental.h: trace_resume_w4).
-template <int INTEG>
-__global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
-megakernel_hbm_wide(KParams P) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 1>(P); }
-template <int INTEG>
-constexpr MkFacts megakernel_hbm_wide_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
-
-// ... and on 32-byte quantised nodes with exact leaf boxes (pt_trace_experimental.h: trace_resume_q).
-template <int INTEG>
-__global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
-megakernel_hbm_compact(KParams P) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 2>(P); }
-template <int INTEG>
-constexpr MkFacts megakernel_hbm_compact_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
-#endif
 
 // The SIMPLE production kernel for scenes in HBM: 8 waves per SIMD, 16-wave workgroups (pt_params.h).
 template <int INTEG>
@@ -660,7 +582,7 @@ __global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
 #if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
 #endif
-megakernel_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, 0, LEAN, true>(P, M); }
+megakernel_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, LEAN, true>(P, M); }
 template <int INTEG, bool ONCHIP, bool REFILL, bool FLAT, bool SIMPLE, int FLATW, bool LEAN>
 constexpr MkFacts megakernel_moments_facts = {kStackLds, !SIMPLE, ONCHIP, 0, kMkMinWaves};
 
@@ -669,19 +591,19 @@ __global__ void __launch_bounds__(1024)
 #if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
 #endif
-megakernel_flat2_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, 0, LEAN, true>(P, M); }
+megakernel_flat2_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, LEAN, true>(P, M); }
 template <int INTEG, bool SIMPLE, bool LEAN>
 constexpr MkFacts megakernel_flat2_moments_facts = {kStackFlat2, !SIMPLE, true, 0, kMkMinWaves};
 
 template <int INTEG, bool LEAN>        // the REFILL forms of megakernel_hbm: the generic bounce and its LEAN form
 __global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))
-megakernel_hbm_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbmGen, false, true, false, false, 1, 0, LEAN, true>(P, M); }
+megakernel_hbm_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbmGen, false, true, false, false, 1, LEAN, true>(P, M); }
 template <int INTEG, bool LEAN>
 constexpr MkFacts megakernel_hbm_moments_facts = {kStackLdsHbmGen, true, false, kWgWavesHbm, kWavesHbm};
 
 template <int INTEG>
 __global__ void __launch_bounds__(64 * kWgWavesHbmSimple) __attribute__((amdgpu_waves_per_eu(kWavesHbmSimple)))
-megakernel_hbm_simple_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, 0, false, true>(P, M); }
+megakernel_hbm_simple_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, false, kStackLdsHbm, false, true, false, true, 1, false, true>(P, M); }
 template <int INTEG>
 constexpr MkFacts megakernel_hbm_simple_moments_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
 

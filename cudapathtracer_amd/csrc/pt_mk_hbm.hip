@@ -1,6 +1,6 @@
 // pt_mk_hbm.hip — megakernel instantiations for scenes in HBM: megakernel_hbm (6 waves per SIMD, 12-wave workgroups
 // sharing a 44 KB copy of the top of the tree; loop exits, REFILL, opt-in culling) and the general 4-wave kernel
-// (launches with too few tiles to fill its waves; -DPT_EXPERIMENTAL builds add the A/B instantiations of DESIGN.md §6).
+// (launches with too few tiles to fill its waves).
 // Built without the SLP vectorizer since round 3 (Makefile: at 64 VGPRs its packed pairs cost spills, -3.4 / -3.8 %), and with the
 // per-lane range test in rcp_exact: the wave-uniform form that pays for the issue-bound LDS-resident kernels measures 0.7-1.0 %
 // slower here (profiles/r03_ab_rcp_uniform_hbm.log).
@@ -23,10 +23,6 @@ const MkRow kMkRowsHbm[] = {
     PT_MK_ROW2(kMkHbm | kMkCull, megakernel_hbm, false, true, false, false, false),
     PT_MK_ROW2(kMkHbm | kMkRefill | kMkLean, megakernel_hbm, false, false, true, false, true),
     PT_MK_ROW2(kMkHbm | kMkRefill | kMkSimple, megakernel_hbm_simple),
-#ifdef PT_EXPERIMENTAL
-    PT_MK_ROW2(kMkHbm | kMkRefill | kMkSimple | kMkWide, megakernel_hbm_wide),
-    PT_MK_ROW2(kMkHbm | kMkRefill | kMkSimple | kMkCompact, megakernel_hbm_compact),
-#endif
     // the general 4-wave kernel, the same forms but culling
     PT_MK_ROW2(kMkCount, megakernel, true, false, false, false, false, false, 1, false),
     PT_MK_ROW2(0u, megakernel, false, false, false, false, false, false, 1, false),
@@ -34,12 +30,7 @@ const MkRow kMkRowsHbm[] = {
     PT_MK_ROW2(kMkRefill, megakernel, false, false, false, true, false, false, 1, false),
     PT_MK_ROW2(kMkRefill | kMkLean, megakernel, false, false, false, true, false, false, 1, true),
     PT_MK_ROW2(kMkRefill | kMkSimple, megakernel, false, false, false, true, false, true, 1, false),
-#ifdef PT_EXPERIMENTAL      // option "defer_shadow": the DEFER pair walk; pt_api.hip never asks for it in a default build
-    PT_MK_ROW(kMkDefer | kMkCount, megakernel, 0, true, true, false, false, false, false, 1, false),
-    PT_MK_ROW(kMkDefer, megakernel, 0, false, true, false, false, false, false, 1, false),
-#endif
-    // The fused moments twins: the REFILL forms with their 4-wave forms. Not built: culling, the plain loops ("refill" 0), and whatever
-    // only an experimental build launches.
+    // The fused moments twins: the REFILL forms with their 4-wave forms. Not built: culling and the plain loops ("refill" 0).
     PT_MK_ROW2(kMkMoments | kMkHbm | kMkRefill, megakernel_hbm_moments, false),
     PT_MK_ROW2(kMkMoments | kMkHbm | kMkRefill | kMkLean, megakernel_hbm_moments, true),
     PT_MK_ROW2(kMkMoments | kMkHbm | kMkRefill | kMkSimple, megakernel_hbm_simple_moments),

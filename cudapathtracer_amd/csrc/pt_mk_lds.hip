@@ -19,10 +19,6 @@ const MkRow kMkRowsLds[] = {
     PT_MK_ROW(kMkLds | kMkFlat * 3 | kMkSimple, megakernel_flat2, 0, true, false),
     PT_MK_ROW(kMkLds | kMkFlat * 3 | kMkLean, megakernel_flat2, 0, false, true),
     PT_MK_ROW(kMkLds | kMkFlat * 3, megakernel_flat2, 0, false, false),
-#ifdef PT_EXPERIMENTAL      // option "refill" 2: the resumable traversal for LDS-resident scenes too (-32 % on Cornell)
-    PT_MK_ROW2(kMkLds | kMkRefill | kMkCount, megakernel, true, false, true, true, false, false, 1, false),
-    PT_MK_ROW2(kMkLds | kMkRefill, megakernel, false, false, true, true, false, false, 1, false),
-#endif
     // the fused moments twins of the timed kernels above
     PT_MK_ROW2(kMkMoments | kMkLds, megakernel_moments, true, false, false, false, 1, false),
     PT_MK_ROW2(kMkMoments | kMkLds | kMkFlat * 1, megakernel_moments, true, false, true, false, 1, false),

@@ -15,9 +15,6 @@ namespace pt {
 #ifndef PT_CACHE_BYTES
 #define PT_CACHE_BYTES 12288      // LDS bytes per workgroup for the scene cache (top PNodes / all PTris)
 #endif
-#ifndef PT_SPEC
-#define PT_SPEC 0                 // resumable traversal of the REFILL kernels: 0 trace_resume, 1 trace_resume_spec (speculative descent), 2 both (A/B)
-#endif
 constexpr int kStackLds = PT_STACK_LDS;
 #ifndef PT_WAVES_HBM
 #define PT_WAVES_HBM 6             // waves per SIMD of the instantiation for scenes that do not fit the LDS cache (0 = use the 4-wave kernel)
@@ -70,6 +67,9 @@ static_assert((kWavesHbmSimple * 4) % kWgWavesHbmSimple == 0 && kWgWavesHbmSimpl
 constexpr int kWgPerCuHbmSimple = (kWavesHbmSimple * 4) / kWgWavesHbmSimple;        // a CU's 160 KB of LDS divided among them
 constexpr int kCacheBytesHbmSimple = ((160 * 1024) / kWgPerCuHbmSimple - kWgWavesHbmSimple * (kStackLdsHbm * 256)) / 64 * 64;
 
+// The pad* members hold the places of the parameters of retired variants (wide / compact trees, speculative descent,
+// XCD bands), same types, same offsets. Like MomentsK below: the hidden kernel arguments follow the explicit ones, so a KParams that
+// shrank would move them and change the code of every kernel. The asserts after the struct pin its size and three live offsets.
 struct KParams {
     DeviceScene S;
     CamK cam;
@@ -77,10 +77,7 @@ struct KParams {
     int tileFirst, tileStride, tileCount, tilesX;
     int cacheNodes, cacheTris;     // scene-cache extent (PNodes / PTris staged in LDS per workgroup)
     int cacheAttrs, cacheMats, cacheLights;   // ONCHIP kernels: PAttr / PMat / PLight records staged behind the stacks (all or none; 0 = read from global memory)
-    int wide;                      // 1: megakernel_hbm_wide — the SIMPLE kernel for scenes in HBM on the 4-wide collapsed tree `wnodes`
-    const WNode* wnodes;
-    int compact;                   // 1: megakernel_hbm_compact — the SIMPLE kernel for scenes in HBM on 32-byte quantised nodes (pt_trace.h: trace_resume_q)
-    const QNode* qnodes; const void* leafBox; const int32_t* mids;
+    int pad0; const void* pad1; int pad2; const void* pad3[3];
     int gnodeFrom;                 // counting launches: node indices from here on count as global fetches — the scene-cache extent of the TIMED instantiation for this launch
     int nLeaves;                   // FLAT kernels: PLeaf records in global memory, read through the scalar cache (0 = none: the lockstep node walk)
     const PLeaf* leaves;
@@ -92,12 +89,12 @@ struct KParams {
     int flat;                      // 1: the FLAT instantiation (pt_trace.h: trace_closest_flat) — LDS-resident scenes with at most 64 internal nodes / 64 triangles
     int refill;                    // 1: the REFILL instantiation (pt_trace.h: trace_resume) — finished lanes shade and come back while the rest keep tracing
     int refillKeep;                // the wave leaves the traversal when no more than busy * refillKeep / 16 lanes are still tracing
-    int spec;                      // REFILL kernels: 0 trace_resume, 1 speculative descent for closest-hit rays (pt_trace.h: trace_resume_spec), 2 also for shadow rays
+    int pad4;
     int wgWaves;                   // waves per workgroup of this launch (4, or kWgWavesHbm for megakernel_hbm)
     int wavesPerSimd;              // PT_MIN_WAVES (megakernel), kWavesHbm (megakernel_hbm) or kWavesHbmSimple (its SIMPLE instantiation)
     int hbm;                       // 1: a megakernel_hbm launch (8-entry LDS stacks, the spill area laid out for them)
     int onchip;                    // 1: every PNode / PTri is in the LDS cache and the stack fits LDS -> ONCHIP kernels
-    int xcdBands;                  // 1: workgroups of one XCD take a contiguous run of tiles (one L2 per XCD, MI355X_MICROARCH.md)
+    int pad5;
     uint32_t* rng;                 // [tile][6][64]
     float4* out;                   // [tile][64], += semantics
     uint32_t* pixCounters;         // [tile][8][64] or null
@@ -114,6 +111,8 @@ struct KParams {
     int lptPrio;                   // longest-remaining-first issue priority once no fresh tile is left
     unsigned long long lightTri8;  // the SIMPLE pair kernel: a byte per light, for the first 8: 1 + the packed triangle the light is (same v0, e1, e2 bit for bit), 0 = none (pt_api.hip: light_triangles)
 };
+static_assert(sizeof(KParams) == 416 && offsetof(KParams, gnodeFrom) == 240 && offsetof(KParams, rng) == 312 &&
+              offsetof(KParams, lightTri8) == 408, "KParams: the layout every kernel's code was built against");
 // What the fused moments twins take besides (pt_megakernel.h: MOMENTS), as a SECOND kernel argument: the hidden arguments
 // (the workgroup's size) follow the explicit ones, so a KParams that grew would move them and change the code of every kernel.
 struct MomentsK {
@@ -180,7 +179,7 @@ struct MkFacts {
 // moments twin, MomentsK is its second argument.
 enum : unsigned {
     kMkI2 = 1u, kMkCount = 2u, kMkDefer = 4u, kMkLds = 8u, kMkHbm = 16u, kMkFlat = 32u /* x KParams::flat, two bits */, kMkSimple = 128u, kMkLean = 256u,
-    kMkRefill = 512u, kMkCull = 1024u, kMkWide = 2048u, kMkCompact = 4096u, kMkMoments = 8192u,
+    kMkRefill = 512u, kMkCull = 1024u, kMkMoments = 8192u,
     kMkBuiltOnly = 16384u          // built and correct, but out of the dispatch: megakernel_choose returns the row, nobody launches it
 };
 struct MkRow { const void* fn; const char* name; MkFacts f; unsigned key; };

@@ -1098,7 +1098,7 @@ struct Trav {
 };
 
 // ---- resumable pair traversal (REFILL kernels) ------------------------------------------------
-// trace_pair leaves a wave in its loops until its LAST lane has finished; without culling the rays of
+// A pair walk in one call keeps a wave in its loops until its LAST lane has finished; without culling the rays of
 // one wave differ widely in length, and on the 263 k-triangle scene a trip through the node loop carries 8.6 of
 // 64 lanes on average (tools/lane_util.py). Here the traversal state of a lane lives in a RayState that
 // survives the call: the wave leaves the loops as soon as no more than `minBusy` lanes are still tracing,
@@ -1120,16 +1120,12 @@ struct RayState {
     V3 o, d;
     float max_t;
     int32_t cur;
-#if PT_RS_KEEP_INV && !defined(PT_EXPERIMENTAL)
+#if PT_RS_KEEP_INV
     V3 inv;
-#endif
-#ifdef PT_EXPERIMENTAL
-    V3 inv; float min_t;
-    int32_t pend;                      // trace_resume_spec / trace_resume_q: the one postponed leaf (kRefNone = none)
 #endif
     uint32_t flags;                    // kRayBusy | kRayShadow | kRayExtFollows | kRayOccluded
 };
-constexpr uint32_t kRayBusy = 1u, kRayShadow = 2u, kRayExtFollows = 4u, kRayInLeaf = 32u, kRayOccluded = 64u;     // (8u, 16u and kRayInLeaf: pt_trace_experimental.h)
+constexpr uint32_t kRayBusy = 1u, kRayShadow = 2u, kRayExtFollows = 4u, kRayOccluded = 64u;
 
 template <bool COUNT, int N>
 PT_DEV void ray_start(const DeviceScene& S, Stack<N>& st, RayState& r, bool hasShadow, V3 so, V3 sd, float smaxt,
@@ -1140,13 +1136,8 @@ PT_DEV void ray_start(const DeviceScene& S, Stack<N>& st, RayState& r, bool hasS
     r.o = hasShadow ? so : eo; r.d = hasShadow ? sd : ed;
     r.max_t = hasShadow ? smaxt : 999999.0f;
     r.cur = S.rootRef;
-#if PT_RS_KEEP_INV && !defined(PT_EXPERIMENTAL)
+#if PT_RS_KEEP_INV
     r.inv = inv3(r.d);
-#endif
-#ifdef PT_EXPERIMENTAL
-    r.inv = inv3(r.d);
-    r.min_t = 3.402823466e+38f;
-    r.pend = kRefNone;
 #endif
     r.flags = kRayBusy | (hasShadow ? kRayShadow : 0u) | ((hasShadow && hasExt) ? kRayExtFollows : 0u);
     st.sp = 0;
@@ -1267,8 +1258,3 @@ PT_DEV void trace_resume(const DeviceScene& S, const SceneCache& C, Stack<N>& st
 }
 
 }  // namespace pt
-
-// A/B variants that lost their measurements: built only with -DPT_EXPERIMENTAL (make EXPERIMENTAL=1).
-#ifdef PT_EXPERIMENTAL
-#include "pt_trace_experimental.h"
-#endif

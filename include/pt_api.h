@@ -238,18 +238,19 @@ int pt_set_culling(pt_scene* scene, int on);
  *                         lanes keep the squared batch sums themselves, at every batch_spp-th sample of their pixel, instead of
  *                         spp / batch_spp launches with a bookkeeping pass between them: the same two buffers in every bit.
  *                         Where the launch's kernel has no fused form in the dispatch — culling, "refill" 0, the wavefront
- *                         variant, an experimental build, the SIMPLE pair kernel of diffuse-only LDS-resident scenes
+ *                         variant, the SIMPLE pair kernel of diffuse-only LDS-resident scenes
  *                          — the call renders in batches as without the option;
  *                         pt_last_moments_launches tells which it was (0)
- * Experimental options — variants that were built, proven bit-identical and measured SLOWER. The default
- * library does not contain their kernels (pt_has_experimental() == 0) and accepts only their "off" value, returning -3
- * otherwise; `make -C cudapathtracer_amd/csrc EXPERIMENTAL=1` builds them for the A/B:
- *   "wide" 0|1 (4-wide collapsed tree), "compact" 0|1 (32-byte quantised nodes), "spec" 1|2 (speculative descent, with
- *   -DPT_SPEC=1), "defer_shadow" 0|1 (pair walk in the 4-wave kernel), "xcd_bands" 0|1 (one band of tiles per XCD),
- *   "refill" 2 (resumable traversal for LDS-resident scenes too).
+ * Retired options — experimental variants that were built, proven bit-identical, measured SLOWER and then removed (DESIGN.md §6
+ * keeps their results and names the commit that last held their code). Their names are still known; each accepts only the value
+ * that meant "off", which is also what pt_get_option reads back, and returns -3 for any other value in its range:
+ *   "wide" 0 (was: 4-wide collapsed tree), "compact" 0 (32-byte quantised nodes), "spec" 2 (speculative descent),
+ *   "defer_shadow" 0 (pair walk in the 4-wave kernel), "xcd_bands" 0 (one band of tiles per XCD); and "refill" refuses 2
+ *   (resumable traversal for LDS-resident scenes too).
  * Returns 0, or < 0 for an unknown name / a value out of range. */
 int pt_set_option(pt_scene* scene, const char* name, int value);
 int pt_get_option(pt_scene* scene, const char* name, int* value);
+/* Always 0: no build holds the retired variants any more. Kept so that callers that ask before an A/B keep linking. */
 int pt_has_experimental(void);
 /* Eight more sums since the last pt_reset_counters. Normal build: out8[0] = internal-node fetches of counting launches
  * that went to global memory (node index beyond the LDS scene cache) — with tri_tests, the L1 line-access count behind
@@ -981,8 +982,7 @@ int pt_debug_packed(pt_scene* scene, int what, void* dst, size_t capacity_bytes)
  * fresh pt_scene_create_from_mesh of the new arrays with the same options, variant and culling applied. The packed
  * triangles, attributes and lights are byte-identical and the packed tree is the same tree; what creation derives from them
  * (which kernels the scene qualifies for, the leaf table, the lights' triangles, the LDS cache split, the stack need and
- * the spill sizes that follow from it) is derived again by the same code, and the trees of EXPERIMENTAL builds are dropped
- * and rebuilt on demand.
+ * the spill sizes that follow from it) is derived again by the same code.
  * KEPT: option values (pt_get_option), variant and culling; the sums of pt_get_counters; pt_queue_stalls; the work buffers.
  * ATOMICITY. Arguments are checked on the host before any HIP call (NULL pointers, counts, for the vertex forms the counts
  * against the scene's). The build goes into spare node / triangle / attribute / light buffers that are swapped in on
@@ -1018,7 +1018,7 @@ int pt_scene_generation(pt_scene* scene);
  * family the scene qualifies for (SIMPLE, LEAN, the pair form's "no leaf triangle", a material type without a dispatch arm) is
  * decided again from scratch, so a diffuse box turned into a mirror leaves the SIMPLE kernels and comes back with the edit undone.
  * KEPT: everything the updates above keep, and the tree, the leaf table, the lights' triangles and the LDS cache split, which no
- * material or emission decides and which are neither read nor rebuilt; the trees of EXPERIMENTAL builds stay too.
+ * material or emission decides and which are neither read nor rebuilt.
  * GENERATION AND MOTION. A successful call adds 1 to pt_scene_generation and makes pt_scene_has_motion 0 until the next vertex
  * update: the previous positions describe a step the viewer has already seen, and a session must not reproject through them again.
  * The position buffers are kept; only the flag drops. So a frame preceded by a vertex update AND THEN an edit is no motion frame.

@@ -44,18 +44,12 @@ int main() {
     using namespace pt;
     // cacheNodes, cacheTris, wgWaves, cacheAttrs, cacheMats, cacheLights: every family stays below 64 KB at set 0 and crosses it at set 1
     const int sets[2][6] = {{63, 64, 4, 64, 10, 2}, {700, 100, 12, 100, 20, 4}};
-#ifdef PT_EXPERIMENTAL
-    const int nx = 8;           // also wide (1), compact (2), xcdBands (4)
-#else
-    const int nx = 1;
-#endif
     for (int integ : {0, 2}) for (int count = 0; count < 2; count++) for (int sync = 1; sync >= 0; sync--) for (int hbm = 0; hbm < 2; hbm++) for (int onchip = 0; onchip < 2; onchip++)
     for (int flat = 0; flat < 4; flat++) for (int simple = 0; simple < 2; simple++) for (int lean = 0; lean < 2; lean++) for (int refill = 0; refill < 2; refill++) for (int cull = 0; cull < 2; cull++)
-    for (int x = 0; x < nx; x++) for (int mo = 0; mo < 2; mo++) {
+    for (int mo = 0; mo < 2; mo++) {
         KParams P;
         memset(&P, 0, sizeof P);
         P.hbm = hbm; P.onchip = onchip; P.flat = flat; P.simple = simple; P.lean = lean; P.refill = refill; P.cull = cull;
-        P.wide = x & 1; P.compact = (x >> 1) & 1; P.xcdBands = (x >> 2) & 1;
         P.tileCount = 1;
         const MomentsK M = {nullptr, nullptr, 2, 0.5f};
         const MkRow* row = megakernel_choose(integ, count != 0, sync != 0, P, mo != 0);

@@ -254,24 +254,19 @@ def test_queue_waiters_that_give_up_do_not_fail_a_complete_frame(api, gpu_ready)
     sc.close()
 
 
-@pytest.mark.parametrize("knobs", [("0", "4", "0", "0", "2", "0", "512", "0"),      # everything off: a wave stays in each loop until its last lane
-                                   ("0", "4", "15", "15", "2", "0", "4", "2"),     # loops left as soon as ONE lane is through, shadow rays traced in the bounce
-                                   ("1", "1", "8", "8", "2", "0", "4", "2"),       # production shape, traversal left only for the last sixteenth
-                                   ("1", "15", "15", "1", "0", "0", "8", "1"),     # 4-wave kernel; traversal and node loop left at the first finished lane; speculation for closest-hit rays only
-                                   ("1", "4", "1", "15", "2", "0", "0", "2"),      # no time slices
-                                   ("1", "4", "8", "8", "2", "0", "4", "0"),       # resumable traversal without speculative descent
-                                   ("1", "4", "0", "0", "2", "0", "16", "2"),      # speculative descent with the loop exits off
-                                   ("2", "4", "8", "8", "1", "1", "4", "2")])      # REFILL also for the LDS-resident instantiation (A/B only)
+@pytest.mark.parametrize("knobs", [("0", "4", "0", "0", "2", "0", "512"),      # everything off: a wave stays in each loop until its last lane
+                                   ("0", "4", "15", "15", "2", "0", "4"),     # loops left as soon as ONE lane is through, shadow rays traced in the bounce
+                                   ("1", "1", "8", "8", "2", "0", "4"),       # production shape, traversal left only for the last sixteenth
+                                   ("1", "15", "15", "1", "0", "0", "8"),     # 4-wave kernel; traversal and node loop left at the first finished lane
+                                   ("1", "4", "1", "15", "2", "0", "0"),      # no time slices
+                                   ("1", "4", "8", "8", "2", "0", "4"),       # resumable traversal, a quarter of the busy lanes kept
+                                   ("1", "4", "0", "0", "2", "0", "16")])     # resumable traversal with the loop exits off
 def test_loop_exits_and_refill(api, gpu_ready, knobs):
     """pt_trace.h LoopExit / trace_resume: when a wave leaves its node loop, its triangle loop or the traversal
     (lanes that are through go on, the others resume later) is scheduling, not arithmetic — golden colours AND the
     per-pixel work counters bit for bit at every threshold, on all kernels (timed and counting instantiations)."""
-    opts = {k: int(v) for k, v in zip(("refill", "refill_keep", "node_keep", "tri_keep", "waves_hbm", "onchip", "slice_iters", "spec"), knobs)}
+    opts = {k: int(v) for k, v in zip(("refill", "refill_keep", "node_keep", "tri_keep", "waves_hbm", "onchip", "slice_iters"), knobs)}
     opts["sched_mask"] = 3
-    if not api.has_experimental():                       # default library: no speculative descent, no REFILL for LDS-resident scenes
-        del opts["spec"]
-        if opts["refill"] == 2:
-            pytest.skip("refill = 2 is an EXPERIMENTAL=1 build (DESIGN.md §6)")
     used = []
     for case in CASES:
         g = np.load(os.path.join(GOLDEN, case + ".npz"))
@@ -349,18 +344,14 @@ def test_render_fresh_scenes_vs_oracle(api, oracle, gpu_ready, scene_dir, integr
         assert_bits_equal(col, ocol, cfg)
 
 
-@pytest.mark.parametrize("layout", ["queue", "one_tile_per_wave", "xcd_bands"])
+@pytest.mark.parametrize("layout", ["queue", "one_tile_per_wave"])
 @pytest.mark.parametrize("integrator", [0, 2])
 def test_render_hand_built_deep_tree(api, oracle, gpu_ready, integrator, layout):
     """Array-level boundary + a tree deeper than the LDS stack, through the full render loop — in the 12-wave
-    workgroups of the kernel for scenes in HBM (shared scene cache, per-wave spill areas), fed by the tile queue,
-    one tile per wave (persistent=0) or in per-XCD bands."""
+    workgroups of the kernel for scenes in HBM (shared scene cache, per-wave spill areas), fed by the tile queue
+    or one tile per wave (persistent=0)."""
     opts = {"waves_hbm": 2}                              # the 6-wave kernel also for this 6-tile frame
     if layout == "one_tile_per_wave": opts["persistent"] = 0
-    if layout == "xcd_bands":
-        if not api.has_experimental():
-            pytest.skip("xcd_bands is an EXPERIMENTAL=1 build (DESIGN.md §6)")
-        opts["xcd_bands"] = 1
     arr = _chain_arrays(api)
     gs, osc = api.Scene.from_arrays(arr, options=opts), oracle.OracleScene(arrays=arr)
     cam = api.Camera.Pinhole((0, 0, 1), 24, 16)
@@ -723,7 +714,7 @@ def test_options_api(api, gpu_ready):
         for k in ("PT_FLAT", "PT_CULL", "PT_ONCHIP"):
             del os.environ[k]
     defaults = {"flat": 1, "onchip": 1, "waves_hbm": 1, "refill": 1, "refill_keep": 6, "node_keep": 10, "tri_keep": 8, "defer_shadow": 0,
-                "slice_iters": 512, "slice_always": 1, "sched_mask": 31, "lpt_prio": 2, "persistent": 1, "xcd_bands": 0, "culling": 0, "spec": 2, "simple": 1, "flat2": 1, "leaf_boxes": 1, "wide": 0, "compact": 0, "wf_wide_wg": 1, "lean": 1, "queue_timeout_ms": 30000}
+                "slice_iters": 512, "slice_always": 1, "sched_mask": 31, "lpt_prio": 2, "persistent": 1, "xcd_bands": 0, "culling": 0, "spec": 2, "simple": 1, "flat2": 1, "leaf_boxes": 1, "wide": 0, "compact": 0, "wf_wide_wg": 1, "lean": 1, "queue_timeout_ms": 30000, "moments_fused": 0}
     assert {k: sc.get_option(k) for k in defaults} == defaults
     sc.render(hs.camera(), 32, 32, 1, 4)
     assert sc.flags()["flat"] and sc.flags()["onchip"] and not sc.flags()["culling"]
@@ -732,14 +723,30 @@ def test_options_api(api, gpu_ready):
             sc.set_option(name, bad)
     sc.set_options({"flat": 0, "sched_mask": 7, "waves_hbm": 2})
     assert (sc.get_option("flat"), sc.get_option("sched_mask"), sc.get_option("waves_hbm")) == (0, 7, 2)
-    # variants that lost their A/B are not in the default library: only their "off" value is accepted (rc -3 otherwise)
-    for name, on in (("wide", 1), ("compact", 1), ("defer_shadow", 1), ("xcd_bands", 1), ("refill", 2), ("spec", 1)):
-        if api.has_experimental():
+    # variants that lost their A/B were removed: only their "off" value is accepted (rc -3 otherwise), and it is what reads back
+    assert not api.has_experimental()
+    for name, on in (("wide", 1), ("compact", 1), ("defer_shadow", 1), ("xcd_bands", 1), ("refill", 2), ("spec", 1), ("spec", 0)):
+        with pytest.raises(api.PtError, match="experimental"):
             sc.set_option(name, on)
-        else:
-            with pytest.raises(api.PtError, match="experimental"):
-                sc.set_option(name, on)
+        assert sc.get_option(name) == defaults[name]           # the refused set changed nothing: a retired option reads back its off value
         sc.set_option(name, defaults[name])
+    retired = {"wide": (0, 1), "compact": (0, 1), "defer_shadow": (0, 1), "xcd_bands": (0, 1), "spec": (0, 2)}      # name: its range
+    # every row of the table: both ends of its range are stored and read back, one step beyond either end is refused
+    ranges = {"flat": (0, 2), "onchip": (0, 1), "waves_hbm": (0, 2), "refill": (0, 1), "refill_keep": (0, 15), "node_keep": (0, 15), "tri_keep": (0, 15),
+              "slice_iters": (0, 1 << 30), "slice_always": (0, 1), "sched_mask": (0, (1 << 20) - 1), "lpt_prio": (0, 2), "persistent": (0, 1), "culling": (0, 1),
+              "simple": (0, 1), "flat2": (0, 1), "leaf_boxes": (0, 1), "wf_wide_wg": (0, 2), "lean": (0, 1), "queue_timeout_ms": (0, 1 << 22), "moments_fused": (0, 1)}
+    assert set(ranges) | set(retired) == set(defaults) and len(defaults) == 25
+    for name, (lo, hi) in ranges.items():
+        for v in (lo, hi):
+            sc.set_option(name, v)
+            assert sc.get_option(name) == v, (name, v)
+    beyond = dict(ranges, **retired, refill=(0, 2), sched_mask=(0, 1 << 20))                                        # the ranges the library states
+    for name, (lo, hi) in beyond.items():
+        for bad in (lo - 1, hi + 1):
+            with pytest.raises(api.PtError, match="outside"):
+                sc.set_option(name, bad)
+    sc.set_options(defaults)
+    assert {k: sc.get_option(k) for k in defaults} == defaults
 
 
 def _render_window(api, sc, cam, w, h, spp, md, rect, counters=False, integrator=0):
@@ -759,7 +766,7 @@ def _render_window(api, sc, cam, w, h, spp, md, rect, counters=False, integrator
     return col[y0:y1, x0:x1], (cnt[y0:y1, x0:x1] if counters else None)
 
 
-@pytest.mark.parametrize("mode", ["production", "generic_bounce", "generic_bounce_all_arms", "plain_loops_4wave", "counted", "wavefront", "compact"])
+@pytest.mark.parametrize("mode", ["production", "generic_bounce", "generic_bounce_all_arms", "plain_loops_4wave", "counted", "wavefront"])
 @pytest.mark.parametrize("case", window_cases())
 def test_real_scene_windows_vs_oracle(api, oracle, gpu_ready, scene_dir, case, mode):
     """BASELINE C3 / C4 / C5 geometry and depth at the 1080p camera, against the oracle: 64x64 windows of the 82 k-triangle
@@ -767,15 +774,13 @@ def test_real_scene_windows_vs_oracle(api, oracle, gpu_ready, scene_dir, case, m
     bounces, paths of up to 100 iterations) — the production kernel for scenes in HBM (12-wave workgroups, loop exits,
     REFILL; forced although a window has few tiles), the 4-wave kernel with plain loops, the counting kernel (all eight
     per-pixel counters) and the wavefront variant (C5). Committed fixture AND a live oracle run of the first window."""
-    if mode == "compact" and not api.has_experimental():
-        pytest.skip("compact nodes are an EXPERIMENTAL=1 build (DESIGN.md §6)")
     g = np.load(os.path.join(GOLDEN, case + ".npz"))
     s = window_scene(g, os.path.join(scene_dir, case))
     assert s["sha256"] == str(g["scene_sha256"])
     hs = api.HostScene(s["config"])
     w, h, spp, md, integ = int(g["w"]), int(g["h"]), int(g["spp"]), int(g["max_depth"]), int(g["integrator"])
     opts = {"production": {"waves_hbm": 2}, "generic_bounce": {"waves_hbm": 2, "simple": 0}, "generic_bounce_all_arms": {"waves_hbm": 2, "simple": 0, "lean": 0}, "plain_loops_4wave": {"waves_hbm": 0, "refill": 0, "node_keep": 0, "tri_keep": 0},
-            "counted": {"waves_hbm": 2}, "wavefront": {"wf_wide_wg": 2}, "compact": {"waves_hbm": 2, "compact": 1}}[mode]
+            "counted": {"waves_hbm": 2}, "wavefront": {"wf_wide_wg": 2}}[mode]
     sc = api.Scene(hs, options=opts)
     if mode == "wavefront":
         sc.set_variant("wavefront")
@@ -785,7 +790,7 @@ def test_real_scene_windows_vs_oracle(api, oracle, gpu_ready, scene_dir, case, m
         assert_bits_equal(col, g["colors"][k], "%s window %d (%s)" % (case, k, mode))
         if mode == "counted":
             assert np.array_equal(cnt, g["counters"][k]), (case, k)
-        if mode in ("production", "generic_bounce", "generic_bounce_all_arms", "compact"):
+        if mode in ("production", "generic_bounce", "generic_bounce_all_arms"):
             fl = sc.flags()
             assert fl["hbm_kernel"] and fl["refill"] and not fl["onchip"] and not fl["culling"], fl
             assert fl["simple"] == (not mode.startswith("generic_bounce")), fl          # both scenes are diffuse-only: the SIMPLE bounce is what production runs
@@ -1068,13 +1073,9 @@ def test_caller_tree_with_loose_boxes_takes_the_reference_walk(api, oracle, gpu_
 
 
 def test_tie_scenes_and_axis_parallel_rays_in_hbm_kernels(api, oracle, gpu_ready, scene_dir):
-    """The production kernel for scenes in HBM on the cases built for the opt-in trees (EXPERIMENTAL=1 builds add those:
-    pt_trace_experimental.h trace_resume_w4: SIMPLE scenes in HBM traverse the reference tree collapsed to 4-wide nodes, children in no
-    particular order; equal-t ties and rays with a zero direction component fall back to the reference traversal. A scene
-    whose every second quad is DOUBLED (each hit on them a two-way tie between different leaves), an axis-aligned camera
-    (primary rays with exact zero components), and a blob — against the oracle. Opt-in ("wide" = 1): measured slower.
-    The same cases for trace_resume_q ("compact" = 1: quantised inner nodes, exact leaf boxes, ties decided by a walk down
-    the reference's nodes; rays with a zero direction component read the reference's nodes in the same loop)."""
+    """The production kernel for scenes in HBM where the visiting order decides the image: a scene whose every second quad is
+    DOUBLED (each hit on them a two-way tie between different leaves), an axis-aligned camera (primary rays with exact zero
+    components), and a blob — against the oracle. (The cases were built for the 4-wide and the quantised tree)"""
     from cudapathtracer_amd import scenes
     cfgs = [scenes.blob_in_box(os.path.join(scene_dir, "wblob4"), 64, 40, 3, 8, subdiv=4, name="wblob4")["config"],
             scenes.cornell(os.path.join(scene_dir, "wtwin"), 48, 32, 4, 10, doubled=17, extra_boxes=7, ceiling_light=True, name="wtwin")["config"]]
@@ -1085,9 +1086,6 @@ def test_tie_scenes_and_axis_parallel_rays_in_hbm_kernels(api, oracle, gpu_ready
         for cam in (hs.camera(), api.Camera.NotPinhole((0.0, 0.0, 1.0), i["width"], i["height"], (0.0, 0.0, 0.0), 60.0, 0.0, 1.0)):
             ocol, _, _ = osc.render(camera=np.frombuffer(cam.tobytes(), np.uint8), threads=8)
             variants = ({"onchip": 0, "waves_hbm": 2}, {"onchip": 0, "waves_hbm": 2, "slice_iters": 8, "sched_mask": 3, "refill_keep": 12})
-            if api.has_experimental():
-                variants += ({"onchip": 0, "waves_hbm": 2, "wide": 1}, {"onchip": 0, "waves_hbm": 2, "wide": 1, "slice_iters": 8, "sched_mask": 3, "refill_keep": 12},
-                             {"onchip": 0, "waves_hbm": 2, "compact": 1}, {"onchip": 0, "waves_hbm": 2, "compact": 1, "slice_iters": 8, "sched_mask": 3, "refill_keep": 12})
             for opts in variants:
                 sc = api.Scene(hs, options=opts)
                 col, _ = sc.render(cam, i["width"], i["height"], i["spp"], i["max_depth"])

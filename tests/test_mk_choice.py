@@ -34,7 +34,7 @@ DRIVER = os.path.join(ROOT, "tests", "mk_choice_driver.hip")
 
 def invariants(i, parent_twin, experimental=False):
     """What render_tiles guarantees about the selector fields of every launch it makes (read off pt_api.hip; pt_set_option
-    refuses "refill" 2, "defer_shadow", "xcd_bands", "wide" and "compact" in a default build)."""
+    refuses "refill" 2, "defer_shadow", "xcd_bands", "wide" and "compact": the record's inputs carry none of the last three)."""
     imp = lambda a, b: (not a) or b
     wide, compact, bands = i.get("wide", 0), i.get("compact", 0), i.get("xcdBands", 0)
     ok = imp(i["hbm"], not i["onchip"])

@@ -38,10 +38,15 @@ def test_a_null_scene_has_made_no_launches(api):
     assert api.lib().pt_last_moments_launches(None) == -1
 
 
-def test_the_option_is_the_last_row_of_the_table():
-    """The experimental-option gate of pt_set_option indexes the option table by position: a new option goes at its end."""
+def test_the_table_keeps_its_25_names_and_has_no_positions():
+    """Every option is one row of kOptions that says where its value lives; pt_set_option / pt_get_option look the row up by name
+    and never by position, so a new row may go anywhere."""
     src = open(os.path.join(ROOT, "cudapathtracer_amd", "csrc", "pt_api.hip")).read()
-    table = re.search(r"const OptionRef kOptions\[\] = \{(.*?)\n\};", src, flags=re.S).group(1)
-    names = re.findall(r'\{"(\w+)",', table)
-    assert names[-1] == "moments_fused" and names[:4] == ["flat", "onchip", "waves_hbm", "refill"] and names[-2] == "queue_timeout_ms", names
-    assert names.index("defer_shadow") == 7 and names.index("xcd_bands") == 13 and names.index("spec") == 15 and names.index("wide") == 19 and names.index("compact") == 20
+    table = re.search(r"const Option kOptions\[\] = \{(.*?)\n\};", src, flags=re.S).group(1)
+    names = re.findall(r'\{"(\w+)", -?\d', table)
+    assert sorted(names) == sorted(["flat", "onchip", "waves_hbm", "refill", "refill_keep", "node_keep", "tri_keep", "defer_shadow", "slice_iters", "slice_always",
+                                    "sched_mask", "lpt_prio", "persistent", "xcd_bands", "culling", "spec", "simple", "flat2", "leaf_boxes", "wide", "compact",
+                                    "wf_wide_wg", "lean", "queue_timeout_ms", "moments_fused"]), names
+    for fn in ("pt_set_option", "pt_get_option"):
+        body = re.search(r"^int %s\(.*?^}" % fn, src, flags=re.S | re.M).group(0)
+        assert "switch" not in body and not re.search(r"\b(k|i) == \d", body) and not re.search(r"kOptions\[\d", body), body

@@ -15,14 +15,10 @@ a = ap.parse_args()
 res = {n: [] for n in a.names}
 for r in range(a.rounds):
     for n in a.names:
-        base, _, opt = n.partition("+")              # "v3+defer" = lib_v3.so with --opt defer_shadow=1
+        base, _, opt = n.partition("+")              # "v3+lean=0" = lib_v3.so with --opt lean=0: any pt_set_option
         lib = os.path.join(ROOT, "cudapathtracer_amd", "csrc", "variants", "lib_%s.so" % base)
         env = dict(os.environ, PT_LIB_PATH=lib)
-        extra = []
-        if opt == "defer":
-            extra = ["--opt", "defer_shadow=1"]
-        elif "=" in opt:                             # "base+compact=1": any pt_set_option
-            extra = ["--opt", opt]
+        extra = ["--opt", opt] if "=" in opt else []
         if a.golden and r == 0:
             t = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_parity.py", "-q", "-x", "-m", "gpu", "-k", "golden or fresh or deep"], cwd=ROOT, env=env, capture_output=True, text=True)
             print(n, "parity:", t.stdout.strip().splitlines()[-1] if t.stdout.strip() else t.stderr[-300:], flush=True)
