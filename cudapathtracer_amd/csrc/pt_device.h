@@ -83,6 +83,16 @@ PT_DEV float rcp_exact(float a) {
 #endif
 constexpr bool kArmInv3 = (PT_LOGIC_ARMS & 1) != 0, kArmOnb = (PT_LOGIC_ARMS & 2) != 0, kArmMis = (PT_LOGIC_ARMS & 4) != 0,
                kArmNorm = (PT_LOGIC_ARMS & 8) != 0, kArmDead = (PT_LOGIC_ARMS & 16) != 0;
+// The pair kernels' pair pass (pt_trace.h: trace_pair_flat), behind the same template switch ARMS and built the
+// same way (-DPT_PAIR_CURSOR=n):
+//   1 the rays' range bounds leave the trips: a trip accepts every positive finite t, the ray's owner applies the bound to the minimum
+//   2 one place for a slot's second minimum, in the rows the bounds freed: the lane's cursor is two registers (needs 1)
+//   4 the leaf loop folds a leaf's triangle mask in with (h & m) | acc, the mask word as the scalar operand
+#ifndef PT_PAIR_CURSOR
+#define PT_PAIR_CURSOR 3
+#endif
+constexpr bool kPairBound = (PT_PAIR_CURSOR & 1) != 0, kPairOneB = (PT_PAIR_CURSOR & 2) != 0, kPairAndOr = (PT_PAIR_CURSOR & 4) != 0;
+static_assert(!kPairOneB || kPairBound, "the uniform second minimum lives in the LDS rows that the bounds leave");
 PT_DEV float rsqrt_(float x) { return rcp_exact(__builtin_sqrtf(x)); }    // rsqrtf := 1/sqrt, both correctly rounded
 PT_DEV V3 normalize(V3 v) { float il = rsqrt_(dot(v, v)); return V3{v.x * il, v.y * il, v.z * il}; }   // util.cuh:128-131
 PT_DEV float length(V3 v) { return __builtin_sqrtf(dot(v, v)); }

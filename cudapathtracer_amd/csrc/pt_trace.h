@@ -810,6 +810,12 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 //   The slots' exclusive prefixes (128 words) live where the 128 minima go until the owner search has read them.
 // A slot's minimum is a hit iff its high word is not ~0u (no hit has a NaN's bit pattern for t): with PT_PAIR_MIN_ALWAYS
 // every trip folds a key into both minima, a miss as (~0u, index) — min with it keeps a hit and leaves a miss a miss.
+// The pair kernels (ARMS; pt_device.h: PT_PAIR_CURSOR) keep no bounds in the scratch: a trip accepts every positive finite t, and
+// the ray's owner applies the bound to the minimum in stage 3 (BOUND, the proof stands at `put`). The two rows of the bounds hold
+// the second minimum of EVERY slot instead (ONEB), 1024 bytes behind its first — records 4096 B, 128 u64 first minima 1024 B
+// (an extension slot's (t, first index), a shadow slot's occlusion word), 128 u64 second minima 1024 B (an extension slot's
+// (t, last index), a shadow slot's dummy that nothing reads): 24 rows as before. A lane's cursor is then two registers, the
+// record's address and the first minimum's. The prefixes (at most 192 words) still live in the minima's 512.
 #ifndef PT_PAIR_MIN_ALWAYS
 #define PT_PAIR_MIN_ALWAYS 0
 #endif
@@ -822,9 +828,11 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     lds_i32* Wd = st.lds - lane;
     // (the prefixes share the minima's words: every lane of the wave has finished the owner search before the minima are set —
     // 24 x 256 B per wave instead of 25, which is what lets a fifth 4-wave workgroup fit a CU's 160 KB next to its copy of the
-    // Cornell scene)
+    // Cornell scene; ONEB spends the same 24 on records and 2 x 128 minima)
     typedef __attribute__((address_space(3))) f4v lds_f4;
-    constexpr int kMax = 8 * 128, kKeyA = 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
+    constexpr bool BOUND = ARMS && kPairBound, ONEB = ARMS && kPairOneB;
+    constexpr int kMax = 8 * 128, kKeyA = ONEB ? 8 * 128 : 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
+    static_assert(kKeyB + (ONEB ? 256 : 128) == 24 * 64 && (ONEB || kMax + 128 == kKeyA), "records, (bounds,) first minima, second minima: 24 rows of 64 words");
     lds_f4* Rec = (lds_f4*)Wd;                                    // slot v's record: Rec[2 v], Rec[2 v + 1] (the scene cache before the stacks is whole 16-byte records)
     V3 invE, invS;
     if constexpr (ARMS && kArmInv3) { invE = inv3_uniform(ed, hasExt); invS = inv3_uniform(sd, hasShadow); }      // (see inv3_uniform: read only where the lane has the ray)
@@ -833,13 +841,33 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     uint64_t tmE = 0ull, tmS = 0ull;
     if (S.rootRef < 0) { const uint64_t all = ~0ull >> (64 - S.nTris); tmE = hasExt ? all : 0ull; tmS = hasShadow ? all : 0ull; }
     else if (nLeaves > 0 && __builtin_amdgcn_ballot_w64((hasExt && !inv_is_regular(invE)) || (hasShadow && !inv_is_regular(invS))) == 0ull) {
-        _Pragma("unroll 2")
-        for (int k = 0; k < nLeaves; ++k) {                       // the leaves' own boxes, both rays (see inv_is_regular)
-            const LeafBox L = leaf_box(leaves, k);                // through the scalar cache: SGPR operands of the slab tests
-            const bool eH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, eo, invE);
-            const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
-            const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;      // s_bfm_b64 (a leaf of a tree with two or more leaves holds < 64 triangles)
-            tmE |= eH ? m : 0ull; tmS |= sH ? m : 0ull;
+        if constexpr (ARMS && kPairAndOr) {
+            // (h & m) | acc per word with the mask word as the one scalar operand (v_and_or_b32): three instructions per test where
+            // the select takes four, its mask words moved to VGPRs first. h is made opaque, or the compiler folds the form back into
+            // the select; the opaque statement keeps its runtime unroll away too, so the two leaves of a trip are written out
+            auto leaf1 = [&](int k) {
+                const LeafBox L = leaf_box(leaves, k);
+                const bool eH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, eo, invE);
+                const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
+                const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;
+                uint32_t hE = eH ? ~0u : 0u, hS = sH ? ~0u : 0u;
+                asm("" : "+v"(hE)); asm("" : "+v"(hS));
+                const uint32_t mLo = (uint32_t)m, mHi = (uint32_t)(m >> 32);
+                tmE = (uint64_t)((hE & mLo) | (uint32_t)tmE) | ((uint64_t)((hE & mHi) | (uint32_t)(tmE >> 32)) << 32);
+                tmS = (uint64_t)((hS & mLo) | (uint32_t)tmS) | ((uint64_t)((hS & mHi) | (uint32_t)(tmS >> 32)) << 32);
+            };
+            int k = 0;
+            for (; k + 2 <= nLeaves; k += 2) { leaf1(k); leaf1(k + 1); }
+            if (k < nLeaves) leaf1(k);
+        } else {
+            _Pragma("unroll 2")
+            for (int k = 0; k < nLeaves; ++k) {                       // the leaves' own boxes, both rays (see inv_is_regular)
+                const LeafBox L = leaf_box(leaves, k);                // through the scalar cache: SGPR operands of the slab tests
+                const bool eH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, eo, invE);
+                const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
+                const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;      // s_bfm_b64 (a leaf of a tree with two or more leaves holds < 64 triangles)
+                tmE |= eH ? m : 0ull; tmS |= sH ? m : 0ull;
+            }
         }
         tmE = hasExt ? tmE : 0ull; tmS = hasShadow ? tmS : 0ull;     // (once, not per leaf)
     } else {
@@ -898,10 +926,21 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     // T in [1, 0x7f800000] (positive, +inf included) orders like its value, so T - 1 < M - 1 <=> t < max_t. A shadow ray's
     // smaxt may be <= 0 or NaN, and then nothing passes `t > 0 && t < smaxt`: it is stored as the smallest positive float
     // (M - 1 = 0: nothing passes either).
+    // BOUND: the trips know no bound. A trip accepts iff f2u(t) - 1 < 0x7f7fffff — by the cases above, exactly the positive finite
+    // t (T in [1, 0x7f7fffff]; +inf, T - 1 = 0x7f7fffff, is out, as it is under every bound: M - 1 <= 0x7f7fffff) — and stage 3
+    // compares the minimum m of the accepted t with the ray's bound b, as floats, before anything else reads it. The accepted
+    // set A contains every t the bounded rule accepts (0 < t < b implies positive and finite), and accepted bit patterns order
+    // like their values. Shadow ray: "some t has 0 < t < smaxt" <=> "A is not empty and m < smaxt" (=>: m <= that t; <=: m is
+    // such a t). A smaxt that is <= 0 or NaN makes `m < smaxt` false for every positive m, which is the stored smallest positive
+    // float's "nothing passes"; smaxt = +inf accepts every finite m, as M - 1 = 0x7f7fffff does. An empty A leaves ~0u in the
+    // word, a NaN as a float: `m < b` is false, no separate test for "no hit". Extension ray (b = 999999): if m >= b no t was
+    // below b and the ray misses, as it did; else m is also the minimum of the t below b, and every t equal to m is below b,
+    // so (m, first index), (m, last index) and the tied set are the bounded rule's. More keys enter the minima (the ceiling
+    // behind the light, for one), no arithmetic changes.
     auto put = [&](int v, V3 ro, V3 rd, float mt, uint64_t tm, int pre) {
         Rec[2 * v] = f4v{ro.x, ro.y, ro.z, rd.x};
         Rec[2 * v + 1] = f4v{rd.y, rd.z, __builtin_bit_cast(float, (uint32_t)tm), __builtin_bit_cast(float, (uint32_t)(tm >> 32))};
-        Wd[kMax + v] = (int32_t)(f2u(mt > 0.0f ? mt : 1.401298464e-45f) - 1u);
+        if constexpr (!BOUND) Wd[kMax + v] = (int32_t)(f2u(mt > 0.0f ? mt : 1.401298464e-45f) - 1u);
         Wd[kPre + v] = pre;
     };
     if (nE > 0) put(slotE, eo, ed, 999999.0f, tmE, preE);
@@ -920,13 +959,13 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     lds_u64* pA = kA;
     lds_u64* pB = kA;
     lds_u64* const kAE = kA + cntE;                                // the first shadow slot's minimum
-    auto fetch = [&]() {                                           // three LDS reads: the slot's record and its bound
+    auto fetch = [&]() {                                           // three LDS reads: the slot's record and its bound (BOUND: two, no bound)
         const f4v a = pR[0], b = pR[1];
         rem = (uint64_t)f2u(b.z) | ((uint64_t)f2u(b.w) << 32);
         ro = v3(a.x, a.y, a.z);
         rd = v3(a.w, b.x, b.y);
-        rmax1 = (uint32_t)*pM;
-        pB = pA < kAE ? pA + (kKeyB - kKeyA) / 2 : pA;            // a shadow ray's two minima both go to its occlusion word
+        if constexpr (!BOUND) rmax1 = (uint32_t)*pM;
+        if constexpr (!ONEB) pB = pA < kAE ? pA + (kKeyB - kKeyA) / 2 : pA;      // a shadow ray's two minima both go to its occlusion word (ONEB: pA + 128, always)
     };
     if (per > 0) {                                                // wave-uniform
         // Every lane runs exactly `per` tests, [p, p + per): the last lanes start early enough to stay inside [0, total) and repeat
@@ -939,38 +978,60 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
         pR = Rec + 2 * l; pM = Wd + kMax + l; pA = kA + l;
         fetch();
         rem &= ~((1ull << select64(rem, p - Wd[kPre + l])) - 1ull);
+        // (the record's other half may still be in flight here, and the compiler then guards the trips' fetch into the same
+        // registers with a wait of its own, once per trip: wait here, once per pass, for reads that have long returned)
+        if constexpr (BOUND) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     }
-    wave_lds_sync();                                              // every lane has read its prefixes ...
-    kA[lane] = ~0ull; kA[64 + lane] = ~0ull; kB[lane] = ~0ull;     // ... the minima take their place
-    wave_lds_sync();
-    for (int trip = 0; trip < per; ++trip) {                      // wave-uniform loop
-        if (rem == 0ull) { pR += 2; pM++; pA++; fetch(); }        // the next slot has tests, and it exists: the lane's tests end below `total`
-        const int ti = __builtin_ctzll(rem);
-        rem &= rem - 1ull;
-        const TriEdges q = load_tri_edges(C, ti);
-        float t, u, v;
-        const bool uvOk = moller_trumbore_sel_uv(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e2z), ro, rd, t, u, v);
-        const bool ok = uvOk & (f2u(t) - 1u < rmax1);             // t > 0 && t < max_t (see put)
+    // BOUND: a pass without tests (per == 0: no lane has a ray with a test) reads no minimum in stage 3, and the trips sit behind the same
+    // wave-uniform test as their set-up — no second guard in front of the loop, and the code of stage 3 stays behind it
+    if (!BOUND || per > 0) {
+        wave_lds_sync();                                              // every lane has read its prefixes ...
+        if constexpr (ONEB) {                                          // ... the minima take their place: all 256, sixteen bytes a lane and write
+            typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+            typedef __attribute__((address_space(3))) u4v lds_u4;
+            ((lds_u4*)kA)[lane] = u4v{~0u, ~0u, ~0u, ~0u}; ((lds_u4*)kB)[lane] = u4v{~0u, ~0u, ~0u, ~0u};
+        } else { kA[lane] = ~0ull; kA[64 + lane] = ~0ull; kB[lane] = ~0ull; }
+        wave_lds_sync();
+        // BOUND: the one bound of all trips lives in a VGPR. As a known constant it is a literal, which the VOP3 compare that the
+        // compiler first selects cannot hold: it comes back as an s_mov_b32 inside the loop, one SALU instruction per trip
+        uint32_t rmaxAll = 0x7f7fffffu;
+        if constexpr (BOUND) asm("" : "+v"(rmaxAll));
+        for (int trip = 0; trip < per; ++trip) {                      // wave-uniform loop
+            if (rem == 0ull) {                                        // the next slot has tests, and it exists: the lane's tests end below `total`
+                pR += 2;
+                if constexpr (!BOUND) pM++;
+                pA++;
+                fetch();
+            }
+            const int ti = __builtin_ctzll(rem);
+            rem &= rem - 1ull;
+            const TriEdges q = load_tri_edges(C, ti);
+            float t, u, v;
+            const bool uvOk = moller_trumbore_sel_uv(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e2z), ro, rd, t, u, v);
+            const bool ok = uvOk & (f2u(t) - 1u < (BOUND ? rmaxAll : rmax1));     // t > 0 && t < max_t; BOUND: t positive and finite (see put)
 #if PT_PAIR_MIN_ALWAYS
-        const uint64_t tb = (uint64_t)(ok ? f2u(t) : ~0u) << 32;  // a miss: (~0u, index), which changes no minimum's hit state
-        __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_min(pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-        if (ok) {                                                 // the same two minima for both kinds of ray: no branch on the kind
-            const uint64_t tb = (uint64_t)f2u(t) << 32;
+            const uint64_t tb = (uint64_t)(ok ? f2u(t) : ~0u) << 32;  // a miss: (~0u, index), which changes no minimum's hit state
             __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_min(pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+            __hip_atomic_fetch_min(ONEB ? pA + (kKeyB - kKeyA) / 2 : pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+            if (ok) {                                                 // the same two minima for both kinds of ray: no branch on the kind
+                const uint64_t tb = (uint64_t)f2u(t) << 32;
+                __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_min(ONEB ? pA + (kKeyB - kKeyA) / 2 : pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
 #endif                                                            // (NOLEAF: any hit below max_t ends the shadow ray, BVHShadowRay returns 0)
+        }
     }
     wave_lds_sync();
-    // 3. results: the shadow ray's throughput, the extension ray's winner (ties as in trace_closest_flat)
+    // 3. results: the shadow ray's throughput, the extension ray's winner (ties as in trace_closest_flat). BOUND: the bound meets the
+    // minimum here, once, as a float compare that is false for "no hit" (~0u: a NaN) as well (see put)
     const uint64_t occ = kA[slotS];                               // (slotS < 128 and slotE < 64 are in range whether or not the entry has a slot)
-    thr = (nS > 0 && (uint32_t)(occ >> 32) != ~0u) ? v3(0.0f) : v3(1.0f);      // (nS > 0: hasShadow)
+    if constexpr (BOUND) { const bool occluded = __builtin_bit_cast(float, (uint32_t)(occ >> 32)) < smaxt; thr = (nS > 0 && occluded) ? v3(0.0f) : v3(1.0f); }
+    else thr = (nS > 0 && (uint32_t)(occ >> 32) != ~0u) ? v3(0.0f) : v3(1.0f);      // (nS > 0: hasShadow)
     hit.tri = -1; hit.t = 0.0f; hit.u = 0.0f; hit.v = 0.0f; hit.material = 0;
     if (nE > 0) {                                                 // (hasExt; with no test the ray misses)
         const uint64_t a = kA[slotE], b = kB[slotE];
-        if ((uint32_t)(a >> 32) != ~0u) {
+        if (BOUND ? __builtin_bit_cast(float, (uint32_t)(a >> 32)) < 999999.0f : (uint32_t)(a >> 32) != ~0u) {
             int win = (int)(uint32_t)a;
             const int last = 63 - (int)(uint32_t)b;
             if (win != last) {
