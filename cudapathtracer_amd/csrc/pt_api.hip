@@ -78,8 +78,8 @@ struct pt_scene {
     // pointer-to-member, so an option's switch is an int); the library reads no environment variable.
     int schedMask = 31;          // "sched_mask": scheduling checks every schedMask + 1 bounce iterations (tests use 3)
     int sliceAlways = 1;         // "slice_always" 0: slices only once no fresh tile is left
-    bool wavesHbmOk = PT_WAVES_HBM > 0;   // "waves_hbm" 0: scenes in HBM use the 4-waves-per-SIMD kernel too (A/B)
-    int nodeKeep = 10, triKeep = 8;        // "node_keep" / "tri_keep" (pt_trace.h: LoopExit)
+    bool wavesHbmOk = true;   // "waves_hbm" 0: scenes in HBM use the 4-waves-per-SIMD kernel too (A/B)
+    int nodeKeep = 10, triKeep = 8;        // "node_keep" / "tri_keep" (pt_trace.h: Keep)
     int refill = 1, refillKeep = 6;       // "refill" / "refill_keep": REFILL instantiation of the kernel for scenes in HBM (pt_trace.h: trace_resume)
     bool refillKeepSet = false;           // (unset: the 4-wave kernel of small shares uses kRefillKeepSmall — it is chain-bound and wants its lanes back sooner)
     int cull = 0;                         // pt_set_culling / "culling": opt-in, not parity-exact by construction
@@ -345,13 +345,11 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
             }
         }
     }
-#ifndef PT_NODE_ORDER_AREA
-#define PT_NODE_ORDER_AREA 1        // 0: plain breadth-first numbering (A/B: 82 k triangles 765 -> 729 ms at 128 spp, 263 k 387 -> 379 ms at 16 spp, 7.5 % fewer node fetches from global memory; profiles/r03_ab_node_order_area.log)
-#endif
-#if PT_NODE_ORDER_AREA
     // Scenes in HBM: the kernels keep PNodes [0, K) in LDS, so number the internal nodes by how often rays visit them rather
     // than by level — a ray enters a box with a probability proportional to its surface area (the SAH's own estimate), and a
     // child's box lies inside its parent's, so descending area (ties: breadth-first order) still numbers parents first.
+    // (Against plain breadth-first numbering: 82 k triangles 765 -> 729 ms at 128 spp, 263 k 387 -> 379 ms at 16 spp, 7.5 % fewer
+    // node fetches from global memory; profiles/r03_ab_node_order_area.log)
     if (nInternal > 128) {
         std::vector<float> area((size_t)nInternal, 0.0f);
         for (int i = 0; i < nN; i++) {
@@ -368,7 +366,6 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         for (int k = 0; k < nInternal; k++) rank[order[k]] = k;
         for (int i = 0; i < nN; i++) if (internalId[i] >= 0) internalId[i] = rank[internalId[i]];
     }
-#endif
     auto childRef = [&](int c) -> int32_t { return d->bvh[c].primCount > 0 ? ~d->bvh[c].first : internalId[c]; };
     nodes.assign(std::max(nInternal, 1), PNode{});
     std::vector<uint8_t> leafEnd(nT, 0);
@@ -521,7 +518,6 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
 // the records the device builder packed into s->nodes. Through the host: one download and one upload of the internal nodes.
 static int renumber_by_area(pt_scene* s, int nInternal, int rootRef) {
     s->renumberMs = 0.0f;
-#if PT_NODE_ORDER_AREA
     const double t0 = wall_ms();
         if (nInternal > 128 && rootRef == 0) {
             std::vector<PNode> pn((size_t)nInternal);
@@ -561,7 +557,6 @@ static int renumber_by_area(pt_scene* s, int nInternal, int rootRef) {
             }
             s->renumberMs = (float)(wall_ms() - t0);
         }
-#endif
     return 0;
 }
 
@@ -1935,7 +1930,7 @@ int removed(const char* name, int v) {
 const Option kOptions[] = {
     {"flat", 0, 2, &pt_scene::flatWanted}, {"onchip", 0, 1, &pt_scene::onchipOk},
     {"waves_hbm", 0, 2, nullptr,
-     [](pt_scene* s, int v) { s->wavesHbmOk = v != 0 && PT_WAVES_HBM > 0; s->wavesHbmForce = s->wavesHbmOk && v == 2; return 0; },
+     [](pt_scene* s, int v) { s->wavesHbmOk = v != 0; s->wavesHbmForce = s->wavesHbmOk && v == 2; return 0; },
      [](const pt_scene* s) { return s->wavesHbmForce ? 2 : (s->wavesHbmOk ? 1 : 0); }},
     {"refill", 0, 2, nullptr,            // (2 was REFILL for LDS-resident scenes: removed)
      [](pt_scene* s, int v) { if (v == 2) return removed("refill", v); s->refill = v; return 0; },

@@ -41,15 +41,13 @@ PT_DEV float fmaxf_(float a, float b) { return __builtin_fmaxf(a, b); }
 // 1.0f / a, correctly rounded, in 4 instructions instead of the 11 of the IEEE division sequence: v_rcp_f32 + one Newton
 // step is bit-identical to the IEEE quotient for EVERY binary32 a with 1e-12 <= |a| <= 1e30 on gfx950 (exhaustive run over
 // all 2^32 inputs on the hardware, tools/exhaustive/rcp_check.hip); anything else (zero, denormal-range, huge, inf, NaN)
-// takes the IEEE sequence. PT_FAST_RCP=0 builds the plain division everywhere (A/B, and the reference point of that proof).
-#ifndef PT_FAST_RCP
-#define PT_FAST_RCP 1
-#endif
+// takes the IEEE sequence.
+// PT_RCP_UNIFORM is the one build switch with two live values: 1 here, 0 in pt_mk_hbm.hip, which defines it before its includes.
 #ifndef PT_RCP_UNIFORM
 #define PT_RCP_UNIFORM 1
 #endif
 PT_DEV float rcp_exact(float a) {
-#if PT_FAST_RCP && PT_RCP_UNIFORM
+#if PT_RCP_UNIFORM
     // The range test is wave-uniform, not per lane: every lane computes the fast form, and only when some lane of the wave is
     // outside its range (practically never) do the lanes run the full division and those lanes take it. A per-lane `if` costs an
     // exec-mask save / restore and two skip branches at every call site, and the LDS-resident kernels are bound by instruction
@@ -61,38 +59,24 @@ PT_DEV float rcp_exact(float a) {
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!inRange) != 0ull, 0)) r = inRange ? r : 1.0f / a;
     return r;
 #else
-#if PT_FAST_RCP
     const float m = __builtin_fabsf(a);
     if (m >= 1e-12f && m <= 1.0e30f) {
         const float r0 = __builtin_amdgcn_rcpf(a);
         return __builtin_fmaf(r0, __builtin_fmaf(-a, r0, 1.0f), r0);
     }
-#endif
     return 1.0f / a;
 #endif
 }
 // The pair kernels' logic step: forms that issue a sequence once per wave where two exclusive arms each
-// carried their own copy, or that leave out work nothing reads. Same IEEE operations on the same operands per lane. One bit per
-// step, so that A/B variants build from one tree (-DPT_LOGIC_ARMS=n); the template switch ARMS (pt_megakernel.h) turns them on
-// for the pair kernels only, every other kernel keeps its code.
-//   1 inv3 of a ray the lane does not have   2 one basis normalise   4 one light pdf and MIS weight for the emitter and the NEE arm
-//   8 one direction normalise for bounce and regeneration           16 the `o` select of a SIMPLE bounce
-// 16 is off: exact, eight static instructions less, and 0.3 % SLOWER in both A/B forms (profiles/r07_ab_logic_arms.log).
-#ifndef PT_LOGIC_ARMS
-#define PT_LOGIC_ARMS 15
-#endif
-constexpr bool kArmInv3 = (PT_LOGIC_ARMS & 1) != 0, kArmOnb = (PT_LOGIC_ARMS & 2) != 0, kArmMis = (PT_LOGIC_ARMS & 4) != 0,
-               kArmNorm = (PT_LOGIC_ARMS & 8) != 0, kArmDead = (PT_LOGIC_ARMS & 16) != 0;
-// The pair kernels' pair pass (pt_trace.h: trace_pair_flat), behind the same template switch ARMS and built the
-// same way (-DPT_PAIR_CURSOR=n):
-//   1 the rays' range bounds leave the trips: a trip accepts every positive finite t, the ray's owner applies the bound to the minimum
-//   2 one place for a slot's second minimum, in the rows the bounds freed: the lane's cursor is two registers (needs 1)
-//   4 the leaf loop folds a leaf's triangle mask in with (h & m) | acc, the mask word as the scalar operand
-#ifndef PT_PAIR_CURSOR
-#define PT_PAIR_CURSOR 3
-#endif
-constexpr bool kPairBound = (PT_PAIR_CURSOR & 1) != 0, kPairOneB = (PT_PAIR_CURSOR & 2) != 0, kPairAndOr = (PT_PAIR_CURSOR & 4) != 0;
-static_assert(!kPairOneB || kPairBound, "the uniform second minimum lives in the LDS rows that the bounds leave");
+// carried their own copy, or that leave out work nothing reads. Same IEEE operations on the same operands per lane. The template
+// switch ARMS (pt_megakernel.h) turns them on for the pair kernels only, every other kernel keeps its code:
+//   inv3 of a ray the lane does not have is not computed (pt_trace.h: inv3_uniform)   one basis normalise (onb_of)
+//   one light pdf and MIS weight for the emitter and the NEE arm (pt_path.h: bounce_core)
+//   one direction normalise for bounce and regeneration (kDirRaw)
+// (measured step by step: profiles/r07_ab_logic_arms.log)
+// ARMS also selects the pair kernels' pair pass (pt_trace.h: trace_pair_flat):
+//   the rays' range bounds leave the trips: a trip accepts every positive finite t, the ray's owner applies the bound to the minimum
+//   one place for a slot's second minimum, in the rows the bounds freed: the lane's cursor is two registers
 PT_DEV float rsqrt_(float x) { return rcp_exact(__builtin_sqrtf(x)); }    // rsqrtf := 1/sqrt, both correctly rounded
 PT_DEV V3 normalize(V3 v) { float il = rsqrt_(dot(v, v)); return V3{v.x * il, v.y * il, v.z * il}; }   // util.cuh:128-131
 PT_DEV float length(V3 v) { return __builtin_sqrtf(dot(v, v)); }

@@ -180,16 +180,13 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     // the logic step (private segment 52 -> 56 B in the LEAN one, which tests/test_isa.py pins), for one test in eleven.
     constexpr bool LTRI = DEFER && FLAT && SIMPLE;
     // ARMS: the logic step and the head of the pair pass issue once per wave what two exclusive arms each carried, and leave out
-    // what nothing reads (pt_device.h: PT_LOGIC_ARMS; pt_path.h: bounce_core; pt_trace.h: inv3_uniform) — the two timed pair kernels,
+    // what nothing reads (listed in pt_device.h; pt_path.h: bounce_core; pt_trace.h: inv3_uniform) — the two timed pair kernels,
     // which run at the CU's instruction-issue ceiling, and their moments twins. Every other instantiation keeps its code byte for
     // byte: the kernels at 64 and 80 VGPRs have lost their scratch pins to a single extra select before.
     constexpr bool ARMS = DEFER && FLAT && (SIMPLE || LEAN);
     // (... and for the 4-wave SIMPLE kernel that small shares of a scene in HBM run — 128 VGPRs, chain-bound: 1/8 shares +4-5 %,
     //  profiles/r03_shards_hbm_final.log; the 8-wave kernel at 64 VGPRs loses 1-6 % to it)
-#ifndef PT_TRISEL_SIMPLE4
-#define PT_TRISEL_SIMPLE4 1
-#endif
-    constexpr bool TRISEL = ((PT_TRISEL_LEAN != 0 && LEAN && !SIMPLE) || (PT_TRISEL_SIMPLE4 != 0 && SIMPLE && STACKN == kStackLds)) && !ONCHIP && !COUNT;      // pt_trace.h: moller_trumbore_sel
+    constexpr bool TRISEL = ((LEAN && !SIMPLE) || (SIMPLE && STACKN == kStackLds)) && !ONCHIP && !COUNT;      // pt_trace.h: moller_trumbore_sel
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nW = blockDim.x >> 6;      // nW waves share this workgroup's scene cache
     DeviceScene S = P.S;
     // ONCHIP kernels: the host guarantees that the bounce's records fit as well (pt_api.hip: `onchip`), so their address
@@ -234,20 +231,10 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     const int tile = P.tileFirst + lt * P.tileStride;
     // (the pixel coordinates are re-derived from the wave-uniform tile origin where they are needed — the start of a sample —
     // instead of living in two VGPRs across every traversal)
-#ifndef PT_XY_VGPR
-#define PT_XY_VGPR 0
-#endif
-#if PT_XY_VGPR
-    const int tileX0 = (tile % P.tilesX) * 8 + (lane & 7), tileY0 = (tile / P.tilesX) * 8 + (lane >> 3);      // (per-lane x, y)
-    const bool inImage = (tileX0 < P.w) && (tileY0 < P.h);
-#define PT_PX (tileX0)
-#define PT_PY (tileY0)
-#else
     const int tileX0 = (tile % P.tilesX) * 8, tileY0 = (tile / P.tilesX) * 8;
     const bool inImage = (tileX0 + (lane & 7) < P.w) && (tileY0 + (lane >> 3) < P.h);
 #define PT_PX (tileX0 + (lane & 7))
 #define PT_PY (tileY0 + (lane >> 3))
-#endif
 
     const int cacheBytes = P.cacheNodes * 64 + P.cacheTris * 48;
     Stack<STACKN> st;
@@ -290,12 +277,6 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     auto shadowSync = [&](V3 ro, V3 wi, float maxt) {
         PT_STAMP(2);
         V3 t_ = trace_shadow<COUNT, STACKN, ONCHIP, CULL, SIMPLE || LEAN>(S, SC, ro, wi, maxt, st, c, Keep{P.nodeKeep, P.triKeep});
-#ifdef PT_DIAG_DOUBLE_SHADOW        // cost measurement only (tools/phase_cost.sh): the shadow ray traced twice, same result
-        {
-            const V3 t2_ = trace_shadow<COUNT, STACKN, ONCHIP, CULL, SIMPLE || LEAN>(S, SC, ro, wi, maxt, st, c, Keep{P.nodeKeep, P.triKeep});
-            t_ = v3(fminf_(t_.x, t2_.x), fminf_(t_.y, t2_.y), fminf_(t_.z, t2_.z));
-        }
-#endif
         PT_STAMP(3);
         return t_;
     };
@@ -422,7 +403,7 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
         occ[0] += 64; occ[1] += __builtin_popcountll(__ballot((ps.flags & kInPath) != 0 || (samplesLeft > 0 && !stopStarting)));
 #endif
         const uint32_t flagsIn = ps.flags;
-        if (DEFER) apply_pending<NOLEAF, ARMS && kArmNorm>(ps, thr, acc);
+        if (DEFER) apply_pending<NOLEAF, ARMS>(ps, thr, acc);
         if constexpr (MOMENTS && DEFER) landed_by_apply(flagsIn);
         // ARMS: the bounce and camera_ray hand back an unnormalised direction, and ONE normalise serves both (they ran back to back
         // for disjoint sets of lanes). kDirRaw: this lane got a new ps.d in this step. A lane that got none keeps its old, normalised
@@ -436,10 +417,10 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
         PT_STAMP(2);                                   // slot 2: scheduling check + bounce logic (shading, NEE shadow ray)
         while (!(ps.flags & kInPath) && samplesLeft > 0 && !stopStarting) {
             samplesLeft--;
-            path_begin<COUNT, ARMS && kArmNorm>(P.cam, ps, ms, PT_PX, PT_PY, c);
+            path_begin<COUNT, ARMS>(P.cam, ps, ms, PT_PX, PT_PY, c);
             if (path_exhausted<INTEG>(ps, P.maxDepth)) { path_finish(ps, acc, DEFER); if constexpr (MOMENTS) landed_by_finish(); }
         }
-        if constexpr (ARMS && kArmNorm) { if (ps.flags & kDirRaw) ps.d = normalize(ps.d); }
+        if constexpr (ARMS) { if (ps.flags & kDirRaw) ps.d = normalize(ps.d); }
         const bool hasExt = (ps.flags & kInPath) != 0;
         const bool hasShadow = DEFER && (ps.flags & kShadowPending) != 0;
         PT_STAMP(0);
@@ -449,16 +430,9 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
         if (__ballot(hasExt || hasShadow) == 0ull) break;
         if constexpr (DEFER && FLAT) {
             trace_pair_flat<STACKN, ARMS>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves);
-#ifdef PT_DIAG_DOUBLE_PAIR          // cost measurement only: the pair pass run twice, same result
-            { Hit h2; V3 thr2; trace_pair_flat<STACKN, ARMS>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr2, h2, c, P.cacheNodes, P.leaves, P.nLeaves);
-              if (hasExt && h2.tri == h.tri) h.t = fminf_(h.t, h2.t); thr.x = fminf_(thr.x, thr2.x); }
-#endif
         }
         else if constexpr (FLAT) {
             trace_closest_flat<STACKN, FLATW>(S, SC, hasExt, ps.o, ps.d, 999999.0f, st, h, c, P.cacheNodes, P.leaves, P.nLeaves);
-#ifdef PT_DIAG_DOUBLE_CLOSEST       // cost measurement only: the closest-hit traversal run twice, same result
-            { Hit h2; trace_closest_flat<STACKN, FLATW>(S, SC, hasExt, ps.o, ps.d, 999999.0f, st, h2, c, P.cacheNodes); if (hasExt && h2.tri == h.tri) h.t = fminf_(h.t, h2.t); }
-#endif
         }
         else if (hasExt) trace_closest<COUNT, STACKN, ONCHIP, CULL>(S, SC, ps.o, ps.d, 999999.0f, st, h, c, Keep{P.nodeKeep, P.triKeep});
         PT_STAMP(1);
@@ -536,16 +510,13 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
 // one copy of the scene per workgroup), hence the launch bound of 1024 for ONCHIP kernels; 4 waves per SIMD either way.
 template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, bool LEAN = false>
 __global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
-#if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))     // cap VGPRs so that PT_MIN_WAVES waves fit per SIMD
-#endif
 megakernel(KParams P) { megakernel_body<INTEG, COUNT, DEFER, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, LEAN>(P); }
 // Each wrapper is followed by what the host needs to know about it (pt_params.h: MkFacts; the tables' rows take it from here): the STACKN
 // it hands the body, whether that body has medium stacks (megakernel_body: kMedBytes, none with SIMPLE), whether it stages the bounce's
 // records (ATTRLDS: the ONCHIP kernels), and its launch bounds and register cap.
-constexpr int kMkMinWaves = PT_MIN_WAVES > 0 ? PT_MIN_WAVES : 4;
 template <int INTEG, bool COUNT, bool DEFER, bool ONCHIP, bool REFILL, bool FLAT, bool SIMPLE, int FLATW, bool LEAN>
-constexpr MkFacts megakernel_facts = {kStackLds, !SIMPLE, ONCHIP, 0, kMkMinWaves};
+constexpr MkFacts megakernel_facts = {kStackLds, !SIMPLE, ONCHIP, 0, PT_MIN_WAVES};
 
 template <int INTEG, bool COUNT, bool CULL, bool REFILL, bool SIMPLE = false, bool LEAN = false>
 __global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))
@@ -559,12 +530,10 @@ constexpr MkFacts megakernel_hbm_facts = {kStackLdsHbmGen, !SIMPLE, false, kWgWa
 constexpr int kStackFlat2 = kStackFlat2Rows;
 template <int INTEG, bool SIMPLE, bool LEAN = false>
 __global__ void __launch_bounds__(1024)
-#if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
-#endif
 megakernel_flat2(KParams P) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, LEAN>(P); }
 template <int INTEG, bool SIMPLE, bool LEAN>
-constexpr MkFacts megakernel_flat2_facts = {kStackFlat2, !SIMPLE, true, 0, kMkMinWaves};
+constexpr MkFacts megakernel_flat2_facts = {kStackFlat2, !SIMPLE, true, 0, PT_MIN_WAVES};
 
 // The SIMPLE production kernel for scenes in HBM: 8 waves per SIMD, 16-wave workgroups (pt_params.h).
 template <int INTEG>
@@ -579,21 +548,17 @@ constexpr MkFacts megakernel_hbm_simple_facts = {kStackLdsHbm, false, false, kWg
 // of their own, so that the kernels above keep their names, their parameter lists and their code.
 template <int INTEG, bool ONCHIP, bool REFILL = false, bool FLAT = false, bool SIMPLE = false, int FLATW = 1, bool LEAN = false>
 __global__ void __launch_bounds__(ONCHIP ? 1024 : 256)
-#if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
-#endif
 megakernel_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, false, ONCHIP, kStackLds, false, REFILL, FLAT, SIMPLE, FLATW, LEAN, true>(P, M); }
 template <int INTEG, bool ONCHIP, bool REFILL, bool FLAT, bool SIMPLE, int FLATW, bool LEAN>
-constexpr MkFacts megakernel_moments_facts = {kStackLds, !SIMPLE, ONCHIP, 0, kMkMinWaves};
+constexpr MkFacts megakernel_moments_facts = {kStackLds, !SIMPLE, ONCHIP, 0, PT_MIN_WAVES};
 
 template <int INTEG, bool SIMPLE, bool LEAN = false>
 __global__ void __launch_bounds__(1024)
-#if PT_MIN_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(PT_MIN_WAVES)))
-#endif
 megakernel_flat2_moments(KParams P, MomentsK M) { megakernel_body<INTEG, false, true, true, kStackFlat2, false, false, true, SIMPLE, 1, LEAN, true>(P, M); }
 template <int INTEG, bool SIMPLE, bool LEAN>
-constexpr MkFacts megakernel_flat2_moments_facts = {kStackFlat2, !SIMPLE, true, 0, kMkMinWaves};
+constexpr MkFacts megakernel_flat2_moments_facts = {kStackFlat2, !SIMPLE, true, 0, PT_MIN_WAVES};
 
 template <int INTEG, bool LEAN>        // the REFILL forms of megakernel_hbm: the generic bounce and its LEAN form
 __global__ void __launch_bounds__(64 * kWgWavesHbm) __attribute__((amdgpu_waves_per_eu(kWavesHbm)))

@@ -10,16 +10,17 @@ namespace pt {
 #define PT_STACK_LDS 16           // LDS traversal-stack entries per lane (256 B each per wave); deeper trees spill to global
 #endif
 #ifndef PT_MIN_WAVES
-#define PT_MIN_WAVES 4            // amdgpu_waves_per_eu for the megakernel: caps VGPRs at 128 (0 = unconstrained)
+#define PT_MIN_WAVES 4            // amdgpu_waves_per_eu for the megakernel: caps VGPRs at 128
 #endif
 #ifndef PT_CACHE_BYTES
 #define PT_CACHE_BYTES 12288      // LDS bytes per workgroup for the scene cache (top PNodes / all PTris)
 #endif
 constexpr int kStackLds = PT_STACK_LDS;
 #ifndef PT_WAVES_HBM
-#define PT_WAVES_HBM 6             // waves per SIMD of the instantiation for scenes that do not fit the LDS cache (0 = use the 4-wave kernel)
+#define PT_WAVES_HBM 6             // waves per SIMD of the instantiation for scenes that do not fit the LDS cache
 #endif
-constexpr int kWavesHbm = PT_WAVES_HBM > 0 ? PT_WAVES_HBM : 6;
+static_assert(PT_MIN_WAVES > 0 && PT_WAVES_HBM > 0, "both are waves per SIMD; the run-time option \"waves_hbm\" 0 selects the 4-wave kernel for scenes in HBM");
+constexpr int kWavesHbm = PT_WAVES_HBM;
 #ifndef PT_STACK_LDS_HBM
 #define PT_STACK_LDS_HBM 8
 #endif
@@ -48,7 +49,7 @@ constexpr int kAttrCacheBytes = PT_ATTR_CACHE_BYTES;
 #ifndef PT_WG_WAVES_HBM
 #define PT_WG_WAVES_HBM 12
 #endif
-constexpr int kWgWavesHbm = (PT_WAVES_HBM > 0 && (kWavesHbm * 4) % PT_WG_WAVES_HBM == 0 && PT_WG_WAVES_HBM <= 16) ? PT_WG_WAVES_HBM : 4;
+constexpr int kWgWavesHbm = ((kWavesHbm * 4) % PT_WG_WAVES_HBM == 0 && PT_WG_WAVES_HBM <= 16) ? PT_WG_WAVES_HBM : 4;
 constexpr int kCacheBytesHbm = kWgWavesHbm == 4 ? kCacheBytes
                                                 : ((160 * 1024) / ((kWavesHbm * 4) / kWgWavesHbm) - kWgWavesHbm * (kStackLdsHbmGen * 256 + kMediumMax * 64)) / 64 * 64;
 
@@ -155,7 +156,7 @@ struct WfParams {
     uint32_t* rng;       // [tile][6][64] as the megakernel
     float4* out;         // [tile][64] tile buffer
     int n, w, h, tileFirst, tileStride, tilesX;
-    int nodeKeep, triKeep;   // loop exits of the trace kernel (pt_trace.h: LoopExit), as KParams
+    int nodeKeep, triKeep;   // loop exits of the trace kernel (pt_trace.h: Keep), as KParams
 };
 size_t wf_state_bytes(int n);
 void wf_carve(WfParams& W, void* base);

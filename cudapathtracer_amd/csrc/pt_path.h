@@ -159,8 +159,8 @@ struct NeeRecord { V3 so, sd; float smaxt; V3 neeRaw, neeBeta; float neeW; };
 // — valid when no triangle is a MAT_LEAF: SIMPLE and LEAN scenes, and every scene the pair form of FLAT accepts.
 // LTRI (the pair pass, pt_trace.h: trace_pair_flat): `flags` also names the packed triangle of the sampled light (kLightTriMask, from
 // the kernel's argument lightTri8) — the one triangle the shadow ray need not be tested against. In a flag word, not a field: it costs no register.
-// ARMS (the pair kernels, pt_megakernel.h; the steps are pt_device.h: PT_LOGIC_ARMS): the same operations per lane, issued once
-// per wave where two exclusive arms each had their copy. With its step 8 the new direction comes back UNNORMALISED and kDirRaw
+// ARMS (the pair kernels, pt_megakernel.h; the steps are listed in pt_device.h): the same operations per lane, issued once
+// per wave where two exclusive arms each had their copy. The new direction comes back UNNORMALISED and kDirRaw
 // says that this bounce wrote one: the caller normalises it together with the directions regeneration produces.
 template <int INTEG, bool COUNT, bool DEFER, bool SIMPLE, bool LEAN, bool PRE, bool LTRI, bool ARMS, class MS, class ShadowFn>
 PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, V3& Li, V3& prevPoint, V3& woLocal,
@@ -193,7 +193,7 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
         return false;
     }
     // ---- Li_unidirectional, deviceCode.cu:332-537 ----
-    const Onb frame = onb_of<ARMS && kArmOnb>(hi.normal);       // toLocal / toWorld of this bounce all use the hit's normal
+    const Onb frame = onb_of<ARMS>(hi.normal);       // toLocal / toWorld of this bounce all use the hit's normal
     V3 wiLocal = to_local(d, frame);
     bool isSpecular = false, trueHit = true;
     if (!SIMPLE) {
@@ -238,7 +238,7 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
     bool done = false;
     if (trueHit) {
         float le2 = dot(hi.emission, hi.emission);
-        if constexpr (ARMS && kArmMis) {
+        if constexpr (ARMS) {
             // One light pdf and one MIS weight for the two arms below (`else`), which exclude each other per lane (le2 > kEps
             // against le2 < kEps) and both compute s2l, normalize(s2l), dist2, cosL and lightPdf of a light, then a weight
             // a * a / (b * b + a * a): (a, b) = (pdf, lightPdf) for a hit on an emitter, (lightPdf, pdfB) for the NEE sample. The
@@ -392,11 +392,11 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
         }
         beta = beta * ((f * __builtin_fabsf(woLocal.z)) / pdf);
         // SIMPLE: woLocal.z = sqrtf(1 - u1) with u1 <= 1 - kEps (cosine_sample_f clamps it), so 1 - u1 >= kEps > 0 and its correctly
-        // rounded root is positive — the `+` arm, always (the !SIMPLE guard above says the same). Taking it unconditionally (step 16
-        // of PT_LOGIC_ARMS) saves the exec split and measured 0.3 % slower, twice: off by default.
-        if ((ARMS && kArmDead && SIMPLE) || woLocal.z > 0.0f) o = hi.point + hi.normal * kEps;
+        // rounded root is positive — the `+` arm, always (the !SIMPLE guard above says the same). The select stays all the same: taking
+        // the arm unconditionally saves the exec split and measured 0.3 % slower, twice (profiles/r07_ab_logic_arms.log).
+        if (woLocal.z > 0.0f) o = hi.point + hi.normal * kEps;
         else o = hi.point - hi.normal * kEps;
-        if constexpr (ARMS && kArmNorm) { d = woWorld; flags |= kDirRaw; }
+        if constexpr (ARMS) { d = woWorld; flags |= kDirRaw; }
         else d = normalize(woWorld);
         prevPoint = hi.point;
     } else {
@@ -428,14 +428,7 @@ PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& 
     // (a fresh record, not a copy of the previous bounce's: whatever the last bounce recorded was consumed — the shadow ray
     // started, the term applied — before this bounce runs, so the old values are dead here and not live across the traversal)
     NeeRecord nr;
-#ifndef PT_NR_FRESH
-#define PT_NR_FRESH 1
-#endif
-#if PT_NR_FRESH
     nr.so = v3(0.0f); nr.sd = v3(0.0f); nr.smaxt = 0.0f; nr.neeRaw = v3(0.0f); nr.neeBeta = v3(0.0f); nr.neeW = 0.0f;
-#else
-    nr.so = ps.so; nr.sd = ps.sd; nr.smaxt = ps.smaxt; nr.neeRaw = ps.neeRaw; nr.neeBeta = ps.neeBeta; nr.neeW = ps.neeW;
-#endif
     bool done = bounce_core<INTEG, COUNT, DEFER, SIMPLE, LEAN, PRE, LTRI, ARMS>(S, rng, o, d, beta, Li, prevPoint, woLocal, pdf, etaI, etaT, depth, msTop, flags, nr,
                                                  ms, h, maxDepth, useMIS, shadow, c, lightTri8);
     ps.rng = rng;

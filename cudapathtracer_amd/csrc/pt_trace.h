@@ -85,7 +85,6 @@ struct Hit { float t, u, v; int32_t tri; int32_t material; };
 // reciprocal when all three components are in its proven range — one branch per ray — else the IEEE divisions (a
 // component of 0 gives the reference's +-inf, a denormal-range one its huge quotient).
 PT_DEV V3 inv3(V3 d) {
-#if PT_FAST_RCP
     const float lo = fminf_(fminf_(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
     const float hi = fmaxf_(fmaxf_(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
     if (lo >= 1e-12f && hi <= 1.0e30f) {                 // (NaN components fail the comparisons and take the IEEE path)
@@ -93,7 +92,6 @@ PT_DEV V3 inv3(V3 d) {
         return v3(__builtin_fmaf(rx, __builtin_fmaf(-d.x, rx, 1.0f), rx), __builtin_fmaf(ry, __builtin_fmaf(-d.y, ry, 1.0f), ry),
                   __builtin_fmaf(rz, __builtin_fmaf(-d.z, rz, 1.0f), rz));
     }
-#endif
     return v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
 }
 // The same with a wave-uniform range test, as rcp_exact has (pt_device.h), for the pair pass: every lane computes the fast form,
@@ -103,7 +101,6 @@ PT_DEV V3 inv3(V3 d) {
 // tie-break (nE > 0) by hasExt / hasShadow. The per-lane form above split exec for the zero direction of every lane whose bounce
 // recorded no shadow ray (pt_path.h: a fresh NeeRecord), in practically every pass.
 PT_DEV V3 inv3_uniform(V3 d, bool has) {
-#if PT_FAST_RCP
     const float lo = fminf_(fminf_(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
     const float hi = fmaxf_(fmaxf_(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
     const float rx = __builtin_amdgcn_rcpf(d.x), ry = __builtin_amdgcn_rcpf(d.y), rz = __builtin_amdgcn_rcpf(d.z);
@@ -114,9 +111,6 @@ PT_DEV V3 inv3_uniform(V3 d, bool has) {
         if (out) r = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     }
     return r;
-#else
-    return v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-#endif
 }
 
 // aabbIntersect (integratorUtilities.cuh:44-82) with a hoisted reciprocal direction.
@@ -192,28 +186,16 @@ PT_DEV bool moller_trumbore_sel(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& t, float
 
 // ONCHIP (template flag of the traversals): every PNode and PTri is in the LDS scene cache and the stack
 // fits its LDS part — Cornell-class scenes. The loops then carry no global-memory path and no branch for it.
-#ifndef PT_NODE_OVERLAP
-#define PT_NODE_OVERLAP 1
-#endif
-#ifndef PT_TRISEL_LEAN
-#define PT_TRISEL_LEAN 1
-#endif
-#ifndef PT_SPILL_UNIFORM
-#define PT_SPILL_UNIFORM 1
-#endif
-#ifndef PT_MT_SEL_RESUME
-#define PT_MT_SEL_RESUME 1
-#endif
 struct NodeData { f4v a, b, c, d; };
 template <bool ONCHIP = false>
 PT_DEV NodeData load_node(const DeviceScene& S, const SceneCache& C, int32_t i) {
     NodeData n;
-#if PT_NODE_OVERLAP
     if (!ONCHIP) {
         // Both halves of the wave in flight at once: the lanes whose node is beyond the LDS copy of the tree top issue their four
         // global loads, the others their four LDS reads INTO THE SAME REGISTERS, then one wait for both counters. Written by hand
         // because the compiler puts `s_waitcnt vmcnt(0)` between the two groups (it sees two writers of one register; the lanes
-        // are disjoint, the hardware has no such hazard), which adds the LDS round trip to every global one.
+        // are disjoint, the hardware has no such hazard), which adds the LDS round trip to every global one (+0.7 to +0.9 % on the
+        // scenes in HBM, profiles/r03_ab_scalar_lean.log).
         const uint32_t la = (uint32_t)(uintptr_t)C.nodes + (uint32_t)i * 64u;
         const f4v* gp = reinterpret_cast<const f4v*>(S.nodes + i);
         unsigned long long sv;
@@ -241,14 +223,8 @@ PT_DEV NodeData load_node(const DeviceScene& S, const SceneCache& C, int32_t i) 
             : "vcc", "memory");
         return n;
     }
-#endif
-    if (ONCHIP || i < C.nNodes) {
-        lds_cf4* p = C.nodes + i * 4;
-        n.a = p[0]; n.b = p[1]; n.c = p[2]; n.d = p[3];
-    } else {
-        const f4v* p = reinterpret_cast<const f4v*>(S.nodes + i);
-        n.a = p[0]; n.b = p[1]; n.c = p[2]; n.d = p[3];
-    }
+    lds_cf4* p = C.nodes + i * 4;                      // ONCHIP: every node is in LDS
+    n.a = p[0]; n.b = p[1]; n.c = p[2]; n.d = p[3];
     return n;
 }
 struct TriData { f4v a, b, e; };
@@ -296,24 +272,11 @@ PT_DEV LeafBox leaf_box(const PLeaf* __restrict__ leaves, int k) {
 // the longest leaf is done. Without culling a ray pierces many boxes between two leaves, the counts differ
 // widely between lanes, and on the 263 k-triangle scene a trip through the node loop carried 8.6 of 64 lanes
 // (tools/lane_util.py). So a wave leaves the node loop once no more than `active * node / 16` lanes are still
-// descending — the others go and test their leaves, the few keep `cur` and continue next time round — and,
-// where enabled, the triangle loop the same way (a lane resumes its leaf at `~ti`). Per ray nothing changes:
+// descending — the others go and test their leaves, the few keep `cur` and continue next time round — and
+// the triangle loop the same way (a lane resumes its leaf at `~ti`). Per ray nothing changes:
 // same nodes, same triangles, same order, same counters. +40 % on that scene, +22 % at 82 k triangles; a scene
 // in LDS (Cornell) has three node steps between leaves and only pays for the test, so ONCHIP kernels keep the
-// plain loops (PT_*_EXIT_ONCHIP for the A/B).
-#ifndef PT_NODE_EXIT_ONCHIP
-#define PT_NODE_EXIT_ONCHIP 0
-#endif
-#ifndef PT_TRI_EXIT_ONCHIP
-#define PT_TRI_EXIT_ONCHIP 0
-#endif
-#ifndef PT_TRI_EXIT_HBM
-#define PT_TRI_EXIT_HBM 1
-#endif
-template <bool ONCHIP> struct LoopExit {
-    static constexpr bool node = ONCHIP ? (PT_NODE_EXIT_ONCHIP != 0) : true;
-    static constexpr bool tri = ONCHIP ? (PT_TRI_EXIT_ONCHIP != 0) : (PT_TRI_EXIT_HBM != 0);
-};
+// plain loops: both exits are on exactly where !ONCHIP.
 struct Keep { int node, tri; };         // sixteenths of the lanes that entered the loop; 0 = stay until the last lane
 PT_DEV int lanes_here() { return __builtin_popcountll(__builtin_amdgcn_ballot_w64(true)); }
 
@@ -341,7 +304,6 @@ PT_DEV int32_t descend_node(const NodeData& n, int32_t cur, V3 o, V3 inv, Stack<
     bool hR = slab(n.b.z, n.b.w, n.c.x, n.c.y, n.c.z, n.c.w, o, inv, tR);
     if (CULL) { hL = hL && !(tL > cullT); hR = hR && !(tR > cullT); }
     int32_t left = f2i(n.d.x), right = f2i(n.d.y);
-#if PT_SPILL_UNIFORM
     if (!ONCHIP && !COUNT && !CULL && N == 16) {        // (kStackLds: the 4-wave kernels)
         // the stack's spill test once per wave and trip instead of inside push and pop (the 4-wave kernels' sixteen LDS entries are
         // rarely exceeded): no lane of the wave at the LDS part's edge -> the forms without a branch for the spill area
@@ -356,7 +318,6 @@ PT_DEV int32_t descend_node(const NodeData& n, int32_t cur, V3 o, V3 inv, Stack<
             return st.sp > 0 ? st.template pop<true>() : kRefNone;
         }
     }
-#endif
     if (hL && hR) {
         bool leftNear = tL < tR;
         st.template push<ONCHIP>(leftNear ? right : left);
@@ -402,10 +363,9 @@ PT_DEV void trace_closest_plain(const DeviceScene& S, const SceneCache& C, V3 o,
     if (COUNT) { if (hit.tri >= 0) c.hits++; }
 }
 
-// ... and with the loop exits of LoopExit (same visits, same order, same counters).
+// ... and with the loop exits (the !ONCHIP kernels; same visits, same order, same counters).
 template <bool COUNT, int N, bool ONCHIP, bool CULL>
 PT_DEV void trace_closest_exits(const DeviceScene& S, const SceneCache& C, V3 o, V3 d, float max_t, Stack<N>& st, Hit& hit, Ctr& c, Keep k) {
-    typedef LoopExit<ONCHIP> X;
     V3 inv = inv3(d);
     float min_t = 3.402823466e+38f;
     hit.tri = -1;
@@ -413,19 +373,17 @@ PT_DEV void trace_closest_exits(const DeviceScene& S, const SceneCache& C, V3 o,
     int32_t cur = S.rootRef;
     if (COUNT) c.raysClosest++;
     while (true) {
-        int keepN = 0;
-        if (X::node) keepN = (lanes_here() * k.node) >> 4;
+        const int keepN = (lanes_here() * k.node) >> 4;
         while (cur >= 0) {
             PT_UTIL_STEP(c, 0);
             cur = descend<COUNT, N, ONCHIP, CULL>(S, C, cur, o, inv, st, c, min_t);
-            if (X::node && lanes_here() <= keepN) break;
+            if (lanes_here() <= keepN) break;
         }
         if (cur == kRefNone) break;
-        if (X::node && cur >= 0) continue;
+        if (cur >= 0) continue;
         int32_t ti = ~cur;
         uint32_t idx;
-        int keepT = 0;
-        if (X::tri) keepT = (lanes_here() * k.tri) >> 4;
+        const int keepT = (lanes_here() * k.tri) >> 4;
         bool more;
         do {
             TriData q = load_tri<ONCHIP>(S, C, ti);
@@ -442,9 +400,9 @@ PT_DEV void trace_closest_exits(const DeviceScene& S, const SceneCache& C, V3 o,
             }
             ti++;
             more = !(idx & 0x80000000u);
-            if (X::tri && more && lanes_here() <= keepT) break;
+            if (more && lanes_here() <= keepT) break;
         } while (more);
-        if (X::tri && more) { cur = ~ti; continue; }          // the rest of this leaf next time round
+        if (more) { cur = ~ti; continue; }          // the rest of this leaf next time round
         if (COUNT) c.pops++;
         cur = st.sp > 0 ? st.template pop<ONCHIP>() : kRefNone;
     }
@@ -455,7 +413,7 @@ template <bool COUNT, int N, bool ONCHIP = false, bool CULL = false>
 PT_DEV void trace_closest(const DeviceScene& S, const SceneCache& C, V3 o, V3 d, float max_t, Stack<N>& st, Hit& hit, Ctr& c, Keep k = Keep{0, 0}) {
     // (two bodies rather than one with dead branches: the plain loops of the LDS-resident kernels are instruction-bound
     // and the optimiser lays the merged form out differently, -2.7 % on Cornell)
-    if (LoopExit<ONCHIP>::node || LoopExit<ONCHIP>::tri) trace_closest_exits<COUNT, N, ONCHIP, CULL>(S, C, o, d, max_t, st, hit, c, k);
+    if (!ONCHIP) trace_closest_exits<COUNT, N, ONCHIP, CULL>(S, C, o, d, max_t, st, hit, c, k);
     else trace_closest_plain<COUNT, N, ONCHIP, CULL>(S, C, o, d, max_t, st, hit, c);
 }
 
@@ -509,29 +467,26 @@ PT_DEV V3 trace_shadow_plain(const DeviceScene& S, const SceneCache& C, V3 o, V3
     return thr;
 }
 
-// ... and with the loop exits of LoopExit.
+// ... and with the loop exits (the !ONCHIP kernels).
 template <bool COUNT, int N, bool ONCHIP, bool CULL, bool NOLEAF = false>
 PT_DEV V3 trace_shadow_exits(const DeviceScene& S, const SceneCache& C, V3 o, V3 d, float max_t, Stack<N>& st, Ctr& c, Keep k) {
-    typedef LoopExit<ONCHIP> X;
     V3 inv = inv3(d);
     V3 thr = v3(1.0f);
     st.sp = 0;
     int32_t cur = S.rootRef;
     if (COUNT) c.raysShadow++;
     while (true) {
-        int keepN = 0;
-        if (X::node) keepN = (lanes_here() * k.node) >> 4;
+        const int keepN = (lanes_here() * k.node) >> 4;
         while (cur >= 0) {
             PT_UTIL_STEP(c, 4);
             cur = descend<COUNT, N, ONCHIP, CULL>(S, C, cur, o, inv, st, c, max_t);
-            if (X::node && lanes_here() <= keepN) break;
+            if (lanes_here() <= keepN) break;
         }
         if (cur == kRefNone) break;
-        if (X::node && cur >= 0) continue;
+        if (cur >= 0) continue;
         int32_t ti = ~cur;
         uint32_t idx;
-        int keepT = 0;
-        if (X::tri) keepT = (lanes_here() * k.tri) >> 4;
+        const int keepT = (lanes_here() * k.tri) >> 4;
         bool more;
         do {
             TriData q = load_tri<ONCHIP>(S, C, ti);
@@ -556,9 +511,9 @@ PT_DEV V3 trace_shadow_exits(const DeviceScene& S, const SceneCache& C, V3 o, V3
             }
             ti++;
             more = !(idx & 0x80000000u);
-            if (X::tri && more && lanes_here() <= keepT) break;
+            if (more && lanes_here() <= keepT) break;
         } while (more);
-        if (X::tri && more) { cur = ~ti; continue; }
+        if (more) { cur = ~ti; continue; }
         if (COUNT) c.pops++;
         cur = st.sp > 0 ? st.template pop<ONCHIP>() : kRefNone;
     }
@@ -567,7 +522,7 @@ PT_DEV V3 trace_shadow_exits(const DeviceScene& S, const SceneCache& C, V3 o, V3
 
 template <bool COUNT, int N, bool ONCHIP = false, bool CULL = false, bool NOLEAF = false>
 PT_DEV V3 trace_shadow(const DeviceScene& S, const SceneCache& C, V3 o, V3 d, float max_t, Stack<N>& st, Ctr& c, Keep k = Keep{0, 0}) {
-    if (LoopExit<ONCHIP>::node || LoopExit<ONCHIP>::tri) return trace_shadow_exits<COUNT, N, ONCHIP, CULL, NOLEAF>(S, C, o, d, max_t, st, c, k);
+    if (!ONCHIP) return trace_shadow_exits<COUNT, N, ONCHIP, CULL, NOLEAF>(S, C, o, d, max_t, st, c, k);
     return trace_shadow_plain<COUNT, N, ONCHIP, CULL, NOLEAF>(S, C, o, d, max_t, st, c);
 }
 
@@ -808,17 +763,14 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 //   ds_read_b128); the slots' bounds (128 words, f2u(max_t) - 1, see below); 128 u64 minima, one per slot: the extension
 //   ray's (t, first index) key, or the shadow ray's occlusion word; 64 u64 minima (t, last index) of the extension slots.
 //   The slots' exclusive prefixes (128 words) live where the 128 minima go until the owner search has read them.
-// A slot's minimum is a hit iff its high word is not ~0u (no hit has a NaN's bit pattern for t): with PT_PAIR_MIN_ALWAYS
-// every trip folds a key into both minima, a miss as (~0u, index) — min with it keeps a hit and leaves a miss a miss.
-// The pair kernels (ARMS; pt_device.h: PT_PAIR_CURSOR) keep no bounds in the scratch: a trip accepts every positive finite t, and
-// the ray's owner applies the bound to the minimum in stage 3 (BOUND, the proof stands at `put`). The two rows of the bounds hold
-// the second minimum of EVERY slot instead (ONEB), 1024 bytes behind its first — records 4096 B, 128 u64 first minima 1024 B
+// A slot's minimum is a hit iff its high word is not ~0u (no hit has a NaN's bit pattern for t). Only a trip that hits folds its key
+// into the minima: both ds_min_u64 on every trip, a miss as (~0u, index), measured 1.4 % slower (profiles/r05_ab_pair_slot_records.log).
+// The pair kernels (ARMS) keep no bounds in the scratch: a trip accepts every positive finite t, and
+// the ray's owner applies the bound to the minimum in stage 3 (the proof stands at `put`). The two rows of the bounds hold
+// the second minimum of EVERY slot instead, 1024 bytes behind its first — records 4096 B, 128 u64 first minima 1024 B
 // (an extension slot's (t, first index), a shadow slot's occlusion word), 128 u64 second minima 1024 B (an extension slot's
 // (t, last index), a shadow slot's dummy that nothing reads): 24 rows as before. A lane's cursor is then two registers, the
 // record's address and the first minimum's. The prefixes (at most 192 words) still live in the minima's 512.
-#ifndef PT_PAIR_MIN_ALWAYS
-#define PT_PAIR_MIN_ALWAYS 0
-#endif
 template <int N, bool ARMS = false>
 PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt, uint32_t ltri1,
                             bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
@@ -828,46 +780,25 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     lds_i32* Wd = st.lds - lane;
     // (the prefixes share the minima's words: every lane of the wave has finished the owner search before the minima are set —
     // 24 x 256 B per wave instead of 25, which is what lets a fifth 4-wave workgroup fit a CU's 160 KB next to its copy of the
-    // Cornell scene; ONEB spends the same 24 on records and 2 x 128 minima)
+    // Cornell scene; ARMS spends the same 24 on records and 2 x 128 minima)
     typedef __attribute__((address_space(3))) f4v lds_f4;
-    constexpr bool BOUND = ARMS && kPairBound, ONEB = ARMS && kPairOneB;
-    constexpr int kMax = 8 * 128, kKeyA = ONEB ? 8 * 128 : 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
-    static_assert(kKeyB + (ONEB ? 256 : 128) == 24 * 64 && (ONEB || kMax + 128 == kKeyA), "records, (bounds,) first minima, second minima: 24 rows of 64 words");
+    constexpr int kMax = 8 * 128, kKeyA = ARMS ? 8 * 128 : 9 * 128, kKeyB = kKeyA + 256, kPre = kKeyA;
+    static_assert(kKeyB + (ARMS ? 256 : 128) == 24 * 64 && (ARMS || kMax + 128 == kKeyA), "records, (bounds,) first minima, second minima: 24 rows of 64 words");
     lds_f4* Rec = (lds_f4*)Wd;                                    // slot v's record: Rec[2 v], Rec[2 v + 1] (the scene cache before the stacks is whole 16-byte records)
     V3 invE, invS;
-    if constexpr (ARMS && kArmInv3) { invE = inv3_uniform(ed, hasExt); invS = inv3_uniform(sd, hasShadow); }      // (see inv3_uniform: read only where the lane has the ray)
+    if constexpr (ARMS) { invE = inv3_uniform(ed, hasExt); invS = inv3_uniform(sd, hasShadow); }      // (see inv3_uniform: read only where the lane has the ray)
     else { invE = inv3(ed); invS = inv3(sd); }
     // 1. one lockstep node walk for both rays
     uint64_t tmE = 0ull, tmS = 0ull;
     if (S.rootRef < 0) { const uint64_t all = ~0ull >> (64 - S.nTris); tmE = hasExt ? all : 0ull; tmS = hasShadow ? all : 0ull; }
     else if (nLeaves > 0 && __builtin_amdgcn_ballot_w64((hasExt && !inv_is_regular(invE)) || (hasShadow && !inv_is_regular(invS))) == 0ull) {
-        if constexpr (ARMS && kPairAndOr) {
-            // (h & m) | acc per word with the mask word as the one scalar operand (v_and_or_b32): three instructions per test where
-            // the select takes four, its mask words moved to VGPRs first. h is made opaque, or the compiler folds the form back into
-            // the select; the opaque statement keeps its runtime unroll away too, so the two leaves of a trip are written out
-            auto leaf1 = [&](int k) {
-                const LeafBox L = leaf_box(leaves, k);
-                const bool eH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, eo, invE);
-                const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
-                const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;
-                uint32_t hE = eH ? ~0u : 0u, hS = sH ? ~0u : 0u;
-                asm("" : "+v"(hE)); asm("" : "+v"(hS));
-                const uint32_t mLo = (uint32_t)m, mHi = (uint32_t)(m >> 32);
-                tmE = (uint64_t)((hE & mLo) | (uint32_t)tmE) | ((uint64_t)((hE & mHi) | (uint32_t)(tmE >> 32)) << 32);
-                tmS = (uint64_t)((hS & mLo) | (uint32_t)tmS) | ((uint64_t)((hS & mHi) | (uint32_t)(tmS >> 32)) << 32);
-            };
-            int k = 0;
-            for (; k + 2 <= nLeaves; k += 2) { leaf1(k); leaf1(k + 1); }
-            if (k < nLeaves) leaf1(k);
-        } else {
-            _Pragma("unroll 2")
-            for (int k = 0; k < nLeaves; ++k) {                       // the leaves' own boxes, both rays (see inv_is_regular)
-                const LeafBox L = leaf_box(leaves, k);                // through the scalar cache: SGPR operands of the slab tests
-                const bool eH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, eo, invE);
-                const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
-                const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;      // s_bfm_b64 (a leaf of a tree with two or more leaves holds < 64 triangles)
-                tmE |= eH ? m : 0ull; tmS |= sH ? m : 0ull;
-            }
+        _Pragma("unroll 2")
+        for (int k = 0; k < nLeaves; ++k) {                       // the leaves' own boxes, both rays (see inv_is_regular)
+            const LeafBox L = leaf_box(leaves, k);                // through the scalar cache: SGPR operands of the slab tests
+            const bool eH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, eo, invE);
+            const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
+            const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;      // s_bfm_b64 (a leaf of a tree with two or more leaves holds < 64 triangles)
+            tmE |= eH ? m : 0ull; tmS |= sH ? m : 0ull;
         }
         tmE = hasExt ? tmE : 0ull; tmS = hasShadow ? tmS : 0ull;     // (once, not per leaf)
     } else {
@@ -926,7 +857,7 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     // T in [1, 0x7f800000] (positive, +inf included) orders like its value, so T - 1 < M - 1 <=> t < max_t. A shadow ray's
     // smaxt may be <= 0 or NaN, and then nothing passes `t > 0 && t < smaxt`: it is stored as the smallest positive float
     // (M - 1 = 0: nothing passes either).
-    // BOUND: the trips know no bound. A trip accepts iff f2u(t) - 1 < 0x7f7fffff — by the cases above, exactly the positive finite
+    // ARMS: the trips know no bound. A trip accepts iff f2u(t) - 1 < 0x7f7fffff — by the cases above, exactly the positive finite
     // t (T in [1, 0x7f7fffff]; +inf, T - 1 = 0x7f7fffff, is out, as it is under every bound: M - 1 <= 0x7f7fffff) — and stage 3
     // compares the minimum m of the accepted t with the ray's bound b, as floats, before anything else reads it. The accepted
     // set A contains every t the bounded rule accepts (0 < t < b implies positive and finite), and accepted bit patterns order
@@ -940,7 +871,7 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     auto put = [&](int v, V3 ro, V3 rd, float mt, uint64_t tm, int pre) {
         Rec[2 * v] = f4v{ro.x, ro.y, ro.z, rd.x};
         Rec[2 * v + 1] = f4v{rd.y, rd.z, __builtin_bit_cast(float, (uint32_t)tm), __builtin_bit_cast(float, (uint32_t)(tm >> 32))};
-        if constexpr (!BOUND) Wd[kMax + v] = (int32_t)(f2u(mt > 0.0f ? mt : 1.401298464e-45f) - 1u);
+        if constexpr (!ARMS) Wd[kMax + v] = (int32_t)(f2u(mt > 0.0f ? mt : 1.401298464e-45f) - 1u);
         Wd[kPre + v] = pre;
     };
     if (nE > 0) put(slotE, eo, ed, 999999.0f, tmE, preE);
@@ -959,13 +890,15 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     lds_u64* pA = kA;
     lds_u64* pB = kA;
     lds_u64* const kAE = kA + cntE;                                // the first shadow slot's minimum
-    auto fetch = [&]() {                                           // three LDS reads: the slot's record and its bound (BOUND: two, no bound)
+    auto fetch = [&]() {                                           // three LDS reads: the slot's record and its bound (ARMS: two, no bound)
         const f4v a = pR[0], b = pR[1];
         rem = (uint64_t)f2u(b.z) | ((uint64_t)f2u(b.w) << 32);
         ro = v3(a.x, a.y, a.z);
         rd = v3(a.w, b.x, b.y);
-        if constexpr (!BOUND) rmax1 = (uint32_t)*pM;
-        if constexpr (!ONEB) pB = pA < kAE ? pA + (kKeyB - kKeyA) / 2 : pA;      // a shadow ray's two minima both go to its occlusion word (ONEB: pA + 128, always)
+        if constexpr (!ARMS) {
+            rmax1 = (uint32_t)*pM;
+            pB = pA < kAE ? pA + (kKeyB - kKeyA) / 2 : pA;         // a shadow ray's two minima both go to its occlusion word (ARMS: pA + 128, always)
+        }
     };
     if (per > 0) {                                                // wave-uniform
         // Every lane runs exactly `per` tests, [p, p + per): the last lanes start early enough to stay inside [0, total) and repeat
@@ -980,26 +913,26 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
         rem &= ~((1ull << select64(rem, p - Wd[kPre + l])) - 1ull);
         // (the record's other half may still be in flight here, and the compiler then guards the trips' fetch into the same
         // registers with a wait of its own, once per trip: wait here, once per pass, for reads that have long returned)
-        if constexpr (BOUND) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+        if constexpr (ARMS) __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     }
-    // BOUND: a pass without tests (per == 0: no lane has a ray with a test) reads no minimum in stage 3, and the trips sit behind the same
+    // ARMS: a pass without tests (per == 0: no lane has a ray with a test) reads no minimum in stage 3, and the trips sit behind the same
     // wave-uniform test as their set-up — no second guard in front of the loop, and the code of stage 3 stays behind it
-    if (!BOUND || per > 0) {
+    if (!ARMS || per > 0) {
         wave_lds_sync();                                              // every lane has read its prefixes ...
-        if constexpr (ONEB) {                                          // ... the minima take their place: all 256, sixteen bytes a lane and write
+        if constexpr (ARMS) {                                          // ... the minima take their place: all 256, sixteen bytes a lane and write
             typedef uint32_t u4v __attribute__((ext_vector_type(4)));
             typedef __attribute__((address_space(3))) u4v lds_u4;
             ((lds_u4*)kA)[lane] = u4v{~0u, ~0u, ~0u, ~0u}; ((lds_u4*)kB)[lane] = u4v{~0u, ~0u, ~0u, ~0u};
         } else { kA[lane] = ~0ull; kA[64 + lane] = ~0ull; kB[lane] = ~0ull; }
         wave_lds_sync();
-        // BOUND: the one bound of all trips lives in a VGPR. As a known constant it is a literal, which the VOP3 compare that the
+        // ARMS: the one bound of all trips lives in a VGPR. As a known constant it is a literal, which the VOP3 compare that the
         // compiler first selects cannot hold: it comes back as an s_mov_b32 inside the loop, one SALU instruction per trip
         uint32_t rmaxAll = 0x7f7fffffu;
-        if constexpr (BOUND) asm("" : "+v"(rmaxAll));
+        if constexpr (ARMS) asm("" : "+v"(rmaxAll));
         for (int trip = 0; trip < per; ++trip) {                      // wave-uniform loop
             if (rem == 0ull) {                                        // the next slot has tests, and it exists: the lane's tests end below `total`
                 pR += 2;
-                if constexpr (!BOUND) pM++;
+                if constexpr (!ARMS) pM++;
                 pA++;
                 fetch();
             }
@@ -1008,30 +941,24 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
             const TriEdges q = load_tri_edges(C, ti);
             float t, u, v;
             const bool uvOk = moller_trumbore_sel_uv(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e2z), ro, rd, t, u, v);
-            const bool ok = uvOk & (f2u(t) - 1u < (BOUND ? rmaxAll : rmax1));     // t > 0 && t < max_t; BOUND: t positive and finite (see put)
-#if PT_PAIR_MIN_ALWAYS
-            const uint64_t tb = (uint64_t)(ok ? f2u(t) : ~0u) << 32;  // a miss: (~0u, index), which changes no minimum's hit state
-            __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_min(ONEB ? pA + (kKeyB - kKeyA) / 2 : pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
+            const bool ok = uvOk & (f2u(t) - 1u < (ARMS ? rmaxAll : rmax1));     // t > 0 && t < max_t; ARMS: t positive and finite (see put)
             if (ok) {                                                 // the same two minima for both kinds of ray: no branch on the kind
                 const uint64_t tb = (uint64_t)f2u(t) << 32;
                 __hip_atomic_fetch_min(pA, (unsigned long long)(tb | (uint64_t)(uint32_t)ti), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_min(ONEB ? pA + (kKeyB - kKeyA) / 2 : pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-#endif                                                            // (NOLEAF: any hit below max_t ends the shadow ray, BVHShadowRay returns 0)
+                __hip_atomic_fetch_min(ARMS ? pA + (kKeyB - kKeyA) / 2 : pB, (unsigned long long)(tb | (uint64_t)(uint32_t)(63 - ti)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }                                                         // (NOLEAF: any hit below max_t ends the shadow ray, BVHShadowRay returns 0)
         }
     }
     wave_lds_sync();
-    // 3. results: the shadow ray's throughput, the extension ray's winner (ties as in trace_closest_flat). BOUND: the bound meets the
+    // 3. results: the shadow ray's throughput, the extension ray's winner (ties as in trace_closest_flat). ARMS: the bound meets the
     // minimum here, once, as a float compare that is false for "no hit" (~0u: a NaN) as well (see put)
     const uint64_t occ = kA[slotS];                               // (slotS < 128 and slotE < 64 are in range whether or not the entry has a slot)
-    if constexpr (BOUND) { const bool occluded = __builtin_bit_cast(float, (uint32_t)(occ >> 32)) < smaxt; thr = (nS > 0 && occluded) ? v3(0.0f) : v3(1.0f); }
+    if constexpr (ARMS) { const bool occluded = __builtin_bit_cast(float, (uint32_t)(occ >> 32)) < smaxt; thr = (nS > 0 && occluded) ? v3(0.0f) : v3(1.0f); }
     else thr = (nS > 0 && (uint32_t)(occ >> 32) != ~0u) ? v3(0.0f) : v3(1.0f);      // (nS > 0: hasShadow)
     hit.tri = -1; hit.t = 0.0f; hit.u = 0.0f; hit.v = 0.0f; hit.material = 0;
     if (nE > 0) {                                                 // (hasExt; with no test the ray misses)
         const uint64_t a = kA[slotE], b = kB[slotE];
-        if (BOUND ? __builtin_bit_cast(float, (uint32_t)(a >> 32)) < 999999.0f : (uint32_t)(a >> 32) != ~0u) {
+        if (ARMS ? __builtin_bit_cast(float, (uint32_t)(a >> 32)) < 999999.0f : (uint32_t)(a >> 32) != ~0u) {
             int win = (int)(uint32_t)a;
             const int last = 63 - (int)(uint32_t)b;
             if (win != last) {
@@ -1106,19 +1033,16 @@ struct Trav {
     // Descend to the next leaf and test its triangles. Returns true when the ray is finished.
     template <bool COUNT>
     PT_DEV bool step(const DeviceScene& S, const SceneCache& C, Stack<N>& st, Ctr& c, Keep k = Keep{0, 0}) {
-        typedef LoopExit<false> X;
-        int keepN = 0;
-        if (X::node) keepN = (lanes_here() * k.node) >> 4;
+        const int keepN = (lanes_here() * k.node) >> 4;
         while (cur >= 0) {
             cur = descend<COUNT, N>(S, C, cur, o, inv, st, c);
-            if (X::node && lanes_here() <= keepN) break;
+            if (lanes_here() <= keepN) break;
         }
-        if (X::node && cur >= 0) return false;          // still descending: next call
+        if (cur >= 0) return false;          // still descending: next call
         if (cur == kRefNone) return true;
         int32_t ti = ~cur;
         uint32_t idx;
-        int keepT = 0;
-        if (X::tri) keepT = (lanes_here() * k.tri) >> 4;
+        const int keepT = (lanes_here() * k.tri) >> 4;
         bool more;
         do {
             TriData q = load_tri(S, C, ti);
@@ -1149,9 +1073,9 @@ struct Trav {
             }
             ti++;
             more = !(idx & 0x80000000u);
-            if (X::tri && more && lanes_here() <= keepT) break;
+            if (more && lanes_here() <= keepT) break;
         } while (more);
-        if (X::tri && more) { cur = ~ti; return false; }       // the rest of this leaf next call
+        if (more) { cur = ~ti; return false; }       // the rest of this leaf next call
         if (COUNT) c.pops++;
         cur = st.sp > 0 ? st.pop() : kRefNone;
         return cur == kRefNone;
@@ -1171,19 +1095,12 @@ struct Trav {
 // on entry (a dozen instructions per call against hundreds of node steps), the best t so far lives in the caller's Hit (h.t,
 // FLT_MAX until something is hit), and the shadow ray of a scene without MAT_LEAF triangles reports "occluded" in a flag bit
 // instead of a three-register throughput.
-#ifndef PT_RS_KEEP_INV
-#define PT_RS_KEEP_INV 0
-#endif
-#ifndef PT_OCCL_BOOL
-#define PT_OCCL_BOOL 0              // 1: "occluded" as a lane mask (an SGPR pair live through the traversal loops: the compiler then spills SGPRs INSIDE them, -3 % on scenes in HBM)
-#endif
+// That bit is a VGPR bit, not a bool: as a lane mask it is an SGPR pair live through the traversal loops, and the compiler then spills
+// SGPRs INSIDE them (measured -3 % on scenes in HBM).
 struct RayState {
     V3 o, d;
     float max_t;
     int32_t cur;
-#if PT_RS_KEEP_INV
-    V3 inv;
-#endif
     uint32_t flags;                    // kRayBusy | kRayShadow | kRayExtFollows | kRayOccluded
 };
 constexpr uint32_t kRayBusy = 1u, kRayShadow = 2u, kRayExtFollows = 4u, kRayOccluded = 64u;
@@ -1197,9 +1114,6 @@ PT_DEV void ray_start(const DeviceScene& S, Stack<N>& st, RayState& r, bool hasS
     r.o = hasShadow ? so : eo; r.d = hasShadow ? sd : ed;
     r.max_t = hasShadow ? smaxt : 999999.0f;
     r.cur = S.rootRef;
-#if PT_RS_KEEP_INV
-    r.inv = inv3(r.d);
-#endif
     r.flags = kRayBusy | (hasShadow ? kRayShadow : 0u) | ((hasShadow && hasExt) ? kRayExtFollows : 0u);
     st.sp = 0;
 }
@@ -1208,21 +1122,12 @@ PT_DEV void ray_start(const DeviceScene& S, Stack<N>& st, RayState& r, bool hasS
 template <bool COUNT, int N, bool ONCHIP, bool NOLEAF = false, bool TRISEL = false>
 PT_DEV void trace_resume(const DeviceScene& S, const SceneCache& C, Stack<N>& st, RayState& r, V3 eo, V3 ed, int minBusy,
                          V3& thr, Hit& h, Ctr& c, Keep k = Keep{0, 0}) {
-    typedef LoopExit<ONCHIP> X;
     if (!(r.flags & kRayBusy)) return;
-#if PT_RS_KEEP_INV
-    V3 o = r.o, d = r.d, inv = r.inv;
-#else
     V3 o = r.o, d = r.d, inv = inv3(r.d);
-#endif
     float max_t = r.max_t;
     int32_t cur = r.cur;
     bool isShadow = (r.flags & kRayShadow) != 0, extFollows = (r.flags & kRayExtFollows) != 0, busy = true;
-#if PT_OCCL_BOOL
-    bool occl = (r.flags & kRayOccluded) != 0;
-#else
     uint32_t occlBits = r.flags & kRayOccluded;                    // a VGPR bit, not a lane mask in an SGPR pair through the loops
-#endif
     while (true) {
         // wave-level early exit: the lanes still here keep their state for the next call
         const int active = lanes_here();
@@ -1234,9 +1139,9 @@ PT_DEV void trace_resume(const DeviceScene& S, const SceneCache& C, Stack<N>& st
             if (COUNT) { c.u[4] += cur < 192; c.u[5] += cur < 704; c.u[6] += cur < 1792; c.u[7] += cur < 8192; }
 #endif
             cur = descend<COUNT, N, ONCHIP>(S, C, cur, o, inv, st, c);
-            if (X::node && lanes_here() <= keepN) break;
+            if (!ONCHIP && lanes_here() <= keepN) break;
         }
-        if (X::node && cur >= 0) continue;
+        if (!ONCHIP && cur >= 0) continue;
         if (cur == kRefNone) {
             if (isShadow && extFollows) {               // shadow ray done: start this lane's extension ray
                 isShadow = false; extFollows = false;
@@ -1251,14 +1156,14 @@ PT_DEV void trace_resume(const DeviceScene& S, const SceneCache& C, Stack<N>& st
         uint32_t idx;
         bool occluded = false, more;
         int keepT = 0;
-        if (X::tri) keepT = (lanes_here() * k.tri) >> 4;
+        if (!ONCHIP) keepT = (lanes_here() * k.tri) >> 4;
         do {
             TriData q = load_tri<ONCHIP>(S, C, ti);
             idx = f2u(q.e.y);
             if (COUNT) c.tris++;
             PT_UTIL_STEP(c, 2);
             float t, u, v;
-            if constexpr (TRISEL && NOLEAF && !COUNT && !PT_OCCL_BOOL) {
+            if constexpr (TRISEL && NOLEAF && !COUNT) {
                 // select form: no divergent branch in the test or in what follows it (moller_trumbore_sel)
                 const bool hitOk = moller_trumbore_sel(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e.x), o, d, t, u, v) & (t < max_t);
                 const bool sh = isShadow & hitOk, upd = !isShadow & hitOk & (t < h.t);
@@ -1269,18 +1174,14 @@ PT_DEV void trace_resume(const DeviceScene& S, const SceneCache& C, Stack<N>& st
                 h.material = upd ? f2i(q.e.z) : h.material;
                 ti++;
                 more = !(idx & 0x80000000u) & !occluded;
-                if (X::tri && more && lanes_here() <= keepT) break;
+                if (!ONCHIP && more && lanes_here() <= keepT) break;
                 continue;
             }
-            bool ok = ((PT_MT_SEL_RESUME && !ONCHIP && !COUNT) ? moller_trumbore_sel : moller_trumbore)(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e.x), o, d, t, u, v);
+            bool ok = ((!ONCHIP && !COUNT) ? moller_trumbore_sel : moller_trumbore)(v3(q.a.x, q.a.y, q.a.z), v3(q.a.w, q.b.x, q.b.y), v3(q.b.z, q.b.w, q.e.x), o, d, t, u, v);
             if (isShadow) {
                 if (ok && (t < max_t)) {
                     uint32_t flags = f2u(q.e.w);
-#if PT_OCCL_BOOL
-                    if (NOLEAF) { occl = true; occluded = true; break; }             // the caller reads kRayOccluded; thr is not touched
-#else
-                    if (NOLEAF) { occlBits = kRayOccluded; occluded = true; break; }
-#endif
+                    if (NOLEAF) { occlBits = kRayOccluded; occluded = true; break; }     // the caller reads kRayOccluded; thr is not touched
                     if (!(flags & 1u)) { thr = v3(0.0f); occluded = true; break; }
                     // MAT_LEAF (integratorUtilities.cuh:218-239)
                     const PMat& m = S.mats[f2i(q.e.z)];
@@ -1300,21 +1201,14 @@ PT_DEV void trace_resume(const DeviceScene& S, const SceneCache& C, Stack<N>& st
             }
             ti++;
             more = !(idx & 0x80000000u);
-            if (X::tri && more && lanes_here() <= keepT) break;
+            if (!ONCHIP && more && lanes_here() <= keepT) break;
         } while (more);
-        if (X::tri && !occluded && more) { cur = ~ti; continue; }                 // the rest of this leaf next time round
+        if (!ONCHIP && !occluded && more) { cur = ~ti; continue; }                 // the rest of this leaf next time round
         if (COUNT) c.pops++;
         cur = (!occluded && st.sp > 0) ? st.template pop<ONCHIP>() : kRefNone;     // an occluded shadow ray ends here (BVHShadowRay returns)
     }
     r.o = o; r.d = d; r.max_t = max_t; r.cur = cur;
-#if PT_RS_KEEP_INV
-    r.inv = inv;
-#endif
-#if PT_OCCL_BOOL
-    r.flags = (busy ? kRayBusy : 0u) | (isShadow ? kRayShadow : 0u) | (extFollows ? kRayExtFollows : 0u) | (occl ? kRayOccluded : 0u);
-#else
     r.flags = (busy ? kRayBusy : 0u) | (isShadow ? kRayShadow : 0u) | (extFollows ? kRayExtFollows : 0u) | occlBits;
-#endif
     if (COUNT) { if (!busy && !isShadow && h.tri >= 0) c.hits++; }
 }
 

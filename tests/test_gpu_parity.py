@@ -262,7 +262,7 @@ def test_queue_waiters_that_give_up_do_not_fail_a_complete_frame(api, gpu_ready)
                                    ("1", "4", "8", "8", "2", "0", "4"),       # resumable traversal, a quarter of the busy lanes kept
                                    ("1", "4", "0", "0", "2", "0", "16")])     # resumable traversal with the loop exits off
 def test_loop_exits_and_refill(api, gpu_ready, knobs):
-    """pt_trace.h LoopExit / trace_resume: when a wave leaves its node loop, its triangle loop or the traversal
+    """pt_trace.h Keep / trace_resume: when a wave leaves its node loop, its triangle loop or the traversal
     (lanes that are through go on, the others resume later) is scheduling, not arithmetic — golden colours AND the
     per-pixel work counters bit for bit at every threshold, on all kernels (timed and counting instantiations)."""
     opts = {k: int(v) for k, v in zip(("refill", "refill_keep", "node_keep", "tri_keep", "waves_hbm", "onchip", "slice_iters"), knobs)}

@@ -165,7 +165,7 @@ def test_traversal_loops_of_the_kernels_for_scenes_in_hbm_hold_no_spill_code(isa
 
 
 def test_node_fetch_keeps_lds_and_global_reads_in_flight_together(isa):
-    """pt_trace.h: load_node (PT_NODE_OVERLAP): the lanes whose node is in HBM issue their four global loads, the lanes whose node
+    """pt_trace.h: load_node: the lanes whose node is in HBM issue their four global loads, the lanes whose node
     is in the LDS copy of the tree top their four LDS reads into the SAME registers, and only then the wave waits — the compiler's own
     if/else puts `s_waitcnt vmcnt(0)` between the two groups. Checked on the code as built: no wait between the first global load
     and the last LDS read of a fetch, one wait for both counters after it."""

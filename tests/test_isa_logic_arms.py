@@ -1,5 +1,5 @@
 """Build-time pins on the logic step of the headline kernel (megakernel_flat2<0, true, false>) after its duplicate arms were merged
-(pt_device.h: PT_LOGIC_ARMS), read from the gfx950 assembly as tools/pair_census.py reads it, and the machine
+(pt_megakernel.h: the ARMS switch), read from the gfx950 assembly as tools/pair_census.py reads it, and the machine
 code of every kernel the change must not touch.
 
 The parent's headline kernel: 3879 static instructions, 11 v_sqrt_f32, 70 v_div_scale_f32. Steps 1 to 4 are kept. Step 5 (the dead

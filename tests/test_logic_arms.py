@@ -1,4 +1,4 @@
-"""The pair kernels' logic step with its duplicate arms merged (pt_device.h: PT_LOGIC_ARMS): the uniform inv3
+"""The pair kernels' logic step with its duplicate arms merged (pt_megakernel.h: the ARMS switch): the uniform inv3
 at the head of the pair pass, one basis normalise, one light pdf and MIS weight for the emitter and the NEE arm, one direction
 normalise for bounce and regeneration. No arithmetic changed, only how often a wave issues it:
 every frame here equals a live oracle render bit for bit (NaNs must coincide). Each case is the smallest frame in which some lanes of
