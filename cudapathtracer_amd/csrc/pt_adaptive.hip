@@ -4,12 +4,12 @@
 //   adaptive_error_kernel    H += S - M, the per-pixel error e, the tile's E_T (a 64-lane max), tile_spp, the stop decision;
 //   adaptive_compact_kernel  the live list without the stopped tiles, in the same (ascending) order, and its length;
 //   adaptive_queue_save_kernel, after each launch: the tile queue's first 8 words, which the next launch's queue init resets —
-//                            the host checks both launches of a round from one read-back (pt_api.hip: render_adaptive).
+//                            the host checks both launches of a round from one read-back (pt_render.hip: render_adaptive).
 // pt_render_adaptive_moments adds, after each of a round's two launches,
 //   adaptive_moments_kernel  d = S - P, Q = Q + d d per rgb channel, P = S on the live tiles: pt_moments.hip's pass on a list.
 // The renders are the ordinary megakernels, launched on the list through the tile queue (pt_kernels.hip: queue_init_list_kernel).
 // S, M and H are tile-major over the whole frame ([tile][64] float4, lane = ly*8+lx), so one wave per live tile reads 1 KB
-// coalesced per buffer. These kernels run once per round: correct and cheap, not clever. Host side: pt_api.hip.
+// coalesced per buffer. These kernels run once per round: correct and cheap, not clever. Host side: pt_render.hip.
 #include "pt_params.h"
 
 namespace pt {

@@ -1,4 +1,4 @@
-// pt_bvh_build.h — what pt_api.hip hands the device builder (pt_bvh_build.hip) when it builds AND packs a scene's tree
+// pt_bvh_build.h — what pt_scene.hip hands the device builder (pt_bvh_build.hip) when it builds AND packs a scene's tree
 // (pt_scene_create_from_mesh, pt_scene_update_*). Internal: not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -860,7 +860,7 @@ void carve(Carver& c, Arrays& A, int n, int nPos, int maxBins) {
 }
 
 // ---- re-layout on the device: the packed records the kernels traverse, straight from the
-// builder's arrays. Same contents as pt_api.hip's host re-pack; PNodes are numbered in the builder's
+// builder's arrays. Same contents as pt_scene.hip's host re-pack; PNodes are numbered in the builder's
 // breadth-first order (children of one level in allocation order, which is any valid breadth-first order).
 struct PackIn { const pt_float4* normals; int nNormals; const pt_float2* uvs; int nUvs; const int* matType; int nMats; int nLights; };
 // mode 0: F = record is an internal node of the breadth-first part; mode 1: F = internal nodes inside the record's subtree
@@ -949,7 +949,7 @@ __global__ void k_pack_attrs(Arrays A, PackIn in, pt::PAttr* attrs, int* flagsOu
     a.lightInd = (t.lightInd >= 0 && t.lightInd < in.nLights) ? t.lightInd : -51;
     attrs[i] = a;
 }
-// The light records (pt_api.hip's host re-pack, same operations in the same order): the light's triangle with the CURRENT positions,
+// The light records (pt_scene.hip's host re-pack, same operations in the same order): the light's triangle with the CURRENT positions,
 // its first normal, its emission and its area = 0.5f * length(cross3(b - a, c - a)) as the kernels used to evaluate it per NEE
 // sample: IEEE subtractions, cross = fma(p, q, -(r * s)), dot = fma(z, z', fma(y, y', x * x')), correctly rounded sqrt. `lights`
 // was zeroed (a scene without lights keeps one zero record).
@@ -1213,7 +1213,7 @@ extern "C" int pt_bvh_build_device(const pt_float4* positions, int n_positions, 
     return B.total;
 }
 
-// Build + re-layout without leaving the device (pt_scene_create_from_mesh and pt_scene_update_*, pt_api.hip): pt_bvh_build.h.
+// Build + re-layout without leaving the device (pt_scene_create_from_mesh and pt_scene_update_*, pt_scene.hip): pt_bvh_build.h.
 extern "C" int pt_bvh_build_pack_(const pt_build_src_* d, int max_leaf_size, void* d_nodes, void* d_tris, void* d_attrs, void* d_lights,
                                   int* out5, pt_bvh_build_stats* stats) {
     const auto wall0 = std::chrono::steady_clock::now();

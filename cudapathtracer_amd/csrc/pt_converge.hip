@@ -9,7 +9,7 @@
 //                            error and its live flag. No LDS, no atomics, no scratch.
 // The ascending list of the live tiles and its length come from adaptive_compact_kernel (pt_adaptive.hip) over an iota list
 // with the live flags as its keep flags. The other two stages of a converging frame live with what they extend: moments on a
-// list in pt_api.hip (render_moments), the accumulation with a tile map in pt_temporal.hip.
+// list in pt_render.hip (render_moments), the accumulation with a tile map in pt_temporal.hip.
 #include <cmath>
 #include <mutex>
 

@@ -1,5 +1,5 @@
 // pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip): the tiling and block
-// count every one of them is launched with, each kernel's waves per SIMD, and the launchers pt_api.hip calls. The kernels' shared pieces are in
+// count every one of them is launched with, each kernel's waves per SIMD, and the launchers pt_feature_api.hip calls. The kernels' shared pieces are in
 // pt_feature.h.
 #pragma once
 #include <algorithm>

@@ -173,7 +173,7 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     static_assert(!MOMENTS || !COUNT, "the fused moments render has no counting form");
     // NOLEAF: no triangle of the scene carries a MAT_LEAF material, so a shadow ray's throughput is exactly 0 or 1 — one flag bit
     // of the resumable traversal, and the DEFER record holds the finished NEE term (PRE). True for SIMPLE and LEAN scenes and
-    // for every scene the pair form of FLAT is launched on (pt_api.hip: noLeafTris).
+    // for every scene the pair form of FLAT is launched on (pt_scene.hip: noLeafTris).
     constexpr bool NOLEAF = SIMPLE || LEAN || (DEFER && FLAT);
     // LTRI: the bounce notes which triangle the sampled light is, and the pair pass skips the shadow ray's test against it (pt_trace.h:
     // trace_pair_flat). The SIMPLE pair kernel only — the headline: in the other two the note costs one more spilled register around
@@ -189,7 +189,7 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     constexpr bool TRISEL = ((LEAN && !SIMPLE) || (SIMPLE && STACKN == kStackLds)) && !ONCHIP && !COUNT;      // pt_trace.h: moller_trumbore_sel
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nW = blockDim.x >> 6;      // nW waves share this workgroup's scene cache
     DeviceScene S = P.S;
-    // ONCHIP kernels: the host guarantees that the bounce's records fit as well (pt_api.hip: `onchip`), so their address
+    // ONCHIP kernels: the host guarantees that the bounce's records fit as well (pt_render.hip: `onchip`), so their address
     // space is a compile-time fact and every access below is a ds_read.
     constexpr bool ATTRLDS = ONCHIP && kAttrCacheBytes > 0;
     constexpr int kMedBytes = SIMPLE ? 0 : kMediumMax * 64;                 // SIMPLE kernels have no medium stack (pt_path.h)
@@ -288,7 +288,7 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
     // VGPRs keep their budget. The stores are ahead of the hand-over's wait for this wave's stores like every other state word.
     // Two of the B boundaries cost no load. The first (k == c) starts from prev = Q = 0, which the lane knows: it only stores. The
     // last (k == spp) is not taken here at all: `acc` is then the frame's S, and the host runs the batch form's own bookkeeping pass
-    // once after the launch (pt_api.hip: render_moments). A load in the logic step is a round trip to the memory side that the wave
+    // once after the launch (pt_render.hip: render_moments). A load in the logic step is a round trip to the memory side that the wave
     // waits for, at four waves per SIMD in the VALU-bound kernels: measured, it is what a boundary costs. Two batches: none at all.
     auto moments_land = [&](int k) {
         if (k >= P.spp) return;
@@ -542,7 +542,7 @@ megakernel_hbm_simple(KParams P) { megakernel_body<INTEG, false, false, false, k
 template <int INTEG>
 constexpr MkFacts megakernel_hbm_simple_facts = {kStackLdsHbm, false, false, kWgWavesHbmSimple, kWavesHbmSimple};
 
-// ---- the fused moments twins (option "moments_fused", pt_api.hip: render_moments) ----
+// ---- the fused moments twins (option "moments_fused", pt_render.hip: render_moments) ----
 // One twin per timed kernel that the launcher picks under default options: the same body with MOMENTS, under the same launch
 // bounds and register cap, launched with the LDS size, workgroup shape and grid the host computes for its counterpart. Entry points
 // of their own, so that the kernels above keep their names, their parameter lists and their code.

@@ -6,7 +6,7 @@
 // so Q ends as the sum of the B squared batch sums. The renders are the ordinary launches of render_tiles (either variant): no
 // megakernel knows about this. S, P and Q are tile-major over the whole frame ([tile][64] float4, lane = ly*8+lx), so a wave
 // reads 1 KB coalesced per buffer; lanes outside the image carry zeros along. ~80 B per pixel and batch: cheap, not clever.
-// Host side: pt_api.hip.
+// Host side: pt_render.hip.
 #include "pt_params.h"
 
 namespace pt {

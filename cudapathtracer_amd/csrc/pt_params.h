@@ -1,5 +1,5 @@
 // pt_params.h — kernel parameter blocks and host-callable launchers shared by pt_kernels.hip
-// (definitions) and pt_api.hip (C ABI).
+// (definitions) and the units of the C ABI (pt_render.hip, pt_probe.hip).
 #pragma once
 #include "pt_device.h"
 
@@ -110,7 +110,7 @@ struct KParams {
     int* left;                     // [tile][64] samples left per pixel of a yielded tile
     int schedMask;                 // the wave looks at the queue / its priority every schedMask + 1 iterations (31)
     int lptPrio;                   // longest-remaining-first issue priority once no fresh tile is left
-    unsigned long long lightTri8;  // the SIMPLE pair kernel: a byte per light, for the first 8: 1 + the packed triangle the light is (same v0, e1, e2 bit for bit), 0 = none (pt_api.hip: light_triangles)
+    unsigned long long lightTri8;  // the SIMPLE pair kernel: a byte per light, for the first 8: 1 + the packed triangle the light is (same v0, e1, e2 bit for bit), 0 = none (pt_scene.hip: light_triangles)
 };
 static_assert(sizeof(KParams) == 416 && offsetof(KParams, gnodeFrom) == 240 && offsetof(KParams, rng) == 312 &&
               offsetof(KParams, lightTri8) == 408, "KParams: the layout every kernel's code was built against");

@@ -151,7 +151,7 @@ PT_DEV bool path_exhausted(PathState& ps, int maxDepth) {
 // offset, which keeps the whole struct in scratch memory.)
 struct NeeRecord { V3 so, sd; float smaxt; V3 neeRaw, neeBeta; float neeW; };
 
-// SIMPLE (chosen per scene by the host, pt_api.hip: scene_simple): every triangle's material is an untextured MAT_DIFFUSE
+// SIMPLE (chosen per scene by the host, pt_scene.hip: apply_material_class): every triangle's material is an untextured MAT_DIFFUSE
 // that is neither a boundary nor specular, and material 0 (the air every path starts in) does not absorb — the reference's
 // own Cornell configuration. Then the medium stack only ever holds air, every hit is a true hit, the three dispatchers
 // have one arm each, and all of that is known at compile time: same values, a third of the code.

@@ -243,7 +243,7 @@ PT_DEV void leaf_sample_f(Rng& rng, V3 wi, float ior, float currIOR, float rough
     pdf = leaf_pdf(ior, currIOR, roughness, transmission, wi, wo);
 }
 
-// LEAN (chosen per scene by the host, pt_api.hip): no triangle's material is a MAT_LEAF and none has a texture or a
+// LEAN (chosen per scene by the host, pt_scene.hip): no triangle's material is a MAT_LEAF and none has a texture or a
 // transmission map — Cornell boxes of glass, mirrors and metals, a glass blob. The leaf arms (the largest of the five) and the
 // bilinear texture fetch are then dead code, known at compile time: same values, a third less code and fewer live registers.
 template <bool LEAN = false>

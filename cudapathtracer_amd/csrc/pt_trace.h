@@ -607,7 +607,7 @@ PT_DEV bool inv_is_regular(V3 inv) {
 }
 
 // All 64 lanes call this together; `active` says who has a ray. PNode.pad0 / pad1 hold the number of triangles
-// below the left / right child (patched in by the host for scenes that qualify, pt_api.hip).
+// below the left / right child (patched in by the host for scenes that qualify, pt_scene.hip).
 template <int N, int W = 1>
 PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool active, V3 o, V3 d, float max_t, Stack<N>& st, Hit& hit, Ctr& c, int nInternal,
                                const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
@@ -822,7 +822,7 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     }
     // The shadow ray is not tested against the light triangle it was aimed at (ltri1: 1 + that triangle's packed index, 0 if the
     // light is no triangle of the scene; at most 63). Its bound is smaxt = t * (1 - kEps), where t is what the bounce's own test of (so, sd) against
-    // that triangle returned: the same operations on the same ray and the same v0, e1, e2 (pt_api.hip: light_triangles checks
+    // that triangle returned: the same operations on the same ray and the same v0, e1, e2 (pt_scene.hip: light_triangles checks
     // them bit for bit), so the trip below would compute the same t and reject it — t < t * (1 - kEps) is false for every
     // positive t (the product rounds to t or below), and a t <= 0 or NaN passes no test at all. Where the bounce's test failed
     // (uvOk false, or t <= 0), the trip's fails identically. One test less per shadow ray, and the result is the same. Once per

@@ -8,7 +8,7 @@ megakernel_has_moments_twin said. Here the driver is built, host code only and w
 launch_megakernel and the two tables, and compared input by input:
 
   * where the ladders launched kernel K with L bytes, the new code launches K with L bytes, or refuses — but only an input that breaks
-    an invariant of render_tiles (pt_api.hip), `invariants` below; what the ladders refused stays refused;
+    an invariant of render_tiles (pt_render.hip), `invariants` below; what the ladders refused stays refused;
   * the LDS attribute is raised exactly when L > 65536, for every row. The ladders raised it under that condition on the arms that
     had PT_LDS_OK and never on the 4-wave general kernel's; wherever they raised it, it is still raised;
   * L follows from the launched row's own stack entries, medium stacks and attribute cache, and the row's name is the kernel that
@@ -33,7 +33,7 @@ DRIVER = os.path.join(ROOT, "tests", "mk_choice_driver.hip")
 
 
 def invariants(i, parent_twin, experimental=False):
-    """What render_tiles guarantees about the selector fields of every launch it makes (read off pt_api.hip; pt_set_option
+    """What render_tiles guarantees about the selector fields of every launch it makes (read off pt_render.hip; pt_set_option
     refuses "refill" 2, "defer_shadow", "xcd_bands", "wide" and "compact": the record's inputs carry none of the last three)."""
     imp = lambda a, b: (not a) or b
     wide, compact, bands = i.get("wide", 0), i.get("compact", 0), i.get("xcdBands", 0)
