@@ -202,5 +202,13 @@ void oracle_bsdf_eval(void* h, int materialID, const float* wi3, const float* wo
     pdf_eval(s->sc, materialID, f4(wi3[0], wi3[1], wi3[2]), f4(wo3[0], wo3[1], wo3[2]), etaI, etaT, pdf, f2(0.0f, 0.0f));
     out4[0] = f.x; out4[1] = f.y; out4[2] = f.z; out4[3] = pdf;
 }
+// batched forms of the two probes above (one call per case set): per-case material, wi, [wo,] backface, subsequence
+void oracle_bsdf_sample_n(void* h, int n, const int* material, const float* wi3, const int* backface, float etaI, float etaT, unsigned long long seed,
+                          const unsigned int* subseq, float* out8) {
+    for (int i = 0; i < n; i++) oracle_bsdf_sample(h, material[i], wi3 + 3 * i, backface[i], etaI, etaT, seed, subseq[i], out8 + 8 * i);
+}
+void oracle_bsdf_eval_n(void* h, int n, const int* material, const float* wi3, const float* wo3, float etaI, float etaT, float* out4) {
+    for (int i = 0; i < n; i++) oracle_bsdf_eval(h, material[i], wi3 + 3 * i, wo3 + 3 * i, etaI, etaT, out4 + 4 * i);
+}
 
 }  // extern "C"

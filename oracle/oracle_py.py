@@ -67,6 +67,8 @@ def lib():
         L.oracle_camera_ray.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.c_int, C.c_void_p]
         L.oracle_bsdf_sample.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_ulonglong, C.c_uint, C.c_void_p]
         L.oracle_bsdf_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+        L.oracle_bsdf_sample_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]
+        L.oracle_bsdf_eval_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         _lib = L
     return _lib
 
@@ -180,6 +182,25 @@ class OracleScene:
         wi = np.ascontiguousarray(wi, np.float32); wo = np.ascontiguousarray(wo, np.float32)
         out = np.zeros(4, np.float32)
         lib().oracle_bsdf_eval(self.h, material, _p(wi), _p(wo), eta_i, eta_t, _p(out))
+        return out
+
+    def bsdf_sample_n(self, material, wi, backface, subseq, eta_i=1.0, eta_t=1.0, seed=103033):
+        """bsdf_sample for n cases in one call (the signature of api.Scene.bsdf_sample): out [n, 8]."""
+        material = np.ascontiguousarray(material, np.int32); wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        backface = np.ascontiguousarray(backface, np.int32); subseq = np.ascontiguousarray(subseq, np.uint32)
+        if material.size and not (0 <= material.min() and material.max() < self.info["n_mats"]):
+            raise ValueError("material index outside the table")
+        out = np.zeros((len(material), 8), np.float32)
+        lib().oracle_bsdf_sample_n(self.h, len(material), _p(material), _p(wi), _p(backface), eta_i, eta_t, seed, _p(subseq), _p(out))
+        return out
+
+    def bsdf_eval_n(self, material, wi, wo, eta_i=1.0, eta_t=1.0):
+        material = np.ascontiguousarray(material, np.int32)
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3); wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        if material.size and not (0 <= material.min() and material.max() < self.info["n_mats"]):
+            raise ValueError("material index outside the table")
+        out = np.zeros((len(material), 4), np.float32)
+        lib().oracle_bsdf_eval_n(self.h, len(material), _p(material), _p(wi), _p(wo), eta_i, eta_t, _p(out))
         return out
 
 
