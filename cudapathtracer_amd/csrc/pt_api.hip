@@ -196,10 +196,10 @@ int pt_get_option(pt_scene* s, const char* name, int* out) {
 
 int pt_scene_flags(pt_scene* s) {
     if (!s) return 0;
-    const bool onchip = scene_onchip(s);
+    const bool onchip = scene_onchip(s->facts, s->opt);
     const bool pers = s->opt.persistent != 0;
     // the kernel the last launch used; before any launch, the one a frame with tiles enough for any kernel would get
-    const bool hbm = s->last.hbm >= 0 ? s->last.hbm == 1 : hbm_kernel_pays(s, false, 1ll << 40);
+    const bool hbm = s->last.hbm >= 0 ? s->last.hbm == 1 : hbm_kernel_pays(s->facts, s->opt, s->dev.numCU, false, 1ll << 40);
     return (onchip ? 1 : 0) | (pers ? 2 : 0) | ((pers && s->opt.sliceIters > 0) ? 4 : 0) | (hbm ? 8 : 0) | ((s->opt.cull && hbm) ? 16 : 0) | (s->last.refill ? 32 : 0) | (s->last.flat ? 64 : 0) | (s->last.simple ? 128 : 0) | (s->last.flat2 ? 256 : 0) | (s->last.leafTable ? 512 : 0) | (s->last.lean ? 1024 : 0);
 }
 

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "../../include/pt_api.h"
-#include "pt_params.h"
+#include "pt_plan.h"
 
 namespace pt {
 
@@ -34,42 +34,8 @@ struct DevBuf {
 
 // ---- the groups of pt_scene ---------------------------------------------------------------------
 struct Device { int id = 0, numCU = 256; hipEvent_t ev0 = nullptr, ev1 = nullptr; };      // ev0 / ev1: around the last render launch
-// Set per scene through pt_set_option (names in quotes; kOptions stores into the int members by pointer-to-member, so an option's
-// switch is an int), pt_set_variant and pt_set_culling; the library reads no environment variable. No update resets any of them.
-struct Options {
-    int variant = 0;             // 0 megakernel, 1 wavefront (pt_set_variant)
-    int cull = 0;                // pt_set_culling / "culling": opt-in, not parity-exact by construction
-    int schedMask = 31;          // "sched_mask": scheduling checks every schedMask + 1 bounce iterations (tests use 3)
-    int sliceAlways = 1;         // "slice_always" 0: slices only once no fresh tile is left
-    int sliceIters = 512;        // "slice_iters": time slice of the tile queue (0 = off)
-    int lptPrio = 2;             // "lpt_prio": 0 no issue-priority steering, 1 once no fresh tile is left, 2 always (A/B)
-    int persistent = 1;          // "persistent" 0: one tile per wave, workgroups launched per 4 tiles (A/B)
-    int queueTimeoutMs = 30000;  // "queue_timeout_ms": how long a wait on the tile queue may see no progress (tests use 0-1 to exercise the give-up path)
-    int onchipOk = 1;            // "onchip" 0: never pick the LDS-only kernel instantiation (A/B)
-    bool wavesHbmOk = true;      // "waves_hbm" 0: scenes in HBM use the 4-waves-per-SIMD kernel too (A/B)
-    bool wavesHbmForce = false;  // "waves_hbm" 2: ... and the 6-wave kernel whatever the tile count (tests)
-    int nodeKeep = 10, triKeep = 8;       // "node_keep" / "tri_keep" (pt_trace.h: Keep)
-    int refill = 1, refillKeep = 6;       // "refill" / "refill_keep": REFILL instantiation of the kernel for scenes in HBM (pt_trace.h: trace_resume)
-    bool refillKeepSet = false;           // (unset: the 4-wave kernel of small shares uses kRefillKeepSmall — it is chain-bound and wants its lanes back sooner)
-    int flatWanted = 1, simpleWanted = 1, leanWanted = 1;      // "flat" / "simple" / "lean" 0 turns the FLAT kernels / the SIMPLE / the LEAN bounce off (A/B)
-    int leafBoxes = 1;           // "leaf_boxes" 0: the FLAT kernels walk the nodes in lockstep instead of testing the leaves' own boxes (A/B)
-    int flat2Wanted = 1;         // "flat2" 1 (default): SIMPLE FLAT scenes trace shadow + extension ray in one FLAT pass (DEFER logic step)
-    int wfWideWg = 1;            // wavefront trace kernel: 16-wave workgroups for scenes in HBM ("wf_wide_wg")
-    int momentsFused = 0;        // "moments_fused" 1: pt_render_moments* renders all its samples in one launch that keeps Q itself, where the kernel has a fused twin
-};
-// What repack / derive_layout / apply_material_class compute from the scene; an update adopts the staging scene's as a whole.
-struct Facts {
-    DeviceScene ds{};
-    int stackNeed = 0, nInternal = 0, cacheNodes = 0, cacheTris = 0, nTrisPacked = 0, nMats = 0, nLightsPacked = 0;
-    int nLeaves = 0;                      // FLAT scenes: the leaf table (pt_trace.h: visited(leaf) == slab(leaf's own box))
-    unsigned long long lightTri8 = 0ull;  // a byte per light, for the first 8: 1 + the packed triangle the light is, 0 = none (light_triangles); KParams::lightTri8
-    bool armless = false;        // a triangle uses a material type without a dispatch arm (pt_path.h): DEFER is not exact
-    bool noLeafTris = false;     // no triangle carries a MAT_LEAF material: a shadow ray is occluded by any hit (order-free)
-    bool simpleOk = false;       // scene qualifies for the SIMPLE bounce (diffuse-only, pt_path.h)
-    bool leanOk = false;         // ... for the LEAN generic bounce (no MAT_LEAF triangle, no texture / transmission map on any triangle's material)
-    bool flatOk = false;         // ... for the FLAT kernels: LDS-resident, at most 128 nodes / triangles (64- or 128-bit masks), checked in derive_layout
-};
-// ... and what it keeps of the description it was made from (only an update of the whole mesh replaces these). deviceLeaf: the device
+// Options (what pt_set_option stores) and Facts (what the scene knows about itself), the two groups the launch decision reads, are
+// in pt_plan.h. Kept: what a scene keeps of the description it was made from (only an update of the whole mesh replaces these). deviceLeaf: the device
 // builder's leaf size; -1: the tree was the caller's (pt_scene_create)
 struct Kept { int deviceLeaf = -1, nPositions = 0, nNormals = 0, nUvs = 0, nTexels = 0; };
 // The last render launch, for pt_scene_flags, the queue-word checks and the counters' entry points.
@@ -117,9 +83,6 @@ struct pt_scene {
 namespace pt {
 
 // ---- helpers that cross units: pt_render.hip ... ---------------------------------------------------
-int scene_onchip_wg(const pt_scene* s);
-bool scene_onchip(const pt_scene* s);
-bool hbm_kernel_pays(const pt_scene* s, bool simple, long long tiles);
 int resolve_tiles(int w, int h, const pt_tile_range* tiles, TileSpan& t);
 CamK cam_to_kernel(const pt_camera& c);
 int check_render_args(pt_scene* s, const pt_camera* cam, int spp, int integrator);

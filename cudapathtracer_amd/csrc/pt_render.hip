@@ -1,40 +1,11 @@
-// pt_render.hip — the launcher boundary (launch_unidirectional / launch_naive_unidirectional, deviceCode.cuh:8-12): the choice and
-// the launch of the render kernels, pt_render*, adaptive sampling and the moments renders. Host code only; the kernels live in
-// pt_kernels.hip.
+// pt_render.hip — the launcher boundary (launch_unidirectional / launch_naive_unidirectional, deviceCode.cuh:8-12): the launch of
+// the render kernels, pt_render*, adaptive sampling and the moments renders. Host code only; the kernels live in pt_kernels.hip,
+// the decision which of them a launch gets and how it is sized in pt_plan.hip.
 #include "pt_host.h"
 
 using namespace pt;
 
 namespace pt {
-
-// LDS-resident instantiation: every PNode and PTri in the scene cache, the tree no deeper than the LDS stack, and the
-// records the bounce reads (PAttr, PMat, PLight) within their own LDS budget.
-// Its workgroups hold ONE copy of the scene each, and a CU has 160 KB of LDS for its 16 waves: workgroups of 4, 8 or 16
-// waves get 1, 2 or 4 times the budgets kCacheBytes (PNodes + PTris) and kAttrCacheBytes. Returns the smallest workgroup
-// size (in waves) that holds the scene, 0 if none does.
-int scene_onchip_wg(const pt_scene* s) {
-    if (!s->opt.onchipOk || s->facts.nTrisPacked <= 0 || s->facts.ds.stackSpill != 0) return 0;
-    const size_t geom = (size_t)s->facts.nInternal * 64 + (size_t)s->facts.nTrisPacked * 48, rec = attr_cache_bytes(s->facts.nTrisPacked, s->facts.nMats, s->facts.nLightsPacked);
-    // ... and 16 / wg such workgroups must fit a CU's 160 KB with the largest per-wave area any LDS-resident kernel uses (the pair
-    // pass scratch, 24 x 256 B, plus the medium stack of the non-SIMPLE kernels): a Cornell box of glass, water and gold at four
-    // waves per workgroup was 1 KB over — three workgroups per CU instead of four, 19 % of the frame (round 3)
-    const size_t perWave = (size_t)kStackFlat2Rows * 256 + (s->facts.simpleOk && s->opt.simpleWanted ? 0 : (size_t)kMediumMax * 64);
-    for (int wg = 4; wg <= 16; wg *= 2)
-        if (geom <= (size_t)kCacheBytes * (wg / 4) && (kAttrCacheBytes == 0 || rec <= (size_t)kAttrCacheBytes * (wg / 4)) &&
-            geom + rec + (size_t)wg * perWave <= (size_t)160 * 1024 * wg / 16) return wg;
-    return 0;
-}
-bool scene_onchip(const pt_scene* s) { return scene_onchip_wg(s) > 0; }
-// Does a launch of `tiles` tiles get megakernel_hbm — six waves per SIMD, eight with the SIMPLE bounce — and not the general 4-wave
-// kernel? A scene in HBM does, with enough tiles to fill those waves: with fewer (a 1/8 shard of a 1080p frame is 4050 tiles for 6144
-// slots) the extra slots stay empty and the 4-wave kernel's faster waves win (measured: 1/8 shard 176 vs 185 ms, 1/4 shard equal, 1/2
-// shard 602 vs 518 ms on the 263 k-triangle scene). The SIMPLE kernel's eight waves pay from ~3/4 of its 8192 slots on — a 1/4 share of
-// a 1080p frame: 201 vs 269 ms — the generic kernel's six from 5/4 of its 6144 (profiles/r02_sched_shards.log).
-bool hbm_kernel_pays(const pt_scene* s, bool simple, long long tiles) {
-    if (scene_onchip(s) || !s->opt.wavesHbmOk) return false;
-    const long long slots = (long long)s->dev.numCU * 4 * (simple ? kWavesHbmSimple : kWavesHbm);
-    return s->opt.wavesHbmForce || tiles * 4 >= slots * (simple ? 3 : 5);
-}
 
 // ---- helpers ----------------------------------------------------------------------------------
 int resolve_tiles(int w, int h, const pt_tile_range* tiles, TileSpan& t) {
@@ -59,14 +30,23 @@ CamK cam_to_kernel(const pt_camera& c) {
     return k;
 }
 
-int check_render_args(pt_scene* s, const pt_camera* cam, int spp, int integrator) {
-    if (!s || !cam) return fail(-1, "null scene or camera");
-    if (spp < 0) return fail(-1, "negative sample count");
+// prefix: the entry point's name and ": ", or ""
+static int check_integrator(int integrator, const char* prefix) {
     if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
-        return fail(-3, "integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", integrator);
+        return fail(-3, "%sintegrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", prefix, integrator);
+    return 0;
+}
+static int check_device(const pt_scene* s) {
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != s->dev.id) return fail(-1, "scene lives on HIP device %d but the current device is %d", s->dev.id, dev);
     return 0;
+}
+
+int check_render_args(pt_scene* s, const pt_camera* cam, int spp, int integrator) {
+    if (!s || !cam) return fail(-1, "null scene or camera");
+    if (spp < 0) return fail(-1, "negative sample count");
+    if (int r = check_integrator(integrator, "")) return r;
+    return check_device(s);
 }
 }  // namespace pt
 
@@ -77,28 +57,29 @@ int check_render_args(pt_scene* s, const pt_camera* cam, int spp, int integrator
 // Fused (render_moments with "moments_fused"): the launch is to keep the squared batch sums itself, batches of c samples, in the
 // tile-major buffers P and Q. If the kernel this launch gets has no fused twin, or the scene renders with the wavefront variant,
 // nothing is rendered and `launched` stays false; `seeded` then says whether the streams have been seeded on `stream` already.
+// The constructor takes what every caller sets; a caller assigns its own extras (spp, stream, list, count, ...) after it.
 struct RenderRequest {
-    const pt_camera* cam; int w, h, spp, maxDepth, integrator, useMIS; uint64_t seed; TileSpan t; void* d_tiles;
-    uint32_t* d_pixcnt = nullptr; bool count = false; hipStream_t stream = nullptr;
+    const pt_camera* cam; int w, h, maxDepth, integrator, useMIS; uint64_t seed; TileSpan t; void* d_tiles;
+    int spp = 0; uint32_t* d_pixcnt = nullptr; bool count = false; hipStream_t stream = nullptr;
     bool continueStreams = false; const int* list = nullptr; int live = -1;
     bool fused = false; float4 *P = nullptr, *Q = nullptr; int c = 0; bool launched = false, seeded = false;
+    RenderRequest(const pt_camera* cam, int w, int h, int maxDepth, int integrator, int useMIS, uint64_t seed, const TileSpan& t, void* d_tiles)
+        : cam(cam), w(w), h(h), maxDepth(maxDepth), integrator(integrator), useMIS(useMIS), seed(seed), t(t), d_tiles(d_tiles) {}
 };
 
 // The wavefront variant of render_tiles: logic / trace kernel pairs until no path is alive.
 static int render_tiles_wavefront(pt_scene* s, const RenderRequest& rq) {
-    const pt_camera* cam = rq.cam; const TileSpan& t = rq.t; void* d_tiles = rq.d_tiles; uint32_t* d_pixcnt = rq.d_pixcnt; hipStream_t stream = rq.stream;
-    const int w = rq.w, h = rq.h, spp = rq.spp, maxDepth = rq.maxDepth, integrator = rq.integrator, useMIS = rq.useMIS; const bool count = rq.count;
     if (s->facts.armless) return fail(-3, "the wavefront variant needs every material to have a dispatch arm (pt_path.h); use the megakernel");
     WfParams W;
-    W.n = t.count * 64; W.w = w; W.h = h; W.tileFirst = t.first; W.tileStride = t.stride; W.tilesX = t.tilesX;
+    W.n = rq.t.count * 64; W.w = rq.w; W.h = rq.h; W.tileFirst = rq.t.first; W.tileStride = rq.t.stride; W.tilesX = rq.t.tilesX;
     W.nodeKeep = s->opt.nodeKeep; W.triKeep = s->opt.triKeep;
     if (int r = s->wf.state.ensure(wf_state_bytes(W.n))) return r;
     if (int r = s->wf.ctl.ensure(64)) return r;
     wf_carve(W, s->wf.state.p);
     W.qctl = (uint32_t*)s->wf.ctl.p;
-    W.rng = (uint32_t*)s->work.rng.p; W.out = (float4*)d_tiles;
+    W.rng = (uint32_t*)s->work.rng.p; W.out = (float4*)rq.d_tiles;
     W.pathCtr = nullptr;
-    if (count) {
+    if (rq.count) {
         if (int r = s->wf.ctr.ensure((size_t)W.n * 8 * sizeof(uint32_t))) return r;
         W.pathCtr = (uint32_t*)s->wf.ctr.p;
     }
@@ -115,136 +96,92 @@ static int render_tiles_wavefront(pt_scene* s, const RenderRequest& rq) {
         if (int r = s->wf.spill.ensure((size_t)blocks * wgWaves * spillPerLane * 64 * sizeof(int32_t))) return r;
         spill = (int32_t*)s->wf.spill.p;
     }
-    const CamK ck = cam_to_kernel(*cam);
-    const bool wfSimple = s->facts.simpleOk && s->opt.simpleWanted && !count;        // the SIMPLE bounce (pt_path.h) in the logic kernel: diffuse-only scenes, timed launches
+    const CamK ck = cam_to_kernel(*rq.cam);
+    const bool wfSimple = s->facts.simpleOk && s->opt.simpleWanted && !rq.count;        // the SIMPLE bounce (pt_path.h) in the logic kernel: diffuse-only scenes, timed launches
     s->last.simple = wfSimple ? 1 : 0;
-    HIP_OK(hipMemsetAsync(W.qctl, 0, 16, stream));
-    HIP_OK(hipEventRecord(s->dev.ev0, stream));
-    HIP_OK(launch_wf_init(W, spp, stream));
+    HIP_OK(hipMemsetAsync(W.qctl, 0, 16, rq.stream));
+    HIP_OK(hipEventRecord(s->dev.ev0, rq.stream));
+    HIP_OK(launch_wf_init(W, rq.spp, rq.stream));
     // Paths end at different iterations; the host polls the queue length every 16 iterations.
-    const long long cap = (long long)std::max(spp, 1) * 4200 + 64;
+    const long long cap = (long long)std::max(rq.spp, 1) * 4200 + 64;
     bool finished = false;
     for (long long it = 0; it < cap; it++) {
-        HIP_OK(launch_wf_logic(integrator, count, wfSimple, W, s->facts.ds, ck, maxDepth, useMIS, (int)(it & 1), stream));
+        HIP_OK(launch_wf_logic(rq.integrator, rq.count, wfSimple, W, s->facts.ds, ck, rq.maxDepth, rq.useMIS, (int)(it & 1), rq.stream));
         if ((it & 15) == 15) {
             uint32_t queued = 0;
-            HIP_OK(hipMemcpyAsync(&queued, W.qctl + (it & 1) * 2, 4, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
+            HIP_OK(hipMemcpyAsync(&queued, W.qctl + (it & 1) * 2, 4, hipMemcpyDeviceToHost, rq.stream));
+            HIP_OK(hipStreamSynchronize(rq.stream));
             if (queued == 0) { finished = true; break; }
         }
-        HIP_OK(launch_wf_trace(count, wgWaves, blocks, W, s->facts.ds, wfNodes, wfTris, spill, spillPerLane, (int)(it & 1), stream));
+        HIP_OK(launch_wf_trace(rq.count, wgWaves, blocks, W, s->facts.ds, wfNodes, wfTris, spill, spillPerLane, (int)(it & 1), rq.stream));
     }
     if (!finished) return fail(-4, "wavefront render did not terminate within %lld iterations", cap);
-    HIP_OK(launch_wf_finish(W, stream));
-    if (count) HIP_OK(launch_wf_counters(W, d_pixcnt, (unsigned long long*)s->data.totals.p, stream));
-    HIP_OK(hipEventRecord(s->dev.ev1, stream));
+    HIP_OK(launch_wf_finish(W, rq.stream));
+    if (rq.count) HIP_OK(launch_wf_counters(W, rq.d_pixcnt, (unsigned long long*)s->data.totals.p, rq.stream));
+    HIP_OK(hipEventRecord(s->dev.ev1, rq.stream));
     s->last.evPending = true;
     return 0;
 }
 
 static int render_tiles(pt_scene* s, RenderRequest& rq) {
-    const pt_camera* cam = rq.cam; const TileSpan& t = rq.t; void* d_tiles = rq.d_tiles; uint32_t* d_pixcnt = rq.d_pixcnt; hipStream_t stream = rq.stream;
-    const int w = rq.w, h = rq.h, spp = rq.spp, maxDepth = rq.maxDepth, integrator = rq.integrator, useMIS = rq.useMIS; const bool count = rq.count;
-    const uint64_t seed = rq.seed; const bool continueStreams = rq.continueStreams, fused = rq.fused; const int* list = rq.list; int live = rq.live;
+    const TileSpan& t = rq.t;
     if (t.count == 0) return 0;
-    if (fused && s->opt.variant == 1) return 0;
-    if (!list) live = t.count;
-    if (list && (count || s->opt.variant != 0 || t.first != 0 || t.stride != 1 || live < 0 || live > t.count)) return fail(-1, "render_tiles: bad tile list");
+    if (rq.fused && s->opt.variant == 1) return 0;
+    const int live = rq.list ? rq.live : t.count;
+    if (rq.list && (rq.count || s->opt.variant != 0 || t.first != 0 || t.stride != 1 || live < 0 || live > t.count)) return fail(-1, "render_tiles: bad tile list");
     // the reference keys the stream by the camera's image size (y*w+x with the launch's w, deviceCode.cu:59)
     if (int r = s->work.rng.ensure((size_t)t.count * 384 * sizeof(uint32_t))) return r;
     // continueStreams: a later chunk of a progressive render keeps the per-pixel XORWOW states the
     // previous chunk stored (the reference reloads / stores them around every sample, deviceCode.cu:294, 541)
-    if (!continueStreams) HIP_OK(launch_rng_init((const uint32_t*)s->data.jump.p, seed, w, h, t, (uint32_t*)s->work.rng.p, stream));
-    if (fused) rq.seeded = !continueStreams;
+    if (!rq.continueStreams) HIP_OK(launch_rng_init((const uint32_t*)s->data.jump.p, rq.seed, rq.w, rq.h, t, (uint32_t*)s->work.rng.p, rq.stream));
+    if (rq.fused) rq.seeded = !rq.continueStreams;
     if (s->opt.variant == 1) return render_tiles_wavefront(s, rq);
-    // First the selector fields of the launch, then the kernel they choose (pt_kernels.hip: megakernel_choose), then everything that is
-    // sized for THAT kernel: its LDS stack length lays out the spill area, its launch bounds give the workgroup and the grid.
-    const bool onchip = scene_onchip(s);
-    // the SIMPLE bounce for a scene in HBM: diffuse-only scenes, timed launches with the resumable traversal
-    const bool simpleTimed = s->facts.simpleOk && s->opt.simpleWanted && s->opt.refill && !s->opt.cull && !s->facts.armless;
-    const bool simpleHbm = !onchip && s->opt.wavesHbmOk && simpleTimed && !count;
-    const bool hbm = hbm_kernel_pays(s, simpleHbm, live);
-    KParams P = {};                                         // (its padding too: pt_params.h)
-    P.onchip = onchip ? 1 : 0;
-    P.hbm = hbm ? 1 : 0;
-    P.cull = (s->opt.cull && hbm) ? 1 : 0;
-    P.refill = (s->opt.refill && !P.cull && !s->facts.armless && !onchip) ? 1 : 0;
-    P.flat = 0;                                             // 1: FLAT with 64-bit masks, 2: with 128-bit masks
-    if (onchip && s->facts.flatOk && s->opt.flatWanted) {
-        P.flat = (s->facts.nInternal <= 64 && s->facts.nTrisPacked <= 64) ? 1 : 2;     // 65..128: +17-20 % over the stack walk with the leaf-box form (profiles/r02_flat_crossover.jsonl)
-    }
-    // the instantiations that have the SIMPLE bounce: FLAT, the production kernel for scenes in HBM and its 4-wave form (small shares)
-    P.simple = ((P.flat && s->facts.simpleOk && s->opt.simpleWanted) || simpleHbm) ? 1 : 0;
-    if (P.flat == 1 && s->facts.noLeafTris && !s->facts.armless && s->opt.flat2Wanted && integrator == PT_UNIDIRECTIONAL && !count && useMIS) P.flat = 3;   // ... and the pair form of FLAT
-    // the LEAN generic bounce exists for the three timed kernels generic scenes run: the pair form of FLAT, the kernel for scenes in HBM
-    // and its 4-wave form (both REFILL)
-    P.lean = (s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !P.simple && !count && !P.cull && (P.flat == 3 || (!onchip && P.refill))) ? 1 : 0;
-    const MkRow* row = megakernel_choose(integrator, count, true, P, false);      // (syncShadow: outside the pair form of FLAT no kernel defers the shadow ray)
+
+    // The decision, the kernel it chooses, and everything that is sized for that kernel (pt_plan.hip)
+    const LaunchAsk ask = {rq.integrator, rq.count, rq.useMIS, live};
+    const LaunchPlan plan = plan_launch(s->facts, s->opt, s->dev.numCU, ask);
+    KParams P = plan_selectors(plan);
+    const MkRow* row = megakernel_choose(rq.integrator, rq.count, true, P, false);      // (syncShadow: outside the pair form of FLAT no kernel defers the shadow ray)
     if (!row) return fail(-1, "render_tiles: no megakernel is built for this launch");
-    const int spillEntries = hbm ? std::max(0, s->facts.stackNeed - row->f.stackEntries) : s->facts.ds.stackSpill;
-    const int wgWaves = row->f.wgWaves ? row->f.wgWaves : (onchip ? scene_onchip_wg(s) : 4);
-    int blocks = megakernel_blocks(t.count, wgWaves);
-    if (spillEntries > 0)
-        if (int r = s->work.spill.ensure((size_t)blocks * wgWaves * spillEntries * 64 * sizeof(int32_t))) return r;
-    P.S = s->facts.ds;
-    P.cam = cam_to_kernel(*cam);
-    P.w = w; P.h = h; P.spp = spp; P.maxDepth = maxDepth; P.useMIS = useMIS;
-    P.tileFirst = t.first; P.tileStride = t.stride; P.tileCount = t.count; P.tilesX = t.tilesX;
-    P.cacheNodes = s->facts.cacheNodes; P.cacheTris = s->facts.cacheTris;
-    if (onchip) { P.cacheNodes = s->facts.nInternal; P.cacheTris = s->facts.nTrisPacked; }      // the whole scene, in workgroups large enough to hold it
-    P.cacheAttrs = P.cacheMats = P.cacheLights = 0;
-    P.nLeaves = 0; P.leaves = nullptr;
-    P.lightTri8 = s->facts.lightTri8;
-    if (onchip && kAttrCacheBytes > 0) { P.cacheAttrs = s->facts.nTrisPacked; P.cacheMats = s->facts.nMats; P.cacheLights = s->facts.nLightsPacked; }   // the bounce's records in LDS as well
-    if (onchip && kAttrCacheBytes > 0 && s->facts.flatOk && s->opt.leafBoxes && s->facts.nLeaves > 0) { P.nLeaves = s->facts.nLeaves; P.leaves = (const PLeaf*)s->geo.leaves.p; }
-    P.wgWaves = wgWaves;
-    if (hbm && s->facts.cacheTris == 0) P.cacheNodes = std::min(s->facts.nInternal, (simpleHbm ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64);     // its workgroups share a larger copy of the top of the tree
-    P.gnodeFrom = P.cacheNodes;
-    if (count && !onchip && s->opt.wavesHbmOk && s->facts.cacheTris == 0) {
-        // a counting launch stands in for the timed launch of the same tiles (bench.py): count a node fetch as "global" against THAT
-        // instantiation's LDS copy of the tree top — the SIMPLE production kernel holds 768 nodes, this counting kernel 704 (or 192)
-        P.gnodeFrom = hbm_kernel_pays(s, simpleTimed, t.count) ? std::min(s->facts.nInternal, (simpleTimed ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64) : s->facts.cacheNodes;
-    }
-    P.S.stackSpill = spillEntries;
-    P.refillKeep = (hbm || s->opt.refillKeepSet) ? s->opt.refillKeep : kRefillKeepSmall;      // re-swept on the round's kernels: 6 for the 8-wave kernel, 10 for the 4-wave one (1/8 shares +5.5 % / +6 %, profiles/r03_shards_hbm_final.log)
-    P.nodeKeep = s->opt.nodeKeep; P.triKeep = s->opt.triKeep;
-    s->last.lean = P.lean;
-    s->last.refill = P.refill; s->last.flat = (P.flat && !count) ? 1 : 0;
-    s->last.simple = (P.simple && !count) ? 1 : 0;
-    s->last.flat2 = (P.flat == 3) ? 1 : 0;
-    s->last.leafTable = (P.flat && !count && P.nLeaves > 0) ? 1 : 0;
-    s->last.hbm = hbm ? 1 : 0;
-    P.wavesPerSimd = row->f.wavesPerSimd;
-    P.queue = nullptr; P.queueMask = 0; P.left = nullptr; P.gridBlocks = 0;
-    P.lptPrio = s->opt.lptPrio; P.sliceIters = s->opt.sliceIters; P.schedMask = s->opt.schedMask; P.sliceAlways = s->opt.sliceAlways ? 1 : 0;
-    P.queueTimeout = (unsigned long long)s->opt.queueTimeoutMs * 100000ull;        // ms -> ticks of the 100 MHz steady counter (hipDeviceAttributeWallClockRate)
-    if (s->opt.persistent || list) {
-        int cap = 256;
-        while (cap < t.count) cap <<= 1;
-        if (int r = s->work.queue.ensure((size_t)(kQueueHeader + 2 * cap) * sizeof(int))) return r;
+    const LaunchSizes z = size_launch(s->facts, s->opt, s->dev.numCU, ask, t, rq.list != nullptr, plan, *row, P);
+
+    // The buffers the sizes name, and the launch's pointers
+    if (z.spillEntries > 0)
+        if (int r = s->work.spill.ensure((size_t)z.blocks * P.wgWaves * z.spillEntries * 64 * sizeof(int32_t))) return r;
+    if (z.queueCap > 0) {
+        if (int r = s->work.queue.ensure((size_t)(kQueueHeader + 2 * z.queueCap) * sizeof(int))) return r;
         if (int r = s->work.left.ensure((size_t)t.count * 64 * sizeof(int))) return r;
-        P.queue = (int*)s->work.queue.p; P.queueMask = cap - 1; P.left = (int*)s->work.left.p;
-        P.gridBlocks = s->dev.numCU * P.wavesPerSimd * 4 / wgWaves;      // n waves per SIMD = 4n waves per CU, in workgroups of wgWaves
+        P.queue = (int*)s->work.queue.p; P.left = (int*)s->work.left.p;
     }
-    s->last.queued = P.queue != nullptr;
-    s->last.tiles = t.count;
-    s->last.pushed = live;
-    P.rng = (uint32_t*)s->work.rng.p; P.out = (float4*)d_tiles; P.pixCounters = d_pixcnt;
-    P.totals = count ? (unsigned long long*)s->data.totals.p : nullptr;
+    P.cam = cam_to_kernel(*rq.cam);
+    P.w = rq.w; P.h = rq.h; P.spp = rq.spp; P.maxDepth = rq.maxDepth;
+    if (P.nLeaves > 0) P.leaves = (const PLeaf*)s->geo.leaves.p;
+    P.rng = (uint32_t*)s->work.rng.p; P.out = (float4*)rq.d_tiles; P.pixCounters = rq.d_pixcnt;
+    P.totals = rq.count ? (unsigned long long*)s->data.totals.p : nullptr;
 #ifdef PT_STAMPS
     P.totals = (unsigned long long*)s->data.totals.p;           // the diagnostic build sums its stamps for timed launches too
 #endif
-    P.spill = spillEntries > 0 ? (int32_t*)s->work.spill.p : nullptr;
+    P.spill = z.spillEntries > 0 ? (int32_t*)s->work.spill.p : nullptr;
+
+    s->last.lean = P.lean; s->last.refill = P.refill; s->last.hbm = P.hbm;
+    s->last.flat = (P.flat && !rq.count) ? 1 : 0;
+    s->last.simple = (P.simple && !rq.count) ? 1 : 0;
+    s->last.flat2 = (P.flat == 3) ? 1 : 0;
+    s->last.leafTable = (P.flat && !rq.count && P.nLeaves > 0) ? 1 : 0;
+    s->last.queued = P.queue != nullptr;
+    s->last.tiles = t.count;
+    s->last.pushed = live;
+
     MomentsK M = {nullptr, nullptr, 0, 0.0f};
-    if (fused) {
-        row = megakernel_choose(integrator, count, true, P, true);     // the twin: its counterpart's facts, so everything sized above stands
+    if (rq.fused) {
+        row = megakernel_choose(rq.integrator, rq.count, true, P, true);     // the twin: its counterpart's facts, so everything sized above stands
         if (!row || (row->key & kMkBuiltOnly)) return 0;                    // the caller renders in batches
         M.P = rq.P; M.Q = rq.Q; M.c = rq.c; M.rc = 1.0f / (float)rq.c;
         rq.launched = true;
     }
-    HIP_OK(hipEventRecord(s->dev.ev0, stream));            // HIP events on the launch stream, around the megakernel only
-    HIP_OK(launch_megakernel(*row, P, live, list, stream, fused ? &M : nullptr));
-    HIP_OK(hipEventRecord(s->dev.ev1, stream));
+    HIP_OK(hipEventRecord(s->dev.ev0, rq.stream));            // HIP events on the launch stream, around the megakernel only
+    HIP_OK(launch_megakernel(*row, P, live, rq.list, rq.stream, rq.fused ? &M : nullptr));
+    HIP_OK(hipEventRecord(s->dev.ev1, rq.stream));
     s->last.evPending = true;
     return 0;
 }
@@ -255,8 +192,8 @@ int pt_render_tiles_device(pt_scene* s, const pt_camera* cam, int w, int h, int 
     if (!d_tile_rgba) return fail(-1, "null tile buffer");
     TileSpan t;
     if (int r = resolve_tiles(w, h, tiles, t)) return r;
-    RenderRequest rq; rq.cam = cam; rq.w = w; rq.h = h; rq.spp = spp; rq.maxDepth = maxDepth; rq.integrator = integrator; rq.useMIS = useMIS; rq.seed = seed;
-    rq.t = t; rq.d_tiles = d_tile_rgba; rq.count = count_work != 0; rq.stream = (hipStream_t)stream;
+    RenderRequest rq(cam, w, h, maxDepth, integrator, useMIS, seed, t, d_tile_rgba);
+    rq.spp = spp; rq.count = count_work != 0; rq.stream = (hipStream_t)stream;
     return render_tiles(s, rq);
 }
 
@@ -281,8 +218,8 @@ static int launch_on_colors(pt_scene* s, const pt_camera* cam, int w, int h, int
     if (int r = resolve_tiles(w, h, tiles, t)) return r;
     if (int r = s->work.tilebuf.ensure(std::max<size_t>((size_t)t.count * 64 * sizeof(float4), 16))) return r;
     HIP_OK(launch_tile(w, h, t, (const float4*)d_colors, (float4*)s->work.tilebuf.p, nullptr));
-    RenderRequest rq; rq.cam = cam; rq.w = w; rq.h = h; rq.spp = spp; rq.maxDepth = maxDepth; rq.integrator = integrator; rq.useMIS = useMIS; rq.seed = seed;
-    rq.t = t; rq.d_tiles = s->work.tilebuf.p; rq.d_pixcnt = d_pixcnt; rq.count = count;
+    RenderRequest rq(cam, w, h, maxDepth, integrator, useMIS, seed, t, s->work.tilebuf.p);
+    rq.spp = spp; rq.d_pixcnt = d_pixcnt; rq.count = count;
     if (int r = render_tiles(s, rq)) return r;
     HIP_OK(launch_untile(w, h, t, (const float4*)s->work.tilebuf.p, (float4*)d_colors, nullptr));
     HIP_OK(hipDeviceSynchronize());                 // cudaDeviceSynchronize, deviceCode.cu:608
@@ -303,8 +240,7 @@ int pt_launch_progressive(int integrator, int maxDepth, pt_camera camera, pt_sce
     if (int r = resolve_tiles(w, h, nullptr, t)) return r;
     if (int r = s->work.tilebuf.ensure(std::max<size_t>((size_t)t.count * 64 * sizeof(float4), 16))) return r;
     HIP_OK(launch_tile(w, h, t, (const float4*)d_colors, (float4*)s->work.tilebuf.p, nullptr));
-    RenderRequest rq; rq.cam = &camera; rq.w = w; rq.h = h; rq.maxDepth = maxDepth; rq.integrator = integrator; rq.useMIS = useMIS; rq.seed = 103033ull;
-    rq.t = t; rq.d_tiles = s->work.tilebuf.p;
+    RenderRequest rq(&camera, w, h, maxDepth, integrator, useMIS, 103033ull, t, s->work.tilebuf.p);
     for (int done = 0; done < numSample;) {
         const int n = std::min(chunk_spp, numSample - done);
         rq.spp = n; rq.continueStreams = done > 0;
@@ -385,15 +321,12 @@ static int check_adaptive_args(pt_scene* s, const pt_camera* cam, int w, int h, 
     if (moments && p->max_spp % (2 * p->chunk_spp) != 0)
         return fail(-1, "pt_render_adaptive_moments: max_spp %d must be a multiple of 2 * chunk_spp (%d), so that every batch has chunk_spp samples",
                     p->max_spp, 2 * p->chunk_spp);
-    if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
-        return fail(-3, "pt_render_adaptive: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", integrator);
+    if (int r = check_integrator(integrator, "pt_render_adaptive: ")) return r;
     if (!cam) return fail(-1, "pt_render_adaptive: null camera");
     if (!out || !tileSpp || (moments && !outSq)) return fail(-1, "pt_render_adaptive: null output buffer");
     if (!s) return fail(-1, "pt_render_adaptive: null scene");
     if (s->opt.variant != 0) return fail(-1, "pt_render_adaptive: the wavefront variant has no tile queue; select the megakernel (pt_set_variant 0)");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != s->dev.id) return fail(-1, "scene lives on HIP device %d but the current device is %d", s->dev.id, dev);
-    return 0;
+    return check_device(s);
 }
 
 // The schedule of include/pt_api.h. Every buffer is the scene's, sized for the whole frame (the tile number indexes it); dOut,
@@ -429,8 +362,8 @@ static int render_adaptive(pt_scene* s, const pt_camera* cam, int w, int h, int 
     HIP_OK(hipMemsetAsync(s->ad.H.p, 0, tileBytes, stream));
     HIP_OK(launch_adaptive_iota(T, lists[0], stream));               // round 0: every tile, in the order of a full frame
     int n = 0, live = T, cur = 0, rounds = 0;
-    RenderRequest rq; rq.cam = cam; rq.w = w; rq.h = h; rq.maxDepth = maxDepth; rq.integrator = integrator; rq.useMIS = useMIS; rq.seed = seed;
-    rq.t = t; rq.d_tiles = S; rq.stream = stream;
+    RenderRequest rq(cam, w, h, maxDepth, integrator, useMIS, seed, t, S);
+    rq.stream = stream;
     while (live > 0) {
         const int c = std::min(p.chunk_spp, (p.max_spp - n) / 2);
         if (c == 0) break;
@@ -526,15 +459,12 @@ static int check_moments_args(pt_scene* s, const pt_camera* cam, int w, int h, i
     if (batchSpp <= 0) return fail(-1, "pt_render_moments: batch_spp %d must be positive", batchSpp);
     if (spp % batchSpp != 0) return fail(-1, "pt_render_moments: spp %d must be a multiple of batch_spp %d", spp, batchSpp);
     if (spp / batchSpp < 2) return fail(-1, "pt_render_moments: spp %d / batch_spp %d must give at least 2 batches", spp, batchSpp);
-    if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
-        return fail(-3, "pt_render_moments: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", integrator);
+    if (int r = check_integrator(integrator, "pt_render_moments: ")) return r;
     if (!cam) return fail(-1, "pt_render_moments: null camera");
     if (cam->w != w || cam->h != h) return fail(-1, "pt_render_moments: the camera is %d x %d, the image %d x %d", cam->w, cam->h, w, h);
     if (!outS || !outQ) return fail(-1, "pt_render_moments: null output buffer");
     if (!s) return fail(-1, "pt_render_moments: null scene");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != s->dev.id) return fail(-1, "scene lives on HIP device %d but the current device is %d", s->dev.id, dev);
-    return 0;
+    return check_device(s);
 }
 
 // B = spp / c ordinary launches of c samples into the scene's own zeroed accumulator, the first seeding the streams as pt_render
@@ -560,8 +490,8 @@ static int render_moments(pt_scene* s, const pt_camera* cam, int w, int h, int s
     // (pt_megakernel.h: MOMENTS) except the last, from P = Q = 0; then the same check and wait as after a batch, and ONE bookkeeping
     // pass: the last batch's boundary (S is final then) and Q.w. Same bits as the loop below. Where the launch's kernel has no fused twin (render_tiles says so and renders nothing) the loop below runs instead.
     bool seeded = false, ranFused = false;
-    RenderRequest rq; rq.cam = cam; rq.w = w; rq.h = h; rq.maxDepth = maxDepth; rq.integrator = integrator; rq.useMIS = useMIS; rq.seed = seed;
-    rq.t = t; rq.d_tiles = S; rq.stream = stream; rq.list = listed ? list : nullptr; rq.live = live;
+    RenderRequest rq(cam, w, h, maxDepth, integrator, useMIS, seed, t, S);
+    rq.stream = stream; rq.list = listed ? list : nullptr; rq.live = live;
     if (s->opt.momentsFused && !(listed && live == 0) && spp < (1 << 22)) {        // (the kernel's boundary test is exact below 2^22 samples)
         HIP_OK(hipMemsetAsync(P, 0, tileBytes, stream));
         HIP_OK(hipMemsetAsync(Q, 0, tileBytes, stream));

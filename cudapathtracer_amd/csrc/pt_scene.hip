@@ -195,7 +195,7 @@ static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef,
     // each, every child numbered after its parent (the breadth-first numbering gives that; checked on the packed records)
     // and the triangle count of every leaf child, which goes into the spare words of its PNode.
     s->facts.flatOk = false;
-    if (nInternal <= 128 && nT >= 1 && nT <= 128 && scene_onchip_wg(s) > 0) {
+    if (nInternal <= 128 && nT >= 1 && nT <= 128 && scene_onchip_wg(s->facts, s->opt) > 0) {
         std::vector<PNode> pn((size_t)std::max(nInternal, 1));
         std::vector<PTri> pt((size_t)nT);
         if (nInternal > 0) HIP_OK(hipMemcpy(pn.data(), s->geo.nodes.p, (size_t)nInternal * sizeof(PNode), hipMemcpyDeviceToHost));

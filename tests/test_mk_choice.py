@@ -8,7 +8,7 @@ megakernel_has_moments_twin said. Here the driver is built, host code only and w
 launch_megakernel and the two tables, and compared input by input:
 
   * where the ladders launched kernel K with L bytes, the new code launches K with L bytes, or refuses — but only an input that breaks
-    an invariant of render_tiles (pt_render.hip), `invariants` below; what the ladders refused stays refused;
+    an invariant of render_tiles (pt_plan.hip: plan_launch), `invariants` below; what the ladders refused stays refused;
   * the LDS attribute is raised exactly when L > 65536, for every row. The ladders raised it under that condition on the arms that
     had PT_LDS_OK and never on the 4-wave general kernel's; wherever they raised it, it is still raised;
   * L follows from the launched row's own stack entries, medium stacks and attribute cache, and the row's name is the kernel that
@@ -19,21 +19,29 @@ launch_megakernel and the two tables, and compared input by input:
     arm did not read them, and sized the LDS of a 4-wave kernel for the pair form's 24 rows at flat == 3 without onchip: inputs
     render_tiles never produces. 136 of the 2048 selector combinations have a recorded twin that is now refused, none of them
     invariant-keeping.)
+
+One step earlier on the launch path, tests/launch_plan_driver.hip walks plan_launch and size_launch (pt_plan.hip) as render_tiles calls
+them, over scene shapes x fact flags x options x requests. tests/golden/launch_plan_parent.json records what the last commit with the
+decision inside render_tiles decided and sized for the same inputs; the plan, the chosen row, the sized fields and the dynamic LDS are
+compared input by input, and every plan is put to `invariants`.
 """
 import json
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
 
 CSRC = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "mk_choice_driver.hip")
+PLAN_DRIVER = os.path.join(ROOT, "tests", "launch_plan_driver.hip")
 
 
 def invariants(i, parent_twin, experimental=False):
-    """What render_tiles guarantees about the selector fields of every launch it makes (read off pt_render.hip; pt_set_option
+    """What render_tiles guarantees about the selector fields of every launch it makes: a restatement by hand of plan_launch
+    (pt_plan.hip), which test_the_invariants_hold_for_every_plan checks against every plan the second driver produces (pt_set_option
     refuses "refill" 2, "defer_shadow", "xcd_bands", "wide" and "compact": the record's inputs carry none of the last three)."""
     imp = lambda a, b: (not a) or b
     wide, compact, bands = i.get("wide", 0), i.get("compact", 0), i.get("xcdBands", 0)
@@ -79,21 +87,31 @@ def record():
 
 
 @pytest.fixture(scope="module")
-def head(tmp_path_factory):
-    """The driver's output against the tables and the choice as they are now: [(set 0, set 1, twin, row)] in input order."""
+def drivers(tmp_path_factory):
+    """The two host-only drivers, built against the tables, the choice and the plan as they are now: (directory, {source: executable})."""
     d = tmp_path_factory.mktemp("mk_choice")
     flags = ["--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "--cuda-host-only", "-I" + CSRC]
-    objs, procs = [], []
-    for src in (os.path.join(CSRC, "pt_kernels.hip"), os.path.join(CSRC, "pt_mk_lds.hip"), os.path.join(CSRC, "pt_mk_hbm.hip"), DRIVER):
-        obj = str(d / (os.path.basename(src) + ".o"))
-        objs.append(obj)
-        procs.append((src, subprocess.Popen(["hipcc"] + flags + ["-c", "-o", obj, src], stderr=subprocess.PIPE)))
+    units = [os.path.join(CSRC, n) for n in ("pt_kernels.hip", "pt_mk_lds.hip", "pt_mk_hbm.hip", "pt_plan.hip")]
+    objs, procs = {}, []
+    for src in units + [DRIVER, PLAN_DRIVER]:
+        objs[src] = str(d / (os.path.basename(src) + ".o"))
+        procs.append((src, subprocess.Popen(["hipcc"] + flags + ["-c", "-o", objs[src], src], stderr=subprocess.PIPE)))
     for src, pr in procs:
         err = pr.communicate()[1]
         assert pr.returncode == 0, (src, err.decode()[-2000:])
-    exe = str(d / "mk_choice_driver")
-    # (host-only objects name a device binary that is never built: the registration calls that would read it end in the driver's stubs)
-    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-rdynamic", "-Wl,--unresolved-symbols=ignore-all", "-o", exe] + objs + ["-ldl"])
+    exes = {}
+    for drv, n in ((DRIVER, 3), (PLAN_DRIVER, 4)):                      # (only the plan's driver links pt_plan.hip)
+        exes[drv] = str(d / os.path.basename(drv)[:-4])
+        # (host-only objects name a device binary that is never built: the registration calls that would read it end in the driver's stubs)
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-rdynamic", "-Wl,--unresolved-symbols=ignore-all", "-o", exes[drv]] +
+                              [objs[u] for u in units[:n]] + [objs[drv], "-ldl"])
+    return d, exes
+
+
+@pytest.fixture(scope="module")
+def head(drivers):
+    """The driver's output against the tables and the choice as they are now: [(set 0, set 1, twin, row)] in input order."""
+    exe = drivers[1][DRIVER]
     out = subprocess.check_output([exe]).decode().strip().split("\n")
     rows = []
     for ln in out:
@@ -178,3 +196,124 @@ def test_a_twin_exists_exactly_when_the_choice_with_moments_returns_a_dispatched
             assert head[k][3] is not None and head[k][3][1:] == head[k + 1][3][1:], (inputs[k], head[k][3], head[k + 1][3])
             twins += 1
     assert twins >= 27
+
+
+# ---- the plan and the sizes (pt_plan.hip) against what render_tiles decided before the decision moved there ----
+PARTS = ("plan", "row", "scene", "grid")
+
+
+def _fields(text):
+    w = text.split()
+    return {w[k]: int(w[k + 1]) for k in range(0, len(w), 2)}
+
+
+def _expand(levels, axes):
+    """A part's index (the record's index_format) as one array of text ids, an entry per input."""
+    cur = None
+    for (name, values), level in zip(reversed(axes), levels):
+        t = np.array(level, dtype=np.int64)
+        assert t.shape[1] == len(values), name
+        cur = t if cur is None else cur[t].reshape(len(t), -1)
+    assert len(cur) == 1
+    return cur[0]
+
+
+def _input(axes, k):
+    i = {}
+    for name, values in reversed(axes):
+        i[name] = values[k % len(values)]
+        k //= len(values)
+    return i
+
+
+@pytest.fixture(scope="module")
+def plan_record():
+    with open(os.path.join(GOLDEN, "launch_plan_parent.json")) as f:
+        fx = json.load(f)
+    return fx, {p: _expand(fx["index"][p], fx["axes"]) for p in PARTS}
+
+
+@pytest.fixture(scope="module")
+def plans(drivers):
+    """The second driver's output: per part its distinct texts and, per input, which of them."""
+    d, exes = drivers
+    ids = str(d / "launch_plan.idx")
+    out = subprocess.check_output([exes[PLAN_DRIVER], ids]).decode().strip().split("\n")
+    texts = {p: [] for p in PARTS}
+    axes = json.loads(out[0][2:])
+    for ln in out[1:]:
+        tag, k, text = ln.split(" ", 2)
+        part = {"P": "plan", "R": "row", "S": "scene", "G": "grid"}[tag]
+        assert int(k) == len(texts[part])
+        texts[part].append(text)
+    index = np.fromfile(ids, dtype=np.int32).reshape(-1, 4)
+    return texts, {p: index[:, k] for k, p in enumerate(PARTS)}, axes
+
+
+def test_the_plan_and_the_sizes_are_what_render_tiles_decided(plan_record, plans):
+    fx, parent = plan_record
+    texts, now, axes = plans
+    assert all(dict(fx["axes"])[a] == axes[a] for a in ("shape", "options", "live")), "the driver's inputs are not the record's"
+    n = len(parent["plan"])
+    assert n == 9 * 32 * 90 * 96 and all(len(now[p]) == n == len(parent[p]) for p in PARTS)
+    for p in PARTS:
+        was = {t: k for k, t in enumerate(fx["parts"][p])}                 # this run's text ids as the record's (-1: a text it has not)
+        differ = np.nonzero(np.array([was.get(t, -1) for t in texts[p]])[now[p]] != parent[p])[0]
+        if len(differ):
+            k = int(differ[0])
+            both = lambda t, idx: {q: t[q][int(idx[q][k])] for q in PARTS}
+            assert False, ("%d inputs differ in '%s'; the first:" % (len(differ), p), _input(fx["axes"], k), "parent", both(fx["parts"], parent),
+                           "now", both(texts, now))
+
+
+def test_the_record_has_every_case_it_is_to_have(plan_record):
+    fx, parent = plan_record
+    axes = dict(fx["axes"])
+    assert [name for name, values in fx["axes"]] == ["shape", "flags", "options", "live", "listed", "integrator", "count", "useMIS"]
+    shapes, sets = axes["shape"], axes["options"]
+    per_shape = len(parent["plan"]) // len(shapes)
+    plan = lambda shape, flags: _fields(fx["parts"]["plan"][parent["plan"][shape * per_shape + flags * (per_shape // 32)]])     # (defaults, first request)
+    # every return of scene_onchip_wg at the defaults, and the shape that the per-wave area of the medium stacks pushes to the next size
+    wg = [(plan(k, 0)["wg"], plan(k, 2)["wg"]) for k in range(len(shapes))]             # generic, SIMPLE (flags bit 1: simpleOk)
+    assert {w for pair in wg for w in pair} == {0, 4, 8, 16} and (8, 4) in wg, wg
+    assert any(sh[4] > 16 for sh in shapes) and any(sh[5] == 0 for sh in shapes) and any(sh[5] > 0 for sh in shapes)    # stackSpill != 0; nLeaves
+    assert {64, 65, 128, 129} <= {sh[0] for sh in shapes} and {64, 65, 128, 129} <= {sh[1] for sh in shapes}
+    # scenes in HBM whose triangles are not cached (the tree alone exceeds the 12 KB cache), below, between and above the two copies of
+    # the tree top that the kernels for scenes in HBM hold: 512 nodes, 768 with the SIMPLE bounce, as the record's sized launches say
+    hbm = [sh[0] for k, sh in enumerate(shapes) if wg[k] == (0, 0) and sh[0] * 64 > 12288]
+    assert any(n < 512 for n in hbm) and any(512 < n < 768 for n in hbm) and any(n > 768 for n in hbm), hbm
+    cached = {(_fields(fx["parts"]["plan"][int(p)])["simple"], _fields(fx["parts"]["scene"][int(s)])["cacheNodes"])
+              for p, s in zip(parent["plan"][-per_shape:], parent["scene"][-per_shape:]) if fx["parts"]["scene"][int(s)] != "-" and _fields(fx["parts"]["plan"][int(p)])["hbm"]}
+    assert cached == {(0, 512), (1, 768)}, cached
+    # the options: the defaults, each setting alone, each pair of settings of different options
+    single = [s[0] for s in sets if len(s) == 1]
+    assert sets[0] == [] and {tuple(s) for s in single} == {("onchip", 0), ("waves_hbm", 0), ("waves_hbm", 2), ("refill", 0), ("culling", 1), ("flat", 0),
+                                                               ("flat", 2), ("flat2", 0), ("simple", 0), ("lean", 0), ("leaf_boxes", 0), ("refill_keep", 3),
+                                                               ("persistent", 0)}
+    pairs = [s for s in sets if len(s) == 2]
+    assert len(sets) == 1 + len(single) + len(pairs) and sorted(map(json.dumps, pairs)) == sorted(
+        json.dumps([a, b]) for k, a in enumerate(single) for b in single[k + 1:] if a[0] != b[0])
+    assert axes["flags"] == list(range(32)) and axes["live"] == [1, 6143, 6144, 7679, 7680, 32400]
+    assert [axes[a] for a in ("listed", "integrator", "count", "useMIS")] == [[0, 1], [0, 2], [0, 1], [0, 1]]
+
+
+def test_the_invariants_hold_for_every_plan(plan_record, plans):
+    fx, parent = plan_record
+    texts, now, axes = plans
+    # integrator and count are the third- and second-innermost axes; a plan's text does not carry them
+    k = np.arange(len(now["plan"]))
+    planned = 0
+    for key in np.unique(now["plan"].astype(np.int64) * 4 + ((k >> 1) & 3)):
+        p, integ, count = int(key) >> 2, (int(key) >> 1) & 1, int(key) & 1
+        if texts["plan"][p] == "-":
+            continue                                                    # (a counting launch with a tile list: refused before it is planned)
+        f = _fields(texts["plan"][p])
+        i = dict(f, onchip=int(f["wg"] > 0), integrator=(0, 2)[integ], count=int(count), syncShadow=1)
+        assert invariants(i, False), i
+        planned += 1
+    assert planned > 100
+    # "render_tiles: no megakernel is built for this launch": no planned launch of the parent's lacked a row, and none does now
+    assert "none" not in fx["parts"]["row"] and "none" not in texts["row"]
+    # a workgroup may take all of its CU's LDS, and no more
+    lds = [_fields(t)["lds"] for t in texts["scene"] if t != "-"]
+    assert len(lds) > 100 and max(lds) <= 160 * 1024, max(lds)
