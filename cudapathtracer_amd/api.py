@@ -98,6 +98,30 @@ class SelectEntry(C.Structure):      # pt_select_entry
                 ("fill_alpha", C.c_int32)]
 
 
+class Ray(C.Structure):              # pt_ray
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("max_t", C.c_float), ("dx", C.c_float), ("dy", C.c_float),
+                ("dz", C.c_float), ("pad", C.c_uint32)]
+
+
+class RayHit(C.Structure):           # pt_ray_hit
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("tri", C.c_int32)]
+
+
+class RaySurface(C.Structure):       # pt_ray_surface
+    _fields_ = [("px", C.c_float), ("py", C.c_float), ("pz", C.c_float), ("uvx", C.c_float), ("nx", C.c_float), ("ny", C.c_float),
+                ("nz", C.c_float), ("uvy", C.c_float), ("material", C.c_int32), ("light", C.c_int32), ("backface", C.c_int32), ("pad", C.c_int32)]
+
+
+def _record_dtype(struct):
+    return np.dtype({"names": [f[0] for f in struct._fields_], "formats": [np.dtype(f[1]) for f in struct._fields_],
+                     "offsets": [getattr(struct, f[0]).offset for f in struct._fields_], "itemsize": C.sizeof(struct)})
+
+
+RAY_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE = _record_dtype(Ray), _record_dtype(RayHit), _record_dtype(RaySurface)
+QUERY_REORDER = 1                    # PT_QUERY_REORDER
+QUERY_MAX_T = 999999.0               # the max_t of the library's own closest-hit rays
+
+
 class PreviewParams(C.Structure):    # pt_preview_params
     _fields_ = [("spp", C.c_int32), ("batches", C.c_int32), ("max_depth", C.c_int32), ("integrator", C.c_int32), ("use_mis", C.c_int32),
                 ("aov_spp", C.c_int32), ("temporal", C.c_int32), ("filter", C.c_int32), ("temporal_params", TemporalParams),
@@ -193,6 +217,11 @@ def lib():
     L.pt_preview_read_ids.argtypes = [vp, vp]
     L.pt_preview_device_ids.restype = vp; L.pt_preview_device_ids.argtypes = [vp]
     L.pt_preview_id_passes.argtypes = [vp]
+    L.pt_query_closest.argtypes = [vp, i32, vp, vp, vp, C.c_uint32]
+    L.pt_query_closest_device.argtypes = [vp, i32, vp, vp, vp, C.c_uint32, vp]
+    L.pt_query_shadow.argtypes = [vp, i32, vp, vp, C.c_uint32]
+    L.pt_query_shadow_device.argtypes = [vp, i32, vp, vp, C.c_uint32, vp]
+    L.pt_query_camera_rays_device.argtypes = [C.POINTER(Camera), i32, i32, f32, vp, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
@@ -773,6 +802,68 @@ class Scene:
         ids, hit = np.zeros((len(q), 4), np.int32), np.zeros((len(q), 4), np.float32)
         _check(lib().pt_pick(self.h, C.byref(camera), w, h, len(q), _p(q), max_links, _p(ids), _p(hit)), "pt_pick")
         return ids, hit
+
+    # -- ray queries ----------------------------------------------------------------------------
+    @staticmethod
+    def _query_rays(what, rays):
+        """(is_torch, rays, n): an [n, 8] float32 numpy array (ox, oy, oz, max_t, dx, dy, dz, pad; a RAY_DTYPE array is viewed as one),
+        or a contiguous float32 torch tensor of that shape on the current HIP device, which is used where it lies."""
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):
+            a = np.asarray(rays)
+            if a.dtype == RAY_DTYPE:
+                a = np.ascontiguousarray(a).view(np.float32)
+            a = np.ascontiguousarray(a, np.float32).reshape(-1, 8)
+            return False, a, len(a)
+        import torch
+        if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise PtError("%s: a torch tensor of rays must be a contiguous [n, 8] float32 tensor on the scene's device" % what)
+        if rays.device.index != torch.cuda.current_device():
+            raise PtError("%s: the rays are on %s but the current device is %d" % (what, rays.device, torch.cuda.current_device()))
+        return True, rays, int(rays.shape[0])
+
+    def query_closest(self, rays, surfaces=False, reorder=False):
+        """pt_query_closest: the closest hit of each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d is not normalised).
+        numpy in: the host form, hits as a RAY_HIT_DTYPE array (t, u, v, tri; tri -1 for a miss) and, with surfaces, a
+        RAY_SURFACE_DTYPE array. A torch tensor on the scene's device in: pt_query_closest_device on torch's current stream, no host
+        copy, hits as an [n, 4] float32 tensor whose column 3 holds tri's bits (hits.view(torch.int32)[:, 3]) and surfaces as
+        [n, 12] float32 (words 8..10 material, light, backface as int32 bits). Returns hits, or (hits, surfaces)."""
+        is_torch, r, n = self._query_rays("query_closest", rays)
+        flags = QUERY_REORDER if reorder else 0
+        if is_torch:
+            import torch
+            hits = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            surf = torch.empty((n, 12), dtype=torch.float32, device=r.device) if surfaces else None
+            if n:        # (an empty tensor has no data pointer to hand over; the library launches nothing for n = 0 either)
+                _check(lib().pt_query_closest_device(self.h, n, r.data_ptr(), hits.data_ptr(), surf.data_ptr() if surfaces else None, flags,
+                                                     torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_closest_device")
+        else:
+            hits = np.zeros(n, RAY_HIT_DTYPE)
+            surf = np.zeros(n, RAY_SURFACE_DTYPE) if surfaces else None
+            if n:
+                _check(lib().pt_query_closest(self.h, n, _p(r), _p(hits), _p(surf), flags), "pt_query_closest")
+        return (hits, surf) if surfaces else hits
+
+    def query_shadow(self, rays, reorder=False):
+        """pt_query_shadow: the shadow ray's throughput along each ray below its max_t, [n, 4] float32 (rgb, 0): zeros when occluded.
+        numpy in, numpy out (host form); a torch tensor on the scene's device in, a torch tensor out, on torch's current stream."""
+        is_torch, r, n = self._query_rays("query_shadow", rays)
+        flags = QUERY_REORDER if reorder else 0
+        if is_torch:
+            import torch
+            thr = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            if n:
+                _check(lib().pt_query_shadow_device(self.h, n, r.data_ptr(), thr.data_ptr(), flags,
+                                                    torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_shadow_device")
+        else:
+            thr = np.zeros((n, 4), np.float32)
+            if n:
+                _check(lib().pt_query_shadow(self.h, n, _p(r), _p(thr), flags), "pt_query_shadow")
+        return thr
+
+    def query_camera_rays(self, camera, w, h, max_t=QUERY_MAX_T):
+        """pt_query_camera_rays_device: the centre rays of render_aovs_centre / render_ids as an [h*w, 8] float32 torch tensor on the
+        current device (ray y*w + x), made on torch's current stream."""
+        return query_camera_rays(camera, w, h, max_t)
 
     @property
     def has_motion(self):
@@ -1965,4 +2056,15 @@ def probe_centre_rays(camera, xy):
     xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
     out = np.zeros((len(xy), 6), np.float32)
     _check(lib().pt_probe_centre_rays(C.byref(camera), len(xy), _p(xy), _p(out)), "pt_probe_centre_rays")
+    return out
+
+
+def query_camera_rays(camera, w, h, max_t=QUERY_MAX_T, out=None):
+    """pt_query_camera_rays_device: ray y*w + x = the centre ray of pixel (x, y) (probe_centre_rays' o and d bit for bit) with the
+    given max_t, as an [h*w, 8] float32 torch tensor on the current device (or into `out`, such a tensor), on torch's current stream."""
+    import torch
+    if out is None:
+        out = torch.empty((max(w, 0) * max(h, 0), 8), dtype=torch.float32, device="cuda:%d" % torch.cuda.current_device())
+    _check(lib().pt_query_camera_rays_device(C.byref(camera), w, h, max_t, out.data_ptr() or None, torch.cuda.current_stream(out.device).cuda_stream or None),
+           "pt_query_camera_rays_device")
     return out

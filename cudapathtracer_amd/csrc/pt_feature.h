@@ -1,6 +1,6 @@
 // pt_feature.h — what the feature kernels are assembled from (pt_aov.hip: aov_kernel, aov_chain_kernel, aov_centre_kernel,
 // aov_centre_chain_kernel; pt_motion.hip: motion_kernel; pt_motion_chain.hip: motion_chain_kernel; pt_ids.hip: ids_kernel,
-// ids_chain_kernel). Every one of them is one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the
+// ids_chain_kernel; pt_query.hip's trace kernels use FeatureWave on 64 rays a tile). Every one of them is one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the
 // tiles, with the non-counting trace_closest (max_t 999999, as pt_probe_trace_closest) on an LDS stack that overflows into the
 // scene's spill area:
 //   FeatureWave, tile_pixel   the wave's traversal state and the pixel of a lane in a tile

@@ -1,5 +1,5 @@
-// pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick.
-// (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip; their launchers and block counts: pt_feature_host.h.)
+// pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
+// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip; their launchers and block counts: pt_feature_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -239,5 +239,115 @@ int pt_pick(pt_scene* s, const pt_camera* cam, int w, int h, int n, const int32_
     if (int r = render_ids(s, cam, w, h, max_links, (const int32_t*)d, n, d + xyBytes, d + xyBytes + recBytes, nullptr)) return r;
     HIP_OK(hipMemcpy(out_ids, d + xyBytes, recBytes, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out_hit, d + xyBytes + recBytes, recBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Ray queries (pt_query.hip: query_closest_kernel, query_shadow_kernel, query_camera_rays_kernel, query_keys_kernel). Every message
+// under the caller's name, all before any HIP call; n == 0 returns before the scene is looked at (the device check comes last).
+static int check_query_args(const char* fn, pt_scene* s, int n, const void* rays, const void* out, uint32_t flags) {
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!rays) return fail(-1, "%s: null rays", fn);
+    if (!out) return fail(-1, "%s: null output buffer", fn);
+    if (n < 0 || n > (1 << 28)) return fail(-1, "%s: n %d must be 0..%d", fn, n, 1 << 28);
+    if (flags & ~PT_QUERY_REORDER) return fail(-1, "%s: unknown flag bits 0x%x", fn, flags & ~PT_QUERY_REORDER);
+    return 0;
+}
+
+static int check_query_device(const char* fn, pt_scene* s) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->dev.id) return fail(-1, "%s: scene lives on HIP device %d but the current device is %d", fn, s->dev.id, dev);
+    return 0;
+}
+
+// PT_QUERY_REORDER: *perm = the rays' order by key (the sorted indices), or NULL where the call takes the unordered path: without
+// the flag, for at most one tile of rays, and for a scene whose root is a leaf (it has no record to read the bounds from).
+static int query_order(pt_scene* s, int n, const void* dRays, uint32_t flags, const uint32_t** perm, hipStream_t stream) {
+    *perm = nullptr;
+    if (!(flags & PT_QUERY_REORDER) || n <= 64 || s->facts.ds.rootRef < 0) return 0;
+    const size_t half = ((size_t)n * sizeof(uint32_t) + 255) & ~(size_t)255;
+    if (int r = s->feat.queryKeys.ensure(2 * half)) return r;
+    if (int r = s->feat.queryIdx.ensure(2 * half)) return r;
+    uint32_t* keys = (uint32_t*)s->feat.queryKeys.p;
+    uint32_t* idx = (uint32_t*)s->feat.queryIdx.p;
+    uint32_t* keysOut = (uint32_t*)((char*)keys + half);
+    uint32_t* idxOut = (uint32_t*)((char*)idx + half);
+    size_t tempBytes = 0;
+    HIP_OK(query_sort(nullptr, &tempBytes, keys, keysOut, idx, idxOut, n, stream));
+    if (int r = s->feat.querySort.ensure(std::max<size_t>(tempBytes, 256))) return r;
+    HIP_OK(launch_query_keys(s->facts.ds, n, dRays, keys, idx, stream));
+    HIP_OK(query_sort(s->feat.querySort.p, &tempBytes, keys, keysOut, idx, idxOut, n, stream));
+    *perm = idxOut;
+    return 0;
+}
+
+static int query_closest(pt_scene* s, int n, const void* dRays, void* dHits, void* dSurf, uint32_t flags, hipStream_t stream) {
+    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, dSurf ? kQuerySurfaceWavesPerSimd : kQueryClosestWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    const uint32_t* perm;
+    if (int r = query_order(s, n, dRays, flags, &perm, stream)) return r;
+    HIP_OK(launch_query_closest(s->facts.ds, n, dRays, perm, blocks, dHits, dSurf, spill, stream));
+    return 0;
+}
+
+static int query_shadow(pt_scene* s, int n, const void* dRays, void* dThr, uint32_t flags, hipStream_t stream) {
+    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, kQueryShadowWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    const uint32_t* perm;
+    if (int r = query_order(s, n, dRays, flags, &perm, stream)) return r;
+    HIP_OK(launch_query_shadow(s->facts.ds, n, dRays, perm, blocks, dThr, spill, stream));
+    return 0;
+}
+
+int pt_query_closest_device(pt_scene* s, int n, const void* d_rays, void* d_hits, void* d_surfaces, uint32_t flags, void* stream) {
+    if (int r = check_query_args("pt_query_closest", s, n, d_rays, d_hits, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_closest", s)) return r;
+    return query_closest(s, n, d_rays, d_hits, d_surfaces, flags, (hipStream_t)stream);
+}
+
+int pt_query_shadow_device(pt_scene* s, int n, const void* d_rays, void* d_throughput, uint32_t flags, void* stream) {
+    if (int r = check_query_args("pt_query_shadow", s, n, d_rays, d_throughput, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_shadow", s)) return r;
+    return query_shadow(s, n, d_rays, d_throughput, flags, (hipStream_t)stream);
+}
+
+// The host forms: the rays go up into the head of the staging buffer, the outputs come down from behind them.
+int pt_query_closest(pt_scene* s, int n, const pt_ray* rays, pt_ray_hit* hits, pt_ray_surface* surfaces, uint32_t flags) {
+    if (int r = check_query_args("pt_query_closest", s, n, rays, hits, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_closest", s)) return r;
+    const size_t rayBytes = (size_t)n * sizeof(pt_ray), hitBytes = (size_t)n * sizeof(pt_ray_hit), surfBytes = surfaces ? (size_t)n * sizeof(pt_ray_surface) : 0;
+    if (int r = s->feat.queryOut.ensure(rayBytes + hitBytes + surfBytes)) return r;
+    char* d = (char*)s->feat.queryOut.p;
+    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
+    if (int r = query_closest(s, n, d, d + rayBytes, surfaces ? d + rayBytes + hitBytes : nullptr, flags, nullptr)) return r;
+    HIP_OK(hipMemcpy(hits, d + rayBytes, hitBytes, hipMemcpyDeviceToHost));
+    if (surfaces) HIP_OK(hipMemcpy(surfaces, d + rayBytes + hitBytes, surfBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pt_query_shadow(pt_scene* s, int n, const pt_ray* rays, float* throughput4, uint32_t flags) {
+    if (int r = check_query_args("pt_query_shadow", s, n, rays, throughput4, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_shadow", s)) return r;
+    const size_t rayBytes = (size_t)n * sizeof(pt_ray), thrBytes = (size_t)n * sizeof(float4);
+    if (int r = s->feat.queryOut.ensure(rayBytes + thrBytes)) return r;
+    char* d = (char*)s->feat.queryOut.p;
+    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
+    if (int r = query_shadow(s, n, d, d + rayBytes, flags, nullptr)) return r;
+    HIP_OK(hipMemcpy(throughput4, d + rayBytes, thrBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pt_query_camera_rays_device(const pt_camera* cam, int w, int h, float max_t, void* d_rays, void* stream) {
+    if (!cam) return fail(-1, "pt_query_camera_rays_device: null camera");
+    if (w <= 0 || h <= 0) return fail(-1, "pt_query_camera_rays_device: image size %d x %d must be positive", w, h);
+    if ((long long)w * h > (1ll << 28)) return fail(-1, "pt_query_camera_rays_device: image of %d x %d pixels is too large", w, h);
+    if (cam->w != w || cam->h != h) return fail(-1, "pt_query_camera_rays_device: the camera is %d x %d, the image %d x %d", cam->w, cam->h, w, h);
+    if (!d_rays) return fail(-1, "pt_query_camera_rays_device: null rays buffer");
+    HIP_OK(launch_query_camera_rays(cam_to_kernel(*cam), w, h, max_t, d_rays, (hipStream_t)stream));
     return 0;
 }

@@ -1,6 +1,6 @@
-// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip): the tiling and block
-// count every one of them is launched with, each kernel's waves per SIMD, and the launchers pt_feature_api.hip calls. The kernels' shared pieces are in
-// pt_feature.h.
+// pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip) and of the ray
+// queries (pt_query.hip): the tiling and block count every one of them is launched with, each kernel's waves per SIMD, and the launchers
+// pt_feature_api.hip calls. The kernels' shared pieces are in pt_feature.h.
 #pragma once
 #include <algorithm>
 #include "pt_params.h"
@@ -26,6 +26,9 @@ constexpr int kMotionChainWavesPerSimd = 5;  // motion_chain_kernel: 93 VGPRs (t
 constexpr int kIdsWavesPerSimd = 8;          // ids_kernel: 63 VGPRs, 8 x 16 KB of LDS, as the centre pass
 constexpr int kIdsChainWavesPerSimd = 6;     // ids_chain_kernel: 76 VGPRs, 18 KB of LDS (the compiler drops follow_chain's record, which the
                                              // kernel never reads): register-bound at aov_centre_chain_kernel's 6
+constexpr int kQueryClosestWavesPerSimd = 8; // query_closest_kernel<false>: 59 VGPRs, 8 x 16 KB of LDS, as the centre pass
+constexpr int kQuerySurfaceWavesPerSimd = 8; // query_closest_kernel<true>: 55 VGPRs, 8 x 16 KB of LDS
+constexpr int kQueryShadowWavesPerSimd = 8;  // query_shadow_kernel: 56 VGPRs, 8 x 16 KB of LDS
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
 
 // spill (every launcher): blocks * 4 waves x S.stackSpill entries x 64 lanes, or NULL for a scene whose stack never leaves the LDS.
@@ -50,5 +53,16 @@ hipError_t launch_motion_chain(const DeviceScene& S, const void* tris, const voi
 // one lane each, ids and hit indexed by entry.
 hipError_t launch_ids(const DeviceScene& S, const CamK& cam, int w, int h, int maxLinks, const int32_t* xy, int nPick, int blocks, int4* ids,
                       float4* hit, int32_t* spill, hipStream_t stream);
+// pt_query.hip: n rays (pt_ray), "tile" t being rays 64 t .. 64 t + 63. perm NULL: lane i takes ray i; else ray perm[i], outputs at perm[i].
+// surfaces NULL: the hits-only kernel. launch_query_keys: every ray's sort key and its index; query_sort: rocprim's radix sort of
+// those pairs (temp NULL: only *tempBytes, the workspace it needs for n pairs, is set). The keys read the root's record: rootRef >= 0.
+hipError_t launch_query_closest(const DeviceScene& S, int n, const void* rays, const uint32_t* perm, int blocks, void* hits, void* surfaces,
+                                int32_t* spill, hipStream_t stream);
+hipError_t launch_query_shadow(const DeviceScene& S, int n, const void* rays, const uint32_t* perm, int blocks, void* throughput, int32_t* spill,
+                               hipStream_t stream);
+hipError_t launch_query_camera_rays(const CamK& cam, int w, int h, float maxT, void* rays, hipStream_t stream);
+hipError_t launch_query_keys(const DeviceScene& S, int n, const void* rays, uint32_t* keys, uint32_t* idx, hipStream_t stream);
+hipError_t query_sort(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, const uint32_t* idxIn, uint32_t* idxOut, int n,
+                      hipStream_t stream);
 
 }  // namespace pt

@@ -71,7 +71,8 @@ struct Adaptive { DevBuf S, M, H, list, keep, count, P, Q, err, out; };
 // pt_render_moments: sums, previous sums, squared batch sums (tile-major); host-form staging; _tiles, host form: the list on the device
 struct Moments { DevBuf S, P, Q, out, list; };
 // the feature passes: their own traversal spill area; host-form staging of pt_render_aovs*, pt_render_motion*, pt_render_ids / pt_pick
-struct Feature { DevBuf spill, aovOut, motionOut, idsOut; };
+// and of pt_query_*; a reordered query's keys and indices (in and out halves each) and rocprim's sort workspace
+struct Feature { DevBuf spill, aovOut, motionOut, idsOut, queryOut, queryKeys, queryIdx, querySort; };
 
 }  // namespace pt
 

@@ -514,7 +514,8 @@ void pt_scene_destroy(pt_scene* s) {
                      &s->spare.geo.nodes, &s->spare.geo.tris, &s->spare.geo.attrs, &s->spare.geo.lights, &s->spare.geo.leaves, &s->spare.normals, &s->spare.pool,
                      &s->work.rng, &s->work.spill, &s->work.tilebuf, &s->work.colors, &s->work.pixcnt, &s->work.queue, &s->work.left, &s->wf.state, &s->wf.ctl, &s->wf.ctr,
                      &s->wf.spill, &s->ad.S, &s->ad.M, &s->ad.H, &s->ad.list, &s->ad.keep, &s->ad.count, &s->ad.P, &s->ad.Q, &s->ad.err, &s->ad.out,
-                     &s->mo.S, &s->mo.P, &s->mo.Q, &s->mo.out, &s->mo.list, &s->feat.spill, &s->feat.aovOut, &s->feat.motionOut, &s->feat.idsOut, &s->upd.edit};
+                     &s->mo.S, &s->mo.P, &s->mo.Q, &s->mo.out, &s->mo.list, &s->feat.spill, &s->feat.aovOut, &s->feat.motionOut, &s->feat.idsOut, &s->feat.queryOut,
+                     &s->feat.queryKeys, &s->feat.queryIdx, &s->feat.querySort, &s->upd.edit};
     for (DevBuf* b : all) b->release();
     if (s->dev.ev0) (void)hipEventDestroy(s->dev.ev0);
     if (s->dev.ev1) (void)hipEventDestroy(s->dev.ev1);

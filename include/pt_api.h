@@ -1242,6 +1242,52 @@ int  pt_preview_read_ids(pt_preview* p, int32_t* out /* w*h*4 */);
 const void* pt_preview_device_ids(pt_preview* p);
 int  pt_preview_id_passes(pt_preview* p);
 
+/* ---- ray queries: closest-hit and shadow rays for a caller's own rays ---- */
+/* A buffer of n rays traced against the scene, on the device and on a stream. Ray i is (o, d, max_t) exactly as given: the direction
+ * is NOT normalised by the library (t is in units of |d|), and pad is not read.
+ * pt_query_closest: the non-counting closest-hit traversal of the feature passes with the ray's own max_t: a hit is accepted if
+ *   t < max_t and it is smaller than the best so far. For max_t <= 999999 the result is therefore pt_probe_trace_closest's hit if that
+ *   hit's t < max_t, and a miss otherwise, bit for bit. A hit writes (t, u, v, tri), tri the index into the description's triangle
+ *   array (as pt_render_ids reports it); a miss writes (0, 0, 0, -1).
+ *   surfaces (NULL: none is written, and nothing of such a buffer is touched): the resolved record of the same hit: its point
+ *   (o + t d, one fma per component), its normal (interpolated, normalised, turned to face the ray), the interpolated uv, the
+ *   material row pt_scene_update_materials replaces, the light index pt_scene_update_emission takes or -1 for a triangle that is no
+ *   light, and backface = 1 if the triangle is seen from its back. A miss writes zeros, with material = light = -1.
+ * pt_query_shadow: throughput[i] = (the shadow traversal's throughput, 0) as a float4: exactly (0, 0, 0) if anything opaque lies
+ *   below max_t, else the product of the transmissions of the leaf-material triangles on the way (the reference's BVHShadowRay);
+ *   pt_probe_trace_shadow's three floats bit for bit.
+ * flags: 0, or PT_QUERY_REORDER: before tracing, every ray gets a 32-bit key (its direction's octant, then a Morton code of its
+ *   origin quantised to 9 bits per axis in the scene's bounds, the union of the root's two child boxes, read on the device; a ray
+ *   with a non-finite origin gets key 0), (key, index) pairs are sorted, and lane i of the trace kernels takes ray perm[i] and writes
+ *   its outputs at perm[i]. Every output is bit-identical to the unordered call for every input: only the order of the work changes.
+ *   A scene whose root is a leaf, and n <= 64, take the unordered path. Opt-in, and so far NOT a gain: on 2 M rays at 1080p the key
+ *   kernel and the sort cost 0.17 ms, and the flag lost on every input measured (1.01 to 1.7 times the unordered call).
+ * The calls touch no RNG state, accumulator or counter of the scene and may run between the chunks of a render. They use the scene's
+ * feature spill area, a reordered call also scene-owned key, index and sort buffers (grown on demand, freed by pt_scene_destroy),
+ * and the host forms a scene-owned staging buffer: like the scene's other work buffers these make the calls ORDERED with other
+ * launches on the same scene (issue them on one stream, or synchronise between streams). After any pt_scene_update_* a query sees
+ * the edited scene, bit for bit as a fresh scene of the edited arrays does.
+ * The device forms are asynchronous on `stream`; d_rays (n pt_ray), d_hits (n pt_ray_hit), d_surfaces (n pt_ray_surface) and
+ * d_throughput (n float4) are device buffers aligned to 16 bytes. The host forms copy in, run on the null stream and copy out.
+ * Arguments are checked before any HIP call, -1 with a message that names the function: a NULL scene, rays or output, n < 0 or
+ * n > 1 << 28, unknown flag bits; n == 0 returns 0 and launches nothing; the device check comes last. */
+typedef struct pt_ray         { float ox, oy, oz, max_t;  float dx, dy, dz;  uint32_t pad; } pt_ray;           /* 32 bytes */
+typedef struct pt_ray_hit     { float t, u, v;  int32_t tri; } pt_ray_hit;                                     /* 16 bytes */
+typedef struct pt_ray_surface { float px, py, pz, uvx;  float nx, ny, nz, uvy;
+                                int32_t material, light, backface, pad; } pt_ray_surface;                      /* 48 bytes */
+#define PT_QUERY_REORDER 1u
+int pt_query_closest_device(pt_scene* scene, int n, const void* d_rays, void* d_hits, void* d_surfaces /* NULL ok */, uint32_t flags,
+                            void* stream);                                                                                    /* async */
+int pt_query_shadow_device(pt_scene* scene, int n, const void* d_rays, void* d_throughput /* n float4 */, uint32_t flags, void* stream);   /* async */
+int pt_query_closest(pt_scene* scene, int n, const pt_ray* rays, pt_ray_hit* hits, pt_ray_surface* surfaces /* NULL ok */,
+                     uint32_t flags);                                                                                         /* host, blocking */
+int pt_query_shadow(pt_scene* scene, int n, const pt_ray* rays, float* throughput4 /* n*4 */, uint32_t flags);                /* host, blocking */
+/* Ray y*w + x = the centre ray of pixel (x, y) as pt_render_aovs_centre and pt_render_ids trace it (pt_probe_centre_rays's o and d
+ * bit for bit), with the given max_t and pad = 0: coherent rays for a tool without an upload, and the tie between a query and those
+ * passes. One thread per pixel, asynchronous on `stream`; needs no scene. Checked before any HIP call (-1, the message names the
+ * function): the camera, a positive size of at most 1 << 28 pixels that is the camera's, the buffer. */
+int pt_query_camera_rays_device(const pt_camera* camera, int w, int h, float max_t, void* d_rays /* w*h pt_ray */, void* stream);         /* async */
+
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
  * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */
