@@ -119,6 +119,7 @@ def _record_dtype(struct):
 
 RAY_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE = _record_dtype(Ray), _record_dtype(RayHit), _record_dtype(RaySurface)
 QUERY_REORDER = 1                    # PT_QUERY_REORDER
+QUERY_STREAM_PAD = 2                 # PT_QUERY_STREAM_PAD
 QUERY_MAX_T = 999999.0               # the max_t of the library's own closest-hit rays
 
 
@@ -222,6 +223,8 @@ def lib():
     L.pt_query_shadow.argtypes = [vp, i32, vp, vp, C.c_uint32]
     L.pt_query_shadow_device.argtypes = [vp, i32, vp, vp, C.c_uint32, vp]
     L.pt_query_camera_rays_device.argtypes = [C.POINTER(Camera), i32, i32, f32, vp, vp]
+    L.pt_query_radiance.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32]
+    L.pt_query_radiance_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
@@ -859,6 +862,25 @@ class Scene:
             if n:
                 _check(lib().pt_query_shadow(self.h, n, _p(r), _p(thr), flags), "pt_query_shadow")
         return thr
+
+    def query_radiance(self, rays, spp, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, first_stream=0, stream_pad=False):
+        """pt_query_radiance: the path-traced light along each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be unit),
+        summed over spp samples: [n, 4] float32 (rgb sums, 0). Ray i draws from stream first_stream + i of `seed`, or, with stream_pad,
+        first_stream + its pad word (uint32). numpy in, numpy out (host form); a torch tensor on the scene's device in, a torch tensor
+        out, on torch's current stream with no host copy. The centre rays of a camera without jitter and aperture give render()'s sums."""
+        is_torch, r, n = self._query_rays("query_radiance", rays)
+        flags = QUERY_STREAM_PAD if stream_pad else 0
+        if is_torch:
+            import torch
+            out = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            _check(lib().pt_query_radiance_device(self.h, n, r.data_ptr() if n else None, spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream,
+                                                  out.data_ptr() if n else None, flags, torch.cuda.current_stream(r.device).cuda_stream or None),
+                   "pt_query_radiance_device")
+        else:
+            out = np.zeros((n, 4), np.float32)
+            _check(lib().pt_query_radiance(self.h, n, _p(r), spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, _p(out), flags),
+                   "pt_query_radiance")
+        return out
 
     def query_camera_rays(self, camera, w, h, max_t=QUERY_MAX_T):
         """pt_query_camera_rays_device: the centre rays of render_aovs_centre / render_ids as an [h*w, 8] float32 torch tensor on the

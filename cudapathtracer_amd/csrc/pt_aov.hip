@@ -9,37 +9,10 @@
 // rng_init_kernel, into registers; the centre ray (pt_centre_ray.h) has no seed. The first-hit kernels follow no specular chain; the
 // chain kernels report the first non-specular surface behind mirrors and glass, the summed path length as depth and the number of
 // links. No pass writes the scene's per-pixel RNG states, its tile accumulator or its counters, so each may run between the chunks of
-// a progressive render.
+// a progressive render. (aov_stream, the seeding, is in pt_feature.h: pt_radiance.hip seeds a ray's stream with it too.)
 #include "pt_feature.h"
 
 namespace pt {
-
-// rng_init_kernel's per-lane body: stream `idx` of XORWOW(seed), via the 2^67-step jump matrices (row-image form).
-PT_DEV Rng aov_stream(const uint32_t* __restrict__ jump, unsigned long long seed, uint32_t idx) {
-    uint32_t s0 = (uint32_t)seed ^ 0xaad26b49u, s1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
-    uint32_t t0 = 1099087573u * s0, t1 = 2591861531u * s1;
-    uint32_t v[5] = {123456789u + t0, 362436069u ^ t0, 521288629u + t1, 88675123u ^ t1, 5783321u + t0};
-    uint32_t d = 6615241u + t1 + t0;
-    for (int k = 0; k < 32; k++) {
-        if (!__ballot((idx >> k) & 1u)) continue;
-        if ((idx >> k) & 1u) {
-            const uint32_t* M = jump + (size_t)k * 800;
-            uint32_t r[5] = {0, 0, 0, 0, 0};
-            for (int i = 0; i < 5; i++) {
-                uint32_t word = v[i];
-#pragma unroll 4          // fully unrolled, the 800 row loads take 256 VGPRs (1 wave per SIMD); by 4: 76 VGPRs, 6 waves
-                for (int j = 0; j < 32; j++) {
-                    uint32_t m = 0u - ((word >> j) & 1u);
-                    const uint32_t* row = M + (i * 32 + j) * 5;
-                    r[0] ^= row[0] & m; r[1] ^= row[1] & m; r[2] ^= row[2] & m; r[3] ^= row[3] & m; r[4] ^= row[4] & m;
-                }
-            }
-            for (int i = 0; i < 5; i++) v[i] = r[i];
-        }
-    }
-    Rng rng = {v[0], v[1], v[2], v[3], v[4], d};
-    return rng;
-}
 
 __global__ void __launch_bounds__(256) aov_kernel(DeviceScene S, CamK cam, const uint32_t* __restrict__ jump, unsigned long long seed,
                                                   int w, int h, int tilesX, int nTiles, int aovSpp, float4* __restrict__ albedo,

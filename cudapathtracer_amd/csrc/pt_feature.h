@@ -4,6 +4,7 @@
 // tiles, with the non-counting trace_closest (max_t 999999, as pt_probe_trace_closest) on an LDS stack that overflows into the
 // scene's spill area:
 //   FeatureWave, tile_pixel   the wave's traversal state and the pixel of a lane in a tile
+//   aov_stream                a XORWOW stream seeded in the kernel, into registers (the jittered aov kernels; pt_radiance.hip)
 //   first_hit_record          a resolved hit's (albedo, 1) and (normal, t)
 //   follow_chain              a ray followed through mirrors and glass to the first non-specular surface; a kernel's ChainHook
 //                             sees every surface and link on the way
@@ -35,6 +36,33 @@ struct FeatureWave {
         C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
     }
 };
+
+// rng_init_kernel's per-lane body: stream `idx` of XORWOW(seed), via the 2^67-step jump matrices (row-image form).
+PT_DEV Rng aov_stream(const uint32_t* __restrict__ jump, unsigned long long seed, uint32_t idx) {
+    uint32_t s0 = (uint32_t)seed ^ 0xaad26b49u, s1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
+    uint32_t t0 = 1099087573u * s0, t1 = 2591861531u * s1;
+    uint32_t v[5] = {123456789u + t0, 362436069u ^ t0, 521288629u + t1, 88675123u ^ t1, 5783321u + t0};
+    uint32_t d = 6615241u + t1 + t0;
+    for (int k = 0; k < 32; k++) {
+        if (!__ballot((idx >> k) & 1u)) continue;
+        if ((idx >> k) & 1u) {
+            const uint32_t* M = jump + (size_t)k * 800;
+            uint32_t r[5] = {0, 0, 0, 0, 0};
+            for (int i = 0; i < 5; i++) {
+                uint32_t word = v[i];
+#pragma unroll 4          // fully unrolled, the 800 row loads take 256 VGPRs (1 wave per SIMD); by 4: 76 VGPRs, 6 waves
+                for (int j = 0; j < 32; j++) {
+                    uint32_t m = 0u - ((word >> j) & 1u);
+                    const uint32_t* row = M + (i * 32 + j) * 5;
+                    r[0] ^= row[0] & m; r[1] ^= row[1] & m; r[2] ^= row[2] & m; r[3] ^= row[3] & m; r[4] ^= row[4] & m;
+                }
+            }
+            for (int i = 0; i < 5; i++) v[i] = r[i];
+        }
+    }
+    Rng rng = {v[0], v[1], v[2], v[3], v[4], d};
+    return rng;
+}
 
 // The pixel of `lane` in tile `tile`; inside: the tile's last column and row may hang over the image.
 struct TilePixel { int x, y; bool inside; };

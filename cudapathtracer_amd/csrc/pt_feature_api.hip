@@ -1,5 +1,5 @@
 // pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
-// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip; their launchers and block counts: pt_feature_host.h.)
+// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_radiance.hip; their launchers and block counts: pt_feature_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -339,6 +339,61 @@ int pt_query_shadow(pt_scene* s, int n, const pt_ray* rays, float* throughput4, 
     HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
     if (int r = query_shadow(s, n, d, d + rayBytes, flags, nullptr)) return r;
     HIP_OK(hipMemcpy(throughput4, d + rayBytes, thrBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Radiance queries (pt_radiance.hip: radiance_kernel). Every message under pt_query_radiance, all before any HIP call; n == 0 returns
+// before the scene or anything else is looked at.
+static int check_radiance_args(pt_scene* s, int n, const void* rays, const void* out, int spp, int integrator, uint32_t firstStream, uint32_t flags) {
+    const char* fn = "pt_query_radiance";
+    if (n < 0 || n > (1 << 28)) return fail(-1, "%s: n %d must be 0..%d", fn, n, 1 << 28);
+    if (n == 0) return 0;
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!rays) return fail(-1, "%s: null rays", fn);
+    if (!out) return fail(-1, "%s: null output buffer", fn);
+    if (spp < 1 || spp > (1 << 22)) return fail(-1, "%s: spp %d must be 1..%d", fn, spp, 1 << 22);
+    if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
+        return fail(-1, "%s: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", fn, integrator);
+    if (flags & PT_QUERY_REORDER) return fail(-1, "%s: PT_QUERY_REORDER is not taken here: a path leaves its first ray's order at once", fn);
+    if (flags & ~PT_QUERY_STREAM_PAD) return fail(-1, "%s: unknown flag bits 0x%x", fn, flags & ~PT_QUERY_STREAM_PAD);
+    if (!(flags & PT_QUERY_STREAM_PAD) && (unsigned long long)firstStream + (unsigned long long)n > (1ull << 31))
+        return fail(-1, "%s: streams %u .. %llu pass 2^31", fn, firstStream, (unsigned long long)firstStream + (unsigned long long)n - 1ull);
+    return 0;
+}
+
+// The scene's material class picks the instantiation as the render launch picks its bounce (pt_plan.hip: launch_plan): SIMPLE for a
+// scene that qualifies unless the "simple" option is 0, else LEAN likewise. No other option is read.
+static int query_radiance(pt_scene* s, int n, const void* dRays, int spp, int maxDepth, int integrator, int useMIS, uint64_t seed, uint32_t firstStream,
+                          void* dOut, uint32_t flags, hipStream_t stream) {
+    const bool simple = s->facts.simpleOk && s->opt.simpleWanted;
+    const bool lean = s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !simple;
+    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, radiance_waves_per_simd(integrator, simple, lean));
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_radiance(s->facts.ds, integrator, simple, lean, n, dRays, (const uint32_t*)s->data.jump.p, seed, firstStream,
+                           (flags & PT_QUERY_STREAM_PAD) != 0, spp, maxDepth, useMIS, blocks, dOut, spill, stream));
+    return 0;
+}
+
+int pt_query_radiance_device(pt_scene* s, int n, const void* d_rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
+                             uint32_t first_stream, void* d_rgba_sum, unsigned flags, void* stream) {
+    if (int r = check_radiance_args(s, n, d_rays, d_rgba_sum, spp, integrator, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_radiance", s)) return r;
+    return query_radiance(s, n, d_rays, spp, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, flags, (hipStream_t)stream);
+}
+
+int pt_query_radiance(pt_scene* s, int n, const pt_ray* rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
+                      uint32_t first_stream, float* out_rgba_sum, unsigned flags) {
+    if (int r = check_radiance_args(s, n, rays, out_rgba_sum, spp, integrator, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_radiance", s)) return r;
+    const size_t rayBytes = (size_t)n * sizeof(pt_ray), outBytes = (size_t)n * sizeof(float4);
+    if (int r = s->feat.queryOut.ensure(rayBytes + outBytes)) return r;
+    char* d = (char*)s->feat.queryOut.p;
+    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
+    if (int r = query_radiance(s, n, d, spp, max_depth, integrator, use_mis, seed, first_stream, d + rayBytes, flags, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_rgba_sum, d + rayBytes, outBytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

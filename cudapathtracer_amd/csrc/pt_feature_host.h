@@ -29,6 +29,14 @@ constexpr int kIdsChainWavesPerSimd = 6;     // ids_chain_kernel: 76 VGPRs, 18 K
 constexpr int kQueryClosestWavesPerSimd = 8; // query_closest_kernel<false>: 59 VGPRs, 8 x 16 KB of LDS, as the centre pass
 constexpr int kQuerySurfaceWavesPerSimd = 8; // query_closest_kernel<true>: 55 VGPRs, 8 x 16 KB of LDS
 constexpr int kQueryShadowWavesPerSimd = 8;  // query_shadow_kernel: 56 VGPRs, 8 x 16 KB of LDS
+// radiance_kernel<INTEG, SIMPLE, LEAN> (pt_radiance.hip): the waves per SIMD each instantiation is launched at and compiled for
+// (amdgpu_waves_per_eu), from the compile and, where one step more costs scratch, from the measurement. VGPRs /
+// scratch bytes per lane at the setting, and at the one not taken:
+//   naive, SIMPLE    6: 79 / 0     (8: 64 / 52, +13 % on the blob)      MIS, SIMPLE    6: 80 / 28    (5: 91 / 0, 4-6 % slower)
+//   naive, LEAN      5: 94 / 0     (6: 80 / 72, level)                  MIS, LEAN      5: 96 / 84    (4: 118 / 0, 11 % slower)
+//   naive, generic   4: 96 / 0     (5: 96 / 20)                         MIS, generic   4: 128 / 12   (5: 96 / 148; 3: 131 / 0)
+// LDS: 16 KB of stacks, and 4 KB of medium stacks in the kernels that are not SIMPLE: 8 workgroups fit a CU either way.
+constexpr int radiance_waves_per_simd(int integrator, bool simple, bool lean) { return simple ? 6 : lean ? 5 : 4; }
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
 
 // spill (every launcher): blocks * 4 waves x S.stackSpill entries x 64 lanes, or NULL for a scene whose stack never leaves the LDS.
@@ -64,5 +72,10 @@ hipError_t launch_query_camera_rays(const CamK& cam, int w, int h, float maxT, v
 hipError_t launch_query_keys(const DeviceScene& S, int n, const void* rays, uint32_t* keys, uint32_t* idx, hipStream_t stream);
 hipError_t query_sort(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, const uint32_t* idxIn, uint32_t* idxOut, int n,
                       hipStream_t stream);
+// pt_radiance.hip: radiance_kernel<integrator, simple, lean> on n rays, ray i on stream firstStream + i of `seed` (streamPad: + its pad
+// word instead of i), spp samples each, out[i] = (the sum of its samples' Li, 0). blocks: feature_blocks at radiance_waves_per_simd.
+hipError_t launch_radiance(const DeviceScene& S, int integrator, bool simple, bool lean, int n, const void* rays, const uint32_t* jump,
+                           unsigned long long seed, uint32_t firstStream, bool streamPad, int spp, int maxDepth, int useMIS, int blocks, void* out,
+                           int32_t* spill, hipStream_t stream);
 
 }  // namespace pt

@@ -1,0 +1,54 @@
+"""Ray buffers for Scene.query_radiance / query_closest / query_shadow: camera models the library's own pt_camera (a pinhole or thin
+lens on a pixel grid) does not have. Plain numpy, or torch when `device` is given; no library call. Every function returns an
+[n, 8] float32 array of pt_ray records (ox, oy, oz, max_t, dx, dy, dz, pad), row-major over the image (ray y*w + x), with unit
+directions and pad = 0: ray i then draws from stream first_stream + i.
+
+    pano = sc.query_radiance(rays.panorama_rays((0, 0, 1.5), 2048, 1024), spp=16, max_depth=8).reshape(1024, 2048, 4) / 16
+"""
+import numpy as np
+
+from .api import QUERY_MAX_T
+
+
+def _xp(device):
+    if device is None:
+        return np, {}
+    import torch
+    return torch, {"device": device}
+
+
+def _records(xp, kw, o, d, n, max_t):
+    out = xp.zeros((n, 8), dtype=xp.float32, **kw)
+    out[:, 0:3] = o
+    out[:, 3] = max_t
+    out[:, 4:7] = d
+    return out
+
+
+def panorama_rays(origin, w, h, max_t=QUERY_MAX_T, device=None):
+    """An equirectangular panorama from `origin`: column x is the azimuth (x + 0.5) / w * 2 pi about +y, counted from -z towards +x
+    (the library's cameras look down -z), row y the elevation ((y + 0.5) / h - 0.5) * pi: the first row looks down, the last up."""
+    xp, kw = _xp(device)
+    az = (xp.arange(w, dtype=xp.float64, **kw) + 0.5) / w * (2.0 * np.pi)
+    el = ((xp.arange(h, dtype=xp.float64, **kw) + 0.5) / h - 0.5) * np.pi
+    ce, se = xp.cos(el)[:, None], xp.sin(el)[:, None]
+    d = xp.stack([ce * xp.sin(az)[None, :], se * xp.ones_like(az)[None, :], -ce * xp.cos(az)[None, :]], -1).reshape(h * w, 3)
+    d = d / xp.sqrt((d * d).sum(-1))[:, None]
+    o = xp.asarray(np.asarray(origin, np.float64), **kw).reshape(1, 3)
+    return _records(xp, kw, o.to(xp.float32) if xp is not np else o, d.to(xp.float32) if xp is not np else d, h * w, max_t)
+
+
+def orthographic_rays(origin, forward, up, width, height, w, h, max_t=QUERY_MAX_T, device=None):
+    """An orthographic sensor of width x height scene units centred at `origin`, looking along `forward` with `up` up: every ray has
+    the direction forward / |forward|; ray y*w + x starts at the centre of cell (x, y) of the sensor, x to the right (forward x up),
+    y upwards."""
+    xp, kw = _xp(device)
+    f = np.asarray(forward, np.float64); f = f / np.linalg.norm(f)
+    r = np.cross(f, np.asarray(up, np.float64)); r = r / np.linalg.norm(r)
+    u = np.cross(r, f)
+    sx = ((xp.arange(w, dtype=xp.float64, **kw) + 0.5) / w - 0.5) * width
+    sy = ((xp.arange(h, dtype=xp.float64, **kw) + 0.5) / h - 0.5) * height
+    c = lambda v: xp.asarray(v, **kw).reshape(1, 1, 3)
+    o = (c(np.asarray(origin, np.float64)) + sx[None, :, None] * c(r) + sy[:, None, None] * c(u)).reshape(h * w, 3)
+    d = xp.asarray(f.astype(np.float32), **kw).reshape(1, 3)
+    return _records(xp, kw, o.to(xp.float32) if xp is not np else o, d, h * w, max_t)

@@ -1287,6 +1287,41 @@ int pt_query_shadow(pt_scene* scene, int n, const pt_ray* rays, float* throughpu
  * passes. One thread per pixel, asynchronous on `stream`; needs no scene. Checked before any HIP call (-1, the message names the
  * function): the camera, a positive size of at most 1 << 28 pixels that is the camera's, the buffer. */
 int pt_query_camera_rays_device(const pt_camera* camera, int w, int h, float max_t, void* d_rays /* w*h pt_ray */, void* stream);         /* async */
+/* pt_query_radiance: the path tracer on the caller's rays: the light that arrives along each ray, summed over spp
+ * samples. This is what a panorama, a fisheye or orthographic sensor, a stereo pair in one launch, lightmap texels and light probes
+ * are rendered with. It is NOT a replacement for pt_render: a per-lane walk, far slower than the megakernels on a scene they hold
+ * in LDS (the measured ratios are in §24).
+ * Stream. Ray i owns one XORWOW stream: the stream rng_init_kernel gives subsequence k_i of `seed`, k_i = first_stream + i, or, with
+ *   PT_QUERY_STREAM_PAD, first_stream + (the ray's pad word read as uint32), in uint32 arithmetic (it wraps). Without the flag
+ *   first_stream + n must not pass 2^31. The stream runs on through the ray's spp samples, as a pixel's does.
+ * Sample. Every sample uses the same ray. It first draws two uniforms and drops them (the two jitter draws the reference's camera
+ *   spends) and draws no lens numbers. Then it runs the reference's Li_unidirectional (integrator 0, use_mis as given) or
+ *   Li_naive_unidirectional (integrator 2) from path_begin's state at (o, d) as given: beta 1, Li 0, prevPoint 0, pdf = etaI = etaT =
+ *   EPS, depth 0, the medium stack holding air. The direction is used as given, NOT normalised: the path's arithmetic assumes
+ *   |d| = 1, and a caller whose d is not unit gets what that arithmetic makes of it. The first segment's closest hit uses the ray's own
+ *   max_t, accepted as pt_query_closest accepts it (t < max_t); every later segment uses 999999, as the path does. The iteration
+ *   guard of DESIGN.md §4 applies. max_depth: any value, as pt_render takes it.
+ * Output. out[i].xyz = ((0 + Li_0) + Li_1) + ... in sample order, in f32; out[i].w = 0. The call writes; it does not add.
+ * Identity. For a camera cam0 with antiAliasJitterDist = 0 and aperture = 0, the rays pt_query_camera_rays_device(cam0, w, h, 999999)
+ *   gives, first_stream = 0 and flags = 0, `out` viewed as w*h float4 equals pt_render(scene, cam0, w, h, spp, max_depth, integrator,
+ *   use_mis, seed, NULL, zeroed) bit for bit, and so the oracle's render.
+ * Independence. A ray's result depends only on the scene, its 32 bytes, k_i, seed, spp, max_depth, integrator and use_mis: not on n,
+ *   on its place in the buffer or on what the other lanes of its wave hold.
+ * What a call touches: the scene's feature spill area and, the host form, its query staging buffer (so it is ORDERED with other
+ *   launches on the scene, as the queries above). No per-pixel RNG state, tile accumulator, counter or tile queue. pt_set_variant
+ *   does not reach it. Of the pt_set_option values the two that decide the material class of the kernel are honoured: "simple" 0
+ *   and "lean" 0 turn the SIMPLE and the LEAN bounce off (same bits, the generic kernel). Scheduling options are not read, nor is
+ *   "culling": there is no CULL form. After any pt_scene_update_* a call sees the edited scene. PT_QUERY_REORDER is refused (-1): it
+ *   lost every measurement of §23, and a path leaves its first ray's order at once.
+ * Checked before any HIP call, -1 with a message under pt_query_radiance: n < 0 or n > 1 << 28 (n == 0 then returns 0 before the
+ *   scene or anything else is looked at); a NULL scene, rays or output; spp < 1 or spp > 1 << 22; an integrator other than 0 and 2;
+ *   PT_QUERY_REORDER and unknown flag bits; without PT_QUERY_STREAM_PAD, first_stream + n > 2^31. The device check comes last.
+ * d_rays (n pt_ray) and d_rgba_sum (n float4) are device buffers aligned to 16 bytes; the device form is asynchronous on `stream`. */
+#define PT_QUERY_STREAM_PAD 2u
+int pt_query_radiance_device(pt_scene* scene, int n, const void* d_rays /* n pt_ray */, int spp, int max_depth, int integrator, int use_mis,
+                             uint64_t seed, uint32_t first_stream, void* d_rgba_sum /* n float4 */, unsigned flags, void* stream);   /* async */
+int pt_query_radiance(pt_scene* scene, int n, const pt_ray* rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
+                      uint32_t first_stream, float* out_rgba_sum /* n*4 */, unsigned flags);                                  /* host, blocking */
 
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
