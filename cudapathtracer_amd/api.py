@@ -225,6 +225,10 @@ def lib():
     L.pt_query_camera_rays_device.argtypes = [C.POINTER(Camera), i32, i32, f32, vp, vp]
     L.pt_query_radiance.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32]
     L.pt_query_radiance_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
+    L.pt_query_radiance_moments.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32]
+    L.pt_query_radiance_moments_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
+    L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
     L.pt_light_triangles.argtypes = [C.POINTER(SceneDesc), vp]
     L.pt_scene_destroy.argtypes = [vp]
@@ -881,6 +885,51 @@ class Scene:
             _check(lib().pt_query_radiance(self.h, n, _p(r), spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, _p(out), flags),
                    "pt_query_radiance")
         return out
+
+    def query_radiance_moments(self, rays, spp, batch_spp, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, first_stream=0,
+                               stream_pad=False):
+        """pt_query_radiance_moments: query_radiance in spp / batch_spp batches of batch_spp samples. Returns (S, Q), both [n, 4]
+        float32: S is query_radiance's output bit for bit, Q per rgb channel the sum of the ray's squared batch sums and Q.w the
+        number of batches, as render_moments defines them. numpy in, numpy out (host form); a torch tensor on the scene's device in,
+        tensors out, on torch's current stream with no host copy. denoise_var(S.reshape(h, w, 4), Q.reshape(h, w, 4), spp,
+        spp // batch_spp, ...) reads the pair."""
+        is_torch, r, n = self._query_rays("query_radiance_moments", rays)
+        flags = QUERY_STREAM_PAD if stream_pad else 0
+        if is_torch:
+            import torch
+            S = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            Q = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            _check(lib().pt_query_radiance_moments_device(self.h, n, r.data_ptr() if n else None, spp, batch_spp, max_depth, integrator, 1 if use_mis else 0,
+                                                          seed, first_stream, S.data_ptr() if n else None, Q.data_ptr() if n else None, flags,
+                                                          torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_radiance_moments_device")
+        else:
+            S = np.zeros((n, 4), np.float32)
+            Q = np.zeros((n, 4), np.float32)
+            _check(lib().pt_query_radiance_moments(self.h, n, _p(r), spp, batch_spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream,
+                                                   _p(S), _p(Q), flags), "pt_query_radiance_moments")
+        return S, Q
+
+    def query_guides(self, rays, max_links=0, links=False):
+        """pt_query_guides: render_aovs_centre's guides for each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be
+        unit): (albedo, normal_depth), both [n, 4] float32: (albedo, 1) and (normal, summed path length) of the first non-specular
+        surface behind at most max_links mirror and glass links, zeros for a ray that hits nothing below its max_t; links=True appends
+        the link count [n] float32. numpy in, numpy out (host form); a torch tensor on the scene's device in, tensors out, on torch's
+        current stream with no host copy."""
+        is_torch, r, n = self._query_rays("query_guides", rays)
+        if is_torch:
+            import torch
+            alb = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            nd = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            ln = torch.empty((n,), dtype=torch.float32, device=r.device) if links else None
+            if n:
+                _check(lib().pt_query_guides_device(self.h, n, r.data_ptr(), max_links, alb.data_ptr(), nd.data_ptr(), ln.data_ptr() if links else None, 0,
+                                                    torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_guides_device")
+        else:
+            alb = np.zeros((n, 4), np.float32)
+            nd = np.zeros((n, 4), np.float32)
+            ln = np.zeros(n, np.float32) if links else None
+            _check(lib().pt_query_guides(self.h, n, _p(r), max_links, _p(alb), _p(nd), _p(ln) if links else None, 0), "pt_query_guides")
+        return (alb, nd, ln) if links else (alb, nd)
 
     def query_camera_rays(self, camera, w, h, max_t=QUERY_MAX_T):
         """pt_query_camera_rays_device: the centre rays of render_aovs_centre / render_ids as an [h*w, 8] float32 torch tensor on the

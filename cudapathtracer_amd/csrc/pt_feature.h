@@ -1,6 +1,7 @@
 // pt_feature.h — what the feature kernels are assembled from (pt_aov.hip: aov_kernel, aov_chain_kernel, aov_centre_kernel,
 // aov_centre_chain_kernel; pt_motion.hip: motion_kernel; pt_motion_chain.hip: motion_chain_kernel; pt_ids.hip: ids_kernel,
-// ids_chain_kernel; pt_query.hip's trace kernels use FeatureWave on 64 rays a tile). Every one of them is one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the
+// ids_chain_kernel; pt_query.hip's trace kernels, pt_query_guides.hip, pt_radiance.hip and pt_radiance_moments.hip use FeatureWave on 64
+// rays a tile). Every one of them is one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the
 // tiles, with the non-counting trace_closest (max_t 999999, as pt_probe_trace_closest) on an LDS stack that overflows into the
 // scene's spill area:
 //   FeatureWave, tile_pixel   the wave's traversal state and the pixel of a lane in a tile
@@ -105,17 +106,18 @@ struct ChainHook {
 // first hit, overwritten where the chain ends on a surface and simply stays when it does not (a miss after the first hit, or the cap),
 // and the caller reads it once afterwards, so it need not be live across the traversals (7 VGPRs: 86 -> 6 waves per SIMD).
 // The direction arithmetic is written out operation by operation (no dot(), normalize(), fmaf): tests/aov_chain_ref.py restates it.
-// hook: the kernel's ChainHook; whatever it keeps is live across the traversals too.
+// hook: the kernel's ChainHook; whatever it keeps is live across the traversals too. firstMaxT: the first ray's max_t (a caller's
+// own ray, pt_query_guides.hip); every link's is 999999, and so is the first ray's in every kernel that passes none.
 template <class Hook = ChainHook>
 PT_DEV int follow_chain(const DeviceScene& S, const SceneCache& C, Stack<kStackLds>& st, Ctr& c, V3 o, V3 d, bool live, int maxLinks, float* rec,
-                        Hook&& hook = Hook()) {
+                        Hook&& hook = Hook(), float firstMaxT = 999999.0f) {
     float depth = 0.0f;
     int links = -1;
     for (int i = 0; i <= maxLinks; i++) {
         if (!__ballot(live)) break;
         if (live) {
             Hit hit;
-            trace_closest<false, kStackLds>(S, C, o, d, 999999.0f, st, hit, c);
+            trace_closest<false, kStackLds>(S, C, o, d, i == 0 ? firstMaxT : 999999.0f, st, hit, c);
             live = false;
             if (hit.tri >= 0) {                  // (a miss: no hit at all at i = 0, the first hit's record stands after that)
                 HitInfo hi; resolve_hit(S, hit, o, d, hi);

@@ -1,5 +1,5 @@
 // pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
-// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_radiance.hip; their launchers and block counts: pt_feature_host.h.)
+// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_query_guides.hip; their launchers and block counts: pt_feature_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -342,10 +342,10 @@ int pt_query_shadow(pt_scene* s, int n, const pt_ray* rays, float* throughput4, 
     return 0;
 }
 
-// Radiance queries (pt_radiance.hip: radiance_kernel). Every message under pt_query_radiance, all before any HIP call; n == 0 returns
-// before the scene or anything else is looked at.
-static int check_radiance_args(pt_scene* s, int n, const void* rays, const void* out, int spp, int integrator, uint32_t firstStream, uint32_t flags) {
-    const char* fn = "pt_query_radiance";
+// Radiance queries (pt_radiance.hip: radiance_kernel; pt_radiance_moments.hip: radiance_moments_kernel). Every message under the
+// caller's name, all before any HIP call; n == 0 returns before the scene or anything else is looked at.
+static int check_radiance_args(const char* fn, pt_scene* s, int n, const void* rays, const void* out, int spp, int integrator, uint32_t firstStream,
+                               uint32_t flags) {
     if (n < 0 || n > (1 << 28)) return fail(-1, "%s: n %d must be 0..%d", fn, n, 1 << 28);
     if (n == 0) return 0;
     if (!s) return fail(-1, "%s: null scene", fn);
@@ -377,7 +377,7 @@ static int query_radiance(pt_scene* s, int n, const void* dRays, int spp, int ma
 
 int pt_query_radiance_device(pt_scene* s, int n, const void* d_rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
                              uint32_t first_stream, void* d_rgba_sum, unsigned flags, void* stream) {
-    if (int r = check_radiance_args(s, n, d_rays, d_rgba_sum, spp, integrator, first_stream, flags)) return r;
+    if (int r = check_radiance_args("pt_query_radiance", s, n, d_rays, d_rgba_sum, spp, integrator, first_stream, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_radiance", s)) return r;
     return query_radiance(s, n, d_rays, spp, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, flags, (hipStream_t)stream);
@@ -385,7 +385,7 @@ int pt_query_radiance_device(pt_scene* s, int n, const void* d_rays, int spp, in
 
 int pt_query_radiance(pt_scene* s, int n, const pt_ray* rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
                       uint32_t first_stream, float* out_rgba_sum, unsigned flags) {
-    if (int r = check_radiance_args(s, n, rays, out_rgba_sum, spp, integrator, first_stream, flags)) return r;
+    if (int r = check_radiance_args("pt_query_radiance", s, n, rays, out_rgba_sum, spp, integrator, first_stream, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_radiance", s)) return r;
     const size_t rayBytes = (size_t)n * sizeof(pt_ray), outBytes = (size_t)n * sizeof(float4);
@@ -394,6 +394,102 @@ int pt_query_radiance(pt_scene* s, int n, const pt_ray* rays, int spp, int max_d
     HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
     if (int r = query_radiance(s, n, d, spp, max_depth, integrator, use_mis, seed, first_stream, d + rayBytes, flags, nullptr)) return r;
     HIP_OK(hipMemcpy(out_rgba_sum, d + rayBytes, outBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// pt_query_radiance_moments: pt_query_radiance's checks in its order, then the batches' and the second output. (n == 0: the callers return.)
+static int check_radiance_moments_args(pt_scene* s, int n, const void* rays, const void* out, const void* sq, int spp, int batchSpp, int integrator,
+                                       uint32_t firstStream, uint32_t flags) {
+    const char* fn = "pt_query_radiance_moments";
+    if (int r = check_radiance_args(fn, s, n, rays, out, spp, integrator, firstStream, flags)) return r;
+    if (n == 0) return 0;
+    if (batchSpp < 1) return fail(-1, "%s: batch_spp %d must be positive", fn, batchSpp);
+    if (spp % batchSpp != 0) return fail(-1, "%s: spp %d is not a multiple of batch_spp %d", fn, spp, batchSpp);
+    if (spp / batchSpp < 2) return fail(-1, "%s: %d batch(es): a variance needs at least 2", fn, spp / batchSpp);
+    if (!sq) return fail(-1, "%s: null sq_sum buffer", fn);
+    return 0;
+}
+
+// query_radiance with radiance_moments_kernel: the same class, its own waves per SIMD.
+static int query_radiance_moments(pt_scene* s, int n, const void* dRays, int spp, int batchSpp, int maxDepth, int integrator, int useMIS, uint64_t seed,
+                                  uint32_t firstStream, void* dOut, void* dSq, uint32_t flags, hipStream_t stream) {
+    const bool simple = s->facts.simpleOk && s->opt.simpleWanted;
+    const bool lean = s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !simple;
+    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, radiance_moments_waves_per_simd(integrator, simple, lean));
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_radiance_moments(s->facts.ds, integrator, simple, lean, n, dRays, (const uint32_t*)s->data.jump.p, seed, firstStream,
+                                   (flags & PT_QUERY_STREAM_PAD) != 0, spp, batchSpp, maxDepth, useMIS, blocks, dOut, dSq, spill, stream));
+    return 0;
+}
+
+int pt_query_radiance_moments_device(pt_scene* s, int n, const void* d_rays, int spp, int batch_spp, int max_depth, int integrator, int use_mis,
+                                     uint64_t seed, uint32_t first_stream, void* d_rgba_sum, void* d_sq_sum, unsigned flags, void* stream) {
+    if (int r = check_radiance_moments_args(s, n, d_rays, d_rgba_sum, d_sq_sum, spp, batch_spp, integrator, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_radiance_moments", s)) return r;
+    return query_radiance_moments(s, n, d_rays, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, d_sq_sum, flags,
+                                  (hipStream_t)stream);
+}
+
+int pt_query_radiance_moments(pt_scene* s, int n, const pt_ray* rays, int spp, int batch_spp, int max_depth, int integrator, int use_mis, uint64_t seed,
+                              uint32_t first_stream, float* out_rgba_sum, float* out_sq_sum, unsigned flags) {
+    if (int r = check_radiance_moments_args(s, n, rays, out_rgba_sum, out_sq_sum, spp, batch_spp, integrator, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_radiance_moments", s)) return r;
+    const size_t rayBytes = (size_t)n * sizeof(pt_ray), outBytes = (size_t)n * sizeof(float4);
+    if (int r = s->feat.queryOut.ensure(rayBytes + 2 * outBytes)) return r;
+    char* d = (char*)s->feat.queryOut.p;
+    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
+    if (int r = query_radiance_moments(s, n, d, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d + rayBytes, d + rayBytes + outBytes,
+                                       flags, nullptr))
+        return r;
+    HIP_OK(hipMemcpy(out_rgba_sum, d + rayBytes, outBytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_sq_sum, d + rayBytes + outBytes, outBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Guide queries (pt_query_guides.hip: query_guides_kernel, query_guides_chain_kernel). Every message under pt_query_guides, all
+// before any HIP call; n == 0 returns once the arguments have passed (the device check comes last).
+static int check_guides_args(pt_scene* s, int n, const void* rays, int maxLinks, const void* a, const void* nd, uint32_t flags) {
+    const char* fn = "pt_query_guides";
+    if (n < 0 || n > (1 << 28)) return fail(-1, "%s: n %d must be 0..%d", fn, n, 1 << 28);
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!rays) return fail(-1, "%s: null rays", fn);
+    if (!a || !nd) return fail(-1, "%s: null output buffer", fn);
+    if (maxLinks < 0 || maxLinks > 16) return fail(-1, "%s: max_links %d must be 0..16", fn, maxLinks);
+    if (flags) return fail(-1, "%s: flags 0x%x: the word is reserved and must be 0", fn, flags);
+    return 0;
+}
+
+static int query_guides(pt_scene* s, int n, const void* dRays, int maxLinks, void* dA, void* dN, void* dL, hipStream_t stream) {
+    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, maxLinks > 0 ? kQueryGuidesChainWavesPerSimd : kQueryGuidesWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_query_guides(s->facts.ds, n, dRays, maxLinks, blocks, dA, dN, (float*)dL, spill, stream));
+    return 0;
+}
+
+int pt_query_guides_device(pt_scene* s, int n, const void* d_rays, int max_links, void* d_albedo, void* d_normal_depth, void* d_links, unsigned flags,
+                           void* stream) {
+    if (int r = check_guides_args(s, n, d_rays, max_links, d_albedo, d_normal_depth, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_guides", s)) return r;
+    return query_guides(s, n, d_rays, max_links, d_albedo, d_normal_depth, d_links, (hipStream_t)stream);
+}
+
+int pt_query_guides(pt_scene* s, int n, const pt_ray* rays, int max_links, float* out_albedo, float* out_normal_depth, float* out_links, unsigned flags) {
+    if (int r = check_guides_args(s, n, rays, max_links, out_albedo, out_normal_depth, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device("pt_query_guides", s)) return r;
+    const size_t rayBytes = (size_t)n * sizeof(pt_ray), recBytes = (size_t)n * sizeof(float4), linkBytes = out_links ? (size_t)n * sizeof(float) : 0;
+    if (int r = s->feat.queryOut.ensure(rayBytes + 2 * recBytes + linkBytes)) return r;
+    char* d = (char*)s->feat.queryOut.p;
+    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
+    if (int r = query_guides(s, n, d, max_links, d + rayBytes, d + rayBytes + recBytes, out_links ? d + rayBytes + 2 * recBytes : nullptr, nullptr)) return r;
+    HIP_OK(hipMemcpy(out_albedo, d + rayBytes, recBytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_normal_depth, d + rayBytes + recBytes, recBytes, hipMemcpyDeviceToHost));
+    if (out_links) HIP_OK(hipMemcpy(out_links, d + rayBytes + 2 * recBytes, linkBytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

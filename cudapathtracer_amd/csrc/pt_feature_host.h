@@ -1,5 +1,5 @@
 // pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip) and of the ray
-// queries (pt_query.hip): the tiling and block count every one of them is launched with, each kernel's waves per SIMD, and the launchers
+// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip): the tiling and block count every one of them is launched with, each kernel's waves per SIMD, and the launchers
 // pt_feature_api.hip calls. The kernels' shared pieces are in pt_feature.h.
 #pragma once
 #include <algorithm>
@@ -37,6 +37,16 @@ constexpr int kQueryShadowWavesPerSimd = 8;  // query_shadow_kernel: 56 VGPRs, 8
 //   naive, generic   4: 96 / 0     (5: 96 / 20)                         MIS, generic   4: 128 / 12   (5: 96 / 148; 3: 131 / 0)
 // LDS: 16 KB of stacks, and 4 KB of medium stacks in the kernels that are not SIMPLE: 8 workgroups fit a CU either way.
 constexpr int radiance_waves_per_simd(int integrator, bool simple, bool lean) { return simple ? 6 : lean ? 5 : 4; }
+// radiance_moments_kernel<INTEG, SIMPLE, LEAN> (pt_radiance_moments.hip): radiance_kernel's settings, unmeasured against their
+// neighbours. With the batch bookkeeping in LDS (7 KB more per workgroup), VGPRs / scratch bytes per lane, and with
+// it in registers:
+//   naive, SIMPLE    6: 80 / 0     (registers: 80 / 16)                 MIS, SIMPLE    6: 80 / 36    (registers: 80 / 64)
+//   naive, LEAN      5: 96 / 0     (registers: 96 / 20)                 MIS, LEAN      5: 96 / 88    (registers: 96 / 112)
+//   naive, generic   4: 99 / 0     (registers: 103 / 0)                 MIS, generic   4: 128 / 12   (registers: 128 / 28)
+// LDS: 23 KB in the SIMPLE kernels (6 workgroups: 138 KB), 27 KB in the others (5: 135 KB).
+constexpr int radiance_moments_waves_per_simd(int integrator, bool simple, bool lean) { return simple ? 6 : lean ? 5 : 4; }
+constexpr int kQueryGuidesWavesPerSimd = 8;       // query_guides_kernel: 55 VGPRs, 8 x 16 KB of LDS, as the centre pass
+constexpr int kQueryGuidesChainWavesPerSimd = 6;  // query_guides_chain_kernel: 60 VGPRs, 23 KB of LDS: 7 workgroups would need 161 KB
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
 
 // spill (every launcher): blocks * 4 waves x S.stackSpill entries x 64 lanes, or NULL for a scene whose stack never leaves the LDS.
@@ -77,5 +87,15 @@ hipError_t query_sort(void* temp, size_t* tempBytes, const uint32_t* keysIn, uin
 hipError_t launch_radiance(const DeviceScene& S, int integrator, bool simple, bool lean, int n, const void* rays, const uint32_t* jump,
                            unsigned long long seed, uint32_t firstStream, bool streamPad, int spp, int maxDepth, int useMIS, int blocks, void* out,
                            int32_t* spill, hipStream_t stream);
+// pt_radiance_moments.hip: radiance_moments_kernel likewise, the spp samples in batches of batchSpp (spp a multiple of it): out[i] as
+// launch_radiance writes it, sq[i] = (the sum of the ray's squared batch sums, spp / batchSpp). blocks: feature_blocks at
+// radiance_moments_waves_per_simd.
+hipError_t launch_radiance_moments(const DeviceScene& S, int integrator, bool simple, bool lean, int n, const void* rays, const uint32_t* jump,
+                                   unsigned long long seed, uint32_t firstStream, bool streamPad, int spp, int batchSpp, int maxDepth, int useMIS,
+                                   int blocks, void* out, void* sq, int32_t* spill, hipStream_t stream);
+// pt_query_guides.hip: n rays, lane i of tile t takes ray 64 t + i. maxLinks 0: the first-hit kernel (links, if set, gets zeros); else
+// the chain kernel. albedo[i] = (a, 1), normalDepth[i] = (n, summed path length), links[i] (NULL ok) the links followed; a miss: zeros.
+hipError_t launch_query_guides(const DeviceScene& S, int n, const void* rays, int maxLinks, int blocks, void* albedo, void* normalDepth, float* links,
+                               int32_t* spill, hipStream_t stream);
 
 }  // namespace pt

@@ -1322,6 +1322,49 @@ int pt_query_radiance_device(pt_scene* scene, int n, const void* d_rays /* n pt_
                              uint64_t seed, uint32_t first_stream, void* d_rgba_sum /* n float4 */, unsigned flags, void* stream);   /* async */
 int pt_query_radiance(pt_scene* scene, int n, const pt_ray* rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
                       uint32_t first_stream, float* out_rgba_sum /* n*4 */, unsigned flags);                                  /* host, blocking */
+/* pt_query_radiance_moments: pt_query_radiance that keeps each ray's variance: the sample sum S and the sum of squared
+ * batch sums Q per ray, pt_render_moments' pair, from one launch, so that pt_denoise_var can filter an image made of the caller's rays.
+ * Everything pt_query_radiance states holds unchanged: stream, sample, max_t on the first segment only, independence, what a call
+ *   touches, PT_QUERY_STREAM_PAD, the options "simple" and "lean", and the refusal of PT_QUERY_REORDER.
+ * Batches. The ray's spp samples are B = spp / batch_spp batches of c = batch_spp samples. With S_j the ray's f32 running sum after
+ *   j c samples (((0 + Li_0) + Li_1) + ..., S_0 = 0): out_rgba_sum[i] = (S_B, 0), pt_query_radiance's output bit for bit.
+ * Q. Per rgb channel Q_j = Q_(j-1) + d d with d = S_j - S_(j-1), Q_0 = 0, the product rounded before the sum, no contraction, no
+ *   special case for NaN or Inf: pt_render_moments' definition. out_sq_sum[i] = (Q_B, (float)B).
+ * The call writes both buffers; it does not add to them.
+ * Identity. With cam0's rays from pt_query_camera_rays_device(cam0, w, h, 999999), first_stream = 0 and flags = 0, both outputs equal
+ *   pt_render_moments(scene, cam0, w, h, spp, batch_spp, ...) bit for bit.
+ * Checked before any HIP call, -1 with a message under pt_query_radiance_moments: pt_query_radiance's checks in its order (n == 0
+ *   returns 0 before the scene or anything else is looked at); batch_spp < 1; spp not a multiple of batch_spp; spp / batch_spp < 2;
+ *   a NULL sq_sum. The device check comes last.
+ * d_rays (n pt_ray), d_rgba_sum and d_sq_sum (n float4 each) are device buffers aligned to 16 bytes; the device form is asynchronous
+ * on `stream`. */
+int pt_query_radiance_moments_device(pt_scene* scene, int n, const void* d_rays /* n pt_ray */, int spp, int batch_spp, int max_depth, int integrator,
+                                     int use_mis, uint64_t seed, uint32_t first_stream, void* d_rgba_sum /* n float4 */,
+                                     void* d_sq_sum /* n float4 */, unsigned flags, void* stream);                                 /* async */
+int pt_query_radiance_moments(pt_scene* scene, int n, const pt_ray* rays, int spp, int batch_spp, int max_depth, int integrator, int use_mis,
+                              uint64_t seed, uint32_t first_stream, float* out_rgba_sum /* n*4 */, float* out_sq_sum /* n*4 */,
+                              unsigned flags);                                                                                  /* host, blocking */
+/* pt_query_guides: the denoisers' guides for the caller's rays: what pt_render_aovs_centre gives for the centre ray of
+ * a pixel, for ray i = (o, d, max_t) as given. d is assumed to be unit length and is NOT normalised; pad is not read.
+ * The first segment's closest hit is accepted as pt_query_closest accepts it (t < max_t); every link after it uses 999999. The hit,
+ *   the link rule (mirrors and smooth dielectrics, deterministically, at most max_links links), the direction arithmetic and the
+ *   fallback (the first hit's record stands when the chain ends in a miss or at the cap) are pt_render_aovs_centre's.
+ * Output. albedo[i] = (a, 1), normal_depth[i] = (n, summed path length), links[i] (NULL: not written) = the number of links followed.
+ *   A ray that hits nothing below its max_t: eight zeros and links 0. The call writes; lanes past n store nothing.
+ * max_links 0 runs a first-hit kernel, 1..16 the chain kernel.
+ * Identity. On cam0's centre-ray records at max_t = 999999 the three outputs are pt_render_aovs_centre(scene, cam, w, h, max_links, ...)
+ *   bit for bit.
+ * What a call touches: the scene's feature spill area and, the host form, its query staging buffer. No RNG state, accumulator or
+ *   counter. After any pt_scene_update_* a call sees the edited scene.
+ * flags is reserved and must be 0.
+ * Checked before any HIP call, -1 with a message under pt_query_guides: n < 0 or n > 1 << 28; a NULL scene, rays, albedo or
+ *   normal_depth; max_links outside 0..16; any flag bit. Then n == 0 returns 0 and launches nothing. The device check comes last.
+ * d_rays (n pt_ray), d_albedo and d_normal_depth (n float4 each, aligned to 16 bytes) and d_links (n floats or NULL) are device
+ * buffers; the device form is asynchronous on `stream`. */
+int pt_query_guides_device(pt_scene* scene, int n, const void* d_rays /* n pt_ray */, int max_links, void* d_albedo /* n float4 */,
+                           void* d_normal_depth /* n float4 */, void* d_links /* n floats, NULL ok */, unsigned flags, void* stream);   /* async */
+int pt_query_guides(pt_scene* scene, int n, const pt_ray* rays, int max_links, float* out_albedo /* n*4 */, float* out_normal_depth /* n*4 */,
+                    float* out_links /* n, NULL ok */, unsigned flags);                                                         /* host, blocking */
 
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
