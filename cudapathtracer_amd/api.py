@@ -118,6 +118,7 @@ def _record_dtype(struct):
 
 
 RAY_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE = _record_dtype(Ray), _record_dtype(RayHit), _record_dtype(RaySurface)
+_F4 = (4, np.float32)                # Scene._query's output of four floats per ray
 QUERY_REORDER = 1                    # PT_QUERY_REORDER
 QUERY_STREAM_PAD = 2                 # PT_QUERY_STREAM_PAD
 QUERY_MAX_T = 999999.0               # the max_t of the library's own closest-hit rays
@@ -828,63 +829,51 @@ class Scene:
             raise PtError("%s: the rays are on %s but the current device is %d" % (what, rays.device, torch.cuda.current_device()))
         return True, rays, int(rays.shape[0])
 
+    def _query(self, name, rays, outs, args, empty=(False, False)):
+        """The form of every query_* method above query_camera_rays: pt_<name>_device on torch's current stream with data_ptr()s for
+        a torch tensor of rays, the host entry pt_<name> for numpy. outs: per output (columns, numpy dtype), or None for one the
+        caller left out: float32 tensors [n, columns] ([n] for 0 columns) on the rays' device, or numpy zeros of that shape (a
+        record dtype: [n] records). args(rays, outs) gives the C arguments between n and the stream from the pointers. empty:
+        whether the (torch, numpy) form makes the call at n == 0; an empty tensor has no data pointer to hand over and passes NULL.
+        Returns the outputs."""
+        is_torch, r, n = self._query_rays(name, rays)
+        if is_torch:
+            import torch
+            out = [o and torch.empty((n, o[0]) if o[0] else (n,), dtype=torch.float32, device=r.device) for o in outs]
+            ptr = lambda t: t.data_ptr() if t is not None and n else None
+            fn, tail = "pt_%s_device" % name, (torch.cuda.current_stream(r.device).cuda_stream or None,)
+        else:
+            out = [o and np.zeros((n, o[0]) if o[0] and not np.dtype(o[1]).names else n, o[1]) for o in outs]
+            ptr, fn, tail = _p, "pt_" + name, ()
+        if n or empty[0 if is_torch else 1]:
+            _check(getattr(lib(), fn)(self.h, n, *args(ptr(r), [ptr(o) for o in out]), *tail), fn)
+        return out
+
     def query_closest(self, rays, surfaces=False, reorder=False):
         """pt_query_closest: the closest hit of each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d is not normalised).
         numpy in: the host form, hits as a RAY_HIT_DTYPE array (t, u, v, tri; tri -1 for a miss) and, with surfaces, a
         RAY_SURFACE_DTYPE array. A torch tensor on the scene's device in: pt_query_closest_device on torch's current stream, no host
         copy, hits as an [n, 4] float32 tensor whose column 3 holds tri's bits (hits.view(torch.int32)[:, 3]) and surfaces as
         [n, 12] float32 (words 8..10 material, light, backface as int32 bits). Returns hits, or (hits, surfaces)."""
-        is_torch, r, n = self._query_rays("query_closest", rays)
         flags = QUERY_REORDER if reorder else 0
-        if is_torch:
-            import torch
-            hits = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            surf = torch.empty((n, 12), dtype=torch.float32, device=r.device) if surfaces else None
-            if n:        # (an empty tensor has no data pointer to hand over; the library launches nothing for n = 0 either)
-                _check(lib().pt_query_closest_device(self.h, n, r.data_ptr(), hits.data_ptr(), surf.data_ptr() if surfaces else None, flags,
-                                                     torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_closest_device")
-        else:
-            hits = np.zeros(n, RAY_HIT_DTYPE)
-            surf = np.zeros(n, RAY_SURFACE_DTYPE) if surfaces else None
-            if n:
-                _check(lib().pt_query_closest(self.h, n, _p(r), _p(hits), _p(surf), flags), "pt_query_closest")
+        hits, surf = self._query("query_closest", rays, [(4, RAY_HIT_DTYPE), (12, RAY_SURFACE_DTYPE) if surfaces else None],
+                                 lambda r, o: (r, o[0], o[1], flags))
         return (hits, surf) if surfaces else hits
 
     def query_shadow(self, rays, reorder=False):
         """pt_query_shadow: the shadow ray's throughput along each ray below its max_t, [n, 4] float32 (rgb, 0): zeros when occluded.
         numpy in, numpy out (host form); a torch tensor on the scene's device in, a torch tensor out, on torch's current stream."""
-        is_torch, r, n = self._query_rays("query_shadow", rays)
         flags = QUERY_REORDER if reorder else 0
-        if is_torch:
-            import torch
-            thr = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            if n:
-                _check(lib().pt_query_shadow_device(self.h, n, r.data_ptr(), thr.data_ptr(), flags,
-                                                    torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_shadow_device")
-        else:
-            thr = np.zeros((n, 4), np.float32)
-            if n:
-                _check(lib().pt_query_shadow(self.h, n, _p(r), _p(thr), flags), "pt_query_shadow")
-        return thr
+        return self._query("query_shadow", rays, [_F4], lambda r, o: (r, o[0], flags))[0]
 
     def query_radiance(self, rays, spp, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, first_stream=0, stream_pad=False):
         """pt_query_radiance: the path-traced light along each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be unit),
         summed over spp samples: [n, 4] float32 (rgb sums, 0). Ray i draws from stream first_stream + i of `seed`, or, with stream_pad,
         first_stream + its pad word (uint32). numpy in, numpy out (host form); a torch tensor on the scene's device in, a torch tensor
         out, on torch's current stream with no host copy. The centre rays of a camera without jitter and aperture give render()'s sums."""
-        is_torch, r, n = self._query_rays("query_radiance", rays)
         flags = QUERY_STREAM_PAD if stream_pad else 0
-        if is_torch:
-            import torch
-            out = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            _check(lib().pt_query_radiance_device(self.h, n, r.data_ptr() if n else None, spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream,
-                                                  out.data_ptr() if n else None, flags, torch.cuda.current_stream(r.device).cuda_stream or None),
-                   "pt_query_radiance_device")
-        else:
-            out = np.zeros((n, 4), np.float32)
-            _check(lib().pt_query_radiance(self.h, n, _p(r), spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, _p(out), flags),
-                   "pt_query_radiance")
-        return out
+        return self._query("query_radiance", rays, [_F4], lambda r, o: (r, spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, o[0], flags),
+                           empty=(True, True))[0]
 
     def query_radiance_moments(self, rays, spp, batch_spp, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, first_stream=0,
                                stream_pad=False):
@@ -893,21 +882,9 @@ class Scene:
         number of batches, as render_moments defines them. numpy in, numpy out (host form); a torch tensor on the scene's device in,
         tensors out, on torch's current stream with no host copy. denoise_var(S.reshape(h, w, 4), Q.reshape(h, w, 4), spp,
         spp // batch_spp, ...) reads the pair."""
-        is_torch, r, n = self._query_rays("query_radiance_moments", rays)
         flags = QUERY_STREAM_PAD if stream_pad else 0
-        if is_torch:
-            import torch
-            S = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            Q = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            _check(lib().pt_query_radiance_moments_device(self.h, n, r.data_ptr() if n else None, spp, batch_spp, max_depth, integrator, 1 if use_mis else 0,
-                                                          seed, first_stream, S.data_ptr() if n else None, Q.data_ptr() if n else None, flags,
-                                                          torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_radiance_moments_device")
-        else:
-            S = np.zeros((n, 4), np.float32)
-            Q = np.zeros((n, 4), np.float32)
-            _check(lib().pt_query_radiance_moments(self.h, n, _p(r), spp, batch_spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream,
-                                                   _p(S), _p(Q), flags), "pt_query_radiance_moments")
-        return S, Q
+        return tuple(self._query("query_radiance_moments", rays, [_F4, _F4], lambda r, o: (
+            r, spp, batch_spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, o[0], o[1], flags), empty=(True, True)))
 
     def query_guides(self, rays, max_links=0, links=False):
         """pt_query_guides: render_aovs_centre's guides for each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be
@@ -915,20 +892,8 @@ class Scene:
         surface behind at most max_links mirror and glass links, zeros for a ray that hits nothing below its max_t; links=True appends
         the link count [n] float32. numpy in, numpy out (host form); a torch tensor on the scene's device in, tensors out, on torch's
         current stream with no host copy."""
-        is_torch, r, n = self._query_rays("query_guides", rays)
-        if is_torch:
-            import torch
-            alb = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            nd = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-            ln = torch.empty((n,), dtype=torch.float32, device=r.device) if links else None
-            if n:
-                _check(lib().pt_query_guides_device(self.h, n, r.data_ptr(), max_links, alb.data_ptr(), nd.data_ptr(), ln.data_ptr() if links else None, 0,
-                                                    torch.cuda.current_stream(r.device).cuda_stream or None), "pt_query_guides_device")
-        else:
-            alb = np.zeros((n, 4), np.float32)
-            nd = np.zeros((n, 4), np.float32)
-            ln = np.zeros(n, np.float32) if links else None
-            _check(lib().pt_query_guides(self.h, n, _p(r), max_links, _p(alb), _p(nd), _p(ln) if links else None, 0), "pt_query_guides")
+        alb, nd, ln = self._query("query_guides", rays, [_F4, _F4, (0, np.float32) if links else None], lambda r, o: (r, max_links, o[0], o[1], o[2], 0),
+                                  empty=(False, True))
         return (alb, nd, ln) if links else (alb, nd)
 
     def query_camera_rays(self, camera, w, h, max_t=QUERY_MAX_T):

@@ -1,11 +1,12 @@
 // pt_feature.h — what the feature kernels are assembled from (pt_aov.hip: aov_kernel, aov_chain_kernel, aov_centre_kernel,
 // aov_centre_chain_kernel; pt_motion.hip: motion_kernel; pt_motion_chain.hip: motion_chain_kernel; pt_ids.hip: ids_kernel,
-// ids_chain_kernel; pt_query.hip's trace kernels, pt_query_guides.hip, pt_radiance.hip and pt_radiance_moments.hip use FeatureWave on 64
-// rays a tile). Every one of them is one wave per 8x8 tile (lane = ly*8+lx), four waves per workgroup, persistent over the
-// tiles, with the non-counting trace_closest (max_t 999999, as pt_probe_trace_closest) on an LDS stack that overflows into the
-// scene's spill area:
+// ids_chain_kernel) and the ray-query kernels (pt_query.hip's trace kernels, pt_query_guides.hip, and pt_radiance.h's walk for
+// pt_radiance.hip and pt_radiance_moments.hip: FeatureWave on 64 rays a tile). Every one of them is one wave per 8x8 tile
+// (lane = ly*8+lx), four waves per workgroup, persistent over the tiles, with the non-counting trace_closest (max_t 999999, as
+// pt_probe_trace_closest, or a caller's ray's own) on an LDS stack that overflows into the scene's spill area:
 //   FeatureWave, tile_pixel   the wave's traversal state and the pixel of a lane in a tile
-//   aov_stream                a XORWOW stream seeded in the kernel, into registers (the jittered aov kernels; pt_radiance.hip)
+//   load_ray                  a caller's ray record (pt_query.hip, pt_query_guides.hip)
+//   aov_stream                a XORWOW stream seeded in the kernel, into registers (the jittered aov kernels; pt_radiance.h)
 //   first_hit_record          a resolved hit's (albedo, 1) and (normal, t)
 //   follow_chain              a ray followed through mirrors and glass to the first non-specular surface; a kernel's ChainHook
 //                             sees every surface and link on the way
@@ -37,6 +38,13 @@ struct FeatureWave {
         C.nodes = nullptr; C.nNodes = 0; C.tris = nullptr; C.nTris = 0;
     }
 };
+
+// Ray `r` of a caller's buffer (pt_ray): (o, max_t), (d, pad).
+struct QueryRay { V3 o, d; float maxT; };
+PT_DEV QueryRay load_ray(const float4* __restrict__ rays, size_t r) {
+    const float4 a = rays[2 * r], b = rays[2 * r + 1];
+    return {v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), a.w};
+}
 
 // rng_init_kernel's per-lane body: stream `idx` of XORWOW(seed), via the 2^67-step jump matrices (row-image form).
 PT_DEV Rng aov_stream(const uint32_t* __restrict__ jump, unsigned long long seed, uint32_t idx) {

@@ -1,5 +1,6 @@
 // pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
-// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_query_guides.hip; their launchers and block counts: pt_feature_host.h.)
+// and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_query_guides.hip,
+// pt_radiance.hip, pt_radiance_moments.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -314,32 +315,21 @@ int pt_query_shadow_device(pt_scene* s, int n, const void* d_rays, void* d_throu
     return query_shadow(s, n, d_rays, d_throughput, flags, (hipStream_t)stream);
 }
 
-// The host forms: the rays go up into the head of the staging buffer, the outputs come down from behind them.
+// The host forms (here and below): pt_host.h's staged_query on the scene's queryOut, the rays at its head, the outputs behind them.
 int pt_query_closest(pt_scene* s, int n, const pt_ray* rays, pt_ray_hit* hits, pt_ray_surface* surfaces, uint32_t flags) {
     if (int r = check_query_args("pt_query_closest", s, n, rays, hits, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_closest", s)) return r;
-    const size_t rayBytes = (size_t)n * sizeof(pt_ray), hitBytes = (size_t)n * sizeof(pt_ray_hit), surfBytes = surfaces ? (size_t)n * sizeof(pt_ray_surface) : 0;
-    if (int r = s->feat.queryOut.ensure(rayBytes + hitBytes + surfBytes)) return r;
-    char* d = (char*)s->feat.queryOut.p;
-    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
-    if (int r = query_closest(s, n, d, d + rayBytes, surfaces ? d + rayBytes + hitBytes : nullptr, flags, nullptr)) return r;
-    HIP_OK(hipMemcpy(hits, d + rayBytes, hitBytes, hipMemcpyDeviceToHost));
-    if (surfaces) HIP_OK(hipMemcpy(surfaces, d + rayBytes + hitBytes, surfBytes, hipMemcpyDeviceToHost));
-    return 0;
+    return staged_query(s->feat.queryOut, n, rays, {{hits, (size_t)n * sizeof(pt_ray_hit)}, {surfaces, (size_t)n * sizeof(pt_ray_surface)}},
+                        [&](const void* dRays, void* const* d) { return query_closest(s, n, dRays, d[0], d[1], flags, nullptr); });
 }
 
 int pt_query_shadow(pt_scene* s, int n, const pt_ray* rays, float* throughput4, uint32_t flags) {
     if (int r = check_query_args("pt_query_shadow", s, n, rays, throughput4, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_shadow", s)) return r;
-    const size_t rayBytes = (size_t)n * sizeof(pt_ray), thrBytes = (size_t)n * sizeof(float4);
-    if (int r = s->feat.queryOut.ensure(rayBytes + thrBytes)) return r;
-    char* d = (char*)s->feat.queryOut.p;
-    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
-    if (int r = query_shadow(s, n, d, d + rayBytes, flags, nullptr)) return r;
-    HIP_OK(hipMemcpy(throughput4, d + rayBytes, thrBytes, hipMemcpyDeviceToHost));
-    return 0;
+    return staged_query(s->feat.queryOut, n, rays, {{throughput4, (size_t)n * sizeof(float4)}},
+                        [&](const void* dRays, void* const* d) { return query_shadow(s, n, dRays, d[0], flags, nullptr); });
 }
 
 // Radiance queries (pt_radiance.hip: radiance_kernel; pt_radiance_moments.hip: radiance_moments_kernel). Every message under the
@@ -362,16 +352,25 @@ static int check_radiance_args(const char* fn, pt_scene* s, int n, const void* r
 }
 
 // The scene's material class picks the instantiation as the render launch picks its bounce (pt_plan.hip: launch_plan): SIMPLE for a
-// scene that qualifies unless the "simple" option is 0, else LEAN likewise. No other option is read.
-static int query_radiance(pt_scene* s, int n, const void* dRays, int spp, int maxDepth, int integrator, int useMIS, uint64_t seed, uint32_t firstStream,
-                          void* dOut, uint32_t flags, hipStream_t stream) {
+// scene that qualifies unless the "simple" option is 0, else LEAN likewise. No other option is read. batchSpp 0 and dSq NULL:
+// radiance_kernel; else radiance_moments_kernel of the same class, at its own waves per SIMD.
+static int query_radiance(pt_scene* s, int n, const void* dRays, int spp, int batchSpp, int maxDepth, int integrator, int useMIS, uint64_t seed,
+                          uint32_t firstStream, void* dOut, void* dSq, uint32_t flags, hipStream_t stream) {
     const bool simple = s->facts.simpleOk && s->opt.simpleWanted;
     const bool lean = s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !simple;
-    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, radiance_waves_per_simd(integrator, simple, lean));
+    const bool moments = batchSpp != 0 || dSq;
+    const int waves = moments ? radiance_moments_waves_per_simd(integrator, simple, lean) : radiance_waves_per_simd(integrator, simple, lean);
+    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, waves);
     int32_t* spill;
     if (int r = feature_spill(s, blocks, &spill)) return r;
-    HIP_OK(launch_radiance(s->facts.ds, integrator, simple, lean, n, dRays, (const uint32_t*)s->data.jump.p, seed, firstStream,
-                           (flags & PT_QUERY_STREAM_PAD) != 0, spp, maxDepth, useMIS, blocks, dOut, spill, stream));
+    const uint32_t* jump = (const uint32_t*)s->data.jump.p;
+    const bool pad = (flags & PT_QUERY_STREAM_PAD) != 0;
+    if (moments)
+        HIP_OK(launch_radiance_moments(s->facts.ds, integrator, simple, lean, n, dRays, jump, seed, firstStream, pad, spp, batchSpp, maxDepth, useMIS,
+                                       blocks, dOut, dSq, spill, stream));
+    else
+        HIP_OK(launch_radiance(s->facts.ds, integrator, simple, lean, n, dRays, jump, seed, firstStream, pad, spp, maxDepth, useMIS, blocks, dOut, spill,
+                               stream));
     return 0;
 }
 
@@ -380,7 +379,7 @@ int pt_query_radiance_device(pt_scene* s, int n, const void* d_rays, int spp, in
     if (int r = check_radiance_args("pt_query_radiance", s, n, d_rays, d_rgba_sum, spp, integrator, first_stream, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_radiance", s)) return r;
-    return query_radiance(s, n, d_rays, spp, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, flags, (hipStream_t)stream);
+    return query_radiance(s, n, d_rays, spp, 0, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, nullptr, flags, (hipStream_t)stream);
 }
 
 int pt_query_radiance(pt_scene* s, int n, const pt_ray* rays, int spp, int max_depth, int integrator, int use_mis, uint64_t seed,
@@ -388,13 +387,9 @@ int pt_query_radiance(pt_scene* s, int n, const pt_ray* rays, int spp, int max_d
     if (int r = check_radiance_args("pt_query_radiance", s, n, rays, out_rgba_sum, spp, integrator, first_stream, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_radiance", s)) return r;
-    const size_t rayBytes = (size_t)n * sizeof(pt_ray), outBytes = (size_t)n * sizeof(float4);
-    if (int r = s->feat.queryOut.ensure(rayBytes + outBytes)) return r;
-    char* d = (char*)s->feat.queryOut.p;
-    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
-    if (int r = query_radiance(s, n, d, spp, max_depth, integrator, use_mis, seed, first_stream, d + rayBytes, flags, nullptr)) return r;
-    HIP_OK(hipMemcpy(out_rgba_sum, d + rayBytes, outBytes, hipMemcpyDeviceToHost));
-    return 0;
+    return staged_query(s->feat.queryOut, n, rays, {{out_rgba_sum, (size_t)n * sizeof(float4)}}, [&](const void* dRays, void* const* d) {
+        return query_radiance(s, n, dRays, spp, 0, max_depth, integrator, use_mis, seed, first_stream, d[0], nullptr, flags, nullptr);
+    });
 }
 
 // pt_query_radiance_moments: pt_query_radiance's checks in its order, then the batches' and the second output. (n == 0: the callers return.)
@@ -410,26 +405,13 @@ static int check_radiance_moments_args(pt_scene* s, int n, const void* rays, con
     return 0;
 }
 
-// query_radiance with radiance_moments_kernel: the same class, its own waves per SIMD.
-static int query_radiance_moments(pt_scene* s, int n, const void* dRays, int spp, int batchSpp, int maxDepth, int integrator, int useMIS, uint64_t seed,
-                                  uint32_t firstStream, void* dOut, void* dSq, uint32_t flags, hipStream_t stream) {
-    const bool simple = s->facts.simpleOk && s->opt.simpleWanted;
-    const bool lean = s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !simple;
-    const int blocks = feature_blocks((n + 63) / 64, s->dev.numCU, radiance_moments_waves_per_simd(integrator, simple, lean));
-    int32_t* spill;
-    if (int r = feature_spill(s, blocks, &spill)) return r;
-    HIP_OK(launch_radiance_moments(s->facts.ds, integrator, simple, lean, n, dRays, (const uint32_t*)s->data.jump.p, seed, firstStream,
-                                   (flags & PT_QUERY_STREAM_PAD) != 0, spp, batchSpp, maxDepth, useMIS, blocks, dOut, dSq, spill, stream));
-    return 0;
-}
-
 int pt_query_radiance_moments_device(pt_scene* s, int n, const void* d_rays, int spp, int batch_spp, int max_depth, int integrator, int use_mis,
                                      uint64_t seed, uint32_t first_stream, void* d_rgba_sum, void* d_sq_sum, unsigned flags, void* stream) {
     if (int r = check_radiance_moments_args(s, n, d_rays, d_rgba_sum, d_sq_sum, spp, batch_spp, integrator, first_stream, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_radiance_moments", s)) return r;
-    return query_radiance_moments(s, n, d_rays, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, d_sq_sum, flags,
-                                  (hipStream_t)stream);
+    return query_radiance(s, n, d_rays, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, d_sq_sum, flags,
+                          (hipStream_t)stream);
 }
 
 int pt_query_radiance_moments(pt_scene* s, int n, const pt_ray* rays, int spp, int batch_spp, int max_depth, int integrator, int use_mis, uint64_t seed,
@@ -437,16 +419,10 @@ int pt_query_radiance_moments(pt_scene* s, int n, const pt_ray* rays, int spp, i
     if (int r = check_radiance_moments_args(s, n, rays, out_rgba_sum, out_sq_sum, spp, batch_spp, integrator, first_stream, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_radiance_moments", s)) return r;
-    const size_t rayBytes = (size_t)n * sizeof(pt_ray), outBytes = (size_t)n * sizeof(float4);
-    if (int r = s->feat.queryOut.ensure(rayBytes + 2 * outBytes)) return r;
-    char* d = (char*)s->feat.queryOut.p;
-    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
-    if (int r = query_radiance_moments(s, n, d, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d + rayBytes, d + rayBytes + outBytes,
-                                       flags, nullptr))
-        return r;
-    HIP_OK(hipMemcpy(out_rgba_sum, d + rayBytes, outBytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(out_sq_sum, d + rayBytes + outBytes, outBytes, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t bytes = (size_t)n * sizeof(float4);
+    return staged_query(s->feat.queryOut, n, rays, {{out_rgba_sum, bytes}, {out_sq_sum, bytes}}, [&](const void* dRays, void* const* d) {
+        return query_radiance(s, n, dRays, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d[0], d[1], flags, nullptr);
+    });
 }
 
 // Guide queries (pt_query_guides.hip: query_guides_kernel, query_guides_chain_kernel). Every message under pt_query_guides, all
@@ -482,15 +458,9 @@ int pt_query_guides(pt_scene* s, int n, const pt_ray* rays, int max_links, float
     if (int r = check_guides_args(s, n, rays, max_links, out_albedo, out_normal_depth, flags)) return r;
     if (n == 0) return 0;
     if (int r = check_query_device("pt_query_guides", s)) return r;
-    const size_t rayBytes = (size_t)n * sizeof(pt_ray), recBytes = (size_t)n * sizeof(float4), linkBytes = out_links ? (size_t)n * sizeof(float) : 0;
-    if (int r = s->feat.queryOut.ensure(rayBytes + 2 * recBytes + linkBytes)) return r;
-    char* d = (char*)s->feat.queryOut.p;
-    HIP_OK(hipMemcpy(d, rays, rayBytes, hipMemcpyHostToDevice));
-    if (int r = query_guides(s, n, d, max_links, d + rayBytes, d + rayBytes + recBytes, out_links ? d + rayBytes + 2 * recBytes : nullptr, nullptr)) return r;
-    HIP_OK(hipMemcpy(out_albedo, d + rayBytes, recBytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(out_normal_depth, d + rayBytes + recBytes, recBytes, hipMemcpyDeviceToHost));
-    if (out_links) HIP_OK(hipMemcpy(out_links, d + rayBytes + 2 * recBytes, linkBytes, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t bytes = (size_t)n * sizeof(float4);
+    return staged_query(s->feat.queryOut, n, rays, {{out_albedo, bytes}, {out_normal_depth, bytes}, {out_links, (size_t)n * sizeof(float)}},
+                        [&](const void* dRays, void* const* d) { return query_guides(s, n, dRays, max_links, d[0], d[1], d[2], nullptr); });
 }
 
 int pt_query_camera_rays_device(const pt_camera* cam, int w, int h, float max_t, void* d_rays, void* stream) {

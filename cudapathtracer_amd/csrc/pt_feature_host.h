@@ -1,6 +1,7 @@
 // pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip) and of the ray
-// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip): the tiling and block count every one of them is launched with, each kernel's waves per SIMD, and the launchers
-// pt_feature_api.hip calls. The kernels' shared pieces are in pt_feature.h.
+// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip): the tiling and block count every one of them is
+// launched with, each kernel's waves per SIMD, and the launchers pt_feature_api.hip calls. The kernels' shared pieces are in
+// pt_feature.h, the radiance kernels' walk in pt_radiance.h.
 #pragma once
 #include <algorithm>
 #include "pt_params.h"
@@ -41,8 +42,8 @@ constexpr int radiance_waves_per_simd(int integrator, bool simple, bool lean) { 
 // neighbours. With the batch bookkeeping in LDS (7 KB more per workgroup), VGPRs / scratch bytes per lane, and with
 // it in registers:
 //   naive, SIMPLE    6: 80 / 0     (registers: 80 / 16)                 MIS, SIMPLE    6: 80 / 36    (registers: 80 / 64)
-//   naive, LEAN      5: 96 / 0     (registers: 96 / 20)                 MIS, LEAN      5: 96 / 88    (registers: 96 / 112)
-//   naive, generic   4: 99 / 0     (registers: 103 / 0)                 MIS, generic   4: 128 / 12   (registers: 128 / 28)
+//   naive, LEAN      5: 95 / 0     (registers: 96 / 20)                 MIS, LEAN      5: 96 / 88    (registers: 96 / 112)
+//   naive, generic   4: 97 / 0     (registers: 103 / 0)                 MIS, generic   4: 128 / 12   (registers: 128 / 28)
 // LDS: 23 KB in the SIMPLE kernels (6 workgroups: 138 KB), 27 KB in the others (5: 135 KB).
 constexpr int radiance_moments_waves_per_simd(int integrator, bool simple, bool lean) { return simple ? 6 : lean ? 5 : 4; }
 constexpr int kQueryGuidesWavesPerSimd = 8;       // query_guides_kernel: 55 VGPRs, 8 x 16 KB of LDS, as the centre pass

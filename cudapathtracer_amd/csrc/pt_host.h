@@ -117,4 +117,22 @@ static int staged_download(DevBuf& staging, const StagedOut (&out)[N], Render re
     return 0;
 }
 
+// A ray query's host form: the n rays go up into the head of `staging`, run(dRays, d) works there, d[i] being output i's slice
+// behind them (NULL for an output the caller left out, which gets no slice), then the copies to the host in order.
+template <int N, class Run>
+static int staged_query(DevBuf& staging, int n, const pt_ray* rays, const StagedOut (&out)[N], Run run) {
+    const size_t rayBytes = (size_t)n * sizeof(pt_ray);
+    size_t total = rayBytes;
+    for (const StagedOut& o : out) total += o.host ? o.bytes : 0;
+    if (int r = staging.ensure(total)) return r;
+    HIP_OK(hipMemcpy(staging.p, rays, rayBytes, hipMemcpyHostToDevice));
+    void* d[N];
+    char* at = (char*)staging.p + rayBytes;
+    for (int i = 0; i < N; i++) { d[i] = out[i].host ? at : nullptr; at += out[i].host ? out[i].bytes : 0; }
+    if (int r = run(staging.p, d)) return r;
+    for (int i = 0; i < N; i++)
+        if (out[i].host) HIP_OK(hipMemcpy(out[i].host, d[i], out[i].bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // namespace pt

@@ -17,13 +17,6 @@
 
 namespace pt {
 
-// Ray `r` of the buffer: (o, max_t), (d, pad).
-struct QueryRay { V3 o, d; float maxT; };
-PT_DEV QueryRay load_ray(const float4* __restrict__ rays, uint32_t r) {
-    const float4 a = rays[2 * (size_t)r], b = rays[2 * (size_t)r + 1];
-    return {v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), a.w};
-}
-
 // The ray of `lane` in tile `tile`: entry i of the order (perm NULL: i itself), or none past n.
 PT_DEV bool query_index(const uint32_t* __restrict__ perm, int n, int tile, int lane, uint32_t& r) {
     const int i = tile * 64 + lane;

@@ -20,12 +20,11 @@ __global__ void __launch_bounds__(256) query_guides_kernel(DeviceScene S, const 
     for (int tile = W.gw; tile < nTiles; tile += gridDim.x * 4) {
         const int i = tile * 64 + W.lane;
         if (i >= n) continue;
-        const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
-        const V3 o = v3(a.x, a.y, a.z), d = v3(b.x, b.y, b.z);
+        const QueryRay q = load_ray(rays, (size_t)i);
         Hit hit;
-        trace_closest<false, kStackLds>(S, W.C, o, d, a.w, W.st, hit, W.c);
+        trace_closest<false, kStackLds>(S, W.C, q.o, q.d, q.maxT, W.st, hit, W.c);
         float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;     // a miss: eight zeros
-        if (hit.tri >= 0) { HitInfo hi; resolve_hit(S, hit, o, d, hi); first_hit_record(S, hi, hit.t, oa, on); }
+        if (hit.tri >= 0) { HitInfo hi; resolve_hit(S, hit, q.o, q.d, hi); first_hit_record(S, hi, hit.t, oa, on); }
         albedo[i] = oa;
         normalDepth[i] = on;
         if (linksOut) linksOut[i] = 0.0f;
@@ -42,13 +41,9 @@ __global__ void __launch_bounds__(256) query_guides_chain_kernel(DeviceScene S, 
     for (int tile = W.gw; tile < nTiles; tile += gridDim.x * 4) {
         const int i = tile * 64 + W.lane;
         const bool live = i < n;
-        V3 o = v3(0.0f), d = v3(0.0f);
-        float maxT = 0.0f;
-        if (live) {
-            const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
-            o = v3(a.x, a.y, a.z); d = v3(b.x, b.y, b.z); maxT = a.w;
-        }
-        const int links = follow_chain(S, W.C, W.st, W.c, o, d, live, maxLinks, rec, ChainHook(), maxT);
+        QueryRay q = {v3(0.0f), v3(0.0f), 0.0f};
+        if (live) q = load_ray(rays, (size_t)i);
+        const int links = follow_chain(S, W.C, W.st, W.c, q.o, q.d, live, maxLinks, rec, ChainHook(), q.maxT);
         if (!live) continue;
         float4 oa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), on = oa;
         float ol = 0.0f;
