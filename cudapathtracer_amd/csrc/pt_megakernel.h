@@ -429,7 +429,8 @@ PT_DEV void megakernel_body(const KParams& P, const MomentsK& M = MomentsK{nullp
 #endif
         if (__ballot(hasExt || hasShadow) == 0ull) break;
         if constexpr (DEFER && FLAT) {
-            trace_pair_flat<STACKN, ARMS>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves);
+            trace_pair_flat<STACKN, ARMS>(S, SC, st, hasShadow, ps.so, ps.sd, ps.smaxt, LTRI ? (ps.flags & kLightTriMask) >> kLightTriShift : 0u, hasExt, ps.o, ps.d, thr, h, c, P.cacheNodes, P.leaves, P.nLeaves,
+                                          ARMS ? P.pad1 : nullptr, ARMS ? P.pad0 : 0);      // (ARMS: the box table, pt_params.h)
         }
         else if constexpr (FLAT) {
             trace_closest_flat<STACKN, FLATW>(S, SC, hasExt, ps.o, ps.d, 999999.0f, st, h, c, P.cacheNodes, P.leaves, P.nLeaves);

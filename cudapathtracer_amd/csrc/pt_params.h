@@ -71,6 +71,9 @@ constexpr int kCacheBytesHbmSimple = ((160 * 1024) / kWgPerCuHbmSimple - kWgWave
 // The pad* members hold the places of the parameters of retired variants (wide / compact trees, speculative descent,
 // XCD bands), same types, same offsets. Like MomentsK below: the hidden kernel arguments follow the explicit ones, so a KParams that
 // shrank would move them and change the code of every kernel. The asserts after the struct pin its size and three live offsets.
+// pad0 / pad1 carry the timed pair kernels' box table (pt_box_table.h: PBox records and their group headers, read by trace_pair_flat
+// under ARMS only): pad0 = records | groups << 8 | grouped axis << 16 (at most 64 of either; 0: no table), pad1 its address. No other
+// kernel reads them.
 struct KParams {
     DeviceScene S;
     CamK cam;

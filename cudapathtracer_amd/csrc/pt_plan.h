@@ -35,6 +35,8 @@ struct Facts {
     DeviceScene ds{};
     int stackNeed = 0, nInternal = 0, cacheNodes = 0, cacheTris = 0, nTrisPacked = 0, nMats = 0, nLightsPacked = 0;
     int nLeaves = 0;                      // FLAT scenes: the leaf table (pt_trace.h: visited(leaf) == slab(leaf's own box))
+    int nBoxes = 0, nBoxGroups = 0, boxAxis = 0;   // ... and the timed pair kernels' table of its distinct boxes, behind it in the same buffer: records, groups of
+                                          // records that share their interval on boxAxis, and that axis (pt_box_table.h); nBoxes 0: none
     unsigned long long lightTri8 = 0ull;  // a byte per light, for the first 8: 1 + the packed triangle the light is, 0 = none (light_triangles); KParams::lightTri8
     bool armless = false;        // a triangle uses a material type without a dispatch arm (pt_path.h): DEFER is not exact
     bool noLeafTris = false;     // no triangle carries a MAT_LEAF material: a shadow ray is occluded by any hit (order-free)

@@ -95,6 +95,7 @@ LaunchSizes size_launch(const Facts& F, const Options& O, int numCU, const Launc
     if (onchip) { P.cacheNodes = F.nInternal; P.cacheTris = F.nTrisPacked; }      // the whole scene, in workgroups large enough to hold it
     if (onchip && kAttrCacheBytes > 0) { P.cacheAttrs = F.nTrisPacked; P.cacheMats = F.nMats; P.cacheLights = F.nLightsPacked; }   // the bounce's records in LDS as well
     if (onchip && kAttrCacheBytes > 0 && F.flatOk && O.leafBoxes && F.nLeaves > 0) P.nLeaves = F.nLeaves;       // (the caller points P.leaves at the table)
+    if (P.nLeaves > 0 && plan.flat == 3) P.pad0 = F.nBoxes | (F.nBoxGroups << 8) | (F.boxAxis << 16);      // the pair kernels' box table (pt_params.h; the caller points P.pad1 at it)
     // (a scene in HBM has no FLAT form, so its kernel has the SIMPLE bounce exactly when it is the SIMPLE production kernel)
     if (plan.hbm && F.cacheTris == 0) P.cacheNodes = std::min(F.nInternal, (plan.simple ? kCacheBytesHbmSimple : kCacheBytesHbm) / 64);     // its workgroups share a larger copy of the top of the tree
     P.gnodeFrom = P.cacheNodes;

@@ -156,6 +156,7 @@ static int render_tiles(pt_scene* s, RenderRequest& rq) {
     P.cam = cam_to_kernel(*rq.cam);
     P.w = rq.w; P.h = rq.h; P.spp = rq.spp; P.maxDepth = rq.maxDepth;
     if (P.nLeaves > 0) P.leaves = (const PLeaf*)s->geo.leaves.p;
+    if (P.pad0 > 0) P.pad1 = P.leaves + s->facts.nLeaves;       // the box table follows the leaf table (pt_scene.hip: derive_layout)
     P.rng = (uint32_t*)s->work.rng.p; P.out = (float4*)rq.d_tiles; P.pixCounters = rq.d_pixcnt;
     P.totals = rq.count ? (unsigned long long*)s->data.totals.p : nullptr;
 #ifdef PT_STAMPS

@@ -5,6 +5,7 @@
 
 #include "pt_host.h"
 #include "pt_bvh_build.h"
+#include "pt_box_table.h"
 #include "xorwow_host.h"
 
 using namespace pt;
@@ -23,30 +24,6 @@ static int upload(DevBuf& b, const void* src, size_t bytes) {
     if (int r = b.ensure(std::max<size_t>(bytes, 16))) return r;
     if (bytes) HIP_OK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
     return 0;
-}
-
-// The leaf table of the FLAT kernels replaces the reference's root-to-leaf box walk by a test of each leaf's OWN box.
-// That equals the reference's visiting set only if every box contains the boxes
-// below it and no box holds a NaN or an infinity (pt_trace.h: inv_is_regular and the monotonicity argument above it). The
-// reference's builder nests exactly (a parent's box is the float-wise min / max of its children's, main.cu:20-233), but
-// pt_scene_create also takes a caller's own BVH arrays — a refit, loose or corrupt tree must fall back to the walk that
-// tests the boxes the caller gave. pn: packed internal nodes, children numbered after their parents.
-static bool boxes_nested_and_finite(const std::vector<PNode>& pn, int nInternal) {
-    for (int i = 0; i < nInternal; i++) {
-        const PNode& p = pn[i];
-        for (int a = 0; a < 3; a++)
-            if (!(std::isfinite(p.lmin[a]) && std::isfinite(p.lmax[a]) && std::isfinite(p.rmin[a]) && std::isfinite(p.rmax[a]))) return false;
-        const int32_t ref[2] = {p.left, p.right};
-        for (int k = 0; k < 2; k++) {
-            if (ref[k] < 0) continue;                              // a leaf child: its box IS the one the table tests
-            if (ref[k] <= i || ref[k] >= nInternal) return false;
-            const PNode& c = pn[ref[k]];
-            const float* mn = k == 0 ? p.lmin : p.rmin; const float* mx = k == 0 ? p.lmax : p.rmax;
-            for (int a = 0; a < 3; a++)
-                if (!(mn[a] <= c.lmin[a] && mn[a] <= c.rmin[a] && mx[a] >= c.lmax[a] && mx[a] >= c.rmax[a])) return false;
-        }
-    }
-    return true;
 }
 
 // For each light: the packed triangle (position in leaf order, the FLAT kernels' numbering) it was made from, or -1. The pair pass
@@ -226,28 +203,23 @@ static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef,
         if (ok && nInternal > 0) ok = first[0] == 0 && pn[0].pad0 + pn[0].pad1 == nT;
         if (ok && nInternal > 0) HIP_OK(hipMemcpy(s->geo.nodes.p, pn.data(), (size_t)nInternal * sizeof(PNode), hipMemcpyHostToDevice));
         s->facts.flatOk = ok;
-        s->facts.nLeaves = 0;
+        s->facts.nLeaves = 0; s->facts.nBoxes = 0; s->facts.nBoxGroups = 0; s->facts.boxAxis = 0;
         if (ok && nLights > 0 && haveLights) {
             // the table travels as a kernel argument, a byte per light: the first 8 lights (a scene of at most 64 triangles rarely has
             // more; a light beyond them is simply tested like any other triangle)
             light_triangles(pt.data(), nT, hostLights, nLights, nLightInd, [&](int idx) { return lightIndOf[idx]; }, lightTri.data());
             for (int i = 0; i < nLights && i < 8; i++) s->facts.lightTri8 |= (uint64_t)(lightTri[i] + 1) << (8 * i);
         }
-        if (ok && nInternal > 0 && boxes_nested_and_finite(pn, nInternal)) {     // the leaf table: every leaf child's box and triangle range
-            std::vector<PLeaf> lf;
-            for (int i = 0; i < nInternal; i++) {
-                const int32_t* ref = &pn[i].left;
-                for (int k = 0; k < 2; k++) {
-                    if (ref[k] >= 0) continue;
-                    PLeaf L;
-                    const float* mn = k == 0 ? pn[i].lmin : pn[i].rmin; const float* mx = k == 0 ? pn[i].lmax : pn[i].rmax;
-                    for (int a = 0; a < 3; a++) { L.mn[a] = mn[a]; L.mx[a] = mx[a]; }
-                    L.first = ~ref[k]; L.count = ref[2 + k];
-                    lf.push_back(L);
-                }
-            }
+        if (ok && nInternal > 0 && boxes_nested_and_finite(pn, nInternal)) {     // the leaf table, and behind it in the same buffer the pair kernels' box table (pt_box_table.h)
+            std::vector<PLeaf> lf = build_leaf_table(pn, nInternal);
+            std::vector<PBox> bx = build_box_table(lf, nT);
+            const int nBoxes = (int)bx.size();
+            const BoxGroups G = group_box_table(bx);              // (sorted by group, the group headers behind the records)
+            const size_t nLeaves = lf.size();
+            lf.resize(nLeaves + bx.size());
+            if (!bx.empty()) memcpy((void*)(lf.data() + nLeaves), bx.data(), bx.size() * sizeof(PBox));
             if (int r = upload(s->geo.leaves, lf.data(), lf.size() * sizeof(PLeaf))) return r;
-            s->facts.nLeaves = (int)lf.size();
+            s->facts.nLeaves = (int)nLeaves; s->facts.nBoxes = nBoxes; s->facts.nBoxGroups = G.nGroups; s->facts.boxAxis = G.axis;
         }
     }
     return 0;

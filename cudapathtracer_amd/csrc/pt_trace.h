@@ -266,6 +266,22 @@ PT_DEV LeafBox leaf_box(const PLeaf* __restrict__ leaves, int k) {
     L.first = ((konst_i*)p)[6]; L.count = ((konst_i*)p)[7];
     return L;
 }
+// A record of the timed pair kernels' box table (pt_box_table.h: one per distinct leaf box, with the triangle mask of every leaf
+// that carries it, the floats rotated so that the grouped axis comes first; a group's header has the same 32 bytes), read the same
+// way: eight dwords in SGPRs, the last two the mask itself instead of (first, count). Read as ONE vector, so that it is one
+// s_load_dwordx8 whichever fields the caller uses (the table starts on a 32-byte boundary).
+struct PairBox { float mng, mnu, mnv, mxg, mxu, mxv; uint64_t mask; };
+PT_DEV PairBox pair_box(const void* __restrict__ boxes, int k) {
+    typedef uint32_t u8v __attribute__((ext_vector_type(8)));
+    typedef __attribute__((address_space(4))) const u8v konst_rec;
+    const u8v r = *((konst_rec*)(uintptr_t)boxes + k);
+    const uint32_t w0 = r[0], w1 = r[1], w2 = r[2], w3 = r[3], w4 = r[4], w5 = r[5];      // (scalars first: a bit cast straight from a vector's element reads element 0)
+    PairBox B;
+    B.mng = __builtin_bit_cast(float, w0); B.mnu = __builtin_bit_cast(float, w1); B.mnv = __builtin_bit_cast(float, w2);
+    B.mxg = __builtin_bit_cast(float, w3); B.mxu = __builtin_bit_cast(float, w4); B.mxv = __builtin_bit_cast(float, w5);
+    B.mask = (uint64_t)r[6] | ((uint64_t)r[7] << 32);
+    return B;
+}
 
 // ---- leaving a loop before its last lane -------------------------------------------------------
 // A wave walks `while (cur >= 0) descend` until its LAST lane has reached a leaf, then the triangle loop until
@@ -773,7 +789,8 @@ PT_DEV void trace_closest_flat(const DeviceScene& S, const SceneCache& C, bool a
 // record's address and the first minimum's. The prefixes (at most 192 words) still live in the minima's 512.
 template <int N, bool ARMS = false>
 PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>& st, bool hasShadow, V3 so, V3 sd, float smaxt, uint32_t ltri1,
-                            bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0) {
+                            bool hasExt, V3 eo, V3 ed, V3& thr, Hit& hit, Ctr& c, int nInternal, const PLeaf* __restrict__ leaves = nullptr, int nLeaves = 0,
+                            const void* __restrict__ boxes = nullptr, int nBoxes = 0) {
     static_assert(N >= 24, "the scratch layout needs 24 x 64 words of the wave's stack area");
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     const int lane = (int)(threadIdx.x & 63u);
@@ -791,7 +808,49 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
     // 1. one lockstep node walk for both rays
     uint64_t tmE = 0ull, tmS = 0ull;
     if (S.rootRef < 0) { const uint64_t all = ~0ull >> (64 - S.nTris); tmE = hasExt ? all : 0ull; tmS = hasShadow ? all : 0ull; }
-    else if (nLeaves > 0 && __builtin_amdgcn_ballot_w64((hasExt && !inv_is_regular(invE)) || (hasShadow && !inv_is_regular(invS))) == 0ull) {
+    else if ((ARMS ? nBoxes : nLeaves) > 0 && __builtin_amdgcn_ballot_w64((hasExt && !inv_is_regular(invE)) || (hasShadow && !inv_is_regular(invS))) == 0ull) {
+        if constexpr (ARMS) {
+            // The distinct boxes of the leaves, both rays (pt_box_table.h). Leaves with bit-equal boxes pass or fail slab_hit together —
+            // it reads nothing else of a leaf — so one test per distinct box with the OR of their triangle ranges sets the same bits
+            // of tmE / tmS as one test per leaf; and the mask arrives with the record, where the loop over the leaves rebuilt it from
+            // (first, count) with three 64-bit scalar shifts in every pass.
+            // The records come in groups that share their interval [lo, hi] on one axis g of the scene (wave-uniform, chosen by the
+            // host), and a group's loop reuses that axis' part of slab_hit: t1 = (lo - o.g) * inv.g, t2 = (hi - o.g) * inv.g,
+            // max(FLT_TRUE_MIN, min(t1, t2)) and min(1e30, max(t1, t2)) are the same operations on the same operands for every box
+            // of the group, computed once; the box's own two axes are folded onto them. Against slab_hit only the ORDER in which the
+            // three axes' minima enter the running max (and the maxima the running min) changes — g first instead of x, y, z — and
+            // the result does not depend on it: behind the inv_is_regular gate a lane that has the ray has finite non-zero inv, the
+            // boxes are finite (boxes_nested_and_finite), so (m - o) * inv is a NaN only where o is one, and v_min / v_max return
+            // their other operand for a NaN in either place: the running max is the largest non-NaN value among FLT_TRUE_MIN and the
+            // three minima, whatever the order, and likewise the running min. (Two zeros of different sign may leave either sign
+            // behind; tmn >= FLT_TRUE_MIN is never a zero, and `tmx >= tmn` does not read tmx's sign.) A lane without the ray
+            // computes on what inv3_uniform left and is cleared by the select behind the loop, as before.
+            const int nB = nBoxes & 255, nG = (nBoxes >> 8) & 255, axis = nBoxes >> 16;
+            auto rot = [&](V3 a) { return axis == 0 ? a : (axis == 1 ? v3(a.y, a.z, a.x) : v3(a.z, a.x, a.y)); };      // (g, u, v), as the records' floats
+            const V3 oE = rot(eo), iE = rot(invE), oS = rot(so), iS = rot(invS);
+            auto uv_hit = [](float gmn, float gmx, const PairBox& B, V3 o, V3 inv) {
+                const float tu1 = (B.mnu - o.y) * inv.y, tu2 = (B.mxu - o.y) * inv.y;
+                float tmn = fmaxf_(gmn, fminf_(tu1, tu2)), tmx = fminf_(gmx, fmaxf_(tu1, tu2));
+                const float tv1 = (B.mnv - o.z) * inv.z, tv2 = (B.mxv - o.z) * inv.z;
+                tmn = fmaxf_(tmn, fminf_(tv1, tv2)); tmx = fminf_(tmx, fmaxf_(tv1, tv2));
+                return tmx >= tmn;
+            };
+            int k = 0;
+            for (int g = 0; g < nG; ++g) {                        // wave-uniform loops, the records through the scalar cache: SGPR operands
+                const PairBox H = pair_box(boxes, nB + g);        // the group's header: lo, hi, its number of records
+                const float e1 = (H.mng - oE.x) * iE.x, e2 = (H.mxg - oE.x) * iE.x;
+                const float gmnE = fmaxf_(1.401298464e-45f, fminf_(e1, e2)), gmxE = fminf_(1e30f, fmaxf_(e1, e2));
+                const float s1 = (H.mng - oS.x) * iS.x, s2 = (H.mxg - oS.x) * iS.x;
+                const float gmnS = fmaxf_(1.401298464e-45f, fminf_(s1, s2)), gmxS = fminf_(1e30f, fmaxf_(s1, s2));
+                const int end = k + (int)(uint32_t)H.mask;
+                do {                                              // (a group holds at least one record)
+                    const PairBox B = pair_box(boxes, k);
+                    const bool eH = uv_hit(gmnE, gmxE, B, oE, iE);
+                    const bool sH = uv_hit(gmnS, gmxS, B, oS, iS);
+                    tmE |= eH ? B.mask : 0ull; tmS |= sH ? B.mask : 0ull;
+                } while (++k < end);
+            }
+        } else {
         _Pragma("unroll 2")
         for (int k = 0; k < nLeaves; ++k) {                       // the leaves' own boxes, both rays (see inv_is_regular)
             const LeafBox L = leaf_box(leaves, k);                // through the scalar cache: SGPR operands of the slab tests
@@ -799,6 +858,7 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
             const bool sH = slab_hit(L.mnx, L.mny, L.mnz, L.mxx, L.mxy, L.mxz, so, invS);
             const uint64_t m = ((1ull << (uint32_t)L.count) - 1ull) << (uint32_t)L.first;      // s_bfm_b64 (a leaf of a tree with two or more leaves holds < 64 triangles)
             tmE |= eH ? m : 0ull; tmS |= sH ? m : 0ull;
+        }
         }
         tmE = hasExt ? tmE : 0ull; tmS = hasShadow ? tmS : 0ull;     // (once, not per leaf)
     } else {
