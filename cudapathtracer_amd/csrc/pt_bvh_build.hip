@@ -44,6 +44,7 @@
 
 #include "../../include/pt_api.h"
 #include "pt_device.h"
+#include "pt_pack.h"
 #include "pt_bvh_build.h"
 
 extern "C" int pt_fail_(int code, const char* msg);
@@ -99,9 +100,22 @@ __device__ inline unsigned wave_max(unsigned v) {
     for (int o = 32; o; o >>= 1) v = umax_(v, (unsigned)__shfl_xor((int)v, o));
     return v;
 }
+__device__ inline unsigned wmin_if(bool c, unsigned v) { return wave_min(c ? v : 0xffffffffu); }
+__device__ inline unsigned wmax_if(bool c, unsigned v) { return wave_max(c ? v : 0u); }
 __device__ inline int lane_id() { return (int)(threadIdx.x & 63); }
 __device__ inline float comp3(const float* cx, const float* cy, const float* cz, int axis, int id) {
     return axis == 0 ? cx[id] : (axis == 1 ? cy[id] : cz[id]);
+}
+__device__ inline void box_keys(const float4& l, const float4& h, unsigned kl[3], unsigned kh[3]) {
+    kl[0] = fkey(l.x); kl[1] = fkey(l.y); kl[2] = fkey(l.z); kh[0] = fkey(h.x); kh[1] = fkey(h.y); kh[2] = fkey(h.z);
+}
+// The split axis of a node with these extents, main.cu:161-168, and the bucket of centroid c on an axis that starts at a0 and is
+// ext long, main.cu:76-85.
+__device__ inline int split_axis(float dx, float dy, float dz) { return (dy > dx && dy > dz) ? 1 : ((dz > dx && dz > dy) ? 2 : 0); }
+__device__ inline int bucket_of(float c, float a0, float ext) {
+    const float q = NB * (c - a0) / ext;
+    const int b = (q == q && fabsf(q) < 1e9f) ? (int)q : 0;       // int(NaN/inf) is UB in the reference; defined 0
+    return b < 0 ? 0 : (b > NB - 1 ? NB - 1 : b);
 }
 
 struct Arrays {
@@ -131,6 +145,7 @@ template <int S> struct StageMem { unsigned lo[S * 3], hi[S * 3]; int cnt[S]; in
 template <int S> __device__ inline void stage_reset(StageMem<S>& m) {
     for (int t = threadIdx.x; t < S * 3; t += blockDim.x) { m.lo[t] = 0xffffffffu; m.hi[t] = 0u; }
     for (int t = threadIdx.x; t < S; t += blockDim.x) m.cnt[t] = 0;
+    __syncthreads();
 }
 template <int S, class Dest> __device__ inline void stage_flush(StageMem<S>& m, int cur, const Dest& dest) {
     __syncthreads();
@@ -150,6 +165,27 @@ template <int S, class Dest> __device__ inline void stage_flush(StageMem<S>& m, 
     }
     __syncthreads();
 }
+// The lanes with `sel`, all of one node, add (kl, kh) to their slots: slot by slot, the box reduced over the slot's lanes and
+// committed once, by the slot's first lane, through commit(slot, lo[3], hi[3], lanes).
+template <class Commit>
+__device__ inline void reduce_slots(bool sel, int slot, const unsigned kl[3], const unsigned kh[3], const Commit& commit) {
+    unsigned long long rem = __ballot(sel);
+    while (rem) {
+        int l = __ffsll((unsigned long long)rem) - 1;
+        int s0 = __shfl(slot, l);
+        bool ss = sel && slot == s0;
+        unsigned long long sm = __ballot(ss);
+        unsigned r[6];
+        for (int k = 0; k < 3; k++) { r[k] = wmin_if(ss, kl[k]); r[3 + k] = wmax_if(ss, kh[k]); }
+        if (lane_id() == l) commit(s0, r, r + 3, (int)__popcll(sm));
+        rem &= ~sm;
+    }
+}
+template <class Dest> __device__ inline void dest_add(const Dest& dest, int node, int slot, const unsigned lo[3], const unsigned hi[3], int count) {
+    for (int k = 0; k < 3; k++) { atomicMin(dest.lo(node, slot) + k, lo[k]); atomicMax(dest.hi(node, slot) + k, hi[k]); }
+    int* c = dest.cnt(node, slot);
+    if (c) atomicAdd(c, count);
+}
 // One tile of the workgroup's chunk: lanes with `pend` add (kl, kh) to slot `slot` of node `node`.
 // Must be called by every thread of the workgroup. `cur` is the node currently held in LDS.
 template <int S, class Dest>
@@ -163,20 +199,10 @@ __device__ inline void stage_add(StageMem<S>& m, int& cur, bool pend, int node, 
         if (cand == INT_MAX) break;
         if (cand != cur) { stage_flush(m, cur, dest); cur = cand; }
         const bool sel = pend && node == cand;
-        unsigned long long rem = __ballot(sel);
-        while (rem) {
-            int l = __ffsll((unsigned long long)rem) - 1;
-            int s0 = __shfl(slot, l);
-            bool ss = sel && slot == s0;
-            unsigned long long sm = __ballot(ss);
-            unsigned r[6];
-            for (int k = 0; k < 3; k++) { r[k] = wave_min(ss ? kl[k] : 0xffffffffu); r[3 + k] = wave_max(ss ? kh[k] : 0u); }
-            if (lane_id() == l) {
-                for (int k = 0; k < 3; k++) { atomicMin(&m.lo[s0 * 3 + k], r[k]); atomicMax(&m.hi[s0 * 3 + k], r[3 + k]); }
-                atomicAdd(&m.cnt[s0], (int)__popcll(sm));
-            }
-            rem &= ~sm;
-        }
+        reduce_slots(sel, slot, kl, kh, [&](int s0, const unsigned* lo, const unsigned* hi, int count) {
+            for (int k = 0; k < 3; k++) { atomicMin(&m.lo[s0 * 3 + k], lo[k]); atomicMax(&m.hi[s0 * 3 + k], hi[k]); }
+            atomicAdd(&m.cnt[s0], count);
+        });
         pend = pend && !sel;
         __syncthreads();
     }
@@ -190,26 +216,8 @@ __device__ inline void direct_add(bool act, int node, int slot, const unsigned k
     bool uniform = __all(!act || node == __shfl(node, lead)) != 0;
     if (uniform) {
         int n0 = __shfl(node, lead);
-        unsigned long long rem = am;
-        while (rem) {
-            int l = __ffsll((unsigned long long)rem) - 1;
-            int s0 = __shfl(slot, l);
-            bool ss = act && slot == s0;
-            unsigned long long sm = __ballot(ss);
-            unsigned r[6];
-            for (int k = 0; k < 3; k++) { r[k] = wave_min(ss ? kl[k] : 0xffffffffu); r[3 + k] = wave_max(ss ? kh[k] : 0u); }
-            if (lane_id() == l) {
-                for (int k = 0; k < 3; k++) { atomicMin(dest.lo(n0, s0) + k, r[k]); atomicMax(dest.hi(n0, s0) + k, r[3 + k]); }
-                int* c = dest.cnt(n0, s0);
-                if (c) atomicAdd(c, (int)__popcll(sm));
-            }
-            rem &= ~sm;
-        }
-    } else if (act) {
-        for (int k = 0; k < 3; k++) { atomicMin(dest.lo(node, slot) + k, kl[k]); atomicMax(dest.hi(node, slot) + k, kh[k]); }
-        int* c = dest.cnt(node, slot);
-        if (c) atomicAdd(c, 1);
-    }
+        reduce_slots(act, slot, kl, kh, [&](int s0, const unsigned* lo, const unsigned* hi, int count) { dest_add(dest, n0, s0, lo, hi, count); });
+    } else if (act) dest_add(dest, node, slot, kl, kh, 1);
 }
 
 struct RootDest {
@@ -235,7 +243,6 @@ struct ChildDest {
 __global__ __launch_bounds__(kBlock) void k_prims(Arrays A, int chunk) {
     __shared__ StageMem<1> sm;
     stage_reset(sm);
-    __syncthreads();
     int cur = -1;
     const RootDest dest{A.workA};
     const bool staged = A.n >= kStageMin;
@@ -252,13 +259,14 @@ __global__ __launch_bounds__(kBlock) void k_prims(Arrays A, int chunk) {
             float mx = fminf(fminf(a.x, b.x), c.x) - 0.000001f, my = fminf(fminf(a.y, b.y), c.y) - 0.000001f, mz = fminf(fminf(a.z, b.z), c.z) - 0.000001f;
             float Mx = fmaxf(fmaxf(a.x, b.x), c.x) + 0.000001f, My = fmaxf(fmaxf(a.y, b.y), c.y) + 0.000001f, Mz = fmaxf(fmaxf(a.z, b.z), c.z) + 0.000001f;
             A.cx[i] = (a.x + b.x + c.x) / 3.0f; A.cy[i] = (a.y + b.y + c.y) / 3.0f; A.cz[i] = (a.z + b.z + c.z) / 3.0f;
-            A.lo[i] = make_float4(mx, my, mz, 0.0f); A.hi[i] = make_float4(Mx, My, Mz, 0.0f);
+            const float4 l = make_float4(mx, my, mz, 0.0f), h = make_float4(Mx, My, Mz, 0.0f);
+            A.lo[i] = l; A.hi[i] = h;
             // non-finite geometry has no defined tree in the reference either (NaN compares); refuse it
             float big = fmaxf(fmaxf(fabsf(mx), fabsf(my)), fmaxf(fmaxf(fabsf(mz), fabsf(Mx)), fmaxf(fabsf(My), fabsf(Mz))));
             float any = ((a.x + a.y + a.z) + (b.x + b.y + b.z)) + (c.x + c.y + c.z);          // NaN anywhere -> NaN
             if (!(big <= 1e37f) || any != any) A.ctl->bad = 2;
             A.idxA[i] = i; A.nodeA[i] = 0; A.nodeB[i] = -1;
-            kl[0] = fkey(mx); kl[1] = fkey(my); kl[2] = fkey(mz); kh[0] = fkey(Mx); kh[1] = fkey(My); kh[2] = fkey(Mz);
+            box_keys(l, h, kl, kh);
         }
         if (staged) stage_add(sm, cur, ok, 0, 0, kl, kh, dest);
         else direct_add(ok, 0, 0, kl, kh, dest);
@@ -289,8 +297,7 @@ __global__ void k_classify(Arrays A, WorkNode* work, int leafMax) {
         return;
     }
     if (n <= kSmallNode) { work[w].state = ST_SMALL; return; }      // k_subtree finishes the whole subtree
-    float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
-    int axis = (dy > dx && dy > dz) ? 1 : ((dz > dx && dz > dy) ? 2 : 0);
+    int axis = split_axis(mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]);
     int b = atomicAdd(&A.ctl->binCount, 1);
     work[w].axis = axis; work[w].state = ST_SPLITTING; work[w].bin = b;
     Bins& B = A.bins[b];
@@ -302,7 +309,6 @@ __global__ void k_classify(Arrays A, WorkNode* work, int leafMax) {
 __global__ __launch_bounds__(kBlock) void k_bin(Arrays A, const WorkNode* work, const int* idx, const int* nodeOf, int chunk) {
     __shared__ StageMem<NB> sm;
     stage_reset(sm);
-    __syncthreads();
     int cur = -1;
     const BinDest dest{work, A.bins};
     const int b0 = blockIdx.x * chunk, b1 = min(A.n, b0 + chunk);
@@ -318,11 +324,8 @@ __global__ __launch_bounds__(kBlock) void k_bin(Arrays A, const WorkNode* work, 
             int id = idx[p], axis = nd.axis;
             big = nd.end - nd.start >= kStageMin;
             float a0 = funkey(nd.lo[axis]), ext = funkey(nd.hi[axis]) - a0;
-            float q = NB * (comp3(A.cx, A.cy, A.cz, axis, id) - a0) / ext;
-            b = (q == q && fabsf(q) < 1e9f) ? (int)q : 0;           // int(NaN/inf) is UB in the reference; defined 0
-            b = b < 0 ? 0 : (b > NB - 1 ? NB - 1 : b);
-            float4 l = A.lo[id], h = A.hi[id];
-            kl[0] = fkey(l.x); kl[1] = fkey(l.y); kl[2] = fkey(l.z); kh[0] = fkey(h.x); kh[1] = fkey(h.y); kh[2] = fkey(h.z);
+            b = bucket_of(comp3(A.cx, A.cy, A.cz, axis, id), a0, ext);
+            box_keys(A.lo[id], A.hi[id], kl, kh);
         }
         direct_add(act && !big, w, b, kl, kh, dest);
         stage_add(sm, cur, act && big, w, b, kl, kh, dest);
@@ -395,8 +398,6 @@ __device__ inline int select64(unsigned long long m, int k) {      // position o
     }
     return pos;
 }
-__device__ inline unsigned wmin_if(bool c, unsigned v) { return wave_min(c ? v : 0xffffffffu); }
-__device__ inline unsigned wmax_if(bool c, unsigned v) { return wave_max(c ? v : 0u); }
 __global__ __launch_bounds__(kBlock) void k_subtree(Arrays A, WorkNode* work, int* idx, int leafMax) {
     __shared__ SubLds lds[kBlock / 64];
     const int wv = threadIdx.x >> 6, lane = lane_id();
@@ -414,8 +415,7 @@ __global__ __launch_bounds__(kBlock) void k_subtree(Arrays A, WorkNode* work, in
     unsigned kl[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, kh[3] = {0u, 0u, 0u};
     if (lane < n0) {
         c3[0] = A.cx[id]; c3[1] = A.cy[id]; c3[2] = A.cz[id];
-        const float4 l = A.lo[id], h = A.hi[id];
-        kl[0] = fkey(l.x); kl[1] = fkey(l.y); kl[2] = fkey(l.z); kh[0] = fkey(h.x); kh[1] = fkey(h.y); kh[2] = fkey(h.z);
+        box_keys(A.lo[id], A.hi[id], kl, kh);
     }
     int top = 0, nLocal = 0, nInternal = 0, height = 0, largest = 0, backups = 0, sorts = 0;
     L.stack[0] = SubStack{0, (short)n0, -1, 2};
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(kBlock) void k_subtree(Arrays A, WorkNode* work, in
         if (!isLeaf) {
             const float mnx = funkey(nlo[0]), mny = funkey(nlo[1]), mnz = funkey(nlo[2]);
             const float dx = funkey(nhi[0]) - mnx, dy = funkey(nhi[1]) - mny, dz = funkey(nhi[2]) - mnz;
-            const int axis = (dy > dx && dy > dz) ? 1 : ((dz > dx && dz > dy) ? 2 : 0);
+            const int axis = split_axis(dx, dy, dz);
             const float c = axis == 0 ? c3[0] : (axis == 1 ? c3[1] : c3[2]);
             const float a0 = funkey(nlo[axis]), ext = funkey(nhi[axis]) - a0;
             // buckets, main.cu:71-85
@@ -452,9 +452,7 @@ __global__ __launch_bounds__(kBlock) void k_subtree(Arrays A, WorkNode* work, in
                 if (lane < NB * 3) { (&L.bins.lo[0][0])[lane] = kmax; (&L.bins.hi[0][0])[lane] = kmin; }
                 if (lane < NB) L.bins.cnt[lane] = 0;
             }
-            float q = NB * (c - a0) / ext;
-            int b = (q == q && fabsf(q) < 1e9f) ? (int)q : 0;
-            b = b < 0 ? 0 : (b > NB - 1 ? NB - 1 : b);
+            const int b = bucket_of(c, a0, ext);
             // one LDS atomic per box word and lane (min / max / add are exact in any order); the wavefront-scope
             // fences keep the initialising stores, the atomics and the sweep's loads in that order for the compiler
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -641,38 +639,39 @@ __device__ inline int load_flags(const unsigned char* F, int n, int base, int f[
     }
     return sum;
 }
-__global__ void k_scan1(Arrays A, int gated) {
-    if (gated && !A.ctl->anyRedo) return;
+// gate (may be NULL): the level's ctl; with it the kernels run only when a node of the level retries (anyRedo).
+__global__ void k_scan1(const unsigned char* F, int n, int* blockSum, const Ctl* gate) {
+    if (gate && !gate->anyRedo) return;
     int f[kScanItems];
     int base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-    int s = load_flags(A.F, A.n, base, f), tot;
+    int s = load_flags(F, n, base, f), tot;
     block_exclusive(s, &tot);
-    if (threadIdx.x == 0) A.blockSum[blockIdx.x] = tot;
+    if (threadIdx.x == 0) blockSum[blockIdx.x] = tot;
 }
-__global__ void k_scan2(Arrays A, int M, int gated) {
-    if (gated && !A.ctl->anyRedo) return;
+__global__ void k_scan2(int* blockSum, int M, int* total, const Ctl* gate) {
+    if (gate && !gate->anyRedo) return;
     __shared__ int carry;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     for (int base = 0; base < M; base += kBlock) {
         int i = base + threadIdx.x;
-        int v = i < M ? A.blockSum[i] : 0, tot;
+        int v = i < M ? blockSum[i] : 0, tot;
         int ex = block_exclusive(v, &tot);
         int c = carry;
-        if (i < M) A.blockSum[i] = c + ex;
+        if (i < M) blockSum[i] = c + ex;
         __syncthreads();
         if (threadIdx.x == 0) carry = c + tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) A.S[A.n] = carry;
+    if (threadIdx.x == 0) *total = carry;
 }
-__global__ void k_scan3(Arrays A, int gated) {
-    if (gated && !A.ctl->anyRedo) return;
+__global__ void k_scan3(const unsigned char* F, int n, const int* blockSum, int* S, const Ctl* gate) {
+    if (gate && !gate->anyRedo) return;
     int f[kScanItems];
     int base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-    int s = load_flags(A.F, A.n, base, f), tot;
-    int run = A.blockSum[blockIdx.x] + block_exclusive(s, &tot);
-    for (int j = 0; j < kScanItems; j++) { if (base + j < A.n) A.S[base + j] = run; run += f[j]; }
+    int s = load_flags(F, n, base, f), tot;
+    int run = blockSum[blockIdx.x] + block_exclusive(s, &tot);
+    for (int j = 0; j < kScanItems; j++) { if (base + j < n) S[base + j] = run; run += f[j]; }
 }
 
 // numLeft test, main.cu:189-190 (pass 0) and :210-221 (pass 1: forced, possibly oversize, leaf).
@@ -750,7 +749,6 @@ __global__ __launch_bounds__(kBlock) void k_scatter(Arrays A, const WorkNode* wo
                                                     int* nodeOf, int* nodeOut, int chunk) {
     __shared__ StageMem<2> sm;
     stage_reset(sm);
-    __syncthreads();
     int cur = -1;
     const ChildDest dest{work, next};
     const int b0 = blockIdx.x * chunk, b1 = min(A.n, b0 + chunk);
@@ -777,8 +775,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter(Arrays A, const WorkNode* wo
             }
             side = dst < s + nl ? 0 : 1;
             idxOut[dst] = id; nodeOut[dst] = nd.child + side;
-            float4 l = A.lo[id], h = A.hi[id];
-            kl[0] = fkey(l.x); kl[1] = fkey(l.y); kl[2] = fkey(l.z); kh[0] = fkey(h.x); kh[1] = fkey(h.y); kh[2] = fkey(h.z);
+            box_keys(A.lo[id], A.hi[id], kl, kh);
         }
         direct_add(act && !big, w, side, kl, kh, dest);
         stage_add(sm, cur, act && big, w, side, kl, kh, dest);
@@ -805,31 +802,36 @@ __global__ void k_pre(Arrays A, int a, int b) {
     A.out[n.left].pre = n.pre + 1;
     A.out[n.right].pre = n.pre + 1 + A.out[n.left].size;
 }
+// N: OutNode or SubNode; at(c): the final index of child c.
+template <class N, class At> __device__ inline pt_bvh_node emit_node(const N& n, const At& at) {
+    pt_bvh_node f;
+    f.aabbMIN = pt_float4{n.lo[0], n.lo[1], n.lo[2], 0.0f};
+    f.aabbMAX = pt_float4{n.hi[0], n.hi[1], n.hi[2], 0.0f};
+    if (n.count > 0) { f.left = f.right = -1; f.first = n.first; f.primCount = n.count; }
+    else { f.left = at(n.left); f.right = at(n.right); f.first = -1; f.primCount = 0; }
+    return f;
+}
 __global__ void k_emit(Arrays A, int total) {
     int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= total) return;
     const OutNode& n = A.out[o];
     if (n.sub >= 0) {                                           // a subtree: its nodes are already in pre-order
         const SubNode* s = A.sub + n.sub;
-        for (int j = 0; j < n.size; j++) {
-            pt_bvh_node f;
-            f.aabbMIN = pt_float4{s[j].lo[0], s[j].lo[1], s[j].lo[2], 0.0f};
-            f.aabbMAX = pt_float4{s[j].hi[0], s[j].hi[1], s[j].hi[2], 0.0f};
-            if (s[j].count > 0) { f.left = f.right = -1; f.first = s[j].first; f.primCount = s[j].count; }
-            else { f.left = n.pre + s[j].left; f.right = n.pre + s[j].right; f.first = -1; f.primCount = 0; }
-            A.fin[n.pre + j] = f;
-        }
+        for (int j = 0; j < n.size; j++) A.fin[n.pre + j] = emit_node(s[j], [&](int c) { return n.pre + c; });
         return;
     }
-    pt_bvh_node f;
-    f.aabbMIN = pt_float4{n.lo[0], n.lo[1], n.lo[2], 0.0f};
-    f.aabbMAX = pt_float4{n.hi[0], n.hi[1], n.hi[2], 0.0f};
-    if (n.count > 0) { f.left = f.right = -1; f.first = n.first; f.primCount = n.count; }
-    else { f.left = A.out[n.left].pre; f.right = A.out[n.right].pre; f.first = -1; f.primCount = 0; }
-    A.fin[n.pre] = f;
+    A.fin[n.pre] = emit_node(n, [&](int c) { return A.out[c].pre; });
 }
 
 inline int blocks(long long n, int per = kBlock) { return (int)std::max<long long>(1, (n + per - 1) / per); }
+
+// The exclusive prefix sum of the n flags F into S[0..n] (S[n]: the total); blockSum: a word per scan tile.
+void launch_scan(const unsigned char* F, int* S, int* blockSum, int n, const Ctl* gate, hipStream_t st) {
+    const int g = blocks(n, kScanTile);
+    hipLaunchKernelGGL(k_scan1, dim3(g), dim3(kBlock), 0, st, F, n, blockSum, gate);
+    hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kBlock), 0, st, blockSum, g, S + n, gate);
+    hipLaunchKernelGGL(k_scan3, dim3(g), dim3(kBlock), 0, st, F, n, blockSum, S, gate);
+}
 
 struct Carver {
     char* base = nullptr; size_t off = 0;
@@ -860,7 +862,7 @@ void carve(Carver& c, Arrays& A, int n, int nPos, int maxBins) {
 }
 
 // ---- re-layout on the device: the packed records the kernels traverse, straight from the
-// builder's arrays. Same contents as pt_scene.hip's host re-pack; PNodes are numbered in the builder's
+// builder's arrays, through the makers the host re-pack calls (pt_pack.h); PNodes are numbered in the builder's
 // breadth-first order (children of one level in allocation order, which is any valid breadth-first order).
 struct PackIn { const pt_float4* normals; int nNormals; const pt_float2* uvs; int nUvs; const int* matType; int nMats; int nLights; };
 // mode 0: F = record is an internal node of the breadth-first part; mode 1: F = internal nodes inside the record's subtree
@@ -885,29 +887,19 @@ __global__ void k_pack_nodes(Arrays A, int total, const int* iid, const int* sub
     if (n.sub >= 0) {                                           // a subtree: walk its pre-order list, internal nodes numbered in that order
         const SubNode* s = A.sub + n.sub;
         const int base = nBfs + subBase[o];
-        int local[127];
-        int k = 0;
+        int local[127], k = 0;
         for (int j = 0; j < n.size; j++) local[j] = s[j].count > 0 ? -1 : k++;
         for (int j = 0; j < n.size; j++) {
             if (s[j].count > 0) { leafEnd[s[j].first + s[j].count - 1] = 1; continue; }
             const SubNode &Lc = s[s[j].left], &Rc = s[s[j].right];
-            pt::PNode p;
-            for (int q = 0; q < 3; q++) { p.lmin[q] = Lc.lo[q]; p.lmax[q] = Lc.hi[q]; p.rmin[q] = Rc.lo[q]; p.rmax[q] = Rc.hi[q]; }
-            p.left = Lc.count > 0 ? ~Lc.first : base + local[s[j].left];
-            p.right = Rc.count > 0 ? ~Rc.first : base + local[s[j].right];
-            p.pad0 = p.pad1 = 0;
-            nodes[base + local[j]] = p;
+            auto ref = [&](int c) { return s[c].count > 0 ? ~s[c].first : base + local[c]; };
+            nodes[base + local[j]] = pt::make_node(Lc.lo, Lc.hi, Rc.lo, Rc.hi, ref(s[j].left), ref(s[j].right));
         }
         return;
     }
     if (n.count > 0) { leafEnd[n.first + n.count - 1] = 1; return; }
     const OutNode &Lc = A.out[n.left], &Rc = A.out[n.right];
-    pt::PNode p;
-    for (int k = 0; k < 3; k++) { p.lmin[k] = Lc.lo[k]; p.lmax[k] = Lc.hi[k]; p.rmin[k] = Rc.lo[k]; p.rmax[k] = Rc.hi[k]; }
-    p.left = pack_ref(A, n.left, iid, subBase, nBfs);
-    p.right = pack_ref(A, n.right, iid, subBase, nBfs);
-    p.pad0 = p.pad1 = 0;
-    nodes[iid[o]] = p;
+    nodes[iid[o]] = pt::make_node(Lc.lo, Lc.hi, Rc.lo, Rc.hi, pack_ref(A, n.left, iid, subBase, nBfs), pack_ref(A, n.right, iid, subBase, nBfs));
 }
 __global__ void k_pack_tris(Arrays A, const int* idx, PackIn in, const unsigned char* leafEnd, pt::PTri* tris, int* flagsOut) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -915,108 +907,43 @@ __global__ void k_pack_tris(Arrays A, const int* idx, PackIn in, const unsigned 
     const int id = idx[i];
     const pt_triangle t = A.mesh[id];
     const pt_float4 a = A.pos[t.aInd], b = A.pos[t.bInd], c = A.pos[t.cInd];      // indices checked by k_prims
-    pt::PTri p;
-    p.v0[0] = a.x; p.v0[1] = a.y; p.v0[2] = a.z;
-    p.e1[0] = b.x - a.x; p.e1[1] = b.y - a.y; p.e1[2] = b.z - a.z;      // trib - tria, integratorUtilities.cuh:13
-    p.e2[0] = c.x - a.x; p.e2[1] = c.y - a.y; p.e2[2] = c.z - a.z;      // tric - tria, :14
-    p.idx = (uint32_t)id | (leafEnd[i] ? 0x80000000u : 0u);
     int mat = t.materialID;
     if (mat < 0 || mat >= in.nMats) { atomicOr(flagsOut, 1); mat = 0; }
-    p.material = mat;
     const int ty = in.matType[mat];
-    p.flags = pt_tri_flags_(ty);
     if (!pt_type_has_arm_(ty)) atomicOr(flagsOut, (int)kTriArmless);
-    tris[i] = p;
+    tris[i] = pt::make_tri(a, b, c, id, leafEnd[i] != 0, mat, ty);
 }
 __global__ void k_pack_attrs(Arrays A, PackIn in, pt::PAttr* attrs, int* flagsOut) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
     const pt_triangle t = A.mesh[i];
-    pt::PAttr a;
     const int ni[3] = {t.naInd, t.nbInd, t.ncInd}, ui[3] = {t.uvaInd, t.uvbInd, t.uvcInd};
-    float* nd[3] = {a.n0, a.n1, a.n2}; float* ud[3] = {a.uv0, a.uv1, a.uv2};
+    pt_float4 nn[3]; pt_float2 uu[3];
     for (int k = 0; k < 3; k++) {
         int nk = ni[k], uk = ui[k];
         if (nk < 0 || nk >= in.nNormals) { atomicOr(flagsOut, 2); nk = 0; }
         if (uk < 0 || uk >= in.nUvs) { atomicOr(flagsOut, 4); uk = 0; }
-        const pt_float4 nn = in.nNormals > 0 ? in.normals[nk] : pt_float4{0, 0, 0, 0};
-        const pt_float2 uu = in.nUvs > 0 ? in.uvs[uk] : pt_float2{0, 0};
-        nd[k][0] = nn.x; nd[k][1] = nn.y; nd[k][2] = nn.z;
-        ud[k][0] = uu.x; ud[k][1] = uu.y;
+        nn[k] = in.nNormals > 0 ? in.normals[nk] : pt_float4{0, 0, 0, 0};
+        uu[k] = in.nUvs > 0 ? in.uvs[uk] : pt_float2{0, 0};
     }
-    a.emission[0] = t.emission.x; a.emission[1] = t.emission.y; a.emission[2] = t.emission.z;
-    a.material = t.materialID;
-    a.lightInd = (t.lightInd >= 0 && t.lightInd < in.nLights) ? t.lightInd : -51;
-    attrs[i] = a;
+    attrs[i] = pt::make_attr(t, nn, uu, in.nLights);
 }
-// The light records (pt_scene.hip's host re-pack, same operations in the same order): the light's triangle with the CURRENT positions,
-// its first normal, its emission and its area = 0.5f * length(cross3(b - a, c - a)) as the kernels used to evaluate it per NEE
-// sample: IEEE subtractions, cross = fma(p, q, -(r * s)), dot = fma(z, z', fma(y, y', x * x')), correctly rounded sqrt. `lights`
-// was zeroed (a scene without lights keeps one zero record).
+// The light records (pt_pack.h: make_light, as the host re-pack): the light's triangle with the CURRENT positions, its first normal,
+// its emission and its area. `lights` was zeroed (a scene without lights keeps one zero record).
 __global__ void k_pack_lights(Arrays A, PackIn in, const pt_triangle* lightTris, pt::PLight* lights, int* flagsOut) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= in.nLights) return;
     const pt_triangle t = lightTris[i];
     int ia = t.aInd, ib = t.bInd, ic = t.cInd, na = t.naInd;
-    if ((unsigned)ia >= (unsigned)A.nPos || (unsigned)ib >= (unsigned)A.nPos || (unsigned)ic >= (unsigned)A.nPos || na < 0 || na >= in.nNormals) {
-        atomicOr(flagsOut, 8);
-        return;
-    }
-    const pt_float4 a = A.pos[ia], b = A.pos[ib], c = A.pos[ic], n = in.normals[na];
-    pt::PLight L;
-    L.a[0] = a.x; L.a[1] = a.y; L.a[2] = a.z; L.b[0] = b.x; L.b[1] = b.y; L.b[2] = b.z; L.c[0] = c.x; L.c[1] = c.y; L.c[2] = c.z;
-    L.na[0] = n.x; L.na[1] = n.y; L.na[2] = n.z;
-    L.emission[0] = t.emission.x; L.emission[1] = t.emission.y; L.emission[2] = t.emission.z;
-    const float ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z, vx = c.x - a.x, vy = c.y - a.y, vz = c.z - a.z;
-    const float cx = fmaf(uy, vz, -(uz * vy)), cy = fmaf(uz, vx, -(ux * vz)), cz = fmaf(ux, vy, -(uy * vx));
-    L.area = 0.5f * sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
-    lights[i] = L;
-}
-
-// ---- edits in place (pt_scene_update_materials / pt_scene_update_emission, pt_bvh_build.h): what the pack kernels above would
-// write for the edited description, without the tree, the positions or the builder's arrays.
-// One thread per packed triangle: its flags word from its material row's class (pt_material_class_), the only word of the record a
-// material decides; the classes are OR-ed over the wave with one ballot per class bit and leave it in one atomicOr. Lanes past the
-// end carry class 0 and stay for the ballots.
-constexpr uint32_t kClassBits[4] = {kTriLeaf, kRowTextured, kRowNotSimple, kTriArmless};
-__global__ void k_edit_materials(pt::PTri* tris, int n, const uint32_t* cls, int nMats, uint32_t* orOut) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t c = 0u;
-    if (i < n) {
-        const int mat = tris[i].material;                      // creation refused an index outside the table
-        if (mat >= 0 && mat < nMats) c = cls[mat];
-        tris[i].flags = c & kTriLeaf;
-    }
-    uint32_t w = 0u;
-    for (int b = 0; b < 4; b++)
-        if (__ballot((c & kClassBits[b]) != 0u)) w |= kClassBits[b];
-    if ((threadIdx.x & 63) == 0 && w) atomicOr(orOut, w);
-}
-// Thread i < n: attribute i (original triangle index, as the kept triangles are) takes its light's emission if that light is edited;
-// thread i < nLights: light i itself. emission / on: the edit as a table by light, so that a triangle does one lookup.
-__global__ void k_edit_emission(pt::PAttr* attrs, int n, pt::PLight* lights, int nLights, const pt_float4* emission, const int32_t* on,
-                                pt_triangle* keptTris, pt_triangle* keptLightTris) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const int li = attrs[i].lightInd;
-        if (li >= 0 && li < nLights && on[li]) {
-            const pt_float4 e = emission[li];
-            attrs[i].emission[0] = e.x; attrs[i].emission[1] = e.y; attrs[i].emission[2] = e.z;
-            if (keptTris) keptTris[i].emission = e;
-        }
-    }
-    if (i < nLights && on[i]) {
-        const pt_float4 e = emission[i];
-        lights[i].emission[0] = e.x; lights[i].emission[1] = e.y; lights[i].emission[2] = e.z;
-        if (keptLightTris) keptLightTris[i].emission = e;
-    }
+    if ((unsigned)ia >= (unsigned)A.nPos || (unsigned)ib >= (unsigned)A.nPos || (unsigned)ic >= (unsigned)A.nPos || na < 0 || na >= in.nNormals) { atomicOr(flagsOut, 8); return; }
+    lights[i] = pt::make_light(A.pos[ia], A.pos[ib], A.pos[ic], in.normals[na], t.emission);
 }
 
 struct Built {                        // what build_core leaves on the device (pool still allocated)
     void* pool = nullptr;
     bool owned = true;                // false: the pool is the caller's and outlives the build
     void drop() {                     // the end of a build, good or bad
-        if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
+        for (hipEvent_t* e : {&ev0, &ev1}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
         if (pool && owned) (void)hipFree(pool);
         pool = nullptr;
     }
@@ -1024,7 +951,7 @@ struct Built {                        // what build_core leaves on the device (p
     int* idx = nullptr;               // the final BVHindices permutation
     int total = 0, outTotal = 0, levels = 0, height = 0;   // reference nodes, breadth-first records, levels built level by level, tree height
     Ctl ctl{};
-    hipEvent_t ev0 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around the device work: recorded by build_core and by its caller
     char* extra = nullptr;            // caller's scratch inside the pool
 };
 
@@ -1080,6 +1007,7 @@ int build_core(const pt_float4* positions, bool posOnDevice, int n_positions, co
     A.n = n; A.nPos = n_positions;
     hipStream_t st = nullptr;
     BVH_HIP(hipEventCreate(&B.ev0));
+    BVH_HIP(hipEventCreate(&B.ev1));
     if (posOnDevice) A.pos = positions;
     else BVH_HIP(hipMemcpy((void*)A.pos, positions, sizeof(pt_float4) * (size_t)n_positions, hipMemcpyHostToDevice));
     if (trisOnDevice) A.mesh = triangles;
@@ -1093,7 +1021,7 @@ int build_core(const pt_float4* positions, bool posOnDevice, int n_positions, co
     root.start = 0; root.end = n; root.out = 0; root.child = -1; root.bin = -1;
     for (int k = 0; k < 3; k++) { root.lo[k] = 0xffffffffu; root.hi[k] = 0u; }
     BVH_HIP(hipMemcpy(A.workA, &root, sizeof(root), hipMemcpyHostToDevice));
-    const int gN = blocks(n), gScan = blocks(n, kScanTile);
+    const int gN = blocks(n);
     const int gChunk = std::min(kChunks, gN);
     const int chunk = ((n + gChunk - 1) / gChunk + kBlock - 1) / kBlock * kBlock;      // positions per workgroup, multiple of the tile
     BVH_HIP(hipEventRecord(B.ev0, st));
@@ -1151,9 +1079,7 @@ int build_core(const pt_float4* positions, bool posOnDevice, int n_positions, co
         }
         for (int pass = 0; pass < 2; pass++) {
             hipLaunchKernelGGL(k_flag, dim3(gN), dim3(kBlock), 0, st, A, work, idx, nodeOf, pass);
-            hipLaunchKernelGGL(k_scan1, dim3(gScan), dim3(kBlock), 0, st, A, pass);
-            hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kBlock), 0, st, A, gScan, pass);
-            hipLaunchKernelGGL(k_scan3, dim3(gScan), dim3(kBlock), 0, st, A, pass);
+            launch_scan(A.F, A.S, A.blockSum, n, pass ? A.ctl : nullptr, st);
             hipLaunchKernelGGL(k_check, dim3(gW), dim3(kBlock), 0, st, A, work, pass);
             if (pass == 0) hipLaunchKernelGGL(k_mean, dim3(std::min(gW, 2048)), dim3(kBlock), 0, st, A, work, idx);
         }
@@ -1200,14 +1126,11 @@ extern "C" int pt_bvh_build_device(const pt_float4* positions, int n_positions, 
     Built B;
     if (int r = build_core(positions, false, n_positions, triangles, false, n_triangles, max_leaf_size, 0, nullptr, nullptr, B)) return r;
     if (B.total > nodes_capacity) { B.drop(); return pt_fail_(-1, "pt_bvh_build_device: nodes_out too small (2*n_triangles-1 always suffices)"); }
-    hipEvent_t ev1 = nullptr;
-    BVH_HIP(hipEventCreate(&ev1));
-    BVH_HIP(hipEventRecord(ev1, nullptr));
+    BVH_HIP(hipEventRecord(B.ev1, nullptr));
     BVH_HIP(hipMemcpy(nodes_out, B.A.fin, sizeof(pt_bvh_node) * (size_t)B.total, hipMemcpyDeviceToHost));
     BVH_HIP(hipMemcpy(indices_out, B.idx, sizeof(int32_t) * (size_t)n_triangles, hipMemcpyDeviceToHost));
     float ms = 0.0f;
-    BVH_HIP(hipEventElapsedTime(&ms, B.ev0, ev1));
-    (void)hipEventDestroy(ev1);
+    BVH_HIP(hipEventElapsedTime(&ms, B.ev0, B.ev1));
     B.drop();
     fill_stats(stats, B, ms, wall0);
     return B.total;
@@ -1215,84 +1138,60 @@ extern "C" int pt_bvh_build_device(const pt_float4* positions, int n_positions, 
 
 // Build + re-layout without leaving the device (pt_scene_create_from_mesh and pt_scene_update_*, pt_scene.hip): pt_bvh_build.h.
 extern "C" int pt_bvh_build_pack_(const pt_build_src_* d, int max_leaf_size, void* d_nodes, void* d_tris, void* d_attrs, void* d_lights,
-                                  int* out5, pt_bvh_build_stats* stats) {
+                                  pt_build_out_* out, pt_bvh_build_stats* stats) {
     const auto wall0 = std::chrono::steady_clock::now();
     const int n = d->n_triangles;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t offLeafEnd = 0;
-    const size_t offF = offLeafEnd + al((size_t)n + 16), offS = offF + al(2 * (size_t)n + 16), offBlk = offS + al(sizeof(int) * (2 * (size_t)n + 2));
-    const size_t offS2 = offBlk + al(sizeof(int) * ((size_t)blocks(2LL * n, kScanTile) + 2));
-    const size_t offFlags = offS2 + al(sizeof(int) * (2 * (size_t)n + 2)), extraBytes = offFlags + 256;
+    // the pack's own arrays: a leaf-end mark per triangle; a flag and two sums per builder record (fewer than 2n); the scans' tile sums; the kernels' report word
+    unsigned char *leafEnd, *F; int *iid, *subBase, *blockSum, *flags;
+    auto carve_pack = [&](Carver& c) {
+        leafEnd = c.take<unsigned char>((size_t)n + 16); F = c.take<unsigned char>(2 * (size_t)n + 16);
+        iid = c.take<int>(2 * (size_t)n + 2); subBase = c.take<int>(2 * (size_t)n + 2);
+        blockSum = c.take<int>((size_t)blocks(2LL * n, kScanTile) + 2); flags = c.take<int>(64);
+    };
+    Carver sizer; carve_pack(sizer);
     Built B;
-    if (int r = build_core(d->positions, d->positions_on_device != 0, d->n_positions, d->d_triangles, true, n, max_leaf_size, extraBytes, d->pool,
+    if (int r = build_core(d->positions, d->positions_on_device != 0, d->n_positions, d->d_triangles, true, n, max_leaf_size, sizer.off, d->pool,
                            d->pool_bytes, B))
         return r;
-    char* X = B.extra;
-    BVH_HIP(hipMemsetAsync(X + offLeafEnd, 0, (size_t)n + 16, nullptr));
-    BVH_HIP(hipMemsetAsync(X + offFlags, 0, 16, nullptr));
+    Carver real; real.base = B.extra; carve_pack(real);
+    BVH_HIP(hipMemsetAsync(leafEnd, 0, (size_t)n + 16, nullptr));
+    BVH_HIP(hipMemsetAsync(flags, 0, 16, nullptr));
     PackIn in{d->d_normals, d->n_normals, d->d_uvs, d->n_uvs, d->d_mat_types, d->n_materials, d->n_lights};
-    unsigned char* leafEnd = (unsigned char*)(X + offLeafEnd);
-    int* flags = (int*)(X + offFlags);
     // internal nodes of the breadth-first part in that order (exclusive scan of "is internal" over the builder's
     // records), then the subtrees' internal nodes (exclusive scan of their counts)
     const int T = B.outTotal;
-    Arrays S = B.A;                                      // the scan kernels read F / S / blockSum / n from their Arrays
-    S.F = (unsigned char*)(X + offF); S.S = (int*)(X + offS); S.blockSum = (int*)(X + offBlk); S.n = T;
-    Arrays S2 = S;
-    S2.S = (int*)(X + offS2);
     hipStream_t st = nullptr;
-    const int gT = blocks(T), gScan = blocks(T, kScanTile);
-    hipLaunchKernelGGL(k_pack_flags, dim3(gT), dim3(kBlock), 0, st, B.A, T, S.F, 0);
-    hipLaunchKernelGGL(k_scan1, dim3(gScan), dim3(kBlock), 0, st, S, 0);
-    hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kBlock), 0, st, S, gScan, 0);
-    hipLaunchKernelGGL(k_scan3, dim3(gScan), dim3(kBlock), 0, st, S, 0);
-    hipLaunchKernelGGL(k_pack_flags, dim3(gT), dim3(kBlock), 0, st, B.A, T, S.F, 1);
-    hipLaunchKernelGGL(k_scan1, dim3(gScan), dim3(kBlock), 0, st, S2, 0);
-    hipLaunchKernelGGL(k_scan2, dim3(1), dim3(kBlock), 0, st, S2, gScan, 0);
-    hipLaunchKernelGGL(k_scan3, dim3(gScan), dim3(kBlock), 0, st, S2, 0);
-    hipLaunchKernelGGL(k_pack_nodes, dim3(gT), dim3(kBlock), 0, st, B.A, T, S.S, S2.S, (pt::PNode*)d_nodes, leafEnd);
+    const int gT = blocks(T);
+    hipLaunchKernelGGL(k_pack_flags, dim3(gT), dim3(kBlock), 0, st, B.A, T, F, 0);
+    launch_scan(F, iid, blockSum, T, nullptr, st);
+    hipLaunchKernelGGL(k_pack_flags, dim3(gT), dim3(kBlock), 0, st, B.A, T, F, 1);
+    launch_scan(F, subBase, blockSum, T, nullptr, st);
+    hipLaunchKernelGGL(k_pack_nodes, dim3(gT), dim3(kBlock), 0, st, B.A, T, iid, subBase, (pt::PNode*)d_nodes, leafEnd);
     hipLaunchKernelGGL(k_pack_tris, dim3(blocks(n)), dim3(kBlock), 0, st, B.A, B.idx, in, leafEnd, (pt::PTri*)d_tris, flags);
     hipLaunchKernelGGL(k_pack_attrs, dim3(blocks(n)), dim3(kBlock), 0, st, B.A, in, (pt::PAttr*)d_attrs, flags);
     if (d_lights) {
         BVH_HIP(hipMemsetAsync(d_lights, 0, sizeof(pt::PLight) * (size_t)std::max(d->n_lights, 1), st));
         if (d->n_lights > 0) hipLaunchKernelGGL(k_pack_lights, dim3(blocks(d->n_lights)), dim3(kBlock), 0, st, B.A, in, d->d_light_tris, (pt::PLight*)d_lights, flags);
     }
-    hipEvent_t ev1 = nullptr;
-    BVH_HIP(hipEventCreate(&ev1));
-    BVH_HIP(hipEventRecord(ev1, st));
+    BVH_HIP(hipEventRecord(B.ev1, st));
     int nBfs = 0, nSub = 0, fl = 0;
     OutNode rootRec{};
     SubNode rootSub{};
-    BVH_HIP(hipMemcpy(&nBfs, S.S + T, sizeof(int), hipMemcpyDeviceToHost));
-    BVH_HIP(hipMemcpy(&nSub, S2.S + T, sizeof(int), hipMemcpyDeviceToHost));
+    BVH_HIP(hipMemcpy(&nBfs, iid + T, sizeof(int), hipMemcpyDeviceToHost));
+    BVH_HIP(hipMemcpy(&nSub, subBase + T, sizeof(int), hipMemcpyDeviceToHost));
     BVH_HIP(hipMemcpy(&fl, flags, sizeof(int), hipMemcpyDeviceToHost));
     BVH_HIP(hipMemcpy(&rootRec, B.A.out, sizeof(OutNode), hipMemcpyDeviceToHost));
     if (rootRec.sub >= 0) BVH_HIP(hipMemcpy(&rootSub, B.A.sub + rootRec.sub, sizeof(SubNode), hipMemcpyDeviceToHost));
     const int nInternal = nBfs + nSub;
     const int rootRef = rootRec.sub >= 0 ? (rootSub.count > 0 ? ~rootSub.first : nBfs) : (rootRec.count > 0 ? ~rootRec.first : 0);
     float ms = 0.0f;
-    BVH_HIP(hipEventElapsedTime(&ms, B.ev0, ev1));
-    (void)hipEventDestroy(ev1);
+    BVH_HIP(hipEventElapsedTime(&ms, B.ev0, B.ev1));
     B.drop();
     if (fl & 8) return pt_fail_(-1, "pt_scene_create_from_mesh: a light's vertex or normal index is out of range");
     if (fl & 1) return pt_fail_(-1, "pt_scene_create_from_mesh: a triangle's material index is out of range");
     if (fl & 2) return pt_fail_(-1, "pt_scene_create_from_mesh: a triangle's normal index is out of range (faces without vn must be given a normal by the loader)");
     if (fl & 4) return pt_fail_(-1, "pt_scene_create_from_mesh: a triangle's uv index is out of range");
-    out5[0] = nInternal; out5[1] = B.height - 1; out5[2] = rootRef; out5[3] = (fl & 0x100) ? 1 : 0; out5[4] = B.total;
+    *out = pt_build_out_{nInternal, B.height - 1, rootRef, (fl & (int)kTriArmless) ? 1 : 0};
     fill_stats(stats, B, ms, wall0);
     return 0;
-}
-
-extern "C" int pt_edit_materials_(void* d_tris, int n_triangles, const uint32_t* d_class, int n_materials, uint32_t* d_or) {
-    hipLaunchKernelGGL(k_edit_materials, dim3(blocks(n_triangles)), dim3(kBlock), 0, nullptr, (pt::PTri*)d_tris, n_triangles, d_class, n_materials, d_or);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pt_fail_(-2, hipGetErrorString(e));
-}
-
-extern "C" int pt_edit_emission_(void* d_attrs, int n_triangles, void* d_lights, int n_lights, const pt_float4* d_emission, const int32_t* d_on,
-                                 pt_triangle* d_kept_tris, pt_triangle* d_kept_light_tris) {
-    hipLaunchKernelGGL(k_edit_emission, dim3(blocks(std::max(n_triangles, n_lights))), dim3(kBlock), 0, nullptr, (pt::PAttr*)d_attrs, n_triangles,
-                       (pt::PLight*)d_lights, n_lights, d_emission, d_on, d_kept_tris, d_kept_light_tris);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pt_fail_(-2, hipGetErrorString(e));
 }

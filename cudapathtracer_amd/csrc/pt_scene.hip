@@ -1,9 +1,10 @@
 // pt_scene.hip — a scene's making and editing behind include/pt_api.h: the re-pack of the reference's data model and its upload,
-// the layout derived from the packed records, pt_scene_create* / pt_scene_destroy and the in-place updates. Host code only.
+// the layout derived from the packed records, pt_scene_create* / pt_scene_destroy, the in-place updates and the two edit kernels. The
+// records themselves, and the host re-pack of a caller's own tree, are made in pt_pack.h.
 #include <chrono>
-#include <cmath>
 
 #include "pt_host.h"
+#include "pt_pack.h"
 #include "pt_bvh_build.h"
 #include "pt_box_table.h"
 #include "xorwow_host.h"
@@ -39,60 +40,20 @@ static void light_triangles(const PTri* pt, int nT, const PLight* lights, int nL
     for (int i = 0; i < nLights; i++) {
         out[i] = -1;
         const PLight& L = lights[i];
-        const float v0[3] = {L.a[0], L.a[1], L.a[2]}, e1[3] = {L.b[0] - L.a[0], L.b[1] - L.a[1], L.b[2] - L.a[2]},
-                    e2[3] = {L.c[0] - L.a[0], L.c[1] - L.a[1], L.c[2] - L.a[2]};
+        const PTri want = make_tri(pt_float4{L.a[0], L.a[1], L.a[2], 0}, pt_float4{L.b[0], L.b[1], L.b[2], 0}, pt_float4{L.c[0], L.c[1], L.c[2], 0}, 0, false, 0, 0);
         for (int p = 0; p < nT && p < 63; p++) {                 // (the pair pass holds a ray's triangles in one 64-bit mask, and clears bit p as (1 << (p + 1)) >> 1)
             const int idx = (int)(pt[p].idx & 0x7fffffffu);
             if (idx >= nTriangles || lightIndOf(idx) != i) continue;
-            if (!memcmp(pt[p].v0, v0, 12) && !memcmp(pt[p].e1, e1, 12) && !memcmp(pt[p].e2, e2, 12)) { out[i] = p; break; }
+            if (!memcmp(pt[p].v0, want.v0, 12) && !memcmp(pt[p].e1, want.e1, 12) && !memcmp(pt[p].e2, want.e2, 12)) { out[i] = p; break; }
         }
     }
-}
-// ... from a description: a light whose vertex indices are out of range gets -1.
-static void light_triangles(const PTri* pt, int nT, const pt_scene_desc* d, int32_t* out) {
-    std::vector<PLight> L((size_t)std::max(d->n_lights, 1));
-    std::vector<uint8_t> bad((size_t)std::max(d->n_lights, 1), 0);
-    for (int i = 0; i < d->n_lights; i++) {
-        const pt_triangle& t = d->lights[i];
-        L[i] = PLight{};
-        if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions) { bad[i] = 1; continue; }
-        const pt_float4 a = d->positions[t.aInd], b = d->positions[t.bInd], c = d->positions[t.cInd];
-        L[i].a[0] = a.x; L[i].a[1] = a.y; L[i].a[2] = a.z; L[i].b[0] = b.x; L[i].b[1] = b.y; L[i].b[2] = b.z; L[i].c[0] = c.x; L[i].c[1] = c.y; L[i].c[2] = c.z;
-    }
-    light_triangles(pt, nT, L.data(), d->n_lights, d->n_triangles, [&](int idx) { const int li = d->triangles[idx].lightInd; return (li >= 0 && li < d->n_lights && bad[li]) ? -1 : li; }, out);
-}
-
-// The material table as the kernels read it, and the class word of every row (pt_bvh_build.h: pt_material_class_). Creation and
-// pt_scene_update_materials both pack through here; fn names the caller in the message of a refused texture window.
-static int pack_materials(const pt_material* materials, int nMats, int nTexels, const char* fn, std::vector<PMat>& mats, std::vector<uint32_t>& matClass) {
-    mats.resize((size_t)nMats); matClass.resize((size_t)nMats);
-    std::memset(mats.data(), 0, mats.size() * sizeof(PMat));
-    for (int i = 0; i < nMats; i++) {
-        const pt_material& m = materials[i];
-        PMat& p = mats[i];
-        p.type = m.type;
-        p.flags = (m.hasTexture ? kMatHasTexture : 0) | (m.hasTransMap ? kMatHasTransMap : 0) | (m.isSpecular ? kMatSpecular : 0) | (m.boundary ? kMatBoundary : 0);
-        p.priority = m.priority;
-        p.texStart = m.startInd; p.texW = m.width; p.texH = m.height;
-        if ((m.hasTexture || m.hasTransMap) && m.width > 0 && m.height > 0 &&
-            (m.startInd < 0 || (long long)m.startInd + (long long)m.width * m.height > nTexels))
-            return fail(-1, "%s: material %d texture window exceeds the texel array", fn, i);
-        p.roughness = m.roughness; p.ior = m.ior; p.transmission = m.transmission;
-        p.albedo[0] = m.albedo.x; p.albedo[1] = m.albedo.y; p.albedo[2] = m.albedo.z;
-        p.eta[0] = m.eta.x; p.eta[1] = m.eta.y; p.eta[2] = m.eta.z;
-        p.k[0] = m.k.x; p.k[1] = m.k.y; p.k[2] = m.k.z;
-        p.absorption[0] = m.absorption.x; p.absorption[1] = m.absorption.y; p.absorption[2] = m.absorption.z;
-        p.albedoOverPi[0] = m.albedo.x / kPi; p.albedoOverPi[1] = m.albedo.y / kPi; p.albedoOverPi[2] = m.albedo.z / kPi;   // cosine_f, reflectors.cuh:10-13
-        matClass[i] = pt_material_class_(m);
-    }
-    return 0;
 }
 
 // What a scene decides from its triangles' materials alone, from `used` = the class words of the rows its triangles use, OR-ed:
 // all four from scratch, since an edit can clear what another set.
 // SIMPLE scenes (pt_path.h): every triangle's material an untextured MAT_DIFFUSE that is neither boundary nor specular, in air
 // (material 0) that does not absorb — then the medium stack never changes and the dispatchers have one arm. noLeafTris: no triangle
-// carries MAT_LEAF. LEAN (pt_shade.h): additionally no triangle's material samples a texture. armless: pt_bvh_build.h.
+// carries MAT_LEAF. LEAN (pt_shade.h): additionally no triangle's material samples a texture. armless: pt_pack.h.
 static void apply_material_class(pt_scene* s, uint32_t used, const pt_material& air) {
     s->facts.simpleOk = air.absorption.x == 0.0f && air.absorption.y == 0.0f && air.absorption.z == 0.0f && !(used & kRowNotSimple);
     s->facts.noLeafTris = !(used & kTriLeaf);
@@ -105,46 +66,46 @@ static void apply_material_class(pt_scene* s, uint32_t used, const pt_material& 
 // the records the device builder packed into s->geo.nodes. Through the host: one download and one upload of the internal nodes.
 static int renumber_by_area(pt_scene* s, int nInternal, int rootRef) {
     s->upd.renumberMs = 0.0f;
+    if (nInternal <= 128 || rootRef != 0) return 0;
     const double t0 = wall_ms();
-        if (nInternal > 128 && rootRef == 0) {
-            std::vector<PNode> pn((size_t)nInternal);
-            HIP_OK(hipMemcpy(pn.data(), s->geo.nodes.p, (size_t)nInternal * sizeof(PNode), hipMemcpyDeviceToHost));
-            std::vector<float> area((size_t)nInternal, 0.0f);
-            std::vector<int> bfs; bfs.reserve((size_t)nInternal); bfs.push_back(0);
-            std::vector<uint8_t> seen((size_t)nInternal, 0); seen[0] = 1;
-            bool tree = true;
-            for (size_t q = 0; q < bfs.size() && tree; q++) {
-                const PNode& p = pn[bfs[q]];
-                const int32_t ref[2] = {p.left, p.right};
-                for (int k = 0; k < 2; k++) {
-                    if (ref[k] < 0) continue;
-                    if (ref[k] >= nInternal || seen[ref[k]]) { tree = false; break; }
-                    seen[ref[k]] = 1;
-                    const float* mn = k == 0 ? p.lmin : p.rmin; const float* mx = k == 0 ? p.lmax : p.rmax;
-                    const float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
-                    const float a = dx * dy + dy * dz + dz * dx;
-                    area[ref[k]] = std::isfinite(a) ? a : 0.0f;
-                    bfs.push_back(ref[k]);
-                }
-            }
-            if (tree && (int)bfs.size() == nInternal) {
-                // bfs[k]: k-th node in breadth-first order; sort those positions by area (stable: ties keep breadth-first order)
-                std::vector<int> order(bfs);
-                std::stable_sort(order.begin() + 1, order.end(), [&](int a, int b) { return area[a] > area[b]; });
-                std::vector<int> rank((size_t)nInternal);
-                for (int k = 0; k < nInternal; k++) rank[order[k]] = k;
-                std::vector<PNode> out((size_t)nInternal);
-                for (int i = 0; i < nInternal; i++) {
-                    PNode p = pn[i];
-                    if (p.left >= 0) p.left = rank[p.left];
-                    if (p.right >= 0) p.right = rank[p.right];
-                    out[rank[i]] = p;
-                }
-                HIP_OK(hipMemcpy(s->geo.nodes.p, out.data(), (size_t)nInternal * sizeof(PNode), hipMemcpyHostToDevice));
-            }
-            s->upd.renumberMs = (float)(wall_ms() - t0);
+    std::vector<PNode> pn((size_t)nInternal);
+    HIP_OK(hipMemcpy(pn.data(), s->geo.nodes.p, (size_t)nInternal * sizeof(PNode), hipMemcpyDeviceToHost));
+    std::vector<int> bfs; bfs.reserve((size_t)nInternal); bfs.push_back(0);      // bfs[k]: k-th node in breadth-first order,
+    std::vector<float> area; area.reserve((size_t)nInternal); area.push_back(0.0f);      // area[k]: of its box (the root's is not read)
+    std::vector<uint8_t> seen((size_t)nInternal, 0); seen[0] = 1;
+    bool tree = true;
+    for (size_t q = 0; q < bfs.size() && tree; q++) {
+        const PNode& p = pn[bfs[q]];
+        const int32_t ref[2] = {p.left, p.right};
+        for (int k = 0; k < 2; k++) {
+            if (ref[k] < 0) continue;
+            if (ref[k] >= nInternal || seen[ref[k]]) { tree = false; break; }
+            seen[ref[k]] = 1;
+            area.push_back(k == 0 ? order_area(p.lmin, p.lmax) : order_area(p.rmin, p.rmax));
+            bfs.push_back(ref[k]);
         }
+    }
+    if (tree && (int)bfs.size() == nInternal) {
+        const std::vector<int> byPlace = rank_by_area(area);
+        std::vector<int> rank((size_t)nInternal);
+        for (int k = 0; k < nInternal; k++) rank[bfs[k]] = byPlace[k];
+        std::vector<PNode> out((size_t)nInternal);
+        for (int i = 0; i < nInternal; i++) {
+            PNode p = pn[i];
+            if (p.left >= 0) p.left = rank[p.left];
+            if (p.right >= 0) p.right = rank[p.right];
+            out[rank[i]] = p;
+        }
+        HIP_OK(hipMemcpy(s->geo.nodes.p, out.data(), (size_t)nInternal * sizeof(PNode), hipMemcpyHostToDevice));
+    }
+    s->upd.renumberMs = (float)(wall_ms() - t0);
     return 0;
+}
+
+// The device scene's six pointers, at the scene's own buffers.
+static void point_ds(pt_scene* s) {
+    s->facts.ds.nodes = (const PNode*)s->geo.nodes.p; s->facts.ds.tris = (const PTri*)s->geo.tris.p; s->facts.ds.attrs = (const PAttr*)s->geo.attrs.p;
+    s->facts.ds.lights = (const PLight*)s->geo.lights.p; s->facts.ds.mats = (const PMat*)s->data.mats.p; s->facts.ds.textures = (const float4*)s->data.textures.p;
 }
 
 // What creation derives from the packed records in s->geo.nodes / tris / attrs / lights, and an update derives again: the device
@@ -158,8 +119,7 @@ static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef,
     s->facts.lightTri8 = 0ull;
     s->facts.nInternal = nInternal;
     s->facts.stackNeed = stackNeed;
-    s->facts.ds.nodes = (const PNode*)s->geo.nodes.p; s->facts.ds.tris = (const PTri*)s->geo.tris.p; s->facts.ds.attrs = (const PAttr*)s->geo.attrs.p;
-    s->facts.ds.lights = (const PLight*)s->geo.lights.p; s->facts.ds.mats = (const PMat*)s->data.mats.p; s->facts.ds.textures = (const float4*)s->data.textures.p;
+    point_ds(s);
     s->facts.ds.rootRef = rootRef;
     s->facts.ds.nLights = nLights; s->facts.ds.nTris = nT;
     s->facts.nMats = nMats; s->facts.nLightsPacked = std::max(nLights, 1);
@@ -179,7 +139,7 @@ static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef,
         HIP_OK(hipMemcpy(pt.data(), s->geo.tris.p, (size_t)nT * sizeof(PTri), hipMemcpyDeviceToHost));
         auto leafCount = [&](int first) {                      // triangles up to and including the one flagged last
             int k = first;
-            while (k < nT) { uint32_t w; memcpy(&w, (const char*)&pt[k] + 36, 4); k++; if (w & 0x80000000u) return k - first; }
+            while (k < nT) if (pt[k++].idx & 0x80000000u) return k - first;
             return 0;                                          // runs off the end: not a well-formed leaf
         };
         bool ok = rootRef < 0 ? (~rootRef == 0 && leafCount(0) == nT) : (rootRef == 0);
@@ -225,139 +185,30 @@ static int derive_layout(pt_scene* s, int nInternal, int stackNeed, int rootRef,
     return 0;
 }
 
-// Position i of the description, for vertex `what` of triangle (or light) `tri`; out of range: the message is set and ok cleared.
-static pt_float4 pos(const pt_scene_desc* d, int i, const char* what, int tri, bool& ok) {
-    if (i < 0 || i >= d->n_positions) { ok = false; fail(-1, "pt_scene_create: triangle %d %s index %d out of range", tri, what, i); return pt_float4{0, 0, 0, 0}; }
-    return d->positions[i];
+// What the device builder packs from: the scene's kept device arrays and the given positions (a host array unless onDevice).
+static pt_build_src_ build_src(const pt_scene* s, const void* positions, bool onDevice, int nT, int nMats, int nLights) {
+    pt_build_src_ src{};
+    src.positions = (const pt_float4*)positions; src.n_positions = s->kept.nPositions; src.positions_on_device = onDevice ? 1 : 0;
+    src.d_triangles = (const pt_triangle*)s->data.kTris.p; src.n_triangles = nT;
+    src.d_normals = (const pt_float4*)s->data.kNormals.p; src.n_normals = s->kept.nNormals;
+    src.d_uvs = (const pt_float2*)s->data.kUvs.p; src.n_uvs = s->kept.nUvs;
+    src.d_mat_types = (const int*)s->data.kTypes.p; src.n_materials = nMats;
+    src.d_light_tris = (const pt_triangle*)s->data.kLightTris.p; src.n_lights = nLights;
+    return src;
+}
+// The tree and the records of t->geo from src, on the device (pt_bvh_build.hip), the internal nodes then numbered by area. dLights:
+// t's PLight buffer, or NULL when the host packs the lights. fn names the caller when the tree is refused as too deep.
+static int build_geometry(pt_scene* t, const pt_build_src_& src, int leaf, void* dLights, const char* fn, pt_bvh_build_stats* stats, pt_build_out_& built) {
+    const size_t nT = (size_t)src.n_triangles;
+    if (int r = t->geo.nodes.ensure(nT * sizeof(PNode))) return r;
+    if (int r = t->geo.tris.ensure(nT * sizeof(PTri))) return r;
+    if (int r = t->geo.attrs.ensure(nT * sizeof(PAttr))) return r;
+    if (int r = pt_bvh_build_pack_(&src, leaf, t->geo.nodes.p, t->geo.tris.p, t->geo.attrs.p, dLights, &built, stats)) return r;
+    if (built.stack_need > 128) return fail(-1, "%s: BVH depth %d exceeds the reference's nodeStack[128] (integratorUtilities.cuh:89)", fn, built.stack_need);
+    return renumber_by_area(t, built.n_internal, built.root_ref);
 }
 
-// The three host-only parts of repack for a caller's own tree; each reads the caller's arrays and returns 0 or what it failed with.
-// Validates the nodes and numbers the internal ones; packs them into `nodes`. leafEnd[i]: packed triangle i is the last of its leaf.
-static int number_nodes(const pt_bvh_node* bvh, int nN, int nT, std::vector<PNode>& nodes, std::vector<uint8_t>& leafEnd, int& nInternal, int& rootRef) {
-    // --- internal nodes renumbered BREADTH-FIRST from the root, so PNodes [0, K) are the top of the
-    //     tree (the part every ray visits) and can be staged in LDS as one contiguous block ---
-    std::vector<int> internalId(nN, -1);
-    for (int i = 0; i < nN; i++) {
-        const pt_bvh_node& n = bvh[i];
-        if (n.primCount > 0) {
-            if (n.first < 0 || n.first + n.primCount > nT) return fail(-1, "pt_scene_create: leaf %d range [%d,+%d) out of bounds", i, n.first, n.primCount);
-        } else {
-            if (n.left < 0 || n.right < 0 || n.left >= nN || n.right >= nN) return fail(-1, "pt_scene_create: internal node %d has child out of range", i);
-        }
-    }
-    {
-        std::vector<int> queue;
-        if (bvh[0].primCount <= 0) { queue.push_back(0); internalId[0] = nInternal++; }
-        for (size_t q = 0; q < queue.size(); q++) {
-            const pt_bvh_node& n = bvh[queue[q]];
-            for (int c : {n.left, n.right}) {
-                if (bvh[c].primCount > 0) continue;
-                if (internalId[c] >= 0 || (int)queue.size() >= nN) return fail(-1, "pt_scene_create: BVH is not a tree");
-                internalId[c] = nInternal++;
-                queue.push_back(c);
-            }
-        }
-    }
-    // Scenes in HBM: the kernels keep PNodes [0, K) in LDS, so number the internal nodes by how often rays visit them rather
-    // than by level — a ray enters a box with a probability proportional to its surface area (the SAH's own estimate), and a
-    // child's box lies inside its parent's, so descending area (ties: breadth-first order) still numbers parents first.
-    // (Against plain breadth-first numbering: 82 k triangles 765 -> 729 ms at 128 spp, 263 k 387 -> 379 ms at 16 spp, 7.5 % fewer
-    // node fetches from global memory; profiles/r03_ab_node_order_area.log)
-    if (nInternal > 128) {
-        std::vector<float> area((size_t)nInternal, 0.0f);
-        for (int i = 0; i < nN; i++) {
-            if (internalId[i] < 0) continue;
-            const pt_bvh_node& n = bvh[i];
-            const float dx = n.aabbMAX.x - n.aabbMIN.x, dy = n.aabbMAX.y - n.aabbMIN.y, dz = n.aabbMAX.z - n.aabbMIN.z;
-            const float a = dx * dy + dy * dz + dz * dx;
-            area[internalId[i]] = std::isfinite(a) ? a : 0.0f;
-        }
-        std::vector<int> order((size_t)nInternal);
-        for (int i = 0; i < nInternal; i++) order[i] = i;
-        std::stable_sort(order.begin() + 1, order.end(), [&](int a, int b) { return area[a] > area[b]; });     // the root stays node 0
-        std::vector<int> rank((size_t)nInternal);
-        for (int k = 0; k < nInternal; k++) rank[order[k]] = k;
-        for (int i = 0; i < nN; i++) if (internalId[i] >= 0) internalId[i] = rank[internalId[i]];
-    }
-    auto childRef = [&](int c) -> int32_t { return bvh[c].primCount > 0 ? ~bvh[c].first : internalId[c]; };
-    nodes.assign(std::max(nInternal, 1), PNode{});
-    leafEnd.assign(nT, 0);
-    for (int i = 0; i < nN; i++) {
-        const pt_bvh_node& n = bvh[i];
-        if (n.primCount > 0) { leafEnd[n.first + n.primCount - 1] = 1; continue; }
-        if (internalId[i] < 0) continue;                       // unreachable from the root
-        PNode& p = nodes[internalId[i]];
-        const pt_bvh_node& L = bvh[n.left];
-        const pt_bvh_node& R = bvh[n.right];
-        p.lmin[0] = L.aabbMIN.x; p.lmin[1] = L.aabbMIN.y; p.lmin[2] = L.aabbMIN.z;
-        p.lmax[0] = L.aabbMAX.x; p.lmax[1] = L.aabbMAX.y; p.lmax[2] = L.aabbMAX.z;
-        p.rmin[0] = R.aabbMIN.x; p.rmin[1] = R.aabbMIN.y; p.rmin[2] = R.aabbMIN.z;
-        p.rmax[0] = R.aabbMAX.x; p.rmax[1] = R.aabbMAX.y; p.rmax[2] = R.aabbMAX.z;
-        p.left = childRef(n.left); p.right = childRef(n.right); p.pad0 = p.pad1 = 0;
-    }
-    rootRef = childRef(0);
-    return 0;
-}
-
-// stack need = the largest number of internal nodes on a root-to-leaf path (each can leave one
-// far child pending); also rejects cycles.
-static int stack_need(const pt_bvh_node* bvh, int nN, int& stackNeed) {
-    std::vector<std::pair<int, int>> st; st.push_back({0, 1});
-    size_t visited = 0;
-    while (!st.empty()) {
-        auto [i, depth] = st.back(); st.pop_back();
-        if (++visited > (size_t)nN) return fail(-1, "pt_scene_create: BVH is not a tree");
-        if (bvh[i].primCount > 0) continue;
-        stackNeed = std::max(stackNeed, depth);
-        st.push_back({bvh[i].left, depth + 1});
-        st.push_back({bvh[i].right, depth + 1});
-    }
-    if (stackNeed > 128) return fail(-1, "pt_scene_create: BVH depth %d exceeds the reference's nodeStack[128] (integratorUtilities.cuh:89)", stackNeed);
-    return 0;
-}
-
-// The triangles in leaf order and the hit attributes by original index, from the description's arrays.
-static int pack_triangles(const pt_scene_desc* d, const std::vector<uint8_t>& leafEnd, std::vector<PTri>& tris, std::vector<PAttr>& attrs) {
-    const int nT = d->n_triangles;
-    // --- triangles in leaf order ---
-    tris.resize(nT);
-    for (int i = 0; i < nT; i++) {
-        int idx = d->bvh_indices[i];
-        if (idx < 0 || idx >= nT) return fail(-1, "pt_scene_create: BVHindices[%d] = %d out of range", i, idx);
-        const pt_triangle& t = d->triangles[idx];
-        bool ok = true;
-        pt_float4 a = pos(d, t.aInd, "a", idx, ok), b = pos(d, t.bInd, "b", idx, ok), c = pos(d, t.cInd, "c", idx, ok);
-        if (!ok) return -1;
-        if (t.materialID < 0 || t.materialID >= d->n_materials) return fail(-1, "pt_scene_create: triangle %d material %d out of range", idx, t.materialID);
-        PTri& p = tris[i];
-        p.v0[0] = a.x; p.v0[1] = a.y; p.v0[2] = a.z;
-        p.e1[0] = b.x - a.x; p.e1[1] = b.y - a.y; p.e1[2] = b.z - a.z;      // trib - tria, integratorUtilities.cuh:13
-        p.e2[0] = c.x - a.x; p.e2[1] = c.y - a.y; p.e2[2] = c.z - a.z;      // tric - tria, :14
-        p.idx = (uint32_t)idx | (leafEnd[i] ? 0x80000000u : 0u);
-        p.material = t.materialID;
-        p.flags = pt_tri_flags_(d->materials[t.materialID].type);
-    }
-    // --- hit attributes by original index ---
-    attrs.resize(nT);
-    for (int i = 0; i < nT; i++) {
-        const pt_triangle& t = d->triangles[i];
-        PAttr& a = attrs[i];
-        const int ni[3] = {t.naInd, t.nbInd, t.ncInd}, ui[3] = {t.uvaInd, t.uvbInd, t.uvcInd};
-        float* nd[3] = {a.n0, a.n1, a.n2}; float* ud[3] = {a.uv0, a.uv1, a.uv2};
-        for (int k = 0; k < 3; k++) {
-            if (ni[k] < 0 || ni[k] >= d->n_normals || !d->normals) return fail(-1, "pt_scene_create: triangle %d normal index %d out of range (faces without vn must be given a normal by the loader)", i, ni[k]);
-            if (ui[k] < 0 || ui[k] >= d->n_uvs || !d->uvs) return fail(-1, "pt_scene_create: triangle %d uv index %d out of range", i, ui[k]);
-            nd[k][0] = d->normals[ni[k]].x; nd[k][1] = d->normals[ni[k]].y; nd[k][2] = d->normals[ni[k]].z;
-            ud[k][0] = d->uvs[ui[k]].x; ud[k][1] = d->uvs[ui[k]].y;
-        }
-        a.emission[0] = t.emission.x; a.emission[1] = t.emission.y; a.emission[2] = t.emission.z;
-        a.material = t.materialID;
-        a.lightInd = (t.lightInd >= 0 && t.lightInd < d->n_lights) ? t.lightInd : -51;
-    }
-    return 0;
-}
-
-// Re-pack the reference's data model for gfx950.
+// Re-pack the reference's data model for gfx950: pack, upload, derive_layout.
 // deviceLeaf < 0: the caller's BVH, packed on the host. deviceLeaf >= 0 (pt_scene_create_from_mesh): the tree is built AND
 // packed on the device (pt_bvh_build.hip) with that leaf size; d->bvh / d->bvh_indices are not read.
 // update: the scene is being updated in place (pt_scene_update_mesh): `s` is the staging scene whose buffers are swapped in on
@@ -377,26 +228,8 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (int r = stack_need(d->bvh, nN, stackNeed)) return r;
         if (int r = pack_triangles(d, leafEnd, tris, attrs)) return r;
     }
-    // --- lights ---
-    std::vector<PLight> lights(std::max(d->n_lights, 1));
-    std::memset(lights.data(), 0, lights.size() * sizeof(PLight));
-    for (int i = 0; i < d->n_lights; i++) {
-        const pt_triangle& t = d->lights[i];
-        bool ok = true;
-        pt_float4 a = pos(d, t.aInd, "a", i, ok), b = pos(d, t.bInd, "b", i, ok), c = pos(d, t.cInd, "c", i, ok);
-        if (!ok) return -1;
-        if (t.naInd < 0 || t.naInd >= d->n_normals) return fail(-1, "pt_scene_create: light %d normal index out of range", i);
-        PLight& L = lights[i];
-        L.a[0] = a.x; L.a[1] = a.y; L.a[2] = a.z; L.b[0] = b.x; L.b[1] = b.y; L.b[2] = b.z; L.c[0] = c.x; L.c[1] = c.y; L.c[2] = c.z;
-        L.na[0] = d->normals[t.naInd].x; L.na[1] = d->normals[t.naInd].y; L.na[2] = d->normals[t.naInd].z;
-        L.emission[0] = t.emission.x; L.emission[1] = t.emission.y; L.emission[2] = t.emission.z;
-        // area = 0.5f * length(cross3(b - a, c - a)) exactly as the kernels used to evaluate it per NEE sample: IEEE
-        // subtractions, cross = fma(p, q, -(r * s)), dot = fma(z, z', fma(y, y', x * x')), correctly rounded sqrt
-        const float ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z, vx = c.x - a.x, vy = c.y - a.y, vz = c.z - a.z;
-        const float cx = fmaf(uy, vz, -(uz * vy)), cy = fmaf(uz, vx, -(ux * vz)), cz = fmaf(ux, vy, -(uy * vx));
-        L.area = 0.5f * sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
-    }
-    // --- materials ---
+    std::vector<PLight> lights;
+    if (int r = pack_lights(d, lights)) return r;
     std::vector<PMat> mats; std::vector<uint32_t> matClass;
     if (int r = pack_materials(d->materials, d->n_materials, d->n_texels, "pt_scene_create", mats, matClass)) return r;
     {
@@ -412,9 +245,6 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (int r = upload(s->geo.tris, tris.data(), tris.size() * sizeof(PTri))) return r;
         if (int r = upload(s->geo.attrs, attrs.data(), attrs.size() * sizeof(PAttr))) return r;
     } else {
-        if (int r = s->geo.nodes.ensure((size_t)nT * sizeof(PNode))) return r;
-        if (int r = s->geo.tris.ensure((size_t)nT * sizeof(PTri))) return r;
-        if (int r = s->geo.attrs.ensure((size_t)nT * sizeof(PAttr))) return r;
         std::vector<int> types(d->n_materials);
         for (int i = 0; i < d->n_materials; i++) types[i] = d->materials[i].type;
         // what the builder packs from stays on the device with the scene: pt_scene_update_vertices rebuilds from it
@@ -425,20 +255,12 @@ static int repack(pt_scene* s, const pt_scene_desc* d, int deviceLeaf = -1, pt_b
         if (int r = upload(s->data.kLightTris, d->lights, d->lights ? (size_t)std::max(d->n_lights, 0) * sizeof(pt_triangle) : 0)) return r;
         if (int r = upload(s->data.posCur, d->positions, (size_t)d->n_positions * sizeof(pt_float4))) return r;      // the motion pass reads them
         s->kept.deviceLeaf = deviceLeaf; s->kept.nPositions = d->n_positions; s->kept.nNormals = d->normals ? std::max(d->n_normals, 0) : 0; s->kept.nUvs = d->uvs ? std::max(d->n_uvs, 0) : 0;
-        pt_build_src_ src{};
-        src.positions = d->positions; src.n_positions = d->n_positions; src.positions_on_device = 0;
-        src.d_triangles = (const pt_triangle*)s->data.kTris.p; src.n_triangles = nT;
-        src.d_normals = (const pt_float4*)s->data.kNormals.p; src.n_normals = s->kept.nNormals;
-        src.d_uvs = (const pt_float2*)s->data.kUvs.p; src.n_uvs = s->kept.nUvs;
-        src.d_mat_types = (const int*)s->data.kTypes.p; src.n_materials = d->n_materials;
-        src.d_light_tris = (const pt_triangle*)s->data.kLightTris.p; src.n_lights = d->n_lights;
+        pt_build_src_ src = build_src(s, d->positions, false, nT, d->n_materials, d->n_lights);
         if (update) { src.pool = &s->spare.pool.p; src.pool_bytes = &s->spare.pool.bytes; }     // (creation allocates and frees its pool, as it always did)
-        int out5[5] = {0, 0, 0, 0, 0};
-        if (int r = pt_bvh_build_pack_(&src, deviceLeaf, s->geo.nodes.p, s->geo.tris.p, s->geo.attrs.p, nullptr, out5, buildStats)) return r;
-        nInternal = out5[0]; stackNeed = out5[1]; rootRef = out5[2];
-        if (out5[3]) s->facts.armless = true;
-        if (stackNeed > 128) return fail(-1, "pt_scene_create_from_mesh: BVH depth %d exceeds the reference's nodeStack[128] (integratorUtilities.cuh:89)", stackNeed);
-        if (int r = renumber_by_area(s, nInternal, rootRef)) return r;
+        pt_build_out_ built{};
+        if (int r = build_geometry(s, src, deviceLeaf, nullptr, "pt_scene_create_from_mesh", buildStats, built)) return r;
+        nInternal = built.n_internal; stackNeed = built.stack_need; rootRef = built.root_ref;
+        if (built.armless) s->facts.armless = true;
     }
     if (int r = upload(s->geo.lights, lights.data(), lights.size() * sizeof(PLight))) return r;
     if (int r = upload(s->data.mats, mats.data(), mats.size() * sizeof(PMat))) return r;
@@ -505,9 +327,13 @@ static void stage_begin(pt_scene* s, pt_scene& t) {
     t.dev.id = s->dev.id; t.dev.numCU = s->dev.numCU;
     t.geo = take(s->spare.geo); t.data.kNormals = take(s->spare.normals); t.spare.pool = take(s->spare.pool);
 }
-static void stage_end(pt_scene* s, pt_scene& t) {
+// The end of an update that began at t0 and came to r: the staging scene's buffers go back; a successful one is timed. Returns r.
+static int stage_end(pt_scene* s, pt_scene& t, int r, double t0, pt_bvh_build_stats* stats) {
     s->spare.geo = t.geo; s->spare.normals = t.data.kNormals; s->spare.pool = t.spare.pool;
     for (DevBuf Data::*m : kMeshOnly) (t.data.*m).release();      // an update of the whole mesh: the old ones (or, failed, the new ones)
+    if (r == 0) s->upd.updateMs = (float)(wall_ms() - t0);
+    if (r == 0 && stats) stats->total_ms = s->upd.updateMs;
+    return r;
 }
 // mesh: materials, textures and the builder's inputs are the staging scene's too (pt_scene_update_mesh); otherwise only the
 // geometry and, if the update brought normals, those.
@@ -520,8 +346,7 @@ static void adopt_geometry(pt_scene* s, pt_scene& t, bool mesh, bool normals) {
         s->kept = t.kept;
     }
     s->facts = t.facts;
-    s->facts.ds.nodes = (const PNode*)s->geo.nodes.p; s->facts.ds.tris = (const PTri*)s->geo.tris.p; s->facts.ds.attrs = (const PAttr*)s->geo.attrs.p;
-    s->facts.ds.lights = (const PLight*)s->geo.lights.p; s->facts.ds.mats = (const PMat*)s->data.mats.p; s->facts.ds.textures = (const float4*)s->data.textures.p;
+    point_ds(s);
     s->last.forget();
     s->upd.renumberMs = t.upd.renumberMs;
     s->upd.generation++;
@@ -530,9 +355,6 @@ static void adopt_geometry(pt_scene* s, pt_scene& t, bool mesh, bool normals) {
 // The per-frame path: everything but the positions (and the normals, if given) is the scene's own device copy.
 static int update_vertices_staged(pt_scene* s, pt_scene& t, const void* pos, const void* nrm, bool onDevice, pt_bvh_build_stats* stats) {
     const int nT = s->facts.nTrisPacked, nL = s->facts.ds.nLights;
-    if (int r = t.geo.nodes.ensure((size_t)nT * sizeof(PNode))) return r;
-    if (int r = t.geo.tris.ensure((size_t)nT * sizeof(PTri))) return r;
-    if (int r = t.geo.attrs.ensure((size_t)nT * sizeof(PAttr))) return r;
     if (int r = t.geo.lights.ensure((size_t)std::max(nL, 1) * sizeof(PLight))) return r;
     const void* normals = s->data.kNormals.p;
     if (nrm) {
@@ -541,21 +363,13 @@ static int update_vertices_staged(pt_scene* s, pt_scene& t, const void* pos, con
         if (bytes) HIP_OK(hipMemcpy(t.data.kNormals.p, nrm, bytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         normals = t.data.kNormals.p;
     }
-    pt_build_src_ src{};
-    src.positions = (const pt_float4*)pos; src.n_positions = s->kept.nPositions; src.positions_on_device = onDevice ? 1 : 0;
-    src.d_triangles = (const pt_triangle*)s->data.kTris.p; src.n_triangles = nT;
-    src.d_normals = (const pt_float4*)normals; src.n_normals = s->kept.nNormals;
-    src.d_uvs = (const pt_float2*)s->data.kUvs.p; src.n_uvs = s->kept.nUvs;
-    src.d_mat_types = (const int*)s->data.kTypes.p; src.n_materials = s->facts.nMats;
-    src.d_light_tris = (const pt_triangle*)s->data.kLightTris.p; src.n_lights = nL;
+    pt_build_src_ src = build_src(s, pos, onDevice, nT, s->facts.nMats, nL);
+    src.d_normals = (const pt_float4*)normals;
     src.pool = &t.spare.pool.p; src.pool_bytes = &t.spare.pool.bytes;
-    int out5[5] = {0, 0, 0, 0, 0};
-    if (int r = pt_bvh_build_pack_(&src, s->kept.deviceLeaf, t.geo.nodes.p, t.geo.tris.p, t.geo.attrs.p, t.geo.lights.p, out5, stats)) return r;
-    const int nInternal = out5[0], stackNeed = out5[1], rootRef = out5[2];
-    if (stackNeed > 128) return fail(-1, "pt_scene_update_vertices: BVH depth %d exceeds the reference's nodeStack[128] (integratorUtilities.cuh:89)", stackNeed);
+    pt_build_out_ built{};
+    if (int r = build_geometry(&t, src, s->kept.deviceLeaf, t.geo.lights.p, "pt_scene_update_vertices", stats, built)) return r;
     // what creation decides from the triangles' materials alone stands: neither changed
     t.facts.armless = s->facts.armless; t.facts.simpleOk = s->facts.simpleOk; t.facts.noLeafTris = s->facts.noLeafTris; t.facts.leanOk = s->facts.leanOk;
-    if (int r = renumber_by_area(&t, nInternal, rootRef)) return r;
     std::vector<PLight> hostLights((size_t)std::max(nL, 1));
     std::vector<int32_t> lightInd;
     if (nT <= 128) {                       // the scenes whose lights' triangles derive_layout looks for: read the records the device made
@@ -565,7 +379,7 @@ static int update_vertices_staged(pt_scene* s, pt_scene& t, const void* pos, con
         lightInd.resize((size_t)nT);
         for (int i = 0; i < nT; i++) lightInd[i] = at[i].lightInd;
     }
-    return derive_layout(&t, nInternal, stackNeed, rootRef, nT, nL, nL > 0, s->facts.nMats, hostLights.data(), lightInd.data(), (int)lightInd.size());
+    return derive_layout(&t, built.n_internal, built.stack_need, built.root_ref, nT, nL, nL > 0, s->facts.nMats, hostLights.data(), lightInd.data(), (int)lightInd.size());
 }
 
 static int update_vertices(pt_scene* s, const void* pos, int nPos, const void* nrm, int nNrm, bool onDevice, pt_bvh_build_stats* stats, const char* fn) {
@@ -592,10 +406,7 @@ static int update_vertices(pt_scene* s, const void* pos, int nPos, const void* n
         std::swap(s->data.posCur, s->data.posPrev); s->upd.hasMotion = true;
         adopt_geometry(s, t, false, nrm != nullptr);
     }
-    stage_end(s, t);
-    if (r == 0) s->upd.updateMs = (float)(wall_ms() - t0);
-    if (r == 0 && stats) stats->total_ms = s->upd.updateMs;
-    return r;
+    return stage_end(s, t, r, t0, stats);
 }
 
 int pt_scene_update_vertices(pt_scene* s, const pt_float4* positions, int n_positions, const pt_float4* normals, int n_normals, pt_bvh_build_stats* stats) {
@@ -619,10 +430,7 @@ int pt_scene_update_mesh(pt_scene* s, const pt_scene_desc* d, int max_leaf_size,
     stage_begin(s, t);
     const int r = repack(&t, d, max_leaf_size, stats, true);
     if (r == 0) adopt_geometry(s, t, true, true);
-    stage_end(s, t);
-    if (r == 0) s->upd.updateMs = (float)(wall_ms() - t0);
-    if (r == 0 && stats) stats->total_ms = s->upd.updateMs;
-    return r;
+    return stage_end(s, t, r, t0, stats);
 }
 
 // ---- material and emission edits: pt_scene_update_materials / pt_scene_update_emission --------------------------------------------
@@ -640,6 +448,50 @@ static void edit_done(pt_scene* s, double t0) {
     s->upd.updateMs = (float)(wall_ms() - t0);
 }
 
+// ---- the edit kernels: what the pack kernels (pt_bvh_build.hip) would write for the edited description, without the tree, the
+// positions or the builder's arrays. Both are launched on the null stream; every pointer is a device pointer.
+// One thread per packed triangle: its flags word from its material row's class (pt_material_class_), the only word of the record a
+// material decides; the classes are OR-ed over the wave with one ballot per class bit and leave it in one atomicOr into *orOut, which
+// the caller zeroes. Lanes past the end carry class 0 and stay for the ballots.
+constexpr int kEditBlock = 256;
+constexpr uint32_t kClassBits[4] = {kTriLeaf, kRowTextured, kRowNotSimple, kTriArmless};
+__global__ void k_edit_materials(PTri* tris, int n, const uint32_t* cls, int nMats, uint32_t* orOut) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c = 0u;
+    if (i < n) {
+        const int mat = tris[i].material;                      // creation refused an index outside the table
+        if (mat >= 0 && mat < nMats) c = cls[mat];
+        tris[i].flags = c & kTriLeaf;
+    }
+    uint32_t w = 0u;
+    for (int b = 0; b < 4; b++)
+        if (__ballot((c & kClassBits[b]) != 0u)) w |= kClassBits[b];
+    if ((threadIdx.x & 63) == 0 && w) atomicOr(orOut, w);
+}
+// Thread i < n: attribute i (original triangle index, as the kept triangles are) takes its light's emission if that light is edited;
+// thread i < nLights: light i itself. emission / on: the edit as a table by light (on[li] != 0: light li is edited), so that a
+// triangle does one lookup. keptTris / keptLightTris (both NULL for a scene without a device builder): the pt_triangle arrays the
+// builder packs from, whose `emission` gets all four floats.
+__global__ void k_edit_emission(PAttr* attrs, int n, PLight* lights, int nLights, const pt_float4* emission, const int32_t* on,
+                                pt_triangle* keptTris, pt_triangle* keptLightTris) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int li = attrs[i].lightInd;
+        if (li >= 0 && li < nLights && on[li]) {
+            const pt_float4 e = emission[li];
+            attrs[i].emission[0] = e.x; attrs[i].emission[1] = e.y; attrs[i].emission[2] = e.z;
+            if (keptTris) keptTris[i].emission = e;
+        }
+    }
+    if (i < nLights && on[i]) {
+        const pt_float4 e = emission[i];
+        lights[i].emission[0] = e.x; lights[i].emission[1] = e.y; lights[i].emission[2] = e.z;
+        if (keptLightTris) keptLightTris[i].emission = e;
+    }
+}
+static int edit_blocks(int n) { return std::max(1, (n + kEditBlock - 1) / kEditBlock); }
+static int launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : fail(-2, "%s", hipGetErrorString(e)); }
+
 int pt_scene_update_materials(pt_scene* s, const pt_material* materials, int n_materials) {
     const char* fn = "pt_scene_update_materials";
     if (!s) return fail(-1, "%s: null scene", fn);
@@ -656,7 +508,8 @@ int pt_scene_update_materials(pt_scene* s, const pt_material* materials, int n_m
     uint32_t* dClass = (uint32_t*)((char*)s->upd.edit.p + classOff);
     HIP_OK(hipMemset(dUsed, 0, sizeof(uint32_t)));
     HIP_OK(hipMemcpy(dClass, matClass.data(), classBytes, hipMemcpyHostToDevice));
-    if (int r = pt_edit_materials_(s->geo.tris.p, s->facts.nTrisPacked, dClass, n_materials, dUsed)) return r;
+    hipLaunchKernelGGL(k_edit_materials, dim3(edit_blocks(s->facts.nTrisPacked)), dim3(kEditBlock), 0, nullptr, (PTri*)s->geo.tris.p, s->facts.nTrisPacked, dClass, n_materials, dUsed);
+    if (int r = launched()) return r;
     uint32_t used = 0u;
     HIP_OK(hipMemcpy(&used, dUsed, sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(s->data.mats.p, mats.data(), mats.size() * sizeof(PMat), hipMemcpyHostToDevice));
@@ -693,9 +546,9 @@ int pt_scene_update_emission(pt_scene* s, int n, const int32_t* light_indices, c
         HIP_OK(hipMemcpy(dTable, table.data(), tableBytes, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(dOn, on.data(), onBytes, hipMemcpyHostToDevice));
         const bool kept = s->kept.deviceLeaf >= 0;       // ... and what the next vertex update packs attributes and lights from
-        if (int r = pt_edit_emission_(s->geo.attrs.p, nT, s->geo.lights.p, nL, dTable, dOn, kept ? (pt_triangle*)s->data.kTris.p : nullptr,
-                                      kept ? (pt_triangle*)s->data.kLightTris.p : nullptr))
-            return r;
+        hipLaunchKernelGGL(k_edit_emission, dim3(edit_blocks(std::max(nT, nL))), dim3(kEditBlock), 0, nullptr, (PAttr*)s->geo.attrs.p, nT, (PLight*)s->geo.lights.p, nL,
+                           dTable, dOn, kept ? (pt_triangle*)s->data.kTris.p : nullptr, kept ? (pt_triangle*)s->data.kLightTris.p : nullptr);
+        if (int r = launched()) return r;
         HIP_OK(hipDeviceSynchronize());
     }
     edit_done(s, t0);
@@ -736,13 +589,16 @@ int pt_light_triangles(const pt_scene_desc* d, int32_t* out) {
         const pt_triangle& t = d->triangles[idx];
         if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions)
             return fail(-1, "pt_light_triangles: triangle %d position index out of range", idx);
-        const pt_float4 a = d->positions[t.aInd], b = d->positions[t.bInd], c = d->positions[t.cInd];
-        PTri& p = pt[i];
-        p.v0[0] = a.x; p.v0[1] = a.y; p.v0[2] = a.z;
-        p.e1[0] = b.x - a.x; p.e1[1] = b.y - a.y; p.e1[2] = b.z - a.z;
-        p.e2[0] = c.x - a.x; p.e2[1] = c.y - a.y; p.e2[2] = c.z - a.z;
-        p.idx = (uint32_t)idx; p.material = t.materialID; p.flags = 0u;
+        pt[i] = make_tri(d->positions[t.aInd], d->positions[t.bInd], d->positions[t.cInd], idx, false, t.materialID, PT_MAT_DIFFUSE);      // (no leaf ends, flags 0: only v0, e1, e2 are compared)
     }
-    light_triangles(pt.data(), d->n_triangles, d, out);
+    std::vector<PLight> L((size_t)std::max(d->n_lights, 1), PLight{});
+    std::vector<uint8_t> bad((size_t)std::max(d->n_lights, 1), 0);      // a light whose vertex indices are out of range gets -1
+    for (int i = 0; i < d->n_lights; i++) {
+        const pt_triangle& t = d->lights[i];
+        if (t.aInd < 0 || t.aInd >= d->n_positions || t.bInd < 0 || t.bInd >= d->n_positions || t.cInd < 0 || t.cInd >= d->n_positions) { bad[i] = 1; continue; }
+        L[i] = make_light(d->positions[t.aInd], d->positions[t.bInd], d->positions[t.cInd], pt_float4{0, 0, 0, 0}, t.emission);
+    }
+    light_triangles(pt.data(), d->n_triangles, L.data(), d->n_lights, d->n_triangles,
+                    [&](int idx) { const int li = d->triangles[idx].lightInd; return (li >= 0 && li < d->n_lights && bad[li]) ? -1 : li; }, out);
     return 0;
 }
