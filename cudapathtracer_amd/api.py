@@ -228,6 +228,9 @@ def lib():
     L.pt_query_radiance_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
     L.pt_query_radiance_moments.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32]
     L.pt_query_radiance_moments_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_query_irradiance.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32]
+    L.pt_query_irradiance_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_query_irradiance_rays_device.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
     L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -885,6 +888,42 @@ class Scene:
         flags = QUERY_STREAM_PAD if stream_pad else 0
         return tuple(self._query("query_radiance_moments", rays, [_F4, _F4], lambda r, o: (
             r, spp, batch_spp, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, o[0], o[1], flags), empty=(True, True)))
+
+    def query_irradiance(self, records, lanes, spp_lane, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, first_stream=0,
+                         moments=False, flags=0):
+        """pt_query_irradiance: cosine-sampled light at surface points. records is [n, 8] float32 (point, max_t, unit normal, pad:
+        rays.irradiance_records, rays.records_from_surfaces); each record runs on `lanes` (1, 2, 4 .. 64) lanes of a wave, lane l of
+        record i on stream first_stream + i * lanes + l of `seed` (with flags = QUERY_STREAM_PAD: the record's pad word for i), spp_lane
+        samples per lane. Returns S, [n, 4] float32 (the rgb sums of the record's lanes * spp_lane samples, 0), or with moments (S, Q),
+        Q the sum of the squared lane sums and Q.w = lanes: denoise_var(S.reshape(h, w, 4), Q.reshape(h, w, 4), lanes * spp_lane, lanes,
+        ...) reads the pair. Irradiance is pi * S / (lanes * spp_lane). numpy in, numpy out (host form); a torch tensor on the scene's
+        device in, tensors out, on torch's current stream with no host copy."""
+        s, q = self._query("query_irradiance", records, [_F4, _F4 if moments else None], lambda r, o: (
+            r, lanes, spp_lane, max_depth, integrator, 1 if use_mis else 0, seed, first_stream, o[0], o[1], flags), empty=(True, True))
+        return (s, q) if moments else s
+
+    def query_irradiance_rays(self, records, lanes, seed=SEED, first_stream=0, draw_offset=None, flags=0):
+        """pt_query_irradiance_rays_device: the rays query_irradiance's samples start from, [n * lanes, 8] float32: ray i * lanes + l is
+        lane l of record i, made of draws draw_offset[i * lanes + l] and the next of that lane's stream ([n * lanes] uint32 or int32;
+        None: the lane's first sample), with the record's max_t and, in its pad word, what the lane adds to first_stream:
+        query_radiance(rays, 1, ..., first_stream=first_stream, stream_pad=True) is such a sample's radiance. A torch tensor of records
+        on the scene's device gives a tensor, on torch's current stream; numpy records are copied up and the rays come back as numpy."""
+        import torch
+        is_torch, r, n = self._query_rays("query_irradiance_rays", records)
+        dev = r.device if is_torch else torch.device("cuda", torch.cuda.current_device())
+        d = r if is_torch else torch.from_numpy(r if r.flags.writeable else r.copy()).to(dev)
+        m = n * lanes if lanes > 0 else 0
+        off = None
+        if draw_offset is not None:
+            off = draw_offset if hasattr(draw_offset, "data_ptr") else torch.from_numpy(np.ascontiguousarray(draw_offset).astype(np.int32).reshape(-1))
+            off = off.to(device=dev, dtype=torch.int32).contiguous()
+            if off.numel() != m:
+                raise PtError("query_irradiance_rays: draw_offset has %d entries for %d rays" % (off.numel(), m))
+        out = torch.empty((m, 8), dtype=torch.float32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and n else None
+        _check(lib().pt_query_irradiance_rays_device(self.h, n, ptr(d), lanes, seed, first_stream, ptr(off), ptr(out), flags,
+                                                     torch.cuda.current_stream(dev).cuda_stream or None), "pt_query_irradiance_rays_device")
+        return out if is_torch else out.cpu().numpy()
 
     def query_guides(self, rays, max_links=0, links=False):
         """pt_query_guides: render_aovs_centre's guides for each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be

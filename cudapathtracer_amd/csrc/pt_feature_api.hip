@@ -1,6 +1,6 @@
 // pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
 // and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_query_guides.hip,
-// pt_radiance.hip, pt_radiance_moments.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
+// pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -423,6 +423,80 @@ int pt_query_radiance_moments(pt_scene* s, int n, const pt_ray* rays, int spp, i
     return staged_query(s->feat.queryOut, n, rays, {{out_rgba_sum, bytes}, {out_sq_sum, bytes}}, [&](const void* dRays, void* const* d) {
         return query_radiance(s, n, dRays, spp, batch_spp, max_depth, integrator, use_mis, seed, first_stream, d[0], d[1], flags, nullptr);
     });
+}
+
+// Irradiance queries (pt_irradiance.hip: irradiance_kernel, irradiance_rays_kernel). Every message under the caller's name, all before
+// any HIP call, in the header's order; n == 0 returns before the scene or anything else is looked at. walk: pt_query_irradiance's
+// checks; else pt_query_irradiance_rays_device's, which has no samples, integrator or sums (`out` is its rays buffer).
+static int check_irradiance_args(const char* fn, bool walk, pt_scene* s, int n, const void* recs, const void* out, const void* sq, int lanes,
+                                 int sppLane, int integrator, uint32_t firstStream, uint32_t flags) {
+    if (n < 0 || (long long)n * lanes > (1ll << 28)) return fail(-1, "%s: n %d at %d lanes must be 0..%d lanes in all", fn, n, lanes, 1 << 28);
+    if (n == 0) return 0;
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!recs) return fail(-1, "%s: null records", fn);
+    if (!out) return fail(-1, "%s: null output buffer", fn);
+    if (lanes < 1 || lanes > 64 || (lanes & (lanes - 1))) return fail(-1, "%s: lanes %d must be a power of two in 1..64", fn, lanes);
+    if (walk) {
+        if (sppLane < 1 || (long long)lanes * sppLane > (1ll << 22))
+            return fail(-1, "%s: spp_lane %d at %d lanes must be 1..%d samples a record", fn, sppLane, lanes, 1 << 22);
+        if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
+            return fail(-1, "%s: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", fn, integrator);
+        if (sq && lanes == 1) return fail(-1, "%s: sq_sum needs lanes >= 2: a lane's sum is one batch", fn);
+    }
+    if (flags & PT_QUERY_REORDER) return fail(-1, "%s: PT_QUERY_REORDER is not taken here: a path leaves its first ray's order at once", fn);
+    if (flags & ~PT_QUERY_STREAM_PAD) return fail(-1, "%s: unknown flag bits 0x%x", fn, flags & ~PT_QUERY_STREAM_PAD);
+    const unsigned long long end = (unsigned long long)firstStream + (unsigned long long)n * (unsigned)lanes;
+    if (!(flags & PT_QUERY_STREAM_PAD) && end > (1ull << 31)) return fail(-1, "%s: streams %u .. %llu pass 2^31", fn, firstStream, end - 1ull);
+    return 0;
+}
+
+static int log2_lanes(int lanes) { return __builtin_ctz((unsigned)lanes); }
+
+// The material class picks the instantiation as query_radiance picks it, from the same two options.
+static int query_irradiance(pt_scene* s, int n, const void* dRecs, int lanes, int sppLane, int maxDepth, int integrator, int useMIS, uint64_t seed,
+                            uint32_t firstStream, void* dOut, void* dSq, uint32_t flags, hipStream_t stream) {
+    const bool simple = s->facts.simpleOk && s->opt.simpleWanted;
+    const bool lean = s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !simple;
+    const int log2L = log2_lanes(lanes);
+    const int blocks = feature_blocks(irradiance_tiles(n, log2L), s->dev.numCU, irradiance_waves_per_simd(integrator, simple, lean));
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_irradiance(s->facts.ds, integrator, simple, lean, n, dRecs, log2L, (const uint32_t*)s->data.jump.p, seed, firstStream,
+                             (flags & PT_QUERY_STREAM_PAD) != 0, sppLane, maxDepth, useMIS, blocks, dOut, dSq, spill, stream));
+    return 0;
+}
+
+int pt_query_irradiance_device(pt_scene* s, int n, const void* d_records, int lanes, int spp_lane, int max_depth, int integrator, int use_mis,
+                               uint64_t seed, uint32_t first_stream, void* d_rgba_sum, void* d_sq_sum, unsigned flags, void* stream) {
+    const char* fn = "pt_query_irradiance";
+    if (int r = check_irradiance_args(fn, true, s, n, d_records, d_rgba_sum, d_sq_sum, lanes, spp_lane, integrator, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    return query_irradiance(s, n, d_records, lanes, spp_lane, max_depth, integrator, use_mis, seed, first_stream, d_rgba_sum, d_sq_sum, flags,
+                            (hipStream_t)stream);
+}
+
+int pt_query_irradiance(pt_scene* s, int n, const pt_ray* records, int lanes, int spp_lane, int max_depth, int integrator, int use_mis, uint64_t seed,
+                        uint32_t first_stream, float* out_rgba_sum, float* out_sq_sum, unsigned flags) {
+    const char* fn = "pt_query_irradiance";
+    if (int r = check_irradiance_args(fn, true, s, n, records, out_rgba_sum, out_sq_sum, lanes, spp_lane, integrator, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    const size_t bytes = (size_t)n * sizeof(float4);
+    return staged_query(s->feat.queryOut, n, records, {{out_rgba_sum, bytes}, {out_sq_sum, bytes}}, [&](const void* dRecs, void* const* d) {
+        return query_irradiance(s, n, dRecs, lanes, spp_lane, max_depth, integrator, use_mis, seed, first_stream, d[0], d[1], flags, nullptr);
+    });
+}
+
+int pt_query_irradiance_rays_device(pt_scene* s, int n, const void* d_records, int lanes, uint64_t seed, uint32_t first_stream,
+                                    const void* d_draw_offset, void* d_rays, unsigned flags, void* stream) {
+    const char* fn = "pt_query_irradiance_rays_device";
+    if (int r = check_irradiance_args(fn, false, s, n, d_records, d_rays, nullptr, lanes, 1, PT_UNIDIRECTIONAL, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    HIP_OK(launch_irradiance_rays(n, d_records, log2_lanes(lanes), (const uint32_t*)s->data.jump.p, seed, first_stream,
+                                  (flags & PT_QUERY_STREAM_PAD) != 0, d_draw_offset, d_rays, (hipStream_t)stream));
+    return 0;
 }
 
 // Guide queries (pt_query_guides.hip: query_guides_kernel, query_guides_chain_kernel). Every message under pt_query_guides, all

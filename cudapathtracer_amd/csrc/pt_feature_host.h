@@ -1,5 +1,5 @@
 // pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip) and of the ray
-// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip): the tiling and block count every one of them is
+// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip): the tiling and block count every one of them is
 // launched with, each kernel's waves per SIMD, and the launchers pt_feature_api.hip calls. The kernels' shared pieces are in
 // pt_feature.h, the radiance kernels' walk in pt_radiance.h.
 #pragma once
@@ -46,7 +46,17 @@ constexpr int radiance_waves_per_simd(int integrator, bool simple, bool lean) { 
 //   naive, generic   4: 97 / 0     (registers: 103 / 0)                 MIS, generic   4: 128 / 12   (registers: 128 / 28)
 // LDS: 23 KB in the SIMPLE kernels (6 workgroups: 138 KB), 27 KB in the others (5: 135 KB).
 constexpr int radiance_moments_waves_per_simd(int integrator, bool simple, bool lean) { return simple ? 6 : lean ? 5 : 4; }
-constexpr int kQueryGuidesWavesPerSimd = 8;       // query_guides_kernel: 55 VGPRs, 8 x 16 KB of LDS, as the centre pass
+// irradiance_kernel<INTEG, SIMPLE, LEAN> (pt_irradiance.hip): radiance_kernel's settings and LDS; the lanes' tree is wave shuffles
+// after the walk. VGPRs / scratch bytes per lane at the setting, and radiance_kernel's beside them: the sample's start, which there
+// is two loads, is here a square root, a sincos and a basis, and four of the six kernels pay for it in 12 to 20 bytes of scratch
+// (tests/test_query_irradiance_api.py pins the table):
+//   naive, SIMPLE    6: 80 / 16    (79 / 0)                                 MIS, SIMPLE    6: 80 / 40    (80 / 28)
+//   naive, LEAN      5: 95 / 20    (94 / 0)                                 MIS, LEAN      5: 96 / 100   (96 / 84)
+//   naive, generic   4: 100 / 0    (96 / 0)                                 MIS, generic   4: 128 / 8    (128 / 12)
+constexpr int irradiance_waves_per_simd(int integrator, bool simple, bool lean) { return radiance_waves_per_simd(integrator, simple, lean); }
+// Its tiles: n records of 1 << log2L lanes each, 64 lanes a tile (n << log2L is at most 1 << 28).
+constexpr int irradiance_tiles(int n, int log2L) { return ((n << log2L) + 63) / 64; }
+constexpr int kQueryGuidesWavesPerSimd = 8;      // query_guides_kernel: 55 VGPRs, 8 x 16 KB of LDS, as the centre pass
 constexpr int kQueryGuidesChainWavesPerSimd = 6;  // query_guides_chain_kernel: 60 VGPRs, 23 KB of LDS: 7 workgroups would need 161 KB
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
 
@@ -94,6 +104,16 @@ hipError_t launch_radiance(const DeviceScene& S, int integrator, bool simple, bo
 hipError_t launch_radiance_moments(const DeviceScene& S, int integrator, bool simple, bool lean, int n, const void* rays, const uint32_t* jump,
                                    unsigned long long seed, uint32_t firstStream, bool streamPad, int spp, int batchSpp, int maxDepth, int useMIS,
                                    int blocks, void* out, void* sq, int32_t* spill, hipStream_t stream);
+// pt_irradiance.hip: irradiance_kernel<integrator, simple, lean> on n records (pt_ray: point, max_t, unit normal, pad) of 1 << log2L
+// lanes each, lane l of record i on stream firstStream + (i << log2L) + l of `seed` (streamPad: the record's pad word for i), sppLane
+// samples per lane: out[i] = (the adjacent-pair tree over the lanes' sums, 0), sq[i] (NULL ok) = (the tree over their squares, lanes).
+// blocks: feature_blocks of irradiance_tiles at irradiance_waves_per_simd. launch_irradiance_rays: rays[(i << log2L) + l] = the ray
+// such a lane's sample starts from, after skip[...] draws of its stream (skip NULL: none); one thread per ray, no scene.
+hipError_t launch_irradiance(const DeviceScene& S, int integrator, bool simple, bool lean, int n, const void* recs, int log2L, const uint32_t* jump,
+                             unsigned long long seed, uint32_t firstStream, bool streamPad, int sppLane, int maxDepth, int useMIS, int blocks, void* out,
+                             void* sq, int32_t* spill, hipStream_t stream);
+hipError_t launch_irradiance_rays(int n, const void* recs, int log2L, const uint32_t* jump, unsigned long long seed, uint32_t firstStream,
+                                  bool streamPad, const void* skip, void* rays, hipStream_t stream);
 // pt_query_guides.hip: n rays, lane i of tile t takes ray 64 t + i. maxLinks 0: the first-hit kernel (links, if set, gets zeros); else
 // the chain kernel. albedo[i] = (a, 1), normalDepth[i] = (n, summed path length), links[i] (NULL ok) the links followed; a miss: zeros.
 hipError_t launch_query_guides(const DeviceScene& S, int n, const void* rays, int maxLinks, int blocks, void* albedo, void* normalDepth, float* links,

@@ -29,9 +29,8 @@
 
 namespace pt {
 
-// The start of a sample: path_begin without the camera. (SYNC: no flag of a previous path survives its end.)
-PT_DEV void radiance_begin(PathState& ps, V3 o, V3 d, Ctr& c) {
-    draw<false>(ps.rng, c); draw<false>(ps.rng, c);         // the two jitter draws of generateCameraRay; no lens numbers
+// path_begin's state at (o, d), without the camera and without a draw. (SYNC: no flag of a previous path survives its end.)
+PT_DEV void radiance_state(PathState& ps, V3 o, V3 d) {
     ps.o = o; ps.d = d;
     ps.beta = v3(1.0f); ps.Li = v3(0.0f); ps.prevPoint = v3(0.0f); ps.woLocal = v3(0.0f);
     ps.pdf = kEps; ps.etaI = kEps; ps.etaT = kEps;
@@ -39,8 +38,28 @@ PT_DEV void radiance_begin(PathState& ps, V3 o, V3 d, Ctr& c) {
     ps.flags = kInPath;
 }
 
+// The start of a sample of a caller's ray.
+PT_DEV void radiance_begin(PathState& ps, V3 o, V3 d, Ctr& c) {
+    draw<false>(ps.rng, c); draw<false>(ps.rng, c);         // the two jitter draws of generateCameraRay; no lens numbers
+    radiance_state(ps, o, d);
+}
+
+// What a sample starts from and which record a lane works on is the walk's second policy, a type with three members (RayBegin is
+// the radiance kernels'; pt_irradiance.hip has CosineBegin):
+//   record(g)                 the record of lane g = 64 tile + lane of the launch; the lane has work if it is below n
+//   stream(rec, pad, g)       what the lane adds to firstStream: from the record's pad word (streamPad) or from g
+//   sample(ps, a, b, c)       a sample begins: the draws it spends, and path_begin's state at its ray; (a, b) are the record's
+//                             32 bytes, read again for every sample
+// Like a sums policy it keeps nothing per lane in registers; what it holds is the same for the whole wave.
+struct RayBegin {
+    PT_DEV int record(int g) const { return g; }
+    PT_DEV uint32_t stream(const float4* __restrict__ rec, int streamPad, int g) const { return streamPad ? __float_as_uint(rec[1].w) : (uint32_t)g; }
+    PT_DEV void sample(PathState& ps, float4 a, float4 b, Ctr& c) const { radiance_begin(ps, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), c); }
+};
+
 // radiance_kernel's policy: one 16-byte store per ray, (acc, 0).
 struct RadianceSums {
+    static constexpr bool kWave = false;
     float4* __restrict__ out;
     PT_DEV void reset() {}
     PT_DEV void sample(V3 acc) {}
@@ -48,10 +67,10 @@ struct RadianceSums {
 };
 
 // The walk over the wave's tiles. ldsMedium: mediumStack[16] per lane, lane-interleaved, one slice per wave; SIMPLE never names it.
-template <int INTEG, bool SIMPLE, bool LEAN, class Sums>
+template <int INTEG, bool SIMPLE, bool LEAN, class Sums, class Begin = RayBegin>
 PT_DEV void radiance_walk(const DeviceScene& S, int32_t (*ldsStack)[kStackLds][64], uint8_t (*ldsMedium)[kMediumMax][64], int32_t* spill,
                           const float4* __restrict__ rays, int n, int nTiles, const uint32_t* __restrict__ jump, unsigned long long seed,
-                          uint32_t firstStream, int streamPad, int spp, int maxDepth, int useMIS, Sums sums) {
+                          uint32_t firstStream, int streamPad, int spp, int maxDepth, int useMIS, Sums sums, Begin begin = Begin()) {
     FeatureWave W(ldsStack, S, spill);
     LdsMedium msLds;
     msLds.p = (LdsMedium::lds_u8*)&ldsMedium[SIMPLE ? 0 : W.wave][0][0] + W.lane;
@@ -59,11 +78,12 @@ PT_DEV void radiance_walk(const DeviceScene& S, int32_t (*ldsStack)[kStackLds][6
     auto& ms = [&]() -> auto& { if constexpr (SIMPLE) return msNone; else return msLds; }();
     auto shadowSync = [&](V3 ro, V3 wi, float maxt) { return trace_shadow<false, kStackLds, false, false, SIMPLE || LEAN>(S, W.C, ro, wi, maxt, W.st, W.c); };
     for (int tile = W.gw; tile < nTiles; tile += gridDim.x * 4) {
-        const int i = tile * 64 + W.lane;
+        const int g = tile * 64 + W.lane;
+        const int i = begin.record(g);
         const bool live = i < n;
         // (the record is read again at the start of every sample, from the cache, instead of living in seven VGPRs across every traversal)
         const float4* ray = rays + 2 * (size_t)(live ? i : 0);
-        const uint32_t k = live ? firstStream + (streamPad ? __float_as_uint(ray[1].w) : (uint32_t)i) : 0u;
+        const uint32_t k = live ? firstStream + begin.stream(ray, streamPad, g) : 0u;
         PathState ps;
         ps.rng = aov_stream(jump, seed, k);                     // (every lane: the seeding ballots per bit)
         ps.o = v3(0.0f); ps.d = v3(0.0f); ps.beta = v3(1.0f); ps.Li = v3(0.0f); ps.prevPoint = v3(0.0f); ps.woLocal = v3(0.0f);
@@ -84,7 +104,7 @@ PT_DEV void radiance_walk(const DeviceScene& S, int32_t (*ldsStack)[kStackLds][6
             while (!(ps.flags & kInPath) && samplesLeft > 0) {
                 samplesLeft--;
                 const float4 a = ray[0], b = ray[1];
-                radiance_begin(ps, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), W.c);
+                begin.sample(ps, a, b, W.c);
                 ms.set(0, 0);
                 maxT = a.w;
                 if (path_exhausted<INTEG>(ps, maxDepth)) { acc = acc + ps.Li; sums.sample(acc); ps.flags &= ~kInPath; }
@@ -93,7 +113,8 @@ PT_DEV void radiance_walk(const DeviceScene& S, int32_t (*ldsStack)[kStackLds][6
             if (__ballot(hasExt) == 0ull) break;
             if (hasExt) trace_closest<false, kStackLds>(S, W.C, ps.o, ps.d, maxT, W.st, h, W.c);
         }
-        if (live) sums.store(i, acc);
+        if constexpr (Sums::kWave) sums.store_wave(live, i, g, acc);
+        else if (live) sums.store(i, acc);
     }
 }
 

@@ -17,6 +17,7 @@ namespace pt {
 
 // The batch bookkeeping of one lane, in its words m[j * 64], j = 0..6, of an LDS array float[7][64]: prev, Q, the counter's bits.
 struct MomentsLds {
+    static constexpr bool kWave = false;
     float* m;
     int batchSpp;
     float batches;

@@ -4,6 +4,9 @@ lens on a pixel grid) does not have. Plain numpy, or torch when `device` is give
 directions and pad = 0: ray i then draws from stream first_stream + i.
 
     pano = sc.query_radiance(rays.panorama_rays((0, 0, 1.5), 2048, 1024), spp=16, max_depth=8).reshape(1024, 2048, 4) / 16
+
+irradiance_records and records_from_surfaces make the records of Scene.query_irradiance in the same layout: a surface point where a
+ray has its origin, the unit normal where it has its direction.
 """
 import numpy as np
 
@@ -36,6 +39,40 @@ def panorama_rays(origin, w, h, max_t=QUERY_MAX_T, device=None):
     d = d / xp.sqrt((d * d).sum(-1))[:, None]
     o = xp.asarray(np.asarray(origin, np.float64), **kw).reshape(1, 3)
     return _records(xp, kw, o.to(xp.float32) if xp is not np else o, d.to(xp.float32) if xp is not np else d, h * w, max_t)
+
+
+def irradiance_records(points, normals, max_t=QUERY_MAX_T, device=None):
+    """Records for Scene.query_irradiance: [n, 8] float32 (point, max_t, normal, pad = 0) from [n, 3] points and normals (numpy, or
+    with `device` anything torch.as_tensor takes). The normals must be unit length and are copied as given: the library does not
+    normalise them."""
+    xp, kw = _xp(device)
+    as_f32 = (lambda v: np.asarray(v, np.float32)) if xp is np else (lambda v: xp.as_tensor(v, dtype=xp.float32, **kw))
+    p, nrm = as_f32(points).reshape(-1, 3), as_f32(normals).reshape(-1, 3)
+    if len(p) != len(nrm):
+        raise ValueError("irradiance_records: %d points but %d normals" % (len(p), len(nrm)))
+    return _records(xp, kw, p, nrm, len(p), max_t)
+
+
+def records_from_surfaces(surfaces, max_t=QUERY_MAX_T):
+    """Records for Scene.query_irradiance from Scene.query_closest(..., surfaces=True)'s surfaces: a RAY_SURFACE_DTYPE array (numpy)
+    or the [n, 12] float32 tensor of the device form, whose point and facing normal are copied bit for bit. A ray that missed
+    (material -1) gives the record (0, 0, 0), max_t = 0, normal (0, 0, 1): no first segment hits anything below 0, so its sums are
+    exact zeros."""
+    if isinstance(surfaces, np.ndarray):
+        s = np.ascontiguousarray(surfaces)
+        f = s.view(np.float32).reshape(len(s), 12) if s.dtype.names else np.ascontiguousarray(s, np.float32).reshape(-1, 12)
+        out = np.zeros((len(f), 8), np.float32)
+        hit = f.view(np.int32)[:, 8] >= 0
+    else:
+        import torch
+        f = surfaces.reshape(-1, 12)
+        out = torch.zeros((f.shape[0], 8), dtype=torch.float32, device=f.device)
+        hit = f.view(torch.int32)[:, 8] >= 0
+    out[:, 0:3] = f[:, 0:3]
+    out[:, 4:7] = f[:, 4:7]
+    out[:, 3] = hit * np.float32(max_t)
+    out[:, 6] += ~hit
+    return out
 
 
 def orthographic_rays(origin, forward, up, width, height, w, h, max_t=QUERY_MAX_T, device=None):

@@ -1365,6 +1365,63 @@ int pt_query_guides_device(pt_scene* scene, int n, const void* d_rays /* n pt_ra
                            void* d_normal_depth /* n float4 */, void* d_links /* n floats, NULL ok */, unsigned flags, void* stream);   /* async */
 int pt_query_guides(pt_scene* scene, int n, const pt_ray* rays, int max_links, float* out_albedo /* n*4 */, float* out_normal_depth /* n*4 */,
                     float* out_links /* n, NULL ok */, unsigned flags);                                                         /* host, blocking */
+/* pt_query_irradiance: cosine-sampled light at surface points: what a lightmap texel or a light probe needs. The
+ * library draws the directions itself, and a record's samples may be spread over several lanes of a wave.
+ * Record. A pt_ray: (ox, oy, oz) is the surface point p, (dx, dy, dz) the unit normal nrm, used as given and NOT normalised, max_t
+ *   bounds the first segment of every sample as in pt_query_radiance, pad is read only with PT_QUERY_STREAM_PAD. A pt_ray_surface of
+ *   pt_query_closest (point, facing normal) becomes a record by copying those fields.
+ * Lanes and streams. lanes = L, one of 1, 2, 4, 8, 16, 32, 64. Record i owns L lanes; lane l owns the XORWOW stream
+ *   k = first_stream + i*L + l, or with PT_QUERY_STREAM_PAD first_stream + pad_i*L + l, in uint32 arithmetic (it wraps), seeded as
+ *   pt_query_radiance seeds a ray's. Without the flag first_stream + n*L must not pass 2^31. A 64-lane tile holds 64 / L records;
+ *   lanes of records past n take no work and store nothing. A lane runs spp_lane samples on its stream, one after the other.
+ * Sample. A sample draws u1, then u2: the two draws a pt_query_radiance sample spends and drops. From them:
+ *   DIRECTION ARITHMETIC, every operation rounded once to f32 in the order written, nothing fused but the fma() named here
+ *   (fma(a, b, c) = a*b + c rounded once). EPS = 1e-5f, PI = 3.141592f, RAY_EPS = 1e-3f.
+ *     u1 = min(u1, 1 - EPS);  r = sqrtf(u1);  phi = (2*PI)*u2;  (sn, cs) = the library's sincos of phi (pt_device.h: sincos_);
+ *     local = (r*cs, r*sn, sqrtf(1 - u1))                                            (cosine_sample_f's direction)
+ *     tangent: |nrm.x| > |nrm.z| ?  v = (-nrm.y, nrm.x, 0)  :  v = (0, -nrm.z, nrm.y);
+ *              t = v * (1 / sqrtf(fma(v.z, v.z, fma(v.y, v.y, v.x*v.x))))            (sqrt, then the reciprocal, both correctly
+ *              rounded, then three products; on the tie |nrm.x| = |nrm.z| the second arm)
+ *     b = (fma(nrm.y, t.z, -(nrm.z*t.y)), fma(nrm.z, t.x, -(nrm.x*t.z)), fma(nrm.x, t.y, -(nrm.y*t.x)))          (cross(nrm, t))
+ *     d = (local.x*t + local.y*b) + local.z*nrm    per component: (t.c*local.x + b.c*local.y) + nrm.c*local.z
+ *     o = p + nrm*RAY_EPS                          per component: p.c + nrm.c*RAY_EPS
+ *   the plain basis of the naive bounce and the offset the bounce gives a reflected ray. From (o, d) the sample runs exactly what a
+ *   pt_query_radiance sample runs after its two draws: path_begin's state, the record's max_t on the first segment and 999999 on
+ *   every later one, Li_unidirectional (integrator 0, use_mis as given) or Li_naive_unidirectional (integrator 2), the same kernel
+ *   class for the scene's materials and the same honouring of the options "simple" and "lean".
+ * Sums. A lane's sum is a_l = ((0 + Li_0) + Li_1) + ... in f32. The record's sum is the adjacent-pair tree over its lanes:
+ *   T_0[l] = a_l, T_(k+1)[l] = T_k[2l] + T_k[2l+1], S = T_(log2 L)[0] per rgb channel; out_rgba_sum[i] = (S, 0).
+ *   sq_sum (NULL: not written; needs L >= 2, a lane's sum being one batch): Q = the same tree over a_l*a_l per channel, the product
+ *   rounded before any sum, no contraction; out_sq_sum[i] = (Q, (float)L). (S, Q) is pt_render_moments' pair for spp = L*spp_lane in
+ *   batches = L, so pt_denoise_var with pt_query_guides' guides filters a baked lightmap as it filters a panorama.
+ *   Irradiance is PI*S / (L*spp_lane); the library does not scale the sums. The call writes its outputs; it does not add to them.
+ * Independence. A record's result depends only on the scene, its 32 bytes, its stream base, L, spp_lane, seed, max_depth, integrator
+ *   and use_mis: not on n, on its place in the buffer or on what the other records of its tile hold.
+ * What a call touches: what pt_query_radiance touches, the scene's feature spill area and, the host form, its query staging
+ *   buffer. No RNG state, accumulator, counter or tile queue of the scene. After any pt_scene_update_* a call sees the edited scene.
+ * pt_query_irradiance_rays_device: the tie to pt_query_radiance, as pt_query_camera_rays_device is the centre passes'. Ray i*L + l is
+ *   the (o, d) a sample of lane l of record i starts from when draws draw_offset[i*L + l] and draw_offset[i*L + l] + 1 of the lane's
+ *   stream play u1 and u2 (NULL: all 0, the lane's first sample). It carries the record's max_t, and pad = i*L + l, or pad_i*L + l
+ *   with PT_QUERY_STREAM_PAD: what the lane adds to first_stream. One thread per ray; of the scene it reads the seeding tables only.
+ * Identity. With spp_lane = 1, a_l equals, bit for bit, the .xyz of pt_query_radiance on that emitted ray with spp = 1,
+ *   PT_QUERY_STREAM_PAD and the same seed, first_stream, max_depth, integrator and use_mis. With more samples the stream runs on:
+ *   sample j of a lane starts at the draw after the last one sample j - 1 spent.
+ * Checked before any HIP call, -1 with a message under the function's name, in this order: n < 0 or n*L > 1 << 28 (n == 0 then
+ *   returns 0 before the scene or anything else is looked at); a NULL scene, records or sum (rays) buffer; lanes not a power of two
+ *   in 1..64; spp_lane < 1 or L*spp_lane > 1 << 22; an integrator other than 0 and 2; sq_sum given with lanes == 1;
+ *   PT_QUERY_REORDER and unknown flag bits; without PT_QUERY_STREAM_PAD, first_stream + n*L > 2^31. (The rays call has no samples,
+ *   integrator or sq_sum to check.) The device check comes last.
+ * d_records (n pt_ray), d_rgba_sum and d_sq_sum (n float4 each), d_rays (n*L pt_ray) and d_draw_offset (n*L uint32) are device
+ * buffers, the first four aligned to 16 bytes; the device forms are asynchronous on `stream`. */
+int pt_query_irradiance_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int lanes, int spp_lane, int max_depth, int integrator,
+                               int use_mis, uint64_t seed, uint32_t first_stream, void* d_rgba_sum /* n float4 */,
+                               void* d_sq_sum /* n float4, NULL ok */, unsigned flags, void* stream);                              /* async */
+int pt_query_irradiance(pt_scene* scene, int n, const pt_ray* records, int lanes, int spp_lane, int max_depth, int integrator, int use_mis,
+                        uint64_t seed, uint32_t first_stream, float* out_rgba_sum /* n*4 */, float* out_sq_sum /* n*4, NULL ok */,
+                        unsigned flags);                                                                                        /* host, blocking */
+int pt_query_irradiance_rays_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int lanes, uint64_t seed, uint32_t first_stream,
+                                    const void* d_draw_offset /* n*lanes uint32, NULL = all 0 */, void* d_rays /* n*lanes pt_ray */,
+                                    unsigned flags, void* stream);                                                              /* async */
 
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
