@@ -231,6 +231,10 @@ def lib():
     L.pt_query_irradiance.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32]
     L.pt_query_irradiance_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.pt_query_irradiance_rays_device.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_query_sh_workspace_bytes.restype = C.c_size_t; L.pt_query_sh_workspace_bytes.argtypes = [i32, i32]
+    L.pt_query_sh.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32]
+    L.pt_query_sh_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_query_sh_rays_device.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
     L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -908,8 +912,12 @@ class Scene:
         None: the lane's first sample), with the record's max_t and, in its pad word, what the lane adds to first_stream:
         query_radiance(rays, 1, ..., first_stream=first_stream, stream_pad=True) is such a sample's radiance. A torch tensor of records
         on the scene's device gives a tensor, on torch's current stream; numpy records are copied up and the rays come back as numpy."""
+        return self._lane_rays("query_irradiance_rays", records, lanes, seed, first_stream, draw_offset, flags)
+
+    def _lane_rays(self, name, records, lanes, seed, first_stream, draw_offset, flags):
+        """query_irradiance_rays and query_sh_rays: pt_<name>_device on [n, 8] records, n * lanes rays out."""
         import torch
-        is_torch, r, n = self._query_rays("query_irradiance_rays", records)
+        is_torch, r, n = self._query_rays(name, records)
         dev = r.device if is_torch else torch.device("cuda", torch.cuda.current_device())
         d = r if is_torch else torch.from_numpy(r if r.flags.writeable else r.copy()).to(dev)
         m = n * lanes if lanes > 0 else 0
@@ -918,12 +926,38 @@ class Scene:
             off = draw_offset if hasattr(draw_offset, "data_ptr") else torch.from_numpy(np.ascontiguousarray(draw_offset).astype(np.int32).reshape(-1))
             off = off.to(device=dev, dtype=torch.int32).contiguous()
             if off.numel() != m:
-                raise PtError("query_irradiance_rays: draw_offset has %d entries for %d rays" % (off.numel(), m))
+                raise PtError("%s: draw_offset has %d entries for %d rays" % (name, off.numel(), m))
         out = torch.empty((m, 8), dtype=torch.float32, device=dev)
         ptr = lambda t: t.data_ptr() if t is not None and n else None
-        _check(lib().pt_query_irradiance_rays_device(self.h, n, ptr(d), lanes, seed, first_stream, ptr(off), ptr(out), flags,
-                                                     torch.cuda.current_stream(dev).cuda_stream or None), "pt_query_irradiance_rays_device")
+        fn = "pt_%s_device" % name
+        _check(getattr(lib(), fn)(self.h, n, ptr(d), lanes, seed, first_stream, ptr(off), ptr(out), flags, torch.cuda.current_stream(dev).cuda_stream or None), fn)
         return out if is_torch else out.cpu().numpy()
+
+    def query_sh(self, records, lanes, spp_lane, max_depth, integrator=UNIDIRECTIONAL, use_mis=True, seed=SEED, first_stream=0, flags=0):
+        """pt_query_sh: a light probe's SH coefficients. records is [n, 8] float32 (probe position, max_t, three words that are not
+        read, pad: rays.sh_records, rays.sh_grid); each record runs on `lanes` (a power of two in 1..4096) lanes, lane l of record i
+        on stream first_stream + i * lanes + l of `seed` (with flags = QUERY_STREAM_PAD: the record's pad word for i), spp_lane
+        samples per lane, each in a uniformly distributed direction. Returns [n, 9, 4] float32: per SH term of bands 0..2 the rgb
+        sums of Li * Y_k over the record's lanes * spp_lane samples, and 0. The radiance coefficients are 4 pi / (lanes * spp_lane)
+        times the sums (rays.sh_irradiance evaluates them). numpy in, numpy out (host form); a torch tensor on the scene's device in,
+        a tensor out, on torch's current stream with no host copy, the workspace of lanes > 64 a torch tensor."""
+        work = None
+        if hasattr(records, "data_ptr") and not isinstance(records, np.ndarray):
+            import torch
+            nbytes = lib().pt_query_sh_workspace_bytes(int(records.shape[0]) if records.dim() else 0, lanes)
+            work = torch.empty(nbytes, dtype=torch.uint8, device=records.device) if nbytes else None
+            tail = lambda o: (o[0], work.data_ptr() if work is not None else None, flags)
+        else:
+            tail = lambda o: (o[0], flags)
+        out = self._query("query_sh", records, [(36, np.float32)], lambda r, o: (
+            r, lanes, spp_lane, max_depth, integrator, 1 if use_mis else 0, seed, first_stream) + tail(o), empty=(True, True))[0]
+        return out.reshape(-1, 9, 4)
+
+    def query_sh_rays(self, records, lanes, seed=SEED, first_stream=0, draw_offset=None, flags=0):
+        """pt_query_sh_rays_device: the rays query_sh's samples start from, [n * lanes, 8] float32, as query_irradiance_rays gives
+        them for query_irradiance: ray i * lanes + l is lane l of record i, made of draws draw_offset[i * lanes + l] and the next of
+        that lane's stream, with the record's max_t and, in its pad word, what the lane adds to first_stream."""
+        return self._lane_rays("query_sh_rays", records, lanes, seed, first_stream, draw_offset, flags)
 
     def query_guides(self, rays, max_links=0, links=False):
         """pt_query_guides: render_aovs_centre's guides for each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be

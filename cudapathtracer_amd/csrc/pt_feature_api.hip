@@ -1,6 +1,6 @@
 // pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
 // and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_query_guides.hip,
-// pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
+// pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip, pt_sh.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -496,6 +496,86 @@ int pt_query_irradiance_rays_device(pt_scene* s, int n, const void* d_records, i
     if (int r = check_query_device(fn, s)) return r;
     HIP_OK(launch_irradiance_rays(n, d_records, log2_lanes(lanes), (const uint32_t*)s->data.jump.p, seed, first_stream,
                                   (flags & PT_QUERY_STREAM_PAD) != 0, d_draw_offset, d_rays, (hipStream_t)stream));
+    return 0;
+}
+
+// SH queries (pt_sh.hip: sh_kernel, sh_reduce_kernel, sh_rays_kernel). Every message under the caller's name, all before any HIP
+// call, in the header's order; n == 0 returns before the scene or anything else is looked at. walk: pt_query_sh's checks; else
+// pt_query_sh_rays_device's, which has no samples, integrator or workspace (`out` is its rays buffer). needWork: the device form,
+// whose caller brings the workspace.
+static int check_sh_args(const char* fn, bool walk, pt_scene* s, int n, const void* recs, const void* out, int lanes, int sppLane, int integrator,
+                         uint32_t firstStream, uint32_t flags, bool needWork, const void* work) {
+    if (n < 0 || (long long)n * lanes > (1ll << 28)) return fail(-1, "%s: n %d at %d lanes must be 0..%d lanes in all", fn, n, lanes, 1 << 28);
+    if (n == 0) return 0;
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!recs) return fail(-1, "%s: null records", fn);
+    if (!out) return fail(-1, "%s: null output buffer", fn);
+    if (lanes < 1 || lanes > 4096 || (lanes & (lanes - 1))) return fail(-1, "%s: lanes %d must be a power of two in 1..4096", fn, lanes);
+    if (walk) {
+        if (sppLane < 1 || (long long)lanes * sppLane > (1ll << 22))
+            return fail(-1, "%s: spp_lane %d at %d lanes must be 1..%d samples a record", fn, sppLane, lanes, 1 << 22);
+        if (integrator != PT_UNIDIRECTIONAL && integrator != PT_NAIVE_UNIDIRECTIONAL)
+            return fail(-1, "%s: integrator %d is out of scope: only UNIDIRECTIONAL (0) and NAIVE_UNIDIRECTIONAL (2) are on this path", fn, integrator);
+    }
+    if (flags & PT_QUERY_REORDER) return fail(-1, "%s: PT_QUERY_REORDER is not taken here: a path leaves its first ray's order at once", fn);
+    if (flags & ~PT_QUERY_STREAM_PAD) return fail(-1, "%s: unknown flag bits 0x%x", fn, flags & ~PT_QUERY_STREAM_PAD);
+    const unsigned long long end = (unsigned long long)firstStream + (unsigned long long)n * (unsigned)lanes;
+    if (!(flags & PT_QUERY_STREAM_PAD) && end > (1ull << 31)) return fail(-1, "%s: streams %u .. %llu pass 2^31", fn, firstStream, end - 1ull);
+    if (needWork && lanes > 64 && !work) return fail(-1, "%s: lanes %d needs a workspace of pt_query_sh_workspace_bytes", fn, lanes);
+    return 0;
+}
+
+size_t pt_query_sh_workspace_bytes(int n, int lanes) { return n > 0 && lanes > 64 ? (size_t)n * (size_t)(lanes / 64) * 9 * sizeof(float4) : 0; }
+
+// The material class picks the instantiation as query_radiance picks it, from the same two options. More than 64 lanes: the walk
+// leaves a tile's sums in dWork and the second stage of the tree follows on the same stream.
+static int query_sh(pt_scene* s, int n, const void* dRecs, int lanes, int sppLane, int maxDepth, int integrator, int useMIS, uint64_t seed,
+                    uint32_t firstStream, void* dOut, void* dWork, uint32_t flags, hipStream_t stream) {
+    const bool simple = s->facts.simpleOk && s->opt.simpleWanted;
+    const bool lean = s->facts.leanOk && s->opt.leanWanted && !s->facts.armless && !simple;
+    const int log2L = log2_lanes(lanes);
+    const int blocks = feature_blocks(irradiance_tiles(n, log2L), s->dev.numCU, sh_waves_per_simd(integrator, simple, lean));
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_sh(s->facts.ds, integrator, simple, lean, n, dRecs, log2L, (const uint32_t*)s->data.jump.p, seed, firstStream,
+                     (flags & PT_QUERY_STREAM_PAD) != 0, sppLane, maxDepth, useMIS, blocks, dOut, dWork, spill, stream));
+    if (lanes > 64) HIP_OK(launch_sh_reduce(n, log2L, dWork, dOut, stream));
+    return 0;
+}
+
+int pt_query_sh_device(pt_scene* s, int n, const void* d_records, int lanes, int spp_lane, int max_depth, int integrator, int use_mis, uint64_t seed,
+                       uint32_t first_stream, void* d_coeffs, void* d_workspace, unsigned flags, void* stream) {
+    const char* fn = "pt_query_sh";
+    if (int r = check_sh_args(fn, true, s, n, d_records, d_coeffs, lanes, spp_lane, integrator, first_stream, flags, true, d_workspace)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    return query_sh(s, n, d_records, lanes, spp_lane, max_depth, integrator, use_mis, seed, first_stream, d_coeffs, d_workspace, flags,
+                    (hipStream_t)stream);
+}
+
+// The host form's workspace lies in the staging buffer behind the coefficients: the buffer is grown for all three before
+// staged_query lays out the first two.
+int pt_query_sh(pt_scene* s, int n, const pt_ray* records, int lanes, int spp_lane, int max_depth, int integrator, int use_mis, uint64_t seed,
+                uint32_t first_stream, float* out_coeffs, unsigned flags) {
+    const char* fn = "pt_query_sh";
+    if (int r = check_sh_args(fn, true, s, n, records, out_coeffs, lanes, spp_lane, integrator, first_stream, flags, false, nullptr)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    const size_t bytes = (size_t)n * 9 * sizeof(float4);
+    if (int r = s->feat.queryOut.ensure((size_t)n * sizeof(pt_ray) + bytes + pt_query_sh_workspace_bytes(n, lanes))) return r;
+    return staged_query(s->feat.queryOut, n, records, {{out_coeffs, bytes}}, [&](const void* dRecs, void* const* d) {
+        return query_sh(s, n, dRecs, lanes, spp_lane, max_depth, integrator, use_mis, seed, first_stream, d[0], (char*)d[0] + bytes, flags, nullptr);
+    });
+}
+
+int pt_query_sh_rays_device(pt_scene* s, int n, const void* d_records, int lanes, uint64_t seed, uint32_t first_stream, const void* d_draw_offset,
+                            void* d_rays, unsigned flags, void* stream) {
+    const char* fn = "pt_query_sh_rays_device";
+    if (int r = check_sh_args(fn, false, s, n, d_records, d_rays, lanes, 1, PT_UNIDIRECTIONAL, first_stream, flags, false, nullptr)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    HIP_OK(launch_sh_rays(n, d_records, log2_lanes(lanes), (const uint32_t*)s->data.jump.p, seed, first_stream, (flags & PT_QUERY_STREAM_PAD) != 0,
+                          d_draw_offset, d_rays, (hipStream_t)stream));
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip) and of the ray
-// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip): the tiling and block count every one of them is
+// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip, pt_sh.hip): the tiling and block count every one of them is
 // launched with, each kernel's waves per SIMD, and the launchers pt_feature_api.hip calls. The kernels' shared pieces are in
 // pt_feature.h, the radiance kernels' walk in pt_radiance.h.
 #pragma once
@@ -56,6 +56,14 @@ constexpr int radiance_moments_waves_per_simd(int integrator, bool simple, bool 
 constexpr int irradiance_waves_per_simd(int integrator, bool simple, bool lean) { return radiance_waves_per_simd(integrator, simple, lean); }
 // Its tiles: n records of 1 << log2L lanes each, 64 lanes a tile (n << log2L is at most 1 << 28).
 constexpr int irradiance_tiles(int n, int log2L) { return ((n << log2L) + 63) / 64; }
+// sh_kernel<INTEG, SIMPLE, LEAN> (pt_sh.hip): the lanes' 27 sums and the sample's direction are 30 LDS words a lane, 30 720 bytes a
+// workgroup on top of the class's 16 or 20 KB: three workgroups fit a CU's 160 KB, so the kernels are compiled for and launched at
+// min(radiance_kernel's waves, 3). At 3 waves a SIMD has 168 VGPRs a lane to give, and no kernel needs scratch. VGPRs / scratch
+// bytes per lane / LDS bytes (tests/test_query_sh_api.py pins the table):
+//   naive, SIMPLE    3: 79 / 0 / 47104                                    MIS, SIMPLE    3: 91 / 0 / 47104
+//   naive, LEAN      3: 96 / 0 / 51200                                    MIS, LEAN      3: 119 / 0 / 51200
+//   naive, generic   3: 96 / 0 / 51200                                    MIS, generic   3: 131 / 0 / 51200
+constexpr int sh_waves_per_simd(int integrator, bool simple, bool lean) { return std::min(radiance_waves_per_simd(integrator, simple, lean), 3); }
 constexpr int kQueryGuidesWavesPerSimd = 8;      // query_guides_kernel: 55 VGPRs, 8 x 16 KB of LDS, as the centre pass
 constexpr int kQueryGuidesChainWavesPerSimd = 6;  // query_guides_chain_kernel: 60 VGPRs, 23 KB of LDS: 7 workgroups would need 161 KB
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
@@ -114,6 +122,17 @@ hipError_t launch_irradiance(const DeviceScene& S, int integrator, bool simple, 
                              void* sq, int32_t* spill, hipStream_t stream);
 hipError_t launch_irradiance_rays(int n, const void* recs, int log2L, const uint32_t* jump, unsigned long long seed, uint32_t firstStream,
                                   bool streamPad, const void* skip, void* rays, hipStream_t stream);
+// pt_sh.hip: sh_kernel<integrator, simple, lean> on n records (pt_ray: point, max_t; the direction words are not read) of 1 << log2L
+// lanes each, log2L 0..12, lanes and streams as launch_irradiance has them. log2L <= 6: out[9 i + k] = (the tree over the lanes' sums
+// of Li * Y_k, 0), work is not read. log2L > 6: work[9 t + k] = tile t's tree, and launch_sh_reduce, on the same stream behind it,
+// writes out[9 i + k] = the tree over record i's (1 << log2L) / 64 tiles. blocks: feature_blocks of irradiance_tiles at
+// sh_waves_per_simd. launch_sh_rays: launch_irradiance_rays for these records.
+hipError_t launch_sh(const DeviceScene& S, int integrator, bool simple, bool lean, int n, const void* recs, int log2L, const uint32_t* jump,
+                     unsigned long long seed, uint32_t firstStream, bool streamPad, int sppLane, int maxDepth, int useMIS, int blocks, void* out,
+                     void* work, int32_t* spill, hipStream_t stream);
+hipError_t launch_sh_reduce(int n, int log2L, const void* work, void* out, hipStream_t stream);
+hipError_t launch_sh_rays(int n, const void* recs, int log2L, const uint32_t* jump, unsigned long long seed, uint32_t firstStream, bool streamPad,
+                          const void* skip, void* rays, hipStream_t stream);
 // pt_query_guides.hip: n rays, lane i of tile t takes ray 64 t + i. maxLinks 0: the first-hit kernel (links, if set, gets zeros); else
 // the chain kernel. albedo[i] = (a, 1), normalDepth[i] = (n, summed path length), links[i] (NULL ok) the links followed; a miss: zeros.
 hipError_t launch_query_guides(const DeviceScene& S, int n, const void* rays, int maxLinks, int blocks, void* albedo, void* normalDepth, float* links,

@@ -28,11 +28,6 @@ PT_DEV void cosine_ray(Rng& rng, V3 p, V3 nrm, V3& o, V3& d, Ctr& c) {
     o = p + nrm * kRayEps;
 }
 
-// What lane g adds to firstStream, as lane l = g & (L - 1) of its record: g itself, or with streamPad (the record's pad word) * L + l.
-PT_DEV uint32_t irradiance_stream(uint32_t padWord, int streamPad, int g, int log2L) {
-    return streamPad ? (padWord << log2L) + ((uint32_t)g & ((1u << log2L) - 1u)) : (uint32_t)g;
-}
-
 // The walk's begin policy: L lanes per record, a cosine-distributed ray per sample.
 struct CosineBegin {
     int log2L;
@@ -47,29 +42,24 @@ struct CosineBegin {
     }
 };
 
-// The walk's sums policy: nothing per sample; at the tile's end the record's lanes add up in the adjacent-pair tree
-// T_0[l] = a_l, T_(k+1)[l] = T_k[2l] + T_k[2l+1]. Step k leaves T_(k+1)[l] in lane l << (k + 1) of the record: every lane adds what
-// the lane 1 << k above it holds, and the lanes that are multiples of 2 << k hold the tree's values. A record's L lanes are one
-// aligned group of the wave, live or idle together (an idle lane holds 0), so every lane of the wave takes every step. sq set: the
-// same tree over a_l * a_l per channel, the product rounded first (the unit is compiled without contraction).
+// The walk's sums policy: nothing per sample; at the tile's end the record's lanes add up in the adjacent-pair tree (pt_radiance.h:
+// lane_tree; the streams are its irradiance_stream's). A record's L lanes are one aligned group of the wave, live or idle together
+// (an idle lane holds 0), so every lane of the wave takes every step. sq set: the same tree over a_l * a_l per channel, the product
+// rounded first (the unit is compiled without contraction).
 struct IrradianceSums {
     static constexpr bool kWave = true;
     int log2L;
     float4* __restrict__ out;
     float4* __restrict__ sq;
     PT_DEV void reset() {}
-    PT_DEV void sample(V3 acc) {}
-    PT_DEV static V3 tree(V3 v, int lanes) {
-        for (int s = 1; s < lanes; s <<= 1) v = v3(v.x + __shfl_down(v.x, s), v.y + __shfl_down(v.y, s), v.z + __shfl_down(v.z, s));
-        return v;
-    }
+    PT_DEV void sample(V3 acc, V3 li) {}
     PT_DEV void store_wave(bool live, int i, int g, V3 acc) {
         const int lanes = 1 << log2L;
-        const V3 s = tree(acc, lanes);
+        const V3 s = lane_tree(acc, lanes);
         const bool first = live && (g & (lanes - 1)) == 0;
         if (first) out[i] = make_float4(s.x, s.y, s.z, 0.0f);
         if (sq) {
-            const V3 q = tree(v3(acc.x * acc.x, acc.y * acc.y, acc.z * acc.z), lanes);
+            const V3 q = lane_tree(v3(acc.x * acc.x, acc.y * acc.y, acc.z * acc.z), lanes);
             if (first) sq[i] = make_float4(q.x, q.y, q.z, (float)lanes);
         }
     }

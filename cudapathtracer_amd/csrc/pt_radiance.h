@@ -14,9 +14,9 @@
 // PathState stays in scalars as pt_path.h demands: path_bounce copies the fields in and out, and the code here assigns whole values.
 //
 // What a kernel does with the sums is its policy, a type with three members (RadianceSums is the plain kernel's; pt_radiance_moments.hip
-// has MomentsLds):
+// has MomentsLds, pt_irradiance.hip IrradianceSums, pt_sh.hip ShSums):
 //   reset()          a tile begins: acc is 0
-//   sample(acc)      a sample has ended: acc is the running sum after it
+//   sample(acc, li)  a sample has ended: acc is the running sum after it, li the sample's own Li
 //   store(i, acc)    the tile is over: ray i's sum is acc
 // A policy keeps nothing per lane in registers. sample() runs between two traversals of a loop whose every value is live across
 // trace_closest and the bounce, and the six plain kernels sit at the edge of their register budgets (tests/test_radiance_api.py pins
@@ -45,7 +45,7 @@ PT_DEV void radiance_begin(PathState& ps, V3 o, V3 d, Ctr& c) {
 }
 
 // What a sample starts from and which record a lane works on is the walk's second policy, a type with three members (RayBegin is
-// the radiance kernels'; pt_irradiance.hip has CosineBegin):
+// the radiance kernels'; pt_irradiance.hip has CosineBegin, pt_sh.hip SphereBegin):
 //   record(g)                 the record of lane g = 64 tile + lane of the launch; the lane has work if it is below n
 //   stream(rec, pad, g)       what the lane adds to firstStream: from the record's pad word (streamPad) or from g
 //   sample(ps, a, b, c)       a sample begins: the draws it spends, and path_begin's state at its ray; (a, b) are the record's
@@ -57,12 +57,26 @@ struct RayBegin {
     PT_DEV void sample(PathState& ps, float4 a, float4 b, Ctr& c) const { radiance_begin(ps, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), c); }
 };
 
+// For the begin policies that spread a record over L = 1 << log2L lanes (pt_irradiance.hip, pt_sh.hip): what lane g adds to
+// firstStream, as lane l = g & (L - 1) of its record: g itself, or with streamPad (the record's pad word) * L + l.
+PT_DEV uint32_t irradiance_stream(uint32_t padWord, int streamPad, int g, int log2L) {
+    return streamPad ? (padWord << log2L) + ((uint32_t)g & ((1u << log2L) - 1u)) : (uint32_t)g;
+}
+
+// ... and for their sums policies the adjacent-pair tree T_0[l] = a_l, T_(k+1)[l] = T_k[2l] + T_k[2l+1] over aligned groups of
+// `lanes` lanes of the wave, in shuffles. Step k leaves T_(k+1)[l] in lane l << (k + 1) of the group: every lane adds what the lane
+// 1 << k above it holds, and the lanes that are multiples of 2 << k hold the tree's values. Every lane of the wave takes every step.
+PT_DEV V3 lane_tree(V3 v, int lanes) {
+    for (int s = 1; s < lanes; s <<= 1) v = v3(v.x + __shfl_down(v.x, s), v.y + __shfl_down(v.y, s), v.z + __shfl_down(v.z, s));
+    return v;
+}
+
 // radiance_kernel's policy: one 16-byte store per ray, (acc, 0).
 struct RadianceSums {
     static constexpr bool kWave = false;
     float4* __restrict__ out;
     PT_DEV void reset() {}
-    PT_DEV void sample(V3 acc) {}
+    PT_DEV void sample(V3 acc, V3 li) {}
     PT_DEV void store(int i, V3 acc) { out[i] = make_float4(acc.x, acc.y, acc.z, 0.0f); }
 };
 
@@ -98,7 +112,7 @@ PT_DEV void radiance_walk(const DeviceScene& S, int32_t (*ldsStack)[kStackLds][6
             if (ps.flags & kInPath) {
                 bool done = path_bounce<INTEG, false, false, SIMPLE, LEAN>(S, ps, ms, h, maxDepth, useMIS, shadowSync, W.c);
                 if (!done) done = path_exhausted<INTEG>(ps, maxDepth);
-                if (done) { acc = acc + ps.Li; sums.sample(acc); ps.flags &= ~kInPath; }          // colors[pixelIdx] += Li
+                if (done) { acc = acc + ps.Li; sums.sample(acc, ps.Li); ps.flags &= ~kInPath; }          // colors[pixelIdx] += Li
                 maxT = 999999.0f;
             }
             while (!(ps.flags & kInPath) && samplesLeft > 0) {
@@ -107,7 +121,7 @@ PT_DEV void radiance_walk(const DeviceScene& S, int32_t (*ldsStack)[kStackLds][6
                 begin.sample(ps, a, b, W.c);
                 ms.set(0, 0);
                 maxT = a.w;
-                if (path_exhausted<INTEG>(ps, maxDepth)) { acc = acc + ps.Li; sums.sample(acc); ps.flags &= ~kInPath; }
+                if (path_exhausted<INTEG>(ps, maxDepth)) { acc = acc + ps.Li; sums.sample(acc, ps.Li); ps.flags &= ~kInPath; }
             }
             const bool hasExt = (ps.flags & kInPath) != 0;
             if (__ballot(hasExt) == 0ull) break;

@@ -27,8 +27,8 @@ struct MomentsLds {
         m[0] = 0.0f; m[64] = 0.0f; m[128] = 0.0f; m[192] = 0.0f; m[256] = 0.0f; m[320] = 0.0f;
         m[384] = __int_as_float(batchSpp);
     }
-    // a sample has been added: acc is the running sum after it
-    PT_DEV void sample(V3 acc) {
+    // a sample has been added: acc is the running sum after it (its own Li is not read)
+    PT_DEV void sample(V3 acc, V3 li) {
         const int left = __float_as_int(m[384]) - 1;
         if (left != 0) { m[384] = __int_as_float(left); return; }
         const V3 d = v3(acc.x - m[0], acc.y - m[64], acc.z - m[128]);

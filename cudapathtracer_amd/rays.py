@@ -6,7 +6,8 @@ directions and pad = 0: ray i then draws from stream first_stream + i.
     pano = sc.query_radiance(rays.panorama_rays((0, 0, 1.5), 2048, 1024), spp=16, max_depth=8).reshape(1024, 2048, 4) / 16
 
 irradiance_records and records_from_surfaces make the records of Scene.query_irradiance in the same layout: a surface point where a
-ray has its origin, the unit normal where it has its direction.
+ray has its origin, the unit normal where it has its direction. sh_records and sh_grid make the records of Scene.query_sh (a probe
+position; the direction words are not read); sh_basis and sh_irradiance evaluate what it returns.
 """
 import numpy as np
 
@@ -73,6 +74,47 @@ def records_from_surfaces(surfaces, max_t=QUERY_MAX_T):
     out[:, 3] = hit * np.float32(max_t)
     out[:, 6] += ~hit
     return out
+
+
+def sh_records(points, max_t=QUERY_MAX_T, device=None):
+    """Records for Scene.query_sh: [n, 8] float32 (probe position, max_t, three words the call does not read, pad = 0) from [n, 3]
+    points (numpy, or with `device` anything torch.as_tensor takes)."""
+    xp, kw = _xp(device)
+    p = (np.asarray(points, np.float32) if xp is np else xp.as_tensor(points, dtype=xp.float32, **kw)).reshape(-1, 3)
+    return _records(xp, kw, p, 0.0, len(p), max_t)
+
+
+def sh_grid(lo, hi, counts, max_t=QUERY_MAX_T, device=None):
+    """Records for Scene.query_sh on a regular grid of counts = (nx, ny, nz) probes from corner lo to corner hi, both included (a
+    count of 1 puts the probe at lo's coordinate): probe (ix, iy, iz) is record (iz * ny + iy) * nx + ix, x fastest."""
+    ax = [np.linspace(float(a), float(b), int(c)) if int(c) > 1 else np.array([float(a)]) for a, b, c in zip(lo, hi, counts)]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return sh_records(np.stack([x.ravel(), y.ravel(), z.ravel()], 1).astype(np.float32), max_t, device)
+
+
+SH_C = (0.2820948, 0.4886025, 1.0925484, 0.3153916, 0.5462742)      # the constants of include/pt_api.h, seven digits each
+SH_LOBE = (np.pi, 2.0 * np.pi / 3.0, np.pi / 4.0)                    # the clamped cosine lobe's factor per band
+
+
+def sh_basis(d):
+    """The nine real spherical harmonics of bands 0..2 at directions d [..., 3], as pt_query_sh orders and writes them: [..., 9] in
+    d's dtype (numpy or torch)."""
+    xp = np if isinstance(d, np.ndarray) else __import__("torch")
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    c0, c1, c2, c3, c4 = SH_C
+    return xp.stack([c0 + 0 * x, c1 * y, c1 * z, c1 * x, c2 * (x * y), c2 * (y * z), c3 * (3 * (z * z) - 1), c2 * (x * z), c4 * (x * x - y * y)], -1)
+
+
+def sh_irradiance(coeff_sums, samples, normals):
+    """Irradiance at unit `normals` [m, 3] from Scene.query_sh's sums [n, 9, 4] of `samples` = lanes * spp_lane samples each: the
+    sums scaled by 4 pi / samples are the radiance coefficients, band l is convolved with the cosine lobe (pi, 2 pi / 3, pi / 4), and
+    the series is evaluated at the normals. Returns [n, m, 3] in the units of pi * S / N of Scene.query_irradiance."""
+    xp = np if isinstance(coeff_sums, np.ndarray) else __import__("torch")
+    lobe = [SH_LOBE[0]] + [SH_LOBE[1]] * 3 + [SH_LOBE[2]] * 5
+    lobe = np.asarray(lobe, coeff_sums.dtype) if xp is np else xp.tensor(lobe, dtype=coeff_sums.dtype, device=coeff_sums.device)
+    e = coeff_sums[..., :3] * (4.0 * np.pi / samples) * lobe[:, None]                  # [n, 9, 3]
+    y = sh_basis(normals if xp is not np else np.asarray(normals, coeff_sums.dtype).reshape(-1, 3))     # [m, 9]
+    return xp.einsum("nkc,mk->nmc", e, y.to(e.dtype) if xp is not np else y)
 
 
 def orthographic_rays(origin, forward, up, width, height, w, h, max_t=QUERY_MAX_T, device=None):

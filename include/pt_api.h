@@ -1422,6 +1422,68 @@ int pt_query_irradiance(pt_scene* scene, int n, const pt_ray* records, int lanes
 int pt_query_irradiance_rays_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int lanes, uint64_t seed, uint32_t first_stream,
                                     const void* d_draw_offset /* n*lanes uint32, NULL = all 0 */, void* d_rays /* n*lanes pt_ray */,
                                     unsigned flags, void* stream);                                                              /* async */
+/* pt_query_sh: a light probe's nine spherical-harmonic coefficients. The library draws uniform directions on the
+ * sphere about a point in free space, walks the paths, and projects every sample's light onto the real spherical harmonics of bands
+ * 0..2. A record's samples may be spread over up to 4096 lanes, that is 64 waves.
+ * Record. A pt_ray: (ox, oy, oz) is the probe position p; max_t bounds the first segment of every sample as in pt_query_radiance;
+ *   the three direction words are NOT read; pad is read only with PT_QUERY_STREAM_PAD.
+ * Lanes and streams. lanes = L, a power of two in 1..4096. Record i owns lanes i*L .. i*L + L-1 of the launch; lane l owns the XORWOW
+ *   stream k = first_stream + i*L + l, or with PT_QUERY_STREAM_PAD first_stream + pad_i*L + l, in uint32 arithmetic (it wraps), seeded
+ *   as pt_query_radiance seeds a ray's. Without the flag first_stream + n*L must not pass 2^31. A lane runs spp_lane samples on its
+ *   stream, one after the other. For L <= 64 a 64-lane tile holds 64 / L records; for L > 64 a record is L / 64 whole tiles, which any
+ *   waves of the launch may take.
+ * Sample. A sample draws u1, then u2: the two draws a pt_query_radiance sample spends and drops. From them
+ *   DIRECTION ARITHMETIC, every operation rounded once to f32 in the order written, nothing fused. EPS = 1e-5f, PI = 3.141592f.
+ *     u1 = min(u1, 1 - EPS);  r = sqrtf(u1);  phi = (2*PI)*u2;  (sn, cs) = the library's sincos of phi (pt_device.h: sincos_);
+ *     w = (r*cs, r*sn, sqrtf(1 - u1))                                                (cosine_sample_f's direction, as above)
+ *     s = 2*w.z;   d = (s*w.x, s*w.y, s*w.z - 1);   o = p
+ *   Archimedes' map of the hemisphere onto the sphere: d.z = 2(1 - u1) - 1 is uniform in [-1, 1], the azimuth is w's, so d is
+ *   uniform on the sphere. The clamp of u1 leaves out a cap of 1e-5 of the sphere's area around -z. d is used as formed, in world
+ *   axes: no basis, no offset, no normalise (|d| is 1 to a few ulp). From (o, d) the sample runs exactly what a pt_query_radiance
+ *   sample runs after its two draws: path_begin's state, the record's max_t on the first segment and 999999 on every later one,
+ *   Li_unidirectional (integrator 0, use_mis as given) or Li_naive_unidirectional (integrator 2), the same kernel class for the
+ *   scene's materials and the same honouring of the options "simple" and "lean".
+ * Projection. With (x, y, z) = d, every product and difference rounded once, nothing contracted:
+ *     C0 = 0.2820948f  C1 = 0.4886025f  C2 = 1.0925484f  C3 = 0.3153916f  C4 = 0.5462742f
+ *     Y0 = C0          Y1 = C1*y        Y2 = C1*z        Y3 = C1*x
+ *     Y4 = C2*(x*y)    Y5 = C2*(y*z)    Y6 = C3*(3*(z*z) - 1)    Y7 = C2*(x*z)    Y8 = C4*(x*x - y*y)
+ *   The term of sample j is t_j[k][c] = Li_j.c * Y_k(d_j) for the three channels c, Li_j being the sample's own light.
+ * Sums. A lane's sums are a_l[k][c] = ((0 + t_0) + t_1) + ... in f32. The record's sums are the adjacent-pair tree over its L lanes,
+ *   T_0[l] = a_l, T_(m+1)[l] = T_m[2l] + T_m[2l+1], run first within each wave and then over the waves' partial sums in tile order:
+ *   L being a power of two, one tree of depth log2 L. coeffs[9*i + k] = (R, G, B, 0). The radiance coefficient is
+ *   4*pi*sum / (L*spp_lane); the library does not scale. The call writes its outputs; it does not add to them.
+ * Workspace. For L > 64 the waves leave their partial sums in a workspace of pt_query_sh_workspace_bytes(n, L) = n * (L/64) * 9 * 16
+ *   bytes (0 for L <= 64), aligned to 16 bytes, which the device form's caller brings (NULL is fine for L <= 64) and a second small
+ *   kernel on the same stream reads. Its contents after the call are unspecified. The host form allocates its own.
+ * pt_query_sh_rays_device: the tie to pt_query_radiance. Ray i*L + l is the (o, d) a sample of lane l of record i starts from when
+ *   draws draw_offset[i*L + l] and draw_offset[i*L + l] + 1 of the lane's stream play u1 and u2 (NULL: all 0, the lane's first
+ *   sample). It carries the record's max_t, and pad = i*L + l, or pad_i*L + l with PT_QUERY_STREAM_PAD: what the lane adds to
+ *   first_stream, exactly as pt_query_irradiance_rays_device does it. One thread per ray; of the scene it reads the seeding tables only.
+ * Identity. With spp_lane = 1, a_l[k][c] = 0 + Li.c * Y_k(d) bit for bit (a product of -0 sums to +0), Li being the .xyz of pt_query_radiance on that emitted ray
+ *   with spp = 1, PT_QUERY_STREAM_PAD and the same seed, first_stream, max_depth, integrator and use_mis, and d the emitted
+ *   direction. With more samples the stream runs on: sample j of a lane starts at the draw after the last one sample j - 1 spent.
+ * Independence. A record's nine coefficients depend only on the scene, p, max_t, its stream base, L, spp_lane, seed, max_depth,
+ *   integrator and use_mis: not on n, on its place in the buffer, on which waves took its tiles or on what other records hold.
+ * What a call touches: what pt_query_radiance touches, the scene's feature spill area and, the host form, its query staging
+ *   buffer. No RNG state, accumulator, counter or tile queue of the scene. After any pt_scene_update_* a call sees the edited scene.
+ * Occupancy. The 27 sums and the direction of a lane live in LDS, 30 KB a workgroup: the kernels run at 3 waves per SIMD where the
+ *   radiance kernels have 4 to 6 (the price is measured in §27).
+ * Checked before any HIP call, -1 with a message under the function's name, in this order: n < 0 or n*L > 1 << 28 (n == 0 then
+ *   returns 0 before the scene or anything else is looked at); a NULL scene, records or coefficient (rays) buffer; lanes not a power
+ *   of two in 1..4096; spp_lane < 1 or L*spp_lane > 1 << 22; an integrator other than 0 and 2; PT_QUERY_REORDER and unknown flag
+ *   bits; without PT_QUERY_STREAM_PAD, first_stream + n*L > 2^31; the device form, lanes > 64 with a NULL workspace. (The rays call
+ *   has no samples, integrator or workspace to check.) The device check comes last.
+ * d_records (n pt_ray), d_coeffs (n*9 float4), d_workspace, d_rays (n*L pt_ray) and d_draw_offset (n*L uint32) are device buffers,
+ * the first four aligned to 16 bytes; the device forms are asynchronous on `stream`. */
+size_t pt_query_sh_workspace_bytes(int n, int lanes);
+int pt_query_sh_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int lanes, int spp_lane, int max_depth, int integrator,
+                       int use_mis, uint64_t seed, uint32_t first_stream, void* d_coeffs /* n*9 float4 */,
+                       void* d_workspace /* NULL ok when lanes <= 64 */, unsigned flags, void* stream);                            /* async */
+int pt_query_sh(pt_scene* scene, int n, const pt_ray* records, int lanes, int spp_lane, int max_depth, int integrator, int use_mis,
+                uint64_t seed, uint32_t first_stream, float* out_coeffs /* n*9*4 */, unsigned flags);                            /* host, blocking */
+int pt_query_sh_rays_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int lanes, uint64_t seed, uint32_t first_stream,
+                            const void* d_draw_offset /* n*lanes uint32, NULL = all 0 */, void* d_rays /* n*lanes pt_ray */, unsigned flags,
+                            void* stream);                                                                                      /* async */
 
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
