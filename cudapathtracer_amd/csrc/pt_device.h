@@ -77,6 +77,19 @@ PT_DEV float rcp_exact(float a) {
 // ARMS also selects the pair kernels' pair pass (pt_trace.h: trace_pair_flat):
 //   the rays' range bounds leave the trips: a trip accepts every positive finite t, the ray's owner applies the bound to the minimum
 //   one place for a slot's second minimum, in the rows the bounds freed: the lane's cursor is two registers
+// ARMS also leaves out the register fills of values that no lane reads on the path that fills them (DESIGN.md §6
+// round 10). Where such a value must exist on a path that never reads it — one arm of a split defines it, the other does not, and
+// the compiler wants something for the join — indeterminate() stands for "no value": a plainly uninitialised local, for which
+// the compiler issues nothing, so the lane keeps whatever the register held, different from lane to lane and from launch to
+// launch. (The other form, a register defined by an empty `asm("" : "=v"(x))`, cost three more copies in the headline kernel and
+// the LEAN pair kernel 12 bytes of scratch; __builtin_nondeterministic_value is lowered to a constant 0, the fill itself.)
+// THE RULE, checked for every use and written down where the value is produced: a value that some lane may hold indeterminate
+// never reaches a branch condition, a ballot or any other cross-lane operation, an address, or a store to LDS or memory that
+// another lane or a later launch reads. A select or an exec mask drops it in every lane that holds it. Arithmetic on it is
+// harmless (no trap is enabled; the result is indeterminate in turn and falls under the same rule).
+PT_DEV V3 indeterminate3() { V3 x; return x; }
+PT_DEV float indeterminate() { return indeterminate3().x; }
+
 PT_DEV float rsqrt_(float x) { return rcp_exact(__builtin_sqrtf(x)); }    // rsqrtf := 1/sqrt, both correctly rounded
 PT_DEV V3 normalize(V3 v) { float il = rsqrt_(dot(v, v)); return V3{v.x * il, v.y * il, v.z * il}; }   // util.cuh:128-131
 PT_DEV float length(V3 v) { return __builtin_sqrtf(dot(v, v)); }

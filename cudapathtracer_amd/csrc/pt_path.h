@@ -248,8 +248,11 @@ PT_DEV bool bounce_core(const DeviceScene& S, Rng& rng, V3& o, V3& d, V3& beta, 
             const bool emArm = le2 > kEps && !firstSeen && useMIS && !isSpecular && hi.lightInd >= 0;      // (without a light record: lightPdf = kEps, nothing added)
             const bool neeArm = useMIS && le2 < kEps && !isSpecular && S.nLights > 0;
             if (le2 > kEps && firstSeen) Li = Li + beta * hi.emission;
+            // s2l: set by both arms and read only under `neeArm || emArm`. A, B, Cc (the sampled light's corners): set and read
+            // only under neeArm. Indeterminate (pt_device.h) in every other lane, and those lanes are masked off wherever the
+            // values are read: they die at the two exec masks below, before any store, ballot or address.
             int li = 0;
-            V3 s2l = v3(0.0f), A = v3(0.0f), B = v3(0.0f), Cc = v3(0.0f);
+            V3 s2l = indeterminate3(), A = indeterminate3(), B = indeterminate3(), Cc = indeterminate3();
             if (neeArm) {
                 li = min((int)(draw<COUNT>(rng, c) * (float)S.nLights), S.nLights - 1);
                 const PLight& L = S.lights[li];
@@ -427,8 +430,21 @@ PT_DEV bool path_bounce(const DeviceScene& S, PathState& ps, MS& ms, const Hit& 
     uint32_t flags = ps.flags;
     // (a fresh record, not a copy of the previous bounce's: whatever the last bounce recorded was consumed — the shadow ray
     // started, the term applied — before this bounce runs, so the old values are dead here and not live across the traversal)
+    // ARMS: the record of a lane whose bounce records nothing is indeterminate (pt_device.h) instead of zero. (so, sd, smaxt) are
+    // written by the NEE arm and neeRaw by the lanes of it that set kShadowPending | kNeeValid; the readers are
+    //   trace_pair_flat (so, sd, smaxt): inv3_uniform's ballot, the inv_is_regular ballot, the leaf stage's final select, the
+    //     node walk's visited sets, `put` and stage 3's `nS > 0 && occluded` are all gated by hasShadow = kShadowPending, and a
+    //     lane's slab arithmetic on them ends in that select: nothing of them reaches LDS, a ballot or an address in a lane
+    //     without the flag;
+    //   apply_pending (neeRaw): `add ? sum : Li` with add = kShadowPending && kNeeValid && ...: the select drops it.
+    // Neither is part of the tile's state write-back. (neeBeta and neeW, read only without PRE, keep their fill: under PRE, which
+    // every pair kernel has, nothing reads them and the compiler drops it.)
     NeeRecord nr;
+    if constexpr (ARMS) {
+        nr.so = indeterminate3(); nr.sd = indeterminate3(); nr.smaxt = indeterminate(); nr.neeRaw = indeterminate3(); nr.neeBeta = v3(0.0f); nr.neeW = 0.0f;
+    } else {
     nr.so = v3(0.0f); nr.sd = v3(0.0f); nr.smaxt = 0.0f; nr.neeRaw = v3(0.0f); nr.neeBeta = v3(0.0f); nr.neeW = 0.0f;
+    }
     bool done = bounce_core<INTEG, COUNT, DEFER, SIMPLE, LEAN, PRE, LTRI, ARMS>(S, rng, o, d, beta, Li, prevPoint, woLocal, pdf, etaI, etaT, depth, msTop, flags, nr,
                                                  ms, h, maxDepth, useMIS, shadow, c, lightTri8);
     ps.rng = rng;

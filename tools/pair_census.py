@@ -2,7 +2,7 @@
 """Static instruction census of the pair pass (pt_trace.h: trace_pair_flat) inside the FLAT pair megakernels, read from the
 gfx950 device code with the Makefile's flags (hipcc -S, no GPU needed):
 
-    python tools/pair_census.py [--asm FILE.s] [--json]
+    python tools/pair_census.py [--asm FILE.s] [--json] [--runs]
 
 Regions of the kernel's bounce loop, found from the code itself:
   leaf loop   the loop that reads the leaf table through the scalar cache (s_load_dwordx8 of a leaf's box)
@@ -11,6 +11,13 @@ Regions of the kernel's bounce loop, found from the code itself:
 Counts per region by class: VALU, SALU (without s_nop / s_waitcnt / branches), branch, LDS, s_nop, s_waitcnt, v_readlane;
 and the trip loop's inner back edges (a loop inside the trip loop: the old "next ray" search), its exec-mask splits, and the
 longest chain of LDS reads in the set-up that each wait for the one before (lgkmcnt(0) between a ds_read and the next).
+
+Register moves (v_mov_b32 / v_mov_b64), under the key "moves" of a kernel, for the regions above and two more:
+  bounce_loop the loop that holds the leaf loop and the trip loop: one logic step and one pair pass
+  logic       the bounce loop's head up to the leaf loop: scheduling check, logic step, regeneration, the pair pass's head
+split by source (from_vgpr, from_const, from_sgpr), and the lengths of the runs of four or more consecutive moves (const_runs:
+those of them that load constants only). --runs lists every run with the first source line it maps to; for that the census
+compiles with line tables (-gline-tables-only), which the library's build never has.
 """
 import argparse
 import json
@@ -26,8 +33,10 @@ KERNELS = {"c2": "_ZN2pt16megakernel_flat2ILi0ELb1ELb0EEEvNS_7KParamsE",        
            "mixed": "_ZN2pt16megakernel_flat2ILi0ELb0ELb1EEEvNS_7KParamsE"}     # megakernel_flat2<0, false, true>: the mixed Cornell row
 
 
-def compile_asm(out):
+def compile_asm(out, lines=False):
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"]
+    if lines:
+        flags.append("-gline-tables-only")
     subprocess.check_call(["hipcc"] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "pt_mk_lds.hip")], stderr=subprocess.DEVNULL)
     return open(out).read()
 
@@ -139,20 +148,141 @@ def regions(lines):
     return out
 
 
+def move_source(s):
+    """"from_vgpr" / "from_const" / "from_sgpr" for a v_mov_b32 / v_mov_b64 (DPP and SDWA forms are cross-lane or partial: no moves), else None."""
+    t = s.split(None, 1)
+    if len(t) < 2 or t[0] not in ("v_mov_b32_e32", "v_mov_b64_e32", "v_mov_b32", "v_mov_b64", "v_mov_b32_e64", "v_mov_b64_e64"):
+        return None
+    src = t[1].split(";")[0].split(",", 1)[1].strip()
+    if src.startswith("v"):
+        return "from_vgpr"
+    if re.match(r"^(s\d|s\[|vcc|exec|ttmp|m0)", src):
+        return "from_sgpr"
+    return "from_const"
+
+
+def move_census(lines):
+    """Moves of a region by source, and its runs of four or more consecutive moves: (index of the first, [source, ...]).
+    zero_fill_runs: the runs that are `v_mov vN, 0` throughout; longest_zero_fill: the most such fills in a row anywhere."""
+    c = {"valu": 0, "v_mov": 0, "from_vgpr": 0, "from_const": 0, "from_sgpr": 0}
+    runs, zero, cur, text, start = [], [], [], [], 0
+    fills = longest = 0                                    # consecutive `v_mov vN, 0`, inside a longer run of moves or not
+    for i, ln in enumerate(list(lines) + ["\ts_endpgm"]):
+        if not is_insn(ln):
+            continue
+        s = ln.strip()
+        k = move_source(s)
+        if classify(s) == "valu":
+            c["valu"] += 1
+        fills = fills + 1 if k and re.search(r",\s*0$", s.split(";")[0].strip()) else 0
+        longest = max(longest, fills)
+        if k:
+            c["v_mov"] += 1
+            c[k] += 1
+            if not cur:
+                start = i
+            cur.append(k)
+            text.append(s.split(";")[0].strip())
+        else:
+            if len(cur) >= 4:
+                runs.append((start, cur))
+                if all(re.search(r",\s*0$", t) for t in text):
+                    zero.append(len(cur))
+            cur, text = [], []
+    c["runs"] = [len(r) for _, r in runs]
+    c["const_runs"] = [len(r) for _, r in runs if all(k == "from_const" for k in r)]
+    c["zero_fill_runs"] = zero
+    c["longest_zero_fill"] = longest
+    return c, runs
+
+
+def blocks(lines):
+    """[(first line, end line, label or None, annotation)] of the basic blocks: a block starts at a .LBB label or at the
+    compiler's `; %bb.N:` comment, and its annotation is what the compiler says there about the loops it is in."""
+    starts = [i for i, ln in enumerate(lines) if re.match(r"^\.LBB\d+_\d+:", ln) or re.match(r"^; %bb\.\d+:", ln)]
+    out = []
+    for n, i in enumerate(starts):
+        end = starts[n + 1] if n + 1 < len(starts) else len(lines)
+        note = lines[i].split(";", 1)[1] if ";" in lines[i] else ""
+        k = i + 1
+        while k < end and lines[k].strip().startswith(";") and not lines[k].startswith("; %bb."):
+            note += " " + lines[k]
+            k += 1
+        m = re.match(r"^\.L(BB\d+_\d+):", lines[i])
+        out.append((i, end, m.group(1) if m else None, note))
+    return out
+
+
+def bounce_loop(lines):
+    """(member line indices, leaf loop's header line) of the bounce loop: the innermost loop that holds both the leaf loop and
+    the trip loop, by the compiler's own loop annotations, so that blocks it lays out behind the back edge count as well."""
+    lp = loops(lines)
+    trip = [(h, e) for h, e in lp if all(any(op in lines[k] for k in range(h, e + 1)) for op in ("ds_min_u64", "v_ffbl_b32"))]
+    th, te = min(trip, key=lambda x: x[1] - x[0])
+    leaf = [(h, e) for h, e in lp if e < th and any("s_load_dwordx8" in lines[k] for k in range(h, e + 1))]
+    lh, le = min(leaf, key=lambda x: x[1] - x[0]) if leaf else (th, th)
+    bl = blocks(lines)
+    parents = {lab: [h for h, _ in re.findall(r"Parent Loop (BB\d+_\d+) Depth=(\d+)", note)] for _, _, lab, note in bl if lab}
+
+    def enclosing(lab, note):
+        """Headers of the loops a block is in, outermost first."""
+        hd = re.search(r"Header=(BB\d+_\d+)", note)
+        if hd:
+            return parents.get(hd.group(1), []) + [hd.group(1)]
+        return parents.get(lab, []) + [lab] if "Loop Header" in note else []
+
+    enc = {i: enclosing(lab, note) for i, _, lab, note in bl}
+    common = [h for h in enc[th] if h in enc[lh]]
+    assert common, "no loop around the leaf loop and the trip loop"
+    head = common[-1]
+    member = []
+    for i, end, lab, note in bl:
+        if head in enc[i]:
+            member.extend(range(i, end))
+    return member, lh
+
+
+def source_of(lines, i):
+    """The last .loc in front of line i (its comment: file:line:col and the inlining chain), or None without line tables."""
+    for k in range(i, -1, -1):
+        m = re.match(r"\s+\.loc\s.*?;\s*(.*)", lines[k])
+        if m:
+            return m.group(1).strip()
+    return None
+
+
+def move_regions(lines):
+    """{"bounce_loop": ..., "logic": ...}: move_census of the two regions, plus "run_list" (line, length, sources, first source line).
+    logic: the bounce loop's blocks laid out in front of the leaf loop."""
+    member, lh = bounce_loop(lines)
+    out = {}
+    for reg, idx in (("bounce_loop", member), ("logic", [i for i in member if i < lh])):
+        sub = [lines[i] for i in idx]
+        c, runs = move_census(sub)
+        c["total"] = census(sub)["total"]
+        c["run_list"] = [{"at": idx[st], "len": len(r), "from_const": r.count("from_const"), "from_vgpr": r.count("from_vgpr"),
+                          "from_sgpr": r.count("from_sgpr"), "first": sub[st].strip().split(";")[0].strip(), "source": source_of(lines, idx[st])}
+                         for st, r in runs]
+        out[reg] = c
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", help="device assembly of pt_mk_lds.hip (default: compile it now)")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--runs", action="store_true", help="list the runs of four or more consecutive moves with their first source line (compiles with line tables)")
     a = ap.parse_args()
     if a.asm:
         text = open(a.asm).read()
     else:
         with tempfile.TemporaryDirectory() as d:
-            text = compile_asm(os.path.join(d, "pt_mk_lds.s"))
+            text = compile_asm(os.path.join(d, "pt_mk_lds.s"), lines=a.runs)
     res = {}
     for key, name in KERNELS.items():
         lines = function(text, name)
-        res[key] = {"kernel": name, "metadata": metadata(text, name), "whole": census(lines), "regions": regions(lines)}
+        res[key] = {"kernel": name, "metadata": metadata(text, name), "whole": census(lines), "regions": regions(lines), "moves": move_regions(lines)}
+        res[key]["moves"]["whole"] = move_census(lines)[0]
     if a.json:
         json.dump(res, sys.stdout, indent=1)
         print()
@@ -161,6 +291,13 @@ def main():
         print("%s  %s  %s" % (key, r["kernel"], " ".join("%s=%s" % kv for kv in r["metadata"].items())))
         for reg, c in [("whole", r["whole"])] + list(r["regions"].items()):
             print("  %-10s %s" % (reg, " ".join("%s=%d" % kv for kv in c.items())))
+        for reg in ("whole", "bounce_loop", "logic"):
+            m = r["moves"][reg]
+            print("  moves %-11s %s runs=%s const_runs=%s zero_fill_runs=%s" % (reg, " ".join("%s=%d" % (k, m[k]) for k in ("total", "valu", "v_mov", "from_vgpr", "from_const", "from_sgpr", "longest_zero_fill") if k in m),
+                                                              m["runs"], m["const_runs"], m["zero_fill_runs"]))
+            if a.runs:
+                for x in m.get("run_list", []):
+                    print("    run of %2d (const %d, vgpr %d, sgpr %d) at line %d: %-28s %s" % (x["len"], x["from_const"], x["from_vgpr"], x["from_sgpr"], x["at"], x["first"], x["source"] or "-"))
 
 
 if __name__ == "__main__":
