@@ -121,6 +121,7 @@ RAY_DTYPE, RAY_HIT_DTYPE, RAY_SURFACE_DTYPE = _record_dtype(Ray), _record_dtype(
 _F4 = (4, np.float32)                # Scene._query's output of four floats per ray
 QUERY_REORDER = 1                    # PT_QUERY_REORDER
 QUERY_STREAM_PAD = 2                 # PT_QUERY_STREAM_PAD
+QUERY_TEXEL_CENTRE = 4               # PT_QUERY_TEXEL_CENTRE
 QUERY_MAX_T = 999999.0               # the max_t of the library's own closest-hit rays
 
 
@@ -235,6 +236,9 @@ def lib():
     L.pt_query_sh.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32]
     L.pt_query_sh_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.pt_query_sh_rays_device.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_query_distance.argtypes = [vp, i32, vp, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32]
+    L.pt_query_distance_device.argtypes = [vp, i32, vp, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
+    L.pt_query_distance_rays_device.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
     L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -914,13 +918,16 @@ class Scene:
         on the scene's device gives a tensor, on torch's current stream; numpy records are copied up and the rays come back as numpy."""
         return self._lane_rays("query_irradiance_rays", records, lanes, seed, first_stream, draw_offset, flags)
 
-    def _lane_rays(self, name, records, lanes, seed, first_stream, draw_offset, flags):
-        """query_irradiance_rays and query_sh_rays: pt_<name>_device on [n, 8] records, n * lanes rays out."""
+    def _lane_rays(self, name, records, lanes, seed, first_stream, draw_offset, flags, per_record=None):
+        """query_irradiance_rays, query_sh_rays and query_distance_rays: pt_<name>_device on [n, 8] records, n * per_record rays out.
+        `lanes` is the argument handed to C; per_record, the lanes a record has, is that number unless given (query_distance_rays
+        hands over res and has res * res)."""
         import torch
         is_torch, r, n = self._query_rays(name, records)
         dev = r.device if is_torch else torch.device("cuda", torch.cuda.current_device())
         d = r if is_torch else torch.from_numpy(r if r.flags.writeable else r.copy()).to(dev)
-        m = n * lanes if lanes > 0 else 0
+        per_record = lanes if per_record is None else per_record
+        m = n * per_record if per_record > 0 else 0
         off = None
         if draw_offset is not None:
             off = draw_offset if hasattr(draw_offset, "data_ptr") else torch.from_numpy(np.ascontiguousarray(draw_offset).astype(np.int32).reshape(-1))
@@ -958,6 +965,29 @@ class Scene:
         them for query_irradiance: ray i * lanes + l is lane l of record i, made of draws draw_offset[i * lanes + l] and the next of
         that lane's stream, with the record's max_t and, in its pad word, what the lane adds to first_stream."""
         return self._lane_rays("query_sh_rays", records, lanes, seed, first_stream, draw_offset, flags)
+
+    def query_distance(self, records, res, spp_lane=1, seed=SEED, first_stream=0, flags=0):
+        """pt_query_distance: a probe's octahedral map of hit-distance moments. records is [n, 8] float32 (probe position, max_t, three
+        words that are not read, pad: rays.distance_records, rays.sh_grid); each record runs on res * res lanes (res 4, 8, 16 or 32),
+        lane ty * res + tx being texel (tx, ty) on stream first_stream + i * res * res + ty * res + tx of `seed` (with flags =
+        QUERY_STREAM_PAD: the record's pad word for i), spp_lane samples per lane, each in a direction of its texel. With flags =
+        QUERY_TEXEL_CENTRE: one sample at the texel's centre, no random number. Returns [n, res, res, 4] float32, indexed [i, ty, tx]:
+        the sum of the samples' distances to the nearest surface (max_t where there is none), the sum of their squares, the number
+        that hit, and the number of those hits seen from behind (rays.distance_visibility and rays.grid_irradiance read the first
+        two). numpy in, numpy out (host form); a torch tensor on the scene's device in, a tensor out, on torch's current stream with
+        no host copy."""
+        cols = res * res * 4 if res in (4, 8, 16, 32) else 4          # (any other res is refused before anything is written)
+        out = self._query("query_distance", records, [(cols, np.float32)], lambda r, o: (r, res, spp_lane, seed, first_stream, o[0], flags),
+                          empty=(True, True))[0]
+        return out.reshape(out.shape[0], res, res, 4)
+
+    def query_distance_rays(self, records, res, seed=SEED, first_stream=0, draw_offset=None, flags=0):
+        """pt_query_distance_rays_device: the rays query_distance's samples start from, [n * res * res, 8] float32, as query_sh_rays
+        gives them for query_sh: ray i * res * res + l is lane l of record i, made of draws draw_offset[i * res * res + l] and the
+        next of that lane's stream (with QUERY_TEXEL_CENTRE: the texel's centre), with the record's max_t and, in its pad word, what
+        the lane adds to first_stream: query_closest on them is what a sample of query_distance sees."""
+        return self._lane_rays("query_distance_rays", records, res, seed, first_stream, draw_offset, flags,
+                               per_record=res * res if res in (4, 8, 16, 32) else 0)
 
     def query_guides(self, rays, max_links=0, links=False):
         """pt_query_guides: render_aovs_centre's guides for each of the caller's rays ([n, 8] float32: o, max_t, d, pad; d must be

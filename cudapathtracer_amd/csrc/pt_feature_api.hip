@@ -1,6 +1,6 @@
 // pt_feature_api.hip — the host side of the feature passes behind include/pt_api.h: their checks, launches and entry points, pt_pick,
 // and the ray queries. (The kernels: pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip, pt_query.hip, pt_query_guides.hip,
-// pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip, pt_sh.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
+// pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip, pt_sh.hip, pt_distance.hip; their launchers and block counts: pt_feature_host.h; the host forms' staging: pt_host.h.)
 #include "pt_host.h"
 #include "pt_feature_host.h"
 
@@ -576,6 +576,73 @@ int pt_query_sh_rays_device(pt_scene* s, int n, const void* d_records, int lanes
     if (int r = check_query_device(fn, s)) return r;
     HIP_OK(launch_sh_rays(n, d_records, log2_lanes(lanes), (const uint32_t*)s->data.jump.p, seed, first_stream, (flags & PT_QUERY_STREAM_PAD) != 0,
                           d_draw_offset, d_rays, (hipStream_t)stream));
+    return 0;
+}
+
+// Distance probes (pt_distance.hip: distance_kernel, distance_rays_kernel). Every message under the caller's name, all before any HIP
+// call, in the header's order, which is pt_query_sh's; n == 0 returns before the scene or anything else is looked at. walk:
+// pt_query_distance's checks; else pt_query_distance_rays_device's, which has no samples (`out` is its rays buffer).
+static int check_distance_args(const char* fn, bool walk, pt_scene* s, int n, const void* recs, const void* out, int res, int sppLane,
+                               uint32_t firstStream, uint32_t flags) {
+    const long long lanes = (long long)res * res;
+    if (n < 0 || (n > 0 && lanes > (1ll << 28)) || (long long)n * lanes > (1ll << 28)) return fail(-1, "%s: n %d at res %d must be 0..%d lanes in all", fn, n, res, 1 << 28);
+    if (n == 0) return 0;
+    if (!s) return fail(-1, "%s: null scene", fn);
+    if (!recs) return fail(-1, "%s: null records", fn);
+    if (!out) return fail(-1, "%s: null output buffer", fn);
+    if (res != 4 && res != 8 && res != 16 && res != 32) return fail(-1, "%s: res %d must be 4, 8, 16 or 32", fn, res);
+    if (walk && (sppLane < 1 || lanes * sppLane > (1ll << 22)))
+        return fail(-1, "%s: spp_lane %d at res %d must be 1..%d samples a record", fn, sppLane, res, 1 << 22);
+    if (flags & PT_QUERY_REORDER) return fail(-1, "%s: PT_QUERY_REORDER is not taken here: the library makes the rays itself", fn);
+    const uint32_t known = PT_QUERY_STREAM_PAD | PT_QUERY_TEXEL_CENTRE;
+    if (flags & ~known) return fail(-1, "%s: unknown flag bits 0x%x", fn, flags & ~known);
+    const bool centre = (flags & PT_QUERY_TEXEL_CENTRE) != 0;
+    if (walk && centre && sppLane != 1) return fail(-1, "%s: PT_QUERY_TEXEL_CENTRE has one sample a texel: spp_lane %d must be 1", fn, sppLane);
+    const unsigned long long end = (unsigned long long)firstStream + (unsigned long long)n * (unsigned long long)lanes;
+    if (!centre && !(flags & PT_QUERY_STREAM_PAD) && end > (1ull << 31)) return fail(-1, "%s: streams %u .. %llu pass 2^31", fn, firstStream, end - 1ull);
+    return 0;
+}
+
+static int query_distance(pt_scene* s, int n, const void* dRecs, int res, int sppLane, uint64_t seed, uint32_t firstStream, void* dMaps, uint32_t flags,
+                          hipStream_t stream) {
+    const bool centre = (flags & PT_QUERY_TEXEL_CENTRE) != 0;
+    const int log2R = log2_lanes(res);
+    const int blocks = feature_blocks(irradiance_tiles(n, 2 * log2R), s->dev.numCU, centre ? kDistanceCentreWavesPerSimd : kDistanceWavesPerSimd);
+    int32_t* spill;
+    if (int r = feature_spill(s, blocks, &spill)) return r;
+    HIP_OK(launch_distance(s->facts.ds, n, dRecs, log2R, (const uint32_t*)s->data.jump.p, seed, firstStream, (flags & PT_QUERY_STREAM_PAD) != 0, centre,
+                           sppLane, blocks, dMaps, spill, stream));
+    return 0;
+}
+
+int pt_query_distance_device(pt_scene* s, int n, const void* d_records, int res, int spp_lane, uint64_t seed, uint32_t first_stream, void* d_maps,
+                             uint32_t flags, void* stream) {
+    const char* fn = "pt_query_distance";
+    if (int r = check_distance_args(fn, true, s, n, d_records, d_maps, res, spp_lane, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    return query_distance(s, n, d_records, res, spp_lane, seed, first_stream, d_maps, flags, (hipStream_t)stream);
+}
+
+int pt_query_distance(pt_scene* s, int n, const pt_ray* records, int res, int spp_lane, uint64_t seed, uint32_t first_stream, float* maps4,
+                      uint32_t flags) {
+    const char* fn = "pt_query_distance";
+    if (int r = check_distance_args(fn, true, s, n, records, maps4, res, spp_lane, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    return staged_query(s->feat.queryOut, n, records, {{maps4, (size_t)n * res * res * sizeof(float4)}}, [&](const void* dRecs, void* const* d) {
+        return query_distance(s, n, dRecs, res, spp_lane, seed, first_stream, d[0], flags, nullptr);
+    });
+}
+
+int pt_query_distance_rays_device(pt_scene* s, int n, const void* d_records, int res, uint64_t seed, uint32_t first_stream, const void* d_skip,
+                                  void* d_rays, uint32_t flags, void* stream) {
+    const char* fn = "pt_query_distance_rays_device";
+    if (int r = check_distance_args(fn, false, s, n, d_records, d_rays, res, 1, first_stream, flags)) return r;
+    if (n == 0) return 0;
+    if (int r = check_query_device(fn, s)) return r;
+    HIP_OK(launch_distance_rays(n, d_records, log2_lanes(res), (const uint32_t*)s->data.jump.p, seed, first_stream, (flags & PT_QUERY_STREAM_PAD) != 0,
+                                (flags & PT_QUERY_TEXEL_CENTRE) != 0, d_skip, d_rays, (hipStream_t)stream));
     return 0;
 }
 

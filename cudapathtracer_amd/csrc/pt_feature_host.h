@@ -1,5 +1,5 @@
 // pt_feature_host.h — the host's view of the feature passes (pt_aov.hip, pt_motion.hip, pt_motion_chain.hip, pt_ids.hip) and of the ray
-// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip, pt_sh.hip): the tiling and block count every one of them is
+// queries (pt_query.hip, pt_query_guides.hip, pt_radiance.hip, pt_radiance_moments.hip, pt_irradiance.hip, pt_sh.hip, pt_distance.hip): the tiling and block count every one of them is
 // launched with, each kernel's waves per SIMD, and the launchers pt_feature_api.hip calls. The kernels' shared pieces are in
 // pt_feature.h, the radiance kernels' walk in pt_radiance.h.
 #pragma once
@@ -64,6 +64,9 @@ constexpr int irradiance_tiles(int n, int log2L) { return ((n << log2L) + 63) / 
 //   naive, LEAN      3: 96 / 0 / 51200                                    MIS, LEAN      3: 119 / 0 / 51200
 //   naive, generic   3: 96 / 0 / 51200                                    MIS, generic   3: 131 / 0 / 51200
 constexpr int sh_waves_per_simd(int integrator, bool simple, bool lean) { return std::min(radiance_waves_per_simd(integrator, simple, lean), 3); }
+constexpr int kDistanceWavesPerSimd = 7;         // distance_kernel<false> (pt_distance.hip): 66 VGPRs (the stream and the four sums stay live across
+                                                 // the trace), 16 KB of LDS, no scratch (tests/test_query_distance_api.py pins both)
+constexpr int kDistanceCentreWavesPerSimd = 8;   // distance_kernel<true>: without the stream 54 VGPRs, 8 x 16 KB of LDS
 constexpr int kQueryGuidesWavesPerSimd = 8;      // query_guides_kernel: 55 VGPRs, 8 x 16 KB of LDS, as the centre pass
 constexpr int kQueryGuidesChainWavesPerSimd = 6;  // query_guides_chain_kernel: 60 VGPRs, 23 KB of LDS: 7 workgroups would need 161 KB
 inline int feature_blocks(int nTiles, int numCU, int wavesPerSimd) { return std::max(1, std::min((nTiles + 3) / 4, numCU * wavesPerSimd)); }
@@ -133,6 +136,16 @@ hipError_t launch_sh(const DeviceScene& S, int integrator, bool simple, bool lea
 hipError_t launch_sh_reduce(int n, int log2L, const void* work, void* out, hipStream_t stream);
 hipError_t launch_sh_rays(int n, const void* recs, int log2L, const uint32_t* jump, unsigned long long seed, uint32_t firstStream, bool streamPad,
                           const void* skip, void* rays, hipStream_t stream);
+// pt_distance.hip: distance_kernel<centre> on n records (pt_ray: point, max_t; the direction words are not read) of R * R lanes each,
+// R = 1 << log2R in 4..32, lane l = ty * R + tx being texel (tx, ty) of the record's octahedral map, on launch_irradiance's streams
+// with log2L = 2 log2R; sppLane samples per lane: out[i * R * R + l] = (the sum of the samples' distances, of their squares, the hits,
+// the hits seen from behind). centre: one sample at the texel's centre; jump, seed, firstStream, streamPad and sppLane are not read.
+// blocks: feature_blocks of irradiance_tiles at kDistanceWavesPerSimd / kDistanceCentreWavesPerSimd. launch_distance_rays:
+// launch_irradiance_rays for these lanes (centre: skip is not read, the pad word is the lane's index in the launch).
+hipError_t launch_distance(const DeviceScene& S, int n, const void* recs, int log2R, const uint32_t* jump, unsigned long long seed, uint32_t firstStream,
+                           bool streamPad, bool centre, int sppLane, int blocks, void* out, int32_t* spill, hipStream_t stream);
+hipError_t launch_distance_rays(int n, const void* recs, int log2R, const uint32_t* jump, unsigned long long seed, uint32_t firstStream, bool streamPad,
+                                bool centre, const void* skip, void* rays, hipStream_t stream);
 // pt_query_guides.hip: n rays, lane i of tile t takes ray 64 t + i. maxLinks 0: the first-hit kernel (links, if set, gets zeros); else
 // the chain kernel. albedo[i] = (a, 1), normalDepth[i] = (n, summed path length), links[i] (NULL ok) the links followed; a miss: zeros.
 hipError_t launch_query_guides(const DeviceScene& S, int n, const void* rays, int maxLinks, int blocks, void* albedo, void* normalDepth, float* links,

@@ -8,6 +8,16 @@ directions and pad = 0: ray i then draws from stream first_stream + i.
 irradiance_records and records_from_surfaces make the records of Scene.query_irradiance in the same layout: a surface point where a
 ray has its origin, the unit normal where it has its direction. sh_records and sh_grid make the records of Scene.query_sh (a probe
 position; the direction words are not read); sh_basis and sh_irradiance evaluate what it returns.
+
+distance_records makes the records of Scene.query_distance (sh_records' layout with a max_t chosen for the lookups; sh_grid lays them
+out on the same grid as the SH probes). oct_decode and oct_encode are the call's octahedral map and its inverse, oct_border gives a
+map the gutter a seamless bilinear lookup needs, distance_visibility is the Chebyshev test of a point against a probe's map, and
+grid_irradiance mixes the eight probes around a point by trilinear weight times that visibility, so that a probe behind a wall
+stops lighting the point:
+
+    probes, near = rays.sh_grid(lo, hi, (8, 8, 8)), rays.sh_grid(lo, hi, (8, 8, 8), max_t=1.5 * cell_diagonal)
+    sums, maps = sc.query_sh(probes, 256, 4, 8), sc.query_distance(near, 8, spp_lane=4)
+    e = rays.grid_irradiance(lo, hi, (8, 8, 8), sums, 1024, points, normals, maps, 4)
 """
 import numpy as np
 
@@ -105,16 +115,151 @@ def sh_basis(d):
     return xp.stack([c0 + 0 * x, c1 * y, c1 * z, c1 * x, c2 * (x * y), c2 * (y * z), c3 * (3 * (z * z) - 1), c2 * (x * z), c4 * (x * x - y * y)], -1)
 
 
+def _sh_convolved(coeff_sums, samples):
+    """Scene.query_sh's sums [..., 9, 4] as irradiance coefficients [..., 9, 3]: scaled by 4 pi / samples, band l times the cosine
+    lobe's factor."""
+    xp = np if isinstance(coeff_sums, np.ndarray) else __import__("torch")
+    lobe = [SH_LOBE[0]] + [SH_LOBE[1]] * 3 + [SH_LOBE[2]] * 5
+    lobe = np.asarray(lobe, coeff_sums.dtype) if xp is np else xp.tensor(lobe, dtype=coeff_sums.dtype, device=coeff_sums.device)
+    return coeff_sums[..., :3] * (4.0 * np.pi / samples) * lobe[:, None]
+
+
 def sh_irradiance(coeff_sums, samples, normals):
     """Irradiance at unit `normals` [m, 3] from Scene.query_sh's sums [n, 9, 4] of `samples` = lanes * spp_lane samples each: the
     sums scaled by 4 pi / samples are the radiance coefficients, band l is convolved with the cosine lobe (pi, 2 pi / 3, pi / 4), and
     the series is evaluated at the normals. Returns [n, m, 3] in the units of pi * S / N of Scene.query_irradiance."""
     xp = np if isinstance(coeff_sums, np.ndarray) else __import__("torch")
-    lobe = [SH_LOBE[0]] + [SH_LOBE[1]] * 3 + [SH_LOBE[2]] * 5
-    lobe = np.asarray(lobe, coeff_sums.dtype) if xp is np else xp.tensor(lobe, dtype=coeff_sums.dtype, device=coeff_sums.device)
-    e = coeff_sums[..., :3] * (4.0 * np.pi / samples) * lobe[:, None]                  # [n, 9, 3]
+    e = _sh_convolved(coeff_sums, samples)                                             # [n, 9, 3]
     y = sh_basis(normals if xp is not np else np.asarray(normals, coeff_sums.dtype).reshape(-1, 3))     # [m, 9]
     return xp.einsum("nkc,mk->nmc", e, y.to(e.dtype) if xp is not np else y)
+
+
+def distance_records(points, max_t, device=None):
+    """Records for Scene.query_distance: sh_records' layout, [n, 8] float32 (probe position, max_t, three words the call does not
+    read, pad = 0) from [n, 3] points; sh_grid(lo, hi, counts, max_t) makes the same records on a grid. max_t is the distance a miss
+    counts with, and every hit beyond it clamps there: set it to the largest distance a lookup will ask about, for example 1.5
+    diagonals of a grid cell. With QUERY_MAX_T's 999999 one miss swamps a texel's mean and variance."""
+    return sh_records(points, max_t, device)
+
+
+def _xp_of(a):
+    return np if isinstance(a, np.ndarray) else __import__("torch")
+
+
+def oct_decode(uv):
+    """The octahedral map of pt_query_distance (include/pt_api.h) from points uv [..., 2] of the unit square to unit directions
+    [..., 3], in uv's dtype (numpy or torch): z is the fold axis, the square's centre +z, its corners -z."""
+    xp = _xp_of(uv)
+    fx, fy = 2 * uv[..., 0] - 1, 2 * uv[..., 1] - 1
+    ax, ay = xp.abs(fx), xp.abs(fy)
+    z = (1 - ax) - ay
+    x = xp.where(z < 0, xp.copysign(1 - ay, fx), fx)
+    y = xp.where(z < 0, xp.copysign(1 - ax, fy), fy)
+    il = 1 / xp.sqrt(x * x + y * y + z * z)
+    return xp.stack([x * il, y * il, z * il], -1)
+
+
+def oct_encode(d):
+    """oct_decode's inverse, from directions d [..., 3] (any length but 0) to points [..., 2] of the unit square: p = d / (|x| + |y| +
+    |z|); below the fold (z < 0) (x, y) = ((1 - |y|) sign x, (1 - |x|) sign y); uv = (p + 1) / 2. The sign of a zero is its sign
+    bit, so -z itself goes to the corner its zeros name."""
+    xp = _xp_of(d)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    s = xp.abs(x) + xp.abs(y) + xp.abs(z)
+    px, py = x / s, y / s
+    one = xp.ones_like(px)
+    qx = xp.where(z < 0, (1 - xp.abs(py)) * xp.copysign(one, x), px)
+    qy = xp.where(z < 0, (1 - xp.abs(px)) * xp.copysign(one, y), py)
+    return xp.stack([(qx + 1) / 2, (qy + 1) / 2], -1)
+
+
+def oct_border(maps):
+    """Octahedral maps [..., R, R, C] (indexed [ty, tx], as Scene.query_distance returns them) with a gutter of one texel:
+    [..., R + 2, R + 2, C]. Each gutter texel copies the interior texel the octahedral wrap of its centre reaches, so that a bilinear
+    lookup is seamless across the square's edges: u < 0 goes to (-u, 1 - v), u > 1 to (2 - u, 1 - v), v < 0 to (1 - u, -v), v > 1 to
+    (1 - u, 2 - v), and a corner, by both rules, to the diagonally opposite interior corner."""
+    xp = _xp_of(maps)
+    r = maps.shape[-2]
+    ty, tx = np.meshgrid(np.arange(-1, r + 1), np.arange(-1, r + 1), indexing="ij")
+    ty, tx = ty.copy(), tx.copy()
+    for out, flip in ((tx < 0, -1 - tx), (tx > r - 1, 2 * r - 1 - tx)):         # u outside: u mirrored at its edge, v at the middle
+        tx, ty = np.where(out, flip, tx), np.where(out, r - 1 - ty, ty)
+    for out, flip in ((ty < 0, -1 - ty), (ty > r - 1, 2 * r - 1 - ty)):
+        ty, tx = np.where(out, flip, ty), np.where(out, r - 1 - tx, tx)
+    if xp is not np:
+        ty, tx = xp.as_tensor(ty, device=maps.device), xp.as_tensor(tx, device=maps.device)
+    return maps[..., ty, tx, :]
+
+
+def distance_visibility(maps, samples, d, dist, power=3):
+    """How much of a probe a point at distance `dist` [...] in direction `d` [..., 3] from it sees, by Chebyshev's inequality on the
+    probe's map: maps [..., R, R, >= 2] are Scene.query_distance's sums of `samples` = spp_lane samples a texel, the leading shape
+    that of dist. (A, B) / samples is looked up bilinearly at oct_encode(d) on the bordered map, texel centres at (i + 0.5) / R, which
+    gives the mean distance m and the mean square; var = max(mean square - m * m, 0). The result is 1 where dist <= m, else
+    (var / (var + (dist - m)^2)) ** power, with 0 / 0 as 0. In maps' dtype."""
+    xp = _xp_of(maps)
+    r = maps.shape[-2]
+    lead = tuple(maps.shape[:-3])
+    b = (oct_border(maps[..., :2]) / samples).reshape((-1, r + 2, r + 2, 2))
+    uv = oct_encode(d).reshape((-1, 2))
+    dist = dist.reshape((-1,)) if hasattr(dist, "reshape") else dist
+    gx, gy = uv[:, 0] * r + 0.5, uv[:, 1] * r + 0.5                            # in texels of the bordered map, whose texel j has its centre at j
+    fl = (lambda v: np.clip(np.floor(v), 0, r).astype(np.int64)) if xp is np else (lambda v: xp.clamp(xp.floor(v), 0, r).to(xp.int64))
+    ix, iy = fl(gx), fl(gy)
+    wx, wy = (gx - ix)[:, None], (gy - iy)[:, None]
+    k = np.arange(len(ix)) if xp is np else xp.arange(len(ix), device=maps.device)
+    top = b[k, iy, ix] + wx * (b[k, iy, ix + 1] - b[k, iy, ix])                  # a + w (b - a): equal texels interpolate to themselves
+    bot = b[k, iy + 1, ix] + wx * (b[k, iy + 1, ix + 1] - b[k, iy + 1, ix])
+    m = top + wy * (bot - top)
+    mean, var = m[:, 0], m[:, 1] - m[:, 0] * m[:, 0]
+    var = xp.where(var > 0, var, 0 * var)
+    den = var + (dist - mean) * (dist - mean)
+    ratio = xp.where(den > 0, var / xp.where(den > 0, den, 1 + 0 * den), 0 * den)
+    return xp.where(dist <= mean, 1 + 0 * den, ratio ** power).reshape(lead)
+
+
+def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, maps=None, map_samples=None, power=3):
+    """Irradiance at `points` [m, 3] with unit `normals` [m, 3] from the probes of an sh_grid(lo, hi, counts): coeff_sums [n, 9, 4]
+    are Scene.query_sh's sums of sh_samples samples a probe, maps [n, R, R, >= 2] (optional) Scene.query_distance's of map_samples
+    samples a texel, both in the grid's order (x fastest). Per point the eight probes around it (clamped at the grid's faces) are
+    weighted trilinearly times distance_visibility of the point as seen from the probe, and the result is sum(w E_j(n)) / sum(w), E_j
+    being probe j's sh_irradiance at the point's normal. Without maps, or where the weights sum to less than 1e-6, the plain
+    trilinear mix. Returns [m, 3] in coeff_sums' dtype (numpy or torch)."""
+    xp = _xp_of(coeff_sums)
+    dt = coeff_sums.dtype
+    conv = (lambda v: np.asarray(v, dt)) if xp is np else (lambda v: xp.as_tensor(v, dtype=dt, device=coeff_sums.device))
+    p, nrm = conv(points).reshape((-1, 3)), conv(normals).reshape((-1, 3))
+    counts = [int(c) for c in counts]
+    i0, i1, f, pos = [], [], [], []
+    for a in range(3):
+        step = (float(hi[a]) - float(lo[a])) / (counts[a] - 1) if counts[a] > 1 else 0.0
+        g = (p[:, a] - float(lo[a])) / step if counts[a] > 1 else 0 * p[:, a]
+        lowc = np.clip(np.floor(g), 0, max(counts[a] - 2, 0)) if xp is np else xp.clamp(xp.floor(g), 0, max(counts[a] - 2, 0))
+        fa = np.clip(g - lowc, 0, 1) if xp is np else xp.clamp(g - lowc, 0, 1)
+        lowi = lowc.astype(np.int64) if xp is np else lowc.to(xp.int64)
+        i0.append(lowi); i1.append(lowi + 1 if counts[a] > 1 else lowi); f.append(fa); pos.append((float(lo[a]), step))
+    y = sh_basis(nrm)                                                               # [m, 9]
+    e = _sh_convolved(coeff_sums, sh_samples)                                       # [n, 9, 3]
+    num, den, plain = 0, 0, 0
+    for cz in (0, 1):
+        for cy in (0, 1):
+            for cx in (0, 1):
+                ix, iy, iz = (i1[0] if cx else i0[0]), (i1[1] if cy else i0[1]), (i1[2] if cz else i0[2])
+                tri = (f[0] if cx else 1 - f[0]) * (f[1] if cy else 1 - f[1]) * (f[2] if cz else 1 - f[2])
+                j = (iz * counts[1] + iy) * counts[0] + ix
+                ej = (e[j] * y[:, :, None]).sum(1)                                  # [m, 3]
+                plain = plain + tri[:, None] * ej
+                if maps is not None:
+                    at = xp.stack([pos[a][0] + pos[a][1] * (ix, iy, iz)[a] for a in range(3)], -1)      # the probe's position
+                    v = p - (at.astype(dt) if xp is np else at.to(dt))
+                    dist = xp.sqrt((v * v).sum(-1))
+                    d = xp.where((dist > 0)[:, None], v, conv([0.0, 0.0, 1.0])[None, :] + 0 * v)
+                    w = tri * distance_visibility(maps[j], map_samples, d, dist, power)
+                    num, den = num + w[:, None] * ej, den + w
+    if maps is None:
+        return plain
+    ok = den >= 1e-6
+    return xp.where(ok[:, None], num / xp.where(ok, den, 1 + 0 * den)[:, None], plain)
 
 
 def orthographic_rays(origin, forward, up, width, height, w, h, max_t=QUERY_MAX_T, device=None):

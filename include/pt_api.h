@@ -1484,6 +1484,60 @@ int pt_query_sh(pt_scene* scene, int n, const pt_ray* records, int lanes, int sp
 int pt_query_sh_rays_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int lanes, uint64_t seed, uint32_t first_stream,
                             const void* d_draw_offset /* n*lanes uint32, NULL = all 0 */, void* d_rays /* n*lanes pt_ray */, unsigned flags,
                             void* stream);                                                                                      /* async */
+/* pt_query_distance: a probe's octahedral map of hit-distance moments: what a probe volume's visibility (Chebyshev)
+ * test reads. About a point in free space the library makes directions texel by texel of an R x R octahedral map, finds the nearest
+ * surface in each, and sums per texel the distance and its square.
+ * Record. A pt_ray as pt_query_sh reads it: (ox, oy, oz) is the probe position p; max_t bounds every sample's ray, and is the distance
+ *   a miss counts with; the three direction words are NOT read; pad is read only with PT_QUERY_STREAM_PAD.
+ * Lanes and streams. res = R, one of 4, 8, 16, 32. Record i owns lanes i*R*R .. i*R*R + R*R-1 of the launch; lane l = ty*R + tx is
+ *   texel (tx, ty) and owns the XORWOW stream k = first_stream + i*R*R + l, or with PT_QUERY_STREAM_PAD first_stream + pad_i*R*R + l,
+ *   in uint32 arithmetic (it wraps), seeded as pt_query_radiance seeds a ray's: pt_query_irradiance's streams at L = R*R. Without the
+ *   flag first_stream + n*R*R must not pass 2^31. A lane runs spp_lane samples on its stream, one after the other. A 64-lane tile
+ *   holds four records at R = 4, one at R = 8, and a part of one at R >= 16.
+ * Sample. A sample draws u1, then u2 (the two draws cosine_sample_f would spend); the trace draws nothing, so sample j of a lane uses
+ *   draws 2j and 2j + 1 of its stream. With PT_QUERY_TEXEL_CENTRE u1 = u2 = 0.5 exactly, spp_lane must be 1, no stream is seeded,
+ *   and seed, first_stream and PT_QUERY_STREAM_PAD are not read.
+ *   DIRECTION ARITHMETIC, every operation rounded once to f32 in the order written, nothing fused but the two fmas of the dot. 1/R is exact.
+ *     px = ((float)tx + u1) * (1/R);   py = ((float)ty + u2) * (1/R)
+ *     fx = 2*px - 1;   fy = 2*py - 1;   ax = |fx|;   ay = |fy|;   z = (1 - ax) - ay
+ *     z < 0:  x = copysign(1 - ay, fx),  y = copysign(1 - ax, fy);   else  x = fx,  y = fy
+ *     dot = fma(z, z, fma(y, y, x*x));   il = 1 / sqrtf(dot) (both correctly rounded);   d = (x*il, y*il, z*il);   o = p
+ *   The octahedron |x| + |y| + |z| = 1 in world axes with z as its fold axis (the pole pt_query_sh's map has): the square's centre is
+ *   +z, its corners are -z, the middle of the edge u = 1 is +x and of v = 1 is +y.
+ * Trace. trace_closest with the record's max_t, exactly what pt_query_closest runs on the ray (o, d, max_t). r = the hit's t, or max_t
+ *   for a miss. `back` is the backface word pt_query_closest's surface record has for that hit, bit for bit.
+ * Output. maps[i*R*R + l] = (A, B, H, K) as a float4: A = ((0 + r_0) + r_1) + ..., B = ((0 + r_0*r_0) + r_1*r_1) + ... with each product
+ *   rounded first, H the number of the lane's samples that hit, K the number of those hits seen from behind, both as floats. The
+ *   call writes; it does not add and does not scale: the mean distance is A / spp_lane, the mean square B / spp_lane. K / H near 1
+ *   says the probe lies inside an object.
+ * pt_query_distance_rays_device: the tie to pt_query_closest, shaped as pt_query_sh_rays_device. Ray g = i*R*R + l is the (o, d) of the
+ *   sample of lane l of record i that draws draw_offset[g] and draw_offset[g] + 1 of the lane's stream (NULL: all 0, the lane's first
+ *   sample). It carries the record's max_t and, in its pad word, what the lane adds to first_stream: g, or pad_i*R*R + l with
+ *   PT_QUERY_STREAM_PAD. With PT_QUERY_TEXEL_CENTRE draw_offset is not read and the pad word is g. One thread per ray; of the scene it
+ *   reads the seeding tables only.
+ * Identity. With spp_lane = 1 a texel is (0 + r, 0 + r*r, hit, back) of pt_query_closest (with surfaces) on the ray
+ *   pt_query_distance_rays_device emits for that lane with the same seed, first_stream and flags. With more samples the stream runs
+ *   on: sample j is the ray emitted with draw_offset 2j.
+ * Independence. A record's map depends only on the scene, p, max_t, its stream base, R, spp_lane and seed: not on n, on its place in the
+ *   buffer, on which waves took its tiles or on what other records hold.
+ * What a call touches: the scene's feature spill area and, the host form, its query staging buffer. No RNG state, accumulator,
+ *   counter or tile queue of the scene. After any pt_scene_update_* a call sees the edited scene. The options "simple" and "lean" are
+ *   not read: there is one kernel per mode.
+ * Checked before any HIP call, -1 with a message under the function's name, in this order: n < 0 or n*R*R > 1 << 28 (n == 0 then
+ *   returns 0 before the scene or anything else is looked at); a NULL scene, records or maps (rays) buffer; res not one of 4, 8, 16,
+ *   32; spp_lane < 1 or R*R*spp_lane > 1 << 22; PT_QUERY_REORDER and unknown flag bits; PT_QUERY_TEXEL_CENTRE with spp_lane != 1;
+ *   without PT_QUERY_STREAM_PAD and without PT_QUERY_TEXEL_CENTRE, first_stream + n*R*R > 2^31. (The rays call has no samples to
+ *   check.) The device check comes last.
+ * d_records (n pt_ray), d_maps (n*R*R float4), d_rays (n*R*R pt_ray) and d_draw_offset (n*R*R uint32) are device buffers, the first
+ * three aligned to 16 bytes; the device forms are asynchronous on `stream`. */
+#define PT_QUERY_TEXEL_CENTRE 4u
+int pt_query_distance_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int res, int spp_lane, uint64_t seed,
+                             uint32_t first_stream, void* d_maps /* n*res*res float4 */, uint32_t flags, void* stream);        /* async */
+int pt_query_distance(pt_scene* scene, int n, const pt_ray* records, int res, int spp_lane, uint64_t seed, uint32_t first_stream,
+                      float* maps4 /* n*res*res*4 */, uint32_t flags);                                                          /* host, blocking */
+int pt_query_distance_rays_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int res, uint64_t seed, uint32_t first_stream,
+                                  const void* d_draw_offset /* n*res*res uint32, NULL = all 0 */, void* d_rays /* n*res*res pt_ray */,
+                                  uint32_t flags, void* stream);                                                                /* async */
 
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
