@@ -125,6 +125,11 @@ QUERY_TEXEL_CENTRE = 4               # PT_QUERY_TEXEL_CENTRE
 QUERY_MAX_T = 999999.0               # the max_t of the library's own closest-hit rays
 
 
+class GridDesc(C.Structure):         # pt_grid_desc
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("counts", C.c_int32 * 3), ("sh_samples", C.c_int32), ("map_res", C.c_int32),
+                ("map_samples", C.c_int32), ("power", C.c_int32)]
+
+
 class PreviewParams(C.Structure):    # pt_preview_params
     _fields_ = [("spp", C.c_int32), ("batches", C.c_int32), ("max_depth", C.c_int32), ("integrator", C.c_int32), ("use_mis", C.c_int32),
                 ("aov_spp", C.c_int32), ("temporal", C.c_int32), ("filter", C.c_int32), ("temporal_params", TemporalParams),
@@ -239,6 +244,11 @@ def lib():
     L.pt_query_distance.argtypes = [vp, i32, vp, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32]
     L.pt_query_distance_device.argtypes = [vp, i32, vp, i32, i32, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
     L.pt_query_distance_rays_device.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.pt_grid_packed_bytes.restype = C.c_size_t; L.pt_grid_packed_bytes.argtypes = [C.POINTER(GridDesc)]
+    L.pt_grid_pack.argtypes = [C.POINTER(GridDesc), vp, vp, vp]
+    L.pt_grid_pack_device.argtypes = [C.POINTER(GridDesc), vp, vp, vp, vp]
+    L.pt_grid_irradiance.argtypes = [C.POINTER(GridDesc), vp, i32, vp, vp]
+    L.pt_grid_irradiance_device.argtypes = [C.POINTER(GridDesc), vp, i32, vp, vp, vp]
     L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
     L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -2113,6 +2123,144 @@ class Preview:
             self.close()
         except Exception:
             pass
+
+
+def grid_desc(lo, hi, counts, sh_samples, map_res=0, map_samples=1, power=3):
+    """A pt_grid_desc: the grid of rays.sh_grid(lo, hi, counts), the samples Scene.query_sh spent on a probe (lanes * spp_lane), and,
+    for a grid with distance maps, Scene.query_distance's res and spp_lane and the exponent of the Chebyshev test."""
+    d = GridDesc()
+    d.lo[:], d.hi[:], d.counts[:] = [float(v) for v in lo], [float(v) for v in hi], [int(v) for v in counts]
+    d.sh_samples, d.map_res, d.map_samples, d.power = int(sh_samples), int(map_res), int(map_samples), int(power)
+    return d
+
+
+def grid_packed_bytes(desc):
+    """pt_grid_packed_bytes: the size of the packed buffer of a grid, or PtError for a desc the library refuses."""
+    n = int(lib().pt_grid_packed_bytes(C.byref(desc)))
+    if not n:
+        _check(-1, "pt_grid_packed_bytes")
+    return n
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+
+def _grid_input(what, name, a, words, like=None):
+    """A float32 input of `words` words: a C-contiguous numpy array for the host form, or, with `like` a tensor, a contiguous tensor
+    on its device for the device form."""
+    if like is not None:
+        import torch
+        if not (_is_tensor(a) and a.is_cuda and a.device == like.device and a.dtype == torch.float32 and a.is_contiguous()):
+            raise PtError("%s: %s must be a contiguous float32 tensor on %s" % (what, name, like.device))
+        if a.device.index != torch.cuda.current_device():
+            raise PtError("%s: %s is on %s but the current device is %d" % (what, name, a.device, torch.cuda.current_device()))
+        got = a.numel()
+    else:
+        if _is_tensor(a):
+            raise PtError("%s: %s is a tensor but the call's other arrays are numpy" % (what, name))
+        a = np.ascontiguousarray(a, np.float32)
+        got = a.size
+    if got != words:
+        raise PtError("%s: %s holds %d float32 words, the grid needs %d" % (what, name, got, words))
+    return a
+
+
+def grid_pack(desc, coeff_sums, maps=None):
+    """pt_grid_pack: Scene.query_sh's sums [n, 9, 4] and, for a grid with maps (desc.map_res = R), Scene.query_distance's maps
+    [n, R, R, 4] of the n probes of rays.sh_grid, as the packed buffer grid_irradiance reads: a 1-D float32 array of
+    grid_packed_bytes(desc) / 4 words. numpy in, numpy out (host form); torch tensors on the current HIP device in, a tensor out, on
+    torch's current stream with no host copy."""
+    words = grid_packed_bytes(desc) // 4
+    n, r = desc.counts[0] * desc.counts[1] * desc.counts[2], desc.map_res
+    if (maps is None) != (r == 0):
+        raise PtError("grid_pack: maps are %s but desc.map_res is %d" % ("missing" if maps is None else "given", r))
+    like = coeff_sums if _is_tensor(coeff_sums) else None
+    s = _grid_input("grid_pack", "coeff_sums", coeff_sums, n * 36, like)
+    m = None if maps is None else _grid_input("grid_pack", "maps", maps, n * r * r * 4, like)
+    if like is not None:
+        import torch
+        packed = torch.empty(words, dtype=torch.float32, device=s.device)
+        _check(lib().pt_grid_pack_device(C.byref(desc), s.data_ptr(), m.data_ptr() if m is not None else None, packed.data_ptr(),
+                                         torch.cuda.current_stream(s.device).cuda_stream or None), "pt_grid_pack_device")
+    else:
+        packed = np.zeros(words, np.float32)
+        _check(lib().pt_grid_pack(C.byref(desc), _p(s), _p(m), _p(packed)), "pt_grid_pack")
+    return packed
+
+
+def grid_irradiance(packed, desc, records):
+    """pt_grid_irradiance: the irradiance at surface points from a packed probe grid. records is [m, 8] float32 (point, a word that
+    is not read, unit normal, a word that is not read: rays.irradiance_records, rays.records_from_surfaces); packed is grid_pack's
+    buffer of the same desc. Returns [m, 4] float32: (E_r, E_g, E_b, W) in rays.grid_irradiance's units, W the weight sum E was
+    divided by; exact zeros for a record whose point or normal is not finite. numpy in, numpy out (host form); tensors on the
+    current HIP device in, a tensor out, on torch's current stream with no host copy."""
+    is_torch, r, m = Scene._query_rays("grid_irradiance", records)
+    p = _grid_input("grid_irradiance", "packed", packed, grid_packed_bytes(desc) // 4, r if is_torch else None)
+    if is_torch:
+        import torch
+        out = torch.empty((m, 4), dtype=torch.float32, device=r.device)
+        if m:
+            _check(lib().pt_grid_irradiance_device(C.byref(desc), p.data_ptr(), m, r.data_ptr(), out.data_ptr(),
+                                                   torch.cuda.current_stream(r.device).cuda_stream or None), "pt_grid_irradiance_device")
+    else:
+        out = np.zeros((m, 4), np.float32)
+        _check(lib().pt_grid_irradiance(C.byref(desc), _p(p), m, _p(r), _p(out)), "pt_grid_irradiance")
+    return out
+
+
+class ProbeGrid:
+    """A baked probe volume over a scene: the SH probes and distance maps of a rays.sh_grid(lo, hi, counts), packed for lookups.
+
+        grid = ProbeGrid(sc, lo, hi, (8, 8, 8)).bake(256, 4, 8, map_spp=4)
+        e = grid.shade(sc.query_closest(sc.query_camera_rays(cam, w, h), surfaces=True)[1])[:, :3]
+
+    res is the distance maps' resolution (4, 8, 16 or 32), or 0 for a grid without maps (a plain trilinear mix); max_t the distance
+    the maps clamp at, by default 1.5 diagonals of a grid cell. With device=True the queries, the pack and the buffers stay on the
+    current HIP device as torch tensors; otherwise they are numpy and lookups take numpy."""
+
+    def __init__(self, scene, lo, hi, counts, res=8, max_t=None, device=False):
+        self.scene, self.lo, self.hi, self.counts = scene, [float(v) for v in lo], [float(v) for v in hi], [int(c) for c in counts]
+        self.res, self.device = int(res), bool(device)
+        cell = [(b - a) / (c - 1) for a, b, c in zip(self.lo, self.hi, self.counts) if c > 1]
+        self.max_t = float(max_t) if max_t is not None else 1.5 * float(np.sqrt(sum(v * v for v in cell)))
+        self.desc = self.sums = self.maps = self.packed = None
+
+    def _where(self):
+        if not self.device:
+            return None
+        import torch
+        return "cuda:%d" % torch.cuda.current_device()
+
+    def bake(self, lanes, spp_lane, max_depth, map_spp=1, power=3, seed=SEED, integrator=UNIDIRECTIONAL, use_mis=True, map_flags=0):
+        """Scene.query_sh (lanes x spp_lane samples a probe, paths of max_depth) and, with maps, Scene.query_distance (map_spp samples
+        a texel, flags map_flags) on the grid's records, then grid_pack. Keeps the sums, the maps and the packed buffer; returns self."""
+        from . import rays
+        self.sums = self.scene.query_sh(rays.sh_grid(self.lo, self.hi, self.counts, device=self._where()), lanes, spp_lane, max_depth, integrator, use_mis, seed)
+        self.maps = None
+        if self.res:
+            self.maps = self.scene.query_distance(rays.sh_grid(self.lo, self.hi, self.counts, self.max_t, self._where()), self.res, map_spp, seed,
+                                                  flags=map_flags)
+        self.desc = grid_desc(self.lo, self.hi, self.counts, lanes * spp_lane, self.res, map_spp, power)
+        self.packed = grid_pack(self.desc, self.sums, self.maps)
+        return self
+
+    def lookup(self, records):
+        """grid_irradiance on the baked grid: [m, 4] (E_r, E_g, E_b, W) for [m, 8] records."""
+        if self.packed is None:
+            raise PtError("ProbeGrid: bake() has not run")
+        return grid_irradiance(self.packed, self.desc, records)
+
+    def irradiance(self, points, normals):
+        """The lookup at `points` [m, 3] with unit `normals` [m, 3]."""
+        from . import rays
+        return self.lookup(rays.irradiance_records(points, normals, device=self._where()))
+
+    def shade(self, surfaces):
+        """The lookup at Scene.query_closest(..., surfaces=True)'s surfaces (rays.records_from_surfaces). A ray that missed has the
+        record (0, 0, 0), normal (0, 0, 1) and is looked up there: mask it by its material word."""
+        from . import rays
+        return self.lookup(rays.records_from_surfaces(surfaces))
 
 
 def adaptive_params(min_spp, max_spp, chunk_spp, threshold):

@@ -1,0 +1,276 @@
+// pt_grid.hip — the lookup side of a probe volume (pt_grid_packed_bytes, pt_grid_pack[_device], pt_grid_irradiance[_device];
+// include/pt_api.h): irradiance at surface points from a regular grid of pt_query_sh's SH probes, each weighted
+// trilinearly times the Chebyshev visibility its pt_query_distance map gives the point. Scene-free, stateless, no workspace:
+// arrays in, arrays out, as the post-process calls. include/pt_api.h states the arithmetic; tests/grid_ref.py restates it in numpy.
+//   grid_pack_kernel          one thread per coefficient row (n * 9: the sums scaled and convolved with the cosine lobe) and per texel of
+//                             the bordered maps (n * (R + 2)^2: the means, the gutter copied by rays.oct_border's rule)
+//   grid_irradiance_kernel<MAPS>   one lane per record: the cell and its three fractions, the nine basis values at the normal, then the
+//                             eight corners in turn: nine float4 of coefficients and, with MAPS, four float2 taps of the probe's
+//                             bordered map, a plain bilinear fetch with no wrap logic. No LDS. The plain form carries no map code.
+//                             Neighbouring records mostly share their cell: when a ballot says that every lane of the wave has the
+//                             same one, the cell's index goes to SGPRs and the coefficients arrive by scalar loads (measured: §29).
+// Every min and max is v_min_f32 / v_max_f32, which drop a NaN operand: every index is in range whatever a record holds.
+#include <cmath>
+
+#include "../../include/pt_api.h"
+#include "pt_device.h"
+#include "pt_postfx_host.h"
+
+namespace pt {
+
+struct GridParams {
+    float lo[3], inv[3], step[3], top[3];       // top = (float)max(counts - 2, 0); inv = step = 0 on an axis with one probe
+    int counts[3];
+    int n;                                      // probes
+    int R, power;
+    float Rf;
+    float scale, mapSamples;                    // the pack's
+};
+
+constexpr float kShC0 = 0.2820948f, kShC1 = 0.4886025f, kShC2 = 1.0925484f, kShC3 = 0.3153916f, kShC4 = 0.5462742f;    // include/pt_api.h
+
+__global__ void __launch_bounds__(256) grid_pack_kernel(GridParams G, const float4* __restrict__ sums, const float4* __restrict__ maps,
+                                                        float4* __restrict__ coeff, float2* __restrict__ texels) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t rows = (size_t)G.n * 9;
+    if (g < rows) {
+        const int k = (int)(g % 9);
+        const float lobe = k == 0 ? 3.14159265358979323846f : (k < 4 ? 2.09439510239319549231f : 0.78539816339744830962f);
+        const float4 c = sums[g];
+        coeff[g] = make_float4((c.x * G.scale) * lobe, (c.y * G.scale) * lobe, (c.z * G.scale) * lobe, 0.0f);
+        return;
+    }
+    const int R = G.R, B = R + 2;
+    const size_t t = g - rows;
+    if (R == 0 || t >= (size_t)G.n * B * B) return;
+    const size_t j = t / ((size_t)B * B);
+    const int l = (int)(t - j * B * B);
+    int sx = l % B - 1, sy = l / B - 1;
+    if (sx < 0) { sx = -1 - sx; sy = R - 1 - sy; } else if (sx > R - 1) { sx = 2 * R - 1 - sx; sy = R - 1 - sy; }
+    if (sy < 0) { sy = -1 - sy; sx = R - 1 - sx; } else if (sy > R - 1) { sy = 2 * R - 1 - sy; sx = R - 1 - sx; }
+    const float4 a = maps[j * R * R + (size_t)sy * R + sx];
+    texels[t] = make_float2(a.x / G.mapSamples, a.y / G.mapSamples);
+}
+
+PT_DEV bool finite_(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// The Chebyshev visibility of a point at `v` from a probe whose bordered map starts at `map` (include/pt_api.h, step 5).
+PT_DEV float grid_visibility(const GridParams& G, const float2* __restrict__ map, V3 v) {
+    const float dist = __builtin_sqrtf(dot(v, v));
+    const V3 d = dist > 0.0f ? v : v3(0.0f, 0.0f, 1.0f);
+    const float s = (__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z);
+    const float px = d.x / s, py = d.y / s;
+    float qx = px, qy = py;
+    if (d.z < 0.0f) {
+        qx = (1.0f - __builtin_fabsf(py)) * __builtin_copysignf(1.0f, d.x);
+        qy = (1.0f - __builtin_fabsf(px)) * __builtin_copysignf(1.0f, d.y);
+    }
+    const float gx = ((qx + 1.0f) * 0.5f) * G.Rf + 0.5f, gy = ((qy + 1.0f) * 0.5f) * G.Rf + 0.5f;
+    const float ix = fminf_(fmaxf_(__builtin_floorf(gx), 0.0f), G.Rf), iy = fminf_(fmaxf_(__builtin_floorf(gy), 0.0f), G.Rf);
+    const float wx = gx - ix, wy = gy - iy;
+    const float2* row = map + (int)iy * (G.R + 2) + (int)ix;
+    const float2 t00 = row[0], t10 = row[1], t01 = row[G.R + 2], t11 = row[G.R + 3];
+    const float topM = t00.x + wx * (t10.x - t00.x), topQ = t00.y + wx * (t10.y - t00.y);
+    const float botM = t01.x + wx * (t11.x - t01.x), botQ = t01.y + wx * (t11.y - t01.y);
+    const float mean = topM + wy * (botM - topM), m2 = topQ + wy * (botQ - topQ);
+    float var = m2 - mean * mean;
+    var = var > 0.0f ? var : 0.0f;
+    const float t = dist - mean;
+    const float den = var + t * t;
+    const float ratio = den > 0.0f ? var / den : 0.0f;
+    float vis = ratio;
+    for (int k = 1; k < G.power; k++) vis = vis * ratio;
+    return dist <= mean ? 1.0f : vis;
+}
+
+// The eight corners of a record's cell (include/pt_api.h, steps 4 to 6) from its lowest probe `low` and the fractions f. Inlined twice:
+// with `low` in SGPRs the nine coefficient rows of a corner are scalar loads.
+template <bool MAPS>
+PT_DEV float4 grid_corners(const GridParams& G, const float4* __restrict__ coeff, const float2* __restrict__ texels, const float (&p)[3],
+                           const float (&y)[9], const int (&low)[3], const float (&f)[3]) {
+    float plain[3] = {0.0f, 0.0f, 0.0f}, num[3] = {0.0f, 0.0f, 0.0f}, W = 0.0f;
+    const int B2 = (G.R + 2) * (G.R + 2);
+#pragma nounroll
+    for (int c = 0; c < 8; c++) {
+        const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
+        const int ix = low[0] + (G.counts[0] > 1 ? cx : 0), iy = low[1] + (G.counts[1] > 1 ? cy : 0), iz = low[2] + (G.counts[2] > 1 ? cz : 0);
+        const float tri = ((cx ? f[0] : 1.0f - f[0]) * (cy ? f[1] : 1.0f - f[1])) * (cz ? f[2] : 1.0f - f[2]);
+        const int j = (iz * G.counts[1] + iy) * G.counts[0] + ix;
+        const float4* E = coeff + (size_t)j * 9;
+        const float4 e0 = E[0];
+        float e[3] = {e0.x * y[0], e0.y * y[0], e0.z * y[0]};
+#pragma unroll
+        for (int k = 1; k < 9; k++) {
+            const float4 ek = E[k];
+            e[0] = __builtin_fmaf(ek.x, y[k], e[0]); e[1] = __builtin_fmaf(ek.y, y[k], e[1]); e[2] = __builtin_fmaf(ek.z, y[k], e[2]);
+        }
+        for (int ch = 0; ch < 3; ch++) plain[ch] = __builtin_fmaf(tri, e[ch], plain[ch]);
+        if constexpr (MAPS) {
+            const V3 at = v3(__builtin_fmaf((float)ix, G.step[0], G.lo[0]), __builtin_fmaf((float)iy, G.step[1], G.lo[1]),
+                             __builtin_fmaf((float)iz, G.step[2], G.lo[2]));
+            const float w = tri * grid_visibility(G, texels + (size_t)j * B2, v3(p[0], p[1], p[2]) - at);
+            for (int ch = 0; ch < 3; ch++) num[ch] = __builtin_fmaf(w, e[ch], num[ch]);
+            W = W + w;
+        } else {
+            W = W + tri;
+        }
+    }
+    if (MAPS && W >= 1e-6f) return make_float4(num[0] / W, num[1] / W, num[2] / W, W);
+    return make_float4(plain[0], plain[1], plain[2], W);
+}
+
+template <bool MAPS>
+__global__ void __launch_bounds__(256) grid_irradiance_kernel(GridParams G, const float4* __restrict__ coeff, const float2* __restrict__ texels,
+                                                              int m, const float4* __restrict__ recs, float4* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)m) return;
+    const float4 a = recs[2 * i], b = recs[2 * i + 1];
+    if (!(finite_(a.x) && finite_(a.y) && finite_(a.z) && finite_(b.x) && finite_(b.y) && finite_(b.z))) {
+        out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float p[3] = {a.x, a.y, a.z};
+    int low[3];
+    float f[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ax++) {
+        low[ax] = 0; f[ax] = 0.0f;
+        if (G.counts[ax] > 1) {
+            const float g = (p[ax] - G.lo[ax]) * G.inv[ax];
+            const float l = fminf_(fmaxf_(__builtin_floorf(g), 0.0f), G.top[ax]);
+            low[ax] = (int)l;
+            f[ax] = fminf_(fmaxf_(g - l, 0.0f), 1.0f);
+        }
+    }
+    const float nx = b.x, ny = b.y, nz = b.z;
+    const float y[9] = {kShC0, kShC1 * ny, kShC1 * nz, kShC1 * nx, kShC2 * (nx * ny), kShC2 * (ny * nz), kShC3 * (3.0f * (nz * nz) - 1.0f),
+                        kShC2 * (nx * nz), kShC4 * (nx * nx - ny * ny)};
+    const int cell = (low[2] * G.counts[1] + low[1]) * G.counts[0] + low[0];
+    if (__builtin_amdgcn_ballot_w64(cell != __builtin_amdgcn_readfirstlane(cell)) == 0) {
+        const int u[3] = {__builtin_amdgcn_readfirstlane(low[0]), __builtin_amdgcn_readfirstlane(low[1]), __builtin_amdgcn_readfirstlane(low[2])};
+        out[i] = grid_corners<MAPS>(G, coeff, texels, p, y, u, f);
+        return;
+    }
+    out[i] = grid_corners<MAPS>(G, coeff, texels, p, y, low, f);
+}
+
+// The desc's checks in the header's order; on success G holds what the kernels read.
+static int grid_params(const char* fn, const pt_grid_desc* d, GridParams& G) {
+    if (!d) return postfx_fail_fn(-1, fn, "null desc");
+    const int32_t* c3 = d->counts;
+    if (c3[0] < 1 || c3[1] < 1 || c3[2] < 1) return postfx_fail_fn(-1, fn, "counts %d x %d x %d must be at least 1 each", c3[0], c3[1], c3[2]);
+    const long long n = (long long)c3[0] * c3[1] > (1ll << 22) ? (1ll << 23) : (long long)c3[0] * c3[1] * c3[2];
+    if (n > (1ll << 22)) return postfx_fail_fn(-1, fn, "counts %d x %d x %d make more than %d probes", c3[0], c3[1], c3[2], 1 << 22);
+    for (int a = 0; a < 3; a++) {
+        if (!std::isfinite(d->lo[a]) || !std::isfinite(d->hi[a])) return postfx_fail_fn(-1, fn, "corner lo[%d] = %g, hi[%d] = %g is not finite", a, d->lo[a], a, d->hi[a]);
+        if (d->counts[a] > 1 && !(d->hi[a] > d->lo[a])) return postfx_fail_fn(-1, fn, "hi[%d] = %g must be above lo[%d] = %g", a, d->hi[a], a, d->lo[a]);
+    }
+    if (d->sh_samples < 1) return postfx_fail_fn(-1, fn, "sh_samples %d must be at least 1", d->sh_samples);
+    const int R = d->map_res;
+    if (R != 0 && R != 4 && R != 8 && R != 16 && R != 32) return postfx_fail_fn(-1, fn, "map_res %d must be 0, 4, 8, 16 or 32", R);
+    if (R != 0 && d->map_samples < 1) return postfx_fail_fn(-1, fn, "map_samples %d must be at least 1", d->map_samples);
+    if (d->power < 1 || d->power > 8) return postfx_fail_fn(-1, fn, "power %d must be 1..8", d->power);
+    for (int a = 0; a < 3; a++) {
+        const int c = d->counts[a];
+        const double span = (double)d->hi[a] - (double)d->lo[a];
+        G.lo[a] = d->lo[a];
+        G.inv[a] = c > 1 ? (float)((c - 1) / span) : 0.0f;
+        G.step[a] = c > 1 ? (float)(span / (c - 1)) : 0.0f;
+        G.top[a] = (float)(c > 1 ? c - 2 : 0);
+        G.counts[a] = c;
+    }
+    G.n = (int)n;
+    G.R = R; G.Rf = (float)R; G.power = d->power;
+    G.scale = (float)(4.0 * 3.14159265358979323846 / (double)d->sh_samples);
+    G.mapSamples = (float)d->map_samples;
+    return 0;
+}
+
+static size_t grid_coeff_bytes(const GridParams& G) { return (size_t)G.n * 9 * sizeof(float4); }
+static size_t grid_texels(const GridParams& G) { return G.R ? (size_t)G.n * (G.R + 2) * (G.R + 2) : 0; }
+static size_t grid_bytes(const GridParams& G) { return grid_coeff_bytes(G) + grid_texels(G) * sizeof(float2); }
+
+static int grid_pack_launch(const GridParams& G, const void* sums, const void* maps, void* packed, hipStream_t stream) {
+    const size_t threads = (size_t)G.n * 9 + grid_texels(G);
+    hipLaunchKernelGGL(grid_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, G, (const float4*)sums, (const float4*)maps,
+                       (float4*)packed, (float2*)((char*)packed + grid_coeff_bytes(G)));
+    POSTFX_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int grid_pack_run(const char* fn, const pt_grid_desc* desc, const void* sums, const void* maps, void* packed, bool host, hipStream_t stream) {
+    GridParams G;
+    if (int r = grid_params(fn, desc, G)) return r;
+    if (!sums) return postfx_fail_fn(-1, fn, "null coeff_sums");
+    if (!packed) return postfx_fail_fn(-1, fn, "null packed buffer");
+    if (G.R == 0 && maps) return postfx_fail_fn(-1, fn, "maps given although map_res is 0");
+    if (G.R != 0 && !maps) return postfx_fail_fn(-1, fn, "null maps although map_res is %d", G.R);
+    const size_t sumBytes = grid_coeff_bytes(G), mapBytes = (size_t)G.n * G.R * G.R * sizeof(float4);
+    if (!host) {
+        if (overlaps(packed, grid_bytes(G), sums, sumBytes) || (maps && overlaps(packed, grid_bytes(G), maps, mapBytes)))
+            return postfx_fail_fn(-1, fn, "the packed buffer overlaps an input");
+        return grid_pack_launch(G, sums, maps, packed, stream);
+    }
+    const HostIn in[] = {{sums, sumBytes}, {maps, mapBytes}};
+    const HostOut out[] = {{packed, grid_bytes(G)}};
+    return postfx_host_form(fn, 0, in, out, [&](char*, char** dIn, char** dOut) { return grid_pack_launch(G, dIn[0], dIn[1], dOut[0], nullptr); });
+}
+
+static int grid_irradiance_launch(const GridParams& G, const void* packed, int m, const void* recs, void* out, hipStream_t stream) {
+    const float4* coeff = (const float4*)packed;
+    const float2* texels = (const float2*)((const char*)packed + grid_coeff_bytes(G));
+    const dim3 grid((unsigned)(((size_t)m + 255) / 256)), block(256);
+    if (G.R) hipLaunchKernelGGL(grid_irradiance_kernel<true>, grid, block, 0, stream, G, coeff, texels, m, (const float4*)recs, (float4*)out);
+    else hipLaunchKernelGGL(grid_irradiance_kernel<false>, grid, block, 0, stream, G, coeff, texels, m, (const float4*)recs, (float4*)out);
+    POSTFX_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int grid_irradiance_run(const char* fn, const pt_grid_desc* desc, const void* packed, int m, const void* recs, void* out, bool host,
+                               hipStream_t stream) {
+    GridParams G;
+    if (int r = grid_params(fn, desc, G)) return r;
+    if (m < 0) return postfx_fail_fn(-1, fn, "m %d must not be negative", m);
+    if (m == 0) return 0;
+    if (!packed) return postfx_fail_fn(-1, fn, "null packed buffer");
+    if (!recs) return postfx_fail_fn(-1, fn, "null records");
+    if (!out) return postfx_fail_fn(-1, fn, "null output buffer");
+    const size_t recBytes = (size_t)m * 32, outBytes = (size_t)m * 16;
+    if (!host) {
+        if (overlaps(out, outBytes, recs, recBytes) || overlaps(out, outBytes, packed, grid_bytes(G)))
+            return postfx_fail_fn(-1, fn, "the output buffer overlaps an input");
+        return grid_irradiance_launch(G, packed, m, recs, out, stream);
+    }
+    const HostIn in[] = {{packed, grid_bytes(G)}, {recs, recBytes}};
+    const HostOut o[] = {{out, outBytes}};
+    return postfx_host_form(fn, 0, in, o, [&](char*, char** dIn, char** dOut) { return grid_irradiance_launch(G, dIn[0], m, dIn[1], dOut[0], nullptr); });
+}
+
+}  // namespace pt
+
+using namespace pt;
+
+extern "C" {
+
+size_t pt_grid_packed_bytes(const pt_grid_desc* desc) {
+    GridParams G;
+    return grid_params("pt_grid_packed_bytes", desc, G) ? 0 : grid_bytes(G);
+}
+
+int pt_grid_pack_device(const pt_grid_desc* desc, const void* d_coeff_sums, const void* d_maps, void* d_packed, void* stream) {
+    return grid_pack_run("pt_grid_pack", desc, d_coeff_sums, d_maps, d_packed, false, (hipStream_t)stream);
+}
+
+int pt_grid_pack(const pt_grid_desc* desc, const float* coeff_sums, const float* maps4, void* packed) {
+    return grid_pack_run("pt_grid_pack", desc, coeff_sums, maps4, packed, true, nullptr);
+}
+
+int pt_grid_irradiance_device(const pt_grid_desc* desc, const void* d_packed, int m, const void* d_records, void* d_out, void* stream) {
+    return grid_irradiance_run("pt_grid_irradiance", desc, d_packed, m, d_records, d_out, false, (hipStream_t)stream);
+}
+
+int pt_grid_irradiance(const pt_grid_desc* desc, const void* packed, int m, const pt_ray* records, float* out4) {
+    return grid_irradiance_run("pt_grid_irradiance", desc, packed, m, records, out4, true, nullptr);
+}
+
+}  // extern "C"

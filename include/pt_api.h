@@ -1538,6 +1538,70 @@ int pt_query_distance(pt_scene* scene, int n, const pt_ray* records, int res, in
 int pt_query_distance_rays_device(pt_scene* scene, int n, const void* d_records /* n pt_ray */, int res, uint64_t seed, uint32_t first_stream,
                                   const void* d_draw_offset /* n*res*res uint32, NULL = all 0 */, void* d_rays /* n*res*res pt_ray */,
                                   uint32_t flags, void* stream);                                                                /* async */
+/* pt_grid_*: the lookup side of a probe volume: irradiance at surface points from the SH probes of pt_query_sh and
+ * the distance maps of pt_query_distance on one regular grid, what cudapathtracer_amd/rays.py's grid_irradiance computes in numpy or
+ * torch. Two scene-free calls shaped as the post-process calls: pt_grid_pack turns the two queries' sums into the form a lookup
+ * reads, pt_grid_irradiance looks m points up. No pt_scene is involved and nothing of one is touched.
+ * Grid. pt_grid_desc names the grid of rays.sh_grid(lo, hi, counts): probe (ix, iy, iz) is record (iz*ny + iy)*nx + ix, n = nx*ny*nz;
+ *   an axis with one probe has it at lo's coordinate, and its hi is not read. sh_samples is lanes*spp_lane of the pt_query_sh call,
+ *   map_samples spp_lane of the pt_query_distance call, map_res its res R, or 0 for a grid without maps; power the exponent of the
+ *   Chebyshev test. pt_grid_irradiance must be given the desc its packed buffer was made with.
+ * Packed buffer, pt_grid_packed_bytes(desc) = n*9*16 + n*(R+2)*(R+2)*8 bytes (R = 0: n*144), aligned to 16 bytes: first n*9 float4
+ *   (E_r, E_g, E_b, 0), probe j's convolved coefficient k at j*9 + k; then n*(R+2)*(R+2) float2 (mean, mean square), probe j's
+ *   bordered map at j*(R+2)*(R+2), texel (gx, gy) of it at gy*(R+2) + gx: interior texel (tx, ty) is (tx+1, ty+1), and the gutter is
+ *   rays.oct_border's: gutter texel (tx, ty), tx or ty one of -1 and R, copies interior texel (sx, sy) from
+ *     sx = tx, sy = ty;  tx < 0: sx = -1 - tx, sy = R-1 - ty;   tx > R-1: sx = 2R-1 - tx, sy = R-1 - ty;   then on the result
+ *     sy < 0: sy = -1 - sy, sx = R-1 - sx;   sy > R-1: sy = 2R-1 - sy, sx = R-1 - sx.
+ * ARITHMETIC, f32, every operation rounded once in the order written, nothing fused but the fmas named; / and sqrt are IEEE; min and
+ *   max ignore a NaN operand (v_min_f32, v_max_f32), so no index leaves its range whatever the data.
+ *   Pack. scale = (float)(4 pi / sh_samples) (the quotient in double); lobe = (float)pi for k = 0, (float)(2 pi / 3) for k = 1..3,
+ *     (float)(pi / 4) for k = 4..8; E_kc = (c_kc * scale) * lobe_k from coeff_sums[j*9 + k]'s channel c. mean = A / (float)map_samples,
+ *     mean square = B / (float)map_samples from maps[j*R*R + ty*R + tx] = (A, B, ., .).
+ *   Lookup of record (p, n) = (ox, oy, oz), (dx, dy, dz); max_t and pad are NOT read.
+ *   1. Any of the six components not finite: out = (0, 0, 0, 0), nothing is indexed.
+ *   2. Per axis a with counts_a > 1: inv_a = (float)((counts_a - 1) / ((double)hi_a - lo_a));  g = (p_a - lo_a) * inv_a;
+ *      low = min(max(floor(g), 0), counts_a - 2) in float, then converted to int;  f_a = min(max(g - low, 0), 1). The corners of the
+ *      axis are probes low and low + 1. An axis with one probe: low = 0, f_a = 0, both corners are probe 0.
+ *   3. y_0 = C0;  y_1 = C1*ny;  y_2 = C1*nz;  y_3 = C1*nx;  y_4 = C2*(nx*ny);  y_5 = C2*(ny*nz);  y_6 = C3*(3*(nz*nz) - 1);
+ *      y_7 = C2*(nx*nz);  y_8 = C4*(nx*nx - ny*ny), with pt_query_sh's constants 0.2820948, 0.4886025, 1.0925484, 0.3153916, 0.5462742.
+ *   4. The eight corners in the order cz, cy, cx with cx fastest, w_a = c_a ? f_a : 1 - f_a:  tri = (w_x * w_y) * w_z;  probe j =
+ *      (i_z*ny + i_y)*nx + i_x;  e_c = E_0c * y_0, then e_c = fma(E_kc, y_k, e_c) for k = 1..8;  plain_c = fma(tri, e_c, plain_c)
+ *      from plain_c = 0. Without maps W = W + tri from 0, and out = (plain, W).
+ *   5. With maps, per corner: step_a = (float)(((double)hi_a - lo_a) / (counts_a - 1)), 0 on an axis with one probe;
+ *      at_a = fma((float)i_a, step_a, lo_a);  v = p - at;  dist = sqrt(fma(v_z, v_z, fma(v_y, v_y, v_x*v_x)));  d = dist > 0 ? v :
+ *      (0, 0, 1);  s = (|d_x| + |d_y|) + |d_z|;  px = d_x / s;  py = d_y / s;  for d_z < 0:  qx = (1 - |py|) * copysign(1, d_x),
+ *      qy = (1 - |px|) * copysign(1, d_y), else qx = px, qy = py;  u = (qx + 1) * 0.5;  v likewise;  gx = u*R + 0.5;
+ *      ix = min(max(floor(gx), 0), R);  wx = gx - ix;  gy, iy, wy likewise. On the bordered map, per component of (mean, mean square):
+ *      top = t(ix, iy) + wx*(t(ix+1, iy) - t(ix, iy));  bot likewise in row iy + 1;  m = top + wy*(bot - top).
+ *      var = m2 - mean*mean;  var > 0 or else var = 0;  t = dist - mean;  den = var + t*t;  ratio = den > 0 ? var / den : 0;
+ *      vis = dist <= mean ? 1 : ((ratio*ratio)*ratio)... with `power` factors;  w = tri * vis;  num_c = fma(w, e_c, num_c);  W = W + w.
+ *   6. With maps out = W >= 1e-6f ? (num_r / W, num_g / W, num_b / W, W) : (plain_r, plain_g, plain_b, W).
+ *   E is in rays.grid_irradiance's units (those of pi * S / N of pt_query_irradiance); W is the weight sum the result was divided by
+ *   or, in the fallback and without maps, the sum that was found. A record's output depends on the record, the desc and the packed
+ *   buffer only.
+ * Checked before any HIP call, -1 with a message under the function's name (pt_grid_packed_bytes: 0), in this order: a NULL desc; a
+ *   count below 1 or counts whose product passes 1 << 22; a corner that is not finite, or hi <= lo on an axis with more than one
+ *   probe; sh_samples < 1; map_res not one of 0, 4, 8, 16, 32; map_samples < 1 with maps; power outside 1..8; m < 0 (m == 0 then
+ *   returns 0); a NULL buffer, maps given although map_res == 0 or missing although it is not; in the device forms the output
+ *   overlapping an input.
+ * d_coeff_sums (n*9 float4, pt_query_sh's), d_maps (n*R*R float4, pt_query_distance's), d_packed, d_records (m pt_ray) and d_out
+ * (m float4) are device buffers aligned to 16 bytes; the device forms are asynchronous on `stream`. */
+typedef struct pt_grid_desc {
+    float lo[3], hi[3];        /* sh_grid's corners, both included                       */
+    int32_t counts[3];         /* nx, ny, nz; probe (ix,iy,iz) is (iz*ny+iy)*nx+ix       */
+    int32_t sh_samples;        /* lanes * spp_lane of the pt_query_sh call               */
+    int32_t map_res;           /* 0: no maps (plain trilinear); else 4, 8, 16, 32        */
+    int32_t map_samples;       /* spp_lane of the pt_query_distance call                 */
+    int32_t power;             /* Chebyshev exponent, 1..8 (rays.py's default is 3)      */
+} pt_grid_desc;                                                                                                                  /* 52 bytes */
+size_t pt_grid_packed_bytes(const pt_grid_desc* desc);                                                                           /* 0 on a bad desc */
+int pt_grid_pack_device(const pt_grid_desc* desc, const void* d_coeff_sums /* n*9 float4 */, const void* d_maps /* n*R*R float4, NULL iff map_res == 0 */,
+                        void* d_packed, void* stream);                                                                           /* async */
+int pt_grid_pack(const pt_grid_desc* desc, const float* coeff_sums /* n*9*4 */, const float* maps4 /* n*R*R*4, NULL iff map_res == 0 */,
+                 void* packed);                                                                                                  /* host, blocking */
+int pt_grid_irradiance_device(const pt_grid_desc* desc, const void* d_packed, int m, const void* d_records /* m pt_ray */, void* d_out /* m float4 */,
+                              void* stream);                                                                                     /* async */
+int pt_grid_irradiance(const pt_grid_desc* desc, const void* packed, int m, const pt_ray* records, float* out4 /* m*4 */);       /* host, blocking */
 
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
