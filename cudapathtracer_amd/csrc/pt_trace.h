@@ -270,8 +270,8 @@ PT_DEV LeafBox leaf_box(const PLeaf* __restrict__ leaves, int k) {
 // that carries it, the floats rotated so that the grouped axis comes first; a group's header has the same 32 bytes), read the same
 // way: eight dwords in SGPRs, the last two the mask itself instead of (first, count). Read as ONE vector, so that it is one
 // s_load_dwordx8 whichever fields the caller uses (the table starts on a 32-byte boundary).
-struct PairBox { float mng, mnu, mnv, mxg, mxu, mxv; uint64_t mask; };
-PT_DEV PairBox pair_box(const void* __restrict__ boxes, int k) {
+struct PairBox { float mng, mnu, mnv, mxg, mxu, mxv; uint32_t lo, hi; };       // (lo, hi: the mask's two dwords, triangles 0..31 and 32..63)
+PT_DEV PairBox pair_box(const void* __restrict__ boxes, int k = 0) {
     typedef uint32_t u8v __attribute__((ext_vector_type(8)));
     typedef __attribute__((address_space(4))) const u8v konst_rec;
     const u8v r = *((konst_rec*)(uintptr_t)boxes + k);
@@ -279,7 +279,7 @@ PT_DEV PairBox pair_box(const void* __restrict__ boxes, int k) {
     PairBox B;
     B.mng = __builtin_bit_cast(float, w0); B.mnu = __builtin_bit_cast(float, w1); B.mnv = __builtin_bit_cast(float, w2);
     B.mxg = __builtin_bit_cast(float, w3); B.mxu = __builtin_bit_cast(float, w4); B.mxv = __builtin_bit_cast(float, w5);
-    B.mask = (uint64_t)r[6] | ((uint64_t)r[7] << 32);
+    B.lo = r[6]; B.hi = r[7];
     return B;
 }
 
@@ -842,13 +842,32 @@ PT_DEV void trace_pair_flat(const DeviceScene& S, const SceneCache& C, Stack<N>&
                 const float gmnE = fmaxf_(1.401298464e-45f, fminf_(e1, e2)), gmxE = fminf_(1e30f, fmaxf_(e1, e2));
                 const float s1 = (H.mng - oS.x) * iS.x, s2 = (H.mxg - oS.x) * iS.x;
                 const float gmnS = fmaxf_(1.401298464e-45f, fminf_(s1, s2)), gmxS = fminf_(1e30f, fmaxf_(s1, s2));
-                const int end = k + (int)(uint32_t)H.mask;
+                const int end = k + (int)H.lo;
+                // The loop steps a 32-bit byte offset into the table, which the record's s_load_dwordx8 takes as its SGPR offset: one
+                // add and one compare per record, where a counter beside a 64-bit pointer was three adds and the compare. That pays
+                // for the scalar compare of the mask word below (tests/test_isa_pair_boxes.py: at most 5 scalar instructions).
+                uint32_t off = 32u * (uint32_t)k;
+                const uint32_t offEnd = 32u * (uint32_t)end;     // (end <= nB <= 255 records of 32 bytes)
+                k = end;
                 do {                                              // (a group holds at least one record)
-                    const PairBox B = pair_box(boxes, k);
+                    const PairBox B = pair_box((const char*)boxes + off);
                     const bool eH = uv_hit(gmnE, gmxE, B, oE, iE);
                     const bool sH = uv_hit(gmnS, gmxS, B, oS, iS);
-                    tmE |= eH ? B.mask : 0ull; tmS |= sH ? B.mask : 0ull;
-                } while (++k < end);
+                    // The record's mask is two SGPRs, B.lo (triangles 0..31) and B.hi (32..63), folded into the two halves of each
+                    // ray's set. A hit is an all-ones / zero VGPR per ray, so that a word's fold is one v_and_or_b32 with the SGPR as
+                    // its one scalar operand (a select of the mask wants it in a VGPR first: a v_mov_b32 per word, and a v_cndmask_b32
+                    // and a v_or_b32 per word and ray). The empty asm keeps the compiler from turning `h & w` back into that select.
+                    // The high word is folded only where it is non-zero: a scalar compare and a scalar branch on an SGPR, wave-uniform
+                    // (no exec split). Exact: the skipped instructions compute x | (c ? 0 : 0). A record without a triangle above 31 —
+                    // 13 of the headline's 15 — issues 34 vector instructions instead of 40 (the low word
+                    // skipped the same way gained half as much on the headline: it is empty only in scenes of more than 32 triangles).
+                    // __builtin_expect lays the high word's block out behind the loop; the empty asm volatile inside keeps it a branch.
+                    uint32_t hE = eH ? ~0u : 0u, hS = sH ? ~0u : 0u;
+                    asm("" : "+v"(hE)); asm("" : "+v"(hS));
+                    auto fold = [&](uint32_t w, int sh) { tmE |= (uint64_t)(hE & w) << sh; tmS |= (uint64_t)(hS & w) << sh; };
+                    fold(B.lo, 0);
+                    if (__builtin_expect(B.hi != 0u, 0)) { asm volatile(""); fold(B.hi, 32); }
+                } while ((off += 32u) < offEnd);
             }
         } else {
         _Pragma("unroll 2")

@@ -16,7 +16,8 @@ Register moves (v_mov_b32 / v_mov_b64), under the key "moves" of a kernel, for t
   bounce_loop the loop that holds the leaf loop and the trip loop: one logic step and one pair pass
   logic       the bounce loop's head up to the leaf loop: scheduling check, logic step, regeneration, the pair pass's head
 split by source (from_vgpr, from_const, from_sgpr), and the lengths of the runs of four or more consecutive moves (const_runs:
-those of them that load constants only). --runs lists every run with the first source line it maps to; for that the census
+those of them that load constants only). "leaf_path" (leaf_record_path): what the leaf loop issues per record on the path every
+record takes and in the blocks that a record with an empty mask word skips, and the scalar branches on a mask dword. --runs lists every run with the first source line it maps to; for that the census
 compiles with line tables (-gline-tables-only), which the library's build never has.
 """
 import argparse
@@ -145,6 +146,67 @@ def regions(lines):
     out["trip_loop"]["exec_splits"] = sum(1 for ln in trip_lines if re.search(r"s_(xor|andn2_saveexec)_b64", ln))
     out["trip_loop"]["ds_min_u64"] = sum(1 for ln in trip_lines if "ds_min_u64" in ln)
     out["setup"]["dependent_lds_chain"] = dependent_lds_chain(lines[s0:th])
+    return out
+
+
+def leaf_record_path(lines):
+    """The leaf loop per record, for a loop whose body branches on a record's mask dword. The loop is the
+    innermost one around the s_load_dwordx8 in front of the trip loop; its blocks are walked from the header, falling through every
+    forward conditional branch that leaves a block for one inside the loop, until the back edge:
+      always      census of the blocks on that walk: what every record issues
+      skipped     census of the loop's other blocks: what only a record with a non-empty word issues
+      v_cndmask, v_or, v_and_or, v_mov   counts on the always-executed walk
+      mask_branches   [(compare, branch)] of the s_cmp_*_u32 of an SGPR of the record against 0 with the s_cbranch_scc* behind it
+      exec_splits     s_and_saveexec / s_or_saveexec / s_andn2_saveexec in the loop
+    The loop's blocks are the ones the compiler's annotations name as its own, wherever it lays them out."""
+    lp = loops(lines)
+    trip = [(h, e) for h, e in lp if all(any(op in lines[k] for k in range(h, e + 1)) for op in ("ds_min_u64", "v_ffbl_b32"))]
+    th, _ = min(trip, key=lambda x: x[1] - x[0])
+    leaf = [(h, e) for h, e in lp if e < th and any("s_load_dwordx8" in lines[k] for k in range(h, e + 1))]
+    lh = min(leaf, key=lambda x: x[1] - x[0])[0]
+    head = re.match(r"^\.L(BB\d+_\d+):", lines[lh]).group(1)
+    rotated = re.search(r"in Loop: Header=(BB\d+_\d+)", lines[lh])     # the branch goes back to a block laid out in front of the header it falls into
+    if rotated:
+        head = rotated.group(1)
+    bl = blocks(lines)
+    member = [n for n, (i, _, lab, note) in enumerate(bl) if lab == head or re.search(r"in Loop: Header=%s\b" % head, note)]
+    at = {bl[n][2]: n for n in member if bl[n][2]}
+    inside = [k for n in member for k in range(bl[n][0], bl[n][1])]
+    # the record's SGPRs: the destination of the loop's s_load_dwordx8
+    m = next(re.search(r"s_load_dwordx8 s\[(\d+):(\d+)\]", lines[k]) for k in inside if "s_load_dwordx8" in lines[k])
+    rec = {"s%d" % i for i in range(int(m.group(1)), int(m.group(2)) + 1)}
+    walk, n, seen = [], at[head], set()
+    while n is not None and n in member and n not in seen:
+        seen.add(n)
+        nxt = n + 1                                                # a conditional branch that is not the back edge: fall through
+        for k in range(bl[n][0], bl[n][1]):
+            walk.append(k)
+            mm = re.match(r"\s+s_c?branch\w*\s+\.L(BB\d+_\d+)", lines[k])
+            if mm and (mm.group(1) == head or lines[k].strip().startswith("s_branch")):
+                nxt = None if mm.group(1) == head else at.get(mm.group(1))
+                break
+        n = nxt
+    always = [lines[k] for k in walk]
+    skipped = [lines[k] for n in member if n not in seen for k in range(bl[n][0], bl[n][1])]      # (whole blocks: not the exit branch behind the back edge)
+    out = {"always": census(always), "skipped": census(skipped)}
+    for op in ("v_cndmask", "v_or", "v_and_or", "v_mov"):
+        out[op] = sum(1 for ln in always if is_insn(ln) and ln.strip().startswith(op + "_"))
+    pairs, cmp_ = [], None
+    for k in inside:
+        if not is_insn(lines[k]):
+            continue
+        s = lines[k].strip().split(";")[0].strip()
+        mm = re.match(r"s_cmp_(?:eq|lg)_u32 (s\d+), 0$", s)
+        if mm and mm.group(1) in rec:
+            cmp_ = s
+        elif s.startswith("s_cmp"):
+            cmp_ = None
+        elif cmp_ and re.match(r"s_cbranch_scc[01] ", s):
+            pairs.append((cmp_, s))
+            cmp_ = None
+    out["mask_branches"] = pairs
+    out["exec_splits"] = sum(1 for k in inside if re.search(r"s_(and|or|andn2|xor)_saveexec_b64", lines[k]))
+    out["v_readlane"] = sum(1 for k in inside if is_insn(lines[k]) and lines[k].strip().startswith("v_readlane"))
     return out
 
 
@@ -283,6 +345,7 @@ def main():
         lines = function(text, name)
         res[key] = {"kernel": name, "metadata": metadata(text, name), "whole": census(lines), "regions": regions(lines), "moves": move_regions(lines)}
         res[key]["moves"]["whole"] = move_census(lines)[0]
+        res[key]["leaf_path"] = leaf_record_path(lines)
     if a.json:
         json.dump(res, sys.stdout, indent=1)
         print()
@@ -291,6 +354,11 @@ def main():
         print("%s  %s  %s" % (key, r["kernel"], " ".join("%s=%s" % kv for kv in r["metadata"].items())))
         for reg, c in [("whole", r["whole"])] + list(r["regions"].items()):
             print("  %-10s %s" % (reg, " ".join("%s=%d" % kv for kv in c.items())))
+        p = r["leaf_path"]
+        print("  leaf path  per record, always executed: %s; %s" % (" ".join("%s=%d" % (k, p["always"][k]) for k in ("total", "valu", "salu", "branch", "s_nop")),
+                                                                     " ".join("%s=%d" % (k, p[k]) for k in ("v_mov", "v_cndmask", "v_or", "v_and_or"))))
+        print("             skipped by a record with an empty mask word: total=%d valu=%d; branches on a mask dword: %s; exec_splits=%d v_readlane=%d"
+              % (p["skipped"]["total"], p["skipped"]["valu"], ", ".join("%s / %s" % b for b in p["mask_branches"]) or "none", p["exec_splits"], p["v_readlane"]))
         for reg in ("whole", "bounce_loop", "logic"):
             m = r["moves"][reg]
             print("  moves %-11s %s runs=%s const_runs=%s zero_fill_runs=%s" % (reg, " ".join("%s=%d" % (k, m[k]) for k in ("total", "valu", "v_mov", "from_vgpr", "from_const", "from_sgpr", "longest_zero_fill") if k in m),
