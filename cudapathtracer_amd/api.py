@@ -123,6 +123,8 @@ QUERY_REORDER = 1                    # PT_QUERY_REORDER
 QUERY_STREAM_PAD = 2                 # PT_QUERY_STREAM_PAD
 QUERY_TEXEL_CENTRE = 4               # PT_QUERY_TEXEL_CENTRE
 QUERY_MAX_T = 999999.0               # the max_t of the library's own closest-hit rays
+PROBE_INSIDE = 1                     # PT_PROBE_INSIDE: the probe lies inside an object, lookups with states skip it
+PROBE_IDLE = 2                       # PT_PROBE_IDLE: no surface within the maps' max_t
 
 
 class GridDesc(C.Structure):         # pt_grid_desc
@@ -249,6 +251,12 @@ def lib():
     L.pt_grid_pack_device.argtypes = [C.POINTER(GridDesc), vp, vp, vp, vp]
     L.pt_grid_irradiance.argtypes = [C.POINTER(GridDesc), vp, i32, vp, vp]
     L.pt_grid_irradiance_device.argtypes = [C.POINTER(GridDesc), vp, i32, vp, vp, vp]
+    L.pt_grid_classify.argtypes = [C.POINTER(GridDesc), i32, vp, vp, f32, vp]
+    L.pt_grid_classify_device.argtypes = [C.POINTER(GridDesc), i32, vp, vp, f32, vp, vp]
+    L.pt_grid_update.argtypes = [C.POINTER(GridDesc), i32, vp, vp, vp, f32, vp]
+    L.pt_grid_update_device.argtypes = [C.POINTER(GridDesc), i32, vp, vp, vp, f32, vp, vp]
+    L.pt_grid_irradiance_states.argtypes = [C.POINTER(GridDesc), vp, vp, i32, vp, vp]
+    L.pt_grid_irradiance_states_device.argtypes = [C.POINTER(GridDesc), vp, vp, i32, vp, vp, vp]
     L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
     L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -2189,23 +2197,120 @@ def grid_pack(desc, coeff_sums, maps=None):
     return packed
 
 
-def grid_irradiance(packed, desc, records):
+def _grid_words(what, name, a, count, like=None, writable=False):
+    """`count` 32-bit integer words (probe numbers, state words): for the host form a C-contiguous int32 or uint32 numpy array (one
+    that is written must be the caller's own array, not a copy), or, with `like` a tensor, a contiguous int32 tensor on its device
+    (torch's 32-bit integer type; a state word's bits are the same)."""
+    if like is not None:
+        import torch
+        if not (_is_tensor(a) and a.is_cuda and a.device == like.device and a.dtype == torch.int32 and a.is_contiguous()):
+            raise PtError("%s: %s must be a contiguous int32 tensor on %s" % (what, name, like.device))
+        got = a.numel()
+    else:
+        if _is_tensor(a):
+            raise PtError("%s: %s is a tensor but the call's other arrays are numpy" % (what, name))
+        if writable:
+            if not (isinstance(a, np.ndarray) and a.dtype in (np.uint32, np.int32) and a.flags.c_contiguous and a.flags.writeable):
+                raise PtError("%s: %s must be a writable C-contiguous uint32 array" % (what, name))
+        else:
+            a = np.asarray(a)
+            a = np.ascontiguousarray(a if a.dtype in (np.uint32, np.int32) else a.astype(np.int32))
+        got = a.size
+    if got != count:
+        raise PtError("%s: %s holds %d words, the call needs %d" % (what, name, got, count))
+    return a
+
+
+def _grid_list(what, desc, indices, like):
+    """(k, indices or None) of a probe list: None is the identity over the grid's n probes."""
+    n = desc.counts[0] * desc.counts[1] * desc.counts[2]
+    if indices is None:
+        return n, None
+    k = int(indices.numel()) if _is_tensor(indices) else int(np.asarray(indices).size)
+    return k, _grid_words(what, "indices", indices, k, like)
+
+
+def _ptr(a):
+    return None if a is None else (a.data_ptr() if _is_tensor(a) else _p(a))
+
+
+def grid_classify(desc, maps, back_fraction=0.25, indices=None, states=None):
+    """pt_grid_classify: a state word per probe from Scene.query_distance's maps [k, R, R, 4] of the probes `indices` [k] (None: all n,
+    in the grid's order). PROBE_INSIDE where the hits seen from behind pass back_fraction of the hits, PROBE_IDLE where nothing was
+    hit. Writes the listed probes' words of `states` [n] (a zeroed array when None; uint32 numpy for the host form, an int32 tensor
+    for the device form) and returns it. numpy in, numpy out; tensors on the current HIP device in, a tensor out, on torch's current
+    stream."""
+    like = maps if _is_tensor(maps) else None
+    n, r = desc.counts[0] * desc.counts[1] * desc.counts[2], desc.map_res
+    k, idx = _grid_list("grid_classify", desc, indices, like)
+    mp = _grid_input("grid_classify", "maps", maps, k * r * r * 4, like)
+    if like is not None:
+        import torch
+        if states is None:
+            states = torch.zeros(n, dtype=torch.int32, device=mp.device)
+        st = _grid_words("grid_classify", "states", states, n, like)
+        _check(lib().pt_grid_classify_device(C.byref(desc), k, _ptr(idx), _ptr(mp), back_fraction, _ptr(st),
+                                             torch.cuda.current_stream(mp.device).cuda_stream or None), "pt_grid_classify_device")
+    else:
+        if states is None:
+            states = np.zeros(n, np.uint32)
+        st = _grid_words("grid_classify", "states", states, n, writable=True)
+        _check(lib().pt_grid_classify(C.byref(desc), k, _ptr(idx), _ptr(mp), back_fraction, _ptr(st)), "pt_grid_classify")
+    return st
+
+
+def grid_update(packed, desc, coeff_sums, maps=None, hysteresis=0.0, indices=None):
+    """pt_grid_update: blends fresh query outputs into grid_pack's buffer in place and returns it. coeff_sums [k, 9, 4] and, for a
+    grid with maps, maps [k, R, R, 4] are Scene.query_sh's and Scene.query_distance's rows for the probes `indices` [k] (None: all n);
+    desc carries the FRESH rows' sample counts. Each word becomes fresh + hysteresis * (old - fresh); hysteresis 0 replaces it.
+    numpy (packed a C-contiguous float32 array, written where it lies) or tensors on the current HIP device, on torch's current
+    stream."""
+    like = packed if _is_tensor(packed) else None
+    r = desc.map_res
+    if (maps is None) != (r == 0):
+        raise PtError("grid_update: maps are %s but desc.map_res is %d" % ("missing" if maps is None else "given", r))
+    if like is None and not (isinstance(packed, np.ndarray) and packed.dtype == np.float32 and packed.flags.c_contiguous and packed.flags.writeable):
+        raise PtError("grid_update: packed must be a writable C-contiguous float32 array: it is updated in place")
+    pk = _grid_input("grid_update", "packed", packed, grid_packed_bytes(desc) // 4, like)
+    k, idx = _grid_list("grid_update", desc, indices, like)
+    s = _grid_input("grid_update", "coeff_sums", coeff_sums, k * 36, like)
+    m = None if maps is None else _grid_input("grid_update", "maps", maps, k * r * r * 4, like)
+    if like is not None:
+        import torch
+        _check(lib().pt_grid_update_device(C.byref(desc), k, _ptr(idx), _ptr(s), _ptr(m), hysteresis, _ptr(pk),
+                                           torch.cuda.current_stream(pk.device).cuda_stream or None), "pt_grid_update_device")
+    else:
+        _check(lib().pt_grid_update(C.byref(desc), k, _ptr(idx), _ptr(s), _ptr(m), hysteresis, _ptr(pk)), "pt_grid_update")
+    return packed
+
+
+def grid_irradiance(packed, desc, records, states=None):
     """pt_grid_irradiance: the irradiance at surface points from a packed probe grid. records is [m, 8] float32 (point, a word that
     is not read, unit normal, a word that is not read: rays.irradiance_records, rays.records_from_surfaces); packed is grid_pack's
     buffer of the same desc. Returns [m, 4] float32: (E_r, E_g, E_b, W) in rays.grid_irradiance's units, W the weight sum E was
     divided by; exact zeros for a record whose point or normal is not finite. numpy in, numpy out (host form); tensors on the
-    current HIP device in, a tensor out, on torch's current stream with no host copy."""
+    current HIP device in, a tensor out, on torch's current stream with no host copy. With `states` [n] (grid_classify's)
+    pt_grid_irradiance_states: the probes whose PROBE_INSIDE bit is set are left out."""
     is_torch, r, m = Scene._query_rays("grid_irradiance", records)
     p = _grid_input("grid_irradiance", "packed", packed, grid_packed_bytes(desc) // 4, r if is_torch else None)
+    st = None
+    if states is not None:
+        st = _grid_words("grid_irradiance", "states", states, desc.counts[0] * desc.counts[1] * desc.counts[2], r if is_torch else None)
     if is_torch:
         import torch
         out = torch.empty((m, 4), dtype=torch.float32, device=r.device)
-        if m:
-            _check(lib().pt_grid_irradiance_device(C.byref(desc), p.data_ptr(), m, r.data_ptr(), out.data_ptr(),
-                                                   torch.cuda.current_stream(r.device).cuda_stream or None), "pt_grid_irradiance_device")
+        stream = torch.cuda.current_stream(r.device).cuda_stream or None
+        if m and st is None:
+            _check(lib().pt_grid_irradiance_device(C.byref(desc), p.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream), "pt_grid_irradiance_device")
+        elif m:
+            _check(lib().pt_grid_irradiance_states_device(C.byref(desc), p.data_ptr(), st.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream),
+                   "pt_grid_irradiance_states_device")
     else:
         out = np.zeros((m, 4), np.float32)
-        _check(lib().pt_grid_irradiance(C.byref(desc), _p(p), m, _p(r), _p(out)), "pt_grid_irradiance")
+        if st is None:
+            _check(lib().pt_grid_irradiance(C.byref(desc), _p(p), m, _p(r), _p(out)), "pt_grid_irradiance")
+        else:
+            _check(lib().pt_grid_irradiance_states(C.byref(desc), _p(p), _p(st), m, _p(r), _p(out)), "pt_grid_irradiance_states")
     return out
 
 
@@ -2224,7 +2329,8 @@ class ProbeGrid:
         self.res, self.device = int(res), bool(device)
         cell = [(b - a) / (c - 1) for a, b, c in zip(self.lo, self.hi, self.counts) if c > 1]
         self.max_t = float(max_t) if max_t is not None else 1.5 * float(np.sqrt(sum(v * v for v in cell)))
-        self.desc = self.sums = self.maps = self.packed = None
+        self.desc = self.sums = self.maps = self.packed = self.states = None
+        self.back_fraction = 0.25
 
     def _where(self):
         if not self.device:
@@ -2243,13 +2349,77 @@ class ProbeGrid:
                                                   flags=map_flags)
         self.desc = grid_desc(self.lo, self.hi, self.counts, lanes * spp_lane, self.res, map_spp, power)
         self.packed = grid_pack(self.desc, self.sums, self.maps)
+        self.states = None
+        return self
+
+    def classify(self, back_fraction=0.25):
+        """grid_classify on the kept maps: keeps a state word per probe in .states (PROBE_INSIDE, PROBE_IDLE), which the lookups pass
+        from then on, so that a probe inside an object lights nothing. bake() forgets them. Returns self."""
+        if self.packed is None:
+            raise PtError("ProbeGrid: bake() has not run")
+        if not self.res:
+            raise PtError("ProbeGrid: a grid without maps (res = 0) has nothing to classify")
+        self.back_fraction = float(back_fraction)
+        self.states = grid_classify(self.desc, self.maps, self.back_fraction)
+        return self
+
+    def update(self, lanes, spp_lane, max_depth, map_spp=1, hysteresis=0.9, probes=None, seed=SEED, skip_idle=False, integrator=UNIDIRECTIONAL,
+               use_mis=True, map_flags=0):
+        """Re-bakes the probes `probes` (numbers in the grid's order; default: all) and blends the fresh samples into the packed buffer
+        in place: new = fresh + hysteresis * (old - fresh). The queries run as bake()'s with QUERY_STREAM_PAD, each record's pad word
+        its probe number, so a listed probe gets the streams a full bake with these arguments gives it. With skip_idle the probes that
+        classify() found PROBE_IDLE are dropped from the list. The fresh rows replace the listed probes' rows of .sums and .maps, and
+        where states are kept the listed probes are classified again from their fresh maps. Returns self."""
+        from . import rays
+        if self.packed is None:
+            raise PtError("ProbeGrid: bake() has not run")
+        n = self.counts[0] * self.counts[1] * self.counts[2]
+        idx = np.arange(n, dtype=np.int32) if probes is None else np.asarray(probes, np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= n):
+            raise PtError("ProbeGrid.update: probe numbers must be in 0..%d" % (n - 1))
+        idx = idx.astype(np.int32)
+        if skip_idle and self.states is not None:
+            st = self.states.cpu().numpy() if _is_tensor(self.states) else self.states
+            idx = idx[(st[idx].astype(np.int64) & PROBE_IDLE) == 0]
+        if not len(idx):
+            return self
+        where = self._where()
+
+        def records(max_t):
+            rec = rays.sh_grid(self.lo, self.hi, self.counts, max_t, where)
+            if where is None:
+                rec = np.ascontiguousarray(rec[idx])
+                rec.view(np.int32)[:, 7] = idx
+            else:
+                import torch
+                t = torch.from_numpy(idx).to(rec.device)
+                rec = rec[t.long()].contiguous()
+                rec.view(torch.int32)[:, 7] = t
+            return rec
+        sums = self.scene.query_sh(records(QUERY_MAX_T), lanes, spp_lane, max_depth, integrator, use_mis, seed, flags=QUERY_STREAM_PAD)
+        maps = None
+        if self.res:
+            maps = self.scene.query_distance(records(self.max_t), self.res, map_spp, seed, flags=map_flags | QUERY_STREAM_PAD)
+        desc = grid_desc(self.lo, self.hi, self.counts, lanes * spp_lane, self.res, map_spp, self.desc.power)
+        if where is None:
+            lst, at = idx, idx
+        else:
+            import torch
+            lst = torch.from_numpy(idx).to(sums.device)
+            at = lst.long()
+        grid_update(self.packed, desc, sums, maps, hysteresis, lst)
+        self.sums[at] = sums
+        if maps is not None:
+            self.maps[at] = maps
+            if self.states is not None:
+                grid_classify(desc, maps, self.back_fraction, lst, self.states)
         return self
 
     def lookup(self, records):
-        """grid_irradiance on the baked grid: [m, 4] (E_r, E_g, E_b, W) for [m, 8] records."""
+        """grid_irradiance on the baked grid: [m, 4] (E_r, E_g, E_b, W) for [m, 8] records; with the states classify() keeps."""
         if self.packed is None:
             raise PtError("ProbeGrid: bake() has not run")
-        return grid_irradiance(self.packed, self.desc, records)
+        return grid_irradiance(self.packed, self.desc, records, self.states)
 
     def irradiance(self, points, normals):
         """The lookup at `points` [m, 3] with unit `normals` [m, 3]."""

@@ -10,24 +10,9 @@
 //                             Neighbouring records mostly share their cell: when a ballot says that every lane of the wave has the
 //                             same one, the cell's index goes to SGPRs and the coefficients arrive by scalar loads (measured: §29).
 // Every min and max is v_min_f32 / v_max_f32, which drop a NaN operand: every index is in range whatever a record holds.
-#include <cmath>
-
-#include "../../include/pt_api.h"
-#include "pt_device.h"
-#include "pt_postfx_host.h"
+#include "pt_grid.h"
 
 namespace pt {
-
-struct GridParams {
-    float lo[3], inv[3], step[3], top[3];       // top = (float)max(counts - 2, 0); inv = step = 0 on an axis with one probe
-    int counts[3];
-    int n;                                      // probes
-    int R, power;
-    float Rf;
-    float scale, mapSamples;                    // the pack's
-};
-
-constexpr float kShC0 = 0.2820948f, kShC1 = 0.4886025f, kShC2 = 1.0925484f, kShC3 = 0.3153916f, kShC4 = 0.5462742f;    // include/pt_api.h
 
 __global__ void __launch_bounds__(256) grid_pack_kernel(GridParams G, const float4* __restrict__ sums, const float4* __restrict__ maps,
                                                         float4* __restrict__ coeff, float2* __restrict__ texels) {
@@ -50,37 +35,6 @@ __global__ void __launch_bounds__(256) grid_pack_kernel(GridParams G, const floa
     if (sy < 0) { sy = -1 - sy; sx = R - 1 - sx; } else if (sy > R - 1) { sy = 2 * R - 1 - sy; sx = R - 1 - sx; }
     const float4 a = maps[j * R * R + (size_t)sy * R + sx];
     texels[t] = make_float2(a.x / G.mapSamples, a.y / G.mapSamples);
-}
-
-PT_DEV bool finite_(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// The Chebyshev visibility of a point at `v` from a probe whose bordered map starts at `map` (include/pt_api.h, step 5).
-PT_DEV float grid_visibility(const GridParams& G, const float2* __restrict__ map, V3 v) {
-    const float dist = __builtin_sqrtf(dot(v, v));
-    const V3 d = dist > 0.0f ? v : v3(0.0f, 0.0f, 1.0f);
-    const float s = (__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z);
-    const float px = d.x / s, py = d.y / s;
-    float qx = px, qy = py;
-    if (d.z < 0.0f) {
-        qx = (1.0f - __builtin_fabsf(py)) * __builtin_copysignf(1.0f, d.x);
-        qy = (1.0f - __builtin_fabsf(px)) * __builtin_copysignf(1.0f, d.y);
-    }
-    const float gx = ((qx + 1.0f) * 0.5f) * G.Rf + 0.5f, gy = ((qy + 1.0f) * 0.5f) * G.Rf + 0.5f;
-    const float ix = fminf_(fmaxf_(__builtin_floorf(gx), 0.0f), G.Rf), iy = fminf_(fmaxf_(__builtin_floorf(gy), 0.0f), G.Rf);
-    const float wx = gx - ix, wy = gy - iy;
-    const float2* row = map + (int)iy * (G.R + 2) + (int)ix;
-    const float2 t00 = row[0], t10 = row[1], t01 = row[G.R + 2], t11 = row[G.R + 3];
-    const float topM = t00.x + wx * (t10.x - t00.x), topQ = t00.y + wx * (t10.y - t00.y);
-    const float botM = t01.x + wx * (t11.x - t01.x), botQ = t01.y + wx * (t11.y - t01.y);
-    const float mean = topM + wy * (botM - topM), m2 = topQ + wy * (botQ - topQ);
-    float var = m2 - mean * mean;
-    var = var > 0.0f ? var : 0.0f;
-    const float t = dist - mean;
-    const float den = var + t * t;
-    const float ratio = den > 0.0f ? var / den : 0.0f;
-    float vis = ratio;
-    for (int k = 1; k < G.power; k++) vis = vis * ratio;
-    return dist <= mean ? 1.0f : vis;
 }
 
 // The eight corners of a record's cell (include/pt_api.h, steps 4 to 6) from its lowest probe `low` and the fractions f. Inlined twice:
@@ -153,42 +107,6 @@ __global__ void __launch_bounds__(256) grid_irradiance_kernel(GridParams G, cons
     }
     out[i] = grid_corners<MAPS>(G, coeff, texels, p, y, low, f);
 }
-
-// The desc's checks in the header's order; on success G holds what the kernels read.
-static int grid_params(const char* fn, const pt_grid_desc* d, GridParams& G) {
-    if (!d) return postfx_fail_fn(-1, fn, "null desc");
-    const int32_t* c3 = d->counts;
-    if (c3[0] < 1 || c3[1] < 1 || c3[2] < 1) return postfx_fail_fn(-1, fn, "counts %d x %d x %d must be at least 1 each", c3[0], c3[1], c3[2]);
-    const long long n = (long long)c3[0] * c3[1] > (1ll << 22) ? (1ll << 23) : (long long)c3[0] * c3[1] * c3[2];
-    if (n > (1ll << 22)) return postfx_fail_fn(-1, fn, "counts %d x %d x %d make more than %d probes", c3[0], c3[1], c3[2], 1 << 22);
-    for (int a = 0; a < 3; a++) {
-        if (!std::isfinite(d->lo[a]) || !std::isfinite(d->hi[a])) return postfx_fail_fn(-1, fn, "corner lo[%d] = %g, hi[%d] = %g is not finite", a, d->lo[a], a, d->hi[a]);
-        if (d->counts[a] > 1 && !(d->hi[a] > d->lo[a])) return postfx_fail_fn(-1, fn, "hi[%d] = %g must be above lo[%d] = %g", a, d->hi[a], a, d->lo[a]);
-    }
-    if (d->sh_samples < 1) return postfx_fail_fn(-1, fn, "sh_samples %d must be at least 1", d->sh_samples);
-    const int R = d->map_res;
-    if (R != 0 && R != 4 && R != 8 && R != 16 && R != 32) return postfx_fail_fn(-1, fn, "map_res %d must be 0, 4, 8, 16 or 32", R);
-    if (R != 0 && d->map_samples < 1) return postfx_fail_fn(-1, fn, "map_samples %d must be at least 1", d->map_samples);
-    if (d->power < 1 || d->power > 8) return postfx_fail_fn(-1, fn, "power %d must be 1..8", d->power);
-    for (int a = 0; a < 3; a++) {
-        const int c = d->counts[a];
-        const double span = (double)d->hi[a] - (double)d->lo[a];
-        G.lo[a] = d->lo[a];
-        G.inv[a] = c > 1 ? (float)((c - 1) / span) : 0.0f;
-        G.step[a] = c > 1 ? (float)(span / (c - 1)) : 0.0f;
-        G.top[a] = (float)(c > 1 ? c - 2 : 0);
-        G.counts[a] = c;
-    }
-    G.n = (int)n;
-    G.R = R; G.Rf = (float)R; G.power = d->power;
-    G.scale = (float)(4.0 * 3.14159265358979323846 / (double)d->sh_samples);
-    G.mapSamples = (float)d->map_samples;
-    return 0;
-}
-
-static size_t grid_coeff_bytes(const GridParams& G) { return (size_t)G.n * 9 * sizeof(float4); }
-static size_t grid_texels(const GridParams& G) { return G.R ? (size_t)G.n * (G.R + 2) * (G.R + 2) : 0; }
-static size_t grid_bytes(const GridParams& G) { return grid_coeff_bytes(G) + grid_texels(G) * sizeof(float2); }
 
 static int grid_pack_launch(const GridParams& G, const void* sums, const void* maps, void* packed, hipStream_t stream) {
     const size_t threads = (size_t)G.n * 9 + grid_texels(G);

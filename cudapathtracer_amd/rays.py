@@ -218,13 +218,16 @@ def distance_visibility(maps, samples, d, dist, power=3):
     return xp.where(dist <= mean, 1 + 0 * den, ratio ** power).reshape(lead)
 
 
-def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, maps=None, map_samples=None, power=3):
+def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, maps=None, map_samples=None, power=3, states=None):
     """Irradiance at `points` [m, 3] with unit `normals` [m, 3] from the probes of an sh_grid(lo, hi, counts): coeff_sums [n, 9, 4]
     are Scene.query_sh's sums of sh_samples samples a probe, maps [n, R, R, >= 2] (optional) Scene.query_distance's of map_samples
     samples a texel, both in the grid's order (x fastest). Per point the eight probes around it (clamped at the grid's faces) are
     weighted trilinearly times distance_visibility of the point as seen from the probe, and the result is sum(w E_j(n)) / sum(w), E_j
     being probe j's sh_irradiance at the point's normal. Without maps, or where the weights sum to less than 1e-6, the plain
-    trilinear mix. Returns [m, 3] in coeff_sums' dtype (numpy or torch)."""
+    trilinear mix. With `states` [n] (api.grid_classify's words; bit 0, api.PROBE_INSIDE, marks a dead probe) the dead corners are
+    left out of every sum, and a point whose weights sum to less than 1e-6 (or a grid without maps) that lost a corner gets the plain
+    mix of its live corners divided by their trilinear weights' sum, zeros where that sum is 0. Returns [m, 3] in coeff_sums' dtype
+    (numpy or torch)."""
     xp = _xp_of(coeff_sums)
     dt = coeff_sums.dtype
     conv = (lambda v: np.asarray(v, dt)) if xp is np else (lambda v: xp.as_tensor(v, dtype=dt, device=coeff_sums.device))
@@ -240,7 +243,9 @@ def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, map
         i0.append(lowi); i1.append(lowi + 1 if counts[a] > 1 else lowi); f.append(fa); pos.append((float(lo[a]), step))
     y = sh_basis(nrm)                                                               # [m, 9]
     e = _sh_convolved(coeff_sums, sh_samples)                                       # [n, 9, 3]
-    num, den, plain = 0, 0, 0
+    num, den, plain, live_sum, lost = 0, 0, 0, 0, False
+    if states is not None:
+        dead = (np.asarray(states).astype(np.int64) & 1) != 0 if xp is np else (xp.as_tensor(states, device=coeff_sums.device).to(xp.int64) & 1) != 0
     for cz in (0, 1):
         for cy in (0, 1):
             for cx in (0, 1):
@@ -248,6 +253,10 @@ def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, map
                 tri = (f[0] if cx else 1 - f[0]) * (f[1] if cy else 1 - f[1]) * (f[2] if cz else 1 - f[2])
                 j = (iz * counts[1] + iy) * counts[0] + ix
                 ej = (e[j] * y[:, :, None]).sum(1)                                  # [m, 3]
+                if states is not None:                                              # a dead corner adds exact zeros, whatever it holds
+                    gone = dead[j]
+                    tri, ej = xp.where(gone, 0 * tri, tri), xp.where(gone[:, None], 0 * ej, ej)
+                    live_sum, lost = live_sum + tri, lost | gone
                 plain = plain + tri[:, None] * ej
                 if maps is not None:
                     at = xp.stack([pos[a][0] + pos[a][1] * (ix, iy, iz)[a] for a in range(3)], -1)      # the probe's position
@@ -255,7 +264,12 @@ def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, map
                     dist = xp.sqrt((v * v).sum(-1))
                     d = xp.where((dist > 0)[:, None], v, conv([0.0, 0.0, 1.0])[None, :] + 0 * v)
                     w = tri * distance_visibility(maps[j], map_samples, d, dist, power)
+                    if states is not None:
+                        w = xp.where(gone, 0 * w, w)
                     num, den = num + w[:, None] * ej, den + w
+    if states is not None:
+        some = live_sum > 0
+        plain = xp.where(lost[:, None], xp.where(some[:, None], plain / xp.where(some, live_sum, 1 + 0 * live_sum)[:, None], 0 * plain), plain)
     if maps is None:
         return plain
     ok = den >= 1e-6

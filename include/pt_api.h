@@ -1603,6 +1603,59 @@ int pt_grid_irradiance_device(const pt_grid_desc* desc, const void* d_packed, in
                               void* stream);                                                                                     /* async */
 int pt_grid_irradiance(const pt_grid_desc* desc, const void* packed, int m, const pt_ray* records, float* out4 /* m*4 */);       /* host, blocking */
 
+/* pt_grid_classify, pt_grid_update, pt_grid_irradiance_states: a probe volume that stays current. Three scene-free
+ * calls beside the five above, shaped as they are: a state word per probe from its distance map's hit counts, a lookup that leaves out
+ * the probes found inside an object, and fresh query sums blended into a packed buffer in place. Nothing above changes.
+ * States. n uint32, one per probe in the grid's order. PT_PROBE_INSIDE: the probe lies inside an object, lookups skip it.
+ *   PT_PROBE_IDLE: no surface within the maps' max_t, so nothing the probe can light is near; lookups still read it, a caller may
+ *   spare its re-bake. A lookup reads bit 0 only: junk in the other 31 bits changes nothing.
+ * The probe list. k rows of fresh query output, row i that of probe indices[i] (int32). indices == NULL requires k == n and means
+ *   the identity. An index outside [0, n) is skipped: that row touches nothing, in the host and the device form alike. A list that
+ *   names a probe twice is the caller's error: that probe's result is then one of the rows', and nothing outside it is touched. A
+ *   subset re-bake gets the full bake's streams through PT_QUERY_STREAM_PAD with the pad word set to the probe number; by the
+ *   queries' independence clause its rows then equal the full bake's bit for bit.
+ * ARITHMETIC as above: f32, every operation rounded once in the order written, nothing fused but the fmas named, / is IEEE.
+ *   Classify. Per listed probe Hs = sum of H and Ks = sum of K over the R*R texels (C, D of maps[i*R*R + ty*R + tx] = (., ., C, D):
+ *     the hits and the hits seen from behind). The values are whole numbers and the totals at most 2^22, so every order of summation
+ *     gives the same sum.  state = (Ks > back_fraction * Hs ? PT_PROBE_INSIDE : 0) | (Hs == 0 ? PT_PROBE_IDLE : 0), the product
+ *     rounded once. The map's contents are not checked: every comparison with a NaN is false, so a map with a NaN count gives 0.
+ *     Only the listed probes' words are written.
+ *   Update. Per word of a listed probe's coefficient rows and bordered map, fresh = what pt_grid_pack computes for that word from the
+ *     row's sums and map, the gutter's source rule included (desc.sh_samples and desc.map_samples are the FRESH sums' and may differ
+ *     from the bake's; counts, lo, hi and map_res must be the buffer's own);  new = hysteresis == 0 ? fresh :
+ *     fma(hysteresis, old - fresh, fresh) on E_r, E_g, E_b, on the mean and on the mean square; the fourth word of a coefficient row
+ *     is written as 0. A gutter texel blends its own old value with its source's fresh value, so a buffer whose gutter was consistent
+ *     stays so. hysteresis 0 over all probes writes pt_grid_pack's buffer.
+ *   Lookup with states. Steps 1 to 3 as pt_grid_irradiance. In step 4 a corner whose states[j] & 1 is set loads nothing else and
+ *     adds nothing; a live corner does what it does above and also T = T + tri, from T = 0. The output, in this order:
+ *       with maps and W >= 1e-6f:       (num_r / W, num_g / W, num_b / W, W), as above;
+ *       else if no corner was skipped:  (plain_r, plain_g, plain_b, W), pt_grid_irradiance's result bit for bit;
+ *       else if T > 0:                  (plain_r / T, plain_g / T, plain_b / T, W), W the sum that was found; without maps W = T;
+ *       else (all corners dead, or the live ones have no weight): exact zeros in all four words.
+ *     With every state's bit 0 clear the output is pt_grid_irradiance's bit for bit.
+ * Checked before any HIP call, -1 with a message under the function's name, in this order: the desc as above; pt_grid_classify:
+ *   map_res == 0; k (or m) < 0 (0 then returns 0); k > n, or NULL indices with k != n; back_fraction not in [0, 1] or hysteresis not
+ *   in [0, 1) (a NaN is in neither); a NULL buffer, and maps against map_res as pt_grid_pack checks them; in the device forms a
+ *   written buffer overlapping a read one.
+ * d_indices (k int32), d_states (n uint32), d_coeff_sums (k*9 float4), d_maps (k*R*R float4), d_packed, d_records and d_out are
+ * device buffers, the float4 ones aligned to 16 bytes; the device forms are asynchronous on `stream`. */
+#define PT_PROBE_INSIDE 1u   /* the probe lies inside an object: lookups skip it */
+#define PT_PROBE_IDLE   2u   /* no surface within the maps' max_t: nothing it can light is near; lookups still read it */
+int pt_grid_classify_device(const pt_grid_desc* desc, int k, const void* d_indices /* k int32, or NULL: k == n, probe i */,
+                            const void* d_maps /* k*R*R float4, pt_query_distance's */, float back_fraction,
+                            void* d_states /* n uint32, entry indices[i] written */, void* stream);                              /* async */
+int pt_grid_classify(const pt_grid_desc* desc, int k, const int32_t* indices, const float* maps4 /* k*R*R*4 */, float back_fraction,
+                     uint32_t* states /* n */);                                                                                  /* host, blocking */
+int pt_grid_update_device(const pt_grid_desc* desc, int k, const void* d_indices, const void* d_coeff_sums /* k*9 float4 */,
+                          const void* d_maps /* k*R*R float4; NULL iff map_res == 0 */, float hysteresis,
+                          void* d_packed /* read and written in place */, void* stream);                                         /* async */
+int pt_grid_update(const pt_grid_desc* desc, int k, const int32_t* indices, const float* coeff_sums /* k*9*4 */,
+                   const float* maps4 /* k*R*R*4, NULL iff map_res == 0 */, float hysteresis, void* packed);                      /* host, blocking */
+int pt_grid_irradiance_states_device(const pt_grid_desc* desc, const void* d_packed, const void* d_states /* n uint32 */,
+                                     int m, const void* d_records /* m pt_ray */, void* d_out /* m float4 */, void* stream);      /* async */
+int pt_grid_irradiance_states(const pt_grid_desc* desc, const void* packed, const uint32_t* states /* n */, int m, const pt_ray* records,
+                              float* out4 /* m*4 */);                                                                            /* host, blocking */
+
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
  * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */
