@@ -257,6 +257,10 @@ def lib():
     L.pt_grid_update_device.argtypes = [C.POINTER(GridDesc), i32, vp, vp, vp, f32, vp, vp]
     L.pt_grid_irradiance_states.argtypes = [C.POINTER(GridDesc), vp, vp, i32, vp, vp]
     L.pt_grid_irradiance_states_device.argtypes = [C.POINTER(GridDesc), vp, vp, i32, vp, vp, vp]
+    L.pt_grid_relocate.argtypes = [C.POINTER(GridDesc), i32, vp, vp, f32, f32, vp, vp]
+    L.pt_grid_relocate_device.argtypes = [C.POINTER(GridDesc), i32, vp, vp, f32, f32, vp, vp, vp]
+    L.pt_grid_irradiance_offsets.argtypes = [C.POINTER(GridDesc), vp, vp, vp, i32, vp, vp]
+    L.pt_grid_irradiance_offsets_device.argtypes = [C.POINTER(GridDesc), vp, vp, vp, i32, vp, vp, vp]
     L.pt_query_guides.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32]
     L.pt_query_guides_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.c_uint32, vp]
     L.pt_debug_update_ms.argtypes = [vp, vp]
@@ -2284,30 +2288,85 @@ def grid_update(packed, desc, coeff_sums, maps=None, hysteresis=0.0, indices=Non
     return packed
 
 
-def grid_irradiance(packed, desc, records, states=None):
+def grid_relocate_defaults(desc, min_dist=None, max_offset=None):
+    """(min_dist, max_offset) as grid_relocate uses them: what is given, and for a None 0.2 of the smallest cell step and, per axis,
+    0.45 of its step (on an axis with one probe 0.45 of the smallest step of the others). A grid of one probe has no step: PtError
+    unless both are given."""
+    if min_dist is not None and max_offset is not None:
+        return min_dist, max_offset
+    steps = [(float(np.float32(desc.hi[a])) - float(np.float32(desc.lo[a]))) / (desc.counts[a] - 1) if desc.counts[a] > 1 else None for a in range(3)]
+    have = [v for v in steps if v is not None]
+    if not have:
+        raise PtError("grid_relocate: a grid of one probe has no cell: give min_dist and max_offset")
+    return (0.2 * min(have) if min_dist is None else min_dist,
+            [0.45 * (v if v is not None else min(have)) for v in steps] if max_offset is None else max_offset)
+
+
+def grid_relocate(desc, maps, offsets=None, back_fraction=0.25, min_dist=None, max_offset=None, indices=None):
+    """pt_grid_relocate: an offset per probe from Scene.query_distance's maps [k, R, R, 4] of the probes `indices` [k] (None: all n, in
+    the grid's order). A probe that grid_classify's rule finds inside moves out through its nearest back face by the face's distance
+    plus min_dist / 2; a probe nearer than min_dist to a front face steps back to min_dist; every offset is clamped to +-max_offset
+    (three numbers, or one for all axes). Writes the listed probes' rows of `offsets` [n, 4] float32 (zeros when None: dx, dy, dz and
+    what was done, 0 kept, 1 pushed out, 2 pushed off) and returns it. numpy in, numpy out (host form, `offsets` written where it
+    lies); tensors on the current HIP device in, a tensor out, on torch's current stream. The defaults are grid_relocate_defaults'."""
+    like = maps if _is_tensor(maps) else None
+    n, r = desc.counts[0] * desc.counts[1] * desc.counts[2], desc.map_res
+    min_dist, max_offset = grid_relocate_defaults(desc, min_dist, max_offset)
+    mx = np.ascontiguousarray(np.broadcast_to(np.asarray(max_offset, np.float32).reshape(-1), (3,)))
+    k, idx = _grid_list("grid_relocate", desc, indices, like)
+    mp = _grid_input("grid_relocate", "maps", maps, k * r * r * 4, like)
+    if like is not None:
+        import torch
+        if offsets is None:
+            offsets = torch.zeros((n, 4), dtype=torch.float32, device=mp.device)
+        off = _grid_input("grid_relocate", "offsets", offsets, n * 4, like)
+        _check(lib().pt_grid_relocate_device(C.byref(desc), k, _ptr(idx), _ptr(mp), back_fraction, min_dist, _p(mx), _ptr(off),
+                                             torch.cuda.current_stream(mp.device).cuda_stream or None), "pt_grid_relocate_device")
+    else:
+        if offsets is None:
+            offsets = np.zeros((n, 4), np.float32)
+        if not (isinstance(offsets, np.ndarray) and offsets.dtype == np.float32 and offsets.flags.c_contiguous and offsets.flags.writeable):
+            raise PtError("grid_relocate: offsets must be a writable C-contiguous float32 array: it is updated in place")
+        off = _grid_input("grid_relocate", "offsets", offsets, n * 4)
+        _check(lib().pt_grid_relocate(C.byref(desc), k, _ptr(idx), _ptr(mp), back_fraction, min_dist, _p(mx), _ptr(off)), "pt_grid_relocate")
+    return offsets
+
+
+def grid_irradiance(packed, desc, records, states=None, offsets=None):
     """pt_grid_irradiance: the irradiance at surface points from a packed probe grid. records is [m, 8] float32 (point, a word that
     is not read, unit normal, a word that is not read: rays.irradiance_records, rays.records_from_surfaces); packed is grid_pack's
     buffer of the same desc. Returns [m, 4] float32: (E_r, E_g, E_b, W) in rays.grid_irradiance's units, W the weight sum E was
     divided by; exact zeros for a record whose point or normal is not finite. numpy in, numpy out (host form); tensors on the
     current HIP device in, a tensor out, on torch's current stream with no host copy. With `states` [n] (grid_classify's)
-    pt_grid_irradiance_states: the probes whose PROBE_INSIDE bit is set are left out."""
+    pt_grid_irradiance_states: the probes whose PROBE_INSIDE bit is set are left out. With `offsets` [n, 4] (grid_relocate's)
+    pt_grid_irradiance_offsets: probe j stands at its grid position + offsets[j, :3]; with states or without."""
     is_torch, r, m = Scene._query_rays("grid_irradiance", records)
-    p = _grid_input("grid_irradiance", "packed", packed, grid_packed_bytes(desc) // 4, r if is_torch else None)
+    like = r if is_torch else None
+    p = _grid_input("grid_irradiance", "packed", packed, grid_packed_bytes(desc) // 4, like)
+    n = desc.counts[0] * desc.counts[1] * desc.counts[2]
     st = None
     if states is not None:
-        st = _grid_words("grid_irradiance", "states", states, desc.counts[0] * desc.counts[1] * desc.counts[2], r if is_torch else None)
+        st = _grid_words("grid_irradiance", "states", states, n, like)
+    off = None
+    if offsets is not None:
+        off = _grid_input("grid_irradiance", "offsets", offsets, n * 4, like)
     if is_torch:
         import torch
         out = torch.empty((m, 4), dtype=torch.float32, device=r.device)
         stream = torch.cuda.current_stream(r.device).cuda_stream or None
-        if m and st is None:
+        if m and off is not None:
+            _check(lib().pt_grid_irradiance_offsets_device(C.byref(desc), p.data_ptr(), _ptr(st), off.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream),
+                   "pt_grid_irradiance_offsets_device")
+        elif m and st is None:
             _check(lib().pt_grid_irradiance_device(C.byref(desc), p.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream), "pt_grid_irradiance_device")
         elif m:
             _check(lib().pt_grid_irradiance_states_device(C.byref(desc), p.data_ptr(), st.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream),
                    "pt_grid_irradiance_states_device")
     else:
         out = np.zeros((m, 4), np.float32)
-        if st is None:
+        if off is not None:
+            _check(lib().pt_grid_irradiance_offsets(C.byref(desc), _p(p), _ptr(st), _p(off), m, _p(r), _p(out)), "pt_grid_irradiance_offsets")
+        elif st is None:
             _check(lib().pt_grid_irradiance(C.byref(desc), _p(p), m, _p(r), _p(out)), "pt_grid_irradiance")
         else:
             _check(lib().pt_grid_irradiance_states(C.byref(desc), _p(p), _p(st), m, _p(r), _p(out)), "pt_grid_irradiance_states")
@@ -2329,8 +2388,9 @@ class ProbeGrid:
         self.res, self.device = int(res), bool(device)
         cell = [(b - a) / (c - 1) for a, b, c in zip(self.lo, self.hi, self.counts) if c > 1]
         self.max_t = float(max_t) if max_t is not None else 1.5 * float(np.sqrt(sum(v * v for v in cell)))
-        self.desc = self.sums = self.maps = self.packed = self.states = None
+        self.desc = self.sums = self.maps = self.packed = self.states = self.offsets = None
         self.back_fraction = 0.25
+        self.relocate_rounds = 0
 
     def _where(self):
         if not self.device:
@@ -2349,7 +2409,7 @@ class ProbeGrid:
                                                   flags=map_flags)
         self.desc = grid_desc(self.lo, self.hi, self.counts, lanes * spp_lane, self.res, map_spp, power)
         self.packed = grid_pack(self.desc, self.sums, self.maps)
-        self.states = None
+        self.states = self.offsets = None
         return self
 
     def classify(self, back_fraction=0.25):
@@ -2369,7 +2429,9 @@ class ProbeGrid:
         in place: new = fresh + hysteresis * (old - fresh). The queries run as bake()'s with QUERY_STREAM_PAD, each record's pad word
         its probe number, so a listed probe gets the streams a full bake with these arguments gives it. With skip_idle the probes that
         classify() found PROBE_IDLE are dropped from the list. The fresh rows replace the listed probes' rows of .sums and .maps, and
-        where states are kept the listed probes are classified again from their fresh maps. Returns self."""
+        where states are kept the listed probes are classified again from their fresh maps. Where offsets are kept (relocate()) the
+        records are built at grid position + offset (rays.sh_grid builds them on the host: a device grid's offsets are copied to the
+        host for it, once per query). Returns self."""
         from . import rays
         if self.packed is None:
             raise PtError("ProbeGrid: bake() has not run")
@@ -2386,7 +2448,7 @@ class ProbeGrid:
         where = self._where()
 
         def records(max_t):
-            rec = rays.sh_grid(self.lo, self.hi, self.counts, max_t, where)
+            rec = rays.sh_grid(self.lo, self.hi, self.counts, max_t, where, offsets=self.offsets)
             if where is None:
                 rec = np.ascontiguousarray(rec[idx])
                 rec.view(np.int32)[:, 7] = idx
@@ -2415,11 +2477,40 @@ class ProbeGrid:
                 grid_classify(desc, maps, self.back_fraction, lst, self.states)
         return self
 
-    def lookup(self, records):
-        """grid_irradiance on the baked grid: [m, 4] (E_r, E_g, E_b, W) for [m, 8] records; with the states classify() keeps."""
+    def relocate(self, lanes, spp_lane, max_depth, map_spp=1, min_dist=None, max_offset=None, iterations=4, seed=SEED, integrator=UNIDIRECTIONAL,
+                 use_mis=True, map_flags=0):
+        """Moves the probes out of the way, at most `iterations` rounds: grid_relocate on the kept maps (back_fraction is classify()'s),
+        then the probes whose offset changed are re-baked at grid position + offset through update(hysteresis=0, probes=moved) with
+        these sample counts, which also classifies them again where states are kept; a round in which nothing moved ends the loop.
+        Keeps the offsets in .offsets ([n, 4]), which lookup(), irradiance(), shade() and update() read from then on, and the number of
+        rounds that ran grid_relocate in .relocate_rounds; bake() forgets the offsets. The defaults of min_dist and max_offset are
+        grid_relocate_defaults'. Returns self."""
         if self.packed is None:
             raise PtError("ProbeGrid: bake() has not run")
-        return grid_irradiance(self.packed, self.desc, records, self.states)
+        if not self.res:
+            raise PtError("ProbeGrid: a grid without maps (res = 0) has nothing to relocate by")
+        if int(map_spp) != self.desc.map_samples:
+            raise PtError("ProbeGrid.relocate: map_spp %d is not the kept maps' %d: their means would mix" % (map_spp, self.desc.map_samples))
+        min_dist, max_offset = grid_relocate_defaults(self.desc, min_dist, max_offset)
+        self.relocate_rounds = 0
+        for _ in range(int(iterations)):
+            before = None if self.offsets is None else (self.offsets.clone() if _is_tensor(self.offsets) else self.offsets.copy())
+            self.offsets = grid_relocate(self.desc, self.maps, self.offsets, self.back_fraction, min_dist, max_offset)
+            self.relocate_rounds += 1
+            now = self.offsets[:, :3]
+            changed = (now != (before[:, :3] if before is not None else 0 * now)).any(1)
+            moved = (changed.nonzero().reshape(-1).cpu().numpy() if _is_tensor(changed) else np.flatnonzero(changed)).astype(np.int32)
+            if not len(moved):
+                break
+            self.update(lanes, spp_lane, max_depth, map_spp, 0.0, moved, seed, False, integrator, use_mis, map_flags)
+        return self
+
+    def lookup(self, records):
+        """grid_irradiance on the baked grid: [m, 4] (E_r, E_g, E_b, W) for [m, 8] records; with the states classify() keeps and the
+        offsets relocate() keeps."""
+        if self.packed is None:
+            raise PtError("ProbeGrid: bake() has not run")
+        return grid_irradiance(self.packed, self.desc, records, self.states, self.offsets)
 
     def irradiance(self, points, normals):
         """The lookup at `points` [m, 3] with unit `normals` [m, 3]."""

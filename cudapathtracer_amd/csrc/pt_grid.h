@@ -1,6 +1,6 @@
-// pt_grid.h — what the two probe-grid units share (pt_grid.hip: pack and lookup; pt_grid_live.hip: probe states,
-// masked lookups and in-place updates, §30): the grid a desc names as the kernels read it, the desc's checks, the packed buffer's
-// layout, and the Chebyshev visibility of a point from a probe's bordered map.
+// pt_grid.h — what the probe-grid units share (pt_grid.hip: pack and lookup; pt_grid_live.hip: probe states,
+// masked lookups and in-place updates, §30; pt_grid_relocate.hip: probe offsets, §31): the grid a desc names as the kernels read
+// it, the desc's checks, the packed buffer's layout, and the Chebyshev visibility of a point from a probe's bordered map.
 #pragma once
 #include <cmath>
 
@@ -81,6 +81,13 @@ static inline int grid_params(const char* fn, const pt_grid_desc* d, GridParams&
     G.R = R; G.Rf = (float)R; G.power = d->power;
     G.scale = (float)(4.0 * 3.14159265358979323846 / (double)d->sh_samples);
     G.mapSamples = (float)d->map_samples;
+    return 0;
+}
+
+// The checks of a probe list (pt_grid_classify, pt_grid_update, pt_grid_relocate): k against n, NULL indices only for the identity.
+static inline int live_list_checks(const char* fn, const GridParams& G, int k, const void* indices) {
+    if (k > G.n) return postfx_fail_fn(-1, fn, "k %d lists more than the grid's %d probes", k, G.n);
+    if (!indices && k != G.n) return postfx_fail_fn(-1, fn, "null indices need k == %d, the grid's probes, not %d", G.n, k);
     return 0;
 }
 

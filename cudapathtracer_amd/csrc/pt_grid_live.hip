@@ -150,13 +150,6 @@ __global__ void __launch_bounds__(256) live_lookup_kernel(GridParams G, const fl
     out[i] = live_corners<MAPS>(G, coeff, texels, states, p, y, low, f);
 }
 
-// The probe list's checks, shared by classify and update: k against n, NULL indices only for the identity.
-static int live_list_checks(const char* fn, const GridParams& G, int k, const void* indices) {
-    if (k > G.n) return postfx_fail_fn(-1, fn, "k %d lists more than the grid's %d probes", k, G.n);
-    if (!indices && k != G.n) return postfx_fail_fn(-1, fn, "null indices need k == %d, the grid's probes, not %d", G.n, k);
-    return 0;
-}
-
 static int live_classify_launch(const GridParams& G, int k, const void* indices, const void* maps, float backFraction, void* states, hipStream_t stream) {
     hipLaunchKernelGGL(live_classify_kernel, dim3((unsigned)(((size_t)k + 3) / 4)), dim3(256), 0, stream, G.n, G.R, k, (const int*)indices,
                        (const float4*)maps, backFraction, (unsigned*)states);

@@ -94,12 +94,18 @@ def sh_records(points, max_t=QUERY_MAX_T, device=None):
     return _records(xp, kw, p, 0.0, len(p), max_t)
 
 
-def sh_grid(lo, hi, counts, max_t=QUERY_MAX_T, device=None):
+def sh_grid(lo, hi, counts, max_t=QUERY_MAX_T, device=None, offsets=None):
     """Records for Scene.query_sh on a regular grid of counts = (nx, ny, nz) probes from corner lo to corner hi, both included (a
-    count of 1 puts the probe at lo's coordinate): probe (ix, iy, iz) is record (iz * ny + iy) * nx + ix, x fastest."""
+    count of 1 puts the probe at lo's coordinate): probe (ix, iy, iz) is record (iz * ny + iy) * nx + ix, x fastest. With `offsets`
+    [n, >= 3] (api.grid_relocate's; numpy or a tensor) probe j stands at its float32 grid position plus offsets[j, :3] as float32,
+    added in float32."""
     ax = [np.linspace(float(a), float(b), int(c)) if int(c) > 1 else np.array([float(a)]) for a, b, c in zip(lo, hi, counts)]
     z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
-    return sh_records(np.stack([x.ravel(), y.ravel(), z.ravel()], 1).astype(np.float32), max_t, device)
+    p = np.stack([x.ravel(), y.ravel(), z.ravel()], 1).astype(np.float32)
+    if offsets is not None:
+        off = offsets if isinstance(offsets, np.ndarray) or not hasattr(offsets, "cpu") else offsets.cpu().numpy()
+        p = p + np.asarray(off, np.float32).reshape(len(p), -1)[:, :3]
+    return sh_records(p, max_t, device)
 
 
 SH_C = (0.2820948, 0.4886025, 1.0925484, 0.3153916, 0.5462742)      # the constants of include/pt_api.h, seven digits each
@@ -218,7 +224,7 @@ def distance_visibility(maps, samples, d, dist, power=3):
     return xp.where(dist <= mean, 1 + 0 * den, ratio ** power).reshape(lead)
 
 
-def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, maps=None, map_samples=None, power=3, states=None):
+def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, maps=None, map_samples=None, power=3, states=None, offsets=None):
     """Irradiance at `points` [m, 3] with unit `normals` [m, 3] from the probes of an sh_grid(lo, hi, counts): coeff_sums [n, 9, 4]
     are Scene.query_sh's sums of sh_samples samples a probe, maps [n, R, R, >= 2] (optional) Scene.query_distance's of map_samples
     samples a texel, both in the grid's order (x fastest). Per point the eight probes around it (clamped at the grid's faces) are
@@ -226,8 +232,9 @@ def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, map
     being probe j's sh_irradiance at the point's normal. Without maps, or where the weights sum to less than 1e-6, the plain
     trilinear mix. With `states` [n] (api.grid_classify's words; bit 0, api.PROBE_INSIDE, marks a dead probe) the dead corners are
     left out of every sum, and a point whose weights sum to less than 1e-6 (or a grid without maps) that lost a corner gets the plain
-    mix of its live corners divided by their trilinear weights' sum, zeros where that sum is 0. Returns [m, 3] in coeff_sums' dtype
-    (numpy or torch)."""
+    mix of its live corners divided by their trilinear weights' sum, zeros where that sum is 0. With `offsets` [n, >= 3]
+    (api.grid_relocate's) probe j stands at its grid position + offsets[j, :3] for the visibility test; the cell and the trilinear
+    weights stay the regular grid's. Returns [m, 3] in coeff_sums' dtype (numpy or torch)."""
     xp = _xp_of(coeff_sums)
     dt = coeff_sums.dtype
     conv = (lambda v: np.asarray(v, dt)) if xp is np else (lambda v: xp.as_tensor(v, dtype=dt, device=coeff_sums.device))
@@ -260,6 +267,8 @@ def grid_irradiance(lo, hi, counts, coeff_sums, sh_samples, points, normals, map
                 plain = plain + tri[:, None] * ej
                 if maps is not None:
                     at = xp.stack([pos[a][0] + pos[a][1] * (ix, iy, iz)[a] for a in range(3)], -1)      # the probe's position
+                    if offsets is not None:
+                        at = (at.astype(dt) if xp is np else at.to(dt)) + conv(offsets).reshape((len(e), -1))[j][:, :3]
                     v = p - (at.astype(dt) if xp is np else at.to(dt))
                     dist = xp.sqrt((v * v).sum(-1))
                     d = xp.where((dist > 0)[:, None], v, conv([0.0, 0.0, 1.0])[None, :] + 0 * v)

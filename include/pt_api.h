@@ -1656,6 +1656,56 @@ int pt_grid_irradiance_states_device(const pt_grid_desc* desc, const void* d_pac
 int pt_grid_irradiance_states(const pt_grid_desc* desc, const void* packed, const uint32_t* states /* n */, int m, const pt_ray* records,
                               float* out4 /* m*4 */);                                                                            /* host, blocking */
 
+/* pt_grid_relocate, pt_grid_irradiance_offsets: probes that move out of the way. Two scene-free calls beside the
+ * eight above, shaped as they are: an offset per probe from its distance map, so that a probe found inside an object moves out
+ * through the nearest back face instead of going dark and a probe just in front of a wall steps back from it; and the lookup that
+ * reads a probe's position as grid position + offset. Nothing above changes.
+ * Offsets. n float4, one per probe in the grid's order: (dx, dy, dz) the probe's displacement from its grid position in world units;
+ *   word 3 what the last relocation did to the probe, as a float: 0 kept, 1 pushed out through a back face, 2 pushed off a front
+ *   face. A lookup reads words 0 to 2 only. The caller bakes a moved probe at grid position + offset (rays.sh_grid(offsets=...)).
+ * The probe list (k, indices, maps) is pt_grid_classify's: row i is probe indices[i], NULL indices need k == n, an index outside
+ *   [0, n) is skipped. Only the listed probes' offsets are written. The indices must be distinct: a listed probe's offset is read
+ *   and then written, so for a probe named twice the result is unspecified (one row's move, or one applied after the other);
+ *   nothing outside that probe's entry is touched.
+ * ARITHMETIC as above: f32, every operation rounded once in the order written, nothing fused but the fmas named, / and sqrt IEEE, min
+ *   and max ignore a NaN operand (v_min_f32, v_max_f32).
+ *   Relocate. Per texel l = ty*R + tx of a listed probe's map, (A, ., H, K) = maps[i*R*R + l]:  m = A / (float)map_samples, the
+ *     pack's mean bit for bit;  back = (K + K > H);  front = (H > 0) && !back;  the texel is a candidate only if m >= 0 is true (a
+ *     NaN or a negative mean is none).  Hs = sum of H, Ks = sum of K, inside = Ks > back_fraction * Hs: pt_grid_classify's bits.
+ *     The chosen texel: among the candidates with `back` if inside, else among those with `front`, the one with the smallest m by
+ *     f32 comparison (+0 and -0 are equal), ties to the smaller l. The key (m, l) is total, so the order of the reduction is free.
+ *     c = the direction of the chosen texel's centre: pt_query_distance's DIRECTION ARITHMETIC with u1 = u2 = 0.5, operation for
+ *     operation. With old = the offset read:
+ *       inside and a texel was chosen:                     t = m + 0.5f*min_dist;  new_a = fma(c_a, t, old_a);   code 1
+ *       not inside, a texel was chosen and m < min_dist:   t = min_dist - m;       new_a = fma(-c_a, t, old_a);  code 2
+ *       otherwise:                                         new = old;                                            code 0
+ *     then in every case new_a = min(max(new_a, -max_offset_a), max_offset_a): a written offset lies in the box whatever was read,
+ *     a NaN included. The sign of a zero that the clamp produces is not part of the contract. max_offset should stay under half a
+ *     cell, since the lookup's cell and trilinear weights stay the regular grid's.
+ *   Lookup with offsets. pt_grid_irradiance_states' lookup with one change in step 5: the probe stands at
+ *     at_a = fma((float)i_a, step_a, lo_a) + off_a, one rounded add per axis. The cell, tri and the corner order are unchanged.
+ *     states == NULL means that no probe is dead: no state word is read and the end is pt_grid_irradiance's step 6 (plain_c and W).
+ *     With every offset +0 or -0 the output is pt_grid_irradiance's (states NULL) and pt_grid_irradiance_states' (states given) bit
+ *     for bit: fma(i, step, lo) with i >= 0 and step >= 0 is never -0 (the product is +0 or positive, and a sum that cancels rounds
+ *     to +0), and x + (+-0) = x for every x but -0.
+ * Checked before any HIP call, -1 with a message under the function's name, in this order: the desc as above; map_res == 0 (a grid
+ *   without maps has no positions to read); k (or m) < 0 (0 then returns 0); pt_grid_relocate: k > n, or NULL indices with k != n;
+ *   back_fraction not in [0, 1]; min_dist not finite or < 0; a max_offset component not finite or < 0; a NULL buffer (max_offset
+ *   among them; states may be NULL in the lookup only); in the device forms a written buffer overlapping a read one.
+ * max_offset is three floats in host memory in both forms. d_offsets (n float4) is a device buffer aligned to 16 bytes, read and
+ * written by pt_grid_relocate_device; the other buffers are as above; the device forms are asynchronous on `stream`. */
+int pt_grid_relocate_device(const pt_grid_desc* desc, int k, const void* d_indices /* k int32, or NULL: k == n, probe i */,
+                            const void* d_maps /* k*R*R float4, pt_query_distance's */, float back_fraction, float min_dist,
+                            const float* max_offset /* 3, host */, void* d_offsets /* n float4, entry indices[i] read and written */,
+                            void* stream);                                                                                       /* async */
+int pt_grid_relocate(const pt_grid_desc* desc, int k, const int32_t* indices, const float* maps4 /* k*R*R*4 */, float back_fraction,
+                     float min_dist, const float* max_offset /* 3 */, float* offsets4 /* n*4, read and written */);             /* host, blocking */
+int pt_grid_irradiance_offsets_device(const pt_grid_desc* desc, const void* d_packed, const void* d_states /* n uint32, or NULL */,
+                                      const void* d_offsets /* n float4 */, int m, const void* d_records /* m pt_ray */,
+                                      void* d_out /* m float4 */, void* stream);                                                 /* async */
+int pt_grid_irradiance_offsets(const pt_grid_desc* desc, const void* packed, const uint32_t* states /* n, or NULL */,
+                               const float* offsets4 /* n*4 */, int m, const pt_ray* records, float* out4 /* m*4 */);            /* host, blocking */
+
 /* For tools (tools/update_time.py): host wall clock, in ms, of parts of the scene's last build. out3[0]: the renumbering of the
  * internal nodes by area through the host, in the last successful update or, before any, at creation (0 for a scene of at most
  * 128 internal nodes, which is not renumbered); out3[1]: the whole last successful update (0 before any); out3[2]: 0. */
