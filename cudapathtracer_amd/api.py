@@ -2350,26 +2350,22 @@ def grid_irradiance(packed, desc, records, states=None, offsets=None):
     off = None
     if offsets is not None:
         off = _grid_input("grid_irradiance", "offsets", offsets, n * 4, like)
+    # the entry point and the arrays it takes after the packed buffer: offsets go with states or without
+    if off is not None:
+        name, extra = "pt_grid_irradiance_offsets", (st, off)
+    elif st is not None:
+        name, extra = "pt_grid_irradiance_states", (st,)
+    else:
+        name, extra = "pt_grid_irradiance", ()
     if is_torch:
         import torch
         out = torch.empty((m, 4), dtype=torch.float32, device=r.device)
-        stream = torch.cuda.current_stream(r.device).cuda_stream or None
-        if m and off is not None:
-            _check(lib().pt_grid_irradiance_offsets_device(C.byref(desc), p.data_ptr(), _ptr(st), off.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream),
-                   "pt_grid_irradiance_offsets_device")
-        elif m and st is None:
-            _check(lib().pt_grid_irradiance_device(C.byref(desc), p.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream), "pt_grid_irradiance_device")
-        elif m:
-            _check(lib().pt_grid_irradiance_states_device(C.byref(desc), p.data_ptr(), st.data_ptr(), m, r.data_ptr(), out.data_ptr(), stream),
-                   "pt_grid_irradiance_states_device")
+        if m:
+            _check(getattr(lib(), name + "_device")(C.byref(desc), _ptr(p), *map(_ptr, extra), m, _ptr(r), _ptr(out),
+                                                    torch.cuda.current_stream(r.device).cuda_stream or None), name + "_device")
     else:
         out = np.zeros((m, 4), np.float32)
-        if off is not None:
-            _check(lib().pt_grid_irradiance_offsets(C.byref(desc), _p(p), _ptr(st), _p(off), m, _p(r), _p(out)), "pt_grid_irradiance_offsets")
-        elif st is None:
-            _check(lib().pt_grid_irradiance(C.byref(desc), _p(p), m, _p(r), _p(out)), "pt_grid_irradiance")
-        else:
-            _check(lib().pt_grid_irradiance_states(C.byref(desc), _p(p), _p(st), m, _p(r), _p(out)), "pt_grid_irradiance_states")
+        _check(getattr(lib(), name)(C.byref(desc), _ptr(p), *map(_ptr, extra), m, _ptr(r), _ptr(out)), name)
     return out
 
 

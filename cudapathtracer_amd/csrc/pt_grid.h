@@ -1,6 +1,7 @@
-// pt_grid.h — what the probe-grid units share (pt_grid.hip: pack and lookup; pt_grid_live.hip: probe states,
-// masked lookups and in-place updates, §30; pt_grid_relocate.hip: probe offsets, §31): the grid a desc names as the kernels read
-// it, the desc's checks, the packed buffer's layout, and the Chebyshev visibility of a point from a probe's bordered map.
+// pt_grid.h — what the probe-grid units share (pt_grid.hip: pack and every lookup; pt_grid_live.hip: probe states
+// and in-place updates, §30; pt_grid_relocate.hip: probe offsets, §31): the grid a desc names as the kernels read it, the desc's
+// checks, the packed buffer's layout, the words pack and update both write (a gutter texel's source, a coefficient row), and the
+// Chebyshev visibility of a point from a probe's bordered map.
 #pragma once
 #include <cmath>
 
@@ -50,6 +51,21 @@ PT_DEV float grid_visibility(const GridParams& G, const float2* __restrict__ map
     float vis = ratio;
     for (int k = 1; k < G.power; k++) vis = vis * ratio;
     return dist <= mean ? 1.0f : vis;
+}
+
+// The interior texel (sx, sy) that texel l of a probe's bordered (R + 2)^2 map copies: itself off the gutter, rays.oct_border's rule on it.
+PT_DEV int2 grid_border_source(int R, int l) {
+    const int B = R + 2;
+    int sx = l % B - 1, sy = l / B - 1;
+    if (sx < 0) { sx = -1 - sx; sy = R - 1 - sy; } else if (sx > R - 1) { sx = 2 * R - 1 - sx; sy = R - 1 - sy; }
+    if (sy < 0) { sy = -1 - sy; sx = R - 1 - sx; } else if (sy > R - 1) { sy = 2 * R - 1 - sy; sx = R - 1 - sx; }
+    return make_int2(sx, sy);
+}
+
+// The packed word of coefficient row k (0..8) from its query sums c: scaled, then convolved with the cosine lobe of the row's band.
+PT_DEV float4 grid_fresh_row(const GridParams& G, int k, float4 c) {
+    const float lobe = k == 0 ? 3.14159265358979323846f : (k < 4 ? 2.09439510239319549231f : 0.78539816339744830962f);
+    return make_float4((c.x * G.scale) * lobe, (c.y * G.scale) * lobe, (c.z * G.scale) * lobe, 0.0f);
 }
 
 // The desc's checks in the header's order; on success G holds what the kernels read.

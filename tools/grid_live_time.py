@@ -1,7 +1,7 @@
 """What keeping a probe grid live costs, in one run.
 
     python tools/grid_live_time.py [--scene cornell|mixed|blob --w 1920 --h 1080 --reps 5 --warmup 1]
-    python tools/grid_live_time.py --resources    (no device needed: compiles pt_grid_live.hip and prints its kernels' registers, scratch and LDS)
+    python tools/grid_live_time.py --resources    (no device needed: compiles pt_grid_live.hip and pt_grid.hip and prints the kernels' registers, scratch and LDS)
 
 tools/grid_time.py's method: HIP events around each call, the median of --reps after --warmup, the grids baked at few samples (64
 lanes x 1 a probe, 8 a texel). On the w x h surface points of cam0's centre rays, for an 8^3 and a 16^3 grid with R = 0 and R = 8:
@@ -15,7 +15,6 @@ With --no-leak the leak table is left out. Prints one JSON line."""
 import argparse
 import json
 import os
-import re
 import sys
 import tempfile
 
@@ -26,13 +25,12 @@ MAP_SPP = 8
 
 
 def live_kernel_resources():
-    """kernel_resources.kernel_resources of pt_grid_live.hip's four kernels under the names live_classify, live_update,
-    live_lookup_maps and live_lookup_plain."""
+    """kernel_resources.kernel_resources of pt_grid_live.hip's two kernels and of the states lookup's two instantiations
+    (pt_grid.hip's grid_lookup_kernel<MAPS, 1, 0>) under the names live_classify, live_update, live_lookup_maps and live_lookup_plain."""
+    from grid_time import lookup_kernel_resources
     from kernel_resources import kernel_resources
-    out = {}
-    for name, r in kernel_resources("pt_grid_live", r"(live_\w+?_kernel)").items():
-        t = re.search(r"live_lookup_kernelILb(\d)E", name)
-        out[name[:-len("_kernel")] if not t else ("live_lookup_maps" if t.group(1) == "1" else "live_lookup_plain")] = r
+    out = {name[:-len("_kernel")]: r for name, r in kernel_resources("pt_grid_live", r"(live_\w+?_kernel)").items()}
+    out.update(lookup_kernel_resources({"110": "live_lookup_maps", "010": "live_lookup_plain"}, {}))
     return out
 
 

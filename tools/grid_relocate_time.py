@@ -1,13 +1,14 @@
 """What probe relocation costs and what it changes, in one run.
 
     python tools/grid_relocate_time.py [--scene cornell|mixed|blob --w 1920 --h 1080 --reps 5 --warmup 1 --parent-lib PATH]
-    python tools/grid_relocate_time.py --resources    (no device needed: compiles pt_grid_relocate.hip and prints its kernels' registers, scratch and LDS)
+    python tools/grid_relocate_time.py --resources    (no device needed: compiles pt_grid_relocate.hip and pt_grid.hip and prints the kernels' registers, scratch and LDS)
 
 tools/grid_live_time.py's method: HIP events around each call, the median of --reps after --warmup, the grids baked at few samples (64
 lanes x 1 a probe, 8 a texel). On the w x h surface points of cam0's centre rays, for an 8^3 and a 16^3 grid with R = 8:
   lookup    pt_grid_irradiance_offsets_device with the scene's states and zero offsets next to pt_grid_irradiance_states_device on
-            the same inputs in the same run (with --parent-lib also that call of another build of the library, the parent commit's),
-            and without states next to pt_grid_irradiance_device, the device forms called as they are into one output buffer;
+            the same inputs in the same run, and without states next to pt_grid_irradiance_device, the device forms called as they
+            are into one output buffer; with --parent-lib each of the four next to the same call into another build of the library
+            (the parent commit's: parent_<form>_ms), the two builds alternating, and <form>_over_parent;
             then the lookup with the relocated grid's offsets and states, next to the states lookup with those states
   relocate  pt_grid_relocate_device of all n probes next to pt_grid_classify_device
   rounds    api.ProbeGrid.relocate round by round (wall clock with a device synchronisation: a round is queries, an update and a
@@ -18,7 +19,6 @@ import argparse
 import ctypes as C
 import json
 import os
-import re
 import sys
 import tempfile
 import time
@@ -31,13 +31,12 @@ ROUNDS = 4
 
 
 def relocate_kernel_resources():
-    """kernel_resources.kernel_resources of pt_grid_relocate.hip's three kernels under the names reloc, reloc_lookup_states and
-    reloc_lookup_none."""
+    """kernel_resources.kernel_resources of pt_grid_relocate.hip's kernel and of the offsets lookup's two instantiations
+    (pt_grid.hip's grid_lookup_kernel<1, STATES, 1>) under the names reloc, reloc_lookup_states and reloc_lookup_none."""
+    from grid_time import lookup_kernel_resources
     from kernel_resources import kernel_resources
-    out = {}
-    for name, r in kernel_resources("pt_grid_relocate", r"(reloc\w*?_kernel)").items():
-        t = re.search(r"reloc_lookup_kernelILb(\d)E", name)
-        out[name[:-len("_kernel")] if not t else ("reloc_lookup_states" if t.group(1) == "1" else "reloc_lookup_none")] = r
+    out = {name[:-len("_kernel")]: r for name, r in kernel_resources("pt_grid_relocate", r"(reloc\w*?_kernel)").items()}
+    out.update(lookup_kernel_resources({"111": "reloc_lookup_states", "101": "reloc_lookup_none"}, {}))
     return out
 
 
@@ -74,7 +73,7 @@ def main():
     ap.add_argument("--scene", choices=("cornell", "mixed", "blob"), default="cornell")
     ap.add_argument("--resources", action="store_true")
     ap.add_argument("--no-leak", action="store_true", help="time the library's calls only: no leak table")
-    ap.add_argument("--parent-lib", help="another build of libptamd.so whose pt_grid_irradiance_states_device is timed in the same run")
+    ap.add_argument("--parent-lib", help="another build of libptamd.so whose four lookup forms are timed in the same run")
     a = ap.parse_args()
     if a.resources:
         print(json.dumps({"resources": relocate_kernel_resources()}))
@@ -97,7 +96,8 @@ def main():
     parent = None
     if a.parent_lib:
         parent = C.CDLL(os.path.abspath(a.parent_lib))
-        parent.pt_grid_irradiance_states_device.argtypes = [C.POINTER(api.GridDesc), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        for fn in ("pt_grid_irradiance_device", "pt_grid_irradiance_states_device", "pt_grid_irradiance_offsets_device"):
+            getattr(parent, fn).argtypes = getattr(api.lib(), fn).argtypes
 
     def events(run):
         ms = []
@@ -129,12 +129,12 @@ def main():
         out = torch.empty((w * h, 4), dtype=torch.float32, device=recs.device)
         L, dref, m = api.lib(), C.byref(g.desc), w * h
         ptr = lambda t: t.data_ptr()
-        names = {"plain_ms": lambda: L.pt_grid_irradiance_device(dref, ptr(g.packed), m, ptr(recs), ptr(out), None),
-                 "states_ms": lambda: L.pt_grid_irradiance_states_device(dref, ptr(g.packed), ptr(st0), m, ptr(recs), ptr(out), None),
-                 "offsets_zero_ms": lambda: L.pt_grid_irradiance_offsets_device(dref, ptr(g.packed), ptr(st0), ptr(zero), m, ptr(recs), ptr(out), None),
-                 "offsets_zero_no_states_ms": lambda: L.pt_grid_irradiance_offsets_device(dref, ptr(g.packed), None, ptr(zero), m, ptr(recs), ptr(out), None)}
-        if parent is not None:
-            names["parent_states_ms"] = lambda: parent.pt_grid_irradiance_states_device(dref, ptr(g.packed), ptr(st0), m, ptr(recs), ptr(out), None)
+        forms = {"plain": lambda B: B.pt_grid_irradiance_device(dref, ptr(g.packed), m, ptr(recs), ptr(out), None),
+                 "states": lambda B: B.pt_grid_irradiance_states_device(dref, ptr(g.packed), ptr(st0), m, ptr(recs), ptr(out), None),
+                 "offsets_zero": lambda B: B.pt_grid_irradiance_offsets_device(dref, ptr(g.packed), ptr(st0), ptr(zero), m, ptr(recs), ptr(out), None),
+                 "offsets_zero_no_states": lambda B: B.pt_grid_irradiance_offsets_device(dref, ptr(g.packed), None, ptr(zero), m, ptr(recs), ptr(out), None)}
+        builds = {"": L} if parent is None else {"": L, "parent_": parent}
+        names = {pre + k + "_ms": (lambda run=run, B=B: run(B)) for k, run in forms.items() for pre, B in builds.items()}
         took = {k: [] for k in names}
         for _ in range(3):
             for k, run in names.items():
@@ -145,9 +145,11 @@ def main():
         assert torch.equal(api.grid_irradiance(g.packed, g.desc, recs, st0, zero), api.grid_irradiance(g.packed, g.desc, recs, st0))
         assert torch.equal(api.grid_irradiance(g.packed, g.desc, recs, None, zero), api.grid_irradiance(g.packed, g.desc, recs))
         if parent is not None:
-            names["parent_states_ms"]()
-            torch.cuda.synchronize()
-            assert torch.equal(out, api.grid_irradiance(g.packed, g.desc, recs, st0))
+            for k, (st, off) in {"plain": (None, None), "states": (st0, None), "offsets_zero": (st0, zero), "offsets_zero_no_states": (None, zero)}.items():
+                row[k + "_over_parent"] = round(row[k + "_ms"] / row["parent_" + k + "_ms"], 3)
+                names["parent_" + k + "_ms"]()
+                torch.cuda.synchronize()
+                assert torch.equal(out, api.grid_irradiance(g.packed, g.desc, recs, st, off)), k
         row["classify_ms"] = events(lambda: api.grid_classify(g.desc, g.maps))
         scratch = torch.zeros((n, 4), dtype=torch.float32, device=recs.device)
         row["relocate_ms"] = events(lambda: api.grid_relocate(g.desc, g.maps, scratch.zero_()))

@@ -31,13 +31,22 @@ MAP_SPP = 8                          # samples a texel of the timed grids' maps:
 
 
 def grid_kernel_resources():
-    """kernel_resources.kernel_resources of pt_grid.hip's three kernels under the names grid_pack, grid_irradiance_maps and
-    grid_irradiance_plain."""
+    """kernel_resources.kernel_resources of pt_grid.hip's pack kernel and of the plain lookup's two instantiations
+    (grid_lookup_kernel<MAPS, 0, 0>) under the names grid_pack, grid_irradiance_maps and grid_irradiance_plain."""
+    return lookup_kernel_resources({"100": "grid_irradiance_maps", "000": "grid_irradiance_plain"}, {"grid_pack_kernel": "grid_pack"})
+
+
+def lookup_kernel_resources(forms, others):
+    """kernel_resources.kernel_resources of pt_grid.hip's kernels under the names asked for: `forms` names instantiations of
+    grid_lookup_kernel<MAPS, STATES, OFFSETS> by their three template arguments as digits, `others` the kernels that are no
+    templates."""
     from kernel_resources import kernel_resources
     out = {}
     for name, r in kernel_resources("pt_grid", r"(grid_\w+?_kernel)").items():
-        t = re.search(r"grid_irradiance_kernelILb(\d)E", name)
-        out["grid_pack" if not t else ("grid_irradiance_maps" if t.group(1) == "1" else "grid_irradiance_plain")] = r
+        t = re.search(r"grid_lookup_kernelILb(\d)ELb(\d)ELb(\d)E", name)
+        key = forms.get("".join(t.groups())) if t else others.get(name)
+        if key:
+            out[key] = r
     return out
 
 
